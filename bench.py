@@ -5,6 +5,8 @@ One "step" = one full pass of the hot path (pooled mean/std, q5/q50/q95, rank-no
 R-hat, ESS bulk, ESS tail, truncation lags) over one synthetic model resident in HBM.
 
   python bench.py                                   # N=1, BASELINE config 1 (4 x 10000 x 100 f64)
+  python bench.py --steps K --dump-outputs DIR      # one timed window of exactly K steps; the last step's summary
+                                                    # arrays as DIR/<name>.npy (float64, seeded inputs)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W      # one rank per GPU, weak scaling
 
@@ -87,10 +89,10 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--windows", type=int, default=0,
-                    help="number of K-step timed windows (ms_per_step is the MEDIAN window); 0 = repeat until they cover "
-                         "0.3 s of timed work, at least 5 and at most 64 (a 5 ms region is fragile: clock ramp-up, fill "
-                         "and drain of the rolling window)")
+    ap.add_argument("--windows", type=int, default=1,
+                    help="number of K-step timed windows (ms_per_step is the MEDIAN window); the default, 1, times exactly "
+                         "--steps steps; 0 = repeat until they cover 0.3 s of timed work, at least 5 and at most 64 (a 5 ms "
+                         "region is fragile: clock ramp-up, fill and drain of the rolling window)")
     ap.add_argument("--workload", choices=["c1", "c1split", "corpus", "stress"], default="c1")
     ap.add_argument("--chains", type=int, default=4)
     ap.add_argument("--draws", type=int, default=10000)
@@ -106,7 +108,35 @@ def parse_args():
     ap.add_argument("--no-probe", action="store_true", help="skip the measured-HBM-peak probe")
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the other single-GPU configurations of the default line (configs / d_sweep / call latencies)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the summary the last timed step returned as DIR/<name>.npy (float64)")
     return ap.parse_args()
+
+
+DUMP_MAX_BYTES = 64_000_000       # all files together, .npy headers included
+
+
+def dump_outputs(a, got: dict, rank: int) -> None:
+    """--dump-outputs: every array of the summary a caller of the timed path receives, as float64 .npy files (other
+    ranks than 0 add `.rank<r>` to the name).  Per-parameter arrays larger than DUMP_MAX_BYTES in all are cut to a fixed
+    sample of parameters (seed 0, ascending), whose indices go to `param_index.npy`."""
+    if a.dump_outputs is None:
+        return
+    out = Path(a.dump_outputs)
+    out.mkdir(parents=True, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in got.items()}
+    P = len(arrays["mean"])
+    per_param = [k for k in arrays if k != "q_lo"]
+    row_bytes = sum(arrays[k][:1].nbytes for k in per_param)
+    budget = DUMP_MAX_BYTES - 256 * (len(arrays) + 1) - arrays["q_lo"].nbytes
+    if P * row_bytes > budget:
+        keep = np.sort(np.random.default_rng(0).choice(P, budget // (row_bytes + 8), replace=False))
+        for k in per_param:
+            arrays[k] = arrays[k][keep]
+        arrays["param_index"] = keep.astype(np.float64)
+    suffix = f".rank{rank}" if rank else ""
+    for k, v in arrays.items():
+        np.save(out / f"{k}{suffix}.npy", v)
 
 
 def validate(got: dict, exp: dict) -> tuple[bool, float]:
@@ -163,10 +193,10 @@ MIN_WINDOWS, MAX_WINDOWS, MIN_TIMED_SECONDS = 5, 64, 0.3
 
 def timed_windows(a, ranks: Ranks, run) -> tuple[float, list[float], object]:
     """W warm-up steps, then timed regions of EXACTLY K steps each, every one bracketed by a barrier + device sync on
-    both sides and clocked as the MAX over ranks.  `--windows N` fixes their number; the default (0) repeats them until
-    they cover MIN_TIMED_SECONDS of timed work (at least MIN_WINDOWS, at most MAX_WINDOWS): a 20-step window is 3.6 ms,
-    and the box needs tens of milliseconds of load before its clocks settle (the first windows of a short run are
-    10 - 20 % slower; all of them are printed).  Returns (median seconds per window, all windows, the last result
+    both sides and clocked as the MAX over ranks.  `--windows N` fixes their number, by default one: --steps is then the
+    number of timed steps.  `--windows 0` repeats them until they cover MIN_TIMED_SECONDS of timed work (at least
+    MIN_WINDOWS, at most MAX_WINDOWS): a 20-step window is 3.6 ms, and the box needs tens of milliseconds of load before
+    its clocks settle (the first windows of a short run are 10 - 20 % slower; all of them are printed).  Returns (median seconds per window, all windows, the last result
     handle of the last window)."""
     run(a.warmup)
     secs, last = [], None
@@ -235,7 +265,7 @@ def corpus_bench(a, ctx, ranks: Ranks):
         return last
 
     elapsed, windows, last = timed_windows(a, ranks, run)
-    recs = []
+    recs, parts = [], {}
     valid = True
     from oracle import oracle as orc
     for (members, big, t), bufs in zip(tensors, last or []):
@@ -245,11 +275,18 @@ def corpus_bench(a, ctx, ranks: Ranks):
             P = models[i][1].shape[0]
             part = {k: (v[p0:p0 + P] if k != "q_lo" else v) for k, v in r.items()}
             recs.append(shard.pack_records(part, i, big.shape[1], big.shape[2]))
+            parts[i] = part
             p0 += P
         if not a.no_validate:
             ok, _ = validate(r, orc.summarize(big, "pcn"))
             valid = valid and ok
         t.free()
+    if parts:                                     # this rank's models in corpus order, one row per parameter
+        order = sorted(parts)
+        got = {k: np.concatenate([parts[i][k] for i in order]) for k in parts[order[0]] if k != "q_lo"}
+        got["q_lo"] = parts[order[0]]["q_lo"]
+        got["model_index"] = np.concatenate([np.full(len(parts[i]["mean"]), i) for i in order])
+        dump_outputs(a, got, rank)
     local = np.concatenate(recs) if recs else np.empty((0, shard.RECORD_DOUBLES))
     allrec = shard.gather_records(local, ranks.comm)
     valid = ranks.all_true(valid and allrec.shape[0] == 460)
@@ -304,6 +341,7 @@ def split_bench(a, ctx, ranks: Ranks):
     recs = np.empty((0, shard.RECORD_DOUBLES))
     if pb:
         got = last.result()
+        dump_outputs(a, got, rank)
         recs = shard.pack_records(got, 0, C, N, param0=p0)
         if not a.no_validate:
             from oracle import oracle as orc
@@ -694,6 +732,7 @@ def c1_bench(a, ctx, ranks: Ranks, _ffi, synth):
     os.environ.pop("MCR_LANES", None)
 
     got = last.result()
+    dump_outputs(a, got, rank)
 
     # final summary gather over RCCL: fixed-size (128 B) per-parameter records to every rank
     gathered_ok = True
