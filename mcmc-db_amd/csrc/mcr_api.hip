@@ -284,7 +284,7 @@ int get_twiddles(mcr_ctx* ctx, int L, double2** out)
 // into two sub-transforms of at most 2048).  slots = listed pairs served per call (the rest take the direct rounds).
 constexpr i64 kFftMinN = 16384;
 constexpr int kFftChainBatch = 4;
-struct FftPlan { bool on = false; int logN = 0, log1 = 0, log2 = 0, slots = 0, cb = 0; size_t bytes = 0; };
+struct FftPlan { bool on = false; int logN = 0, log1 = 0, log2 = 0, slots = 0, cb = 0; };
 FftPlan plan_fft(i64 n, int C, bool enabled)
 {
     FftPlan f;
@@ -297,7 +297,6 @@ FftPlan plan_fft(i64 n, int C, bool enabled)
     i64 slots = ((i64)1 << 23) / N;
     f.slots = (int)(slots < 2 ? 2 : (slots > 32 ? 32 : slots));
     f.cb = (C + 1) / 2 < kFftChainBatch ? (C + 1) / 2 : kFftChainBatch;     // transforms per batch: two chains share one
-    f.bytes = (size_t)f.slots * ((size_t)f.cb * N * 16 + (size_t)N * 8 + (size_t)N * 16) + 3 * 256;
     return f;
 }
 
@@ -328,19 +327,22 @@ int ensure_slot(mcr_ctx* ctx, Slot& s, size_t res_doubles, size_t off_entries)
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// Cuts a workspace into 256-byte aligned buffers.  A Carve with a null base only measures: off ends as the byte count.
+// Over a real workspace of `end` bytes a take past the end hands out nullptr, and the caller fails on over().
 struct Carve {
-    char* base; size_t off = 0;
+    char* base; size_t end = SIZE_MAX; size_t off = 0;
     template <typename T> T* take(size_t n)
     {
         off = align_up(off, 256);
-        T* p = reinterpret_cast<T*>(base + off);
+        T* p = base && off + n * sizeof(T) <= end ? reinterpret_cast<T*>(base + off) : nullptr;
         off += n * sizeof(T);
         return p;
     }
+    bool over() const { return off > end; }
 };
 
+// Tiling of the sort of M pooled draws
 struct WsPlan {
-    size_t per_param;  // bytes per parameter (upper bound incl. alignment slack handled separately)
     i64 ntiles;
     // bucket path: the pooled array is cut into bk_k <= 16 sorted runs of length bk_R (a tile, or tiles
     // pre-merged by a few pairwise passes); #buckets, samples per bucket
@@ -348,7 +350,7 @@ struct WsPlan {
     i64 bk_R = 0;
 };
 
-WsPlan plan_ws(i64 M, int C, bool ingest, bool ranks, i64 nstage)
+WsPlan plan_ws(i64 M)
 {
     WsPlan w;
     w.ntiles = (M + kTile - 1) / kTile;
@@ -365,13 +367,6 @@ WsPlan plan_ws(i64 M, int C, bool ingest, bool ranks, i64 nstage)
             if (w.bk_B < 1) w.bk_B = 1;
         }
     }
-    w.per_param = (size_t)(w.ntiles + 16) * 64 * 8 + (size_t)(w.bk_B + 1) * ((size_t)w.bk_k + 1) * 4 + 16 +
-                  (size_t)M * (8 + 4) * 2 + (size_t)M * 4 * 2 + (ingest ? (size_t)M * 8 : 0) +
-                  (ranks ? (size_t)M * 32 + 1024 : 0) + (size_t)w.ntiles * kMomRec * 8 + 8 +
-                  (size_t)2 * (size_t)(C > 0 ? C : 1) *
-                      ((size_t)((nstage + kSeg - 1) / kSeg + 1) * (kSegRec + 64 * kMoreBlocks) + kChState) * 8 +
-                  (size_t)2 * (size_t)(nstage > 0 ? nstage : 1) * 8 + 2 * 4 + 2 * (kT3Stages + 1) * 4 + 2 * kPairState * 8 +
-                  8 + 64;
     return w;
 }
 
@@ -413,6 +408,64 @@ struct PipeIn {
     bool do_diag = true;  // false: Backend.stats only (sort + order statistics + moments)
     bool fork = false;    // lone call: the bulk half of the diagnostics on the lane's second stream (run_pipeline)
 };
+
+// The FFT tier's buffers: shared by all parameters of a call.
+void carve_fft(Carve& cv, PipeIn& a, const FftPlan& fp)
+{
+    a.fft = fp;
+    if (!fp.on) return;
+    const size_t Nf = (size_t)1 << fp.logN;
+    a.fft_A = cv.take<double2>((size_t)fp.slots * fp.cb * Nf);
+    a.fft_S = cv.take<double>((size_t)fp.slots * Nf);
+    a.fft_B = cv.take<double2>((size_t)fp.slots * Nf);
+}
+
+// The one layout of the pipeline's workspace: the buffers of a.pc parameters of a.M draws in a.C chains (the shortest
+// a.n draws long, the segment grid over a.nstage).  Every entry point carves with it, and measures with it (null base)
+// how much workspace it needs.  records = false: the sort alone, without rank codes and diagnostics records.  ingest:
+// an f64 copy X[pc][M] of the draws at the end, returned.
+double* carve_pipe(Carve& cv, PipeIn& a, bool records, const FftPlan& fp, bool ingest)
+{
+    const WsPlan wp = plan_ws(a.M);
+    const size_t pc = (size_t)a.pc, M = (size_t)a.M;
+    a.ntiles = wp.ntiles;
+    a.bk_B = wp.bk_B; a.bk_D = wp.bk_D; a.bk_k = wp.bk_k; a.bk_R = wp.bk_R;
+    a.kA = cv.take<double>(pc * M); a.kB = cv.take<double>(pc * M);
+    a.iA = cv.take<u32>(pc * M);    a.iB = cv.take<u32>(pc * M);
+    if (records) { a.zb = cv.take<u32>(pc * M); a.zt = cv.take<u32>(pc * M); }
+    a.part = cv.take<double>(pc * wp.ntiles * kMomRec);
+    if (records) {
+        const size_t cc = (size_t)(a.C > 0 ? a.C : 1), ns = (size_t)((a.nstage + kSeg - 1) / kSeg + 1);
+        a.split = cv.take<i64>(pc);
+        a.rec = cv.take<double>(pc * 2 * cc * ns * kSegRec);
+        a.rec2 = cv.take<double>(pc * 2 * cc * ns * 64 * kMoreBlocks);
+        a.chstate = cv.take<double>(pc * 2 * cc * kChState);
+        a.more = cv.take<unsigned>(pc * 2);
+        a.state = cv.take<double>(pc * 2 * kPairState);
+        a.acov = cv.take<double>(pc * 2 * (size_t)(a.n > 0 ? a.n : 1));
+        a.long_count = cv.take<unsigned>(1);
+        a.long_list = cv.take<unsigned>(pc * 2);
+        a.t3c = cv.take<unsigned>(pc * 2 * (kT3Stages + 1));
+    }
+    a.samp = cv.take<double>(pc * (wp.ntiles + 16) * 64);
+    a.cut = cv.take<u32>(pc * (wp.bk_B + 1) * (size_t)(wp.bk_k + 1));
+    a.boff = cv.take<u32>(pc * (wp.bk_B + 1));
+    carve_fft(cv, a, fp);
+    return ingest ? cv.take<double>(pc * M) : nullptr;
+}
+
+// Measures a layout (a callable on a Carve&), makes the workspace that large, then carves it.
+template <class Layout> int carve_ws(mcr_ctx* ctx, Layout&& layout)
+{
+    Carve m{nullptr};
+    layout(m);
+    const int rc = ensure_ws(ctx, m.off);
+    if (rc) return rc;
+    Carve cv{reinterpret_cast<char*>(ctx->ws), ctx->ws_bytes};
+    layout(cv);
+    if (cv.over()) return fail(ctx, MCR_ENOMEM, "workspace layout needs %zu bytes; the workspace has %zu", cv.off, cv.end);
+    return MCR_OK;
+}
 
 // Tiers 1 and 2 of one kind (0 bulk, 1 folded) or of both (kind_sel < 0): segment products, combine, the flagged pairs'
 // lags 64..255 -- everything of the diagnostics that does not need the other kind.  On ctx->stream.
@@ -874,31 +927,46 @@ int check_common(mcr_ctx* ctx, const void* draws, int dtype, i64 C, i64 N, i64 P
 
 // How a call of this shape is cut into workspace chunks of parameters (a pure function of the shape, the workspace limit
 // and MCR_FFT): shared by enqueue_impl and mcr_plan_chunks.
-struct ChunkPlan { bool ingest = false; WsPlan wp{}; FftPlan fp{}; size_t slack = 0; i64 pcmax = 0; };
+struct ChunkPlan { bool ingest = false; FftPlan fp{}; i64 pcmax = 0; size_t bytes = 0; };
 int plan_chunks(mcr_ctx* ctx, i64 C, i64 N, i64 P, i64 sc, i64 sn, i64 sp, bool do_diag, ChunkPlan& cp)
 {
     const i64 M = C * N;
     // tensors in the Arrow column layout [P][C][N] are consumed in place, f64 and f32 alike (the tile sort widens f32
     // as it loads); anything else goes through one ingest pass into X[P][M] f64
     cp.ingest = !((N <= 1 || sn == 1) && (C <= 1 || sc == N) && (P <= 1 || sp == M));
-    cp.wp = plan_ws(M, (int)C, cp.ingest, false, N);
     cp.fp = plan_fft(N, (int)C, do_diag && ctx->fft_on);
+    auto fft_bytes = [&]() {
+        PipeIn a{};
+        Carve m{nullptr};
+        carve_fft(m, a, cp.fp);
+        return m.off;
+    };
+    auto measure = [&](i64 pc) {
+        PipeIn a{};
+        a.M = M; a.pc = pc; a.C = (int)C; a.n = N; a.nstage = N > 0 ? N : 1;
+        Carve m{nullptr};
+        carve_pipe(m, a, true, cp.fp, cp.ingest);
+        return m.off;
+    };
     // the FFT tier is an accelerator, not a requirement: under a tight workspace limit it gets fewer slots, or none
     // (the direct rounds then serve every listed pair), but at least a third of the limit stays with the parameters
-    while (cp.fp.on && cp.fp.bytes > ctx->ws_limit / 3) {
+    while (cp.fp.on && fft_bytes() > ctx->ws_limit / 3) {
         if (cp.fp.slots <= 1) { cp.fp = FftPlan{}; break; }
         cp.fp.slots /= 2;
-        const size_t Nf = (size_t)1 << cp.fp.logN;
-        cp.fp.bytes = (size_t)cp.fp.slots * ((size_t)cp.fp.cb * Nf * 16 + Nf * 8 + Nf * 16) + 3 * 256;
     }
-    cp.slack = 40 * 256 + cp.fp.bytes;
-    if (cp.wp.per_param + cp.slack > ctx->ws_limit)
-        return fail(ctx, MCR_ENOMEM, "one parameter needs %zu bytes of workspace (%zu for the parameter + %zu shared, of which %zu "
-                    "for the FFT tier); limit is %zu", cp.wp.per_param + cp.slack, cp.wp.per_param, cp.slack, cp.fp.bytes, ctx->ws_limit);
-    i64 pcmax = (i64)((ctx->ws_limit - cp.slack) / cp.wp.per_param);
-    if (pcmax > P) pcmax = P;
-    if (pcmax > kMaxGridY / 2) pcmax = kMaxGridY / 2;   // k_acov_seg uses grid.z = 2 * pc
-    cp.pcmax = pcmax;
+    i64 lo = 1, hi = P < kMaxGridY / 2 ? P : kMaxGridY / 2;   // k_acov_seg uses grid.z = 2 * pc
+    cp.bytes = measure(hi);
+    if (cp.bytes > ctx->ws_limit) {                          // (the common case fits at once: no search)
+        if (measure(1) > ctx->ws_limit)
+            return fail(ctx, MCR_ENOMEM, "one parameter needs %zu bytes of workspace (%zu of them for the FFT tier); limit is %zu",
+                        measure(1), fft_bytes(), ctx->ws_limit);
+        while (lo < hi) {                                    // the most parameters whose layout fits the limit
+            const i64 mid = lo + (hi - lo + 1) / 2;
+            if (measure(mid) <= ctx->ws_limit) lo = mid; else hi = mid - 1;
+        }
+        cp.bytes = measure(lo);
+    }
+    cp.pcmax = hi;
     return MCR_OK;
 }
 
@@ -930,9 +998,7 @@ int enqueue_impl(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i
         rc = plan_chunks(ctx, C, N, P, sc, sn, sp, do_diag_early, cp);
         if (rc) return rc;
         const bool ingest = cp.ingest;
-        const WsPlan& wp = cp.wp;
         const FftPlan& fp = cp.fp;
-        const size_t slack = cp.slack;
         const i64 pcmax = cp.pcmax;
         double2 *tw1 = nullptr, *tw2 = nullptr;
         if (fp.on) {
@@ -940,7 +1006,7 @@ int enqueue_impl(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i
             if (!rc) rc = get_twiddles(ctx, 1 << fp.log2, &tw2);
             if (rc) return rc;
         }
-        rc = ensure_ws(ctx, (size_t)pcmax * wp.per_param + slack);
+        rc = ensure_ws(ctx, cp.bytes);
         if (rc) return rc;
         const int R = res_fields(nq);
         rc = ensure_slot(ctx, s, (size_t)R * (size_t)P, (size_t)C + 1);
@@ -957,48 +1023,21 @@ int enqueue_impl(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i
                 HIP_TRY(ctx, hipMemcpyAsync(s.d_off, s.h_off, sizeof(i64) * (size_t)(C + 1), hipMemcpyHostToDevice, ctx->stream));
             for (i64 p0 = 0; p0 < P; p0 += pcmax) {
                 const i64 pc = (P - p0 < pcmax) ? P - p0 : pcmax;
-                Carve cv{reinterpret_cast<char*>(ctx->ws)};
+                Carve cv{reinterpret_cast<char*>(ctx->ws), ctx->ws_bytes};
                 PipeIn a{};
                 a.M = M; a.pc = pc; a.C = (int)C; a.d_off = s.d_off; a.n = N; a.nh = (N >= 2) ? N / 2 : 0; a.q = q;
-                a.ntiles = wp.ntiles;
-                a.kA = cv.take<double>((size_t)pc * M); a.kB = cv.take<double>((size_t)pc * M);
-                a.iA = cv.take<u32>((size_t)pc * M);    a.iB = cv.take<u32>((size_t)pc * M);
-                a.zb = cv.take<u32>((size_t)pc * M); a.zt = cv.take<u32>((size_t)pc * M);
-                a.part = cv.take<double>((size_t)pc * wp.ntiles * kMomRec);
-                a.split = cv.take<i64>((size_t)pc);
-                {
-                    const size_t cc = (size_t)(C > 0 ? C : 1), ns = (size_t)((N + kSeg - 1) / kSeg + 1);
-                    a.rec = cv.take<double>((size_t)pc * 2 * cc * ns * kSegRec);
-                    a.rec2 = cv.take<double>((size_t)pc * 2 * cc * ns * 64 * kMoreBlocks);
-                    a.chstate = cv.take<double>((size_t)pc * 2 * cc * kChState);
-                    a.more = cv.take<unsigned>((size_t)pc * 2);
-                    a.state = cv.take<double>((size_t)pc * 2 * kPairState);
-                    a.acov = cv.take<double>((size_t)pc * 2 * (size_t)(N > 0 ? N : 1));
-                    a.long_count = cv.take<unsigned>(1);
-                    a.long_list = cv.take<unsigned>((size_t)pc * 2);
-                    a.t3c = cv.take<unsigned>((size_t)pc * 2 * (kT3Stages + 1));
-                }
                 a.nstage = N > 0 ? N : 1;
+                double* X = carve_pipe(cv, a, true, fp, ingest);
+                if (cv.over()) return fail(ctx, MCR_ENOMEM, "workspace layout needs %zu bytes; the workspace has %zu", cv.off, cv.end);
                 a.ztab = ztab;
-                a.samp = cv.take<double>((size_t)pc * (wp.ntiles + 16) * 64);
-                a.cut = cv.take<u32>((size_t)pc * (wp.bk_B + 1) * (size_t)(wp.bk_k + 1));
-                a.boff = cv.take<u32>((size_t)pc * (wp.bk_B + 1));
-                a.bk_B = wp.bk_B; a.bk_D = wp.bk_D; a.bk_k = wp.bk_k; a.bk_R = wp.bk_R;
                 a.do_diag = do_diag;
                 // (a graph capture or the per-kernel event pairs of the profiling mode keep the single stream)
                 a.fork = ctx->fork_lone && ctx->n_inflight == 0 && !ctx->prof && !ctx->graph_on && P <= pcmax &&
                          (double)M * (double)pc >= 2e6 && (double)M * (double)pc <= 8e6;    // kernels long enough to be worth
                                                    // three more launches and two event waits (measured: C1 4 M param-draws 306 -> 288 us,
                                                    // 10 x 1000 x 45 149 -> 166, 4 x 1000 x 10 124 -> 133), short enough not to fill the chip
-                a.fft = fp; a.tw1 = tw1; a.tw2 = tw2;
-                if (fp.on) {
-                    const size_t Nf = (size_t)1 << fp.logN;
-                    a.fft_A = cv.take<double2>((size_t)fp.slots * fp.cb * Nf);
-                    a.fft_S = cv.take<double>((size_t)fp.slots * Nf);
-                    a.fft_B = cv.take<double2>((size_t)fp.slots * Nf);
-                }
+                a.tw1 = tw1; a.tw2 = tw2;
                 if (ingest) {
-                    double* X = cv.take<double>((size_t)pc * M);
                     const int r2 = (dtype == MCR_F64) ? launch_ingest<double>(ctx, draws_dev, X, C, N, pc, sc, sn, sp, p0)
                                                       : launch_ingest<float>(ctx, draws_dev, X, C, N, pc, sc, sn, sp, p0);
                     if (r2) return r2;
@@ -1492,14 +1531,20 @@ int mcr_diagnose_chains(mcr_ctx* ctx, const double* pooled, const int64_t* chain
         const i64 len = chain_off[c + 1] - chain_off[c];
         if (len >= 2 && len / 2 + nh > nstage) nstage = len / 2 + nh;
     }
-    const WsPlan wp = plan_ws(M, C, true, want_dbg, nstage);
     FftPlan fp = plan_fft(n, C, ctx->fft_on);
     fp.slots = fp.on ? 2 : 0;                       // one parameter: two (parameter, kind) pairs at most
-    if (fp.on) { const size_t Nf = (size_t)1 << fp.logN; fp.bytes = (size_t)fp.slots * ((size_t)fp.cb * Nf * 16 + Nf * 8 + Nf * 16) + 3 * 256; }
-    if (fp.on && wp.per_param + 40 * 256 + fp.bytes > ctx->ws_limit) fp = FftPlan{};
-    const size_t slack = 40 * 256 + fp.bytes;
-    if (wp.per_param + slack > ctx->ws_limit) return fail(ctx, MCR_ENOMEM, "workspace limit too small for %lld draws", M);
-    int rc = ensure_ws(ctx, wp.per_param + slack);
+    PipeIn a{};
+    a.M = M; a.pc = 1; a.C = C; a.n = n; a.nh = nh; a.q.nq = 0; a.nstage = nstage;
+    double* X = nullptr;
+    double* dbg[4] = {nullptr, nullptr, nullptr, nullptr};     // z_bulk, z_tail, rank_bulk, rank_tail (decoded codes)
+    auto layout = [&](Carve& cv) {
+        X = carve_pipe(cv, a, true, fp, true);
+        if (want_dbg) for (int i = 0; i < 4; ++i) dbg[i] = cv.take<double>((size_t)M);
+    };
+    auto measure = [&]() { Carve m{nullptr}; layout(m); return m.off; };
+    if (fp.on && measure() > ctx->ws_limit) fp = FftPlan{};
+    if (measure() > ctx->ws_limit) return fail(ctx, MCR_ENOMEM, "workspace limit too small for %lld draws", M);
+    int rc = carve_ws(ctx, layout);
     if (rc) return rc;
     const int R = res_fields(0);
     rc = ensure_slot(ctx, s, (size_t)R, (size_t)C + 1);
@@ -1507,46 +1552,14 @@ int mcr_diagnose_chains(mcr_ctx* ctx, const double* pooled, const int64_t* chain
     s.off_C = s.off_N = -1;
     memcpy(s.h_off, chain_off, sizeof(i64) * (size_t)(C + 1));
     HIP_TRY(ctx, hipMemcpyAsync(s.d_off, s.h_off, sizeof(i64) * (size_t)(C + 1), hipMemcpyHostToDevice, ctx->stream));
-    Carve cv{reinterpret_cast<char*>(ctx->ws)};
-    PipeIn a{};
-    a.M = M; a.pc = 1; a.C = C; a.d_off = s.d_off; a.n = n; a.nh = nh; a.q.nq = 0; a.ntiles = wp.ntiles;
-    a.kA = cv.take<double>((size_t)M); a.kB = cv.take<double>((size_t)M);
-    a.iA = cv.take<u32>((size_t)M);    a.iB = cv.take<u32>((size_t)M);
-    a.zb = cv.take<u32>((size_t)M); a.zt = cv.take<u32>((size_t)M);
-    a.part = cv.take<double>((size_t)wp.ntiles * kMomRec);
-    a.split = cv.take<i64>(1);
-    {
-        const size_t cc = (size_t)(C > 0 ? C : 1), ns = (size_t)((nstage + kSeg - 1) / kSeg + 1);
-        a.rec = cv.take<double>((size_t)2 * cc * ns * kSegRec);
-        a.rec2 = cv.take<double>((size_t)2 * cc * ns * 64 * kMoreBlocks);
-        a.chstate = cv.take<double>((size_t)2 * cc * kChState);
-        a.more = cv.take<unsigned>(2);
-        a.state = cv.take<double>(2 * kPairState);
-        a.acov = cv.take<double>((size_t)2 * (size_t)(n > 0 ? n : 1));
-        a.long_count = cv.take<unsigned>(1);
-        a.long_list = cv.take<unsigned>(2);
-        a.t3c = cv.take<unsigned>(2 * (kT3Stages + 1));
-    }
-    a.nstage = nstage;
+    a.d_off = s.d_off;
     rc = get_ztab(ctx, M, &a.ztab);
     if (rc) return rc;
-    a.samp = cv.take<double>((size_t)(wp.ntiles + 16) * 64);
-    a.cut = cv.take<u32>((size_t)(wp.bk_B + 1) * (size_t)(wp.bk_k + 1));
-    a.boff = cv.take<u32>((size_t)(wp.bk_B + 1));
-    a.bk_B = wp.bk_B; a.bk_D = wp.bk_D; a.bk_k = wp.bk_k; a.bk_R = wp.bk_R;
-    a.fft = fp;
     if (fp.on) {
         rc = get_twiddles(ctx, 1 << fp.log1, &a.tw1);
         if (!rc) rc = get_twiddles(ctx, 1 << fp.log2, &a.tw2);
         if (rc) return rc;
-        const size_t Nf = (size_t)1 << fp.logN;
-        a.fft_A = cv.take<double2>((size_t)fp.slots * fp.cb * Nf);
-        a.fft_S = cv.take<double>((size_t)fp.slots * Nf);
-        a.fft_B = cv.take<double2>((size_t)fp.slots * Nf);
     }
-    double* X = cv.take<double>((size_t)M);
-    double* dbg[4] = {nullptr, nullptr, nullptr, nullptr};     // z_bulk, z_tail, rank_bulk, rank_tail (decoded codes)
-    if (want_dbg) for (int i = 0; i < 4; ++i) dbg[i] = cv.take<double>((size_t)M);
     HIP_TRY(ctx, hipMemcpyAsync(X, pooled, sizeof(double) * (size_t)M, hipMemcpyHostToDevice, ctx->stream));
     a.X = X;
     a.d_res = s.d_res;
@@ -1600,13 +1613,13 @@ int mcr_moments_dev(mcr_ctx* ctx, const void* draws_dev, int dtype, int64_t C, i
         if (S < 1) S = 1;
         if (S > kMaxGridY) S = kMaxGridY;
     }
-    const size_t need = align_up((size_t)P * S * kMomRec * 8, 256) + align_up((size_t)P * 8, 256) * 2 + 1024;
-    int rc = ensure_ws(ctx, need);
+    double *part, *d_mean, *d_std;
+    int rc = carve_ws(ctx, [&](Carve& cv) {
+        part = cv.take<double>((size_t)P * S * kMomRec);
+        d_mean = cv.take<double>((size_t)P);
+        d_std = cv.take<double>((size_t)P);
+    });
     if (rc) return rc;
-    Carve cv{reinterpret_cast<char*>(ctx->ws)};
-    double* part = cv.take<double>((size_t)P * S * kMomRec);
-    double* d_mean = cv.take<double>((size_t)P);
-    double* d_std = cv.take<double>((size_t)P);
     rc = dtype == MCR_F64 ? moments_impl<double>(ctx, (const double*)draws_dev, C, N, P, sc, sn, sp, d_mean, d_std, part, S, rows)
                           : moments_impl<float>(ctx, (const float*)draws_dev, C, N, P, sc, sn, sp, d_mean, d_std, part, S, rows);
     if (rc) return rc;
@@ -1639,14 +1652,15 @@ int mcr_compare(mcr_ctx* ctx, const double* ref, const double* actual, int64_t n
     if (n < 0 || (n > 0 && (!ref || !actual || !rel_error || !passed))) return fail(ctx, MCR_EINVAL, "bad argument");
     if (n == 0) return MCR_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t need = align_up((size_t)n * 8, 256) * 3 + align_up((size_t)n, 256) + 1024;
-    int rc = ensure_ws(ctx, need);
+    double *d_ref, *d_act, *d_rel;
+    unsigned char* d_ok;
+    const int rc = carve_ws(ctx, [&](Carve& cv) {
+        d_ref = cv.take<double>((size_t)n);
+        d_act = cv.take<double>((size_t)n);
+        d_rel = cv.take<double>((size_t)n);
+        d_ok = cv.take<unsigned char>((size_t)n);
+    });
     if (rc) return rc;
-    Carve cv{reinterpret_cast<char*>(ctx->ws)};
-    double* d_ref = cv.take<double>((size_t)n);
-    double* d_act = cv.take<double>((size_t)n);
-    double* d_rel = cv.take<double>((size_t)n);
-    unsigned char* d_ok = cv.take<unsigned char>((size_t)n);
     HIP_TRY(ctx, hipMemcpyAsync(d_ref, ref, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(d_act, actual, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
     LAUNCH(ctx, K_COMPARE, k_compare, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const double*)d_ref,
@@ -1655,22 +1669,6 @@ int mcr_compare(mcr_ctx* ctx, const double* ref, const double* actual, int64_t n
     HIP_TRY(ctx, hipMemcpyAsync(passed, d_ok, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     prof_resolve(ctx);
-    return MCR_OK;
-}
-
-// Sort-only carve of the workspace for P parameters of M draws each (no diagnostics buffers).
-static int carve_sort(mcr_ctx* ctx, Carve& cv, i64 M, i64 P, PipeIn& a)
-{
-    const WsPlan wp = plan_ws(M, 1, false, false, 1);
-    a = PipeIn{};
-    a.M = M; a.pc = P; a.C = 1; a.ntiles = wp.ntiles; a.do_diag = false;
-    a.kA = cv.take<double>((size_t)P * M); a.kB = cv.take<double>((size_t)P * M);
-    a.iA = cv.take<u32>((size_t)P * M);    a.iB = cv.take<u32>((size_t)P * M);
-    a.part = cv.take<double>((size_t)P * wp.ntiles * kMomRec);
-    a.samp = cv.take<double>((size_t)P * (wp.ntiles + 16) * 64);
-    a.cut = cv.take<u32>((size_t)P * (wp.bk_B + 1) * (size_t)(wp.bk_k + 1));
-    a.boff = cv.take<u32>((size_t)P * (wp.bk_B + 1));
-    a.bk_B = wp.bk_B; a.bk_D = wp.bk_D; a.bk_k = wp.bk_k; a.bk_R = wp.bk_R;
     return MCR_OK;
 }
 
@@ -1686,45 +1684,41 @@ int mcr_two_sample(mcr_ctx* ctx, const double* ref, int64_t Mr, const double* ac
         return fail(ctx, MCR_EINVAL, "samples too long (Mr * Ma must stay below 2^53)");
     if (ctx->n_inflight) return fail(ctx, MCR_EINVAL, "mcr_two_sample with summaries in flight");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const i64 Mx = Mr > Ma ? Mr : Ma;
     const int nblk = (int)((Mr + Ma + kTile - 1) / kTile);
-    const size_t need = (size_t)P * (size_t)Mx * (8 + 4) * 2 + (size_t)P * (size_t)(Mr + Ma) * 8 * 2 +
-                        (size_t)P * ((size_t)((Mx + kTile - 1) / kTile) * (32 + 512 + 4 * 80) + (size_t)nblk * 16 + 64) +
-                        64 * 256;
-    int rc = ensure_ws(ctx, need);
+    double *Xr, *Xa, *Sr, *part, *d_ks, *d_w, *bad;
+    PipeIn ar{}, aa{};            // the sorts of the two samples: one after the other, in the same space
+    ar.M = Mr; aa.M = Ma;
+    ar.pc = aa.pc = P; ar.C = aa.C = 1; ar.do_diag = aa.do_diag = false;
+    int rc = carve_ws(ctx, [&](Carve& cv) {
+        Xr = cv.take<double>((size_t)P * Mr);
+        Xa = cv.take<double>((size_t)P * Ma);
+        Sr = cv.take<double>((size_t)P * Mr);
+        part = cv.take<double>((size_t)P * nblk * 2);
+        d_ks = cv.take<double>((size_t)P);
+        d_w = cv.take<double>((size_t)P);
+        bad = cv.take<double>((size_t)P * 2);
+        const size_t base = cv.off;
+        carve_pipe(cv, ar, false, FftPlan{}, false);
+        const size_t end_r = cv.off;
+        cv.off = base;
+        carve_pipe(cv, aa, false, FftPlan{}, false);
+        if (end_r > cv.off) cv.off = end_r;
+    });
     if (rc) return rc;
-    Carve cv{reinterpret_cast<char*>(ctx->ws)};
-    double* Xr = cv.take<double>((size_t)P * Mr);
-    double* Xa = cv.take<double>((size_t)P * Ma);
-    double* Sr = cv.take<double>((size_t)P * Mr);
-    double* part = cv.take<double>((size_t)P * nblk * 2);
-    double* d_ks = cv.take<double>((size_t)P);
-    double* d_w = cv.take<double>((size_t)P);
-    double* bad = cv.take<double>((size_t)P * 2);
-    const size_t base = cv.off;
     HIP_TRY(ctx, hipMemcpyAsync(Xr, ref, sizeof(double) * (size_t)P * Mr, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(Xa, act, sizeof(double) * (size_t)P * Ma, hipMemcpyHostToDevice, ctx->stream));
     double *kin, *kout; void *iin, *iout; bool ranked;
-    PipeIn a;
-    {   // ascending order of the reference sample, parked in Sr
-        Carve c2{reinterpret_cast<char*>(ctx->ws), base};
-        carve_sort(ctx, c2, Mr, P, a);
-        a.X = Xr;
-        rc = sort_stage(ctx, a, &kin, &iin, &kout, &iout, &ranked);
-        if (rc) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(Sr, kin, sizeof(double) * (size_t)P * Mr, hipMemcpyDeviceToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_bad_count, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)a.part,
-                           (int)a.ntiles, (i64)P, bad);
-    }
-    {   // ascending order of the actual sample, then one merge-path pass over both
-        Carve c2{reinterpret_cast<char*>(ctx->ws), base};
-        carve_sort(ctx, c2, Ma, P, a);
-        a.X = Xa;
-        rc = sort_stage(ctx, a, &kin, &iin, &kout, &iout, &ranked);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_bad_count, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)a.part,
-                           (int)a.ntiles, (i64)P, bad + P);
-    }
+    ar.X = Xr;                    // ascending order of the reference sample, parked in Sr
+    rc = sort_stage(ctx, ar, &kin, &iin, &kout, &iout, &ranked);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(Sr, kin, sizeof(double) * (size_t)P * Mr, hipMemcpyDeviceToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_bad_count, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)ar.part,
+                       (int)ar.ntiles, (i64)P, bad);
+    aa.X = Xa;                    // ascending order of the actual sample, then one merge-path pass over both
+    rc = sort_stage(ctx, aa, &kin, &iin, &kout, &iout, &ranked);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_bad_count, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)aa.part,
+                       (int)aa.ntiles, (i64)P, bad + P);
     LAUNCH(ctx, K_TWO_SAMPLE, (k_two_sample<256, 16>), dim3((unsigned)nblk, (unsigned)P), dim3(256), 0,
            (const double*)Sr, (i64)Mr, (const double*)kin, (i64)Ma, part, nblk);
     LAUNCH(ctx, K_TWO_SAMPLE, k_two_sample_final, dim3((unsigned)((P + 255) / 256)), dim3(256), 0,
@@ -1766,14 +1760,14 @@ int mcr_covariance_dev(mcr_ctx* ctx, const double* draws_dev, int64_t M, int64_t
     kchunk = (kchunk + kCovBK - 1) / kCovBK * kCovBK;
     ksplit = (int)((M + kchunk - 1) / kchunk);
     const int S = 8;
-    const size_t need = (size_t)ksplit * P64 * P64 * 8 + (size_t)P * (S * kMomRec * 8 + 16) + 16 * 256;
-    int rc = ensure_ws(ctx, need);
+    double *partial, *mpart, *d_mean, *d_std;
+    int rc = carve_ws(ctx, [&](Carve& cv) {
+        partial = cv.take<double>((size_t)ksplit * P64 * P64);
+        mpart = cv.take<double>((size_t)P * S * kMomRec);
+        d_mean = cv.take<double>((size_t)P);
+        d_std = cv.take<double>((size_t)P);
+    });
     if (rc) return rc;
-    Carve cv{reinterpret_cast<char*>(ctx->ws)};
-    double* partial = cv.take<double>((size_t)ksplit * P64 * P64);
-    double* mpart = cv.take<double>((size_t)P * S * kMomRec);
-    double* d_mean = cv.take<double>((size_t)P);
-    double* d_std = cv.take<double>((size_t)P);
     rc = moments_impl<double>(ctx, draws_dev, 1, M, P, M, 1, M, d_mean, d_std, mpart, (M >= 8 * 2048) ? S : 1, true);
     if (rc) return rc;
     if ((M & 1) == 0 && (reinterpret_cast<uintptr_t>(draws_dev) & 15) == 0) {

@@ -19,13 +19,19 @@ def ctx():
 def test_two_sample_matches_scipy(ctx):
     from scipy.stats import ks_2samp, wasserstein_distance
     rng = np.random.default_rng(4)
-    cases = [(3, 10000, 4000), (2, 5000, 5000), (4, 37, 41), (1, 1, 1), (2, 70000, 9000), (1, 4096, 8192)]
+    from mcmc_ref_hip import _ffi
+    cases = [(3, 10000, 4000), (2, 5000, 5000), (4, 37, 41), (1, 1, 1), (2, 70000, 9000), (1, 4096, 8192),
+             (1000, 100, 100), (2000, 10, 10)]
     for P, Mr, Ma in cases:
         ref = rng.normal(size=(P, Mr))
         act = rng.normal(loc=0.1, scale=1.2, size=(P, Ma))
         if P > 1:
             ref[1] = np.round(ref[1], 1); act[1] = np.round(act[1], 1)        # ties within and across samples
-        ks, w1 = ctx.two_sample(ref, act)
+        if P >= 1000:   # short samples, many parameters: a fresh context, whose workspace no earlier call has grown
+            with _ffi.Context() as fresh:
+                ks, w1 = fresh.two_sample(ref, act)
+        else:
+            ks, w1 = ctx.two_sample(ref, act)
         for p in range(P):
             exact = ks_2samp(ref[p], act[p], method="exact" if max(Mr, Ma) <= 10000 else "asymp").statistic
             if max(Mr, Ma) <= 10000:
