@@ -36,7 +36,12 @@ using namespace mcr;
 
 namespace {
 
-constexpr int kTile = 4096;          // pooled draws per sorted tile / bucket capacity (256 lanes x 16 or 512 x 8)
+constexpr int kTile = 4096;          // pooled draws per sorted tile / bucket capacity
+// Threads x draws per lane of the tile sort and of the merge kernels (passes, bucket merge, fold): the fastest measured
+// (DESIGN.md section 4): 16 draws per lane give the tile sort its register merge levels, more waves hide the merges' LDS.
+constexpr int kTileNT = 256, kTileVT = 16;
+constexpr int kMergeNT = 512, kMergeVT = 8;
+static_assert(kTileNT * kTileVT == kTile && kMergeNT * kMergeVT == kTile, "sort geometry");
 constexpr i64 kIdx16Max = 65535;      // pooled arrays up to this length carry 16-bit positions through the sort
 constexpr int kMaxChains = 256;
 constexpr int kMaxGridY = 65535;
@@ -126,8 +131,6 @@ struct mcr_ctx {
     bool fft_on = true;      // MCR_FFT=0: long chains take the direct tier-3 rounds only (A/B measurements, parity tests)
     bool f32_records = true; // MCR_F32_RECORDS=0: f32 tensors take the f64 kernels (widened by the tile sort) instead of mcr_sort32.hpp
     bool splitters_pairwise = false;   // MCR_SPLITTERS_PAIRWISE=1: rank the regular samples pair by pair whatever their number (A/B, parity tests)
-    int sort_cfg = 10;       // MCR_SORT_CFG = tile + 10 * merge geometry (see sort_stage_i); default: tile 256 x 16, merges 512 x 8
-    size_t dbg_lds_pad[3] = {0, 0, 0};   // MCR_DBG_LDS_PAD="t,b,f": extra dynamic LDS bytes for tile sort / bucket merge / fold (occupancy experiments)
     double rho_band = kRhoBand;   // MCR_RHO_BAND: half-width of the guard band of the tier-3 scan (0 = decide on the raw values)
     unsigned* guard_count = nullptr;   // device counter: band lags re-derived the reference's way (mcr_rho_guard_count)
     bool graph_on = false;   // MCR_GRAPH=1: capture / replay (measured: no throughput gain, +0.17 ms per synchronous call)
@@ -373,7 +376,10 @@ WsPlan plan_ws(i64 M)
 struct PipeIn {
     const void* X;       // [pc][M] contiguous: f64 (user tensor or ingest buffer) or, x_f32, the user's f32 tensor itself
     bool x_f32 = false;
-    bool no_records = false;   // MCR_F32_RECORDS=0: keep f32 tensors on the f64 kernels (A/B measurements, parity tests)
+    // f32 tensors take the packed records of mcr_sort32.hpp whenever the bucket partition applies (pooled arrays up to
+    // 512 K draws) and MCR_F32_RECORDS is not 0; otherwise the tile sort widens the f32 draws and the f64 kernels run
+    bool records = false;
+    bool idx16 = false;  // M <= kIdx16Max: 16-bit positions through the sort (else 32-bit)
     i64 M, pc;
     int C;
     const i64* d_off;
@@ -383,7 +389,7 @@ struct PipeIn {
     // carved buffers
     double *kA, *kB, *part;
     u32 *zb, *zt;        // rank codes n2 of every draw in time order (z = ztab[n2], rank = (n2 + 1) / 2)
-    void *iA, *iB;       // pooled-position payload of the sort: u16 when M <= kIdx16Max, else u32
+    void *iA, *iB;       // pooled-position payload of the sort: u16 when idx16, else u32
     i64* split;
     double* rec;         // [pc][2][C][nseg][kSegRec] first-pass segment records
     unsigned* more;      // [pc][2] continuation flags
@@ -429,6 +435,7 @@ double* carve_pipe(Carve& cv, PipeIn& a, bool records, const FftPlan& fp, bool i
     const WsPlan wp = plan_ws(a.M);
     const size_t pc = (size_t)a.pc, M = (size_t)a.M;
     a.ntiles = wp.ntiles;
+    a.idx16 = a.M <= kIdx16Max;
     a.bk_B = wp.bk_B; a.bk_D = wp.bk_D; a.bk_k = wp.bk_k; a.bk_R = wp.bk_R;
     a.kA = cv.take<double>(pc * M); a.kB = cv.take<double>(pc * M);
     a.iA = cv.take<u32>(pc * M);    a.iB = cv.take<u32>(pc * M);
@@ -467,6 +474,18 @@ template <class Layout> int carve_ws(mcr_ctx* ctx, Layout&& layout)
     return MCR_OK;
 }
 
+// One k_acov_seg pass of NT threads over SEG-draw segments: tier 1 (FIRST, every pair, lags 0..63, into a.rec) or tier 2
+// (the pairs a.more flags, lags 64..255, into a.rec2).
+template <int NT, int SEG, bool FIRST>
+int launch_acov_seg(mcr_ctx* ctx, const PipeIn& a, int nseg, int kind_sel)
+{
+    const unsigned pk = (unsigned)((kind_sel < 0 ? 2 : 1) * a.pc);
+    LAUNCH(ctx, FIRST ? K_ACOV_SEG : K_ACOV_MORE, (k_acov_seg<NT, SEG, FIRST>), dim3((unsigned)nseg, (unsigned)a.C, pk),
+           dim3(NT), 0, (const u32*)a.zb, (const u32*)a.zt, (const double*)a.ztab, a.M, a.d_off, a.C, a.n, a.nh, nseg,
+           FIRST ? (const unsigned*)nullptr : (const unsigned*)a.more, FIRST ? a.rec : a.rec2, kind_sel);
+    return MCR_OK;
+}
+
 // Tiers 1 and 2 of one kind (0 bulk, 1 folded) or of both (kind_sel < 0): segment products, combine, the flagged pairs'
 // lags 64..255 -- everything of the diagnostics that does not need the other kind.  On ctx->stream.
 int launch_diag_front(mcr_ctx* ctx, const PipeIn& a, int kind_sel)
@@ -476,31 +495,15 @@ int launch_diag_front(mcr_ctx* ctx, const PipeIn& a, int kind_sel)
     const bool small = a.nstage <= 1024;
     const int seg = small ? 1024 : kSeg;
     const int nseg = (int)((a.nstage + seg - 1) / seg);
-    const unsigned pk = (unsigned)((kind_sel < 0 ? 2 : 1) * a.pc), ky = kind_sel < 0 ? 2u : 1u;
-    if (small) {
-        LAUNCH(ctx, K_ACOV_SEG, (k_acov_seg<128, 1024, true>), dim3((unsigned)nseg, (unsigned)a.C, pk), dim3(128), 0,
-               (const u32*)a.zb, (const u32*)a.zt, (const double*)a.ztab, a.M, a.d_off, a.C, a.n, a.nh, nseg,
-               (const unsigned*)nullptr, a.rec, kind_sel);
-    } else {
-        LAUNCH(ctx, K_ACOV_SEG, (k_acov_seg<256, kSeg, true>), dim3((unsigned)nseg, (unsigned)a.C, pk), dim3(256), 0,
-               (const u32*)a.zb, (const u32*)a.zt, (const double*)a.ztab, a.M, a.d_off, a.C, a.n, a.nh, nseg,
-               (const unsigned*)nullptr, a.rec, kind_sel);
-    }
+    const unsigned ky = kind_sel < 0 ? 2u : 1u;
+    int rc = small ? launch_acov_seg<128, 1024, true>(ctx, a, nseg, kind_sel) : launch_acov_seg<256, kSeg, true>(ctx, a, nseg, kind_sel);
+    if (rc) return rc;
     LAUNCH(ctx, K_DIAG, k_diag_combine, dim3((unsigned)a.pc, ky), dim3(64u * (unsigned)(a.C < kCombineWaves ? a.C : kCombineWaves)), (size_t)6 * a.C * 8, (const u32*)a.zb,
            (const u32*)a.zt, (const double*)a.ztab, a.M, a.d_off, a.C, a.n, a.nh, nseg, (const double*)a.rec, a.d_res, a.pc, a.more, a.state, a.chstate,
            a.long_count, a.t3c,
            ctx->rho_band, ctx->guard_count, kind_sel);
     // tier 2 for pairs whose first negative rho lies beyond lag 63 (others exit at once)
-    if (small) {
-        LAUNCH(ctx, K_ACOV_MORE, (k_acov_seg<128, 1024, false>), dim3((unsigned)nseg, (unsigned)a.C, pk), dim3(128), 0,
-               (const u32*)a.zb, (const u32*)a.zt, (const double*)a.ztab, a.M, a.d_off, a.C, a.n, a.nh, nseg,
-               (const unsigned*)a.more, a.rec2, kind_sel);
-    } else {
-        LAUNCH(ctx, K_ACOV_MORE, (k_acov_seg<256, kSeg, false>), dim3((unsigned)nseg, (unsigned)a.C, pk), dim3(256), 0,
-               (const u32*)a.zb, (const u32*)a.zt, (const double*)a.ztab, a.M, a.d_off, a.C, a.n, a.nh, nseg,
-               (const unsigned*)a.more, a.rec2, kind_sel);
-    }
-    return MCR_OK;
+    return small ? launch_acov_seg<128, 1024, false>(ctx, a, nseg, kind_sel) : launch_acov_seg<256, kSeg, false>(ctx, a, nseg, kind_sel);
 }
 
 // Split R-hat + ESS (mcr_diag.hpp): the joint part -- tier 2's combine (+ finalize), tier 3.
@@ -606,13 +609,19 @@ int launch_splitters(mcr_ctx* ctx, const PipeIn& a, const KT* keys)
     return launch_splitters_v<KT, 8>(ctx, a, keys);       // (MVT must divide the runs' 64 j samples: a thread's outputs never straddle two pairs of runs)
 }
 
-// Tile sort + (bucket partition | merge passes): leaves the pooled ascending (key, idx) order of every
-// parameter in *kin / *iin (one of the two ping-pong sets) and, on the bucket path with do_diag, z_bulk.
-// (TNT, TVT): threads x draws per lane of the tile sort; (MNT, MVT): of the merge kernels (bucket merge, fold, passes).
-template <typename IdxT, int TNT, int TVT, int MNT, int MVT>
-int sort_stage_t(mcr_ctx* ctx, PipeIn& a, double** kin_o, void** iin_o, double** kout_o, void** iout_o, bool* ranked_o)
+// What the sort stage leaves: the ascending (key, position) order of every parameter in one of the two ping-pong buffer
+// pairs, the other pair free, and whether the bulk rank codes z_bulk are written already (bucket path with do_diag).
+// On the f32 records path the keys are packed (key, position) records and the positions are unused.
+struct Sorted {
+    double* keys; void* pos;
+    double* keys_free; void* pos_free;
+    bool ranked;
+};
+
+// Tile sort + (bucket partition | merge passes).
+template <typename IdxT>
+int sort_stage_t(mcr_ctx* ctx, PipeIn& a, Sorted& out)
 {
-    static_assert(TNT * TVT == kTile && MNT * MVT == kTile, "tile geometry");
     const i64 M = a.M, pc = a.pc;
     const unsigned py = (unsigned)pc;
     constexpr size_t lds_tile = sort_lds_bytes<IdxT>(kTile);
@@ -621,20 +630,19 @@ int sort_stage_t(mcr_ctx* ctx, PipeIn& a, double** kin_o, void** iin_o, double**
     const bool bucket = a.bk_B > 0;
     double* const samp1 = (bucket && a.bk_R == kTile) ? a.samp : (double*)nullptr;
     if (a.x_f32) {
-        LAUNCH(ctx, K_TILE_SORT, (k_tile_sort<TNT, TVT, IdxT, float>), dim3((unsigned)a.ntiles, py), dim3(TNT),
+        LAUNCH(ctx, K_TILE_SORT, (k_tile_sort<kTileNT, kTileVT, IdxT, float>), dim3((unsigned)a.ntiles, py), dim3(kTileNT),
                lds_tile, (const float*)a.X, M, a.kA, (IdxT*)a.iA, a.part, (int)a.ntiles, samp1);
     } else {
-        LAUNCH(ctx, K_TILE_SORT, (k_tile_sort<TNT, TVT, IdxT, double>), dim3((unsigned)a.ntiles, py), dim3(TNT),
-               lds_tile + ctx->dbg_lds_pad[0], (const double*)a.X, M, a.kA, (IdxT*)a.iA, a.part, (int)a.ntiles, samp1);
+        LAUNCH(ctx, K_TILE_SORT, (k_tile_sort<kTileNT, kTileVT, IdxT, double>), dim3((unsigned)a.ntiles, py), dim3(kTileNT),
+               lds_tile, (const double*)a.X, M, a.kA, (IdxT*)a.iA, a.part, (int)a.ntiles, samp1);
     }
     double *kin = a.kA, *kout = a.kB;
     IdxT *iin = (IdxT*)a.iA, *iout = (IdxT*)a.iB;
     const unsigned nblk = (unsigned)((M + kTile - 1) / kTile);
-    bool ranked = false;
     // 2. pairwise merge-path passes: up to the run length of the bucket partition, or all the way
     const i64 Rstop = bucket ? a.bk_R : M;
     for (i64 R = kTile; R < Rstop; R *= 2) {
-        LAUNCH(ctx, K_MERGE, (k_merge<MNT, MVT, false, IdxT>), dim3(nblk, py), dim3(MNT), lds_tile + 256,
+        LAUNCH(ctx, K_MERGE, (k_merge<kMergeNT, kMergeVT, false, IdxT>), dim3(nblk, py), dim3(kMergeNT), lds_tile + 256,
                (const double*)kin, (const IdxT*)iin, kout, iout, M, R, (double*)nullptr, pc,
                QArgs{}, (u32*)nullptr, (const i64*)nullptr);
         std::swap(kin, kout);
@@ -650,54 +658,29 @@ int sort_stage_t(mcr_ctx* ctx, PipeIn& a, double** kin_o, void** iin_o, double**
             if (rc) return rc;
         }
         const unsigned pgrp = (unsigned)((pc + 7) / 8 * 8);   // XCD-aware 1-D grid (xcd_map)
-        LAUNCH(ctx, K_BUCKET_MERGE, (k_bucket_merge<MNT, MVT, IdxT>), dim3(pgrp * (unsigned)a.bk_B), dim3(MNT), lds_tile + ctx->dbg_lds_pad[1],
-               (const double*)kin, (const IdxT*)iin, kout, iout, M, a.bk_k, a.bk_B, (const u32*)a.cut,
+        LAUNCH(ctx, K_BUCKET_MERGE, (k_bucket_merge<kMergeNT, kMergeVT, IdxT>), dim3(pgrp * (unsigned)a.bk_B), dim3(kMergeNT),
+               lds_tile, (const double*)kin, (const IdxT*)iin, kout, iout, M, a.bk_k, a.bk_B, (const u32*)a.cut,
                (const u32*)a.boff, a.do_diag ? a.zb : (u32*)nullptr, pc, a.bk_R);
         std::swap(kin, kout);
         std::swap(iin, iout);
-        ranked = true;
     }
-    *kin_o = kin; *iin_o = iin; *kout_o = kout; *iout_o = iout; *ranked_o = ranked;
-    return MCR_OK;
-}
-
-// Order statistics by the fold kernel's own workgroups (a launch less) while a parameter has few of them; a pooled
-// array beyond 16-bit positions has a hundred fold workgroups per parameter, and one k_order_stats launch serves them.
-inline bool order_stats_in_fold(const PipeIn& a) { return a.do_diag && a.M <= kIdx16Max; }
-inline const i64* fold_split(const PipeIn& a) { return order_stats_in_fold(a) ? (const i64*)nullptr : (const i64*)a.split; }
-
-template <typename IdxT, int NT, int VT>
-int launch_fold_rec(mcr_ctx* ctx, PipeIn& a, double* kin, unsigned fgrid)
-{
-    LAUNCH(ctx, K_FOLD_MERGE, (k_merge<NT, VT, true, IdxT, u64>), dim3(fgrid), dim3(NT), sort_lds_bytes<IdxT>(kTile),
-           (const u64*)kin, (const IdxT*)nullptr, (double*)nullptr, (IdxT*)nullptr, a.M, (i64)0, a.d_res, a.pc,
-           a.q, a.zt, fold_split(a));
-    return MCR_OK;
-}
-
-template <typename IdxT, int NT, int VT>
-int launch_fold(mcr_ctx* ctx, PipeIn& a, double* kin, void* iin, double* kout, void* iout, unsigned fgrid)
-{
-    LAUNCH(ctx, K_FOLD_MERGE, (k_merge<NT, VT, true, IdxT>), dim3(fgrid), dim3(NT), sort_lds_bytes<IdxT>(kTile) + ctx->dbg_lds_pad[2],
-           (const double*)kin, (const IdxT*)iin, kout, (IdxT*)iout, a.M, (i64)0, a.d_res, a.pc,
-           a.q, a.zt, fold_split(a));
+    out = Sorted{kin, iin, kout, iout, bucket};
     return MCR_OK;
 }
 
 // f32 tensors (Arrow layout, bucket path): the same stage on packed (key, position) records (mcr_sort32.hpp).  The
 // record arrays live in the f64 key buffers kA / kB (8 bytes per draw); the position buffers stay unused.
-template <int TNT, int TVT, int MNT, int MVT>
-int sort_stage_rec(mcr_ctx* ctx, PipeIn& a, double** kin_o, void** iin_o, double** kout_o, void** iout_o, bool* ranked_o)
+int sort_stage_rec(mcr_ctx* ctx, PipeIn& a, Sorted& out)
 {
-    static_assert(TNT * TVT == kTile && MNT * MVT == kTile, "tile geometry");
     const i64 M = a.M, pc = a.pc;
     const unsigned py = (unsigned)pc;
     u64 *rin = reinterpret_cast<u64*>(a.kA), *rout = reinterpret_cast<u64*>(a.kB);
-    LAUNCH(ctx, K_TILE_SORT, (k_tile_sort32<TNT, TVT>), dim3((unsigned)a.ntiles, py), dim3(TNT), (size_t)kTile * 8,
+    LAUNCH(ctx, K_TILE_SORT, (k_tile_sort32<kTileNT, kTileVT>), dim3((unsigned)a.ntiles, py), dim3(kTileNT), (size_t)kTile * 8,
            (const float*)a.X, M, rin, a.part, (int)a.ntiles, (a.bk_R == kTile) ? a.samp : (double*)nullptr);
     const unsigned nblk = (unsigned)((M + kTile - 1) / kTile);
     for (i64 R = kTile; R < a.bk_R; R *= 2) {
-        LAUNCH(ctx, K_MERGE, (k_merge32<MNT, MVT>), dim3(nblk, py), dim3(MNT), rec_lds_bytes(kTile), (const u64*)rin, rout, M, R);
+        LAUNCH(ctx, K_MERGE, (k_merge32<kMergeNT, kMergeVT>), dim3(nblk, py), dim3(kMergeNT), rec_lds_bytes(kTile),
+               (const u64*)rin, rout, M, R);
         std::swap(rin, rout);
     }
     if (a.bk_R != kTile)
@@ -707,69 +690,40 @@ int sort_stage_rec(mcr_ctx* ctx, PipeIn& a, double** kin_o, void** iin_o, double
         if (rc) return rc;
     }
     const unsigned pgrp = (unsigned)((pc + 7) / 8 * 8);
-    LAUNCH(ctx, K_BUCKET_MERGE, (k_bucket_merge32<MNT, MVT>), dim3(pgrp * (unsigned)a.bk_B), dim3(MNT), rec_lds_bytes(kTile) + 512,
-           (const u64*)rin, rout, M, a.bk_k, a.bk_B, (const u32*)a.cut, (const u32*)a.boff,
+    LAUNCH(ctx, K_BUCKET_MERGE, (k_bucket_merge32<kMergeNT, kMergeVT>), dim3(pgrp * (unsigned)a.bk_B), dim3(kMergeNT),
+           rec_lds_bytes(kTile) + 512, (const u64*)rin, rout, M, a.bk_k, a.bk_B, (const u32*)a.cut, (const u32*)a.boff,
            a.do_diag ? a.zb : (u32*)nullptr, pc, a.bk_R);
-    std::swap(rin, rout);
-    *kin_o = reinterpret_cast<double*>(rin); *kout_o = reinterpret_cast<double*>(rout);
-    *iin_o = a.iA; *iout_o = a.iB; *ranked_o = true;
+    out = Sorted{reinterpret_cast<double*>(rout), a.iA, reinterpret_cast<double*>(rin), a.iB, true};
     return MCR_OK;
 }
 
-int sort_stage_rec_i(mcr_ctx* ctx, PipeIn& a, double** kin_o, void** iin_o, double** kout_o, void** iout_o, bool* ranked_o)
+int sort_stage(mcr_ctx* ctx, PipeIn& a, Sorted& out)
 {
-    const int t = ctx->sort_cfg % 10, m = ctx->sort_cfg / 10;
-    if (t == 0) {
-        if (m == 0) return sort_stage_rec<256, 16, 256, 16>(ctx, a, kin_o, iin_o, kout_o, iout_o, ranked_o);
-        if (m == 1) return sort_stage_rec<256, 16, 512, 8>(ctx, a, kin_o, iin_o, kout_o, iout_o, ranked_o);
-        return sort_stage_rec<256, 16, 1024, 4>(ctx, a, kin_o, iin_o, kout_o, iout_o, ranked_o);
-    }
-    if (m == 0) return sort_stage_rec<512, 8, 256, 16>(ctx, a, kin_o, iin_o, kout_o, iout_o, ranked_o);
-    if (m == 1) return sort_stage_rec<512, 8, 512, 8>(ctx, a, kin_o, iin_o, kout_o, iout_o, ranked_o);
-    return sort_stage_rec<512, 8, 1024, 4>(ctx, a, kin_o, iin_o, kout_o, iout_o, ranked_o);
+    if (a.records) return sort_stage_rec(ctx, a, out);
+    return a.idx16 ? sort_stage_t<unsigned short>(ctx, a, out) : sort_stage_t<u32>(ctx, a, out);
 }
 
-// MCR_SORT_CFG = tile + 10 * merge.  tile: 0 = 256 lanes x 16 draws, 1 = 512 x 8.  merge: 0 = 256 x 16, 1 = 512 x 8,
-// 2 = 1024 x 4.  Measured on C1 (profiles/r02_*): the tile sort is fastest with long per-lane runs (the register
-// network does four levels for free), the merge kernels with short ones (twice the waves per CU hide the dependent
-// LDS chains of the serial merge, which has no register phase to amortise).
+// Order statistics by the fold kernel's own workgroups (a launch less) while a parameter has few of them; a pooled
+// array beyond 16-bit positions has a hundred fold workgroups per parameter, and one k_order_stats launch serves them.
+inline bool order_stats_in_fold(const PipeIn& a) { return a.do_diag && a.idx16; }
+
+// Fold: one merge of the two monotone halves around the median, fused with ranks -> z (and the order statistics).
+// The records fold takes the LDS of the position width all the same.
 template <typename IdxT>
-int sort_stage_i(mcr_ctx* ctx, PipeIn& a, double** kin_o, void** iin_o, double** kout_o, void** iout_o, bool* ranked_o)
+int launch_fold(mcr_ctx* ctx, const PipeIn& a, const Sorted& s)
 {
-    const int t = ctx->sort_cfg % 10, m = ctx->sort_cfg / 10;
-    if (t == 0) {
-        if (m == 0) return sort_stage_t<IdxT, 256, 16, 256, 16>(ctx, a, kin_o, iin_o, kout_o, iout_o, ranked_o);
-        if (m == 1) return sort_stage_t<IdxT, 256, 16, 512, 8>(ctx, a, kin_o, iin_o, kout_o, iout_o, ranked_o);
-        return sort_stage_t<IdxT, 256, 16, 1024, 4>(ctx, a, kin_o, iin_o, kout_o, iout_o, ranked_o);
+    const unsigned fgrid = (unsigned)((a.pc + 7) / 8 * 8) * (unsigned)((a.M + (kTile - 64) - 1) / (kTile - 64));   // 4032 outputs per fold workgroup
+    const i64* split = order_stats_in_fold(a) ? (const i64*)nullptr : (const i64*)a.split;
+    if (a.records) {
+        LAUNCH(ctx, K_FOLD_MERGE, (k_merge<kMergeNT, kMergeVT, true, IdxT, u64>), dim3(fgrid), dim3(kMergeNT),
+               sort_lds_bytes<IdxT>(kTile), (const u64*)s.keys, (const IdxT*)nullptr, (double*)nullptr, (IdxT*)nullptr, a.M,
+               (i64)0, a.d_res, a.pc, a.q, a.zt, split);
+    } else {
+        LAUNCH(ctx, K_FOLD_MERGE, (k_merge<kMergeNT, kMergeVT, true, IdxT>), dim3(fgrid), dim3(kMergeNT),
+               sort_lds_bytes<IdxT>(kTile), (const double*)s.keys, (const IdxT*)s.pos, s.keys_free, (IdxT*)s.pos_free, a.M,
+               (i64)0, a.d_res, a.pc, a.q, a.zt, split);
     }
-    if (m == 0) return sort_stage_t<IdxT, 512, 8, 256, 16>(ctx, a, kin_o, iin_o, kout_o, iout_o, ranked_o);
-    if (m == 1) return sort_stage_t<IdxT, 512, 8, 512, 8>(ctx, a, kin_o, iin_o, kout_o, iout_o, ranked_o);
-    return sort_stage_t<IdxT, 512, 8, 1024, 4>(ctx, a, kin_o, iin_o, kout_o, iout_o, ranked_o);
-}
-
-// Records are used for f32 tensors whenever the bucket partition applies (pooled arrays up to 512 K draws); beyond
-// that the tile sort widens the f32 draws itself and the f64 kernels run.
-inline bool use_records(const PipeIn& a) { return a.x_f32 && a.bk_B > 0 && !a.no_records; }
-
-int sort_stage(mcr_ctx* ctx, PipeIn& a, double** kin_o, void** iin_o, double** kout_o, void** iout_o, bool* ranked_o)
-{
-    if (use_records(a)) return sort_stage_rec_i(ctx, a, kin_o, iin_o, kout_o, iout_o, ranked_o);
-    return a.M <= kIdx16Max ? sort_stage_i<unsigned short>(ctx, a, kin_o, iin_o, kout_o, iout_o, ranked_o)
-                            : sort_stage_i<u32>(ctx, a, kin_o, iin_o, kout_o, iout_o, ranked_o);
-}
-
-template <typename IdxT>
-int fold_stage_i(mcr_ctx* ctx, PipeIn& a, double* kin, void* iin, double* kout, void* iout, unsigned fgrid)
-{
-    const int m = ctx->sort_cfg / 10;
-    if (use_records(a)) {
-        if (m == 0) return launch_fold_rec<IdxT, 256, 16>(ctx, a, kin, fgrid);
-        if (m == 1) return launch_fold_rec<IdxT, 512, 8>(ctx, a, kin, fgrid);
-        return launch_fold_rec<IdxT, 1024, 4>(ctx, a, kin, fgrid);
-    }
-    if (m == 0) return launch_fold<IdxT, 256, 16>(ctx, a, kin, iin, kout, iout, fgrid);
-    if (m == 1) return launch_fold<IdxT, 512, 8>(ctx, a, kin, iin, kout, iout, fgrid);
-    return launch_fold<IdxT, 1024, 4>(ctx, a, kin, iin, kout, iout, fgrid);
+    return MCR_OK;
 }
 
 // The whole per-chunk pipeline on ctx->stream.  M >= 1, pc >= 1.
@@ -777,28 +731,26 @@ int run_pipeline(mcr_ctx* ctx, PipeIn& a)
 {
     const i64 M = a.M, pc = a.pc;
     const unsigned py = (unsigned)pc;
-    double *kin, *kout;
-    void *iin, *iout;
-    bool ranked;
+    Sorted so;
     {
-        const int rc = sort_stage(ctx, a, &kin, &iin, &kout, &iout, &ranked);
+        const int rc = sort_stage(ctx, a, so);
         if (rc) return rc;
     }
     // 3. order statistics: with diagnostics, by the fold kernel itself; a launch of their own for Backend.stats calls
     if (!order_stats_in_fold(a)) {
-        if (use_records(a)) {
+        if (a.records) {
             LAUNCH(ctx, K_ORDER_STATS, k_order_stats<u64>, dim3((unsigned)((pc + 3) / 4)), dim3(256), 0,
-                   (const u64*)kin, M, pc, a.q, a.d_res, a.split);
+                   (const u64*)so.keys, M, pc, a.q, a.d_res, a.split);
         } else {
             LAUNCH(ctx, K_ORDER_STATS, k_order_stats<double>, dim3((unsigned)((pc + 3) / 4)), dim3(256), 0,
-                   (const double*)kin, M, pc, a.q, a.d_res, a.split);
+                   (const double*)so.keys, M, pc, a.q, a.d_res, a.split);
         }
     }
     if (a.do_diag) {
         // 4. bulk ranks -> z (already done by k_bucket_merge on the bucket path)
-        if (!ranked)
+        if (!so.ranked)
             LAUNCH(ctx, K_RANK_Z, k_rank_z, dim3((unsigned)((M + 255) / 256), py), dim3(256), 0,
-                   (const double*)kin, (const u32*)iin, M, a.zb);       // no bucket path only beyond 512 K draws: u32 positions
+                   (const double*)so.keys, (const u32*)so.pos, M, a.zb);       // no bucket path only beyond 512 K draws: u32 positions
         // A LONE call (nothing else in flight on the context: what reference.compare makes) forks here: the bulk half of
         // tiers 1 and 2 needs only the bulk rank codes, which exist now, so it runs on the lane's second stream UNDER the fold
         // kernel, and the two halves join in front of combine2 -- ~35 us off the critical path of a 0.3 ms call.  A pipelined
@@ -815,10 +767,8 @@ int run_pipeline(mcr_ctx* ctx, PipeIn& a)
             HIP_TRY(ctx, hipEventRecord(ctx->lane_join[ctx->lane], ctx->lane_aux[ctx->lane]));
         }
         // 5+6. fold: one merge of the two monotone halves around the median, fused with ranks -> z
-        const unsigned fgrid = (unsigned)((pc + 7) / 8 * 8) * (unsigned)((M + (kTile - 64) - 1) / (kTile - 64));   // 4032 outputs per fold workgroup
         {
-            const int rc = M <= kIdx16Max ? fold_stage_i<unsigned short>(ctx, a, kin, iin, kout, iout, fgrid)
-                                          : fold_stage_i<u32>(ctx, a, kin, iin, kout, iout, fgrid);
+            const int rc = a.idx16 ? launch_fold<unsigned short>(ctx, a, so) : launch_fold<u32>(ctx, a, so);
             if (rc) return rc;
         }
         // 7. R-hat + ESS (+ the finalize step, inside k_diag_combine2)
@@ -1044,7 +994,7 @@ int enqueue_impl(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i
                     a.X = X;
                 } else {
                     a.x_f32 = dtype == MCR_F32;
-                    a.no_records = !ctx->f32_records;
+                    a.records = a.x_f32 && a.bk_B > 0 && ctx->f32_records;
                     a.X = a.x_f32 ? (const void*)(reinterpret_cast<const float*>(draws_dev) + p0 * M)
                                   : (const void*)(reinterpret_cast<const double*>(draws_dev) + p0 * M);
                 }
@@ -1271,20 +1221,12 @@ int mcr_init(int device, mcr_ctx** out)
     if (const char* env = getenv("MCR_SPLITTERS_PAIRWISE")) ctx->splitters_pairwise = atoi(env) != 0;
     if (const char* env = getenv("MCR_FORK")) ctx->fork_lone = atoi(env) != 0;
     if (const char* env = getenv("MCR_T3_WG")) { const int v = atoi(env); if (v > 0) ctx->t3_workgroups = v; }
-    if (const char* env = getenv("MCR_DBG_LDS_PAD")) {
-        unsigned long t = 0, b = 0, f = 0;
-        if (sscanf(env, "%lu,%lu,%lu", &t, &b, &f) >= 1) { ctx->dbg_lds_pad[0] = t; ctx->dbg_lds_pad[1] = b; ctx->dbg_lds_pad[2] = f; }
-    }
     if (const char* env = getenv("MCR_RHO_BAND")) { const double v = atof(env); if (v >= 0.0 && v < 1.0) ctx->rho_band = v; }
     if (hipMalloc((void**)&ctx->guard_count, sizeof(unsigned)) != hipSuccess ||
         hipMemsetAsync(ctx->guard_count, 0, sizeof(unsigned), ctx->stream) != hipSuccess ||
         hipStreamSynchronize(ctx->stream) != hipSuccess) {
         mcr_free(ctx);
         return fail(nullptr, MCR_ENOMEM, "device %d: cannot allocate the guard counter", device);
-    }
-    if (const char* env = getenv("MCR_SORT_CFG")) {
-        const int v = atoi(env);
-        if (v >= 0 && v % 10 <= 1 && v / 10 <= 2) ctx->sort_cfg = v;
     }
     *out = ctx;
     return MCR_OK;
@@ -1707,20 +1649,20 @@ int mcr_two_sample(mcr_ctx* ctx, const double* ref, int64_t Mr, const double* ac
     if (rc) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(Xr, ref, sizeof(double) * (size_t)P * Mr, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(Xa, act, sizeof(double) * (size_t)P * Ma, hipMemcpyHostToDevice, ctx->stream));
-    double *kin, *kout; void *iin, *iout; bool ranked;
+    Sorted so;
     ar.X = Xr;                    // ascending order of the reference sample, parked in Sr
-    rc = sort_stage(ctx, ar, &kin, &iin, &kout, &iout, &ranked);
+    rc = sort_stage(ctx, ar, so);
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(Sr, kin, sizeof(double) * (size_t)P * Mr, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(Sr, so.keys, sizeof(double) * (size_t)P * Mr, hipMemcpyDeviceToDevice, ctx->stream));
     hipLaunchKernelGGL(k_bad_count, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)ar.part,
                        (int)ar.ntiles, (i64)P, bad);
     aa.X = Xa;                    // ascending order of the actual sample, then one merge-path pass over both
-    rc = sort_stage(ctx, aa, &kin, &iin, &kout, &iout, &ranked);
+    rc = sort_stage(ctx, aa, so);
     if (rc) return rc;
     hipLaunchKernelGGL(k_bad_count, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)aa.part,
                        (int)aa.ntiles, (i64)P, bad + P);
     LAUNCH(ctx, K_TWO_SAMPLE, (k_two_sample<256, 16>), dim3((unsigned)nblk, (unsigned)P), dim3(256), 0,
-           (const double*)Sr, (i64)Mr, (const double*)kin, (i64)Ma, part, nblk);
+           (const double*)Sr, (i64)Mr, (const double*)so.keys, (i64)Ma, part, nblk);
     LAUNCH(ctx, K_TWO_SAMPLE, k_two_sample_final, dim3((unsigned)((P + 255) / 256)), dim3(256), 0,
            (const double*)part, nblk, (i64)P, (double)Mr * (double)Ma, d_ks, d_w);
     HIP_TRY(ctx, hipMemcpyAsync(ks, d_ks, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, ctx->stream));
