@@ -59,26 +59,21 @@ const char* const kKernelNames[K_COUNT] = {
 
 struct EvPair { hipEvent_t a, b; int kid; };
 
-struct Chunk { i64 p0, pc; size_t res_off; };
-
 struct Slot {
-    bool busy = false;
     double* d_res = nullptr; double* h_res = nullptr; size_t res_cap = 0;   // doubles
     i64* d_off = nullptr; i64* h_off = nullptr; size_t off_cap = 0;          // entries
     i64 off_C = -1, off_N = -1;     // regular chain offsets c * N already resident in d_off (no upload per call)
     mcr_summary out{};
-    i64 P = 0, M = 0; int nq = 0; int C = 0;
+    i64 P = 0; int nq = 0;
     bool trivial_nan = false;  // M == 0: no kernels ran
     hipEvent_t done = nullptr;  // recorded on the slot's lane after its last copy (mcr_summarize_wait_one)
-    int lane = 0;
     i64 qlo[MCR_MAX_QUANTILES];
-    std::vector<Chunk> chunks;
+    i64 pcmax = 0;             // parameters per workspace chunk: chunk k has the results of [k pcmax, (k + 1) pcmax)
 };
 
 struct GraphEntry {
     std::vector<uint64_t> key;
     hipGraphExec_t exec = nullptr;
-    std::vector<Chunk> chunks;
 };
 
 char g_init_err[512] = "";
@@ -118,8 +113,8 @@ struct mcr_ctx {
     struct Twiddle { int L; double2* tab; };          // exp(-2 pi i t / L), t < L / 2, per sub-transform length (mcr_fft.hpp)
     std::vector<Twiddle> twiddles;
     Slot slots[MCR_MAX_INFLIGHT];
-    int n_inflight = 0, next_slot = 0;
-    std::vector<int> order;  // busy slots in enqueue order
+    int next_slot = 0;
+    std::vector<int> order;  // busy slots in enqueue order (the summaries in flight)
     bool prof = false;
     std::vector<EvPair> pending;
     std::vector<hipEvent_t> free_ev;
@@ -839,20 +834,20 @@ int unpack_slot(mcr_ctx* ctx, Slot& s)
     if (o.q_lo) for (int k = 0; k < s.nq; ++k) o.q_lo[k] = s.qlo[k];
     if (s.trivial_nan) { fill_nan(o, s.P, s.nq); return MCR_OK; }
     double nbad = 0.0;
-    for (const Chunk& ch : s.chunks) {
-        const double* r = s.h_res + ch.res_off;
-        const i64 pc = ch.pc;
+    for (i64 p0 = 0; p0 < s.P; p0 += s.pcmax) {
+        const i64 pc = s.P - p0 < s.pcmax ? s.P - p0 : s.pcmax;
+        const double* r = s.h_res + (size_t)res_fields(s.nq) * (size_t)p0;
         auto cp = [&](double* dst, int field) {
-            if (dst) memcpy(dst + ch.p0, r + (size_t)field * pc, sizeof(double) * (size_t)pc);
+            if (dst) memcpy(dst + p0, r + (size_t)field * pc, sizeof(double) * (size_t)pc);
         };
         cp(o.mean, R_MEAN); cp(o.std, R_STD); cp(o.median, R_MEDIAN); cp(o.rhat, R_RHAT);
         cp(o.rhat_bulk, R_RHAT_BULK); cp(o.rhat_tail, R_RHAT_TAIL); cp(o.ess_bulk, R_ESS_BULK);
         cp(o.ess_tail, R_ESS_TAIL);
         for (i64 p = 0; p < pc; ++p) {
-            if (o.lag_bulk) o.lag_bulk[ch.p0 + p] = (int64_t)r[(size_t)R_LAG_BULK * pc + p];
-            if (o.lag_tail) o.lag_tail[ch.p0 + p] = (int64_t)r[(size_t)R_LAG_TAIL * pc + p];
+            if (o.lag_bulk) o.lag_bulk[p0 + p] = (int64_t)r[(size_t)R_LAG_BULK * pc + p];
+            if (o.lag_tail) o.lag_tail[p0 + p] = (int64_t)r[(size_t)R_LAG_TAIL * pc + p];
             nbad += r[(size_t)R_BAD * pc + p];
-            if (o.q) for (int k = 0; k < s.nq; ++k) o.q[(ch.p0 + p) * s.nq + k] = r[(size_t)(R_Q0 + k) * pc + p];
+            if (o.q) for (int k = 0; k < s.nq; ++k) o.q[(p0 + p) * s.nq + k] = r[(size_t)(R_Q0 + k) * pc + p];
         }
     }
     if (nbad > 0.0) return fail(ctx, MCR_ENONFINITE, "draws contain %.0f non-finite value(s)", nbad);
@@ -920,42 +915,57 @@ int plan_chunks(mcr_ctx* ctx, i64 C, i64 N, i64 P, i64 sc, i64 sn, i64 sp, bool 
     return MCR_OK;
 }
 
+// The call-wide tables of a pipeline, from the context's caches: the FFT tier's twiddles (fp.on), the z table (ztab).
+int get_tables(mcr_ctx* ctx, PipeIn& a, const FftPlan& fp, bool ztab)
+{
+    int rc = fp.on ? get_twiddles(ctx, 1 << fp.log1, &a.tw1) : MCR_OK;
+    if (!rc && fp.on) rc = get_twiddles(ctx, 1 << fp.log2, &a.tw2);
+    return (!rc && ztab) ? get_ztab(ctx, a.M, &a.ztab) : rc;
+}
+
+// A result slot's lifecycle: fill_slot describes the call it serves (the caller picks slot and lane), commit_slot records
+// its completion event behind the call's work on the current lane and puts it in flight.
+Slot& fill_slot(mcr_ctx* ctx, int si, const mcr_summary* out, i64 P, i64 M, int nq)
+{
+    Slot& s = ctx->slots[si];
+    s.out = *out; s.P = P; s.nq = nq; s.trivial_nan = (M == 0 || P == 0);
+    s.pcmax = P;
+    return s;
+}
+int commit_slot(mcr_ctx* ctx, int si)
+{
+    Slot& s = ctx->slots[si];
+    if (!s.done) HIP_TRY(ctx, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+    HIP_TRY(ctx, hipEventRecord(s.done, ctx->stream));
+    ctx->order.push_back(si);
+    return MCR_OK;
+}
+
 int enqueue_impl(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i64 P, i64 sc, i64 sn, i64 sp,
                  int min_chains, const double* quantiles, int nq, const mcr_summary* out)
 {
     int rc = check_common(ctx, draws_dev, dtype, C, N, P, min_chains, out);
     if (rc) return rc;
-    if (ctx->n_inflight >= MCR_MAX_INFLIGHT) return fail(ctx, MCR_EINVAL, "more than %d summaries in flight", MCR_MAX_INFLIGHT);
+    if (ctx->order.size() >= MCR_MAX_INFLIGHT) return fail(ctx, MCR_EINVAL, "more than %d summaries in flight", MCR_MAX_INFLIGHT);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const i64 M = C * N;
     int si = -1;
     for (int k = 0; k < MCR_MAX_INFLIGHT; ++k) {
         const int c = (ctx->next_slot + k) % MCR_MAX_INFLIGHT;
-        if (!ctx->slots[c].busy) { si = c; break; }
+        if (std::find(ctx->order.begin(), ctx->order.end(), c) == ctx->order.end()) { si = c; break; }
     }
-    Slot& s = ctx->slots[si];
     QArgs q;
-    rc = prep_quantiles(ctx, quantiles, nq, M, q, s.qlo);
+    rc = prep_quantiles(ctx, quantiles, nq, M, q, ctx->slots[si].qlo);
     if (rc) return rc;
     use_lane(ctx, si % ctx->n_lanes);
-    s.out = *out; s.P = P; s.M = M; s.nq = nq; s.C = (int)C;
-    s.chunks.clear();
-    s.trivial_nan = (M == 0 || P == 0);
+    Slot& s = fill_slot(ctx, si, out, P, M, nq);
     if (!s.trivial_nan) {
-        const bool do_diag_early = out->rhat || out->rhat_bulk || out->rhat_tail || out->ess_bulk || out->ess_tail ||
-                                   out->lag_bulk || out->lag_tail;
+        const bool do_diag = out->rhat || out->rhat_bulk || out->rhat_tail || out->ess_bulk || out->ess_tail ||
+                             out->lag_bulk || out->lag_tail;
         ChunkPlan cp;
-        rc = plan_chunks(ctx, C, N, P, sc, sn, sp, do_diag_early, cp);
+        rc = plan_chunks(ctx, C, N, P, sc, sn, sp, do_diag, cp);
         if (rc) return rc;
-        const bool ingest = cp.ingest;
-        const FftPlan& fp = cp.fp;
-        const i64 pcmax = cp.pcmax;
-        double2 *tw1 = nullptr, *tw2 = nullptr;
-        if (fp.on) {
-            rc = get_twiddles(ctx, 1 << fp.log1, &tw1);
-            if (!rc) rc = get_twiddles(ctx, 1 << fp.log2, &tw2);
-            if (rc) return rc;
-        }
+        const i64 pcmax = s.pcmax = cp.pcmax;
         rc = ensure_ws(ctx, cp.bytes);
         if (rc) return rc;
         const int R = res_fields(nq);
@@ -963,10 +973,11 @@ int enqueue_impl(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i
         if (rc) return rc;
         const bool off_resident = s.off_C == C && s.off_N == N;
         if (!off_resident) for (i64 c = 0; c <= C; ++c) s.h_off[c] = c * N;
-        const bool do_diag = out->rhat || out->rhat_bulk || out->rhat_tail || out->ess_bulk || out->ess_tail ||
-                             out->lag_bulk || out->lag_tail;
-        double* ztab = nullptr;
-        if (do_diag) { rc = get_ztab(ctx, M, &ztab); if (rc) return rc; }
+        PipeIn call{};                  // the fields every chunk shares
+        call.M = M; call.C = (int)C; call.d_off = s.d_off; call.n = N; call.nh = (N >= 2) ? N / 2 : 0; call.q = q;
+        call.nstage = N > 0 ? N : 1; call.do_diag = do_diag;
+        rc = get_tables(ctx, call, cp.fp, do_diag);
+        if (rc) return rc;
         // Everything below only enqueues stream work with arguments that are a pure function of `key`.
         auto issue = [&]() -> int {
             if (!off_resident)
@@ -974,20 +985,16 @@ int enqueue_impl(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i
             for (i64 p0 = 0; p0 < P; p0 += pcmax) {
                 const i64 pc = (P - p0 < pcmax) ? P - p0 : pcmax;
                 Carve cv{reinterpret_cast<char*>(ctx->ws), ctx->ws_bytes};
-                PipeIn a{};
-                a.M = M; a.pc = pc; a.C = (int)C; a.d_off = s.d_off; a.n = N; a.nh = (N >= 2) ? N / 2 : 0; a.q = q;
-                a.nstage = N > 0 ? N : 1;
-                double* X = carve_pipe(cv, a, true, fp, ingest);
+                PipeIn a = call;
+                a.pc = pc;
+                double* X = carve_pipe(cv, a, true, cp.fp, cp.ingest);
                 if (cv.over()) return fail(ctx, MCR_ENOMEM, "workspace layout needs %zu bytes; the workspace has %zu", cv.off, cv.end);
-                a.ztab = ztab;
-                a.do_diag = do_diag;
                 // (a graph capture or the per-kernel event pairs of the profiling mode keep the single stream)
-                a.fork = ctx->fork_lone && ctx->n_inflight == 0 && !ctx->prof && !ctx->graph_on && P <= pcmax &&
+                a.fork = ctx->fork_lone && ctx->order.empty() && !ctx->prof && !ctx->graph_on && P <= pcmax &&
                          (double)M * (double)pc >= 2e6 && (double)M * (double)pc <= 8e6;    // kernels long enough to be worth
                                                    // three more launches and two event waits (measured: C1 4 M param-draws 306 -> 288 us,
                                                    // 10 x 1000 x 45 149 -> 166, 4 x 1000 x 10 124 -> 133), short enough not to fill the chip
-                a.tw1 = tw1; a.tw2 = tw2;
-                if (ingest) {
+                if (cp.ingest) {
                     const int r2 = (dtype == MCR_F64) ? launch_ingest<double>(ctx, draws_dev, X, C, N, pc, sc, sn, sp, p0)
                                                       : launch_ingest<float>(ctx, draws_dev, X, C, N, pc, sc, sn, sp, p0);
                     if (r2) return r2;
@@ -998,11 +1005,9 @@ int enqueue_impl(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i
                     a.X = a.x_f32 ? (const void*)(reinterpret_cast<const float*>(draws_dev) + p0 * M)
                                   : (const void*)(reinterpret_cast<const double*>(draws_dev) + p0 * M);
                 }
-                const size_t res_off = (size_t)R * (size_t)p0;
-                a.d_res = s.d_res + res_off;
+                a.d_res = s.d_res + (size_t)R * (size_t)p0;
                 const int r3 = run_pipeline(ctx, a);
                 if (r3) return r3;
-                s.chunks.push_back(Chunk{p0, pc, res_off});
             }
             HIP_TRY(ctx, hipMemcpyAsync(s.h_res, s.d_res, sizeof(double) * (size_t)R * (size_t)P, hipMemcpyDeviceToHost,
                                         ctx->stream));
@@ -1013,7 +1018,7 @@ int enqueue_impl(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i
                                          (uint64_t)P, (uint64_t)sc, (uint64_t)sn, (uint64_t)sp, (uint64_t)nq,
                                          (uint64_t)si, (uint64_t)do_diag, (uint64_t)(uintptr_t)ctx->ws,
                                          (uint64_t)(uintptr_t)s.d_res, (uint64_t)(uintptr_t)s.d_off,
-                                         (uint64_t)pcmax, (uint64_t)(uintptr_t)ztab, (uint64_t)off_resident};
+                                         (uint64_t)pcmax, (uint64_t)(uintptr_t)call.ztab, (uint64_t)off_resident};
             for (int k = 0; k < nq; ++k) {
                 uint64_t bits; memcpy(&bits, &q.g[k], 8);
                 key.push_back((uint64_t)q.lo[k]); key.push_back(bits);
@@ -1033,11 +1038,9 @@ int enqueue_impl(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i
                 const hipError_t ie = hipGraphInstantiate(&ge.exec, graph, nullptr, nullptr, 0);
                 hipGraphDestroy(graph);
                 if (ie != hipSuccess) return fail(ctx, MCR_EHIP, "hipGraphInstantiate failed: %s", hipGetErrorString(ie));
-                ge.chunks = s.chunks;
                 ctx->graphs.push_back(std::move(ge));
                 hit = &ctx->graphs.back();
             }
-            s.chunks = hit->chunks;
             HIP_TRY(ctx, hipGraphLaunch(hit->exec, ctx->stream));
         } else {
             rc = issue();
@@ -1045,12 +1048,8 @@ int enqueue_impl(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i
         }
     }
     if (!s.trivial_nan) { s.off_C = C; s.off_N = N; }
-    if (!s.done) HIP_TRY(ctx, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-    HIP_TRY(ctx, hipEventRecord(s.done, ctx->stream));
-    s.lane = ctx->lane;
-    s.busy = true;
-    ctx->order.push_back(si);
-    ctx->n_inflight++;
+    rc = commit_slot(ctx, si);
+    if (rc) return rc;
     ctx->next_slot = (si + 1) % MCR_MAX_INFLIGHT;
     return MCR_OK;
 }
@@ -1075,13 +1074,10 @@ int wait_event(mcr_ctx* ctx, hipEvent_t ev)
 int wait_one_impl(mcr_ctx* ctx)
 {
     if (ctx->order.empty()) return MCR_OK;
-    const int si = ctx->order.front();
-    Slot& s = ctx->slots[si];
+    Slot& s = ctx->slots[ctx->order.front()];
     { const int rc = wait_event(ctx, s.done); if (rc) return rc; }
     const int rc = unpack_slot(ctx, s);
-    s.busy = false;
     ctx->order.erase(ctx->order.begin());
-    ctx->n_inflight--;
     return rc;
 }
 
@@ -1089,21 +1085,13 @@ int wait_impl(mcr_ctx* ctx)
 {
     // every slot in flight records its event behind its last copy on its lane: waiting for the events (polled, see
     // wait_event) leaves every lane idle; the stream synchronisations below then return at once
-    // (slots filled by mcr_diagnose_chains carry no event of their own: the stream synchronisation waits for those)
-    for (int si : ctx->order)
-        if (ctx->slots[si].done) { const int rc = wait_event(ctx, ctx->slots[si].done); if (rc) return rc; }
+    for (int si : ctx->order) { const int rc = wait_event(ctx, ctx->slots[si].done); if (rc) return rc; }
     for (hipStream_t st : ctx->lane_stream) if (st) HIP_TRY(ctx, hipStreamSynchronize(st));
     use_lane(ctx, 0);
     prof_resolve(ctx);
     int rc = MCR_OK;
-    for (int si : ctx->order) {
-        Slot& s = ctx->slots[si];
-        const int r = unpack_slot(ctx, s);
-        if (r && !rc) rc = r;
-        s.busy = false;
-    }
+    for (int si : ctx->order) { const int r = unpack_slot(ctx, ctx->slots[si]); if (r && !rc) rc = r; }
     ctx->order.clear();
-    ctx->n_inflight = 0;
     return rc;
 }
 
@@ -1113,9 +1101,29 @@ void abort_inflight(mcr_ctx* ctx)
     sync_all(ctx);
     use_lane(ctx, 0);
     prof_resolve(ctx);
-    for (int si : ctx->order) ctx->slots[si].busy = false;
     ctx->order.clear();
-    ctx->n_inflight = 0;
+}
+
+// Ends a call that enqueued summaries: delivers everything in flight (or, abort, drops it) and returns the first error,
+// rc with its message before the outcome of the wait.
+int drain(mcr_ctx* ctx, int rc, bool abort = false)
+{
+    char keep[sizeof ctx->err];
+    memcpy(keep, ctx->err, sizeof keep);
+    const int rw = abort ? (abort_inflight(ctx), MCR_OK) : wait_impl(ctx);
+    if (rc) memcpy(ctx->err, keep, sizeof keep);
+    return rc ? rc : rw;
+}
+
+// The results of parameter p0 on: every array of o shifted by p0 parameters (q by p0 * nq quantiles).
+mcr_summary summary_at(mcr_summary r, i64 p0, int nq)
+{
+    for (double** a : {&r.mean, &r.std, &r.median, &r.rhat, &r.rhat_bulk, &r.rhat_tail, &r.ess_bulk, &r.ess_tail})
+        if (*a) *a += p0;
+    for (int64_t** a : {&r.lag_bulk, &r.lag_tail})
+        if (*a) *a += p0;
+    if (r.q) r.q += p0 * nq;
+    return r;
 }
 
 int ensure_stage(mcr_ctx* ctx, size_t bytes)
@@ -1341,12 +1349,7 @@ int mcr_summarize_enqueue(mcr_ctx* ctx, const void* draws_dev, int dtype, int64_
                           mcr_summary* out)
 {
     const int rc = enqueue_impl(ctx, draws_dev, dtype, C, N, P, sc, sn, sp, min_chains, quantiles, n_q, out);
-    if (rc && ctx && rc != MCR_EMINCHAINS && rc != MCR_EMINCHAINS_ARG && rc != MCR_EINVAL) {
-        char keep[512];
-        memcpy(keep, ctx->err, sizeof keep);
-        abort_inflight(ctx);
-        memcpy(ctx->err, keep, sizeof keep);
-    }
+    if (rc && ctx && rc != MCR_EMINCHAINS && rc != MCR_EMINCHAINS_ARG && rc != MCR_EINVAL) return drain(ctx, rc, true);
     return rc;
 }
 
@@ -1369,17 +1372,13 @@ int mcr_summarize_models(mcr_ctx* ctx, const mcr_model_desc* models, int n_model
     if (n_models < 0 || (n_models > 0 && (!models || !outs))) return fail(ctx, MCR_EINVAL, "bad argument");
     int rc = MCR_OK;
     for (int i = 0; i < n_models && !rc; ++i) {
-        if (ctx->n_inflight >= MCR_MAX_INFLIGHT) rc = wait_one_impl(ctx);
+        if (ctx->order.size() >= MCR_MAX_INFLIGHT) rc = wait_one_impl(ctx);
         if (rc) break;
         const mcr_model_desc& m = models[i];
         rc = mcr_summarize_enqueue(ctx, m.draws_dev, m.dtype, m.C, m.N, m.P, m.stride_c, m.stride_n, m.stride_p,
                                    m.min_chains, quantiles, n_q, &outs[i]);
     }
-    char keep[512];
-    memcpy(keep, ctx->err, sizeof keep);
-    const int rw = wait_impl(ctx);          // deliver everything that was enqueued
-    if (rc) { memcpy(ctx->err, keep, sizeof keep); return rc; }
-    return rw;
+    return drain(ctx, rc);                  // deliver everything that was enqueued
 }
 
 int mcr_summarize_dev(mcr_ctx* ctx, const void* draws_dev, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc,
@@ -1407,11 +1406,10 @@ int mcr_summarize(mcr_ctx* ctx, const void* draws, int dtype, int64_t C, int64_t
     // crosses PCIe on the copy stream, the kernels of piece k already run on a lane (pageable host memory makes
     // the copy itself synchronous for the host, which has nothing better to do).
     const i64 per_param = tensor_extent(C, N, 1, sc, sn, 0);
-    const bool separable = P >= 2 && C * N > 0 && sp >= per_param && ctx->n_inflight == 0 && ctx->n_lanes > 1;
+    const bool separable = P >= 2 && C * N > 0 && sp >= per_param && ctx->order.empty() && ctx->n_lanes > 1;
     if (separable && (size_t)ext * es >= ((size_t)8 << 20)) {
         int pieces = ctx->n_lanes < 4 ? ctx->n_lanes : 4;
         if ((i64)pieces > P) pieces = (int)P;
-        const int nqq = n_q > 0 ? n_q : 0;
         for (int k = 0; k < pieces && !rc; ++k) {
             const i64 p0 = P * k / pieces, p1 = P * (k + 1) / pieces, pc = p1 - p0;
             const size_t b0 = (size_t)p0 * (size_t)sp * es;
@@ -1419,19 +1417,10 @@ int mcr_summarize(mcr_ctx* ctx, const void* draws, int dtype, int64_t C, int64_t
             hipError_t e = hipMemcpyAsync((char*)ctx->stage + b0, (const char*)draws + b0, bytes, hipMemcpyHostToDevice, ctx->copy_stream);
             if (e == hipSuccess) e = hipStreamSynchronize(ctx->copy_stream);
             if (e != hipSuccess) { rc = fail(ctx, MCR_EHIP, "upload failed: %s", hipGetErrorString(e)); break; }
-            mcr_summary o = *out;
-            auto adv = [&](double*& q, i64 n) { if (q) q += n; };
-            adv(o.mean, p0); adv(o.std, p0); adv(o.q, p0 * nqq); adv(o.median, p0); adv(o.rhat, p0); adv(o.rhat_bulk, p0);
-            adv(o.rhat_tail, p0); adv(o.ess_bulk, p0); adv(o.ess_tail, p0);
-            if (o.lag_bulk) o.lag_bulk += p0;
-            if (o.lag_tail) o.lag_tail += p0;
+            mcr_summary o = summary_at(*out, p0, n_q > 0 ? n_q : 0);
             rc = mcr_summarize_enqueue(ctx, (const char*)ctx->stage + b0, dtype, C, N, pc, sc, sn, sp, min_chains, quantiles, n_q, &o);
         }
-        char keep[512];
-        memcpy(keep, ctx->err, sizeof keep);
-        const int rw = wait_impl(ctx);
-        if (rc) { memcpy(ctx->err, keep, sizeof keep); return rc; }
-        return rw;
+        return drain(ctx, rc);
     }
     if (ext > 0) {
         HIP_TRY(ctx, hipMemcpyAsync(ctx->stage, draws, (size_t)ext * es, hipMemcpyHostToDevice, ctx->stream));
@@ -1450,7 +1439,7 @@ int mcr_diagnose_chains(mcr_ctx* ctx, const double* pooled, const int64_t* chain
     if (C < min_chains) return fail(ctx, MCR_EMINCHAINS, "diagnostics require at least %d chains; got %d chain(s)", min_chains, C);
     if (C > kMaxChains) return fail(ctx, MCR_EINVAL, "at most %d chains are supported; got %d", kMaxChains, C);
     if (C > 0 && !chain_off) return fail(ctx, MCR_EINVAL, "chain_off is NULL");
-    if (ctx->n_inflight) return fail(ctx, MCR_EINVAL, "mcr_diagnose_chains with summaries in flight");
+    if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "mcr_diagnose_chains with summaries in flight");
     const i64 M = C > 0 ? chain_off[C] : 0;
     if (M < 0 || M >= (i64)0x7FFFFFFFll) return fail(ctx, MCR_EINVAL, "pooled length out of range");
     i64 n = 0, nh = 0;
@@ -1462,11 +1451,9 @@ int mcr_diagnose_chains(mcr_ctx* ctx, const double* pooled, const int64_t* chain
         if (len >= 2) { if (!have_h || len / 2 < nh) nh = len / 2; have_h = true; }
     }
     if (M > 0 && !pooled) return fail(ctx, MCR_EINVAL, "pooled is NULL");
-    Slot& s = ctx->slots[0];
-    s.out = *out; s.P = 1; s.M = M; s.nq = 0; s.C = C; s.chunks.clear();
-    s.trivial_nan = (M == 0);
-    if (s.trivial_nan) { s.busy = true; ctx->order.push_back(0); ctx->n_inflight = 1; return wait_impl(ctx); }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    Slot& s = fill_slot(ctx, 0, out, 1, M, 0);     // slot 0 on the current lane; next_slot stays
+    if (s.trivial_nan) { const int rc = commit_slot(ctx, 0); return rc ? rc : wait_impl(ctx); }
     const bool want_dbg = z_bulk || z_tail || rank_bulk || rank_tail;
     i64 nstage = n > 0 ? n : 1;
     for (int c = 0; c < C; ++c) {
@@ -1479,6 +1466,7 @@ int mcr_diagnose_chains(mcr_ctx* ctx, const double* pooled, const int64_t* chain
     a.M = M; a.pc = 1; a.C = C; a.n = n; a.nh = nh; a.q.nq = 0; a.nstage = nstage;
     double* X = nullptr;
     double* dbg[4] = {nullptr, nullptr, nullptr, nullptr};     // z_bulk, z_tail, rank_bulk, rank_tail (decoded codes)
+    double* const dst[4] = {z_bulk, z_tail, rank_bulk, rank_tail};
     auto layout = [&](Carve& cv) {
         X = carve_pipe(cv, a, true, fp, true);
         if (want_dbg) for (int i = 0; i < 4; ++i) dbg[i] = cv.take<double>((size_t)M);
@@ -1495,23 +1483,14 @@ int mcr_diagnose_chains(mcr_ctx* ctx, const double* pooled, const int64_t* chain
     memcpy(s.h_off, chain_off, sizeof(i64) * (size_t)(C + 1));
     HIP_TRY(ctx, hipMemcpyAsync(s.d_off, s.h_off, sizeof(i64) * (size_t)(C + 1), hipMemcpyHostToDevice, ctx->stream));
     a.d_off = s.d_off;
-    rc = get_ztab(ctx, M, &a.ztab);
+    rc = get_tables(ctx, a, fp, true);
     if (rc) return rc;
-    if (fp.on) {
-        rc = get_twiddles(ctx, 1 << fp.log1, &a.tw1);
-        if (!rc) rc = get_twiddles(ctx, 1 << fp.log2, &a.tw2);
-        if (rc) return rc;
-    }
     HIP_TRY(ctx, hipMemcpyAsync(X, pooled, sizeof(double) * (size_t)M, hipMemcpyHostToDevice, ctx->stream));
     a.X = X;
     a.d_res = s.d_res;
     rc = run_pipeline(ctx, a);
     if (rc) { abort_inflight(ctx); return rc; }
-    s.chunks.push_back(Chunk{0, 1, 0});
     HIP_TRY(ctx, hipMemcpyAsync(s.h_res, s.d_res, sizeof(double) * (size_t)R, hipMemcpyDeviceToHost, ctx->stream));
-    auto back = [&](double* dst, const double* srcp) -> hipError_t {
-        return dst ? hipMemcpyAsync(dst, srcp, sizeof(double) * (size_t)M, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
-    };
     if (want_dbg) {
         const unsigned nb = (unsigned)((M + 255) / 256);
         hipLaunchKernelGGL(k_decode_codes, dim3(nb), dim3(256), 0, ctx->stream, (const u32*)a.zb, (const double*)a.ztab, M,
@@ -1520,12 +1499,10 @@ int mcr_diagnose_chains(mcr_ctx* ctx, const double* pooled, const int64_t* chain
                            z_tail ? dbg[1] : (double*)nullptr, rank_tail ? dbg[3] : (double*)nullptr);
         HIP_TRY(ctx, hipGetLastError());
     }
-    HIP_TRY(ctx, back(z_bulk, dbg[0]));
-    HIP_TRY(ctx, back(z_tail, dbg[1]));
-    HIP_TRY(ctx, back(rank_bulk, dbg[2]));
-    HIP_TRY(ctx, back(rank_tail, dbg[3]));
-    s.busy = true; ctx->order.push_back(0); ctx->n_inflight = 1;
-    return wait_impl(ctx);
+    for (int i = 0; i < 4; ++i)
+        if (dst[i]) HIP_TRY(ctx, hipMemcpyAsync(dst[i], dbg[i], sizeof(double) * (size_t)M, hipMemcpyDeviceToHost, ctx->stream));
+    rc = commit_slot(ctx, 0);
+    return rc ? rc : wait_impl(ctx);
 }
 
 int mcr_moments_dev(mcr_ctx* ctx, const void* draws_dev, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc,
@@ -1624,7 +1601,7 @@ int mcr_two_sample(mcr_ctx* ctx, const double* ref, int64_t Mr, const double* ac
     if (P > kMaxGridY) return fail(ctx, MCR_EINVAL, "P > %d", kMaxGridY);
     if (Mr >= (i64)0xFFFFFFFFll || Ma >= (i64)0xFFFFFFFFll || (double)Mr * (double)Ma >= 9007199254740992.0)
         return fail(ctx, MCR_EINVAL, "samples too long (Mr * Ma must stay below 2^53)");
-    if (ctx->n_inflight) return fail(ctx, MCR_EINVAL, "mcr_two_sample with summaries in flight");
+    if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "mcr_two_sample with summaries in flight");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int nblk = (int)((Mr + Ma + kTile - 1) / kTile);
     double *Xr, *Xa, *Sr, *part, *d_ks, *d_w, *bad;
@@ -1685,7 +1662,7 @@ int mcr_covariance_dev(mcr_ctx* ctx, const double* draws_dev, int64_t M, int64_t
     if (P < 0 || M < 1 || (P > 0 && (!draws_dev || !cov_dev))) return fail(ctx, MCR_EINVAL, "bad argument");
     if (P == 0) return MCR_OK;
     if (P > 8192) return fail(ctx, MCR_EINVAL, "P > 8192 not supported by mcr_covariance");
-    if (ctx->n_inflight) return fail(ctx, MCR_EINVAL, "mcr_covariance with summaries in flight");
+    if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "mcr_covariance with summaries in flight");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int nb = (int)((P + kCovBM - 1) / kCovBM);
     const i64 P64 = (i64)nb * kCovBM;
@@ -1731,7 +1708,7 @@ int mcr_covariance(mcr_ctx* ctx, const double* draws, int64_t M, int64_t P, doub
     if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
     if (P < 0 || M < 1 || (P > 0 && (!draws || !cov))) return fail(ctx, MCR_EINVAL, "bad argument");
     if (P == 0) return MCR_OK;
-    if (ctx->n_inflight) return fail(ctx, MCR_EINVAL, "mcr_covariance with summaries in flight");
+    if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "mcr_covariance with summaries in flight");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc = ensure_stage(ctx, (size_t)P * M * 8 + (size_t)P * P * 8 + 256);
     if (rc) return rc;
@@ -2433,277 +2410,299 @@ struct mcr_fileset {
 };
 
 namespace {
-struct OpenFile {          // a draws file of mcr_summarize_files: descriptor, size, parsed metadata (its image lives in the pinned buffer)
-    int fd = -1; size_t len = 0; mcr_parquet* pq = nullptr;
-    ~OpenFile() {
-        if (pq) mcr_parquet_close(pq);
-        if (fd >= 0) close(fd);
-    }
+namespace pq = mcr::pq;
+
+struct BatchFile {    // a file of mcr_summarize_files: descriptor, image, parsed metadata, column roles, place in the arena
+    int fd = -1; size_t len = 0, img = 0; mcr_parquet* pq = nullptr;   // img: offset of the image in pq_pin and pq_stage
+    int rc = MCR_OK; std::string err;                                  // set by its reader
+    std::vector<int> cols; int chain = -1, draw = -1;
+    i64 M = 0, C = 0, N = 0; size_t off = 0, ioff = 0;                 // draws at arena + off, ids at arena + ids_base + ioff
+    BatchFile() = default; BatchFile(const BatchFile&) = delete;
+    ~BatchFile() { if (pq) mcr_parquet_close(pq); if (fd >= 0) close(fd); }
 };
+
+// What the stages of mcr_summarize_files hand on.  It holds the host ends of their copies, so that these outlive any copy
+// still queued when a stage returns early.
+struct FileBatch {
+    const char* const* paths;
+    std::vector<BatchFile> f;
+    size_t img_total = 0, ids_base = 0, lay_base = 0, lay_out = 0;   // arena: draws, ids, FileIds, chain layouts
+    char* arena = nullptr;
+    std::vector<mcr_parquet_request> reqs; PqPlan pp;
+    std::vector<pq::FileIds> fids; std::vector<i64> lay; int h_err[2] = {0, 0};   // lay: k_chain_layout, 4 per file
+    FileBatch(const char* const* p, int n) : paths(p), f((size_t)n) {}
+};
+
+// 1. Opens and sizes the files, lays their images out back to back and makes the device and pinned staging that large.
+int fs_open(mcr_ctx* ctx, FileBatch& B)
+{
+    for (size_t i = 0; i < B.f.size(); ++i) {
+        BatchFile& m = B.f[i];
+        m.fd = open(B.paths[i], O_RDONLY);
+        struct stat st;
+        if (m.fd < 0 || fstat(m.fd, &st) != 0) return fail(ctx, MCR_EINVAL, "cannot open %s", B.paths[i]);
+        m.len = (size_t)st.st_size;
+        if (m.len == 0) return fail(ctx, MCR_EINVAL, "parquet: %s is empty", B.paths[i]);
+        m.img = B.img_total;
+        B.img_total = align_up(m.img + m.len, 256);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int rc = ensure_buf(ctx, &ctx->pq_stage, &ctx->pq_stage_bytes, B.img_total + pq::kInWin + 256);
+    if (rc) return rc;
+    if (B.img_total > ctx->pq_pin_bytes) {                  // pinned staging, kept for the life of the context
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->pq_pin) { hipHostFree(ctx->pq_pin); ctx->pq_pin = nullptr; ctx->pq_pin_bytes = 0; }
+        const size_t want = B.img_total + (B.img_total >> 2);
+        HIP_TRY(ctx, hipHostMalloc(&ctx->pq_pin, want, hipHostMallocDefault));
+        ctx->pq_pin_bytes = want;
+    }
+    return MCR_OK;
+}
+
+// The readers of fs_read: however the stage ends, the pool stops handing out files and joins every thread it started.
+struct ReaderPool {
+    int n; std::atomic<int> next{0}; std::vector<std::thread> th;
+    ~ReaderPool() { next.store(n); for (std::thread& t : th) t.join(); }
+};
+
+// 2. The images go WHOLE into one pinned host buffer (nearly every byte of a draws file is a column chunk this call decodes):
+//    MCR_IO_THREADS host threads pread() them -- the page cache's copy lands in memory the DMA engine reads directly; no
+//    mapping is set up or torn down (57 munmaps cost 2 ms of TLB shoot-downs in a process with this many threads), no page
+//    faults, no pageable staging inside the runtime -- and parse each footer and its page headers from that image, while
+//    THIS thread, the only one making HIP calls, uploads the finished prefix behind them in pieces of >= 2 MB.
+int fs_read(mcr_ctx* ctx, FileBatch& B)
+{
+    const int n = (int)B.f.size();
+    if (n == 0) return MCR_OK;
+    char* pin = (char*)ctx->pq_pin;
+    std::vector<std::atomic<int>> done((size_t)n);       // (value-initialised: 0)
+    hipError_t he = hipSuccess;
+    {
+        ReaderPool pool{n};
+        auto reader = [&]() {
+            for (int i; (i = pool.next.fetch_add(1)) < n;) {
+                BatchFile& m = B.f[(size_t)i];
+                auto bad = [&](int code, const std::string& msg) { m.rc = code; m.err = msg; };
+                try {
+                    size_t got = 0;
+                    for (ssize_t r; got < m.len && (r = pread(m.fd, pin + m.img + got, m.len - got, (off_t)got)) > 0;) got += (size_t)r;
+                    if (got < m.len) bad(MCR_EINVAL, std::string("short read of ") + B.paths[i]);
+                    else {
+                        m.pq = new mcr_parquet();
+                        if (!pq::open(m.pq->f, pin + m.img, m.len)) bad(MCR_EINVAL, std::string(B.paths[i]) + ": parquet: " + m.pq->f.error);
+                    }
+                } catch (const std::exception& e) { bad(MCR_ENOMEM, std::string("host allocation failed: ") + e.what()); }
+                done[(size_t)i].store(1, std::memory_order_release);
+            }
+        };
+        try { while ((int)pool.th.size() < std::min(ctx->io_threads, n)) pool.th.emplace_back(reader); }
+        catch (const std::exception&) {}    // std::system_error under a thread limit: the readers started share the files
+        if (pool.th.empty()) reader();      // none: this thread reads them
+        int sent = 0;                                        // files [0, sent) are uploaded
+        for (int i = 0; i < n; ++i) {
+            while (done[(size_t)i].load(std::memory_order_acquire) == 0) std::this_thread::yield();
+            const size_t from = B.f[(size_t)sent].img, upto = align_up(B.f[(size_t)i].img + B.f[(size_t)i].len, 256);
+            if (he == hipSuccess && (upto - from >= ctx->io_piece || i + 1 == n)) {
+                he = hipMemcpyAsync((char*)ctx->pq_stage + from, pin + from, upto - from, hipMemcpyHostToDevice, ctx->stream);
+                sent = i + 1;
+            }
+        }
+    }
+    for (const BatchFile& m : B.f)
+        if (m.rc) return fail(ctx, m.rc, "%s", m.err.c_str());
+    if (he != hipSuccess) return fail(ctx, MCR_EHIP, "hipMemcpyAsync of the file images failed: %s", hipGetErrorString(he));
+    return MCR_OK;
+}
+
+// 3. Column roles, the arena ([P][M] draws per file, packed, then the chain / draw ids), the decode requests and the page
+//    table.  Arena order = path order: on the packaged corpus (statistics phase 1.18 - 1.20 ms, five tensors as the files
+//    come, before k_tier3's short-chain slots) files of one shape side by side measured 1.42 - 1.48 ms, tensors capped at
+//    160 / 100 / 60 / 30 parameters 1.29 / 1.33 / 1.40 / 1.90 ms, every tensor forked over two streams 1.31 - 1.34 ms.
+int fs_layout(mcr_ctx* ctx, FileBatch& B)
+{
+    size_t arena = 0, ids = 0;
+    for (size_t i = 0; i < B.f.size(); ++i) {
+        BatchFile& m = B.f[i];
+        const pq::File& f = m.pq->f;
+        for (int c = 0; c < (int)f.cols.size(); ++c) {
+            const int ty = f.cols[(size_t)c].type;
+            const bool numeric = ty == pq::T_INT32 || ty == pq::T_INT64 || ty == pq::T_FLOAT || ty == pq::T_DOUBLE;
+            if (f.cols[(size_t)c].name == "chain") m.chain = c;
+            else if (f.cols[(size_t)c].name == "draw") m.draw = c;
+            else if (numeric) m.cols.push_back(c);
+        }
+        if (m.chain < 0 || m.draw < 0) return fail(ctx, MCR_EINVAL, "%s: no chain / draw columns", B.paths[i]);
+        m.M = f.num_rows;
+        m.ioff = ids; ids += (size_t)2 * (size_t)m.M * 8;
+        m.off = arena; arena += m.cols.size() * (size_t)m.M * 8;
+    }
+    const size_t n = B.f.size();
+    B.ids_base = align_up(arena, 256);
+    B.lay_base = align_up(B.ids_base + ids, 256), B.lay_out = align_up(B.lay_base + n * sizeof(pq::FileIds), 256);
+    const int rc = ensure_buf(ctx, &ctx->fs_arena, &ctx->fs_arena_bytes, B.lay_out + n * 32 + 256);
+    if (rc) return rc;
+    char* base = B.arena = (char*)ctx->fs_arena;
+    std::vector<FileBase> bases;
+    for (const BatchFile& m : B.f) {
+        for (size_t j = 0; j < m.cols.size(); ++j)
+            B.reqs.push_back(mcr_parquet_request{m.pq, m.cols[j], MCR_PQ_F64, base + m.off + j * (size_t)m.M * 8});
+        B.reqs.push_back(mcr_parquet_request{m.pq, m.chain, MCR_PQ_I64, base + B.ids_base + m.ioff});
+        B.reqs.push_back(mcr_parquet_request{m.pq, m.draw, MCR_PQ_I64, base + B.ids_base + m.ioff + (size_t)m.M * 8});
+        bases.emplace_back(&m.pq->f, m.img);
+    }
+    if (B.reqs.empty()) return MCR_OK;
+    std::sort(bases.begin(), bases.end(), [](const FileBase& a, const FileBase& b) { return std::less<const pq::File*>()(a.first, b.first); });
+    const int rp = pq_plan(ctx, B.reqs.data(), (int)B.reqs.size(), B.pp, &bases, B.img_total);
+    return rp ? rp : pq_buffers(ctx, B.pp);   // (pq_stage is large enough already: no reallocation under the uploads in flight)
+}
+
+// 4. Decode kernels + the chain / draw bookkeeping on the device (k_chain_layout: 32 bytes per file come back instead of the
+//    id columns), then the layout checks (convert._chains_from_table): rows must already be in (chain, draw) order.
+int fs_decode(mcr_ctx* ctx, FileBatch& B, int min_chains, int diagnostics)
+{
+    const size_t n = B.f.size();
+    B.lay.assign(n * 4, 0);
+    if (!B.reqs.empty()) {
+        int rc = pq_launch(ctx, B.pp);
+        if (rc) return rc;
+        for (const BatchFile& m : B.f) {
+            const i64* id = (const i64*)(B.arena + B.ids_base + m.ioff);
+            B.fids.push_back(pq::FileIds{id, id + m.M, m.M});
+        }
+        char* fids = B.arena + B.lay_base;
+        i64* lay = (i64*)(B.arena + B.lay_out);
+        HIP_TRY(ctx, hipMemcpyAsync(fids, B.fids.data(), n * sizeof(pq::FileIds), hipMemcpyHostToDevice, ctx->stream));
+        LAUNCH(ctx, K_GATHER, pq::k_chain_layout, dim3((unsigned)n), dim3(256), 0, (const pq::FileIds*)fids, lay);
+        HIP_TRY(ctx, hipMemcpyAsync(B.lay.data(), lay, n * 32, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(B.h_err, B.pp.d_err, 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        prof_resolve(ctx);
+        rc = pq_error(ctx, B.h_err);
+        if (rc) return rc;
+    }
+    for (size_t i = 0; i < n; ++i) {
+        BatchFile& m = B.f[i];
+        const i64* L = B.lay.data() + i * 4;
+        if (m.M > 0 && !L[3]) return fail(ctx, MCR_ELAYOUT, "%s: rows are not in (chain, draw) order", B.paths[i]);
+        const bool equal = m.M == 0 || L[2] != 0;
+        m.C = m.M > 0 ? L[0] : 0;
+        m.N = m.M > 0 ? L[1] : 0;
+        if (diagnostics && !m.cols.empty()) {
+            if (m.C < min_chains) return fail(ctx, MCR_EMINCHAINS, "%s: R-hat diagnostics require at least %d chains; got %lld chain(s)", B.paths[i], min_chains, (long long)m.C);
+            if (!equal) return fail(ctx, MCR_ELAYOUT, "%s: chains of unequal length", B.paths[i]);
+        }
+        if (!diagnostics && !m.cols.empty() && m.M == 0) return fail(ctx, MCR_EINVAL, "%s: cannot compute stats of empty columns", B.paths[i]);
+    }
+    return MCR_OK;
+}
+
+// One statistics call: the files [first, first + count), parameters [p0, p0 + P) of the batch in path order.
+struct Job { int first, count; i64 C, N, P, p0; };
+
+// Every job's results, parameters in path order, until fs_scatter hands them to the files.
+struct Staged { std::vector<double> f[MCR_FS_FIELDS]; std::vector<int64_t> lag[2], qlo; };
+
+// 5. The result set (NaN until filled), the jobs (runs of neighbouring files of one shape are one tensor), enqueue, drain.
+int fs_stats(mcr_ctx* ctx, const FileBatch& B, mcr_fileset& fs, Staged& S, int min_chains, const double* quantiles, int n_q,
+             int diagnostics)
+{
+    std::vector<Job> jobs;
+    fs.files.resize(B.f.size());
+    i64 p0 = 0;
+    for (int i = 0; i < (int)B.f.size(); ++i) {
+        const BatchFile& m = B.f[(size_t)i];
+        const i64 P = (i64)m.cols.size(), Cj = diagnostics ? m.C : 1, Nj = diagnostics ? m.N : m.M;
+        mcr_fileset::Entry& e = fs.files[(size_t)i];
+        for (int c : m.cols) e.names.push_back(m.pq->f.cols[(size_t)c].name);
+        e.C = m.C; e.N = m.N;
+        for (int k = 0; k < MCR_FS_FIELDS; ++k) e.f[k].assign((size_t)P * (k == MCR_FS_Q ? (size_t)fs.n_q : 1), NAN);
+        if (P == 0) continue;
+        Job* j = jobs.empty() ? nullptr : &jobs.back();      // (the arena holds the files' draws back to back in path order)
+        if (j && j->first + j->count == i && j->C == Cj && j->N == Nj) { ++j->count; j->P += P; }
+        else jobs.push_back(Job{i, 1, Cj, Nj, P, p0});
+        p0 += P;
+    }
+    fs.n_jobs = (int)jobs.size();
+    const size_t P = (size_t)p0;
+    for (int k = 0; k < MCR_FS_FIELDS; ++k) S.f[k].assign(P * (k == MCR_FS_Q ? (size_t)n_q : 1), NAN);
+    S.lag[0].assign(P, 0); S.lag[1].assign(P, 0); S.qlo.assign((size_t)(n_q > 0 ? n_q : 1), 0);
+    mcr_summary all{};
+    all.mean = S.f[MCR_FS_MEAN].data(); all.std = S.f[MCR_FS_STD].data();
+    all.q = n_q > 0 ? S.f[MCR_FS_Q].data() : nullptr; all.median = S.f[MCR_FS_MEDIAN].data();
+    all.q_lo = S.qlo.data();
+    if (diagnostics) {
+        all.rhat = S.f[MCR_FS_RHAT].data(); all.ess_bulk = S.f[MCR_FS_ESS_BULK].data(); all.ess_tail = S.f[MCR_FS_ESS_TAIL].data();
+        all.rhat_bulk = S.f[MCR_FS_RHAT_BULK].data(); all.rhat_tail = S.f[MCR_FS_RHAT_TAIL].data();
+        all.lag_bulk = S.lag[0].data(); all.lag_tail = S.lag[1].data();
+    }
+    int rc = MCR_OK;
+    for (size_t k = 0; k < jobs.size() && !rc; ++k) {
+        const Job& j = jobs[k];
+        mcr_summary o = summary_at(all, j.p0, n_q);
+        if (ctx->order.size() >= MCR_MAX_INFLIGHT) rc = wait_one_impl(ctx);
+        if (!rc)
+            rc = enqueue_impl(ctx, B.arena + B.f[(size_t)j.first].off, MCR_F64, j.C, j.N, j.P, j.N, 1, j.C * j.N,
+                              diagnostics ? min_chains : 1, quantiles, n_q, &o);
+    }
+    return drain(ctx, rc);
+}
+
+// 6. The staged results into the set, file by file.
+void fs_scatter(Staged& S, int diagnostics, mcr_fileset& fs)
+{
+    for (size_t p = 0; diagnostics && p < S.lag[0].size(); ++p) {
+        S.f[MCR_FS_LAG_BULK][p] = (double)S.lag[0][p];
+        S.f[MCR_FS_LAG_TAIL][p] = (double)S.lag[1][p];
+    }
+    size_t p0 = 0;
+    for (mcr_fileset::Entry& e : fs.files) {
+        const size_t P = e.names.size();
+        for (int k = 0; k < MCR_FS_FIELDS; ++k) {
+            const size_t w = k == MCR_FS_Q ? (size_t)fs.n_q : 1;
+            if (w) memcpy(e.f[k].data(), S.f[k].data() + p0 * w, P * w * sizeof(double));
+        }
+        p0 += P;
+    }
+}
+
+struct StreamSync { hipStream_t st; ~StreamSync() { if (st) hipStreamSynchronize(st); } };   // unless released (st = nullptr)
 }  // namespace
 
 int mcr_summarize_files(mcr_ctx* ctx, const char* const* paths, int n_paths, int min_chains, const double* quantiles,
                         int n_q, int diagnostics, mcr_fileset** out)
 {
-    namespace pq = mcr::pq;
     if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
     if (!out || n_paths < 0 || (n_paths > 0 && !paths)) return fail(ctx, MCR_EINVAL, "bad argument");
     if (min_chains < 1) return fail(ctx, MCR_EMINCHAINS_ARG, "min_chains must be >= 1; got %d", min_chains);
     if (n_q < 0 || n_q > MCR_MAX_QUANTILES || (n_q > 0 && !quantiles)) return fail(ctx, MCR_EINVAL, "bad quantile list");
-    if (ctx->n_inflight) return fail(ctx, MCR_EINVAL, "mcr_summarize_files with summaries in flight");
-    using clk = std::chrono::steady_clock;
-    const clk::time_point t_start = clk::now();
-    double phase[MCR_FS_PHASES] = {0};
-    clk::time_point t_prev = t_start;
-    auto lap = [&](int k) { const clk::time_point now = clk::now(); phase[k] += std::chrono::duration<double, std::milli>(now - t_prev).count(); t_prev = now; };
+    if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "mcr_summarize_files with summaries in flight");
     try {
-        std::vector<OpenFile> mf((size_t)n_paths);
-        struct Plan { std::vector<int> cols; int chain = -1, draw = -1; i64 M = 0; size_t off = 0, ioff = 0; i64 C = 0, N = 0; };
-        std::vector<Plan> plan((size_t)n_paths);
-        size_t arena = 0, ids = 0;
-        // 1. The files' images go WHOLE into one pinned host buffer (nearly every byte of a draws file is a column chunk this
-        //    call decodes): MCR_IO_THREADS host threads pread() them -- the page cache's copy lands in memory the DMA engine
-        //    reads directly; no mapping is set up or torn down (57 munmaps cost 2 ms of TLB shoot-downs in a process with
-        //    this many threads), no page faults, no pageable staging inside the runtime -- and parse each footer and its
-        //    page headers from that image, while THIS thread uploads the finished prefix behind them in pieces of >= 2 MB.
-        //    HIP calls stay on the calling thread.
-        std::vector<size_t> img_off((size_t)n_paths + 1, 0);
-        for (int i = 0; i < n_paths; ++i) {
-            OpenFile& m = mf[(size_t)i];
-            m.fd = open(paths[i], O_RDONLY);
-            struct stat st;
-            if (m.fd < 0 || fstat(m.fd, &st) != 0) return fail(ctx, MCR_EINVAL, "cannot open %s", paths[i]);
-            m.len = (size_t)st.st_size;
-            if (m.len == 0) return fail(ctx, MCR_EINVAL, "parquet: %s is empty", paths[i]);
-            img_off[(size_t)i + 1] = align_up(img_off[(size_t)i] + m.len, 256);
-        }
-        const size_t img_total = img_off[(size_t)n_paths];
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        int rc = ensure_buf(ctx, &ctx->pq_stage, &ctx->pq_stage_bytes, img_total + pq::kInWin + 256);
-        if (rc) return rc;
-        if (img_total > ctx->pq_pin_bytes) {                    // pinned staging, kept for the life of the context
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->pq_pin) { hipHostFree(ctx->pq_pin); ctx->pq_pin = nullptr; ctx->pq_pin_bytes = 0; }
-            const size_t want = img_total + (img_total >> 2);
-            HIP_TRY(ctx, hipHostMalloc(&ctx->pq_pin, want, hipHostMallocDefault));
-            ctx->pq_pin_bytes = want;
-        }
-        lap(MCR_FS_PH_OPEN);
-        std::vector<int> frc((size_t)n_paths, MCR_OK);
-        std::vector<std::string> ferr((size_t)n_paths);
-        if (n_paths > 0) {
-            char* pin = (char*)ctx->pq_pin;
-            std::vector<std::atomic<int>> done((size_t)n_paths);
-            for (auto& d : done) d.store(0, std::memory_order_relaxed);
-            std::atomic<int> next{0};
-            auto reader = [&]() {
-                for (int i; (i = next.fetch_add(1)) < n_paths;) {
-                    OpenFile& m = mf[(size_t)i];
-                    auto bad = [&](int code, const std::string& msg) { frc[(size_t)i] = code; ferr[(size_t)i] = msg; };
-                    try {
-                        size_t got = 0;
-                        while (got < m.len) {
-                            const ssize_t r = pread(m.fd, pin + img_off[(size_t)i] + got, m.len - got, (off_t)got);
-                            if (r <= 0) break;
-                            got += (size_t)r;
-                        }
-                        if (got < m.len) bad(MCR_EINVAL, std::string("short read of ") + paths[i]);
-                        else {
-                            m.pq = new mcr_parquet();
-                            if (!pq::open(m.pq->f, pin + img_off[(size_t)i], m.len)) bad(MCR_EINVAL, std::string(paths[i]) + ": parquet: " + m.pq->f.error);
-                        }
-                    } catch (const std::exception& e) { bad(MCR_ENOMEM, std::string("host allocation failed: ") + e.what()); }
-                    done[(size_t)i].store(1, std::memory_order_release);
-                }
-            };
-            std::vector<std::thread> th;
-            const int TR = std::max(1, std::min(ctx->io_threads, n_paths));
-            for (int t = 0; t < TR; ++t) th.emplace_back(reader);
-            int sent = 0;                                        // files [0, sent) are uploaded
-            hipError_t he = hipSuccess;
-            for (int i = 0; i < n_paths; ++i) {
-                while (done[(size_t)i].load(std::memory_order_acquire) == 0) std::this_thread::yield();
-                const size_t from = img_off[(size_t)sent], upto = img_off[(size_t)i + 1];
-                if (he == hipSuccess && (upto - from >= ctx->io_piece || i + 1 == n_paths)) {
-                    he = hipMemcpyAsync((char*)ctx->pq_stage + from, pin + from, upto - from, hipMemcpyHostToDevice, ctx->stream);
-                    sent = i + 1;
-                }
-            }
-            for (std::thread& x : th) x.join();
-            for (int i = 0; i < n_paths; ++i)
-                if (frc[(size_t)i]) { hipStreamSynchronize(ctx->stream); return fail(ctx, frc[(size_t)i], "%s", ferr[(size_t)i].c_str()); }
-            if (he != hipSuccess) return fail(ctx, MCR_EHIP, "hipMemcpyAsync of the file images failed: %s", hipGetErrorString(he));
-        }
-        lap(MCR_FS_PH_READ);
-        for (int i = 0; i < n_paths; ++i) {
-            const pq::File& f = mf[(size_t)i].pq->f;
-            Plan& pl = plan[(size_t)i];
-            for (int c = 0; c < (int)f.cols.size(); ++c) {
-                const int ty = f.cols[(size_t)c].type;
-                const bool numeric = ty == pq::T_INT32 || ty == pq::T_INT64 || ty == pq::T_FLOAT || ty == pq::T_DOUBLE;
-                if (f.cols[(size_t)c].name == "chain") pl.chain = c;
-                else if (f.cols[(size_t)c].name == "draw") pl.draw = c;
-                else if (numeric) pl.cols.push_back(c);
-            }
-            if (pl.chain < 0 || pl.draw < 0) { hipStreamSynchronize(ctx->stream); return fail(ctx, MCR_EINVAL, "%s: no chain / draw columns", paths[i]); }
-            pl.M = f.num_rows;
-            pl.ioff = ids; ids += (size_t)2 * (size_t)pl.M * 8;
-        }
-        // arena order = path order.  Measured in round 4 on the packaged corpus -- BEFORE k_tier3 got its extra slots for short
-        // chains, i.e. with 17 listed pairs per slot on the critical path of the statistics phase (1.18 - 1.20 ms then, 0.68 ms
-        // now; five tensors as the files come): files of one hinted shape laid next to each other (two tensors): 1.42 - 1.48 ms;
-        // tensors capped at 160 / 100 / 60 / 30 parameters (6 / 8 / 11 / 20 tensors): 1.29 / 1.33 / 1.40 / 1.90 ms; every tensor
-        // forked over two streams: 1.31 - 1.34 ms.
-        std::vector<int> order((size_t)n_paths);
-        for (int i = 0; i < n_paths; ++i) {
-            order[(size_t)i] = i;
-            Plan& pl = plan[(size_t)i];
-            pl.off = arena; arena += pl.cols.size() * (size_t)pl.M * 8;
-        }
-        // 2. one batched decode into the arena ([P][M] per file, packed) + chain / draw ids behind it
-        const size_t ids_base = align_up(arena, 256);
-        const size_t lay_base = align_up(ids_base + ids, 256), lay_out = align_up(lay_base + (size_t)n_paths * sizeof(pq::FileIds), 256);
-        rc = ensure_buf(ctx, &ctx->fs_arena, &ctx->fs_arena_bytes, lay_out + (size_t)n_paths * 32 + 256);
-        if (rc) return rc;
-        char* base = (char*)ctx->fs_arena;
-        std::vector<mcr_parquet_request> reqs;
-        for (int i = 0; i < n_paths; ++i) {
-            const Plan& pl = plan[(size_t)i];
-            for (size_t j = 0; j < pl.cols.size(); ++j)
-                reqs.push_back(mcr_parquet_request{mf[(size_t)i].pq, pl.cols[j], MCR_PQ_F64, base + pl.off + j * (size_t)pl.M * 8});
-            reqs.push_back(mcr_parquet_request{mf[(size_t)i].pq, pl.chain, MCR_PQ_I64, base + ids_base + pl.ioff});
-            reqs.push_back(mcr_parquet_request{mf[(size_t)i].pq, pl.draw, MCR_PQ_I64, base + ids_base + pl.ioff + (size_t)pl.M * 8});
-        }
-        PqPlan PP;
-        if (!reqs.empty()) {
-            std::vector<FileBase> bases;
-            for (int i = 0; i < n_paths; ++i) bases.emplace_back(&mf[(size_t)i].pq->f, img_off[(size_t)i]);
-            std::sort(bases.begin(), bases.end(), [](const FileBase& a, const FileBase& b) { return std::less<const pq::File*>()(a.first, b.first); });
-            rc = pq_plan(ctx, reqs.data(), (int)reqs.size(), PP, &bases, img_total);
-            if (rc) { hipStreamSynchronize(ctx->stream); return rc; }
-            rc = pq_buffers(ctx, PP);            // (pq_stage is large enough already: no reallocation under the uploads in flight)
-            if (rc) return rc;
-        }
-        lap(MCR_FS_PH_PLAN);
-        // 2c. decode kernels + the chain / draw bookkeeping on the device (k_chain_layout: 32 bytes per file come back
-        //     instead of the id columns)
-        std::vector<i64> h_lay((size_t)n_paths * 4, 0);
-        int h_err[2] = {0, 0};
-        if (!reqs.empty()) {
-            rc = pq_launch(ctx, PP);
-            if (rc) return rc;
-            std::vector<pq::FileIds> fids((size_t)n_paths);
-            for (int i = 0; i < n_paths; ++i) {
-                const Plan& pl = plan[(size_t)i];
-                fids[(size_t)i] = pq::FileIds{(const i64*)(base + ids_base + pl.ioff), (const i64*)(base + ids_base + pl.ioff + (size_t)pl.M * 8), pl.M};
-            }
-            HIP_TRY(ctx, hipMemcpyAsync(base + lay_base, fids.data(), fids.size() * sizeof(pq::FileIds), hipMemcpyHostToDevice, ctx->stream));
-            LAUNCH(ctx, K_GATHER, pq::k_chain_layout, dim3((unsigned)n_paths), dim3(256), 0, (const pq::FileIds*)(base + lay_base), (i64*)(base + lay_out));
-            HIP_TRY(ctx, hipMemcpyAsync(h_lay.data(), base + lay_out, (size_t)n_paths * 32, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipMemcpyAsync(h_err, PP.d_err, 8, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            prof_resolve(ctx);
-            rc = pq_error(ctx, h_err);
-            if (rc) return rc;
-        }
-        // 3. chain / draw bookkeeping (convert._chains_from_table): rows must already be in (chain, draw) order
-        for (int i = 0; i < n_paths; ++i) {
-            Plan& pl = plan[(size_t)i];
-            const i64* L = h_lay.data() + (size_t)i * 4;
-            if (pl.M > 0 && !L[3]) return fail(ctx, MCR_ELAYOUT, "%s: rows are not in (chain, draw) order", paths[i]);
-            const i64 C = pl.M > 0 ? L[0] : 0;
-            const bool equal = pl.M == 0 || L[2] != 0;
-            pl.C = C; pl.N = pl.M > 0 ? L[1] : 0;
-            if (diagnostics && !pl.cols.empty()) {
-                if (C < min_chains) return fail(ctx, MCR_EMINCHAINS, "%s: R-hat diagnostics require at least %d chains; got %lld chain(s)", paths[i], min_chains, (long long)C);
-                if (!equal) return fail(ctx, MCR_ELAYOUT, "%s: chains of unequal length", paths[i]);
-            }
-            if (!diagnostics && !pl.cols.empty() && pl.M == 0) return fail(ctx, MCR_EINVAL, "%s: cannot compute stats of empty columns", paths[i]);
-        }
-        lap(MCR_FS_PH_DECODE);
-        // 4. result set + jobs (runs of neighbouring files of one shape are one tensor)
         std::unique_ptr<mcr_fileset> fs(new mcr_fileset());
         fs->n_q = n_q;
-        fs->files.resize((size_t)n_paths);
-        for (int i = 0; i < n_paths; ++i) {
-            mcr_fileset::Entry& e = fs->files[(size_t)i];
-            const Plan& pl = plan[(size_t)i];
-            const size_t P = pl.cols.size();
-            for (int c : pl.cols) e.names.push_back(mf[(size_t)i].pq->f.cols[(size_t)c].name);
-            e.C = pl.C; e.N = pl.N;
-            for (int k = 0; k < MCR_FS_FIELDS; ++k) e.f[k].assign(k == MCR_FS_Q ? P * (size_t)n_q : P, NAN);
-        }
-        struct Job { int first, count; i64 C, N, P; };
-        std::vector<Job> jobs;
-        for (int oi = 0; oi < n_paths; ++oi) {             // (first / count index `order`, the arena's sequence of files)
-            const Plan& pl = plan[(size_t)order[(size_t)oi]];
-            if (pl.cols.empty()) continue;
-            const i64 Cj = diagnostics ? pl.C : 1, Nj = diagnostics ? pl.N : pl.M;
-            if (!jobs.empty()) {
-                Job& j = jobs.back();
-                const Plan& last = plan[(size_t)order[(size_t)(j.first + j.count - 1)]];
-                if (j.first + j.count == oi && j.C == Cj && j.N == Nj && last.off + last.cols.size() * (size_t)last.M * 8 == pl.off) {
-                    ++j.count; j.P += (i64)pl.cols.size();
-                    continue;
-                }
-            }
-            jobs.push_back(Job{oi, 1, Cj, Nj, (i64)pl.cols.size()});
-        }
-        fs->n_jobs = (int)jobs.size();
-        // per-job staging of the results (a job spans files; scattered back below)
-        constexpr int NF = MCR_FS_FIELDS;
-        std::vector<std::vector<double>> jf(jobs.size() * NF);
-        std::vector<std::vector<int64_t>> jl(jobs.size() * 2);
-        std::vector<int64_t> qlo((size_t)(n_q > 0 ? n_q : 1));
-        int err = MCR_OK;
-        char keep[512] = "";
-        for (size_t k = 0; k < jobs.size() && !err; ++k) {
-            const Job& j = jobs[k];
-            for (int q = 0; q < NF; ++q) jf[k * NF + q].assign(q == MCR_FS_Q ? (size_t)j.P * (size_t)n_q : (size_t)j.P, NAN);
-            jl[k * 2].assign((size_t)j.P, 0); jl[k * 2 + 1].assign((size_t)j.P, 0);
-            mcr_summary o{};
-            o.mean = jf[k * NF + MCR_FS_MEAN].data(); o.std = jf[k * NF + MCR_FS_STD].data();
-            o.q = n_q > 0 ? jf[k * NF + MCR_FS_Q].data() : nullptr; o.median = jf[k * NF + MCR_FS_MEDIAN].data();
-            o.q_lo = qlo.data();
-            if (diagnostics) {
-                o.rhat = jf[k * NF + MCR_FS_RHAT].data(); o.ess_bulk = jf[k * NF + MCR_FS_ESS_BULK].data();
-                o.ess_tail = jf[k * NF + MCR_FS_ESS_TAIL].data();
-                o.rhat_bulk = jf[k * NF + MCR_FS_RHAT_BULK].data(); o.rhat_tail = jf[k * NF + MCR_FS_RHAT_TAIL].data();
-                o.lag_bulk = jl[k * 2].data(); o.lag_tail = jl[k * 2 + 1].data();
-            }
-            if (ctx->n_inflight >= MCR_MAX_INFLIGHT) err = wait_one_impl(ctx);
-            if (!err)
-                err = enqueue_impl(ctx, base + plan[(size_t)order[(size_t)j.first]].off, MCR_F64, j.C, j.N, j.P, j.N, 1, j.C * j.N,
-                                   diagnostics ? min_chains : 1, quantiles, n_q, &o);
-            if (err) memcpy(keep, ctx->err, sizeof keep);
-        }
-        const int rw = wait_impl(ctx);
-        if (err) { memcpy(ctx->err, keep, sizeof keep); return err; }
-        if (rw) return rw;
+        using clk = std::chrono::steady_clock;
+        const clk::time_point t_start = clk::now();
+        clk::time_point t_prev = t_start;
+        auto lap = [&](int k) { const clk::time_point now = clk::now(); fs->phase_ms[k] += std::chrono::duration<double, std::milli>(now - t_prev).count(); t_prev = now; };
+        FileBatch B(paths, n_paths);
+        int rc = fs_open(ctx, B);
+        if (rc) return rc;
+        lap(MCR_FS_PH_OPEN);
+        StreamSync uploads{ctx->stream};   // they read pq_pin, which the next call's readers write: a return waits for them
+        rc = fs_read(ctx, B);
+        if (!rc) { lap(MCR_FS_PH_READ); rc = fs_layout(ctx, B); }
+        if (!rc) { lap(MCR_FS_PH_PLAN); rc = fs_decode(ctx, B, min_chains, diagnostics); }
+        if (rc) return rc;
+        uploads.st = nullptr;                                 // fs_decode waited for the stream
+        lap(MCR_FS_PH_DECODE);
+        Staged S;
+        rc = fs_stats(ctx, B, *fs, S, min_chains, quantiles, n_q, diagnostics);
+        if (rc) return rc;
         lap(MCR_FS_PH_STATS);
-        if (diagnostics)
-            for (size_t k = 0; k < jobs.size(); ++k)
-                for (size_t p = 0; p < (size_t)jobs[k].P; ++p) {
-                    jf[k * NF + MCR_FS_LAG_BULK][p] = (double)jl[k * 2][p];
-                    jf[k * NF + MCR_FS_LAG_TAIL][p] = (double)jl[k * 2 + 1][p];
-                }
-        for (size_t k = 0; k < jobs.size(); ++k) {
-            size_t p0 = 0;
-            for (int oi = jobs[k].first; oi < jobs[k].first + jobs[k].count; ++oi) {
-                mcr_fileset::Entry& e = fs->files[(size_t)order[(size_t)oi]];
-                const size_t P = e.names.size();
-                for (int q = 0; q < NF; ++q) {
-                    const size_t w = q == MCR_FS_Q ? (size_t)n_q : 1;
-                    if (w) memcpy(e.f[q].data(), jf[k * NF + q].data() + p0 * w, P * w * sizeof(double));
-                }
-                p0 += P;
-            }
-        }
+        fs_scatter(S, diagnostics, *fs);
         lap(MCR_FS_PH_COLLECT);
-        mf.clear();                                   // unmap, close, free the parsed metadata
+        B.f.clear();                                          // close, free the parsed metadata
         lap(MCR_FS_PH_CLOSE);
-        phase[MCR_FS_PH_TOTAL] = std::chrono::duration<double, std::milli>(clk::now() - t_start).count();
-        memcpy(fs->phase_ms, phase, sizeof phase);
+        fs->phase_ms[MCR_FS_PH_TOTAL] = std::chrono::duration<double, std::milli>(clk::now() - t_start).count();
         *out = fs.release();
         return MCR_OK;
     } catch (const std::exception& e) {
