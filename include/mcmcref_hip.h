@@ -96,8 +96,7 @@ int mcr_device_count(void);
 /* Creates a context bound to HIP device `device` (own non-blocking streams, lazily grown
  * workspaces).  Fails with MCR_ENODEVICE when no GPU is present: there is no CPU fallback.
  * Environment read here: MCR_LANES (streams + workspaces that consecutive calls rotate over,
- * default 4, max MCR_MAX_INFLIGHT), MCR_GRAPH=1 (hipGraph capture / replay of the launch
- * sequence; off by default), MCR_WORKSPACE_MB (see mcr_set_workspace_limit).
+ * default 4, max MCR_MAX_INFLIGHT), MCR_WORKSPACE_MB (see mcr_set_workspace_limit).
  * Limits: C <= 256 chains, C * N < 2^31 pooled draws per parameter (rank codes are 32-bit),
  * any number of parameters (chunked through the workspace). */
 int mcr_init(int device, mcr_ctx** out);
@@ -241,9 +240,8 @@ int mcr_fill_synthetic_at(mcr_ctx* ctx, void* draws_dev, int dtype, int64_t C, i
  * against MCR_COMM_TIMEOUT_S (default 300).  A peer that never arrives or dies -- the reference's loop
  * simply continues past a failed recipe, src/mcmc_ref/generate.py:77-96 -- ends the call with MCR_ECOMM
  * naming the call and the rank after that time instead of blocking for ever; the communicator is
- * aborted (ncclCommAbort) and every later call on it fails at once.  MCR_COMM_NONBLOCKING=1 creates
- * the communicator with ncclCommInitRankConfig(blocking = 0); MCR_COMM_BLOCKING=1 switches the
- * deadlines off (plain blocking calls); mcr_comm_has_deadline tells.
+ * aborted (ncclCommAbort) and every later call on it fails at once.  A collective that fails or
+ * times out leaves the caller's output buffer unwritten: the result is copied out only after the wait.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct mcr_comm mcr_comm;
 #define MCR_COMM_ID_BYTES 128
@@ -253,7 +251,7 @@ int mcr_comm_init(mcr_ctx* ctx, const void* id, int world, int rank, mcr_comm** 
 void mcr_comm_free(mcr_comm* comm);
 int mcr_comm_world(const mcr_comm* comm);
 int mcr_comm_rank(const mcr_comm* comm);
-int mcr_comm_has_deadline(const mcr_comm* comm); /* 1: every wait on this communicator is bounded */
+int mcr_comm_has_deadline(const mcr_comm* comm); /* 1 for any communicator: every wait is bounded */
 /* ncclAllGather: every rank sends `count` doubles and receives world * count doubles in rank order. */
 int mcr_comm_all_gather(mcr_comm* comm, const double* send, int64_t count, double* recv);
 /* ncclAllReduce in place over n doubles; op: 0 = sum, 1 = max, 2 = min (max-over-ranks clock, all-valid flag). */

@@ -45,6 +45,7 @@ static_assert(kTileNT * kTileVT == kTile && kMergeNT * kMergeVT == kTile, "sort 
 constexpr i64 kIdx16Max = 65535;      // pooled arrays up to this length carry 16-bit positions through the sort
 constexpr int kMaxChains = 256;
 constexpr int kMaxGridY = 65535;
+constexpr int kT3Workgroups = 256;    // workgroups of a k_tier3 launch (they share the (listed pair, lag group) items)
 
 enum KernelId {
     K_INGEST = 0, K_MOMENTS, K_MOMENTS_FINAL, K_TILE_SORT, K_MERGE, K_ORDER_STATS, K_RANK_Z, K_FOLD_MERGE,
@@ -71,11 +72,6 @@ struct Slot {
     i64 pcmax = 0;             // parameters per workspace chunk: chunk k has the results of [k pcmax, (k + 1) pcmax)
 };
 
-struct GraphEntry {
-    std::vector<uint64_t> key;
-    hipGraphExec_t exec = nullptr;
-};
-
 char g_init_err[512] = "";
 
 }  // namespace
@@ -92,7 +88,6 @@ struct mcr_ctx {
     hipStream_t lane_aux[MCR_MAX_INFLIGHT] = {};      // second stream of a lane + its fork / join events (lone calls: run_pipeline)
     hipEvent_t lane_fork[MCR_MAX_INFLIGHT] = {}, lane_join[MCR_MAX_INFLIGHT] = {};
     bool fork_lone = true;                            // MCR_FORK=0: never fork
-    int t3_workgroups = 256;                          // MCR_T3_WG: workgroups of a k_tier3 launch (they share the (listed pair, lag group) items)
     void* lane_ws[MCR_MAX_INFLIGHT] = {};
     size_t lane_ws_bytes[MCR_MAX_INFLIGHT] = {};
     int lane = 0, n_lanes = 4;
@@ -120,16 +115,11 @@ struct mcr_ctx {
     std::vector<hipEvent_t> free_ev;
     int64_t k_launches[K_COUNT] = {0};
     double k_ms[K_COUNT] = {0};
-    // hipGraph cache: the launch sequence of one summarize call is static for a given shape,
-    // buffer set and slot, so it is captured once and replayed (removes ~5 us of host launch gap
-    // between each of the ~12 kernels).  Disabled while profiling (events sit between kernels).
     bool fft_on = true;      // MCR_FFT=0: long chains take the direct tier-3 rounds only (A/B measurements, parity tests)
     bool f32_records = true; // MCR_F32_RECORDS=0: f32 tensors take the f64 kernels (widened by the tile sort) instead of mcr_sort32.hpp
     bool splitters_pairwise = false;   // MCR_SPLITTERS_PAIRWISE=1: rank the regular samples pair by pair whatever their number (A/B, parity tests)
     double rho_band = kRhoBand;   // MCR_RHO_BAND: half-width of the guard band of the tier-3 scan (0 = decide on the raw values)
     unsigned* guard_count = nullptr;   // device counter: band lags re-derived the reference's way (mcr_rho_guard_count)
-    bool graph_on = false;   // MCR_GRAPH=1: capture / replay (measured: no throughput gain, +0.17 ms per synchronous call)
-    std::vector<GraphEntry> graphs;
 };
 
 namespace {
@@ -206,19 +196,11 @@ void sync_all(mcr_ctx* ctx)
     for (hipStream_t s : ctx->lane_stream) if (s) hipStreamSynchronize(s);
 }
 
-void drop_graphs(mcr_ctx* ctx)   // waits for every lane first (a cached graph may be in flight on any)
-{
-    sync_all(ctx);
-    for (GraphEntry& g : ctx->graphs)
-        if (g.exec) hipGraphExecDestroy(g.exec);
-    ctx->graphs.clear();
-}
-
 int ensure_ws(mcr_ctx* ctx, size_t bytes)
 {
     if (bytes <= ctx->ws_bytes) return MCR_OK;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    drop_graphs(ctx);
+    sync_all(ctx);
     if (ctx->ws) { hipFree(ctx->ws); ctx->ws = nullptr; ctx->ws_bytes = 0; }
     const size_t want = bytes + (bytes >> 3);  // a little slack so near-equal shapes do not realloc
     hipError_t e = hipMalloc(&ctx->ws, want);
@@ -247,7 +229,6 @@ int get_ztab(mcr_ctx* ctx, i64 M, double** out)
         }
     if (ctx->ztabs.size() >= kMaxZTabs) {           // the evicted table may still be read by a call in flight
         sync_all(ctx);
-        drop_graphs(ctx);
         hipFree(ctx->ztabs.back().tab);
         ctx->ztabs.pop_back();
     }
@@ -302,7 +283,7 @@ int ensure_slot(mcr_ctx* ctx, Slot& s, size_t res_doubles, size_t off_entries)
 {
     if (res_doubles > s.res_cap || off_entries > s.off_cap) {
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        drop_graphs(ctx);
+        sync_all(ctx);
     }
     if (res_doubles > s.res_cap) {
         if (s.d_res) hipFree(s.d_res);
@@ -516,10 +497,10 @@ int launch_diag(mcr_ctx* ctx, const PipeIn& a)
     if (a.n <= kLag2) return MCR_OK;       // chains short enough to be decided by lag 255 never reach tier 3
     if (fused_tier3) {
         // the common case in ONE launch: list, products of the lags [256, n) stage by stage, scans (k_tier3); a fixed number
-        // of workgroups (MCR_T3_WG) shares the (listed pair, lag group) items
+        // of workgroups (kT3Workgroups) shares the (listed pair, lag group) items
         const i64 groups = (a.n - kLag2 + kLongGroup - 1) / kLongGroup;
         const i64 most = 2 * a.pc * groups;                                  // work items if every pair were listed
-        const unsigned wgs = (unsigned)(most < (i64)ctx->t3_workgroups ? most : (i64)ctx->t3_workgroups);
+        const unsigned wgs = (unsigned)(most < (i64)kT3Workgroups ? most : (i64)kT3Workgroups);
         LAUNCH(ctx, K_ACOV_LONG, k_tier3, dim3(wgs), dim3(256), 0, (const double*)a.kA, (const double*)a.kB, a.M, a.d_off,
                a.C, a.n, (const unsigned*)a.more, a.state, a.acov, a.d_res, a.pc, ctx->rho_band, ctx->guard_count, a.t3c,
                (const u32*)a.zb, (const u32*)a.zt, (const double*)a.ztab, a.chstate);
@@ -978,74 +959,37 @@ int enqueue_impl(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i
         call.nstage = N > 0 ? N : 1; call.do_diag = do_diag;
         rc = get_tables(ctx, call, cp.fp, do_diag);
         if (rc) return rc;
-        // Everything below only enqueues stream work with arguments that are a pure function of `key`.
-        auto issue = [&]() -> int {
-            if (!off_resident)
-                HIP_TRY(ctx, hipMemcpyAsync(s.d_off, s.h_off, sizeof(i64) * (size_t)(C + 1), hipMemcpyHostToDevice, ctx->stream));
-            for (i64 p0 = 0; p0 < P; p0 += pcmax) {
-                const i64 pc = (P - p0 < pcmax) ? P - p0 : pcmax;
-                Carve cv{reinterpret_cast<char*>(ctx->ws), ctx->ws_bytes};
-                PipeIn a = call;
-                a.pc = pc;
-                double* X = carve_pipe(cv, a, true, cp.fp, cp.ingest);
-                if (cv.over()) return fail(ctx, MCR_ENOMEM, "workspace layout needs %zu bytes; the workspace has %zu", cv.off, cv.end);
-                // (a graph capture or the per-kernel event pairs of the profiling mode keep the single stream)
-                a.fork = ctx->fork_lone && ctx->order.empty() && !ctx->prof && !ctx->graph_on && P <= pcmax &&
-                         (double)M * (double)pc >= 2e6 && (double)M * (double)pc <= 8e6;    // kernels long enough to be worth
-                                                   // three more launches and two event waits (measured: C1 4 M param-draws 306 -> 288 us,
-                                                   // 10 x 1000 x 45 149 -> 166, 4 x 1000 x 10 124 -> 133), short enough not to fill the chip
-                if (cp.ingest) {
-                    const int r2 = (dtype == MCR_F64) ? launch_ingest<double>(ctx, draws_dev, X, C, N, pc, sc, sn, sp, p0)
-                                                      : launch_ingest<float>(ctx, draws_dev, X, C, N, pc, sc, sn, sp, p0);
-                    if (r2) return r2;
-                    a.X = X;
-                } else {
-                    a.x_f32 = dtype == MCR_F32;
-                    a.records = a.x_f32 && a.bk_B > 0 && ctx->f32_records;
-                    a.X = a.x_f32 ? (const void*)(reinterpret_cast<const float*>(draws_dev) + p0 * M)
-                                  : (const void*)(reinterpret_cast<const double*>(draws_dev) + p0 * M);
-                }
-                a.d_res = s.d_res + (size_t)R * (size_t)p0;
-                const int r3 = run_pipeline(ctx, a);
-                if (r3) return r3;
+        if (!off_resident)
+            HIP_TRY(ctx, hipMemcpyAsync(s.d_off, s.h_off, sizeof(i64) * (size_t)(C + 1), hipMemcpyHostToDevice, ctx->stream));
+        for (i64 p0 = 0; p0 < P; p0 += pcmax) {
+            const i64 pc = (P - p0 < pcmax) ? P - p0 : pcmax;
+            Carve cv{reinterpret_cast<char*>(ctx->ws), ctx->ws_bytes};
+            PipeIn a = call;
+            a.pc = pc;
+            double* X = carve_pipe(cv, a, true, cp.fp, cp.ingest);
+            if (cv.over()) return fail(ctx, MCR_ENOMEM, "workspace layout needs %zu bytes; the workspace has %zu", cv.off, cv.end);
+            // (the per-kernel event pairs of the profiling mode keep the single stream)
+            a.fork = ctx->fork_lone && ctx->order.empty() && !ctx->prof && P <= pcmax &&
+                     (double)M * (double)pc >= 2e6 && (double)M * (double)pc <= 8e6;    // kernels long enough to be worth
+                                               // three more launches and two event waits (measured: C1 4 M param-draws 306 -> 288 us,
+                                               // 10 x 1000 x 45 149 -> 166, 4 x 1000 x 10 124 -> 133), short enough not to fill the chip
+            if (cp.ingest) {
+                rc = (dtype == MCR_F64) ? launch_ingest<double>(ctx, draws_dev, X, C, N, pc, sc, sn, sp, p0)
+                                        : launch_ingest<float>(ctx, draws_dev, X, C, N, pc, sc, sn, sp, p0);
+                if (rc) return rc;
+                a.X = X;
+            } else {
+                a.x_f32 = dtype == MCR_F32;
+                a.records = a.x_f32 && a.bk_B > 0 && ctx->f32_records;
+                a.X = a.x_f32 ? (const void*)(reinterpret_cast<const float*>(draws_dev) + p0 * M)
+                              : (const void*)(reinterpret_cast<const double*>(draws_dev) + p0 * M);
             }
-            HIP_TRY(ctx, hipMemcpyAsync(s.h_res, s.d_res, sizeof(double) * (size_t)R * (size_t)P, hipMemcpyDeviceToHost,
-                                        ctx->stream));
-            return MCR_OK;
-        };
-        if (ctx->graph_on && !ctx->prof) {
-            std::vector<uint64_t> key = {(uint64_t)(uintptr_t)draws_dev, (uint64_t)dtype, (uint64_t)C, (uint64_t)N,
-                                         (uint64_t)P, (uint64_t)sc, (uint64_t)sn, (uint64_t)sp, (uint64_t)nq,
-                                         (uint64_t)si, (uint64_t)do_diag, (uint64_t)(uintptr_t)ctx->ws,
-                                         (uint64_t)(uintptr_t)s.d_res, (uint64_t)(uintptr_t)s.d_off,
-                                         (uint64_t)pcmax, (uint64_t)(uintptr_t)call.ztab, (uint64_t)off_resident};
-            for (int k = 0; k < nq; ++k) {
-                uint64_t bits; memcpy(&bits, &q.g[k], 8);
-                key.push_back((uint64_t)q.lo[k]); key.push_back(bits);
-            }
-            GraphEntry* hit = nullptr;
-            for (GraphEntry& g : ctx->graphs) if (g.key == key) { hit = &g; break; }
-            if (!hit) {
-                if (ctx->graphs.size() >= 64) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); drop_graphs(ctx); }
-                HIP_TRY(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-                rc = issue();
-                hipGraph_t graph = nullptr;
-                const hipError_t ce = hipStreamEndCapture(ctx->stream, &graph);
-                if (rc) { if (graph) hipGraphDestroy(graph); return rc; }
-                if (ce != hipSuccess) return fail(ctx, MCR_EHIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
-                GraphEntry ge;
-                ge.key = key;
-                const hipError_t ie = hipGraphInstantiate(&ge.exec, graph, nullptr, nullptr, 0);
-                hipGraphDestroy(graph);
-                if (ie != hipSuccess) return fail(ctx, MCR_EHIP, "hipGraphInstantiate failed: %s", hipGetErrorString(ie));
-                ctx->graphs.push_back(std::move(ge));
-                hit = &ctx->graphs.back();
-            }
-            HIP_TRY(ctx, hipGraphLaunch(hit->exec, ctx->stream));
-        } else {
-            rc = issue();
+            a.d_res = s.d_res + (size_t)R * (size_t)p0;
+            rc = run_pipeline(ctx, a);
             if (rc) return rc;
         }
+        HIP_TRY(ctx, hipMemcpyAsync(s.h_res, s.d_res, sizeof(double) * (size_t)R * (size_t)P, hipMemcpyDeviceToHost,
+                                    ctx->stream));
     }
     if (!s.trivial_nan) { s.off_C = C; s.off_N = N; }
     rc = commit_slot(ctx, si);
@@ -1223,12 +1167,10 @@ int mcr_init(int device, mcr_ctx** out)
     size_t mb = 8192;
     if (const char* env = getenv("MCR_WORKSPACE_MB")) { const long v = atol(env); if (v > 0) mb = (size_t)v; }
     ctx->ws_limit = mb << 20;
-    if (const char* env = getenv("MCR_GRAPH")) ctx->graph_on = atoi(env) != 0;
     if (const char* env = getenv("MCR_F32_RECORDS")) ctx->f32_records = atoi(env) != 0;
     if (const char* env = getenv("MCR_FFT")) ctx->fft_on = atoi(env) != 0;
     if (const char* env = getenv("MCR_SPLITTERS_PAIRWISE")) ctx->splitters_pairwise = atoi(env) != 0;
     if (const char* env = getenv("MCR_FORK")) ctx->fork_lone = atoi(env) != 0;
-    if (const char* env = getenv("MCR_T3_WG")) { const int v = atoi(env); if (v > 0) ctx->t3_workgroups = v; }
     if (const char* env = getenv("MCR_RHO_BAND")) { const double v = atof(env); if (v >= 0.0 && v < 1.0) ctx->rho_band = v; }
     if (hipMalloc((void**)&ctx->guard_count, sizeof(unsigned)) != hipSuccess ||
         hipMemsetAsync(ctx->guard_count, 0, sizeof(unsigned), ctx->stream) != hipSuccess ||
@@ -1247,7 +1189,6 @@ void mcr_free(mcr_ctx* ctx)
     sync_all(ctx);
     use_lane(ctx, 0);
     prof_resolve(ctx);
-    drop_graphs(ctx);
     for (hipEvent_t e : ctx->free_ev) hipEventDestroy(e);
     for (Slot& s : ctx->slots) {
         if (s.done) hipEventDestroy(s.done);
@@ -1839,8 +1780,6 @@ struct mcr_comm {
     hipStream_t stream = nullptr;
     int world = 1, rank = 0;
     void* dbuf = nullptr; size_t dbytes = 0;      // device staging (send block + receive blocks)
-    bool deadline = true;                         // every wait is bounded by timeout_s (MCR_COMM_BLOCKING=1 switches that off)
-    bool nonblocking = false;                     // MCR_COMM_NONBLOCKING=1: communicator created with config.blocking = 0
     bool dead = false;                            // aborted after a deadline or an asynchronous error
     double timeout_s = 300.0;                     // MCR_COMM_TIMEOUT_S
 };
@@ -1849,7 +1788,7 @@ namespace {
 int comm_fail(mcr_ctx* ctx, const char* what, ncclResult_t r)
 {
     mcr::comm::Api* a = mcr::comm::api();
-    return fail(ctx, MCR_ECOMM, "%s failed: %s", what, (a && a->GetErrorString) ? a->GetErrorString(r) : "RCCL error");
+    return fail(ctx, MCR_ECOMM, "%s failed: %s", what, a ? a->GetErrorString(r) : "RCCL error");
 }
 int comm_buf(mcr_comm* c, size_t bytes)
 {
@@ -1868,13 +1807,13 @@ int comm_buf(mcr_comm* c, size_t bytes)
 //   * the collectives are enqueued on the communicator's stream as usual (the RCCL call returns once its kernel is in the
 //     stream) and the wait for that stream is a poll of hipStreamQuery + ncclCommGetAsyncError against
 //     MCR_COMM_TIMEOUT_S (default 300 s; the first init of a node can take tens of seconds) instead of a
-//     hipStreamSynchronize;
+//     hipStreamSynchronize.  Only then is the result copied to the caller's (pageable) buffer: that copy would block
+//     the host behind a stuck collective;
 //   * on expiry, or on an asynchronous RCCL error, the communicator is aborted (ncclCommAbort, itself bounded: it tears
 //     down the stuck kernel and the proxy), marked dead, and the call returns MCR_ECOMM naming the call, the rank and the
 //     time; every later call on it fails at once.
-// The communicator itself is the ordinary BLOCKING one (what every RCCL application runs; its first world > 1 run here
-// is the driver's); MCR_COMM_NONBLOCKING=1 creates it with ncclCommInitRankConfig(blocking = 0) instead, where the RCCL
-// calls themselves return ncclInProgress and are polled too.  MCR_COMM_BLOCKING=1: no deadlines at all (round 3).
+// The communicator itself is the ordinary BLOCKING one (what every RCCL application runs).  A non-blocking one and a mode
+// without deadlines were built and removed.
 using comm_clock = std::chrono::steady_clock;
 
 // ncclCommAbort with a bound of its own: measured on RCCL 2.27.7, aborting a communicator whose ncclCommInitRank is still
@@ -1885,7 +1824,7 @@ constexpr double kAbortGraceS = 5.0;
 void bounded_abort(ncclComm_t nccl)
 {
     mcr::comm::Api* a = mcr::comm::api();
-    if (!a || !a->CommAbort || !nccl) return;
+    if (!a || !nccl) return;
     auto done = std::make_shared<std::atomic<int>>(0);
     std::thread([a, nccl, done]() { a->CommAbort(nccl); done->store(1, std::memory_order_release); }).detach();
     const comm_clock::time_point t0 = comm_clock::now();
@@ -1902,45 +1841,50 @@ int comm_abort(mcr_comm* c, const char* what, const char* why)
                 what, c->rank, c->world, why, c->timeout_s);
 }
 
-// Waits until the communicator's pending RCCL call has been issued (non-blocking mode: state leaves ncclInProgress) and,
-// with `stream`, until the work on its stream has finished.
-int comm_wait(mcr_comm* c, const char* what, bool stream)
+// Waits until the work on the communicator's stream has finished, the communicator reports an asynchronous error, or
+// the deadline passes.
+int comm_wait(mcr_comm* c, const char* what)
 {
     mcr::comm::Api* a = mcr::comm::api();
     const comm_clock::time_point t0 = comm_clock::now();
-    auto expired = [&]() { return std::chrono::duration<double>(comm_clock::now() - t0).count() > c->timeout_s; };
-    auto nap = [&](int& spins) { if (++spins > 2000) std::this_thread::sleep_for(std::chrono::microseconds(50)); };
-    int spins = 0;
-    if (c->nonblocking) {
-        for (;;) {
-            ncclResult_t st = ncclSuccess;
-            const ncclResult_t r = a->CommGetAsyncError(c->nccl, &st);
-            if (r != ncclSuccess) { comm_abort(c, what, "ncclCommGetAsyncError failed"); return MCR_ECOMM; }
-            if (st == ncclSuccess) break;
-            if (st != ncclInProgress) {
-                char why[160];
-                snprintf(why, sizeof why, "asynchronous RCCL error: %s", a->GetErrorString ? a->GetErrorString(st) : "?");
-                return comm_abort(c, what, why);
-            }
-            if (expired()) return comm_abort(c, what, "a peer did not arrive before the deadline");
-            nap(spins);
-        }
-    }
-    if (!stream) return MCR_OK;
-    if (!c->deadline) { HIP_TRY(c->ctx, hipStreamSynchronize(c->stream)); return MCR_OK; }
-    for (;;) {
+    for (int spins = 0;; ) {
         const hipError_t q = hipStreamQuery(c->stream);
         if (q == hipSuccess) return MCR_OK;
         if (q != hipErrorNotReady) return fail(c->ctx, MCR_EHIP, "%s: hipStreamQuery failed: %s", what, hipGetErrorString(q));
         ncclResult_t st = ncclSuccess;
-        if (a->CommGetAsyncError && a->CommGetAsyncError(c->nccl, &st) == ncclSuccess && st != ncclSuccess && st != ncclInProgress) {
+        if (a->CommGetAsyncError(c->nccl, &st) == ncclSuccess && st != ncclSuccess && st != ncclInProgress) {
             char why[160];
-            snprintf(why, sizeof why, "asynchronous RCCL error: %s", a->GetErrorString ? a->GetErrorString(st) : "?");
+            snprintf(why, sizeof why, "asynchronous RCCL error: %s", a->GetErrorString(st));
             return comm_abort(c, what, why);
         }
-        if (expired()) return comm_abort(c, what, "the collective did not complete before the deadline (a peer is gone or stuck)");
-        nap(spins);
+        if (std::chrono::duration<double>(comm_clock::now() - t0).count() > c->timeout_s)
+            return comm_abort(c, what, "the collective did not complete before the deadline (a peer is gone or stuck)");
+        if (++spins > 2000) std::this_thread::sleep_for(std::chrono::microseconds(50));
     }
+}
+
+// The one path of both collectives: `in_bytes` from `in` are uploaded to the front of the staging buffer, `rccl` issues
+// the collective on the communicator's stream with (staging, staging + out_at), and the `out_bytes` at out_at are
+// copied to `out` -- after the bounded wait, so a timeout or an RCCL error never writes the caller's buffer.
+int comm_collective(mcr_comm* c, const char* what, bool args_ok, const double* in, size_t in_bytes, double* out,
+                    size_t out_at, size_t out_bytes, const std::function<ncclResult_t(void*, void*)>& rccl)
+{
+    mcr_ctx* ctx = c->ctx;
+    if (c->dead) return fail(ctx, MCR_ECOMM, "%s: the communicator of rank %d was aborted by an earlier failure", what, c->rank);
+    if (!args_ok) return fail(ctx, MCR_EINVAL, "bad argument");
+    if (in_bytes == 0) return MCR_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = comm_buf(c, out_at + out_bytes);
+    if (rc) return rc;
+    char* d = (char*)c->dbuf;
+    HIP_TRY(ctx, hipMemcpyAsync(d, in, in_bytes, hipMemcpyHostToDevice, c->stream));
+    const ncclResult_t r = rccl(d, d + out_at);
+    if (r != ncclSuccess) return comm_fail(ctx, what, r);
+    rc = comm_wait(c, what);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(out, d + out_at, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(c->stream));
+    return MCR_OK;
 }
 }  // namespace
 
@@ -1969,69 +1913,41 @@ int mcr_comm_init(mcr_ctx* ctx, const void* id, int world, int rank, mcr_comm** 
     if (!c) return fail(ctx, MCR_ENOMEM, "out of host memory");
     c->ctx = ctx; c->world = world; c->rank = rank;
     if (const char* env = getenv("MCR_COMM_TIMEOUT_S")) { const double v = atof(env); if (v > 0.0) c->timeout_s = v; }
-    const char* blk = getenv("MCR_COMM_BLOCKING");
-    const char* nbl = getenv("MCR_COMM_NONBLOCKING");
-    c->deadline = !(blk && atoi(blk) != 0);
-    c->nonblocking = c->deadline && a->nonblocking() && nbl && atoi(nbl) != 0;
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) { delete c; return fail(ctx, MCR_EHIP, "hipStreamCreate failed: %s", hipGetErrorString(e)); }
     ncclUniqueId uid;
     memcpy(&uid, id, sizeof uid);
-    // collective: every rank of the world calls it
-    if (c->deadline) {
-        // The whole init runs on a helper thread and THIS thread only watches the clock: on RCCL 2.27.7 neither the init of a
-        // rank whose peers never come nor an abort of it is guaranteed to return, and the caller must get its error anyway.
-        struct InitJob {
-            std::atomic<int> state{0}, cancel{0};      // state 1: finished (r / async say how)
-            std::atomic<ncclComm_t> nccl{nullptr};
-            ncclResult_t r = ncclSuccess, async = ncclSuccess;
-        };
-        auto job = std::make_shared<InitJob>();
-        const int dev = ctx->device;
-        const bool nonblocking = c->nonblocking;
-        std::thread([a, job, dev, world, uid, rank, nonblocking]() {
-            hipSetDevice(dev);
-            ncclComm_t h = nullptr;
-            if (nonblocking) {
-                ncclConfig_t cfg = NCCL_CONFIG_INITIALIZER;
-                cfg.blocking = 0;
-                job->r = a->CommInitRankConfig(&h, world, uid, rank, &cfg);
-            } else {
-                job->r = a->CommInitRank(&h, world, uid, rank);          // returns when every rank has arrived -- or never
-            }
-            job->nccl.store(h, std::memory_order_release);
-            if (nonblocking && (job->r == ncclSuccess || job->r == ncclInProgress) && h) {
-                ncclResult_t st = ncclInProgress;
-                int spins = 0;
-                while (!job->cancel.load(std::memory_order_acquire)) {
-                    if (a->CommGetAsyncError(h, &st) != ncclSuccess) { st = ncclInternalError; break; }
-                    if (st != ncclInProgress) break;
-                    if (++spins > 2000) std::this_thread::sleep_for(std::chrono::microseconds(50));
-                }
-                job->async = st;
-            }
-            job->state.store(1, std::memory_order_release);
-        }).detach();
-        const comm_clock::time_point t0 = comm_clock::now();
-        int spins = 0;
-        while (!job->state.load(std::memory_order_acquire) &&
-               std::chrono::duration<double>(comm_clock::now() - t0).count() <= c->timeout_s)
-            if (++spins > 2000) std::this_thread::sleep_for(std::chrono::microseconds(100));
-        int rc = MCR_OK;
-        if (!job->state.load(std::memory_order_acquire)) {
-            job->cancel.store(1, std::memory_order_release);
-            bounded_abort(job->nccl.load(std::memory_order_acquire));
-            rc = fail(ctx, MCR_ECOMM, "ncclCommInitRank: rank %d of %d gave up: a peer did not arrive before the deadline "
-                      "(MCR_COMM_TIMEOUT_S = %g s); the communicator was aborted", rank, world, c->timeout_s);
-        } else if (job->r != ncclSuccess && job->r != ncclInProgress) rc = comm_fail(ctx, "ncclCommInitRank", job->r);
-        else if (!job->nccl.load()) rc = fail(ctx, MCR_ECOMM, "ncclCommInitRank returned no communicator");
-        else if (job->async != ncclSuccess) { bounded_abort(job->nccl.load()); rc = comm_fail(ctx, "ncclCommInitRank (asynchronous)", job->async); }
-        if (rc) { hipStreamDestroy(c->stream); delete c; return rc; }
-        c->nccl = job->nccl.load();
-    } else {
-        const ncclResult_t r = a->CommInitRank(&c->nccl, world, uid, rank);
-        if (r != ncclSuccess) { hipStreamDestroy(c->stream); delete c; return comm_fail(ctx, "ncclCommInitRank", r); }
-    }
+    // Collective: every rank of the world calls it.  The init runs on a helper thread and THIS thread only watches the
+    // clock: on RCCL 2.27.7 neither the init of a rank whose peers never come nor an abort of it is guaranteed to return,
+    // and the caller must get its error anyway.
+    struct InitJob {
+        std::atomic<int> state{0};                 // 1: finished (r says how)
+        std::atomic<ncclComm_t> nccl{nullptr};
+        ncclResult_t r = ncclSuccess;
+    };
+    auto job = std::make_shared<InitJob>();
+    const int dev = ctx->device;
+    std::thread([a, job, dev, world, uid, rank]() {
+        hipSetDevice(dev);
+        ncclComm_t h = nullptr;
+        job->r = a->CommInitRank(&h, world, uid, rank);          // returns when every rank has arrived -- or never
+        job->nccl.store(h, std::memory_order_release);
+        job->state.store(1, std::memory_order_release);
+    }).detach();
+    const comm_clock::time_point t0 = comm_clock::now();
+    int spins = 0;
+    while (!job->state.load(std::memory_order_acquire) &&
+           std::chrono::duration<double>(comm_clock::now() - t0).count() <= c->timeout_s)
+        if (++spins > 2000) std::this_thread::sleep_for(std::chrono::microseconds(100));
+    int rc = MCR_OK;
+    if (!job->state.load(std::memory_order_acquire)) {
+        bounded_abort(job->nccl.load(std::memory_order_acquire));   // nullptr unless the init returned just now
+        rc = fail(ctx, MCR_ECOMM, "ncclCommInitRank: rank %d of %d gave up: a peer did not arrive before the deadline "
+                  "(MCR_COMM_TIMEOUT_S = %g s); the communicator was aborted", rank, world, c->timeout_s);
+    } else if (job->r != ncclSuccess) rc = comm_fail(ctx, "ncclCommInitRank", job->r);
+    else if (!job->nccl.load()) rc = fail(ctx, MCR_ECOMM, "ncclCommInitRank returned no communicator");
+    if (rc) { hipStreamDestroy(c->stream); delete c; return rc; }
+    c->nccl = job->nccl.load();
     *out = c;
     return MCR_OK;
 }
@@ -2040,17 +1956,7 @@ void mcr_comm_free(mcr_comm* c)
 {
     if (!c) return;
     hipSetDevice(c->ctx->device);
-    mcr::comm::Api* a = mcr::comm::api();
-    if (c->nccl && !c->dead) {
-        if (c->deadline) {
-            if (comm_wait(c, "mcr_comm_free", true) == MCR_OK && c->nccl) {
-                a->CommDestroy(c->nccl);            // (returns ncclInProgress on a non-blocking communicator: finalisation goes on inside RCCL)
-            }
-        } else {
-            if (c->stream) hipStreamSynchronize(c->stream);
-            if (a) a->CommDestroy(c->nccl);
-        }
-    }
+    if (c->nccl && !c->dead && comm_wait(c, "mcr_comm_free") == MCR_OK) mcr::comm::api()->CommDestroy(c->nccl);
     if (c->dbuf) hipFree(c->dbuf);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
@@ -2058,31 +1964,18 @@ void mcr_comm_free(mcr_comm* c)
 
 int mcr_comm_world(const mcr_comm* c) { return c ? c->world : -1; }
 int mcr_comm_rank(const mcr_comm* c) { return c ? c->rank : -1; }
-int mcr_comm_has_deadline(const mcr_comm* c) { return (c && c->deadline) ? 1 : 0; }
+int mcr_comm_has_deadline(const mcr_comm* c) { return c ? 1 : 0; }
 
 // THE collective of the path: every rank contributes `count` doubles, every rank receives world * count doubles in
 // rank order (ncclAllGather over xGMI).  Host pointers; staged through a small device buffer on the communicator's stream.
 int mcr_comm_all_gather(mcr_comm* c, const double* send, int64_t count, double* recv)
 {
     if (!c) return fail(nullptr, MCR_EINVAL, "comm is NULL");
-    mcr_ctx* ctx = c->ctx;
-    if (c->dead) return fail(ctx, MCR_ECOMM, "ncclAllGather: the communicator of rank %d was aborted by an earlier failure", c->rank);
-    if (count < 0 || (count > 0 && (!send || !recv))) return fail(ctx, MCR_EINVAL, "bad argument");
-    if (count == 0) return MCR_OK;
-    mcr::comm::Api* a = mcr::comm::api();
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t sb = (size_t)count * 8, rb = sb * (size_t)c->world;
-    int rc = comm_buf(c, align_up(sb, 256) + rb);
-    if (rc) return rc;
-    char* d_send = (char*)c->dbuf;
-    char* d_recv = d_send + align_up(sb, 256);
-    HIP_TRY(ctx, hipMemcpyAsync(d_send, send, sb, hipMemcpyHostToDevice, c->stream));
-    const ncclResult_t r = a->AllGather(d_send, d_recv, (size_t)count, ncclDouble, c->nccl, c->stream);
-    if (r != ncclSuccess && r != ncclInProgress) return comm_fail(ctx, "ncclAllGather", r);
-    rc = comm_wait(c, "ncclAllGather", false);                 // issued (non-blocking mode)
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(recv, d_recv, rb, hipMemcpyDeviceToHost, c->stream));
-    return comm_wait(c, "ncclAllGather", true);
+    const size_t sb = (size_t)count * 8;
+    return comm_collective(c, "ncclAllGather", count >= 0 && (count == 0 || (send && recv)), send, sb, recv,
+                           align_up(sb, 256), sb * (size_t)c->world, [c, count](void* d_send, void* d_recv) {
+                               return mcr::comm::api()->AllGather(d_send, d_recv, (size_t)count, ncclDouble, c->nccl, c->stream);
+                           });
 }
 
 // Element-wise reduction of n host doubles over the ranks, in place (op: 0 sum, 1 max, 2 min): the bench's
@@ -2090,23 +1983,12 @@ int mcr_comm_all_gather(mcr_comm* c, const double* send, int64_t count, double* 
 int mcr_comm_all_reduce(mcr_comm* c, double* vals, int64_t n, int op)
 {
     if (!c) return fail(nullptr, MCR_EINVAL, "comm is NULL");
-    mcr_ctx* ctx = c->ctx;
-    if (c->dead) return fail(ctx, MCR_ECOMM, "ncclAllReduce: the communicator of rank %d was aborted by an earlier failure", c->rank);
-    if (n < 0 || (n > 0 && !vals) || op < 0 || op > 2) return fail(ctx, MCR_EINVAL, "bad argument");
-    if (n == 0) return MCR_OK;
-    mcr::comm::Api* a = mcr::comm::api();
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t b = (size_t)n * 8;
-    int rc = comm_buf(c, b);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(c->dbuf, vals, b, hipMemcpyHostToDevice, c->stream));
-    const ncclRedOp_t ops[3] = {ncclSum, ncclMax, ncclMin};
-    const ncclResult_t r = a->AllReduce(c->dbuf, c->dbuf, (size_t)n, ncclDouble, ops[op], c->nccl, c->stream);
-    if (r != ncclSuccess && r != ncclInProgress) return comm_fail(ctx, "ncclAllReduce", r);
-    rc = comm_wait(c, "ncclAllReduce", false);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(vals, c->dbuf, b, hipMemcpyDeviceToHost, c->stream));
-    return comm_wait(c, "ncclAllReduce", true);
+    return comm_collective(c, "ncclAllReduce", n >= 0 && (n == 0 || vals) && op >= 0 && op <= 2, vals, b, vals, 0, b,
+                           [c, n, op](void* d_in, void* d_out) {
+                               const ncclRedOp_t ops[3] = {ncclSum, ncclMax, ncclMin};
+                               return mcr::comm::api()->AllReduce(d_in, d_out, (size_t)n, ncclDouble, ops[op], c->nccl, c->stream);
+                           });
 }
 
 int mcr_comm_barrier(mcr_comm* c)

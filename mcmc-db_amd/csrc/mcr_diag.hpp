@@ -990,7 +990,7 @@ union Tier3Lds {
 };
 // ONE launch for the whole of tier 3 on chains of at most 16 384 draws and at most kTier3MaxPairs pairs per chunk -- what
 // every call of the C1 shape and of the packaged corpus takes, with nothing listed more often than not.  grid: a FIXED number
-// of workgroups (MCR_T3_WG), block 256.
+// of workgroups (kT3Workgroups in mcr_api.hip), block 256.
 //   * Every workgroup compacts the tier-3 marks of the 2 P pairs into its own LDS in ascending pair order (the list
 //     k_long_list would build; with nothing listed it is done after one pass over the marks).
 //   * The work items are (listed pair, group of 256 lags), handed out round-robin, STAGE by stage: stages of 2, 6, 8, 8, ...

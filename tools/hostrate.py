@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Host-side cost of one pipelined call: a tiny tensor (the kernels take no time), rolling window of 8 calls, with and
 without reuse of the result buffers.  What is measured is Python + ctypes + the library's launch sequence."""
-import os, sys, time
+import sys, time
 from pathlib import Path
 ROOT = Path(__file__).resolve().parents[1]
 sys.path[:0] = [str(ROOT), str(ROOT / "mcmc-db_amd")]
@@ -22,4 +22,4 @@ for reuse in (False, True):
     run(100)
     t0 = time.perf_counter()
     run(2000)
-    print(f"tiny call, buffer reuse {reuse}, MCR_GRAPH={os.environ.get('MCR_GRAPH', '0')}: {(time.perf_counter() - t0) / 2000 * 1e6:.1f} us per call")
+    print(f"tiny call, buffer reuse {reuse}: {(time.perf_counter() - t0) / 2000 * 1e6:.1f} us per call")

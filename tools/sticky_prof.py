@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Sticky chains at the C1 shape (every parameter AR(1) with phi = 0.99 / 0.999: dozens to hundreds of pairs in tier 3):
-per-kernel times of a lone call and the pipelined step; MCR_T3_WG sets how many workgroups a tier-3 launch aims at."""
+per-kernel times of a lone call and the pipelined step."""
 import os, sys, time
 from pathlib import Path
 import numpy as np
@@ -27,6 +27,6 @@ for phi, (C, N, P) in ((0.99, (4, 10000, 100)), (0.999, (4, 10000, 100)), (0.99,
             ctx.enqueue(t2)
         ctx.wait()
     run(20); t0 = time.perf_counter(); run(100); dt = (time.perf_counter() - t0) / 100
-    print(f"T3_WG={os.environ.get('MCR_T3_WG', '256')} phi={phi} {C}x{N}x{P}: pairs beyond lag 255: {(lags > 255).sum()} of {lags.size}, max lag {lags.max()}; "
+    print(f"phi={phi} {C}x{N}x{P}: pairs beyond lag 255: {(lags > 255).sum()} of {lags.size}, max lag {lags.max()}; "
           f"pipelined {dt*1e6:.0f} us/call; alone: " + "  ".join(f"{k[2:]}={v['total_ms']/v['launches']*1e3:.0f}" for k, v in sorted(pr.items(), key=lambda kv: -kv[1]['total_ms'])[:6]), flush=True)
     c1.close(); ctx.close()
