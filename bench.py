@@ -7,19 +7,24 @@ R-hat, ESS bulk, ESS tail, truncation lags) over one synthetic model resident in
   python bench.py                                   # N=1, BASELINE config 1 (4 x 10000 x 100 f64)
   python bench.py --steps K --dump-outputs DIR      # one timed window of exactly K steps; the last step's summary
                                                     # arrays as DIR/<name>.npy (float64, seeded inputs)
+  python bench.py --full                            # the same line + every leg below (about half a minute more)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W      # one rank per GPU, weak scaling
 
-Prints ONE JSON line on rank 0 (contract in the task statement) carrying `roofline` (dominant
-kernel, HIP-event timed inside this process) and `cpu_baseline` (the C oracle on this host's cores).
+Prints ONE JSON line on rank 0 (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).  A plain run
+does only what that line's headline needs: set up, warm up, time the steps, check the last timed step against the C
+oracle (`validated`; `value` is 0 when it fails), write --dump-outputs, print.
 No torch anywhere: for N > 1 the ranks read RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment
 the launcher sets and talk through the library's RCCL communicator (mcmc_ref_hip.shard.Communicator:
 barrier, MAX-over-ranks clock, and the one all-gather of the per-parameter summary records).
 
-At N = 1 the default run also carries `configs` (every other single-GPU BASELINE configuration, driver-timed in the same
-process: the 57 committed corpus files end to end, the corpus shapes device-resident, the full pipeline on the 16 GB
-stress tensor), `d_sweep` (P = 10 / 100 / 1000 at 4 x 10000), `sync_call_us` / `host_call_us` (ONE synchronous call, which
-is what reference.compare pays) -- each with its own `validated` flag; --no-extras skips them.
+--full adds, to the c1 workload, `roofline` and `kernels` (a second, single-lane pass of the K steps with a HIP event pair
+around every kernel), `hbm_probe`, `cpu_baseline` (the C oracle and the NumPy path on this host's cores) and
+`moments_roofline` (the 16 GB streaming-moments leg).  At N = 1 it also carries `configs` (every other single-GPU
+BASELINE configuration, timed in the same process: the 57 committed corpus files end to end, the corpus shapes
+device-resident, the full pipeline on the 16 GB stress tensor), `d_sweep` (P = 10 / 100 / 1000 at 4 x 10000),
+`sync_call_us` / `host_call_us` (ONE synchronous call, which is what reference.compare pays) -- each with its own
+`validated` flag.  --no-cpu-baseline / --no-moments / --no-probe / --no-extras drop single legs of a --full run.
 
 Workloads (--workload):
   c1       BASELINE config 1, the headline: every rank its own 4 x 10000 x 100 f64 model (weak scaling)
@@ -44,6 +49,7 @@ sys.path[:0] = [str(ROOT), str(ROOT / "mcmc-db_amd")]
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md: 8.0 TB/s; ~6.3 TB/s achievable)
 TRAFFIC_FILE = ROOT / "profiles" / "pmc_traffic.json"      # rocprofv3 --pmc passes of tools/collect_profiles.sh
+HOST_THREADS = 16       # host threads of the C oracle: the CPU share of a one-GPU box
 
 # Algorithmic (compulsory) HBM bytes per param-draw and launch of each kernel, f64 input
 # (DESIGN.md "Kernels and rooflines").  Intermediate traffic a kernel causes
@@ -101,13 +107,16 @@ def parse_args():
                     help="pcn = Arrow column layout [P][C][N]; cnp = Draws.to_numpy layout [C][N][P]")
     ap.add_argument("--dtype", choices=["f64", "f32"], default="f64")
     ap.add_argument("--inflight", type=int, default=8, help="steps enqueued before a host wait (1..8)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline (c1: per-kernel roofline, HBM probe, CPU baselines, "
+                         "streaming-moments leg and, at N = 1, the other single-GPU configurations)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline leg")
     ap.add_argument("--no-validate", action="store_true")
     ap.add_argument("--no-moments", action="store_true",
-                    help="skip the streaming-moments HBM roofline leg (16 GB f32 tensor generated on the device)")
-    ap.add_argument("--no-probe", action="store_true", help="skip the measured-HBM-peak probe")
+                    help="--full without the streaming-moments HBM roofline leg (16 GB f32 tensor generated on the device)")
+    ap.add_argument("--no-probe", action="store_true", help="--full without the measured-HBM-peak probe")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the other single-GPU configurations of the default line (configs / d_sweep / call latencies)")
+                    help="--full without the other single-GPU configurations (configs / d_sweep / call latencies)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the summary the last timed step returned as DIR/<name>.npy (float64)")
     return ap.parse_args()
@@ -377,7 +386,7 @@ def split_bench(a, ctx, ranks: Ranks):
 
 
 # =====================================================================================================================
-# The other single-GPU BASELINE configurations, inside the default run.  Rank 0, N = 1 only.  Every
+# The other single-GPU BASELINE configurations, inside a --full run.  Rank 0, N = 1 only.  Every
 # leg times its own work between device syncs with the host clock, validates the results of the calls it timed, and
 # reports `validated`; none of them touches `value`.
 # =====================================================================================================================
@@ -683,6 +692,129 @@ def main():
         ctx.close()
 
 
+def kernel_event_pass(a, ctx, t, _ffi, inflight: int) -> tuple[dict, float]:
+    """--full: the same K steps again with a HIP event pair around every kernel launch (per-kernel roofline).  With
+    several lanes the kernels of consecutive steps overlap, which would inflate every per-kernel duration: this pass runs
+    on a single-lane context (same device buffer), so the durations are those of each kernel running alone and agree
+    with rocprofv3 --kernel-trace of `MCR_LANES=1 python bench.py --full`.  Returns (profile, seconds of the pass)."""
+    os.environ["MCR_LANES"] = "1"
+    ctx1 = _ffi.Context(ctx.device)
+    t_one = _ffi.DeviceTensor(ctx1, t.buf, t.targs)
+    for _ in range(2):
+        ctx1.enqueue(t_one); ctx1.wait()
+    ctx1.profile(True)
+    ctx1.profile_reset()
+    t1 = time.perf_counter()
+    for k in range(a.steps):
+        ctx1.enqueue(t_one)
+        if (k + 1) % inflight == 0:
+            ctx1.wait()
+    ctx1.wait()
+    elapsed_prof = time.perf_counter() - t1
+    prof = ctx1.profile_get()
+    ctx1.profile(False)
+    ctx1.close()
+    os.environ.pop("MCR_LANES", None)
+    return prof, elapsed_prof
+
+
+def leg_cpu_baseline(a, orc, host: np.ndarray, cpu_s: float) -> dict:
+    """--full, rank 0: the C oracle on this host's cores.  Bounded sample (~12 s of wall time): the same model, parameters
+    split over T host threads (ctypes releases the GIL; parameters are independent, so this is how a CPU deployment of the
+    restatement would run).  The single-thread rate of the validation pass (`cpu_s`) is reported beside it."""
+    from concurrent.futures import ThreadPoolExecutor
+    C, N, P = a.chains, a.draws, a.params
+
+    def split(T):
+        cuts = [P * i // T for i in range(T + 1)]
+        sl = [(slice(cuts[i], cuts[i + 1]),) if a.layout == "pcn" else (Ellipsis, slice(cuts[i], cuts[i + 1]))
+              for i in range(T)]
+        return [np.ascontiguousarray(host[ix]) for ix in sl]
+
+    def timed_passes(T, parts, budget_s, fn):
+        passes, total_s = 0, 0.0
+        with ThreadPoolExecutor(T) as pool:
+            while total_s < budget_s and passes < 64:
+                t1 = time.perf_counter()
+                list(pool.map(fn, parts))
+                total_s += time.perf_counter() - t1
+                passes += 1
+        return passes, total_s
+
+    ncpu = os.cpu_count() or 1
+    # SURVEY 8(d): the restatement on 1 core and on all cores.  `value` = every visible core (one thread per
+    # parameter at most: the parameters are the unit of work), `value_16` = 16 threads, the CPU share of a
+    # one-GPU box on this pool, `value_1core` = the single-threaded validation pass.
+    T_all = max(1, min(ncpu, P))
+    T = max(1, min(HOST_THREADS, ncpu, P))
+    parts = split(T)
+    passes, total_s = timed_passes(T, parts, 8.0, lambda x: orc.summarize(x, a.layout))
+    v16 = passes * C * N * P / total_s
+    if T_all > T:
+        pa, sa = timed_passes(T_all, split(T_all), 8.0, lambda x: orc.summarize(x, a.layout))
+        v_all = pa * C * N * P / sa
+    else:
+        pa, sa, v_all = passes, total_s, v16
+    cpu = {"value": v_all, "unit": "param-draws/s", "cores": T_all, "kind": "port",
+           "cpu_model": cpu_model(), "cores_visible": ncpu,
+           "sample": f"the same {C}x{N}x{P} {a.dtype} model through oracle/mcr_oracle.c, its parameters split over "
+                     f"{T_all} threads ({pa} passes, {sa:.1f} s); value_16: over {T} threads ({passes} passes, "
+                     f"{total_s:.1f} s); value_1core: one pass on one thread ({cpu_s:.1f} s)",
+           "value_16": v16, "cores_16": T, "value_1core": C * N * P / cpu_s}
+    if a.layout == "pcn" and a.dtype == "f64" and C >= 2:
+        # the "NumPy CPU path" of SURVEY 8(d): the same statistics vectorised with numpy / scipy
+        # (argsort ranks, ndtri, FFT autocovariances), same thread split, ~6 s sample
+        from oracle import numpy_path
+        npass, nsec = timed_passes(T, parts, 6.0, numpy_path.summarize)
+        cpu["numpy_path"] = {"value": npass * C * N * P / nsec, "unit": "param-draws/s", "cores": T,
+                             "sample": f"{npass} passes of oracle/numpy_path.py over {T} threads ({nsec:.1f} s)"}
+    return cpu
+
+
+def roofline_fields(a, prof: dict, elapsed_prof: float, probe: dict | None, peak_measured: float | None) -> dict:
+    """--full, rank 0: the per-kernel table of the single-lane HIP-event pass and the roofline of its dominant kernel."""
+    C, N, P = a.chains, a.draws, a.params
+    pd_step = C * N * P
+    es = 8 if a.dtype == "f64" else 4
+    kern = {}
+    dom, dom_ms = None, -1.0
+    ktraffic = traffic_table().get(f"{C}x{N}x{P}-{a.dtype}-{a.layout}", {})
+    if N <= 16384 and "k_acov_long" in prof:       # chains up to 16 384 draws: the tier-3 launch behind this HIP-event label is k_tier3
+        prof["k_tier3"] = prof.pop("k_acov_long")
+    for name, r in prof.items():
+        avg_ms = r["total_ms"] / max(r["launches"], 1)
+        alg = alg_bytes(name, es)
+        tb = ktraffic.get(TRAFFIC_NAMES.get(name, name), ktraffic.get(name))
+        kern[name] = {"launches_per_step": r["launches"] / a.steps, "avg_us": round(avg_ms * 1e3, 2),
+                      "alg_GBps": round(alg * pd_step / (avg_ms * 1e-3) / 1e9, 1) if avg_ms > 0 else None,
+                      # SURVEY 8(d): FETCH_SIZE + WRITE_SIZE of the kernel / its time.  The bytes are per launch from the
+                      # committed rocprofv3 --pmc passes of this configuration (traffic_source below), the time is this
+                      # run's HIP-event average.
+                      "traffic_bytes": tb,
+                      "traffic_GBps": round(tb / (avg_ms * 1e-3) / 1e9, 1) if tb is not None and avg_ms > 0 else None}
+        if r["total_ms"] > dom_ms and name in ALG_BYTES_PER_PD:
+            dom, dom_ms = name, r["total_ms"]
+    dom_avg_s = prof[dom]["total_ms"] / prof[dom]["launches"] * 1e-3
+    dom_alg = alg_bytes(dom, es) * pd_step
+    traffic = ktraffic.get(dom)
+    achieved = dom_alg / dom_avg_s / 1e9
+    return {
+        "ms_per_step_event_pass": elapsed_prof / a.steps * 1e3,
+        "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS,
+                     "peak_measured": peak_measured, "unit": "GB/s",
+                     "frac": achieved / HBM_PEAK_GBS, "frac_of_measured": (achieved / peak_measured) if peak_measured else None,
+                     "traffic": traffic,
+                     "traffic_source": (str(TRAFFIC_FILE.relative_to(ROOT)) + " (rocprofv3 --pmc passes of an earlier run of this "
+                                        "configuration, not counters of this run)") if traffic is not None else None,
+                     "avg_launch_us": dom_avg_s * 1e6, "alg_bytes_per_launch": dom_alg},
+        "hbm_probe": probe,
+        "kernels": kern,
+        "kernels_traffic_source": (str(TRAFFIC_FILE.relative_to(ROOT)) + " (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of "
+                                   "an earlier run of this configuration, MCR_LANES=1; not counters of this run)") if ktraffic else None,
+        "traffic_bytes_per_step": int(sum(v for k, v in ktraffic.items() if isinstance(v, (int, float)))) if ktraffic else None,
+    }
+
+
 def c1_bench(a, ctx, ranks: Ranks, _ffi, synth):
     world, rank = ranks.world, ranks.rank
     C, N, P = a.chains, a.draws, a.params
@@ -707,29 +839,8 @@ def c1_bench(a, ctx, ranks: Ranks, _ffi, synth):
 
     # ---- timed region: windows of exactly K steps (rolling window of up to `inflight` calls over the lanes) ----
     elapsed, windows, last = timed_windows(a, ranks, run)
-    # ---- same K steps again with a HIP event pair around every kernel launch (per-kernel roofline).
-    #      With several lanes the kernels of consecutive steps overlap, which would inflate every
-    #      per-kernel duration: this pass runs on a single-lane
-    #      context (same device buffer), so the durations are those of each kernel running alone
-    #      and agree with rocprofv3 --kernel-trace of `MCR_LANES=1 python bench.py`. ----
-    os.environ["MCR_LANES"] = "1"
-    ctx1 = _ffi.Context(ctx.device)
-    t_one = _ffi.DeviceTensor(ctx1, t.buf, t.targs)
-    for _ in range(2):
-        ctx1.enqueue(t_one); ctx1.wait()
-    ctx1.profile(True)
-    ctx1.profile_reset()
-    t1 = time.perf_counter()
-    for k in range(a.steps):
-        ctx1.enqueue(t_one)
-        if (k + 1) % inflight == 0:
-            ctx1.wait()
-    ctx1.wait()
-    elapsed_prof = time.perf_counter() - t1
-    prof = ctx1.profile_get()
-    ctx1.profile(False)
-    ctx1.close()
-    os.environ.pop("MCR_LANES", None)
+    if a.full:
+        prof, elapsed_prof = kernel_event_pass(a, ctx, t, _ffi, inflight)
 
     got = last.result()
     dump_outputs(a, got, rank)
@@ -745,69 +856,26 @@ def c1_bench(a, ctx, ranks: Ranks, _ffi, synth):
 
     valid, worst = True, 0.0
     cpu = None
-    if not a.no_validate or not a.no_cpu_baseline:
+    cpu_leg = a.full and not a.no_cpu_baseline
+    if not a.no_validate or cpu_leg:
         from oracle import oracle as orc          # checker + cpu_baseline leg only
         t1 = time.perf_counter()
-        exp = orc.summarize(host, a.layout)
+        if cpu_leg:                               # one thread: this pass is the cpu_baseline's value_1core
+            exp = orc.summarize(host, a.layout)
+        else:                                     # the same result (parameters are independent), on the host's share of cores
+            exp = orc.summarize_mt(host, a.layout, threads=max(1, min(HOST_THREADS, os.cpu_count() or 1) // world))
         cpu_s = time.perf_counter() - t1
         if not a.no_validate:
             valid, worst = validate(got, exp)
-        if rank == 0 and not a.no_cpu_baseline:
-            # Bounded sample (~12 s of wall time): the same model, parameters split over T host threads
-            # (ctypes releases the GIL; parameters are independent, so this is how a CPU deployment of the
-            # restatement would run).  The single-thread rate of the validation pass is reported beside it.
-            from concurrent.futures import ThreadPoolExecutor
-
-            def split(T):
-                cuts = [P * i // T for i in range(T + 1)]
-                sl = [(slice(cuts[i], cuts[i + 1]),) if a.layout == "pcn" else (Ellipsis, slice(cuts[i], cuts[i + 1]))
-                      for i in range(T)]
-                return [np.ascontiguousarray(host[ix]) for ix in sl]
-
-            def timed_passes(T, parts, budget_s, fn):
-                passes, total_s = 0, 0.0
-                with ThreadPoolExecutor(T) as pool:
-                    while total_s < budget_s and passes < 64:
-                        t1 = time.perf_counter()
-                        list(pool.map(fn, parts))
-                        total_s += time.perf_counter() - t1
-                        passes += 1
-                return passes, total_s
-
-            ncpu = os.cpu_count() or 1
-            # the restatement on 1 core and on all cores.  `value` = every visible core (one thread per
-            # parameter at most: the parameters are the unit of work), `value_16` = 16 threads, the CPU share of a
-            # one-GPU box on this pool, `value_1core` = the single-threaded validation pass above.
-            T_all = max(1, min(ncpu, P))
-            T = max(1, min(16, ncpu, P))
-            parts = split(T)
-            passes, total_s = timed_passes(T, parts, 8.0, lambda x: orc.summarize(x, a.layout))
-            v16 = passes * C * N * P / total_s
-            if T_all > T:
-                pa, sa = timed_passes(T_all, split(T_all), 8.0, lambda x: orc.summarize(x, a.layout))
-                v_all = pa * C * N * P / sa
-            else:
-                pa, sa, v_all = passes, total_s, v16
-            cpu = {"value": v_all, "unit": "param-draws/s", "cores": T_all, "kind": "port",
-                   "cpu_model": cpu_model(), "cores_visible": ncpu,
-                   "sample": f"the same {C}x{N}x{P} {a.dtype} model through oracle/mcr_oracle.c, its parameters split over "
-                             f"{T_all} threads ({pa} passes, {sa:.1f} s); value_16: over {T} threads ({passes} passes, "
-                             f"{total_s:.1f} s); value_1core: one pass on one thread ({cpu_s:.1f} s)",
-                   "value_16": v16, "cores_16": T, "value_1core": C * N * P / cpu_s}
-            if a.layout == "pcn" and a.dtype == "f64" and C >= 2:
-                # the "NumPy CPU path" of SURVEY 8(d): the same statistics vectorised with numpy / scipy
-                # (argsort ranks, ndtri, FFT autocovariances), same thread split, ~6 s sample
-                from oracle import numpy_path
-                npass, nsec = timed_passes(T, parts, 6.0, numpy_path.summarize)
-                cpu["numpy_path"] = {"value": npass * C * N * P / nsec, "unit": "param-draws/s", "cores": T,
-                                     "sample": f"{npass} passes of oracle/numpy_path.py over {T} threads ({nsec:.1f} s)"}
+        if rank == 0 and cpu_leg:
+            cpu = leg_cpu_baseline(a, orc, host, cpu_s)
     valid = ranks.all_true(valid and gathered_ok)
 
-    probe = hbm_probe(ctx, a) if rank == 0 else None
+    probe = hbm_probe(ctx, a) if rank == 0 and a.full else None
     peak_measured = probe.get("read_GBps") if probe and "error" not in probe else None
 
     moments, extras = None, {}
-    if rank == 0 and world == 1 and not a.no_extras and a.layout == "pcn" and a.dtype == "f64":
+    if rank == 0 and world == 1 and a.full and not a.no_extras and a.layout == "pcn" and a.dtype == "f64":
         from oracle import oracle as orc          # checker of every leg below
         extras["configs"] = {}
         lat = leg_call_latency(ctx, t, host, got)
@@ -819,7 +887,7 @@ def c1_bench(a, ctx, ranks: Ranks, _ffi, synth):
         cf = leg_corpus_files(ctx)
         if cf is not None:
             extras["configs"]["corpus_files"] = cf
-    if rank == 0 and not a.no_moments:
+    if rank == 0 and a.full and not a.no_moments:
         from oracle import oracle as orc
         # BASELINE config 4 itself: 4 x 100000 x 10000 f32 = 16 GB, generated on the device: the streaming-moments
         # roofline (one HBM pass per launch, 4 B per param-draw) and, with the extras, the full pipeline on it.
@@ -834,31 +902,8 @@ def c1_bench(a, ctx, ranks: Ranks, _ffi, synth):
     per_rank_ms = [x / a.steps * 1e3 for x in ranks.gather(statistics.median(ranks.own_secs))]
 
     if rank == 0:
-        pd_step = C * N * P
         es = 8 if a.dtype == "f64" else 4
-        kern = {}
-        dom, dom_ms = None, -1.0
-        ktraffic = traffic_table().get(f"{C}x{N}x{P}-{a.dtype}-{a.layout}", {})
-        if N <= 16384 and "k_acov_long" in prof:       # chains up to 16 384 draws: the tier-3 launch behind this HIP-event label is k_tier3
-            prof["k_tier3"] = prof.pop("k_acov_long")
-        for name, r in prof.items():
-            avg_ms = r["total_ms"] / max(r["launches"], 1)
-            alg = alg_bytes(name, es)
-            tb = ktraffic.get(TRAFFIC_NAMES.get(name, name), ktraffic.get(name))
-            kern[name] = {"launches_per_step": r["launches"] / a.steps, "avg_us": round(avg_ms * 1e3, 2),
-                          "alg_GBps": round(alg * pd_step / (avg_ms * 1e-3) / 1e9, 1) if avg_ms > 0 else None,
-                          # FETCH_SIZE + WRITE_SIZE of the kernel / its time.  The bytes are per launch from the
-                          # committed rocprofv3 --pmc passes of this configuration (traffic_source below), the time is this
-                          # run's HIP-event average.
-                          "traffic_bytes": tb,
-                          "traffic_GBps": round(tb / (avg_ms * 1e-3) / 1e9, 1) if tb is not None and avg_ms > 0 else None}
-            if r["total_ms"] > dom_ms and name in ALG_BYTES_PER_PD:
-                dom, dom_ms = name, r["total_ms"]
-        dom_avg_s = prof[dom]["total_ms"] / prof[dom]["launches"] * 1e-3
-        dom_alg = alg_bytes(dom, es) * pd_step
-        traffic = traffic_table().get(f"{C}x{N}x{P}-{a.dtype}-{a.layout}", {}).get(dom)
-        achieved = dom_alg / dom_avg_s / 1e9
-        value = world * a.steps * pd_step / elapsed
+        value = world * a.steps * C * N * P / elapsed
         out = {
             "metric": "validated param-draws/sec", "value": value if valid else 0.0, "unit": "param-draws/s",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": elapsed / a.steps * 1e3,
@@ -871,25 +916,13 @@ def c1_bench(a, ctx, ranks: Ranks, _ffi, synth):
             "validated": valid, "max_rel_err": worst,
             "timing": timing_note(a, windows), "ms_per_step_first_window": round(windows[0] / a.steps * 1e3, 5),
             "ms_per_step_windows": [round(s / a.steps * 1e3, 5) for s in windows],
-            "ms_per_step_event_pass": elapsed_prof / a.steps * 1e3,
             "pipeline_alg_GBps": value / world * es / 1e9,
             "pipeline_frac_of_hbm": value / world * es / 1e9 / HBM_PEAK_GBS,
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "peak_measured": peak_measured, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "frac_of_measured": (achieved / peak_measured) if peak_measured else None,
-                         "traffic": traffic,
-                         "traffic_source": (str(TRAFFIC_FILE.relative_to(ROOT)) + " (rocprofv3 --pmc passes of an earlier run of this "
-                                            "configuration, not counters of this run)") if traffic is not None else None,
-                         "avg_launch_us": dom_avg_s * 1e6, "alg_bytes_per_launch": dom_alg},
-            "hbm_probe": probe,
-            "kernels": kern,
-            "kernels_traffic_source": (str(TRAFFIC_FILE.relative_to(ROOT)) + " (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of "
-                                       "an earlier run of this configuration, MCR_LANES=1; not counters of this run)") if ktraffic else None,
-            "traffic_bytes_per_step": int(sum(v for k, v in ktraffic.items() if isinstance(v, (int, float)))) if ktraffic else None,
-            "moments_roofline": moments,
-            "cpu_baseline": cpu,
             "ms_per_step_per_rank": [round(x, 5) for x in per_rank_ms],
         }
+        if a.full:
+            out.update(roofline_fields(a, prof, elapsed_prof, probe, peak_measured))
+            out["moments_roofline"], out["cpu_baseline"] = moments, cpu
         out.update(extras)
         print(json.dumps(out), flush=True)
     t.free()
