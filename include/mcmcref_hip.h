@@ -16,7 +16,9 @@
  *     thread, or several ctxs in one thread).
  *   - tensors are described by element strides (stride_c, stride_n, stride_p), so both the
  *     Arrow column layout [P][C][N] and `Draws.to_numpy` layout [C][N][P] (src/mcmc_ref/draws.py:28-29)
- *     are accepted without a host-side copy.
+ *     are accepted without a host-side copy.  Any non-negative strides are accepted, padded, sliced and thinned
+ *     views included; zero or aliasing strides (broadcast views, parameters or chains sharing elements) are read as
+ *     they are: the library only reads the draws.
  *   - dtype: MCR_F64 (the reference's only dtype) or MCR_F32 (widened to f64 on load).
  *   - NaN/Inf in the draws are rejected with MCR_ENONFINITE (the reference's behaviour for
  *     them is undefined: sort order with NaN).

@@ -229,8 +229,9 @@ __global__ __launch_bounds__(256) void k_moments_rows(const T* __restrict__ X, i
     if (threadIdx.x == 0) store_slice_moments(part + (p * S + s) * kMomRec, K, s1, s2, bad, (double)(e > b ? e - b : 0));
 }
 
-// strided variant ([C][N][P]-like tensors, stride_p == 1): lanes run along p, each thread owns one
-// parameter and walks a slice of the C*N rows.  grid (ceil(P/64), S), block (64, 4).
+// strided variant: every tensor that is not row-contiguous (stride_n != 1 or stride_c != N), whatever its stride_p
+// (coalesced when stride_p == 1, the [C][N][P] layout): lanes run along p, each thread owns one parameter and walks a
+// slice of the C*N rows.  grid (ceil(P/64), S), block (64, 4).
 template <typename T>
 __global__ __launch_bounds__(256) void k_moments_cols(const T* __restrict__ src, i64 C, i64 N, i64 P,
                                                       i64 sc, i64 sn, i64 sp, double* __restrict__ part,
