@@ -2,9 +2,16 @@
 
 If the shared library or a HIP device is missing every entry point raises
 `HipUnavailableError`: the product path never silently computes on the CPU.
+
+The summarize plumbing the Python API shares lives here too, once: the fileset reader
+(`Context.summarize_files`), the rolling window over enqueue / wait_one (`pipeline`, `split_result`),
+the reference-shaped per-parameter dicts (`entries`), the ragged-chain route (`ragged_diagnostics`) and
+the McrError -> ValueError translation of the reference-compatible functions (`value_errors`).
 """
 from __future__ import annotations
 
+import collections
+import contextlib
 import ctypes as C
 import math
 import os
@@ -181,6 +188,12 @@ def _as_ip(a):
 
 
 SUMMARY_F64 = ("mean", "std", "median", "rhat", "rhat_bulk", "rhat_tail", "ess_bulk", "ess_tail")
+DIAG_KEYS = ("rhat", "ess_bulk", "ess_tail")          # the diagnostics the reference API reports per parameter
+
+# mcr_fileset_export: one row per parameter, files and parameters in order -- these MCR_FS_* fields, then q[0 .. n_q)
+FS_EXPORT = ("mean", "std", "median", "rhat", "ess_bulk", "ess_tail", "rhat_bulk", "rhat_tail", "lag_bulk", "lag_tail")
+FS_PHASES = ("open_ms", "read_pinned_parse_ms", "plan_ms", "upload_decode_layout_ms", "statistics_ms",
+             "collect_ms", "close_ms", "total_ms")          # MCR_FS_PH_*
 
 
 class SummaryBuffers:
@@ -389,6 +402,50 @@ class Context:
         self._check(self.lib.mcr_summarize_models(self.handle, descs, n, _as_dp(qs), qs.size, outs))
         return [b.result() for b in bufs]
 
+    def summarize_files(self, paths, min_chains: int = 4, quantiles=(0.05, 0.5, 0.95), diagnostics: bool = True,
+                        phases: dict | None = None) -> tuple[list[tuple[list[str], int, int]], dict] | None:
+        """Draws files -> statistics in ONE mcr_summarize_files call (mmap, parse, batched decode, layout check,
+        pipelined statistics): ([(parameter names, chains, draws per chain) per file], the statistics of all their
+        parameters in file order as ONE summary shaped like summarize()'s, without q_lo -- split_result cuts it per
+        file).  None when a file needs the general route (MCR_ELAYOUT: rows out of (chain, draw) order, or chains of
+        unequal length with diagnostics).  `phases` is filled with the call's host clock (FS_PHASES, ms) and its
+        `jobs`."""
+        L, fs = self.lib, C.c_void_p()
+        qs = np.ascontiguousarray(list(quantiles), dtype=np.float64)
+        arr = (C.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])
+        rc = L.mcr_summarize_files(self.handle, arr, len(paths), int(min_chains), _as_dp(qs), qs.size,
+                                   int(diagnostics), C.byref(fs))
+        if rc == MCR_ELAYOUT:
+            return None
+        self._check(rc)
+        try:
+            if phases is not None:
+                ms = np.zeros(len(FS_PHASES))
+                L.mcr_fileset_phases(fs, _as_dp(ms), len(FS_PHASES))
+                phases.update(zip(FS_PHASES, ms.tolist()))
+                phases["jobs"] = int(L.mcr_fileset_jobs(fs))
+            files = range(L.mcr_fileset_size(fs))
+            counts = [int(L.mcr_fileset_params(fs, i)) for i in files]
+            total, w = sum(counts), len(FS_EXPORT)
+            rows = np.empty((max(total, 1), w + qs.size))            # the whole set in one export
+            L.mcr_fileset_export(fs, _as_dp(rows), total)
+            rows = rows[:total]
+            need = int(L.mcr_fileset_names(fs, None, 0))
+            buf = C.create_string_buffer(max(need, 1))
+            L.mcr_fileset_names(fs, buf, need)
+            names = buf.raw[:need].decode().split("\0")
+            r = {k: rows[:, j] for j, k in enumerate(FS_EXPORT)}
+            for k in ("lag_bulk", "lag_tail"):      # NaN without diagnostics: zeros, as summarize() leaves them
+                r[k] = r[k].astype(np.int64) if diagnostics else np.zeros(total, dtype=np.int64)
+            r["q"] = rows[:, w:]
+            out, r0 = [], 0
+            for i, P in zip(files, counts):
+                out.append((names[r0:r0 + P], int(L.mcr_fileset_chains(fs, i)), int(L.mcr_fileset_draws(fs, i))))
+                r0 += P
+            return out, r
+        finally:
+            L.mcr_fileset_free(fs)
+
     def wait(self):
         try:
             self._check(self.lib.mcr_summarize_wait(self.handle))
@@ -507,6 +564,97 @@ class Context:
         self._check(self.lib.mcr_profile_get(self.handle, arr, 32, C.byref(n)))
         return {arr[i].name.decode(): {"launches": int(arr[i].launches), "total_ms": float(arr[i].total_ms)}
                 for i in range(min(n.value, 32))}
+
+
+def pipeline(ctx: Context, jobs, owns: bool = False):
+    """Rolling window of ctx.enqueue / ctx.wait_one over `jobs`, an iterable of (tag, DeviceTensor, enqueue() keyword
+    arguments) consumed lazily.  Yields (tag, result dict or the McrError of that job's enqueue or wait) in submission
+    order with at most MCR_MAX_INFLIGHT calls outstanding; calls already in flight on `ctx` are waited for first, so
+    that every wait_one delivers one of these jobs.  owns=True: the helper frees each tensor once its call is retired.
+
+    However the generator ends -- exhausted, closed early, an exception in `jobs` -- nothing stays in flight and no
+    owned tensor stays allocated; use it under contextlib.closing so that an exception in the consumer's loop closes
+    it at once.  The consumer does not use `ctx` between two results."""
+    if ctx.inflight:
+        ctx.wait()
+    window = collections.deque()            # (tag, tensor, result buffers or the McrError of its enqueue)
+    try:
+        for tag, t, kw in jobs:
+            try:
+                window.append((tag, t, ctx.enqueue(t, **kw)))
+            except McrError as exc:
+                window.append((tag, t, exc))
+            if len(window) == MCR_MAX_INFLIGHT:
+                yield _retire(ctx, window, owns)
+        while window:
+            yield _retire(ctx, window, owns)
+    finally:
+        if window:
+            try:
+                ctx.wait()
+            except McrError:                # the exception that ended the generator is the one to report
+                pass
+            if owns:
+                for _tag, t, _ in window:
+                    t.free()
+            window.clear()
+
+
+def _retire(ctx: Context, window, owns: bool):
+    """The oldest job of the window: (tag, result dict or McrError); its tensor is freed if owned."""
+    tag, t, got = window[0]
+    if not isinstance(got, McrError):
+        try:
+            if ctx.wait_one() is not got:    # never hand a job another call's numbers
+                raise RuntimeError("pipeline: the context delivered a result that is not this job's")
+            got = got.result()
+        except McrError as exc:
+            got = exc
+    window.popleft()
+    if owns:
+        t.free()
+    return tag, got
+
+
+def split_result(r: dict, sizes) -> list[dict]:
+    """A batched call's result cut back into its models: `sizes` = parameters per model, in tensor order."""
+    out, p0 = [], 0
+    for P in sizes:
+        out.append({k: (v if k == "q_lo" else v[p0:p0 + P]) for k, v in r.items()})
+        p0 += P
+    return out
+
+
+def entries(r: dict, quantiles=None, diagnostics: bool = True) -> list[dict[str, float]]:
+    """The per-parameter dicts of the reference API from a summary dict, in parameter order: {"mean", "std", "qNN"...}
+    for `quantiles` (the keys f"q{int(q * 100)}"), then {"rhat", "ess_bulk", "ess_tail"} with diagnostics.
+    quantiles=None: the diagnostics triple alone."""
+    keys, cols = [], []                     # whole columns to Python floats, not one value at a time
+    if quantiles is not None:
+        keys = ["mean", "std"] + [f"q{int(q * 100)}" for q in quantiles]
+        cols = [r["mean"].tolist(), r["std"].tolist()] + r["q"].T.tolist()      # q: [P][n_q]
+    if diagnostics:
+        keys += DIAG_KEYS
+        cols += [r["rhat"].tolist(), r["ess_bulk"].tolist(), r["ess_tail"].tolist()]
+    return [dict(zip(keys, row)) for row in zip(*cols)]
+
+
+def ragged_diagnostics(ctx: Context, x: np.ndarray, counts, min_chains: int) -> dict[str, np.ndarray]:
+    """rhat / ess_bulk / ess_tail of every row of x [P][M] whose chains are `counts` draws long, one
+    mcr_diagnose_chains call per parameter (chains of unequal length)."""
+    off = np.concatenate([[0], np.cumsum(counts)])
+    got = [ctx.diagnose_chains([row[off[c]:off[c + 1]] for c in range(len(counts))], min_chains=min_chains)
+           for row in x]
+    return {k: np.array([g[k] for g in got], dtype=np.float64) for k in DIAG_KEYS}
+
+
+@contextlib.contextmanager
+def value_errors():
+    """McrError -> ValueError with the library's message: the exception the reference-compatible functions raise."""
+    try:
+        yield
+    except McrError as exc:
+        raise ValueError(exc.message) from exc
 
 
 _default = threading.local()

@@ -106,21 +106,15 @@ class HipBackend:
         by_len: dict[int, list[int]] = {}
         for i, c in enumerate(cols):
             by_len.setdefault(len(c), []).append(i)
-        entries: dict[int, dict[str, float]] = {}
+        out: dict[str, dict[str, float]] = {}
         for M, members in by_len.items():          # one group unless nulls were dropped unevenly
             x = np.empty((len(members), 1, M), dtype=np.float64)
             for k, i in enumerate(members):
                 x[k, 0] = cols[i]
-            try:
+            with _ffi.value_errors():
                 r = self._ctx.summarize(x, "pcn", min_chains=1, quantiles=qs, diagnostics=False)
-            except _ffi.McrError as exc:
-                raise ValueError(exc.message) from exc
-            for k, i in enumerate(members):
-                entry = {"mean": float(r["mean"][k]), "std": float(r["std"][k])}
-                for q, v in zip(qs, r["q"][k], strict=False):
-                    entry[f"q{int(q * 100)}"] = float(v)
-                entries[i] = entry
-        return {param: entries[i] for i, param in enumerate(params)}
+            out.update(zip([params[i] for i in members], _ffi.entries(r, qs, diagnostics=False)))
+        return {param: out[param] for param in params}
 
 
 def _load_hip() -> Backend:

@@ -80,10 +80,8 @@ def compute_basic_stats(values: Sequence[float], context=None) -> dict[str, floa
     if n == 0:
         return {"mean": float("nan"), "std": float("nan")}
     ctx = context or _ffi.default_context()
-    try:
+    with _ffi.value_errors():
         out = ctx.basic_stats(np.asarray(values, dtype=np.float64))
-    except _ffi.McrError as exc:
-        raise ValueError(exc.message) from exc
     return {"mean": float(out["mean"]), "std": float(out["std"])}
 
 
@@ -96,9 +94,8 @@ def compute_stats_from_draws(draws: Mapping[str, Sequence[float]], context=None)
         x = np.stack([np.asarray(draws[p], dtype=np.float64).reshape(-1) for p in names])
         t = ctx.upload(x.reshape(len(names), 1, -1), "pcn")
         try:
-            mean, std = ctx.moments(t)
-        except _ffi.McrError as exc:
-            raise ValueError(exc.message) from exc
+            with _ffi.value_errors():
+                mean, std = ctx.moments(t)
         finally:
             t.free()
         return {p: {"mean": float(mean[i]), "std": float(std[i])} for i, p in enumerate(names)}

@@ -10,6 +10,7 @@ from __future__ import annotations
 import json
 import zipfile
 from collections.abc import Iterable
+from contextlib import closing
 from dataclasses import dataclass
 from datetime import date
 from pathlib import Path
@@ -75,23 +76,12 @@ def _compute_diagnostics(table: Any, params: Iterable[str], *, min_chains: int =
     if C < min_chains:
         raise ValueError(f"R-hat diagnostics require at least {min_chains} chains; got {C} chain(s)")
     ctx = context or _ffi.default_context()
-    diag: dict[str, dict[str, float]] = {}
-    try:
-        if C >= 1 and np.all(counts == counts[0]):
-            r = ctx.summarize(x.reshape(len(params), C, int(counts[0])), "pcn", min_chains=min_chains,
-                              quantiles=())
-            for i, p in enumerate(params):
-                diag[p] = {"rhat": float(r["rhat"][i]), "ess_bulk": float(r["ess_bulk"][i]),
-                           "ess_tail": float(r["ess_tail"][i])}
+    with _ffi.value_errors():
+        if np.all(counts == counts[0]):
+            r = ctx.summarize(x.reshape(len(params), C, int(counts[0])), "pcn", min_chains=min_chains, quantiles=())
         else:                                       # ragged chains: one pipeline per parameter
-            off = np.concatenate([[0], np.cumsum(counts)])
-            for i, p in enumerate(params):
-                chains = [x[i, off[c]:off[c + 1]] for c in range(C)]
-                d = ctx.diagnose_chains(chains, min_chains=min_chains)
-                diag[p] = {"rhat": d["rhat"], "ess_bulk": d["ess_bulk"], "ess_tail": d["ess_tail"]}
-    except _ffi.McrError as exc:
-        raise ValueError(exc.message) from exc
-    return diag
+            r = _ffi.ragged_diagnostics(ctx, x, counts, min_chains)
+    return dict(zip(params, _ffi.entries(r)))
 
 
 def summarize_table(table: Any, params: Iterable[str], *, min_chains: int = 4, context=None,
@@ -106,18 +96,9 @@ def summarize_table(table: Any, params: Iterable[str], *, min_chains: int = 4, c
         raise ValueError("summarize_table needs chains of equal length")
     ctx = context or _ffi.default_context()
     qs = list(quantiles)
-    try:
+    with _ffi.value_errors():
         r = ctx.summarize(x.reshape(len(params), C, int(counts[0])), "pcn", min_chains=min_chains, quantiles=qs)
-    except _ffi.McrError as exc:
-        raise ValueError(exc.message) from exc
-    out: dict[str, dict[str, float]] = {}
-    for i, p in enumerate(params):
-        e = {"mean": float(r["mean"][i]), "std": float(r["std"][i])}
-        for q, v in zip(qs, r["q"][i], strict=False):
-            e[f"q{int(q * 100)}"] = float(v)
-        e.update(rhat=float(r["rhat"][i]), ess_bulk=float(r["ess_bulk"][i]), ess_tail=float(r["ess_tail"][i]))
-        out[p] = e
-    return out
+    return dict(zip(params, _ffi.entries(r, qs)))
 
 
 def _checks(n_chains: int, n_draws: int, diag: dict[str, dict[str, float]]) -> dict[str, bool]:
@@ -228,61 +209,33 @@ def convert_files(jobs, out_draws_dir: Path, out_meta_dir: Path, force: bool = F
         except Exception as exc:  # noqa: BLE001 - reported per job
             results[i] = exc
     diags: dict[int, dict] = {}
-    ctx = None
-    if any(v[1] for v in prepared.values()):
-        ctx = context or _ffi.default_context()
-    window: list[tuple[int, object, object]] = []          # (job, device tensor, the result buffers enqueue() handed back)
-    if ctx is not None and ctx.inflight:
-        ctx.wait()       # somebody else's calls on this context: wait_one() below must deliver OUR oldest call, nobody else's
+    rect, ragged = [], []
+    for i, (_table, params, _nc, _nd, _x, counts) in prepared.items():
+        if not params:
+            diags[i] = {}
+        else:
+            (rect if np.all(counts == counts[0]) else ragged).append(i)
+    ctx = (context or _ffi.default_context()) if rect or ragged else None
 
-    def retire():
-        i, t, mine = window.pop(0)
-        try:
-            got = ctx.wait_one()
-            if got is not mine:        # cannot happen on a context drained above; never hand a model another call's numbers
-                raise RuntimeError("convert_files: the context delivered a result that is not this model's")
-            r = got.result()
-            diags[i] = {p: {"rhat": float(r["rhat"][k]), "ess_bulk": float(r["ess_bulk"][k]),
-                            "ess_tail": float(r["ess_tail"][k])} for k, p in enumerate(prepared[i][1])}
-        except _ffi.McrError as exc:
-            results[i] = ValueError(exc.message)
-        finally:
-            t.free()
-
-    ragged = []
-    try:
-        for i, (table, params, n_chains, n_draws, x, counts) in prepared.items():
-            if not params:
-                diags[i] = {}
-                continue
-            if not np.all(counts == counts[0]):
-                ragged.append(i)
-                continue
-            if len(window) == _ffi.MCR_MAX_INFLIGHT:
-                retire()
+    def calls():
+        for i in rect:
+            _table, params, _nc, _nd, x, counts = prepared[i]
             try:
                 t = ctx.upload(x.reshape(len(params), len(counts), int(counts[0])), "pcn")
-                try:
-                    bufs = ctx.enqueue(t, min_chains=min_chains, quantiles=())
-                except Exception:
-                    t.free()
-                    raise
-                window.append((i, t, bufs))
             except _ffi.McrError as exc:
                 results[i] = ValueError(exc.message)
-        while window:
-            retire()
-    finally:
-        # anything but a kernel-side failure of one model (handled above) ends the batch: nothing stays in flight and no
-        # device tensor stays allocated behind the exception
-        if window:
-            try:
-                ctx.wait()
-            except Exception:  # noqa: BLE001 - the original exception is the one to report
-                pass
-            for _i, t, _b in window:
-                t.free()
-            window.clear()
+                continue
+            yield i, t, {"min_chains": min_chains, "quantiles": ()}
+
+    # anything but a kernel-side failure of one model (an McrError of its own, kept as its result) ends the batch, and
+    # the window then leaves nothing in flight and no device tensor allocated behind the exception
+    if rect:
+        with closing(_ffi.pipeline(ctx, calls(), owns=True)) as done:
+            for i, r in done:
+                if isinstance(r, _ffi.McrError):
+                    results[i] = ValueError(r.message)
+                else:
+                    diags[i] = dict(zip(prepared[i][1], _ffi.entries(r)))
     for i in ragged:                                  # chains of unequal length: one pipeline per parameter
         table, params = prepared[i][:2]
         try:

@@ -31,10 +31,8 @@ def diagnose(chains: Sequence[Sequence[float]], *, min_chains: int = 4, context=
         nan = float("nan")
         return {"rhat": nan, "ess_bulk": nan, "ess_tail": nan}
     ctx = context or _ffi.default_context()
-    try:
+    with _ffi.value_errors():
         return ctx.diagnose_chains(chains, min_chains=min_chains)
-    except _ffi.McrError as exc:
-        raise ValueError(exc.message) from exc
 
 
 def split_rhat(chains: Sequence[Sequence[float]], *, min_chains: int = 4) -> float:

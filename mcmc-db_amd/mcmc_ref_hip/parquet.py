@@ -11,6 +11,7 @@ from __future__ import annotations
 import ctypes as C
 import mmap
 import os
+from contextlib import closing
 from pathlib import Path
 from typing import Iterable, Sequence
 
@@ -266,74 +267,26 @@ def read_columns(ctx: "_ffi.Context", source, columns: Iterable[str] | None = No
             f.close()
 
 
-def _entry(r: dict, i: int, qs, diagnostics: bool) -> dict[str, float]:
-    e = {"mean": float(r["mean"][i]), "std": float(r["std"][i])}
-    for q, v in zip(qs, r["q"][i]):
-        e[f"q{int(q * 100)}"] = float(v)
-    if diagnostics:
-        e.update(rhat=float(r["rhat"][i]), ess_bulk=float(r["ess_bulk"][i]), ess_tail=float(r["ess_tail"][i]))
-    return e
-
-
-_FS_FIELDS = (("mean", 0), ("std", 1), ("rhat", 4), ("ess_bulk", 5), ("ess_tail", 6))
-
-
-FS_PHASES = ("open_ms", "read_pinned_parse_ms", "plan_ms", "upload_decode_layout_ms", "statistics_ms",
-             "collect_ms", "close_ms", "total_ms")          # MCR_FS_PH_* of include/mcmcref_hip.h
-
-
 def _summarize_paths(ctx: "_ffi.Context", paths: list[str], min_chains: int, qs: list[float], diagnostics: bool,
                      phases: dict | None = None):
-    """All of summarize_files in ONE C call (mcr_summarize_files: mmap, parse, batched decode, layout check,
-    pipelined statistics).  Returns None when a file needs the general route (rows out of (chain, draw) order,
-    chains of unequal length)."""
-    L = ctx.lib
-    arr = (C.c_char_p * len(paths))(*[p.encode() for p in paths])
-    q = np.ascontiguousarray(qs, dtype=np.float64)
-    fs = C.c_void_p()
-    rc = L.mcr_summarize_files(ctx.handle, arr, len(paths), int(min_chains), q.ctypes.data_as(C.POINTER(C.c_double)),
-                               q.size, 1 if diagnostics else 0, C.byref(fs))
-    if rc == _ffi.MCR_ELAYOUT:
-        return None
-    if rc != _ffi.MCR_OK:
-        msg = (L.mcr_last_error(ctx.handle) or b"").decode()
-        if rc in (_ffi.MCR_EMINCHAINS, _ffi.MCR_EMINCHAINS_ARG, _ffi.MCR_ENONFINITE):
-            raise ValueError(msg.split(": ", 1)[-1] if rc == _ffi.MCR_EMINCHAINS else msg)
-        if "cannot compute stats of empty columns" in msg:
-            raise ValueError("cannot compute stats of empty columns")
-        raise McrError(rc, msg)
+    """All of summarize_files in ONE C call (Context.summarize_files).  Returns None when a file needs the general
+    route (rows out of (chain, draw) order, chains of unequal length); `phases`: see Context.summarize_files."""
     try:
-        if phases is not None:
-            ms = (C.c_double * len(FS_PHASES))()
-            L.mcr_fileset_phases(fs, ms, len(FS_PHASES))
-            phases.update(zip(FS_PHASES, (float(v) for v in ms)))
-            phases["jobs"] = int(L.mcr_fileset_jobs(fs))
-        nq = len(qs)
-        qkeys = [f"q{int(v * 100)}" for v in qs]
-        nfiles = L.mcr_fileset_size(fs)
-        counts = [int(L.mcr_fileset_params(fs, i)) for i in range(nfiles)]
-        total = sum(counts)
-        rows = np.empty((max(total, 1), 10 + nq))                  # one export of the whole set (mcr_fileset_export)
-        L.mcr_fileset_export(fs, rows.ctypes.data_as(C.POINTER(C.c_double)), total)
-        need = int(L.mcr_fileset_names(fs, None, 0))
-        buf = C.create_string_buffer(max(need, 1))
-        L.mcr_fileset_names(fs, buf, need)
-        names = buf.raw[:need].decode().split("\0")[:total]
-        table = rows[:total].tolist()
-        out, r = [], 0
-        for P in counts:
-            res = {}
-            for name, row in zip(names[r:r + P], table[r:r + P]):
-                e = {"mean": row[0], "std": row[1]}
-                e.update(zip(qkeys, row[10:]))
-                if diagnostics:
-                    e["rhat"], e["ess_bulk"], e["ess_tail"] = row[3], row[4], row[5]
-                res[name] = e
-            out.append(res)
-            r += P
-        return out
-    finally:
-        L.mcr_fileset_free(fs)
+        got = ctx.summarize_files(paths, min_chains, qs, diagnostics, phases)
+    except McrError as exc:
+        if exc.code in (_ffi.MCR_EMINCHAINS, _ffi.MCR_EMINCHAINS_ARG, _ffi.MCR_ENONFINITE):
+            raise ValueError(exc.message.split(": ", 1)[-1] if exc.code == _ffi.MCR_EMINCHAINS else exc.message) from exc
+        if "cannot compute stats of empty columns" in exc.message:
+            raise ValueError("cannot compute stats of empty columns") from exc
+        raise
+    if got is None:
+        return None
+    files, r = got
+    rows, out, r0 = _ffi.entries(r, qs, diagnostics), [], 0
+    for names, _C, _N in files:
+        out.append(dict(zip(names, rows[r0:r0 + len(names)])))
+        r0 += len(names)
+    return out
 
 
 def summarize_files(ctx: "_ffi.Context", sources: Sequence, params: Sequence[Iterable[str] | None] | None = None, *,
@@ -377,54 +330,31 @@ def summarize_files(ctx: "_ffi.Context", sources: Sequence, params: Sequence[Ite
                     j["P"] += P
                     continue
             jobs.append({"first": k, "count": 1, "shape": shape, "full": full, "P": P, "buf": d.buf})
-        pending = []
-        for j in jobs:
-            Cn, N = j["shape"]
-            t = DeviceTensor(ctx, j["buf"], (MCR_F64, Cn, N, j["P"], N, 1, Cn * N))
-            if ctx.inflight >= _ffi.MCR_MAX_INFLIGHT:
-                ctx.wait_one()
-            try:
-                pending.append(ctx.enqueue(t, min_chains=min_chains if j["full"] else 1, quantiles=qs,
-                                           diagnostics=j["full"]))
-            except McrError as exc:
-                raise ValueError(exc.message) from exc
-        try:
-            ctx.wait()
-        except McrError as exc:
-            raise ValueError(exc.message) from exc
+
+        def calls():
+            for j in jobs:
+                Cn, N = j["shape"]
+                t = DeviceTensor(ctx, j["buf"], (MCR_F64, Cn, N, j["P"], N, 1, Cn * N))
+                yield j, t, {"min_chains": min_chains if j["full"] else 1, "quantiles": qs, "diagnostics": j["full"]}
+
         results = [None] * len(models)
-        for j, b in zip(jobs, pending):
-            r = b.result()
-            p0 = 0
-            for k in range(j["first"], j["first"] + j["count"]):
-                P = len(models[k].params)
-                if P == 0:
-                    continue
-                results[k] = {key: (v[p0:p0 + P] if key != "q_lo" else v) for key, v in r.items()}
-                p0 += P
+        with _ffi.value_errors(), closing(_ffi.pipeline(ctx, calls())) as done:
+            for j, r in done:
+                if isinstance(r, McrError):
+                    raise r
+                k0, k1 = j["first"], j["first"] + j["count"]
+                results[k0:k1] = _ffi.split_result(r, [len(d.params) for d in models[k0:k1]])
         out = []
         for d, r in zip(models, results):
-            if r is not None and diagnostics and d.tensor is None:
+            if r is None:
+                out.append({})
+                continue
+            if diagnostics and d.tensor is None:         # ragged chains: one pipeline per parameter
                 x = d.to_host()
-                off = np.concatenate([[0], np.cumsum(d.counts)])
-                r = dict(r)
-                for k in ("rhat", "ess_bulk", "ess_tail"):
-                    r[k] = np.full(len(d.params), np.nan)
-                for i in range(len(d.params)):
-                    try:
-                        g = ctx.diagnose_chains([x[i, off[c]:off[c + 1]] for c in range(len(d.counts))],
-                                                min_chains=min_chains)
-                    except McrError as exc:
-                        raise ValueError(exc.message) from exc
-                    for k in ("rhat", "ess_bulk", "ess_tail"):
-                        r[k][i] = g[k]
-            out.append({p: _entry(r, i, qs, diagnostics) for i, p in enumerate(d.params)})
+                with _ffi.value_errors():
+                    r = {**r, **_ffi.ragged_diagnostics(ctx, x, d.counts, min_chains)}
+            out.append(dict(zip(d.params, _ffi.entries(r, qs, diagnostics))))
         return out
     finally:
-        try:
-            if ctx.inflight:
-                ctx.wait()
-        except McrError:
-            pass
         for d in models:
             d.free()

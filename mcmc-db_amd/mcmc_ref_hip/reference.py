@@ -9,7 +9,7 @@ from __future__ import annotations
 import os
 from collections.abc import Mapping, Sequence
 
-from . import convert
+from . import _ffi, convert
 from .backends import get_backend
 from .compare import compare_stats, compute_stats_from_draws
 from .draws import Draws, coerce_return
@@ -42,7 +42,7 @@ def _native_reader() -> bool:
 
 
 def _native_summaries(store: DataStore, models: Sequence[str], params, *, diagnostics: bool, min_chains: int = 4):
-    from . import _ffi, parquet
+    from . import parquet
     ctx = _ffi.default_context()
     paths = [store.resolve_draws_path(m) for m in models]
     try:
@@ -97,7 +97,7 @@ def diagnostics_for_model(model: str, params: Sequence[str] | None = None,
         return diag if params is None else {p: diag[p] for p in params if p in diag}
     if _native_reader():
         full = _native_summaries(store, [model], params, diagnostics=True)[0]
-        return {p: {k: v[k] for k in ("rhat", "ess_bulk", "ess_tail")} for p, v in full.items()}
+        return {p: {k: v[k] for k in _ffi.DIAG_KEYS} for p, v in full.items()}
     table, params = _table_and_params(store, model, params)
     return convert._compute_diagnostics(table, params)
 

@@ -23,6 +23,7 @@ import os
 import tempfile
 import time
 from collections.abc import Sequence
+from contextlib import closing
 from pathlib import Path
 
 import numpy as np
@@ -308,44 +309,27 @@ def summarize_models(ctx, models: Sequence[tuple[np.ndarray, str]], comm=None, m
             groups.setdefault(("b", arr.shape[1], arr.shape[2], arr.dtype.str), []).append(i)
         else:
             groups[("s", i)] = [i]
-    recs = []
-    pending = []
 
-    def drain():
-        try:
-            ctx.wait()
-            for members, bufs, t, dims in pending:
-                r = bufs.result()
-                p0 = 0
-                for i in members:
-                    P = models[i][0].shape[models[i][1].index("p")]
-                    part = {k: (v[p0:p0 + P] if k != "q_lo" else v) for k, v in r.items()}
-                    recs.append(pack_records(part, i, dims[0], dims[1]))
-                    p0 += P
-        finally:
-            for _, _, t, _ in pending:
-                t.free()
-            pending.clear()
-
-    error = None
-    try:
+    def calls():
         for key, members in groups.items():
             if key[0] == "b" and len(members) > 1:
-                big = np.concatenate([models[i][0] for i in members], axis=0)
-                t = ctx.upload(big, "pcn")
+                t = ctx.upload(np.concatenate([models[i][0] for i in members], axis=0), "pcn")
             else:
                 arr, layout = models[members[0]]
                 t = ctx.upload(np.ascontiguousarray(arr), layout)
-            pending.append((members, None, t, t.shape_cnp))
-            pending[-1] = (members, ctx.enqueue(t, min_chains=min_chains), t, t.shape_cnp)
-            if len(pending) == _ffi.MCR_MAX_INFLIGHT:
-                drain()
-        drain()
+            yield (members, t.shape_cnp), t, {"min_chains": min_chains}
+
+    recs, error = [], None
+    try:
+        with closing(_ffi.pipeline(ctx, calls(), owns=True)) as done:
+            for (members, (Cn, N, _P)), r in done:
+                if isinstance(r, _ffi.McrError):
+                    raise r
+                sizes = [models[i][0].shape[models[i][1].index("p")] for i in members]
+                for i, part in zip(members, _ffi.split_result(r, sizes)):
+                    recs.append(pack_records(part, i, Cn, N))
     except Exception as exc:  # noqa: BLE001 - settled with the other ranks below
         error = exc
-        for _, _, t, _ in pending:
-            t.free()
-        pending.clear()
     _agree(comm, error, "summarize_models")
     local = np.concatenate(recs, axis=0) if recs else np.empty((0, RECORD_DOUBLES))
     return gather_records(local, comm)
@@ -372,52 +356,30 @@ def summarize_param_split(ctx, draws: np.ndarray, comm=None, min_chains: int = 4
 def summarize_paths(ctx, paths: Sequence, comm=None, min_chains: int = 4) -> np.ndarray:
     """The corpus straight from disk on N GPUs: `paths` (draws/<model>.draws.parquet files, the same list on every
     rank) are assigned to ranks by greedy LPT over file size, each rank turns its share into statistics with ONE
-    `mcr_summarize_files` call (native Parquet ingest + kernels), and one all-gather of the 128-byte records puts
+    `Context.summarize_files` call (native Parquet ingest + kernels), and one all-gather of the 128-byte records puts
     every model's summary on every rank.  `model_idx` in the records indexes `paths`."""
     from . import _ffi, parquet
     world, rank = (comm.world, comm.rank) if comm is not None else (1, 0)
     paths = [os.fspath(p) for p in paths]
     mine = plan_shards([float(os.path.getsize(p)) for p in paths], world)[rank]
-    qs = np.array([0.05, 0.5, 0.95])
-    recs = []
-    error = None
+    recs, error = [], None
     try:
-        if mine:
-            L = ctx.lib
-            arr = (C.c_char_p * len(mine))(*[paths[i].encode() for i in mine])
-            fs = C.c_void_p()
-            rc = L.mcr_summarize_files(ctx.handle, arr, len(mine), int(min_chains), qs.ctypes.data_as(C.POINTER(C.c_double)),
-                                       3, 1, C.byref(fs))
-            if rc == _ffi.MCR_OK:
-                try:
-                    for k, i in enumerate(mine):
-                        P = int(L.mcr_fileset_params(fs, k))
-                        if P == 0:
-                            continue
-                        fld = lambda f, w=1: np.ctypeslib.as_array(L.mcr_fileset_field(fs, k, f), shape=(P * w,)).copy()  # noqa: E731
-                        q = fld(2, 3).reshape(P, 3)
-                        rec = np.empty((P, RECORD_DOUBLES))
-                        cols = [fld(0), fld(1), q[:, 0], q[:, 1], q[:, 2], fld(7), fld(8), fld(4), fld(5), fld(6), fld(9), fld(10),
-                                np.full(P, float(L.mcr_fileset_chains(fs, k))), np.full(P, float(L.mcr_fileset_draws(fs, k))),
-                                np.arange(P, dtype=np.float64), np.full(P, float(i))]
-                        for j, c in enumerate(cols):
-                            rec[:, j] = c
-                        recs.append(rec)
-                finally:
-                    L.mcr_fileset_free(fs)
-            elif rc == _ffi.MCR_ELAYOUT:          # shuffled rows somewhere in the share: the per-file route (device gather)
-                decoded = parquet.read_draws_many(ctx, [paths[i] for i in mine])
-                try:
-                    for d, i in zip(decoded, mine):
-                        if d.tensor is None:
-                            raise ValueError(f"{paths[i]}: chains of unequal length")
-                        r = ctx.summarize(d.tensor, min_chains=min_chains)
-                        recs.append(pack_records(r, i, len(d.counts), int(d.counts[0])))
-                finally:
-                    for d in decoded:
-                        d.free()
-            else:
-                ctx._check(rc)
+        got = ctx.summarize_files([paths[i] for i in mine], min_chains) if mine else ([], {})
+        if got is None:                         # shuffled rows somewhere in the share: the per-file route (device gather)
+            decoded = parquet.read_draws_many(ctx, [paths[i] for i in mine])
+            try:
+                for d, i in zip(decoded, mine):
+                    if d.tensor is None:
+                        raise ValueError(f"{paths[i]}: chains of unequal length")
+                    r = ctx.summarize(d.tensor, min_chains=min_chains)
+                    recs.append(pack_records(r, i, len(d.counts), int(d.counts[0])))
+            finally:
+                for d in decoded:
+                    d.free()
+        else:
+            files, r = got
+            for i, (_names, Cn, N), part in zip(mine, files, _ffi.split_result(r, [len(f[0]) for f in files])):
+                recs.append(pack_records(part, i, Cn, N))
     except Exception as exc:  # noqa: BLE001
         error = exc
     _agree(comm, error, "summarize_paths")

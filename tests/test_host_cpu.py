@@ -371,3 +371,122 @@ def test_convert_readers_cpu(tmp_path):
     assert bare.column_names == ["x", "chain", "draw"] and bare.column("draw").to_pylist() == [0, 1, 2]
     only_chain = convert._ensure_chain_draw(pa.table({"chain": [0, 0], "x": [1.0, 2.0]}))
     assert only_chain.column_names == ["chain", "x", "draw"]
+
+
+class _FakeTensor:
+    def __init__(self, k: int):
+        self.k, self.freed = k, 0
+
+    def free(self):
+        self.freed += 1
+
+
+class _FakeBufs:
+    def __init__(self, k):
+        self.k = k
+
+    def result(self) -> dict:
+        return {"k": self.k}
+
+
+class _FakeContext:
+    """enqueue / wait_one / wait / inflight with the bookkeeping of _ffi.Context, recorded in `log`; the jobs named in
+    `fail_enqueue` / `fail_wait` fail in that call."""
+
+    def __init__(self, foreign: int = 0, fail_enqueue=(), fail_wait=()):
+        from mcmc_ref_hip._ffi import McrError
+        self.McrError, self.fail_enqueue, self.fail_wait = McrError, set(fail_enqueue), set(fail_wait)
+        self.pending = [_FakeBufs(f"foreign{i}") for i in range(foreign)]
+        self.log, self.peak = [], len(self.pending)
+
+    @property
+    def inflight(self) -> int:
+        return len(self.pending)
+
+    def enqueue(self, t, **kw):
+        assert kw == {"min_chains": 4}
+        self.log.append(("enqueue", t.k))
+        if t.k in self.fail_enqueue:
+            raise self.McrError(-1, f"enqueue of {t.k}")
+        self.pending.append(_FakeBufs(t.k))
+        self.peak = max(self.peak, len(self.pending))
+        return self.pending[-1]
+
+    def wait_one(self):
+        b = self.pending.pop(0)
+        self.log.append(("wait_one", b.k))
+        if b.k in self.fail_wait:
+            raise self.McrError(-4, f"draws of {b.k} contain 1 non-finite value(s)")
+        return b
+
+    def wait(self):
+        self.log.append(("wait", [b.k for b in self.pending]))
+        self.pending.clear()
+
+
+def _jobs(n: int, pulled: list):
+    for k in range(n):
+        t = _FakeTensor(k)
+        pulled.append(t)
+        yield f"job{k}", t, {"min_chains": 4}
+
+
+def test_pipeline_window_order_errors_and_cleanup():
+    """_ffi.pipeline on a fake context: foreign calls drained first, at most MCR_MAX_INFLIGHT outstanding, results in
+    submission order, an error delivered for its own job only, every owned tensor freed once."""
+    from mcmc_ref_hip._ffi import MCR_MAX_INFLIGHT, McrError, pipeline
+    n = 3 * MCR_MAX_INFLIGHT + 1
+    ctx, pulled = _FakeContext(foreign=2, fail_enqueue={4}, fail_wait={9}), []
+    got = list(pipeline(ctx, _jobs(n, pulled), owns=True))
+    assert ctx.log[0] == ("wait", ["foreign0", "foreign1"])
+    assert [tag for tag, _ in got] == [f"job{k}" for k in range(n)]
+    assert ctx.peak <= MCR_MAX_INFLIGHT and ctx.inflight == 0
+    for k, (_, r) in enumerate(got):
+        if k in (4, 9):
+            assert isinstance(r, McrError) and str(k) in r.message
+        else:
+            assert r == {"k": k}
+    assert [op for op in ctx.log if op[0] == "wait_one"] == [("wait_one", k) for k in range(n) if k != 4]
+    assert [t.freed for t in pulled] == [1] * n
+    ctx = _FakeContext()                            # owns=False: the caller keeps its tensors
+    assert len(list(pipeline(ctx, _jobs(3, pulled := [])))) == 3 and [t.freed for t in pulled] == [0] * 3
+
+
+def test_pipeline_leaves_nothing_behind_when_stopped_early():
+    """An exception in the consumer's loop (under contextlib.closing) and an early close(): nothing in flight, every
+    tensor the window took freed exactly once, and no job pulled after the stop."""
+    from contextlib import closing
+    from mcmc_ref_hip._ffi import MCR_MAX_INFLIGHT, pipeline
+    n = 3 * MCR_MAX_INFLIGHT
+    ctx, pulled = _FakeContext(), []
+    with pytest.raises(KeyError):
+        with closing(pipeline(ctx, _jobs(n, pulled), owns=True)) as done:
+            for tag, _ in done:
+                if tag == "job2":
+                    raise KeyError(tag)
+    assert ctx.inflight == 0 and ctx.log[-1][0] == "wait"
+    assert len(pulled) == MCR_MAX_INFLIGHT + 2 and [t.freed for t in pulled] == [1] * len(pulled)
+
+    ctx, pulled = _FakeContext(), []
+    gen = pipeline(ctx, _jobs(n, pulled), owns=True)
+    assert next(gen)[0] == "job0" and next(gen)[0] == "job1"
+    gen.close()
+    assert ctx.inflight == 0 and len(pulled) == MCR_MAX_INFLIGHT + 1 and [t.freed for t in pulled] == [1] * len(pulled)
+
+
+def test_entries_and_split_result():
+    """The reference-shaped dicts built from a summary dict, and a batched result cut back into its models."""
+    from mcmc_ref_hip._ffi import entries, split_result
+    r = {"mean": np.array([1.0, 2.0]), "std": np.array([0.5, 0.25]), "q": np.array([[0.1, 0.9], [1.1, 2.9]]),
+         "rhat": np.array([1.001, 1.002]), "ess_bulk": np.array([900.0, 800.0]), "ess_tail": np.array([700.0, 600.0]),
+         "q_lo": np.array([3, 7])}
+    full = entries(r, (0.05, 0.95))
+    assert full[1] == {"mean": 2.0, "std": 0.25, "q5": 1.1, "q95": 2.9, "rhat": 1.002, "ess_bulk": 800.0,
+                       "ess_tail": 600.0}
+    assert list(full[0]) == ["mean", "std", "q5", "q95", "rhat", "ess_bulk", "ess_tail"]
+    assert all(type(v) is float for e in full for v in e.values())
+    assert entries(r, (0.05, 0.95), diagnostics=False)[0] == {"mean": 1.0, "std": 0.5, "q5": 0.1, "q95": 0.9}
+    assert entries(r) == [{"rhat": 1.001, "ess_bulk": 900.0, "ess_tail": 700.0},
+                          {"rhat": 1.002, "ess_bulk": 800.0, "ess_tail": 600.0}]
+    first, second = split_result(r, [1, 1])
+    assert entries(second, (0.05, 0.95)) == [full[1]] and first["q_lo"] is r["q_lo"] and list(first["q"][0]) == [0.1, 0.9]

@@ -75,7 +75,7 @@ def main():
             for t in tens:
                 t.free()
             qs = (0.05, 0.5, 0.95)
-            return [{p: parquet._entry(b.result(), i, qs, True) for i, p in enumerate(params)} for params, b in pend], t_dec, t_rest
+            return [dict(zip(params, _ffi.entries(b.result(), qs))) for params, b in pend], t_dec, t_rest
 
         def native_pass():
             return parquet.summarize_files(ctx, paths)
