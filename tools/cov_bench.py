@@ -11,13 +11,38 @@ instruction sustains on this chip depends on how densely it is issued (the chip 
 of back-to-back independent `v_mfma_f64_16x16x4f64` on every CU holds 46.1 TFLOP/s, the same instruction at 5 MFMAs per 4
 LDS loads 72.5 TFLOP/s (tools/ubench/mfma64_rate.hip, profiles/r03_mfma64_rate.txt); `frac_of_dense_loop` is against
 the first figure.
-Parity unpinned by the reference (no covariance there): the result is checked against numpy.cov(ddof=0)."""
+Parity unpinned by the reference (no covariance there).  Every size is checked before it is timed, on integer-valued
+draws whose covariance is exact in f64 in any summation order (the inputs of tests/test_ext_refs_cpu.py,
+`exact_cov_inputs`: offset + d with d in [-1000, 1000] in adjacent negated pairs, so the mean is the offset and
+G = D D^T an integer matrix below 2^53): every entry within (M + 8) eps sqrt(c_ii c_jj) + d_i d_j of G / M, d_i the
+moments kernel's mean bound, and the number of entries that differ from G / M in bits reported.  The kernel's time does
+not depend on the values."""
 import argparse, json, sys, time
 from pathlib import Path
 import numpy as np
 ROOT = Path(__file__).resolve().parents[1]
 sys.path[:0] = [str(ROOT), str(ROOT / "mcmc-db_amd")]
 from mcmc_ref_hip import _ffi
+
+EPS = 2.0 ** -52
+
+
+def exact_cov_inputs(P, M, rng):
+    """(x, off, D): x[p] = off[p] + D[p]; D integers in adjacent negated pairs, off[p] distinct multiples of 8."""
+    assert M % 2 == 0 and M * 1000 * 1000 < 2 ** 53
+    half = rng.integers(-1000, 1001, size=(P, M // 2)).astype(np.float64)
+    D = np.empty((P, M))
+    D[:, 0::2] = half
+    D[:, 1::2] = -half
+    off = 8.0 * (17 * np.arange(P) - 5 * P)
+    return D + off[:, None], off, D
+
+
+def cov_tolerance(ref, mean, M):
+    sd = np.sqrt(np.diag(ref))
+    d = 2 * np.spacing(np.abs(mean)) + 16 * EPS * sd
+    return (M + 8) * EPS * np.outer(sd, sd) + np.outer(d, d)
+
 
 PEAK_TF = 78.6
 MFMA_LOOP_TF = 46.1      # measured: tools/ubench/mfma64_rate, 5 independent accumulators, every CU busy
@@ -30,14 +55,19 @@ ctx = _ffi.Context(0)
 rows = []
 for P, M in ((100, 40000), (1000, 40000), (2048, 40000), (4096, 20000)):
     rng = np.random.default_rng(P)
-    x = rng.normal(size=(P, M)) * (1.0 + np.arange(P)[:, None] % 7) + np.arange(P)[:, None]
+    x, off, D = exact_cov_inputs(P, M, rng)
     dx = _ffi.DeviceBuffer(ctx, x.nbytes).upload(x)
     dc = _ffi.DeviceBuffer(ctx, P * P * 8)
     call = lambda: ctx._check(ctx.lib.mcr_covariance_dev(ctx.handle, dx.ptr, M, P, dc.ptr))
     call()
     cov = dc.download(np.float64, P * P).reshape(P, P)
-    exp = np.cov(x, ddof=0) if P <= 1000 else None
-    err = float(np.max(np.abs(cov - exp)) / np.max(np.abs(exp))) if exp is not None else None
+    exp = (D @ D.T) / float(M)                       # exact, rounded once
+    del D
+    err = float(np.max(np.abs(cov - exp)) / np.max(np.abs(exp)))
+    over = float(np.max(np.abs(cov - exp) / cov_tolerance(exp, off, M)))
+    nbits = int(np.count_nonzero(cov.view(np.int64) != exp.view(np.int64)))
+    assert over <= 1.0, (P, M, over)
+    del exp
     ctx.profile(True); ctx.profile_reset()
     t0 = time.perf_counter()
     for _ in range(a.reps):
@@ -53,6 +83,7 @@ for P, M in ((100, 40000), (1000, 40000), (2048, 40000), (4096, 20000)):
                  "executed_TFLOPs": ex_tf, "frac_of_peak": ex_tf / PEAK_TF, "frac_of_dense_loop": ex_tf / MFMA_LOOP_TF,
                  "priced_TFLOPs": priced / (kms * 1e-3) / 1e12, "priced_frac_of_peak": priced / (kms * 1e-3) / 1e12 / PEAK_TF,
                  "executed_over_priced": executed / priced, "max_rel_err_vs_numpy": err,
+                 "max_err_over_bound": over, "entries_differing_in_bits": nbits,
                  "other_kernels_ms": {k: v["total_ms"] / v["launches"] for k, v in pr.items() if k != "k_cov_mfma"}})
     print(json.dumps(rows[-1]), flush=True)
     dx.free(); dc.free()
