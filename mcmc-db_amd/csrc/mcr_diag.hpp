@@ -48,7 +48,7 @@ constexpr int kLag2 = kLag1 + 64 * kMoreBlocks;   // first lag of tier 3
 constexpr int kLongGroup = 256; // lags per k_acov_long workgroup
 constexpr int kLongSlots = 2;   // listed pairs a k_acov_long launch works on at a time (its grid: lag groups x this; a launch
                                 // with nothing listed must stay cheap: every workgroup of it still has to find a CU with free LDS)
-enum SegField { SG_S = kLag1, SG_S0, SG_Q0, SG_S1, SG_Q1, SG_MIN, SG_MAX, SG_MIN0, SG_MAX0, SG_MIN1, SG_MAX1 };   // (MIN / MAX of the rank codes: chain, first half, second half)
+enum SegField { SG_S = kLag1, SG_S0, SG_Q0, SG_S1, SG_Q1, SG_MIN, SG_MAX, SG_MIN0, SG_MAX0, SG_MIN1, SG_MAX1 };   // (MIN == MAX over the segments <=> all rank codes equal: chain, first half, second half; k_acov_seg writes 0 / 1)
 
 __device__ __forceinline__ i64 pos8(i64 j) { return j + ((j >> 3) << 1); }
 
@@ -172,8 +172,7 @@ __global__ __launch_bounds__(NT) void k_acov_seg(const u32* __restrict__ zb, con
     __shared__ __attribute__((aligned(16))) double sx[LX];
     __shared__ __attribute__((aligned(16))) double scr2[FIRST ? 8 : NW * 4 * 64];
     __shared__ double tot[64];
-    __shared__ double wred[NW * 4 * 8];     // (the half windows' min / max go through `tot`, free until the lag products are reduced:
-                                            //  512 more bytes here cost the seventh resident workgroup per CU)
+    __shared__ double wred[NW * 4 * 8];     // (5 sums + 3 flags per DPP row: 512 more bytes here cost the seventh resident workgroup per CU)
 
     const int tid = threadIdx.x;
     const int seg = blockIdx.x, c = blockIdx.y;
@@ -201,11 +200,12 @@ __global__ __launch_bounds__(NT) void k_acov_seg(const u32* __restrict__ zb, con
         const int a0 = (hc > 0) ? clip(rel(0)) : 0, a1 = (hc > 0) ? clip(rel(nh)) : 0;             // first half
         const int b0 = (hc > 0) ? clip(rel(hc)) : 0, b1 = (hc > 0) ? clip(rel(hc + nh)) : 0;        // second half
         double S = 0.0, S0 = 0.0, Q0 = 0.0, S1 = 0.0, Q1 = 0.0;
-        // min / max only tell a constant chain (min == max) from the others, and z = ztab[code] is strictly monotone:
-        // they are taken on the integer codes (full-rate v_min_u32 / v_max_u32; the f64 pair is not, and needs its operands
-        // canonicalised) and stored as doubles, which hold a u32 exactly
-        u32 cmin = 0xFFFFFFFFu, cmax = 0u;
-        u32 c0min = 0xFFFFFFFFu, c0max = 0u, c1min = 0xFFFFFFFFu, c1max = 0u;    // the same for the two halves of the chain (split R-hat)
+        // A constant chain (or half) is one whose rank codes are all equal (z = ztab[code] is strictly monotone), that is,
+        // all equal to ONE code of the window that every workgroup of the chain can load: the chain's first draw for the
+        // chain and its first half, draw hc for the second half.  Per draw and window that is one compare whose lane mask
+        // is ORed on the scalar unit; the masks are wave-uniform, so there is nothing to reduce across lanes.
+        const u32 ref0 = (nc > 0) ? zc[0] : 0u, ref1 = (hc > 0) ? zc[hc] : 0u;
+        unsigned long long dif = 0ull, dif0 = 0ull, dif1 = 0ull;      // lanes that saw a code other than the window's reference
         double v[NLD];
         u32 cd[NLD];
 #pragma unroll
@@ -217,42 +217,47 @@ __global__ __launch_bounds__(NT) void k_acov_seg(const u32* __restrict__ zb, con
         // The three windows are ranges of j and a wave's 64 slots are consecutive: a wave that lies wholly inside (or
         // outside) a window -- all but a handful -- decides that with scalar compares and adds without per-lane masks.
         const int jw0 = __builtin_amdgcn_readfirstlane(tid & ~63);
-#define MCR_IN_WINDOW(lo, hi, BODY)                                                        \
-        if (jw >= (lo) && jw + 64 <= (hi)) { BODY }                                        \
-        else if (jw + 64 > (lo) && jw < (hi)) { if (j >= (lo) && j < (hi)) { BODY } }
+        // (The compare mask of a wave that straddles a window edge is taken with every lane active, outside the per-lane
+        // test: updated under it, the mask would live in VGPRs.)
+#define MCR_IN_WINDOW(lo, hi, DIF, REF, BODY)                                              \
+        if (jw >= (lo) && jw + 64 <= (hi)) { BODY DIF |= __builtin_amdgcn_ballot_w64(cd[u] != (REF)); } \
+        else if (jw + 64 > (lo) && jw < (hi)) {                                            \
+            const bool in = j >= (lo) && j < (hi);                                         \
+            DIF |= __builtin_amdgcn_ballot_w64(in && cd[u] != (REF));                      \
+            if (in) { BODY }                                                               \
+        }
 #pragma unroll
         for (int u = 0; u < NLD; ++u) {
             const int jw = u * NT + jw0, j = u * NT + tid;
             const double x = v[u];
-            MCR_IN_WINDOW(0, own_n, S += x; cmin = min(cmin, cd[u]); cmax = max(cmax, cd[u]);)
-            MCR_IN_WINDOW(a0, a1, S0 += x; Q0 = fma(x, x, Q0); c0min = min(c0min, cd[u]); c0max = max(c0max, cd[u]);)
-            MCR_IN_WINDOW(b0, b1, S1 += x; Q1 = fma(x, x, Q1); c1min = min(c1min, cd[u]); c1max = max(c1max, cd[u]);)
+            MCR_IN_WINDOW(0, own_n, dif, ref0, S += x;)
+            MCR_IN_WINDOW(a0, a1, dif0, ref0, S0 += x; Q0 = fma(x, x, Q0);)
+            MCR_IN_WINDOW(b0, b1, dif1, ref1, S1 += x; Q1 = fma(x, x, Q1);)
             if (j < WIN) sx[pos8(j)] = (j < r_n) ? x : 0.0;
         }
 #undef MCR_IN_WINDOW
-        // The five sums and min / max: DPP inside the rows of 16 lanes, the 4 NW row results through the LDS, seven
-        // lanes finish (one barrier; no cross-row shuffles).
+        // The five sums: DPP inside the rows of 16 lanes, the 4 NW row results through the LDS, eight lanes finish (one
+        // barrier; no cross-row shuffles); the three masks ride along as 0 / 1.  The record keeps its (MIN, MAX) fields and
+        // k_diag_combine its `min == max over the segments` test: a segment writes (0, 0) for a window in which nothing
+        // differed from the reference -- also the neutral pair of a segment without a draw in the window -- and (0, 1)
+        // otherwise.
         S = row_sum(S); S0 = row_sum(S0); Q0 = row_sum(Q0); S1 = row_sum(S1); Q1 = row_sum(Q1);
-        cmin = row_min_u32(cmin); cmax = row_max_u32(cmax);
-        c0min = row_min_u32(c0min); c0max = row_max_u32(c0max); c1min = row_min_u32(c1min); c1max = row_max_u32(c1max);
-        static_assert(NW * 4 * 4 <= 64, "the four half-window fields of every DPP row fit `tot`");
         if ((tid & 15) == 0) {
             double* q = wred + (tid >> 4) * 8;
-            q[0] = S; q[1] = S0; q[2] = Q0; q[3] = S1; q[4] = Q1; q[5] = (double)cmin; q[6] = (double)cmax;
-            double* q2 = tot + (tid >> 4) * 4;
-            q2[0] = (double)c0min; q2[1] = (double)c0max; q2[2] = (double)c1min; q2[3] = (double)c1max;
+            q[0] = S; q[1] = S0; q[2] = Q0; q[3] = S1; q[4] = Q1;
+            q[5] = dif ? 1.0 : 0.0; q[6] = dif0 ? 1.0 : 0.0; q[7] = dif1 ? 1.0 : 0.0;
         }
         __syncthreads();
         double* r = rec + ((pk * C + c) * (i64)nseg + seg) * kSegRec;
-        if (tid < 11) {
-            const double* src = (tid < 7) ? wred + tid : tot + (tid - 7);
-            const int stride = (tid < 7) ? 8 : 4;
+        if (tid < 8) {
+            const double* src = wred + tid;
             double t = src[0];
             for (int w = 1; w < NW * 4; ++w) {
-                const double x = src[w * stride];
-                t = (tid < 5) ? t + x : (((tid & 1) == 1) ? fmin(t, x) : fmax(t, x));      // 5, 7, 9: minima; 6, 8, 10: maxima
+                const double x = src[w * 8];
+                t = (tid < 5) ? t + x : fmax(t, x);
             }
-            r[SG_S + tid] = t;        // SG_S, SG_S0, SG_Q0, SG_S1, SG_Q1, SG_MIN, SG_MAX, SG_MIN0 .. SG_MAX1 are consecutive
+            if (tid < 5) r[SG_S + tid] = t;         // SG_S, SG_S0, SG_Q0, SG_S1, SG_Q1 are consecutive
+            else { r[SG_MIN + 2 * (tid - 5)] = 0.0; r[SG_MAX + 2 * (tid - 5)] = t; }      // ... and so are the (MIN, MAX) pairs
         }
         double acc[8];
 #pragma unroll

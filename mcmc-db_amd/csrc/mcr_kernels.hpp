@@ -23,6 +23,7 @@
 //
 // (aN) = row of SURVEY.md section 8(a); reference file:line citations are next to each kernel.
 #pragma once
+#include <type_traits>
 #include "mcr_device.hpp"
 #include "mcr_sortnet.h"
 
@@ -447,31 +448,34 @@ __global__ __launch_bounds__(NT) void k_tile_sort(const XT* __restrict__ X, i64 
     const int count = (int)((M - base < (i64)T) ? M - base : (i64)T);
     const XT* src = X + p * M + base;    // XT = float: f32 tensors in the Arrow layout are widened here, not by an ingest pass
 
-    double bad = 0.0;
-#pragma unroll
-    for (int i = 0; i < VT; ++i) {
-        const int e = i * NT + tid;
-        double v = INFINITY;
-        if (e < count) {
-            v = (double)src[e];
-            bad += isfinite(v) ? 0.0 : 1.0;
-        }
-        skey[pos16(e)] = v;
-    }
-    __syncthreads();
-
+    // Lane tid takes draws i * NT + tid straight into its sort registers (coalesced loads, no staging pass through the LDS):
+    // the network and the merge levels sort whatever 16 draws a lane starts with.  Which of a tile's equal draws comes first
+    // therefore differs from a blocked hand-out; nothing downstream sees it (equal draws share one average rank).
+    // count == T is workgroup-uniform: a full tile (nine of C1's ten per parameter) takes the paths without a per-draw
+    // `e < count` test, chosen by a scalar branch around each of the three places that have one.
+    const bool full = count == T;
     double k[VT];
     u32 ix[VT];
+    double bad = 0.0;
+    auto load = [&](auto full_c) {
+        constexpr bool FULL = decltype(full_c)::value;
 #pragma unroll
-    for (int i = 0; i < VT; ++i) {
-        const int e = tid * VT + i;
-        k[i] = skey[pos16(e)];
-        ix[i] = (e < count) ? (u32)(base + e) : 0xFFFFFFFFu;
-    }
+        for (int i = 0; i < VT; ++i) {
+            const int e = i * NT + tid;
+            const bool live = FULL || e < count;
+            // a pad slot re-reads the tile's last draw instead of skipping the load: a load under a per-lane test waits for
+            // its value inside the test, and the lane's 16 loads go out one round trip after the other
+            const double v = (double)src[FULL ? e : min(e, count - 1)];
+            k[i] = live ? v : INFINITY;
+            ix[i] = live ? (u32)(base + e) : 0xFFFFFFFFu;
+            bad += (live && !isfinite(v)) ? 1.0 : 0.0;
+        }
+    };
+    if (full) load(std::true_type{}); else load(std::false_type{});
     thread_sort<VT>(k, ix);
     constexpr bool kLaneLevels = MCR_TILE_DPP_LEVELS >= 2 && VT == 16;
     if constexpr (kLaneLevels) lane_merge_levels_16_to_64(k, ix);
-    __syncthreads();
+    // (no barrier: this is the workgroup's first access to the LDS)
 #pragma unroll
     for (int i = 0; i < VT; ++i) {
         const int e = tid * VT + i;
@@ -502,10 +506,15 @@ __global__ __launch_bounds__(NT) void k_tile_sort(const XT* __restrict__ X, i64 
         __syncthreads();
     }
 
-    for (int e = tid; e < count; e += NT) {
-        keys[p * M + base + e] = skey[pos16(e)];
-        idx[p * M + base + e] = sidx[posi(e)];
-    }
+    auto write_out = [&](auto full_c) {
+        constexpr bool FULL = decltype(full_c)::value;
+#pragma nounroll
+        for (int e = tid; e < (FULL ? T : count); e += NT) {
+            keys[p * M + base + e] = skey[pos16(e)];
+            idx[p * M + base + e] = sidx[posi(e)];
+        }
+    };
+    if (full) write_out(std::true_type{}); else write_out(std::false_type{});
     // regular samples (every 64th order statistic of the tile) for the exact bucket partition
     if (samp != nullptr && tid < T / 64) {
         const int e = 64 * tid + 63;
@@ -515,14 +524,19 @@ __global__ __launch_bounds__(NT) void k_tile_sort(const XT* __restrict__ X, i64 
     // Moments of the tile, two-pass like the reference (mean first, then squared deviations; compare.py:62-63), from the
     // lane's VT sorted draws still in registers (the draws are read from HBM exactly once): k_finalize merges the
     // tiles with Chan's update.  Slots at or beyond `count` hold the +inf pads.
-    double s1 = 0.0;
+    double s1 = 0.0, s2 = 0.0, e1 = 0.0, mt = 0.0;
+    auto moments = [&](auto full_c) {
+        constexpr bool FULL = decltype(full_c)::value;
+        const int nlive = count - tid * VT;         // the lane's sorted slots [0, nlive) hold draws, the others pads
 #pragma unroll
-    for (int i = 0; i < VT; ++i) s1 += (tid * VT + i < count) ? k[i] : 0.0;
-    s1 = block_sum<NT>(s1, red);
-    const double mt = s1 / (double)count;
-    double s2 = 0.0, e1 = 0.0;       // second pass about mt; e1 = sum (x - mt) is what rounding left of the mean
+        for (int i = 0; i < VT; ++i) s1 += (FULL || i < nlive) ? k[i] : 0.0;
+        s1 = block_sum<NT>(s1, red);
+        mt = s1 / (double)count;
+        // second pass about mt; e1 = sum (x - mt) is what rounding left of the mean
 #pragma unroll
-    for (int i = 0; i < VT; ++i) { const double d = (tid * VT + i < count) ? k[i] - mt : 0.0; s2 = fma(d, d, s2); e1 += d; }
+        for (int i = 0; i < VT; ++i) { const double d = (FULL || i < nlive) ? k[i] - mt : 0.0; s2 = fma(d, d, s2); e1 += d; }
+    };
+    if (full) moments(std::true_type{}); else moments(std::false_type{});
     block_sum3<NT>(s2, e1, bad, red);
     if (tid == 0) store_slice_moments(part + (p * ntiles + tile) * kMomRec, mt, e1, s2, bad, (double)count);
 }

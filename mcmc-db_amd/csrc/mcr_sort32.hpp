@@ -141,26 +141,28 @@ __global__ __launch_bounds__(NT) void k_tile_sort32(const float* __restrict__ X,
     const int count = (int)((M - base < (i64)T) ? M - base : (i64)T);
     const float* src = X + p * M + base;
 
-    double bad = 0.0;
-#pragma unroll
-    for (int i = 0; i < VT; ++i) {
-        const int e = i * NT + tid;
-        u64 r = kRecPad;
-        if (e < count) {
-            const float v = src[e];
-            bad += isfinite(v) ? 0.0 : 1.0;
-            r = ((u64)f32_key(v) << 32) | (u64)(u32)(base + e);
-        }
-        srec[pos16(e)] = r;
-    }
-    __syncthreads();
+    // As k_tile_sort: lane tid takes draws i * NT + tid straight into its sort registers (no staging pass through the LDS),
+    // and a full tile (count == T, workgroup-uniform) runs without the per-draw `e < count` tests.  Records are distinct
+    // (the position is the low word), so the sorted tile does not depend on which draws a lane starts with.
+    const bool full = count == T;
     u64 r[VT];
+    double bad = 0.0;
+    auto load = [&](auto full_c) {
+        constexpr bool FULL = decltype(full_c)::value;
 #pragma unroll
-    for (int i = 0; i < VT; ++i) r[i] = srec[pos16(tid * VT + i)];
+        for (int i = 0; i < VT; ++i) {
+            const int e = i * NT + tid;
+            const bool live = FULL || e < count;
+            const float v = src[FULL ? e : min(e, count - 1)];      // every load unconditional and in flight, as in k_tile_sort
+            bad += (live && !isfinite(v)) ? 1.0 : 0.0;
+            r[i] = live ? (((u64)f32_key(v) << 32) | (u64)(u32)(base + e)) : kRecPad;
+        }
+    };
+    if (full) load(std::true_type{}); else load(std::false_type{});
     thread_sort_rec<VT>(r);
     constexpr bool kLaneLevels = MCR_TILE_DPP_LEVELS >= 3 && VT == 16;
     if constexpr (kLaneLevels) lane_merge_levels_rec(r);
-    __syncthreads();
+    // (no barrier: this is the workgroup's first access to the LDS)
 #pragma unroll
     for (int i = 0; i < VT; ++i) srec[pos16(tid * VT + i)] = r[i];
     __syncthreads();
@@ -179,20 +181,29 @@ __global__ __launch_bounds__(NT) void k_tile_sort32(const float* __restrict__ X,
         for (int i = 0; i < VT; ++i) srec[pos16(tid * VT + i)] = r[i];
         __syncthreads();
     }
-    for (int e = tid; e < count; e += NT) recs[p * M + base + e] = srec[pos16(e)];
+    auto write_out = [&](auto full_c) {
+        constexpr bool FULL = decltype(full_c)::value;
+#pragma nounroll
+        for (int e = tid; e < (FULL ? T : count); e += NT) recs[p * M + base + e] = srec[pos16(e)];
+    };
+    if (full) write_out(std::true_type{}); else write_out(std::false_type{});
     if (samp != nullptr && tid < T / 64) {
         const int e = 64 * tid + 63;
         samp[(p * ntiles + tile) * (T / 64) + tid] = (e < count) ? key_value(rec_key(srec[pos16(e)])) : INFINITY;
     }
     __syncthreads();                 // `red` aliases srec from here on
-    double s1 = 0.0;
+    double s1 = 0.0, s2 = 0.0, e1 = 0.0, mt = 0.0;
+    auto moments = [&](auto full_c) {
+        constexpr bool FULL = decltype(full_c)::value;
+        const int nlive = count - tid * VT;         // the lane's sorted slots [0, nlive) hold draws, the others pads
 #pragma unroll
-    for (int i = 0; i < VT; ++i) s1 += (tid * VT + i < count) ? key_value(rec_key(r[i])) : 0.0;
-    s1 = block_sum<NT>(s1, red);
-    const double mt = s1 / (double)count;
-    double s2 = 0.0, e1 = 0.0;
+        for (int i = 0; i < VT; ++i) s1 += (FULL || i < nlive) ? key_value(rec_key(r[i])) : 0.0;
+        s1 = block_sum<NT>(s1, red);
+        mt = s1 / (double)count;
 #pragma unroll
-    for (int i = 0; i < VT; ++i) { const double d = (tid * VT + i < count) ? key_value(rec_key(r[i])) - mt : 0.0; s2 = fma(d, d, s2); e1 += d; }
+        for (int i = 0; i < VT; ++i) { const double d = (FULL || i < nlive) ? key_value(rec_key(r[i])) - mt : 0.0; s2 = fma(d, d, s2); e1 += d; }
+    };
+    if (full) moments(std::true_type{}); else moments(std::false_type{});
     block_sum3<NT>(s2, e1, bad, red);
     if (tid == 0) store_slice_moments(part + (p * ntiles + tile) * kMomRec, mt, e1, s2, bad, (double)count);
 }
