@@ -64,6 +64,8 @@ typedef struct mcr_ctx mcr_ctx;
  *                 backends_numpy.py:40-47).  q_lo[k] = floor((M-1)*q_k): the order-statistic
  *                 index (integer, bit-exact gate).
  *  median         statistics.median of the pooled draws, the fold point (diagnostics.py:97).
+ *                 Where the middle draws are zeros of mixed sign, the earlier ones in time order count as the
+ *                 smaller, as in Python's sorted(); a median that only rounds to zero keeps the sign of the sum.
  *  rhat           split_rhat(): max(rhat_bulk, rhat_tail) with Python max() NaN ordering
  *                 (diagnostics.py:13-40); rhat_bulk / rhat_tail are its two operands.
  *  ess_bulk/tail  ess_bulk(), ess_tail() (diagnostics.py:43-73).

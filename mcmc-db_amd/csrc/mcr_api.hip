@@ -707,6 +707,7 @@ int run_pipeline(mcr_ctx* ctx, PipeIn& a)
 {
     const i64 M = a.M, pc = a.pc;
     const unsigned py = (unsigned)pc;
+    a.q.xt = a.X; a.q.xf32 = a.x_f32 ? 1 : 0;      // the time order, for the sign of a median made of zero draws
     Sorted so;
     {
         const int rc = sort_stage(ctx, a, so);

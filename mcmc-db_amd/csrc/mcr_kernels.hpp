@@ -44,6 +44,9 @@ struct QArgs {
     int nq;
     i64 lo[32];
     double g[32];
+    // the draws in time order, [pc][M] (f64, or f32 with xf32): only a median of exactly zero looks at them (wave_order_stats)
+    const void* xt = nullptr;
+    int xf32 = 0;
 };
 
 // XCD-aware block -> (parameter, block-within-parameter) map for kernels that scatter into one
@@ -644,6 +647,48 @@ __device__ __forceinline__ void block_tie_runs(KF key_at, int total, int* wsh, i
     __syncthreads();
 }
 
+// Signs of the zeros number t0 and t1 = t0 + 1 (0-based) of x[0, M) in time order, by one wave in ONE pass: bit 0 = zero t0
+// is a negative zero, bit 1 = zero t1 is (t0 < 0: only t1 is asked for).  A step takes 512 draws, eight independent loads
+// per lane (sixteen would halve the fold kernel's occupancy), and counts their zeros with ballots; only the step that holds a target is looked at draw by draw.  Only
+// wave_order_stats calls it, for a median that is a zero draw.
+__device__ __forceinline__ bool sign_bit_set(double v) { return __double_as_longlong(v) < 0; }
+__device__ __forceinline__ bool sign_bit_set(float v) { return __float_as_int(v) < 0; }
+template <typename T>
+__device__ __noinline__ unsigned wave_zero_signs(const T* __restrict__ x, i64 M, i64 t0, i64 t1)
+{
+    constexpr int U = 8;
+    const int lane = threadIdx.x & 63;
+    i64 seen = 0, t = (t0 >= 0) ? t0 : t1;
+    unsigned out = 0;
+    for (i64 b = 0; b < M; b += 64 * U) {
+        T v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const i64 i = b + u * 64 + lane;
+            v[u] = (i < M) ? x[i] : (T)1;
+        }
+        i64 c = 0;
+#pragma unroll
+        for (int u = 0; u < U; ++u) c += (i64)__popcll(__ballot(v[u] == (T)0));
+        if (seen + c <= t) { seen += c; continue; }          // (wave-uniform: the ballots are)
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const unsigned long long zm = __ballot(v[u] == (T)0), nm = __ballot(v[u] == (T)0 && sign_bit_set(v[u]));
+            const i64 cu = (i64)__popcll(zm);
+            while (seen + cu > t) {                          // zero number t is among these 64 draws
+                unsigned long long m = zm;
+                for (i64 j = seen; j < t; ++j) m &= m - 1;   // drop the zeros in front of it
+                const bool neg = (nm & m & (~m + 1ull)) != 0;   // its lane: the lowest bit left
+                if (t == t1) return out | (neg ? 2u : 0u);
+                out |= neg ? 1u : 0u;
+                t = t1;
+            }
+            seen += cu;
+        }
+    }
+    return out;
+}
+
 // Order statistics of one parameter by ONE WAVE from its pooled ascending keys: quantiles (numpy `linear` lerp, which
 // pyarrow's interpolation="linear" agrees with to 1 ulp; src/mcmc_ref/backends_numpy.py:44, backends_arrow.py:40-42),
 // statistics.median (diagnostics.py:97) and the fold split point s = #(x < med), found by a 64-ary search (64 probes and
@@ -665,11 +710,21 @@ __device__ __forceinline__ i64 wave_order_stats(const KT* __restrict__ k, i64 M,
     // every draw up to index M/2 - 1 is below the median and the one at M/2 is not, so s = M/2 and the search (three
     // dependent rounds of loads in front of every fold workgroup's merge) is skipped
     const double below = (M >= 2) ? sorted_key(k, M / 2 - 1) : -INFINITY, at = sorted_key(k, M / 2);
-    const double med = (M & 1) ? at : (below + at) / 2.0;
-    if (write && lane == 0) res[R_MEDIAN * P + p] = med;
-    // (!(at < med): draws near 1e308 can overflow below + at to +inf, and then #(x < med) is M, not M / 2: ADVICE r3)
-    if (below < med && !(at < med)) { med_out = med; return M / 2; }
+    double med = (M & 1) ? at : (below + at) / 2.0;
+    // A median that IS a zero draw (odd M), or the mean of two zero draws (even M): -0.0 and +0.0 tie, the sort keeps no order
+    // among them, and which of them stand in the middle decides the sign of the median.  statistics.median sorts stably, so
+    // its middle draws are the zeros number M/2 - s (and M/2 - s - 1, even M) of the TIME order, s = #(x < 0): look those up in
+    // the draws themselves.  (Only the reported median: |x - med| and the split point are the same for either sign.)  Any
+    // other median skips this -- also one that is zero by arithmetic alone ((-5e-324 + 0.0) / 2 rounds to -0.0, (-a + a) / 2
+    // is +0.0): its sign is the sum's.
+    const bool zero_med = write && q.xt != nullptr && at == 0.0 && ((M & 1) || below == 0.0);
+    if (write && lane == 0 && !zero_med) res[R_MEDIAN * P + p] = med;
     i64 lo = 0, hi = M;  // first index with k[i] >= med lies in [lo, hi]
+    // (!(at < med): draws near 1e308 can overflow below + at to +inf, and then #(x < med) is M, not M / 2: ADVICE r3)
+    if (below < med && !(at < med)) {
+        if (!zero_med) { med_out = med; return M / 2; }
+        lo = hi = M / 2;
+    }
     while (lo < hi) {
         const i64 step = (hi - lo + 63) / 64;
         const i64 pos = lo + step * (lane + 1) - 1;                 // ascending probes, the last one at or beyond hi - 1
@@ -678,6 +733,15 @@ __device__ __forceinline__ i64 wave_order_stats(const KT* __restrict__ k, i64 M,
         const i64 nhi = lo + step * (cnt + 1) - 1;                  // probe cnt (if any) is the first one not below
         lo += step * cnt;
         hi = (nhi < hi) ? nhi : hi;
+    }
+    if (zero_med) {
+        const i64 r = M / 2 - lo;                                   // the draw at M/2 is zero number r (r >= 1 for even M)
+        const i64 t0 = (M & 1) ? -1 : r - 1;
+        const unsigned sg = q.xf32 ? wave_zero_signs(reinterpret_cast<const float*>(q.xt) + p * M, M, t0, r)
+                                   : wave_zero_signs(reinterpret_cast<const double*>(q.xt) + p * M, M, t0, r);
+        const bool neg = (M & 1) ? (sg & 2u) != 0 : sg == 3u;       // (-0.0 + -0.0) / 2 alone is -0.0
+        med = neg ? -0.0 : 0.0;
+        if (lane == 0) res[R_MEDIAN * P + p] = med;
     }
     med_out = med;
     return lo;
