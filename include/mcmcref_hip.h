@@ -378,6 +378,50 @@ int mcr_fileset_phases(const mcr_fileset* fs, double* ms, int cap);
 int mcr_fileset_jobs(const mcr_fileset* fs);
 void mcr_fileset_free(mcr_fileset* fs);
 
+/* ------------------------------------------------------------------------------------------------
+ * CmdStan chain CSVs -> device tensor.
+ * Replaces parse_cmdstan_csv (src/mcmc_ref/cmdstan_generate.py:13-29): the csv.DictReader row loop and
+ * its float() per field.  Lines starting with '#' are dropped wherever they stand, the first remaining
+ * line is the header, whitespace-only lines are no rows.  The text is uploaded once; one kernel indexes
+ * the data rows, one parses them: every field is converted on the device by the Eisel-Lemire algorithm
+ * (Lemire 2021; Mushtak & Lemire 2023), which is float()'s correctly rounded value or "hard".  Hard
+ * fields -- more than 19 significant digits that sit on a rounding boundary, inf / nan, anything outside
+ * [ws][+-]digits[.digits][eE[+-]digits][ws] -- are finished on the host with strtod after a check of
+ * float()'s grammar (no underscores) and patched in; text float() would refuse ends the call with
+ * MCR_EINVAL naming file, data row, column and text.  So does a row whose field count differs from the
+ * header's and a '"' in a data row ("quoted fields are not supported").
+ * Limits: the files of one call hold less than 4 GiB of text (offsets are 32-bit); at most 65535 files.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct mcr_csv mcr_csv;
+#define MCR_CSV_CHUNK 16384 /* bytes of text one workgroup of the line index scans */
+
+/* Host only (ctx may be NULL, like mcr_parquet_open): finds the header line (cmdstan_generate.py:16-20), the body
+ * offset and the column names of a file image, which the caller keeps alive and unchanged until mcr_csv_close. */
+int mcr_csv_open(mcr_ctx* ctx, const void* bytes, size_t len, mcr_csv** out);
+/* The same for files: replaces Path(path).open() + the line filter (cmdstan_generate.py:16-19) with the reader of
+ * mcr_summarize_files -- MCR_IO_THREADS threads pread the images into the context's pinned buffer, the uploads are
+ * issued behind them -- and fills out[0 .. n_paths).  The handles stay stageable until the context reads other files
+ * (the next mcr_csv_open_paths, mcr_csv_stage of caller images, mcr_summarize_files or mcr_parquet_decode). */
+int mcr_csv_open_paths(mcr_ctx* ctx, const char* const* paths, int n_paths, mcr_csv** out);
+void mcr_csv_close(mcr_csv* f);
+int mcr_csv_num_columns(const mcr_csv* f);                   /* 0: the file has no header line */
+const char* mcr_csv_column_name(const mcr_csv* f, int column); /* raw header field, whitespace stripped; NULL if out of range */
+int64_t mcr_csv_body_offset(const mcr_csv* f);               /* first byte after the header line */
+
+/* Uploads the images (unless mcr_csv_open_paths already has), runs the line index and returns the data rows of
+ * every file: the `for row in reader` count of cmdstan_generate.py:23.  All files share the launches. */
+int mcr_csv_stage(mcr_ctx* ctx, const mcr_csv* const* files, int n_files, int64_t* rows);
+
+/* Parses header columns columns[f * n_cols + k], k < n_cols, of the first max_rows data rows of every staged file f
+ * into out_dev[f * stride_file + r * stride_row + k * stride_col] (float(value), cmdstan_generate.py:28; the caller
+ * picks the columns, e.g. those not ending in "__", cmdstan_generate.py:25).  *hard = fields finished on the host. */
+int mcr_csv_decode(mcr_ctx* ctx, const int* columns, int n_cols, int64_t max_rows, double* out_dev,
+                   int64_t stride_file, int64_t stride_row, int64_t stride_col, int64_t* hard);
+
+/* The device's field parser on the host (float(), cmdstan_generate.py:28).  Returns 0 = decided, 1 = hard (*out is
+ * then the host finisher's strtod value), MCR_EINVAL = float() would raise ValueError. */
+int mcr_parse_double(const char* text, size_t len, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,7 @@
 #include "mcr_fft.hpp"
 #include "mcr_ext.hpp"
 #include "mcr_parquet.hpp"
+#include "mcr_csv.hpp"
 #include "mcr_comm.hpp"
 
 using namespace mcr;
@@ -50,13 +51,15 @@ constexpr int kT3Workgroups = 256;    // workgroups of a k_tier3 launch (they sh
 enum KernelId {
     K_INGEST = 0, K_MOMENTS, K_MOMENTS_FINAL, K_TILE_SORT, K_MERGE, K_ORDER_STATS, K_RANK_Z, K_FOLD_MERGE,
     K_DIAG, K_FINALIZE, K_COMPARE, K_FILL, K_SPLITTERS, K_BUCKET_MERGE, K_ACOV_MORE,
-    K_DIAG2, K_ACOV_SEG, K_TWO_SAMPLE, K_COV, K_ZTABLE, K_PQ_SNAPPY, K_PQ_DECODE, K_GATHER, K_ACOV_LONG, K_DIAG_LONG, K_COV_FINAL, K_FFT, K_COUNT
+    K_DIAG2, K_ACOV_SEG, K_TWO_SAMPLE, K_COV, K_ZTABLE, K_PQ_SNAPPY, K_PQ_DECODE, K_GATHER, K_ACOV_LONG, K_DIAG_LONG, K_COV_FINAL, K_FFT,
+    K_CSV_LINES, K_CSV_SCAN, K_CSV_PARSE, K_CSV_PATCH, K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {
     "k_ingest", "k_moments", "k_moments_final", "k_tile_sort", "k_merge", "k_order_stats", "k_rank_z",
     "k_fold_merge", "k_diag", "k_finalize", "k_compare", "k_fill_synth", "k_splitters",
     "k_bucket_merge", "k_acov_more", "k_diag_combine2", "k_acov_seg", "k_two_sample", "k_cov_mfma", "k_ztable",
-    "k_pq_snappy", "k_pq_decode", "k_gather_rows", "k_acov_long", "k_diag_long_scan", "k_cov_final", "k_fft"};
+    "k_pq_snappy", "k_pq_decode", "k_gather_rows", "k_acov_long", "k_diag_long_scan", "k_cov_final", "k_fft",
+    "k_csv_lines", "k_csv_scan", "k_csv_parse", "k_csv_patch"};
 
 struct EvPair { hipEvent_t a, b; int kid; };
 
@@ -99,6 +102,18 @@ struct mcr_ctx {
     void* pq_tab = nullptr; size_t pq_tab_bytes = 0;
     void* fs_arena = nullptr; size_t fs_arena_bytes = 0;   // mcr_summarize_files: decoded draws + chain / draw ids
     void* pq_pin = nullptr; size_t pq_pin_bytes = 0;       // mcr_summarize_files: pinned host staging of the files' column chunks
+    // CSV ingest (mcr_csv_*): the text of a call lives in pq_pin / pq_stage like the draws files' images.  img_gen counts
+    // the times these two were rewritten: handles of mcr_csv_open_paths and the staged line index hold the value they saw.
+    uint64_t img_gen = 0;
+    struct CsvFile { size_t img, len, body; int ncols; std::string path; };
+    std::vector<CsvFile> csv_files; std::vector<uint32_t> csv_row0;      // staged files, first data row of each (+ total)
+    uint64_t csv_staged_gen = 0; bool csv_staged = false;
+    size_t csv_row0_off = 0;                                             // file_row0 within csv_tab
+    void* csv_tab = nullptr; size_t csv_tab_bytes = 0;                   // FileDesc, chunk -> file, chunk counts / first rows, file_row0
+    void* csv_rows = nullptr; size_t csv_rows_bytes = 0;                 // start offset of every data row
+    void* csv_aux = nullptr; size_t csv_aux_bytes = 0;                   // decode: slot tables, hard list, counters, patch list
+    void* csv_pow5 = nullptr;                                            // device copy of csv::kPow5
+    uint32_t csv_hard_cap = 4096;
     int io_threads = 8;                                    // MCR_IO_THREADS: host threads that read the file images and parse their footers
     size_t io_piece = (size_t)2 << 20;                     // MCR_IO_PIECE_KB: the finished prefix is uploaded in pieces of at least this size
     // z tables (k_ztable): a function of M alone, so they are computed once per pooled length and kept for the life of
@@ -1209,6 +1224,7 @@ void mcr_free(mcr_ctx* ctx)
     if (ctx->pq_tab) hipFree(ctx->pq_tab);
     if (ctx->fs_arena) hipFree(ctx->fs_arena);
     if (ctx->pq_pin) hipHostFree(ctx->pq_pin);
+    for (void* b : {ctx->csv_tab, ctx->csv_rows, ctx->csv_aux, ctx->csv_pow5}) if (b) hipFree(b);
     for (hipStream_t st : ctx->lane_stream) if (st) hipStreamDestroy(st);
     for (hipStream_t st : ctx->lane_aux) if (st) hipStreamDestroy(st);
     for (hipEvent_t ev : ctx->lane_fork) if (ev) hipEventDestroy(ev);
@@ -2004,6 +2020,8 @@ int mcr_comm_barrier(mcr_comm* c)
 // ---- Parquet ingest (replaces pq.read_table at store.py:79-95 / convert.py:61-65) -----------
 
 struct mcr_parquet { mcr::pq::File f; };
+// A chain CSV's header.  owner / gen / img: the image is this context's pq_pin + img and already uploaded (mcr_csv_open_paths).
+struct mcr_csv { mcr::csv::Image im; mcr_ctx* owner = nullptr; uint64_t gen = 0; size_t img = 0; };
 
 namespace {
 int ensure_buf(mcr_ctx* ctx, void** p, size_t* cap, size_t bytes)
@@ -2188,6 +2206,7 @@ int pq_buffers(mcr_ctx* ctx, PqPlan& P)
 {
     namespace pq = mcr::pq;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ++ctx->img_gen;
     int rc = ensure_buf(ctx, &ctx->pq_stage, &ctx->pq_stage_bytes, P.stage_total + pq::kInWin + 256);
     if (rc) return rc;
     rc = ensure_buf(ctx, &ctx->pq_scratch, &ctx->pq_scratch_bytes, P.scratch_total + 256);
@@ -2297,17 +2316,19 @@ namespace pq = mcr::pq;
 
 struct BatchFile {    // a file of mcr_summarize_files: descriptor, image, parsed metadata, column roles, place in the arena
     int fd = -1; size_t len = 0, img = 0; mcr_parquet* pq = nullptr;   // img: offset of the image in pq_pin and pq_stage
+    mcr_csv* csv = nullptr;                                            // FileBatch::csv: the parsed header instead of pq
     int rc = MCR_OK; std::string err;                                  // set by its reader
     std::vector<int> cols; int chain = -1, draw = -1;
     i64 M = 0, C = 0, N = 0; size_t off = 0, ioff = 0;                 // draws at arena + off, ids at arena + ids_base + ioff
     BatchFile() = default; BatchFile(const BatchFile&) = delete;
-    ~BatchFile() { if (pq) mcr_parquet_close(pq); if (fd >= 0) close(fd); }
+    ~BatchFile() { if (pq) mcr_parquet_close(pq); if (csv) mcr_csv_close(csv); if (fd >= 0) close(fd); }
 };
 
 // What the stages of mcr_summarize_files hand on.  It holds the host ends of their copies, so that these outlive any copy
 // still queued when a stage returns early.
 struct FileBatch {
     const char* const* paths;
+    bool csv = false;                                                // CmdStan chain CSVs (mcr_csv_open_paths), else draws files
     std::vector<BatchFile> f;
     size_t img_total = 0, ids_base = 0, lay_base = 0, lay_out = 0;   // arena: draws, ids, FileIds, chain layouts
     char* arena = nullptr;
@@ -2325,11 +2346,12 @@ int fs_open(mcr_ctx* ctx, FileBatch& B)
         struct stat st;
         if (m.fd < 0 || fstat(m.fd, &st) != 0) return fail(ctx, MCR_EINVAL, "cannot open %s", B.paths[i]);
         m.len = (size_t)st.st_size;
-        if (m.len == 0) return fail(ctx, MCR_EINVAL, "parquet: %s is empty", B.paths[i]);
+        if (m.len == 0 && !B.csv) return fail(ctx, MCR_EINVAL, "parquet: %s is empty", B.paths[i]);
         m.img = B.img_total;
         B.img_total = align_up(m.img + m.len, 256);
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ++ctx->img_gen;
     const int rc = ensure_buf(ctx, &ctx->pq_stage, &ctx->pq_stage_bytes, B.img_total + pq::kInWin + 256);
     if (rc) return rc;
     if (B.img_total > ctx->pq_pin_bytes) {                  // pinned staging, kept for the life of the context
@@ -2370,7 +2392,11 @@ int fs_read(mcr_ctx* ctx, FileBatch& B)
                     size_t got = 0;
                     for (ssize_t r; got < m.len && (r = pread(m.fd, pin + m.img + got, m.len - got, (off_t)got)) > 0;) got += (size_t)r;
                     if (got < m.len) bad(MCR_EINVAL, std::string("short read of ") + B.paths[i]);
-                    else {
+                    else if (B.csv) {
+                        m.csv = new mcr_csv();
+                        csv::open_image(m.csv->im, pin + m.img, m.len);
+                        m.csv->im.path = B.paths[i];
+                    } else {
                         m.pq = new mcr_parquet();
                         if (!pq::open(m.pq->f, pin + m.img, m.len)) bad(MCR_EINVAL, std::string(B.paths[i]) + ": parquet: " + m.pq->f.error);
                     }
@@ -2386,7 +2412,7 @@ int fs_read(mcr_ctx* ctx, FileBatch& B)
             while (done[(size_t)i].load(std::memory_order_acquire) == 0) std::this_thread::yield();
             const size_t from = B.f[(size_t)sent].img, upto = align_up(B.f[(size_t)i].img + B.f[(size_t)i].len, 256);
             if (he == hipSuccess && (upto - from >= ctx->io_piece || i + 1 == n)) {
-                he = hipMemcpyAsync((char*)ctx->pq_stage + from, pin + from, upto - from, hipMemcpyHostToDevice, ctx->stream);
+                if (upto > from) he = hipMemcpyAsync((char*)ctx->pq_stage + from, pin + from, upto - from, hipMemcpyHostToDevice, ctx->stream);
                 sent = i + 1;
             }
         }
@@ -2650,5 +2676,268 @@ int mcr_fileset_phases(const mcr_fileset* fs, double* ms, int cap)
     return MCR_FS_PHASES;
 }
 void mcr_fileset_free(mcr_fileset* fs) { delete fs; }
+
+// ---- CmdStan CSV ingest (replaces parse_cmdstan_csv, src/mcmc_ref/cmdstan_generate.py:13-29) --------
+
+int mcr_csv_open(mcr_ctx* ctx, const void* bytes, size_t len, mcr_csv** out)
+{
+    if ((!bytes && len) || !out) return fail(ctx, MCR_EINVAL, "NULL argument");     // ctx may be NULL: host only
+    try {
+        std::unique_ptr<mcr_csv> f(new mcr_csv());
+        csv::open_image(f->im, (const char*)bytes, len);
+        *out = f.release();
+    } catch (const std::exception& e) { return fail(ctx, MCR_ENOMEM, "csv: host allocation failed: %s", e.what()); }
+    return MCR_OK;
+}
+void mcr_csv_close(mcr_csv* f) { delete f; }
+int mcr_csv_num_columns(const mcr_csv* f) { return f ? (int)f->im.names.size() : -1; }
+const char* mcr_csv_column_name(const mcr_csv* f, int col)
+{
+    return (f && col >= 0 && col < (int)f->im.names.size()) ? f->im.names[(size_t)col].c_str() : nullptr;
+}
+int64_t mcr_csv_body_offset(const mcr_csv* f) { return f ? (int64_t)f->im.body : -1; }
+
+int mcr_parse_double(const char* text, size_t len, double* out)
+{
+    if ((!text && len) || !out) return MCR_EINVAL;
+    uint64_t bits = 0;
+    if (csv::parse_field(text, len, csv::kPow5, &bits) == 0) { memcpy(out, &bits, 8); return 0; }
+    return csv::finish_field(text, len, out) ? 1 : MCR_EINVAL;
+}
+
+}  // extern "C"
+
+namespace {
+constexpr size_t kCsvTextMax = ((size_t)1 << 32) - ((size_t)1 << 20);   // offsets are 32-bit
+
+std::string csv_file_name(const mcr_ctx* ctx, size_t f)
+{
+    const std::string& p = ctx->csv_files[f].path;
+    return p.empty() ? "file " + std::to_string(f) : p;
+}
+}  // namespace
+
+extern "C" {
+
+int mcr_csv_open_paths(mcr_ctx* ctx, const char* const* paths, int n_paths, mcr_csv** out)
+{
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    if (!out || n_paths < 0 || (n_paths > 0 && !paths)) return fail(ctx, MCR_EINVAL, "bad argument");
+    if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "mcr_csv_open_paths with summaries in flight");
+    try {
+        FileBatch B(paths, n_paths);
+        B.csv = true;
+        ctx->csv_staged = false;
+        int rc = fs_open(ctx, B);
+        if (rc) return rc;
+        if (B.img_total > kCsvTextMax) return fail(ctx, MCR_EINVAL, "csv: the chain files of one call hold %zu bytes; the limit is 4 GiB", B.img_total);
+        StreamSync uploads{ctx->stream};                      // the handles promise that the text is on the device
+        rc = fs_read(ctx, B);
+        if (rc) return rc;
+        for (int i = 0; i < n_paths; ++i) {
+            BatchFile& m = B.f[(size_t)i];
+            m.csv->im.bytes = (const char*)ctx->pq_pin + m.img;
+            m.csv->owner = ctx; m.csv->gen = ctx->img_gen; m.csv->img = m.img;
+            out[i] = m.csv;
+            m.csv = nullptr;
+        }
+    } catch (const std::exception& e) { return fail(ctx, MCR_ENOMEM, "csv: host allocation failed: %s", e.what()); }
+    return MCR_OK;
+}
+
+int mcr_csv_stage(mcr_ctx* ctx, const mcr_csv* const* files, int n_files, int64_t* rows)
+{
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    if (n_files < 0 || n_files > kMaxGridY || (n_files > 0 && (!files || !rows))) return fail(ctx, MCR_EINVAL, "bad file list");
+    if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "mcr_csv_stage with summaries in flight");
+    ctx->csv_staged = false;
+    try {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        hipStream_t st = ctx->stream;
+        int held = 0;
+        for (int i = 0; i < n_files; ++i) {
+            if (!files[i]) return fail(ctx, MCR_EINVAL, "file %d is NULL", i);
+            if (files[i]->owner) {
+                if (files[i]->owner != ctx || files[i]->gen != ctx->img_gen)
+                    return fail(ctx, MCR_EINVAL, "csv: file %d was read by an earlier call whose images are gone; open it again", i);
+                ++held;
+            }
+        }
+        if (held && held != n_files) return fail(ctx, MCR_EINVAL, "csv: files read by the library and caller images cannot share a call");
+        ctx->csv_files.assign((size_t)n_files, mcr_ctx::CsvFile());
+        if (!held) {                                           // caller images: into the pinned buffer, one upload
+            size_t total = 0;
+            for (int i = 0; i < n_files; ++i) { ctx->csv_files[(size_t)i].img = total; total = align_up(total + files[i]->im.len, 256); }
+            if (total > kCsvTextMax) return fail(ctx, MCR_EINVAL, "csv: the chain files of one call hold %zu bytes; the limit is 4 GiB", total);
+            ++ctx->img_gen;
+            const int rc = ensure_buf(ctx, &ctx->pq_stage, &ctx->pq_stage_bytes, total + pq::kInWin + 256);
+            if (rc) return rc;
+            if (total > ctx->pq_pin_bytes) {
+                HIP_TRY(ctx, hipStreamSynchronize(st));
+                if (ctx->pq_pin) { hipHostFree(ctx->pq_pin); ctx->pq_pin = nullptr; ctx->pq_pin_bytes = 0; }
+                HIP_TRY(ctx, hipHostMalloc(&ctx->pq_pin, total + (total >> 2), hipHostMallocDefault));
+                ctx->pq_pin_bytes = total + (total >> 2);
+            }
+            for (int i = 0; i < n_files; ++i)
+                if (files[i]->im.len) memcpy((char*)ctx->pq_pin + ctx->csv_files[(size_t)i].img, files[i]->im.bytes, files[i]->im.len);
+            if (total) HIP_TRY(ctx, hipMemcpyAsync(ctx->pq_stage, ctx->pq_pin, total, hipMemcpyHostToDevice, st));
+        }
+        std::vector<csv::FileDesc> desc((size_t)n_files);
+        std::vector<uint32_t> chunk_file;
+        uint32_t slot0 = 0;
+        for (int i = 0; i < n_files; ++i) {
+            mcr_ctx::CsvFile& c = ctx->csv_files[(size_t)i];
+            const csv::Image& im = files[i]->im;
+            if (held) c.img = files[i]->img;
+            c.len = im.len; c.body = im.body; c.ncols = (int)im.names.size(); c.path = im.path;
+            desc[(size_t)i] = csv::FileDesc{(uint32_t)c.img, (uint32_t)(c.img + c.body), (uint32_t)(c.img + c.len), (uint32_t)c.ncols,
+                                            (uint32_t)chunk_file.size(), slot0};
+            slot0 += (uint32_t)c.ncols;
+            chunk_file.insert(chunk_file.end(), (c.len + csv::kChunk - 1) / csv::kChunk, (uint32_t)i);
+        }
+        const uint32_t n_chunks = (uint32_t)chunk_file.size();
+        ctx->csv_row0.assign((size_t)n_files + 1, 0u);
+        if (n_chunks) {
+            const size_t o_file = align_up(desc.size() * sizeof(csv::FileDesc), 256), o_cnt = o_file + align_up((size_t)n_chunks * 4, 256),
+                         o_first = o_cnt + align_up((size_t)n_chunks * 4, 256), o_row0 = o_first + align_up((size_t)n_chunks * 4 + 4, 256);
+            int rc = ensure_buf(ctx, &ctx->csv_tab, &ctx->csv_tab_bytes, o_row0 + align_up((size_t)n_files * 4 + 4, 256));
+            if (rc) return rc;
+            ctx->csv_row0_off = o_row0;
+            char* tb = (char*)ctx->csv_tab;
+            const csv::FileDesc* d_desc = (const csv::FileDesc*)tb;
+            uint32_t *d_cfile = (uint32_t*)(tb + o_file), *d_cnt = (uint32_t*)(tb + o_cnt), *d_first = (uint32_t*)(tb + o_first),
+                     *d_row0 = (uint32_t*)(tb + o_row0);
+            HIP_TRY(ctx, hipMemcpyAsync(tb, desc.data(), desc.size() * sizeof(csv::FileDesc), hipMemcpyHostToDevice, st));
+            HIP_TRY(ctx, hipMemcpyAsync(d_cfile, chunk_file.data(), (size_t)n_chunks * 4, hipMemcpyHostToDevice, st));
+            const char* text = (const char*)ctx->pq_stage;
+            LAUNCH(ctx, K_CSV_LINES, csv::k_csv_lines<false>, dim3(n_chunks), dim3(csv::kLinesNT), 0, text, d_desc, (const uint32_t*)d_cfile,
+                   d_cnt, (const uint32_t*)d_first, (uint32_t*)nullptr);
+            LAUNCH(ctx, K_CSV_SCAN, csv::k_csv_scan, dim3(1), dim3(1024), 0, (const uint32_t*)d_cnt, n_chunks, d_first, d_desc,
+                   (uint32_t)n_files, d_row0);
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->csv_row0.data(), d_row0, ((size_t)n_files + 1) * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(ctx, hipStreamSynchronize(st));
+            const uint32_t total_rows = ctx->csv_row0[(size_t)n_files];
+            if (total_rows) {
+                rc = ensure_buf(ctx, &ctx->csv_rows, &ctx->csv_rows_bytes, (size_t)total_rows * 4 + 256);
+                if (rc) return rc;
+                LAUNCH(ctx, K_CSV_LINES, csv::k_csv_lines<true>, dim3(n_chunks), dim3(csv::kLinesNT), 0, text, d_desc, (const uint32_t*)d_cfile,
+                       d_cnt, (const uint32_t*)d_first, (uint32_t*)ctx->csv_rows);
+            }
+        }
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        prof_resolve(ctx);
+        for (int i = 0; i < n_files; ++i) rows[i] = (int64_t)(ctx->csv_row0[(size_t)i + 1] - ctx->csv_row0[(size_t)i]);
+        ctx->csv_staged = true;
+        ctx->csv_staged_gen = ctx->img_gen;
+    } catch (const std::exception& e) { return fail(ctx, MCR_ENOMEM, "csv: host allocation failed: %s", e.what()); }
+    return MCR_OK;
+}
+
+int mcr_csv_decode(mcr_ctx* ctx, const int* columns, int n_cols, int64_t max_rows, double* out_dev, int64_t stride_file,
+                   int64_t stride_row, int64_t stride_col, int64_t* hard)
+{
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    if (hard) *hard = 0;
+    if (n_cols < 0 || max_rows < 0 || (n_cols > 0 && !columns) || stride_file < 0 || stride_row < 0 || stride_col < 0)
+        return fail(ctx, MCR_EINVAL, "bad argument");
+    if (!ctx->csv_staged || ctx->csv_staged_gen != ctx->img_gen) return fail(ctx, MCR_EINVAL, "csv: no staged files (call mcr_csv_stage first)");
+    if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "mcr_csv_decode with summaries in flight");
+    try {
+        const size_t nf = ctx->csv_files.size();
+        std::vector<int> slots;
+        int64_t rows_eff = 0;
+        for (size_t f = 0; f < nf; ++f) {
+            const int nc = ctx->csv_files[f].ncols;
+            const size_t s0 = slots.size();
+            slots.insert(slots.end(), (size_t)nc, -1);
+            for (int k = 0; k < n_cols; ++k) {
+                const int c = columns[f * (size_t)n_cols + (size_t)k];
+                if (c < 0 || c >= nc) return fail(ctx, MCR_EINVAL, "csv: %s has no column %d", csv_file_name(ctx, f).c_str(), c);
+                if (slots[s0 + (size_t)c] >= 0) return fail(ctx, MCR_EINVAL, "csv: column %d of %s is requested twice", c, csv_file_name(ctx, f).c_str());
+                slots[s0 + (size_t)c] = k;
+            }
+            rows_eff = std::max(rows_eff, std::min<int64_t>(max_rows, (int64_t)(ctx->csv_row0[f + 1] - ctx->csv_row0[f])));
+        }
+        if (rows_eff == 0 || n_cols == 0) return MCR_OK;
+        if (!out_dev) return fail(ctx, MCR_EINVAL, "out_dev is NULL");
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        hipStream_t st = ctx->stream;
+        if (!ctx->csv_pow5) {
+            HIP_TRY(ctx, hipMalloc(&ctx->csv_pow5, sizeof(csv::kPow5)));
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->csv_pow5, csv::kPow5, sizeof(csv::kPow5), hipMemcpyHostToDevice, st));
+        }
+        const char* tb = (const char*)ctx->csv_tab;          // as mcr_csv_stage carved it: descriptors first
+        const size_t o_row0 = ctx->csv_row0_off;
+        uint32_t h_count = 0;
+        unsigned long long h_err = ~0ull;
+        std::vector<csv::HardField> list;
+        for (int pass = 0; pass < 2; ++pass) {                 // a hard list that overflows: once more with one that fits
+            const size_t o_hard = align_up(slots.size() * 4, 256), o_ctr = o_hard + align_up((size_t)ctx->csv_hard_cap * sizeof(csv::HardField), 256);
+            const int rc = ensure_buf(ctx, &ctx->csv_aux, &ctx->csv_aux_bytes, o_ctr + 256);
+            if (rc) return rc;
+            char* ax = (char*)ctx->csv_aux;
+            HIP_TRY(ctx, hipMemcpyAsync(ax, slots.data(), slots.size() * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(ctx, hipMemsetAsync(ax + o_ctr, 0xFF, 8, st));
+            HIP_TRY(ctx, hipMemsetAsync(ax + o_ctr + 8, 0, 8, st));
+            csv::ParseArgs a{(const char*)ctx->pq_stage, (const csv::FileDesc*)tb, (const uint32_t*)ctx->csv_rows, (const uint32_t*)(tb + o_row0),
+                             (const int*)ax, (const uint64_t*)ctx->csv_pow5, (long long)max_rows, out_dev, (long long)stride_file,
+                             (long long)stride_row, (long long)stride_col, (csv::HardField*)(ax + o_hard), ctx->csv_hard_cap,
+                             (uint32_t*)(ax + o_ctr + 8), (unsigned long long*)(ax + o_ctr)};
+            LAUNCH(ctx, K_CSV_PARSE, csv::k_csv_parse, dim3((unsigned)((rows_eff + csv::kParseWaves - 1) / csv::kParseWaves), (unsigned)nf),
+                   dim3(csv::kParseWaves * 64), 0, a);
+            HIP_TRY(ctx, hipMemcpyAsync(&h_err, ax + o_ctr, 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(ctx, hipMemcpyAsync(&h_count, ax + o_ctr + 8, 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(ctx, hipStreamSynchronize(st));
+            if (h_count <= ctx->csv_hard_cap) {
+                list.resize(h_count);
+                if (h_count) HIP_TRY(ctx, hipMemcpy(list.data(), ax + o_hard, (size_t)h_count * sizeof(csv::HardField), hipMemcpyDeviceToHost));
+                break;
+            }
+            ctx->csv_hard_cap = h_count + (h_count >> 3);
+        }
+        prof_resolve(ctx);
+        const char* pin = (const char*)ctx->pq_pin;
+        if (h_err != ~0ull) {
+            const size_t f = (size_t)(h_err >> 44);
+            const unsigned long long row = (h_err >> 4) & ((1ull << 40) - 1);
+            const mcr_ctx::CsvFile& c = ctx->csv_files[f];
+            if ((h_err & 15) == csv::kErrQuote)
+                return fail(ctx, MCR_EINVAL, "%s: data row %llu: quoted fields are not supported", csv_file_name(ctx, f).c_str(), row);
+            uint32_t start = 0;
+            HIP_TRY(ctx, hipMemcpy(&start, (const uint32_t*)ctx->csv_rows + ctx->csv_row0[f] + row, 4, hipMemcpyDeviceToHost));
+            size_t fields = 1;
+            for (size_t i = start; i < c.img + c.len && pin[i] != '\n'; ++i) fields += pin[i] == ',';
+            return fail(ctx, MCR_EINVAL, "%s: data row %llu has %zu fields, header has %d", csv_file_name(ctx, f).c_str(), row, fields, c.ncols);
+        }
+        if (!list.empty()) {                                  // the host finishes them: strtod on the pinned image, one upload, one scatter
+            std::vector<long long> idx(list.size());
+            std::vector<double> val(list.size());
+            for (size_t i = 0; i < list.size(); ++i) {
+                const csv::HardField& h = list[i];
+                if (!csv::finish_field(pin + h.off, h.len, &val[i])) {
+                    int col = 0;
+                    size_t base = 0;
+                    for (size_t s = 0; s < h.file; ++s) base += (size_t)ctx->csv_files[s].ncols;
+                    while (col < ctx->csv_files[h.file].ncols && slots[base + (size_t)col] != (int)h.slot) ++col;
+                    return fail(ctx, MCR_EINVAL, "%s: data row %u, column %d: could not convert string to float: '%.*s'",
+                                csv_file_name(ctx, h.file).c_str(), h.row, col, (int)std::min<uint32_t>(h.len, 200u), pin + h.off);
+                }
+                idx[i] = (long long)h.file * stride_file + (long long)h.row * stride_row + (long long)h.slot * stride_col;
+            }
+            const size_t nb = list.size() * 8;
+            const int rc = ensure_buf(ctx, &ctx->csv_aux, &ctx->csv_aux_bytes, 2 * align_up(nb, 256));
+            if (rc) return rc;
+            char* ax = (char*)ctx->csv_aux;
+            HIP_TRY(ctx, hipMemcpyAsync(ax, idx.data(), nb, hipMemcpyHostToDevice, st));
+            HIP_TRY(ctx, hipMemcpyAsync(ax + align_up(nb, 256), val.data(), nb, hipMemcpyHostToDevice, st));
+            LAUNCH(ctx, K_CSV_PATCH, csv::k_csv_patch, dim3((unsigned)((list.size() + 255) / 256)), dim3(256), 0, out_dev, (const long long*)ax,
+                   (const double*)(ax + align_up(nb, 256)), (uint32_t)list.size());
+            HIP_TRY(ctx, hipStreamSynchronize(st));
+            prof_resolve(ctx);
+        }
+        if (hard) *hard = (int64_t)list.size();
+    } catch (const std::exception& e) { return fail(ctx, MCR_ENOMEM, "csv: host allocation failed: %s", e.what()); }
+    return MCR_OK;
+}
 
 }  // extern "C"

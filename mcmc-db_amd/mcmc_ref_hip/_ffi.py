@@ -5,7 +5,8 @@ If the shared library or a HIP device is missing every entry point raises
 
 The summarize plumbing the Python API shares lives here too, once: the fileset reader
 (`Context.summarize_files`), the rolling window over enqueue / wait_one (`pipeline`, `split_result`),
-the reference-shaped per-parameter dicts (`entries`), the ragged-chain route (`ragged_diagnostics`) and
+the reference-shaped per-parameter dicts (`entries`), the ragged-chain route (`ragged_diagnostics`), the CmdStan CSV
+decoder (`Context.csv_decode`) and
 the McrError -> ValueError translation of the reference-compatible functions (`value_errors`).
 """
 from __future__ import annotations
@@ -16,6 +17,7 @@ import ctypes as C
 import math
 import os
 import threading
+import time
 from pathlib import Path
 
 import numpy as np
@@ -138,6 +140,15 @@ SYMBOLS = {
     "mcr_fileset_export": (C.c_int64, [C.c_void_p, _dp, C.c_int64]),
     "mcr_fileset_names": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_int64]),
     "mcr_fileset_free": (None, [C.c_void_p]),
+    "mcr_csv_open": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    "mcr_csv_open_paths": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_void_p)]),
+    "mcr_csv_close": (None, [C.c_void_p]),
+    "mcr_csv_num_columns": (C.c_int, [C.c_void_p]),
+    "mcr_csv_column_name": (C.c_char_p, [C.c_void_p, C.c_int]),
+    "mcr_csv_body_offset": (C.c_int64, [C.c_void_p]),
+    "mcr_csv_stage": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, _ip]),
+    "mcr_csv_decode": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, _I64, C.c_void_p, _I64, _I64, _I64, _ip]),
+    "mcr_parse_double": (C.c_int, [C.c_char_p, C.c_size_t, _dp]),
 }
 
 _lib = None
@@ -445,6 +456,52 @@ class Context:
             return out, r
         finally:
             L.mcr_fileset_free(fs)
+
+    def csv_decode(self, paths, select, phases: dict | None = None) -> tuple[list[str], "DeviceTensor", int]:
+        """CmdStan chain files -> (parameter names, [P][C][N] DeviceTensor, fields finished on the host): the library
+        reads the files (mcr_csv_open_paths), indexes their data rows (mcr_csv_stage) and parses the selected columns of
+        the first N = min over files rows on the device (mcr_csv_decode).  `select(file index, header names)` returns
+        (names, header column of each name) of one file; the first file's names give the tensor's parameter order and
+        every other file must hold the same set.  `phases` is filled with the host clock of the three calls (ms)."""
+        L, n = self.lib, len(paths)
+        arr = (C.c_char_p * max(n, 1))(*[os.fsencode(p) for p in paths])
+        hs = (C.c_void_p * max(n, 1))()
+        t0 = time.perf_counter()
+        self._check(L.mcr_csv_open_paths(self.handle, arr, n, hs))
+        try:
+            picked = [select(f, [(L.mcr_csv_column_name(hs[f], c) or b"").decode() for c in range(L.mcr_csv_num_columns(hs[f]))])
+                      for f in range(n)]
+            names = picked[0][0]
+            if not names:
+                raise ValueError("chain draws contain no parameters")
+            cols = np.empty((n, len(names)), dtype=np.intc)
+            for f, (nm, cl) in enumerate(picked):
+                if set(nm) != set(names):
+                    raise ValueError(f"chain {f} parameter keys mismatch")
+                at = dict(zip(nm, cl))
+                cols[f] = [at[k] for k in names]
+            t1 = time.perf_counter()
+            rows = np.zeros(n, dtype=np.int64)
+            self._check(L.mcr_csv_stage(self.handle, hs, n, _as_ip(rows)))
+            t2 = time.perf_counter()
+            N, P = int(rows.min()), len(names)
+            t = self.alloc_tensor(n, N, P)
+            hard = C.c_int64(0)
+            try:
+                self._check(L.mcr_csv_decode(self.handle, cols.ctypes.data_as(C.POINTER(C.c_int)), P, N, t.buf.ptr,
+                                             N, 1, n * N, C.byref(hard)))
+            except Exception:
+                t.free()
+                raise
+            if phases is not None:
+                t3 = time.perf_counter()
+                phases.update(read_upload_ms=(t1 - t0) * 1e3, index_ms=(t2 - t1) * 1e3, parse_finish_ms=(t3 - t2) * 1e3,
+                              text_bytes=sum(os.path.getsize(p) for p in paths), hard=int(hard.value))
+            return names, t, int(hard.value)
+        finally:
+            for h in hs[:n]:
+                if h:
+                    L.mcr_csv_close(h)
 
     def wait(self):
         try:

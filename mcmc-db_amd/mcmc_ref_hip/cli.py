@@ -4,7 +4,8 @@ Mirrors src/mcmc_ref/cli.py for `list`, `stats`, `diagnostics`, `info`, `compare
 `provenance-generate` and `provenance-publish` (same options, echo strings and exit codes: compare exits 2 when the
 gate fails, provenance-generate exits 1 when any recipe failed); `--backend` accepts "hip" (default) and the
 reference's "arrow" / "numpy".  `provenance-scaffold` (Stan programs + data literals), pairs and draws-export
-commands are outside the statistics path and not included.
+commands are outside the statistics path and not included.  `cmdstan-summary CHAIN.csv...` is this package's own:
+the chain files of a CmdStan run, parsed on the GPU, printed like `stats --include-diagnostics`.
 """
 from __future__ import annotations
 
@@ -40,6 +41,18 @@ def _print_table(stats: dict) -> None:
         click.echo(" ".join(v.ljust(w) for v, w in zip(row, widths, strict=False)))
 
 
+def _echo_stats(stats: dict, format_: str) -> None:
+    if format_ == "json":
+        click.echo(json.dumps(stats, indent=2, sort_keys=True))
+    elif format_ == "csv":
+        headers = ["param"] + _headers(stats)
+        click.echo(",".join(headers))
+        for param, metrics in stats.items():
+            click.echo(",".join([param] + [str(metrics.get(h, "")) for h in headers[1:]]))
+    else:
+        _print_table(stats)
+
+
 @main.command("list")
 @click.option("--format", "format_", type=click.Choice(["table", "json"], case_sensitive=False), default="table")
 def list_cmd(format_: str) -> None:
@@ -64,15 +77,21 @@ def stats_cmd(model, params, format_, backend, quantile_mode, include_diagnostic
     if include_diagnostics:
         for param, metrics in reference.diagnostics_for_model(model, params=param_list).items():
             stats.setdefault(param, {}).update(metrics)
-    if format_ == "json":
-        click.echo(json.dumps(stats, indent=2, sort_keys=True))
-    elif format_ == "csv":
-        headers = ["param"] + _headers(stats)
-        click.echo(",".join(headers))
-        for param, metrics in stats.items():
-            click.echo(",".join([param] + [str(metrics.get(h, "")) for h in headers[1:]]))
-    else:
-        _print_table(stats)
+    _echo_stats(stats, format_)
+
+
+@main.command("cmdstan-summary")
+@click.argument("chains", nargs=-1, required=True, type=click.Path(path_type=Path, exists=True, dir_okay=False))
+@click.option("--format", "format_", type=click.Choice(["table", "csv", "json"], case_sensitive=False), default="table")
+@click.option("--min-chains", default=4, type=int)
+def cmdstan_summary_cmd(chains, format_: str, min_chains: int) -> None:
+    """Statistics and diagnostics of a CmdStan run's chain CSVs, parsed on the GPU (no counterpart in the reference)."""
+    from . import cmdstan_generate
+    try:
+        stats = cmdstan_generate.summarize_chains(list(chains), min_chains=min_chains)
+    except ValueError as exc:
+        raise click.ClickException(str(exc)) from exc
+    _echo_stats(stats, format_)
 
 
 @main.command("diagnostics")

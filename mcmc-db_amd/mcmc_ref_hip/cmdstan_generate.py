@@ -4,7 +4,8 @@ Behaviour of the reference's src/mcmc_ref/cmdstan_generate.py:13-88: `#` comment
 columns (names ending in `__`) are skipped, `theta.1.2` becomes `theta[1,2]`, a payload is one dict per chain with
 equal parameter sets and equal draw counts.  The CSV body is parsed column-wise with numpy (one pass over the text)
 instead of a DictReader row loop; `chains_tensor` additionally hands the chains over as the `[P][C][N]` array the
-kernels consume, so CmdStan output can go to `Context.summarize` without the JSON round trip.
+kernels consume, so CmdStan output can go to `Context.summarize` without the JSON round trip.  `chains_tensor_dev` /
+`summarize_chains` are the same route with the text parsed on the GPU (mcr_csv_*): no host number parsing at all.
 """
 from __future__ import annotations
 
@@ -100,6 +101,54 @@ def chains_tensor(paths: list[Path]) -> tuple[list[str], np.ndarray]:
         for i, name in enumerate(names):
             out[i, c] = x[n.index(name), :n_draws]
     return names, out
+
+
+def _select_params(path):
+    """Header names of one chain file -> (normalised parameter names, their header columns): `__` columns skipped."""
+    def select(_f: int, header: list[str]) -> tuple[list[str], list[int]]:
+        names: list[str] = []
+        cols: list[int] = []
+        for i, h in enumerate(header):
+            if not h or h.endswith("__"):
+                continue
+            n = _normalize_cmdstan_param_name(h)
+            if n in names:
+                raise ValueError(f"{path(_f)}: header columns {header[cols[names.index(n)]]!r} and {h!r} both normalise to "
+                                 f"{n!r}; the device route keeps one column per parameter (read_cmdstan_csv concatenates them)")
+            names.append(n)
+            cols.append(i)
+        return names, cols
+    return select
+
+
+def chains_tensor_dev(paths: list[Path], context=None, phases: dict | None = None):
+    """`chains_tensor` without the host parse: (parameter names, [P][C][N] DeviceTensor) of the chain files of one model,
+    the same names, column order, n_draws = min over chains and error cases.  The files' text is read and uploaded by
+    the library and every field is converted on the GPU (mcr_csv_*); `phases` receives the host clock of the steps and
+    `hard`, the number of fields the host had to finish.  Free the tensor when done."""
+    from . import _ffi
+    paths = [Path(p) for p in paths]
+    if not paths:
+        raise ValueError("no chain draws provided")
+    ctx = context if context is not None else _ffi.default_context()
+    with _ffi.value_errors():
+        names, t, _hard = ctx.csv_decode([str(p) for p in paths], _select_params(lambda f: paths[f]), phases)
+    return names, t
+
+
+def summarize_chains(paths: list[Path], min_chains: int = 4, quantiles=(0.05, 0.5, 0.95), diagnostics: bool = True,
+                     context=None) -> dict[str, dict[str, float]]:
+    """{param: {"mean", "std", "qNN"..., "rhat", "ess_bulk", "ess_tail"}} of a CmdStan run's chain files, the shape
+    `reference.summary_for_model` returns: bytes to statistics on the GPU."""
+    from . import _ffi
+    ctx = context if context is not None else _ffi.default_context()
+    names, t = chains_tensor_dev(paths, context=ctx)
+    try:
+        with _ffi.value_errors():
+            r = ctx.summarize(t, min_chains=min_chains, quantiles=quantiles, diagnostics=diagnostics)
+    finally:
+        t.free()
+    return dict(zip(names, _ffi.entries(r, list(quantiles), diagnostics)))
 
 
 def write_posteriordb_json_zip(payload: list[dict[str, list[float]]], out_path: Path, *, model_name: str) -> Path:
