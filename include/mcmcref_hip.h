@@ -46,6 +46,8 @@ extern "C" {
 #define MCR_ENODEVICE (-7)      /* no usable HIP device / bad device index */
 #define MCR_ECOMM (-8)          /* RCCL error (multi-GPU gather) */
 #define MCR_ELAYOUT (-9)        /* mcr_summarize_files: rows not in (chain, draw) order or chains of unequal length */
+#define MCR_EFALLBACK (-10)     /* mcr_json_*: valid input for the caller's host reader, but outside the subset the device
+                                   reader certifies; the message names the first reason and its byte offset */
 
 #define MCR_F64 0
 #define MCR_F32 1
@@ -421,6 +423,47 @@ int mcr_csv_decode(mcr_ctx* ctx, const int* columns, int n_cols, int64_t max_row
 /* The device's field parser on the host (float(), cmdstan_generate.py:28).  Returns 0 = decided, 1 = hard (*out is
  * then the host finisher's strtod value), MCR_EINVAL = float() would raise ValueError. */
 int mcr_parse_double(const char* text, size_t len, double* out);
+
+/* ------------------------------------------------------------------------------------------------
+ * Chain-list JSON -> device tensor.
+ * Replaces json.loads + np.asarray of the JSON-zip reader (src/mcmc_ref/convert.py:78-102) for the
+ * inflated text of a `<name>.json.zip` member: [ {"param": [draws...], ...}, ... ], one object per chain.
+ * The text is uploaded once.  A structural index finds every [ ] { } : , outside a string; the host
+ * walks the few tokens that are not commas against the text (chains, keys, arrays and their lengths);
+ * one kernel checks every array element against the strict JSON number grammar
+ * -?(0|[1-9][0-9]*)(\.[0-9]+)?([eE][+-]?[0-9]+)? and converts the selected ones like mcr_parse_double.
+ * Hard elements (rounding decided by digits past the 19th; exactly NaN, Infinity, -Infinity) are
+ * finished on the host and patched in.  An integer literal has no negative zero (-0 is +0.0).
+ * The certified subset: no backslash anywhere; a non-empty top-level array of objects; every member a
+ * key without control characters and a flat array of numbers; no key twice in one object; no integer
+ * literal above 2^53 among the stored elements.  Everything else -- valid JSON or not -- ends the call
+ * with MCR_EFALLBACK and the caller's host reader decides (it is the source of every exception).
+ * Limit: a document holds less than 4 GiB (offsets are 32-bit), checked before a byte is read.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct mcr_json mcr_json;
+#define MCR_JSON_CHUNK 16384      /* bytes of text one workgroup of the structural index scans */
+#define MCR_JSON_PARSE_BLOCK 256  /* array elements one workgroup of the element parser converts */
+
+/* Uploads the document, runs the structural index and the skeleton walk.  The caller keeps `bytes` alive and unchanged
+ * until mcr_json_close, and closes the handle before the context is freed. */
+int mcr_json_open(mcr_ctx* ctx, const void* bytes, size_t len, mcr_json** out);
+void mcr_json_close(mcr_json* f);
+int mcr_json_num_chains(const mcr_json* f);
+int mcr_json_num_keys(const mcr_json* f, int chain);
+const char* mcr_json_key(const mcr_json* f, int chain, int k); /* raw UTF-8 between the quotes, document order */
+int64_t mcr_json_length(const mcr_json* f, int chain, int k);  /* elements of the key's array */
+
+/* arrays[c * n_params + p] = the key, within chain c, of parameter slot p.  The first n_draws elements of each selected
+ * array (none may be shorter) go to out_dev[c * stride_c + v * stride_n + p * stride_p]; every other element of the
+ * document is checked against the grammar only.  all_int[c * n_params + p] = 1 when all stored elements of that array
+ * were integer literals (no fraction, no exponent).  *hard = elements finished on the host. */
+int mcr_json_decode(mcr_ctx* ctx, const mcr_json* f, const int* arrays, int n_params, int64_t n_draws, double* out_dev,
+                    int64_t stride_c, int64_t stride_n, int64_t stride_p, uint8_t* all_int, int64_t* hard);
+
+/* The device's element routine on the host (float(json.loads(text))).  Returns 0 = decided, 1 = hard (*value is then the
+ * host finisher's), MCR_EINVAL = not a number json.loads accepts, MCR_EFALLBACK = an integer literal above 2^53.
+ * *is_int = the literal has neither fraction nor exponent. */
+int mcr_parse_json_number(const char* text, size_t len, double* value, int* is_int);
 
 #ifdef __cplusplus
 }

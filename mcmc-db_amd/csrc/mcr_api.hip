@@ -31,6 +31,7 @@
 #include "mcr_ext.hpp"
 #include "mcr_parquet.hpp"
 #include "mcr_csv.hpp"
+#include "mcr_json.hpp"
 #include "mcr_comm.hpp"
 
 using namespace mcr;
@@ -52,14 +53,16 @@ enum KernelId {
     K_INGEST = 0, K_MOMENTS, K_MOMENTS_FINAL, K_TILE_SORT, K_MERGE, K_ORDER_STATS, K_RANK_Z, K_FOLD_MERGE,
     K_DIAG, K_FINALIZE, K_COMPARE, K_FILL, K_SPLITTERS, K_BUCKET_MERGE, K_ACOV_MORE,
     K_DIAG2, K_ACOV_SEG, K_TWO_SAMPLE, K_COV, K_ZTABLE, K_PQ_SNAPPY, K_PQ_DECODE, K_GATHER, K_ACOV_LONG, K_DIAG_LONG, K_COV_FINAL, K_FFT,
-    K_CSV_LINES, K_CSV_SCAN, K_CSV_PARSE, K_CSV_PATCH, K_COUNT
+    K_CSV_LINES, K_CSV_SCAN, K_CSV_PARSE, K_CSV_PATCH,
+    K_JSON_INDEX, K_JSON_SCAN, K_JSON_PARSE, K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {
     "k_ingest", "k_moments", "k_moments_final", "k_tile_sort", "k_merge", "k_order_stats", "k_rank_z",
     "k_fold_merge", "k_diag", "k_finalize", "k_compare", "k_fill_synth", "k_splitters",
     "k_bucket_merge", "k_acov_more", "k_diag_combine2", "k_acov_seg", "k_two_sample", "k_cov_mfma", "k_ztable",
     "k_pq_snappy", "k_pq_decode", "k_gather_rows", "k_acov_long", "k_diag_long_scan", "k_cov_final", "k_fft",
-    "k_csv_lines", "k_csv_scan", "k_csv_parse", "k_csv_patch"};
+    "k_csv_lines", "k_csv_scan", "k_csv_parse", "k_csv_patch",
+    "k_json_index", "k_json_scan", "k_json_parse"};
 
 struct EvPair { hipEvent_t a, b; int kid; };
 
@@ -2937,6 +2940,239 @@ int mcr_csv_decode(mcr_ctx* ctx, const int* columns, int n_cols, int64_t max_row
         }
         if (hard) *hard = (int64_t)list.size();
     } catch (const std::exception& e) { return fail(ctx, MCR_ENOMEM, "csv: host allocation failed: %s", e.what()); }
+    return MCR_OK;
+}
+
+}  // extern "C"
+
+// ---- chain-list JSON ingest (replaces json.loads + np.asarray of the JSON-zip reader, src/mcmc_ref/convert.py:78-102)
+
+// An indexed document.  The caller keeps `bytes` alive and unchanged; the device holds a copy and every token's offset.
+struct mcr_json {
+    mcr_ctx* ctx = nullptr; const char* bytes = nullptr; size_t len = 0;
+    void* d_text = nullptr;                  // the text, padded to whole chunks
+    void* d_tok = nullptr; uint32_t n_tok = 0;
+    std::vector<json::Chain> chains;
+    ~mcr_json()
+    {
+        if (!d_text && !d_tok) return;
+        hipSetDevice(ctx->device);
+        if (d_text) hipFree(d_text);
+        if (d_tok) hipFree(d_tok);
+    }
+};
+
+namespace {
+int json_pow5(mcr_ctx* ctx)
+{
+    if (ctx->csv_pow5) return MCR_OK;
+    HIP_TRY(ctx, hipMalloc(&ctx->csv_pow5, sizeof(csv::kPow5)));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->csv_pow5, csv::kPow5, sizeof(csv::kPow5), hipMemcpyHostToDevice, ctx->stream));
+    return MCR_OK;
+}
+
+// The text of the element that starts at `off`, for a message: up to the next ',' or ']', at most 48 bytes.
+std::string json_excerpt(const mcr_json* f, size_t off)
+{
+    size_t e = off;
+    while (e < f->len && e - off < 48 && f->bytes[e] != ',' && f->bytes[e] != ']') ++e;
+    std::string s(f->bytes + off, e - off);
+    for (char& c : s) if ((unsigned char)c < 0x20) c = ' ';
+    return s;
+}
+}  // namespace
+
+extern "C" {
+
+int mcr_json_open(mcr_ctx* ctx, const void* bytes, size_t len, mcr_json** out)
+{
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    if ((!bytes && len) || !out) return fail(ctx, MCR_EINVAL, "NULL argument");
+    if (len >= ((size_t)1 << 32)) return fail(ctx, MCR_EINVAL, "json: the document holds %zu bytes; the limit is 4 GiB", len);
+    if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "mcr_json_open with summaries in flight");
+    if (len == 0) return fail(ctx, MCR_EFALLBACK, "json: the document is empty (byte 0)");
+    try {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        hipStream_t st = ctx->stream;
+        std::unique_ptr<mcr_json> f(new mcr_json());
+        f->ctx = ctx; f->bytes = (const char*)bytes; f->len = len;
+        const uint32_t n_chunks = (uint32_t)((len + json::kChunk - 1) / json::kChunk);
+        HIP_TRY(ctx, hipMalloc(&f->d_text, (size_t)n_chunks * json::kChunk));
+        HIP_TRY(ctx, hipMemcpyAsync(f->d_text, bytes, len, hipMemcpyHostToDevice, st));
+        // scratch: chunk counts | in_string | first | sfirst (n_chunks + 1 each) | first backslash
+        const size_t o_in = align_up((size_t)n_chunks * sizeof(json::ChunkCount), 256), w = align_up(((size_t)n_chunks + 1) * 4, 256),
+                     o_first = o_in + w, o_sfirst = o_first + w, o_bsl = o_sfirst + w;
+        int rc = ensure_buf(ctx, &ctx->csv_aux, &ctx->csv_aux_bytes, o_bsl + 256);
+        if (rc) return rc;
+        char* ax = (char*)ctx->csv_aux;
+        json::ChunkCount* d_cnt = (json::ChunkCount*)ax;
+        uint32_t *d_in = (uint32_t*)(ax + o_in), *d_first = (uint32_t*)(ax + o_first), *d_sfirst = (uint32_t*)(ax + o_sfirst),
+                 *d_bsl = (uint32_t*)(ax + o_bsl);
+        const char* text = (const char*)f->d_text;
+        HIP_TRY(ctx, hipMemsetAsync(d_bsl, 0xFF, 4, st));
+        LAUNCH(ctx, K_JSON_INDEX, json::k_json_index<false>, dim3(n_chunks), dim3(json::kIndexNT), 0, text, (uint32_t)len, d_cnt, d_bsl,
+               (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
+               (uint32_t*)nullptr);
+        LAUNCH(ctx, K_JSON_SCAN, json::k_json_scan, dim3(1), dim3(1024), 0, (const json::ChunkCount*)d_cnt, n_chunks, d_in, d_first, d_sfirst);
+        uint32_t bsl = 0, n_tok = 0, n_skel = 0;
+        HIP_TRY(ctx, hipMemcpyAsync(&bsl, d_bsl, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(&n_tok, d_first + n_chunks, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(&n_skel, d_sfirst + n_chunks, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        if (bsl != json::kNoOffset) { prof_resolve(ctx); return fail(ctx, MCR_EFALLBACK, "json: a backslash (byte %u): escapes take the host reader", bsl); }
+        std::vector<uint32_t> skel((size_t)n_skel * 2);
+        if (n_tok) {
+            HIP_TRY(ctx, hipMalloc(&f->d_tok, (size_t)n_tok * 4));
+            rc = ensure_buf(ctx, &ctx->csv_rows, &ctx->csv_rows_bytes, (size_t)n_skel * 8 + 256);
+            if (rc) return rc;
+            uint32_t* d_skel = (uint32_t*)ctx->csv_rows;
+            LAUNCH(ctx, K_JSON_INDEX, json::k_json_index<true>, dim3(n_chunks), dim3(json::kIndexNT), 0, text, (uint32_t)len, d_cnt, d_bsl,
+                   (const uint32_t*)d_in, (const uint32_t*)d_first, (const uint32_t*)d_sfirst, (uint32_t*)f->d_tok, d_skel, d_skel + n_skel);
+            if (n_skel) HIP_TRY(ctx, hipMemcpyAsync(skel.data(), d_skel, (size_t)n_skel * 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(ctx, hipStreamSynchronize(st));
+        }
+        prof_resolve(ctx);
+        f->n_tok = n_tok;
+        size_t where = 0;
+        const char* why = json::walk(f->bytes, len, skel.data(), skel.data() + n_skel, n_skel, f->chains, &where);
+        if (*why) return fail(ctx, MCR_EFALLBACK, "json: %s (byte %zu)", why, where);
+        *out = f.release();
+    } catch (const std::exception& e) { return fail(ctx, MCR_ENOMEM, "json: host allocation failed: %s", e.what()); }
+    return MCR_OK;
+}
+
+void mcr_json_close(mcr_json* f) { delete f; }
+int mcr_json_num_chains(const mcr_json* f) { return f ? (int)f->chains.size() : -1; }
+int mcr_json_num_keys(const mcr_json* f, int chain)
+{
+    return (f && chain >= 0 && chain < (int)f->chains.size()) ? (int)f->chains[(size_t)chain].keys.size() : -1;
+}
+const char* mcr_json_key(const mcr_json* f, int chain, int k)
+{
+    return mcr_json_num_keys(f, chain) > k && k >= 0 ? f->chains[(size_t)chain].keys[(size_t)k].c_str() : nullptr;
+}
+int64_t mcr_json_length(const mcr_json* f, int chain, int k)
+{
+    return mcr_json_num_keys(f, chain) > k && k >= 0 ? (int64_t)f->chains[(size_t)chain].arrays[(size_t)k].count : -1;
+}
+
+int mcr_parse_json_number(const char* text, size_t len, double* value, int* is_int)
+{
+    if ((!text && len) || !value || !is_int) return MCR_EINVAL;
+    uint64_t bits = 0;
+    bool integer = false;
+    const int rc = json::json_token(text, len, csv::kPow5, &bits, &integer);
+    *is_int = integer;
+    if (rc == json::kTokDecided) { memcpy(value, &bits, 8); return 0; }
+    if (rc == json::kTokHard) return json::finish_token(text, len, value) ? 1 : MCR_EINVAL;
+    return rc == json::kTokBigInt ? MCR_EFALLBACK : MCR_EINVAL;
+}
+
+int mcr_json_decode(mcr_ctx* ctx, const mcr_json* f, const int* arrays, int n_params, int64_t n_draws, double* out_dev,
+                    int64_t stride_c, int64_t stride_n, int64_t stride_p, uint8_t* all_int, int64_t* hard)
+{
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    if (hard) *hard = 0;
+    if (!f || f->ctx != ctx || n_params < 0 || n_draws < 0 || (n_params > 0 && (!arrays || !all_int)) || stride_c < 0 || stride_n < 0 ||
+        stride_p < 0)
+        return fail(ctx, MCR_EINVAL, "bad argument");
+    if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "mcr_json_decode with summaries in flight");
+    try {
+        const size_t n_chains = f->chains.size();
+        std::vector<json::ArrayDesc> descs;
+        std::vector<size_t> desc_of((size_t)n_params * n_chains, SIZE_MAX);      // [c * n_params + p] -> descs index
+        uint64_t n_values = 0;
+        for (size_t c = 0; c < n_chains; ++c) {
+            const json::Chain& ch = f->chains[c];
+            std::vector<int> slot(ch.keys.size(), -1);
+            for (int p = 0; p < n_params; ++p) {
+                const int k = arrays[c * (size_t)n_params + (size_t)p];
+                if (k < 0 || k >= (int)ch.keys.size()) return fail(ctx, MCR_EINVAL, "json: chain %zu has no key %d", c, k);
+                if (slot[(size_t)k] >= 0) return fail(ctx, MCR_EINVAL, "json: key %d of chain %zu is requested twice", k, c);
+                if ((int64_t)ch.arrays[(size_t)k].count < n_draws)
+                    return fail(ctx, MCR_EINVAL, "json: chain %zu, key %d holds %u values, %lld are requested", c, k, ch.arrays[(size_t)k].count,
+                                (long long)n_draws);
+                slot[(size_t)k] = p;
+            }
+            for (size_t k = 0; k < ch.keys.size(); ++k) {       // every element of the document is checked, the selected ones stored
+                const json::Array& a = ch.arrays[k];
+                if (!a.count) continue;
+                const int p = slot[k];
+                if (p >= 0) desc_of[c * (size_t)n_params + (size_t)p] = descs.size();
+                descs.push_back(json::ArrayDesc{a.tok0, a.count, p >= 0 ? (uint32_t)n_draws : 0u, (uint32_t)n_values,
+                                                p >= 0 ? (long long)c * stride_c + (long long)p * stride_p : -1ll});
+                n_values += a.count;
+            }
+        }
+        for (size_t i = 0; i < (size_t)n_params * n_chains; ++i) all_int[i] = 1;
+        if (n_values == 0) return MCR_OK;
+        if (n_params > 0 && n_draws > 0 && !out_dev) return fail(ctx, MCR_EINVAL, "out_dev is NULL");
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        hipStream_t st = ctx->stream;
+        int rc = json_pow5(ctx);
+        if (rc) return rc;
+        const size_t n_arrays = descs.size();
+        uint32_t h_count = 0;
+        unsigned long long h_err = ~0ull;
+        std::vector<json::HardToken> list;
+        std::vector<uint32_t> not_int(n_arrays);
+        for (int pass = 0; pass < 2; ++pass) {                 // a hard list that overflows: once more with one that fits
+            const size_t o_ni = align_up(n_arrays * sizeof(json::ArrayDesc), 256), o_hard = o_ni + align_up(n_arrays * 4, 256),
+                         o_ctr = o_hard + align_up((size_t)ctx->csv_hard_cap * sizeof(json::HardToken), 256);
+            rc = ensure_buf(ctx, &ctx->csv_aux, &ctx->csv_aux_bytes, o_ctr + 256);
+            if (rc) return rc;
+            char* ax = (char*)ctx->csv_aux;
+            HIP_TRY(ctx, hipMemcpyAsync(ax, descs.data(), n_arrays * sizeof(json::ArrayDesc), hipMemcpyHostToDevice, st));
+            HIP_TRY(ctx, hipMemsetAsync(ax + o_ni, 0, n_arrays * 4, st));
+            HIP_TRY(ctx, hipMemsetAsync(ax + o_ctr, 0xFF, 8, st));
+            HIP_TRY(ctx, hipMemsetAsync(ax + o_ctr + 8, 0, 8, st));
+            json::ParseArgs a{(const char*)f->d_text, (const uint32_t*)f->d_tok, (const json::ArrayDesc*)ax, (uint32_t)n_arrays, (uint32_t)n_values,
+                              (const uint64_t*)ctx->csv_pow5, out_dev, (long long)stride_n, (uint32_t*)(ax + o_ni),
+                              (json::HardToken*)(ax + o_hard), ctx->csv_hard_cap, (uint32_t*)(ax + o_ctr + 8), (unsigned long long*)(ax + o_ctr)};
+            LAUNCH(ctx, K_JSON_PARSE, json::k_json_parse, dim3((unsigned)((n_values + json::kParseNT - 1) / json::kParseNT)), dim3(json::kParseNT),
+                   0, a);
+            HIP_TRY(ctx, hipMemcpyAsync(&h_err, ax + o_ctr, 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(ctx, hipMemcpyAsync(&h_count, ax + o_ctr + 8, 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(ctx, hipMemcpyAsync(not_int.data(), ax + o_ni, n_arrays * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(ctx, hipStreamSynchronize(st));
+            if (h_count <= ctx->csv_hard_cap) {
+                list.resize(h_count);
+                if (h_count) HIP_TRY(ctx, hipMemcpy(list.data(), ax + o_hard, (size_t)h_count * sizeof(json::HardToken), hipMemcpyDeviceToHost));
+                break;
+            }
+            ctx->csv_hard_cap = h_count + (h_count >> 3);
+        }
+        prof_resolve(ctx);
+        if (h_err != ~0ull) {
+            const size_t off = (size_t)(h_err >> 4);
+            if ((h_err & 15) == json::kErrBigInt)
+                return fail(ctx, MCR_EFALLBACK, "json: the integer literal '%s' (byte %zu) is beyond 2^53", json_excerpt(f, off).c_str(), off);
+            return fail(ctx, MCR_EFALLBACK, "json: the array element '%s' (byte %zu) is not a number", json_excerpt(f, off).c_str(), off);
+        }
+        if (!list.empty()) {                                  // the host finishes them: strtod on the caller's image, one upload, one scatter
+            std::vector<long long> idx(list.size());
+            std::vector<double> val(list.size());
+            for (size_t i = 0; i < list.size(); ++i) {
+                const json::HardToken& h = list[i];
+                if (!json::finish_token(f->bytes + h.off, h.len, &val[i]))
+                    return fail(ctx, MCR_EFALLBACK, "json: the array element '%s' (byte %u) is not a number", json_excerpt(f, h.off).c_str(), h.off);
+                idx[i] = descs[h.array].base + (long long)h.v * stride_n;
+            }
+            const size_t nb = list.size() * 8;
+            rc = ensure_buf(ctx, &ctx->csv_aux, &ctx->csv_aux_bytes, 2 * align_up(nb, 256));
+            if (rc) return rc;
+            char* ax = (char*)ctx->csv_aux;
+            HIP_TRY(ctx, hipMemcpyAsync(ax, idx.data(), nb, hipMemcpyHostToDevice, st));
+            HIP_TRY(ctx, hipMemcpyAsync(ax + align_up(nb, 256), val.data(), nb, hipMemcpyHostToDevice, st));
+            LAUNCH(ctx, K_CSV_PATCH, csv::k_csv_patch, dim3((unsigned)((list.size() + 255) / 256)), dim3(256), 0, out_dev, (const long long*)ax,
+                   (const double*)(ax + align_up(nb, 256)), (uint32_t)list.size());
+            HIP_TRY(ctx, hipStreamSynchronize(st));
+            prof_resolve(ctx);
+        }
+        for (size_t i = 0; i < desc_of.size(); ++i)
+            if (desc_of[i] != SIZE_MAX) all_int[i] = not_int[desc_of[i]] ? 0 : 1;
+        if (hard) *hard = (int64_t)list.size();
+    } catch (const std::exception& e) { return fail(ctx, MCR_ENOMEM, "json: host allocation failed: %s", e.what()); }
     return MCR_OK;
 }
 

@@ -6,7 +6,7 @@ If the shared library or a HIP device is missing every entry point raises
 The summarize plumbing the Python API shares lives here too, once: the fileset reader
 (`Context.summarize_files`), the rolling window over enqueue / wait_one (`pipeline`, `split_result`),
 the reference-shaped per-parameter dicts (`entries`), the ragged-chain route (`ragged_diagnostics`), the CmdStan CSV
-decoder (`Context.csv_decode`) and
+decoder (`Context.csv_decode`), the chain-list JSON decoder (`Context.json_decode`) and
 the McrError -> ValueError translation of the reference-compatible functions (`value_errors`).
 """
 from __future__ import annotations
@@ -25,6 +25,7 @@ import numpy as np
 MCR_OK = 0
 MCR_EINVAL, MCR_EMINCHAINS, MCR_EMINCHAINS_ARG, MCR_ENONFINITE = -1, -2, -3, -4
 MCR_EHIP, MCR_ENOMEM, MCR_ENODEVICE, MCR_ECOMM, MCR_ELAYOUT = -5, -6, -7, -8, -9
+MCR_EFALLBACK = -10        # mcr_json_*: the document is for the caller's host reader
 MCR_F64, MCR_F32 = 0, 1
 MCR_MAX_QUANTILES = 32
 MCR_MAX_INFLIGHT = 8
@@ -149,6 +150,15 @@ SYMBOLS = {
     "mcr_csv_stage": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, _ip]),
     "mcr_csv_decode": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, _I64, C.c_void_p, _I64, _I64, _I64, _ip]),
     "mcr_parse_double": (C.c_int, [C.c_char_p, C.c_size_t, _dp]),
+    "mcr_json_open": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    "mcr_json_close": (None, [C.c_void_p]),
+    "mcr_json_num_chains": (C.c_int, [C.c_void_p]),
+    "mcr_json_num_keys": (C.c_int, [C.c_void_p, C.c_int]),
+    "mcr_json_key": (C.c_char_p, [C.c_void_p, C.c_int, C.c_int]),
+    "mcr_json_length": (C.c_int64, [C.c_void_p, C.c_int, C.c_int]),
+    "mcr_json_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int, _I64, C.c_void_p, _I64, _I64, _I64,
+                                  C.POINTER(C.c_uint8), _ip]),
+    "mcr_parse_json_number": (C.c_int, [C.c_char_p, C.c_size_t, _dp, C.POINTER(C.c_int)]),
 }
 
 _lib = None
@@ -502,6 +512,56 @@ class Context:
             for h in hs[:n]:
                 if h:
                     L.mcr_csv_close(h)
+
+    def json_decode(self, text: bytes, select, phases: dict | None = None):
+        """Chain-list JSON text -> (parameter names, [P][C][N] DeviceTensor, all_int [C][P], elements finished on the
+        host): the library uploads and indexes the document and walks its skeleton (mcr_json_open), then parses the
+        selected arrays on the device (mcr_json_decode).  `select(keys per chain, array lengths per chain)` returns
+        (names, N, key index [C][P]) or None.  None when the host reader must decide: the library answers
+        MCR_EFALLBACK (`phases["fallback"]` has its message), a key is not UTF-8, or `select` returns None.  `phases`
+        is filled with the host clock of the two calls (ms)."""
+        L, h = self.lib, C.c_void_p()
+        note = phases if phases is not None else {}
+        t0 = time.perf_counter()
+        rc = L.mcr_json_open(self.handle, text, len(text), C.byref(h))
+        if rc == MCR_EFALLBACK:
+            note["fallback"] = (L.mcr_last_error(self.handle) or b"").decode(errors="replace")
+            return None
+        self._check(rc)
+        try:
+            n = L.mcr_json_num_chains(h)
+            counts = [L.mcr_json_num_keys(h, c) for c in range(n)]
+            try:
+                keys = [[L.mcr_json_key(h, c, k).decode() for k in range(counts[c])] for c in range(n)]
+            except UnicodeDecodeError:
+                note["fallback"] = "json: a key is not UTF-8"
+                return None
+            lengths = [[int(L.mcr_json_length(h, c, k)) for k in range(counts[c])] for c in range(n)]
+            picked = select(keys, lengths)
+            if picked is None:
+                return None
+            names, N, arrays = picked
+            P = len(names)
+            arrays = np.ascontiguousarray(arrays, dtype=np.intc).reshape(n, P)
+            t1 = time.perf_counter()
+            t = self.alloc_tensor(n, N, P)
+            hard = C.c_int64(0)
+            all_int = np.zeros((n, max(P, 1)), dtype=np.uint8)
+            rc = L.mcr_json_decode(self.handle, h, arrays.ctypes.data_as(C.POINTER(C.c_int)), P, N, t.buf.ptr, N, 1, n * N,
+                                   all_int.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(hard))
+            if rc != MCR_OK:
+                t.free()
+                if rc == MCR_EFALLBACK:
+                    note["fallback"] = (L.mcr_last_error(self.handle) or b"").decode(errors="replace")
+                    return None
+                self._check(rc)
+            if phases is not None:
+                t2 = time.perf_counter()
+                phases.update(upload_index_walk_ms=(t1 - t0) * 1e3, parse_finish_ms=(t2 - t1) * 1e3, text_bytes=len(text),
+                              hard=int(hard.value))
+            return list(names), t, all_int[:, :P].astype(bool), int(hard.value)
+        finally:
+            L.mcr_json_close(h)
 
     def wait(self):
         try:

@@ -5,7 +5,8 @@ Mirrors src/mcmc_ref/cli.py for `list`, `stats`, `diagnostics`, `info`, `compare
 gate fails, provenance-generate exits 1 when any recipe failed); `--backend` accepts "hip" (default) and the
 reference's "arrow" / "numpy".  `provenance-scaffold` (Stan programs + data literals), pairs and draws-export
 commands are outside the statistics path and not included.  `cmdstan-summary CHAIN.csv...` is this package's own:
-the chain files of a CmdStan run, parsed on the GPU, printed like `stats --include-diagnostics`.
+the chain files of a CmdStan run, parsed on the GPU, printed like `stats --include-diagnostics`; so is
+`json-summary ARCHIVE.json.zip...` for chain-list JSON archives.
 """
 from __future__ import annotations
 
@@ -92,6 +93,27 @@ def cmdstan_summary_cmd(chains, format_: str, min_chains: int) -> None:
     except ValueError as exc:
         raise click.ClickException(str(exc)) from exc
     _echo_stats(stats, format_)
+
+
+@main.command("json-summary")
+@click.argument("archives", nargs=-1, required=True, type=click.Path(path_type=Path, exists=True, dir_okay=False))
+@click.option("--format", "format_", type=click.Choice(["table", "csv", "json"], case_sensitive=False), default="table")
+@click.option("--min-chains", default=4, type=int)
+def json_summary_cmd(archives, format_: str, min_chains: int) -> None:
+    """Statistics and diagnostics of chain-list JSON archives, parsed on the GPU (no counterpart in the reference).
+    One archive prints like `cmdstan-summary`; several print one block per archive (json: one object keyed by path)."""
+    try:
+        stats = {str(a): convert_mod.summarize_json_zip(a, min_chains=min_chains) for a in archives}
+    except (ValueError, KeyError, IndexError) as exc:
+        raise click.ClickException(str(exc)) from exc
+    if len(archives) == 1:
+        _echo_stats(stats[str(archives[0])], format_)
+    elif format_ == "json":
+        click.echo(json.dumps(stats, indent=2, sort_keys=True))
+    else:
+        for name, st in stats.items():
+            click.echo(f"# {name}")
+            _echo_stats(st, format_)
 
 
 @main.command("diagnostics")

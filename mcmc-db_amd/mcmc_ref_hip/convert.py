@@ -8,6 +8,7 @@ parameter), `_checks` (:164-172) and `_enforce_checks` (:175-178).
 from __future__ import annotations
 
 import json
+import time
 import zipfile
 from collections.abc import Iterable
 from contextlib import closing
@@ -155,11 +156,122 @@ def _read_json_zip(path: Path):
     return pa.table(cols)
 
 
+def _is_json_zip(path: Path) -> bool:
+    return path.suffixes[-2:] == [".json", ".zip"]
+
+
+def _select_json_arrays(keys: list[list[str]], lengths: list[list[int]]):
+    """The reference's choice of arrays (convert.py:78-102) from the keys and array lengths of every chain, in document
+    order: (sorted keys of chain 0, n_draws = length of chain 0's document-first array, key index [C][P]).  None where
+    `_read_json_zip` raises or leaves the plain path: no parameter at all, a parameter named like a bookkeeping column,
+    a chain without one of the parameters (KeyError), an array shorter than n_draws (IndexError)."""
+    if not keys[0] or {"chain", "draw"} & set(keys[0]):
+        return None
+    params = sorted(keys[0])
+    n_draws = lengths[0][0]
+    arrays = []
+    for ks, ls in zip(keys, lengths):
+        at = {k: i for i, k in enumerate(ks)}
+        if any(p not in at or ls[at[p]] < n_draws for p in params):
+            return None
+        arrays.append([at[p] for p in params])
+    return params, n_draws, arrays
+
+
+def read_json_zip_dev(path: Path, context=None, phases: dict | None = None):
+    """`_read_json_zip` without the host parse: (params, [P][C][N] DeviceTensor, int_columns) of a chain-list JSON-zip.
+    The member is inflated here, its text is indexed and every selected number converted on the GPU (mcr_json_*), by
+    the reference's rules: params sorted, n_draws from chain 0's document-first key, longer arrays cut, extra keys of
+    later chains ignored.  int_columns[p]: every draw of the parameter is an integer literal, the column the host
+    reader leaves int64.  None when the host reader must decide -- the document is outside the subset the device
+    reader certifies, or it is one for which `_read_json_zip` raises (`phases["fallback"]` says why).  `phases`
+    receives the host clock of the steps (ms) and `hard`, the numbers the host had to finish.  Free the tensor."""
+    note = phases if phases is not None else {}
+    t0 = time.perf_counter()
+    try:
+        with zipfile.ZipFile(path) as zf:
+            text = zf.read(zf.namelist()[0])
+    except Exception as exc:  # noqa: BLE001 - the host reader raises it again
+        note["fallback"] = f"{type(exc).__name__}: {exc}"
+        return None
+    note["inflate_ms"] = (time.perf_counter() - t0) * 1e3
+    ctx = context if context is not None else _ffi.default_context()
+    with _ffi.value_errors():
+        got = ctx.json_decode(text, _select_json_arrays, note)
+    if got is None:
+        note.setdefault("fallback", "the reference's reader raises for this document")
+        return None
+    params, t, all_int, _hard = got
+    n_draws = t.shape_cnp[1]
+    return params, t, [bool(n_draws and col.all()) for col in all_int.T]
+
+
+def _json_table(params: list[str], flat: np.ndarray, n_chains: int, n_draws: int, int_columns: list[bool]):
+    """The Arrow table `_read_json_zip` builds, from the downloaded [P][C * N] draws."""
+    import pyarrow as pa
+    cols = {"chain": np.repeat(np.arange(n_chains, dtype=np.int64), n_draws),
+            "draw": np.tile(np.arange(n_draws, dtype=np.int64), n_chains)}
+    for p, row, is_int in zip(params, flat, int_columns):
+        cols[p] = row.astype(np.int64) if is_int else row
+    return pa.table(cols)
+
+
+def _read_json_zip_prepared(path: Path, min_chains: int, context):
+    """A `.json.zip` input of convert_files through the device reader: the `prepared` entry with the draws resident
+    (a DeviceTensor in place of the host matrix), or None for the host route."""
+    try:
+        ctx = context or _ffi.default_context()
+    except _ffi.HipUnavailableError:
+        return None
+    got = read_json_zip_dev(path, context=ctx)
+    if got is None:
+        return None
+    params, t, int_columns = got
+    try:
+        _, n_chains, n_draws, P = t.targs[:4]
+        if n_draws == 0:                                   # nothing to parse: the host reader's empty table
+            t.free()
+            return None
+        if n_chains < min_chains:
+            raise ValueError(f"R-hat diagnostics require at least {min_chains} chains; got {n_chains} chain(s)")
+        flat = t.buf.download(np.float64, P * n_chains * n_draws).reshape(P, n_chains * n_draws)
+        table = _json_table(params, flat, n_chains, n_draws, int_columns)
+    except BaseException:
+        t.free()
+        raise
+    return table, params, n_chains, n_draws, t, np.full(n_chains, n_draws)
+
+
+def summarize_json_zip(path: Path, min_chains: int = 4, quantiles=(0.05, 0.5, 0.95), diagnostics: bool = True,
+                       context=None) -> dict[str, dict[str, float]]:
+    """{param: {"mean", "std", "qNN"..., "rhat", "ess_bulk", "ess_tail"}} of a chain-list JSON-zip, the shape
+    `reference.summary_for_model` returns: text to statistics on the GPU.  A document for the host reader is read by it
+    (and raises what it raises) and its tensor uploaded."""
+    ctx = context if context is not None else _ffi.default_context()
+    got = read_json_zip_dev(Path(path), context=ctx)
+    if got is None:
+        table = _read_json_zip(Path(path))
+        params = [c for c in table.column_names if c not in {"chain", "draw"}]
+        x, counts = table_to_tensor(table, params)
+        if not params or len(counts) == 0:
+            return {}
+        with _ffi.value_errors():
+            t = ctx.upload(x.reshape(len(params), len(counts), int(counts[0])), "pcn")
+    else:
+        params, t, _ints = got
+    try:
+        with _ffi.value_errors():
+            r = ctx.summarize(t, min_chains=min_chains, quantiles=quantiles, diagnostics=diagnostics)
+    finally:
+        t.free()
+    return dict(zip(params, _ffi.entries(r, list(quantiles), diagnostics)))
+
+
 def _read_input(path: Path):
     import pyarrow.csv as pacsv
     if path.suffix == ".csv":
         return pacsv.read_csv(path)
-    if path.suffixes[-2:] == [".json", ".zip"]:
+    if _is_json_zip(path):
         return _read_json_zip(path)
     raise ValueError(f"Unsupported input format: {path}")
 
@@ -182,10 +294,14 @@ def _ensure_chain_draw(table):
 
 
 def convert_files(jobs, out_draws_dir: Path, out_meta_dir: Path, force: bool = False, source: str = "converted",
-                  context=None) -> list:
+                  context=None, reader: str = "auto") -> list:
     """`convert_file` for many inputs with the kernels pipelined: jobs = [(input_path, name), ...]; returns, per job,
     a ConvertResult or the exception that `convert_file` would have raised for it (the per-recipe try/except of
     generate.generate_reference_corpus, src/mcmc_ref/generate.py:77-96, becomes per-entry results).
+
+    reader="auto": a `.json.zip` input is parsed on the GPU (`read_json_zip_dev`); its diagnostics run on that tensor
+    and one download gives the table that is written.  A document the device reader does not certify, and every input
+    with reader="host", goes through `_read_json_zip`; both give the same files, meta and exceptions.
 
     All inputs are read and laid out first, the rectangular models are uploaded and enqueued with a rolling window of
     MCR_MAX_INFLIGHT calls (consecutive models overlap on the context's lanes; a NaN draw or any other kernel-side
@@ -193,12 +309,19 @@ def convert_files(jobs, out_draws_dir: Path, out_meta_dir: Path, force: bool = F
     two files of every model are written."""
     import pyarrow.parquet as pq
     out_draws_dir, out_meta_dir = Path(out_draws_dir), Path(out_meta_dir)
+    if reader not in ("auto", "host"):
+        raise ValueError(f"reader must be 'auto' or 'host'; got {reader!r}")
     min_chains = 1 if force else 4
     n = len(jobs)
     results: list = [None] * n
     prepared: dict[int, tuple] = {}
     for i, (input_path, _name) in enumerate(jobs):
         try:
+            if reader == "auto" and _is_json_zip(Path(input_path)):
+                got = _read_json_zip_prepared(Path(input_path), min_chains, context)
+                if got is not None:
+                    prepared[i] = got
+                    continue
             table = _ensure_chain_draw(_read_input(Path(input_path)))
             params = [c for c in table.column_names if c not in {"chain", "draw"}]
             n_chains, n_draws = _count_chains_draws(table)
@@ -220,6 +343,10 @@ def convert_files(jobs, out_draws_dir: Path, out_meta_dir: Path, force: bool = F
     def calls():
         for i in rect:
             _table, params, _nc, _nd, x, counts = prepared[i]
+            if isinstance(x, _ffi.DeviceTensor):            # read on the device: already resident
+                resident.discard(i)
+                yield i, x, {"min_chains": min_chains, "quantiles": ()}
+                continue
             try:
                 t = ctx.upload(x.reshape(len(params), len(counts), int(counts[0])), "pcn")
             except _ffi.McrError as exc:
@@ -229,13 +356,18 @@ def convert_files(jobs, out_draws_dir: Path, out_meta_dir: Path, force: bool = F
 
     # anything but a kernel-side failure of one model (an McrError of its own, kept as its result) ends the batch, and
     # the window then leaves nothing in flight and no device tensor allocated behind the exception
-    if rect:
-        with closing(_ffi.pipeline(ctx, calls(), owns=True)) as done:
-            for i, r in done:
-                if isinstance(r, _ffi.McrError):
-                    results[i] = ValueError(r.message)
-                else:
-                    diags[i] = dict(zip(prepared[i][1], _ffi.entries(r)))
+    resident = {i for i in rect if isinstance(prepared[i][4], _ffi.DeviceTensor)}   # not yet handed to the window
+    try:
+        if rect:
+            with closing(_ffi.pipeline(ctx, calls(), owns=True)) as done:
+                for i, r in done:
+                    if isinstance(r, _ffi.McrError):
+                        results[i] = ValueError(r.message)
+                    else:
+                        diags[i] = dict(zip(prepared[i][1], _ffi.entries(r)))
+    finally:
+        for i in resident:
+            prepared[i][4].free()
     for i in ragged:                                  # chains of unequal length: one pipeline per parameter
         table, params = prepared[i][:2]
         try:
