@@ -189,8 +189,8 @@ __global__ __launch_bounds__(NT) void k_acov_seg(const u32* __restrict__ zb, con
     const int seglen = (int)((n - s0 < 0) ? 0 : ((n - s0 < (i64)SEG) ? n - s0 : (i64)SEG));
 
     if (FIRST) {
-        // ---- stage (all loads of a lane in flight together) + segment sums; all index tests in 32-bit,
-        //      relative to the segment start ----
+        // ---- stage (a lane's NLD code loads in flight together, then its NLD table reads) + segment sums; all index
+        //      tests in 32-bit, relative to the segment start ----
         auto rel = [&](i64 x) -> int { const i64 d = x - s0; return (int)(d < 0 ? 0 : (d > WIN ? WIN : d)); };
         const int r_load = rel(nload);                      // draws [0, r_load) of the window exist
         const int r_n = rel(n);                             // draws [0, r_n) enter the products
@@ -206,17 +206,36 @@ __global__ __launch_bounds__(NT) void k_acov_seg(const u32* __restrict__ zb, con
         // is ORed on the scalar unit; the masks are wave-uniform, so there is nothing to reduce across lanes.
         const u32 ref0 = (nc > 0) ? zc[0] : 0u, ref1 = (hc > 0) ? zc[hc] : 0u;
         unsigned long long dif = 0ull, dif0 = 0ull, dif1 = 0ull;      // lanes that saw a code other than the window's reference
+        // Every slot loads, none under a per-lane test: a load behind a test is a branch with its wait inside, which made
+        // the staging NLD dependent (code, z) round trips.  A slot at or beyond r_load reads the last draw the window has
+        // instead -- the chain's first draw in a workgroup whose window is empty, the draw ref0 reads -- so the NLD code
+        // loads go out back to back, the NLD table reads follow as the codes arrive, and each round below waits for its
+        // own z only.  What such a slot loaded reaches no result: the three windows end at or before own <= r_load
+        // (own_n, a0 .. b1 are clipped to own), their wave-uniform path requires jw + 64 <= hi, their per-lane path tests
+        // j < hi, and the LDS store zeroes every slot from r_n <= r_load on (nload >= n).
         double v[NLD];
         u32 cd[NLD];
+        const u32* zl = zc + (r_load > 0 ? s0 : 0);
+        const int jlast = r_load > 0 ? r_load - 1 : 0;
+        const int jw0 = __builtin_amdgcn_readfirstlane(tid & ~63);
+        // (the last round is the end of the halo, 80 of NT slots: a wave that lies wholly beyond WIN -- two of the four
+        //  on 256 threads -- has nothing to stage and skips its two loads on a scalar branch: 438 -> 429 us per 1000
+        //  parameters)
+        auto live = [&](int u) -> bool { return (u + 1) * NT <= WIN || u * NT + jw0 < WIN; };
+        if (nc > 0) {           // (a chain without a draw has no address to read: workgroup-uniform)
 #pragma unroll
-        for (int u = 0; u < NLD; ++u) {
-            const int j = u * NT + tid;
-            cd[u] = (j < r_load) ? zc[s0 + j] : 0u;
-            v[u] = (j < r_load) ? zdec(ztab, cd[u], M) : 0.0;
+            for (int u = 0; u < NLD; ++u) {
+                const int j = u * NT + tid;
+                cd[u] = live(u) ? zl[j < jlast ? j : jlast] : 0u;
+            }
+#pragma unroll
+            for (int u = 0; u < NLD; ++u) v[u] = live(u) ? zdec(ztab, cd[u], M) : 0.0;
+        } else {
+#pragma unroll
+            for (int u = 0; u < NLD; ++u) { cd[u] = 0u; v[u] = 0.0; }
         }
         // The three windows are ranges of j and a wave's 64 slots are consecutive: a wave that lies wholly inside (or
         // outside) a window -- all but a handful -- decides that with scalar compares and adds without per-lane masks.
-        const int jw0 = __builtin_amdgcn_readfirstlane(tid & ~63);
         // (The compare mask of a wave that straddles a window edge is taken with every lane active, outside the per-lane
         // test: updated under it, the mask would live in VGPRs.)
 #define MCR_IN_WINDOW(lo, hi, DIF, REF, BODY)                                              \
@@ -230,9 +249,11 @@ __global__ __launch_bounds__(NT) void k_acov_seg(const u32* __restrict__ zb, con
         for (int u = 0; u < NLD; ++u) {
             const int jw = u * NT + jw0, j = u * NT + tid;
             const double x = v[u];
-            MCR_IN_WINDOW(0, own_n, dif, ref0, S += x;)
-            MCR_IN_WINDOW(a0, a1, dif0, ref0, S0 += x; Q0 = fma(x, x, Q0);)
-            MCR_IN_WINDOW(b0, b1, dif1, ref1, S1 += x; Q1 = fma(x, x, Q1);)
+            if (u * NT < SEG) {         // (the windows end at own <= SEG: a round of halo slots only is in none)
+                MCR_IN_WINDOW(0, own_n, dif, ref0, S += x;)
+                MCR_IN_WINDOW(a0, a1, dif0, ref0, S0 += x; Q0 = fma(x, x, Q0);)
+                MCR_IN_WINDOW(b0, b1, dif1, ref1, S1 += x; Q1 = fma(x, x, Q1);)
+            }
             if (j < WIN) sx[pos8(j)] = (j < r_n) ? x : 0.0;
         }
 #undef MCR_IN_WINDOW
@@ -271,16 +292,27 @@ __global__ __launch_bounds__(NT) void k_acov_seg(const u32* __restrict__ zb, con
             for (int j = tid; j < 64 * kMoreBlocks; j += NT) r[j] = 0.0;
             return;
         }
+        // Staged as in tier 1: every slot loads, a slot beyond the window's last draw reads that draw (seglen > 0, so there
+        // is one) and is zeroed when it is stored -- here the padding is a value the products read.
+        const int r_n = (int)((n - s0 < (i64)WIN) ? n - s0 : (i64)WIN);         // draws [0, r_n) of the window exist; >= 1
         double v[NLD];
+        u32 cd[NLD];
 #pragma unroll
         for (int u = 0; u < NLD; ++u) {
             const int j = u * NT + tid;
-            v[u] = (j < WIN && s0 + j < n) ? zdec(ztab, zc[s0 + j], M) : 0.0;
+            cd[u] = zc[s0 + (j < r_n - 1 ? j : r_n - 1)];
         }
 #pragma unroll
+        for (int u = 0; u < NLD; ++u) v[u] = zdec(ztab, cd[u], M);
+#pragma unroll
         for (int u = 0; u < NLD; ++u) {
             const int j = u * NT + tid;
-            if (j < WIN) sx[pos8(j)] = v[u];
+            // (a value that is only used under a per-lane test -- `j < WIN` in the last round, `j < r_n` in any -- has its
+            //  two loads sunk into that test by the compiler, behind a wait for all the others: the empty statement uses
+            //  it in every lane, where the store would wait for it anyway)
+            double x = v[u];
+            asm volatile("" : "+v"(x));
+            if (j < WIN) sx[pos8(j)] = (j < r_n) ? x : 0.0;
         }
         __syncthreads();
         for (int blk = 0; blk < kMoreBlocks; ++blk) {
@@ -776,10 +808,12 @@ __global__ __launch_bounds__(256) void k_dev_fill(const u32* __restrict__ zb, co
         const u32* z = ((pk & 1) ? zt : zb) + p * M;
         double* dev = ((pk & 1) ? dev_t : dev_b) + p * M;
         for (i64 j = j0 + threadIdx.x; j < j0 + 4096 && j < M; j += 256) {
+            const double zj = zdec(ztab, z[j], M);       // j < M: every position loads, under the chain search and not behind its test
             int lo = 0, hi = C;                          // chain of pooled position j: last c with off[c] <= j
             while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (off[mid] <= j) lo = mid; else hi = mid; }
             const double* cs = chstate + (pk * C + lo) * kChState;
-            if (j - off[lo] < n) dev[j] = (cs[2] != 0.0) ? 0.0 : zdec(ztab, z[j], M) - cs[0];
+            const double m = cs[0], konst = cs[2];
+            if (j - off[lo] < n) dev[j] = (konst != 0.0) ? 0.0 : zj - m;
         }
     }
 }
