@@ -47,7 +47,10 @@ extern "C" {
 #define MCR_ECOMM (-8)          /* RCCL error (multi-GPU gather) */
 #define MCR_ELAYOUT (-9)        /* mcr_summarize_files: rows not in (chain, draw) order or chains of unequal length */
 #define MCR_EFALLBACK (-10)     /* mcr_json_*: valid input for the caller's host reader, but outside the subset the device
-                                   reader certifies; the message names the first reason and its byte offset */
+                                   reader certifies; the message names the first reason and its byte offset.
+                                   mcr_chain_layout_dev: the chain-id and draw-index ranges of the table need more than
+                                   64 bits together, so no packed row key exists; the caller sorts on the host
+                                   (np.lexsort) and takes mcr_gather_rows_dev */
 
 #define MCR_F64 0
 #define MCR_F32 1
@@ -119,6 +122,11 @@ int mcr_set_workspace_limit(mcr_ctx* ctx, size_t bytes);
 int mcr_plan_chunks(mcr_ctx* ctx, int64_t C, int64_t N, int64_t P, int64_t stride_c, int64_t stride_n, int64_t stride_p,
                     int diagnostics, int64_t* params_per_chunk);
 
+/* mcr_plan_chunks for a ragged call (mcr_summarize_chains_enqueue) on contiguous parameters (stride_p == chain_off[C]).
+ * 0 for a call without draws. */
+int mcr_plan_chunks_chains(mcr_ctx* ctx, const int64_t* chain_off, int C, int64_t P, int diagnostics,
+                           int64_t* params_per_chunk);
+
 /* How many autocorrelation lags this context has re-derived the reference's way so far: no tier of the ESS walk takes
  * a `rho < 0` decision (src/mcmc_ref/diagnostics.py:171-177) on a value within MCR_RHO_BAND (default 1e-10) of zero --
  * segment records + mean correction below lag 256, tree sums or FFTs beyond; such a lag is recomputed with _autocorr's
@@ -183,6 +191,24 @@ int mcr_summarize_models(mcr_ctx* ctx, const mcr_model_desc* models, int n_model
 int mcr_diagnose_chains(mcr_ctx* ctx, const double* pooled, const int64_t* chain_off, int C,
                         int min_chains, mcr_summary* out, double* z_bulk, double* z_tail,
                         double* rank_bulk, double* rank_tail);
+
+/* Every statistic of P parameters whose chains differ in length, in ONE pipeline (the per-parameter loop of
+ * convert._compute_diagnostics, src/mcmc_ref/convert.py:134-147, over chains `_chains_from_table` left ragged,
+ * :150-161).  draws_dev: f64 device memory, parameter p at draws_dev[p * stride_p .. + M), M = chain_off[C], its chains
+ * back to back in (chain, draw) order: chain c is [chain_off[c], chain_off[c + 1]).  chain_off is a HOST array of C + 1
+ * non-decreasing entries starting at 0; it is copied by the call.  stride_p >= M; stride_p != M goes through one ingest
+ * pass.  mean / std / q / q_lo / median are taken over the M pooled draws (Backend.stats); the diagnostics are
+ * diagnostics.py's for ragged chains, exactly as mcr_diagnose_chains computes them (ranks over all pooled draws, n = the
+ * shortest chain, halves of len / 2 per chain, a chain of one draw contributes no halves; diagnostics.py:13-85,
+ * 154-193).  All diagnostics members NULL: Backend.stats only, no rank or autocovariance kernel is launched.
+ * Slots, lanes, chunking under the workspace limit, mcr_summarize_wait / _wait_one: as mcr_summarize_enqueue, and calls
+ * of both kinds may be in flight together.  Errors as mcr_diagnose_chains: MCR_EMINCHAINS_ARG, MCR_EMINCHAINS,
+ * MCR_EINVAL (C > 256, M >= 2^31 - 1, a decreasing table), MCR_ENONFINITE at the wait; M == 0 or P == 0 gives NaN. */
+int mcr_summarize_chains_enqueue(mcr_ctx* ctx, const double* draws_dev, int64_t stride_p, const int64_t* chain_off, int C,
+                                 int64_t P, int min_chains, const double* quantiles, int n_q, mcr_summary* out);
+/* mcr_summarize_chains_enqueue + mcr_summarize_wait */
+int mcr_summarize_chains_dev(mcr_ctx* ctx, const double* draws_dev, int64_t stride_p, const int64_t* chain_off, int C,
+                             int64_t P, int min_chains, const double* quantiles, int n_q, mcr_summary* out);
 
 /* compare.compute_basic_stats (src/mcmc_ref/compare.py:58-64): mean and population std of n
  * host values; n == 0 gives NaN, NaN.  Also the streaming "moments" kernel (HBM-bound). */
@@ -321,6 +347,35 @@ int mcr_parquet_decode(mcr_ctx* ctx, const mcr_parquet_request* reqs, int n_reqs
 int mcr_gather_rows_dev(mcr_ctx* ctx, const double* src_dev, int64_t P, int64_t M, const int64_t* order,
                         double* dst_dev);
 
+/* The row order of `_chains_from_table` (src/mcmc_ref/convert.py:150-161) from the decoded id columns, on the device:
+ * order = np.lexsort((draw, chain)) -- chain id ascending, draw ascending within a chain, rows with equal (chain, draw)
+ * in file order -- by a stable LSD radix sort of the packed key (chain - min chain) << bits(draw range) | (draw - min
+ * draw), one 8-bit pass per significant key byte.  chain_dev / draw_dev: int64 device columns of M rows (M < 2^31 - 1).
+ * *in_order = 1: the rows are in that order already; no sort runs and order_dev is not written (it may be NULL).
+ * Otherwise order_dev (device, M entries) receives the order.  chain_ids / counts (host, cap entries): the distinct chain
+ * ids ascending and their row counts, *n_chains of them; more than cap distinct ids is MCR_EINVAL.  Ranges that do not
+ * fit one 64-bit key: MCR_EFALLBACK.  Synchronous; uses the current lane's workspace, so no summary may be in flight.
+ * MCR_LAYOUT_SPAN: rows per workgroup of a sort pass. */
+#define MCR_LAYOUT_SPAN 2048
+int mcr_chain_layout_dev(mcr_ctx* ctx, const int64_t* chain_dev, const int64_t* draw_dev, int64_t M, int64_t* order_dev,
+                         int64_t* chain_ids, int64_t* counts, int cap, int* n_chains, int* in_order);
+/* Step one of mcr_chain_layout_dev for MANY tables in one round trip (a corpus pass reads dozens of files, nearly all in
+ * order): per table t, in_order[t], n_chains[t] (the number of maximal runs of equal chain id in file order) and --
+ * meaningful when in_order[t] is 1 -- chain_ids / counts at [t * cap, t * cap + min(n_chains[t], cap)).  A table that is
+ * not in order is then sorted by its own mcr_chain_layout_dev call; one with n_chains[t] > cap has only its first cap
+ * chains reported.  Never sorts, never answers MCR_EFALLBACK. */
+typedef struct mcr_id_columns {
+    const int64_t* chain_dev;
+    const int64_t* draw_dev;
+    int64_t rows;
+} mcr_id_columns;
+int mcr_chain_layout_many_dev(mcr_ctx* ctx, const mcr_id_columns* tables, int n_tables, int64_t* chain_ids, int64_t* counts,
+                              int cap, int* n_chains, int* in_order);
+/* mcr_gather_rows_dev with the order in device memory (what mcr_chain_layout_dev wrote): dst[p][k] = src[p][order[k]].
+ * An entry outside [0, M) is not read: MCR_EINVAL. */
+int mcr_gather_rows_order_dev(mcr_ctx* ctx, const double* src_dev, int64_t P, int64_t M, const int64_t* order_dev,
+                              double* dst_dev);
+
 /* ------------------------------------------------------------------------------------------------
  * Many draws files -> statistics in ONE call (the per-model loop of reference.stats /
  * diagnostics_for_model, src/mcmc_ref/reference.py:30-104, over a list of
@@ -329,7 +384,7 @@ int mcr_gather_rows_dev(mcr_ctx* ctx, const double* src_dev, int64_t P, int64_t 
  * tensor, results in a host-side set.  Parameters = every numeric column except `chain` and `draw`,
  * in schema order.  Files whose rows are not in (chain, draw) order, or whose chains differ in
  * length while diagnostics are requested, end the call with MCR_ELAYOUT (use mcr_parquet_decode +
- * mcr_gather_rows_dev + mcr_diagnose_chains for those).  diagnostics = 0: Backend.stats only
+ * mcr_chain_layout_dev + mcr_gather_rows_order_dev + mcr_summarize_chains_dev for those).  diagnostics = 0: Backend.stats only
  * (pooled mean / std / quantiles; any chain structure).
  * ---------------------------------------------------------------------------------------------- */
 typedef struct mcr_fileset mcr_fileset;

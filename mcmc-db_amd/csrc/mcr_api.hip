@@ -30,6 +30,7 @@
 #include "mcr_fft.hpp"
 #include "mcr_ext.hpp"
 #include "mcr_parquet.hpp"
+#include "mcr_layout.hpp"
 #include "mcr_csv.hpp"
 #include "mcr_json.hpp"
 #include "mcr_comm.hpp"
@@ -54,7 +55,8 @@ enum KernelId {
     K_DIAG, K_FINALIZE, K_COMPARE, K_FILL, K_SPLITTERS, K_BUCKET_MERGE, K_ACOV_MORE,
     K_DIAG2, K_ACOV_SEG, K_TWO_SAMPLE, K_COV, K_ZTABLE, K_PQ_SNAPPY, K_PQ_DECODE, K_GATHER, K_ACOV_LONG, K_DIAG_LONG, K_COV_FINAL, K_FFT,
     K_CSV_LINES, K_CSV_SCAN, K_CSV_PARSE, K_CSV_PATCH,
-    K_JSON_INDEX, K_JSON_SCAN, K_JSON_PARSE, K_COUNT
+    K_JSON_INDEX, K_JSON_SCAN, K_JSON_PARSE,
+    K_LAYOUT_SCAN, K_LAYOUT_KEYS, K_LAYOUT_HIST, K_LAYOUT_OFFSETS, K_LAYOUT_SCATTER, K_LAYOUT_BOUNDS, K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {
     "k_ingest", "k_moments", "k_moments_final", "k_tile_sort", "k_merge", "k_order_stats", "k_rank_z",
@@ -62,7 +64,8 @@ const char* const kKernelNames[K_COUNT] = {
     "k_bucket_merge", "k_acov_more", "k_diag_combine2", "k_acov_seg", "k_two_sample", "k_cov_mfma", "k_ztable",
     "k_pq_snappy", "k_pq_decode", "k_gather_rows", "k_acov_long", "k_diag_long_scan", "k_cov_final", "k_fft",
     "k_csv_lines", "k_csv_scan", "k_csv_parse", "k_csv_patch",
-    "k_json_index", "k_json_scan", "k_json_parse"};
+    "k_json_index", "k_json_scan", "k_json_parse",
+    "k_layout_scan", "k_layout_keys", "k_layout_hist", "k_layout_offsets", "k_layout_scatter", "k_layout_bounds"};
 
 struct EvPair { hipEvent_t a, b; int kid; };
 
@@ -873,13 +876,41 @@ int check_common(mcr_ctx* ctx, const void* draws, int dtype, i64 C, i64 N, i64 P
 // How a call of this shape is cut into workspace chunks of parameters (a pure function of the shape, the workspace limit
 // and MCR_FFT): shared by enqueue_impl and mcr_plan_chunks.
 struct ChunkPlan { bool ingest = false; FftPlan fp{}; i64 pcmax = 0; size_t bytes = 0; };
-int plan_chunks(mcr_ctx* ctx, i64 C, i64 N, i64 P, i64 sc, i64 sn, i64 sp, bool do_diag, ChunkPlan& cp)
+
+// The chain structure of a call as the kernels see it next to the offset table: C chains, M pooled draws, n = the
+// shortest chain (what _ess walks, src/mcmc_ref/diagnostics.py:154-169), nh = the smallest half len / 2 over the chains
+// of at least two draws (_split_chains, diagnostics.py:76-85; a chain of one draw contributes no halves), nstage = the
+// longest chain prefix k_acov_seg reads (n, or second half start + nh).  Rectangular tensors are the case off[c] = c N.
+struct ChainShape { i64 C = 0, M = 0, n = 0, nh = 0, nstage = 1; };
+ChainShape shape_regular(i64 C, i64 N)
 {
-    const i64 M = C * N;
-    // tensors in the Arrow column layout [P][C][N] are consumed in place, f64 and f32 alike (the tile sort widens f32
-    // as it loads); anything else goes through one ingest pass into X[P][M] f64
-    cp.ingest = !((N <= 1 || sn == 1) && (C <= 1 || sc == N) && (P <= 1 || sp == M));
-    cp.fp = plan_fft(N, (int)C, do_diag && ctx->fft_on);
+    ChainShape h;
+    h.C = C; h.M = C * N; h.n = N; h.nh = (N >= 2) ? N / 2 : 0; h.nstage = N > 0 ? N : 1;
+    return h;
+}
+ChainShape shape_offsets(const i64* off, i64 C)
+{
+    ChainShape h;
+    h.C = C; h.M = C > 0 ? off[C] : 0;
+    bool have_h = false;
+    for (i64 c = 0; c < C; ++c) {
+        const i64 len = off[c + 1] - off[c];
+        if (c == 0 || len < h.n) h.n = len;
+        if (len >= 2) { if (!have_h || len / 2 < h.nh) h.nh = len / 2; have_h = true; }
+    }
+    h.nstage = h.n > 0 ? h.n : 1;
+    for (i64 c = 0; c < C; ++c) {
+        const i64 len = off[c + 1] - off[c];
+        if (len >= 2 && len / 2 + h.nh > h.nstage) h.nstage = len / 2 + h.nh;
+    }
+    return h;
+}
+
+int plan_chunks(mcr_ctx* ctx, const ChainShape& h, i64 P, bool ingest, bool do_diag, ChunkPlan& cp)
+{
+    const i64 M = h.M, C = h.C;
+    cp.ingest = ingest;
+    cp.fp = plan_fft(h.n, (int)C, do_diag && ctx->fft_on);
     auto fft_bytes = [&]() {
         PipeIn a{};
         Carve m{nullptr};
@@ -888,7 +919,7 @@ int plan_chunks(mcr_ctx* ctx, i64 C, i64 N, i64 P, i64 sc, i64 sn, i64 sp, bool 
     };
     auto measure = [&](i64 pc) {
         PipeIn a{};
-        a.M = M; a.pc = pc; a.C = (int)C; a.n = N; a.nstage = N > 0 ? N : 1;
+        a.M = M; a.pc = pc; a.C = (int)C; a.n = h.n; a.nstage = h.nstage;
         Carve m{nullptr};
         carve_pipe(m, a, true, cp.fp, cp.ingest);
         return m.off;
@@ -913,6 +944,13 @@ int plan_chunks(mcr_ctx* ctx, i64 C, i64 N, i64 P, i64 sc, i64 sn, i64 sp, bool 
     }
     cp.pcmax = hi;
     return MCR_OK;
+}
+
+// Tensors in the Arrow column layout [P][C][N] are consumed in place, f64 and f32 alike (the tile sort widens f32 as it
+// loads); anything else goes through one ingest pass into X[P][M] f64.
+inline bool needs_ingest(i64 C, i64 N, i64 P, i64 sc, i64 sn, i64 sp)
+{
+    return !((N <= 1 || sn == 1) && (C <= 1 || sc == N) && (P <= 1 || sp == C * N));
 }
 
 // The call-wide tables of a pipeline, from the context's caches: the FFT tier's twiddles (fp.on), the z table (ztab).
@@ -941,14 +979,43 @@ int commit_slot(mcr_ctx* ctx, int si)
     return MCR_OK;
 }
 
-int enqueue_impl(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i64 P, i64 sc, i64 sn, i64 sp,
-                 int min_chains, const double* quantiles, int nq, const mcr_summary* out)
+// Acceptance of a ragged call: the codes mcr_diagnose_chains answers with.
+int check_chains(mcr_ctx* ctx, const void* draws, const i64* chain_off, i64 C, i64 P, i64 sp, int min_chains,
+                 const mcr_summary* out)
 {
-    int rc = check_common(ctx, draws_dev, dtype, C, N, P, min_chains, out);
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    if (!out) return fail(ctx, MCR_EINVAL, "out is NULL");
+    if (C < 0 || P < 0) return fail(ctx, MCR_EINVAL, "negative dimension (C=%lld P=%lld)", (long long)C, (long long)P);
+    if (min_chains < 1) return fail(ctx, MCR_EMINCHAINS_ARG, "min_chains must be >= 1; got %d", min_chains);
+    if (C < min_chains)
+        return fail(ctx, MCR_EMINCHAINS, "diagnostics require at least %d chains; got %lld chain(s)", min_chains, (long long)C);
+    if (C > kMaxChains) return fail(ctx, MCR_EINVAL, "at most %d chains are supported; got %lld", kMaxChains, (long long)C);
+    if (C > 0 && !chain_off) return fail(ctx, MCR_EINVAL, "chain_off is NULL");
+    const i64 M = C > 0 ? chain_off[C] : 0;
+    if (C > 0 && chain_off[0] != 0) return fail(ctx, MCR_EINVAL, "chain_off[0] must be 0");
+    for (i64 c = 0; c < C; ++c)
+        if (chain_off[c + 1] < chain_off[c]) return fail(ctx, MCR_EINVAL, "chain_off must be non-decreasing");
+    if (M < 0 || M >= (i64)0x7FFFFFFFll) return fail(ctx, MCR_EINVAL, "pooled length out of range");
+    if (P > 1 && M > 0 && sp < M) return fail(ctx, MCR_EINVAL, "stride_p must be at least the pooled length");
+    if (!draws && M * P > 0) return fail(ctx, MCR_EINVAL, "draws is NULL");
+    return MCR_OK;
+}
+
+// One summary call on a free slot and the next lane.  !ragged: a rectangular tensor (C, N, strides), chain c at c * N --
+// the offset table stays resident in the slot between calls of one shape.  ragged: f64 draws with the chains back to
+// back as chain_off says (host, C + 1 entries), parameter p at draws_dev + p * sp; N, sc and sn are unused and the table
+// goes up with the call.
+int enqueue_impl(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i64 P, i64 sc, i64 sn, i64 sp,
+                 const i64* chain_off, bool ragged, int min_chains, const double* quantiles, int nq,
+                 const mcr_summary* out)
+{
+    int rc = ragged ? check_chains(ctx, draws_dev, chain_off, C, P, sp, min_chains, out)
+                    : check_common(ctx, draws_dev, dtype, C, N, P, min_chains, out);
     if (rc) return rc;
     if (ctx->order.size() >= MCR_MAX_INFLIGHT) return fail(ctx, MCR_EINVAL, "more than %d summaries in flight", MCR_MAX_INFLIGHT);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const i64 M = C * N;
+    const ChainShape h = ragged ? shape_offsets(chain_off, C) : shape_regular(C, N);
+    const i64 M = h.M;
     int si = -1;
     for (int k = 0; k < MCR_MAX_INFLIGHT; ++k) {
         const int c = (ctx->next_slot + k) % MCR_MAX_INFLIGHT;
@@ -962,8 +1029,10 @@ int enqueue_impl(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i
     if (!s.trivial_nan) {
         const bool do_diag = out->rhat || out->rhat_bulk || out->rhat_tail || out->ess_bulk || out->ess_tail ||
                              out->lag_bulk || out->lag_tail;
+        // the ingest pass sees a ragged parameter as one row of M draws
+        const i64 iC = ragged ? 1 : C, iN = ragged ? M : N, isc = ragged ? M : sc, isn = ragged ? 1 : sn;
         ChunkPlan cp;
-        rc = plan_chunks(ctx, C, N, P, sc, sn, sp, do_diag, cp);
+        rc = plan_chunks(ctx, h, P, needs_ingest(iC, iN, P, isc, isn, sp), do_diag, cp);
         if (rc) return rc;
         const i64 pcmax = s.pcmax = cp.pcmax;
         rc = ensure_ws(ctx, cp.bytes);
@@ -971,11 +1040,16 @@ int enqueue_impl(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i
         const int R = res_fields(nq);
         rc = ensure_slot(ctx, s, (size_t)R * (size_t)P, (size_t)C + 1);
         if (rc) return rc;
-        const bool off_resident = s.off_C == C && s.off_N == N;
-        if (!off_resident) for (i64 c = 0; c <= C; ++c) s.h_off[c] = c * N;
+        const bool off_resident = !ragged && s.off_C == C && s.off_N == N;
+        if (ragged) {
+            memcpy(s.h_off, chain_off, sizeof(i64) * (size_t)(C + 1));
+            s.off_C = s.off_N = -1;
+        } else if (!off_resident) {
+            for (i64 c = 0; c <= C; ++c) s.h_off[c] = c * N;
+        }
         PipeIn call{};                  // the fields every chunk shares
-        call.M = M; call.C = (int)C; call.d_off = s.d_off; call.n = N; call.nh = (N >= 2) ? N / 2 : 0; call.q = q;
-        call.nstage = N > 0 ? N : 1; call.do_diag = do_diag;
+        call.M = M; call.C = (int)C; call.d_off = s.d_off; call.n = h.n; call.nh = h.nh; call.q = q;
+        call.nstage = h.nstage; call.do_diag = do_diag;
         rc = get_tables(ctx, call, cp.fp, do_diag);
         if (rc) return rc;
         if (!off_resident)
@@ -993,8 +1067,8 @@ int enqueue_impl(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i
                                                // three more launches and two event waits (measured: C1 4 M param-draws 306 -> 288 us,
                                                // 10 x 1000 x 45 149 -> 166, 4 x 1000 x 10 124 -> 133), short enough not to fill the chip
             if (cp.ingest) {
-                rc = (dtype == MCR_F64) ? launch_ingest<double>(ctx, draws_dev, X, C, N, pc, sc, sn, sp, p0)
-                                        : launch_ingest<float>(ctx, draws_dev, X, C, N, pc, sc, sn, sp, p0);
+                rc = (dtype == MCR_F64) ? launch_ingest<double>(ctx, draws_dev, X, iC, iN, pc, isc, isn, sp, p0)
+                                        : launch_ingest<float>(ctx, draws_dev, X, iC, iN, pc, isc, isn, sp, p0);
                 if (rc) return rc;
                 a.X = X;
             } else {
@@ -1010,7 +1084,7 @@ int enqueue_impl(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i
         HIP_TRY(ctx, hipMemcpyAsync(s.h_res, s.d_res, sizeof(double) * (size_t)R * (size_t)P, hipMemcpyDeviceToHost,
                                     ctx->stream));
     }
-    if (!s.trivial_nan) { s.off_C = C; s.off_N = N; }
+    if (!s.trivial_nan && !ragged) { s.off_C = C; s.off_N = N; }
     rc = commit_slot(ctx, si);
     if (rc) return rc;
     ctx->next_slot = (si + 1) % MCR_MAX_INFLIGHT;
@@ -1261,7 +1335,7 @@ int mcr_plan_chunks(mcr_ctx* ctx, int64_t C, int64_t N, int64_t P, int64_t sc, i
     if (!ctx || !params_per_chunk) return fail(ctx, MCR_EINVAL, "mcr_plan_chunks: NULL argument");
     if (C <= 0 || N <= 0 || P <= 0) { *params_per_chunk = 0; return MCR_OK; }
     ChunkPlan cp;
-    const int rc = plan_chunks(ctx, C, N, P, sc, sn, sp, diagnostics != 0, cp);
+    const int rc = plan_chunks(ctx, shape_regular(C, N), P, needs_ingest(C, N, P, sc, sn, sp), diagnostics != 0, cp);
     if (rc) return rc;
     *params_per_chunk = cp.pcmax;
     return MCR_OK;
@@ -1309,9 +1383,43 @@ int mcr_summarize_enqueue(mcr_ctx* ctx, const void* draws_dev, int dtype, int64_
                           int64_t sc, int64_t sn, int64_t sp, int min_chains, const double* quantiles, int n_q,
                           mcr_summary* out)
 {
-    const int rc = enqueue_impl(ctx, draws_dev, dtype, C, N, P, sc, sn, sp, min_chains, quantiles, n_q, out);
+    const int rc = enqueue_impl(ctx, draws_dev, dtype, C, N, P, sc, sn, sp, nullptr, false, min_chains, quantiles, n_q, out);
     if (rc && ctx && rc != MCR_EMINCHAINS && rc != MCR_EMINCHAINS_ARG && rc != MCR_EINVAL) return drain(ctx, rc, true);
     return rc;
+}
+
+int mcr_summarize_chains_enqueue(mcr_ctx* ctx, const double* draws_dev, int64_t stride_p, const int64_t* chain_off, int C,
+                                 int64_t P, int min_chains, const double* quantiles, int n_q, mcr_summary* out)
+{
+    const int rc = enqueue_impl(ctx, draws_dev, MCR_F64, C, 0, P, 0, 1, stride_p, reinterpret_cast<const i64*>(chain_off), true,
+                                min_chains, quantiles, n_q, out);
+    if (rc && ctx && rc != MCR_EMINCHAINS && rc != MCR_EMINCHAINS_ARG && rc != MCR_EINVAL) return drain(ctx, rc, true);
+    return rc;
+}
+
+int mcr_summarize_chains_dev(mcr_ctx* ctx, const double* draws_dev, int64_t stride_p, const int64_t* chain_off, int C,
+                             int64_t P, int min_chains, const double* quantiles, int n_q, mcr_summary* out)
+{
+    const int rc = mcr_summarize_chains_enqueue(ctx, draws_dev, stride_p, chain_off, C, P, min_chains, quantiles, n_q, out);
+    if (rc) return rc;
+    return wait_impl(ctx);
+}
+
+int mcr_plan_chunks_chains(mcr_ctx* ctx, const int64_t* chain_off, int C, int64_t P, int diagnostics,
+                           int64_t* params_per_chunk)
+{
+    if (!ctx || !params_per_chunk) return fail(ctx, MCR_EINVAL, "mcr_plan_chunks_chains: NULL argument");
+    if (C < 0 || C > kMaxChains || (C > 0 && !chain_off))
+        return fail(ctx, MCR_EINVAL, "mcr_plan_chunks_chains: bad chain table");
+    for (int c = 0; c < C; ++c)
+        if (chain_off[c + 1] < chain_off[c]) return fail(ctx, MCR_EINVAL, "chain_off must be non-decreasing");
+    if (C == 0 || P <= 0 || chain_off[C] <= 0) { *params_per_chunk = 0; return MCR_OK; }
+    if (chain_off[C] >= (i64)0x7FFFFFFFll) return fail(ctx, MCR_EINVAL, "pooled length out of range");
+    ChunkPlan cp;
+    const int rc = plan_chunks(ctx, shape_offsets(reinterpret_cast<const i64*>(chain_off), C), P, false, diagnostics != 0, cp);
+    if (rc) return rc;
+    *params_per_chunk = cp.pcmax;
+    return MCR_OK;
 }
 
 int mcr_summarize_wait(mcr_ctx* ctx)
@@ -2300,6 +2408,192 @@ int mcr_gather_rows_dev(mcr_ctx* ctx, const double* src_dev, int64_t P, int64_t 
     return MCR_OK;
 }
 
+// ---- device row order (mcr_layout.hpp) -------------------------------------------------------------------------
+
+namespace {
+namespace lay = mcr::layout;
+static_assert(lay::kLayoutSpan == MCR_LAYOUT_SPAN, "the header states the sort span");
+
+// The one layout of the row-order workspace: per table the block the host reads (res, `stride` words each: the four
+// extremes, the in-order word, then the distinct chains' count, ids and first rows), the table descriptors and the scan's
+// partial records, then -- the sort of one table of M rows -- the ping-pong key / row-number buffers and the (digit,
+// workgroup) histogram.
+struct LayoutBufs {
+    i64 *res, *part; lay::Table* tab;
+    u64 *kA, *kB; u32 *iA, *iB, *hist;
+};
+constexpr int kLayoutRes = 8;         // words of a table's res in front of its bounds
+inline size_t layout_stride(int cap) { return (size_t)kLayoutRes + 1 + 2 * (size_t)cap; }
+void carve_layout(Carve& cv, LayoutBufs& b, int n, int cap, i64 sort_M)
+{
+    b.res = cv.take<i64>((size_t)n * layout_stride(cap));
+    b.tab = cv.take<lay::Table>((size_t)n);
+    b.part = cv.take<i64>((size_t)n * 5 * (size_t)lay::kScanGrid);
+    if (sort_M <= 0) return;
+    const size_t m = (size_t)sort_M, G = (size_t)((sort_M + lay::kLayoutSpan - 1) / lay::kLayoutSpan);
+    b.kA = cv.take<u64>(m); b.kB = cv.take<u64>(m);
+    b.iA = cv.take<u32>(m); b.iB = cv.take<u32>(m);
+    b.hist = cv.take<u32>(256 * G);
+}
+inline int bit_length(u64 v) { int b = 0; while (v) { ++b; v >>= 1; } return b; }
+
+// Step 1 for n tables in one round trip: already in (chain, draw) order?  + the extremes of both columns, + the chains of
+// every table as it stands (all an ordered table needs: most are).  h receives the n result blocks.
+int layout_scan(mcr_ctx* ctx, const lay::Table* tables, int n, int cap, LayoutBufs& b, std::vector<i64>& h)
+{
+    int rc = carve_ws(ctx, [&](Carve& cv) { carve_layout(cv, b, n, cap, 0); });
+    if (rc) return rc;
+    try { h.resize((size_t)n * layout_stride(cap)); } catch (const std::exception&) { return fail(ctx, MCR_ENOMEM, "host allocation failed"); }
+    hipStream_t st = ctx->stream;
+    HIP_TRY(ctx, hipMemcpyAsync(b.tab, tables, sizeof(lay::Table) * (size_t)n, hipMemcpyHostToDevice, st));
+    LAUNCH(ctx, K_LAYOUT_SCAN, lay::k_layout_scan, dim3((unsigned)lay::kScanGrid, (unsigned)n), dim3(lay::kLayoutNT), 0,
+           (const lay::Table*)b.tab, b.part);
+    LAUNCH(ctx, K_LAYOUT_SCAN, lay::k_layout_scan_final, dim3((unsigned)n), dim3(64), 0, (const i64*)b.part, lay::kScanGrid,
+           b.res, (i64)layout_stride(cap));
+    LAUNCH(ctx, K_LAYOUT_BOUNDS, lay::k_layout_bounds, dim3((unsigned)n), dim3(1024), 0, (const lay::Table*)b.tab,
+           (const u32*)nullptr, cap, b.res + kLayoutRes, (i64)layout_stride(cap));
+    HIP_TRY(ctx, hipMemcpyAsync(h.data(), b.res, sizeof(i64) * h.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));      // (the pageable copies above are done with `tables` and `h` by now)
+    return MCR_OK;
+}
+
+// ids / counts of one table from its result block; false when it has more than cap distinct chains.
+bool layout_chains(const i64* blk, int cap, i64 M, int64_t* ids, int64_t* counts, int* n_chains)
+{
+    const i64* hb = blk + kLayoutRes;
+    *n_chains = (int)(hb[0] < 0x7FFFFFFF ? hb[0] : 0x7FFFFFFF);
+    if (hb[0] > cap) return false;
+    const int n = (int)hb[0];
+    for (int j = 0; j < n; ++j) {
+        ids[j] = hb[1 + j];
+        counts[j] = (j + 1 < n ? hb[1 + cap + j + 1] : M) - hb[1 + cap + j];
+    }
+    return true;
+}
+
+int layout_args(mcr_ctx* ctx, int cap, const int64_t* chain_ids, const int64_t* counts, const int* n_chains, const int* in_order)
+{
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    if (!n_chains || !in_order || cap < 0 || (cap > 0 && (!chain_ids || !counts)))
+        return fail(ctx, MCR_EINVAL, "chain layout: NULL argument");
+    if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "chain layout with summaries in flight");
+    return MCR_OK;
+}
+
+}  // namespace
+
+int mcr_chain_layout_dev(mcr_ctx* ctx, const int64_t* chain_dev, const int64_t* draw_dev, int64_t M, int64_t* order_dev,
+                         int64_t* chain_ids, int64_t* counts, int cap, int* n_chains, int* in_order)
+{
+    int rc = layout_args(ctx, cap, chain_ids, counts, n_chains, in_order);
+    if (rc) return rc;
+    if (M < 0 || M >= (i64)0x7FFFFFFFll) return fail(ctx, MCR_EINVAL, "mcr_chain_layout_dev: row count out of range");
+    *n_chains = 0; *in_order = 1;
+    if (M == 0) return MCR_OK;
+    if (!chain_dev || !draw_dev) return fail(ctx, MCR_EINVAL, "mcr_chain_layout_dev: NULL id column");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const lay::Table tab{reinterpret_cast<const i64*>(chain_dev), reinterpret_cast<const i64*>(draw_dev), (i64)M};
+    LayoutBufs b{};
+    std::vector<i64> h;
+    rc = layout_scan(ctx, &tab, 1, cap, b, h);
+    if (rc) return rc;
+    const bool ordered = h[4] != 0;
+    if (!ordered) {
+        if (!order_dev) return fail(ctx, MCR_EINVAL, "mcr_chain_layout_dev: order_dev is NULL");
+        hipStream_t st = ctx->stream;
+        const i64 cmin = h[0], dmin = h[2];
+        const int cbits = bit_length((u64)h[1] - (u64)cmin), dbits = bit_length((u64)h[3] - (u64)dmin);
+        if (cbits + dbits > 64) {
+            prof_resolve(ctx);
+            return fail(ctx, MCR_EFALLBACK, "chain ids span %d bits and draw indices %d: no 64-bit row key", cbits, dbits);
+        }
+        // 2. keys + a stable 8-bit pass per significant key byte
+        rc = carve_ws(ctx, [&](Carve& cv) { carve_layout(cv, b, 1, cap, M); });
+        if (rc) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(b.tab, &tab, sizeof tab, hipMemcpyHostToDevice, st));      // (the workspace may have moved)
+        const unsigned nb = (unsigned)((M + lay::kLayoutNT - 1) / lay::kLayoutNT);
+        const int G = (int)((M + lay::kLayoutSpan - 1) / lay::kLayoutSpan);
+        LAUNCH(ctx, K_LAYOUT_KEYS, lay::k_layout_keys, dim3(nb), dim3(lay::kLayoutNT), 0, tab.chain, tab.draw, (i64)M, cmin, dmin,
+               dbits, b.kA, b.iA);
+        u64 *kin = b.kA, *kout = b.kB;
+        u32 *iin = b.iA, *iout = b.iB;
+        const int passes = (cbits + dbits + 7) / 8;
+        for (int ps = 0; ps < passes; ++ps) {
+            LAUNCH(ctx, K_LAYOUT_HIST, lay::k_layout_hist, dim3((unsigned)G), dim3(lay::kLayoutNT), 0, (const u64*)kin, (i64)M,
+                   8 * ps, G, b.hist);
+            LAUNCH(ctx, K_LAYOUT_OFFSETS, lay::k_layout_offsets, dim3(1), dim3(1024), 0, b.hist, (i64)256 * G);
+            LAUNCH(ctx, K_LAYOUT_SCATTER, lay::k_layout_scatter, dim3((unsigned)G), dim3(lay::kLayoutNT), 0, (const u64*)kin,
+                   (const u32*)iin, (i64)M, 8 * ps, G, (const u32*)b.hist, kout, iout);
+            std::swap(kin, kout);
+            std::swap(iin, iout);
+        }
+        LAUNCH(ctx, K_LAYOUT_KEYS, lay::k_layout_order, dim3(nb), dim3(lay::kLayoutNT), 0, (const u32*)iin, (i64)M,
+               reinterpret_cast<i64*>(order_dev));
+        // 3. the chains again, over the sorted rows
+        LAUNCH(ctx, K_LAYOUT_BOUNDS, lay::k_layout_bounds, dim3(1), dim3(1024), 0, (const lay::Table*)b.tab, (const u32*)iin, cap,
+               b.res + kLayoutRes, (i64)layout_stride(cap));
+        HIP_TRY(ctx, hipMemcpyAsync(h.data(), b.res, sizeof(i64) * h.size(), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+    }
+    prof_resolve(ctx);
+    *in_order = ordered ? 1 : 0;
+    if (!layout_chains(h.data(), cap, M, chain_ids, counts, n_chains))
+        return fail(ctx, MCR_EINVAL, "%d distinct chain ids; the caller has room for %d", *n_chains, cap);
+    return MCR_OK;
+}
+
+int mcr_chain_layout_many_dev(mcr_ctx* ctx, const mcr_id_columns* tables, int n_tables, int64_t* chain_ids, int64_t* counts,
+                              int cap, int* n_chains, int* in_order)
+{
+    int rc = layout_args(ctx, cap, chain_ids, counts, n_chains, in_order);
+    if (rc) return rc;
+    if (n_tables < 0 || n_tables > kMaxGridY || (n_tables > 0 && !tables)) return fail(ctx, MCR_EINVAL, "mcr_chain_layout_many_dev: bad table list");
+    if (n_tables == 0) return MCR_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<lay::Table> tabs;
+    std::vector<i64> h;
+    try { tabs.resize((size_t)n_tables); } catch (const std::exception&) { return fail(ctx, MCR_ENOMEM, "host allocation failed"); }
+    for (int t = 0; t < n_tables; ++t) {
+        const mcr_id_columns& c = tables[t];
+        if (c.rows < 0 || c.rows >= (i64)0x7FFFFFFFll) return fail(ctx, MCR_EINVAL, "mcr_chain_layout_many_dev: row count out of range");
+        if (c.rows > 0 && (!c.chain_dev || !c.draw_dev)) return fail(ctx, MCR_EINVAL, "mcr_chain_layout_many_dev: NULL id column");
+        tabs[(size_t)t] = lay::Table{reinterpret_cast<const i64*>(c.chain_dev), reinterpret_cast<const i64*>(c.draw_dev), (i64)c.rows};
+    }
+    LayoutBufs b{};
+    rc = layout_scan(ctx, tabs.data(), n_tables, cap, b, h);
+    if (rc) return rc;
+    prof_resolve(ctx);
+    for (int t = 0; t < n_tables; ++t) {
+        const i64* blk = h.data() + (size_t)t * layout_stride(cap);
+        in_order[t] = blk[4] != 0 ? 1 : 0;
+        layout_chains(blk, cap, tabs[(size_t)t].M, chain_ids + (size_t)t * cap, counts + (size_t)t * cap, &n_chains[t]);
+    }
+    return MCR_OK;
+}
+
+int mcr_gather_rows_order_dev(mcr_ctx* ctx, const double* src_dev, int64_t P, int64_t M, const int64_t* order_dev,
+                              double* dst_dev)
+{
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    if (P < 0 || M < 0 || P > kMaxGridY) return fail(ctx, MCR_EINVAL, "bad shape");
+    if (P == 0 || M == 0) return MCR_OK;
+    if (!src_dev || !dst_dev || !order_dev) return fail(ctx, MCR_EINVAL, "NULL argument");
+    if (src_dev == dst_dev) return fail(ctx, MCR_EINVAL, "gather cannot run in place");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_buf(ctx, &ctx->pq_tab, &ctx->pq_tab_bytes, 256);
+    if (rc) return rc;
+    int* d_err = (int*)ctx->pq_tab;
+    HIP_TRY(ctx, hipMemsetAsync(d_err, 0, sizeof(int), ctx->stream));
+    LAUNCH(ctx, K_GATHER, lay::k_gather_rows_order, dim3((unsigned)((M + 255) / 256), (unsigned)P), dim3(256), 0, src_dev,
+           (const i64*)order_dev, (i64)M, dst_dev, d_err);
+    int h_err = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&h_err, d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    prof_resolve(ctx);
+    if (h_err) return fail(ctx, MCR_EINVAL, "order has an entry outside [0, %lld)", (long long)M);
+    return MCR_OK;
+}
+
 
 // ---- many files in one call -------------------------------------------------------------------------------
 
@@ -2553,7 +2847,7 @@ int fs_stats(mcr_ctx* ctx, const FileBatch& B, mcr_fileset& fs, Staged& S, int m
         mcr_summary o = summary_at(all, j.p0, n_q);
         if (ctx->order.size() >= MCR_MAX_INFLIGHT) rc = wait_one_impl(ctx);
         if (!rc)
-            rc = enqueue_impl(ctx, B.arena + B.f[(size_t)j.first].off, MCR_F64, j.C, j.N, j.P, j.N, 1, j.C * j.N,
+            rc = enqueue_impl(ctx, B.arena + B.f[(size_t)j.first].off, MCR_F64, j.C, j.N, j.P, j.N, 1, j.C * j.N, nullptr, false,
                               diagnostics ? min_chains : 1, quantiles, n_q, &o);
     }
     return drain(ctx, rc);

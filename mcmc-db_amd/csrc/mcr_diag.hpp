@@ -539,7 +539,9 @@ __global__ __launch_bounds__(64 * kCombineWaves) void k_diag_combine(const u32* 
         // a HALF of the chain can be constant when the chain is not (a few draws, heavy ties: the one odd draw is the last
         // of an odd-length chain, which the split drops): its squared deviations are exactly zero in the reference
         // (diagnostics.py:196-201 on equal values), and Q - S m is that only up to rounding
-        const bool const0 = constant || !(vmin0 < vmax0), const1 = constant || !(vmin1 < vmax1);
+        // (each half has its own test: `constant` covers the first n draws, the shortest chain's length, and with chains of
+        //  unequal length a half reaches beyond them -- next to a chain of one draw, n = 1, every chain is `constant`)
+        const bool const0 = !(vmin0 < vmax0), const1 = !(vmin1 < vmax1);
         const double m = (n > 0) ? S / (double)n : 0.0;
         const u32* zc = z + off[c];
         double th, tt;

@@ -5,7 +5,8 @@ If the shared library or a HIP device is missing every entry point raises
 
 The summarize plumbing the Python API shares lives here too, once: the fileset reader
 (`Context.summarize_files`), the rolling window over enqueue / wait_one (`pipeline`, `split_result`),
-the reference-shaped per-parameter dicts (`entries`), the ragged-chain route (`ragged_diagnostics`), the CmdStan CSV
+the reference-shaped per-parameter dicts (`entries`), the ragged-chain route (`Context.summarize_chains`,
+`ragged_diagnostics`), the device row order (`Context.chain_layout`), the CmdStan CSV
 decoder (`Context.csv_decode`), the chain-list JSON decoder (`Context.json_decode`) and
 the McrError -> ValueError translation of the reference-compatible functions (`value_errors`).
 """
@@ -68,6 +69,10 @@ class ParquetRequest(C.Structure):
 MCR_PQ_F64, MCR_PQ_I64 = 0, 1
 
 
+class IdColumns(C.Structure):
+    _fields_ = [("chain_dev", C.c_void_p), ("draw_dev", C.c_void_p), ("rows", C.c_int64)]
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int64), ("total_ms", C.c_double)]
 
@@ -84,6 +89,7 @@ SYMBOLS = {
     "mcr_set_workspace_limit": (C.c_int, [C.c_void_p, C.c_size_t]),
     "mcr_rho_guard_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "mcr_plan_chunks": (C.c_int, [C.c_void_p] + [C.c_int64] * 6 + [C.c_int, C.POINTER(C.c_int64)]),
+    "mcr_plan_chunks_chains": (C.c_int, [C.c_void_p, _ip, C.c_int, _I64, C.c_int, C.POINTER(C.c_int64)]),
     "mcr_dev_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "mcr_dev_free": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mcr_memcpy_h2d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -97,6 +103,10 @@ SYMBOLS = {
     "mcr_summarize_wait_one": (C.c_int, [C.c_void_p]),
     "mcr_diagnose_chains": (C.c_int, [C.c_void_p, _dp, _ip, C.c_int, C.c_int, C.POINTER(Summary),
                                       _dp, _dp, _dp, _dp]),
+    "mcr_summarize_chains_enqueue": (C.c_int, [C.c_void_p, C.c_void_p, _I64, _ip, C.c_int, _I64, C.c_int, _dp, C.c_int,
+                                               C.POINTER(Summary)]),
+    "mcr_summarize_chains_dev": (C.c_int, [C.c_void_p, C.c_void_p, _I64, _ip, C.c_int, _I64, C.c_int, _dp, C.c_int,
+                                           C.POINTER(Summary)]),
     "mcr_basic_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _I64, _dp, _dp]),
     "mcr_moments_dev": (C.c_int, [C.c_void_p] + _TENSOR + [_dp, _dp]),
     "mcr_compare": (C.c_int, [C.c_void_p, _dp, _dp, _I64, C.c_double, _dp, C.POINTER(C.c_uint8)]),
@@ -128,6 +138,11 @@ SYMBOLS = {
     "mcr_parquet_page_info": (C.c_int, [C.c_void_p, C.c_int, _ip]),
     "mcr_parquet_decode": (C.c_int, [C.c_void_p, C.POINTER(ParquetRequest), C.c_int]),
     "mcr_gather_rows_dev": (C.c_int, [C.c_void_p, C.c_void_p, _I64, _I64, _ip, C.c_void_p]),
+    "mcr_chain_layout_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _I64, C.c_void_p, _ip, _ip, C.c_int,
+                                       C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "mcr_chain_layout_many_dev": (C.c_int, [C.c_void_p, C.POINTER(IdColumns), C.c_int, _ip, _ip, C.c_int,
+                                            C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "mcr_gather_rows_order_dev": (C.c_int, [C.c_void_p, C.c_void_p, _I64, _I64, C.c_void_p, C.c_void_p]),
     "mcr_summarize_files": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, _dp, C.c_int, C.c_int,
                                       C.POINTER(C.c_void_p)]),
     "mcr_fileset_size": (C.c_int, [C.c_void_p]),
@@ -287,10 +302,13 @@ class DeviceBuffer:
 
 
 class DeviceTensor:
-    """A draw tensor resident in HBM: device buffer + the (dtype, dims, strides) it was uploaded with."""
+    """A draw tensor resident in HBM: device buffer + the (dtype, dims, strides) it was uploaded with.
 
-    def __init__(self, ctx: "Context", buf: DeviceBuffer, targs):
-        self.ctx, self.buf, self.targs = ctx, buf, targs
+    chain_off (int64, C + 1 offsets) marks f64 draws [P][M] whose chains differ in length (Context.ragged_tensor): the
+    calls that take a tensor then use the ragged entry points; targs = (MCR_F64, C, shortest chain, P, 0, 1, stride_p)."""
+
+    def __init__(self, ctx: "Context", buf: DeviceBuffer, targs, chain_off: np.ndarray | None = None):
+        self.ctx, self.buf, self.targs, self.chain_off = ctx, buf, targs, chain_off
 
     @property
     def shape_cnp(self):
@@ -385,6 +403,8 @@ class Context:
         autocovariance kernels are not launched and the diagnostics come back as NaN.
         """
         qs = self._quantiles(quantiles)
+        if isinstance(draws, DeviceTensor) and draws.chain_off is not None:
+            return self.summarize_chains(draws, min_chains=min_chains, quantiles=quantiles, diagnostics=diagnostics)
         if isinstance(draws, DeviceTensor):
             targs, ptr, fn = draws.targs, draws.buf.ptr, self.lib.mcr_summarize_dev
         else:
@@ -402,10 +422,95 @@ class Context:
         qs = self._quantiles(quantiles)
         if bufs is None or bufs.P != t.targs[3] or bufs.nq != qs.size or bufs.diagnostics != diagnostics:
             bufs = SummaryBuffers(t.targs[3], qs.size, diagnostics)
-        self._check(self.lib.mcr_summarize_enqueue(self.handle, t.buf.ptr, *t.targs, int(min_chains), _as_dp(qs),
-                                                   qs.size, C.byref(bufs.struct)))
+        if t.chain_off is not None:
+            rc = self.lib.mcr_summarize_chains_enqueue(self.handle, t.buf.ptr, t.targs[6], _as_ip(t.chain_off), t.targs[1],
+                                                       t.targs[3], int(min_chains), _as_dp(qs), qs.size,
+                                                       C.byref(bufs.struct))
+        else:
+            rc = self.lib.mcr_summarize_enqueue(self.handle, t.buf.ptr, *t.targs, int(min_chains), _as_dp(qs), qs.size,
+                                                C.byref(bufs.struct))
+        self._check(rc)
         self._pending.append(bufs)
         return bufs
+
+    def ragged_tensor(self, buf, counts, P: int, stride_p: int | None = None) -> DeviceTensor:
+        """The DeviceTensor of f64 draws [P][M] already in `buf` whose chains are `counts` draws long, back to back in
+        (chain, draw) order; parameter p starts at element p * stride_p (default M)."""
+        counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+        off = np.concatenate([np.zeros(1, dtype=np.int64), np.cumsum(counts, dtype=np.int64)])
+        M = int(off[-1])
+        n = int(counts.min()) if counts.size else 0
+        return DeviceTensor(self, buf, (MCR_F64, int(counts.size), n, int(P), 0, 1, M if stride_p is None else int(stride_p)),
+                            np.ascontiguousarray(off))
+
+    def summarize_chains(self, draws, counts=None, min_chains: int = 4, quantiles=(0.05, 0.5, 0.95),
+                         diagnostics: bool = True) -> dict:
+        """All per-parameter statistics of draws [P][M] whose chains are `counts` draws long (chains of unequal length,
+        mcr_summarize_chains_dev): ONE pipeline for all parameters.  `draws`: a host array [P][M] (uploaded for the
+        call) or a DeviceTensor of ragged_tensor (then `counts` is not needed).  The result is shaped like
+        summarize()'s: pooled mean / std / q / median, and the diagnostics of diagnostics.py for ragged chains."""
+        qs = self._quantiles(quantiles)
+        owned = None
+        if isinstance(draws, DeviceTensor):
+            t = draws if draws.chain_off is not None else self.ragged_tensor(draws.buf, counts, draws.targs[3])
+        else:
+            x = np.ascontiguousarray(draws, dtype=np.float64)
+            if x.ndim != 2:
+                raise ValueError("draws must be 2-D [P][M]")
+            if int(np.sum(counts)) != x.shape[1]:
+                raise ValueError("counts must add up to the number of draws per parameter")
+            owned = DeviceBuffer(self, max(x.nbytes, 8))
+            if x.nbytes:
+                owned.upload(x)
+            t = self.ragged_tensor(owned, counts, x.shape[0])
+        try:
+            bufs = SummaryBuffers(t.targs[3], qs.size, diagnostics)
+            self._check(self.lib.mcr_summarize_chains_dev(self.handle, t.buf.ptr, t.targs[6], _as_ip(t.chain_off),
+                                                          t.targs[1], t.targs[3], int(min_chains), _as_dp(qs), qs.size,
+                                                          C.byref(bufs.struct)))
+        finally:
+            if owned is not None:
+                owned.free()
+        return bufs.result()
+
+    def chain_layout(self, chain_ptr, draw_ptr, M: int, cap: int = 256, order: "DeviceBuffer | None" = None):
+        """(chain ids, order, counts) of a table's id columns in device memory (mcr_chain_layout_dev): `order` is a
+        DeviceBuffer of M int64 row numbers in np.lexsort((draw, chain)) order -- the caller's `order` buffer (at least
+        8 M bytes) or, without one, a new buffer the caller frees -- or None when the rows are in that order already.
+        None when the library declines (MCR_EFALLBACK: no 64-bit row key) -- sort on the host then."""
+        mine = order is None
+        if mine:
+            order = DeviceBuffer(self, max(int(M) * 8, 8))
+        ids, counts = np.zeros(max(cap, 1), dtype=np.int64), np.zeros(max(cap, 1), dtype=np.int64)
+        n, in_order = C.c_int(0), C.c_int(0)
+        rc = self.lib.mcr_chain_layout_dev(self.handle, chain_ptr, draw_ptr, int(M), order.ptr, _as_ip(ids), _as_ip(counts),
+                                           int(cap), C.byref(n), C.byref(in_order))
+        if rc != MCR_OK or in_order.value:
+            if mine:
+                order.free()
+            order = None
+        if rc == MCR_EFALLBACK:
+            return None
+        self._check(rc)
+        return ids[:n.value].copy(), order, counts[:n.value].copy()
+
+    def chain_layout_many(self, tables, cap: int = 256) -> list:
+        """The in-order test of many tables in one round trip (mcr_chain_layout_many_dev): tables = [(chain pointer,
+        draw pointer, rows), ...] in device memory; per table (chain ids, counts) when its rows are in (chain, draw)
+        order and it has at most `cap` chains, else None -- chain_layout sorts that one."""
+        n = len(tables)
+        arr = (IdColumns * max(n, 1))()
+        for i, (cp, dp, M) in enumerate(tables):
+            arr[i] = IdColumns(cp if isinstance(cp, int) else cp.value, dp if isinstance(dp, int) else dp.value, int(M))
+        ids = np.zeros((max(n, 1), max(cap, 1)), dtype=np.int64)
+        counts = np.zeros((max(n, 1), max(cap, 1)), dtype=np.int64)
+        nch, ino = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
+        self._check(self.lib.mcr_chain_layout_many_dev(self.handle, arr, n, _as_ip(ids), _as_ip(counts), int(cap), nch, ino))
+        return [(ids[i, :nch[i]].copy(), counts[i, :nch[i]].copy()) if ino[i] and nch[i] <= cap else None for i in range(n)]
+
+    def gather_rows_order(self, src_ptr, P: int, M: int, order_ptr, dst_ptr):
+        """dst[p][k] = src[p][order[k]], everything in device memory (mcr_gather_rows_order_dev)."""
+        self._check(self.lib.mcr_gather_rows_order_dev(self.handle, src_ptr, int(P), int(M), order_ptr, dst_ptr))
 
     def summarize_models(self, tensors, min_chains: int = 4, quantiles=(0.05, 0.5, 0.95)) -> list[dict]:
         """One C call for a list of DeviceTensors (independent models), pipelined through the lanes."""
@@ -660,6 +765,9 @@ class Context:
         """Parameters per workspace chunk of a call on this tensor (mcr_plan_chunks): chunk k is [k * n, (k + 1) * n)."""
         _, C_, N, P, sc, sn, sp = t.targs
         v = C.c_int64(0)
+        if t.chain_off is not None:
+            self._check(self.lib.mcr_plan_chunks_chains(self.handle, _as_ip(t.chain_off), C_, P, int(diagnostics), C.byref(v)))
+            return int(v.value)
         self._check(self.lib.mcr_plan_chunks(self.handle, C_, N, P, sc, sn, sp, int(diagnostics), C.byref(v)))
         return int(v.value)
 
@@ -676,16 +784,17 @@ class Context:
         self._check(self.lib.mcr_profile_reset(self.handle))
 
     def profile_get(self) -> dict:
-        arr = (KernelTime * 32)()
+        arr = (KernelTime * 64)()
         n = C.c_int(0)
-        self._check(self.lib.mcr_profile_get(self.handle, arr, 32, C.byref(n)))
+        self._check(self.lib.mcr_profile_get(self.handle, arr, 64, C.byref(n)))
         return {arr[i].name.decode(): {"launches": int(arr[i].launches), "total_ms": float(arr[i].total_ms)}
-                for i in range(min(n.value, 32))}
+                for i in range(min(n.value, 64))}
 
 
 def pipeline(ctx: Context, jobs, owns: bool = False):
     """Rolling window of ctx.enqueue / ctx.wait_one over `jobs`, an iterable of (tag, DeviceTensor, enqueue() keyword
-    arguments) consumed lazily.  Yields (tag, result dict or the McrError of that job's enqueue or wait) in submission
+    arguments) consumed lazily; a tensor with chain_off (Context.ragged_tensor) is a ragged call, and both kinds share
+    the window.  Yields (tag, result dict or the McrError of that job's enqueue or wait) in submission
     order with at most MCR_MAX_INFLIGHT calls outstanding; calls already in flight on `ctx` are waited for first, so
     that every wait_one delivers one of these jobs.  owns=True: the helper frees each tensor once its call is retired.
 
@@ -757,12 +866,13 @@ def entries(r: dict, quantiles=None, diagnostics: bool = True) -> list[dict[str,
 
 
 def ragged_diagnostics(ctx: Context, x: np.ndarray, counts, min_chains: int) -> dict[str, np.ndarray]:
-    """rhat / ess_bulk / ess_tail of every row of x [P][M] whose chains are `counts` draws long, one
-    mcr_diagnose_chains call per parameter (chains of unequal length)."""
-    off = np.concatenate([[0], np.cumsum(counts)])
-    got = [ctx.diagnose_chains([row[off[c]:off[c + 1]] for c in range(len(counts))], min_chains=min_chains)
-           for row in x]
-    return {k: np.array([g[k] for g in got], dtype=np.float64) for k in DIAG_KEYS}
+    """rhat / ess_bulk / ess_tail of every row of x [P][M] whose chains are `counts` draws long (chains of unequal
+    length): one upload and one batched mcr_summarize_chains_dev call."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.shape[0] == 0:
+        return {k: np.empty(0) for k in DIAG_KEYS}
+    r = ctx.summarize_chains(x, counts, min_chains=min_chains, quantiles=())
+    return {k: np.asarray(r[k], dtype=np.float64) for k in DIAG_KEYS}
 
 
 @contextlib.contextmanager

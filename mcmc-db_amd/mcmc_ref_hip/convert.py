@@ -80,7 +80,7 @@ def _compute_diagnostics(table: Any, params: Iterable[str], *, min_chains: int =
     with _ffi.value_errors():
         if np.all(counts == counts[0]):
             r = ctx.summarize(x.reshape(len(params), C, int(counts[0])), "pcn", min_chains=min_chains, quantiles=())
-        else:                                       # ragged chains: one pipeline per parameter
+        else:                                       # ragged chains: one batched call (mcr_summarize_chains_dev)
             r = _ffi.ragged_diagnostics(ctx, x, counts, min_chains)
     return dict(zip(params, _ffi.entries(r)))
 
@@ -303,10 +303,10 @@ def convert_files(jobs, out_draws_dir: Path, out_meta_dir: Path, force: bool = F
     and one download gives the table that is written.  A document the device reader does not certify, and every input
     with reader="host", goes through `_read_json_zip`; both give the same files, meta and exceptions.
 
-    All inputs are read and laid out first, the rectangular models are uploaded and enqueued with a rolling window of
+    All inputs are read and laid out first, the models are uploaded and enqueued with a rolling window of
     MCR_MAX_INFLIGHT calls (consecutive models overlap on the context's lanes; a NaN draw or any other kernel-side
-    failure stays confined to its model), ragged models take the per-parameter route, then the quality gate and the
-    two files of every model are written."""
+    failure stays confined to its model) -- rectangular models and models whose chains differ in length alike, the
+    latter through the ragged entry point -- then the quality gate and the two files of every model are written."""
     import pyarrow.parquet as pq
     out_draws_dir, out_meta_dir = Path(out_draws_dir), Path(out_meta_dir)
     if reader not in ("auto", "host"):
@@ -332,23 +332,27 @@ def convert_files(jobs, out_draws_dir: Path, out_meta_dir: Path, force: bool = F
         except Exception as exc:  # noqa: BLE001 - reported per job
             results[i] = exc
     diags: dict[int, dict] = {}
-    rect, ragged = [], []
-    for i, (_table, params, _nc, _nd, _x, counts) in prepared.items():
+    todo = []                                         # models with parameters, rectangular and ragged, in job order
+    for i, (_table, params, _nc, _nd, _x, _counts) in prepared.items():
         if not params:
             diags[i] = {}
         else:
-            (rect if np.all(counts == counts[0]) else ragged).append(i)
-    ctx = (context or _ffi.default_context()) if rect or ragged else None
+            todo.append(i)
+    ctx = (context or _ffi.default_context()) if todo else None
 
     def calls():
-        for i in rect:
+        for i in todo:
             _table, params, _nc, _nd, x, counts = prepared[i]
             if isinstance(x, _ffi.DeviceTensor):            # read on the device: already resident
                 resident.discard(i)
                 yield i, x, {"min_chains": min_chains, "quantiles": ()}
                 continue
             try:
-                t = ctx.upload(x.reshape(len(params), len(counts), int(counts[0])), "pcn")
+                if np.all(counts == counts[0]):
+                    t = ctx.upload(x.reshape(len(params), len(counts), int(counts[0])), "pcn")
+                else:                                       # chains of unequal length: a ragged call in the same window
+                    xc = np.ascontiguousarray(x, dtype=np.float64)
+                    t = ctx.ragged_tensor(_ffi.DeviceBuffer(ctx, max(xc.nbytes, 8)).upload(xc), counts, len(params))
             except _ffi.McrError as exc:
                 results[i] = ValueError(exc.message)
                 continue
@@ -356,9 +360,9 @@ def convert_files(jobs, out_draws_dir: Path, out_meta_dir: Path, force: bool = F
 
     # anything but a kernel-side failure of one model (an McrError of its own, kept as its result) ends the batch, and
     # the window then leaves nothing in flight and no device tensor allocated behind the exception
-    resident = {i for i in rect if isinstance(prepared[i][4], _ffi.DeviceTensor)}   # not yet handed to the window
+    resident = {i for i in todo if isinstance(prepared[i][4], _ffi.DeviceTensor)}   # not yet handed to the window
     try:
-        if rect:
+        if todo:
             with closing(_ffi.pipeline(ctx, calls(), owns=True)) as done:
                 for i, r in done:
                     if isinstance(r, _ffi.McrError):
@@ -368,12 +372,6 @@ def convert_files(jobs, out_draws_dir: Path, out_meta_dir: Path, force: bool = F
     finally:
         for i in resident:
             prepared[i][4].free()
-    for i in ragged:                                  # chains of unequal length: one pipeline per parameter
-        table, params = prepared[i][:2]
-        try:
-            diags[i] = _compute_diagnostics(table, params, min_chains=min_chains, context=ctx)
-        except Exception as exc:  # noqa: BLE001
-            results[i] = exc
     for i, (table, params, n_chains, n_draws, _x, _counts) in prepared.items():
         if results[i] is not None:
             continue

@@ -122,6 +122,28 @@ def _layout(chain: np.ndarray, draw: np.ndarray):
     return ids, order, counts
 
 
+_LAYOUT_CAP = 256       # distinct chains mcr_chain_layout_dev reports (the library's chain limit); more take the host's np.unique
+
+
+def _device_layout(ctx: "_ffi.Context", chain_ptr, draw_ptr, M: int, order: DeviceBuffer):
+    """`_layout` from id columns in device memory (mcr_chain_layout_dev): (chain ids, `order` filled with the row
+    order or None for rows in order, counts); None when the table is for the host (MCR_EFALLBACK, or more than
+    _LAYOUT_CAP distinct chains)."""
+    try:
+        return ctx.chain_layout(chain_ptr, draw_ptr, M, cap=_LAYOUT_CAP, order=order)
+    except McrError as exc:
+        if exc.code == _ffi.MCR_EINVAL and "distinct chain ids" in exc.message:
+            return None
+        raise
+
+
+def _download(ctx: "_ffi.Context", ptr, dtype, count: int) -> np.ndarray:
+    out = np.empty(count, dtype=dtype)
+    if out.nbytes:
+        ctx._check(ctx.lib.mcr_memcpy_d2h(ctx.handle, out.ctypes.data_as(C.c_void_p), ptr, out.nbytes))
+    return out
+
+
 class _Arena:
     """One device allocation shared by the models of a batch (hipMalloc / hipFree cost ~0.1 ms each, which
     would dominate a 57-file corpus pass); freed when the last view is."""
@@ -148,11 +170,7 @@ class _View:
         self.ptr = C.c_void_p(arena.buf.ptr.value + offset)
 
     def download(self, dtype, count: int) -> np.ndarray:
-        out = np.empty(count, dtype=dtype)
-        if out.nbytes:
-            self.ctx._check(self.ctx.lib.mcr_memcpy_d2h(self.ctx.handle, out.ctypes.data_as(C.c_void_p), self.ptr,
-                                                        out.nbytes))
-        return out
+        return _download(self.ctx, self.ptr, dtype, count)
 
     def free(self):
         if self.arena is not None:
@@ -198,6 +216,7 @@ def read_draws_many(ctx: "_ffi.Context", sources: Sequence, params: Sequence[Ite
         arena = _Arena(ctx, sum(sizes))
         id_rows = sum(f.num_rows for f in files)
         ids_all = DeviceBuffer(ctx, max(2 * id_rows * 8, 8))
+        order_buf = DeviceBuffer(ctx, max(max((f.num_rows for f in files), default=0) * 8, 8))    # one file's row order at a time
         off = ioff = 0
         for f, want, size, cols, (i_chain, i_draw) in zip(files, wants, sizes, colidx, ididx):
             M = f.num_rows
@@ -211,31 +230,53 @@ def read_draws_many(ctx: "_ffi.Context", sources: Sequence, params: Sequence[Ite
             bufs.append(buf)
             off += size
             ioff += 2 * M
+        out = []
         try:
             decode(ctx, reqs)
-            ids_host = ids_all.download(np.int64, 2 * id_rows)
-        except Exception:
+            # nearly every file is in (chain, draw) order: one round trip says so for all of them, and gives their chains
+            ordered = ctx.chain_layout_many([(ids_all.ptr.value + ioff * 8, ids_all.ptr.value + (ioff + M) * 8, M)
+                                             for _want, M, _buf, ioff in plan], cap=_LAYOUT_CAP)
+            for k, (want, M, buf, ioff) in enumerate(plan):
+                chain_ptr = C.c_void_p(ids_all.ptr.value + ioff * 8)
+                draw_ptr = C.c_void_p(ids_all.ptr.value + (ioff + M) * 8)
+                lay = (ordered[k][0], None, ordered[k][1]) if ordered[k] is not None else \
+                    _device_layout(ctx, chain_ptr, draw_ptr, M, order_buf)
+                if lay is None:                              # no 64-bit row key, or very many chains: the host's lexsort
+                    cd = _download(ctx, chain_ptr, np.int64, 2 * M)
+                    chain_ids, order, counts = _layout(cd[:M], cd[M:])
+                    if order is not None and want and M:
+                        dst = DeviceBuffer(ctx, len(want) * M * 8)
+                        bufs[k] = None
+                        order = np.ascontiguousarray(order, dtype=np.int64)
+                        try:
+                            ctx._check(ctx.lib.mcr_gather_rows_dev(ctx.handle, buf.ptr, len(want), M,
+                                                                   order.ctypes.data_as(C.POINTER(C.c_int64)), dst.ptr))
+                        finally:
+                            buf.free()
+                            buf = bufs[k] = dst
+                else:
+                    chain_ids, order, counts = lay           # order: order_buf, or None for rows in order
+                    if order is not None and want and M:
+                        dst = DeviceBuffer(ctx, len(want) * M * 8)
+                        bufs[k] = None
+                        try:
+                            ctx.gather_rows_order(buf.ptr, len(want), M, order.ptr, dst.ptr)
+                        finally:
+                            buf.free()
+                            buf = bufs[k] = dst
+                tensor = None
+                if len(counts) and np.all(counts == counts[0]):
+                    Cn, N = len(counts), int(counts[0])
+                    tensor = DeviceTensor(ctx, buf, (MCR_F64, Cn, N, len(want), N, 1, Cn * N))
+                out.append(DeviceDraws(tensor, buf, want, chain_ids, counts))
+        except BaseException:
             for b in bufs:
-                b.free()
+                if b is not None:
+                    b.free()
             raise
         finally:
             ids_all.free()
-        out = []
-        for want, M, buf, ioff in plan:
-            cd = ids_host[ioff:ioff + 2 * M]
-            chain_ids, order, counts = _layout(cd[:M], cd[M:])
-            if order is not None and want and M:
-                dst = DeviceBuffer(ctx, len(want) * M * 8)
-                order = np.ascontiguousarray(order, dtype=np.int64)
-                ctx._check(ctx.lib.mcr_gather_rows_dev(ctx.handle, buf.ptr, len(want), M,
-                                                       order.ctypes.data_as(C.POINTER(C.c_int64)), dst.ptr))
-                buf.free()
-                buf = dst
-            tensor = None
-            if len(counts) and np.all(counts == counts[0]):
-                Cn, N = len(counts), int(counts[0])
-                tensor = DeviceTensor(ctx, buf, (MCR_F64, Cn, N, len(want), N, 1, Cn * N))
-            out.append(DeviceDraws(tensor, buf, want, chain_ids, counts))
+            order_buf.free()
         return out
     finally:
         for f, o in zip(files, owned):
@@ -296,8 +337,9 @@ def summarize_files(ctx: "_ffi.Context", sources: Sequence, params: Sequence[Ite
     one batched decode, then the models are pipelined through the summarise lanes (rolling window).
 
     diagnostics=False is `Backend.stats` (pooled mean / std / quantiles, any chain structure);
-    diagnostics=True adds rhat / ess_bulk / ess_tail and needs equal-length chains (what
-    `convert._compute_diagnostics` + `Backend.stats` give for the same file).
+    diagnostics=True adds rhat / ess_bulk / ess_tail (what `convert._compute_diagnostics` + `Backend.stats` give
+    for the same file); a model whose chains differ in length is one job of the same window
+    (mcr_summarize_chains_enqueue: statistics and diagnostics of all its parameters from one sort).
     """
     qs = list(quantiles)
     if sources and all(isinstance(s_, (str, os.PathLike)) for s_ in sources) and \
@@ -318,24 +360,29 @@ def summarize_files(ctx: "_ffi.Context", sources: Sequence, params: Sequence[Ite
                 raise ValueError(f"R-hat diagnostics require at least {min_chains} chains; got {len(d.counts)} chain(s)")
             if not diagnostics and M == 0:
                 raise ValueError("cannot compute stats of empty columns")
-            full = diagnostics and d.tensor is not None      # ragged chains: pooled stats here, diagnostics below
-            shape = (len(d.counts), int(d.counts[0])) if full else (1, M)
+            rect = d.tensor is not None
+            # with diagnostics a model's chains shape the call: (C, N) rectangular, the chain lengths when ragged;
+            # Backend.stats alone pools the draws, whatever the chains
+            shape = ((len(d.counts), int(d.counts[0])) if rect else tuple(int(c) for c in d.counts)) if diagnostics else (1, M)
             if jobs and M > 0:
                 j = jobs[-1]
                 last = models[j["first"] + j["count"] - 1]
-                if (k == j["first"] + j["count"] and j["shape"] == shape and j["full"] == full
+                if (k == j["first"] + j["count"] and j["shape"] == shape and j["rect"] == (rect or not diagnostics)
                         and isinstance(d.buf, _View) and isinstance(last.buf, _View)
                         and last.buf.ptr.value + len(last.params) * M * 8 == d.buf.ptr.value):
                     j["count"] += 1
                     j["P"] += P
                     continue
-            jobs.append({"first": k, "count": 1, "shape": shape, "full": full, "P": P, "buf": d.buf})
+            jobs.append({"first": k, "count": 1, "shape": shape, "rect": rect or not diagnostics, "P": P, "buf": d.buf})
 
         def calls():
             for j in jobs:
-                Cn, N = j["shape"]
-                t = DeviceTensor(ctx, j["buf"], (MCR_F64, Cn, N, j["P"], N, 1, Cn * N))
-                yield j, t, {"min_chains": min_chains if j["full"] else 1, "quantiles": qs, "diagnostics": j["full"]}
+                if j["rect"]:
+                    Cn, N = j["shape"]
+                    t = DeviceTensor(ctx, j["buf"], (MCR_F64, Cn, N, j["P"], N, 1, Cn * N))
+                else:                                # chains of unequal length: the same window, the ragged entry point
+                    t = ctx.ragged_tensor(j["buf"], j["shape"], j["P"])
+                yield j, t, {"min_chains": min_chains if diagnostics else 1, "quantiles": qs, "diagnostics": diagnostics}
 
         results = [None] * len(models)
         with _ffi.value_errors(), closing(_ffi.pipeline(ctx, calls())) as done:
@@ -344,17 +391,8 @@ def summarize_files(ctx: "_ffi.Context", sources: Sequence, params: Sequence[Ite
                     raise r
                 k0, k1 = j["first"], j["first"] + j["count"]
                 results[k0:k1] = _ffi.split_result(r, [len(d.params) for d in models[k0:k1]])
-        out = []
-        for d, r in zip(models, results):
-            if r is None:
-                out.append({})
-                continue
-            if diagnostics and d.tensor is None:         # ragged chains: one pipeline per parameter
-                x = d.to_host()
-                with _ffi.value_errors():
-                    r = {**r, **_ffi.ragged_diagnostics(ctx, x, d.counts, min_chains)}
-            out.append(dict(zip(d.params, _ffi.entries(r, qs, diagnostics))))
-        return out
+        return [{} if r is None else dict(zip(d.params, _ffi.entries(r, qs, diagnostics)))
+                for d, r in zip(models, results)]
     finally:
         for d in models:
             d.free()
