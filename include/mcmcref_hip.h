@@ -480,6 +480,55 @@ int mcr_csv_decode(mcr_ctx* ctx, const int* columns, int n_cols, int64_t max_row
 int mcr_parse_double(const char* text, size_t len, double* out);
 
 /* ------------------------------------------------------------------------------------------------
+ * Table CSVs -> device matrix: the table mode of the mcr_csv family.
+ * Replaces pyarrow.csv.read_csv of the reference's convert_file (src/mcmc_ref/convert.py:70-75) for the
+ * subset of its inputs that is certified against it: a header line (the first non-empty line, names raw)
+ * and rows of numbers.  Every line is a data row unless it is empty ("\n\n", "\r\n\r\n"); "\r\n" is a
+ * line end and the last line needs no newline; nothing is dropped for starting with '#'.  Every field
+ * has to match -?(0|[1-9][0-9]*)(\.[0-9]+)?([eE][+-]?[0-9]+)? with nothing around it and is converted
+ * like mcr_parse_double; hard fields are finished on the host and patched in.  A column whose literals
+ * all lack fraction and exponent is one pyarrow types int64 (all_int); -0 is stored as -0.0 and stays
+ * so in a column that ends up double, as with pyarrow; a column that ends up all_int has its -0.0
+ * rewritten to +0.0 before the call returns (int64 has no negative zero).
+ * What leaves the subset ends the call with MCR_EFALLBACK -- the message names the first reason, the
+ * file and the byte offset -- and the caller's host reader decides (it is the source of every
+ * exception): a '"' anywhere, a field outside the grammar (empty, whitespace, '+', leading zeros, .5,
+ * 5., inf, nan, text), an integer literal above 2^53, a row whose field count differs from the header's,
+ * a "\r" without "\n", a non-empty whitespace-only line, a byte-order mark, a duplicated or empty header
+ * name, a non-integer literal in an id column, no header or no data rows.  Limits as for the chain files
+ * (4 GiB of text: MCR_EINVAL).
+ * ---------------------------------------------------------------------------------------------- */
+#define MCR_CSV_T_BOM 1        /* mcr_csv_table_flags: the header conditions that leave the subset */
+#define MCR_CSV_T_DUP_NAME 2
+#define MCR_CSV_T_EMPTY_NAME 4
+#define MCR_CSV_T_QUOTE 8
+#define MCR_CSV_T_CR 16
+#define MCR_CSV_T_NO_HEADER 32
+/* mcr_csv_open / mcr_csv_open_paths in table mode.  The handles work with mcr_csv_close, mcr_csv_num_columns,
+ * mcr_csv_column_name (raw bytes, not stripped), mcr_csv_body_offset and mcr_csv_stage, which counts the rows by the
+ * table rules and answers MCR_EFALLBACK for a flagged header or a file without data rows.  Table files and chain files
+ * do not share a stage call. */
+int mcr_csv_open_table(mcr_ctx* ctx, const void* bytes, size_t len, mcr_csv** out);
+int mcr_csv_open_table_paths(mcr_ctx* ctx, const char* const* paths, int n_paths, mcr_csv** out);
+int mcr_csv_table_flags(const mcr_csv* f); /* MCR_CSV_T_* bits; -1 for NULL or a chain-file handle */
+
+/* Parses the staged table files whole.  columns[f * n_cols + k] = header column of file f stored as output column k
+ * (-1: the file has fewer), id_columns[2 * f] / [2 * f + 1] = its `chain` / `draw` column (-1: absent); every header
+ * column has to be one or the other.  Values go to out_dev[f * stride_file + r * stride_row + k * stride_col];
+ * stride_file = stride_col = 0 asks for the packed layout: file after file, each [its columns][its rows] ([P][M] with
+ * stride_row = 1).  Id fields go as int64 to ids_dev, laid out [file][chain | draw][row] (2 * rows entries per file,
+ * packed).  all_int[f * n_cols + k] (host) = 1 when every literal of the column is an integer.  Rows past max_rows are
+ * not read.  *hard = fields finished on the host. */
+int mcr_csv_decode_table(mcr_ctx* ctx, const int* columns, int n_cols, const int* id_columns, int64_t max_rows,
+                         double* out_dev, int64_t stride_file, int64_t stride_row, int64_t stride_col,
+                         int64_t* ids_dev, uint8_t* all_int, int64_t* hard);
+
+/* The table parser's field routine on the host.  Returns 0 = decided, 1 = hard (*value is then the host finisher's),
+ * MCR_EFALLBACK = text outside the subset or an integer literal above 2^53.
+ * *is_int = the literal has neither fraction nor exponent ("-0": -0.0 with *is_int = 1). */
+int mcr_parse_csv_number(const char* text, size_t len, double* value, int* is_int);
+
+/* ------------------------------------------------------------------------------------------------
  * Chain-list JSON -> device tensor.
  * Replaces json.loads + np.asarray of the JSON-zip reader (src/mcmc_ref/convert.py:78-102) for the
  * inflated text of a `<name>.json.zip` member: [ {"param": [draws...], ...}, ... ], one object per chain.

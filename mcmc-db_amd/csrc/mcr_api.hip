@@ -54,7 +54,7 @@ enum KernelId {
     K_INGEST = 0, K_MOMENTS, K_MOMENTS_FINAL, K_TILE_SORT, K_MERGE, K_ORDER_STATS, K_RANK_Z, K_FOLD_MERGE,
     K_DIAG, K_FINALIZE, K_COMPARE, K_FILL, K_SPLITTERS, K_BUCKET_MERGE, K_ACOV_MORE,
     K_DIAG2, K_ACOV_SEG, K_TWO_SAMPLE, K_COV, K_ZTABLE, K_PQ_SNAPPY, K_PQ_DECODE, K_GATHER, K_ACOV_LONG, K_DIAG_LONG, K_COV_FINAL, K_FFT,
-    K_CSV_LINES, K_CSV_SCAN, K_CSV_PARSE, K_CSV_PATCH,
+    K_CSV_LINES, K_CSV_SCAN, K_CSV_PARSE, K_CSV_PATCH, K_CSV_TABLE_PARSE, K_CSV_UNSIGN_ZERO,
     K_JSON_INDEX, K_JSON_SCAN, K_JSON_PARSE,
     K_LAYOUT_SCAN, K_LAYOUT_KEYS, K_LAYOUT_HIST, K_LAYOUT_OFFSETS, K_LAYOUT_SCATTER, K_LAYOUT_BOUNDS, K_COUNT
 };
@@ -63,7 +63,7 @@ const char* const kKernelNames[K_COUNT] = {
     "k_fold_merge", "k_diag", "k_finalize", "k_compare", "k_fill_synth", "k_splitters",
     "k_bucket_merge", "k_acov_more", "k_diag_combine2", "k_acov_seg", "k_two_sample", "k_cov_mfma", "k_ztable",
     "k_pq_snappy", "k_pq_decode", "k_gather_rows", "k_acov_long", "k_diag_long_scan", "k_cov_final", "k_fft",
-    "k_csv_lines", "k_csv_scan", "k_csv_parse", "k_csv_patch",
+    "k_csv_lines", "k_csv_scan", "k_csv_parse", "k_csv_patch", "k_csv_table_parse", "k_csv_unsign_zero",
     "k_json_index", "k_json_scan", "k_json_parse",
     "k_layout_scan", "k_layout_keys", "k_layout_hist", "k_layout_offsets", "k_layout_scatter", "k_layout_bounds"};
 
@@ -114,6 +114,7 @@ struct mcr_ctx {
     struct CsvFile { size_t img, len, body; int ncols; std::string path; };
     std::vector<CsvFile> csv_files; std::vector<uint32_t> csv_row0;      // staged files, first data row of each (+ total)
     uint64_t csv_staged_gen = 0; bool csv_staged = false;
+    bool csv_table = false;                                              // the staged files are table CSVs (mcr_csv_open_table*)
     size_t csv_row0_off = 0;                                             // file_row0 within csv_tab
     void* csv_tab = nullptr; size_t csv_tab_bytes = 0;                   // FileDesc, chunk -> file, chunk counts / first rows, file_row0
     void* csv_rows = nullptr; size_t csv_rows_bytes = 0;                 // start offset of every data row
@@ -2132,7 +2133,8 @@ int mcr_comm_barrier(mcr_comm* c)
 
 struct mcr_parquet { mcr::pq::File f; };
 // A chain CSV's header.  owner / gen / img: the image is this context's pq_pin + img and already uploaded (mcr_csv_open_paths).
-struct mcr_csv { mcr::csv::Image im; mcr_ctx* owner = nullptr; uint64_t gen = 0; size_t img = 0; };
+// table / tflags / twhere: a table CSV (mcr_csv_open_table*), its MCR_CSV_T_* header flags and the first one's byte offset.
+struct mcr_csv { mcr::csv::Image im; mcr_ctx* owner = nullptr; uint64_t gen = 0; size_t img = 0; bool table = false; int tflags = 0; size_t twhere = 0; };
 
 namespace {
 int ensure_buf(mcr_ctx* ctx, void** p, size_t* cap, size_t bytes)
@@ -2626,6 +2628,7 @@ struct BatchFile {    // a file of mcr_summarize_files: descriptor, image, parse
 struct FileBatch {
     const char* const* paths;
     bool csv = false;                                                // CmdStan chain CSVs (mcr_csv_open_paths), else draws files
+    bool table = false;                                              // csv: table CSVs (mcr_csv_open_table_paths)
     std::vector<BatchFile> f;
     size_t img_total = 0, ids_base = 0, lay_base = 0, lay_out = 0;   // arena: draws, ids, FileIds, chain layouts
     char* arena = nullptr;
@@ -2691,7 +2694,8 @@ int fs_read(mcr_ctx* ctx, FileBatch& B)
                     if (got < m.len) bad(MCR_EINVAL, std::string("short read of ") + B.paths[i]);
                     else if (B.csv) {
                         m.csv = new mcr_csv();
-                        csv::open_image(m.csv->im, pin + m.img, m.len);
+                        if (B.table) { m.csv->table = true; m.csv->tflags = csv::open_table_image(m.csv->im, pin + m.img, m.len, &m.csv->twhere); }
+                        else csv::open_image(m.csv->im, pin + m.img, m.len);
                         m.csv->im.path = B.paths[i];
                     } else {
                         m.pq = new mcr_parquet();
@@ -3016,7 +3020,8 @@ std::string csv_file_name(const mcr_ctx* ctx, size_t f)
 
 extern "C" {
 
-int mcr_csv_open_paths(mcr_ctx* ctx, const char* const* paths, int n_paths, mcr_csv** out)
+namespace {
+int csv_open_paths(mcr_ctx* ctx, const char* const* paths, int n_paths, mcr_csv** out, bool table)
 {
     if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
     if (!out || n_paths < 0 || (n_paths > 0 && !paths)) return fail(ctx, MCR_EINVAL, "bad argument");
@@ -3024,10 +3029,11 @@ int mcr_csv_open_paths(mcr_ctx* ctx, const char* const* paths, int n_paths, mcr_
     try {
         FileBatch B(paths, n_paths);
         B.csv = true;
+        B.table = table;
         ctx->csv_staged = false;
         int rc = fs_open(ctx, B);
         if (rc) return rc;
-        if (B.img_total > kCsvTextMax) return fail(ctx, MCR_EINVAL, "csv: the chain files of one call hold %zu bytes; the limit is 4 GiB", B.img_total);
+        if (B.img_total > kCsvTextMax) return fail(ctx, MCR_EINVAL, "csv: the files of one call hold %zu bytes; the limit is 4 GiB", B.img_total);
         StreamSync uploads{ctx->stream};                      // the handles promise that the text is on the device
         rc = fs_read(ctx, B);
         if (rc) return rc;
@@ -3040,6 +3046,57 @@ int mcr_csv_open_paths(mcr_ctx* ctx, const char* const* paths, int n_paths, mcr_
         }
     } catch (const std::exception& e) { return fail(ctx, MCR_ENOMEM, "csv: host allocation failed: %s", e.what()); }
     return MCR_OK;
+}
+
+// "<file>: <what> (byte <offset within the file>)": the message of a table that goes back to the host reader.
+int table_fallback(mcr_ctx* ctx, const std::string& file, const char* what, size_t byte)
+{
+    return fail(ctx, MCR_EFALLBACK, "csv table: %s: %s (byte %zu)", file.c_str(), what, byte);
+}
+
+const char* table_flag_text(int flags)
+{
+    if (flags & csv::kTabBom) return "a byte-order mark";
+    if (flags & csv::kTabNoHeader) return "no header line";
+    if (flags & csv::kTabHdrQuote) return "a '\"' in the header";
+    if (flags & csv::kTabHdrCr) return "a carriage return without a line feed in the header";
+    if (flags & csv::kTabEmptyName) return "an empty header name";
+    return "a duplicated header name";
+}
+}  // namespace
+
+int mcr_csv_open_paths(mcr_ctx* ctx, const char* const* paths, int n_paths, mcr_csv** out)
+{
+    return csv_open_paths(ctx, paths, n_paths, out, false);
+}
+int mcr_csv_open_table_paths(mcr_ctx* ctx, const char* const* paths, int n_paths, mcr_csv** out)
+{
+    return csv_open_paths(ctx, paths, n_paths, out, true);
+}
+
+int mcr_csv_open_table(mcr_ctx* ctx, const void* bytes, size_t len, mcr_csv** out)
+{
+    if ((!bytes && len) || !out) return fail(ctx, MCR_EINVAL, "NULL argument");     // ctx may be NULL: host only
+    try {
+        std::unique_ptr<mcr_csv> f(new mcr_csv());
+        f->table = true;
+        f->tflags = csv::open_table_image(f->im, (const char*)bytes, len, &f->twhere);
+        *out = f.release();
+    } catch (const std::exception& e) { return fail(ctx, MCR_ENOMEM, "csv: host allocation failed: %s", e.what()); }
+    return MCR_OK;
+}
+int mcr_csv_table_flags(const mcr_csv* f) { return (f && f->table) ? f->tflags : -1; }
+
+int mcr_parse_csv_number(const char* text, size_t len, double* value, int* is_int)
+{
+    if ((!text && len) || !value || !is_int) return MCR_EINVAL;
+    uint64_t bits = 0;
+    bool integer = false;
+    const int rc = csv::table_token(text, len, csv::kPow5, &bits, &integer);
+    *is_int = integer;
+    if (rc == csv::kTabDecided) { memcpy(value, &bits, 8); return 0; }
+    if (rc != csv::kTabHard) return MCR_EFALLBACK;
+    return csv::finish_field(text, len, value) ? 1 : MCR_EFALLBACK;
 }
 
 int mcr_csv_stage(mcr_ctx* ctx, const mcr_csv* const* files, int n_files, int64_t* rows)
@@ -3061,11 +3118,19 @@ int mcr_csv_stage(mcr_ctx* ctx, const mcr_csv* const* files, int n_files, int64_
             }
         }
         if (held && held != n_files) return fail(ctx, MCR_EINVAL, "csv: files read by the library and caller images cannot share a call");
+        const bool table = n_files > 0 && files[0]->table;
+        for (int i = 0; i < n_files; ++i) {
+            if (files[i]->table != table) return fail(ctx, MCR_EINVAL, "csv: table files and chain files cannot share a call");
+            if (table && files[i]->tflags)
+                return table_fallback(ctx, files[i]->im.path.empty() ? "file " + std::to_string(i) : files[i]->im.path,
+                                      table_flag_text(files[i]->tflags), files[i]->twhere);
+        }
+        ctx->csv_table = table;
         ctx->csv_files.assign((size_t)n_files, mcr_ctx::CsvFile());
         if (!held) {                                           // caller images: into the pinned buffer, one upload
             size_t total = 0;
             for (int i = 0; i < n_files; ++i) { ctx->csv_files[(size_t)i].img = total; total = align_up(total + files[i]->im.len, 256); }
-            if (total > kCsvTextMax) return fail(ctx, MCR_EINVAL, "csv: the chain files of one call hold %zu bytes; the limit is 4 GiB", total);
+            if (total > kCsvTextMax) return fail(ctx, MCR_EINVAL, "csv: the files of one call hold %zu bytes; the limit is 4 GiB", total);
             ++ctx->img_gen;
             const int rc = ensure_buf(ctx, &ctx->pq_stage, &ctx->pq_stage_bytes, total + pq::kInWin + 256);
             if (rc) return rc;
@@ -3107,6 +3172,10 @@ int mcr_csv_stage(mcr_ctx* ctx, const mcr_csv* const* files, int n_files, int64_
             HIP_TRY(ctx, hipMemcpyAsync(tb, desc.data(), desc.size() * sizeof(csv::FileDesc), hipMemcpyHostToDevice, st));
             HIP_TRY(ctx, hipMemcpyAsync(d_cfile, chunk_file.data(), (size_t)n_chunks * 4, hipMemcpyHostToDevice, st));
             const char* text = (const char*)ctx->pq_stage;
+            if (table)
+                LAUNCH(ctx, K_CSV_LINES, (csv::k_csv_lines<false, true>), dim3(n_chunks), dim3(csv::kLinesNT), 0, text, d_desc,
+                       (const uint32_t*)d_cfile, d_cnt, (const uint32_t*)d_first, (uint32_t*)nullptr);
+            else
             LAUNCH(ctx, K_CSV_LINES, csv::k_csv_lines<false>, dim3(n_chunks), dim3(csv::kLinesNT), 0, text, d_desc, (const uint32_t*)d_cfile,
                    d_cnt, (const uint32_t*)d_first, (uint32_t*)nullptr);
             LAUNCH(ctx, K_CSV_SCAN, csv::k_csv_scan, dim3(1), dim3(1024), 0, (const uint32_t*)d_cnt, n_chunks, d_first, d_desc,
@@ -3117,6 +3186,10 @@ int mcr_csv_stage(mcr_ctx* ctx, const mcr_csv* const* files, int n_files, int64_
             if (total_rows) {
                 rc = ensure_buf(ctx, &ctx->csv_rows, &ctx->csv_rows_bytes, (size_t)total_rows * 4 + 256);
                 if (rc) return rc;
+                if (table)
+                    LAUNCH(ctx, K_CSV_LINES, (csv::k_csv_lines<true, true>), dim3(n_chunks), dim3(csv::kLinesNT), 0, text, d_desc,
+                           (const uint32_t*)d_cfile, d_cnt, (const uint32_t*)d_first, (uint32_t*)ctx->csv_rows);
+                else
                 LAUNCH(ctx, K_CSV_LINES, csv::k_csv_lines<true>, dim3(n_chunks), dim3(csv::kLinesNT), 0, text, d_desc, (const uint32_t*)d_cfile,
                        d_cnt, (const uint32_t*)d_first, (uint32_t*)ctx->csv_rows);
             }
@@ -3124,6 +3197,8 @@ int mcr_csv_stage(mcr_ctx* ctx, const mcr_csv* const* files, int n_files, int64_
         HIP_TRY(ctx, hipStreamSynchronize(st));
         prof_resolve(ctx);
         for (int i = 0; i < n_files; ++i) rows[i] = (int64_t)(ctx->csv_row0[(size_t)i + 1] - ctx->csv_row0[(size_t)i]);
+        for (int i = 0; table && i < n_files; ++i)
+            if (rows[i] == 0) return table_fallback(ctx, csv_file_name(ctx, (size_t)i), "no data rows", files[i]->im.body);
         ctx->csv_staged = true;
         ctx->csv_staged_gen = ctx->img_gen;
     } catch (const std::exception& e) { return fail(ctx, MCR_ENOMEM, "csv: host allocation failed: %s", e.what()); }
@@ -3138,6 +3213,7 @@ int mcr_csv_decode(mcr_ctx* ctx, const int* columns, int n_cols, int64_t max_row
     if (n_cols < 0 || max_rows < 0 || (n_cols > 0 && !columns) || stride_file < 0 || stride_row < 0 || stride_col < 0)
         return fail(ctx, MCR_EINVAL, "bad argument");
     if (!ctx->csv_staged || ctx->csv_staged_gen != ctx->img_gen) return fail(ctx, MCR_EINVAL, "csv: no staged files (call mcr_csv_stage first)");
+    if (ctx->csv_table) return fail(ctx, MCR_EINVAL, "csv: the staged files are table CSVs (mcr_csv_decode_table reads them)");
     if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "mcr_csv_decode with summaries in flight");
     try {
         const size_t nf = ctx->csv_files.size();
@@ -3229,6 +3305,179 @@ int mcr_csv_decode(mcr_ctx* ctx, const int* columns, int n_cols, int64_t max_row
             HIP_TRY(ctx, hipMemcpyAsync(ax + align_up(nb, 256), val.data(), nb, hipMemcpyHostToDevice, st));
             LAUNCH(ctx, K_CSV_PATCH, csv::k_csv_patch, dim3((unsigned)((list.size() + 255) / 256)), dim3(256), 0, out_dev, (const long long*)ax,
                    (const double*)(ax + align_up(nb, 256)), (uint32_t)list.size());
+            HIP_TRY(ctx, hipStreamSynchronize(st));
+            prof_resolve(ctx);
+        }
+        if (hard) *hard = (int64_t)list.size();
+    } catch (const std::exception& e) { return fail(ctx, MCR_ENOMEM, "csv: host allocation failed: %s", e.what()); }
+    return MCR_OK;
+}
+
+int mcr_csv_decode_table(mcr_ctx* ctx, const int* columns, int n_cols, const int* id_columns, int64_t max_rows, double* out_dev,
+                         int64_t stride_file, int64_t stride_row, int64_t stride_col, int64_t* ids_dev, uint8_t* all_int, int64_t* hard)
+{
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    if (hard) *hard = 0;
+    if (n_cols < 0 || max_rows < 0 || (n_cols > 0 && !columns) || !id_columns || stride_file < 0 || stride_row < 0 || stride_col < 0)
+        return fail(ctx, MCR_EINVAL, "bad argument");
+    if (!ctx->csv_staged || ctx->csv_staged_gen != ctx->img_gen || !ctx->csv_table)
+        return fail(ctx, MCR_EINVAL, "csv: no staged table files (call mcr_csv_open_table_paths and mcr_csv_stage first)");
+    if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "mcr_csv_decode_table with summaries in flight");
+    try {
+        const size_t nf = ctx->csv_files.size();
+        const bool packed = stride_file == 0 && stride_col == 0;
+        std::vector<int> slots;
+        std::vector<csv::TableOut> outs(nf);
+        int64_t rows_eff = 0, at = 0, id_at = 0;
+        bool any_col = false, any_id = false;
+        for (size_t f = 0; f < nf; ++f) {
+            const int nc = ctx->csv_files[f].ncols;
+            const size_t s0 = slots.size();
+            slots.insert(slots.end(), (size_t)nc, -1);
+            int used = 0;
+            for (int k = 0; k < n_cols; ++k) {
+                const int c = columns[f * (size_t)n_cols + (size_t)k];
+                if (c == -1) continue;
+                if (c < 0 || c >= nc) return fail(ctx, MCR_EINVAL, "csv: %s has no column %d", csv_file_name(ctx, f).c_str(), c);
+                if (slots[s0 + (size_t)c] != -1) return fail(ctx, MCR_EINVAL, "csv: column %d of %s is requested twice", c, csv_file_name(ctx, f).c_str());
+                slots[s0 + (size_t)c] = k;
+                used = k + 1;
+            }
+            for (int w = 0; w < 2; ++w) {
+                const int c = id_columns[2 * f + (size_t)w];
+                if (c == -1) continue;
+                if (c < 0 || c >= nc) return fail(ctx, MCR_EINVAL, "csv: %s has no column %d", csv_file_name(ctx, f).c_str(), c);
+                if (slots[s0 + (size_t)c] != -1) return fail(ctx, MCR_EINVAL, "csv: column %d of %s is requested twice", c, csv_file_name(ctx, f).c_str());
+                slots[s0 + (size_t)c] = w ? csv::kSlotDraw : csv::kSlotChain;
+                any_id = true;
+            }
+            for (int c = 0; c < nc; ++c)
+                if (slots[s0 + (size_t)c] == -1)
+                    return fail(ctx, MCR_EINVAL, "csv: column %d of %s is neither requested nor an id column (a table is read whole)", c, csv_file_name(ctx, f).c_str());
+            const int64_t rows = std::min<int64_t>(max_rows, (int64_t)(ctx->csv_row0[f + 1] - ctx->csv_row0[f]));
+            csv::TableOut& o = outs[f];
+            o.rows = rows; o.sr = packed ? 1 : stride_row; o.sc = packed ? rows : stride_col;
+            o.base = packed ? at : (int64_t)f * stride_file;
+            o.ids = id_at;
+            at += (int64_t)used * rows; id_at += 2 * rows;
+            any_col |= used > 0;
+            rows_eff = std::max(rows_eff, rows);
+        }
+        if (rows_eff == 0 || nf == 0) return MCR_OK;
+        if (any_col && !out_dev) return fail(ctx, MCR_EINVAL, "out_dev is NULL");
+        if (any_id && !ids_dev) return fail(ctx, MCR_EINVAL, "ids_dev is NULL");
+        if (n_cols > 0 && !all_int) return fail(ctx, MCR_EINVAL, "all_int is NULL");
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        hipStream_t st = ctx->stream;
+        if (!ctx->csv_pow5) {
+            HIP_TRY(ctx, hipMalloc(&ctx->csv_pow5, sizeof(csv::kPow5)));
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->csv_pow5, csv::kPow5, sizeof(csv::kPow5), hipMemcpyHostToDevice, st));
+        }
+        const char* tb = (const char*)ctx->csv_tab;          // as mcr_csv_stage carved it: descriptors first
+        const size_t o_row0 = ctx->csv_row0_off;
+        uint32_t h_count = 0;
+        unsigned long long h_err = ~0ull;
+        std::vector<csv::HardField> list;
+        std::vector<uint8_t> flags(2 * slots.size());       // all_int, then neg_zero
+        for (int pass = 0; pass < 2; ++pass) {                 // a hard list that overflows: once more with one that fits
+            const size_t o_outs = align_up(slots.size() * 4, 256), o_int = o_outs + align_up(nf * sizeof(csv::TableOut), 256),
+                         o_hard = o_int + align_up(2 * slots.size(), 256),
+                         o_ctr = o_hard + align_up((size_t)ctx->csv_hard_cap * sizeof(csv::HardField), 256);
+            const int rc = ensure_buf(ctx, &ctx->csv_aux, &ctx->csv_aux_bytes, o_ctr + 256);
+            if (rc) return rc;
+            char* ax = (char*)ctx->csv_aux;
+            HIP_TRY(ctx, hipMemcpyAsync(ax, slots.data(), slots.size() * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(ctx, hipMemcpyAsync(ax + o_outs, outs.data(), nf * sizeof(csv::TableOut), hipMemcpyHostToDevice, st));
+            HIP_TRY(ctx, hipMemsetAsync(ax + o_int, 1, slots.size(), st));
+            HIP_TRY(ctx, hipMemsetAsync(ax + o_int + slots.size(), 0, slots.size(), st));
+            HIP_TRY(ctx, hipMemsetAsync(ax + o_ctr, 0xFF, 8, st));
+            HIP_TRY(ctx, hipMemsetAsync(ax + o_ctr + 8, 0, 8, st));
+            csv::TableArgs a{(const char*)ctx->pq_stage, (const csv::FileDesc*)tb, (const uint32_t*)ctx->csv_rows, (const uint32_t*)(tb + o_row0),
+                             (const int*)ax, (const uint64_t*)ctx->csv_pow5, (const csv::TableOut*)(ax + o_outs), out_dev, (long long*)ids_dev,
+                             (unsigned char*)(ax + o_int), (unsigned char*)(ax + o_int + slots.size()), (csv::HardField*)(ax + o_hard), ctx->csv_hard_cap,
+                             (uint32_t*)(ax + o_ctr + 8), (unsigned long long*)(ax + o_ctr)};
+            LAUNCH(ctx, K_CSV_TABLE_PARSE, csv::k_csv_table_parse, dim3((unsigned)((rows_eff + csv::kParseWaves - 1) / csv::kParseWaves), (unsigned)nf),
+                   dim3(csv::kParseWaves * 64), 0, a);
+            HIP_TRY(ctx, hipMemcpyAsync(&h_err, ax + o_ctr, 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(ctx, hipMemcpyAsync(&h_count, ax + o_ctr + 8, 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(ctx, hipMemcpyAsync(flags.data(), ax + o_int, 2 * slots.size(), hipMemcpyDeviceToHost, st));
+            HIP_TRY(ctx, hipStreamSynchronize(st));
+            if (h_count <= ctx->csv_hard_cap) {
+                list.resize(h_count);
+                if (h_count) HIP_TRY(ctx, hipMemcpy(list.data(), ax + o_hard, (size_t)h_count * sizeof(csv::HardField), hipMemcpyDeviceToHost));
+                break;
+            }
+            ctx->csv_hard_cap = h_count + (h_count >> 3);
+        }
+        prof_resolve(ctx);
+        const char* pin = (const char*)ctx->pq_pin;
+        if (h_err != ~0ull) {                                  // the first byte that leaves the subset: the host reader's file
+            const size_t off = (size_t)(h_err >> 4);
+            size_t f = 0;
+            while (f + 1 < nf && ctx->csv_files[f + 1].img <= off) ++f;
+            const mcr_ctx::CsvFile& c = ctx->csv_files[f];
+            const int kind = (int)(h_err & 15);
+            size_t ls = off, le = off;                         // the line around it
+            while (ls > c.img && pin[ls - 1] != '\n') --ls;
+            while (le < c.img + c.len && pin[le] != '\n') ++le;
+            bool blank = true, cr = false;
+            for (size_t i = ls; i < le; ++i) {
+                blank = blank && (pin[i] == ' ' || (pin[i] >= '\t' && pin[i] <= '\r'));
+                cr = cr || (pin[i] == '\r' && i + 1 < le);
+            }
+            if (le == c.img + c.len && le > ls && pin[le - 1] == '\r') cr = true;     // a "\r" that ends the file
+            size_t fe = off;                                   // the field that starts at `off` (a quoted one fails the grammar first)
+            while (fe < le && pin[fe] != ',') ++fe;
+            const void* q = kind == csv::kTabErrQuote ? nullptr : memchr(pin + off, '"', fe - off);
+            if (q) return table_fallback(ctx, csv_file_name(ctx, f), "a '\"'", (size_t)((const char*)q - pin) - c.img);
+            const char* what = kind == csv::kTabErrQuote ? "a '\"'"
+                : cr ? "a carriage return without a line feed"
+                : blank ? "a whitespace-only line"
+                : kind == csv::kTabErrFields ? "a row whose field count differs from the header's"
+                : kind == csv::kTabErrBigInt ? "an integer literal above 2^53"
+                : kind == csv::kTabErrIdField ? "a non-integer literal in an id column"
+                : "a field outside the number grammar";
+            return table_fallback(ctx, csv_file_name(ctx, f), what, off - c.img);
+        }
+        std::vector<size_t> slot_base(nf, 0);
+        bool unsign = false;
+        for (size_t f = 1; f < nf; ++f) slot_base[f] = slot_base[f - 1] + (size_t)ctx->csv_files[f - 1].ncols;
+        if (!list.empty()) {                                  // the host finishes them: strtod on the pinned image, one upload, one scatter
+            std::vector<long long> idx(list.size());
+            std::vector<double> val(list.size());
+            for (size_t i = 0; i < list.size(); ++i) {
+                const csv::HardField& h = list[i];
+                if (!csv::finish_field(pin + h.off, h.len, &val[i]))      // (cannot happen: the device checked the grammar)
+                    return table_fallback(ctx, csv_file_name(ctx, h.file), "a field outside the number grammar", h.off - ctx->csv_files[h.file].img);
+                const csv::TableOut& o = outs[h.file];
+                idx[i] = o.base + (long long)h.row * o.sr + (long long)h.slot * o.sc;
+            }
+            const size_t nb = list.size() * 8;
+            const int rc = ensure_buf(ctx, &ctx->csv_aux, &ctx->csv_aux_bytes, 2 * align_up(nb, 256));
+            if (rc) return rc;
+            char* ax = (char*)ctx->csv_aux;
+            HIP_TRY(ctx, hipMemcpyAsync(ax, idx.data(), nb, hipMemcpyHostToDevice, st));
+            HIP_TRY(ctx, hipMemcpyAsync(ax + align_up(nb, 256), val.data(), nb, hipMemcpyHostToDevice, st));
+            LAUNCH(ctx, K_CSV_PATCH, csv::k_csv_patch, dim3((unsigned)((list.size() + 255) / 256)), dim3(256), 0, out_dev, (const long long*)ax,
+                   (const double*)(ax + align_up(nb, 256)), (uint32_t)list.size());
+            HIP_TRY(ctx, hipStreamSynchronize(st));
+            prof_resolve(ctx);
+        }
+        for (size_t f = 0; f < nf && n_cols > 0; ++f) {
+            for (int k = 0; k < n_cols; ++k) all_int[f * (size_t)n_cols + (size_t)k] = 0;
+            for (int c = 0; c < ctx->csv_files[f].ncols; ++c) {
+                const int k = slots[slot_base[f] + (size_t)c];
+                if (k < 0) continue;
+                all_int[f * (size_t)n_cols + (size_t)k] = flags[slot_base[f] + (size_t)c];
+                if (flags[slot_base[f] + (size_t)c] && flags[slots.size() + slot_base[f] + (size_t)c] && outs[f].rows > 0) {   // an int64 column: no -0
+                    const csv::TableOut& o = outs[f];
+                    LAUNCH(ctx, K_CSV_UNSIGN_ZERO, csv::k_csv_unsign_zero, dim3((unsigned)((o.rows + 255) / 256)), dim3(256), 0,
+                           out_dev + o.base + (long long)k * o.sc, o.sr, o.rows);
+                    unsign = true;
+                }
+            }
+        }
+        if (unsign) {
             HIP_TRY(ctx, hipStreamSynchronize(st));
             prof_resolve(ctx);
         }

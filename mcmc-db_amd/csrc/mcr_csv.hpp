@@ -9,6 +9,9 @@
 //   k_csv_parse     one wavefront per data row: 64-byte batches, a ballot on ',' gives the field boundaries, a running
 //                   popcount the column, each lane that owns a selected field parses it.
 //   open_image      host: header, body offset and column names of a file image.
+//   table mode      plain table CSVs by pyarrow.csv.read_csv's rules, as far as they are certified: table_token (the
+//                   strict number grammar), k_csv_lines<., true> (every non-empty line is a row), k_csv_table_parse,
+//                   open_table_image.  What leaves the subset is reported, never guessed: the host reader decides.
 //   finish_field    host: the float() grammar (no underscores) + strtod for the fields the device reported hard.
 #pragma once
 
@@ -144,6 +147,44 @@ __host__ __device__ inline int parse_field(const char* p, size_t n, const u64* p
     return 0;
 }
 
+constexpr u64 kMaxExactInt = 1ull << 53;   // integer literals above it leave the certified subset
+constexpr int kTabDecided = 0, kTabHard = 1, kTabNotNumber = -1, kTabBigInt = -2;   // table_token
+
+// -?(0|[1-9][0-9]*)(\.[0-9]+)?([eE][+-]?[0-9]+)? and nothing around it -> the double pyarrow.csv gives the field.
+// kTabDecided: *bits is the value; kTabHard: the dropped digits decide the rounding (the host finishes it);
+// kTabNotNumber: outside the grammar; kTabBigInt: an integer literal above 2^53.  *is_int: no fraction and no
+// exponent; -0 keeps its sign (bits of -0.0).  Like pyarrow, 1e400 is inf and 1e-400 is 0.
+__host__ __device__ inline int table_token(const char* t, size_t m, const u64* pow5, u64* bits, bool* is_int)
+{
+    *is_int = false;
+    size_t k = (m && t[0] == '-') ? 1 : 0;
+    if (k >= m || (unsigned)(t[k] - '0') > 9) return kTabNotNumber;
+    const size_t d0 = k;
+    u64 mag = 0;
+    if (t[k] == '0') ++k;
+    else for (; k < m && (unsigned)(t[k] - '0') <= 9; ++k) if (k - d0 < 17) mag = mag * 10 + (u64)(t[k] - '0');
+    const size_t int_digits = k - d0;
+    bool integer = true;
+    if (k < m && t[k] == '.') {
+        integer = false;
+        const size_t f0 = ++k;
+        while (k < m && (unsigned)(t[k] - '0') <= 9) ++k;
+        if (k == f0) return kTabNotNumber;
+    }
+    if (k < m && (t[k] == 'e' || t[k] == 'E')) {
+        integer = false;
+        ++k;
+        if (k < m && (t[k] == '+' || t[k] == '-')) ++k;
+        const size_t x0 = k;
+        while (k < m && (unsigned)(t[k] - '0') <= 9) ++k;
+        if (k == x0) return kTabNotNumber;
+    }
+    if (k != m) return kTabNotNumber;
+    *is_int = integer;
+    if (integer && (int_digits > 16 || mag > kMaxExactInt)) return kTabBigInt;      // 17 digits: at least 10^16 > 2^53
+    return parse_field(t, m, pow5, bits) == 0 ? kTabDecided : kTabHard;
+}
+
 // ---- device side ------------------------------------------------------------------------------------------------
 
 struct FileDesc {       // absolute byte offsets into the call's text buffer (all files back to back, 256-byte aligned)
@@ -166,6 +207,13 @@ __device__ inline bool data_row(const char* text, u32 s, u32 end)
     return s < end && text[s] != '\n';
 }
 
+// Table mode: every line is a data row unless it is empty ("\n" or "\r\n" right at its start).
+__device__ inline bool table_row(const char* text, u32 s, u32 end)
+{
+    if (text[s] == '\n') return false;
+    return !(text[s] == '\r' && s + 1 < end && text[s + 1] == '\n');
+}
+
 template <int NT> __device__ inline u32 block_scan_excl(u32 v, u32* sh, u32* total)
 {
     const int t = threadIdx.x;
@@ -185,8 +233,8 @@ template <int NT> __device__ inline u32 block_scan_excl(u32 v, u32* sh, u32* tot
 
 // Every '\n' at p, body - 1 <= p < end - 1, starts a line at p + 1 (the header's own newline starts the first one), and
 // the thread that holds the newline owns that line.  WRITE = false: counts[chunk] = data rows owned by the chunk;
-// WRITE = true: their start offsets go to rowtab[chunk_first[chunk] ...] in text order.
-template <bool WRITE>
+// WRITE = true: their start offsets go to rowtab[chunk_first[chunk] ...] in text order.  TABLE: table_row decides.
+template <bool WRITE, bool TABLE = false>
 __global__ __launch_bounds__(kLinesNT) void k_csv_lines(const char* __restrict__ text, const FileDesc* __restrict__ files,
                                                         const u32* __restrict__ chunk_file, u32* __restrict__ counts,
                                                         const u32* __restrict__ chunk_first, u32* __restrict__ rowtab)
@@ -206,7 +254,8 @@ __global__ __launch_bounds__(kLinesNT) void k_csv_lines(const char* __restrict__
                 if (((x - 0x01010101u) & ~x & 0x80808080u) == 0) continue;  // no '\n' in these four bytes
                 for (int b = 0; b < 4; ++b) {
                     const u32 p = pos0 + v * 16 + j * 4 + b;
-                    if (((wds[j] >> (8 * b)) & 0xFF) == '\n' && p + 1 >= f.body && p + 1 < f.end && data_row(text, p + 1, f.end))
+                    if (((wds[j] >> (8 * b)) & 0xFF) == '\n' && p + 1 >= f.body && p + 1 < f.end &&
+                        (TABLE ? table_row(text, p + 1, f.end) : data_row(text, p + 1, f.end)))
                         starts |= 1ull << (v * 16 + j * 4 + b);
                 }
             }
@@ -308,6 +357,100 @@ __global__ void k_csv_patch(double* __restrict__ out, const long long* __restric
     if (i < n) out[idx[i]] = val[i];
 }
 
+// ---- table mode ---------------------------------------------------------------------------------------------------
+
+// Why a table leaves the certified subset: low bits of the error key (byte offset << 4 | kind), smallest offset wins.
+constexpr int kTabErrFields = 1, kTabErrQuote = 2, kTabErrField = 3, kTabErrBigInt = 4, kTabErrIdField = 5;
+constexpr int kSlotChain = -2, kSlotDraw = -3;   // slot table entries of the id columns (>= 0: a parameter's output column)
+
+struct TableOut {       // where file f's values go
+    long long base, sr, sc;     // out[base + row * sr + k * sc]
+    long long ids;              // ids[ids + which * rows + row], which = 0 chain, 1 draw
+    long long rows;             // rows of the file that are parsed
+};
+struct TableArgs {
+    const char* text; const FileDesc* files; const u32* rowtab; const u32* file_row0; const int* slots; const u64* pow5;
+    const TableOut* outs; double* out; long long* ids;
+    unsigned char *all_int, *neg_zero;      // [slot0 + header column]: start 1 / 0; neg_zero: the integer literal -0 occurs
+    HardField* hard; u32 hard_cap; u32* hard_count; unsigned long long* err;
+};
+
+// k_csv_parse's geometry (one wavefront per row, 64-byte batches, the lane at a field's leading comma parses it) by the
+// table rules: EVERY field has to be a number of the strict grammar, a "\r" in front of the row's "\n" belongs to the
+// line end, id columns are stored as int64, and a literal with a fraction or an exponent clears its column's all_int byte
+// (every lane stores the same 0).  Anything else sets the error key and the host reader gets the file.
+__global__ __launch_bounds__(kParseWaves * 64) void k_csv_table_parse(const TableArgs a)
+{
+    const u32 fi = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * kParseWaves + (threadIdx.x >> 6);
+    const TableOut o = a.outs[fi];
+    if (row >= o.rows) return;
+    const u32 r0 = a.file_row0[fi];
+    const FileDesc f = a.files[fi];
+    const int* slot = a.slots + f.slot0;
+    const u32 start = a.rowtab[r0 + (u32)row];
+    u32 pos = start - 1;
+    int col = -1;
+    bool first = true;
+    for (;;) {
+        const u32 at = pos + lane;
+        const char c = at < f.end ? a.text[at] : '\n';
+        u64 comma = __ballot(c == ','), nl = __ballot(c == '\n'), quote = __ballot(c == '"');
+        if (first) { comma |= 1; nl &= ~1ull; quote &= ~1ull; first = false; }
+        const u64 term = nl & (0 - nl);                 // the row's terminator, if it is in this batch
+        const u64 inrow = term ? term - 1 : ~0ull;
+        comma &= inrow;
+        quote &= inrow;                                 // (the fields around it are still parsed: an earlier reason wins)
+        if (quote && lane == 0) atomicMin(a.err, ((unsigned long long)(pos + (u32)__ffsll((long long)quote) - 1) << 4) | kTabErrQuote);
+        if ((comma >> lane) & 1) {
+            const int mycol = col + 1 + __popcll(comma & ((1ull << lane) - 1));
+            if (mycol < (int)f.ncols) {
+                const int k = slot[mycol];
+                const u32 s = at + 1;
+                const u64 after = (comma | term) & ~((2ull << lane) - 1);
+                u32 e;
+                if (after) e = pos + (u32)__ffsll((long long)after) - 1;
+                else for (e = pos + 64; e < f.end && a.text[e] != ',' && a.text[e] != '\n'; ++e) {}
+                u32 n = e - s;
+                if (n && e < f.end && a.text[e] == '\n' && a.text[e - 1] == '\r') --n;     // "\r\n" ends the row
+                u64 bits = 0;
+                bool is_int = false;
+                const int rc = table_token(a.text + s, n, a.pow5, &bits, &is_int);
+                if (rc < 0) {
+                    const int kind = rc == kTabBigInt ? kTabErrBigInt : kTabErrField;
+                    atomicMin(a.err, ((unsigned long long)s << 4) | kind);
+                } else if (k >= 0) {
+                    if (!is_int) a.all_int[f.slot0 + mycol] = 0;
+                    else if (bits == 1ull << 63) a.neg_zero[f.slot0 + mycol] = 1;
+                    if (rc == kTabDecided) {
+                        a.out[o.base + row * o.sr + (long long)k * o.sc] = __longlong_as_double((long long)bits);
+                    } else {
+                        const u32 h = atomicAdd(a.hard_count, 1u);
+                        if (h < a.hard_cap) a.hard[h] = HardField{fi, (u32)row, (u32)k, s, n};
+                    }
+                } else if (!is_int) {                   // (an integer literal is never hard)
+                    atomicMin(a.err, ((unsigned long long)s << 4) | kTabErrIdField);
+                } else {
+                    a.ids[o.ids + (k == kSlotDraw ? o.rows : 0) + row] = (long long)__longlong_as_double((long long)bits);
+                }
+            }
+        }
+        col += __popcll(comma);
+        if (term) break;
+        pos += 64;
+    }
+    if (col + 1 != (int)f.ncols && lane == 0) atomicMin(a.err, ((unsigned long long)start << 4) | kTabErrFields);
+}
+
+// out[i * stride] = +0.0 where it is -0.0, i < n: a column of integer literals only is one pyarrow types int64, which
+// has no negative zero, so the resident draws of such a column carry none either.
+__global__ void k_csv_unsign_zero(double* __restrict__ out, long long stride, long long n)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && __double_as_longlong(out[i * stride]) == (long long)(1ull << 63)) out[i * stride] = 0.0;
+}
+
 // ---- host side --------------------------------------------------------------------------------------------------
 
 struct Image {
@@ -342,6 +485,40 @@ inline void open_image(Image& im, const char* bytes, size_t len)
         }
         s = nl ? e + 1 : len;
     }
+}
+
+// Table mode: header conditions that leave the certified subset (MCR_CSV_T_*).
+constexpr int kTabBom = 1, kTabDupName = 2, kTabEmptyName = 4, kTabHdrQuote = 8, kTabHdrCr = 16, kTabNoHeader = 32;
+
+// pyarrow.csv.read_csv's header: the first non-empty line ("\n" and "\r\n" lines are skipped), split on ',', the names
+// raw.  Returns the kTab* flags; *where = byte offset of the first flagged condition.
+inline int open_table_image(Image& im, const char* bytes, size_t len, size_t* where)
+{
+    im.bytes = bytes; im.len = len; im.body = len; im.names.clear();
+    *where = 0;
+    int flags = 0;
+    if (len >= 3 && (unsigned char)bytes[0] == 0xEF && (unsigned char)bytes[1] == 0xBB && (unsigned char)bytes[2] == 0xBF) flags |= kTabBom;
+    size_t s = 0;
+    while (s < len && (bytes[s] == '\n' || (bytes[s] == '\r' && s + 1 < len && bytes[s + 1] == '\n'))) s += bytes[s] == '\n' ? 1 : 2;
+    if (s >= len) return flags | kTabNoHeader;
+    const char* nl = (const char*)memchr(bytes + s, '\n', len - s);
+    size_t e = nl ? (size_t)(nl - bytes) : len;
+    im.body = nl ? e + 1 : len;
+    if (nl && e > s && bytes[e - 1] == '\r') --e;
+    auto flag = [&](int bit, size_t at) { if (!flags) *where = at; flags |= bit; };
+    if (const void* q = memchr(bytes + s, '"', e - s)) flag(kTabHdrQuote, (size_t)((const char*)q - bytes));
+    if (const void* r = memchr(bytes + s, '\r', e - s)) flag(kTabHdrCr, (size_t)((const char*)r - bytes));
+    for (size_t a = s;;) {
+        const char* cm = (const char*)memchr(bytes + a, ',', e - a);
+        const size_t b = cm ? (size_t)(cm - bytes) : e;
+        std::string name(bytes + a, b - a);
+        if (name.empty()) flag(kTabEmptyName, a);
+        else for (const std::string& x : im.names) if (x == name) { flag(kTabDupName, a); break; }
+        im.names.push_back(std::move(name));
+        if (!cm) break;
+        a = b + 1;
+    }
+    return flags;
 }
 
 // A field the parser left: Python float()'s grammar without underscores -- a decimal, or signed inf / infinity / nan

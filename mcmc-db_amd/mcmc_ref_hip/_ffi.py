@@ -165,6 +165,12 @@ SYMBOLS = {
     "mcr_csv_stage": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, _ip]),
     "mcr_csv_decode": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, _I64, C.c_void_p, _I64, _I64, _I64, _ip]),
     "mcr_parse_double": (C.c_int, [C.c_char_p, C.c_size_t, _dp]),
+    "mcr_csv_open_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    "mcr_csv_open_table_paths": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_void_p)]),
+    "mcr_csv_table_flags": (C.c_int, [C.c_void_p]),
+    "mcr_csv_decode_table": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), _I64, C.c_void_p, _I64, _I64,
+                                       _I64, C.c_void_p, C.POINTER(C.c_uint8), _ip]),
+    "mcr_parse_csv_number": (C.c_int, [C.c_char_p, C.c_size_t, _dp, C.POINTER(C.c_int)]),
     "mcr_json_open": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "mcr_json_close": (None, [C.c_void_p]),
     "mcr_json_num_chains": (C.c_int, [C.c_void_p]),
@@ -298,6 +304,48 @@ class DeviceBuffer:
     def free(self):
         if self.ptr:
             self.ctx.lib.mcr_dev_free(self.ctx.handle, self.ptr)
+            self.ptr = C.c_void_p()
+
+
+class DeviceArena:
+    """One device allocation shared by the models of a batch (hipMalloc / hipFree cost ~0.1 ms each, which
+    would dominate a 57-file corpus pass); freed when the last view is."""
+
+    def __init__(self, ctx, nbytes: int):
+        self.buf = DeviceBuffer(ctx, max(nbytes, 8))
+        self.refs = 0
+
+    def view(self, offset: int, nbytes: int) -> "DeviceView":
+        self.refs += 1
+        return DeviceView(self, offset, nbytes)
+
+    def release(self):
+        self.refs -= 1
+        if self.refs <= 0:
+            self.buf.free()
+
+
+class DeviceView:
+    """Slice of an arena with DeviceBuffer's interface (ptr / download / free)."""
+
+    def __init__(self, arena: DeviceArena, offset: int, nbytes: int):
+        self.arena, self.ctx, self.nbytes = arena, arena.buf.ctx, nbytes
+        self.ptr = C.c_void_p(arena.buf.ptr.value + offset)
+
+    def download(self, dtype, count: int) -> np.ndarray:
+        out = np.empty(count, dtype=dtype)
+        if out.nbytes:
+            self.ctx._check(self.ctx.lib.mcr_memcpy_d2h(self.ctx.handle, out.ctypes.data_as(C.c_void_p), self.ptr, out.nbytes))
+        return out
+
+    def share(self) -> "DeviceView":
+        """Another view of the same bytes; the arena lives until both are freed."""
+        return self.arena.view(self.ptr.value - self.arena.buf.ptr.value, self.nbytes)
+
+    def free(self):
+        if self.arena is not None:
+            self.arena.release()
+            self.arena = None
             self.ptr = C.c_void_p()
 
 
@@ -613,6 +661,83 @@ class Context:
                 phases.update(read_upload_ms=(t1 - t0) * 1e3, index_ms=(t2 - t1) * 1e3, parse_finish_ms=(t3 - t2) * 1e3,
                               text_bytes=sum(os.path.getsize(p) for p in paths), hard=int(hard.value))
             return names, t, int(hard.value)
+        finally:
+            for h in hs[:n]:
+                if h:
+                    L.mcr_csv_close(h)
+
+    def csv_table_decode(self, paths, phases: dict | None = None):
+        """Table CSVs -> per file (parameter names in file order without `chain` / `draw`, [P][M] f64 DeviceView in file
+        row order, all_int flags [P], (chain ids, draw ids) as int64 DeviceViews of M entries or None for an absent
+        column, fields finished on the host, header names): ONE read (mcr_csv_open_table_paths), one line index
+        (mcr_csv_stage) and one parse (mcr_csv_decode_table) for all files.  None when the host reader must decide for
+        one of them: the library answers MCR_EFALLBACK or a header is not UTF-8 (`phases["fallback"]` says why).
+        `phases` receives the host clock of the three calls (ms).  Free every slice."""
+        L, n = self.lib, len(paths)
+        note = phases if phases is not None else {}
+        arr = (C.c_char_p * max(n, 1))(*[os.fsencode(p) for p in paths])
+        hs = (C.c_void_p * max(n, 1))()
+        t0 = time.perf_counter()
+        self._check(L.mcr_csv_open_table_paths(self.handle, arr, n, hs))
+
+        def declined(rc: int) -> bool:
+            if rc == MCR_EFALLBACK:
+                note["fallback"] = (L.mcr_last_error(self.handle) or b"").decode(errors="replace")
+                return True
+            self._check(rc)
+            return False
+
+        try:
+            try:
+                heads = [[(L.mcr_csv_column_name(hs[f], c) or b"").decode() for c in range(L.mcr_csv_num_columns(hs[f]))]
+                         for f in range(n)]
+            except UnicodeDecodeError:
+                note["fallback"] = "csv table: a header name is not UTF-8"
+                return None
+            t1 = time.perf_counter()
+            rows = np.zeros(max(n, 1), dtype=np.int64)
+            if declined(L.mcr_csv_stage(self.handle, hs, n, _as_ip(rows))):
+                return None
+            t2 = time.perf_counter()
+            params = [[c for c, name in enumerate(h) if name not in ("chain", "draw")] for h in heads]
+            Pmax = max((len(p) for p in params), default=0)
+            cols = np.full((max(n, 1), max(Pmax, 1)), -1, dtype=np.intc)
+            ids = np.full((max(n, 1), 2), -1, dtype=np.intc)
+            for f, h in enumerate(heads):
+                cols[f, :len(params[f])] = params[f]
+                ids[f] = [h.index("chain") if "chain" in h else -1, h.index("draw") if "draw" in h else -1]
+            all_int = np.zeros((max(n, 1), max(Pmax, 1)), dtype=np.uint8)
+            sizes = [len(params[f]) * int(rows[f]) * 8 for f in range(n)]
+            out = DeviceArena(self, sum(sizes))
+            idb = DeviceArena(self, 2 * int(rows[:n].sum()) * 8)
+            hard = C.c_int64(0)
+            try:
+                fell = declined(L.mcr_csv_decode_table(self.handle, cols.ctypes.data_as(C.POINTER(C.c_int)), cols.shape[1],
+                                                       ids.ctypes.data_as(C.POINTER(C.c_int)), int(rows.max()), out.buf.ptr, 0, 1, 0,
+                                                       idb.buf.ptr, all_int.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(hard)))
+            except BaseException:
+                out.buf.free()
+                idb.buf.free()
+                raise
+            if fell or n == 0:
+                out.buf.free()
+                idb.buf.free()
+                return None if fell else []
+            got, off, ioff = [], 0, 0
+            for f in range(n):
+                M, P = int(rows[f]), len(params[f])
+                pair = [idb.view((ioff + w * M) * 8, M * 8) if ids[f, w] >= 0 else None for w in range(2)]
+                got.append(([heads[f][c] for c in params[f]], out.view(off, sizes[f]),
+                            all_int[f, :P].astype(bool), tuple(pair), int(hard.value), heads[f]))
+                off += sizes[f]
+                ioff += 2 * M
+            if idb.refs == 0:
+                idb.buf.free()
+            if phases is not None:
+                t3 = time.perf_counter()
+                phases.update(read_upload_ms=(t1 - t0) * 1e3, index_ms=(t2 - t1) * 1e3, parse_finish_ms=(t3 - t2) * 1e3,
+                              text_bytes=sum(os.path.getsize(p) for p in paths), hard=int(hard.value))
+            return got
         finally:
             for h in hs[:n]:
                 if h:

@@ -6,7 +6,7 @@ gate fails, provenance-generate exits 1 when any recipe failed); `--backend` acc
 reference's "arrow" / "numpy".  `provenance-scaffold` (Stan programs + data literals), pairs and draws-export
 commands are outside the statistics path and not included.  `cmdstan-summary CHAIN.csv...` is this package's own:
 the chain files of a CmdStan run, parsed on the GPU, printed like `stats --include-diagnostics`; so is
-`json-summary ARCHIVE.json.zip...` for chain-list JSON archives.
+`json-summary ARCHIVE.json.zip...` for chain-list JSON archives and `csv-summary FILE.csv...` for table CSVs.
 """
 from __future__ import annotations
 
@@ -108,6 +108,27 @@ def json_summary_cmd(archives, format_: str, min_chains: int) -> None:
         raise click.ClickException(str(exc)) from exc
     if len(archives) == 1:
         _echo_stats(stats[str(archives[0])], format_)
+    elif format_ == "json":
+        click.echo(json.dumps(stats, indent=2, sort_keys=True))
+    else:
+        for name, st in stats.items():
+            click.echo(f"# {name}")
+            _echo_stats(st, format_)
+
+
+@main.command("csv-summary")
+@click.argument("files", nargs=-1, required=True, type=click.Path(path_type=Path, exists=True, dir_okay=False))
+@click.option("--format", "format_", type=click.Choice(["table", "csv", "json"], case_sensitive=False), default="table")
+@click.option("--min-chains", default=4, type=int)
+def csv_summary_cmd(files, format_: str, min_chains: int) -> None:
+    """Statistics and diagnostics of table CSVs (a header, one row per draw, optional `chain` / `draw` columns), parsed
+    on the GPU (no counterpart in the reference).  Prints like `json-summary`."""
+    try:
+        stats = {str(f): convert_mod.summarize_csv(f, min_chains=min_chains) for f in files}
+    except (ValueError, KeyError, IndexError) as exc:
+        raise click.ClickException(str(exc)) from exc
+    if len(files) == 1:
+        _echo_stats(stats[str(files[0])], format_)
     elif format_ == "json":
         click.echo(json.dumps(stats, indent=2, sort_keys=True))
     else:

@@ -267,6 +267,242 @@ def summarize_json_zip(path: Path, min_chains: int = 4, quantiles=(0.05, 0.5, 0.
     return dict(zip(params, _ffi.entries(r, list(quantiles), diagnostics)))
 
 
+def _csv_draws(ctx, got, note: dict):
+    """One file of Context.csv_table_decode -> (parquet.DeviceDraws, file-order buffer, int flags, header, ids) with the
+    rows put in (chain, draw) order by the device layout code (`parquet._device_layout`, the host's lexsort where that
+    declines, as parquet.read_draws_many does).  A missing `chain` is chain 0 and a missing `draw` the row number
+    (`_ensure_chain_draw`); without both the rows are in order as they stand.  ids: the downloaded (chain, draw) columns or None.  Takes over `got`'s
+    buffers: they are freed here if anything fails."""
+    import ctypes as C
+
+    from . import parquet
+    names, buf, ints, (chain, draw), _hard, header = got
+    P, M = len(names), buf.nbytes // 8 // max(len(names), 1)
+    made, dbuf = [], None
+    try:
+        if not names:
+            M = (chain or draw).nbytes // 8
+        if chain is None and draw is None:
+            chain_ids, order, counts = np.zeros(1, dtype=np.int64), None, np.full(1, M, dtype=np.int64)
+        else:
+            cptr, dptr = (b.ptr if b is not None else None for b in (chain, draw))
+            if cptr is None:                                   # one chain
+                made.append(_ffi.DeviceBuffer(ctx, M * 8).upload(np.zeros(M, dtype=np.int64)))
+                cptr = made[-1].ptr
+            if dptr is None:                                   # file order within each chain: draw = row number
+                made.append(_ffi.DeviceBuffer(ctx, M * 8).upload(np.arange(M, dtype=np.int64)))
+                dptr = made[-1].ptr
+            made.append(_ffi.DeviceBuffer(ctx, M * 8))         # the row order, if the rows need one
+            lay = parquet._device_layout(ctx, cptr, dptr, M, made[-1])
+            if lay is None:                                    # no 64-bit row key, or very many chains
+                note["layout"] = "host"
+                hc = chain.download(np.int64, M) if chain is not None else np.zeros(M, dtype=np.int64)
+                hd = draw.download(np.int64, M) if draw is not None else np.arange(M, dtype=np.int64)
+                chain_ids, order, counts = parquet._layout(hc, hd)
+                if order is not None and P:
+                    order = np.ascontiguousarray(order, dtype=np.int64)
+                    dbuf = _ffi.DeviceBuffer(ctx, P * M * 8)
+                    ctx._check(ctx.lib.mcr_gather_rows_dev(ctx.handle, buf.ptr, P, M, order.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                           dbuf.ptr))
+            else:
+                chain_ids, order, counts = lay
+                if order is not None and P:
+                    dbuf = _ffi.DeviceBuffer(ctx, P * M * 8)
+                    ctx.gather_rows_order(buf.ptr, P, M, order.ptr, dbuf.ptr)
+        ids = tuple(None if b is None else b.download(np.int64, M) for b in (chain, draw))
+        if dbuf is None:
+            dbuf = buf.share()
+        tensor = None
+        if P and len(counts) and np.all(counts == counts[0]):
+            Cn, N = len(counts), int(counts[0])
+            tensor = _ffi.DeviceTensor(ctx, dbuf, (_ffi.MCR_F64, Cn, N, P, N, 1, Cn * N))
+        return parquet.DeviceDraws(tensor, dbuf, names, chain_ids, np.asarray(counts, dtype=np.int64)), buf, [bool(v) for v in ints], header, ids
+    except BaseException:
+        buf.free()
+        if dbuf is not None:
+            dbuf.free()
+        raise
+    finally:
+        for b in made + [chain, draw]:
+            if b is not None:
+                b.free()
+
+
+def read_csv_many_dev(paths, context=None, phases: dict | None = None):
+    """`read_csv_dev` for several files with one read, one line index and one parse (Context.csv_table_decode): a list
+    of (DeviceDraws, file-order buffer, int flags, header names, (chain, draw) id columns or None each), or None when
+    the host reader must decide for one of them (`phases["fallback"]` says why and for which)."""
+    import os
+    note = phases if phases is not None else {}
+    paths = [Path(p) for p in paths]
+    for p in paths:
+        if not os.path.isfile(p):
+            note["fallback"] = f"csv table: {p}: not a file"
+            return None
+    ctx = context if context is not None else _ffi.default_context()
+    with _ffi.value_errors():
+        got = ctx.csv_table_decode([str(p) for p in paths], note)
+    if got is None:
+        return None
+    out = []
+    try:
+        while got:
+            out.append(_csv_draws(ctx, got.pop(0), note))
+    except BaseException:
+        for g in got:
+            for b in (g[1], *g[3]):
+                if b is not None:
+                    b.free()
+        for d, fb, *_ in out:
+            d.free()
+            fb.free()
+        raise
+    return out
+
+
+def read_csv_dev(path: Path, context=None, phases: dict | None = None):
+    """`pyarrow.csv.read_csv` + `table_to_tensor` without the host parse: (parquet.DeviceDraws -- [P][M] in (chain, draw)
+    order, chain ids, counts --, the [P][M] buffer in FILE row order, int_columns) of a table CSV.  The text is read,
+    indexed and converted on the GPU (the table mode of mcr_csv_*), the row order comes from the device layout code.
+    int_columns[p]: every literal of the column is an integer, the column pyarrow types int64.  None when the host
+    reader must decide -- the file is outside the subset the device reader certifies (`phases["fallback"]` says why).
+    Free both the draws and the buffer (they may share memory; either order)."""
+    got = read_csv_many_dev([path], context, phases)
+    if got is None:
+        return None
+    return got[0][:3]
+
+
+def _csv_table(d, flat: np.ndarray, int_columns, header, ids):
+    """The Arrow table `pacsv.read_csv` builds, from the downloaded file-order [P][M] values and id columns."""
+    import pyarrow as pa
+    rows, cols = iter(flat), {}
+    kinds = iter(int_columns)
+    for name in header:
+        if name in ("chain", "draw"):
+            cols[name] = ids[0 if name == "chain" else 1]
+        else:
+            row = next(rows)
+            cols[name] = row.astype(np.int64) if next(kinds) else row
+    return pa.table(cols)
+
+
+def _csv_prepared(ctx, got, min_chains: int):
+    """The `prepared` entry of convert_files for one file of read_csv_many_dev (the draws resident)."""
+    d, fbuf, int_columns, header, ids = got
+    try:
+        P, M = len(d.params), int(d.counts.sum())
+        flat = fbuf.download(np.float64, P * M).reshape(P, M)
+        fbuf.free()
+        fbuf = None
+        table = _ensure_chain_draw(_csv_table(d, flat, int_columns, header, ids))
+        if d.params and len(d.counts) < min_chains:
+            raise ValueError(f"R-hat diagnostics require at least {min_chains} chains; got {len(d.counts)} chain(s)")
+        t = d.tensor if d.rectangular else ctx.ragged_tensor(d.buf, d.counts, P)
+        return table, d.params, int(len(d.counts)), int(d.counts.min()), t, d.counts
+    except BaseException:
+        d.free()
+        if fbuf is not None:
+            fbuf.free()
+        raise
+
+
+_CSV_BATCH_BYTES = 3 << 30     # text of the .csv jobs read by one library call (its limit is 4 GiB less 1 MiB, padding included)
+
+
+def _read_csv_prepared_many(paths, min_chains: int, context) -> dict:
+    """The `.csv` inputs of convert_files through the device reader: {index into paths: `prepared` entry or the
+    exception of the job}; a path that is missing from it takes the host route, which is the source of every exception
+    of the read itself.  The files share one read and one parse, in groups of at most _CSV_BATCH_BYTES of text (the
+    library's limit holds for a call); a file the device reader hands back is named by its message and the group is
+    read again without it; whatever else the library answers for a group (a file it cannot open, no memory, the
+    limit) sends its files through the reader one by one, and a file for which it answers that again to the host."""
+    try:
+        ctx = context or _ffi.default_context()
+    except _ffi.HipUnavailableError:
+        return {}
+
+    def read(group):
+        """read_csv_many_dev of the group, or None with `note` filled; an error of the library is no answer either."""
+        note: dict = {}
+        try:
+            return read_csv_many_dev([paths[i] for i in group], ctx, note), note
+        except (ValueError, _ffi.McrError, OSError) as exc:
+            return None, {"error": str(exc)}
+
+    groups, size = [[]], 0
+    for i, p in enumerate(paths):
+        n = p.stat().st_size if p.is_file() else 0
+        if groups[-1] and size + n > _CSV_BATCH_BYTES:
+            groups.append([])
+            size = 0
+        groups[-1].append(i)
+        size += n
+    got: list = [None] * len(paths)
+    for group in groups:
+        while group:
+            res, note = read(group)
+            if res is not None:
+                for i, g in zip(group, res):
+                    got[i] = g
+                break
+            named = [i for i in group if note.get("fallback", "").startswith(f"csv table: {paths[i]}: ")]
+            if len(named) != 1:                                # not a fallback of one file: each on its own
+                for i in group if len(group) > 1 else []:
+                    got[i] = (read([i])[0] or [None])[0]
+                break
+            group = [i for i in group if i != named[0]]
+    done: dict = {}
+    for i, g in enumerate(got):
+        if g is None:
+            continue
+        if not g[0].params:                                    # only bookkeeping columns: the host route's empty model
+            g[0].free()
+            g[1].free()
+            continue
+        try:
+            done[i] = _csv_prepared(ctx, g, min_chains)
+        except Exception as exc:  # noqa: BLE001 - reported per job
+            done[i] = exc
+    return done
+
+
+def summarize_csv(path: Path, min_chains: int = 4, quantiles=(0.05, 0.5, 0.95), diagnostics: bool = True,
+                  context=None) -> dict[str, dict[str, float]]:
+    """{param: {"mean", "std", "qNN"..., "rhat", "ess_bulk", "ess_tail"}} of a table CSV, the shape
+    `reference.summary_for_model` returns: text to statistics on the GPU, chains of unequal length included.  A file
+    for the host reader is read by it (and raises what it raises) and its tensor uploaded."""
+    import pyarrow.csv as pacsv
+    ctx = context if context is not None else _ffi.default_context()
+    got = read_csv_dev(Path(path), context=ctx)
+    if got is None:
+        table = _ensure_chain_draw(pacsv.read_csv(Path(path)))
+        params = [c for c in table.column_names if c not in {"chain", "draw"}]
+        x, counts = table_to_tensor(table, params)
+        if not params or len(counts) == 0:
+            return {}
+        with _ffi.value_errors():
+            if np.all(counts == counts[0]):
+                t = ctx.upload(x.reshape(len(params), len(counts), int(counts[0])), "pcn")
+            else:
+                xc = np.ascontiguousarray(x, dtype=np.float64)
+                t = ctx.ragged_tensor(_ffi.DeviceBuffer(ctx, max(xc.nbytes, 8)).upload(xc), counts, len(params))
+    else:
+        d, fbuf, _ints = got
+        fbuf.free()
+        params = d.params
+        if not params:
+            d.free()
+            return {}
+        t = d.tensor if d.rectangular else ctx.ragged_tensor(d.buf, d.counts, len(params))
+    try:
+        with _ffi.value_errors():
+            r = ctx.summarize(t, min_chains=min_chains, quantiles=quantiles, diagnostics=diagnostics)
+    finally:
+        t.free()
+    return dict(zip(params, _ffi.entries(r, list(quantiles), diagnostics)))
+
+
 def _read_input(path: Path):
     import pyarrow.csv as pacsv
     if path.suffix == ".csv":
@@ -299,9 +535,10 @@ def convert_files(jobs, out_draws_dir: Path, out_meta_dir: Path, force: bool = F
     a ConvertResult or the exception that `convert_file` would have raised for it (the per-recipe try/except of
     generate.generate_reference_corpus, src/mcmc_ref/generate.py:77-96, becomes per-entry results).
 
-    reader="auto": a `.json.zip` input is parsed on the GPU (`read_json_zip_dev`); its diagnostics run on that tensor
-    and one download gives the table that is written.  A document the device reader does not certify, and every input
-    with reader="host", goes through `_read_json_zip`; both give the same files, meta and exceptions.
+    reader="auto": a `.json.zip` input is parsed on the GPU (`read_json_zip_dev`) and so is a `.csv` input
+    (`read_csv_many_dev`, all of them in one read and one parse); the diagnostics run on that tensor and one download
+    gives the table that is written.  A document the device reader does not certify, and every input with
+    reader="host", goes through `_read_json_zip` / `pyarrow.csv.read_csv`; both give the same files, meta and exceptions.
 
     All inputs are read and laid out first, the models are uploaded and enqueued with a rolling window of
     MCR_MAX_INFLIGHT calls (consecutive models overlap on the context's lanes; a NaN draw or any other kernel-side
@@ -315,7 +552,16 @@ def convert_files(jobs, out_draws_dir: Path, out_meta_dir: Path, force: bool = F
     n = len(jobs)
     results: list = [None] * n
     prepared: dict[int, tuple] = {}
+    csv_jobs = [i for i, (p, _name) in enumerate(jobs) if reader == "auto" and Path(p).suffix == ".csv"]
+    csv_done = _read_csv_prepared_many([Path(jobs[i][0]) for i in csv_jobs], min_chains, context) if csv_jobs else {}
+    for k, got in csv_done.items():
+        if isinstance(got, Exception):
+            results[csv_jobs[k]] = got
+        else:
+            prepared[csv_jobs[k]] = got
     for i, (input_path, _name) in enumerate(jobs):
+        if i in prepared or results[i] is not None:
+            continue
         try:
             if reader == "auto" and _is_json_zip(Path(input_path)):
                 got = _read_json_zip_prepared(Path(input_path), min_chains, context)
@@ -331,6 +577,7 @@ def convert_files(jobs, out_draws_dir: Path, out_meta_dir: Path, force: bool = F
             prepared[i] = (table, params, n_chains, n_draws, x, counts)
         except Exception as exc:  # noqa: BLE001 - reported per job
             results[i] = exc
+    prepared = dict(sorted(prepared.items()))               # job order, whichever reader prepared a job
     diags: dict[int, dict] = {}
     todo = []                                         # models with parameters, rectangular and ragged, in job order
     for i, (_table, params, _nc, _nd, _x, _counts) in prepared.items():

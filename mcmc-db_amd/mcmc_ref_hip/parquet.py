@@ -144,39 +144,7 @@ def _download(ctx: "_ffi.Context", ptr, dtype, count: int) -> np.ndarray:
     return out
 
 
-class _Arena:
-    """One device allocation shared by the models of a batch (hipMalloc / hipFree cost ~0.1 ms each, which
-    would dominate a 57-file corpus pass); freed when the last view is."""
-
-    def __init__(self, ctx, nbytes: int):
-        self.buf = DeviceBuffer(ctx, max(nbytes, 8))
-        self.refs = 0
-
-    def view(self, offset: int, nbytes: int) -> "_View":
-        self.refs += 1
-        return _View(self, offset, nbytes)
-
-    def release(self):
-        self.refs -= 1
-        if self.refs <= 0:
-            self.buf.free()
-
-
-class _View:
-    """Slice of an arena with DeviceBuffer's interface (ptr / download / free)."""
-
-    def __init__(self, arena: _Arena, offset: int, nbytes: int):
-        self.arena, self.ctx, self.nbytes = arena, arena.buf.ctx, nbytes
-        self.ptr = C.c_void_p(arena.buf.ptr.value + offset)
-
-    def download(self, dtype, count: int) -> np.ndarray:
-        return _download(self.ctx, self.ptr, dtype, count)
-
-    def free(self):
-        if self.arena is not None:
-            self.arena.release()
-            self.arena = None
-            self.ptr = C.c_void_p()
+_Arena, _View = _ffi.DeviceArena, _ffi.DeviceView      # one allocation shared by the models of a batch, and its slices
 
 
 class DeviceDraws:
