@@ -3016,6 +3016,95 @@ std::string csv_file_name(const mcr_ctx* ctx, size_t f)
     const std::string& p = ctx->csv_files[f].path;
     return p.empty() ? "file " + std::to_string(f) : p;
 }
+
+// ---- what the text decoders share (mcr_csv_decode, mcr_csv_decode_table, mcr_json_decode) ---------------------------
+
+int ensure_pow5(mcr_ctx* ctx)
+{
+    if (ctx->csv_pow5) return MCR_OK;
+    HIP_TRY(ctx, hipMalloc(&ctx->csv_pow5, sizeof(csv::kPow5)));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->csv_pow5, csv::kPow5, sizeof(csv::kPow5), hipMemcpyHostToDevice, ctx->stream));
+    return MCR_OK;
+}
+
+// carve_ws for one of the ingest buffers: measures the layout, makes *buf that large, then carves it.
+template <class Layout> int carve_buf(mcr_ctx* ctx, void** buf, size_t* cap, Layout&& layout)
+{
+    Carve m{nullptr};
+    layout(m);
+    const int rc = ensure_buf(ctx, buf, cap, m.off);
+    if (rc) return rc;
+    Carve cv{(char*)*buf, *cap};
+    layout(cv);
+    return MCR_OK;
+}
+
+// One parse with a hard list of Rec (csv::HardField, json::HardToken) in csv_aux, and once more with a list that fits
+// when the first overflows.  layout(cv) takes the decoder's own tables in front of the list (it runs twice per pass,
+// measuring and carving, so it only takes); fill() enqueues their uploads and initial values; launch(hard, cap, count,
+// err) enqueues the kernel and the read-back of the decoder's flags.  Hands back the list and the error key (~0: none).
+template <class Rec, class Layout, class Fill, class Launch>
+int hard_pass(mcr_ctx* ctx, std::vector<Rec>& list, unsigned long long* err, Layout&& layout, Fill&& fill, Launch&& launch)
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    int rc = ensure_pow5(ctx);
+    for (int pass = 0; pass < 2 && !rc; ++pass) {
+        const uint32_t cap = ctx->csv_hard_cap;
+        Rec* d_hard = nullptr;
+        unsigned long long* d_ctr = nullptr;                  // [0] the error key, smallest wins; [1] the hard count
+        rc = carve_buf(ctx, &ctx->csv_aux, &ctx->csv_aux_bytes, [&](Carve& cv) {
+            layout(cv);
+            d_hard = cv.take<Rec>(cap);
+            d_ctr = cv.take<unsigned long long>(2);
+        });
+        if (!rc) rc = fill();
+        if (rc) return rc;
+        HIP_TRY(ctx, hipMemsetAsync(d_ctr, 0xFF, 8, st));
+        HIP_TRY(ctx, hipMemsetAsync(d_ctr + 1, 0, 8, st));
+        rc = launch(d_hard, cap, (uint32_t*)(d_ctr + 1), d_ctr);
+        if (rc) return rc;
+        uint32_t count = 0;
+        HIP_TRY(ctx, hipMemcpyAsync(err, d_ctr, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(&count, d_ctr + 1, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        if (count <= cap) {
+            list.resize(count);
+            if (count) HIP_TRY(ctx, hipMemcpy(list.data(), d_hard, (size_t)count * sizeof(Rec), hipMemcpyDeviceToHost));
+            break;
+        }
+        ctx->csv_hard_cap = count + (count >> 3);
+    }
+    prof_resolve(ctx);
+    return rc;
+}
+
+// out_dev[idx[i]] = val[i]: the values the host finished, in one upload and one scatter.
+int patch_values(mcr_ctx* ctx, double* out_dev, const std::vector<long long>& idx, const std::vector<double>& val)
+{
+    const size_t n = idx.size();
+    if (!n) return MCR_OK;
+    long long* d_idx = nullptr;
+    double* d_val = nullptr;
+    const int rc = carve_buf(ctx, &ctx->csv_aux, &ctx->csv_aux_bytes, [&](Carve& cv) { d_idx = cv.take<long long>(n); d_val = cv.take<double>(n); });
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(d_idx, idx.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_val, val.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
+    LAUNCH(ctx, K_CSV_PATCH, csv::k_csv_patch, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, out_dev, (const long long*)d_idx,
+           (const double*)d_val, (uint32_t)n);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    prof_resolve(ctx);
+    return MCR_OK;
+}
+
+// Column c of file f, whose nc slot table entries start at slots[s0], goes to `slot`.
+int claim_slot(mcr_ctx* ctx, std::vector<int>& slots, size_t s0, int nc, size_t f, int c, int slot)
+{
+    if (c < 0 || c >= nc) return fail(ctx, MCR_EINVAL, "csv: %s has no column %d", csv_file_name(ctx, f).c_str(), c);
+    if (slots[s0 + (size_t)c] != -1) return fail(ctx, MCR_EINVAL, "csv: column %d of %s is requested twice", c, csv_file_name(ctx, f).c_str());
+    slots[s0 + (size_t)c] = slot;
+    return MCR_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -3092,10 +3181,10 @@ int mcr_parse_csv_number(const char* text, size_t len, double* value, int* is_in
     if ((!text && len) || !value || !is_int) return MCR_EINVAL;
     uint64_t bits = 0;
     bool integer = false;
-    const int rc = csv::table_token(text, len, csv::kPow5, &bits, &integer);
+    const int rc = csv::strict_number(text, len, csv::kPow5, &bits, &integer);
     *is_int = integer;
-    if (rc == csv::kTabDecided) { memcpy(value, &bits, 8); return 0; }
-    if (rc != csv::kTabHard) return MCR_EFALLBACK;
+    if (rc == csv::kNumDecided) { memcpy(value, &bits, 8); return 0; }
+    if (rc != csv::kNumHard) return MCR_EFALLBACK;
     return csv::finish_field(text, len, value) ? 1 : MCR_EFALLBACK;
 }
 
@@ -3160,38 +3249,39 @@ int mcr_csv_stage(mcr_ctx* ctx, const mcr_csv* const* files, int n_files, int64_
         const uint32_t n_chunks = (uint32_t)chunk_file.size();
         ctx->csv_row0.assign((size_t)n_files + 1, 0u);
         if (n_chunks) {
-            const size_t o_file = align_up(desc.size() * sizeof(csv::FileDesc), 256), o_cnt = o_file + align_up((size_t)n_chunks * 4, 256),
-                         o_first = o_cnt + align_up((size_t)n_chunks * 4, 256), o_row0 = o_first + align_up((size_t)n_chunks * 4 + 4, 256);
-            int rc = ensure_buf(ctx, &ctx->csv_tab, &ctx->csv_tab_bytes, o_row0 + align_up((size_t)n_files * 4 + 4, 256));
+            csv::FileDesc* d_desc = nullptr;                  // first: the decoders find the descriptors at csv_tab itself
+            uint32_t *d_cfile = nullptr, *d_cnt = nullptr, *d_first = nullptr, *d_row0 = nullptr;
+            int rc = carve_buf(ctx, &ctx->csv_tab, &ctx->csv_tab_bytes, [&](Carve& cv) {
+                d_desc = cv.take<csv::FileDesc>(desc.size());
+                d_cfile = cv.take<uint32_t>(n_chunks);
+                d_cnt = cv.take<uint32_t>(n_chunks);
+                d_first = cv.take<uint32_t>((size_t)n_chunks + 1);
+                d_row0 = cv.take<uint32_t>((size_t)n_files + 1);
+            });
             if (rc) return rc;
-            ctx->csv_row0_off = o_row0;
-            char* tb = (char*)ctx->csv_tab;
-            const csv::FileDesc* d_desc = (const csv::FileDesc*)tb;
-            uint32_t *d_cfile = (uint32_t*)(tb + o_file), *d_cnt = (uint32_t*)(tb + o_cnt), *d_first = (uint32_t*)(tb + o_first),
-                     *d_row0 = (uint32_t*)(tb + o_row0);
-            HIP_TRY(ctx, hipMemcpyAsync(tb, desc.data(), desc.size() * sizeof(csv::FileDesc), hipMemcpyHostToDevice, st));
+            ctx->csv_row0_off = (size_t)((char*)d_row0 - (char*)ctx->csv_tab);
+            HIP_TRY(ctx, hipMemcpyAsync(d_desc, desc.data(), desc.size() * sizeof(csv::FileDesc), hipMemcpyHostToDevice, st));
             HIP_TRY(ctx, hipMemcpyAsync(d_cfile, chunk_file.data(), (size_t)n_chunks * 4, hipMemcpyHostToDevice, st));
             const char* text = (const char*)ctx->pq_stage;
-            if (table)
-                LAUNCH(ctx, K_CSV_LINES, (csv::k_csv_lines<false, true>), dim3(n_chunks), dim3(csv::kLinesNT), 0, text, d_desc,
-                       (const uint32_t*)d_cfile, d_cnt, (const uint32_t*)d_first, (uint32_t*)nullptr);
-            else
-            LAUNCH(ctx, K_CSV_LINES, csv::k_csv_lines<false>, dim3(n_chunks), dim3(csv::kLinesNT), 0, text, d_desc, (const uint32_t*)d_cfile,
-                   d_cnt, (const uint32_t*)d_first, (uint32_t*)nullptr);
-            LAUNCH(ctx, K_CSV_SCAN, csv::k_csv_scan, dim3(1), dim3(1024), 0, (const uint32_t*)d_cnt, n_chunks, d_first, d_desc,
-                   (uint32_t)n_files, d_row0);
+            auto lines = [&](bool write) {                    // count pass, then the write pass into csv_rows
+                const auto kern = table ? (write ? csv::k_csv_lines<true, true> : csv::k_csv_lines<false, true>)
+                                        : (write ? csv::k_csv_lines<true, false> : csv::k_csv_lines<false, false>);
+                LAUNCH(ctx, K_CSV_LINES, kern, dim3(n_chunks), dim3(csv::kLinesNT), 0, text, (const csv::FileDesc*)d_desc,
+                       (const uint32_t*)d_cfile, d_cnt, (const uint32_t*)d_first, write ? (uint32_t*)ctx->csv_rows : nullptr);
+                return (int)MCR_OK;
+            };
+            rc = lines(false);
+            if (rc) return rc;
+            LAUNCH(ctx, K_CSV_SCAN, csv::k_csv_scan, dim3(1), dim3(1024), 0, (const uint32_t*)d_cnt, n_chunks, d_first,
+                   (const csv::FileDesc*)d_desc, (uint32_t)n_files, d_row0);
             HIP_TRY(ctx, hipMemcpyAsync(ctx->csv_row0.data(), d_row0, ((size_t)n_files + 1) * 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(ctx, hipStreamSynchronize(st));
             const uint32_t total_rows = ctx->csv_row0[(size_t)n_files];
             if (total_rows) {
                 rc = ensure_buf(ctx, &ctx->csv_rows, &ctx->csv_rows_bytes, (size_t)total_rows * 4 + 256);
                 if (rc) return rc;
-                if (table)
-                    LAUNCH(ctx, K_CSV_LINES, (csv::k_csv_lines<true, true>), dim3(n_chunks), dim3(csv::kLinesNT), 0, text, d_desc,
-                           (const uint32_t*)d_cfile, d_cnt, (const uint32_t*)d_first, (uint32_t*)ctx->csv_rows);
-                else
-                LAUNCH(ctx, K_CSV_LINES, csv::k_csv_lines<true>, dim3(n_chunks), dim3(csv::kLinesNT), 0, text, d_desc, (const uint32_t*)d_cfile,
-                       d_cnt, (const uint32_t*)d_first, (uint32_t*)ctx->csv_rows);
+                rc = lines(true);
+                if (rc) return rc;
             }
         }
         HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -3224,51 +3314,29 @@ int mcr_csv_decode(mcr_ctx* ctx, const int* columns, int n_cols, int64_t max_row
             const size_t s0 = slots.size();
             slots.insert(slots.end(), (size_t)nc, -1);
             for (int k = 0; k < n_cols; ++k) {
-                const int c = columns[f * (size_t)n_cols + (size_t)k];
-                if (c < 0 || c >= nc) return fail(ctx, MCR_EINVAL, "csv: %s has no column %d", csv_file_name(ctx, f).c_str(), c);
-                if (slots[s0 + (size_t)c] >= 0) return fail(ctx, MCR_EINVAL, "csv: column %d of %s is requested twice", c, csv_file_name(ctx, f).c_str());
-                slots[s0 + (size_t)c] = k;
+                const int rc = claim_slot(ctx, slots, s0, nc, f, columns[f * (size_t)n_cols + (size_t)k], k);
+                if (rc) return rc;
             }
             rows_eff = std::max(rows_eff, std::min<int64_t>(max_rows, (int64_t)(ctx->csv_row0[f + 1] - ctx->csv_row0[f])));
         }
         if (rows_eff == 0 || n_cols == 0) return MCR_OK;
         if (!out_dev) return fail(ctx, MCR_EINVAL, "out_dev is NULL");
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
         hipStream_t st = ctx->stream;
-        if (!ctx->csv_pow5) {
-            HIP_TRY(ctx, hipMalloc(&ctx->csv_pow5, sizeof(csv::kPow5)));
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->csv_pow5, csv::kPow5, sizeof(csv::kPow5), hipMemcpyHostToDevice, st));
-        }
         const char* tb = (const char*)ctx->csv_tab;          // as mcr_csv_stage carved it: descriptors first
-        const size_t o_row0 = ctx->csv_row0_off;
-        uint32_t h_count = 0;
         unsigned long long h_err = ~0ull;
         std::vector<csv::HardField> list;
-        for (int pass = 0; pass < 2; ++pass) {                 // a hard list that overflows: once more with one that fits
-            const size_t o_hard = align_up(slots.size() * 4, 256), o_ctr = o_hard + align_up((size_t)ctx->csv_hard_cap * sizeof(csv::HardField), 256);
-            const int rc = ensure_buf(ctx, &ctx->csv_aux, &ctx->csv_aux_bytes, o_ctr + 256);
-            if (rc) return rc;
-            char* ax = (char*)ctx->csv_aux;
-            HIP_TRY(ctx, hipMemcpyAsync(ax, slots.data(), slots.size() * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(ctx, hipMemsetAsync(ax + o_ctr, 0xFF, 8, st));
-            HIP_TRY(ctx, hipMemsetAsync(ax + o_ctr + 8, 0, 8, st));
-            csv::ParseArgs a{(const char*)ctx->pq_stage, (const csv::FileDesc*)tb, (const uint32_t*)ctx->csv_rows, (const uint32_t*)(tb + o_row0),
-                             (const int*)ax, (const uint64_t*)ctx->csv_pow5, (long long)max_rows, out_dev, (long long)stride_file,
-                             (long long)stride_row, (long long)stride_col, (csv::HardField*)(ax + o_hard), ctx->csv_hard_cap,
-                             (uint32_t*)(ax + o_ctr + 8), (unsigned long long*)(ax + o_ctr)};
+        int* d_slots = nullptr;
+        int rc = hard_pass(ctx, list, &h_err, [&](Carve& cv) { d_slots = cv.take<int>(slots.size()); },
+                           [&] { HIP_TRY(ctx, hipMemcpyAsync(d_slots, slots.data(), slots.size() * 4, hipMemcpyHostToDevice, st)); return (int)MCR_OK; },
+                           [&](csv::HardField* d_hard, uint32_t cap, uint32_t* d_count, unsigned long long* d_err) {
+            csv::ParseArgs a{(const char*)ctx->pq_stage, (const csv::FileDesc*)tb, (const uint32_t*)ctx->csv_rows,
+                             (const uint32_t*)(tb + ctx->csv_row0_off), d_slots, (const uint64_t*)ctx->csv_pow5, (long long)max_rows, out_dev,
+                             (long long)stride_file, (long long)stride_row, (long long)stride_col, d_hard, cap, d_count, d_err};
             LAUNCH(ctx, K_CSV_PARSE, csv::k_csv_parse, dim3((unsigned)((rows_eff + csv::kParseWaves - 1) / csv::kParseWaves), (unsigned)nf),
                    dim3(csv::kParseWaves * 64), 0, a);
-            HIP_TRY(ctx, hipMemcpyAsync(&h_err, ax + o_ctr, 8, hipMemcpyDeviceToHost, st));
-            HIP_TRY(ctx, hipMemcpyAsync(&h_count, ax + o_ctr + 8, 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(ctx, hipStreamSynchronize(st));
-            if (h_count <= ctx->csv_hard_cap) {
-                list.resize(h_count);
-                if (h_count) HIP_TRY(ctx, hipMemcpy(list.data(), ax + o_hard, (size_t)h_count * sizeof(csv::HardField), hipMemcpyDeviceToHost));
-                break;
-            }
-            ctx->csv_hard_cap = h_count + (h_count >> 3);
-        }
-        prof_resolve(ctx);
+            return (int)MCR_OK;
+        });
+        if (rc) return rc;
         const char* pin = (const char*)ctx->pq_pin;
         if (h_err != ~0ull) {
             const size_t f = (size_t)(h_err >> 44);
@@ -3282,32 +3350,22 @@ int mcr_csv_decode(mcr_ctx* ctx, const int* columns, int n_cols, int64_t max_row
             for (size_t i = start; i < c.img + c.len && pin[i] != '\n'; ++i) fields += pin[i] == ',';
             return fail(ctx, MCR_EINVAL, "%s: data row %llu has %zu fields, header has %d", csv_file_name(ctx, f).c_str(), row, fields, c.ncols);
         }
-        if (!list.empty()) {                                  // the host finishes them: strtod on the pinned image, one upload, one scatter
-            std::vector<long long> idx(list.size());
-            std::vector<double> val(list.size());
-            for (size_t i = 0; i < list.size(); ++i) {
-                const csv::HardField& h = list[i];
-                if (!csv::finish_field(pin + h.off, h.len, &val[i])) {
-                    int col = 0;
-                    size_t base = 0;
-                    for (size_t s = 0; s < h.file; ++s) base += (size_t)ctx->csv_files[s].ncols;
-                    while (col < ctx->csv_files[h.file].ncols && slots[base + (size_t)col] != (int)h.slot) ++col;
-                    return fail(ctx, MCR_EINVAL, "%s: data row %u, column %d: could not convert string to float: '%.*s'",
-                                csv_file_name(ctx, h.file).c_str(), h.row, col, (int)std::min<uint32_t>(h.len, 200u), pin + h.off);
-                }
-                idx[i] = (long long)h.file * stride_file + (long long)h.row * stride_row + (long long)h.slot * stride_col;
+        std::vector<long long> idx(list.size());              // the host finishes them: strtod on the pinned image
+        std::vector<double> val(list.size());
+        for (size_t i = 0; i < list.size(); ++i) {
+            const csv::HardField& h = list[i];
+            if (!csv::finish_field(pin + h.off, h.len, &val[i])) {
+                int col = 0;
+                size_t base = 0;
+                for (size_t s = 0; s < h.file; ++s) base += (size_t)ctx->csv_files[s].ncols;
+                while (col < ctx->csv_files[h.file].ncols && slots[base + (size_t)col] != (int)h.slot) ++col;
+                return fail(ctx, MCR_EINVAL, "%s: data row %u, column %d: could not convert string to float: '%.*s'",
+                            csv_file_name(ctx, h.file).c_str(), h.row, col, (int)std::min<uint32_t>(h.len, 200u), pin + h.off);
             }
-            const size_t nb = list.size() * 8;
-            const int rc = ensure_buf(ctx, &ctx->csv_aux, &ctx->csv_aux_bytes, 2 * align_up(nb, 256));
-            if (rc) return rc;
-            char* ax = (char*)ctx->csv_aux;
-            HIP_TRY(ctx, hipMemcpyAsync(ax, idx.data(), nb, hipMemcpyHostToDevice, st));
-            HIP_TRY(ctx, hipMemcpyAsync(ax + align_up(nb, 256), val.data(), nb, hipMemcpyHostToDevice, st));
-            LAUNCH(ctx, K_CSV_PATCH, csv::k_csv_patch, dim3((unsigned)((list.size() + 255) / 256)), dim3(256), 0, out_dev, (const long long*)ax,
-                   (const double*)(ax + align_up(nb, 256)), (uint32_t)list.size());
-            HIP_TRY(ctx, hipStreamSynchronize(st));
-            prof_resolve(ctx);
+            idx[i] = (long long)h.file * stride_file + (long long)h.row * stride_row + (long long)h.slot * stride_col;
         }
+        rc = patch_values(ctx, out_dev, idx, val);
+        if (rc) return rc;
         if (hard) *hard = (int64_t)list.size();
     } catch (const std::exception& e) { return fail(ctx, MCR_ENOMEM, "csv: host allocation failed: %s", e.what()); }
     return MCR_OK;
@@ -3338,17 +3396,15 @@ int mcr_csv_decode_table(mcr_ctx* ctx, const int* columns, int n_cols, const int
             for (int k = 0; k < n_cols; ++k) {
                 const int c = columns[f * (size_t)n_cols + (size_t)k];
                 if (c == -1) continue;
-                if (c < 0 || c >= nc) return fail(ctx, MCR_EINVAL, "csv: %s has no column %d", csv_file_name(ctx, f).c_str(), c);
-                if (slots[s0 + (size_t)c] != -1) return fail(ctx, MCR_EINVAL, "csv: column %d of %s is requested twice", c, csv_file_name(ctx, f).c_str());
-                slots[s0 + (size_t)c] = k;
+                const int rc = claim_slot(ctx, slots, s0, nc, f, c, k);
+                if (rc) return rc;
                 used = k + 1;
             }
             for (int w = 0; w < 2; ++w) {
                 const int c = id_columns[2 * f + (size_t)w];
                 if (c == -1) continue;
-                if (c < 0 || c >= nc) return fail(ctx, MCR_EINVAL, "csv: %s has no column %d", csv_file_name(ctx, f).c_str(), c);
-                if (slots[s0 + (size_t)c] != -1) return fail(ctx, MCR_EINVAL, "csv: column %d of %s is requested twice", c, csv_file_name(ctx, f).c_str());
-                slots[s0 + (size_t)c] = w ? csv::kSlotDraw : csv::kSlotChain;
+                const int rc = claim_slot(ctx, slots, s0, nc, f, c, w ? csv::kSlotDraw : csv::kSlotChain);
+                if (rc) return rc;
                 any_id = true;
             }
             for (int c = 0; c < nc; ++c)
@@ -3367,49 +3423,33 @@ int mcr_csv_decode_table(mcr_ctx* ctx, const int* columns, int n_cols, const int
         if (any_col && !out_dev) return fail(ctx, MCR_EINVAL, "out_dev is NULL");
         if (any_id && !ids_dev) return fail(ctx, MCR_EINVAL, "ids_dev is NULL");
         if (n_cols > 0 && !all_int) return fail(ctx, MCR_EINVAL, "all_int is NULL");
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
         hipStream_t st = ctx->stream;
-        if (!ctx->csv_pow5) {
-            HIP_TRY(ctx, hipMalloc(&ctx->csv_pow5, sizeof(csv::kPow5)));
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->csv_pow5, csv::kPow5, sizeof(csv::kPow5), hipMemcpyHostToDevice, st));
-        }
         const char* tb = (const char*)ctx->csv_tab;          // as mcr_csv_stage carved it: descriptors first
-        const size_t o_row0 = ctx->csv_row0_off;
-        uint32_t h_count = 0;
         unsigned long long h_err = ~0ull;
         std::vector<csv::HardField> list;
         std::vector<uint8_t> flags(2 * slots.size());       // all_int, then neg_zero
-        for (int pass = 0; pass < 2; ++pass) {                 // a hard list that overflows: once more with one that fits
-            const size_t o_outs = align_up(slots.size() * 4, 256), o_int = o_outs + align_up(nf * sizeof(csv::TableOut), 256),
-                         o_hard = o_int + align_up(2 * slots.size(), 256),
-                         o_ctr = o_hard + align_up((size_t)ctx->csv_hard_cap * sizeof(csv::HardField), 256);
-            const int rc = ensure_buf(ctx, &ctx->csv_aux, &ctx->csv_aux_bytes, o_ctr + 256);
-            if (rc) return rc;
-            char* ax = (char*)ctx->csv_aux;
-            HIP_TRY(ctx, hipMemcpyAsync(ax, slots.data(), slots.size() * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(ctx, hipMemcpyAsync(ax + o_outs, outs.data(), nf * sizeof(csv::TableOut), hipMemcpyHostToDevice, st));
-            HIP_TRY(ctx, hipMemsetAsync(ax + o_int, 1, slots.size(), st));
-            HIP_TRY(ctx, hipMemsetAsync(ax + o_int + slots.size(), 0, slots.size(), st));
-            HIP_TRY(ctx, hipMemsetAsync(ax + o_ctr, 0xFF, 8, st));
-            HIP_TRY(ctx, hipMemsetAsync(ax + o_ctr + 8, 0, 8, st));
-            csv::TableArgs a{(const char*)ctx->pq_stage, (const csv::FileDesc*)tb, (const uint32_t*)ctx->csv_rows, (const uint32_t*)(tb + o_row0),
-                             (const int*)ax, (const uint64_t*)ctx->csv_pow5, (const csv::TableOut*)(ax + o_outs), out_dev, (long long*)ids_dev,
-                             (unsigned char*)(ax + o_int), (unsigned char*)(ax + o_int + slots.size()), (csv::HardField*)(ax + o_hard), ctx->csv_hard_cap,
-                             (uint32_t*)(ax + o_ctr + 8), (unsigned long long*)(ax + o_ctr)};
+        int* d_slots = nullptr;
+        csv::TableOut* d_outs = nullptr;
+        unsigned char* d_flags = nullptr;
+        int rc = hard_pass(ctx, list, &h_err,
+                           [&](Carve& cv) { d_slots = cv.take<int>(slots.size()); d_outs = cv.take<csv::TableOut>(nf); d_flags = cv.take<unsigned char>(flags.size()); },
+                           [&] {
+            HIP_TRY(ctx, hipMemcpyAsync(d_slots, slots.data(), slots.size() * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(ctx, hipMemcpyAsync(d_outs, outs.data(), nf * sizeof(csv::TableOut), hipMemcpyHostToDevice, st));
+            HIP_TRY(ctx, hipMemsetAsync(d_flags, 1, slots.size(), st));
+            HIP_TRY(ctx, hipMemsetAsync(d_flags + slots.size(), 0, slots.size(), st));
+            return (int)MCR_OK;
+        },
+                           [&](csv::HardField* d_hard, uint32_t cap, uint32_t* d_count, unsigned long long* d_err) {
+            csv::TableArgs a{(const char*)ctx->pq_stage, (const csv::FileDesc*)tb, (const uint32_t*)ctx->csv_rows,
+                             (const uint32_t*)(tb + ctx->csv_row0_off), d_slots, (const uint64_t*)ctx->csv_pow5, d_outs, out_dev, (long long*)ids_dev,
+                             d_flags, d_flags + slots.size(), d_hard, cap, d_count, d_err};
             LAUNCH(ctx, K_CSV_TABLE_PARSE, csv::k_csv_table_parse, dim3((unsigned)((rows_eff + csv::kParseWaves - 1) / csv::kParseWaves), (unsigned)nf),
                    dim3(csv::kParseWaves * 64), 0, a);
-            HIP_TRY(ctx, hipMemcpyAsync(&h_err, ax + o_ctr, 8, hipMemcpyDeviceToHost, st));
-            HIP_TRY(ctx, hipMemcpyAsync(&h_count, ax + o_ctr + 8, 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(ctx, hipMemcpyAsync(flags.data(), ax + o_int, 2 * slots.size(), hipMemcpyDeviceToHost, st));
-            HIP_TRY(ctx, hipStreamSynchronize(st));
-            if (h_count <= ctx->csv_hard_cap) {
-                list.resize(h_count);
-                if (h_count) HIP_TRY(ctx, hipMemcpy(list.data(), ax + o_hard, (size_t)h_count * sizeof(csv::HardField), hipMemcpyDeviceToHost));
-                break;
-            }
-            ctx->csv_hard_cap = h_count + (h_count >> 3);
-        }
-        prof_resolve(ctx);
+            HIP_TRY(ctx, hipMemcpyAsync(flags.data(), d_flags, flags.size(), hipMemcpyDeviceToHost, st));
+            return (int)MCR_OK;
+        });
+        if (rc) return rc;
         const char* pin = (const char*)ctx->pq_pin;
         if (h_err != ~0ull) {                                  // the first byte that leaves the subset: the host reader's file
             const size_t off = (size_t)(h_err >> 4);
@@ -3442,27 +3482,17 @@ int mcr_csv_decode_table(mcr_ctx* ctx, const int* columns, int n_cols, const int
         std::vector<size_t> slot_base(nf, 0);
         bool unsign = false;
         for (size_t f = 1; f < nf; ++f) slot_base[f] = slot_base[f - 1] + (size_t)ctx->csv_files[f - 1].ncols;
-        if (!list.empty()) {                                  // the host finishes them: strtod on the pinned image, one upload, one scatter
-            std::vector<long long> idx(list.size());
-            std::vector<double> val(list.size());
-            for (size_t i = 0; i < list.size(); ++i) {
-                const csv::HardField& h = list[i];
-                if (!csv::finish_field(pin + h.off, h.len, &val[i]))      // (cannot happen: the device checked the grammar)
-                    return table_fallback(ctx, csv_file_name(ctx, h.file), "a field outside the number grammar", h.off - ctx->csv_files[h.file].img);
-                const csv::TableOut& o = outs[h.file];
-                idx[i] = o.base + (long long)h.row * o.sr + (long long)h.slot * o.sc;
-            }
-            const size_t nb = list.size() * 8;
-            const int rc = ensure_buf(ctx, &ctx->csv_aux, &ctx->csv_aux_bytes, 2 * align_up(nb, 256));
-            if (rc) return rc;
-            char* ax = (char*)ctx->csv_aux;
-            HIP_TRY(ctx, hipMemcpyAsync(ax, idx.data(), nb, hipMemcpyHostToDevice, st));
-            HIP_TRY(ctx, hipMemcpyAsync(ax + align_up(nb, 256), val.data(), nb, hipMemcpyHostToDevice, st));
-            LAUNCH(ctx, K_CSV_PATCH, csv::k_csv_patch, dim3((unsigned)((list.size() + 255) / 256)), dim3(256), 0, out_dev, (const long long*)ax,
-                   (const double*)(ax + align_up(nb, 256)), (uint32_t)list.size());
-            HIP_TRY(ctx, hipStreamSynchronize(st));
-            prof_resolve(ctx);
+        std::vector<long long> idx(list.size());              // the host finishes them: strtod on the pinned image
+        std::vector<double> val(list.size());
+        for (size_t i = 0; i < list.size(); ++i) {
+            const csv::HardField& h = list[i];
+            if (!csv::finish_field(pin + h.off, h.len, &val[i]))      // (cannot happen: the device checked the grammar)
+                return table_fallback(ctx, csv_file_name(ctx, h.file), "a field outside the number grammar", h.off - ctx->csv_files[h.file].img);
+            const csv::TableOut& o = outs[h.file];
+            idx[i] = o.base + (long long)h.row * o.sr + (long long)h.slot * o.sc;
         }
+        rc = patch_values(ctx, out_dev, idx, val);
+        if (rc) return rc;
         for (size_t f = 0; f < nf && n_cols > 0; ++f) {
             for (int k = 0; k < n_cols; ++k) all_int[f * (size_t)n_cols + (size_t)k] = 0;
             for (int c = 0; c < ctx->csv_files[f].ncols; ++c) {
@@ -3506,14 +3536,6 @@ struct mcr_json {
 };
 
 namespace {
-int json_pow5(mcr_ctx* ctx)
-{
-    if (ctx->csv_pow5) return MCR_OK;
-    HIP_TRY(ctx, hipMalloc(&ctx->csv_pow5, sizeof(csv::kPow5)));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->csv_pow5, csv::kPow5, sizeof(csv::kPow5), hipMemcpyHostToDevice, ctx->stream));
-    return MCR_OK;
-}
-
 // The text of the element that starts at `off`, for a message: up to the next ',' or ']', at most 48 bytes.
 std::string json_excerpt(const mcr_json* f, size_t off)
 {
@@ -3606,9 +3628,9 @@ int mcr_parse_json_number(const char* text, size_t len, double* value, int* is_i
     bool integer = false;
     const int rc = json::json_token(text, len, csv::kPow5, &bits, &integer);
     *is_int = integer;
-    if (rc == json::kTokDecided) { memcpy(value, &bits, 8); return 0; }
-    if (rc == json::kTokHard) return json::finish_token(text, len, value) ? 1 : MCR_EINVAL;
-    return rc == json::kTokBigInt ? MCR_EFALLBACK : MCR_EINVAL;
+    if (rc == csv::kNumDecided) { memcpy(value, &bits, 8); return 0; }
+    if (rc == csv::kNumHard) return json::finish_token(text, len, value) ? 1 : MCR_EINVAL;
+    return rc == csv::kNumBigInt ? MCR_EFALLBACK : MCR_EINVAL;
 }
 
 int mcr_json_decode(mcr_ctx* ctx, const mcr_json* f, const int* arrays, int n_params, int64_t n_draws, double* out_dev,
@@ -3650,68 +3672,44 @@ int mcr_json_decode(mcr_ctx* ctx, const mcr_json* f, const int* arrays, int n_pa
         for (size_t i = 0; i < (size_t)n_params * n_chains; ++i) all_int[i] = 1;
         if (n_values == 0) return MCR_OK;
         if (n_params > 0 && n_draws > 0 && !out_dev) return fail(ctx, MCR_EINVAL, "out_dev is NULL");
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
         hipStream_t st = ctx->stream;
-        int rc = json_pow5(ctx);
-        if (rc) return rc;
         const size_t n_arrays = descs.size();
-        uint32_t h_count = 0;
         unsigned long long h_err = ~0ull;
         std::vector<json::HardToken> list;
         std::vector<uint32_t> not_int(n_arrays);
-        for (int pass = 0; pass < 2; ++pass) {                 // a hard list that overflows: once more with one that fits
-            const size_t o_ni = align_up(n_arrays * sizeof(json::ArrayDesc), 256), o_hard = o_ni + align_up(n_arrays * 4, 256),
-                         o_ctr = o_hard + align_up((size_t)ctx->csv_hard_cap * sizeof(json::HardToken), 256);
-            rc = ensure_buf(ctx, &ctx->csv_aux, &ctx->csv_aux_bytes, o_ctr + 256);
-            if (rc) return rc;
-            char* ax = (char*)ctx->csv_aux;
-            HIP_TRY(ctx, hipMemcpyAsync(ax, descs.data(), n_arrays * sizeof(json::ArrayDesc), hipMemcpyHostToDevice, st));
-            HIP_TRY(ctx, hipMemsetAsync(ax + o_ni, 0, n_arrays * 4, st));
-            HIP_TRY(ctx, hipMemsetAsync(ax + o_ctr, 0xFF, 8, st));
-            HIP_TRY(ctx, hipMemsetAsync(ax + o_ctr + 8, 0, 8, st));
-            json::ParseArgs a{(const char*)f->d_text, (const uint32_t*)f->d_tok, (const json::ArrayDesc*)ax, (uint32_t)n_arrays, (uint32_t)n_values,
-                              (const uint64_t*)ctx->csv_pow5, out_dev, (long long)stride_n, (uint32_t*)(ax + o_ni),
-                              (json::HardToken*)(ax + o_hard), ctx->csv_hard_cap, (uint32_t*)(ax + o_ctr + 8), (unsigned long long*)(ax + o_ctr)};
+        json::ArrayDesc* d_descs = nullptr;
+        uint32_t* d_ni = nullptr;
+        int rc = hard_pass(ctx, list, &h_err, [&](Carve& cv) { d_descs = cv.take<json::ArrayDesc>(n_arrays); d_ni = cv.take<uint32_t>(n_arrays); },
+                           [&] {
+            HIP_TRY(ctx, hipMemcpyAsync(d_descs, descs.data(), n_arrays * sizeof(json::ArrayDesc), hipMemcpyHostToDevice, st));
+            HIP_TRY(ctx, hipMemsetAsync(d_ni, 0, n_arrays * 4, st));
+            return (int)MCR_OK;
+        },
+                           [&](json::HardToken* d_hard, uint32_t cap, uint32_t* d_count, unsigned long long* d_err) {
+            json::ParseArgs a{(const char*)f->d_text, (const uint32_t*)f->d_tok, d_descs, (uint32_t)n_arrays, (uint32_t)n_values,
+                              (const uint64_t*)ctx->csv_pow5, out_dev, (long long)stride_n, d_ni, d_hard, cap, d_count, d_err};
             LAUNCH(ctx, K_JSON_PARSE, json::k_json_parse, dim3((unsigned)((n_values + json::kParseNT - 1) / json::kParseNT)), dim3(json::kParseNT),
                    0, a);
-            HIP_TRY(ctx, hipMemcpyAsync(&h_err, ax + o_ctr, 8, hipMemcpyDeviceToHost, st));
-            HIP_TRY(ctx, hipMemcpyAsync(&h_count, ax + o_ctr + 8, 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(ctx, hipMemcpyAsync(not_int.data(), ax + o_ni, n_arrays * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(ctx, hipStreamSynchronize(st));
-            if (h_count <= ctx->csv_hard_cap) {
-                list.resize(h_count);
-                if (h_count) HIP_TRY(ctx, hipMemcpy(list.data(), ax + o_hard, (size_t)h_count * sizeof(json::HardToken), hipMemcpyDeviceToHost));
-                break;
-            }
-            ctx->csv_hard_cap = h_count + (h_count >> 3);
-        }
-        prof_resolve(ctx);
+            HIP_TRY(ctx, hipMemcpyAsync(not_int.data(), d_ni, n_arrays * 4, hipMemcpyDeviceToHost, st));
+            return (int)MCR_OK;
+        });
+        if (rc) return rc;
         if (h_err != ~0ull) {
             const size_t off = (size_t)(h_err >> 4);
             if ((h_err & 15) == json::kErrBigInt)
                 return fail(ctx, MCR_EFALLBACK, "json: the integer literal '%s' (byte %zu) is beyond 2^53", json_excerpt(f, off).c_str(), off);
             return fail(ctx, MCR_EFALLBACK, "json: the array element '%s' (byte %zu) is not a number", json_excerpt(f, off).c_str(), off);
         }
-        if (!list.empty()) {                                  // the host finishes them: strtod on the caller's image, one upload, one scatter
-            std::vector<long long> idx(list.size());
-            std::vector<double> val(list.size());
-            for (size_t i = 0; i < list.size(); ++i) {
-                const json::HardToken& h = list[i];
-                if (!json::finish_token(f->bytes + h.off, h.len, &val[i]))
-                    return fail(ctx, MCR_EFALLBACK, "json: the array element '%s' (byte %u) is not a number", json_excerpt(f, h.off).c_str(), h.off);
-                idx[i] = descs[h.array].base + (long long)h.v * stride_n;
-            }
-            const size_t nb = list.size() * 8;
-            rc = ensure_buf(ctx, &ctx->csv_aux, &ctx->csv_aux_bytes, 2 * align_up(nb, 256));
-            if (rc) return rc;
-            char* ax = (char*)ctx->csv_aux;
-            HIP_TRY(ctx, hipMemcpyAsync(ax, idx.data(), nb, hipMemcpyHostToDevice, st));
-            HIP_TRY(ctx, hipMemcpyAsync(ax + align_up(nb, 256), val.data(), nb, hipMemcpyHostToDevice, st));
-            LAUNCH(ctx, K_CSV_PATCH, csv::k_csv_patch, dim3((unsigned)((list.size() + 255) / 256)), dim3(256), 0, out_dev, (const long long*)ax,
-                   (const double*)(ax + align_up(nb, 256)), (uint32_t)list.size());
-            HIP_TRY(ctx, hipStreamSynchronize(st));
-            prof_resolve(ctx);
+        std::vector<long long> idx(list.size());              // the host finishes them: strtod on the caller's image
+        std::vector<double> val(list.size());
+        for (size_t i = 0; i < list.size(); ++i) {
+            const json::HardToken& h = list[i];
+            if (!json::finish_token(f->bytes + h.off, h.len, &val[i]))
+                return fail(ctx, MCR_EFALLBACK, "json: the array element '%s' (byte %u) is not a number", json_excerpt(f, h.off).c_str(), h.off);
+            idx[i] = descs[h.array].base + (long long)h.v * stride_n;
         }
+        rc = patch_values(ctx, out_dev, idx, val);
+        if (rc) return rc;
         for (size_t i = 0; i < desc_of.size(); ++i)
             if (desc_of[i] != SIZE_MAX) all_int[i] = not_int[desc_of[i]] ? 0 : 1;
         if (hard) *hard = (int64_t)list.size();

@@ -9,7 +9,7 @@
 //   k_csv_parse     one wavefront per data row: 64-byte batches, a ballot on ',' gives the field boundaries, a running
 //                   popcount the column, each lane that owns a selected field parses it.
 //   open_image      host: header, body offset and column names of a file image.
-//   table mode      plain table CSVs by pyarrow.csv.read_csv's rules, as far as they are certified: table_token (the
+//   table mode      plain table CSVs by pyarrow.csv.read_csv's rules, as far as they are certified: strict_number (the
 //                   strict number grammar), k_csv_lines<., true> (every non-empty line is a row), k_csv_table_parse,
 //                   open_table_image.  What leaves the subset is reported, never guessed: the host reader decides.
 //   finish_field    host: the float() grammar (no underscores) + strtod for the fields the device reported hard.
@@ -147,18 +147,19 @@ __host__ __device__ inline int parse_field(const char* p, size_t n, const u64* p
     return 0;
 }
 
-constexpr u64 kMaxExactInt = 1ull << 53;   // integer literals above it leave the certified subset
-constexpr int kTabDecided = 0, kTabHard = 1, kTabNotNumber = -1, kTabBigInt = -2;   // table_token
+constexpr u64 kMaxExactInt = 1ull << 53;   // integer literals above it leave the certified subset (pyarrow refuses the mix)
+constexpr int kNumDecided = 0, kNumHard = 1, kNumNotNumber = -1, kNumBigInt = -2;   // strict_number
 
+// The strict number grammar of the table CSV and the JSON reader (json::json_token adds what is JSON's own):
 // -?(0|[1-9][0-9]*)(\.[0-9]+)?([eE][+-]?[0-9]+)? and nothing around it -> the double pyarrow.csv gives the field.
-// kTabDecided: *bits is the value; kTabHard: the dropped digits decide the rounding (the host finishes it);
-// kTabNotNumber: outside the grammar; kTabBigInt: an integer literal above 2^53.  *is_int: no fraction and no
+// kNumDecided: *bits is the value; kNumHard: the dropped digits decide the rounding (the host finishes it);
+// kNumNotNumber: outside the grammar; kNumBigInt: an integer literal above 2^53.  *is_int: no fraction and no
 // exponent; -0 keeps its sign (bits of -0.0).  Like pyarrow, 1e400 is inf and 1e-400 is 0.
-__host__ __device__ inline int table_token(const char* t, size_t m, const u64* pow5, u64* bits, bool* is_int)
+__host__ __device__ inline int strict_number(const char* t, size_t m, const u64* pow5, u64* bits, bool* is_int)
 {
     *is_int = false;
     size_t k = (m && t[0] == '-') ? 1 : 0;
-    if (k >= m || (unsigned)(t[k] - '0') > 9) return kTabNotNumber;
+    if (k >= m || (unsigned)(t[k] - '0') > 9) return kNumNotNumber;
     const size_t d0 = k;
     u64 mag = 0;
     if (t[k] == '0') ++k;
@@ -169,7 +170,7 @@ __host__ __device__ inline int table_token(const char* t, size_t m, const u64* p
         integer = false;
         const size_t f0 = ++k;
         while (k < m && (unsigned)(t[k] - '0') <= 9) ++k;
-        if (k == f0) return kTabNotNumber;
+        if (k == f0) return kNumNotNumber;
     }
     if (k < m && (t[k] == 'e' || t[k] == 'E')) {
         integer = false;
@@ -177,12 +178,12 @@ __host__ __device__ inline int table_token(const char* t, size_t m, const u64* p
         if (k < m && (t[k] == '+' || t[k] == '-')) ++k;
         const size_t x0 = k;
         while (k < m && (unsigned)(t[k] - '0') <= 9) ++k;
-        if (k == x0) return kTabNotNumber;
+        if (k == x0) return kNumNotNumber;
     }
-    if (k != m) return kTabNotNumber;
+    if (k != m) return kNumNotNumber;
     *is_int = integer;
-    if (integer && (int_digits > 16 || mag > kMaxExactInt)) return kTabBigInt;      // 17 digits: at least 10^16 > 2^53
-    return parse_field(t, m, pow5, bits) == 0 ? kTabDecided : kTabHard;
+    if (integer && (int_digits > 16 || mag > kMaxExactInt)) return kNumBigInt;      // 17 digits: at least 10^16 > 2^53
+    return parse_field(t, m, pow5, bits) == 0 ? kNumDecided : kNumHard;
 }
 
 // ---- device side ------------------------------------------------------------------------------------------------
@@ -416,14 +417,14 @@ __global__ __launch_bounds__(kParseWaves * 64) void k_csv_table_parse(const Tabl
                 if (n && e < f.end && a.text[e] == '\n' && a.text[e - 1] == '\r') --n;     // "\r\n" ends the row
                 u64 bits = 0;
                 bool is_int = false;
-                const int rc = table_token(a.text + s, n, a.pow5, &bits, &is_int);
+                const int rc = strict_number(a.text + s, n, a.pow5, &bits, &is_int);
                 if (rc < 0) {
-                    const int kind = rc == kTabBigInt ? kTabErrBigInt : kTabErrField;
+                    const int kind = rc == kNumBigInt ? kTabErrBigInt : kTabErrField;
                     atomicMin(a.err, ((unsigned long long)s << 4) | kind);
                 } else if (k >= 0) {
                     if (!is_int) a.all_int[f.slot0 + mycol] = 0;
                     else if (bits == 1ull << 63) a.neg_zero[f.slot0 + mycol] = 1;
-                    if (rc == kTabDecided) {
+                    if (rc == kNumDecided) {
                         a.out[o.base + row * o.sr + (long long)k * o.sc] = __longlong_as_double((long long)bits);
                     } else {
                         const u32 h = atomicAdd(a.hard_count, 1u);

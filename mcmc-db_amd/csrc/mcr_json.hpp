@@ -1,8 +1,8 @@
 // mcr_json.hpp -- chain-list JSON text, [ {param: [draws...], ...}, ... ], -> draw tensor (replaces the
 // json.loads + np.asarray of the JSON-zip reader, src/mcmc_ref/convert.py:78-102, on the way into the statistics).
 //
-//   json_token      one array element -> binary64 bits: the strict JSON number grammar, then csv::parse_field
-//                   (Eisel-Lemire: correctly rounded or HARD).  __host__ __device__: the CPU tests run the kernels' text.
+//   json_token      one array element -> binary64 bits: csv::strict_number (the strict number grammar, then Eisel-Lemire:
+//                   correctly rounded or HARD) with JSON's whitespace, NaN / Infinity and unsigned integer zero.  __host__ __device__: the CPU tests run the kernels' text.
 //   k_json_index    structural index: every workgroup scans kChunk bytes for [ ] { } : , outside strings.  The count
 //                   pass counts under both quote states at the chunk's start; k_json_scan picks the true one from the
 //                   chunks' quote parities and forms the prefix sums; the write pass stores tok[] (every token's
@@ -24,11 +24,6 @@ constexpr int kParseNT = 256;          // array elements per k_json_parse workgr
 static_assert(kIndexNT * 64 == kChunk, "structural index geometry");
 
 constexpr u32 kNoOffset = 0xFFFFFFFFu;
-constexpr u64 kMaxExactInt = 1ull << 53;   // integer literals above it leave the certified subset (pyarrow refuses the mix)
-
-// What json_token returns.
-constexpr int kTokDecided = 0, kTokHard = 1, kTokNotNumber = -1, kTokBigInt = -2;
-
 __host__ __device__ inline bool json_ws(char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r'; }
 
 __host__ __device__ inline bool token_is(const char* p, size_t n, const char* w, size_t m)
@@ -38,50 +33,24 @@ __host__ __device__ inline bool token_is(const char* p, size_t n, const char* w,
     return true;
 }
 
-// [ws] -?(0|[1-9][0-9]*)(\.[0-9]+)?([eE][+-]?[0-9]+)? [ws] -> float(json.loads(text)).  kTokDecided: *bits is the value;
-// kTokHard: a number whose dropped digits decide the rounding, or exactly NaN / Infinity / -Infinity (the host finishes
-// it); kTokNotNumber: json.loads would refuse it or give something else than a number; kTokBigInt: an integer literal
-// above 2^53.  *is_int: no fraction and no exponent; such a literal has no negative zero.
+// [ws] -?(0|[1-9][0-9]*)(\.[0-9]+)?([eE][+-]?[0-9]+)? [ws] -> float(json.loads(text)): csv::strict_number and its
+// csv::kNum* codes, with what is JSON's own.  The whitespace around the token is trimmed; exactly NaN / Infinity /
+// -Infinity are kNumHard too (the host finishes them); kNumNotNumber: json.loads would refuse it or give something
+// else than a number; an integer literal has no negative zero.
 __host__ __device__ inline int json_token(const char* p, size_t n, const u64* pow5, u64* bits, bool* is_int)
 {
     size_t i = 0, e = n;
     while (i < e && json_ws(p[i])) ++i;
     while (e > i && json_ws(p[e - 1])) --e;
-    *is_int = false;
     const char* t = p + i;
     const size_t m = e - i;
-    if (m == 0) return kTokNotNumber;
-    if (t[0] == 'N' || t[0] == 'I' || (m > 1 && t[1] == 'I'))
-        return token_is(t, m, "NaN", 3) || token_is(t, m, "Infinity", 8) || token_is(t, m, "-Infinity", 9) ? kTokHard : kTokNotNumber;
-    size_t k = t[0] == '-' ? 1 : 0;
-    if (k >= m || (unsigned)(t[k] - '0') > 9) return kTokNotNumber;
-    const size_t d0 = k;
-    u64 mag = 0;
-    if (t[k] == '0') ++k;
-    else for (; k < m && (unsigned)(t[k] - '0') <= 9; ++k) if (k - d0 < 17) mag = mag * 10 + (u64)(t[k] - '0');
-    const size_t int_digits = k - d0;
-    bool integer = true;
-    if (k < m && t[k] == '.') {
-        integer = false;
-        const size_t f0 = ++k;
-        while (k < m && (unsigned)(t[k] - '0') <= 9) ++k;
-        if (k == f0) return kTokNotNumber;
+    if (m && (t[0] == 'N' || t[0] == 'I' || (m > 1 && t[1] == 'I'))) {
+        *is_int = false;
+        return token_is(t, m, "NaN", 3) || token_is(t, m, "Infinity", 8) || token_is(t, m, "-Infinity", 9) ? csv::kNumHard : csv::kNumNotNumber;
     }
-    if (k < m && (t[k] == 'e' || t[k] == 'E')) {
-        integer = false;
-        ++k;
-        if (k < m && (t[k] == '+' || t[k] == '-')) ++k;
-        const size_t x0 = k;
-        while (k < m && (unsigned)(t[k] - '0') <= 9) ++k;
-        if (k == x0) return kTokNotNumber;
-    }
-    if (k != m) return kTokNotNumber;
-    *is_int = integer;
-    if (integer) {
-        if (int_digits > 16 || mag > kMaxExactInt) return kTokBigInt;      // 17 digits: at least 10^16 > 2^53
-        if (mag == 0) { *bits = 0; return kTokDecided; }
-    }
-    return csv::parse_field(t, m, pow5, bits) == 0 ? kTokDecided : kTokHard;
+    const int rc = csv::strict_number(t, m, pow5, bits, is_int);
+    if (*is_int && rc == csv::kNumDecided && *bits == 1ull << 63) *bits = 0;
+    return rc;
 }
 
 // ---- device side ------------------------------------------------------------------------------------------------
@@ -216,11 +185,11 @@ __global__ __launch_bounds__(kParseNT) void k_json_parse(const ParseArgs a)
     u64 bits = 0;
     bool is_int = false;
     const int rc = json_token(a.text + s, e - s, a.pow5, &bits, &is_int);
-    if (rc == kTokNotNumber) { atomicMin(a.err, ((unsigned long long)s << 4) | kErrToken); return; }
+    if (rc == csv::kNumNotNumber) { atomicMin(a.err, ((unsigned long long)s << 4) | kErrToken); return; }
     if (d.base < 0 || v >= d.limit) return;
-    if (rc == kTokBigInt) { atomicMin(a.err, ((unsigned long long)s << 4) | kErrBigInt); return; }
+    if (rc == csv::kNumBigInt) { atomicMin(a.err, ((unsigned long long)s << 4) | kErrBigInt); return; }
     if (!is_int) a.not_int[lo] = 1;
-    if (rc == kTokDecided) {
+    if (rc == csv::kNumDecided) {
         a.out[d.base + (long long)v * a.stride_n] = __longlong_as_double((long long)bits);
     } else {
         const u32 h = atomicAdd(a.hard_count, 1u);

@@ -105,6 +105,30 @@ def test_the_field_routine_equals_pyarrow_in_bits_and_in_column_type(L):
     assert parse(L, "9007199254740992") == (0, 2.0 ** 53, 1) and parse(L, "-9007199254740992") == (0, -(2.0 ** 53), 1)
 
 
+def test_the_csv_and_the_json_entry_point_agree_where_their_grammars_overlap(L):
+    """Both run csv::strict_number.  Without whitespace around the text and without NaN / Infinity, JSON adds one thing:
+    the integer literal -0 has no sign (int(-0) is 0), where pyarrow's double column keeps it."""
+    strings = _strings(5_000, 20260118)
+
+    def parse_json(s: str):
+        b = s.encode()
+        out, is_int = ctypes.c_double(math.nan), ctypes.c_int(-1)
+        rc = L.mcr_parse_json_number(b, len(b), ctypes.byref(out), ctypes.byref(is_int))
+        return rc, struct.pack("<d", out.value), is_int.value
+
+    seen = {0: 0, 1: 0, EFALLBACK: 0}
+    for s in strings:
+        rc, v, is_int = parse(L, s)
+        got = parse_json(s)
+        if s == "-0":
+            assert (rc, struct.pack("<d", v), is_int) == (0, struct.pack("<d", -0.0), 1), s
+            assert got == (0, struct.pack("<d", 0.0), 1), s
+            continue
+        assert got == (rc, struct.pack("<d", v), is_int), s
+        seen[rc] += 1
+    assert strings.count("-0") >= 1 and seen[0] > 20_000 and seen[1] >= 200 and seen[EFALLBACK] >= 1, seen
+
+
 REJECTED = ["", " 1", "1 ", "+1", "01", ".5", "5.", "1e", "-", "inf", "Infinity", "nan", "NaN", "true", "0x10", "1_0",
             "2020-01-01", '"1"', "9007199254740993"]
 

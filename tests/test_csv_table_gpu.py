@@ -179,6 +179,22 @@ def test_fields_at_batch_edges_and_long_fields(ctx, tmp_path):
     assert phases["hard"] >= 3
 
 
+def test_a_hard_list_that_overflows_is_parsed_once_more(tmp_path):
+    """5 961 of the 6 000 value fields are midpoints of neighbouring doubles whose digits past the 19th decide: more
+    than the first capacity of the hard list (4 096), so the parse runs again with a list that fits."""
+    import random
+
+    import pyarrow as pa
+    from mcmc_ref_hip import _ffi
+    from test_csv_gpu import halfway
+    rng = random.Random(13)
+    rows = [f"{c},{n},{halfway(rng)},{halfway(rng)}" for c in range(4) for n in range(750)]
+    data = ("chain,draw,x,y\n" + "\n".join(rows) + "\n").encode()
+    assert read_host(data).schema.types == [pa.int64(), pa.int64(), pa.float64(), pa.float64()]
+    with _ffi.Context(0) as fresh:                           # its capacity is the initial one whatever the module's has seen
+        check_against_pyarrow(fresh, put(tmp_path, "overflow", data), data, min_hard=4097)
+
+
 def test_type_inference_covers_the_whole_file(ctx, tmp_path):
     import pyarrow as pa
     lines = ["a,b"] + [f"{k},{k % 7}" for k in range(6000)] + ["1.5,3"]
