@@ -377,6 +377,56 @@ int mcr_gather_rows_order_dev(mcr_ctx* ctx, const double* src_dev, int64_t P, in
                               double* dst_dev);
 
 /* ------------------------------------------------------------------------------------------------
+ * Parquet writing: device columns -> draws file image.
+ * Replaces `pq.write_table(table, draws_path)` (src/mcmc_ref/convert.py:64): every data page is
+ * formed (definition levels + PLAIN values), Snappy-compressed and measured (min / max) by one HIP
+ * workgroup, the host writes page headers and the footer from the pages' sizes, and one kernel
+ * packs everything into the file image that one copy brings to pinned host memory.
+ * Written: a flat schema of OPTIONAL leaves without nulls, INT32 / INT64 / DOUBLE, data pages v1 of
+ * MCR_PQW_PAGE_ROWS rows, PLAIN values, RLE levels, SNAPPY with copy offsets <= 65535, no
+ * dictionary pages, row groups of row_group_rows rows, Statistics (null_count 0, min_value /
+ * max_value; a zero minimum is -0.0 and a zero maximum +0.0; none for a chunk with a NaN),
+ * created_by "mcmc-ref-hip version <major.minor.patch of MCR_VERSION>".  The same columns give the
+ * same bytes.
+ * A column is `rows` elements of a source: device memory through an element stride, or generated.
+ * f64 -> DOUBLE keeps the bits; f64 -> INT64 / INT32 and i64 -> INT64 / INT32 are checked: a value
+ * that is no integer or outside the type's range ends the call with MCR_EINVAL naming the column
+ * and the first such row.  Also MCR_EINVAL: rows <= 0 or >= 2^31, an empty or repeated name, a
+ * type other than the three, an integer source written as DOUBLE, stride < 1.
+ * ---------------------------------------------------------------------------------------------- */
+#define MCR_PQW_PAGE_ROWS 8192         /* rows per data page: 64 KiB of 8-byte values */
+#define MCR_PQW_ROW_GROUP_ROWS 1048576 /* rows per row group when row_group_rows is 0 (pyarrow's default) */
+
+#define MCR_PQW_F64 0 /* src_dev: double, element r at src_dev[r * stride] */
+#define MCR_PQW_I64 1 /* src_dev: int64_t, same addressing */
+#define MCR_PQW_SEQ 2 /* no memory: value(r) = (r / seq_div) % seq_mod.  chain of a rectangular model: div = N;
+                         draw: mod = N; row number: div = 1, mod = INT64_MAX; zeros: mod = 1 */
+typedef struct mcr_pq_column {
+    const char* name;
+    int type;     /* MCR_PQ_INT32, MCR_PQ_INT64 or MCR_PQ_DOUBLE */
+    int src_kind; /* MCR_PQW_* */
+    const void* src_dev;
+    int64_t stride;
+    int64_t seq_div, seq_mod;
+} mcr_pq_column;
+typedef struct mcr_pq_image mcr_pq_image;
+
+/* Synchronous; uses the current lane's workspace, so no summary may be in flight (as mcr_chain_layout_dev).
+ * *out owns the image (pinned host memory) until mcr_pq_image_free. */
+int mcr_parquet_write_dev(mcr_ctx* ctx, const mcr_pq_column* cols, int n_cols, int64_t rows, int64_t row_group_rows,
+                          mcr_pq_image** out);
+/* The same file format from HOST columns (src_dev points to host memory), without a device: ctx may be NULL.  Page
+ * headers, footer, levels and statistics come from the same code, the pages from a scalar restatement of the
+ * compressor that shares the token emission; its sequential match finder sees every earlier element, so the bytes
+ * may differ from the device's.  Both are valid files with equal contents. */
+int mcr_parquet_write_host(mcr_ctx* ctx, const mcr_pq_column* cols, int n_cols, int64_t rows, int64_t row_group_rows,
+                           mcr_pq_image** out);
+const void* mcr_pq_image_data(const mcr_pq_image* image);
+size_t mcr_pq_image_size(const mcr_pq_image* image);
+int mcr_pq_image_pages(const mcr_pq_image* image); /* data pages of the file */
+void mcr_pq_image_free(mcr_pq_image* image);
+
+/* ------------------------------------------------------------------------------------------------
  * Many draws files -> statistics in ONE call (the per-model loop of reference.stats /
  * diagnostics_for_model, src/mcmc_ref/reference.py:30-104, over a list of
  * draws/<model>.draws.parquet files): mmap + footer parse on the host, one batched GPU decode, the

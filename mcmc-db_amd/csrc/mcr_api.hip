@@ -30,6 +30,7 @@
 #include "mcr_fft.hpp"
 #include "mcr_ext.hpp"
 #include "mcr_parquet.hpp"
+#include "mcr_pqwrite.hpp"
 #include "mcr_layout.hpp"
 #include "mcr_csv.hpp"
 #include "mcr_json.hpp"
@@ -56,7 +57,8 @@ enum KernelId {
     K_DIAG2, K_ACOV_SEG, K_TWO_SAMPLE, K_COV, K_ZTABLE, K_PQ_SNAPPY, K_PQ_DECODE, K_GATHER, K_ACOV_LONG, K_DIAG_LONG, K_COV_FINAL, K_FFT,
     K_CSV_LINES, K_CSV_SCAN, K_CSV_PARSE, K_CSV_PATCH, K_CSV_TABLE_PARSE, K_CSV_UNSIGN_ZERO,
     K_JSON_INDEX, K_JSON_SCAN, K_JSON_PARSE,
-    K_LAYOUT_SCAN, K_LAYOUT_KEYS, K_LAYOUT_HIST, K_LAYOUT_OFFSETS, K_LAYOUT_SCATTER, K_LAYOUT_BOUNDS, K_COUNT
+    K_LAYOUT_SCAN, K_LAYOUT_KEYS, K_LAYOUT_HIST, K_LAYOUT_OFFSETS, K_LAYOUT_SCATTER, K_LAYOUT_BOUNDS,
+    K_PQW_ENCODE, K_PQW_COMPACT, K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {
     "k_ingest", "k_moments", "k_moments_final", "k_tile_sort", "k_merge", "k_order_stats", "k_rank_z",
@@ -65,7 +67,8 @@ const char* const kKernelNames[K_COUNT] = {
     "k_pq_snappy", "k_pq_decode", "k_gather_rows", "k_acov_long", "k_diag_long_scan", "k_cov_final", "k_fft",
     "k_csv_lines", "k_csv_scan", "k_csv_parse", "k_csv_patch", "k_csv_table_parse", "k_csv_unsign_zero",
     "k_json_index", "k_json_scan", "k_json_parse",
-    "k_layout_scan", "k_layout_keys", "k_layout_hist", "k_layout_offsets", "k_layout_scatter", "k_layout_bounds"};
+    "k_layout_scan", "k_layout_keys", "k_layout_hist", "k_layout_offsets", "k_layout_scatter", "k_layout_bounds",
+    "k_pqw_encode", "k_pqw_compact"};
 
 struct EvPair { hipEvent_t a, b; int kid; };
 
@@ -2408,6 +2411,179 @@ int mcr_gather_rows_dev(mcr_ctx* ctx, const double* src_dev, int64_t P, int64_t 
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     prof_resolve(ctx);
     return MCR_OK;
+}
+
+// ---- Parquet writing (mcr_pqwrite.hpp; replaces pq.write_table at convert.py:64) --------------------------------
+
+struct mcr_pq_image { unsigned char* data = nullptr; size_t size = 0; int pages = 0; bool pinned = false; };
+
+namespace {
+namespace pqw = mcr::pqw;
+static_assert(pqw::kPageRows == MCR_PQW_PAGE_ROWS && pqw::kRowGroupRows == MCR_PQW_ROW_GROUP_ROWS, "the header states the page geometry");
+static_assert(pqw::SRC_F64 == MCR_PQW_F64 && pqw::SRC_I64 == MCR_PQW_I64 && pqw::SRC_SEQ == MCR_PQW_SEQ, "source kinds");
+
+struct PqwJob {
+    std::vector<pqw::ColSpec> specs; std::vector<pqw::ColDev> cols; std::vector<pqw::PagePlan> pages;
+    std::vector<u64> slot_off; size_t slots_total = 0;
+};
+
+int pqw_args(mcr_ctx* ctx, const char* who, const mcr_pq_column* cols, int n_cols, int64_t rows, int64_t row_group_rows,
+             mcr_pq_image** out, PqwJob& J)
+{
+    namespace pq = mcr::pq;
+    if (!cols || !out || n_cols < 1) return fail(ctx, MCR_EINVAL, "%s: NULL argument or no columns", who);
+    if (rows <= 0 || rows >= (int64_t)1 << 31) return fail(ctx, MCR_EINVAL, "%s: row count %lld out of range (1 .. 2^31 - 1)", who, (long long)rows);
+    if (row_group_rows < 0) return fail(ctx, MCR_EINVAL, "%s: negative row_group_rows", who);
+    std::vector<int> types;
+    for (int c = 0; c < n_cols; ++c) {
+        const mcr_pq_column& q = cols[c];
+        if (!q.name || !*q.name) return fail(ctx, MCR_EINVAL, "%s: column %d has an empty name", who, c);
+        for (int b = 0; b < c; ++b)
+            if (strcmp(cols[b].name, q.name) == 0) return fail(ctx, MCR_EINVAL, "%s: duplicate column name '%s'", who, q.name);
+        if (q.type != MCR_PQ_INT32 && q.type != MCR_PQ_INT64 && q.type != MCR_PQ_DOUBLE)
+            return fail(ctx, MCR_EINVAL, "%s: column '%s' has type %d; only INT32, INT64 and DOUBLE are written", who, q.name, q.type);
+        if (q.src_kind == MCR_PQW_F64 || q.src_kind == MCR_PQW_I64) {
+            if (!q.src_dev || q.stride < 1) return fail(ctx, MCR_EINVAL, "%s: column '%s' needs a source and a stride >= 1", who, q.name);
+        } else if (q.src_kind == MCR_PQW_SEQ) {
+            if (q.seq_div < 1 || q.seq_mod < 1) return fail(ctx, MCR_EINVAL, "%s: column '%s' needs seq_div >= 1 and seq_mod >= 1", who, q.name);
+        } else return fail(ctx, MCR_EINVAL, "%s: column '%s' has source kind %d", who, q.name, q.src_kind);
+        if (q.src_kind != MCR_PQW_F64 && q.type == MCR_PQ_DOUBLE)
+            return fail(ctx, MCR_EINVAL, "%s: column '%s': an integer source is written as INT32 or INT64", who, q.name);
+        J.specs.push_back(pqw::ColSpec{q.name, q.type});
+        J.cols.push_back(pqw::ColDev{q.src_dev, (i64)q.stride, (i64)q.seq_div, (i64)q.seq_mod, q.src_kind, q.type});
+        types.push_back(q.type);
+    }
+    pqw::plan_pages(n_cols, types.data(), (i64)rows, row_group_rows ? (i64)row_group_rows : pqw::kRowGroupRows, J.pages);
+    if (J.pages.size() > (size_t)0x3FFFFFFF) return fail(ctx, MCR_EINVAL, "%s: too many pages", who);
+    for (const pqw::PagePlan& p : J.pages) { J.slot_off.push_back(J.slots_total); J.slots_total += pqw::slot_bytes(p.uncomp); }
+    return MCR_OK;
+}
+
+int pqw_bad_value(mcr_ctx* ctx, const char* who, const PqwJob& J, int col, long long row)
+{
+    const int t = J.specs[col].type;
+    return fail(ctx, MCR_EINVAL, "%s: column '%s', row %lld: the value is not an integer or is outside the range of %s", who,
+                J.specs[col].name.c_str(), row, t == MCR_PQ_INT32 ? "INT32" : "INT64");
+}
+}  // namespace
+
+int mcr_parquet_write_dev(mcr_ctx* ctx, const mcr_pq_column* cols, int n_cols, int64_t rows, int64_t row_group_rows,
+                          mcr_pq_image** out)
+{
+    static const char* who = "mcr_parquet_write_dev";
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "%s with summaries in flight", who);
+    mcr_pq_image* img = nullptr;
+    try {
+        PqwJob J;
+        int rc = pqw_args(ctx, who, cols, n_cols, rows, row_group_rows, out, J);
+        if (rc) return rc;
+        *out = nullptr;
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const size_t np = J.pages.size(), bound = pqw::image_bound(J.specs, J.pages), blob_cap = bound - J.slots_total;
+        pqw::ColDev* d_cols; pqw::PageW* d_pages; pqw::PageRec* d_recs; unsigned long long* d_err; pqw::Seg* d_segs;
+        unsigned char *d_slots, *d_blob, *d_image;
+        rc = carve_ws(ctx, [&](Carve& cv) {
+            d_cols = cv.take<pqw::ColDev>((size_t)n_cols); d_pages = cv.take<pqw::PageW>(np); d_recs = cv.take<pqw::PageRec>(np);
+            d_err = cv.take<unsigned long long>((size_t)n_cols); d_segs = cv.take<pqw::Seg>(2 * np + 2);
+            d_slots = cv.take<unsigned char>(J.slots_total); d_blob = cv.take<unsigned char>(blob_cap);
+            d_image = cv.take<unsigned char>(bound);
+        });
+        if (rc) return rc;
+        std::vector<pqw::PageW> h_pages(np);
+        for (size_t k = 0; k < np; ++k) h_pages[k] = pqw::PageW{J.pages[k].col, J.pages[k].nrows, J.pages[k].row0, J.slot_off[k]};
+        std::vector<pqw::PageRec> recs(np);
+        std::vector<unsigned long long> h_err((size_t)n_cols);
+        hipStream_t st = ctx->stream;
+        HIP_TRY(ctx, hipMemcpyAsync(d_cols, J.cols.data(), sizeof(pqw::ColDev) * (size_t)n_cols, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(d_pages, h_pages.data(), sizeof(pqw::PageW) * np, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemsetAsync(d_err, 0xFF, 8 * (size_t)n_cols, st));
+        LAUNCH(ctx, K_PQW_ENCODE, pqw::k_pqw_encode, dim3((unsigned)np), dim3(pqw::kNT), 0, (const pqw::ColDev*)d_cols,
+               (const pqw::PageW*)d_pages, d_slots, d_recs, d_err);
+        HIP_TRY(ctx, hipMemcpyAsync(recs.data(), d_recs, sizeof(pqw::PageRec) * np, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(h_err.data(), d_err, 8 * (size_t)n_cols, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        for (int c = 0; c < n_cols; ++c)
+            if (h_err[c] != ~0ull) { prof_resolve(ctx); return pqw_bad_value(ctx, who, J, c, (long long)h_err[c]); }
+        pqw::Layout L;
+        pqw::build_layout(J.specs, J.pages, recs, J.slot_off, (i64)rows, MCR_VERSION, L);
+        if (L.blob.size() > blob_cap || L.image_bytes > bound || L.segs.size() > 2 * np + 2) {
+            prof_resolve(ctx);
+            return fail(ctx, MCR_ENOMEM, "%s: the file image (%zu bytes) exceeds its bound (%zu)", who, L.image_bytes, bound);
+        }
+        for (size_t k = 0; k < np; ++k)
+            if (recs[k].comp_size > pqw::slot_bytes(J.pages[k].uncomp)) return prof_resolve(ctx), fail(ctx, MCR_EHIP, "%s: page %zu overran its slot", who, k);
+        img = new mcr_pq_image();
+        img->size = L.image_bytes; img->pages = (int)np; img->pinned = true;
+        {
+            const hipError_t e = hipHostMalloc((void**)&img->data, L.image_bytes, hipHostMallocDefault);
+            if (e != hipSuccess) { delete img; return fail(ctx, MCR_ENOMEM, "hipHostMalloc(%zu) failed: %s", L.image_bytes, hipGetErrorString(e)); }
+        }
+        auto drop = [&](int code) { hipHostFree(img->data); delete img; return code; };
+        hipError_t e = hipMemcpyAsync(d_blob, L.blob.data(), L.blob.size(), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_segs, L.segs.data(), sizeof(pqw::Seg) * L.segs.size(), hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) return drop(fail(ctx, MCR_EHIP, "%s: upload failed: %s", who, hipGetErrorString(e)));
+        prof_begin(ctx, K_PQW_COMPACT);
+        hipLaunchKernelGGL(pqw::k_pqw_compact, dim3((unsigned)L.segs.size()), dim3(256), 0, st, (const pqw::Seg*)d_segs,
+                           (const unsigned char*)d_slots, (const unsigned char*)d_blob, d_image);
+        prof_end(ctx);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(img->data, d_image, L.image_bytes, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        prof_resolve(ctx);
+        if (e != hipSuccess) return drop(fail(ctx, MCR_EHIP, "%s: compaction failed: %s", who, hipGetErrorString(e)));
+        *out = img;
+    } catch (const std::exception& ex) {
+        return fail(ctx, MCR_ENOMEM, "%s: host allocation failed: %s", who, ex.what());
+    }
+    return MCR_OK;
+}
+
+int mcr_parquet_write_host(mcr_ctx* ctx, const mcr_pq_column* cols, int n_cols, int64_t rows, int64_t row_group_rows,
+                           mcr_pq_image** out)
+{
+    static const char* who = "mcr_parquet_write_host";
+    try {
+        PqwJob J;
+        int rc = pqw_args(ctx, who, cols, n_cols, rows, row_group_rows, out, J);
+        if (rc) return rc;
+        *out = nullptr;
+        const size_t np = J.pages.size();
+        std::vector<unsigned char> payload;
+        std::vector<pqw::PageRec> recs(np);
+        std::vector<u64> at(np);
+        long long bad_row = -1; int bad_col = -1;
+        for (size_t k = 0; k < np; ++k) {
+            const pqw::PagePlan& p = J.pages[k];
+            at[k] = payload.size();
+            const i64 bad = pqw::encode_page_host(J.cols[p.col], pqw::PageW{p.col, p.nrows, p.row0, 0}, payload, recs[k]);
+            if (bad >= 0 && (bad_col < 0 || p.col < bad_col || (p.col == bad_col && bad < bad_row))) { bad_col = p.col; bad_row = bad; }
+            if (bad >= 0) recs[k].comp_size = 0;
+        }
+        if (bad_col >= 0) return pqw_bad_value(ctx, who, J, bad_col, bad_row);
+        pqw::Layout L;
+        pqw::build_layout(J.specs, J.pages, recs, at, (i64)rows, MCR_VERSION, L);
+        mcr_pq_image* img = new mcr_pq_image();
+        img->data = (unsigned char*)malloc(L.image_bytes);
+        if (!img->data) { delete img; return fail(ctx, MCR_ENOMEM, "%s: out of host memory", who); }
+        img->size = L.image_bytes; img->pages = (int)np;
+        for (const pqw::Seg& sg : L.segs)
+            memcpy(img->data + sg.dst_off, (sg.from_blob ? L.blob.data() : payload.data()) + sg.src_off, sg.len);
+        *out = img;
+    } catch (const std::exception& ex) {
+        return fail(ctx, MCR_ENOMEM, "%s: host allocation failed: %s", who, ex.what());
+    }
+    return MCR_OK;
+}
+
+const void* mcr_pq_image_data(const mcr_pq_image* im) { return im ? im->data : nullptr; }
+size_t mcr_pq_image_size(const mcr_pq_image* im) { return im ? im->size : 0; }
+int mcr_pq_image_pages(const mcr_pq_image* im) { return im ? im->pages : -1; }
+void mcr_pq_image_free(mcr_pq_image* im)
+{
+    if (!im) return;
+    if (im->pinned) hipHostFree(im->data); else free(im->data);
+    delete im;
 }
 
 // ---- device row order (mcr_layout.hpp) -------------------------------------------------------------------------

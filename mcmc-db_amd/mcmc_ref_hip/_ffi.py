@@ -67,6 +67,26 @@ class ParquetRequest(C.Structure):
 
 
 MCR_PQ_F64, MCR_PQ_I64 = 0, 1
+MCR_PQ_INT32, MCR_PQ_INT64, MCR_PQ_DOUBLE = 1, 2, 5          # physical types (parquet.thrift)
+MCR_PQW_F64, MCR_PQW_I64, MCR_PQW_SEQ = 0, 1, 2              # sources of a written column
+MCR_PQW_PAGE_ROWS, MCR_PQW_ROW_GROUP_ROWS = 8192, 1048576
+INT64_MAX = (1 << 63) - 1
+
+
+class PqColumn(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("type", C.c_int), ("src_kind", C.c_int), ("src_dev", C.c_void_p),
+                ("stride", C.c_int64), ("seq_div", C.c_int64), ("seq_mod", C.c_int64)]
+
+
+def pq_column(name: str, type_: int, src, stride: int = 1, kind: int | None = None) -> tuple:
+    """A column of write_parquet read from memory: `src` is a device pointer / buffer (Context.write_parquet) or a
+    numpy array of float64 / int64 (write_parquet_host, where kind and stride follow from the array)."""
+    return (name, type_, kind, src, stride, 1, 1)
+
+
+def pq_sequence(name: str, type_: int, div: int = 1, mod: int = INT64_MAX) -> tuple:
+    """A generated column of write_parquet: value(r) = (r // div) % mod."""
+    return (name, type_, MCR_PQW_SEQ, None, 0, div, mod)
 
 
 class IdColumns(C.Structure):
@@ -137,6 +157,12 @@ SYMBOLS = {
     "mcr_parquet_num_pages": (C.c_int, [C.c_void_p]),
     "mcr_parquet_page_info": (C.c_int, [C.c_void_p, C.c_int, _ip]),
     "mcr_parquet_decode": (C.c_int, [C.c_void_p, C.POINTER(ParquetRequest), C.c_int]),
+    "mcr_parquet_write_dev": (C.c_int, [C.c_void_p, C.POINTER(PqColumn), C.c_int, _I64, _I64, C.POINTER(C.c_void_p)]),
+    "mcr_parquet_write_host": (C.c_int, [C.c_void_p, C.POINTER(PqColumn), C.c_int, _I64, _I64, C.POINTER(C.c_void_p)]),
+    "mcr_pq_image_data": (C.c_void_p, [C.c_void_p]),
+    "mcr_pq_image_size": (C.c_size_t, [C.c_void_p]),
+    "mcr_pq_image_pages": (C.c_int, [C.c_void_p]),
+    "mcr_pq_image_free": (None, [C.c_void_p]),
     "mcr_gather_rows_dev": (C.c_int, [C.c_void_p, C.c_void_p, _I64, _I64, _ip, C.c_void_p]),
     "mcr_chain_layout_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _I64, C.c_void_p, _ip, _ip, C.c_int,
                                        C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -280,6 +306,75 @@ def tensor_args(draws: np.ndarray, layout: str):
     if any(s < 0 for s in strides):
         raise ValueError("negative strides are not supported")
     return (code, *dims, *strides)
+
+
+class PqImage:
+    """A Parquet file image the library owns (mcr_pq_image): `view` is its bytes without a copy, valid until close()."""
+
+    def __init__(self, lib, handle):
+        self.lib, self.handle = lib, handle
+        self.size = int(lib.mcr_pq_image_size(handle))
+        self.pages = int(lib.mcr_pq_image_pages(handle))
+        self.view = memoryview((C.c_ubyte * self.size).from_address(lib.mcr_pq_image_data(handle))).cast("B")
+
+    def tobytes(self) -> bytes:
+        return self.view.tobytes()
+
+    def __len__(self):
+        return self.size
+
+    def close(self):
+        if self.handle:
+            self.view.release()
+            self.view = None
+            self.lib.mcr_pq_image_free(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):  # pragma: no cover - best effort
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _pq_columns(columns, host: bool):
+    """(PqColumn array, objects to keep alive) of pq_column / pq_sequence tuples."""
+    arr = (PqColumn * max(len(columns), 1))()
+    keep = []
+    for k, (name, type_, kind, src, stride, div, mod) in enumerate(columns):
+        if kind != MCR_PQW_SEQ and host:
+            a = np.asarray(src)
+            if a.ndim != 1 or a.dtype not in (np.float64, np.int64) or (a.size and a.strides[0] % 8) or (a.size and a.strides[0] < 8):
+                raise ValueError(f"column {name!r}: a 1-D float64 or int64 array with a positive stride is needed")
+            keep.append(a)
+            kind = MCR_PQW_F64 if a.dtype == np.float64 else MCR_PQW_I64
+            stride = a.strides[0] // 8 if a.size else 1
+            src = a.ctypes.data
+        elif kind != MCR_PQW_SEQ:
+            if kind is None:
+                raise ValueError(f"column {name!r}: kind (MCR_PQW_F64 or MCR_PQW_I64) is needed for device memory")
+            src = getattr(src, "ptr", src)
+            src = src.value if isinstance(src, C.c_void_p) else src
+        keep.append(str(name).encode())
+        arr[k] = PqColumn(keep[-1], int(type_), int(kind), src, int(stride), int(div), int(mod))
+    return arr, keep
+
+
+def write_parquet_host(columns, rows: int, row_group_rows: int = 0) -> PqImage:
+    """mcr_parquet_write_host: the Parquet image of host columns (numpy arrays or pq_sequence), without a device."""
+    lib = load_library()
+    arr, _keep = _pq_columns(columns, host=True)
+    h = C.c_void_p()
+    rc = lib.mcr_parquet_write_host(None, arr, len(columns), int(rows), int(row_group_rows), C.byref(h))
+    if rc != MCR_OK:
+        raise McrError(rc, (lib.mcr_last_error(None) or b"").decode())
+    return PqImage(lib, h)
 
 
 class DeviceBuffer:
@@ -555,6 +650,14 @@ class Context:
         nch, ino = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
         self._check(self.lib.mcr_chain_layout_many_dev(self.handle, arr, n, _as_ip(ids), _as_ip(counts), int(cap), nch, ino))
         return [(ids[i, :nch[i]].copy(), counts[i, :nch[i]].copy()) if ino[i] and nch[i] <= cap else None for i in range(n)]
+
+    def write_parquet(self, columns, rows: int, row_group_rows: int = 0) -> PqImage:
+        """mcr_parquet_write_dev: the Parquet image of `rows` rows of device columns (pq_column / pq_sequence tuples), encoded and
+        compressed on the GPU.  Close the image (or use it as a context manager) to free its pinned memory."""
+        arr, _keep = _pq_columns(columns, host=False)
+        h = C.c_void_p()
+        self._check(self.lib.mcr_parquet_write_dev(self.handle, arr, len(columns), int(rows), int(row_group_rows), C.byref(h)))
+        return PqImage(self.lib, h)
 
     def gather_rows_order(self, src_ptr, P: int, M: int, order_ptr, dst_ptr):
         """dst[p][k] = src[p][order[k]], everything in device memory (mcr_gather_rows_order_dev)."""

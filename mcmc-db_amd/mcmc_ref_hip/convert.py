@@ -216,9 +216,36 @@ def _json_table(params: list[str], flat: np.ndarray, n_chains: int, n_draws: int
     return pa.table(cols)
 
 
-def _read_json_zip_prepared(path: Path, min_chains: int, context):
+def _writer_choice(writer: str) -> str:
+    """"auto" or "host" of convert_files' `writer`; the environment variable MCMC_REF_HIP_WRITER=arrow forces "host".
+    "auto" has no size threshold: text to both files, median [range] of 9 alternating runs on one MI355X
+    (profiles/parquet_write.json), the device writer took 36.5 ms [34.0 - 43.5] against 150 ms [145 - 158] at
+    4 x 10 000 x 100 and 1.60 ms [1.50 - 2.50] against 2.34 ms [2.23 - 2.63] at 4 x 1 000 x 10."""
+    import os
+    if writer not in ("auto", "host"):
+        raise ValueError(f"writer must be 'auto' or 'host'; got {writer!r}")
+    return "host" if os.environ.get("MCMC_REF_HIP_WRITER", "") == "arrow" else writer
+
+
+def _json_image(ctx, params: list[str], t, int_columns: list[bool]):
+    """The draws file `_json_table` + pq.write_table give, encoded on the device from the resident [P][C][N] tensor
+    (Context.write_parquet): chain and draw generated, a parameter int64 where every draw is an integer literal."""
+    _, n_chains, n_draws, _P, stride_c, stride_n, stride_p = t.targs
+    if stride_c != n_draws * stride_n:
+        return None                                        # rows of a parameter not evenly spaced: the table route
+    cols = [_ffi.pq_sequence("chain", _ffi.MCR_PQ_INT64, div=n_draws), _ffi.pq_sequence("draw", _ffi.MCR_PQ_INT64, mod=n_draws)]
+    base = t.buf.ptr.value
+    for k, (p, is_int) in enumerate(zip(params, int_columns)):
+        cols.append(_ffi.pq_column(p, _ffi.MCR_PQ_INT64 if is_int else _ffi.MCR_PQ_DOUBLE, base + 8 * k * stride_p, stride_n,
+                                   _ffi.MCR_PQW_F64))
+    with _ffi.value_errors():
+        return ctx.write_parquet(cols, n_chains * n_draws)
+
+
+def _read_json_zip_prepared(path: Path, min_chains: int, context, writer: str = "host"):
     """A `.json.zip` input of convert_files through the device reader: the `prepared` entry with the draws resident
-    (a DeviceTensor in place of the host matrix), or None for the host route."""
+    (a DeviceTensor in place of the host matrix), or None for the host route.  writer="auto": the entry holds the
+    encoded draws file (a PqImage) in place of the table, and nothing is downloaded."""
     try:
         ctx = context or _ffi.default_context()
     except _ffi.HipUnavailableError:
@@ -234,8 +261,10 @@ def _read_json_zip_prepared(path: Path, min_chains: int, context):
             return None
         if n_chains < min_chains:
             raise ValueError(f"R-hat diagnostics require at least {min_chains} chains; got {n_chains} chain(s)")
-        flat = t.buf.download(np.float64, P * n_chains * n_draws).reshape(P, n_chains * n_draws)
-        table = _json_table(params, flat, n_chains, n_draws, int_columns)
+        table = _json_image(ctx, params, t, int_columns) if writer == "auto" else None
+        if table is None:
+            flat = t.buf.download(np.float64, P * n_chains * n_draws).reshape(P, n_chains * n_draws)
+            table = _json_table(params, flat, n_chains, n_draws, int_columns)
     except BaseException:
         t.free()
         raise
@@ -387,20 +416,53 @@ def _csv_table(d, flat: np.ndarray, int_columns, header, ids):
     return pa.table(cols)
 
 
-def _csv_prepared(ctx, got, min_chains: int):
-    """The `prepared` entry of convert_files for one file of read_csv_many_dev (the draws resident)."""
+def _csv_image(ctx, fbuf, M: int, int_columns, header, ids):
+    """The draws file `_ensure_chain_draw(_csv_table(...))` + pq.write_table give, encoded on the device from the resident
+    file-order [P][M] values (Context.write_parquet): the file's columns in its order, int64 where every literal is an
+    integer, the id columns from the file (16 bytes per row go back up: the layout step downloaded and freed them), and
+    the bookkeeping columns `_ensure_chain_draw` appends as generated int32 columns, in its positions."""
+    cols, made, k = [], [], 0
+    try:
+        for name in header:
+            if name in ("chain", "draw"):
+                made.append(_ffi.DeviceBuffer(ctx, max(M * 8, 8)).upload(np.ascontiguousarray(ids[name == "draw"], dtype=np.int64)))
+                cols.append(_ffi.pq_column(name, _ffi.MCR_PQ_INT64, made[-1], 1, _ffi.MCR_PQW_I64))
+            else:
+                cols.append(_ffi.pq_column(name, _ffi.MCR_PQ_INT64 if int_columns[k] else _ffi.MCR_PQ_DOUBLE,
+                                           fbuf.ptr.value + 8 * k * M, 1, _ffi.MCR_PQW_F64))
+                k += 1
+        if "chain" not in header:
+            cols.append(_ffi.pq_sequence("chain", _ffi.MCR_PQ_INT32, mod=1))
+        if "draw" not in header:
+            cols.append(_ffi.pq_sequence("draw", _ffi.MCR_PQ_INT32))
+        with _ffi.value_errors():
+            return ctx.write_parquet(cols, M)
+    finally:
+        for b in made:
+            b.free()
+
+
+def _csv_prepared(ctx, got, min_chains: int, writer: str = "host"):
+    """The `prepared` entry of convert_files for one file of read_csv_many_dev (the draws resident).  writer="auto": the
+    entry holds the encoded draws file (a PqImage) in place of the table, and the matrix is not downloaded."""
     d, fbuf, int_columns, header, ids = got
+    table = None
     try:
         P, M = len(d.params), int(d.counts.sum())
-        flat = fbuf.download(np.float64, P * M).reshape(P, M)
+        if writer == "auto":
+            table = _csv_image(ctx, fbuf, M, int_columns, header, ids)
+        else:
+            flat = fbuf.download(np.float64, P * M).reshape(P, M)
+            table = _ensure_chain_draw(_csv_table(d, flat, int_columns, header, ids))
         fbuf.free()
         fbuf = None
-        table = _ensure_chain_draw(_csv_table(d, flat, int_columns, header, ids))
         if d.params and len(d.counts) < min_chains:
             raise ValueError(f"R-hat diagnostics require at least {min_chains} chains; got {len(d.counts)} chain(s)")
         t = d.tensor if d.rectangular else ctx.ragged_tensor(d.buf, d.counts, P)
         return table, d.params, int(len(d.counts)), int(d.counts.min()), t, d.counts
     except BaseException:
+        if isinstance(table, _ffi.PqImage):
+            table.close()
         d.free()
         if fbuf is not None:
             fbuf.free()
@@ -410,7 +472,7 @@ def _csv_prepared(ctx, got, min_chains: int):
 _CSV_BATCH_BYTES = 3 << 30     # text of the .csv jobs read by one library call (its limit is 4 GiB less 1 MiB, padding included)
 
 
-def _read_csv_prepared_many(paths, min_chains: int, context) -> dict:
+def _read_csv_prepared_many(paths, min_chains: int, context, writer: str = "host") -> dict:
     """The `.csv` inputs of convert_files through the device reader: {index into paths: `prepared` entry or the
     exception of the job}; a path that is missing from it takes the host route, which is the source of every exception
     of the read itself.  The files share one read and one parse, in groups of at most _CSV_BATCH_BYTES of text (the
@@ -461,7 +523,7 @@ def _read_csv_prepared_many(paths, min_chains: int, context) -> dict:
             g[1].free()
             continue
         try:
-            done[i] = _csv_prepared(ctx, g, min_chains)
+            done[i] = _csv_prepared(ctx, g, min_chains, writer)
         except Exception as exc:  # noqa: BLE001 - reported per job
             done[i] = exc
     return done
@@ -530,7 +592,7 @@ def _ensure_chain_draw(table):
 
 
 def convert_files(jobs, out_draws_dir: Path, out_meta_dir: Path, force: bool = False, source: str = "converted",
-                  context=None, reader: str = "auto") -> list:
+                  context=None, reader: str = "auto", writer: str = "auto") -> list:
     """`convert_file` for many inputs with the kernels pipelined: jobs = [(input_path, name), ...]; returns, per job,
     a ConvertResult or the exception that `convert_file` would have raised for it (the per-recipe try/except of
     generate.generate_reference_corpus, src/mcmc_ref/generate.py:77-96, becomes per-entry results).
@@ -543,17 +605,23 @@ def convert_files(jobs, out_draws_dir: Path, out_meta_dir: Path, force: bool = F
     All inputs are read and laid out first, the models are uploaded and enqueued with a rolling window of
     MCR_MAX_INFLIGHT calls (consecutive models overlap on the context's lanes; a NaN draw or any other kernel-side
     failure stays confined to its model) -- rectangular models and models whose chains differ in length alike, the
-    latter through the ragged entry point -- then the quality gate and the two files of every model are written."""
+    latter through the ragged entry point -- then the quality gate and the two files of every model are written.
+
+    writer="auto": the draws file of a job that was read on the device is encoded and compressed on the device too, while
+    its matrix is resident (Context.write_parquet: neither the matrix nor an Arrow table reaches the host), and kept
+    as host bytes until the gate has passed.  A job read on the host, and every job with writer="host" or with the
+    environment variable MCMC_REF_HIP_WRITER=arrow, is written by `pq.write_table`.  Both give the same table."""
     import pyarrow.parquet as pq
     out_draws_dir, out_meta_dir = Path(out_draws_dir), Path(out_meta_dir)
     if reader not in ("auto", "host"):
         raise ValueError(f"reader must be 'auto' or 'host'; got {reader!r}")
+    writer = _writer_choice(writer)
     min_chains = 1 if force else 4
     n = len(jobs)
     results: list = [None] * n
     prepared: dict[int, tuple] = {}
     csv_jobs = [i for i, (p, _name) in enumerate(jobs) if reader == "auto" and Path(p).suffix == ".csv"]
-    csv_done = _read_csv_prepared_many([Path(jobs[i][0]) for i in csv_jobs], min_chains, context) if csv_jobs else {}
+    csv_done = _read_csv_prepared_many([Path(jobs[i][0]) for i in csv_jobs], min_chains, context, writer) if csv_jobs else {}
     for k, got in csv_done.items():
         if isinstance(got, Exception):
             results[csv_jobs[k]] = got
@@ -564,7 +632,7 @@ def convert_files(jobs, out_draws_dir: Path, out_meta_dir: Path, force: bool = F
             continue
         try:
             if reader == "auto" and _is_json_zip(Path(input_path)):
-                got = _read_json_zip_prepared(Path(input_path), min_chains, context)
+                got = _read_json_zip_prepared(Path(input_path), min_chains, context, writer)
                 if got is not None:
                     prepared[i] = got
                     continue
@@ -620,7 +688,10 @@ def convert_files(jobs, out_draws_dir: Path, out_meta_dir: Path, force: bool = F
         for i in resident:
             prepared[i][4].free()
     for i, (table, params, n_chains, n_draws, _x, _counts) in prepared.items():
+        image = table if isinstance(table, _ffi.PqImage) else None        # encoded on the device: host bytes by now
         if results[i] is not None:
+            if image is not None:
+                image.close()
             continue
         name = jobs[i][1]
         try:
@@ -632,11 +703,17 @@ def convert_files(jobs, out_draws_dir: Path, out_meta_dir: Path, force: bool = F
                     "source": source}
             draws_path = out_draws_dir / f"{name}.draws.parquet"
             meta_path = out_meta_dir / f"{name}.meta.json"
-            pq.write_table(table, draws_path)
+            if image is not None:
+                draws_path.write_bytes(image.view)
+            else:
+                pq.write_table(table, draws_path)
             meta_path.write_text(json.dumps(meta, indent=2, sort_keys=True))
             results[i] = ConvertResult(draws_path=draws_path, meta_path=meta_path, meta=meta)
         except Exception as exc:  # noqa: BLE001
             results[i] = exc
+        finally:
+            if image is not None:
+                image.close()
     return results
 
 

@@ -276,6 +276,15 @@ def read_columns(ctx: "_ffi.Context", source, columns: Iterable[str] | None = No
             f.close()
 
 
+def write_draws_dev(ctx: "_ffi.Context", path, columns, rows: int, row_group_rows: int = 0) -> int:
+    """Writes `rows` rows of device columns (_ffi.pq_column / _ffi.pq_sequence) as a Parquet draws file, encoded and
+    compressed on the GPU (Context.write_parquet); the replacement of `pq.write_table` (src/mcmc_ref/convert.py:64).
+    Returns the file's size."""
+    with ctx.write_parquet(columns, rows, row_group_rows) as image:
+        Path(path).write_bytes(image.view)
+        return len(image)
+
+
 def _summarize_paths(ctx: "_ffi.Context", paths: list[str], min_chains: int, qs: list[float], diagnostics: bool,
                      phases: dict | None = None):
     """All of summarize_files in ONE C call (Context.summarize_files).  Returns None when a file needs the general
