@@ -599,7 +599,8 @@ typedef struct mcr_json mcr_json;
 #define MCR_JSON_PARSE_BLOCK 256  /* array elements one workgroup of the element parser converts */
 
 /* Uploads the document, runs the structural index and the skeleton walk.  The caller keeps `bytes` alive and unchanged
- * until mcr_json_close, and closes the handle before the context is freed. */
+ * until mcr_json_close, and closes the handle before the context is freed.  It invalidates files staged by mcr_csv_stage
+ * and handles of mcr_csv_open_paths (the index borrows the staged row table): open and stage them again before a decode. */
 int mcr_json_open(mcr_ctx* ctx, const void* bytes, size_t len, mcr_json** out);
 void mcr_json_close(mcr_json* f);
 int mcr_json_num_chains(const mcr_json* f);

@@ -72,9 +72,27 @@ const char* const kKernelNames[K_COUNT] = {
 
 struct EvPair { hipEvent_t a, b; int kid; };
 
+// The owners of the library's memory: DevBuf (hipMalloc) and PinBuf (pinned host memory, hipHostMalloc).  Move-only; the
+// destructor frees.  reserve is the one growth rule (defined behind the context, whose streams it waits for).
+template <bool kPinned> struct Buf {
+    void* p = nullptr; size_t cap = 0;       // bytes
+    size_t slack_div = 0;                    // reserve allocates bytes + bytes / slack_div, so that near-equal sizes do not
+                                             // reallocate (0: the exact size)
+    explicit Buf(size_t slack = 0) : slack_div(slack) {}
+    Buf(const Buf&) = delete;
+    Buf& operator=(const Buf&) = delete;
+    Buf(Buf&& o) noexcept : p(o.p), cap(o.cap), slack_div(o.slack_div) { o.p = nullptr; o.cap = 0; }
+    Buf& operator=(Buf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); std::swap(slack_div, o.slack_div); return *this; }
+    ~Buf() { release(); }
+    void release() { if (p) { kPinned ? hipHostFree(p) : hipFree(p); } p = nullptr; cap = 0; }
+    template <typename T> T* as() const { return static_cast<T*>(p); }
+    int reserve(mcr_ctx* ctx, size_t bytes);
+};
+using DevBuf = Buf<false>;
+using PinBuf = Buf<true>;
+
 struct Slot {
-    double* d_res = nullptr; double* h_res = nullptr; size_t res_cap = 0;   // doubles
-    i64* d_off = nullptr; i64* h_off = nullptr; size_t off_cap = 0;          // entries
+    DevBuf d_res, d_off; PinBuf h_res, h_off;   // result table (doubles) and chain offsets (i64): device, pinned host
     i64 off_C = -1, off_N = -1;     // regular chain offsets c * N already resident in d_off (no upload per call)
     mcr_summary out{};
     i64 P = 0; int nq = 0;
@@ -93,44 +111,63 @@ struct mcr_ctx {
     hipStream_t stream = nullptr;
     char err[512] = "";
     size_t ws_limit = 0;
-    void* ws = nullptr; size_t ws_bytes = 0;          // workspace of the CURRENT lane (see use_lane)
     // Lanes = streams with a workspace each (MCR_LANES, default 4): consecutive enqueues rotate lanes, so the
     // tail of one call's kernels (partial last waves of workgroups) overlaps the next call's head.
-    hipStream_t lane_stream[MCR_MAX_INFLIGHT] = {};
-    hipStream_t lane_aux[MCR_MAX_INFLIGHT] = {};      // second stream of a lane + its fork / join events (lone calls: run_pipeline)
-    hipEvent_t lane_fork[MCR_MAX_INFLIGHT] = {}, lane_join[MCR_MAX_INFLIGHT] = {};
+    struct Lane {
+        hipStream_t stream = nullptr;
+        hipStream_t aux = nullptr;                     // second stream + its fork / join events (lone calls: run_pipeline)
+        hipEvent_t fork = nullptr, join = nullptr;
+        DevBuf ws{8};
+        Lane() = default;
+        Lane(const Lane&) = delete;
+        ~Lane()
+        {
+            for (hipStream_t s : {stream, aux}) if (s) hipStreamDestroy(s);
+            for (hipEvent_t e : {fork, join}) if (e) hipEventDestroy(e);
+        }
+    };
+    Lane lanes[MCR_MAX_INFLIGHT];
+    int lane = 0, n_lanes = 4;                        // the current lane: `stream` is its stream, or for a forked half its aux
     bool fork_lone = true;                            // MCR_FORK=0: never fork
-    void* lane_ws[MCR_MAX_INFLIGHT] = {};
-    size_t lane_ws_bytes[MCR_MAX_INFLIGHT] = {};
-    int lane = 0, n_lanes = 4;
-    void* stage = nullptr; size_t stage_bytes = 0;  // device copy of host tensors (mcr_summarize)
-    hipStream_t copy_stream = nullptr;              // uploads of mcr_summarize, overlapped with the lanes' kernels
-    // Parquet ingest (mcr_parquet_decode): uploaded column chunks, decompression scratch, page table + error word
-    void* pq_stage = nullptr; size_t pq_stage_bytes = 0;
-    void* pq_scratch = nullptr; size_t pq_scratch_bytes = 0;
-    void* pq_tab = nullptr; size_t pq_tab_bytes = 0;
-    void* fs_arena = nullptr; size_t fs_arena_bytes = 0;   // mcr_summarize_files: decoded draws + chain / draw ids
-    void* pq_pin = nullptr; size_t pq_pin_bytes = 0;       // mcr_summarize_files: pinned host staging of the files' column chunks
-    // CSV ingest (mcr_csv_*): the text of a call lives in pq_pin / pq_stage like the draws files' images.  img_gen counts
-    // the times these two were rewritten: handles of mcr_csv_open_paths and the staged line index hold the value they saw.
-    uint64_t img_gen = 0;
-    struct CsvFile { size_t img, len, body; int ncols; std::string path; };
-    std::vector<CsvFile> csv_files; std::vector<uint32_t> csv_row0;      // staged files, first data row of each (+ total)
-    uint64_t csv_staged_gen = 0; bool csv_staged = false;
-    bool csv_table = false;                                              // the staged files are table CSVs (mcr_csv_open_table*)
-    size_t csv_row0_off = 0;                                             // file_row0 within csv_tab
-    void* csv_tab = nullptr; size_t csv_tab_bytes = 0;                   // FileDesc, chunk -> file, chunk counts / first rows, file_row0
-    void* csv_rows = nullptr; size_t csv_rows_bytes = 0;                 // start offset of every data row
-    void* csv_aux = nullptr; size_t csv_aux_bytes = 0;                   // decode: slot tables, hard list, counters, patch list
-    void* csv_pow5 = nullptr;                                            // device copy of csv::kPow5
+    DevBuf stage;                                     // device copy of host tensors (mcr_summarize)
+    hipStream_t copy_stream = nullptr;                // uploads of mcr_summarize, overlapped with the lanes' kernels
+    // Parquet ingest (mcr_parquet_decode): decompression scratch, page table + page lists + error word
+    DevBuf pq_scratch{4}, pq_tab{4};
+    DevBuf fs_arena{4};                               // mcr_summarize_files: decoded draws + chain / draw ids
+    // The file bytes of an ingest call -- the column chunks or whole images of draws files, the text of CSV files -- and what
+    // mcr_csv_stage derives from the text.  gen counts the times any of it was handed out for writing (rewrite, the only way
+    // to write it from outside mcr_csv_stage): the handles of mcr_csv_open_paths and the staged tables hold the value they saw.
+    struct FileImage {
+        PinBuf pin{4};                                // the bytes in pinned host memory (mcr_summarize_files, mcr_csv_*)
+        DevBuf dev{4};                                // their device copy
+        DevBuf tab{4};                                // staged: FileDesc, chunk -> file, chunk counts / first rows, file_row0
+        DevBuf rows{4};                               // staged: start offset of every data row
+        uint64_t gen = 0;
+        struct File { size_t img, len, body; int ncols; std::string path; };
+        std::vector<File> files; std::vector<uint32_t> row0;             // staged files, first data row of each (+ total)
+        uint64_t staged_gen = 0; bool staged = false;
+        bool table = false;                           // the staged files are table CSVs (mcr_csv_open_table*)
+        size_t row0_off = 0;                          // file_row0 within tab
+        bool is_staged() const { return staged && staged_gen == gen; }
+        // Room for a call's bytes on the device, in pinned memory, and for row starts: whatever was opened or staged is gone.
+        int rewrite(mcr_ctx* ctx, size_t dev_bytes, size_t pin_bytes, size_t rows_bytes)
+        {
+            ++gen;
+            int rc = dev.reserve(ctx, dev_bytes);
+            if (!rc) rc = pin.reserve(ctx, pin_bytes);
+            return rc ? rc : rows.reserve(ctx, rows_bytes);
+        }
+    } img;
+    DevBuf parse_scratch{4};   // a text decoder's call: slot tables, hard list, counters, patch list; mcr_json_open: chunk counts
+    DevBuf pow5;               // device copy of csv::kPow5
     uint32_t csv_hard_cap = 4096;
     int io_threads = 8;                                    // MCR_IO_THREADS: host threads that read the file images and parse their footers
     size_t io_piece = (size_t)2 << 20;                     // MCR_IO_PIECE_KB: the finished prefix is uploaded in pieces of at least this size
     // z tables (k_ztable): a function of M alone, so they are computed once per pooled length and kept for the life of
     // the context instead of being relaunched by every call (most recently used first; a handful of shapes is typical)
-    struct ZTab { i64 M; double* tab; };
+    struct ZTab { i64 M; DevBuf tab; };
     std::vector<ZTab> ztabs;
-    struct Twiddle { int L; double2* tab; };          // exp(-2 pi i t / L), t < L / 2, per sub-transform length (mcr_fft.hpp)
+    struct Twiddle { int L; DevBuf tab; };          // exp(-2 pi i t / L), t < L / 2, per sub-transform length (mcr_fft.hpp)
     std::vector<Twiddle> twiddles;
     Slot slots[MCR_MAX_INFLIGHT];
     int next_slot = 0;
@@ -144,7 +181,7 @@ struct mcr_ctx {
     bool f32_records = true; // MCR_F32_RECORDS=0: f32 tensors take the f64 kernels (widened by the tile sort) instead of mcr_sort32.hpp
     bool splitters_pairwise = false;   // MCR_SPLITTERS_PAIRWISE=1: rank the regular samples pair by pair whatever their number (A/B, parity tests)
     double rho_band = kRhoBand;   // MCR_RHO_BAND: half-width of the guard band of the tier-3 scan (0 = decide on the raw values)
-    unsigned* guard_count = nullptr;   // device counter: band lags re-derived the reference's way (mcr_rho_guard_count)
+    DevBuf guard_count;                // device counter (unsigned): band lags re-derived the reference's way (mcr_rho_guard_count)
 };
 
 namespace {
@@ -210,33 +247,39 @@ void prof_resolve(mcr_ctx* ctx)
 
 void use_lane(mcr_ctx* ctx, int lane)
 {
-    ctx->lane_ws[ctx->lane] = ctx->ws; ctx->lane_ws_bytes[ctx->lane] = ctx->ws_bytes;   // save current
     ctx->lane = lane;
-    ctx->stream = ctx->lane_stream[lane];
-    ctx->ws = ctx->lane_ws[lane]; ctx->ws_bytes = ctx->lane_ws_bytes[lane];
+    ctx->stream = ctx->lanes[lane].stream;
 }
-void sync_all(mcr_ctx* ctx)
+inline DevBuf& lane_ws(mcr_ctx* ctx) { return ctx->lanes[ctx->lane].ws; }
+
+// Every stream of the context idle (ctx->stream is always one of them); the first failure.
+hipError_t sync_all(mcr_ctx* ctx)
 {
-    for (hipStream_t s : ctx->lane_aux) if (s) hipStreamSynchronize(s);     // (joined into the lane's stream in normal operation)
-    for (hipStream_t s : ctx->lane_stream) if (s) hipStreamSynchronize(s);
+    hipError_t first = hipSuccess;
+    auto sync = [&](hipStream_t s) { const hipError_t e = s ? hipStreamSynchronize(s) : hipSuccess; if (first == hipSuccess) first = e; };
+    for (const mcr_ctx::Lane& l : ctx->lanes) { sync(l.aux); sync(l.stream); }    // (aux is joined into the lane's stream in normal operation)
+    sync(ctx->copy_stream);
+    return first;
 }
 
-int ensure_ws(mcr_ctx* ctx, size_t bytes)
+// The one growth rule.  Large enough: nothing happens.  Otherwise everything that can touch the old allocation finishes
+// first (growth is amortised, and hipFree synchronises the device anyway), then the buffer is replaced by one of the new
+// size plus its slack, or of the exact size when that is out of memory.  The contents are not kept.
+template <bool kPinned> int Buf<kPinned>::reserve(mcr_ctx* ctx, size_t bytes)
 {
-    if (bytes <= ctx->ws_bytes) return MCR_OK;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    sync_all(ctx);
-    if (ctx->ws) { hipFree(ctx->ws); ctx->ws = nullptr; ctx->ws_bytes = 0; }
-    const size_t want = bytes + (bytes >> 3);  // a little slack so near-equal shapes do not realloc
-    hipError_t e = hipMalloc(&ctx->ws, want);
+    if (bytes <= cap) return MCR_OK;
+    if (p) HIP_TRY(ctx, sync_all(ctx));
+    release();
+    auto alloc = [&](size_t n) { return kPinned ? hipHostMalloc(&p, n, hipHostMallocDefault) : hipMalloc(&p, n); };
+    size_t want = bytes + (slack_div ? bytes / slack_div : 0);
+    hipError_t e = alloc(want);
+    if (e != hipSuccess && want > bytes) { (void)hipGetLastError(); e = alloc(want = bytes); }     // (the launches check the last error)
     if (e != hipSuccess) {
-        e = hipMalloc(&ctx->ws, bytes);
-        if (e != hipSuccess) return fail(ctx, MCR_ENOMEM, "workspace hipMalloc(%zu) failed: %s", bytes,
-                                         hipGetErrorString(e));
-        ctx->ws_bytes = bytes;
-    } else {
-        ctx->ws_bytes = want;
+        p = nullptr;
+        return fail(ctx, e == hipErrorOutOfMemory ? MCR_ENOMEM : MCR_EHIP, "%s(%zu) failed: %s", kPinned ? "hipHostMalloc" : "hipMalloc",
+                    bytes, hipGetErrorString(e));
     }
+    cap = want;
     return MCR_OK;
 }
 
@@ -246,25 +289,23 @@ int get_ztab(mcr_ctx* ctx, i64 M, double** out)
 {
     for (size_t k = 0; k < ctx->ztabs.size(); ++k)
         if (ctx->ztabs[k].M == M) {
-            const mcr_ctx::ZTab hit = ctx->ztabs[k];
-            ctx->ztabs.erase(ctx->ztabs.begin() + (long)k);
-            ctx->ztabs.insert(ctx->ztabs.begin(), hit);
-            *out = hit.tab;
+            std::rotate(ctx->ztabs.begin(), ctx->ztabs.begin() + (long)k, ctx->ztabs.begin() + (long)k + 1);
+            *out = ctx->ztabs[0].tab.as<double>();
             return MCR_OK;
         }
     if (ctx->ztabs.size() >= kMaxZTabs) {           // the evicted table may still be read by a call in flight
         sync_all(ctx);
-        hipFree(ctx->ztabs.back().tab);
         ctx->ztabs.pop_back();
     }
-    double* tab = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&tab, sizeof(double) * (size_t)(2 * M > 2 ? 2 * M : 2)));
-    hipLaunchKernelGGL(k_ztable, dim3((unsigned)((2 * M + 255) / 256)), dim3(256), 0, ctx->stream, tab, M);
+    mcr_ctx::ZTab z{M, DevBuf()};
+    const int rc = z.tab.reserve(ctx, sizeof(double) * (size_t)(2 * M > 2 ? 2 * M : 2));
+    if (rc) return rc;
+    *out = z.tab.as<double>();
+    hipLaunchKernelGGL(k_ztable, dim3((unsigned)((2 * M + 255) / 256)), dim3(256), 0, ctx->stream, *out, M);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);     // other lanes will read it: complete before anyone can
-    if (e != hipSuccess) { hipFree(tab); return fail(ctx, MCR_EHIP, "k_ztable failed: %s", hipGetErrorString(e)); }
-    ctx->ztabs.insert(ctx->ztabs.begin(), mcr_ctx::ZTab{M, tab});
-    *out = tab;
+    if (e != hipSuccess) return fail(ctx, MCR_EHIP, "k_ztable failed: %s", hipGetErrorString(e));
+    ctx->ztabs.insert(ctx->ztabs.begin(), std::move(z));
     return MCR_OK;
 }
 
@@ -272,15 +313,16 @@ int get_ztab(mcr_ctx* ctx, i64 M, double** out)
 int get_twiddles(mcr_ctx* ctx, int L, double2** out)
 {
     for (const mcr_ctx::Twiddle& t : ctx->twiddles)
-        if (t.L == L) { *out = t.tab; return MCR_OK; }
-    double2* tab = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&tab, sizeof(double2) * (size_t)(L / 2 > 1 ? L / 2 : 1)));
-    hipLaunchKernelGGL(fft::k_fft_twiddles, dim3((unsigned)((L / 2 + 255) / 256)), dim3(256), 0, ctx->stream, tab, L);
+        if (t.L == L) { *out = t.tab.as<double2>(); return MCR_OK; }
+    mcr_ctx::Twiddle t{L, DevBuf()};
+    const int rc = t.tab.reserve(ctx, sizeof(double2) * (size_t)(L / 2 > 1 ? L / 2 : 1));
+    if (rc) return rc;
+    *out = t.tab.as<double2>();
+    hipLaunchKernelGGL(fft::k_fft_twiddles, dim3((unsigned)((L / 2 + 255) / 256)), dim3(256), 0, ctx->stream, *out, L);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { hipFree(tab); return fail(ctx, MCR_EHIP, "k_fft_twiddles failed: %s", hipGetErrorString(e)); }
-    ctx->twiddles.push_back(mcr_ctx::Twiddle{L, tab});
-    *out = tab;
+    if (e != hipSuccess) return fail(ctx, MCR_EHIP, "k_fft_twiddles failed: %s", hipGetErrorString(e));
+    ctx->twiddles.push_back(std::move(t));
     return MCR_OK;
 }
 
@@ -306,27 +348,12 @@ FftPlan plan_fft(i64 n, int C, bool enabled)
 
 int ensure_slot(mcr_ctx* ctx, Slot& s, size_t res_doubles, size_t off_entries)
 {
-    if (res_doubles > s.res_cap || off_entries > s.off_cap) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        sync_all(ctx);
-    }
-    if (res_doubles > s.res_cap) {
-        if (s.d_res) hipFree(s.d_res);
-        if (s.h_res) hipHostFree(s.h_res);
-        s.d_res = nullptr; s.h_res = nullptr; s.res_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&s.d_res, res_doubles * sizeof(double)));
-        HIP_TRY(ctx, hipHostMalloc((void**)&s.h_res, res_doubles * sizeof(double), hipHostMallocDefault));
-        s.res_cap = res_doubles;
-    }
-    if (off_entries > s.off_cap) {
-        if (s.d_off) hipFree(s.d_off);
-        if (s.h_off) hipHostFree(s.h_off);
-        s.d_off = nullptr; s.h_off = nullptr; s.off_cap = 0; s.off_C = s.off_N = -1;
-        HIP_TRY(ctx, hipMalloc((void**)&s.d_off, off_entries * sizeof(i64)));
-        HIP_TRY(ctx, hipHostMalloc((void**)&s.h_off, off_entries * sizeof(i64), hipHostMallocDefault));
-        s.off_cap = off_entries;
-    }
-    return MCR_OK;
+    const size_t res = res_doubles * sizeof(double), off = off_entries * sizeof(i64);
+    if (off > s.d_off.cap) s.off_C = s.off_N = -1;       // a new offset table holds no resident offsets
+    int rc = s.d_res.reserve(ctx, res);
+    if (!rc) rc = s.h_res.reserve(ctx, res);
+    if (!rc) rc = s.d_off.reserve(ctx, off);
+    return rc ? rc : s.h_off.reserve(ctx, off);
 }
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -462,16 +489,16 @@ double* carve_pipe(Carve& cv, PipeIn& a, bool records, const FftPlan& fp, bool i
     return ingest ? cv.take<double>(pc * M) : nullptr;
 }
 
-// Measures a layout (a callable on a Carve&), makes the workspace that large, then carves it.
-template <class Layout> int carve_ws(mcr_ctx* ctx, Layout&& layout)
+// Measures a layout (a callable on a Carve&), makes the buffer that large, then carves it.
+template <class Layout> int carve(mcr_ctx* ctx, DevBuf& buf, Layout&& layout)
 {
     Carve m{nullptr};
     layout(m);
-    const int rc = ensure_ws(ctx, m.off);
+    const int rc = buf.reserve(ctx, m.off);
     if (rc) return rc;
-    Carve cv{reinterpret_cast<char*>(ctx->ws), ctx->ws_bytes};
+    Carve cv{buf.as<char>(), buf.cap};
     layout(cv);
-    if (cv.over()) return fail(ctx, MCR_ENOMEM, "workspace layout needs %zu bytes; the workspace has %zu", cv.off, cv.end);
+    if (cv.over()) return fail(ctx, MCR_ENOMEM, "buffer layout needs %zu bytes; the buffer has %zu", cv.off, cv.end);
     return MCR_OK;
 }
 
@@ -502,7 +529,7 @@ int launch_diag_front(mcr_ctx* ctx, const PipeIn& a, int kind_sel)
     LAUNCH(ctx, K_DIAG, k_diag_combine, dim3((unsigned)a.pc, ky), dim3(64u * (unsigned)(a.C < kCombineWaves ? a.C : kCombineWaves)), (size_t)6 * a.C * 8, (const u32*)a.zb,
            (const u32*)a.zt, (const double*)a.ztab, a.M, a.d_off, a.C, a.n, a.nh, nseg, (const double*)a.rec, a.d_res, a.pc, a.more, a.state, a.chstate,
            a.long_count, a.t3c,
-           ctx->rho_band, ctx->guard_count, kind_sel);
+           ctx->rho_band, ctx->guard_count.as<unsigned>(), kind_sel);
     // tier 2 for pairs whose first negative rho lies beyond lag 63 (others exit at once)
     return small ? launch_acov_seg<128, 1024, false>(ctx, a, nseg, kind_sel) : launch_acov_seg<256, kSeg, false>(ctx, a, nseg, kind_sel);
 }
@@ -518,7 +545,7 @@ int launch_diag(mcr_ctx* ctx, const PipeIn& a)
            (const u32*)a.zt, (const double*)a.ztab, a.M, a.d_off, a.C,
            a.n, nseg, (const double*)a.rec2, (const unsigned*)a.more, a.state,
            a.chstate, a.d_res, a.pc, a.kA, a.kB,   // kA / kB: the sort's key buffers, free by now
-           (const double*)a.part, (int)a.ntiles, fused_tier3 ? 0 : 1, ctx->rho_band, ctx->guard_count);
+           (const double*)a.part, (int)a.ntiles, fused_tier3 ? 0 : 1, ctx->rho_band, ctx->guard_count.as<unsigned>());
     if (a.n <= kLag2) return MCR_OK;       // chains short enough to be decided by lag 255 never reach tier 3
     if (fused_tier3) {
         // the common case in ONE launch: list, products of the lags [256, n) stage by stage, scans (k_tier3); a fixed number
@@ -527,7 +554,7 @@ int launch_diag(mcr_ctx* ctx, const PipeIn& a)
         const i64 most = 2 * a.pc * groups;                                  // work items if every pair were listed
         const unsigned wgs = (unsigned)(most < (i64)kT3Workgroups ? most : (i64)kT3Workgroups);
         LAUNCH(ctx, K_ACOV_LONG, k_tier3, dim3(wgs), dim3(256), 0, (const double*)a.kA, (const double*)a.kB, a.M, a.d_off,
-               a.C, a.n, (const unsigned*)a.more, a.state, a.acov, a.d_res, a.pc, ctx->rho_band, ctx->guard_count, a.t3c,
+               a.C, a.n, (const unsigned*)a.more, a.state, a.acov, a.d_res, a.pc, ctx->rho_band, ctx->guard_count.as<unsigned>(), a.t3c,
                (const u32*)a.zb, (const u32*)a.zt, (const double*)a.ztab, a.chstate);
         return MCR_OK;
     }
@@ -579,7 +606,7 @@ int launch_diag(mcr_ctx* ctx, const PipeIn& a)
                (const double*)a.state, a.acov, slot_from);
         LAUNCH(ctx, K_DIAG_LONG, k_diag_long_scan, dim3(scan_slots), dim3(256), 0, a.C, a.n, L0, L1, (const unsigned*)a.long_count,
                (const unsigned*)a.long_list, a.state, a.acov, a.d_res, a.pc, (const u32*)a.zb, (const u32*)a.zt,
-               (const double*)a.ztab, a.chstate, a.M, a.d_off, ctx->rho_band, ctx->guard_count);
+               (const double*)a.ztab, a.chstate, a.M, a.d_off, ctx->rho_band, ctx->guard_count.as<unsigned>());
         L0 = L1;
     }
     return MCR_OK;
@@ -757,16 +784,17 @@ int run_pipeline(mcr_ctx* ctx, PipeIn& a)
         // tiers 1 and 2 needs only the bulk rank codes, which exist now, so it runs on the lane's second stream UNDER the fold
         // kernel, and the two halves join in front of combine2 -- ~35 us off the critical path of a 0.3 ms call.  A pipelined
         // caller keeps the single stream: its lanes are full anyway, and three more launches per call would only cost.
-        const bool fork = a.fork && a.C >= 2 && ctx->lane_aux[ctx->lane] != nullptr;
+        const mcr_ctx::Lane& ln = ctx->lanes[ctx->lane];
+        const bool fork = a.fork && a.C >= 2 && ln.aux != nullptr;
         hipStream_t main_stream = ctx->stream;
         if (fork) {
-            HIP_TRY(ctx, hipEventRecord(ctx->lane_fork[ctx->lane], main_stream));
-            HIP_TRY(ctx, hipStreamWaitEvent(ctx->lane_aux[ctx->lane], ctx->lane_fork[ctx->lane], 0));
-            ctx->stream = ctx->lane_aux[ctx->lane];
+            HIP_TRY(ctx, hipEventRecord(ln.fork, main_stream));
+            HIP_TRY(ctx, hipStreamWaitEvent(ln.aux, ln.fork, 0));
+            ctx->stream = ln.aux;
             const int rc = launch_diag_front(ctx, a, 0);
             ctx->stream = main_stream;
             if (rc) return rc;
-            HIP_TRY(ctx, hipEventRecord(ctx->lane_join[ctx->lane], ctx->lane_aux[ctx->lane]));
+            HIP_TRY(ctx, hipEventRecord(ln.join, ln.aux));
         }
         // 5+6. fold: one merge of the two monotone halves around the median, fused with ranks -> z
         {
@@ -777,7 +805,7 @@ int run_pipeline(mcr_ctx* ctx, PipeIn& a)
         if (a.C >= 2) {
             const int rc = launch_diag_front(ctx, a, fork ? 1 : -1);
             if (rc) return rc;
-            if (fork) HIP_TRY(ctx, hipStreamWaitEvent(main_stream, ctx->lane_join[ctx->lane], 0));
+            if (fork) HIP_TRY(ctx, hipStreamWaitEvent(main_stream, ln.join, 0));
             return launch_diag(ctx, a);
         }
     }
@@ -843,7 +871,7 @@ int unpack_slot(mcr_ctx* ctx, Slot& s)
     double nbad = 0.0;
     for (i64 p0 = 0; p0 < s.P; p0 += s.pcmax) {
         const i64 pc = s.P - p0 < s.pcmax ? s.P - p0 : s.pcmax;
-        const double* r = s.h_res + (size_t)res_fields(s.nq) * (size_t)p0;
+        const double* r = s.h_res.as<double>() + (size_t)res_fields(s.nq) * (size_t)p0;
         auto cp = [&](double* dst, int field) {
             if (dst) memcpy(dst + p0, r + (size_t)field * pc, sizeof(double) * (size_t)pc);
         };
@@ -1039,28 +1067,28 @@ int enqueue_impl(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i
         rc = plan_chunks(ctx, h, P, needs_ingest(iC, iN, P, isc, isn, sp), do_diag, cp);
         if (rc) return rc;
         const i64 pcmax = s.pcmax = cp.pcmax;
-        rc = ensure_ws(ctx, cp.bytes);
+        rc = lane_ws(ctx).reserve(ctx, cp.bytes);
         if (rc) return rc;
         const int R = res_fields(nq);
         rc = ensure_slot(ctx, s, (size_t)R * (size_t)P, (size_t)C + 1);
         if (rc) return rc;
         const bool off_resident = !ragged && s.off_C == C && s.off_N == N;
         if (ragged) {
-            memcpy(s.h_off, chain_off, sizeof(i64) * (size_t)(C + 1));
+            memcpy(s.h_off.p, chain_off, sizeof(i64) * (size_t)(C + 1));
             s.off_C = s.off_N = -1;
         } else if (!off_resident) {
-            for (i64 c = 0; c <= C; ++c) s.h_off[c] = c * N;
+            for (i64 c = 0; c <= C; ++c) s.h_off.as<i64>()[c] = c * N;
         }
         PipeIn call{};                  // the fields every chunk shares
-        call.M = M; call.C = (int)C; call.d_off = s.d_off; call.n = h.n; call.nh = h.nh; call.q = q;
+        call.M = M; call.C = (int)C; call.d_off = s.d_off.as<i64>(); call.n = h.n; call.nh = h.nh; call.q = q;
         call.nstage = h.nstage; call.do_diag = do_diag;
         rc = get_tables(ctx, call, cp.fp, do_diag);
         if (rc) return rc;
         if (!off_resident)
-            HIP_TRY(ctx, hipMemcpyAsync(s.d_off, s.h_off, sizeof(i64) * (size_t)(C + 1), hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(s.d_off.p, s.h_off.p, sizeof(i64) * (size_t)(C + 1), hipMemcpyHostToDevice, ctx->stream));
         for (i64 p0 = 0; p0 < P; p0 += pcmax) {
             const i64 pc = (P - p0 < pcmax) ? P - p0 : pcmax;
-            Carve cv{reinterpret_cast<char*>(ctx->ws), ctx->ws_bytes};
+            Carve cv{lane_ws(ctx).as<char>(), lane_ws(ctx).cap};
             PipeIn a = call;
             a.pc = pc;
             double* X = carve_pipe(cv, a, true, cp.fp, cp.ingest);
@@ -1081,11 +1109,11 @@ int enqueue_impl(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i
                 a.X = a.x_f32 ? (const void*)(reinterpret_cast<const float*>(draws_dev) + p0 * M)
                               : (const void*)(reinterpret_cast<const double*>(draws_dev) + p0 * M);
             }
-            a.d_res = s.d_res + (size_t)R * (size_t)p0;
+            a.d_res = s.d_res.as<double>() + (size_t)R * (size_t)p0;
             rc = run_pipeline(ctx, a);
             if (rc) return rc;
         }
-        HIP_TRY(ctx, hipMemcpyAsync(s.h_res, s.d_res, sizeof(double) * (size_t)R * (size_t)P, hipMemcpyDeviceToHost,
+        HIP_TRY(ctx, hipMemcpyAsync(s.h_res.p, s.d_res.p, sizeof(double) * (size_t)R * (size_t)P, hipMemcpyDeviceToHost,
                                     ctx->stream));
     }
     if (!s.trivial_nan && !ragged) { s.off_C = C; s.off_N = N; }
@@ -1127,7 +1155,7 @@ int wait_impl(mcr_ctx* ctx)
     // every slot in flight records its event behind its last copy on its lane: waiting for the events (polled, see
     // wait_event) leaves every lane idle; the stream synchronisations below then return at once
     for (int si : ctx->order) { const int rc = wait_event(ctx, ctx->slots[si].done); if (rc) return rc; }
-    for (hipStream_t st : ctx->lane_stream) if (st) HIP_TRY(ctx, hipStreamSynchronize(st));
+    for (const mcr_ctx::Lane& l : ctx->lanes) if (l.stream) HIP_TRY(ctx, hipStreamSynchronize(l.stream));
     use_lane(ctx, 0);
     prof_resolve(ctx);
     int rc = MCR_OK;
@@ -1165,16 +1193,6 @@ mcr_summary summary_at(mcr_summary r, i64 p0, int nq)
         if (*a) *a += p0;
     if (r.q) r.q += p0 * nq;
     return r;
-}
-
-int ensure_stage(mcr_ctx* ctx, size_t bytes)
-{
-    if (bytes <= ctx->stage_bytes) return MCR_OK;
-    sync_all(ctx);
-    if (ctx->stage) { hipFree(ctx->stage); ctx->stage = nullptr; ctx->stage_bytes = 0; }
-    HIP_TRY(ctx, hipMalloc(&ctx->stage, bytes));
-    ctx->stage_bytes = bytes;
-    return MCR_OK;
 }
 
 // Extent (in elements) touched by a strided tensor, or -1 if strides are negative.
@@ -1244,23 +1262,18 @@ int mcr_init(int device, mcr_ctx** out)
     }
     e = hipSetDevice(device);
     for (int l = 0; l < ctx->n_lanes && e == hipSuccess; ++l)
-        e = hipStreamCreateWithFlags(&ctx->lane_stream[l], hipStreamNonBlocking);
+        e = hipStreamCreateWithFlags(&ctx->lanes[l].stream, hipStreamNonBlocking);
     for (int l = 0; l < ctx->n_lanes && e == hipSuccess; ++l) {
-        e = hipStreamCreateWithFlags(&ctx->lane_aux[l], hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->lane_fork[l], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->lane_join[l], hipEventDisableTiming);
+        e = hipStreamCreateWithFlags(&ctx->lanes[l].aux, hipStreamNonBlocking);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->lanes[l].fork, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->lanes[l].join, hipEventDisableTiming);
     }
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
-        if (ctx->copy_stream) hipStreamDestroy(ctx->copy_stream);
-        for (hipStream_t st : ctx->lane_stream) if (st) hipStreamDestroy(st);
-        for (hipStream_t st : ctx->lane_aux) if (st) hipStreamDestroy(st);
-        for (hipEvent_t ev : ctx->lane_fork) if (ev) hipEventDestroy(ev);
-        for (hipEvent_t ev : ctx->lane_join) if (ev) hipEventDestroy(ev);
-        delete ctx;
+        mcr_free(ctx);
         return fail(nullptr, MCR_EHIP, "device %d init failed: %s", device, hipGetErrorString(e));
     }
-    ctx->stream = ctx->lane_stream[0];
+    use_lane(ctx, 0);
     size_t mb = 8192;
     if (const char* env = getenv("MCR_WORKSPACE_MB")) { const long v = atol(env); if (v > 0) mb = (size_t)v; }
     ctx->ws_limit = mb << 20;
@@ -1269,8 +1282,8 @@ int mcr_init(int device, mcr_ctx** out)
     if (const char* env = getenv("MCR_SPLITTERS_PAIRWISE")) ctx->splitters_pairwise = atoi(env) != 0;
     if (const char* env = getenv("MCR_FORK")) ctx->fork_lone = atoi(env) != 0;
     if (const char* env = getenv("MCR_RHO_BAND")) { const double v = atof(env); if (v >= 0.0 && v < 1.0) ctx->rho_band = v; }
-    if (hipMalloc((void**)&ctx->guard_count, sizeof(unsigned)) != hipSuccess ||
-        hipMemsetAsync(ctx->guard_count, 0, sizeof(unsigned), ctx->stream) != hipSuccess ||
+    if (ctx->guard_count.reserve(ctx, sizeof(unsigned)) != MCR_OK ||
+        hipMemsetAsync(ctx->guard_count.p, 0, sizeof(unsigned), ctx->stream) != hipSuccess ||
         hipStreamSynchronize(ctx->stream) != hipSuccess) {
         mcr_free(ctx);
         return fail(nullptr, MCR_ENOMEM, "device %d: cannot allocate the guard counter", device);
@@ -1284,32 +1297,10 @@ void mcr_free(mcr_ctx* ctx)
     if (!ctx) return;
     hipSetDevice(ctx->device);
     sync_all(ctx);
-    use_lane(ctx, 0);
     prof_resolve(ctx);
+    // what no member owns: the event pool, the slots' completion events, the copy stream; the rest goes with the members
     for (hipEvent_t e : ctx->free_ev) hipEventDestroy(e);
-    for (Slot& s : ctx->slots) {
-        if (s.done) hipEventDestroy(s.done);
-        if (s.d_res) hipFree(s.d_res);
-        if (s.h_res) hipHostFree(s.h_res);
-        if (s.d_off) hipFree(s.d_off);
-        if (s.h_off) hipHostFree(s.h_off);
-    }
-    ctx->lane_ws[0] = ctx->ws;
-    for (void* w : ctx->lane_ws) if (w) hipFree(w);
-    for (const mcr_ctx::ZTab& z : ctx->ztabs) hipFree(z.tab);
-    for (const mcr_ctx::Twiddle& t : ctx->twiddles) hipFree(t.tab);
-    if (ctx->guard_count) hipFree(ctx->guard_count);
-    if (ctx->stage) hipFree(ctx->stage);
-    if (ctx->pq_stage) hipFree(ctx->pq_stage);
-    if (ctx->pq_scratch) hipFree(ctx->pq_scratch);
-    if (ctx->pq_tab) hipFree(ctx->pq_tab);
-    if (ctx->fs_arena) hipFree(ctx->fs_arena);
-    if (ctx->pq_pin) hipHostFree(ctx->pq_pin);
-    for (void* b : {ctx->csv_tab, ctx->csv_rows, ctx->csv_aux, ctx->csv_pow5}) if (b) hipFree(b);
-    for (hipStream_t st : ctx->lane_stream) if (st) hipStreamDestroy(st);
-    for (hipStream_t st : ctx->lane_aux) if (st) hipStreamDestroy(st);
-    for (hipEvent_t ev : ctx->lane_fork) if (ev) hipEventDestroy(ev);
-    for (hipEvent_t ev : ctx->lane_join) if (ev) hipEventDestroy(ev);
+    for (Slot& s : ctx->slots) if (s.done) hipEventDestroy(s.done);
     if (ctx->copy_stream) hipStreamDestroy(ctx->copy_stream);
     delete ctx;
 }
@@ -1320,7 +1311,7 @@ int mcr_rho_guard_count(mcr_ctx* ctx, int64_t* rederived)
     hipSetDevice(ctx->device);
     sync_all(ctx);
     unsigned v = 0;
-    HIP_TRY(ctx, hipMemcpy(&v, ctx->guard_count, sizeof(unsigned), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(&v, ctx->guard_count.p, sizeof(unsigned), hipMemcpyDeviceToHost));
     *rederived = (int64_t)v;
     return MCR_OK;
 }
@@ -1379,7 +1370,7 @@ int mcr_memcpy_d2h(mcr_ctx* ctx, void* hptr, const void* dptr, size_t bytes)
 int mcr_sync(mcr_ctx* ctx)
 {
     if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
-    for (hipStream_t st : ctx->lane_stream) if (st) HIP_TRY(ctx, hipStreamSynchronize(st));
+    for (const mcr_ctx::Lane& l : ctx->lanes) if (l.stream) HIP_TRY(ctx, hipStreamSynchronize(l.stream));
     return MCR_OK;
 }
 
@@ -1472,7 +1463,7 @@ int mcr_summarize(mcr_ctx* ctx, const void* draws, int dtype, int64_t C, int64_t
     const size_t es = dtype == MCR_F64 ? 8 : 4;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (ext > 0) {
-        rc = ensure_stage(ctx, (size_t)ext * es);
+        rc = ctx->stage.reserve(ctx, (size_t)ext * es);
         if (rc) return rc;
     }
     // Parameter-major tensors (the Arrow column layout) of some size go up in a few pieces: while piece k + 1
@@ -1487,19 +1478,19 @@ int mcr_summarize(mcr_ctx* ctx, const void* draws, int dtype, int64_t C, int64_t
             const i64 p0 = P * k / pieces, p1 = P * (k + 1) / pieces, pc = p1 - p0;
             const size_t b0 = (size_t)p0 * (size_t)sp * es;
             const size_t bytes = (size_t)tensor_extent(C, N, pc, sc, sn, sp) * es;
-            hipError_t e = hipMemcpyAsync((char*)ctx->stage + b0, (const char*)draws + b0, bytes, hipMemcpyHostToDevice, ctx->copy_stream);
+            hipError_t e = hipMemcpyAsync(ctx->stage.as<char>() + b0, (const char*)draws + b0, bytes, hipMemcpyHostToDevice, ctx->copy_stream);
             if (e == hipSuccess) e = hipStreamSynchronize(ctx->copy_stream);
             if (e != hipSuccess) { rc = fail(ctx, MCR_EHIP, "upload failed: %s", hipGetErrorString(e)); break; }
             mcr_summary o = summary_at(*out, p0, n_q > 0 ? n_q : 0);
-            rc = mcr_summarize_enqueue(ctx, (const char*)ctx->stage + b0, dtype, C, N, pc, sc, sn, sp, min_chains, quantiles, n_q, &o);
+            rc = mcr_summarize_enqueue(ctx, ctx->stage.as<char>() + b0, dtype, C, N, pc, sc, sn, sp, min_chains, quantiles, n_q, &o);
         }
         return drain(ctx, rc);
     }
     if (ext > 0) {
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->stage, draws, (size_t)ext * es, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->stage.p, draws, (size_t)ext * es, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // the pipeline may run on the other lane
     }
-    return mcr_summarize_dev(ctx, ctx->stage, dtype, C, N, P, sc, sn, sp, min_chains, quantiles, n_q, out);
+    return mcr_summarize_dev(ctx, ctx->stage.p, dtype, C, N, P, sc, sn, sp, min_chains, quantiles, n_q, out);
 }
 
 int mcr_diagnose_chains(mcr_ctx* ctx, const double* pooled, const int64_t* chain_off, int C, int min_chains,
@@ -1547,23 +1538,23 @@ int mcr_diagnose_chains(mcr_ctx* ctx, const double* pooled, const int64_t* chain
     auto measure = [&]() { Carve m{nullptr}; layout(m); return m.off; };
     if (fp.on && measure() > ctx->ws_limit) fp = FftPlan{};
     if (measure() > ctx->ws_limit) return fail(ctx, MCR_ENOMEM, "workspace limit too small for %lld draws", M);
-    int rc = carve_ws(ctx, layout);
+    int rc = carve(ctx, lane_ws(ctx), layout);
     if (rc) return rc;
     const int R = res_fields(0);
     rc = ensure_slot(ctx, s, (size_t)R, (size_t)C + 1);
     if (rc) return rc;
     s.off_C = s.off_N = -1;
-    memcpy(s.h_off, chain_off, sizeof(i64) * (size_t)(C + 1));
-    HIP_TRY(ctx, hipMemcpyAsync(s.d_off, s.h_off, sizeof(i64) * (size_t)(C + 1), hipMemcpyHostToDevice, ctx->stream));
-    a.d_off = s.d_off;
+    memcpy(s.h_off.p, chain_off, sizeof(i64) * (size_t)(C + 1));
+    HIP_TRY(ctx, hipMemcpyAsync(s.d_off.p, s.h_off.p, sizeof(i64) * (size_t)(C + 1), hipMemcpyHostToDevice, ctx->stream));
+    a.d_off = s.d_off.as<i64>();
     rc = get_tables(ctx, a, fp, true);
     if (rc) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(X, pooled, sizeof(double) * (size_t)M, hipMemcpyHostToDevice, ctx->stream));
     a.X = X;
-    a.d_res = s.d_res;
+    a.d_res = s.d_res.as<double>();
     rc = run_pipeline(ctx, a);
     if (rc) { abort_inflight(ctx); return rc; }
-    HIP_TRY(ctx, hipMemcpyAsync(s.h_res, s.d_res, sizeof(double) * (size_t)R, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(s.h_res.p, s.d_res.p, sizeof(double) * (size_t)R, hipMemcpyDeviceToHost, ctx->stream));
     if (want_dbg) {
         const unsigned nb = (unsigned)((M + 255) / 256);
         hipLaunchKernelGGL(k_decode_codes, dim3(nb), dim3(256), 0, ctx->stream, (const u32*)a.zb, (const double*)a.ztab, M,
@@ -1606,7 +1597,7 @@ int mcr_moments_dev(mcr_ctx* ctx, const void* draws_dev, int dtype, int64_t C, i
         if (S > kMaxGridY) S = kMaxGridY;
     }
     double *part, *d_mean, *d_std;
-    int rc = carve_ws(ctx, [&](Carve& cv) {
+    int rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) {
         part = cv.take<double>((size_t)P * S * kMomRec);
         d_mean = cv.take<double>((size_t)P);
         d_std = cv.take<double>((size_t)P);
@@ -1631,10 +1622,10 @@ int mcr_basic_stats(mcr_ctx* ctx, const void* values, int dtype, int64_t n, doub
     if (!values) return fail(ctx, MCR_EINVAL, "values is NULL");
     const size_t es = dtype == MCR_F64 ? 8 : 4;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = ensure_stage(ctx, (size_t)n * es);
+    int rc = ctx->stage.reserve(ctx, (size_t)n * es);
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->stage, values, (size_t)n * es, hipMemcpyHostToDevice, ctx->stream));
-    return mcr_moments_dev(ctx, ctx->stage, dtype, 1, n, 1, n, 1, n, mean, std);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->stage.p, values, (size_t)n * es, hipMemcpyHostToDevice, ctx->stream));
+    return mcr_moments_dev(ctx, ctx->stage.p, dtype, 1, n, 1, n, 1, n, mean, std);
 }
 
 int mcr_compare(mcr_ctx* ctx, const double* ref, const double* actual, int64_t n, double tol, double* rel_error,
@@ -1646,7 +1637,7 @@ int mcr_compare(mcr_ctx* ctx, const double* ref, const double* actual, int64_t n
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     double *d_ref, *d_act, *d_rel;
     unsigned char* d_ok;
-    const int rc = carve_ws(ctx, [&](Carve& cv) {
+    const int rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) {
         d_ref = cv.take<double>((size_t)n);
         d_act = cv.take<double>((size_t)n);
         d_rel = cv.take<double>((size_t)n);
@@ -1681,7 +1672,7 @@ int mcr_two_sample(mcr_ctx* ctx, const double* ref, int64_t Mr, const double* ac
     PipeIn ar{}, aa{};            // the sorts of the two samples: one after the other, in the same space
     ar.M = Mr; aa.M = Ma;
     ar.pc = aa.pc = P; ar.C = aa.C = 1; ar.do_diag = aa.do_diag = false;
-    int rc = carve_ws(ctx, [&](Carve& cv) {
+    int rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) {
         Xr = cv.take<double>((size_t)P * Mr);
         Xa = cv.take<double>((size_t)P * Ma);
         Sr = cv.take<double>((size_t)P * Mr);
@@ -1753,7 +1744,7 @@ int mcr_covariance_dev(mcr_ctx* ctx, const double* draws_dev, int64_t M, int64_t
     ksplit = (int)((M + kchunk - 1) / kchunk);
     const int S = 8;
     double *partial, *mpart, *d_mean, *d_std;
-    int rc = carve_ws(ctx, [&](Carve& cv) {
+    int rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) {
         partial = cv.take<double>((size_t)ksplit * P64 * P64);
         mpart = cv.take<double>((size_t)P * S * kMomRec);
         d_mean = cv.take<double>((size_t)P);
@@ -1783,10 +1774,10 @@ int mcr_covariance(mcr_ctx* ctx, const double* draws, int64_t M, int64_t P, doub
     if (P == 0) return MCR_OK;
     if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "mcr_covariance with summaries in flight");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = ensure_stage(ctx, (size_t)P * M * 8 + (size_t)P * P * 8 + 256);
+    int rc = ctx->stage.reserve(ctx, (size_t)P * M * 8 + (size_t)P * P * 8 + 256);
     if (rc) return rc;
-    double* X = (double*)ctx->stage;
-    double* d_cov = (double*)((char*)ctx->stage + align_up((size_t)P * M * 8, 256));
+    double* X = ctx->stage.as<double>();
+    double* d_cov = (double*)(ctx->stage.as<char>() + align_up((size_t)P * M * 8, 256));
     HIP_TRY(ctx, hipMemcpyAsync(X, draws, sizeof(double) * (size_t)P * M, hipMemcpyHostToDevice, ctx->stream));
     rc = mcr_covariance_dev(ctx, X, M, P, d_cov);
     if (rc) return rc;
@@ -1835,13 +1826,14 @@ int mcr_hbm_probe(mcr_ctx* ctx, size_t bytes, int iters, double* read_gbps, doub
     if (bytes < ((size_t)1 << 20) || iters < 1 || (!read_gbps && !copy_gbps)) return fail(ctx, MCR_EINVAL, "bad argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     bytes &= ~(size_t)4095;
-    void *a = nullptr, *b = nullptr;
-    HIP_TRY(ctx, hipMalloc(&a, bytes));
-    if (hipMalloc(&b, copy_gbps ? bytes : 4096 * 4) != hipSuccess) { hipFree(a); return fail(ctx, MCR_ENOMEM, "probe buffer"); }
+    DevBuf src, dst;
+    int rc = src.reserve(ctx, bytes);
+    if (!rc) rc = dst.reserve(ctx, copy_gbps ? bytes : 4096 * 4);
+    if (rc) return rc;
+    void *const a = src.p, *const b = dst.p;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     hipEventCreate(&e0); hipEventCreate(&e1);
     hipStream_t st = ctx->stream;
-    int rc = MCR_OK;
     auto best_of = [&](auto&& launch) -> double {
         float best = 1e30f;
         launch();                                                  // warm-up (page faults, clocks)
@@ -1870,7 +1862,6 @@ int mcr_hbm_probe(mcr_ctx* ctx, size_t bytes, int iters, double* read_gbps, doub
     hipStreamSynchronize(st);
     if (hipGetLastError() != hipSuccess && !rc) rc = fail(ctx, MCR_EHIP, "probe launch failed");
     hipEventDestroy(e0); hipEventDestroy(e1);
-    hipFree(a); hipFree(b);
     return rc;
 }
 
@@ -1911,7 +1902,7 @@ struct mcr_comm {
     ncclComm_t nccl = nullptr;
     hipStream_t stream = nullptr;
     int world = 1, rank = 0;
-    void* dbuf = nullptr; size_t dbytes = 0;      // device staging (send block + receive blocks)
+    DevBuf dbuf;                                  // device staging (send block + receive blocks)
     bool dead = false;                            // aborted after a deadline or an asynchronous error
     double timeout_s = 300.0;                     // MCR_COMM_TIMEOUT_S
 };
@@ -1921,14 +1912,6 @@ int comm_fail(mcr_ctx* ctx, const char* what, ncclResult_t r)
 {
     mcr::comm::Api* a = mcr::comm::api();
     return fail(ctx, MCR_ECOMM, "%s failed: %s", what, a ? a->GetErrorString(r) : "RCCL error");
-}
-int comm_buf(mcr_comm* c, size_t bytes)
-{
-    if (bytes <= c->dbytes) return MCR_OK;
-    if (c->dbuf) { hipFree(c->dbuf); c->dbuf = nullptr; c->dbytes = 0; }
-    HIP_TRY(c->ctx, hipMalloc(&c->dbuf, bytes));
-    c->dbytes = bytes;
-    return MCR_OK;
 }
 
 // A DEADLINE ON EVERY COLLECTIVE.  The ranks are separate processes; one that dies after the
@@ -2006,9 +1989,9 @@ int comm_collective(mcr_comm* c, const char* what, bool args_ok, const double* i
     if (!args_ok) return fail(ctx, MCR_EINVAL, "bad argument");
     if (in_bytes == 0) return MCR_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = comm_buf(c, out_at + out_bytes);
+    int rc = c->dbuf.reserve(ctx, out_at + out_bytes);      // (a collective returns with the communicator's stream idle, or dead)
     if (rc) return rc;
-    char* d = (char*)c->dbuf;
+    char* d = c->dbuf.as<char>();
     HIP_TRY(ctx, hipMemcpyAsync(d, in, in_bytes, hipMemcpyHostToDevice, c->stream));
     const ncclResult_t r = rccl(d, d + out_at);
     if (r != ncclSuccess) return comm_fail(ctx, what, r);
@@ -2089,7 +2072,6 @@ void mcr_comm_free(mcr_comm* c)
     if (!c) return;
     hipSetDevice(c->ctx->device);
     if (c->nccl && !c->dead && comm_wait(c, "mcr_comm_free") == MCR_OK) mcr::comm::api()->CommDestroy(c->nccl);
-    if (c->dbuf) hipFree(c->dbuf);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
 }
@@ -2126,7 +2108,7 @@ int mcr_comm_all_reduce(mcr_comm* c, double* vals, int64_t n, int op)
 int mcr_comm_barrier(mcr_comm* c)
 {
     if (!c) return fail(nullptr, MCR_EINVAL, "comm is NULL");
-    for (hipStream_t st : c->ctx->lane_stream) if (st) HIP_TRY(c->ctx, hipStreamSynchronize(st));
+    for (const mcr_ctx::Lane& l : c->ctx->lanes) if (l.stream) HIP_TRY(c->ctx, hipStreamSynchronize(l.stream));
     double one = 1.0;
     return mcr_comm_all_reduce(c, &one, 1, 0);
 }
@@ -2135,23 +2117,9 @@ int mcr_comm_barrier(mcr_comm* c)
 // ---- Parquet ingest (replaces pq.read_table at store.py:79-95 / convert.py:61-65) -----------
 
 struct mcr_parquet { mcr::pq::File f; };
-// A chain CSV's header.  owner / gen / img: the image is this context's pq_pin + img and already uploaded (mcr_csv_open_paths).
+// A chain CSV's header.  owner / gen / img: the image is this context's img.pin + img and already uploaded (mcr_csv_open_paths).
 // table / tflags / twhere: a table CSV (mcr_csv_open_table*), its MCR_CSV_T_* header flags and the first one's byte offset.
 struct mcr_csv { mcr::csv::Image im; mcr_ctx* owner = nullptr; uint64_t gen = 0; size_t img = 0; bool table = false; int tflags = 0; size_t twhere = 0; };
-
-namespace {
-int ensure_buf(mcr_ctx* ctx, void** p, size_t* cap, size_t bytes)
-{
-    if (bytes <= *cap) return MCR_OK;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (*p) { hipFree(*p); *p = nullptr; *cap = 0; }
-    const size_t want = bytes + (bytes >> 2);
-    const hipError_t e = hipMalloc(p, want);
-    if (e != hipSuccess) return fail(ctx, MCR_ENOMEM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
-    *cap = want;
-    return MCR_OK;
-}
-}  // namespace
 
 int mcr_parquet_open(mcr_ctx* ctx, const void* bytes, size_t len, mcr_parquet** out)
 {
@@ -2194,8 +2162,8 @@ int mcr_parquet_page_info(const mcr_parquet* f, int page, int64_t* info)
 
 namespace {
 // A batched decode in three steps: pq_plan (host only: byte spans to stage, page table), pq_buffers (device buffers +
-// table uploads), pq_launch (the two kernels).  Between buffers and launch the caller stages the spans' file bytes at
-// pq_stage + span.stage_off: mcr_parquet_decode copies them from the caller's file image (pageable memory),
+// table uploads), pq_launch (the two kernels).  The caller makes room for the file bytes first (FileImage::rewrite) and
+// stages the spans at img.dev + span.stage_off before the launch: mcr_parquet_decode copies them from the caller's file image (pageable memory),
 // mcr_summarize_files reads them into pinned memory on host threads and uploads behind them.
 struct PqSpan { const mcr::pq::File* f; u64 start, end; size_t stage_off; };
 struct PqPlan {
@@ -2317,26 +2285,27 @@ int pq_plan(mcr_ctx* ctx, const mcr_parquet_request* reqs, int n_reqs, PqPlan& P
     return MCR_OK;
 }
 
-// 3. device buffers + the page table and the two page lists, on ctx->stream
+// 3. device buffers + the page table and the two page lists, on ctx->stream.  The staged bytes' buffer is the caller's to
+//    size (pq_stage_bytes: it may be uploading into it already), never reallocated here.
+inline size_t pq_stage_bytes(size_t staged) { return staged + mcr::pq::kInWin + 256; }    // the kernels' read window behind the end
 int pq_buffers(mcr_ctx* ctx, PqPlan& P)
 {
     namespace pq = mcr::pq;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ++ctx->img_gen;
-    int rc = ensure_buf(ctx, &ctx->pq_stage, &ctx->pq_stage_bytes, P.stage_total + pq::kInWin + 256);
-    if (rc) return rc;
-    rc = ensure_buf(ctx, &ctx->pq_scratch, &ctx->pq_scratch_bytes, P.scratch_total + 256);
+    if (ctx->img.dev.cap < pq_stage_bytes(P.stage_total))
+        return fail(ctx, MCR_EINVAL, "parquet: the plan stages %zu bytes; the caller made room for %zu", pq_stage_bytes(P.stage_total), ctx->img.dev.cap);
+    int rc = ctx->pq_scratch.reserve(ctx, P.scratch_total + 256);
     if (rc) return rc;
     const size_t tab_bytes = align_up(P.tab.size() * sizeof(pq::PageDev), 256);
     const size_t ls_bytes = align_up(P.l_snappy.size() * 4 + 4, 256), ld_bytes = align_up(P.l_decode.size() * 4 + 4, 256);
-    rc = ensure_buf(ctx, &ctx->pq_tab, &ctx->pq_tab_bytes, tab_bytes + ls_bytes + ld_bytes + 256);
+    rc = ctx->pq_tab.reserve(ctx, tab_bytes + ls_bytes + ld_bytes + 256);
     if (rc) return rc;
-    char* tb = (char*)ctx->pq_tab;
+    char* tb = ctx->pq_tab.as<char>();
     P.d_tab = (pq::PageDev*)tb;
     P.d_ls = (int*)(tb + tab_bytes); P.d_ld = (int*)(tb + tab_bytes + ls_bytes);
     P.d_err = (int*)(tb + tab_bytes + ls_bytes + ld_bytes);
     hipStream_t st = ctx->stream;
-    HIP_TRY(ctx, hipMemsetAsync((char*)ctx->pq_stage + P.stage_total, 0, pq::kInWin + 256, st));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->img.dev.as<char>() + P.stage_total, 0, pq::kInWin + 256, st));
     if (!P.tab.empty()) HIP_TRY(ctx, hipMemcpyAsync(P.d_tab, P.tab.data(), P.tab.size() * sizeof(pq::PageDev), hipMemcpyHostToDevice, st));
     if (!P.l_snappy.empty()) HIP_TRY(ctx, hipMemcpyAsync(P.d_ls, P.l_snappy.data(), P.l_snappy.size() * 4, hipMemcpyHostToDevice, st));
     if (!P.l_decode.empty()) HIP_TRY(ctx, hipMemcpyAsync(P.d_ld, P.l_decode.data(), P.l_decode.size() * 4, hipMemcpyHostToDevice, st));
@@ -2348,11 +2317,11 @@ int pq_launch(mcr_ctx* ctx, const PqPlan& P)
 {
     namespace pq = mcr::pq;
     if (!P.l_snappy.empty())
-        LAUNCH(ctx, K_PQ_SNAPPY, pq::k_pq_snappy, dim3((unsigned)P.l_snappy.size()), dim3(64), 0, (const unsigned char*)ctx->pq_stage,
-               (unsigned char*)ctx->pq_scratch, (const pq::PageDev*)P.d_tab, (const int*)P.d_ls, P.d_err);
+        LAUNCH(ctx, K_PQ_SNAPPY, pq::k_pq_snappy, dim3((unsigned)P.l_snappy.size()), dim3(64), 0, ctx->img.dev.as<const unsigned char>(),
+               ctx->pq_scratch.as<unsigned char>(), (const pq::PageDev*)P.d_tab, (const int*)P.d_ls, P.d_err);
     if (!P.l_decode.empty())
-        LAUNCH(ctx, K_PQ_DECODE, pq::k_pq_decode, dim3((unsigned)P.l_decode.size()), dim3(256), 0, (const unsigned char*)ctx->pq_stage,
-               (const unsigned char*)ctx->pq_scratch, (const pq::PageDev*)P.d_tab, (const int*)P.d_ld, P.d_err);
+        LAUNCH(ctx, K_PQ_DECODE, pq::k_pq_decode, dim3((unsigned)P.l_decode.size()), dim3(256), 0, ctx->img.dev.as<const unsigned char>(),
+               ctx->pq_scratch.as<const unsigned char>(), (const pq::PageDev*)P.d_tab, (const int*)P.d_ld, P.d_err);
     return MCR_OK;
 }
 
@@ -2375,11 +2344,13 @@ int mcr_parquet_decode(mcr_ctx* ctx, const mcr_parquet_request* reqs, int n_reqs
         PqPlan P;
         int rc = pq_plan(ctx, reqs, n_reqs, P);
         if (rc) return rc;
-        rc = pq_buffers(ctx, P);
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        rc = ctx->img.rewrite(ctx, pq_stage_bytes(P.stage_total), 0, 0);
+        if (!rc) rc = pq_buffers(ctx, P);
         if (rc) return rc;
         hipStream_t st = ctx->stream;
         for (const PqSpan& s : P.merged)
-            HIP_TRY(ctx, hipMemcpyAsync((char*)ctx->pq_stage + s.stage_off, s.f->bytes + s.start, (size_t)(s.end - s.start), hipMemcpyHostToDevice, st));
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->img.dev.as<char>() + s.stage_off, s.f->bytes + s.start, (size_t)(s.end - s.start), hipMemcpyHostToDevice, st));
         rc = pq_launch(ctx, P);
         if (rc) return rc;
         int h_err[2] = {0, 0};
@@ -2403,11 +2374,12 @@ int mcr_gather_rows_dev(mcr_ctx* ctx, const double* src_dev, int64_t P, int64_t 
     if (src_dev == dst_dev) return fail(ctx, MCR_EINVAL, "gather cannot run in place");
     for (i64 k = 0; k < M; ++k) if (order[k] < 0 || order[k] >= M) return fail(ctx, MCR_EINVAL, "order[%lld] out of range", (long long)k);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = ensure_buf(ctx, &ctx->pq_tab, &ctx->pq_tab_bytes, (size_t)M * 8);
+    i64* d_order = nullptr;
+    const int rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) { d_order = cv.take<i64>((size_t)M); });
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->pq_tab, order, (size_t)M * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_order, order, (size_t)M * 8, hipMemcpyHostToDevice, ctx->stream));
     LAUNCH(ctx, K_GATHER, mcr::pq::k_gather_rows, dim3((unsigned)((M + 255) / 256), (unsigned)P), dim3(256), 0, src_dev,
-           (const i64*)ctx->pq_tab, (i64)M, dst_dev);
+           (const i64*)d_order, (i64)M, dst_dev);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     prof_resolve(ctx);
     return MCR_OK;
@@ -2483,7 +2455,7 @@ int mcr_parquet_write_dev(mcr_ctx* ctx, const mcr_pq_column* cols, int n_cols, i
         const size_t np = J.pages.size(), bound = pqw::image_bound(J.specs, J.pages), blob_cap = bound - J.slots_total;
         pqw::ColDev* d_cols; pqw::PageW* d_pages; pqw::PageRec* d_recs; unsigned long long* d_err; pqw::Seg* d_segs;
         unsigned char *d_slots, *d_blob, *d_image;
-        rc = carve_ws(ctx, [&](Carve& cv) {
+        rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) {
             d_cols = cv.take<pqw::ColDev>((size_t)n_cols); d_pages = cv.take<pqw::PageW>(np); d_recs = cv.take<pqw::PageRec>(np);
             d_err = cv.take<unsigned long long>((size_t)n_cols); d_segs = cv.take<pqw::Seg>(2 * np + 2);
             d_slots = cv.take<unsigned char>(J.slots_total); d_blob = cv.take<unsigned char>(blob_cap);
@@ -2619,7 +2591,7 @@ inline int bit_length(u64 v) { int b = 0; while (v) { ++b; v >>= 1; } return b; 
 // every table as it stands (all an ordered table needs: most are).  h receives the n result blocks.
 int layout_scan(mcr_ctx* ctx, const lay::Table* tables, int n, int cap, LayoutBufs& b, std::vector<i64>& h)
 {
-    int rc = carve_ws(ctx, [&](Carve& cv) { carve_layout(cv, b, n, cap, 0); });
+    int rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) { carve_layout(cv, b, n, cap, 0); });
     if (rc) return rc;
     try { h.resize((size_t)n * layout_stride(cap)); } catch (const std::exception&) { return fail(ctx, MCR_ENOMEM, "host allocation failed"); }
     hipStream_t st = ctx->stream;
@@ -2686,7 +2658,7 @@ int mcr_chain_layout_dev(mcr_ctx* ctx, const int64_t* chain_dev, const int64_t* 
             return fail(ctx, MCR_EFALLBACK, "chain ids span %d bits and draw indices %d: no 64-bit row key", cbits, dbits);
         }
         // 2. keys + a stable 8-bit pass per significant key byte
-        rc = carve_ws(ctx, [&](Carve& cv) { carve_layout(cv, b, 1, cap, M); });
+        rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) { carve_layout(cv, b, 1, cap, M); });
         if (rc) return rc;
         HIP_TRY(ctx, hipMemcpyAsync(b.tab, &tab, sizeof tab, hipMemcpyHostToDevice, st));      // (the workspace may have moved)
         const unsigned nb = (unsigned)((M + lay::kLayoutNT - 1) / lay::kLayoutNT);
@@ -2758,9 +2730,9 @@ int mcr_gather_rows_order_dev(mcr_ctx* ctx, const double* src_dev, int64_t P, in
     if (!src_dev || !dst_dev || !order_dev) return fail(ctx, MCR_EINVAL, "NULL argument");
     if (src_dev == dst_dev) return fail(ctx, MCR_EINVAL, "gather cannot run in place");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = ensure_buf(ctx, &ctx->pq_tab, &ctx->pq_tab_bytes, 256);
+    int* d_err = nullptr;
+    const int rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) { d_err = cv.take<int>(1); });
     if (rc) return rc;
-    int* d_err = (int*)ctx->pq_tab;
     HIP_TRY(ctx, hipMemsetAsync(d_err, 0, sizeof(int), ctx->stream));
     LAUNCH(ctx, K_GATHER, lay::k_gather_rows_order, dim3((unsigned)((M + 255) / 256), (unsigned)P), dim3(256), 0, src_dev,
            (const i64*)order_dev, (i64)M, dst_dev, d_err);
@@ -2790,7 +2762,7 @@ namespace {
 namespace pq = mcr::pq;
 
 struct BatchFile {    // a file of mcr_summarize_files: descriptor, image, parsed metadata, column roles, place in the arena
-    int fd = -1; size_t len = 0, img = 0; mcr_parquet* pq = nullptr;   // img: offset of the image in pq_pin and pq_stage
+    int fd = -1; size_t len = 0, img = 0; mcr_parquet* pq = nullptr;   // img: offset of the image in img.pin and img.dev
     mcr_csv* csv = nullptr;                                            // FileBatch::csv: the parsed header instead of pq
     int rc = MCR_OK; std::string err;                                  // set by its reader
     std::vector<int> cols; int chain = -1, draw = -1;
@@ -2827,17 +2799,7 @@ int fs_open(mcr_ctx* ctx, FileBatch& B)
         B.img_total = align_up(m.img + m.len, 256);
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ++ctx->img_gen;
-    const int rc = ensure_buf(ctx, &ctx->pq_stage, &ctx->pq_stage_bytes, B.img_total + pq::kInWin + 256);
-    if (rc) return rc;
-    if (B.img_total > ctx->pq_pin_bytes) {                  // pinned staging, kept for the life of the context
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->pq_pin) { hipHostFree(ctx->pq_pin); ctx->pq_pin = nullptr; ctx->pq_pin_bytes = 0; }
-        const size_t want = B.img_total + (B.img_total >> 2);
-        HIP_TRY(ctx, hipHostMalloc(&ctx->pq_pin, want, hipHostMallocDefault));
-        ctx->pq_pin_bytes = want;
-    }
-    return MCR_OK;
+    return ctx->img.rewrite(ctx, pq_stage_bytes(B.img_total), B.img_total, 0);
 }
 
 // The readers of fs_read: however the stage ends, the pool stops handing out files and joins every thread it started.
@@ -2855,7 +2817,7 @@ int fs_read(mcr_ctx* ctx, FileBatch& B)
 {
     const int n = (int)B.f.size();
     if (n == 0) return MCR_OK;
-    char* pin = (char*)ctx->pq_pin;
+    char* pin = ctx->img.pin.as<char>();
     std::vector<std::atomic<int>> done((size_t)n);       // (value-initialised: 0)
     hipError_t he = hipSuccess;
     {
@@ -2889,7 +2851,7 @@ int fs_read(mcr_ctx* ctx, FileBatch& B)
             while (done[(size_t)i].load(std::memory_order_acquire) == 0) std::this_thread::yield();
             const size_t from = B.f[(size_t)sent].img, upto = align_up(B.f[(size_t)i].img + B.f[(size_t)i].len, 256);
             if (he == hipSuccess && (upto - from >= ctx->io_piece || i + 1 == n)) {
-                if (upto > from) he = hipMemcpyAsync((char*)ctx->pq_stage + from, pin + from, upto - from, hipMemcpyHostToDevice, ctx->stream);
+                if (upto > from) he = hipMemcpyAsync(ctx->img.dev.as<char>() + from, pin + from, upto - from, hipMemcpyHostToDevice, ctx->stream);
                 sent = i + 1;
             }
         }
@@ -2925,9 +2887,9 @@ int fs_layout(mcr_ctx* ctx, FileBatch& B)
     const size_t n = B.f.size();
     B.ids_base = align_up(arena, 256);
     B.lay_base = align_up(B.ids_base + ids, 256), B.lay_out = align_up(B.lay_base + n * sizeof(pq::FileIds), 256);
-    const int rc = ensure_buf(ctx, &ctx->fs_arena, &ctx->fs_arena_bytes, B.lay_out + n * 32 + 256);
+    const int rc = ctx->fs_arena.reserve(ctx, B.lay_out + n * 32 + 256);
     if (rc) return rc;
-    char* base = B.arena = (char*)ctx->fs_arena;
+    char* base = B.arena = ctx->fs_arena.as<char>();
     std::vector<FileBase> bases;
     for (const BatchFile& m : B.f) {
         for (size_t j = 0; j < m.cols.size(); ++j)
@@ -2939,7 +2901,7 @@ int fs_layout(mcr_ctx* ctx, FileBatch& B)
     if (B.reqs.empty()) return MCR_OK;
     std::sort(bases.begin(), bases.end(), [](const FileBase& a, const FileBase& b) { return std::less<const pq::File*>()(a.first, b.first); });
     const int rp = pq_plan(ctx, B.reqs.data(), (int)B.reqs.size(), B.pp, &bases, B.img_total);
-    return rp ? rp : pq_buffers(ctx, B.pp);   // (pq_stage is large enough already: no reallocation under the uploads in flight)
+    return rp ? rp : pq_buffers(ctx, B.pp);   // (the images are uploading into img.dev, which fs_open sized for this plan)
 }
 
 // 4. Decode kernels + the chain / draw bookkeeping on the device (k_chain_layout: 32 bytes per file come back instead of the
@@ -3073,7 +3035,7 @@ int mcr_summarize_files(mcr_ctx* ctx, const char* const* paths, int n_paths, int
         int rc = fs_open(ctx, B);
         if (rc) return rc;
         lap(MCR_FS_PH_OPEN);
-        StreamSync uploads{ctx->stream};   // they read pq_pin, which the next call's readers write: a return waits for them
+        StreamSync uploads{ctx->stream};   // they read img.pin, which the next call's readers write: a return waits for them
         rc = fs_read(ctx, B);
         if (!rc) { lap(MCR_FS_PH_READ); rc = fs_layout(ctx, B); }
         if (!rc) { lap(MCR_FS_PH_PLAN); rc = fs_decode(ctx, B, min_chains, diagnostics); }
@@ -3189,7 +3151,7 @@ constexpr size_t kCsvTextMax = ((size_t)1 << 32) - ((size_t)1 << 20);   // offse
 
 std::string csv_file_name(const mcr_ctx* ctx, size_t f)
 {
-    const std::string& p = ctx->csv_files[f].path;
+    const std::string& p = ctx->img.files[f].path;
     return p.empty() ? "file " + std::to_string(f) : p;
 }
 
@@ -3197,25 +3159,14 @@ std::string csv_file_name(const mcr_ctx* ctx, size_t f)
 
 int ensure_pow5(mcr_ctx* ctx)
 {
-    if (ctx->csv_pow5) return MCR_OK;
-    HIP_TRY(ctx, hipMalloc(&ctx->csv_pow5, sizeof(csv::kPow5)));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->csv_pow5, csv::kPow5, sizeof(csv::kPow5), hipMemcpyHostToDevice, ctx->stream));
-    return MCR_OK;
-}
-
-// carve_ws for one of the ingest buffers: measures the layout, makes *buf that large, then carves it.
-template <class Layout> int carve_buf(mcr_ctx* ctx, void** buf, size_t* cap, Layout&& layout)
-{
-    Carve m{nullptr};
-    layout(m);
-    const int rc = ensure_buf(ctx, buf, cap, m.off);
+    if (ctx->pow5.p) return MCR_OK;
+    const int rc = ctx->pow5.reserve(ctx, sizeof(csv::kPow5));
     if (rc) return rc;
-    Carve cv{(char*)*buf, *cap};
-    layout(cv);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->pow5.p, csv::kPow5, sizeof(csv::kPow5), hipMemcpyHostToDevice, ctx->stream));
     return MCR_OK;
 }
 
-// One parse with a hard list of Rec (csv::HardField, json::HardToken) in csv_aux, and once more with a list that fits
+// One parse with a hard list of Rec (csv::HardField, json::HardToken) in parse_scratch, and once more with a list that fits
 // when the first overflows.  layout(cv) takes the decoder's own tables in front of the list (it runs twice per pass,
 // measuring and carving, so it only takes); fill() enqueues their uploads and initial values; launch(hard, cap, count,
 // err) enqueues the kernel and the read-back of the decoder's flags.  Hands back the list and the error key (~0: none).
@@ -3229,7 +3180,7 @@ int hard_pass(mcr_ctx* ctx, std::vector<Rec>& list, unsigned long long* err, Lay
         const uint32_t cap = ctx->csv_hard_cap;
         Rec* d_hard = nullptr;
         unsigned long long* d_ctr = nullptr;                  // [0] the error key, smallest wins; [1] the hard count
-        rc = carve_buf(ctx, &ctx->csv_aux, &ctx->csv_aux_bytes, [&](Carve& cv) {
+        rc = carve(ctx, ctx->parse_scratch, [&](Carve& cv) {
             layout(cv);
             d_hard = cv.take<Rec>(cap);
             d_ctr = cv.take<unsigned long long>(2);
@@ -3262,7 +3213,7 @@ int patch_values(mcr_ctx* ctx, double* out_dev, const std::vector<long long>& id
     if (!n) return MCR_OK;
     long long* d_idx = nullptr;
     double* d_val = nullptr;
-    const int rc = carve_buf(ctx, &ctx->csv_aux, &ctx->csv_aux_bytes, [&](Carve& cv) { d_idx = cv.take<long long>(n); d_val = cv.take<double>(n); });
+    const int rc = carve(ctx, ctx->parse_scratch, [&](Carve& cv) { d_idx = cv.take<long long>(n); d_val = cv.take<double>(n); });
     if (rc) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(d_idx, idx.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(d_val, val.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -3295,7 +3246,7 @@ int csv_open_paths(mcr_ctx* ctx, const char* const* paths, int n_paths, mcr_csv*
         FileBatch B(paths, n_paths);
         B.csv = true;
         B.table = table;
-        ctx->csv_staged = false;
+        ctx->img.staged = false;
         int rc = fs_open(ctx, B);
         if (rc) return rc;
         if (B.img_total > kCsvTextMax) return fail(ctx, MCR_EINVAL, "csv: the files of one call hold %zu bytes; the limit is 4 GiB", B.img_total);
@@ -3304,8 +3255,8 @@ int csv_open_paths(mcr_ctx* ctx, const char* const* paths, int n_paths, mcr_csv*
         if (rc) return rc;
         for (int i = 0; i < n_paths; ++i) {
             BatchFile& m = B.f[(size_t)i];
-            m.csv->im.bytes = (const char*)ctx->pq_pin + m.img;
-            m.csv->owner = ctx; m.csv->gen = ctx->img_gen; m.csv->img = m.img;
+            m.csv->im.bytes = ctx->img.pin.as<const char>() + m.img;
+            m.csv->owner = ctx; m.csv->gen = ctx->img.gen; m.csv->img = m.img;
             out[i] = m.csv;
             m.csv = nullptr;
         }
@@ -3369,7 +3320,7 @@ int mcr_csv_stage(mcr_ctx* ctx, const mcr_csv* const* files, int n_files, int64_
     if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
     if (n_files < 0 || n_files > kMaxGridY || (n_files > 0 && (!files || !rows))) return fail(ctx, MCR_EINVAL, "bad file list");
     if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "mcr_csv_stage with summaries in flight");
-    ctx->csv_staged = false;
+    ctx->img.staged = false;
     try {
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         hipStream_t st = ctx->stream;
@@ -3377,7 +3328,7 @@ int mcr_csv_stage(mcr_ctx* ctx, const mcr_csv* const* files, int n_files, int64_
         for (int i = 0; i < n_files; ++i) {
             if (!files[i]) return fail(ctx, MCR_EINVAL, "file %d is NULL", i);
             if (files[i]->owner) {
-                if (files[i]->owner != ctx || files[i]->gen != ctx->img_gen)
+                if (files[i]->owner != ctx || files[i]->gen != ctx->img.gen)
                     return fail(ctx, MCR_EINVAL, "csv: file %d was read by an earlier call whose images are gone; open it again", i);
                 ++held;
             }
@@ -3390,30 +3341,23 @@ int mcr_csv_stage(mcr_ctx* ctx, const mcr_csv* const* files, int n_files, int64_
                 return table_fallback(ctx, files[i]->im.path.empty() ? "file " + std::to_string(i) : files[i]->im.path,
                                       table_flag_text(files[i]->tflags), files[i]->twhere);
         }
-        ctx->csv_table = table;
-        ctx->csv_files.assign((size_t)n_files, mcr_ctx::CsvFile());
+        ctx->img.table = table;
+        ctx->img.files.assign((size_t)n_files, mcr_ctx::FileImage::File());
         if (!held) {                                           // caller images: into the pinned buffer, one upload
             size_t total = 0;
-            for (int i = 0; i < n_files; ++i) { ctx->csv_files[(size_t)i].img = total; total = align_up(total + files[i]->im.len, 256); }
+            for (int i = 0; i < n_files; ++i) { ctx->img.files[(size_t)i].img = total; total = align_up(total + files[i]->im.len, 256); }
             if (total > kCsvTextMax) return fail(ctx, MCR_EINVAL, "csv: the files of one call hold %zu bytes; the limit is 4 GiB", total);
-            ++ctx->img_gen;
-            const int rc = ensure_buf(ctx, &ctx->pq_stage, &ctx->pq_stage_bytes, total + pq::kInWin + 256);
+            const int rc = ctx->img.rewrite(ctx, pq_stage_bytes(total), total, 0);
             if (rc) return rc;
-            if (total > ctx->pq_pin_bytes) {
-                HIP_TRY(ctx, hipStreamSynchronize(st));
-                if (ctx->pq_pin) { hipHostFree(ctx->pq_pin); ctx->pq_pin = nullptr; ctx->pq_pin_bytes = 0; }
-                HIP_TRY(ctx, hipHostMalloc(&ctx->pq_pin, total + (total >> 2), hipHostMallocDefault));
-                ctx->pq_pin_bytes = total + (total >> 2);
-            }
             for (int i = 0; i < n_files; ++i)
-                if (files[i]->im.len) memcpy((char*)ctx->pq_pin + ctx->csv_files[(size_t)i].img, files[i]->im.bytes, files[i]->im.len);
-            if (total) HIP_TRY(ctx, hipMemcpyAsync(ctx->pq_stage, ctx->pq_pin, total, hipMemcpyHostToDevice, st));
+                if (files[i]->im.len) memcpy(ctx->img.pin.as<char>() + ctx->img.files[(size_t)i].img, files[i]->im.bytes, files[i]->im.len);
+            if (total) HIP_TRY(ctx, hipMemcpyAsync(ctx->img.dev.p, ctx->img.pin.p, total, hipMemcpyHostToDevice, st));
         }
         std::vector<csv::FileDesc> desc((size_t)n_files);
         std::vector<uint32_t> chunk_file;
         uint32_t slot0 = 0;
         for (int i = 0; i < n_files; ++i) {
-            mcr_ctx::CsvFile& c = ctx->csv_files[(size_t)i];
+            mcr_ctx::FileImage::File& c = ctx->img.files[(size_t)i];
             const csv::Image& im = files[i]->im;
             if (held) c.img = files[i]->img;
             c.len = im.len; c.body = im.body; c.ncols = (int)im.names.size(); c.path = im.path;
@@ -3423,11 +3367,12 @@ int mcr_csv_stage(mcr_ctx* ctx, const mcr_csv* const* files, int n_files, int64_
             chunk_file.insert(chunk_file.end(), (c.len + csv::kChunk - 1) / csv::kChunk, (uint32_t)i);
         }
         const uint32_t n_chunks = (uint32_t)chunk_file.size();
-        ctx->csv_row0.assign((size_t)n_files + 1, 0u);
+        ctx->img.row0.assign((size_t)n_files + 1, 0u);
         if (n_chunks) {
-            csv::FileDesc* d_desc = nullptr;                  // first: the decoders find the descriptors at csv_tab itself
+            // (the tables below are this call's own to fill: it stamps staged_gen when they are whole)
+            csv::FileDesc* d_desc = nullptr;                  // first: the decoders find the descriptors at img.tab itself
             uint32_t *d_cfile = nullptr, *d_cnt = nullptr, *d_first = nullptr, *d_row0 = nullptr;
-            int rc = carve_buf(ctx, &ctx->csv_tab, &ctx->csv_tab_bytes, [&](Carve& cv) {
+            int rc = carve(ctx, ctx->img.tab, [&](Carve& cv) {
                 d_desc = cv.take<csv::FileDesc>(desc.size());
                 d_cfile = cv.take<uint32_t>(n_chunks);
                 d_cnt = cv.take<uint32_t>(n_chunks);
@@ -3435,26 +3380,26 @@ int mcr_csv_stage(mcr_ctx* ctx, const mcr_csv* const* files, int n_files, int64_
                 d_row0 = cv.take<uint32_t>((size_t)n_files + 1);
             });
             if (rc) return rc;
-            ctx->csv_row0_off = (size_t)((char*)d_row0 - (char*)ctx->csv_tab);
+            ctx->img.row0_off = (size_t)((char*)d_row0 - ctx->img.tab.as<char>());
             HIP_TRY(ctx, hipMemcpyAsync(d_desc, desc.data(), desc.size() * sizeof(csv::FileDesc), hipMemcpyHostToDevice, st));
             HIP_TRY(ctx, hipMemcpyAsync(d_cfile, chunk_file.data(), (size_t)n_chunks * 4, hipMemcpyHostToDevice, st));
-            const char* text = (const char*)ctx->pq_stage;
-            auto lines = [&](bool write) {                    // count pass, then the write pass into csv_rows
+            const char* text = ctx->img.dev.as<const char>();
+            auto lines = [&](bool write) {                    // count pass, then the write pass into img.rows
                 const auto kern = table ? (write ? csv::k_csv_lines<true, true> : csv::k_csv_lines<false, true>)
                                         : (write ? csv::k_csv_lines<true, false> : csv::k_csv_lines<false, false>);
                 LAUNCH(ctx, K_CSV_LINES, kern, dim3(n_chunks), dim3(csv::kLinesNT), 0, text, (const csv::FileDesc*)d_desc,
-                       (const uint32_t*)d_cfile, d_cnt, (const uint32_t*)d_first, write ? (uint32_t*)ctx->csv_rows : nullptr);
+                       (const uint32_t*)d_cfile, d_cnt, (const uint32_t*)d_first, write ? ctx->img.rows.as<uint32_t>() : nullptr);
                 return (int)MCR_OK;
             };
             rc = lines(false);
             if (rc) return rc;
             LAUNCH(ctx, K_CSV_SCAN, csv::k_csv_scan, dim3(1), dim3(1024), 0, (const uint32_t*)d_cnt, n_chunks, d_first,
                    (const csv::FileDesc*)d_desc, (uint32_t)n_files, d_row0);
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->csv_row0.data(), d_row0, ((size_t)n_files + 1) * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->img.row0.data(), d_row0, ((size_t)n_files + 1) * 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(ctx, hipStreamSynchronize(st));
-            const uint32_t total_rows = ctx->csv_row0[(size_t)n_files];
+            const uint32_t total_rows = ctx->img.row0[(size_t)n_files];
             if (total_rows) {
-                rc = ensure_buf(ctx, &ctx->csv_rows, &ctx->csv_rows_bytes, (size_t)total_rows * 4 + 256);
+                rc = ctx->img.rows.reserve(ctx, (size_t)total_rows * 4 + 256);
                 if (rc) return rc;
                 rc = lines(true);
                 if (rc) return rc;
@@ -3462,11 +3407,11 @@ int mcr_csv_stage(mcr_ctx* ctx, const mcr_csv* const* files, int n_files, int64_
         }
         HIP_TRY(ctx, hipStreamSynchronize(st));
         prof_resolve(ctx);
-        for (int i = 0; i < n_files; ++i) rows[i] = (int64_t)(ctx->csv_row0[(size_t)i + 1] - ctx->csv_row0[(size_t)i]);
+        for (int i = 0; i < n_files; ++i) rows[i] = (int64_t)(ctx->img.row0[(size_t)i + 1] - ctx->img.row0[(size_t)i]);
         for (int i = 0; table && i < n_files; ++i)
             if (rows[i] == 0) return table_fallback(ctx, csv_file_name(ctx, (size_t)i), "no data rows", files[i]->im.body);
-        ctx->csv_staged = true;
-        ctx->csv_staged_gen = ctx->img_gen;
+        ctx->img.staged = true;
+        ctx->img.staged_gen = ctx->img.gen;
     } catch (const std::exception& e) { return fail(ctx, MCR_ENOMEM, "csv: host allocation failed: %s", e.what()); }
     return MCR_OK;
 }
@@ -3478,50 +3423,50 @@ int mcr_csv_decode(mcr_ctx* ctx, const int* columns, int n_cols, int64_t max_row
     if (hard) *hard = 0;
     if (n_cols < 0 || max_rows < 0 || (n_cols > 0 && !columns) || stride_file < 0 || stride_row < 0 || stride_col < 0)
         return fail(ctx, MCR_EINVAL, "bad argument");
-    if (!ctx->csv_staged || ctx->csv_staged_gen != ctx->img_gen) return fail(ctx, MCR_EINVAL, "csv: no staged files (call mcr_csv_stage first)");
-    if (ctx->csv_table) return fail(ctx, MCR_EINVAL, "csv: the staged files are table CSVs (mcr_csv_decode_table reads them)");
+    if (!ctx->img.is_staged()) return fail(ctx, MCR_EINVAL, "csv: no staged files (call mcr_csv_stage first)");
+    if (ctx->img.table) return fail(ctx, MCR_EINVAL, "csv: the staged files are table CSVs (mcr_csv_decode_table reads them)");
     if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "mcr_csv_decode with summaries in flight");
     try {
-        const size_t nf = ctx->csv_files.size();
+        const size_t nf = ctx->img.files.size();
         std::vector<int> slots;
         int64_t rows_eff = 0;
         for (size_t f = 0; f < nf; ++f) {
-            const int nc = ctx->csv_files[f].ncols;
+            const int nc = ctx->img.files[f].ncols;
             const size_t s0 = slots.size();
             slots.insert(slots.end(), (size_t)nc, -1);
             for (int k = 0; k < n_cols; ++k) {
                 const int rc = claim_slot(ctx, slots, s0, nc, f, columns[f * (size_t)n_cols + (size_t)k], k);
                 if (rc) return rc;
             }
-            rows_eff = std::max(rows_eff, std::min<int64_t>(max_rows, (int64_t)(ctx->csv_row0[f + 1] - ctx->csv_row0[f])));
+            rows_eff = std::max(rows_eff, std::min<int64_t>(max_rows, (int64_t)(ctx->img.row0[f + 1] - ctx->img.row0[f])));
         }
         if (rows_eff == 0 || n_cols == 0) return MCR_OK;
         if (!out_dev) return fail(ctx, MCR_EINVAL, "out_dev is NULL");
         hipStream_t st = ctx->stream;
-        const char* tb = (const char*)ctx->csv_tab;          // as mcr_csv_stage carved it: descriptors first
+        const char* tb = ctx->img.tab.as<const char>();          // as mcr_csv_stage carved it: descriptors first
         unsigned long long h_err = ~0ull;
         std::vector<csv::HardField> list;
         int* d_slots = nullptr;
         int rc = hard_pass(ctx, list, &h_err, [&](Carve& cv) { d_slots = cv.take<int>(slots.size()); },
                            [&] { HIP_TRY(ctx, hipMemcpyAsync(d_slots, slots.data(), slots.size() * 4, hipMemcpyHostToDevice, st)); return (int)MCR_OK; },
                            [&](csv::HardField* d_hard, uint32_t cap, uint32_t* d_count, unsigned long long* d_err) {
-            csv::ParseArgs a{(const char*)ctx->pq_stage, (const csv::FileDesc*)tb, (const uint32_t*)ctx->csv_rows,
-                             (const uint32_t*)(tb + ctx->csv_row0_off), d_slots, (const uint64_t*)ctx->csv_pow5, (long long)max_rows, out_dev,
+            csv::ParseArgs a{ctx->img.dev.as<const char>(), (const csv::FileDesc*)tb, ctx->img.rows.as<const uint32_t>(),
+                             (const uint32_t*)(tb + ctx->img.row0_off), d_slots, ctx->pow5.as<const uint64_t>(), (long long)max_rows, out_dev,
                              (long long)stride_file, (long long)stride_row, (long long)stride_col, d_hard, cap, d_count, d_err};
             LAUNCH(ctx, K_CSV_PARSE, csv::k_csv_parse, dim3((unsigned)((rows_eff + csv::kParseWaves - 1) / csv::kParseWaves), (unsigned)nf),
                    dim3(csv::kParseWaves * 64), 0, a);
             return (int)MCR_OK;
         });
         if (rc) return rc;
-        const char* pin = (const char*)ctx->pq_pin;
+        const char* pin = ctx->img.pin.as<const char>();
         if (h_err != ~0ull) {
             const size_t f = (size_t)(h_err >> 44);
             const unsigned long long row = (h_err >> 4) & ((1ull << 40) - 1);
-            const mcr_ctx::CsvFile& c = ctx->csv_files[f];
+            const mcr_ctx::FileImage::File& c = ctx->img.files[f];
             if ((h_err & 15) == csv::kErrQuote)
                 return fail(ctx, MCR_EINVAL, "%s: data row %llu: quoted fields are not supported", csv_file_name(ctx, f).c_str(), row);
             uint32_t start = 0;
-            HIP_TRY(ctx, hipMemcpy(&start, (const uint32_t*)ctx->csv_rows + ctx->csv_row0[f] + row, 4, hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(&start, ctx->img.rows.as<const uint32_t>() + ctx->img.row0[f] + row, 4, hipMemcpyDeviceToHost));
             size_t fields = 1;
             for (size_t i = start; i < c.img + c.len && pin[i] != '\n'; ++i) fields += pin[i] == ',';
             return fail(ctx, MCR_EINVAL, "%s: data row %llu has %zu fields, header has %d", csv_file_name(ctx, f).c_str(), row, fields, c.ncols);
@@ -3533,8 +3478,8 @@ int mcr_csv_decode(mcr_ctx* ctx, const int* columns, int n_cols, int64_t max_row
             if (!csv::finish_field(pin + h.off, h.len, &val[i])) {
                 int col = 0;
                 size_t base = 0;
-                for (size_t s = 0; s < h.file; ++s) base += (size_t)ctx->csv_files[s].ncols;
-                while (col < ctx->csv_files[h.file].ncols && slots[base + (size_t)col] != (int)h.slot) ++col;
+                for (size_t s = 0; s < h.file; ++s) base += (size_t)ctx->img.files[s].ncols;
+                while (col < ctx->img.files[h.file].ncols && slots[base + (size_t)col] != (int)h.slot) ++col;
                 return fail(ctx, MCR_EINVAL, "%s: data row %u, column %d: could not convert string to float: '%.*s'",
                             csv_file_name(ctx, h.file).c_str(), h.row, col, (int)std::min<uint32_t>(h.len, 200u), pin + h.off);
             }
@@ -3554,18 +3499,18 @@ int mcr_csv_decode_table(mcr_ctx* ctx, const int* columns, int n_cols, const int
     if (hard) *hard = 0;
     if (n_cols < 0 || max_rows < 0 || (n_cols > 0 && !columns) || !id_columns || stride_file < 0 || stride_row < 0 || stride_col < 0)
         return fail(ctx, MCR_EINVAL, "bad argument");
-    if (!ctx->csv_staged || ctx->csv_staged_gen != ctx->img_gen || !ctx->csv_table)
+    if (!ctx->img.is_staged() || !ctx->img.table)
         return fail(ctx, MCR_EINVAL, "csv: no staged table files (call mcr_csv_open_table_paths and mcr_csv_stage first)");
     if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "mcr_csv_decode_table with summaries in flight");
     try {
-        const size_t nf = ctx->csv_files.size();
+        const size_t nf = ctx->img.files.size();
         const bool packed = stride_file == 0 && stride_col == 0;
         std::vector<int> slots;
         std::vector<csv::TableOut> outs(nf);
         int64_t rows_eff = 0, at = 0, id_at = 0;
         bool any_col = false, any_id = false;
         for (size_t f = 0; f < nf; ++f) {
-            const int nc = ctx->csv_files[f].ncols;
+            const int nc = ctx->img.files[f].ncols;
             const size_t s0 = slots.size();
             slots.insert(slots.end(), (size_t)nc, -1);
             int used = 0;
@@ -3586,7 +3531,7 @@ int mcr_csv_decode_table(mcr_ctx* ctx, const int* columns, int n_cols, const int
             for (int c = 0; c < nc; ++c)
                 if (slots[s0 + (size_t)c] == -1)
                     return fail(ctx, MCR_EINVAL, "csv: column %d of %s is neither requested nor an id column (a table is read whole)", c, csv_file_name(ctx, f).c_str());
-            const int64_t rows = std::min<int64_t>(max_rows, (int64_t)(ctx->csv_row0[f + 1] - ctx->csv_row0[f]));
+            const int64_t rows = std::min<int64_t>(max_rows, (int64_t)(ctx->img.row0[f + 1] - ctx->img.row0[f]));
             csv::TableOut& o = outs[f];
             o.rows = rows; o.sr = packed ? 1 : stride_row; o.sc = packed ? rows : stride_col;
             o.base = packed ? at : (int64_t)f * stride_file;
@@ -3600,7 +3545,7 @@ int mcr_csv_decode_table(mcr_ctx* ctx, const int* columns, int n_cols, const int
         if (any_id && !ids_dev) return fail(ctx, MCR_EINVAL, "ids_dev is NULL");
         if (n_cols > 0 && !all_int) return fail(ctx, MCR_EINVAL, "all_int is NULL");
         hipStream_t st = ctx->stream;
-        const char* tb = (const char*)ctx->csv_tab;          // as mcr_csv_stage carved it: descriptors first
+        const char* tb = ctx->img.tab.as<const char>();          // as mcr_csv_stage carved it: descriptors first
         unsigned long long h_err = ~0ull;
         std::vector<csv::HardField> list;
         std::vector<uint8_t> flags(2 * slots.size());       // all_int, then neg_zero
@@ -3617,8 +3562,8 @@ int mcr_csv_decode_table(mcr_ctx* ctx, const int* columns, int n_cols, const int
             return (int)MCR_OK;
         },
                            [&](csv::HardField* d_hard, uint32_t cap, uint32_t* d_count, unsigned long long* d_err) {
-            csv::TableArgs a{(const char*)ctx->pq_stage, (const csv::FileDesc*)tb, (const uint32_t*)ctx->csv_rows,
-                             (const uint32_t*)(tb + ctx->csv_row0_off), d_slots, (const uint64_t*)ctx->csv_pow5, d_outs, out_dev, (long long*)ids_dev,
+            csv::TableArgs a{ctx->img.dev.as<const char>(), (const csv::FileDesc*)tb, ctx->img.rows.as<const uint32_t>(),
+                             (const uint32_t*)(tb + ctx->img.row0_off), d_slots, ctx->pow5.as<const uint64_t>(), d_outs, out_dev, (long long*)ids_dev,
                              d_flags, d_flags + slots.size(), d_hard, cap, d_count, d_err};
             LAUNCH(ctx, K_CSV_TABLE_PARSE, csv::k_csv_table_parse, dim3((unsigned)((rows_eff + csv::kParseWaves - 1) / csv::kParseWaves), (unsigned)nf),
                    dim3(csv::kParseWaves * 64), 0, a);
@@ -3626,12 +3571,12 @@ int mcr_csv_decode_table(mcr_ctx* ctx, const int* columns, int n_cols, const int
             return (int)MCR_OK;
         });
         if (rc) return rc;
-        const char* pin = (const char*)ctx->pq_pin;
+        const char* pin = ctx->img.pin.as<const char>();
         if (h_err != ~0ull) {                                  // the first byte that leaves the subset: the host reader's file
             const size_t off = (size_t)(h_err >> 4);
             size_t f = 0;
-            while (f + 1 < nf && ctx->csv_files[f + 1].img <= off) ++f;
-            const mcr_ctx::CsvFile& c = ctx->csv_files[f];
+            while (f + 1 < nf && ctx->img.files[f + 1].img <= off) ++f;
+            const mcr_ctx::FileImage::File& c = ctx->img.files[f];
             const int kind = (int)(h_err & 15);
             size_t ls = off, le = off;                         // the line around it
             while (ls > c.img && pin[ls - 1] != '\n') --ls;
@@ -3657,13 +3602,13 @@ int mcr_csv_decode_table(mcr_ctx* ctx, const int* columns, int n_cols, const int
         }
         std::vector<size_t> slot_base(nf, 0);
         bool unsign = false;
-        for (size_t f = 1; f < nf; ++f) slot_base[f] = slot_base[f - 1] + (size_t)ctx->csv_files[f - 1].ncols;
+        for (size_t f = 1; f < nf; ++f) slot_base[f] = slot_base[f - 1] + (size_t)ctx->img.files[f - 1].ncols;
         std::vector<long long> idx(list.size());              // the host finishes them: strtod on the pinned image
         std::vector<double> val(list.size());
         for (size_t i = 0; i < list.size(); ++i) {
             const csv::HardField& h = list[i];
             if (!csv::finish_field(pin + h.off, h.len, &val[i]))      // (cannot happen: the device checked the grammar)
-                return table_fallback(ctx, csv_file_name(ctx, h.file), "a field outside the number grammar", h.off - ctx->csv_files[h.file].img);
+                return table_fallback(ctx, csv_file_name(ctx, h.file), "a field outside the number grammar", h.off - ctx->img.files[h.file].img);
             const csv::TableOut& o = outs[h.file];
             idx[i] = o.base + (long long)h.row * o.sr + (long long)h.slot * o.sc;
         }
@@ -3671,7 +3616,7 @@ int mcr_csv_decode_table(mcr_ctx* ctx, const int* columns, int n_cols, const int
         if (rc) return rc;
         for (size_t f = 0; f < nf && n_cols > 0; ++f) {
             for (int k = 0; k < n_cols; ++k) all_int[f * (size_t)n_cols + (size_t)k] = 0;
-            for (int c = 0; c < ctx->csv_files[f].ncols; ++c) {
+            for (int c = 0; c < ctx->img.files[f].ncols; ++c) {
                 const int k = slots[slot_base[f] + (size_t)c];
                 if (k < 0) continue;
                 all_int[f * (size_t)n_cols + (size_t)k] = flags[slot_base[f] + (size_t)c];
@@ -3699,16 +3644,10 @@ int mcr_csv_decode_table(mcr_ctx* ctx, const int* columns, int n_cols, const int
 // An indexed document.  The caller keeps `bytes` alive and unchanged; the device holds a copy and every token's offset.
 struct mcr_json {
     mcr_ctx* ctx = nullptr; const char* bytes = nullptr; size_t len = 0;
-    void* d_text = nullptr;                  // the text, padded to whole chunks
-    void* d_tok = nullptr; uint32_t n_tok = 0;
+    DevBuf d_text;                           // the text, padded to whole chunks
+    DevBuf d_tok; uint32_t n_tok = 0;
     std::vector<json::Chain> chains;
-    ~mcr_json()
-    {
-        if (!d_text && !d_tok) return;
-        hipSetDevice(ctx->device);
-        if (d_text) hipFree(d_text);
-        if (d_tok) hipFree(d_tok);
-    }
+    ~mcr_json() { if (ctx) hipSetDevice(ctx->device); }      // (the members free themselves behind this)
 };
 
 namespace {
@@ -3738,18 +3677,19 @@ int mcr_json_open(mcr_ctx* ctx, const void* bytes, size_t len, mcr_json** out)
         std::unique_ptr<mcr_json> f(new mcr_json());
         f->ctx = ctx; f->bytes = (const char*)bytes; f->len = len;
         const uint32_t n_chunks = (uint32_t)((len + json::kChunk - 1) / json::kChunk);
-        HIP_TRY(ctx, hipMalloc(&f->d_text, (size_t)n_chunks * json::kChunk));
-        HIP_TRY(ctx, hipMemcpyAsync(f->d_text, bytes, len, hipMemcpyHostToDevice, st));
+        int rc = f->d_text.reserve(ctx, (size_t)n_chunks * json::kChunk);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(f->d_text.p, bytes, len, hipMemcpyHostToDevice, st));
         // scratch: chunk counts | in_string | first | sfirst (n_chunks + 1 each) | first backslash
         const size_t o_in = align_up((size_t)n_chunks * sizeof(json::ChunkCount), 256), w = align_up(((size_t)n_chunks + 1) * 4, 256),
                      o_first = o_in + w, o_sfirst = o_first + w, o_bsl = o_sfirst + w;
-        int rc = ensure_buf(ctx, &ctx->csv_aux, &ctx->csv_aux_bytes, o_bsl + 256);
+        rc = ctx->parse_scratch.reserve(ctx, o_bsl + 256);
         if (rc) return rc;
-        char* ax = (char*)ctx->csv_aux;
+        char* ax = ctx->parse_scratch.as<char>();
         json::ChunkCount* d_cnt = (json::ChunkCount*)ax;
         uint32_t *d_in = (uint32_t*)(ax + o_in), *d_first = (uint32_t*)(ax + o_first), *d_sfirst = (uint32_t*)(ax + o_sfirst),
                  *d_bsl = (uint32_t*)(ax + o_bsl);
-        const char* text = (const char*)f->d_text;
+        const char* text = f->d_text.as<const char>();
         HIP_TRY(ctx, hipMemsetAsync(d_bsl, 0xFF, 4, st));
         LAUNCH(ctx, K_JSON_INDEX, json::k_json_index<false>, dim3(n_chunks), dim3(json::kIndexNT), 0, text, (uint32_t)len, d_cnt, d_bsl,
                (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
@@ -3763,12 +3703,13 @@ int mcr_json_open(mcr_ctx* ctx, const void* bytes, size_t len, mcr_json** out)
         if (bsl != json::kNoOffset) { prof_resolve(ctx); return fail(ctx, MCR_EFALLBACK, "json: a backslash (byte %u): escapes take the host reader", bsl); }
         std::vector<uint32_t> skel((size_t)n_skel * 2);
         if (n_tok) {
-            HIP_TRY(ctx, hipMalloc(&f->d_tok, (size_t)n_tok * 4));
-            rc = ensure_buf(ctx, &ctx->csv_rows, &ctx->csv_rows_bytes, (size_t)n_skel * 8 + 256);
+            rc = f->d_tok.reserve(ctx, (size_t)n_tok * 4);
+            // the skeleton borrows the row starts' buffer: whatever mcr_csv_stage left there is gone, and a decode says so
+            if (!rc) rc = ctx->img.rewrite(ctx, 0, 0, (size_t)n_skel * 8 + 256);
             if (rc) return rc;
-            uint32_t* d_skel = (uint32_t*)ctx->csv_rows;
+            uint32_t* d_skel = ctx->img.rows.as<uint32_t>();
             LAUNCH(ctx, K_JSON_INDEX, json::k_json_index<true>, dim3(n_chunks), dim3(json::kIndexNT), 0, text, (uint32_t)len, d_cnt, d_bsl,
-                   (const uint32_t*)d_in, (const uint32_t*)d_first, (const uint32_t*)d_sfirst, (uint32_t*)f->d_tok, d_skel, d_skel + n_skel);
+                   (const uint32_t*)d_in, (const uint32_t*)d_first, (const uint32_t*)d_sfirst, f->d_tok.as<uint32_t>(), d_skel, d_skel + n_skel);
             if (n_skel) HIP_TRY(ctx, hipMemcpyAsync(skel.data(), d_skel, (size_t)n_skel * 8, hipMemcpyDeviceToHost, st));
             HIP_TRY(ctx, hipStreamSynchronize(st));
         }
@@ -3862,8 +3803,8 @@ int mcr_json_decode(mcr_ctx* ctx, const mcr_json* f, const int* arrays, int n_pa
             return (int)MCR_OK;
         },
                            [&](json::HardToken* d_hard, uint32_t cap, uint32_t* d_count, unsigned long long* d_err) {
-            json::ParseArgs a{(const char*)f->d_text, (const uint32_t*)f->d_tok, d_descs, (uint32_t)n_arrays, (uint32_t)n_values,
-                              (const uint64_t*)ctx->csv_pow5, out_dev, (long long)stride_n, d_ni, d_hard, cap, d_count, d_err};
+            json::ParseArgs a{f->d_text.as<const char>(), f->d_tok.as<const uint32_t>(), d_descs, (uint32_t)n_arrays, (uint32_t)n_values,
+                              ctx->pow5.as<const uint64_t>(), out_dev, (long long)stride_n, d_ni, d_hard, cap, d_count, d_err};
             LAUNCH(ctx, K_JSON_PARSE, json::k_json_parse, dim3((unsigned)((n_values + json::kParseNT - 1) / json::kParseNT)), dim3(json::kParseNT),
                    0, a);
             HIP_TRY(ctx, hipMemcpyAsync(not_int.data(), d_ni, n_arrays * 4, hipMemcpyDeviceToHost, st));
