@@ -427,6 +427,54 @@ int mcr_pq_image_pages(const mcr_pq_image* image); /* data pages of the file */
 void mcr_pq_image_free(mcr_pq_image* image);
 
 /* ------------------------------------------------------------------------------------------------
+ * CSV writing: device columns -> text image.
+ * Replaces `pyarrow.csv.write_csv(table, out)` of the reference's `draws` command
+ * (src/mcmc_ref/cli.py:100-127), byte for byte, for float64 / int64 columns without nulls.
+ * A double is nan, [-]inf, [-]0, or the shortest digits d1..dn that read back to it (the closest
+ * such string), v = d1.d2..dn x 10^e: positional without exponent when -6 <= e <= 9 (0.000001,
+ * 1500000000, 12345.678), d1[.d2..dn]e[+-]E otherwise (1e+10, 1.2e-7, 5e-324); never more than 25
+ * bytes.  Integers are plain decimal.  Separator ',', '\n' after every row.
+ * Columns are addressed as for mcr_parquet_write_dev; `type` says only integer (MCR_PQ_INT32 and
+ * MCR_PQ_INT64 print alike, the full int64 range) or MCR_PQ_DOUBLE (printed from its 64 bits, never
+ * through a float32).  An f64 source declared integer is checked: a value that is no integer ends
+ * the call with MCR_EINVAL naming the column and the first such row.
+ * `rows` is the row count of the source.  Without a row list the rows 0 .. rows - 1 are written;
+ * with one, its n_index entries select and order them (repeats allowed, n_index may be 0: the header
+ * alone).  MCR_EINVAL, with the reason in the message: rows < 0 or >= 2^31, n_index < 0 or >= 2^31,
+ * n_cols < 1, stride < 1, an integer source declared DOUBLE, a list entry outside 0 .. rows - 1.
+ * A table whose worst-case text (26 bytes per field) exceeds the workspace limit is written in row
+ * ranges appended to the one image.
+ * ---------------------------------------------------------------------------------------------- */
+#define MCR_CSVW_TILE_FIELDS 2048 /* fields per k_csvw_format workgroup: whole rows when n_cols <= this, else a row is cut */
+#define MCR_CSVW_FIELD_MAX 26     /* the longest field and its separator */
+#define MCR_CSVW_HEADER_QUOTED 0  /* "name" with an inner quote doubled: pyarrow's default */
+#define MCR_CSVW_HEADER_PLAIN 1   /* the names as they are (MCR_EINVAL for a name with a quote, comma, CR or LF) */
+#define MCR_CSVW_HEADER_NONE 2
+typedef struct mcr_text_image mcr_text_image;
+
+/* Synchronous; uses the current lane's workspace, so no summary may be in flight.  index_dev: device memory.
+ * *out owns the image (pinned host memory) until mcr_text_image_free. */
+int mcr_csv_write_dev(mcr_ctx* ctx, const mcr_pq_column* cols, int n_cols, int64_t rows, const int64_t* index_dev,
+                      int64_t n_index, int header, mcr_text_image** out);
+/* The same from HOST columns and a host row list, without a device: ctx may be NULL.  The same formatter walks the
+ * same tiles: the bytes are identical to the device's. */
+int mcr_csv_write_host(mcr_ctx* ctx, const mcr_pq_column* cols, int n_cols, int64_t rows, const int64_t* index,
+                       int64_t n_index, int header, mcr_text_image** out);
+const void* mcr_text_image_data(const mcr_text_image* image);
+size_t mcr_text_image_size(const mcr_text_image* image);
+void mcr_text_image_free(mcr_text_image* image);
+/* The grammar for one value (host, like mcr_parse_double): writes len <= 25 bytes, no terminator. */
+int mcr_format_double(double v, char* out26, int* len);
+
+/* Stable selection (the reference's `ds.field("chain").isin(chains)`, src/mcmc_ref/store.py:79-95): the indices of
+ * the rows of chain_dev[0 .. M) whose value is in chains[0 .. n_chains) (host memory), in order, into
+ * rows_dev[0 .. *n_selected) (device memory, room for M).  An empty list selects nothing; repeats are harmless.
+ * Synchronous; uses the current lane's workspace. */
+#define MCR_SELECT_BLOCK_ROWS 256 /* rows per k_select_rows workgroup */
+int mcr_select_rows_dev(mcr_ctx* ctx, const int64_t* chain_dev, int64_t M, const int64_t* chains, int n_chains,
+                        int64_t* rows_dev, int64_t* n_selected);
+
+/* ------------------------------------------------------------------------------------------------
  * Many draws files -> statistics in ONE call (the per-model loop of reference.stats /
  * diagnostics_for_model, src/mcmc_ref/reference.py:30-104, over a list of
  * draws/<model>.draws.parquet files): mmap + footer parse on the host, one batched GPU decode, the

@@ -31,6 +31,7 @@
 #include "mcr_ext.hpp"
 #include "mcr_parquet.hpp"
 #include "mcr_pqwrite.hpp"
+#include "mcr_csvwrite.hpp"
 #include "mcr_layout.hpp"
 #include "mcr_csv.hpp"
 #include "mcr_json.hpp"
@@ -58,7 +59,7 @@ enum KernelId {
     K_CSV_LINES, K_CSV_SCAN, K_CSV_PARSE, K_CSV_PATCH, K_CSV_TABLE_PARSE, K_CSV_UNSIGN_ZERO,
     K_JSON_INDEX, K_JSON_SCAN, K_JSON_PARSE,
     K_LAYOUT_SCAN, K_LAYOUT_KEYS, K_LAYOUT_HIST, K_LAYOUT_OFFSETS, K_LAYOUT_SCATTER, K_LAYOUT_BOUNDS,
-    K_PQW_ENCODE, K_PQW_COMPACT, K_COUNT
+    K_PQW_ENCODE, K_PQW_COMPACT, K_CSVW_FORMAT, K_CSVW_SCAN, K_CSVW_COMPACT, K_SELECT_ROWS, K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {
     "k_ingest", "k_moments", "k_moments_final", "k_tile_sort", "k_merge", "k_order_stats", "k_rank_z",
@@ -68,7 +69,7 @@ const char* const kKernelNames[K_COUNT] = {
     "k_csv_lines", "k_csv_scan", "k_csv_parse", "k_csv_patch", "k_csv_table_parse", "k_csv_unsign_zero",
     "k_json_index", "k_json_scan", "k_json_parse",
     "k_layout_scan", "k_layout_keys", "k_layout_hist", "k_layout_offsets", "k_layout_scatter", "k_layout_bounds",
-    "k_pqw_encode", "k_pqw_compact"};
+    "k_pqw_encode", "k_pqw_compact", "k_csvw_format", "k_csvw_scan", "k_csvw_compact", "k_select_rows"};
 
 struct EvPair { hipEvent_t a, b; int kid; };
 
@@ -160,6 +161,7 @@ struct mcr_ctx {
     } img;
     DevBuf parse_scratch{4};   // a text decoder's call: slot tables, hard list, counters, patch list; mcr_json_open: chunk counts
     DevBuf pow5;               // device copy of csv::kPow5
+    DevBuf pow10;              // device copy of csvw::kPow10
     uint32_t csv_hard_cap = 4096;
     int io_threads = 8;                                    // MCR_IO_THREADS: host threads that read the file images and parse their footers
     size_t io_piece = (size_t)2 << 20;                     // MCR_IO_PIECE_KB: the finished prefix is uploaded in pieces of at least this size
@@ -2556,6 +2558,254 @@ void mcr_pq_image_free(mcr_pq_image* im)
     if (!im) return;
     if (im->pinned) hipHostFree(im->data); else free(im->data);
     delete im;
+}
+
+// ---- CSV writing (mcr_csvwrite.hpp; replaces pacsv.write_csv of the reference's draws command, cli.py:100-127) ------
+
+struct mcr_text_image { PinBuf pin; std::vector<unsigned char> host; size_t size = 0; bool pinned = false; };
+
+namespace {
+namespace csvw = mcr::csvw;
+static_assert(csvw::kTileFields == MCR_CSVW_TILE_FIELDS && csvw::kFieldMax == MCR_CSVW_FIELD_MAX && csvw::kSelectNT == MCR_SELECT_BLOCK_ROWS,
+              "the header states the tile geometry");
+static_assert(csvw::HEADER_QUOTED == MCR_CSVW_HEADER_QUOTED && csvw::HEADER_PLAIN == MCR_CSVW_HEADER_PLAIN && csvw::HEADER_NONE == MCR_CSVW_HEADER_NONE,
+              "header modes");
+
+struct CsvwJob {
+    std::vector<std::string> names; std::vector<pqw::ColDev> cols; std::vector<unsigned char> header;
+    csvw::Tiling tiling; i64 count = 0;       // rows to write
+};
+
+int csvw_args(mcr_ctx* ctx, const char* who, const mcr_pq_column* cols, int n_cols, int64_t rows, const int64_t* index, int64_t n_index,
+              int header, mcr_text_image** out, CsvwJob& J)
+{
+    namespace pq = mcr::pq;
+    if (!cols || !out) return fail(ctx, MCR_EINVAL, "%s: NULL argument", who);
+    if (n_cols < 1) return fail(ctx, MCR_EINVAL, "%s: n_cols = %d; at least one column is needed", who, n_cols);
+    if (rows < 0 || rows >= (int64_t)1 << 31) return fail(ctx, MCR_EINVAL, "%s: row count %lld out of range (0 .. 2^31 - 1)", who, (long long)rows);
+    if (index && (n_index < 0 || n_index >= (int64_t)1 << 31))
+        return fail(ctx, MCR_EINVAL, "%s: row list length %lld out of range (0 .. 2^31 - 1)", who, (long long)n_index);
+    if (header != MCR_CSVW_HEADER_QUOTED && header != MCR_CSVW_HEADER_PLAIN && header != MCR_CSVW_HEADER_NONE)
+        return fail(ctx, MCR_EINVAL, "%s: header mode %d", who, header);
+    for (int c = 0; c < n_cols; ++c) {
+        const mcr_pq_column& q = cols[c];
+        if (!q.name) return fail(ctx, MCR_EINVAL, "%s: column %d has no name", who, c);
+        if (header == MCR_CSVW_HEADER_PLAIN && strpbrk(q.name, "\",\r\n"))
+            return fail(ctx, MCR_EINVAL, "%s: column '%s' cannot be written in a plain header (quote, comma or line end in the name)", who, q.name);
+        if (q.type != MCR_PQ_INT32 && q.type != MCR_PQ_INT64 && q.type != MCR_PQ_DOUBLE)
+            return fail(ctx, MCR_EINVAL, "%s: column '%s' has type %d; only INT32, INT64 and DOUBLE are written", who, q.name, q.type);
+        if (q.src_kind == MCR_PQW_F64 || q.src_kind == MCR_PQW_I64) {
+            if (q.stride < 1) return fail(ctx, MCR_EINVAL, "%s: column '%s' has stride %lld; a stride >= 1 is needed", who, q.name, (long long)q.stride);
+            if (!q.src_dev && rows > 0) return fail(ctx, MCR_EINVAL, "%s: column '%s' has no source", who, q.name);
+        } else if (q.src_kind == MCR_PQW_SEQ) {
+            if (q.seq_div < 1 || q.seq_mod < 1) return fail(ctx, MCR_EINVAL, "%s: column '%s' needs seq_div >= 1 and seq_mod >= 1", who, q.name);
+        } else return fail(ctx, MCR_EINVAL, "%s: column '%s' has source kind %d", who, q.name, q.src_kind);
+        if (q.src_kind != MCR_PQW_F64 && q.type == MCR_PQ_DOUBLE)
+            return fail(ctx, MCR_EINVAL, "%s: column '%s': an integer source is written as INT32 or INT64", who, q.name);
+        J.names.push_back(q.name);
+        J.cols.push_back(pqw::ColDev{q.src_dev, (i64)q.stride, (i64)q.seq_div, (i64)q.seq_mod, q.src_kind,
+                                     q.type == MCR_PQ_DOUBLE ? pq::T_DOUBLE : pq::T_INT64});
+    }
+    J.tiling = csvw::make_tiling(n_cols);
+    J.count = index ? (i64)n_index : (i64)rows;
+    csvw::put_header(J.names, header, J.header);
+    return MCR_OK;
+}
+
+// err as k_csvw_format leaves it
+int csvw_bad(mcr_ctx* ctx, const char* who, const CsvwJob& J, const unsigned long long* err, i64 rows)
+{
+    if (err[0] != ~0ull)
+        return fail(ctx, MCR_EINVAL, "%s: entry %llu of the row list is outside the source's rows (0 .. %lld)", who, err[0], (long long)rows - 1);
+    const unsigned long long nc = (unsigned long long)J.cols.size();
+    return fail(ctx, MCR_EINVAL, "%s: column '%s', row %llu of the output: the value is not an integer", who, J.names[err[1] % nc].c_str(), err[1] / nc);
+}
+
+int ensure_pow10(mcr_ctx* ctx)
+{
+    if (ctx->pow10.p) return MCR_OK;
+    const int rc = ctx->pow10.reserve(ctx, sizeof(csvw::kPow10));
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpy(ctx->pow10.p, csvw::kPow10, sizeof(csvw::kPow10), hipMemcpyHostToDevice));
+    return MCR_OK;
+}
+
+struct CsvwBufs { pqw::ColDev* cols; unsigned long long* err; u32* sizes; u64* offs; unsigned char *slots, *image; };
+constexpr i64 kCsvwMaxTiles = (i64)1 << 30;       // of one launch
+
+// The one layout of a row range's workspace: nr rows of the job.
+void carve_csvw(Carve& cv, const CsvwJob& J, i64 nr, CsvwBufs& b)
+{
+    const size_t nt = (size_t)csvw::tile_count(J.tiling, nr);
+    b.cols = cv.take<pqw::ColDev>(J.cols.size()); b.err = cv.take<unsigned long long>(2);
+    b.sizes = cv.take<u32>(nt); b.offs = cv.take<u64>(nt + 1);
+    b.slots = cv.take<unsigned char>(nt * csvw::slot_bytes(J.tiling));
+    b.image = cv.take<unsigned char>((size_t)nr * J.cols.size() * csvw::kFieldMax);
+}
+}  // namespace
+
+int mcr_csv_write_dev(mcr_ctx* ctx, const mcr_pq_column* cols, int n_cols, int64_t rows, const int64_t* index_dev, int64_t n_index,
+                      int header, mcr_text_image** out)
+{
+    static const char* who = "mcr_csv_write_dev";
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "%s with summaries in flight", who);
+    try {
+        CsvwJob J;
+        int rc = csvw_args(ctx, who, cols, n_cols, rows, index_dev, n_index, header, out, J);
+        if (rc) return rc;
+        *out = nullptr;
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        rc = ensure_pow10(ctx);
+        if (rc) return rc;
+        std::unique_ptr<mcr_text_image> img(new mcr_text_image());
+        img->pinned = true;
+        const size_t hdr = J.header.size();
+        const i64 count = J.count;
+        auto measure = [&](i64 nr) { Carve m{nullptr}; CsvwBufs b; carve_csvw(m, J, nr, b); return m.off; };
+        // rows per range: all of them, or the most whole tiles whose layout fits the workspace limit
+        const i64 step = J.tiling.R;
+        i64 per = count;
+        if (count > 0 && (measure(count) > ctx->ws_limit || csvw::tile_count(J.tiling, count) > kCsvwMaxTiles)) {
+            auto fits = [&](i64 k) { const i64 nr = std::min(count, k * step); return measure(nr) <= ctx->ws_limit && csvw::tile_count(J.tiling, nr) <= kCsvwMaxTiles; };
+            if (!fits(1)) return fail(ctx, MCR_ENOMEM, "%s: %lld row(s) of %d columns need %zu bytes of workspace; limit is %zu", who, (long long)step,
+                                      n_cols, measure(std::min(count, step)), ctx->ws_limit);
+            i64 lo = 1, hi = (count + step - 1) / step;
+            while (lo < hi) { const i64 mid = lo + (hi - lo + 1) / 2; if (fits(mid)) lo = mid; else hi = mid - 1; }
+            per = lo * step;
+        }
+        size_t used = 0;
+        // room for `need` bytes of the image (or `hint`, when that is more), the first `used` kept
+        auto ensure = [&](size_t need, size_t hint) {
+            if (need <= img->pin.cap) return (int)MCR_OK;
+            PinBuf grown;
+            const int rc2 = grown.reserve(ctx, std::max(need, hint));
+            if (rc2) return rc2;
+            if (used) memcpy(grown.p, img->pin.p, used);
+            img->pin = std::move(grown);
+            return (int)MCR_OK;
+        };
+        auto with_header = [&](size_t body, size_t hint) {
+            if (used || hdr + body == 0) return ensure(used + body, hint);
+            const int rc2 = ensure(hdr + body, hint);
+            if (rc2) return rc2;
+            memcpy(img->pin.p, J.header.data(), hdr);
+            used = hdr;
+            return (int)MCR_OK;
+        };
+        hipStream_t st = ctx->stream;
+        for (i64 r0 = 0; r0 < count; r0 += per) {
+            const i64 nr = std::min(per, count - r0);
+            const i64 nt = csvw::tile_count(J.tiling, nr);
+            CsvwBufs b;
+            rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) { carve_csvw(cv, J, nr, b); });
+            if (rc) return rc;
+            HIP_TRY(ctx, hipMemcpyAsync(b.cols, J.cols.data(), sizeof(pqw::ColDev) * J.cols.size(), hipMemcpyHostToDevice, st));
+            HIP_TRY(ctx, hipMemsetAsync(b.err, 0xFF, 16, st));
+            const csvw::FormatArgs fa{b.cols, J.tiling, r0, nr, (const i64*)index_dev, (i64)rows, ctx->pow10.as<const uint64_t>(), b.slots, b.sizes, b.err};
+            LAUNCH(ctx, K_CSVW_FORMAT, csvw::k_csvw_format, dim3((unsigned)nt), dim3(csvw::kNT), 0, fa);
+            LAUNCH(ctx, K_CSVW_SCAN, csvw::k_csvw_scan, dim3(1), dim3(256), 0, (const u32*)b.sizes, nt, b.offs);
+            unsigned long long h_err[2]; u64 total = 0;
+            HIP_TRY(ctx, hipMemcpyAsync(h_err, b.err, 16, hipMemcpyDeviceToHost, st));
+            HIP_TRY(ctx, hipMemcpyAsync(&total, b.offs + nt, 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(ctx, hipStreamSynchronize(st));
+            if (h_err[0] != ~0ull || h_err[1] != ~0ull) { prof_resolve(ctx); return csvw_bad(ctx, who, J, h_err, (i64)rows); }
+            if (total > (u64)nr * J.cols.size() * csvw::kFieldMax) { prof_resolve(ctx); return fail(ctx, MCR_EHIP, "%s: the text overran its bound", who); }
+            // a later range of several: room for the rest at this range's bytes per row, and a twentieth more
+            const size_t hint = r0 + nr < count ? hdr + (size_t)((double)(used + total) / (double)(r0 + nr) * 1.05 * (double)count) : 0;
+            rc = with_header((size_t)total, hint);
+            if (rc) { prof_resolve(ctx); return rc; }
+            LAUNCH(ctx, K_CSVW_COMPACT, csvw::k_csvw_compact, dim3((unsigned)nt), dim3(256), 0, (const unsigned char*)b.slots, csvw::slot_bytes(J.tiling),
+                   (const u32*)b.sizes, (const u64*)b.offs, b.image);
+            HIP_TRY(ctx, hipMemcpyAsync(img->pin.as<unsigned char>() + used, b.image, (size_t)total, hipMemcpyDeviceToHost, st));
+            HIP_TRY(ctx, hipStreamSynchronize(st));
+            prof_resolve(ctx);
+            used += (size_t)total;
+        }
+        if (!used) { rc = with_header(0, 0); if (rc) return rc; }
+        img->size = used;
+        *out = img.release();
+    } catch (const std::exception& ex) {
+        return fail(ctx, MCR_ENOMEM, "%s: host allocation failed: %s", who, ex.what());
+    }
+    return MCR_OK;
+}
+
+int mcr_csv_write_host(mcr_ctx* ctx, const mcr_pq_column* cols, int n_cols, int64_t rows, const int64_t* index, int64_t n_index, int header,
+                       mcr_text_image** out)
+{
+    static const char* who = "mcr_csv_write_host";
+    try {
+        CsvwJob J;
+        const int rc = csvw_args(ctx, who, cols, n_cols, rows, index, n_index, header, out, J);
+        if (rc) return rc;
+        *out = nullptr;
+        std::unique_ptr<mcr_text_image> img(new mcr_text_image());
+        img->host = std::move(J.header);
+        unsigned long long err[2] = {~0ull, ~0ull};
+        csvw::format_host(J.cols.data(), J.tiling, J.count, (const i64*)index, (i64)rows, img->host, err);
+        if (err[0] != ~0ull || err[1] != ~0ull) return csvw_bad(ctx, who, J, err, (i64)rows);
+        img->size = img->host.size();
+        *out = img.release();
+    } catch (const std::exception& ex) {
+        return fail(ctx, MCR_ENOMEM, "%s: host allocation failed: %s", who, ex.what());
+    }
+    return MCR_OK;
+}
+
+const void* mcr_text_image_data(const mcr_text_image* im) { return !im ? nullptr : im->pinned ? im->pin.p : (const void*)im->host.data(); }
+size_t mcr_text_image_size(const mcr_text_image* im) { return im ? im->size : 0; }
+void mcr_text_image_free(mcr_text_image* im) { delete im; }
+
+int mcr_format_double(double v, char* out26, int* len)
+{
+    if (!out26 || !len) return MCR_EINVAL;
+    u64 bits;
+    memcpy(&bits, &v, 8);
+    const csvw::Dec d = csvw::dec_double(bits, csvw::kPow10);
+    csvw::dec_put(d, (unsigned char*)out26);
+    *len = (int)csvw::dec_len(d);
+    return MCR_OK;
+}
+
+int mcr_select_rows_dev(mcr_ctx* ctx, const int64_t* chain_dev, int64_t M, const int64_t* chains, int n_chains, int64_t* rows_dev,
+                        int64_t* n_selected)
+{
+    static const char* who = "mcr_select_rows_dev";
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    if (!n_selected || n_chains < 0 || (n_chains > 0 && !chains)) return fail(ctx, MCR_EINVAL, "%s: NULL argument or a negative list length", who);
+    if (M < 0 || M >= (int64_t)1 << 31) return fail(ctx, MCR_EINVAL, "%s: row count %lld out of range (0 .. 2^31 - 1)", who, (long long)M);
+    *n_selected = 0;
+    if (M == 0 || n_chains == 0) return MCR_OK;
+    if (!chain_dev || !rows_dev) return fail(ctx, MCR_EINVAL, "%s: NULL argument", who);
+    if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "%s with summaries in flight", who);
+    try {
+        std::vector<i64> list(chains, chains + n_chains);
+        std::sort(list.begin(), list.end());
+        list.erase(std::unique(list.begin(), list.end()), list.end());
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const i64 nb = (M + csvw::kSelectNT - 1) / csvw::kSelectNT;
+        i64* d_list; u32* d_counts; u64* d_offs;
+        const int rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) {
+            d_list = cv.take<i64>(list.size()); d_counts = cv.take<u32>((size_t)nb); d_offs = cv.take<u64>((size_t)nb + 1);
+        });
+        if (rc) return rc;
+        hipStream_t st = ctx->stream;
+        HIP_TRY(ctx, hipMemcpyAsync(d_list, list.data(), 8 * list.size(), hipMemcpyHostToDevice, st));
+        LAUNCH(ctx, K_SELECT_ROWS, csvw::k_select_rows<false>, dim3((unsigned)nb), dim3(csvw::kSelectNT), 0, (const i64*)chain_dev, (i64)M,
+               (const i64*)d_list, (int)list.size(), d_counts, (const u64*)d_offs, (i64*)rows_dev);
+        LAUNCH(ctx, K_CSVW_SCAN, csvw::k_csvw_scan, dim3(1), dim3(256), 0, (const u32*)d_counts, nb, d_offs);
+        LAUNCH(ctx, K_SELECT_ROWS, csvw::k_select_rows<true>, dim3((unsigned)nb), dim3(csvw::kSelectNT), 0, (const i64*)chain_dev, (i64)M,
+               (const i64*)d_list, (int)list.size(), d_counts, (const u64*)d_offs, (i64*)rows_dev);
+        u64 total = 0;
+        HIP_TRY(ctx, hipMemcpyAsync(&total, d_offs + nb, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        prof_resolve(ctx);
+        *n_selected = (int64_t)total;
+    } catch (const std::exception& ex) {
+        return fail(ctx, MCR_ENOMEM, "%s: host allocation failed: %s", who, ex.what());
+    }
+    return MCR_OK;
 }
 
 // ---- device row order (mcr_layout.hpp) -------------------------------------------------------------------------

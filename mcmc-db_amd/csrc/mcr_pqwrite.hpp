@@ -297,24 +297,28 @@ __global__ __launch_bounds__(kNT) void k_pqw_encode(const ColDev* __restrict__ c
     }
 }
 
-// One workgroup per segment of the file image: a page's stream from its slot, or host-built bytes from the blob.
-__global__ __launch_bounds__(256) void k_pqw_compact(const Seg* __restrict__ segs, const unsigned char* __restrict__ slots,
-                                                     const unsigned char* __restrict__ blob, unsigned char* __restrict__ image)
+// len bytes from src to dst by a workgroup of 256 threads, in 16-byte stores where dst allows.
+__device__ __forceinline__ void wg_copy(unsigned char* __restrict__ dst, const unsigned char* __restrict__ src, u32 len)
 {
-    const Seg sg = segs[blockIdx.x];
-    const unsigned char* src = (sg.from_blob ? blob : slots) + sg.src_off;
-    unsigned char* dst = image + sg.dst_off;
     const u32 tid = threadIdx.x;
-    const u32 head = min(sg.len, (16u - (u32)((uintptr_t)dst & 15)) & 15);
+    const u32 head = min(len, (16u - (u32)((uintptr_t)dst & 15)) & 15);
     if (tid < head) dst[tid] = src[tid];
-    const u32 nv = (sg.len - head) >> 4;
+    const u32 nv = (len - head) >> 4;
     for (u32 v = tid; v < nv; v += 256) {
         uint4 x;
         __builtin_memcpy(&x, src + head + 16 * (size_t)v, 16);      // the source is at any byte offset
         *(uint4*)(dst + head + 16 * (size_t)v) = x;
     }
     const u32 done = head + 16 * nv;
-    if (tid < sg.len - done) dst[done + tid] = src[done + tid];
+    if (tid < len - done) dst[done + tid] = src[done + tid];
+}
+
+// One workgroup per segment of the file image: a page's stream from its slot, or host-built bytes from the blob.
+__global__ __launch_bounds__(256) void k_pqw_compact(const Seg* __restrict__ segs, const unsigned char* __restrict__ slots,
+                                                     const unsigned char* __restrict__ blob, unsigned char* __restrict__ image)
+{
+    const Seg sg = segs[blockIdx.x];
+    wg_copy(image + sg.dst_off, (sg.from_blob ? blob : slots) + sg.src_off, sg.len);
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------

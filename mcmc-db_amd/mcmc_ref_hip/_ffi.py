@@ -70,6 +70,8 @@ MCR_PQ_F64, MCR_PQ_I64 = 0, 1
 MCR_PQ_INT32, MCR_PQ_INT64, MCR_PQ_DOUBLE = 1, 2, 5          # physical types (parquet.thrift)
 MCR_PQW_F64, MCR_PQW_I64, MCR_PQW_SEQ = 0, 1, 2              # sources of a written column
 MCR_PQW_PAGE_ROWS, MCR_PQW_ROW_GROUP_ROWS = 8192, 1048576
+MCR_CSVW_TILE_FIELDS, MCR_CSVW_FIELD_MAX, MCR_SELECT_BLOCK_ROWS = 2048, 26, 256
+CSV_HEADERS = {"quoted": 0, "plain": 1, "none": 2}           # MCR_CSVW_HEADER_*
 INT64_MAX = (1 << 63) - 1
 
 
@@ -163,6 +165,13 @@ SYMBOLS = {
     "mcr_pq_image_size": (C.c_size_t, [C.c_void_p]),
     "mcr_pq_image_pages": (C.c_int, [C.c_void_p]),
     "mcr_pq_image_free": (None, [C.c_void_p]),
+    "mcr_csv_write_dev": (C.c_int, [C.c_void_p, C.POINTER(PqColumn), C.c_int, _I64, C.c_void_p, _I64, C.c_int, C.POINTER(C.c_void_p)]),
+    "mcr_csv_write_host": (C.c_int, [C.c_void_p, C.POINTER(PqColumn), C.c_int, _I64, _ip, _I64, C.c_int, C.POINTER(C.c_void_p)]),
+    "mcr_text_image_data": (C.c_void_p, [C.c_void_p]),
+    "mcr_text_image_size": (C.c_size_t, [C.c_void_p]),
+    "mcr_text_image_free": (None, [C.c_void_p]),
+    "mcr_format_double": (C.c_int, [C.c_double, C.c_char_p, C.POINTER(C.c_int)]),
+    "mcr_select_rows_dev": (C.c_int, [C.c_void_p, C.c_void_p, _I64, _ip, C.c_int, C.c_void_p, _ip]),
     "mcr_gather_rows_dev": (C.c_int, [C.c_void_p, C.c_void_p, _I64, _I64, _ip, C.c_void_p]),
     "mcr_chain_layout_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _I64, C.c_void_p, _ip, _ip, C.c_int,
                                        C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -343,6 +352,41 @@ class PqImage:
             pass
 
 
+class TextImage:
+    """A text image the library owns (mcr_text_image): `view` is its bytes without a copy, valid until close()."""
+
+    def __init__(self, lib, handle):
+        self.lib, self.handle = lib, handle
+        self.size = int(lib.mcr_text_image_size(handle))
+        data = lib.mcr_text_image_data(handle)
+        self.view = memoryview((C.c_ubyte * self.size).from_address(data)).cast("B") if self.size else memoryview(b"")
+
+    def tobytes(self) -> bytes:
+        return self.view.tobytes()
+
+    def __len__(self):
+        return self.size
+
+    def close(self):
+        if self.handle:
+            self.view.release()
+            self.view = None
+            self.lib.mcr_text_image_free(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):  # pragma: no cover - best effort
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _pq_columns(columns, host: bool):
     """(PqColumn array, objects to keep alive) of pq_column / pq_sequence tuples."""
     arr = (PqColumn * max(len(columns), 1))()
@@ -375,6 +419,31 @@ def write_parquet_host(columns, rows: int, row_group_rows: int = 0) -> PqImage:
     if rc != MCR_OK:
         raise McrError(rc, (lib.mcr_last_error(None) or b"").decode())
     return PqImage(lib, h)
+
+
+def write_csv_host(columns, rows: int, row_index=None, header: str = "quoted") -> TextImage:
+    """mcr_csv_write_host: the CSV text of host columns (numpy arrays or pq_sequence), without a device; `row_index`
+    (int64 values) selects and orders the rows.  The bytes are the device's (Context.write_csv)."""
+    lib = load_library()
+    arr, _keep = _pq_columns(columns, host=True)
+    idx = None if row_index is None else np.ascontiguousarray(row_index, dtype=np.int64)
+    n = 0 if idx is None else idx.size
+    if idx is not None and n == 0:
+        idx = np.zeros(1, dtype=np.int64)         # an empty list is still a list: its pointer must not be NULL
+    h = C.c_void_p()
+    rc = lib.mcr_csv_write_host(None, arr, len(columns), int(rows), _as_ip(idx), n, CSV_HEADERS[header], C.byref(h))
+    if rc != MCR_OK:
+        raise McrError(rc, (lib.mcr_last_error(None) or b"").decode())
+    return TextImage(lib, h)
+
+
+def format_double(v: float) -> str:
+    """mcr_format_double: the text write_csv gives one float64 (pyarrow's, byte for byte)."""
+    buf, n = C.create_string_buffer(MCR_CSVW_FIELD_MAX), C.c_int()
+    rc = load_library().mcr_format_double(float(v), buf, C.byref(n))
+    if rc != MCR_OK:
+        raise McrError(rc, "mcr_format_double")
+    return buf.raw[:n.value].decode()
 
 
 class DeviceBuffer:
@@ -658,6 +727,43 @@ class Context:
         h = C.c_void_p()
         self._check(self.lib.mcr_parquet_write_dev(self.handle, arr, len(columns), int(rows), int(row_group_rows), C.byref(h)))
         return PqImage(self.lib, h)
+
+    def write_csv(self, columns, rows: int, row_index=None, header: str = "quoted") -> TextImage:
+        """mcr_csv_write_dev: the CSV text of device columns (pq_column / pq_sequence tuples) of `rows` rows, formatted on
+        the GPU, byte for byte what pyarrow.csv.write_csv gives the same table.  row_index selects and orders the rows:
+        (device pointer or buffer, count) -- what select_rows returns -- or int64 values in host memory, uploaded
+        here.  header: "quoted" (pyarrow's default), "plain" or "none".  Close the image to free its pinned memory."""
+        arr, _keep = _pq_columns(columns, host=False)
+        own, ptr, n = None, None, 0
+        if row_index is not None and isinstance(row_index, tuple):
+            ptr, n = row_index
+            ptr = getattr(ptr, "ptr", ptr)
+        elif row_index is not None:
+            idx = np.ascontiguousarray(row_index, dtype=np.int64)
+            own = DeviceBuffer(self, max(idx.nbytes, 8)).upload(idx)
+            ptr, n = own.ptr, idx.size
+        h = C.c_void_p()
+        try:
+            self._check(self.lib.mcr_csv_write_dev(self.handle, arr, len(columns), int(rows), ptr, int(n), CSV_HEADERS[header],
+                                                   C.byref(h)))
+        finally:
+            if own is not None:
+                own.free()
+        return TextImage(self.lib, h)
+
+    def select_rows(self, chain_ptr, M: int, chains) -> tuple:
+        """mcr_select_rows_dev: (device buffer of int64 row indices, count) of the rows of the device int64 column
+        `chain_ptr[0 .. M)` whose value is in `chains`, in order: the row_index of write_csv.  Free the buffer."""
+        want = np.ascontiguousarray(list(chains), dtype=np.int64)
+        out = DeviceBuffer(self, max(int(M) * 8, 8))
+        n = C.c_int64()
+        try:
+            self._check(self.lib.mcr_select_rows_dev(self.handle, getattr(chain_ptr, "ptr", chain_ptr), int(M), _as_ip(want), want.size,
+                                                     out.ptr, C.byref(n)))
+        except BaseException:
+            out.free()
+            raise
+        return out, int(n.value)
 
     def gather_rows_order(self, src_ptr, P: int, M: int, order_ptr, dst_ptr):
         """dst[p][k] = src[p][order[k]], everything in device memory (mcr_gather_rows_order_dev)."""

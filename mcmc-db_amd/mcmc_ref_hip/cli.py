@@ -3,14 +3,16 @@
 Mirrors src/mcmc_ref/cli.py for `list`, `stats`, `diagnostics`, `info`, `compare`, `convert`,
 `provenance-generate` and `provenance-publish` (same options, echo strings and exit codes: compare exits 2 when the
 gate fails, provenance-generate exits 1 when any recipe failed); `--backend` accepts "hip" (default) and the
-reference's "arrow" / "numpy".  `provenance-scaffold` (Stan programs + data literals), pairs and draws-export
-commands are outside the statistics path and not included.  `cmdstan-summary CHAIN.csv...` is this package's own:
-the chain files of a CmdStan run, parsed on the GPU, printed like `stats --include-diagnostics`; so is
+reference's "arrow" / "numpy".  `draws` writes a model's draws as CSV or Parquet with the reference's options and
+bytes, decoded, filtered and formatted on the GPU (reference.export_draws).  `provenance-scaffold` (Stan programs + data
+literals) and the pairs commands are outside the statistics path and not included.  `cmdstan-summary CHAIN.csv...` is
+this package's own: the chain files of a CmdStan run, parsed on the GPU, printed like `stats --include-diagnostics`; so is
 `json-summary ARCHIVE.json.zip...` for chain-list JSON archives and `csv-summary FILE.csv...` for table CSVs.
 """
 from __future__ import annotations
 
 import json
+import sys
 from pathlib import Path
 
 import click
@@ -79,6 +81,20 @@ def stats_cmd(model, params, format_, backend, quantile_mode, include_diagnostic
         for param, metrics in reference.diagnostics_for_model(model, params=param_list).items():
             stats.setdefault(param, {}).update(metrics)
     _echo_stats(stats, format_)
+
+
+@main.command("draws")
+@click.argument("model")
+@click.option("--params", default=None, help="Comma-separated parameter list")
+@click.option("--chains", default=None, help="Comma-separated chain indices")
+@click.option("--format", "format_", type=click.Choice(["csv", "parquet"], case_sensitive=False), default="csv")
+@click.option("--output", type=click.Path(path_type=Path), default=None)
+def draws_cmd(model: str, params: str | None, chains: str | None, format_: str, output: Path | None) -> None:
+    """A model's draws as CSV (default) or Parquet, to --output or stdout (reference cli.py:100-127)."""
+    param_list = params.split(",") if params else None
+    chain_list = [int(c) for c in chains.split(",")] if chains else None
+    reference.export_draws(model, sys.stdout.buffer if output is None else output, params=param_list, chains=chain_list,
+                           format_=format_.lower())
 
 
 @main.command("cmdstan-summary")

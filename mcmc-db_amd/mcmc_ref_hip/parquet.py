@@ -256,16 +256,29 @@ def read_draws(ctx: "_ffi.Context", source, params: Iterable[str] | None = None)
     return read_draws_many(ctx, [source], [params])[0]
 
 
+def decode_columns(ctx: "_ffi.Context", f: ParquetFile, names: Sequence[str]):
+    """(device buffer [len(names)][num_rows] of 8-byte values in FILE row order, kinds): INT32 / INT64 columns as
+    int64 (MCR_PQ_I64), the other numeric ones as float64.  Free the buffer."""
+    M = f.num_rows
+    cols = [f.index(n) for n in names]               # KeyError for an unknown name before any device allocation
+    kinds = [MCR_PQ_I64 if f.column_types[c] in (1, 2) else MCR_PQ_F64 for c in cols]
+    buf = DeviceBuffer(ctx, max(len(names) * M * 8, 8))
+    try:
+        decode(ctx, [(f, c, k, buf.ptr.value + j * M * 8) for j, (c, k) in enumerate(zip(cols, kinds))])
+    except BaseException:
+        buf.free()
+        raise
+    return buf, kinds
+
+
 def read_columns(ctx: "_ffi.Context", source, columns: Iterable[str] | None = None) -> dict[str, np.ndarray]:
     """Host arrays of numeric columns decoded on the device (ints as int64, floats as float64)."""
     f = source if isinstance(source, ParquetFile) else ParquetFile(source, ctx)
     try:
         names = list(columns) if columns is not None else [n for n, t in zip(f.column_names, f.column_types) if t in NUMERIC]
         M = f.num_rows
-        buf = DeviceBuffer(ctx, max(len(names) * M * 8, 8))
+        buf, kinds = decode_columns(ctx, f, names)
         try:
-            kinds = [MCR_PQ_I64 if f.column_types[f.index(n)] in (1, 2) else MCR_PQ_F64 for n in names]
-            decode(ctx, [(f, f.index(n), k, buf.ptr.value + j * M * 8) for j, (n, k) in enumerate(zip(names, kinds))])
             raw = buf.download(np.int64, len(names) * M).reshape(len(names), M)
         finally:
             buf.free()
@@ -282,6 +295,22 @@ def write_draws_dev(ctx: "_ffi.Context", path, columns, rows: int, row_group_row
     Returns the file's size."""
     with ctx.write_parquet(columns, rows, row_group_rows) as image:
         Path(path).write_bytes(image.view)
+        return len(image)
+
+
+def _write_view(dest, view) -> None:
+    if hasattr(dest, "write"):
+        dest.write(view)
+    else:
+        Path(dest).write_bytes(view)
+
+
+def write_csv_dev(ctx: "_ffi.Context", dest, columns, rows: int, row_index=None, header: str = "quoted") -> int:
+    """Writes device columns (_ffi.pq_column / _ffi.pq_sequence) of `rows` rows as CSV text formatted on the GPU
+    (Context.write_csv): the bytes `pyarrow.csv.write_csv` gives the same table (src/mcmc_ref/cli.py:117-120).  `dest` is
+    a path or a binary file object; row_index and header as for Context.write_csv.  Returns the text's size."""
+    with ctx.write_csv(columns, rows, row_index, header) as image:
+        _write_view(dest, image.view)
         return len(image)
 
 

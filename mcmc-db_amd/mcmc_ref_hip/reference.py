@@ -83,6 +83,88 @@ def draws(model: str, params: Sequence[str] | None = None, chains: Sequence[int]
     return coerce_return(Draws(data=reader, params=list(params), chains=list(chains) if chains else None), return_)
 
 
+def _host_writer() -> bool:
+    return os.environ.get("MCMC_REF_HIP_WRITER", "native").lower() == "arrow"
+
+
+def _export_arrow(model, dest, params, chains, format_, store) -> None:
+    """The reference's route (src/mcmc_ref/cli.py:113-127): pyarrow reads, filters and writes."""
+    import pyarrow.csv as pacsv
+    import pyarrow.parquet as pq
+    data = draws(model, params=params, chains=chains, return_="arrow", store=store)
+    table = data.read_all() if hasattr(data, "read_all") else data      # (write_csv of current pyarrow takes no reader)
+    if format_ == "parquet":
+        pq.write_table(table, dest)
+    elif hasattr(dest, "write"):
+        pacsv.write_csv(table, dest)
+    else:
+        with open(dest, "wb") as fh:
+            pacsv.write_csv(table, fh)
+
+
+def export_draws(model: str, dest, params: Sequence[str] | None = None, chains: Sequence[int] | None = None,
+                 format_: str = "csv", store: DataStore | None = None, context=None, writer: str = "auto") -> None:
+    """A model's draws as CSV or Parquet into `dest` (a path or a binary file object): what the reference's `draws`
+    command writes (src/mcmc_ref/cli.py:100-127), byte for byte for CSV.
+
+    The file is decoded on the device, id columns included, in file row order; the columns are `chain`, `draw` and
+    `params` in that order (None: the file's columns without the ids, as the reference's scanner selects them); `chains`
+    keeps the rows whose chain id is listed (`ds.field("chain").isin(chains)`: a given but empty list keeps none), selected
+    on the device; the text is formatted on the device (parquet.write_csv_dev), the Parquet file encoded there.
+
+    writer="host" or MCMC_REF_HIP_WRITER=arrow takes the reference's route (`draws(..., return_="arrow")`, then
+    pyarrow.csv.write_csv / pq.write_table).  So do, whatever the writer: files the device reader rejects by name;
+    files with a selected column that is neither INT32, INT64 nor DOUBLE -- a FLOAT column among them, which pyarrow
+    prints as shortest float32; and format_="parquet" with a chain selection (the Parquet writer takes no row list)."""
+    if format_ not in ("csv", "parquet"):
+        raise ValueError(f"format_ must be 'csv' or 'parquet', got {format_!r}")
+    if writer not in ("auto", "device", "host"):
+        raise ValueError(f"writer must be 'auto', 'device' or 'host', got {writer!r}")
+    store = store or DataStore()
+    if writer == "host" or (writer == "auto" and _host_writer()) or (format_ == "parquet" and chains is not None):
+        return _export_arrow(model, dest, params, chains, format_, store)
+    from . import parquet
+    ctx = context or _ffi.default_context()
+    try:
+        f = parquet.ParquetFile(store.resolve_draws_path(model), ctx)
+    except _ffi.McrError:                             # a file outside the device reader's subset: it names the feature
+        return _export_arrow(model, dest, params, chains, format_, store)
+    with f:
+        names = ["chain", "draw", *(params if params is not None else
+                                    [n for n in f.column_names if n not in ("chain", "draw")])]
+        try:
+            types = [f.column_types[f.index(n)] for n in names]
+        except KeyError:                              # pyarrow's exception for an unknown column
+            return _export_arrow(model, dest, params, chains, format_, store)
+        if any(t not in (_ffi.MCR_PQ_INT32, _ffi.MCR_PQ_INT64, _ffi.MCR_PQ_DOUBLE) for t in types):
+            return _export_arrow(model, dest, params, chains, format_, store)
+        M = f.num_rows
+        try:
+            buf, kinds = parquet.decode_columns(ctx, f, names)
+        except _ffi.McrError as exc:
+            if exc.code != _ffi.MCR_EINVAL:
+                raise
+            return _export_arrow(model, dest, params, chains, format_, store)
+    sel = None
+    try:
+        cols = [_ffi.pq_column(n, t, buf.ptr.value + j * M * 8, 1, _ffi.MCR_PQW_I64 if k == _ffi.MCR_PQ_I64 else _ffi.MCR_PQW_F64)
+                for j, (n, t, k) in enumerate(zip(names, types, kinds))]
+        if format_ == "parquet":
+            if M == 0:                                # (the Parquet writer wants a row)
+                return _export_arrow(model, dest, params, chains, format_, store)
+            with ctx.write_parquet(cols, M) as image:
+                parquet._write_view(dest, image.view)
+            return None
+        if chains is not None:
+            sel = ctx.select_rows(buf.ptr.value, M, [int(c) for c in chains])
+        parquet.write_csv_dev(ctx, dest, cols, M, row_index=sel)
+    finally:
+        if sel is not None:
+            sel[0].free()
+        buf.free()
+    return None
+
+
 def diagnostics_for_model(model: str, params: Sequence[str] | None = None,
                           store: DataStore | None = None) -> dict[str, dict[str, float]]:
     """meta.json's cached diagnostics when present (reference.py:82-90), else computed on the GPU for
