@@ -265,6 +265,11 @@ __device__ __forceinline__ i64 merge_path_wave(FA a, i64 na, FB b, i64 nb, i64 d
     return lo;
 }
 
+// s_waitcnt vmcnt(0) alone (gfx9 encoding: expcnt and lgkmcnt left at their maxima).  For the end of a gather whose
+// dead slots drop what they loaded: a load nobody consumed stays "in flight" for the compiler, which then waits for
+// ALL memory traffic -- later stores included -- at the first reuse of its register.
+__device__ __forceinline__ void wait_loads() { __builtin_amdgcn_s_waitcnt(0x0F70); }
+
 // LDS index swizzle: the low four bits of an element index are XORed with the next four, so that "thread t owns
 // elements [16t, 16t+16)" accesses (element i of every thread at once) spread over all banks, and a run of 16
 // consecutive elements still occupies its own 16 slots.  One instruction cheaper per access than the pad slot per

@@ -753,6 +753,11 @@ __device__ __forceinline__ i64 wave_order_stats(const KT* __restrict__ k, i64 M,
 // single merge: the values below the median, walked downwards (med - x, non-decreasing because
 // rounding is monotone), against the values at or above it (x - med).  This replaces the second
 // full sort of src/mcmc_ref/diagnostics.py:93-98 + :110.  Each workgroup owns OB = NT*VT outputs.
+// FOLD, fused ranks: whether the block's first / last tie run goes on outside it is decided from the element just
+// before and just behind the block in each run.  Those four neighbours are loaded WITH the gather, in four of its dead
+// slots (clamped index, no test in front of the load) and parked in the scratch; after the merge every thread compares
+// them with the block's edge keys in the LDS.  (They were four scalar loads behind the merge, each inside its own test
+// and waited for alone by one thread, between two barriers that are gone with them.)
 // ------------------------------------------------------------------------------------------------
 // KT = double: sorted keys in `kin`, positions in `iin`.  KT = u64 (FOLD only): sorted f32 records in `kin`
 // (mcr_sort32.hpp), `iin` unused -- the fold step widens the keys on the fly, its own keys |x - med| are f64.
@@ -830,15 +835,38 @@ __global__ __launch_bounds__(NT) void k_merge(const KT* __restrict__ kin, const 
     const int ca = (int)(ai1 - ai0), cb = (int)((d1 - ai1) - bi0);
     const int total = ca + cb;
 
+    // The fold's edge neighbours: the element just before and just behind the block in each run, which decide after the
+    // merge whether the first / last tie run goes on outside the block.  Their places follow from s and the two split
+    // points, so they ride with the gather: the slots OB .. OB + 3 are dead in every workgroup (total <= OB), and the
+    // four lanes that own them load a neighbour there instead of element 0 -- index clamped into [0, M), no test in
+    // front of the load -- and park it, folded like GA / GB fold it, in sh[kEdge ..].  A neighbour that does not exist
+    // (the block starts or ends a run) is parked as NaN, which equals no key.
+    // sh: [0, 2) split point and median, then the two diagonals' split points; [2, 10) the edge bounds; [12, 20) the
+    // tie-run scratch; [kEdge, kEdge + 4) the neighbours -- and scatter_codes_by_line's wave totals in [0, 4) at the end.
+    constexpr int kEdge = 24;
     {   // gather the two runs: slot e = j * NT + tid; all VT (key, position) loads of a lane are issued before the first
         // LDS store waits for one (slots at or beyond `total` read element 0 and are not stored)
         double gv[VT]; u32 gi[VT];
+        const int edge = tid - (OB - (VT - 1) * NT);                  // 0 .. 3 in the lanes of the slots OB .. OB + 3
+        const bool is_edge = FOLD && edge >= 0 && edge < 4;
+        bool edge_there = false;
 #pragma unroll
         for (int j = 0; j < VT; ++j) {
             const int e = j * NT + tid;
-            const bool inA = e < ca;
+            bool inA = e < ca;
             i64 g = inA ? (FOLD ? abase - (ai0 + e) : abase + ai0 + e) : bbase + bi0 + (e - ca);
             g = (e < total) ? g : 0;
+            if (FOLD && j == VT - 1) {
+                // A before: GA(ai0 - 1), A behind: GA(ai1), B before: GB(bi0 - 1), B behind: GB(bi1)
+                const i64 bi1 = d1 - ai1;
+                const bool behind = (edge & 1) != 0, inB = (edge & 2) != 0;
+                const i64 i = inB ? (behind ? bi1 : bi0 - 1) : (behind ? ai1 : ai0 - 1);
+                i64 ge = inB ? bbase + i : abase - i;
+                ge = (ge < 0) ? 0 : ((ge < M) ? ge : M - 1);
+                edge_there = is_edge && i >= 0 && i < (inB ? nb : na);
+                g = is_edge ? ge : g;
+                inA = is_edge ? !inB : inA;
+            }
             const double x = KEY(g);
             gv[j] = FOLD ? (inA ? med - x : x - med) : x;
             gi[j] = POS(g);
@@ -848,6 +876,7 @@ __global__ __launch_bounds__(NT) void k_merge(const KT* __restrict__ kin, const 
             const int e = j * NT + tid;
             if (e < total) { skey[pos16(e)] = gv[j]; sidx[posi(e)] = (IdxT)gi[j]; }
         }
+        if (is_edge) reinterpret_cast<double*>(sh)[kEdge + edge] = edge_there ? gv[VT - 1] : __builtin_nan("");
     }
     __syncthreads();
 
@@ -871,7 +900,7 @@ __global__ __launch_bounds__(NT) void k_merge(const KT* __restrict__ kin, const 
         }
     }
     __syncthreads();
-    if (z == nullptr) {
+    if (!FOLD || z == nullptr) {
         for (int e = tid; e < total; e += NT) {
             kout[p * M + o0 + e] = skey[pos16(e)];
             iout[p * M + o0 + e] = sidx[posi(e)];
@@ -880,24 +909,16 @@ __global__ __launch_bounds__(NT) void k_merge(const KT* __restrict__ kin, const 
     }
     // Fused ranks -> z (src/mcmc_ref/diagnostics.py:113-133): the merged order never goes to memory.
     // Tie runs touching the block edges are completed with lower/upper bounds over the two runs.
-    // Does the first / last tie run continue outside this block?  Look at the one element before
-    // and after the block in each run; only then pay for the bound searches (rare: heavy ties).
-    if (tid == 0) {
-        const i64 bi1 = d1 - ai1;
-        const double v0 = skey[pos16(0)], v1 = skey[pos16(total - 1)];
-        bool ext0 = false, ext1 = false;
-        if (ai0 > 0 && GA(ai0 - 1) == v0) ext0 = true;
-        if (bi0 > 0 && GB(bi0 - 1) == v0) ext0 = true;
-        if (ai1 < na && GA(ai1) == v1) ext1 = true;
-        if (bi1 < nb && GB(bi1) == v1) ext1 = true;
-        sh[2] = ext0; sh[3] = ext1;
-    }
-    __syncthreads();
-    const bool ext0 = sh[2] != 0, ext1 = sh[3] != 0;
-    __syncthreads();
+    // Does the first / last tie run continue outside this block?  Every thread compares the block's first and last key
+    // with the four neighbours the gather parked (no global access, no barrier); only then pay for the bound searches
+    // (rare: heavy ties).
+    const double vfirst = skey[pos16(0)], vlast = skey[pos16(total - 1)];
+    const double* edge_key = reinterpret_cast<const double*>(sh) + kEdge;
+    const bool ext0 = edge_key[0] == vfirst || edge_key[2] == vfirst;
+    const bool ext1 = edge_key[1] == vlast || edge_key[3] == vlast;
     if ((ext0 || ext1) && tid < 8) {
         const int which = tid >> 2, side = (tid >> 1) & 1, upper = tid & 1;   // value, run, bound kind
-        const double v = which ? skey[pos16(total - 1)] : skey[pos16(0)];
+        const double v = which ? vlast : vfirst;
         const i64 len = side ? nb : na;
         i64 lo = 0, hi = len;
         while (lo < hi) {
@@ -909,7 +930,6 @@ __global__ __launch_bounds__(NT) void k_merge(const KT* __restrict__ kin, const 
         sh[2 + tid] = lo;
     }
     __syncthreads();
-    const double vfirst = skey[pos16(0)], vlast = skey[pos16(total - 1)];
     const i64 gfirst = sh[2 + 0] + sh[2 + 2];   // lower bounds (both runs) of the first value
     const i64 glast = sh[2 + 5] + sh[2 + 7];    // upper bounds (both runs) of the last value
     int rs[VT], re[VT];
@@ -1125,6 +1145,43 @@ __global__ __launch_bounds__(256) void k_sample_runs(const KT* __restrict__ keys
     }
 }
 
+// The 512-byte scratch of the bucket merges, in ints: padded piece starts [k + 1], piece lengths [k], piece source
+// offsets [k] (k <= 16), the two "tie run goes on" flags, the four edge bounds (i64), and the 2k neighbour keys (8 bytes
+// each) -- whose place the tie-run scratch of block_tie_runs takes once the flags are made of them.
+constexpr int kBkLen = kMaxBucketTiles + 1, kBkSrc = kBkLen + kMaxBucketTiles, kBkExt = kBkSrc + kMaxBucketTiles,
+              kBkEdge = (kBkExt + 2 + 1) / 2 * 2, kBkNext = kBkEdge + 8;
+static_assert((kBkNext + 4 * kMaxBucketTiles) * sizeof(int) <= 512, "the bucket merges' scratch is 64 key slots");
+
+// The piece table of a bucket by the first wave (all 64 lanes): lane t < k reads the two cuts of tile t -- the 2k loads
+// are one round trip -- and a DPP scan over the padded lengths gives the pieces' starts in the LDS.
+__device__ __forceinline__ void bucket_piece_table(const u32* __restrict__ c0, const u32* __restrict__ c1, int k,
+                                                   int* sst, int* spl, int* sps)
+{
+    const int lane = threadIdx.x & 63;
+    const int t = (lane < k) ? lane : k - 1;
+    const u32 from = c0[t], to = c1[t];
+    const int len = (lane < k) ? (int)(to - from) : 0;
+    u32 acc;
+    const u32 start = wave_excl_scan_u32((u32)((len + 15) & ~15), acc);
+    if (lane < k) { sst[lane] = (int)start; spl[lane] = len; sps[lane] = (int)from; }
+    if (lane == 0) sst[k] = (int)acc;
+}
+
+// Where lane `lane` of the gather's last wave finds its neighbour of the bucket: lanes [0, k) the element just before the
+// piece of tile `lane`, lanes [k, 2k) the one just behind the piece of tile `lane - k`.  Returns its index in the
+// parameter's keys, clamped into [0, M) -- every lane may load it -- and `there`: this lane has a neighbour and it exists.
+__device__ __forceinline__ i64 bucket_neighbour(int lane, int k, i64 R, i64 M, const int* spl, const int* sps, bool& there)
+{
+    const bool behind = lane >= k;
+    const int t0 = behind ? lane - k : lane, t = (t0 < 0) ? 0 : ((t0 < k) ? t0 : k - 1);
+    const i64 tbase = (i64)t * R;
+    const i64 cnt = (M - tbase < R) ? M - tbase : R;
+    const i64 i = behind ? (i64)sps[t] + spl[t] : (i64)sps[t] - 1;
+    there = lane >= 0 && lane < 2 * k && i >= 0 && i < cnt;
+    const i64 g = tbase + i;
+    return (g < 0) ? 0 : ((g < M) ? g : M - 1);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Bucket merge: one workgroup per (bucket, parameter) gathers its <= k sorted pieces (one per tile)
 // into LDS, each padded with +inf to a multiple of 16, merges them with ceil(log2 k) merge-path
@@ -1132,6 +1189,10 @@ __global__ __launch_bounds__(256) void k_sample_runs(const KT* __restrict__ keys
 // order statistics) and -- fused -- turns positions into tie-averaged ranks, z = Phi^-1((r-1/2)/M)
 // and scatters z to time order (src/mcmc_ref/diagnostics.py:101-133).  Tie runs that touch a bucket
 // edge are completed with lower/upper bounds over the k sorted tiles, which are complete in memory.
+// No load of the kernel waits alone: the piece table is built by the lanes t < k of the first wave (their 2k cut
+// loads are one round trip, a DPP scan gives the padded starts -- not one thread walking k tiles), and the 2k tile
+// neighbours that tell whether an edge tie run goes on in the next bucket are loaded with the gather, in its dead
+// last slots, and parked in the scratch until the rounds are done (they were two guarded loads per lane behind them).
 // Replaces log2(k) global merge passes + k_rank_z of the first version.
 // ------------------------------------------------------------------------------------------------
 template <int NT, int VT, typename IdxT>
@@ -1148,10 +1209,13 @@ __global__ __launch_bounds__(NT) void k_bucket_merge(const double* __restrict__ 
     IdxT* sidx = reinterpret_cast<IdxT*>(skey + T);
     // k_splitters bounds every bucket by T - 64 slots; the 64 key slots above hold the scratch, so the workgroup's LDS
     // is exactly T * (8 + sizeof(IdxT)) bytes: FOUR buckets per CU with 16-bit positions.
-    int* sst = reinterpret_cast<int*>(skey + (T - 64));   // padded piece starts [k+1], then scratch
-    int* spl = sst + 40;                            // piece lengths [k]
-    int* sps = spl + 40;                            // piece source offsets in tile [k]
-    i64* sedge = reinterpret_cast<i64*>(sps + 40);  // [4] global run bounds of the edge values
+    int* sst = reinterpret_cast<int*>(skey + (T - 64));   // padded piece starts [k+1]
+    int* spl = sst + kBkLen;                        // piece lengths [k]
+    int* sps = sst + kBkSrc;                        // piece source offsets in tile [k]
+    int* sext = sst + kBkExt;                       // [2] does the first / last tie run go on outside the bucket?
+    i64* sedge = reinterpret_cast<i64*>(sst + kBkEdge);     // [4] global run bounds of the edge values
+    double* sne = reinterpret_cast<double*>(sst + kBkNext); // [2k] the tiles' keys just before / behind their pieces
+    static_assert(2 * (NT / kWave) <= 2 * (int)sizeof(double) / (int)sizeof(int) * kMaxBucketTiles, "the tie-run scratch takes the neighbours' place");
 
     const int tid = threadIdx.x;
     i64 p;
@@ -1161,20 +1225,24 @@ __global__ __launch_bounds__(NT) void k_bucket_merge(const double* __restrict__ 
     const IdxT* ip = iin + p * M;
     const u32* c0 = cut + (p * (B + 1) + b) * k;
     const u32* c1 = c0 + k;
-    if (tid == 0) {
-        int acc = 0;
-        for (int t = 0; t < k; ++t) {
-            const int len = (int)(c1[t] - c0[t]);
-            sst[t] = acc; spl[t] = len; sps[t] = (int)c0[t];
-            acc += (len + 15) & ~15;
-        }
-        sst[k] = acc;
-    }
+    if (k < 1 || k > kMaxBucketTiles) return;       // (the scratch holds sixteen pieces)
+    if (tid < kWave) bucket_piece_table(c0, c1, k, sst, spl, sps);
     __syncthreads();
     const int padded = sst[k];          // <= 4096 by construction of D
     const int total = (int)(boff[p * (B + 1) + b + 1] - boff[p * (B + 1) + b]);
     const i64 obase = boff[p * (B + 1) + b];
     if (padded > T - 64 || total < 0 || total > padded || obase + total > M) return;   // never with a valid partition
+    // The tiles' keys just before and just behind this bucket's pieces decide, after the rounds, whether the first /
+    // last tie run goes on in a neighbouring bucket.  Their places are known now, so they ride with the gather: its
+    // last 64 slots are dead in every workgroup (padded <= T - 64), and the first 2k lanes that own them load a neighbour
+    // there instead of element 0 (index clamped, no test in front of the load) and park it next to the piece table; a
+    // neighbour that does not exist is parked as NaN, which equals no key.
+    const int ne_lane = tid - (T - 64 - (VT - 1) * NT);     // >= 0 in the wave of the slots T - 64 .. T - 1
+    bool ne_there = false;
+    i64 ne_g = 0;
+    if (ne_lane >= 0) ne_g = bucket_neighbour(ne_lane, k, R, M, spl, sps, ne_there);
+    const bool is_ne = ne_lane >= 0 && ne_lane < 2 * k;
+    double ne = 0.0;
     // gather pieces (+inf pads).  Slot e = j * NT + tid: a wave's j-th load covers 64 consecutive slots = four 16-slot
     // chunks, one per DPP row of 16 lanes, and a chunk never straddles pieces (they are padded to 16).  Lane j of row q
     // looks up the piece of the row's j-th chunk ONCE; the element loop takes {source offset, live length} from that lane
@@ -1202,9 +1270,11 @@ __global__ __launch_bounds__(NT) void k_bucket_merge(const double* __restrict__ 
             const u32 g0 = (u32)row_lane((int)my_g, j);      // lane j of my row of 16 looked the chunk up
             const int n = row_lane(my_n, j);
             const bool live = within < n;
-            const i64 g = live ? (i64)(g0 + (u32)within) : 0;     // dead slots read element 0 (always there) and drop it
+            i64 g = live ? (i64)(g0 + (u32)within) : 0;           // dead slots read element 0 (always there) and drop it
+            if (j == VT - 1) g = is_ne ? ne_g : g;
             const double v = kp[g]; const IdxT id = ip[g];
             gv[j] = live ? v : INFINITY; gi[j] = live ? id : (IdxT)~(IdxT)0;
+            if (j == VT - 1) ne = v;
         }
 #pragma unroll
         for (int j = 0; j < VT; ++j) {
@@ -1212,6 +1282,8 @@ __global__ __launch_bounds__(NT) void k_bucket_merge(const double* __restrict__ 
             if (e < padded) { skey[pos16(e)] = gv[j]; sidx[posi(e)] = gi[j]; }
         }
     }
+    if (is_ne) sne[ne_lane] = ne_there ? ne : __builtin_nan("");
+    wait_loads();
     __syncthreads();
     // merge rounds over adjacent runs (run boundaries = sst[] at stride 2^r)
     const int chunk0 = tid * VT;
@@ -1252,23 +1324,18 @@ __global__ __launch_bounds__(NT) void k_bucket_merge(const double* __restrict__ 
         iout[p * M + obase + e] = sidx[posi(e)];
     }
     if (z == nullptr || total == 0) return;
-    // Do the first / last tie runs continue in a neighbouring bucket?  Look at the element just
-    // before / after this bucket's piece in every tile; only then pay for the bound searches.
+    // Do the first / last tie runs continue in a neighbouring bucket?  Compare with the element just before / after
+    // this bucket's piece in every tile (parked by the gather: no global access); only then pay for the bound searches.
     if (tid < 4) sedge[tid] = 0;
-    if (tid < 64) {
-        bool e0 = false, e1 = false;
-        if (tid < k) {
-            const i64 tbase = (i64)tid * R;
-            const int cnt = (int)((M - tbase < R) ? M - tbase : R);
-            const int lo = sps[tid], hi = sps[tid] + spl[tid];
-            if (lo > 0) e0 = (kp[tbase + lo - 1] == skey[pos16(0)]);
-            if (hi < cnt) e1 = (kp[tbase + hi] == skey[pos16(total - 1)]);
-        }
+    if (tid < kWave) {
+        const int t = (tid < k) ? tid : k - 1;
+        const bool e0 = tid < k && sne[t] == skey[pos16(0)];
+        const bool e1 = tid < k && sne[k + t] == skey[pos16(total - 1)];
         const bool a0 = __ballot(e0) != 0, a1 = __ballot(e1) != 0;
-        if (tid == 0) { sst[36] = a0; sst[37] = a1; }
+        if (tid == 0) { sext[0] = a0; sext[1] = a1; }
     }
     __syncthreads();
-    const bool ext0 = sst[36] != 0, ext1 = sst[37] != 0;
+    const bool ext0 = sext[0] != 0, ext1 = sext[1] != 0;
     if ((ext0 || ext1) && tid < 2 * k) {
         const int t = tid % k, which = tid / k;           // 0: first value, 1: last value
         const double v = which ? skey[pos16(total - 1)] : skey[pos16(0)];
@@ -1286,7 +1353,7 @@ __global__ __launch_bounds__(NT) void k_bucket_merge(const double* __restrict__ 
     __syncthreads();
     const double vfirst = skey[pos16(0)], vlast = skey[pos16(total - 1)];
     int rs[VT], re[VT];
-    block_tie_runs<NT, VT>([&](int g) { return skey[pos16(g)]; }, total, sst + 24, rs, re);
+    block_tie_runs<NT, VT>([&](int g) { return skey[pos16(g)]; }, total, sst + kBkNext, rs, re);
 #pragma unroll
     for (int i = 0; i < VT; ++i) {
         const int e = tid * VT + i;

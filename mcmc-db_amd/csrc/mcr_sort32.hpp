@@ -279,10 +279,13 @@ __global__ __launch_bounds__(NT) void k_bucket_merge32(const u64* __restrict__ r
     static_assert(T == 4096, "the partition bound of k_splitters assumes 4096-slot buckets");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     u64* srec = reinterpret_cast<u64*>(smem);
-    int* sst = reinterpret_cast<int*>(srec + T + 2);   // padded piece starts [k+1], then scratch
-    int* spl = sst + 40;                                // piece lengths [k]
-    int* sps = spl + 40;                                // piece source offsets in tile [k]
-    i64* sedge = reinterpret_cast<i64*>(sps + 40);      // [4] global run bounds of the edge values
+    int* sst = reinterpret_cast<int*>(srec + T + 2);   // padded piece starts [k+1]; the scratch is laid out as in k_bucket_merge
+    int* spl = sst + kBkLen;                            // piece lengths [k]
+    int* sps = sst + kBkSrc;                            // piece source offsets in tile [k]
+    int* sext = sst + kBkExt;                           // [2] does the first / last tie run go on outside the bucket?
+    i64* sedge = reinterpret_cast<i64*>(sst + kBkEdge); // [4] global run bounds of the edge values
+    u64* sne = reinterpret_cast<u64*>(sst + kBkNext);   // [2k] the runs' keys just before / behind their pieces
+    static_assert(2 * (NT / kWave) <= 4 * kMaxBucketTiles, "the tie-run scratch takes the neighbours' place");
 
     const int tid = threadIdx.x;
     i64 p;
@@ -291,20 +294,21 @@ __global__ __launch_bounds__(NT) void k_bucket_merge32(const u64* __restrict__ r
     const u64* rp = rin + p * M;
     const u32* c0 = cut + (p * (B + 1) + b) * k;
     const u32* c1 = c0 + k;
-    if (tid == 0) {
-        int acc = 0;
-        for (int t = 0; t < k; ++t) {
-            const int len = (int)(c1[t] - c0[t]);
-            sst[t] = acc; spl[t] = len; sps[t] = (int)c0[t];
-            acc += (len + 15) & ~15;
-        }
-        sst[k] = acc;
-    }
+    if (k < 1 || k > kMaxBucketTiles) return;       // (the scratch holds sixteen pieces)
+    if (tid < kWave) bucket_piece_table(c0, c1, k, sst, spl, sps);
     __syncthreads();
     const int padded = sst[k];
     const int total = (int)(boff[p * (B + 1) + b + 1] - boff[p * (B + 1) + b]);
     const i64 obase = boff[p * (B + 1) + b];
     if (padded > T - 64 || total < 0 || total > padded || obase + total > M) return;   // never with a valid partition
+    // the runs' records just before / behind this bucket's pieces ride in the gather's dead last slots (see
+    // k_bucket_merge); a neighbour that does not exist is parked as a value no 32-bit key equals
+    const int ne_lane = tid - (T - 64 - (VT - 1) * NT);
+    bool ne_there = false;
+    i64 ne_g = 0;
+    if (ne_lane >= 0) ne_g = bucket_neighbour(ne_lane, k, R, M, spl, sps, ne_there);
+    const bool is_ne = ne_lane >= 0 && ne_lane < 2 * k;
+    u64 ne = 0;
     {   // gather: one piece search per 16-slot chunk, all VT loads in flight together (see k_bucket_merge)
         const int lane = tid & 63, wv = tid >> 6;
         u32 my_g = 0; int my_n = 0;
@@ -327,8 +331,11 @@ __global__ __launch_bounds__(NT) void k_bucket_merge32(const u64* __restrict__ r
             const u32 g0 = (u32)row_lane((int)my_g, j);      // lane j of my row of 16 looked the chunk up
             const int n = row_lane(my_n, j);
             const bool live = within < n;
-            const u64 r = rp[live ? (i64)(g0 + (u32)within) : 0];
+            i64 g = live ? (i64)(g0 + (u32)within) : 0;
+            if (j == VT - 1) g = is_ne ? ne_g : g;
+            const u64 r = rp[g];
             gr[j] = live ? r : kRecPad;
+            if (j == VT - 1) ne = r;
         }
 #pragma unroll
         for (int j = 0; j < VT; ++j) {
@@ -336,6 +343,8 @@ __global__ __launch_bounds__(NT) void k_bucket_merge32(const u64* __restrict__ r
             if (e < padded) srec[pos16(e)] = gr[j];
         }
     }
+    if (is_ne) sne[ne_lane] = ne_there ? (u64)rec_key(ne) : ~0ull;
+    wait_loads();
     __syncthreads();
     const int chunk0 = tid * VT;
     int mypiece = 0;      // the piece that holds slot chunk0 (pieces are padded to 16 >= VT slots)
@@ -372,20 +381,15 @@ __global__ __launch_bounds__(NT) void k_bucket_merge32(const u64* __restrict__ r
     // every run; only then pay for the bound searches
     if (tid < 4) sedge[tid] = 0;
     const u32 kfirst = rec_key(srec[pos16(0)]), klast = rec_key(srec[pos16(total - 1)]);
-    if (tid < 64) {
-        bool e0 = false, e1 = false;
-        if (tid < k) {
-            const i64 tbase = (i64)tid * R;
-            const int cnt = (int)((M - tbase < R) ? M - tbase : R);
-            const int lo = sps[tid], hi = sps[tid] + spl[tid];
-            if (lo > 0) e0 = rec_key(rp[tbase + lo - 1]) == kfirst;
-            if (hi < cnt) e1 = rec_key(rp[tbase + hi]) == klast;
-        }
+    if (tid < kWave) {
+        const int t = (tid < k) ? tid : k - 1;
+        const bool e0 = tid < k && sne[t] == (u64)kfirst;
+        const bool e1 = tid < k && sne[k + t] == (u64)klast;
         const bool a0 = __ballot(e0) != 0, a1 = __ballot(e1) != 0;
-        if (tid == 0) { sst[36] = a0; sst[37] = a1; }
+        if (tid == 0) { sext[0] = a0; sext[1] = a1; }
     }
     __syncthreads();
-    const bool ext0 = sst[36] != 0, ext1 = sst[37] != 0;
+    const bool ext0 = sext[0] != 0, ext1 = sext[1] != 0;
     if ((ext0 || ext1) && tid < 2 * k) {
         const int t = tid % k, which = tid / k;           // 0: first value, 1: last value
         const u32 v = which ? klast : kfirst;
@@ -402,7 +406,7 @@ __global__ __launch_bounds__(NT) void k_bucket_merge32(const u64* __restrict__ r
     }
     __syncthreads();
     int rs[VT], re[VT];
-    block_tie_runs<NT, VT>([&](int g) { return rec_key(srec[pos16(g)]); }, total, sst + 24, rs, re);
+    block_tie_runs<NT, VT>([&](int g) { return rec_key(srec[pos16(g)]); }, total, sst + kBkNext, rs, re);
 #pragma unroll
     for (int i = 0; i < VT; ++i) {
         const int e = tid * VT + i;
