@@ -230,6 +230,31 @@ int mcr_compare(mcr_ctx* ctx, const double* ref, const double* actual, int64_t n
  * both samples are sorted on the device and compared in one merge-path pass.  SURVEY.md rows X1, X2. */
 int mcr_two_sample(mcr_ctx* ctx, const double* ref, int64_t Mr, const double* act, int64_t Ma, int64_t P,
                    double* ks, double* w1);
+/* Sliced two-sample check: both samples are projected onto K directions and every projected row goes through the
+ * two-sample pass above, so a difference in the DEPENDENCE between parameters that no marginal shows is seen as a KS /
+ * W1 along some direction.  ref[P][Mr], act[P][Ma] as in mcr_two_sample; dirs[K][P], center[P] (NULL = zeros), host.
+ *     z[k][m] = sum_p dirs[k][p] * (x[p][m] - center[p])
+ * in ONE fixed order: the accumulator starts at +0.0 and, for p = 0 .. P-1, d = x[p][m] - center[p] is rounded once
+ * and acc = fma(dirs[k][p], d, acc).  z[k][m] therefore has the same bits whatever K is, wherever k stands in dirs,
+ * however the directions are chunked to fit the workspace limit, for odd and even M and any 8-byte alignment of the
+ * draws.  ks[k], w1[k]: mcr_two_sample's statistics of (z_ref[k], z_act[k]), the same kernels on the same values.
+ * proj_ref[K][Mr] / proj_act[K][Ma]: the projected rows, copied out when not NULL (debug outputs).
+ * MCR_EINVAL: a NULL pointer where one is needed, K < 0, P < 1 with K > 0, Mr or Ma < 1, K > 65535, mcr_two_sample's
+ * length limits, a non-finite entry of dirs or center, summaries in flight.  MCR_ENONFINITE: non-finite draws, or a
+ * projection that overflows.  K == 0: MCR_OK, nothing written.  Synchronous.  Parity unpinned by the reference. */
+int mcr_sliced_two_sample(mcr_ctx* ctx, const double* ref, int64_t Mr, const double* act, int64_t Ma, int64_t P,
+                          const double* dirs, const double* center, int64_t K, double* ks, double* w1,
+                          double* proj_ref, double* proj_act);
+/* The same with ref_dev / act_dev in this ctx's device memory; everything else on the host as above. */
+int mcr_sliced_two_sample_dev(mcr_ctx* ctx, const double* ref_dev, int64_t Mr, const double* act_dev, int64_t Ma,
+                              int64_t P, const double* dirs, const double* center, int64_t K, double* ks, double* w1,
+                              double* proj_ref, double* proj_act);
+/* Directions per workspace chunk of such a call under the current workspace limit (K when all fit at once; 0 for an
+ * empty shape).  MCR_ENOMEM when the limit does not fit one direction. */
+int mcr_sliced_plan(mcr_ctx* ctx, int64_t Mr, int64_t Ma, int64_t P, int64_t K, int64_t* dirs_per_chunk);
+#define MCR_PROJ_TILE_M 512  /* draws per k_project workgroup (two per lane) */
+#define MCR_PROJ_TILE_K 8    /* directions per k_project workgroup (accumulators in registers) */
+#define MCR_PROJ_CHUNK_P 64  /* parameters whose weights and centers a k_project workgroup stages in LDS at a time */
 /* Population covariance matrix (ddof = 0, like compare.py:63) of P parameters over M pooled draws,
  * draws[P][M] host row-major -> cov[P][P].  The one dense contraction of the path: fp64 MFMA
  * (v_mfma_f64_16x16x4f64; LDS-staged 64 x 64 tiles, upper triangle, split over the draw axis).

@@ -59,7 +59,7 @@ enum KernelId {
     K_CSV_LINES, K_CSV_SCAN, K_CSV_PARSE, K_CSV_PATCH, K_CSV_TABLE_PARSE, K_CSV_UNSIGN_ZERO,
     K_JSON_INDEX, K_JSON_SCAN, K_JSON_PARSE,
     K_LAYOUT_SCAN, K_LAYOUT_KEYS, K_LAYOUT_HIST, K_LAYOUT_OFFSETS, K_LAYOUT_SCATTER, K_LAYOUT_BOUNDS,
-    K_PQW_ENCODE, K_PQW_COMPACT, K_CSVW_FORMAT, K_CSVW_SCAN, K_CSVW_COMPACT, K_SELECT_ROWS, K_COUNT
+    K_PQW_ENCODE, K_PQW_COMPACT, K_CSVW_FORMAT, K_CSVW_SCAN, K_CSVW_COMPACT, K_SELECT_ROWS, K_PROJECT, K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {
     "k_ingest", "k_moments", "k_moments_final", "k_tile_sort", "k_merge", "k_order_stats", "k_rank_z",
@@ -69,7 +69,7 @@ const char* const kKernelNames[K_COUNT] = {
     "k_csv_lines", "k_csv_scan", "k_csv_parse", "k_csv_patch", "k_csv_table_parse", "k_csv_unsign_zero",
     "k_json_index", "k_json_scan", "k_json_parse",
     "k_layout_scan", "k_layout_keys", "k_layout_hist", "k_layout_offsets", "k_layout_scatter", "k_layout_bounds",
-    "k_pqw_encode", "k_pqw_compact", "k_csvw_format", "k_csvw_scan", "k_csvw_compact", "k_select_rows"};
+    "k_pqw_encode", "k_pqw_compact", "k_csvw_format", "k_csvw_scan", "k_csvw_compact", "k_select_rows", "k_project"};
 
 struct EvPair { hipEvent_t a, b; int kid; };
 
@@ -1657,6 +1657,74 @@ int mcr_compare(mcr_ctx* ctx, const double* ref, const double* actual, int64_t n
     return MCR_OK;
 }
 
+// The workspace of a two-sample pass over P rows: the two samples, the parked sorted reference, the merge partials, the
+// results, the non-finite counts, then the two sorts one after the other in the same space.
+struct TwoSampleWs {
+    double *Xr, *Xa, *Sr, *part, *d_ks, *d_w, *bad;
+    PipeIn ar{}, aa{};
+    int nblk;
+};
+
+static void carve_two_sample(Carve& cv, TwoSampleWs& t, i64 P, i64 Mr, i64 Ma)
+{
+    t.nblk = (int)((Mr + Ma + kTile - 1) / kTile);
+    t.ar.M = Mr; t.aa.M = Ma;
+    t.ar.pc = t.aa.pc = P; t.ar.C = t.aa.C = 1; t.ar.do_diag = t.aa.do_diag = false;
+    t.Xr = cv.take<double>((size_t)P * Mr);
+    t.Xa = cv.take<double>((size_t)P * Ma);
+    t.Sr = cv.take<double>((size_t)P * Mr);
+    t.part = cv.take<double>((size_t)P * t.nblk * 2);
+    t.d_ks = cv.take<double>((size_t)P);
+    t.d_w = cv.take<double>((size_t)P);
+    t.bad = cv.take<double>((size_t)P * 2);
+    const size_t base = cv.off;
+    carve_pipe(cv, t.ar, false, FftPlan{}, false);
+    const size_t end_r = cv.off;
+    cv.off = base;
+    carve_pipe(cv, t.aa, false, FftPlan{}, false);
+    if (end_r > cv.off) cv.off = end_r;
+}
+
+// From the rows t.Xr [P][Mr], t.Xa [P][Ma] on the device to ks[P], w1[P] on the host: the two sorts, the non-finite
+// counts, one merge-path pass, the finisher and the non-finite check (`what` names the rows in its message).  Synchronous.
+static int two_sample_tail(mcr_ctx* ctx, TwoSampleWs& t, i64 P, double* ks, double* w1, const char* what)
+{
+    const i64 Mr = t.ar.M, Ma = t.aa.M;
+    const int nblk = t.nblk;
+    Sorted so;
+    t.ar.X = t.Xr;                // ascending order of the reference sample, parked in Sr
+    int rc = sort_stage(ctx, t.ar, so);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(t.Sr, so.keys, sizeof(double) * (size_t)P * Mr, hipMemcpyDeviceToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_bad_count, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)t.ar.part,
+                       (int)t.ar.ntiles, (i64)P, t.bad);
+    t.aa.X = t.Xa;                // ascending order of the actual sample, then one merge-path pass over both
+    rc = sort_stage(ctx, t.aa, so);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_bad_count, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)t.aa.part,
+                       (int)t.aa.ntiles, (i64)P, t.bad + P);
+    LAUNCH(ctx, K_TWO_SAMPLE, (k_two_sample<256, 16>), dim3((unsigned)nblk, (unsigned)P), dim3(256), 0,
+           (const double*)t.Sr, (i64)Mr, (const double*)so.keys, (i64)Ma, t.part, nblk);
+    LAUNCH(ctx, K_TWO_SAMPLE, k_two_sample_final, dim3((unsigned)((P + 255) / 256)), dim3(256), 0,
+           (const double*)t.part, nblk, (i64)P, (double)Mr * (double)Ma, t.d_ks, t.d_w);
+    HIP_TRY(ctx, hipMemcpyAsync(ks, t.d_ks, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(w1, t.d_w, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<double> h_bad((size_t)2 * (size_t)P);
+    HIP_TRY(ctx, hipMemcpyAsync(h_bad.data(), t.bad, sizeof(double) * h_bad.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    prof_resolve(ctx);
+    for (i64 p = 0; p < P; ++p)
+        if (h_bad[(size_t)p] != 0.0 || h_bad[(size_t)(P + p)] != 0.0 || !(ks[p] == ks[p]) || !(w1[p] == w1[p]) || std::isinf(w1[p]))
+            return fail(ctx, MCR_ENONFINITE, "%s contain non-finite values", what);
+    return MCR_OK;
+}
+
+// The length limits of a two-sample pass (positions are 32-bit; the KS numerator must stay exact in f64).
+static bool two_sample_too_long(i64 Mr, i64 Ma)
+{
+    return Mr >= (i64)0xFFFFFFFFll || Ma >= (i64)0xFFFFFFFFll || (double)Mr * (double)Ma >= 9007199254740992.0;
+}
+
 int mcr_two_sample(mcr_ctx* ctx, const double* ref, int64_t Mr, const double* act, int64_t Ma, int64_t P,
                    double* ks, double* w1)
 {
@@ -1665,59 +1733,139 @@ int mcr_two_sample(mcr_ctx* ctx, const double* ref, int64_t Mr, const double* ac
         return fail(ctx, MCR_EINVAL, "bad argument (both samples need at least one draw)");
     if (P == 0) return MCR_OK;
     if (P > kMaxGridY) return fail(ctx, MCR_EINVAL, "P > %d", kMaxGridY);
-    if (Mr >= (i64)0xFFFFFFFFll || Ma >= (i64)0xFFFFFFFFll || (double)Mr * (double)Ma >= 9007199254740992.0)
-        return fail(ctx, MCR_EINVAL, "samples too long (Mr * Ma must stay below 2^53)");
+    if (two_sample_too_long(Mr, Ma)) return fail(ctx, MCR_EINVAL, "samples too long (Mr * Ma must stay below 2^53)");
     if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "mcr_two_sample with summaries in flight");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int nblk = (int)((Mr + Ma + kTile - 1) / kTile);
-    double *Xr, *Xa, *Sr, *part, *d_ks, *d_w, *bad;
-    PipeIn ar{}, aa{};            // the sorts of the two samples: one after the other, in the same space
-    ar.M = Mr; aa.M = Ma;
-    ar.pc = aa.pc = P; ar.C = aa.C = 1; ar.do_diag = aa.do_diag = false;
-    int rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) {
-        Xr = cv.take<double>((size_t)P * Mr);
-        Xa = cv.take<double>((size_t)P * Ma);
-        Sr = cv.take<double>((size_t)P * Mr);
-        part = cv.take<double>((size_t)P * nblk * 2);
-        d_ks = cv.take<double>((size_t)P);
-        d_w = cv.take<double>((size_t)P);
-        bad = cv.take<double>((size_t)P * 2);
-        const size_t base = cv.off;
-        carve_pipe(cv, ar, false, FftPlan{}, false);
-        const size_t end_r = cv.off;
-        cv.off = base;
-        carve_pipe(cv, aa, false, FftPlan{}, false);
-        if (end_r > cv.off) cv.off = end_r;
-    });
+    TwoSampleWs t;
+    const int rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) { carve_two_sample(cv, t, P, Mr, Ma); });
     if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(t.Xr, ref, sizeof(double) * (size_t)P * Mr, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(t.Xa, act, sizeof(double) * (size_t)P * Ma, hipMemcpyHostToDevice, ctx->stream));
+    return two_sample_tail(ctx, t, P, ks, w1, "draws");
+}
+
+// One k_project launch: Z[K][M] = W[K][P] (X[P][M] - c[P]).  The 16-byte instance when every row of X and Z starts
+// 16-byte aligned; both instances give the same bits.
+static int launch_project(mcr_ctx* ctx, const double* X, const double* W, const double* c, i64 M, i64 P, i64 K, double* Z)
+{
+    const i64 mtiles = ((M + kProjTileM - 1) / kProjTileM + 7) / 8 * 8, ktiles = (K + kProjTileK - 1) / kProjTileK;
+    if (mtiles * ktiles > 0x7FFFFFFFll) return fail(ctx, MCR_EINVAL, "too many draws x directions for one projection launch");
+    const dim3 grid((unsigned)(mtiles * ktiles));
+    if ((M & 1) == 0 && ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Z)) & 15) == 0)
+        LAUNCH(ctx, K_PROJECT, (k_project<true>), grid, dim3(kProjNT), 0, X, W, c, M, P, K, Z);
+    else
+        LAUNCH(ctx, K_PROJECT, (k_project<false>), grid, dim3(kProjNT), 0, X, W, c, M, P, K, Z);
+    return MCR_OK;
+}
+
+// The workspace of kc directions of a sliced call: the two-sample workspace over kc rows (its Xr / Xa are the
+// projections), the chunk's directions and the center.
+struct SlicedWs { TwoSampleWs t; double *W, *c; };
+
+static void carve_sliced(Carve& cv, SlicedWs& s, i64 kc, i64 Mr, i64 Ma, i64 P)
+{
+    carve_two_sample(cv, s.t, kc, Mr, Ma);
+    s.W = cv.take<double>((size_t)kc * P);
+    s.c = cv.take<double>((size_t)P);
+}
+
+// Directions per workspace chunk: the most whose workspace fits the limit (all K when they fit at once).
+static int plan_sliced(mcr_ctx* ctx, i64 Mr, i64 Ma, i64 P, i64 K, i64& kc)
+{
+    auto measure = [&](i64 k) { Carve m{nullptr}; SlicedWs s; carve_sliced(m, s, k, Mr, Ma, P); return m.off; };
+    const i64 Mmax = Mr > Ma ? Mr : Ma;                // k_project's one-dimensional grid: draw tiles x direction tiles < 2^31
+    const i64 grid_cap = 0x7FFFFFFFll / (((Mmax + kProjTileM - 1) / kProjTileM + 7) / 8 * 8) * kProjTileK;
+    if (K > grid_cap) K = grid_cap;
+    kc = K;
+    if (measure(K) <= ctx->ws_limit) return MCR_OK;
+    if (measure(1) > ctx->ws_limit)
+        return fail(ctx, MCR_ENOMEM, "workspace limit too small: one direction needs %zu bytes, the limit is %zu", measure(1),
+                    ctx->ws_limit);
+    i64 lo = 1, hi = K;           // measure(lo) fits, measure(hi) does not
+    while (hi - lo > 1) { const i64 mid = lo + (hi - lo) / 2; if (measure(mid) <= ctx->ws_limit) lo = mid; else hi = mid; }
+    kc = lo;
+    return MCR_OK;
+}
+
+static int sliced_check(mcr_ctx* ctx, const void* ref, i64 Mr, const void* act, i64 Ma, i64 P, const double* dirs,
+                 const double* center, i64 K, const double* ks, const double* w1)
+{
+    if (K < 0 || Mr < 1 || Ma < 1 || (K > 0 && (P < 1 || !ref || !act || !dirs || !ks || !w1)))
+        return fail(ctx, MCR_EINVAL, "bad argument (both samples need at least one draw and one parameter)");
+    if (K == 0) return MCR_OK;
+    if (K > kMaxGridY) return fail(ctx, MCR_EINVAL, "K > %d", kMaxGridY);
+    if (two_sample_too_long(Mr, Ma)) return fail(ctx, MCR_EINVAL, "samples too long (Mr * Ma must stay below 2^53)");
+    for (i64 i = 0; i < K * P; ++i)
+        if (!std::isfinite(dirs[i])) return fail(ctx, MCR_EINVAL, "direction %lld has a non-finite weight", (long long)(i / P));
+    for (i64 p = 0; center && p < P; ++p)
+        if (!std::isfinite(center[p])) return fail(ctx, MCR_EINVAL, "center[%lld] is not finite", (long long)p);
+    if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "mcr_sliced_two_sample with summaries in flight");
+    return MCR_OK;
+}
+
+static_assert(kProjTileM == MCR_PROJ_TILE_M && kProjTileK == MCR_PROJ_TILE_K && kProjChunkP == MCR_PROJ_CHUNK_P,
+              "mcmcref_hip.h states k_project's geometry");
+
+int mcr_sliced_plan(mcr_ctx* ctx, int64_t Mr, int64_t Ma, int64_t P, int64_t K, int64_t* dirs_per_chunk)
+{
+    if (!ctx || !dirs_per_chunk) return fail(ctx, MCR_EINVAL, "mcr_sliced_plan: NULL argument");
+    if (Mr < 1 || Ma < 1 || P < 1 || K < 1 || K > kMaxGridY) { *dirs_per_chunk = 0; return MCR_OK; }
+    i64 kc = 0;
+    const int rc = plan_sliced(ctx, Mr, Ma, P, K, kc);
+    if (rc) return rc;
+    *dirs_per_chunk = kc;
+    return MCR_OK;
+}
+
+int mcr_sliced_two_sample_dev(mcr_ctx* ctx, const double* ref_dev, int64_t Mr, const double* act_dev, int64_t Ma, int64_t P,
+                              const double* dirs, const double* center, int64_t K, double* ks, double* w1,
+                              double* proj_ref, double* proj_act)
+{
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    int rc = sliced_check(ctx, ref_dev, Mr, act_dev, Ma, P, dirs, center, K, ks, w1);
+    if (rc || K == 0) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    i64 kcmax = 0;
+    rc = plan_sliced(ctx, Mr, Ma, P, K, kcmax);
+    if (rc) return rc;
+    const std::vector<double> zeros(center ? 0 : (size_t)P, 0.0);
+    for (i64 k0 = 0; k0 < K; k0 += kcmax) {            // the directions are independent: chunking changes no bit
+        const i64 kc = K - k0 < kcmax ? K - k0 : kcmax;
+        SlicedWs s;
+        rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) { carve_sliced(cv, s, kc, Mr, Ma, P); });
+        if (rc) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(s.W, dirs + k0 * P, sizeof(double) * (size_t)kc * P, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(s.c, center ? center : zeros.data(), sizeof(double) * (size_t)P, hipMemcpyHostToDevice,
+                                    ctx->stream));
+        rc = launch_project(ctx, ref_dev, s.W, s.c, Mr, P, kc, s.t.Xr);
+        if (!rc) rc = launch_project(ctx, act_dev, s.W, s.c, Ma, P, kc, s.t.Xa);
+        if (rc) return rc;
+        if (proj_ref)
+            HIP_TRY(ctx, hipMemcpyAsync(proj_ref + k0 * Mr, s.t.Xr, sizeof(double) * (size_t)kc * Mr, hipMemcpyDeviceToHost, ctx->stream));
+        if (proj_act)
+            HIP_TRY(ctx, hipMemcpyAsync(proj_act + k0 * Ma, s.t.Xa, sizeof(double) * (size_t)kc * Ma, hipMemcpyDeviceToHost, ctx->stream));
+        rc = two_sample_tail(ctx, s.t, kc, ks + k0, w1 + k0, "draws or their projections");
+        if (rc) return rc;
+    }
+    return MCR_OK;
+}
+
+int mcr_sliced_two_sample(mcr_ctx* ctx, const double* ref, int64_t Mr, const double* act, int64_t Ma, int64_t P,
+                          const double* dirs, const double* center, int64_t K, double* ks, double* w1,
+                          double* proj_ref, double* proj_act)
+{
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    int rc = sliced_check(ctx, ref, Mr, act, Ma, P, dirs, center, K, ks, w1);
+    if (rc || K == 0) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t rbytes = align_up((size_t)P * Mr * 8, 256);
+    rc = ctx->stage.reserve(ctx, rbytes + (size_t)P * Ma * 8);
+    if (rc) return rc;
+    double* Xr = ctx->stage.as<double>();
+    double* Xa = (double*)(ctx->stage.as<char>() + rbytes);
     HIP_TRY(ctx, hipMemcpyAsync(Xr, ref, sizeof(double) * (size_t)P * Mr, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(Xa, act, sizeof(double) * (size_t)P * Ma, hipMemcpyHostToDevice, ctx->stream));
-    Sorted so;
-    ar.X = Xr;                    // ascending order of the reference sample, parked in Sr
-    rc = sort_stage(ctx, ar, so);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(Sr, so.keys, sizeof(double) * (size_t)P * Mr, hipMemcpyDeviceToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_bad_count, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)ar.part,
-                       (int)ar.ntiles, (i64)P, bad);
-    aa.X = Xa;                    // ascending order of the actual sample, then one merge-path pass over both
-    rc = sort_stage(ctx, aa, so);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_bad_count, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)aa.part,
-                       (int)aa.ntiles, (i64)P, bad + P);
-    LAUNCH(ctx, K_TWO_SAMPLE, (k_two_sample<256, 16>), dim3((unsigned)nblk, (unsigned)P), dim3(256), 0,
-           (const double*)Sr, (i64)Mr, (const double*)so.keys, (i64)Ma, part, nblk);
-    LAUNCH(ctx, K_TWO_SAMPLE, k_two_sample_final, dim3((unsigned)((P + 255) / 256)), dim3(256), 0,
-           (const double*)part, nblk, (i64)P, (double)Mr * (double)Ma, d_ks, d_w);
-    HIP_TRY(ctx, hipMemcpyAsync(ks, d_ks, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(w1, d_w, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, ctx->stream));
-    std::vector<double> h_bad((size_t)2 * (size_t)P);
-    HIP_TRY(ctx, hipMemcpyAsync(h_bad.data(), bad, sizeof(double) * h_bad.size(), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    prof_resolve(ctx);
-    for (i64 p = 0; p < P; ++p)
-        if (h_bad[(size_t)p] != 0.0 || h_bad[(size_t)(P + p)] != 0.0 || !(ks[p] == ks[p]) || !(w1[p] == w1[p]) || std::isinf(w1[p]))
-            return fail(ctx, MCR_ENONFINITE, "draws contain non-finite values");
-    return MCR_OK;
+    return mcr_sliced_two_sample_dev(ctx, Xr, Mr, Xa, Ma, P, dirs, center, K, ks, w1, proj_ref, proj_act);
 }
 
 // Device-resident form (draws_dev [P][M] f64, cov_dev [P][P] f64, both in this context's device memory): what

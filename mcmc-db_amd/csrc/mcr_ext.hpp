@@ -1,7 +1,8 @@
 // mcr_ext.hpp -- extensions named in the north star but ABSENT from the reference (SURVEY.md 8(a)
 // rows X1-X3): two-sample Kolmogorov-Smirnov statistic, Wasserstein-1 distance and the parameter
 // covariance matrix.  PARITY UNPINNED by the reference; the tests pin them to scipy.stats.ks_2samp /
-// scipy.stats.wasserstein_distance / numpy.cov, whose published definitions are restated here.
+// scipy.stats.wasserstein_distance / numpy.cov, whose published definitions are restated here.  Also the projection of
+// the draws onto directions (k_project), which turns the two-sample pass into a check of the joint distribution.
 #pragma once
 #include "mcr_device.hpp"
 
@@ -103,6 +104,84 @@ __global__ void k_bad_count(const double* __restrict__ part, int ntiles, i64 P, 
     double b = 0.0;
     for (int t = 0; t < ntiles; ++t) b += part[(p * ntiles + t) * kMomRec + 3];
     bad[p] = b;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Projection of the draws onto K directions (mcr_sliced_two_sample):  Z[k][m] = sum_p W[k][p] (X[p][m] - c[p]),
+// X [P][M], W [K][P], Z [K][M], all f64 row-major.  THE ARITHMETIC IS FIXED: acc = +0.0, then for p = 0 .. P-1 in
+// order d = X[p][m] - c[p] (rounded once), acc = fma(W[k][p], d, acc).  No split over p, no reassociation, so Z[k][m]
+// has the same bits for every K, every place of k in the batch, every place of m in a tile, either template
+// instance and any chunking of the directions.  That rules MFMA out (its internal summation order is its own), and the
+// shape does not ask for it: the contraction is P long, and the kernel streams P M doubles in and K M out.
+//
+// Lanes along m, two draws each (one 16-byte load per row when EVEN): a 256-thread workgroup owns kProjTileM = 512 draws
+// and kProjTileK = 8 directions, 16 accumulators per lane in registers.  W and c are wave-uniform: a workgroup stages
+// them in LDS kProjChunkP parameters at a time, W transposed to [p][k] so that the 8 weights of a parameter are four
+// broadcast 16-byte reads.  X is re-read once per direction tile: from the XCD's L2, which the workgroup remap below is for.
+// Directions past K get weight 0 and are not stored; lanes past M read a clamped address and do not store.
+// grid (ceil(M / kProjTileM) rounded up to a multiple of 8) * ceil(K / kProjTileK), one-dimensional.
+// ------------------------------------------------------------------------------------------------
+constexpr int kProjNT = 256, kProjTileM = 2 * kProjNT, kProjTileK = 8, kProjChunkP = 64;
+
+template <bool EVEN>     // EVEN: M even, X and Z 16-byte aligned, so every row takes 16-byte loads and stores
+__global__ __launch_bounds__(kProjNT) void k_project(const double* __restrict__ X, const double* __restrict__ W,
+                                                     const double* __restrict__ c, i64 M, i64 P, i64 K,
+                                                     double* __restrict__ Z)
+{
+    __shared__ __attribute__((aligned(16))) double sW[kProjChunkP * kProjTileK];
+    __shared__ double sC[kProjChunkP];
+    const int tid = threadIdx.x;
+    // Workgroup ids go round the 8 XCDs, whose L2s are private: the remap hands every XCD a contiguous range of
+    // (draw tile, direction tile) pairs, direction tiles fastest, so the workgroups that re-read one draw tile of X
+    // follow each other on one XCD and find it in that L2.  A speed choice only; any bijection gives the same Z.
+    const unsigned swz = (blockIdx.x % 8) * (gridDim.x / 8) + blockIdx.x / 8;      // gridDim.x is a multiple of 8
+    const unsigned ktiles = (unsigned)((K + kProjTileK - 1) / kProjTileK);
+    const i64 k0 = (i64)(swz % ktiles) * kProjTileK;
+    const i64 m = (i64)(swz / ktiles) * kProjTileM + 2 * tid;
+    if ((i64)(swz / ktiles) * kProjTileM >= M) return;      // the draw tiles are padded to a multiple of 8
+    const bool v0 = m < M, v1 = m + 1 < M;
+    // clamped into the row: the loads are unconditional, the stores are not
+    // (EVEN: m and M are even, so m < M implies m + 1 < M, and a lane past the end re-reads the last aligned pair)
+    const i64 a0 = v0 ? m : (EVEN ? M - 2 : M - 1), a1 = v1 ? m + 1 : M - 1;
+    double acc0[kProjTileK], acc1[kProjTileK];
+#pragma unroll
+    for (int j = 0; j < kProjTileK; ++j) acc0[j] = acc1[j] = 0.0;
+    for (i64 p0 = 0; p0 < P; p0 += kProjChunkP) {
+        const int np = (int)((P - p0 < kProjChunkP) ? P - p0 : kProjChunkP);
+        __syncthreads();                                   // the previous chunk's readers are done
+        for (int e = tid; e < kProjChunkP * kProjTileK; e += kProjNT) {
+            const int pp = e % kProjChunkP, j = e / kProjChunkP;       // consecutive lanes: consecutive p of one direction
+            sW[pp * kProjTileK + j] = (pp < np && k0 + j < K) ? W[(k0 + j) * P + p0 + pp] : 0.0;
+        }
+        if (tid < kProjChunkP) sC[tid] = (tid < np) ? c[p0 + tid] : 0.0;
+        __syncthreads();
+        const double* row = X + p0 * M;
+#pragma unroll 4
+        for (int pp = 0; pp < np; ++pp, row += M) {
+            double x0, x1;
+            if constexpr (EVEN) {
+                const double2 x = *reinterpret_cast<const double2*>(row + a0);
+                x0 = x.x; x1 = x.y;
+            } else {
+                x0 = row[a0]; x1 = row[a1];
+            }
+            const double cc = sC[pp];
+            const double d0 = x0 - cc, d1 = x1 - cc;
+#pragma unroll
+            for (int j = 0; j < kProjTileK; j += 2) {
+                const double2 w = *reinterpret_cast<const double2*>(&sW[pp * kProjTileK + j]);
+                acc0[j] = fma(w.x, d0, acc0[j]);         acc1[j] = fma(w.x, d1, acc1[j]);
+                acc0[j + 1] = fma(w.y, d0, acc0[j + 1]); acc1[j + 1] = fma(w.y, d1, acc1[j + 1]);
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < kProjTileK; ++j) {
+        if (k0 + j >= K) break;
+        double* z = Z + (k0 + j) * M + m;
+        if constexpr (EVEN) { if (v0) *reinterpret_cast<double2*>(z) = make_double2(acc0[j], acc1[j]); }
+        else { if (v0) z[0] = acc0[j]; if (v1) z[1] = acc1[j]; }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -71,6 +71,7 @@ MCR_PQ_INT32, MCR_PQ_INT64, MCR_PQ_DOUBLE = 1, 2, 5          # physical types (p
 MCR_PQW_F64, MCR_PQW_I64, MCR_PQW_SEQ = 0, 1, 2              # sources of a written column
 MCR_PQW_PAGE_ROWS, MCR_PQW_ROW_GROUP_ROWS = 8192, 1048576
 MCR_CSVW_TILE_FIELDS, MCR_CSVW_FIELD_MAX, MCR_SELECT_BLOCK_ROWS = 2048, 26, 256
+MCR_PROJ_TILE_M, MCR_PROJ_TILE_K, MCR_PROJ_CHUNK_P = 512, 8, 64     # k_project's geometry
 CSV_HEADERS = {"quoted": 0, "plain": 1, "none": 2}           # MCR_CSVW_HEADER_*
 INT64_MAX = (1 << 63) - 1
 
@@ -133,6 +134,10 @@ SYMBOLS = {
     "mcr_moments_dev": (C.c_int, [C.c_void_p] + _TENSOR + [_dp, _dp]),
     "mcr_compare": (C.c_int, [C.c_void_p, _dp, _dp, _I64, C.c_double, _dp, C.POINTER(C.c_uint8)]),
     "mcr_two_sample": (C.c_int, [C.c_void_p, _dp, _I64, _dp, _I64, _I64, _dp, _dp]),
+    "mcr_sliced_two_sample": (C.c_int, [C.c_void_p, _dp, _I64, _dp, _I64, _I64, _dp, _dp, _I64, _dp, _dp, _dp, _dp]),
+    "mcr_sliced_two_sample_dev": (C.c_int, [C.c_void_p, C.c_void_p, _I64, C.c_void_p, _I64, _I64, _dp, _dp, _I64, _dp, _dp,
+                                            _dp, _dp]),
+    "mcr_sliced_plan": (C.c_int, [C.c_void_p, _I64, _I64, _I64, _I64, C.POINTER(C.c_int64)]),
     "mcr_covariance": (C.c_int, [C.c_void_p, _dp, _I64, _I64, _dp]),
     "mcr_covariance_dev": (C.c_int, [C.c_void_p, C.c_void_p, _I64, _I64, C.c_void_p]),
     "mcr_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
@@ -1083,6 +1088,57 @@ class Context:
         self._check(self.lib.mcr_two_sample(self.handle, _as_dp(r), r.shape[1], _as_dp(a), a.shape[1], P,
                                             _as_dp(ks), _as_dp(w1)))
         return ks[:P], w1[:P]
+
+    @staticmethod
+    def _sliced_args(directions, center, P: int):
+        w = np.ascontiguousarray(directions, dtype=np.float64)
+        if w.ndim != 2 or (w.shape[0] and w.shape[1] != P):
+            raise ValueError("directions must be 2-D [K][P] with one weight per parameter")
+        c = None if center is None else np.ascontiguousarray(center, dtype=np.float64)
+        if c is not None and c.shape != (P,):
+            raise ValueError("center must have one entry per parameter")
+        if not (np.isfinite(w).all() and (c is None or np.isfinite(c).all())):
+            raise ValueError("directions and center must be finite")
+        return w, c
+
+    def sliced_two_sample(self, ref, actual, directions, center=None, projections: bool = False):
+        """(KS statistic, Wasserstein-1) per direction of the two samples projected onto `directions` [K][P]:
+        z[k] = sum_p directions[k][p] * (x[p] - center[p]), p in order, one fma each (mcr_sliced_two_sample).  ref [P][Mr],
+        actual [P][Ma] (2-D, finite); center [P] or None for zeros.  projections=True appends the projected rows
+        zr [K][Mr], za [K][Ma]."""
+        r = np.ascontiguousarray(ref, dtype=np.float64)
+        a = np.ascontiguousarray(actual, dtype=np.float64)
+        if r.ndim != 2 or a.ndim != 2 or r.shape[0] != a.shape[0]:
+            raise ValueError("ref and actual must be 2-D with the same number of parameters")
+        if not (np.isfinite(r).all() and np.isfinite(a).all()):
+            raise ValueError("draws contain non-finite values")
+        w, c = self._sliced_args(directions, center, r.shape[0])
+        return self._sliced(self.lib.mcr_sliced_two_sample, _as_dp(r), r.shape[1], _as_dp(a), a.shape[1], r.shape[0], w, c,
+                            projections)
+
+    def sliced_two_sample_dev(self, ref_ptr, Mr: int, act_ptr, Ma: int, P: int, directions, center=None,
+                              projections: bool = False):
+        """sliced_two_sample on draws already in this context's device memory: ref_ptr -> [P][Mr] f64, act_ptr -> [P][Ma]
+        f64 (device addresses or DeviceBuffer.ptr).  Non-finite draws raise McrError (MCR_ENONFINITE)."""
+        w, c = self._sliced_args(directions, center, P)
+        as_ptr = lambda v: v if isinstance(v, C.c_void_p) else C.c_void_p(int(v))
+        return self._sliced(self.lib.mcr_sliced_two_sample_dev, as_ptr(ref_ptr), int(Mr), as_ptr(act_ptr), int(Ma), int(P), w, c,
+                            projections)
+
+    def _sliced(self, entry, ref, Mr, act, Ma, P, w, c, projections):
+        K = w.shape[0]
+        ks, w1 = np.full(max(K, 1), np.nan), np.full(max(K, 1), np.nan)
+        zr = np.empty((K, Mr)) if projections else None
+        za = np.empty((K, Ma)) if projections else None
+        self._check(entry(self.handle, ref, Mr, act, Ma, P, _as_dp(w), _as_dp(c), K, _as_dp(ks), _as_dp(w1),
+                          _as_dp(zr), _as_dp(za)))
+        return (ks[:K], w1[:K], zr, za) if projections else (ks[:K], w1[:K])
+
+    def sliced_dirs_per_chunk(self, Mr: int, Ma: int, P: int, K: int) -> int:
+        """Directions per workspace chunk of a sliced_two_sample call of this shape (mcr_sliced_plan)."""
+        v = C.c_int64(0)
+        self._check(self.lib.mcr_sliced_plan(self.handle, Mr, Ma, P, K, C.byref(v)))
+        return int(v.value)
 
     def covariance(self, draws) -> np.ndarray:
         """Population covariance (ddof=0) of draws [P][M] -> [P][P] (fp64 MFMA)."""

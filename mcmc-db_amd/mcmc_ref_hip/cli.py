@@ -7,7 +7,9 @@ reference's "arrow" / "numpy".  `draws` writes a model's draws as CSV or Parquet
 bytes, decoded, filtered and formatted on the GPU (reference.export_draws).  `provenance-scaffold` (Stan programs + data
 literals) and the pairs commands are outside the statistics path and not included.  `cmdstan-summary CHAIN.csv...` is
 this package's own: the chain files of a CmdStan run, parsed on the GPU, printed like `stats --include-diagnostics`; so is
-`json-summary ARCHIVE.json.zip...` for chain-list JSON archives and `csv-summary FILE.csv...` for table CSVs.
+`json-summary ARCHIVE.json.zip...` for chain-list JSON archives and `csv-summary FILE.csv...` for table CSVs, and
+`validate MODEL --actual FILE.csv`, the command of `validate.validate` (compare's gate plus KS / Wasserstein-1 per
+parameter and, with `--sliced K`, along K random directions of the joint distribution; exits like `compare`).
 """
 from __future__ import annotations
 
@@ -192,6 +194,44 @@ def compare_cmd(model: str, actual_path: Path, tolerance: float, format_: str) -
         details = {p: {k: vars(v) for k, v in ms.items()} for p, ms in result.details.items()}
         click.echo(json.dumps({"passed": result.passed, "failures": result.failures, "details": details},
                               indent=2, sort_keys=True))
+    else:
+        click.echo("passed" if result.passed else "failed")
+        for failure in result.failures:
+            click.echo(f"- {failure}")
+    raise SystemExit(0 if result.passed else 2)
+
+
+@main.command("validate")
+@click.argument("model")
+@click.option("--actual", "actual_path", type=click.Path(path_type=Path), required=True)
+@click.option("--tolerance", default=0.15, type=float)
+@click.option("--metrics", default="mean,std", help="Comma-separated metrics of the relative-error gate")
+@click.option("--ks-max", default=None, type=float, help="Fail a parameter whose two-sample KS statistic exceeds this")
+@click.option("--w1-scaled-max", default=None, type=float, help="Fail a parameter whose W1 / reference std exceeds this")
+@click.option("--sliced", default=0, type=click.IntRange(min=0), help="Random directions of the joint (sliced) KS / W1 check")
+@click.option("--sliced-seed", default=4711, type=int)
+@click.option("--sliced-ks-max", default=None, type=float, help="Fail when the largest sliced KS exceeds this")
+@click.option("--sliced-w1-max", default=None, type=float, help="Fail when the largest sliced W1 exceeds this")
+@click.option("--format", "format_", type=click.Choice(["table", "json"], case_sensitive=False), default="table")
+def validate_cmd(model: str, actual_path: Path, tolerance: float, metrics: str, ks_max, w1_scaled_max, sliced: int, sliced_seed: int,
+                 sliced_ks_max, sliced_w1_max, format_: str) -> None:
+    """The reference's mean / std gate plus per-parameter KS / Wasserstein-1 and, with --sliced K, the same distances
+    along K random directions of the joint distribution (validate.validate; no counterpart in the reference)."""
+    from .validate import validate
+    try:
+        result = validate(model, _read_actual_csv(actual_path), tolerance=tolerance, metrics=tuple(metrics.split(",")),
+                          ks_max=ks_max, w1_scaled_max=w1_scaled_max, sliced=sliced, sliced_seed=sliced_seed,
+                          sliced_ks_max=sliced_ks_max, sliced_w1_max=sliced_w1_max)
+    except ValueError as exc:
+        raise click.ClickException(str(exc)) from exc
+    if format_ == "json":
+        details = {p: {k: vars(v) for k, v in ms.items()} for p, ms in result.compare.details.items()}
+        click.echo(json.dumps({"passed": result.passed, "failures": result.failures,
+                               "compare": {"passed": result.compare.passed, "failures": result.compare.failures,
+                                           "details": details},
+                               "ks": result.ks, "wasserstein": result.wasserstein,
+                               "wasserstein_scaled": result.wasserstein_scaled, "sliced_ks": result.sliced_ks,
+                               "sliced_w1": result.sliced_w1, "sliced": result.sliced}, indent=2, sort_keys=True))
     else:
         click.echo("passed" if result.passed else "failed")
         for failure in result.failures:

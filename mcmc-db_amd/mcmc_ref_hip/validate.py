@@ -4,7 +4,9 @@ The reference gates a sampler's draws with `reference.compare` (relative error o
 src/mcmc_ref/reference.py:107-122).  `validate` keeps that gate unchanged and adds, per parameter,
 distribution-level distances computed on the GPU -- the two-sample Kolmogorov-Smirnov statistic and
 the Wasserstein-1 distance (scaled by the reference std) -- plus the reference draws' own
-diagnostics.  Nothing here exists in the reference: parity for these extras is pinned to scipy only
+diagnostics.  `sliced=K` adds a check of the JOINT distribution: both samples are projected onto K random
+directions of the standardised parameter space and each projected pair goes through the same KS / W1 pass, so a
+wrong dependence between parameters whose marginals are all right shows up along some direction.  Nothing here exists in the reference: parity for these extras is pinned to scipy only
 (tests/test_ext_gpu.py), and they never change `passed` unless thresholds are given explicitly.
 """
 from __future__ import annotations
@@ -28,11 +30,43 @@ class ValidateResult:
     wasserstein: dict[str, float]                # W1 per parameter
     wasserstein_scaled: dict[str, float]         # W1 / reference std
     failures: list[str] = field(default_factory=list)
+    sliced_ks: float | None = None               # largest KS over the sliced directions (sliced > 0)
+    sliced_w1: float | None = None               # largest W1 over them, in units of reference std
+    sliced: dict | None = None                   # per-direction "ks" / "w1", "worst" (index of the largest KS) and
+    #                                              "worst_direction" {param: weight in standardised space}
+
+
+def sliced_directions(k: int, std, seed: int = 4711) -> tuple[np.ndarray, np.ndarray]:
+    """k projection directions for parameters whose reference std is `std` [P]: (W [k][P], live [P] bool).
+
+    The recipe, so that a direction can be reproduced outside the package: `live` marks the parameters whose std is
+    finite and > 0, n_live of them;
+
+        G = np.random.default_rng(seed).standard_normal((k, n_live))
+        U = G / np.linalg.norm(G, axis=1, keepdims=True)          # unit rows: directions of the standardised space
+        W[:, live] = U / std[live]                                 # ... applied to (x - mean) in the draws' own units
+
+    and W is 0 for every other parameter.  W[j] @ (x - mean) is therefore U[j] @ ((x - mean) / std): for draws that
+    match the reference and are uncorrelated it has unit variance, and a W1 along it is in units of reference std.
+    """
+    std = np.asarray(std, dtype=np.float64).reshape(-1)
+    live = np.isfinite(std) & (std > 0)
+    W = np.zeros((int(k), std.size))
+    if k > 0 and live.any():
+        G = np.random.default_rng(seed).standard_normal((int(k), int(live.sum())))
+        W[:, live] = G / np.linalg.norm(G, axis=1, keepdims=True) / std[live]
+    return W, live
 
 
 def validate(model: str, actual: Mapping[str, Sequence[float]], tolerance: float = 0.15,
              metrics: Sequence[str] = ("mean", "std"), ks_max: float | None = None,
-             w1_scaled_max: float | None = None, store: DataStore | None = None, context=None) -> ValidateResult:
+             w1_scaled_max: float | None = None, store: DataStore | None = None, context=None, sliced: int = 0,
+             sliced_seed: int = 4711, sliced_ks_max: float | None = None,
+             sliced_w1_max: float | None = None) -> ValidateResult:
+    """sliced=K > 0: K directions `sliced_directions(K, reference std, sliced_seed)` around the reference means, one
+    `Context.sliced_two_sample` call; the result's `sliced_ks` / `sliced_w1` are the maxima over the directions and
+    `sliced` holds the detail.  `sliced_ks_max` / `sliced_w1_max` turn them into failures; without them `passed` is what
+    it is without `sliced`.  Needs joint draws: every parameter of `actual` must have the same length."""
     store = store or DataStore()
     ctx = context or _ffi.default_context()
     params = list(actual.keys())
@@ -43,6 +77,10 @@ def validate(model: str, actual: Mapping[str, Sequence[float]], tolerance: float
     cmp_res = compare_stats(ref_stats, compute_stats_from_draws(actual, ctx), tolerance=tolerance, metrics=metrics,
                             context=ctx)
     lens = {len(actual[p]) for p in params}
+    if sliced < 0:
+        raise ValueError("sliced must be >= 0")
+    if sliced > 0 and len(lens) > 1:
+        raise ValueError("sliced needs joint draws: the parameters of `actual` differ in length")
     ks: dict[str, float] = {}
     w1: dict[str, float] = {}
     if len(lens) == 1 and params:
@@ -61,5 +99,20 @@ def validate(model: str, actual: Mapping[str, Sequence[float]], tolerance: float
         failures += [f"{p}.ks={ks[p]:.3g} > {ks_max}" for p in params if not ks[p] <= ks_max]
     if w1_scaled_max is not None:
         failures += [f"{p}.w1_scaled={scaled[p]:.3g} > {w1_scaled_max}" for p in params if not scaled[p] <= w1_scaled_max]
+    extra = {}
+    if sliced > 0 and params:
+        W, live = sliced_directions(sliced, [ref_stats[p]["std"] for p in params], sliced_seed)
+        if live.any():
+            center = np.array([ref_stats[p]["mean"] for p in params], dtype=np.float64)
+            sk, sw = ctx.sliced_two_sample(ref, act, W, np.where(live, center, 0.0))
+            worst = int(np.argmax(sk))
+            std = np.array([ref_stats[p]["std"] for p in params], dtype=np.float64)
+            extra = {"sliced_ks": float(sk.max()), "sliced_w1": float(sw.max()),
+                     "sliced": {"ks": [float(v) for v in sk], "w1": [float(v) for v in sw], "worst": worst,
+                                "worst_direction": {p: float(W[worst, i] * std[i]) for i, p in enumerate(params) if live[i]}}}
+            if sliced_ks_max is not None and not extra["sliced_ks"] <= sliced_ks_max:
+                failures.append(f"sliced.ks={extra['sliced_ks']:.3g} > {sliced_ks_max}")
+            if sliced_w1_max is not None and not extra["sliced_w1"] <= sliced_w1_max:
+                failures.append(f"sliced.w1={extra['sliced_w1']:.3g} > {sliced_w1_max}")
     return ValidateResult(passed=not failures, compare=cmp_res, ks=ks, wasserstein=w1, wasserstein_scaled=scaled,
-                          failures=failures)
+                          failures=failures, **extra)
