@@ -255,6 +255,41 @@ int mcr_sliced_plan(mcr_ctx* ctx, int64_t Mr, int64_t Ma, int64_t P, int64_t K, 
 #define MCR_PROJ_TILE_M 512  /* draws per k_project workgroup (two per lane) */
 #define MCR_PROJ_TILE_K 8    /* directions per k_project workgroup (accumulators in registers) */
 #define MCR_PROJ_CHUNK_P 64  /* parameters whose weights and centers a k_project workgroup stages in LDS at a time */
+/* Nested R-hat: the convergence diagnostic for MANY SHORT chains (Margossian, Hoffman, Sountsov, Riou-Durand, Vehtari,
+ * Gelman, "Nested R-hat: assessing the convergence of Markov chain Monte Carlo when running many short chains";
+ * rhat_nested of the R package posterior).  ABSENT from the reference: it replaces no reference line, and split R-hat /
+ * ESS keep their limit of 256 chains.  The C chains are grouped into K superchains of L chains each (chains of a
+ * superchain share a starting point): superchain[c] is any int32 label, labels need be neither contiguous nor sorted,
+ * every label must occur equally often (superchains are summed in the order of their first chain, so the labels are
+ * names only).  For one kind of value v[c][n], in IEEE double, every variance two-pass:
+ *     m_c  = (sum_n v[c][n]) / N                 q_c = sum_n (v[c][n] - m_c)^2
+ *     mu_k = (sum_{c in k} m_c) / L              b_k = sum_{c in k} (m_c - mu_k)^2        w_k = sum_{c in k} q_c
+ *     mu   = (sum_k mu_k) / K                    B   = sum_k (mu_k - mu)^2 / (K - 1)
+ *     W    = (sum_k (b_k / (L - 1) + w_k / (L (N - 1)))) / K        (a term with L == 1 resp. N == 1 is 0)
+ *     nrhat = sqrt(1 + B / W);  W == 0: 1.0 when B == 0, else inf;  NaN when K < 2 or C * N == 0
+ * Three kinds, as for split R-hat: raw (v = the draws: the paper's definition), bulk (v = z of the pooled tie-averaged
+ * ranks) and tail (the same of |x - median|); nrhat = max(nrhat_bulk, nrhat_tail) with Python's NaN ordering.  Chains
+ * are not split.  between_* / within_* are B and W.  Every sum has one order that depends on (C, N, K) only: a
+ * parameter's results have the same bits alone or in a batch, under any workspace limit, on either entry.
+ * draws: host tensor addressed like mcr_summarize's (dtype, C, N, P, element strides; f32 is widened first).
+ * Limits: C <= 1 048 576, C * N < 2^31 - 1.  MCR_EINVAL (message names the cause): superchains of unequal size, a NULL
+ * superchain with C > 0, C over the limit, summaries in flight.  MCR_ENONFINITE: NaN / Inf draws.  The context stays
+ * usable after every error.  Synchronous. */
+typedef struct mcr_nested { /* P entries each, NULL members skipped */
+    double *nrhat, *nrhat_bulk, *nrhat_tail, *nrhat_raw;
+    double *between_bulk, *within_bulk, *between_tail, *within_tail, *between_raw, *within_raw;
+} mcr_nested;
+int mcr_nested_rhat(mcr_ctx* ctx, const void* draws, int dtype, int64_t C, int64_t N, int64_t P, int64_t stride_c,
+                    int64_t stride_n, int64_t stride_p, const int32_t* superchain, mcr_nested* out);
+/* The same on draws in this ctx's device memory; superchain and out stay on the host. */
+int mcr_nested_rhat_dev(mcr_ctx* ctx, const void* draws_dev, int dtype, int64_t C, int64_t N, int64_t P, int64_t stride_c,
+                        int64_t stride_n, int64_t stride_p, const int32_t* superchain, mcr_nested* out);
+/* Parameters per workspace chunk of such a call with K superchains under the current workspace limit (0 for an empty
+ * shape).  MCR_ENOMEM when the limit does not fit one parameter. */
+int mcr_nested_plan(mcr_ctx* ctx, int dtype, int64_t C, int64_t N, int64_t P, int64_t stride_c, int64_t stride_n,
+                    int64_t stride_p, int64_t K, int64_t* params_per_chunk);
+#define MCR_NESTED_MAX_CHAINS 1048576 /* chains of a mcr_nested_rhat call */
+#define MCR_NESTED_BLOCK 512          /* draws of a chain k_chain_moments keeps in registers for its second pass */
 /* Population covariance matrix (ddof = 0, like compare.py:63) of P parameters over M pooled draws,
  * draws[P][M] host row-major -> cov[P][P].  The one dense contraction of the path: fp64 MFMA
  * (v_mfma_f64_16x16x4f64; LDS-staged 64 x 64 tiles, upper triangle, split over the draw axis).

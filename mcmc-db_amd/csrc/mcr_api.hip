@@ -19,6 +19,7 @@
 #include <exception>
 #include <memory>
 #include <thread>
+#include <unordered_map>
 #include <string>
 #include <functional>
 #include <new>
@@ -29,6 +30,7 @@
 #include "mcr_diag.hpp"
 #include "mcr_fft.hpp"
 #include "mcr_ext.hpp"
+#include "mcr_nested.hpp"
 #include "mcr_parquet.hpp"
 #include "mcr_pqwrite.hpp"
 #include "mcr_csvwrite.hpp"
@@ -59,7 +61,8 @@ enum KernelId {
     K_CSV_LINES, K_CSV_SCAN, K_CSV_PARSE, K_CSV_PATCH, K_CSV_TABLE_PARSE, K_CSV_UNSIGN_ZERO,
     K_JSON_INDEX, K_JSON_SCAN, K_JSON_PARSE,
     K_LAYOUT_SCAN, K_LAYOUT_KEYS, K_LAYOUT_HIST, K_LAYOUT_OFFSETS, K_LAYOUT_SCATTER, K_LAYOUT_BOUNDS,
-    K_PQW_ENCODE, K_PQW_COMPACT, K_CSVW_FORMAT, K_CSVW_SCAN, K_CSVW_COMPACT, K_SELECT_ROWS, K_PROJECT, K_COUNT
+    K_PQW_ENCODE, K_PQW_COMPACT, K_CSVW_FORMAT, K_CSVW_SCAN, K_CSVW_COMPACT, K_SELECT_ROWS, K_PROJECT,
+    K_CHAIN_MOMENTS, K_NESTED_COMBINE, K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {
     "k_ingest", "k_moments", "k_moments_final", "k_tile_sort", "k_merge", "k_order_stats", "k_rank_z",
@@ -69,7 +72,8 @@ const char* const kKernelNames[K_COUNT] = {
     "k_csv_lines", "k_csv_scan", "k_csv_parse", "k_csv_patch", "k_csv_table_parse", "k_csv_unsign_zero",
     "k_json_index", "k_json_scan", "k_json_parse",
     "k_layout_scan", "k_layout_keys", "k_layout_hist", "k_layout_offsets", "k_layout_scatter", "k_layout_bounds",
-    "k_pqw_encode", "k_pqw_compact", "k_csvw_format", "k_csvw_scan", "k_csvw_compact", "k_select_rows", "k_project"};
+    "k_pqw_encode", "k_pqw_compact", "k_csvw_format", "k_csvw_scan", "k_csvw_compact", "k_select_rows", "k_project",
+    "k_chain_moments", "k_nested_combine"};
 
 struct EvPair { hipEvent_t a, b; int kid; };
 
@@ -183,6 +187,8 @@ struct mcr_ctx {
     bool f32_records = true; // MCR_F32_RECORDS=0: f32 tensors take the f64 kernels (widened by the tile sort) instead of mcr_sort32.hpp
     bool splitters_pairwise = false;   // MCR_SPLITTERS_PAIRWISE=1: rank the regular samples pair by pair whatever their number (A/B, parity tests)
     double rho_band = kRhoBand;   // MCR_RHO_BAND: half-width of the guard band of the tier-3 scan (0 = decide on the raw values)
+    DevBuf nest_dev{4};                // mcr_nested_rhat: chain permutation + result table
+    PinBuf nest_host{4};               // its results on the host
     DevBuf guard_count;                // device counter (unsigned): band lags re-derived the reference's way (mcr_rho_guard_count)
 };
 
@@ -1866,6 +1872,222 @@ int mcr_sliced_two_sample(mcr_ctx* ctx, const double* ref, int64_t Mr, const dou
     HIP_TRY(ctx, hipMemcpyAsync(Xr, ref, sizeof(double) * (size_t)P * Mr, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(Xa, act, sizeof(double) * (size_t)P * Ma, hipMemcpyHostToDevice, ctx->stream));
     return mcr_sliced_two_sample_dev(ctx, Xr, Mr, Xa, Ma, P, dirs, center, K, ks, w1, proj_ref, proj_act);
+}
+
+// ---- nested R-hat (mcr_nested.hpp) ------------------------------------------------------------------------------------
+constexpr i64 kMaxNestedChains = (i64)1 << 20;
+constexpr int kNestKinds = 3;                              // raw, bulk, tail
+constexpr int kNestField0 = R_Q0;                          // the pipeline runs without quantiles: its rows end here
+constexpr int kNestFields = kNestField0 + 3 * kNestKinds;  // + (nrhat, B, W) per kind
+
+static_assert(kMaxNestedChains == MCR_NESTED_MAX_CHAINS && kNestBlock == MCR_NESTED_BLOCK, "mcmcref_hip.h states the nested limits");
+
+struct NestedWs { double *X, *mom, *sup; };
+
+// The workspace of a chunk of a.pc parameters: the summary pipeline's layout for ONE chain of M draws (no buffer grows
+// with chains x segments), then the chain moments and the superchain records.
+static void carve_nested(Carve& cv, PipeIn& a, NestedWs& w, i64 C, i64 K, bool ingest)
+{
+    w.X = carve_pipe(cv, a, true, FftPlan{}, ingest);
+    w.mom = cv.take<double>((size_t)a.pc * kNestKinds * (size_t)C * 2);
+    w.sup = cv.take<double>((size_t)a.pc * kNestKinds * (size_t)(K > 0 ? K : 1) * 2);
+}
+
+static PipeIn nested_pipe(i64 M, i64 pc)
+{
+    PipeIn a{};
+    a.M = M; a.pc = pc; a.C = 1; a.n = 1; a.nh = 0; a.nstage = 1; a.q.nq = 0; a.do_diag = true;
+    return a;
+}
+
+// Parameters per workspace chunk of a nested call (the most whose layout fits the limit and whose grids fit a launch).
+static int plan_nested(mcr_ctx* ctx, i64 C, i64 N, i64 P, i64 K, bool ingest, i64& pcmax)
+{
+    const i64 M = C * N;
+    auto measure = [&](i64 pc) {
+        PipeIn a = nested_pipe(M, pc);
+        NestedWs w;
+        Carve m{nullptr};
+        carve_nested(m, a, w, C, K, ingest);
+        return m.off;
+    };
+    const i64 nb = (C + kNestChains - 1) / kNestChains;
+    const i64 grid_cap = ((i64)0x7FFFFFFF / nb) / 8 * 8;   // k_chain_moments: ceil(pc / 8) * 8 * nb workgroups
+    i64 lo = 1, hi = P < kMaxGridY / 2 ? P : kMaxGridY / 2;
+    if (hi > grid_cap) hi = grid_cap;
+    if (measure(hi) > ctx->ws_limit) {
+        if (measure(1) > ctx->ws_limit)
+            return fail(ctx, MCR_ENOMEM, "one parameter needs %zu bytes of workspace; limit is %zu", measure(1), ctx->ws_limit);
+        while (lo < hi) {
+            const i64 mid = lo + (hi - lo + 1) / 2;
+            if (measure(mid) <= ctx->ws_limit) lo = mid; else hi = mid - 1;
+        }
+    }
+    pcmax = hi;
+    return MCR_OK;
+}
+
+// Acceptance of a nested call, and the chains ordered by superchain (stable): K runs of L chains in perm.
+static int nested_check(mcr_ctx* ctx, const void* draws, int dtype, i64 C, i64 N, i64 P, const int32_t* superchain,
+                        const mcr_nested* out, std::vector<int32_t>& perm, i64& K, i64& L)
+{
+    if (!out) return fail(ctx, MCR_EINVAL, "out is NULL");
+    if (dtype != MCR_F64 && dtype != MCR_F32) return fail(ctx, MCR_EINVAL, "unsupported dtype %d", dtype);
+    if (C < 0 || N < 0 || P < 0) return fail(ctx, MCR_EINVAL, "negative dimension (C=%lld N=%lld P=%lld)", (long long)C, (long long)N, (long long)P);
+    if (C > kMaxNestedChains)
+        return fail(ctx, MCR_EINVAL, "nested R-hat supports at most %lld chains; got %lld", (long long)kMaxNestedChains, (long long)C);
+    if (C * N >= (i64)0x7FFFFFFFll) return fail(ctx, MCR_EINVAL, "C*N must be < 2^31");
+    if (!draws && C * N * P > 0) return fail(ctx, MCR_EINVAL, "draws is NULL");
+    if (C > 0 && !superchain) return fail(ctx, MCR_EINVAL, "superchain is NULL");
+    if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "mcr_nested_rhat with summaries in flight");
+    // superchains in the order of their first chain, chains in index order inside: the labels are names only
+    std::unordered_map<int32_t, int32_t> dense;
+    std::vector<int32_t> sid((size_t)C), count, first_label;
+    for (i64 c = 0; c < C; ++c) {
+        const auto it = dense.emplace(superchain[c], (int32_t)count.size());
+        if (it.second) { count.push_back(0); first_label.push_back(superchain[c]); }
+        sid[(size_t)c] = it.first->second;
+        ++count[(size_t)it.first->second];
+    }
+    K = (i64)count.size();
+    L = K > 0 ? count[0] : 0;
+    for (i64 k = 1; k < K; ++k)
+        if (count[(size_t)k] != L)
+            return fail(ctx, MCR_EINVAL, "superchains must have the same number of chains: superchain %d has %lld, superchain %d has %lld",
+                        (int)first_label[0], (long long)L, (int)first_label[(size_t)k], (long long)count[(size_t)k]);
+    perm.resize((size_t)C);
+    std::vector<i64> fill((size_t)K, 0);
+    for (i64 c = 0; c < C; ++c) { const i64 k = sid[(size_t)c]; perm[(size_t)(k * L + fill[(size_t)k]++)] = (int32_t)c; }
+    return MCR_OK;
+}
+
+static int nested_run(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i64 P, i64 sc, i64 sn, i64 sp,
+                      const std::vector<int32_t>& perm, i64 K, i64 L, const mcr_nested* out)
+{
+    const i64 M = C * N;
+    // f32 draws are widened by the ingest pass: the raw kind reads f64 rows, and the answer is the f64 call's on the widened tensor
+    const bool ingest = dtype == MCR_F32 || needs_ingest(C, N, P, sc, sn, sp);
+    i64 pcmax = 0;
+    int rc = plan_nested(ctx, C, N, P, K, ingest, pcmax);
+    if (rc) return rc;
+    int32_t* d_perm = nullptr;
+    double* d_res = nullptr;
+    rc = carve(ctx, ctx->nest_dev, [&](Carve& cv) {
+        d_perm = cv.take<int32_t>((size_t)C);
+        d_res = cv.take<double>((size_t)kNestFields * (size_t)P);
+    });
+    if (!rc) rc = ctx->nest_host.reserve(ctx, sizeof(double) * (size_t)kNestFields * (size_t)P);
+    if (rc) return rc;
+    double* ztab = nullptr;
+    rc = get_ztab(ctx, M, &ztab);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(d_perm, perm.data(), sizeof(int32_t) * (size_t)C, hipMemcpyHostToDevice, ctx->stream));
+    for (i64 p0 = 0; p0 < P; p0 += pcmax) {
+        const i64 pc = (P - p0 < pcmax) ? P - p0 : pcmax;
+        PipeIn a = nested_pipe(M, pc);
+        NestedWs w;
+        rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) { carve_nested(cv, a, w, C, K, ingest); });
+        if (rc) return rc;
+        a.ztab = ztab;
+        if (ingest) {
+            rc = (dtype == MCR_F64) ? launch_ingest<double>(ctx, draws_dev, w.X, C, N, pc, sc, sn, sp, p0)
+                                    : launch_ingest<float>(ctx, draws_dev, w.X, C, N, pc, sc, sn, sp, p0);
+            if (rc) return rc;
+            a.X = w.X;
+        } else {
+            a.X = reinterpret_cast<const double*>(draws_dev) + p0 * M;
+        }
+        a.d_res = d_res + (size_t)kNestFields * (size_t)p0;
+        rc = run_pipeline(ctx, a);             // one chain: sort, order statistics, bulk codes, fold, finalize (the bad count)
+        if (rc) return rc;
+        const i64 nb = (C + kNestChains - 1) / kNestChains;
+        LAUNCH(ctx, K_CHAIN_MOMENTS, k_chain_moments, dim3((unsigned)((pc + 7) / 8 * 8 * nb)), dim3(kNestNT), 0,
+               (const double*)a.X, (const u32*)a.zb, (const u32*)a.zt, (const double*)ztab, M, C, N, pc, w.mom);
+        LAUNCH(ctx, K_NESTED_COMBINE, k_nested_combine, dim3((unsigned)pc, kNestKinds), dim3(kNestCombNT), 0,
+               (const double*)w.mom, (const int*)d_perm, C, K, L, N, w.sup, a.d_res, pc, kNestField0);
+    }
+    double* h = ctx->nest_host.as<double>();
+    HIP_TRY(ctx, hipMemcpyAsync(h, d_res, sizeof(double) * (size_t)kNestFields * (size_t)P, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    prof_resolve(ctx);
+    double nbad = 0.0;
+    double* const dst[kNestKinds][3] = {{out->nrhat_raw, out->between_raw, out->within_raw},
+                                        {out->nrhat_bulk, out->between_bulk, out->within_bulk},
+                                        {out->nrhat_tail, out->between_tail, out->within_tail}};
+    for (i64 p0 = 0; p0 < P; p0 += pcmax) {
+        const i64 pc = (P - p0 < pcmax) ? P - p0 : pcmax;
+        const double* r = h + (size_t)kNestFields * (size_t)p0;
+        for (i64 p = 0; p < pc; ++p) {
+            nbad += r[(size_t)R_BAD * pc + p];
+            for (int k = 0; k < kNestKinds; ++k)
+                for (int f = 0; f < 3; ++f)
+                    if (dst[k][f]) dst[k][f][p0 + p] = r[(size_t)(kNestField0 + 3 * k + f) * pc + p];
+            if (out->nrhat) {                  // Python's max(bulk, tail)
+                const double rb = r[(size_t)(kNestField0 + 3) * pc + p], rt = r[(size_t)(kNestField0 + 6) * pc + p];
+                out->nrhat[p0 + p] = (rt > rb) ? rt : rb;
+            }
+        }
+    }
+    if (nbad > 0.0) return fail(ctx, MCR_ENONFINITE, "draws contain %.0f non-finite value(s)", nbad);
+    return MCR_OK;
+}
+
+static void nested_fill_nan(const mcr_nested* o, i64 P)
+{
+    double* arrs[] = {o->nrhat, o->nrhat_bulk, o->nrhat_tail, o->nrhat_raw, o->between_bulk, o->within_bulk,
+                      o->between_tail, o->within_tail, o->between_raw, o->within_raw};
+    for (double* a : arrs)
+        if (a) for (i64 p = 0; p < P; ++p) a[p] = NAN;
+}
+
+int mcr_nested_plan(mcr_ctx* ctx, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc, int64_t sn, int64_t sp,
+                    int64_t K, int64_t* params_per_chunk)
+{
+    if (!ctx || !params_per_chunk) return fail(ctx, MCR_EINVAL, "mcr_nested_plan: NULL argument");
+    if (C < 1 || N < 1 || P < 1 || K < 1 || C > kMaxNestedChains || C * N >= (i64)0x7FFFFFFFll) { *params_per_chunk = 0; return MCR_OK; }
+    i64 pcmax = 0;
+    const int rc = plan_nested(ctx, C, N, P, K, dtype == MCR_F32 || needs_ingest(C, N, P, sc, sn, sp), pcmax);
+    if (rc) return rc;
+    *params_per_chunk = pcmax;
+    return MCR_OK;
+}
+
+int mcr_nested_rhat_dev(mcr_ctx* ctx, const void* draws_dev, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc,
+                        int64_t sn, int64_t sp, const int32_t* superchain, mcr_nested* out)
+{
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    std::vector<int32_t> perm;
+    i64 K = 0, L = 0;
+    int rc = nested_check(ctx, draws_dev, dtype, C, N, P, superchain, out, perm, K, L);
+    if (rc || P == 0) return rc;
+    if (C * N == 0) { nested_fill_nan(out, P); return MCR_OK; }
+    if (tensor_extent(C, N, P, sc, sn, sp) < 0) return fail(ctx, MCR_EINVAL, "negative strides are not supported");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = nested_run(ctx, draws_dev, dtype, C, N, P, sc, sn, sp, perm, K, L, out);
+    if (rc) { char keep[sizeof ctx->err]; memcpy(keep, ctx->err, sizeof keep); abort_inflight(ctx); memcpy(ctx->err, keep, sizeof keep); }
+    return rc;
+}
+
+int mcr_nested_rhat(mcr_ctx* ctx, const void* draws, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc, int64_t sn,
+                    int64_t sp, const int32_t* superchain, mcr_nested* out)
+{
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    {
+        std::vector<int32_t> perm;             // (the device entry checks again: the errors come before the upload)
+        i64 K = 0, L = 0;
+        const int rc = nested_check(ctx, draws, dtype, C, N, P, superchain, out, perm, K, L);
+        if (rc) return rc;
+    }
+    const i64 ext = tensor_extent(C, N, P, sc, sn, sp);
+    if (ext < 0) return fail(ctx, MCR_EINVAL, "negative strides are not supported");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (ext > 0) {
+        const size_t es = dtype == MCR_F64 ? 8 : 4;
+        const int rc = ctx->stage.reserve(ctx, (size_t)ext * es);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->stage.p, draws, (size_t)ext * es, hipMemcpyHostToDevice, ctx->stream));
+    }
+    return mcr_nested_rhat_dev(ctx, ctx->stage.p ? ctx->stage.p : draws, dtype, C, N, P, sc, sn, sp, superchain, out);
 }
 
 // Device-resident form (draws_dev [P][M] f64, cov_dev [P][P] f64, both in this context's device memory): what

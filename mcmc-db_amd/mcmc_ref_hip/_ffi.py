@@ -56,6 +56,15 @@ class Summary(C.Structure):
                [("lag_bulk", _ip), ("lag_tail", _ip), ("q_lo", _ip)]
 
 
+NESTED_FIELDS = ("nrhat", "nrhat_bulk", "nrhat_tail", "nrhat_raw", "between_bulk", "within_bulk", "between_tail",
+                 "within_tail", "between_raw", "within_raw")
+MCR_NESTED_MAX_CHAINS, MCR_NESTED_BLOCK = 1048576, 512     # mcr_nested_rhat's chain limit, k_chain_moments' register block
+
+
+class Nested(C.Structure):
+    _fields_ = [(n, _dp) for n in NESTED_FIELDS]
+
+
 class ModelDesc(C.Structure):
     _fields_ = [("draws_dev", C.c_void_p), ("dtype", C.c_int), ("min_chains", C.c_int),
                 ("C", C.c_int64), ("N", C.c_int64), ("P", C.c_int64),
@@ -138,6 +147,9 @@ SYMBOLS = {
     "mcr_sliced_two_sample_dev": (C.c_int, [C.c_void_p, C.c_void_p, _I64, C.c_void_p, _I64, _I64, _dp, _dp, _I64, _dp, _dp,
                                             _dp, _dp]),
     "mcr_sliced_plan": (C.c_int, [C.c_void_p, _I64, _I64, _I64, _I64, C.POINTER(C.c_int64)]),
+    "mcr_nested_rhat": (C.c_int, [C.c_void_p] + _TENSOR + [C.POINTER(C.c_int32), C.POINTER(Nested)]),
+    "mcr_nested_rhat_dev": (C.c_int, [C.c_void_p] + _TENSOR + [C.POINTER(C.c_int32), C.POINTER(Nested)]),
+    "mcr_nested_plan": (C.c_int, [C.c_void_p, C.c_int] + [_I64] * 7 + [C.POINTER(C.c_int64)]),
     "mcr_covariance": (C.c_int, [C.c_void_p, _dp, _I64, _I64, _dp]),
     "mcr_covariance_dev": (C.c_int, [C.c_void_p, C.c_void_p, _I64, _I64, C.c_void_p]),
     "mcr_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
@@ -320,6 +332,27 @@ def tensor_args(draws: np.ndarray, layout: str):
     if any(s < 0 for s in strides):
         raise ValueError("negative strides are not supported")
     return (code, *dims, *strides)
+
+
+def superchain_labels(superchain_ids, n_chains: int) -> np.ndarray:
+    """The int32 label of every chain: `superchain_ids` as given (one per chain), or for an int K the K contiguous
+    blocks of n_chains / K chains.  ValueError for a length other than the number of chains, a K that does not divide
+    it, labels outside int32, or superchains of unequal size."""
+    if isinstance(superchain_ids, (int, np.integer)) and not isinstance(superchain_ids, bool):
+        K = int(superchain_ids)
+        if K < 1 or n_chains % K:
+            raise ValueError(f"{K} superchains do not divide {n_chains} chains into equal blocks")
+        return np.repeat(np.arange(K, dtype=np.int32), n_chains // K)
+    ids = np.asarray(superchain_ids)
+    if ids.ndim != 1 or ids.shape[0] != n_chains:
+        raise ValueError(f"superchain_ids must have one label per chain: got {ids.size} for {n_chains} chains")
+    if ids.size and not np.issubdtype(ids.dtype, np.integer):
+        raise ValueError("superchain_ids must be integers")
+    if ids.size and (ids.min() < -2**31 or ids.max() >= 2**31):
+        raise ValueError("superchain_ids must fit int32")
+    if ids.size and len(set(np.unique(ids, return_counts=True)[1].tolist())) != 1:
+        raise ValueError("superchains must have the same number of chains")
+    return np.ascontiguousarray(ids, dtype=np.int32)
 
 
 class PqImage:
@@ -1138,6 +1171,32 @@ class Context:
         """Directions per workspace chunk of a sliced_two_sample call of this shape (mcr_sliced_plan)."""
         v = C.c_int64(0)
         self._check(self.lib.mcr_sliced_plan(self.handle, Mr, Ma, P, K, C.byref(v)))
+        return int(v.value)
+
+    def nested_rhat(self, draws, superchain_ids, layout: str = "pcn") -> dict:
+        """Nested R-hat per parameter (mcr_nested_rhat: Margossian et al., posterior::rhat_nested) of a host array or a
+        DeviceTensor with any number of chains up to MCR_NESTED_MAX_CHAINS.  superchain_ids: one integer label per chain
+        (any labels, every one equally often), or an int K for K contiguous blocks of C / K chains.  Arrays per
+        parameter: nrhat = max(nrhat_bulk, nrhat_tail), nrhat_raw (the paper's, on the draws), between_* / within_* (B and
+        W of each kind).  Chains are not split."""
+        if isinstance(draws, DeviceTensor):
+            if draws.chain_off is not None:
+                raise ValueError("nested R-hat needs chains of equal length; a ragged tensor is not supported")
+            targs, ptr, fn = draws.targs, draws.buf.ptr, self.lib.mcr_nested_rhat_dev
+        else:
+            targs, fn = tensor_args(draws, layout), self.lib.mcr_nested_rhat
+            ptr = draws.ctypes.data_as(C.c_void_p)
+        ids = superchain_labels(superchain_ids, targs[1])
+        P = targs[3]
+        arrs = {n: np.full(max(P, 1), np.nan) for n in NESTED_FIELDS}
+        out = Nested(**{n: _as_dp(a) for n, a in arrs.items()})
+        self._check(fn(self.handle, ptr, *targs, ids.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(out)))
+        return {n: a[:P] for n, a in arrs.items()}
+
+    def nested_params_per_chunk(self, t: "DeviceTensor", K: int) -> int:
+        """Parameters per workspace chunk of a nested_rhat call on this tensor with K superchains (mcr_nested_plan)."""
+        v = C.c_int64(0)
+        self._check(self.lib.mcr_nested_plan(self.handle, *t.targs, int(K), C.byref(v)))
         return int(v.value)
 
     def covariance(self, draws) -> np.ndarray:

@@ -10,6 +10,7 @@ this package's own: the chain files of a CmdStan run, parsed on the GPU, printed
 `json-summary ARCHIVE.json.zip...` for chain-list JSON archives and `csv-summary FILE.csv...` for table CSVs, and
 `validate MODEL --actual FILE.csv`, the command of `validate.validate` (compare's gate plus KS / Wasserstein-1 per
 parameter and, with `--sliced K`, along K random directions of the joint distribution; exits like `compare`).
+`nested-rhat FILE --superchains K` prints nested R-hat, the diagnostic for many short chains, of a draws table.
 """
 from __future__ import annotations
 
@@ -153,6 +154,21 @@ def csv_summary_cmd(files, format_: str, min_chains: int) -> None:
         for name, st in stats.items():
             click.echo(f"# {name}")
             _echo_stats(st, format_)
+
+
+@main.command("nested-rhat")
+@click.argument("file", type=click.Path(path_type=Path, exists=True, dir_okay=False))
+@click.option("--superchains", required=True, type=int, help="Number of superchains: blocks of chains in chain-id order")
+@click.option("--params", default=None, help="Comma-separated parameter list")
+@click.option("--format", "format_", type=click.Choice(["table", "csv", "json"], case_sensitive=False), default="table")
+def nested_rhat_cmd(file: Path, superchains: int, params: str | None, format_: str) -> None:
+    """Nested R-hat (Margossian et al.) of a draws table with any number of equal-length chains (no counterpart in the
+    reference): nrhat = max(nrhat_bulk, nrhat_tail), and nrhat_raw on the draws themselves."""
+    try:
+        stats = convert_mod.nested_rhat_file(file, superchains, params=params.split(",") if params else None)
+    except (ValueError, KeyError, IndexError) as exc:
+        raise click.ClickException(str(exc)) from exc
+    _echo_stats(stats, format_)
 
 
 @main.command("diagnostics")

@@ -574,6 +574,31 @@ def _read_input(path: Path):
     raise ValueError(f"Unsupported input format: {path}")
 
 
+def nested_rhat_file(path: Path, superchains: int, params: Iterable[str] | None = None,
+                     context=None) -> dict[str, dict[str, float]]:
+    """Nested R-hat of every parameter of a draws table (a `.csv` or chain-list `.json.zip`, read on the host): any
+    number of equal-length chains, dealt to `superchains` superchains in blocks, in chain-id order.  Per parameter:
+    nrhat, nrhat_bulk, nrhat_tail, nrhat_raw (Context.nested_rhat)."""
+    table = _ensure_chain_draw(_read_input(Path(path)))
+    names = [c for c in table.column_names if c not in ("chain", "draw")]
+    if params is not None:
+        missing = [p for p in params if p not in names]
+        if missing:
+            raise ValueError(f"Unknown parameter(s): {', '.join(missing)}")
+        names = list(params)
+    if not names:
+        return {}
+    x, counts = table_to_tensor(table, names)
+    if len(counts) and not np.all(counts == counts[0]):
+        raise ValueError("nested R-hat requires chains of equal length")
+    C = len(counts)
+    ctx = context or _ffi.default_context()
+    with _ffi.value_errors():
+        r = ctx.nested_rhat(x.reshape(len(names), C, int(counts[0]) if C else 0), int(superchains), "pcn")
+    keys = ("nrhat", "nrhat_bulk", "nrhat_tail", "nrhat_raw")
+    return {n: {k: float(r[k][i]) for k in keys} for i, n in enumerate(names)}
+
+
 def _ensure_chain_draw(table):
     """Add the missing bookkeeping columns like the reference does (convert.py:105-120): a missing
     `draw` is the row number, a missing `chain` is chain 0 (int32, appended after the parameters)."""

@@ -4,10 +4,16 @@ Mirrors src/mcmc_ref/diagnostics.py:13-73 (`split_rhat`, `ess_bulk`, `ess_tail`)
 same guards, same ValueError texts, NaN for fewer than two chains.  The arithmetic (pooled sort,
 tie-averaged ranks, AS241 inverse normal, fold, split-chain variances, first-negative-rho
 autocovariance sum) runs in libmcmcref_hip; chains may be ragged.
+
+`nested_rhat` is not the reference's: the diagnostic for many short chains (Margossian et al., "Nested R-hat: assessing
+the convergence of Markov chain Monte Carlo when running many short chains"; posterior::rhat_nested), for any number
+of equal-length chains.
 """
 from __future__ import annotations
 
 from collections.abc import Sequence
+
+import numpy as np
 
 from . import _ffi
 
@@ -52,3 +58,38 @@ def ess_tail(chains: Sequence[Sequence[float]], *, min_chains: int = 4) -> float
     if _guard(chains, min_chains, "ESS"):
         return float("nan")
     return diagnose(chains, min_chains=min_chains)["ess_tail"]
+
+
+def _nested_args(chains, superchain_ids):
+    """(draws [1][C][N] f64, int32 labels) of one parameter's chains; the ValueErrors of nested_rhat."""
+    lengths = {len(c) for c in chains}
+    if len(lengths) > 1:
+        raise ValueError(f"nested R-hat requires chains of equal length; got lengths {sorted(lengths)}")
+    if not isinstance(superchain_ids, (int, np.integer)) and len(superchain_ids) != len(chains):
+        raise ValueError(f"superchain_ids must have one label per chain: got {len(superchain_ids)} for {len(chains)} chains")
+    ids = _ffi.superchain_labels(superchain_ids, len(chains))
+    n = lengths.pop() if lengths else 0
+    x = np.ascontiguousarray(chains, dtype=np.float64).reshape(1, len(chains), n)
+    return x, ids
+
+
+def nested_rhat_detail(chains: Sequence[Sequence[float]], superchain_ids, *, context=None) -> dict:
+    """Nested R-hat of ONE parameter given as equal-length chains, chain c in superchain superchain_ids[c] (or an int K:
+    K contiguous blocks of chains): floats nrhat = max(nrhat_bulk, nrhat_tail), nrhat_raw, and the between / within
+    variances B and W of each kind (Context.nested_rhat)."""
+    x, ids = _nested_args(chains, superchain_ids)
+    ctx = context or _ffi.default_context()
+    with _ffi.value_errors():
+        res = ctx.nested_rhat(x, ids, "pcn")
+    return {k: float(v[0]) for k, v in res.items()}
+
+
+def nested_rhat(chains: Sequence[Sequence[float]], superchain_ids, *, context=None) -> float:
+    """Rank-normalized nested R-hat with folded variant (the max of both); NaN for fewer than two superchains.  Chains are
+    not split and may be any number; values near 1 (the paper suggests 1.01) say the superchains forgot their starts."""
+    x, ids = _nested_args(chains, superchain_ids)
+    if np.unique(ids).size < 2:
+        return float("nan")
+    ctx = context or _ffi.default_context()
+    with _ffi.value_errors():
+        return float(ctx.nested_rhat(x, ids, "pcn")["nrhat"][0])
