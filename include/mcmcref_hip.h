@@ -134,6 +134,12 @@ int mcr_plan_chunks_chains(mcr_ctx* ctx, const int64_t* chain_off, int C, int64_
  * to show that the guard ran.  Waits for the calls in flight. */
 int mcr_rho_guard_count(mcr_ctx* ctx, int64_t* rederived);
 
+/* How many 4096-draw tiles of f64 draws this context has sorted as (key, position) pairs so far, after their sort as
+ * 64-bit records (upper 52 bits of the draw + tile slot) failed its order check: draws of one tile that agree in their
+ * upper 52 bits and whose low bits order them against their slots.  A diagnostic: tests use it to show which path ran.
+ * Waits for the calls in flight. */
+int mcr_tile_fallback_count(mcr_ctx* ctx, int64_t* tiles);
+
 /* ---- device memory plumbing (for device-resident benchmarking and pipelines) --------- */
 int mcr_dev_alloc(mcr_ctx* ctx, size_t bytes, void** dptr);
 int mcr_dev_free(mcr_ctx* ctx, void* dptr);

@@ -189,7 +189,8 @@ struct mcr_ctx {
     double rho_band = kRhoBand;   // MCR_RHO_BAND: half-width of the guard band of the tier-3 scan (0 = decide on the raw values)
     DevBuf nest_dev{4};                // mcr_nested_rhat: chain permutation + result table
     PinBuf nest_host{4};               // its results on the host
-    DevBuf guard_count;                // device counter (unsigned): band lags re-derived the reference's way (mcr_rho_guard_count)
+    DevBuf guard_count;                // device counters (2 unsigned): band lags re-derived the reference's way (mcr_rho_guard_count),
+                                       // tiles the tile sort sorted as pairs after all (mcr_tile_fallback_count)
 };
 
 namespace {
@@ -667,10 +668,12 @@ int sort_stage_t(mcr_ctx* ctx, PipeIn& a, Sorted& out)
     double* const samp1 = (bucket && a.bk_R == kTile) ? a.samp : (double*)nullptr;
     if (a.x_f32) {
         LAUNCH(ctx, K_TILE_SORT, (k_tile_sort<kTileNT, kTileVT, IdxT, float>), dim3((unsigned)a.ntiles, py), dim3(kTileNT),
-               lds_tile, (const float*)a.X, M, a.kA, (IdxT*)a.iA, a.part, (int)a.ntiles, samp1);
+               lds_tile, (const float*)a.X, M, a.kA, (IdxT*)a.iA, a.part, (int)a.ntiles, samp1,
+               ctx->guard_count.as<unsigned>() + 1);
     } else {
         LAUNCH(ctx, K_TILE_SORT, (k_tile_sort<kTileNT, kTileVT, IdxT, double>), dim3((unsigned)a.ntiles, py), dim3(kTileNT),
-               lds_tile, (const double*)a.X, M, a.kA, (IdxT*)a.iA, a.part, (int)a.ntiles, samp1);
+               lds_tile, (const double*)a.X, M, a.kA, (IdxT*)a.iA, a.part, (int)a.ntiles, samp1,
+               ctx->guard_count.as<unsigned>() + 1);
     }
     double *kin = a.kA, *kout = a.kB;
     IdxT *iin = (IdxT*)a.iA, *iout = (IdxT*)a.iB;
@@ -1290,8 +1293,8 @@ int mcr_init(int device, mcr_ctx** out)
     if (const char* env = getenv("MCR_SPLITTERS_PAIRWISE")) ctx->splitters_pairwise = atoi(env) != 0;
     if (const char* env = getenv("MCR_FORK")) ctx->fork_lone = atoi(env) != 0;
     if (const char* env = getenv("MCR_RHO_BAND")) { const double v = atof(env); if (v >= 0.0 && v < 1.0) ctx->rho_band = v; }
-    if (ctx->guard_count.reserve(ctx, sizeof(unsigned)) != MCR_OK ||
-        hipMemsetAsync(ctx->guard_count.p, 0, sizeof(unsigned), ctx->stream) != hipSuccess ||
+    if (ctx->guard_count.reserve(ctx, 2 * sizeof(unsigned)) != MCR_OK ||
+        hipMemsetAsync(ctx->guard_count.p, 0, 2 * sizeof(unsigned), ctx->stream) != hipSuccess ||
         hipStreamSynchronize(ctx->stream) != hipSuccess) {
         mcr_free(ctx);
         return fail(nullptr, MCR_ENOMEM, "device %d: cannot allocate the guard counter", device);
@@ -1321,6 +1324,17 @@ int mcr_rho_guard_count(mcr_ctx* ctx, int64_t* rederived)
     unsigned v = 0;
     HIP_TRY(ctx, hipMemcpy(&v, ctx->guard_count.p, sizeof(unsigned), hipMemcpyDeviceToHost));
     *rederived = (int64_t)v;
+    return MCR_OK;
+}
+
+int mcr_tile_fallback_count(mcr_ctx* ctx, int64_t* tiles)
+{
+    if (!ctx || !tiles) return fail(ctx, MCR_EINVAL, "NULL argument");
+    hipSetDevice(ctx->device);
+    sync_all(ctx);
+    unsigned v = 0;
+    HIP_TRY(ctx, hipMemcpy(&v, ctx->guard_count.as<unsigned>() + 1, sizeof(unsigned), hipMemcpyDeviceToHost));
+    *tiles = (int64_t)v;
     return MCR_OK;
 }
 

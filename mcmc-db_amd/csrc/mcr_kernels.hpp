@@ -3,7 +3,8 @@
 // Per model (C chains x N draws, M = C*N pooled draws per parameter, P parameters) the pipeline is
 //
 //   k_ingest_*      (only if the tensor is not in the Arrow layout [P][C][N])  strided -> X[P][M] f64
-//   k_tile_sort     X (f64, or f32 widened on load) -> sorted 4096-draw tiles of (key f64, pooled position u16 | u32)
+//   k_tile_sort     X (f64, or f32 widened on load) -> sorted 4096-draw tiles of (key f64, pooled position u16 | u32),
+//                   sorted as 64-bit records (upper 52 bits + tile slot), checked, as (key, position) pairs if that fails
 //                   + the tile's (count, mean, M2) + every 64th order statistic of each tile
 //                   (f32 tensors: the packed-record kernels of mcr_sort32.hpp take the first four places of this list)
 //   k_merge<false>  only for M > 64K: pairwise merge-path passes until at most 16 sorted runs remain
@@ -310,7 +311,7 @@ __device__ __forceinline__ void thread_sort(double (&k)[VT], u32 (&ix)[VT])
 }
 
 #ifndef MCR_TILE_DPP_LEVELS
-#define MCR_TILE_DPP_LEVELS 3      // 0: every merge level in LDS; 2 / 3: the first two / three in registers (below)
+#define MCR_TILE_DPP_LEVELS 3      // 0: every merge level in LDS; 2 / 3: the first two / three in registers (below); 2 only with MCR_TILE_REC=0
 #endif
 
 // The first two merge levels of the tile sort (16 -> 32 -> 64 sorted draws) without the LDS: bitonic merges across 2 and 4
@@ -427,17 +428,31 @@ __device__ __forceinline__ void serial_merge(const double* skey, int a0, int na,
     }
 }
 
+#ifndef MCR_TILE_REC
+#define MCR_TILE_REC 1      // 1: f64 tiles are sorted as records, with the pair sort as the fallback (k_tile_sort below)
+#endif
+// The pair sort is a function of its own under the record sort: inlined, the two sorts' registers exceed the 128 that four
+// waves per SIMD allow, or spill on the record path.  As a call the record path has no spill; the callee's frame (104
+// bytes per lane, its callee-saved registers) is touched by falling tiles only.
+#if MCR_TILE_REC == 0
+#define MCR_TILE_PAIRS_INLINE __forceinline__
+#else
+#define MCR_TILE_PAIRS_INLINE __noinline__
+#endif
+
 // IdxT = the pooled-position payload: u16 when M < 65536 (C1 and every packaged model: 10 bytes per LDS slot, so FOUR
 // 4096-draw tiles are resident per CU instead of three, and 10 instead of 12 bytes per draw go to HBM and back),
 // u32 otherwise.  LDS: skey[T] then sidx[T], nothing else -- the single read "one slot past the last run" of
 // serial_merge lands on sidx[0] (in bounds, value never selected); the reduction scratch reuses skey at the end.
 template <typename IdxT> constexpr size_t sort_lds_bytes(int T) { return (size_t)T * (8 + sizeof(IdxT)); }
 
+// The tile sort on (f64 key, position) PAIRS: the whole kernel up to round 7, and since then what a workgroup falls back to
+// when its tile cannot be sorted as records (below); inlined as the kernel itself with -DMCR_TILE_REC=0.
 template <int NT, int VT, typename IdxT, typename XT>
-__global__ __launch_bounds__(NT) void k_tile_sort(const XT* __restrict__ X, i64 M,
-                                                  double* __restrict__ keys, IdxT* __restrict__ idx,
-                                                  double* __restrict__ part, int ntiles,
-                                                  double* __restrict__ samp)
+__device__ MCR_TILE_PAIRS_INLINE void tile_sort_pairs(const XT* __restrict__ X, i64 M,
+                                                      double* __restrict__ keys, IdxT* __restrict__ idx,
+                                                      double* __restrict__ part, int ntiles,
+                                                      double* __restrict__ samp)
 {
     constexpr int T = NT * VT;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -542,6 +557,321 @@ __global__ __launch_bounds__(NT) void k_tile_sort(const XT* __restrict__ X, i64 
     if (full) moments(std::true_type{}); else moments(std::false_type{});
     block_sum3<NT>(s2, e1, bad, red);
     if (tid == 0) store_slice_moments(part + (p * ntiles + tile) * kMomRec, mt, e1, s2, bad, (double)count);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Sorting RECORDS: one 64-bit word per draw that orders by itself and carries its payload, so a compare-exchange is one
+// compare + four selects (or one minimum + one maximum) instead of one compare + six selects, a lane-pair exchange moves
+// two words instead of three, and nothing is gathered after a merge level.  R = u64 (f32 draws: key image << 32 |
+// position, mcr_sort32.hpp) or double (f64 draws: the draw with its low 12 mantissa bits replaced by its tile slot,
+// k_tile_sort below).
+// ------------------------------------------------------------------------------------------------
+#ifndef MCR_TILE_REC_MINMAX
+#define MCR_TILE_REC_MINMAX 1      // 0: double records are exchanged by compare + selects like the integer ones (A/B builds)
+#endif
+template <typename R> __device__ __forceinline__ R rec_pad();
+template <> __device__ __forceinline__ u64 rec_pad<u64>() { return kRecPad; }
+template <> __device__ __forceinline__ double rec_pad<double>() { return INFINITY; }
+
+__device__ __forceinline__ void rec_ce(u64& a, u64& b)
+{
+    const bool sw = b < a;
+    const u64 lo = sw ? b : a, hi = sw ? a : b;
+    a = lo; b = hi;
+}
+// Double records are finite or the +inf pad, never NaN, and no two live ones are equal (they differ in the slot bits; of +0.0
+// and -0.0 only slot 0 can hold one), so minimum and maximum return the two operands themselves, bit for bit (fp64
+// denormals are never flushed on this target).  As instructions, not as fmin / fmax: those canonicalise operands the
+// compiler cannot prove quiet -- one more instruction for every register that comes out of a DPP move.
+__device__ __forceinline__ void rec_ce(double& a, double& b)
+{
+#if MCR_TILE_REC_MINMAX
+    double lo, hi;
+    asm("v_min_f64 %0, %1, %2" : "=v"(lo) : "v"(a), "v"(b));
+    asm("v_max_f64 %0, %1, %2" : "=v"(hi) : "v"(a), "v"(b));
+    a = lo; b = hi;
+#else
+    const bool sw = b < a;
+    const double lo = sw ? b : a, hi = sw ? a : b;
+    a = lo; b = hi;
+#endif
+}
+
+// Register sort of VT records per lane (the networks of mcr_sortnet.h).
+template <int VT, typename R>
+__device__ __forceinline__ void thread_sort_rec(R (&r)[VT])
+{
+    static_assert(VT == 16 || VT == 8, "sorting networks exist for 16 and 8 items per lane");
+#define MCR_CE(a, b) rec_ce(r[a], r[b]);
+    if constexpr (VT == 16) { MCR_NET16(MCR_CE) } else { MCR_NET8(MCR_CE) }
+#undef MCR_CE
+}
+
+// lane_merge_levels_16_to_64 (+ the third level) on records: the first three merge levels of the tile sort (16 -> 128
+// records) as bitonic merges across 2, 4 and 8 lanes over DPP; records are distinct, so an exchange is one compare per side.
+template <int CTRL>
+__device__ __forceinline__ u64 dpp_rec(u64 v)
+{
+    return ((u64)dpp_u32<CTRL>((u32)(v >> 32)) << 32) | (u64)dpp_u32<CTRL>((u32)v);
+}
+template <int CTRL>
+__device__ __forceinline__ double dpp_rec(double v) { return dpp_f64<CTRL>(v); }
+__device__ __forceinline__ u64 select_by_mask(u64 a, u64 b, unsigned long long m)
+{
+    return ((u64)select_by_mask((u32)(a >> 32), (u32)(b >> 32), m) << 32) | (u64)select_by_mask((u32)a, (u32)b, m);
+}
+
+template <int CTRL, bool MIRROR, unsigned long long MIN_LANES, typename R>
+__device__ __forceinline__ void lane_pair_stage_rec(R (&r)[16])
+{
+    auto exchange = [](R& own, R o) {
+        const unsigned long long lt = __builtin_amdgcn_ballot_w64(o < own), gt = __builtin_amdgcn_ballot_w64(own < o);
+        own = select_by_mask(own, o, (lt & MIN_LANES) | (gt & ~MIN_LANES));
+    };
+#pragma unroll
+    for (int i = 0; i < (MIRROR ? 8 : 16); ++i) {
+        const int s = MIRROR ? 15 - i : i;
+        const R o_i = dpp_rec<CTRL>(r[s]);
+        if (MIRROR) {
+            const R o_s = dpp_rec<CTRL>(r[i]);
+            exchange(r[s], o_s);
+        }
+        exchange(r[i], o_i);
+    }
+}
+
+template <typename R>
+__device__ __forceinline__ void lane_bitonic_merge16_rec(R (&r)[16])
+{
+#define MCR_CE(a, b) rec_ce(r[a], r[b]);
+    MCR_BITONIC16(MCR_CE)
+#undef MCR_CE
+}
+
+template <typename R>
+__device__ __forceinline__ void lane_merge_levels_rec(R (&r)[16])
+{
+    constexpr unsigned long long kEvenLanes = 0x5555555555555555ull, kLowPairs = 0x3333333333333333ull,
+                                 kLowQuads = 0x0F0F0F0F0F0F0F0Full;
+    lane_pair_stage_rec<0xB1, true, kEvenLanes>(r);
+    lane_bitonic_merge16_rec(r);
+    lane_pair_stage_rec<0x1B, true, kLowPairs>(r);
+    lane_pair_stage_rec<0xB1, false, kEvenLanes>(r);
+    lane_bitonic_merge16_rec(r);
+    lane_pair_stage_rec<0x141, true, kLowQuads>(r);
+    lane_pair_stage_rec<0x4E, false, kLowPairs>(r);
+    lane_pair_stage_rec<0xB1, false, kEvenLanes>(r);
+    lane_bitonic_merge16_rec(r);
+}
+
+// serial_merge on records: the record IS the payload, so there is nothing to gather afterwards.
+// LIM > 0: slot indices are clamped to LIM (k_tile_sort32 declares exactly T slots so that five tiles fit a CU, and
+// the unconditional read one past the last run must not leave them).
+template <int VT, int LIM = 0, typename R>
+__device__ __forceinline__ void serial_merge_rec(const R* srec, int a0, int na, int b0, int nb, int ai, int bi,
+                                                 int nout, R (&out)[VT])
+{
+    int pa = a0 + ai, pb = b0 + bi;
+    const int ea = a0 + na, eb = b0 + nb;
+    auto slot = [](int e) { return pos16(LIM > 0 ? min(e, LIM) : e); };
+    R ar = srec[slot(pa)], br = srec[slot(pb)];
+#pragma unroll
+    for (int i = 0; i < VT; ++i) {
+        if (i < nout) {
+            const bool takeA = (pb >= eb) | ((pa < ea) & !(br < ar));
+            out[i] = takeA ? ar : br;
+            pa += takeA ? 1 : 0;
+            pb += takeA ? 0 : 1;
+            const int pn = takeA ? pa : pb;
+            const R nv = srec[slot(pn)];
+            ar = takeA ? nv : ar;
+            br = takeA ? br : nv;
+        } else {
+            out[i] = rec_pad<R>();
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The tile sort proper: f64 draws as 64-bit records, with the pair sort above as the exact fallback.
+// An f64 key and a 12-bit tile slot do not fit 64 bits, but they almost do: two draws of one tile that agree in their upper
+// 52 bits and differ below lie within 2^-40 of each other, relatively -- rounded, tied or ordinary draws never do.  So
+//   record = the draw with its low 12 mantissa bits replaced by its slot e (the 12 bits wait in slow[e], 8 KB of LDS where
+//            the pair sort keeps its positions), compared as a double: the order of (upper 52 bits, then slot, up or down
+//            with the sign);
+//   sort     network, three DPP levels and five LDS levels on records alone (no ix[], no src[], no position traffic);
+//   rebuild  key = record with slow[slot] back in its low bits (exact), position = base + slot, in registers, where the
+//            lane's 16 consecutive sorted draws are -- the moments run on them as in the pair sort, bit for bit;
+//   CHECK    every adjacent pair of rebuilt keys non-decreasing: 15 compares in the lane, the lane boundary over DPP, the
+//            wave boundaries and the waves' flags through a few words of the dead record array.  Adjacent order is
+//            sorted order.
+// A workgroup whose check fails (some draws tie in the upper 52 bits and their low bits order them against their slots)
+// runs tile_sort_pairs on the same 40 KB and writes the tile from there: no second launch, nothing written before the
+// check.  Equal keys come out by slot instead of by hand-out; nothing downstream sees it.  Non-finite draws are counted and
+// sorted as a tiny finite stand-in (the call fails with MCR_ENONFINITE anyway), pads are +inf.  f32 draws widen to
+// doubles whose low 29 bits are zero: they never fall back.
+// -DMCR_TILE_REC=0: the pair sort alone; 2: every tile falls back after its record sort (tests, and the price of one).
+// `fallbacks` (may be null) counts the tiles that fell back (mcr_tile_fallback_count).
+// amdgpu_waves_per_eu(4): 40 KB of LDS put four workgroups = four waves per SIMD on a CU; told so, the compiler keeps kernel
+// and callee within 128 registers (two waves per SIMD otherwise).
+// ------------------------------------------------------------------------------------------------
+template <int NT, int VT, typename IdxT, typename XT>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void k_tile_sort(const XT* __restrict__ X, i64 M,
+                                                  double* __restrict__ keys, IdxT* __restrict__ idx,
+                                                  double* __restrict__ part, int ntiles,
+                                                  double* __restrict__ samp, unsigned* __restrict__ fallbacks)
+{
+#if MCR_TILE_REC == 0
+    tile_sort_pairs<NT, VT, IdxT, XT>(X, M, keys, idx, part, ntiles, samp);
+#else
+    constexpr int T = NT * VT;
+    constexpr u32 kSlotMask = 0xFFFu;
+    static_assert(T <= 4096, "a record has 12 bits for the tile slot");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    double* srec = reinterpret_cast<double*>(smem);                          // records, then the rebuilt keys
+    unsigned short* slow = reinterpret_cast<unsigned short*>(srec + T);      // the draws' low 12 bits by slot ...
+    IdxT* sidx = reinterpret_cast<IdxT*>(srec + T);                          // ... and, once they are back in the keys, the positions
+    double* red = srec;      // only after the sorted tile has left LDS
+
+    const int tid = threadIdx.x, tile = blockIdx.x;
+    const i64 p = blockIdx.y;
+    const i64 base = (i64)tile * T;
+    const int count = (int)((M - base < (i64)T) ? M - base : (i64)T);
+    const XT* src = X + p * M + base;
+    const bool full = count == T;        // workgroup-uniform, as in the pair sort
+    const int nlive = count - tid * VT;  // after the sort the lane's slots [0, nlive) hold draws, the others pads
+
+    double r[VT];
+    double bad = 0.0;
+    auto load = [&](auto full_c) {
+        constexpr bool FULL = decltype(full_c)::value;
+        XT v[VT];
+#pragma unroll
+        for (int i = 0; i < VT; ++i) {       // every load unconditional and in flight (a pad slot re-reads the last draw)
+            const int e = i * NT + tid;
+            v[i] = src[FULL ? e : min(e, count - 1)];
+        }
+#pragma unroll
+        for (int i = 0; i < VT; ++i) {
+            const int e = i * NT + tid;
+            const bool live = FULL || e < count;
+            const double d = (double)v[i];
+            const bool fin = isfinite(d);
+            bad += (live && !fin) ? 1.0 : 0.0;
+            const u32 lo = (u32)__double2loint(d), hi = (u32)__double2hiint(d);
+            if (live) slow[e] = (unsigned short)(lo & kSlotMask);                // lane tid, slot i * NT + tid: conflict-free
+            const double rec = __hiloint2double((int)(fin ? hi : 0u), (int)((lo & ~kSlotMask) | (u32)e));
+            r[i] = live ? rec : INFINITY;
+        }
+    };
+    if (full) load(std::true_type{}); else load(std::false_type{});
+    thread_sort_rec<VT>(r);
+    static_assert(MCR_TILE_DPP_LEVELS == 0 || MCR_TILE_DPP_LEVELS >= 3,
+                  "the record sort has all three register levels or none: build MCR_TILE_DPP_LEVELS=2 with MCR_TILE_REC=0");
+    constexpr bool kLaneLevels = MCR_TILE_DPP_LEVELS >= 3 && VT == 16;
+    if constexpr (kLaneLevels) lane_merge_levels_rec(r);
+#pragma unroll
+    for (int i = 0; i < VT; ++i) srec[pos16(tid * VT + i)] = r[i];
+    __syncthreads();
+    // (the read "one slot past the last run" of serial_merge_rec lands on slow[0..3]: in bounds, never selected)
+    for (int coop = kLaneLevels ? 16 : 2; coop <= NT; coop <<= 1) {
+        const int first = tid & ~(coop - 1);
+        const int run = VT * (coop >> 1);
+        const int a0 = first * VT, b0 = a0 + run;
+        const int diag = VT * (tid - first);
+        auto A = [&](int i) { return srec[pos16(a0 + i)]; };
+        auto B = [&](int j) { return srec[pos16(b0 + j)]; };
+        const int ai = merge_path32(A, run, B, run, diag);
+        serial_merge_rec<VT>(srec, a0, run, b0, run, ai, diag - ai, VT, r);
+        __syncthreads();
+        if (coop < NT) {                 // the last level's records stay in registers
+#pragma unroll
+            for (int i = 0; i < VT; ++i) srec[pos16(tid * VT + i)] = r[i];
+            __syncthreads();
+        }
+    }
+
+    // rebuild keys and positions of the lane's 16 consecutive sorted draws; check; stage them for the coalesced write-out
+    double k[VT];
+    u32 slot[VT];
+    bool viol = false;
+    auto rebuild = [&](auto full_c) {
+        constexpr bool FULL = decltype(full_c)::value;
+#pragma unroll
+        for (int i = 0; i < VT; ++i) {
+            const u32 lo = (u32)__double2loint(r[i]);
+            slot[i] = lo & kSlotMask;                     // (a pad's "slot" is 0: read, not used)
+            const double key = __hiloint2double(__double2hiint(r[i]), (int)((lo & ~kSlotMask) | (u32)slow[slot[i]]));
+            k[i] = (FULL || i < nlive) ? key : INFINITY;
+        }
+    };
+    if (full) rebuild(std::true_type{}); else rebuild(std::false_type{});
+#pragma unroll
+    for (int i = 0; i + 1 < VT; ++i) viol |= k[i + 1] < k[i];
+    // The lane boundary inside a wave over DPP (wave_shl:1 hands lane L the first key of lane L + 1); the three wave
+    // boundaries and the waves' flags through 12 words at the head of the record array, which is dead since the barrier
+    // behind the last level.  No __syncthreads_or: its 256 bytes of static LDS on top of the 40 960 dynamic ones would
+    // leave three workgroups per CU instead of four.
+    constexpr int NW = NT / kWave;
+    const int lane = tid & (kWave - 1), wave = tid / kWave;
+    const double next_first = dpp_f64<0x130>(k[0]);
+    viol |= lane + 1 < kWave && next_first < k[VT - 1];
+    int* wflag = reinterpret_cast<int*>(srec + 2 * NW);
+    const bool wave_viol = __builtin_amdgcn_ballot_w64(viol) != 0;
+    if (lane == 0) { srec[wave] = k[0]; wflag[wave] = wave_viol ? 1 : 0; }
+    if (lane == kWave - 1) srec[NW + wave] = k[VT - 1];
+    __syncthreads();
+    bool fall = MCR_TILE_REC == 2;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+        fall |= wflag[w] != 0;
+        if (w + 1 < NW) fall |= srec[w + 1] < srec[NW + w];
+    }
+    __syncthreads();                     // the scratch is read: the keys (or the pair sort) may take its place
+    if (fall) {
+        if (tid == 0 && fallbacks != nullptr) atomicAdd(fallbacks, 1u);
+        tile_sort_pairs<NT, VT, IdxT, XT>(X, M, keys, idx, part, ntiles, samp);
+        return;
+    }
+    // (every lane read its low bits before the first of the two barriers: the positions may take their place)
+#pragma unroll
+    for (int i = 0; i < VT; ++i) {
+        srec[pos16(tid * VT + i)] = k[i];
+        sidx[posi(tid * VT + i)] = (IdxT)((u32)base + slot[i]);
+    }
+    __syncthreads();
+
+    auto write_out = [&](auto full_c) {
+        constexpr bool FULL = decltype(full_c)::value;
+#pragma nounroll
+        for (int e = tid; e < (FULL ? T : count); e += NT) {
+            keys[p * M + base + e] = srec[pos16(e)];
+            idx[p * M + base + e] = sidx[posi(e)];
+        }
+    };
+    if (full) write_out(std::true_type{}); else write_out(std::false_type{});
+    // regular samples (every 64th order statistic of the tile) for the exact bucket partition
+    if (samp != nullptr && tid < T / 64) {
+        const int e = 64 * tid + 63;
+        samp[(p * ntiles + tile) * (T / 64) + tid] = (e < count) ? srec[pos16(e)] : INFINITY;
+    }
+    __syncthreads();                 // `red` aliases srec from here on
+    // the tile's moments from the lane's sorted draws in registers: the same values in the same slots as in the pair sort,
+    // added in the same order
+    double s1 = 0.0, s2 = 0.0, e1 = 0.0, mt = 0.0;
+    auto moments = [&](auto full_c) {
+        constexpr bool FULL = decltype(full_c)::value;
+#pragma unroll
+        for (int i = 0; i < VT; ++i) s1 += (FULL || i < nlive) ? k[i] : 0.0;
+        s1 = block_sum<NT>(s1, red);
+        mt = s1 / (double)count;
+#pragma unroll
+        for (int i = 0; i < VT; ++i) { const double d = (FULL || i < nlive) ? k[i] - mt : 0.0; s2 = fma(d, d, s2); e1 += d; }
+    };
+    if (full) moments(std::true_type{}); else moments(std::false_type{});
+    block_sum3<NT>(s2, e1, bad, red);
+    if (tid == 0) store_slice_moments(part + (p * ntiles + tile) * kMomRec, mt, e1, s2, bad, (double)count);
+#endif
 }
 
 // ------------------------------------------------------------------------------------------------

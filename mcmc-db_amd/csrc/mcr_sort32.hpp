@@ -17,107 +17,8 @@ namespace mcr {
 __device__ __forceinline__ u32 rec_key(u64 r) { return (u32)(r >> 32); }
 __device__ __forceinline__ u32 rec_pos(u64 r) { return (u32)r; }
 
-// Register sort of VT records per lane (the networks of mcr_sortnet.h on 64-bit integers).
-template <int VT>
-__device__ __forceinline__ void thread_sort_rec(u64 (&r)[VT])
-{
-    static_assert(VT == 16 || VT == 8, "sorting networks exist for 16 and 8 items per lane");
-#define MCR_CE(a, b)                                         \
-    {                                                        \
-        const bool sw = r[b] < r[a];                         \
-        const u64 lo = sw ? r[b] : r[a], hi = sw ? r[a] : r[b]; \
-        r[a] = lo; r[b] = hi;                                \
-    }
-    if constexpr (VT == 16) { MCR_NET16(MCR_CE) } else { MCR_NET8(MCR_CE) }
-#undef MCR_CE
-}
-
-// lane_merge_levels of mcr_kernels.hpp on records: the first three merge levels of the tile sort (16 -> 128 records) as
-// bitonic merges across 2, 4 and 8 lanes over DPP; records are distinct (the position is in the low word), so an
-// exchange is one unsigned compare per side.
-template <int CTRL>
-__device__ __forceinline__ u64 dpp_u64(u64 v)
-{
-    return ((u64)dpp_u32<CTRL>((u32)(v >> 32)) << 32) | (u64)dpp_u32<CTRL>((u32)v);
-}
-__device__ __forceinline__ u64 select_by_mask(u64 a, u64 b, unsigned long long m)
-{
-    return ((u64)select_by_mask((u32)(a >> 32), (u32)(b >> 32), m) << 32) | (u64)select_by_mask((u32)a, (u32)b, m);
-}
-
-template <int CTRL, bool MIRROR, unsigned long long MIN_LANES>
-__device__ __forceinline__ void lane_pair_stage_rec(u64 (&r)[16])
-{
-    auto exchange = [](u64& own, u64 o) {
-        const unsigned long long lt = __builtin_amdgcn_ballot_w64(o < own), gt = __builtin_amdgcn_ballot_w64(own < o);
-        own = select_by_mask(own, o, (lt & MIN_LANES) | (gt & ~MIN_LANES));
-    };
-#pragma unroll
-    for (int i = 0; i < (MIRROR ? 8 : 16); ++i) {
-        const int s = MIRROR ? 15 - i : i;
-        const u64 o_i = dpp_u64<CTRL>(r[s]);
-        if (MIRROR) {
-            const u64 o_s = dpp_u64<CTRL>(r[i]);
-            exchange(r[s], o_s);
-        }
-        exchange(r[i], o_i);
-    }
-}
-
-__device__ __forceinline__ void lane_bitonic_merge16_rec(u64 (&r)[16])
-{
-#define MCR_CE(a, b)                                         \
-    {                                                        \
-        const bool sw = r[b] < r[a];                         \
-        const u64 lo = sw ? r[b] : r[a], hi = sw ? r[a] : r[b]; \
-        r[a] = lo; r[b] = hi;                                \
-    }
-    MCR_BITONIC16(MCR_CE)
-#undef MCR_CE
-}
-
-__device__ __forceinline__ void lane_merge_levels_rec(u64 (&r)[16])
-{
-    constexpr unsigned long long kEvenLanes = 0x5555555555555555ull, kLowPairs = 0x3333333333333333ull,
-                                 kLowQuads = 0x0F0F0F0F0F0F0F0Full;
-    lane_pair_stage_rec<0xB1, true, kEvenLanes>(r);
-    lane_bitonic_merge16_rec(r);
-    lane_pair_stage_rec<0x1B, true, kLowPairs>(r);
-    lane_pair_stage_rec<0xB1, false, kEvenLanes>(r);
-    lane_bitonic_merge16_rec(r);
-    lane_pair_stage_rec<0x141, true, kLowQuads>(r);
-    lane_pair_stage_rec<0x4E, false, kLowPairs>(r);
-    lane_pair_stage_rec<0xB1, false, kEvenLanes>(r);
-    lane_bitonic_merge16_rec(r);
-}
-
-// serial_merge of mcr_kernels.hpp on records: the record IS the payload, so there is nothing to gather afterwards.
-// LIM > 0: slot indices are clamped to LIM (k_tile_sort32 declares exactly T slots so that five tiles fit a CU, and
-// the unconditional read one past the last run must not leave them).
-template <int VT, int LIM = 0>
-__device__ __forceinline__ void serial_merge_rec(const u64* srec, int a0, int na, int b0, int nb, int ai, int bi,
-                                                 int nout, u64 (&out)[VT])
-{
-    int pa = a0 + ai, pb = b0 + bi;
-    const int ea = a0 + na, eb = b0 + nb;
-    auto slot = [](int e) { return pos16(LIM > 0 ? min(e, LIM) : e); };
-    u64 ar = srec[slot(pa)], br = srec[slot(pb)];
-#pragma unroll
-    for (int i = 0; i < VT; ++i) {
-        if (i < nout) {
-            const bool takeA = (pb >= eb) | ((pa < ea) & !(br < ar));
-            out[i] = takeA ? ar : br;
-            pa += takeA ? 1 : 0;
-            pb += takeA ? 0 : 1;
-            const int pn = takeA ? pa : pb;
-            const u64 nv = srec[slot(pn)];
-            ar = takeA ? nv : ar;
-            br = takeA ? br : nv;
-        } else {
-            out[i] = kRecPad;
-        }
-    }
-}
+// (thread_sort_rec, lane_merge_levels_rec and serial_merge_rec -- the register sort, the three DPP merge levels and the
+// serial LDS merge on records -- live in mcr_kernels.hpp: the f64 tile sort runs on records as well.)
 
 // One more slot than records: the unconditional read "one past the last run" of serial_merge_rec stays in bounds.
 constexpr size_t rec_lds_bytes(int T) { return (size_t)(T + 2) * 8; }

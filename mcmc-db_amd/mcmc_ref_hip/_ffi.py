@@ -120,6 +120,7 @@ SYMBOLS = {
     "mcr_last_error": (C.c_char_p, [C.c_void_p]),
     "mcr_set_workspace_limit": (C.c_int, [C.c_void_p, C.c_size_t]),
     "mcr_rho_guard_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "mcr_tile_fallback_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "mcr_plan_chunks": (C.c_int, [C.c_void_p] + [C.c_int64] * 6 + [C.c_int, C.POINTER(C.c_int64)]),
     "mcr_plan_chunks_chains": (C.c_int, [C.c_void_p, _ip, C.c_int, _I64, C.c_int, C.POINTER(C.c_int64)]),
     "mcr_dev_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
@@ -1224,6 +1225,12 @@ class Context:
         """Band lags of the tier-3 ESS scan re-derived with the reference's own sums so far (mcr_rho_guard_count)."""
         v = C.c_int64(0)
         self._check(self.lib.mcr_rho_guard_count(self.handle, C.byref(v)))
+        return int(v.value)
+
+    def tile_fallback_count(self) -> int:
+        """Tiles the f64 tile sort sorted as (key, position) pairs after its record sort failed its order check, so far."""
+        v = C.c_int64(0)
+        self._check(self.lib.mcr_tile_fallback_count(self.handle, C.byref(v)))
         return int(v.value)
 
     def profile(self, on: bool):

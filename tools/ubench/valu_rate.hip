@@ -56,6 +56,19 @@ __global__ __launch_bounds__(256) void k_rate(unsigned* out, int iters)
             asm volatile("v_cmp_lt_f64_e64 %8, %10, %11\n v_cndmask_b32_e64 %0, %0, %9, %8\n v_cndmask_b32_e64 %1, %1, %9, %8\n v_cndmask_b32_e64 %2, %2, %9, %8\n"
                          "v_cndmask_b32_e64 %3, %3, %9, %8\n v_cndmask_b32_e64 %4, %4, %9, %8\n v_cndmask_b32_e64 %5, %5, %9, %8\n v_mov_b32_e32 %6, %7\n"
                          : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7), "=&s"(s0) : "v"(b), "v"(d0), "v"(d1));
+        } else if (KIND == 10) {  // v_cmp_lt_u64 (to SGPR pairs): the compare of records under an integer image
+            unsigned long long s0, s1, s2, s3;
+            asm volatile("v_cmp_lt_u64_e64 %0, %4, %5\n v_cmp_lt_u64_e64 %1, %5, %4\n v_cmp_lt_u64_e64 %2, %4, %5\n v_cmp_lt_u64_e64 %3, %5, %4\n"
+                         "v_cmp_lt_u64_e64 %0, %4, %5\n v_cmp_lt_u64_e64 %1, %5, %4\n v_cmp_lt_u64_e64 %2, %4, %5\n v_cmp_lt_u64_e64 %3, %5, %4\n"
+                         : "=&s"(s0), "=&s"(s1), "=&s"(s2), "=&s"(s3) : "v"(d0), "v"(d1));
+            m ^= s0 ^ s1 ^ s2 ^ s3;
+        } else if (KIND == 11) {  // v_min_f64 / v_max_f64: a compare-exchange of two records compared as doubles
+            double e0 = d0, e1 = d1, e2 = d0 + 1.0, e3 = d1 + 1.0, lo, hi;
+            asm volatile("v_min_f64 %4, %0, %1\n v_max_f64 %5, %0, %1\n v_min_f64 %0, %2, %3\n v_max_f64 %1, %2, %3\n"
+                         "v_min_f64 %2, %4, %0\n v_max_f64 %3, %5, %1\n v_min_f64 %0, %4, %5\n v_max_f64 %1, %2, %3\n"
+                         : "+v"(e0), "+v"(e1), "+v"(e2), "+v"(e3), "=&v"(lo), "=&v"(hi));
+            d0 = e0; d1 = e1;
+            a0 ^= (unsigned)__double2loint(e2) ^ (unsigned)__double2loint(e3);
         } else {                  // v_fma_f32 for reference
             float f0 = __uint_as_float(a0), f1 = __uint_as_float(a1), f2 = __uint_as_float(a2), f3 = __uint_as_float(a3);
             float f4 = __uint_as_float(a4), f5 = __uint_as_float(a5), f6 = __uint_as_float(a6), f7 = __uint_as_float(a7), g = 1.0001f;
@@ -93,5 +106,6 @@ int main()
     run<3>("v_cmp_lt_f64_e64", out); run<4>("v_mov_b32_dpp", out);
     run<6>("cmp_u32->vcc + 3 sel e32", out); run<7>("cmp_u32->sgpr + 3 sel e64", out);
     run<8>("CE f64: vcc + 6 sel e32", out); run<9>("CE f64: sgpr + 6 sel e64", out);
+    run<10>("v_cmp_lt_u64_e64", out); run<11>("v_min_f64 / v_max_f64", out);
     return 0;
 }
