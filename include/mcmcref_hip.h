@@ -190,7 +190,8 @@ int mcr_summarize_models(mcr_ctx* ctx, const mcr_model_desc* models, int n_model
 
 /* diagnostics.split_rhat / ess_bulk / ess_tail for ONE parameter given as possibly ragged
  * chains (src/mcmc_ref/diagnostics.py:13-73): `pooled` holds the chains back to back, chain c
- * is pooled[chain_off[c] .. chain_off[c+1]).  Host pointers.  out arrays have 1 entry.
+ * is pooled[chain_off[c] .. chain_off[c+1]), chain_off being C + 1 non-decreasing entries
+ * starting at 0.  Host pointers.  out arrays have 1 entry.
  * Optional debug outputs (host, length chain_off[C], may be NULL): z_bulk / z_tail =
  * _rank_normalize(x) / _rank_normalize(_fold_chains(x)) (diagnostics.py:93-133), rank_bulk /
  * rank_tail = the average ranks (exact multiples of 0.5). */

@@ -381,6 +381,19 @@ struct Carve {
     bool over() const { return off > end; }
 };
 
+// The chunk size of a call under the workspace limit: the largest k in [1, hi] that fits, 0 when not even 1 does.  fits
+// is monotone (k fits: so does every smaller count) and is asked about hi first -- a call that fits whole costs one
+// measurement.
+template <class Fits> i64 most_that_fit(i64 hi, Fits&& fits)
+{
+    if (hi < 1) return 0;
+    if (fits(hi)) return hi;
+    if (!fits(1)) return 0;
+    i64 lo = 1;                                              // lo fits, hi does not
+    while (hi - lo > 1) { const i64 mid = lo + (hi - lo) / 2; if (fits(mid)) lo = mid; else hi = mid; }
+    return lo;
+}
+
 // Tiling of the sort of M pooled draws
 struct WsPlan {
     i64 ntiles;
@@ -509,6 +522,13 @@ template <class Layout> int carve(mcr_ctx* ctx, DevBuf& buf, Layout&& layout)
     layout(cv);
     if (cv.over()) return fail(ctx, MCR_ENOMEM, "buffer layout needs %zu bytes; the buffer has %zu", cv.off, cv.end);
     return MCR_OK;
+}
+
+// Room in ctx->stage, the device copy of a host entry's arrays, for one buffer per byte count: ptr[i] is the i-th,
+// 256-byte aligned like everything carved.
+int stage_buffers(mcr_ctx* ctx, std::initializer_list<size_t> bytes, void** ptr)
+{
+    return carve(ctx, ctx->stage, [&](Carve& cv) { void** p = ptr; for (size_t b : bytes) *p++ = cv.take<char>(b); });
 }
 
 // One k_acov_seg pass of NT threads over SEG-draw segments: tier 1 (FIRST, every pair, lags 0..63, into a.rec) or tier 2
@@ -848,7 +868,7 @@ int prep_quantiles(mcr_ctx* ctx, const double* qs, int nq, i64 M, QArgs& q, i64*
 constexpr int res_fields(int nq) { return R_Q0 + nq; }
 
 template <typename T>
-int launch_ingest(mcr_ctx* ctx, const void* src, double* X, i64 C, i64 N, i64 pc, i64 sc, i64 sn, i64 sp, i64 p0)
+int launch_ingest_as(mcr_ctx* ctx, const void* src, double* X, i64 C, i64 N, i64 pc, i64 sc, i64 sn, i64 sp, i64 p0)
 {
     if (sp == 1 && sn != 1 && pc > 1) {
         const i64 nb = (N + 63) / 64;
@@ -860,6 +880,11 @@ int launch_ingest(mcr_ctx* ctx, const void* src, double* X, i64 C, i64 N, i64 pc
                (const T*)src, X, C, N, sc, sn, sp, p0);
     }
     return MCR_OK;
+}
+int launch_ingest(mcr_ctx* ctx, const void* src, int dtype, double* X, i64 C, i64 N, i64 pc, i64 sc, i64 sn, i64 sp, i64 p0)
+{
+    return dtype == MCR_F64 ? launch_ingest_as<double>(ctx, src, X, C, N, pc, sc, sn, sp, p0)
+                            : launch_ingest_as<float>(ctx, src, X, C, N, pc, sc, sn, sp, p0);
 }
 
 void fill_nan(const mcr_summary& o, i64 P, int nq)
@@ -917,7 +942,7 @@ int check_common(mcr_ctx* ctx, const void* draws, int dtype, i64 C, i64 N, i64 P
 }
 
 // How a call of this shape is cut into workspace chunks of parameters (a pure function of the shape, the workspace limit
-// and MCR_FFT): shared by enqueue_impl and mcr_plan_chunks.
+// and MCR_FFT): shared by run_summary and mcr_plan_chunks.
 struct ChunkPlan { bool ingest = false; FftPlan fp{}; i64 pcmax = 0; size_t bytes = 0; };
 
 // The chain structure of a call as the kernels see it next to the offset table: C chains, M pooled draws, n = the
@@ -949,11 +974,13 @@ ChainShape shape_offsets(const i64* off, i64 C)
     return h;
 }
 
-int plan_chunks(mcr_ctx* ctx, const ChainShape& h, i64 P, bool ingest, bool do_diag, ChunkPlan& cp)
+// fft_slot_cap > 0: the FFT tier gets at most that many slots (a caller that knows how few pairs it can list).
+int plan_chunks(mcr_ctx* ctx, const ChainShape& h, i64 P, bool ingest, bool do_diag, ChunkPlan& cp, int fft_slot_cap = 0)
 {
     const i64 M = h.M, C = h.C;
     cp.ingest = ingest;
     cp.fp = plan_fft(h.n, (int)C, do_diag && ctx->fft_on);
+    if (fft_slot_cap > 0 && cp.fp.slots > fft_slot_cap) cp.fp.slots = fft_slot_cap;
     auto fft_bytes = [&]() {
         PipeIn a{};
         Carve m{nullptr};
@@ -973,19 +1000,12 @@ int plan_chunks(mcr_ctx* ctx, const ChainShape& h, i64 P, bool ingest, bool do_d
         if (cp.fp.slots <= 1) { cp.fp = FftPlan{}; break; }
         cp.fp.slots /= 2;
     }
-    i64 lo = 1, hi = P < kMaxGridY / 2 ? P : kMaxGridY / 2;   // k_acov_seg uses grid.z = 2 * pc
-    cp.bytes = measure(hi);
-    if (cp.bytes > ctx->ws_limit) {                          // (the common case fits at once: no search)
-        if (measure(1) > ctx->ws_limit)
-            return fail(ctx, MCR_ENOMEM, "one parameter needs %zu bytes of workspace (%zu of them for the FFT tier); limit is %zu",
-                        measure(1), fft_bytes(), ctx->ws_limit);
-        while (lo < hi) {                                    // the most parameters whose layout fits the limit
-            const i64 mid = lo + (hi - lo + 1) / 2;
-            if (measure(mid) <= ctx->ws_limit) lo = mid; else hi = mid - 1;
-        }
-        cp.bytes = measure(lo);
-    }
-    cp.pcmax = hi;
+    // the most parameters whose layout fits the limit; k_acov_seg uses grid.z = 2 * pc
+    cp.pcmax = most_that_fit(P < kMaxGridY / 2 ? P : kMaxGridY / 2, [&](i64 pc) { return measure(pc) <= ctx->ws_limit; });
+    if (!cp.pcmax)
+        return fail(ctx, MCR_ENOMEM, "one parameter needs %zu bytes of workspace (%zu of them for the FFT tier); limit is %zu",
+                    measure(1), fft_bytes(), ctx->ws_limit);
+    cp.bytes = measure(cp.pcmax);
     return MCR_OK;
 }
 
@@ -1004,21 +1024,16 @@ int get_tables(mcr_ctx* ctx, PipeIn& a, const FftPlan& fp, bool ztab)
     return (!rc && ztab) ? get_ztab(ctx, a.M, &a.ztab) : rc;
 }
 
-// A result slot's lifecycle: fill_slot describes the call it serves (the caller picks slot and lane), commit_slot records
-// its completion event behind the call's work on the current lane and puts it in flight.
-Slot& fill_slot(mcr_ctx* ctx, int si, const mcr_summary* out, i64 P, i64 M, int nq)
+// Acceptance of a chain offset table of C + 1 entries: it is there, starts at 0, never decreases, and the pooled length
+// fits the rank codes (2M - 1 of them in u32).
+int check_chain_table(mcr_ctx* ctx, const i64* chain_off, i64 C)
 {
-    Slot& s = ctx->slots[si];
-    s.out = *out; s.P = P; s.nq = nq; s.trivial_nan = (M == 0 || P == 0);
-    s.pcmax = P;
-    return s;
-}
-int commit_slot(mcr_ctx* ctx, int si)
-{
-    Slot& s = ctx->slots[si];
-    if (!s.done) HIP_TRY(ctx, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-    HIP_TRY(ctx, hipEventRecord(s.done, ctx->stream));
-    ctx->order.push_back(si);
+    if (C <= 0) return MCR_OK;
+    if (!chain_off) return fail(ctx, MCR_EINVAL, "chain_off is NULL");
+    if (chain_off[0] != 0) return fail(ctx, MCR_EINVAL, "chain_off[0] must be 0");
+    for (i64 c = 0; c < C; ++c)
+        if (chain_off[c + 1] < chain_off[c]) return fail(ctx, MCR_EINVAL, "chain_off must be non-decreasing");
+    if (chain_off[C] >= (i64)0x7FFFFFFFll) return fail(ctx, MCR_EINVAL, "pooled length out of range");
     return MCR_OK;
 }
 
@@ -1033,62 +1048,69 @@ int check_chains(mcr_ctx* ctx, const void* draws, const i64* chain_off, i64 C, i
     if (C < min_chains)
         return fail(ctx, MCR_EMINCHAINS, "diagnostics require at least %d chains; got %lld chain(s)", min_chains, (long long)C);
     if (C > kMaxChains) return fail(ctx, MCR_EINVAL, "at most %d chains are supported; got %lld", kMaxChains, (long long)C);
-    if (C > 0 && !chain_off) return fail(ctx, MCR_EINVAL, "chain_off is NULL");
+    const int rc = check_chain_table(ctx, chain_off, C);
+    if (rc) return rc;
     const i64 M = C > 0 ? chain_off[C] : 0;
-    if (C > 0 && chain_off[0] != 0) return fail(ctx, MCR_EINVAL, "chain_off[0] must be 0");
-    for (i64 c = 0; c < C; ++c)
-        if (chain_off[c + 1] < chain_off[c]) return fail(ctx, MCR_EINVAL, "chain_off must be non-decreasing");
-    if (M < 0 || M >= (i64)0x7FFFFFFFll) return fail(ctx, MCR_EINVAL, "pooled length out of range");
     if (P > 1 && M > 0 && sp < M) return fail(ctx, MCR_EINVAL, "stride_p must be at least the pooled length");
     if (!draws && M * P > 0) return fail(ctx, MCR_EINVAL, "draws is NULL");
     return MCR_OK;
 }
 
-// One summary call on a free slot and the next lane.  !ragged: a rectangular tensor (C, N, strides), chain c at c * N --
-// the offset table stays resident in the slot between calls of one shape.  ragged: f64 draws with the chains back to
-// back as chain_off says (host, C + 1 entries), parameter p at draws_dev + p * sp; N, sc and sn are unused and the table
-// goes up with the call.
-int enqueue_impl(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i64 P, i64 sc, i64 sn, i64 sp,
-                 const i64* chain_off, bool ragged, int min_chains, const double* quantiles, int nq,
-                 const mcr_summary* out)
+// One summary call.  !ragged: a rectangular tensor (C, N, strides), chain c at c * N -- the offset table stays resident
+// in the slot between calls of one shape.  ragged: f64 draws with the chains back to back as chain_off says (host, C + 1
+// entries), parameter p at draws_dev + p * sp; N, sc and sn are unused and the table goes up with the call.  The members
+// with a default are what mcr_diagnose_chains asks for.
+struct SummaryCall {
+    const void* draws_dev; int dtype; i64 C, N, P, sc, sn, sp;
+    const i64* chain_off; bool ragged;
+    int min_chains; const double* quantiles; int nq; const mcr_summary* out;
+    int slot = -1;              // >= 0: that slot on the current lane, next_slot stays (else: a free slot and the next lane)
+    bool always_diag = false;   // the rank and diagnostics kernels whatever `out` asks for
+    bool may_fork = true;       // a lone call may put its bulk half on the lane's second stream (ctx->fork_lone)
+    int fft_slot_cap = 0;       // > 0: at most so many FFT slots (plan_chunks)
+    PipeIn* last = nullptr;     // receives the last chunk's pipeline: its rank codes and the z table
+};
+
+// An accepted call (the context's device is current): shape, quantiles, slot and lane, the chunk plan, the offset table,
+// the chunks, the result copy, and the slot goes in flight.
+int run_summary(mcr_ctx* ctx, const SummaryCall& c)
 {
-    int rc = ragged ? check_chains(ctx, draws_dev, chain_off, C, P, sp, min_chains, out)
-                    : check_common(ctx, draws_dev, dtype, C, N, P, min_chains, out);
-    if (rc) return rc;
-    if (ctx->order.size() >= MCR_MAX_INFLIGHT) return fail(ctx, MCR_EINVAL, "more than %d summaries in flight", MCR_MAX_INFLIGHT);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const ChainShape h = ragged ? shape_offsets(chain_off, C) : shape_regular(C, N);
+    const i64 C = c.C, N = c.N, P = c.P;
+    const bool ragged = c.ragged;
+    const ChainShape h = ragged ? shape_offsets(c.chain_off, C) : shape_regular(C, N);
     const i64 M = h.M;
-    int si = -1;
-    for (int k = 0; k < MCR_MAX_INFLIGHT; ++k) {
-        const int c = (ctx->next_slot + k) % MCR_MAX_INFLIGHT;
-        if (std::find(ctx->order.begin(), ctx->order.end(), c) == ctx->order.end()) { si = c; break; }
+    int si = c.slot;
+    for (int k = 0; si < 0 && k < MCR_MAX_INFLIGHT; ++k) {
+        const int f = (ctx->next_slot + k) % MCR_MAX_INFLIGHT;
+        if (std::find(ctx->order.begin(), ctx->order.end(), f) == ctx->order.end()) si = f;
     }
     QArgs q;
-    rc = prep_quantiles(ctx, quantiles, nq, M, q, ctx->slots[si].qlo);
+    int rc = prep_quantiles(ctx, c.quantiles, c.nq, M, q, ctx->slots[si].qlo);
     if (rc) return rc;
-    use_lane(ctx, si % ctx->n_lanes);
-    Slot& s = fill_slot(ctx, si, out, P, M, nq);
+    if (c.slot < 0) use_lane(ctx, si % ctx->n_lanes);
+    Slot& s = ctx->slots[si];           // the call this slot serves
+    s.out = *c.out; s.P = P; s.nq = c.nq; s.trivial_nan = (M == 0 || P == 0); s.pcmax = P;
     if (!s.trivial_nan) {
-        const bool do_diag = out->rhat || out->rhat_bulk || out->rhat_tail || out->ess_bulk || out->ess_tail ||
-                             out->lag_bulk || out->lag_tail;
+        const mcr_summary* out = c.out;
+        const bool do_diag = c.always_diag || out->rhat || out->rhat_bulk || out->rhat_tail || out->ess_bulk ||
+                             out->ess_tail || out->lag_bulk || out->lag_tail;
         // the ingest pass sees a ragged parameter as one row of M draws
-        const i64 iC = ragged ? 1 : C, iN = ragged ? M : N, isc = ragged ? M : sc, isn = ragged ? 1 : sn;
+        const i64 iC = ragged ? 1 : C, iN = ragged ? M : N, isc = ragged ? M : c.sc, isn = ragged ? 1 : c.sn;
         ChunkPlan cp;
-        rc = plan_chunks(ctx, h, P, needs_ingest(iC, iN, P, isc, isn, sp), do_diag, cp);
+        rc = plan_chunks(ctx, h, P, needs_ingest(iC, iN, P, isc, isn, c.sp), do_diag, cp, c.fft_slot_cap);
         if (rc) return rc;
         const i64 pcmax = s.pcmax = cp.pcmax;
         rc = lane_ws(ctx).reserve(ctx, cp.bytes);
         if (rc) return rc;
-        const int R = res_fields(nq);
+        const int R = res_fields(c.nq);
         rc = ensure_slot(ctx, s, (size_t)R * (size_t)P, (size_t)C + 1);
         if (rc) return rc;
         const bool off_resident = !ragged && s.off_C == C && s.off_N == N;
         if (ragged) {
-            memcpy(s.h_off.p, chain_off, sizeof(i64) * (size_t)(C + 1));
+            memcpy(s.h_off.p, c.chain_off, sizeof(i64) * (size_t)(C + 1));
             s.off_C = s.off_N = -1;
         } else if (!off_resident) {
-            for (i64 c = 0; c <= C; ++c) s.h_off.as<i64>()[c] = c * N;
+            for (i64 k = 0; k <= C; ++k) s.h_off.as<i64>()[k] = k * N;
         }
         PipeIn call{};                  // the fields every chunk shares
         call.M = M; call.C = (int)C; call.d_off = s.d_off.as<i64>(); call.n = h.n; call.nh = h.nh; call.q = q;
@@ -1105,33 +1127,46 @@ int enqueue_impl(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i
             double* X = carve_pipe(cv, a, true, cp.fp, cp.ingest);
             if (cv.over()) return fail(ctx, MCR_ENOMEM, "workspace layout needs %zu bytes; the workspace has %zu", cv.off, cv.end);
             // (the per-kernel event pairs of the profiling mode keep the single stream)
-            a.fork = ctx->fork_lone && ctx->order.empty() && !ctx->prof && P <= pcmax &&
+            a.fork = c.may_fork && ctx->fork_lone && ctx->order.empty() && !ctx->prof && P <= pcmax &&
                      (double)M * (double)pc >= 2e6 && (double)M * (double)pc <= 8e6;    // kernels long enough to be worth
                                                // three more launches and two event waits (measured: C1 4 M param-draws 306 -> 288 us,
                                                // 10 x 1000 x 45 149 -> 166, 4 x 1000 x 10 124 -> 133), short enough not to fill the chip
             if (cp.ingest) {
-                rc = (dtype == MCR_F64) ? launch_ingest<double>(ctx, draws_dev, X, iC, iN, pc, isc, isn, sp, p0)
-                                        : launch_ingest<float>(ctx, draws_dev, X, iC, iN, pc, isc, isn, sp, p0);
+                rc = launch_ingest(ctx, c.draws_dev, c.dtype, X, iC, iN, pc, isc, isn, c.sp, p0);
                 if (rc) return rc;
                 a.X = X;
             } else {
-                a.x_f32 = dtype == MCR_F32;
+                a.x_f32 = c.dtype == MCR_F32;
                 a.records = a.x_f32 && a.bk_B > 0 && ctx->f32_records;
-                a.X = a.x_f32 ? (const void*)(reinterpret_cast<const float*>(draws_dev) + p0 * M)
-                              : (const void*)(reinterpret_cast<const double*>(draws_dev) + p0 * M);
+                a.X = a.x_f32 ? (const void*)(reinterpret_cast<const float*>(c.draws_dev) + p0 * M)
+                              : (const void*)(reinterpret_cast<const double*>(c.draws_dev) + p0 * M);
             }
             a.d_res = s.d_res.as<double>() + (size_t)R * (size_t)p0;
             rc = run_pipeline(ctx, a);
             if (rc) return rc;
+            if (c.last) *c.last = a;
         }
         HIP_TRY(ctx, hipMemcpyAsync(s.h_res.p, s.d_res.p, sizeof(double) * (size_t)R * (size_t)P, hipMemcpyDeviceToHost,
                                     ctx->stream));
     }
     if (!s.trivial_nan && !ragged) { s.off_C = C; s.off_N = N; }
-    rc = commit_slot(ctx, si);
-    if (rc) return rc;
-    ctx->next_slot = (si + 1) % MCR_MAX_INFLIGHT;
+    // the slot's completion event behind the call's work on its lane: the slot is in flight
+    if (!s.done) HIP_TRY(ctx, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+    HIP_TRY(ctx, hipEventRecord(s.done, ctx->stream));
+    ctx->order.push_back(si);
+    if (c.slot < 0) ctx->next_slot = (si + 1) % MCR_MAX_INFLIGHT;
     return MCR_OK;
+}
+
+// A summary call on a free slot and the next lane: acceptance, then the shared path.
+int enqueue_impl(mcr_ctx* ctx, const SummaryCall& c)
+{
+    const int rc = c.ragged ? check_chains(ctx, c.draws_dev, c.chain_off, c.C, c.P, c.sp, c.min_chains, c.out)
+                            : check_common(ctx, c.draws_dev, c.dtype, c.C, c.N, c.P, c.min_chains, c.out);
+    if (rc) return rc;
+    if (ctx->order.size() >= MCR_MAX_INFLIGHT) return fail(ctx, MCR_EINVAL, "more than %d summaries in flight", MCR_MAX_INFLIGHT);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return run_summary(ctx, c);
 }
 
 // Waits for a slot's completion event.  The host polls the event for a while before it blocks in the runtime: a blocking
@@ -1400,7 +1435,7 @@ int mcr_summarize_enqueue(mcr_ctx* ctx, const void* draws_dev, int dtype, int64_
                           int64_t sc, int64_t sn, int64_t sp, int min_chains, const double* quantiles, int n_q,
                           mcr_summary* out)
 {
-    const int rc = enqueue_impl(ctx, draws_dev, dtype, C, N, P, sc, sn, sp, nullptr, false, min_chains, quantiles, n_q, out);
+    const int rc = enqueue_impl(ctx, SummaryCall{draws_dev, dtype, C, N, P, sc, sn, sp, nullptr, false, min_chains, quantiles, n_q, out});
     if (rc && ctx && rc != MCR_EMINCHAINS && rc != MCR_EMINCHAINS_ARG && rc != MCR_EINVAL) return drain(ctx, rc, true);
     return rc;
 }
@@ -1408,8 +1443,8 @@ int mcr_summarize_enqueue(mcr_ctx* ctx, const void* draws_dev, int dtype, int64_
 int mcr_summarize_chains_enqueue(mcr_ctx* ctx, const double* draws_dev, int64_t stride_p, const int64_t* chain_off, int C,
                                  int64_t P, int min_chains, const double* quantiles, int n_q, mcr_summary* out)
 {
-    const int rc = enqueue_impl(ctx, draws_dev, MCR_F64, C, 0, P, 0, 1, stride_p, reinterpret_cast<const i64*>(chain_off), true,
-                                min_chains, quantiles, n_q, out);
+    const int rc = enqueue_impl(ctx, SummaryCall{draws_dev, MCR_F64, C, 0, P, 0, 1, stride_p, reinterpret_cast<const i64*>(chain_off),
+                                                 true, min_chains, quantiles, n_q, out});
     if (rc && ctx && rc != MCR_EMINCHAINS && rc != MCR_EMINCHAINS_ARG && rc != MCR_EINVAL) return drain(ctx, rc, true);
     return rc;
 }
@@ -1426,14 +1461,13 @@ int mcr_plan_chunks_chains(mcr_ctx* ctx, const int64_t* chain_off, int C, int64_
                            int64_t* params_per_chunk)
 {
     if (!ctx || !params_per_chunk) return fail(ctx, MCR_EINVAL, "mcr_plan_chunks_chains: NULL argument");
-    if (C < 0 || C > kMaxChains || (C > 0 && !chain_off))
-        return fail(ctx, MCR_EINVAL, "mcr_plan_chunks_chains: bad chain table");
-    for (int c = 0; c < C; ++c)
-        if (chain_off[c + 1] < chain_off[c]) return fail(ctx, MCR_EINVAL, "chain_off must be non-decreasing");
-    if (C == 0 || P <= 0 || chain_off[C] <= 0) { *params_per_chunk = 0; return MCR_OK; }
-    if (chain_off[C] >= (i64)0x7FFFFFFFll) return fail(ctx, MCR_EINVAL, "pooled length out of range");
+    if (C < 0 || C > kMaxChains) return fail(ctx, MCR_EINVAL, "mcr_plan_chunks_chains: bad chain count %d", C);
+    const i64* off = reinterpret_cast<const i64*>(chain_off);
+    int rc = check_chain_table(ctx, off, C);
+    if (rc) return rc;
+    if (C == 0 || P <= 0 || off[C] == 0) { *params_per_chunk = 0; return MCR_OK; }
     ChunkPlan cp;
-    const int rc = plan_chunks(ctx, shape_offsets(reinterpret_cast<const i64*>(chain_off), C), P, false, diagnostics != 0, cp);
+    rc = plan_chunks(ctx, shape_offsets(off, C), P, false, diagnostics != 0, cp);
     if (rc) return rc;
     *params_per_chunk = cp.pcmax;
     return MCR_OK;
@@ -1484,8 +1518,9 @@ int mcr_summarize(mcr_ctx* ctx, const void* draws, int dtype, int64_t C, int64_t
     if (ext < 0) return fail(ctx, MCR_EINVAL, "negative strides are not supported");
     const size_t es = dtype == MCR_F64 ? 8 : 4;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    void* X = ctx->stage.p;
     if (ext > 0) {
-        rc = ctx->stage.reserve(ctx, (size_t)ext * es);
+        rc = stage_buffers(ctx, {(size_t)ext * es}, &X);
         if (rc) return rc;
     }
     // Parameter-major tensors (the Arrow column layout) of some size go up in a few pieces: while piece k + 1
@@ -1500,95 +1535,59 @@ int mcr_summarize(mcr_ctx* ctx, const void* draws, int dtype, int64_t C, int64_t
             const i64 p0 = P * k / pieces, p1 = P * (k + 1) / pieces, pc = p1 - p0;
             const size_t b0 = (size_t)p0 * (size_t)sp * es;
             const size_t bytes = (size_t)tensor_extent(C, N, pc, sc, sn, sp) * es;
-            hipError_t e = hipMemcpyAsync(ctx->stage.as<char>() + b0, (const char*)draws + b0, bytes, hipMemcpyHostToDevice, ctx->copy_stream);
+            hipError_t e = hipMemcpyAsync((char*)X + b0, (const char*)draws + b0, bytes, hipMemcpyHostToDevice, ctx->copy_stream);
             if (e == hipSuccess) e = hipStreamSynchronize(ctx->copy_stream);
             if (e != hipSuccess) { rc = fail(ctx, MCR_EHIP, "upload failed: %s", hipGetErrorString(e)); break; }
             mcr_summary o = summary_at(*out, p0, n_q > 0 ? n_q : 0);
-            rc = mcr_summarize_enqueue(ctx, ctx->stage.as<char>() + b0, dtype, C, N, pc, sc, sn, sp, min_chains, quantiles, n_q, &o);
+            rc = mcr_summarize_enqueue(ctx, (char*)X + b0, dtype, C, N, pc, sc, sn, sp, min_chains, quantiles, n_q, &o);
         }
         return drain(ctx, rc);
     }
     if (ext > 0) {
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->stage.p, draws, (size_t)ext * es, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(X, draws, (size_t)ext * es, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // the pipeline may run on the other lane
     }
-    return mcr_summarize_dev(ctx, ctx->stage.p, dtype, C, N, P, sc, sn, sp, min_chains, quantiles, n_q, out);
+    return mcr_summarize_dev(ctx, X, dtype, C, N, P, sc, sn, sp, min_chains, quantiles, n_q, out);
 }
 
 int mcr_diagnose_chains(mcr_ctx* ctx, const double* pooled, const int64_t* chain_off, int C, int min_chains,
                         mcr_summary* out, double* z_bulk, double* z_tail, double* rank_bulk, double* rank_tail)
 {
-    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
-    if (!out) return fail(ctx, MCR_EINVAL, "out is NULL");
-    if (C < 0) return fail(ctx, MCR_EINVAL, "negative chain count");
-    if (min_chains < 1) return fail(ctx, MCR_EMINCHAINS_ARG, "min_chains must be >= 1; got %d", min_chains);
-    if (C < min_chains) return fail(ctx, MCR_EMINCHAINS, "diagnostics require at least %d chains; got %d chain(s)", min_chains, C);
-    if (C > kMaxChains) return fail(ctx, MCR_EINVAL, "at most %d chains are supported; got %d", kMaxChains, C);
-    if (C > 0 && !chain_off) return fail(ctx, MCR_EINVAL, "chain_off is NULL");
+    const i64* off = reinterpret_cast<const i64*>(chain_off);
+    int rc = check_chains(ctx, pooled, off, C, 1, 0, min_chains, out);
+    if (rc) return rc;
     if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "mcr_diagnose_chains with summaries in flight");
-    const i64 M = C > 0 ? chain_off[C] : 0;
-    if (M < 0 || M >= (i64)0x7FFFFFFFll) return fail(ctx, MCR_EINVAL, "pooled length out of range");
-    i64 n = 0, nh = 0;
-    bool have_h = false;
-    for (int c = 0; c < C; ++c) {
-        const i64 len = chain_off[c + 1] - chain_off[c];
-        if (len < 0) return fail(ctx, MCR_EINVAL, "chain_off must be non-decreasing");
-        if (c == 0 || len < n) n = len;
-        if (len >= 2) { if (!have_h || len / 2 < nh) nh = len / 2; have_h = true; }
-    }
-    if (M > 0 && !pooled) return fail(ctx, MCR_EINVAL, "pooled is NULL");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    Slot& s = fill_slot(ctx, 0, out, 1, M, 0);     // slot 0 on the current lane; next_slot stays
-    if (s.trivial_nan) { const int rc = commit_slot(ctx, 0); return rc ? rc : wait_impl(ctx); }
-    const bool want_dbg = z_bulk || z_tail || rank_bulk || rank_tail;
-    i64 nstage = n > 0 ? n : 1;
-    for (int c = 0; c < C; ++c) {
-        const i64 len = chain_off[c + 1] - chain_off[c];
-        if (len >= 2 && len / 2 + nh > nstage) nstage = len / 2 + nh;
-    }
-    FftPlan fp = plan_fft(n, C, ctx->fft_on);
-    fp.slots = fp.on ? 2 : 0;                       // one parameter: two (parameter, kind) pairs at most
-    PipeIn a{};
-    a.M = M; a.pc = 1; a.C = C; a.n = n; a.nh = nh; a.q.nq = 0; a.nstage = nstage;
-    double* X = nullptr;
-    double* dbg[4] = {nullptr, nullptr, nullptr, nullptr};     // z_bulk, z_tail, rank_bulk, rank_tail (decoded codes)
+    const i64 M = C > 0 ? off[C] : 0;
+    const size_t row = sizeof(double) * (size_t)M;
     double* const dst[4] = {z_bulk, z_tail, rank_bulk, rank_tail};
-    auto layout = [&](Carve& cv) {
-        X = carve_pipe(cv, a, true, fp, true);
-        if (want_dbg) for (int i = 0; i < 4; ++i) dbg[i] = cv.take<double>((size_t)M);
-    };
-    auto measure = [&]() { Carve m{nullptr}; layout(m); return m.off; };
-    if (fp.on && measure() > ctx->ws_limit) fp = FftPlan{};
-    if (measure() > ctx->ws_limit) return fail(ctx, MCR_ENOMEM, "workspace limit too small for %lld draws", M);
-    int rc = carve(ctx, lane_ws(ctx), layout);
-    if (rc) return rc;
-    const int R = res_fields(0);
-    rc = ensure_slot(ctx, s, (size_t)R, (size_t)C + 1);
-    if (rc) return rc;
-    s.off_C = s.off_N = -1;
-    memcpy(s.h_off.p, chain_off, sizeof(i64) * (size_t)(C + 1));
-    HIP_TRY(ctx, hipMemcpyAsync(s.d_off.p, s.h_off.p, sizeof(i64) * (size_t)(C + 1), hipMemcpyHostToDevice, ctx->stream));
-    a.d_off = s.d_off.as<i64>();
-    rc = get_tables(ctx, a, fp, true);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(X, pooled, sizeof(double) * (size_t)M, hipMemcpyHostToDevice, ctx->stream));
-    a.X = X;
-    a.d_res = s.d_res.as<double>();
-    rc = run_pipeline(ctx, a);
-    if (rc) { abort_inflight(ctx); return rc; }
-    HIP_TRY(ctx, hipMemcpyAsync(s.h_res.p, s.d_res.p, sizeof(double) * (size_t)R, hipMemcpyDeviceToHost, ctx->stream));
-    if (want_dbg) {
-        const unsigned nb = (unsigned)((M + 255) / 256);
-        hipLaunchKernelGGL(k_decode_codes, dim3(nb), dim3(256), 0, ctx->stream, (const u32*)a.zb, (const double*)a.ztab, M,
-                           z_bulk ? dbg[0] : (double*)nullptr, rank_bulk ? dbg[2] : (double*)nullptr);
-        hipLaunchKernelGGL(k_decode_codes, dim3(nb), dim3(256), 0, ctx->stream, (const u32*)a.zt, (const double*)a.ztab, M,
-                           z_tail ? dbg[1] : (double*)nullptr, rank_tail ? dbg[3] : (double*)nullptr);
-        HIP_TRY(ctx, hipGetLastError());
+    const bool want_dbg = M > 0 && (z_bulk || z_tail || rank_bulk || rank_tail);
+    void* d[5] = {};                    // the draws; z_bulk, z_tail, rank_bulk, rank_tail (decoded codes)
+    if (M > 0) {
+        rc = want_dbg ? stage_buffers(ctx, {row, row, row, row, row}, d) : stage_buffers(ctx, {row}, d);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(d[0], pooled, row, hipMemcpyHostToDevice, ctx->stream));
     }
-    for (int i = 0; i < 4; ++i)
-        if (dst[i]) HIP_TRY(ctx, hipMemcpyAsync(dst[i], dbg[i], sizeof(double) * (size_t)M, hipMemcpyDeviceToHost, ctx->stream));
-    rc = commit_slot(ctx, 0);
-    return rc ? rc : wait_impl(ctx);
+    // one parameter of the ragged path, consumed where it lies: slot 0 on the current lane, diagnostics whatever `out`
+    // holds, and two (parameter, kind) pairs at most for the FFT tier
+    PipeIn a{};
+    SummaryCall c{d[0], MCR_F64, C, 0, 1, 0, 1, M, off, true, min_chains, nullptr, 0, out};
+    c.slot = 0; c.always_diag = true; c.may_fork = false; c.fft_slot_cap = 2; c.last = &a;
+    rc = run_summary(ctx, c);
+    if (!rc && want_dbg) {
+        auto decode = [&]() {
+            const unsigned nb = (unsigned)((M + 255) / 256);
+            auto dev = [&](int i) { return dst[i] ? (double*)d[1 + i] : (double*)nullptr; };
+            hipLaunchKernelGGL(k_decode_codes, dim3(nb), dim3(256), 0, ctx->stream, (const u32*)a.zb, (const double*)a.ztab, M, dev(0), dev(2));
+            hipLaunchKernelGGL(k_decode_codes, dim3(nb), dim3(256), 0, ctx->stream, (const u32*)a.zt, (const double*)a.ztab, M, dev(1), dev(3));
+            HIP_TRY(ctx, hipGetLastError());
+            for (int i = 0; i < 4; ++i)
+                if (dst[i]) HIP_TRY(ctx, hipMemcpyAsync(dst[i], d[1 + i], row, hipMemcpyDeviceToHost, ctx->stream));
+            return (int)MCR_OK;
+        };
+        rc = decode();
+    }
+    return drain(ctx, rc, rc != MCR_OK);
 }
 
 int mcr_moments_dev(mcr_ctx* ctx, const void* draws_dev, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc,
@@ -1644,10 +1643,11 @@ int mcr_basic_stats(mcr_ctx* ctx, const void* values, int dtype, int64_t n, doub
     if (!values) return fail(ctx, MCR_EINVAL, "values is NULL");
     const size_t es = dtype == MCR_F64 ? 8 : 4;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = ctx->stage.reserve(ctx, (size_t)n * es);
+    void* X = nullptr;
+    const int rc = stage_buffers(ctx, {(size_t)n * es}, &X);
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->stage.p, values, (size_t)n * es, hipMemcpyHostToDevice, ctx->stream));
-    return mcr_moments_dev(ctx, ctx->stage.p, dtype, 1, n, 1, n, 1, n, mean, std);
+    HIP_TRY(ctx, hipMemcpyAsync(X, values, (size_t)n * es, hipMemcpyHostToDevice, ctx->stream));
+    return mcr_moments_dev(ctx, X, dtype, 1, n, 1, n, 1, n, mean, std);
 }
 
 int mcr_compare(mcr_ctx* ctx, const double* ref, const double* actual, int64_t n, double tol, double* rel_error,
@@ -1796,14 +1796,10 @@ static int plan_sliced(mcr_ctx* ctx, i64 Mr, i64 Ma, i64 P, i64 K, i64& kc)
     const i64 Mmax = Mr > Ma ? Mr : Ma;                // k_project's one-dimensional grid: draw tiles x direction tiles < 2^31
     const i64 grid_cap = 0x7FFFFFFFll / (((Mmax + kProjTileM - 1) / kProjTileM + 7) / 8 * 8) * kProjTileK;
     if (K > grid_cap) K = grid_cap;
-    kc = K;
-    if (measure(K) <= ctx->ws_limit) return MCR_OK;
-    if (measure(1) > ctx->ws_limit)
+    kc = most_that_fit(K, [&](i64 k) { return measure(k) <= ctx->ws_limit; });
+    if (!kc)
         return fail(ctx, MCR_ENOMEM, "workspace limit too small: one direction needs %zu bytes, the limit is %zu", measure(1),
                     ctx->ws_limit);
-    i64 lo = 1, hi = K;           // measure(lo) fits, measure(hi) does not
-    while (hi - lo > 1) { const i64 mid = lo + (hi - lo) / 2; if (measure(mid) <= ctx->ws_limit) lo = mid; else hi = mid; }
-    kc = lo;
     return MCR_OK;
 }
 
@@ -1878,11 +1874,10 @@ int mcr_sliced_two_sample(mcr_ctx* ctx, const double* ref, int64_t Mr, const dou
     int rc = sliced_check(ctx, ref, Mr, act, Ma, P, dirs, center, K, ks, w1);
     if (rc || K == 0) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t rbytes = align_up((size_t)P * Mr * 8, 256);
-    rc = ctx->stage.reserve(ctx, rbytes + (size_t)P * Ma * 8);
+    void* X[2];
+    rc = stage_buffers(ctx, {sizeof(double) * (size_t)P * Mr, sizeof(double) * (size_t)P * Ma}, X);
     if (rc) return rc;
-    double* Xr = ctx->stage.as<double>();
-    double* Xa = (double*)(ctx->stage.as<char>() + rbytes);
+    double *Xr = (double*)X[0], *Xa = (double*)X[1];
     HIP_TRY(ctx, hipMemcpyAsync(Xr, ref, sizeof(double) * (size_t)P * Mr, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(Xa, act, sizeof(double) * (size_t)P * Ma, hipMemcpyHostToDevice, ctx->stream));
     return mcr_sliced_two_sample_dev(ctx, Xr, Mr, Xa, Ma, P, dirs, center, K, ks, w1, proj_ref, proj_act);
@@ -1927,17 +1922,10 @@ static int plan_nested(mcr_ctx* ctx, i64 C, i64 N, i64 P, i64 K, bool ingest, i6
     };
     const i64 nb = (C + kNestChains - 1) / kNestChains;
     const i64 grid_cap = ((i64)0x7FFFFFFF / nb) / 8 * 8;   // k_chain_moments: ceil(pc / 8) * 8 * nb workgroups
-    i64 lo = 1, hi = P < kMaxGridY / 2 ? P : kMaxGridY / 2;
+    i64 hi = P < kMaxGridY / 2 ? P : kMaxGridY / 2;
     if (hi > grid_cap) hi = grid_cap;
-    if (measure(hi) > ctx->ws_limit) {
-        if (measure(1) > ctx->ws_limit)
-            return fail(ctx, MCR_ENOMEM, "one parameter needs %zu bytes of workspace; limit is %zu", measure(1), ctx->ws_limit);
-        while (lo < hi) {
-            const i64 mid = lo + (hi - lo + 1) / 2;
-            if (measure(mid) <= ctx->ws_limit) lo = mid; else hi = mid - 1;
-        }
-    }
-    pcmax = hi;
+    pcmax = most_that_fit(hi, [&](i64 pc) { return measure(pc) <= ctx->ws_limit; });
+    if (!pcmax) return fail(ctx, MCR_ENOMEM, "one parameter needs %zu bytes of workspace; limit is %zu", measure(1), ctx->ws_limit);
     return MCR_OK;
 }
 
@@ -2004,8 +1992,7 @@ static int nested_run(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64
         if (rc) return rc;
         a.ztab = ztab;
         if (ingest) {
-            rc = (dtype == MCR_F64) ? launch_ingest<double>(ctx, draws_dev, w.X, C, N, pc, sc, sn, sp, p0)
-                                    : launch_ingest<float>(ctx, draws_dev, w.X, C, N, pc, sc, sn, sp, p0);
+            rc = launch_ingest(ctx, draws_dev, dtype, w.X, C, N, pc, sc, sn, sp, p0);
             if (rc) return rc;
             a.X = w.X;
         } else {
@@ -2078,8 +2065,7 @@ int mcr_nested_rhat_dev(mcr_ctx* ctx, const void* draws_dev, int dtype, int64_t 
     if (tensor_extent(C, N, P, sc, sn, sp) < 0) return fail(ctx, MCR_EINVAL, "negative strides are not supported");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     rc = nested_run(ctx, draws_dev, dtype, C, N, P, sc, sn, sp, perm, K, L, out);
-    if (rc) { char keep[sizeof ctx->err]; memcpy(keep, ctx->err, sizeof keep); abort_inflight(ctx); memcpy(ctx->err, keep, sizeof keep); }
-    return rc;
+    return rc ? drain(ctx, rc, true) : rc;
 }
 
 int mcr_nested_rhat(mcr_ctx* ctx, const void* draws, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc, int64_t sn,
@@ -2095,13 +2081,14 @@ int mcr_nested_rhat(mcr_ctx* ctx, const void* draws, int dtype, int64_t C, int64
     const i64 ext = tensor_extent(C, N, P, sc, sn, sp);
     if (ext < 0) return fail(ctx, MCR_EINVAL, "negative strides are not supported");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    void* X = ctx->stage.p;
     if (ext > 0) {
         const size_t es = dtype == MCR_F64 ? 8 : 4;
-        const int rc = ctx->stage.reserve(ctx, (size_t)ext * es);
+        const int rc = stage_buffers(ctx, {(size_t)ext * es}, &X);
         if (rc) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->stage.p, draws, (size_t)ext * es, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(X, draws, (size_t)ext * es, hipMemcpyHostToDevice, ctx->stream));
     }
-    return mcr_nested_rhat_dev(ctx, ctx->stage.p ? ctx->stage.p : draws, dtype, C, N, P, sc, sn, sp, superchain, out);
+    return mcr_nested_rhat_dev(ctx, X ? X : draws, dtype, C, N, P, sc, sn, sp, superchain, out);
 }
 
 // Device-resident form (draws_dev [P][M] f64, cov_dev [P][P] f64, both in this context's device memory): what
@@ -2160,10 +2147,10 @@ int mcr_covariance(mcr_ctx* ctx, const double* draws, int64_t M, int64_t P, doub
     if (P == 0) return MCR_OK;
     if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "mcr_covariance with summaries in flight");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = ctx->stage.reserve(ctx, (size_t)P * M * 8 + (size_t)P * P * 8 + 256);
+    void* buf[2];
+    int rc = stage_buffers(ctx, {sizeof(double) * (size_t)P * M, sizeof(double) * (size_t)P * P}, buf);
     if (rc) return rc;
-    double* X = ctx->stage.as<double>();
-    double* d_cov = (double*)(ctx->stage.as<char>() + align_up((size_t)P * M * 8, 256));
+    double *X = (double*)buf[0], *d_cov = (double*)buf[1];
     HIP_TRY(ctx, hipMemcpyAsync(X, draws, sizeof(double) * (size_t)P * M, hipMemcpyHostToDevice, ctx->stream));
     rc = mcr_covariance_dev(ctx, X, M, P, d_cov);
     if (rc) return rc;
@@ -3050,13 +3037,12 @@ int mcr_csv_write_dev(mcr_ctx* ctx, const mcr_pq_column* cols, int n_cols, int64
         // rows per range: all of them, or the most whole tiles whose layout fits the workspace limit
         const i64 step = J.tiling.R;
         i64 per = count;
-        if (count > 0 && (measure(count) > ctx->ws_limit || csvw::tile_count(J.tiling, count) > kCsvwMaxTiles)) {
+        if (count > 0) {
             auto fits = [&](i64 k) { const i64 nr = std::min(count, k * step); return measure(nr) <= ctx->ws_limit && csvw::tile_count(J.tiling, nr) <= kCsvwMaxTiles; };
-            if (!fits(1)) return fail(ctx, MCR_ENOMEM, "%s: %lld row(s) of %d columns need %zu bytes of workspace; limit is %zu", who, (long long)step,
-                                      n_cols, measure(std::min(count, step)), ctx->ws_limit);
-            i64 lo = 1, hi = (count + step - 1) / step;
-            while (lo < hi) { const i64 mid = lo + (hi - lo + 1) / 2; if (fits(mid)) lo = mid; else hi = mid - 1; }
-            per = lo * step;
+            const i64 k = most_that_fit((count + step - 1) / step, fits);
+            if (!k) return fail(ctx, MCR_ENOMEM, "%s: %lld row(s) of %d columns need %zu bytes of workspace; limit is %zu", who, (long long)step,
+                                n_cols, measure(std::min(count, step)), ctx->ws_limit);
+            per = std::min(count, k * step);
         }
         size_t used = 0;
         // room for `need` bytes of the image (or `hint`, when that is more), the first `used` kept
@@ -3623,8 +3609,8 @@ int fs_stats(mcr_ctx* ctx, const FileBatch& B, mcr_fileset& fs, Staged& S, int m
         mcr_summary o = summary_at(all, j.p0, n_q);
         if (ctx->order.size() >= MCR_MAX_INFLIGHT) rc = wait_one_impl(ctx);
         if (!rc)
-            rc = enqueue_impl(ctx, B.arena + B.f[(size_t)j.first].off, MCR_F64, j.C, j.N, j.P, j.N, 1, j.C * j.N, nullptr, false,
-                              diagnostics ? min_chains : 1, quantiles, n_q, &o);
+            rc = enqueue_impl(ctx, SummaryCall{B.arena + B.f[(size_t)j.first].off, MCR_F64, j.C, j.N, j.P, j.N, 1, j.C * j.N, nullptr, false,
+                                               diagnostics ? min_chains : 1, quantiles, n_q, &o});
     }
     return drain(ctx, rc);
 }

@@ -136,7 +136,7 @@ CASES = {
     "j": Case(2, 2097153, 2, 0.99, 1, "2^23 > limit: FFT off, direct rounds up to [1 048 576, 4 194 304)"),
 }
 WS_CASE = Case(4, 60000, 4, 0.995, 1, "workspace limits: slots 1, FFT dropped, chunks sharing 2 slots")
-RAGGED = (131073, 140000, 150000)       # diagnose_chains: n = 131 073 (2^19), C = 3, the route's fixed 2 slots
+RAGGED = (131073, 140000, 150000)       # diagnose_chains: n = 131 073 (2^19), C = 3, FFT slots capped at 2
 RAGGED_PHI, RAGGED_SEED = 0.99, 1
 MIXED = ("b", "f", "i")                 # one summarize_models call over three FFT sizes
 
@@ -305,7 +305,7 @@ def test_workspace_limit_halves_slots_and_drops_fft(oracles):
 
 def test_ragged_chains_fixed_two_slots_both_engines(engines, oracles):
     """mcr_diagnose_chains on three chains whose shortest has 131 073 draws: N = 2^19, an odd chain count, the ragged
-    route's fixed 2 slots (one parameter: both its pairs by FFT)."""
+    route's FFT slots capped at 2 (one parameter: both its pairs by FFT)."""
     chains, e = oracles.ragged()
     assert min(e["lag_bulk"], e["lag_tail"]) >= LAG2 - 1, e
     n, C = min(RAGGED), len(RAGGED)
