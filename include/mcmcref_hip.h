@@ -297,6 +297,68 @@ int mcr_nested_plan(mcr_ctx* ctx, int dtype, int64_t C, int64_t N, int64_t P, in
                     int64_t stride_p, int64_t K, int64_t* params_per_chunk);
 #define MCR_NESTED_MAX_CHAINS 1048576 /* chains of a mcr_nested_rhat call */
 #define MCR_NESTED_BLOCK 512          /* draws of a chain k_chain_moments keeps in registers for its second pass */
+/* Pareto k-hat: the tail diagnostic for the draws behind a mean and a std (Vehtari, Simpson, Gelman, Yao, Gabry, "Pareto
+ * smoothed importance sampling"; pareto_khat(tail = "both") / pareto_diags of the R package posterior, with Zhang and
+ * Stephens' (2009) profile fit, gpdfit).  ABSENT from the reference.  It estimates the shape k of a generalised Pareto
+ * distribution fitted to each tail: k < 0.5 the variance is finite and the central limit theorem holds; 0.5 <= k < 0.7 the
+ * mean estimate converges slowly and a std gate is not trustworthy; k >= 0.7 the estimate is unreliable; k >= 1 no mean
+ * exists.
+ * For one parameter, let x_(0) <= ... <= x_(M-1) be its M pooled draws in ascending order.  The chains are pooled and
+ * their structure plays no part.  Everything is IEEE double.
+ * Tail length.  Each parameter takes a requested length t_req >= 1 from the caller, or the default
+ *     t_req = ceil(3 * sqrt(M / r_eff))  when M > 225,  else  floor(M / 5)
+ * with r_eff = 1 when none is given.  mcr_pareto_tail_length(M, r_eff) computes the default on the host and needs no
+ * device.  It works in integers: the smallest t with t^2 * r_eff >= 9 M (t^2 exact, the product rounded once; capped at
+ * 2^31); it does not depend on how a floating-point sqrt rounds.  It returns 0 for M < 1 and MCR_EINVAL unless r_eff is
+ * finite and > 0.  The effective length is
+ *     t = min(max(t_req, 5), floor(M / 2))
+ * If t < 5, that is M < 10, both tails give NaN.
+ * Right tail.  Let cutoff = x_(M-t-1) and e_i = x_(M-t+i) - cutoff for i = 0 ... t-1.  The e_i are ascending and >= 0.
+ * Left tail.  This is the right tail of -x.  Let cutoff' = x_(t) and e_i = x_(t) - x_(t-1-i).  This is the same
+ * subtraction, so khat_left(x) and khat_right(-x) agree in bits.
+ * Fit of one tail of n = t exceedances:
+ *  1. If e_(n-1) == e_0, the tail is constant: khat = NaN.
+ *  2. Let G = 30 + floor(sqrt(n)) and xstar = e_(floor(n/4 + 0.5) - 1).  If xstar == 0: khat = +inf.
+ *     (From here on the e_i stand for 2^s e_i, the power of two that brings e_(n-1) into [1, 2), |s| <= 1000: an exact
+ *     scaling.  The fit is scale-free in exact arithmetic, but log(-theta_j / k_j) below is not in floating point; read
+ *     this way khat(x) and khat(2^m x) agree in bits.  Against the unscaled formulas the difference is rounding, ~1e-13.)
+ *  3. For j = 1 ... G:   theta_j = 1/e_(n-1) + (1 - sqrt(G / (j - 0.5))) / 3 / xstar
+ *                        k_j = (sum_i log1p(-theta_j e_i)) / n
+ *                        l_j = n (log(-theta_j / k_j) - k_j - 1)
+ *  4. Let w_j = exp(l_j - L), with L = m + log sum_j exp(l_j - m) and m = max_j l_j.  Then theta = sum_j theta_j w_j.
+ *  5. Let k = (sum_i log1p(-theta e_i)) / n.  Then khat = (k n + 5) / (n + 10).  This is the weakly informative prior:
+ *     mean 0.5, weight 10.
+ *  6. If khat is NaN it becomes +inf.
+ * Outputs per parameter: khat_left, khat_right, khat = max(khat_left, khat_right) with Python's max NaN ordering, as
+ * for rhat, and ndraws_tail, the effective t as an int64.
+ * Summation order.  Every sum over i and over j has one order that depends on n alone (for the j sums on G, itself a
+ * function of n): 64 partial sums, partial l adding the terms l, l + 64, ... in order, joined by the tree 32, 16, ... 1.
+ * A parameter's outputs therefore have the same bits alone or in a batch, at any place in the batch, under any workspace
+ * limit, in either layout, on the host entry or the device entry.  f32 draws are widened first by the ingest pass, as
+ * nested R-hat does; the answer is that of the f64 call on the widened tensor.
+ * draws: host tensor addressed like mcr_summarize's.  ndraws_tail: P requested lengths, or NULL for the default.
+ * Limits: any C, C * N < 2^31 - 1.  MCR_EINVAL (message names the cause): a negative dimension, a ndraws_tail entry < 1,
+ * summaries in flight, negative strides.  MCR_ENONFINITE: NaN / Inf draws.  M == 0 gives NaN (ndraws_tail 0), P == 0
+ * writes nothing.  The context stays usable after every error.  Synchronous.  A tail beyond MCR_PARETO_LDS_TAIL draws is
+ * fitted from global memory, and every tail by ONE workgroup: beyond ~10^5 draws a tail takes milliseconds. */
+typedef struct mcr_pareto { double *khat, *khat_left, *khat_right; int64_t* ndraws_tail; } mcr_pareto; /* P entries, NULL skipped */
+int mcr_pareto_khat(mcr_ctx* ctx, const void* draws, int dtype, int64_t C, int64_t N, int64_t P, int64_t stride_c,
+                    int64_t stride_n, int64_t stride_p, const int64_t* ndraws_tail /* P entries or NULL */, mcr_pareto* out);
+/* The same on draws in this ctx's device memory; ndraws_tail and out stay on the host. */
+int mcr_pareto_khat_dev(mcr_ctx* ctx, const void* draws_dev, int dtype, int64_t C, int64_t N, int64_t P, int64_t stride_c,
+                        int64_t stride_n, int64_t stride_p, const int64_t* ndraws_tail, mcr_pareto* out);
+/* Parameters per workspace chunk of such a call under the current workspace limit (0 for an empty shape).  MCR_ENOMEM
+ * when the limit does not fit one parameter. */
+int mcr_pareto_plan(mcr_ctx* ctx, int dtype, int64_t C, int64_t N, int64_t P, int64_t stride_c, int64_t stride_n,
+                    int64_t stride_p, int64_t* params_per_chunk);
+int64_t mcr_pareto_tail_length(int64_t M, double r_eff);                 /* host only */
+/* The same fit routine on an ascending host array (host only, no ctx; ndraws_tail 0 = the default, NULL outputs are
+ * skipped).  It runs the device's text in the device's summation order, but with the host's libm: log1p, log and exp
+ * are not the device's, so the results equal the device's to ~1e-13, not in bits.  MCR_EINVAL: M < 0, ndraws_tail < 0,
+ * a NULL array.  Non-finite entries are not looked for. */
+int mcr_pareto_fit_host(const double* sorted, int64_t M, int64_t ndraws_tail /* 0 = default */,
+                        double* khat_left, double* khat_right, int64_t* t_eff);
+#define MCR_PARETO_LDS_TAIL 8192      /* the longest tail k_pareto_fit stages in LDS */
 /* Population covariance matrix (ddof = 0, like compare.py:63) of P parameters over M pooled draws,
  * draws[P][M] host row-major -> cov[P][P].  The one dense contraction of the path: fp64 MFMA
  * (v_mfma_f64_16x16x4f64; LDS-staged 64 x 64 tiles, upper triangle, split over the draw axis).

@@ -31,6 +31,7 @@
 #include "mcr_fft.hpp"
 #include "mcr_ext.hpp"
 #include "mcr_nested.hpp"
+#include "mcr_pareto.hpp"
 #include "mcr_parquet.hpp"
 #include "mcr_pqwrite.hpp"
 #include "mcr_csvwrite.hpp"
@@ -62,7 +63,7 @@ enum KernelId {
     K_JSON_INDEX, K_JSON_SCAN, K_JSON_PARSE,
     K_LAYOUT_SCAN, K_LAYOUT_KEYS, K_LAYOUT_HIST, K_LAYOUT_OFFSETS, K_LAYOUT_SCATTER, K_LAYOUT_BOUNDS,
     K_PQW_ENCODE, K_PQW_COMPACT, K_CSVW_FORMAT, K_CSVW_SCAN, K_CSVW_COMPACT, K_SELECT_ROWS, K_PROJECT,
-    K_CHAIN_MOMENTS, K_NESTED_COMBINE, K_COUNT
+    K_CHAIN_MOMENTS, K_NESTED_COMBINE, K_PARETO_FIT, K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {
     "k_ingest", "k_moments", "k_moments_final", "k_tile_sort", "k_merge", "k_order_stats", "k_rank_z",
@@ -73,7 +74,7 @@ const char* const kKernelNames[K_COUNT] = {
     "k_json_index", "k_json_scan", "k_json_parse",
     "k_layout_scan", "k_layout_keys", "k_layout_hist", "k_layout_offsets", "k_layout_scatter", "k_layout_bounds",
     "k_pqw_encode", "k_pqw_compact", "k_csvw_format", "k_csvw_scan", "k_csvw_compact", "k_select_rows", "k_project",
-    "k_chain_moments", "k_nested_combine"};
+    "k_chain_moments", "k_nested_combine", "k_pareto_fit"};
 
 struct EvPair { hipEvent_t a, b; int kid; };
 
@@ -189,6 +190,8 @@ struct mcr_ctx {
     double rho_band = kRhoBand;   // MCR_RHO_BAND: half-width of the guard band of the tier-3 scan (0 = decide on the raw values)
     DevBuf nest_dev{4};                // mcr_nested_rhat: chain permutation + result table
     PinBuf nest_host{4};               // its results on the host
+    DevBuf pareto_dev{4};              // mcr_pareto_khat: tail lengths + result table
+    PinBuf pareto_host{4};             // its results on the host
     DevBuf guard_count;                // device counters (2 unsigned): band lags re-derived the reference's way (mcr_rho_guard_count),
                                        // tiles the tile sort sorted as pairs after all (mcr_tile_fallback_count)
 };
@@ -785,8 +788,8 @@ int launch_fold(mcr_ctx* ctx, const PipeIn& a, const Sorted& s)
     return MCR_OK;
 }
 
-// The whole per-chunk pipeline on ctx->stream.  M >= 1, pc >= 1.
-int run_pipeline(mcr_ctx* ctx, PipeIn& a)
+// The whole per-chunk pipeline on ctx->stream.  M >= 1, pc >= 1.  sorted_out (optional): what the sort stage left.
+int run_pipeline(mcr_ctx* ctx, PipeIn& a, Sorted* sorted_out = nullptr)
 {
     const i64 M = a.M, pc = a.pc;
     const unsigned py = (unsigned)pc;
@@ -796,6 +799,7 @@ int run_pipeline(mcr_ctx* ctx, PipeIn& a)
         const int rc = sort_stage(ctx, a, so);
         if (rc) return rc;
     }
+    if (sorted_out) *sorted_out = so;
     // 3. order statistics: with diagnostics, by the fold kernel itself; a launch of their own for Backend.stats calls
     if (!order_stats_in_fold(a)) {
         if (a.records) {
@@ -2089,6 +2093,228 @@ int mcr_nested_rhat(mcr_ctx* ctx, const void* draws, int dtype, int64_t C, int64
         HIP_TRY(ctx, hipMemcpyAsync(X, draws, (size_t)ext * es, hipMemcpyHostToDevice, ctx->stream));
     }
     return mcr_nested_rhat_dev(ctx, X ? X : draws, dtype, C, N, P, sc, sn, sp, superchain, out);
+}
+
+// ---- Pareto k-hat (mcr_pareto.hpp) --------------------------------------------------------------------------------------
+constexpr int kParField0 = R_Q0;                           // the pipeline runs without quantiles: its rows end here
+constexpr int kParFields = kParField0 + 2;                 // + khat_left, khat_right
+
+static_assert(kParetoLdsTail == MCR_PARETO_LDS_TAIL, "mcmcref_hip.h states the LDS tail");
+
+struct ParetoWs { double *X, *lg; };
+
+static PipeIn pareto_pipe(i64 M, i64 pc)
+{
+    PipeIn a{};
+    a.M = M; a.pc = pc; a.C = 1; a.n = 1; a.nh = 0; a.nstage = 1; a.q.nq = 0; a.do_diag = false;
+    return a;
+}
+
+// The workspace of a chunk of a.pc parameters: the sort alone (the stats-only layout), the split points k_order_stats
+// writes, and the grid values l_j of every tail.
+static void carve_pareto(Carve& cv, PipeIn& a, ParetoWs& w, bool ingest)
+{
+    w.X = carve_pipe(cv, a, false, FftPlan{}, ingest);
+    a.split = cv.take<i64>((size_t)a.pc);
+    w.lg = cv.take<double>((size_t)a.pc * 2 * (size_t)pareto_grid(a.M / 2));
+}
+
+// Parameters per workspace chunk of a Pareto call.
+static int plan_pareto(mcr_ctx* ctx, i64 M, i64 P, bool ingest, i64& pcmax)
+{
+    auto measure = [&](i64 pc) {
+        PipeIn a = pareto_pipe(M, pc);
+        ParetoWs w;
+        Carve m{nullptr};
+        carve_pareto(m, a, w, ingest);
+        return m.off;
+    };
+    pcmax = most_that_fit(P < kMaxGridY / 2 ? P : kMaxGridY / 2, [&](i64 pc) { return measure(pc) <= ctx->ws_limit; });
+    if (!pcmax) return fail(ctx, MCR_ENOMEM, "one parameter needs %zu bytes of workspace; limit is %zu", measure(1), ctx->ws_limit);
+    return MCR_OK;
+}
+
+// The default tail length: the smallest t with t^2 r_eff >= 9 M (that is ceil(3 sqrt(M / r_eff))) for M > 225, else
+// floor(M / 5).  A bisection over integers: t^2 is exact, its product with r_eff rounds once and is monotone in t, no
+// sqrt takes part.  Capped at 2^31, beyond the floor(M / 2) of any call.
+static i64 pareto_default_tail(i64 M, double r_eff)
+{
+    if (M <= 225) return M / 5;
+    const double need = 9.0 * (double)M;
+    i64 lo = 0, hi = (i64)1 << 31;                         // lo fails, hi holds (or is the cap)
+    while (hi - lo > 1) {
+        const i64 mid = lo + (hi - lo) / 2;
+        if ((double)(mid * mid) * r_eff >= need) hi = mid; else lo = mid;
+    }
+    return hi;
+}
+
+// Acceptance of a Pareto call, and the effective tail length of every parameter.
+static int pareto_check(mcr_ctx* ctx, const void* draws, int dtype, i64 C, i64 N, i64 P, const int64_t* ndraws_tail,
+                        const mcr_pareto* out, std::vector<i64>& teff)
+{
+    if (!out) return fail(ctx, MCR_EINVAL, "out is NULL");
+    if (dtype != MCR_F64 && dtype != MCR_F32) return fail(ctx, MCR_EINVAL, "unsupported dtype %d", dtype);
+    if (C < 0 || N < 0 || P < 0) return fail(ctx, MCR_EINVAL, "negative dimension (C=%lld N=%lld P=%lld)", (long long)C, (long long)N, (long long)P);
+    if (N > 0 && (C > (i64)0x7FFFFFFFll / N || C * N >= (i64)0x7FFFFFFFll)) return fail(ctx, MCR_EINVAL, "C*N must be < 2^31 - 1");
+    if (!draws && C * N * P > 0) return fail(ctx, MCR_EINVAL, "draws is NULL");
+    if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "mcr_pareto_khat with summaries in flight");
+    const i64 M = C * N;
+    teff.resize((size_t)P);
+    for (i64 p = 0; p < P; ++p) {
+        if (ndraws_tail && ndraws_tail[p] < 1)
+            return fail(ctx, MCR_EINVAL, "ndraws_tail[%lld] = %lld: a tail length must be >= 1", (long long)p, (long long)ndraws_tail[p]);
+        teff[(size_t)p] = pareto_tail_eff(M, ndraws_tail ? ndraws_tail[p] : pareto_default_tail(M, 1.0));
+    }
+    return MCR_OK;
+}
+
+static int pareto_run(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i64 P, i64 sc, i64 sn, i64 sp,
+                      const std::vector<i64>& teff, const mcr_pareto* out)
+{
+    const i64 M = C * N;
+    // f32 draws are widened by the ingest pass: the answer is the f64 call's on the widened tensor
+    const bool ingest = dtype == MCR_F32 || needs_ingest(C, N, P, sc, sn, sp);
+    i64 pcmax = 0;
+    int rc = plan_pareto(ctx, M, P, ingest, pcmax);
+    if (rc) return rc;
+    i64* d_tail = nullptr;
+    double* d_res = nullptr;
+    rc = carve(ctx, ctx->pareto_dev, [&](Carve& cv) {
+        d_tail = cv.take<i64>((size_t)P);
+        d_res = cv.take<double>((size_t)kParFields * (size_t)P);
+    });
+    if (!rc) rc = ctx->pareto_host.reserve(ctx, sizeof(double) * (size_t)kParFields * (size_t)P);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(d_tail, teff.data(), sizeof(i64) * (size_t)P, hipMemcpyHostToDevice, ctx->stream));
+    const i64 gmax = pareto_grid(M / 2);
+    for (i64 p0 = 0; p0 < P; p0 += pcmax) {
+        const i64 pc = (P - p0 < pcmax) ? P - p0 : pcmax;
+        PipeIn a = pareto_pipe(M, pc);
+        ParetoWs w;
+        rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) { carve_pareto(cv, a, w, ingest); });
+        if (rc) return rc;
+        if (ingest) {
+            rc = launch_ingest(ctx, draws_dev, dtype, w.X, C, N, pc, sc, sn, sp, p0);
+            if (rc) return rc;
+            a.X = w.X;
+        } else {
+            a.X = reinterpret_cast<const double*>(draws_dev) + p0 * M;
+        }
+        a.d_res = d_res + (size_t)kParFields * (size_t)p0;
+        Sorted so;
+        rc = run_pipeline(ctx, a, &so);        // sort, order statistics, finalize (the bad count)
+        if (rc) return rc;
+        i64 tmax = 0;                          // the chunk's LDS: its longest tail that is staged there
+        for (i64 p = p0; p < p0 + pc; ++p)
+            if (teff[(size_t)p] <= kParetoLdsTail && teff[(size_t)p] > tmax) tmax = teff[(size_t)p];
+        const size_t lds = sizeof(double) * (size_t)tmax;
+        if (lds > 60 * 1024)
+            HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pareto_fit),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        LAUNCH(ctx, K_PARETO_FIT, k_pareto_fit, dim3((unsigned)((pc + 7) / 8 * 8 * 2)), dim3(kParetoNT), lds,
+               (const double*)so.keys, M, pc, (const i64*)(d_tail + p0), so.keys_free, w.lg, gmax, a.d_res, kParField0);
+    }
+    double* h = ctx->pareto_host.as<double>();
+    HIP_TRY(ctx, hipMemcpyAsync(h, d_res, sizeof(double) * (size_t)kParFields * (size_t)P, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    prof_resolve(ctx);
+    double nbad = 0.0;
+    for (i64 p0 = 0; p0 < P; p0 += pcmax) {
+        const i64 pc = (P - p0 < pcmax) ? P - p0 : pcmax;
+        const double* r = h + (size_t)kParFields * (size_t)p0;
+        for (i64 p = 0; p < pc; ++p) {
+            nbad += r[(size_t)R_BAD * pc + p];
+            const double kl = r[(size_t)kParField0 * pc + p], kr = r[(size_t)(kParField0 + 1) * pc + p];
+            if (out->khat_left) out->khat_left[p0 + p] = kl;
+            if (out->khat_right) out->khat_right[p0 + p] = kr;
+            if (out->khat) out->khat[p0 + p] = (kr > kl) ? kr : kl;     // Python's max(left, right)
+            if (out->ndraws_tail) out->ndraws_tail[p0 + p] = teff[(size_t)(p0 + p)];
+        }
+    }
+    if (nbad > 0.0) return fail(ctx, MCR_ENONFINITE, "draws contain %.0f non-finite value(s)", nbad);
+    return MCR_OK;
+}
+
+static void pareto_fill_nan(const mcr_pareto* o, i64 P)
+{
+    for (double* a : {o->khat, o->khat_left, o->khat_right})
+        if (a) for (i64 p = 0; p < P; ++p) a[p] = NAN;
+    if (o->ndraws_tail) for (i64 p = 0; p < P; ++p) o->ndraws_tail[p] = 0;
+}
+
+int mcr_pareto_plan(mcr_ctx* ctx, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc, int64_t sn, int64_t sp,
+                    int64_t* params_per_chunk)
+{
+    if (!ctx || !params_per_chunk) return fail(ctx, MCR_EINVAL, "mcr_pareto_plan: NULL argument");
+    if (C < 1 || N < 1 || P < 1 || C > (i64)0x7FFFFFFFll / N || C * N >= (i64)0x7FFFFFFFll) { *params_per_chunk = 0; return MCR_OK; }
+    i64 pcmax = 0;
+    const int rc = plan_pareto(ctx, C * N, P, dtype == MCR_F32 || needs_ingest(C, N, P, sc, sn, sp), pcmax);
+    if (rc) return rc;
+    *params_per_chunk = pcmax;
+    return MCR_OK;
+}
+
+int mcr_pareto_khat_dev(mcr_ctx* ctx, const void* draws_dev, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc,
+                        int64_t sn, int64_t sp, const int64_t* ndraws_tail, mcr_pareto* out)
+{
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    std::vector<i64> teff;
+    int rc = pareto_check(ctx, draws_dev, dtype, C, N, P, ndraws_tail, out, teff);
+    if (rc || P == 0) return rc;
+    if (C * N == 0) { pareto_fill_nan(out, P); return MCR_OK; }
+    if (tensor_extent(C, N, P, sc, sn, sp) < 0) return fail(ctx, MCR_EINVAL, "negative strides are not supported");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = pareto_run(ctx, draws_dev, dtype, C, N, P, sc, sn, sp, teff, out);
+    return rc ? drain(ctx, rc, true) : rc;
+}
+
+int mcr_pareto_khat(mcr_ctx* ctx, const void* draws, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc, int64_t sn,
+                    int64_t sp, const int64_t* ndraws_tail, mcr_pareto* out)
+{
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    {
+        std::vector<i64> teff;                 // (the device entry checks again: the errors come before the upload)
+        const int rc = pareto_check(ctx, draws, dtype, C, N, P, ndraws_tail, out, teff);
+        if (rc) return rc;
+    }
+    const i64 ext = tensor_extent(C, N, P, sc, sn, sp);
+    if (ext < 0) return fail(ctx, MCR_EINVAL, "negative strides are not supported");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    void* X = ctx->stage.p;
+    if (ext > 0) {
+        const size_t es = dtype == MCR_F64 ? 8 : 4;
+        const int rc = stage_buffers(ctx, {(size_t)ext * es}, &X);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(X, draws, (size_t)ext * es, hipMemcpyHostToDevice, ctx->stream));
+    }
+    return mcr_pareto_khat_dev(ctx, X ? X : draws, dtype, C, N, P, sc, sn, sp, ndraws_tail, out);
+}
+
+int64_t mcr_pareto_tail_length(int64_t M, double r_eff)
+{
+    if (!(r_eff > 0.0) || std::isinf(r_eff)) return MCR_EINVAL;
+    return M < 1 ? 0 : pareto_default_tail(M, r_eff);
+}
+
+int mcr_pareto_fit_host(const double* sorted, int64_t M, int64_t ndraws_tail, double* khat_left, double* khat_right,
+                        int64_t* t_eff)
+{
+    if (M < 0 || ndraws_tail < 0 || (M > 0 && !sorted)) return MCR_EINVAL;
+    const i64 t = pareto_tail_eff(M, ndraws_tail > 0 ? ndraws_tail : pareto_default_tail(M, 1.0));
+    if (t_eff) *t_eff = t;
+    double kl = NAN, kr = NAN;
+    if (t >= kParetoMinTail && t < (i64)0x7FFFFFFFll) {
+        std::vector<double> e((size_t)t), lg((size_t)pareto_grid(t));
+        const ParetoHostWave w;
+        for (i64 i = 0; i < t; ++i) e[(size_t)i] = sorted[t] - sorted[t - 1 - i];
+        kl = pareto_fit(w, e.data(), (int)t, lg.data());
+        for (i64 i = 0; i < t; ++i) e[(size_t)i] = sorted[M - t + i] - sorted[M - t - 1];
+        kr = pareto_fit(w, e.data(), (int)t, lg.data());
+    }
+    if (khat_left) *khat_left = kl;
+    if (khat_right) *khat_right = kr;
+    return MCR_OK;
 }
 
 // Device-resident form (draws_dev [P][M] f64, cov_dev [P][P] f64, both in this context's device memory): what

@@ -65,6 +65,13 @@ class Nested(C.Structure):
     _fields_ = [(n, _dp) for n in NESTED_FIELDS]
 
 
+MCR_PARETO_LDS_TAIL = 8192                                  # the longest tail k_pareto_fit stages in LDS
+
+
+class Pareto(C.Structure):
+    _fields_ = [("khat", _dp), ("khat_left", _dp), ("khat_right", _dp), ("ndraws_tail", _ip)]
+
+
 class ModelDesc(C.Structure):
     _fields_ = [("draws_dev", C.c_void_p), ("dtype", C.c_int), ("min_chains", C.c_int),
                 ("C", C.c_int64), ("N", C.c_int64), ("P", C.c_int64),
@@ -151,6 +158,11 @@ SYMBOLS = {
     "mcr_nested_rhat": (C.c_int, [C.c_void_p] + _TENSOR + [C.POINTER(C.c_int32), C.POINTER(Nested)]),
     "mcr_nested_rhat_dev": (C.c_int, [C.c_void_p] + _TENSOR + [C.POINTER(C.c_int32), C.POINTER(Nested)]),
     "mcr_nested_plan": (C.c_int, [C.c_void_p, C.c_int] + [_I64] * 7 + [C.POINTER(C.c_int64)]),
+    "mcr_pareto_khat": (C.c_int, [C.c_void_p] + _TENSOR + [_ip, C.POINTER(Pareto)]),
+    "mcr_pareto_khat_dev": (C.c_int, [C.c_void_p] + _TENSOR + [_ip, C.POINTER(Pareto)]),
+    "mcr_pareto_plan": (C.c_int, [C.c_void_p, C.c_int] + [_I64] * 6 + [C.POINTER(C.c_int64)]),
+    "mcr_pareto_tail_length": (C.c_int64, [_I64, C.c_double]),
+    "mcr_pareto_fit_host": (C.c_int, [_dp, _I64, _I64, _dp, _dp, C.POINTER(C.c_int64)]),
     "mcr_covariance": (C.c_int, [C.c_void_p, _dp, _I64, _I64, _dp]),
     "mcr_covariance_dev": (C.c_int, [C.c_void_p, C.c_void_p, _I64, _I64, C.c_void_p]),
     "mcr_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
@@ -354,6 +366,37 @@ def superchain_labels(superchain_ids, n_chains: int) -> np.ndarray:
     if ids.size and len(set(np.unique(ids, return_counts=True)[1].tolist())) != 1:
         raise ValueError("superchains must have the same number of chains")
     return np.ascontiguousarray(ids, dtype=np.int32)
+
+
+def pareto_tail_length(M: int, r_eff: float = 1.0) -> int:
+    """The default tail length of Pareto k-hat for M draws (mcr_pareto_tail_length: ceil(3 sqrt(M / r_eff)) for M > 225,
+    else M // 5; no device).  ValueError unless r_eff is finite and > 0."""
+    t = int(load_library().mcr_pareto_tail_length(int(M), float(r_eff)))
+    if t < 0:
+        raise ValueError(f"r_eff must be finite and > 0; got {r_eff}")
+    return t
+
+
+def pareto_fit_host(sorted_draws, ndraws_tail: int = 0) -> tuple[float, float, int]:
+    """(khat_left, khat_right, effective tail length) of an ASCENDING float64 array by the library's host routine
+    (mcr_pareto_fit_host: the device's text and summation order with the host's libm; no device).  ndraws_tail 0: the default."""
+    x = np.ascontiguousarray(sorted_draws, dtype=np.float64)
+    kl, kr, t = C.c_double(), C.c_double(), C.c_int64()
+    rc = load_library().mcr_pareto_fit_host(_as_dp(x), x.size, int(ndraws_tail), C.byref(kl), C.byref(kr), C.byref(t))
+    if rc != MCR_OK:
+        raise ValueError(f"mcr_pareto_fit_host: bad argument (ndraws_tail = {ndraws_tail})")
+    return kl.value, kr.value, int(t.value)
+
+
+def pareto_companions(khat: np.ndarray, M: int) -> tuple[np.ndarray, float]:
+    """posterior::pareto_diags' companions of k-hat values from M draws: min_ss = 10^(1 / (1 - max(0, khat))), +inf for
+    khat >= 1 (NaN stays NaN), and khat_threshold = 1 - 1 / log10(M) (NaN for M < 1)."""
+    k = np.asarray(khat, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        min_ss = np.where(k >= 1.0, np.inf, np.power(10.0, 1.0 / (1.0 - np.maximum(k, 0.0))))
+        min_ss = np.where(np.isnan(k), np.nan, min_ss)
+        threshold = 1.0 - 1.0 / math.log10(M) if M > 1 else float("-inf") if M == 1 else float("nan")
+    return min_ss, threshold
 
 
 class PqImage:
@@ -1198,6 +1241,47 @@ class Context:
         """Parameters per workspace chunk of a nested_rhat call on this tensor with K superchains (mcr_nested_plan)."""
         v = C.c_int64(0)
         self._check(self.lib.mcr_nested_plan(self.handle, *t.targs, int(K), C.byref(v)))
+        return int(v.value)
+
+    def _pareto_tensor(self, draws, layout: str):
+        """(targs, pointer, entry) of a pareto_khat call; a ragged tensor is one chain of its pooled draws."""
+        if isinstance(draws, DeviceTensor):
+            targs = draws.targs
+            if draws.chain_off is not None:
+                M = int(draws.chain_off[-1])
+                targs = (targs[0], 1, M, targs[3], M, 1, targs[6])
+            return targs, draws.buf.ptr, self.lib.mcr_pareto_khat_dev
+        return tensor_args(draws, layout), draws.ctypes.data_as(C.c_void_p), self.lib.mcr_pareto_khat
+
+    def pareto_khat(self, draws, layout: str = "pcn", r_eff=None, ndraws_tail=None) -> dict:
+        """Pareto k-hat of every parameter's tails (mcr_pareto_khat: posterior::pareto_khat(tail = "both")) of a host
+        array or a DeviceTensor; the chains are pooled, so a ragged tensor is accepted.  ndraws_tail: a tail length or P of
+        them (>= 1); or r_eff: a relative efficiency or P of them, turned into tail lengths by mcr_pareto_tail_length;
+        neither: the default of r_eff = 1.  Arrays per parameter: khat = max(khat_left, khat_right), khat_left, khat_right,
+        ndraws_tail (the effective length), min_ss; and the float khat_threshold (pareto_companions)."""
+        if r_eff is not None and ndraws_tail is not None:
+            raise ValueError("give r_eff or ndraws_tail, not both")
+        targs, ptr, fn = self._pareto_tensor(draws, layout)
+        M, P = targs[1] * targs[2], targs[3]
+        tails = None
+        if r_eff is not None:
+            r = np.broadcast_to(np.asarray(r_eff, dtype=np.float64), (P,))
+            tails = np.array([max(pareto_tail_length(M, v), 1) for v in r], dtype=np.int64)
+        elif ndraws_tail is not None:
+            tails = np.ascontiguousarray(np.broadcast_to(np.asarray(ndraws_tail), (P,)), dtype=np.int64)
+        arrs = {n: np.full(max(P, 1), np.nan) for n in ("khat", "khat_left", "khat_right")}
+        nt = np.zeros(max(P, 1), dtype=np.int64)
+        out = Pareto(ndraws_tail=_as_ip(nt), **{n: _as_dp(a) for n, a in arrs.items()})
+        self._check(fn(self.handle, ptr, *targs, None if tails is None else _as_ip(tails), C.byref(out)))
+        res = {n: a[:P] for n, a in arrs.items()}
+        res["ndraws_tail"] = nt[:P]
+        res["min_ss"], res["khat_threshold"] = pareto_companions(res["khat"], M)
+        return res
+
+    def pareto_params_per_chunk(self, t: "DeviceTensor") -> int:
+        """Parameters per workspace chunk of a pareto_khat call on this tensor (mcr_pareto_plan)."""
+        v = C.c_int64(0)
+        self._check(self.lib.mcr_pareto_plan(self.handle, *self._pareto_tensor(t, "pcn")[0], C.byref(v)))
         return int(v.value)
 
     def covariance(self, draws) -> np.ndarray:

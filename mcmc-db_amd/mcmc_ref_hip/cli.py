@@ -11,6 +11,7 @@ this package's own: the chain files of a CmdStan run, parsed on the GPU, printed
 `validate MODEL --actual FILE.csv`, the command of `validate.validate` (compare's gate plus KS / Wasserstein-1 per
 parameter and, with `--sliced K`, along K random directions of the joint distribution; exits like `compare`).
 `nested-rhat FILE --superchains K` prints nested R-hat, the diagnostic for many short chains, of a draws table.
+`pareto-khat FILE` prints the Pareto k-hat of every parameter's tails: whether a mean and a std of the draws can be trusted.
 """
 from __future__ import annotations
 
@@ -171,6 +172,21 @@ def nested_rhat_cmd(file: Path, superchains: int, params: str | None, format_: s
     _echo_stats(stats, format_)
 
 
+@main.command("pareto-khat")
+@click.argument("file", type=click.Path(path_type=Path, exists=True, dir_okay=False))
+@click.option("--params", default=None, help="Comma-separated parameter list")
+@click.option("--tail-draws", default=None, type=int, help="Draws per tail (default: ceil(3 sqrt(M)), M // 5 up to 225 draws)")
+@click.option("--format", "format_", type=click.Choice(["table", "csv", "json"], case_sensitive=False), default="table")
+def pareto_khat_cmd(file: Path, params: str | None, tail_draws: int | None, format_: str) -> None:
+    """Pareto k-hat (Vehtari et al.) of the pooled draws of a table (no counterpart in the reference): khat =
+    max(khat_left, khat_right); below 0.5 mean and std can be trusted, from 0.7 neither."""
+    try:
+        stats = convert_mod.pareto_khat_file(file, params=params.split(",") if params else None, ndraws_tail=tail_draws)
+    except (ValueError, KeyError, IndexError) as exc:
+        raise click.ClickException(str(exc)) from exc
+    _echo_stats(stats, format_)
+
+
 @main.command("diagnostics")
 @click.argument("model")
 @click.option("--format", "format_", type=click.Choice(["table", "csv", "json"], case_sensitive=False), default="table")
@@ -228,16 +244,17 @@ def compare_cmd(model: str, actual_path: Path, tolerance: float, format_: str) -
 @click.option("--sliced-seed", default=4711, type=int)
 @click.option("--sliced-ks-max", default=None, type=float, help="Fail when the largest sliced KS exceeds this")
 @click.option("--sliced-w1-max", default=None, type=float, help="Fail when the largest sliced W1 exceeds this")
+@click.option("--khat-max", default=None, type=float, help="Fail a parameter whose Pareto k-hat of the actual draws exceeds this")
 @click.option("--format", "format_", type=click.Choice(["table", "json"], case_sensitive=False), default="table")
 def validate_cmd(model: str, actual_path: Path, tolerance: float, metrics: str, ks_max, w1_scaled_max, sliced: int, sliced_seed: int,
-                 sliced_ks_max, sliced_w1_max, format_: str) -> None:
+                 sliced_ks_max, sliced_w1_max, khat_max, format_: str) -> None:
     """The reference's mean / std gate plus per-parameter KS / Wasserstein-1 and, with --sliced K, the same distances
     along K random directions of the joint distribution (validate.validate; no counterpart in the reference)."""
     from .validate import validate
     try:
         result = validate(model, _read_actual_csv(actual_path), tolerance=tolerance, metrics=tuple(metrics.split(",")),
                           ks_max=ks_max, w1_scaled_max=w1_scaled_max, sliced=sliced, sliced_seed=sliced_seed,
-                          sliced_ks_max=sliced_ks_max, sliced_w1_max=sliced_w1_max)
+                          sliced_ks_max=sliced_ks_max, sliced_w1_max=sliced_w1_max, khat_max=khat_max)
     except ValueError as exc:
         raise click.ClickException(str(exc)) from exc
     if format_ == "json":
@@ -247,11 +264,14 @@ def validate_cmd(model: str, actual_path: Path, tolerance: float, metrics: str, 
                                            "details": details},
                                "ks": result.ks, "wasserstein": result.wasserstein,
                                "wasserstein_scaled": result.wasserstein_scaled, "sliced_ks": result.sliced_ks,
-                               "sliced_w1": result.sliced_w1, "sliced": result.sliced}, indent=2, sort_keys=True))
+                               "sliced_w1": result.sliced_w1, "sliced": result.sliced, "khat_ref": result.khat_ref,
+                               "khat_actual": result.khat_actual}, indent=2, sort_keys=True))
     else:
         click.echo("passed" if result.passed else "failed")
         for failure in result.failures:
             click.echo(f"- {failure}")
+        if khat_max is not None:               # the two k-hat columns (the JSON form always has them)
+            _print_table({p: {"khat_ref": result.khat_ref[p], "khat_actual": result.khat_actual[p]} for p in result.khat_actual})
     raise SystemExit(0 if result.passed else 2)
 
 

@@ -599,6 +599,30 @@ def nested_rhat_file(path: Path, superchains: int, params: Iterable[str] | None 
     return {n: {k: float(r[k][i]) for k in keys} for i, n in enumerate(names)}
 
 
+def pareto_khat_file(path: Path, params: Iterable[str] | None = None, ndraws_tail: int | None = None,
+                     context=None) -> dict[str, dict[str, float]]:
+    """Pareto k-hat of every parameter of a draws table (a `.csv` or chain-list `.json.zip`, read on the host); the chains
+    are pooled and may differ in length.  Per parameter: khat, khat_left, khat_right, ndraws_tail, min_ss
+    (Context.pareto_khat); `ndraws_tail`: the tail length for every parameter instead of the default."""
+    table = _ensure_chain_draw(_read_input(Path(path)))
+    names = [c for c in table.column_names if c not in ("chain", "draw")]
+    if params is not None:
+        missing = [p for p in params if p not in names]
+        if missing:
+            raise ValueError(f"Unknown parameter(s): {', '.join(missing)}")
+        names = list(params)
+    if not names:
+        return {}
+    if ndraws_tail is not None and ndraws_tail < 1:
+        raise ValueError(f"the tail length must be >= 1; got {ndraws_tail}")
+    x, _ = table_to_tensor(table, names)
+    ctx = context or _ffi.default_context()
+    with _ffi.value_errors():
+        r = ctx.pareto_khat(x.reshape(len(names), 1, -1), "pcn", ndraws_tail=ndraws_tail)
+    keys = ("khat", "khat_left", "khat_right", "ndraws_tail", "min_ss")
+    return {n: {k: (int if k == "ndraws_tail" else float)(r[k][i]) for k in keys} for i, n in enumerate(names)}
+
+
 def _ensure_chain_draw(table):
     """Add the missing bookkeeping columns like the reference does (convert.py:105-120): a missing
     `draw` is the row number, a missing `chain` is chain 0 (int32, appended after the parameters)."""

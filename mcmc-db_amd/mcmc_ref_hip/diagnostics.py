@@ -7,7 +7,8 @@ autocovariance sum) runs in libmcmcref_hip; chains may be ragged.
 
 `nested_rhat` is not the reference's: the diagnostic for many short chains (Margossian et al., "Nested R-hat: assessing
 the convergence of Markov chain Monte Carlo when running many short chains"; posterior::rhat_nested), for any number
-of equal-length chains.
+of equal-length chains.  `pareto_khat` is not the reference's either: the tail diagnostic for the draws behind a mean
+and a std (Vehtari et al., "Pareto smoothed importance sampling"; posterior::pareto_khat), on the pooled chains.
 """
 from __future__ import annotations
 
@@ -93,3 +94,26 @@ def nested_rhat(chains: Sequence[Sequence[float]], superchain_ids, *, context=No
     ctx = context or _ffi.default_context()
     with _ffi.value_errors():
         return float(ctx.nested_rhat(x, ids, "pcn")["nrhat"][0])
+
+
+def pareto_khat_detail(chains: Sequence[Sequence[float]], *, r_eff=None, ndraws_tail=None, context=None) -> dict:
+    """Pareto k-hat of ONE parameter given as chains of any lengths (they are pooled): khat = max(khat_left, khat_right),
+    khat_left, khat_right, ndraws_tail (the effective tail length), min_ss and khat_threshold (Context.pareto_khat).  The
+    tail length comes from `ndraws_tail`, or from the relative efficiency `r_eff`, or is the default of r_eff = 1."""
+    if r_eff is not None and ndraws_tail is not None:
+        raise ValueError("give r_eff or ndraws_tail, not both")
+    x = np.concatenate([np.asarray(c, dtype=np.float64).reshape(-1) for c in chains]) if len(chains) else np.zeros(0)
+    ctx = context or _ffi.default_context()
+    with _ffi.value_errors():
+        res = ctx.pareto_khat(x.reshape(1, 1, -1), "pcn", r_eff=r_eff, ndraws_tail=ndraws_tail)
+    out = {k: float(res[k][0]) for k in ("khat", "khat_left", "khat_right", "min_ss")}
+    out["ndraws_tail"] = int(res["ndraws_tail"][0])
+    out["khat_threshold"] = res["khat_threshold"]
+    return out
+
+
+def pareto_khat(chains: Sequence[Sequence[float]], *, r_eff=None, ndraws_tail=None, context=None) -> float:
+    """Pareto k-hat of the pooled chains' tails, the larger of the two: below 0.5 the variance is finite and the central
+    limit theorem holds, from 0.5 the mean converges slowly and a std is not trustworthy, from 0.7 the estimates are
+    unreliable, from 1 no mean exists.  NaN for fewer than 10 draws or constant tails."""
+    return pareto_khat_detail(chains, r_eff=r_eff, ndraws_tail=ndraws_tail, context=context)["khat"]

@@ -4,7 +4,8 @@ The reference gates a sampler's draws with `reference.compare` (relative error o
 src/mcmc_ref/reference.py:107-122).  `validate` keeps that gate unchanged and adds, per parameter,
 distribution-level distances computed on the GPU -- the two-sample Kolmogorov-Smirnov statistic and
 the Wasserstein-1 distance (scaled by the reference std) -- plus the reference draws' own
-diagnostics.  `sliced=K` adds a check of the JOINT distribution: both samples are projected onto K random
+diagnostics, and the Pareto k-hat of both samples' tails (`khat_ref` / `khat_actual`: above 0.5 the std gate is not
+trustworthy, above 0.7 the mean gate is not either).  `sliced=K` adds a check of the JOINT distribution: both samples are projected onto K random
 directions of the standardised parameter space and each projected pair goes through the same KS / W1 pass, so a
 wrong dependence between parameters whose marginals are all right shows up along some direction.  Nothing here exists in the reference: parity for these extras is pinned to scipy only
 (tests/test_ext_gpu.py), and they never change `passed` unless thresholds are given explicitly.
@@ -34,6 +35,8 @@ class ValidateResult:
     sliced_w1: float | None = None               # largest W1 over them, in units of reference std
     sliced: dict | None = None                   # per-direction "ks" / "w1", "worst" (index of the largest KS) and
     #                                              "worst_direction" {param: weight in standardised space}
+    khat_ref: dict[str, float] = field(default_factory=dict)       # Pareto k-hat (the larger tail) of the reference draws
+    khat_actual: dict[str, float] = field(default_factory=dict)    # ... and of `actual`
 
 
 def sliced_directions(k: int, std, seed: int = 4711) -> tuple[np.ndarray, np.ndarray]:
@@ -62,8 +65,9 @@ def validate(model: str, actual: Mapping[str, Sequence[float]], tolerance: float
              metrics: Sequence[str] = ("mean", "std"), ks_max: float | None = None,
              w1_scaled_max: float | None = None, store: DataStore | None = None, context=None, sliced: int = 0,
              sliced_seed: int = 4711, sliced_ks_max: float | None = None,
-             sliced_w1_max: float | None = None) -> ValidateResult:
-    """sliced=K > 0: K directions `sliced_directions(K, reference std, sliced_seed)` around the reference means, one
+             sliced_w1_max: float | None = None, khat_max: float | None = None) -> ValidateResult:
+    """khat_max: a parameter whose `khat_actual` (Context.pareto_khat, default tail length) exceeds it is a failure;
+    without it the two k-hat columns are information only.  sliced=K > 0: K directions `sliced_directions(K, reference std, sliced_seed)` around the reference means, one
     `Context.sliced_two_sample` call; the result's `sliced_ks` / `sliced_w1` are the maxima over the directions and
     `sliced` holds the detail.  `sliced_ks_max` / `sliced_w1_max` turn them into failures; without them `passed` is what
     it is without `sliced`.  Needs joint draws: every parameter of `actual` must have the same length."""
@@ -94,7 +98,16 @@ def validate(model: str, actual: Mapping[str, Sequence[float]], tolerance: float
             ks[p], w1[p] = float(k[0]), float(w[0])
     scaled = {p: (w1[p] / ref_stats[p]["std"] if ref_stats[p]["std"] > 0 else float("inf") if w1[p] > 0 else 0.0)
               for p in params}
+    khat_ref = {p: float(v) for p, v in zip(params, ctx.pareto_khat(ref.reshape(len(params), 1, -1), "pcn")["khat"])} if params else {}
+    khat_act: dict[str, float] = {}
+    if len(lens) == 1 and params:
+        khat_act = {p: float(v) for p, v in zip(params, ctx.pareto_khat(act.reshape(len(params), 1, -1), "pcn")["khat"])}
+    else:
+        for p in params:
+            khat_act[p] = float(ctx.pareto_khat(np.asarray(actual[p], dtype=np.float64).reshape(1, 1, -1), "pcn")["khat"][0])
     failures = list(cmp_res.failures)
+    if khat_max is not None:
+        failures += [f"{p}.khat_actual={khat_act[p]:.3g} > {khat_max}" for p in params if not khat_act[p] <= khat_max]
     if ks_max is not None:
         failures += [f"{p}.ks={ks[p]:.3g} > {ks_max}" for p in params if not ks[p] <= ks_max]
     if w1_scaled_max is not None:
@@ -115,4 +128,4 @@ def validate(model: str, actual: Mapping[str, Sequence[float]], tolerance: float
             if sliced_w1_max is not None and not extra["sliced_w1"] <= sliced_w1_max:
                 failures.append(f"sliced.w1={extra['sliced_w1']:.3g} > {sliced_w1_max}")
     return ValidateResult(passed=not failures, compare=cmp_res, ks=ks, wasserstein=w1, wasserstein_scaled=scaled,
-                          failures=failures, **extra)
+                          failures=failures, khat_ref=khat_ref, khat_actual=khat_act, **extra)
