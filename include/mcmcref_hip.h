@@ -359,6 +359,48 @@ int64_t mcr_pareto_tail_length(int64_t M, double r_eff);                 /* host
 int mcr_pareto_fit_host(const double* sorted, int64_t M, int64_t ndraws_tail /* 0 = default */,
                         double* khat_left, double* khat_right, int64_t* t_eff);
 #define MCR_PARETO_LDS_TAIL 8192      /* the longest tail k_pareto_fit stages in LDS */
+/* Highest-density intervals (HDI): the shortest interval that holds a given share of a parameter's draws (ArviZ's
+ * unimodal hdi, the hdi_3% / hdi_97% columns of its summary; hdi of bayestestR).  ABSENT from the reference.  For a skewed
+ * or bounded parameter it differs from the equal-tailed interval of the same share by a large part of its width.
+ * For one parameter, let x_(0) <= ... <= x_(M-1) be its M pooled draws in ascending order.  The chains are pooled and
+ * their structure plays no part.  Everything is IEEE double.  For each requested probability prob:
+ *     inc = (int64) floor(prob * (double)M)        one rounded product, computed on the host
+ *     W   = M - inc                                the number of windows
+ *     w_i = x_(i + inc) - x_(i),  i = 0 ... W-1
+ *     i*  = the smallest i with w_i = min_j w_j    (numpy.argmin: the first minimum)
+ *     lo = x_(i*),  hi = x_(i* + inc),  index = i*
+ * that is numpy.argmin(s[inc:] - s[:M - inc]) on s = numpy.sort(x).  The interval holds inc + 1 draws.  If W < 1 -- only
+ * when the product rounds up to M -- lo = hi = NaN and index = -1.  A width that overflows to +inf is an ordinary value
+ * of the comparison.
+ * One answer.  The minimum over (w_i, i) in lexicographic order does not depend on the order of evaluation: a
+ * parameter's outputs have the same bits alone or in a batch, at any place in the batch, under any workspace limit, in
+ * either layout, on the host entry or the device entry, and for any split of the window range.  lo and hi are keys of
+ * the sort: where the draws hold both -0.0 and +0.0 the sign of a zero endpoint is the sort's and is not specified.
+ * f32 draws are widened first by the ingest pass; the answer is that of the f64 call on the widened tensor.
+ * draws: host tensor addressed like mcr_summarize's.  probs: nprob probabilities, each finite with 0 < prob < 1, in any
+ * order, repeats allowed.  out: [P][nprob] row-major arrays, NULL skipped.
+ * Limits: any C, C * N < 2^31 - 1.  MCR_EINVAL (message names the cause): a negative dimension, nprob < 1 or >
+ * MCR_HDI_MAX_PROBS, a probability outside (0, 1) or NaN, summaries in flight, negative strides.  MCR_ENONFINITE: NaN /
+ * Inf draws.  M == 0 gives NaN and -1, P == 0 writes nothing.  The context stays usable after every error.  Synchronous.
+ * k_hdi_window gives MCR_HDI_SLICE windows of a (parameter, probability) to one workgroup; k_hdi_pick takes the least of
+ * the slices' candidates. */
+typedef struct mcr_hdi_out { double *lo, *hi; int64_t* index; } mcr_hdi_out;   /* [P][nprob] each, NULL skipped */
+int mcr_hdi(mcr_ctx* ctx, const void* draws, int dtype, int64_t C, int64_t N, int64_t P, int64_t stride_c, int64_t stride_n,
+            int64_t stride_p, const double* probs, int nprob, mcr_hdi_out* out);
+/* The same on draws in this ctx's device memory; probs and out stay on the host. */
+int mcr_hdi_dev(mcr_ctx* ctx, const void* draws_dev, int dtype, int64_t C, int64_t N, int64_t P, int64_t stride_c,
+                int64_t stride_n, int64_t stride_p, const double* probs, int nprob, mcr_hdi_out* out);
+/* Parameters per workspace chunk of such a call with nprob probabilities under the current workspace limit (0 for an
+ * empty shape).  MCR_ENOMEM when the limit does not fit one parameter. */
+int mcr_hdi_plan(mcr_ctx* ctx, int dtype, int64_t C, int64_t N, int64_t P, int64_t stride_c, int64_t stride_n,
+                 int64_t stride_p, int nprob, int64_t* params_per_chunk);
+/* The same intervals of an ascending host array (host only, no ctx, no device): lo, hi, index take nprob entries, NULL
+ * skipped.  The comparison of two windows is the device's text.  MCR_EINVAL: M < 0, a NULL array, nprob or a probability
+ * as above.  Non-finite entries are not looked for. */
+int mcr_hdi_sorted_host(const double* sorted, int64_t M, const double* probs, int nprob, double* lo, double* hi,
+                        int64_t* index);
+#define MCR_HDI_MAX_PROBS 16          /* probabilities of a mcr_hdi call */
+#define MCR_HDI_SLICE 16384           /* windows k_hdi_window gives one workgroup */
 /* Population covariance matrix (ddof = 0, like compare.py:63) of P parameters over M pooled draws,
  * draws[P][M] host row-major -> cov[P][P].  The one dense contraction of the path: fp64 MFMA
  * (v_mfma_f64_16x16x4f64; LDS-staged 64 x 64 tiles, upper triangle, split over the draw axis).

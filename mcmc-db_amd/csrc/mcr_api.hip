@@ -32,6 +32,7 @@
 #include "mcr_ext.hpp"
 #include "mcr_nested.hpp"
 #include "mcr_pareto.hpp"
+#include "mcr_hdi.hpp"
 #include "mcr_parquet.hpp"
 #include "mcr_pqwrite.hpp"
 #include "mcr_csvwrite.hpp"
@@ -63,7 +64,7 @@ enum KernelId {
     K_JSON_INDEX, K_JSON_SCAN, K_JSON_PARSE,
     K_LAYOUT_SCAN, K_LAYOUT_KEYS, K_LAYOUT_HIST, K_LAYOUT_OFFSETS, K_LAYOUT_SCATTER, K_LAYOUT_BOUNDS,
     K_PQW_ENCODE, K_PQW_COMPACT, K_CSVW_FORMAT, K_CSVW_SCAN, K_CSVW_COMPACT, K_SELECT_ROWS, K_PROJECT,
-    K_CHAIN_MOMENTS, K_NESTED_COMBINE, K_PARETO_FIT, K_COUNT
+    K_CHAIN_MOMENTS, K_NESTED_COMBINE, K_PARETO_FIT, K_HDI_WINDOW, K_HDI_PICK, K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {
     "k_ingest", "k_moments", "k_moments_final", "k_tile_sort", "k_merge", "k_order_stats", "k_rank_z",
@@ -74,7 +75,7 @@ const char* const kKernelNames[K_COUNT] = {
     "k_json_index", "k_json_scan", "k_json_parse",
     "k_layout_scan", "k_layout_keys", "k_layout_hist", "k_layout_offsets", "k_layout_scatter", "k_layout_bounds",
     "k_pqw_encode", "k_pqw_compact", "k_csvw_format", "k_csvw_scan", "k_csvw_compact", "k_select_rows", "k_project",
-    "k_chain_moments", "k_nested_combine", "k_pareto_fit"};
+    "k_chain_moments", "k_nested_combine", "k_pareto_fit", "k_hdi_window", "k_hdi_pick"};
 
 struct EvPair { hipEvent_t a, b; int kid; };
 
@@ -192,6 +193,8 @@ struct mcr_ctx {
     PinBuf nest_host{4};               // its results on the host
     DevBuf pareto_dev{4};              // mcr_pareto_khat: tail lengths + result table
     PinBuf pareto_host{4};             // its results on the host
+    DevBuf hdi_dev{4};                 // mcr_hdi: result table
+    PinBuf hdi_host{4};                // its results on the host
     DevBuf guard_count;                // device counters (2 unsigned): band lags re-derived the reference's way (mcr_rho_guard_count),
                                        // tiles the tile sort sorted as pairs after all (mcr_tile_fallback_count)
 };
@@ -1269,6 +1272,126 @@ int moments_impl(mcr_ctx* ctx, const T* src, i64 C, i64 N, i64 P, i64 sc, i64 sn
     return MCR_OK;
 }
 
+// ---- Calls on the pooled ascending order (Pareto k-hat, HDI) ---------------------------------------------------------------
+// Both run the summary pipeline without diagnostics and quantiles -- tile sort, merges / bucket partition, k_order_stats,
+// k_finalize for the non-finite count -- and then their own kernels on the keys the sort stage left.
+constexpr int kPoolField0 = R_Q0;                          // the pipeline runs without quantiles: its rows end here
+
+PipeIn stats_only_pipe(i64 M, i64 pc)
+{
+    PipeIn a{};
+    a.M = M; a.pc = pc; a.C = 1; a.n = 1; a.nh = 0; a.nstage = 1; a.q.nq = 0; a.do_diag = false;
+    return a;
+}
+
+// The workspace of a stats-only chunk of a.pc parameters: the sort alone and the split points k_order_stats writes.
+// Returns the ingest copy.
+double* carve_stats_only(Carve& cv, PipeIn& a, bool ingest)
+{
+    double* X = carve_pipe(cv, a, false, FftPlan{}, ingest);
+    a.split = cv.take<i64>((size_t)a.pc);
+    return X;
+}
+
+// Parameters per workspace chunk, at most hi: extra(cv, a) carves what the caller needs behind the pipeline's buffers.
+template <class Extra>
+int plan_pooled(mcr_ctx* ctx, i64 M, i64 hi, bool ingest, Extra&& extra, i64& pcmax)
+{
+    auto measure = [&](i64 pc) {
+        PipeIn a = stats_only_pipe(M, pc);
+        Carve m{nullptr};
+        carve_stats_only(m, a, ingest);
+        extra(m, a);
+        return m.off;
+    };
+    pcmax = most_that_fit(hi < kMaxGridY / 2 ? hi : kMaxGridY / 2, [&](i64 pc) { return measure(pc) <= ctx->ws_limit; });
+    if (!pcmax) return fail(ctx, MCR_ENOMEM, "one parameter needs %zu bytes of workspace; limit is %zu", measure(1), ctx->ws_limit);
+    return MCR_OK;
+}
+
+// Acceptance of the tensor of such a call (`what` names the entry in the message).
+int pooled_check(mcr_ctx* ctx, const char* what, const void* draws, int dtype, i64 C, i64 N, i64 P, const void* out)
+{
+    if (!out) return fail(ctx, MCR_EINVAL, "out is NULL");
+    if (dtype != MCR_F64 && dtype != MCR_F32) return fail(ctx, MCR_EINVAL, "unsupported dtype %d", dtype);
+    if (C < 0 || N < 0 || P < 0) return fail(ctx, MCR_EINVAL, "negative dimension (C=%lld N=%lld P=%lld)", (long long)C, (long long)N, (long long)P);
+    if (N > 0 && (C > (i64)0x7FFFFFFFll / N || C * N >= (i64)0x7FFFFFFFll)) return fail(ctx, MCR_EINVAL, "C*N must be < 2^31 - 1");
+    if (!draws && C * N * P > 0) return fail(ctx, MCR_EINVAL, "draws is NULL");
+    if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "%s with summaries in flight", what);
+    return MCR_OK;
+}
+
+// The host entries' upload: the tensor's extent into ctx->stage.  *dev: the device copy (the host pointer for an empty one).
+int pooled_upload(mcr_ctx* ctx, const void* draws, int dtype, i64 C, i64 N, i64 P, i64 sc, i64 sn, i64 sp, const void** dev)
+{
+    const i64 ext = tensor_extent(C, N, P, sc, sn, sp);
+    if (ext < 0) return fail(ctx, MCR_EINVAL, "negative strides are not supported");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    void* X = ctx->stage.p;
+    if (ext > 0) {
+        const size_t es = dtype == MCR_F64 ? 8 : 4;
+        const int rc = stage_buffers(ctx, {(size_t)ext * es}, &X);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(X, draws, (size_t)ext * es, hipMemcpyHostToDevice, ctx->stream));
+    }
+    *dev = X ? X : draws;
+    return MCR_OK;
+}
+
+// The chunks of such a call: per chunk of at most pcmax parameters the ingest pass where the tensor needs one (f32 draws
+// are widened by it: the answer is the f64 call's on the widened tensor), the stats-only pipeline into the chunk's rows
+// d_res + fields * p0, then after(a, so, p0): the caller's kernels on the chunk's keys.  extra: as in plan_pooled.
+template <class Extra, class After>
+int pooled_chunks(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i64 P, i64 sc, i64 sn, i64 sp,
+                         bool ingest, i64 pcmax, int fields, double* d_res, Extra&& extra, After&& after)
+{
+    const i64 M = C * N;
+    for (i64 p0 = 0; p0 < P; p0 += pcmax) {
+        const i64 pc = (P - p0 < pcmax) ? P - p0 : pcmax;
+        PipeIn a = stats_only_pipe(M, pc);
+        double* X = nullptr;
+        int rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) { X = carve_stats_only(cv, a, ingest); extra(cv, a); });
+        if (rc) return rc;
+        if (ingest) {
+            rc = launch_ingest(ctx, draws_dev, dtype, X, C, N, pc, sc, sn, sp, p0);
+            if (rc) return rc;
+            a.X = X;
+        } else {
+            a.X = reinterpret_cast<const double*>(draws_dev) + p0 * M;
+        }
+        a.d_res = d_res + (size_t)fields * (size_t)p0;
+        Sorted so;
+        rc = run_pipeline(ctx, a, &so);        // sort, order statistics, finalize (the bad count)
+        if (!rc) rc = after(a, so, p0);
+        if (rc) return rc;
+    }
+    return MCR_OK;
+}
+
+// The one D2H of the result table at the end of such a call; each(r, pc, p0, p): the rows r of the chunk at p0, parameter
+// p of its pc.  MCR_ENONFINITE when the pipeline counted a NaN or Inf draw (the outputs are written all the same).
+template <class Each>
+int pooled_results(mcr_ctx* ctx, PinBuf& host, const double* d_res, int fields, i64 P, i64 pcmax, Each&& each)
+{
+    int rc = host.reserve(ctx, sizeof(double) * (size_t)fields * (size_t)P);
+    if (rc) return rc;
+    double* h = host.as<double>();
+    HIP_TRY(ctx, hipMemcpyAsync(h, d_res, sizeof(double) * (size_t)fields * (size_t)P, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    prof_resolve(ctx);
+    double nbad = 0.0;
+    for (i64 p0 = 0; p0 < P; p0 += pcmax) {
+        const i64 pc = (P - p0 < pcmax) ? P - p0 : pcmax;
+        const double* r = h + (size_t)fields * (size_t)p0;
+        for (i64 p = 0; p < pc; ++p) {
+            nbad += r[(size_t)R_BAD * pc + p];
+            each(r, pc, p0, p);
+        }
+    }
+    if (nbad > 0.0) return fail(ctx, MCR_ENONFINITE, "draws contain %.0f non-finite value(s)", nbad);
+    return MCR_OK;
+}
+
 }  // namespace
 
 // =================================================================================================
@@ -2096,42 +2219,21 @@ int mcr_nested_rhat(mcr_ctx* ctx, const void* draws, int dtype, int64_t C, int64
 }
 
 // ---- Pareto k-hat (mcr_pareto.hpp) --------------------------------------------------------------------------------------
-constexpr int kParField0 = R_Q0;                           // the pipeline runs without quantiles: its rows end here
+constexpr int kParField0 = kPoolField0;
 constexpr int kParFields = kParField0 + 2;                 // + khat_left, khat_right
 
 static_assert(kParetoLdsTail == MCR_PARETO_LDS_TAIL, "mcmcref_hip.h states the LDS tail");
 
-struct ParetoWs { double *X, *lg; };
-
-static PipeIn pareto_pipe(i64 M, i64 pc)
+// Behind the pipeline's buffers: the grid values l_j of every tail.
+static double* carve_pareto(Carve& cv, const PipeIn& a)
 {
-    PipeIn a{};
-    a.M = M; a.pc = pc; a.C = 1; a.n = 1; a.nh = 0; a.nstage = 1; a.q.nq = 0; a.do_diag = false;
-    return a;
-}
-
-// The workspace of a chunk of a.pc parameters: the sort alone (the stats-only layout), the split points k_order_stats
-// writes, and the grid values l_j of every tail.
-static void carve_pareto(Carve& cv, PipeIn& a, ParetoWs& w, bool ingest)
-{
-    w.X = carve_pipe(cv, a, false, FftPlan{}, ingest);
-    a.split = cv.take<i64>((size_t)a.pc);
-    w.lg = cv.take<double>((size_t)a.pc * 2 * (size_t)pareto_grid(a.M / 2));
+    return cv.take<double>((size_t)a.pc * 2 * (size_t)pareto_grid(a.M / 2));
 }
 
 // Parameters per workspace chunk of a Pareto call.
 static int plan_pareto(mcr_ctx* ctx, i64 M, i64 P, bool ingest, i64& pcmax)
 {
-    auto measure = [&](i64 pc) {
-        PipeIn a = pareto_pipe(M, pc);
-        ParetoWs w;
-        Carve m{nullptr};
-        carve_pareto(m, a, w, ingest);
-        return m.off;
-    };
-    pcmax = most_that_fit(P < kMaxGridY / 2 ? P : kMaxGridY / 2, [&](i64 pc) { return measure(pc) <= ctx->ws_limit; });
-    if (!pcmax) return fail(ctx, MCR_ENOMEM, "one parameter needs %zu bytes of workspace; limit is %zu", measure(1), ctx->ws_limit);
-    return MCR_OK;
+    return plan_pooled(ctx, M, P, ingest, [](Carve& cv, PipeIn& a) { carve_pareto(cv, a); }, pcmax);
 }
 
 // The default tail length: the smallest t with t^2 r_eff >= 9 M (that is ceil(3 sqrt(M / r_eff))) for M > 225, else
@@ -2153,12 +2255,8 @@ static i64 pareto_default_tail(i64 M, double r_eff)
 static int pareto_check(mcr_ctx* ctx, const void* draws, int dtype, i64 C, i64 N, i64 P, const int64_t* ndraws_tail,
                         const mcr_pareto* out, std::vector<i64>& teff)
 {
-    if (!out) return fail(ctx, MCR_EINVAL, "out is NULL");
-    if (dtype != MCR_F64 && dtype != MCR_F32) return fail(ctx, MCR_EINVAL, "unsupported dtype %d", dtype);
-    if (C < 0 || N < 0 || P < 0) return fail(ctx, MCR_EINVAL, "negative dimension (C=%lld N=%lld P=%lld)", (long long)C, (long long)N, (long long)P);
-    if (N > 0 && (C > (i64)0x7FFFFFFFll / N || C * N >= (i64)0x7FFFFFFFll)) return fail(ctx, MCR_EINVAL, "C*N must be < 2^31 - 1");
-    if (!draws && C * N * P > 0) return fail(ctx, MCR_EINVAL, "draws is NULL");
-    if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "mcr_pareto_khat with summaries in flight");
+    const int rc = pooled_check(ctx, "mcr_pareto_khat", draws, dtype, C, N, P, out);
+    if (rc) return rc;
     const i64 M = C * N;
     teff.resize((size_t)P);
     for (i64 p = 0; p < P; ++p) {
@@ -2173,7 +2271,6 @@ static int pareto_run(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64
                       const std::vector<i64>& teff, const mcr_pareto* out)
 {
     const i64 M = C * N;
-    // f32 draws are widened by the ingest pass: the answer is the f64 call's on the widened tensor
     const bool ingest = dtype == MCR_F32 || needs_ingest(C, N, P, sc, sn, sp);
     i64 pcmax = 0;
     int rc = plan_pareto(ctx, M, P, ingest, pcmax);
@@ -2184,56 +2281,32 @@ static int pareto_run(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64
         d_tail = cv.take<i64>((size_t)P);
         d_res = cv.take<double>((size_t)kParFields * (size_t)P);
     });
-    if (!rc) rc = ctx->pareto_host.reserve(ctx, sizeof(double) * (size_t)kParFields * (size_t)P);
     if (rc) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(d_tail, teff.data(), sizeof(i64) * (size_t)P, hipMemcpyHostToDevice, ctx->stream));
     const i64 gmax = pareto_grid(M / 2);
-    for (i64 p0 = 0; p0 < P; p0 += pcmax) {
-        const i64 pc = (P - p0 < pcmax) ? P - p0 : pcmax;
-        PipeIn a = pareto_pipe(M, pc);
-        ParetoWs w;
-        rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) { carve_pareto(cv, a, w, ingest); });
-        if (rc) return rc;
-        if (ingest) {
-            rc = launch_ingest(ctx, draws_dev, dtype, w.X, C, N, pc, sc, sn, sp, p0);
-            if (rc) return rc;
-            a.X = w.X;
-        } else {
-            a.X = reinterpret_cast<const double*>(draws_dev) + p0 * M;
-        }
-        a.d_res = d_res + (size_t)kParFields * (size_t)p0;
-        Sorted so;
-        rc = run_pipeline(ctx, a, &so);        // sort, order statistics, finalize (the bad count)
-        if (rc) return rc;
+    double* lg = nullptr;
+    rc = pooled_chunks(ctx, draws_dev, dtype, C, N, P, sc, sn, sp, ingest, pcmax, kParFields, d_res,
+                       [&](Carve& cv, PipeIn& a) { lg = carve_pareto(cv, a); },
+                       [&](const PipeIn& a, const Sorted& so, i64 p0) -> int {
         i64 tmax = 0;                          // the chunk's LDS: its longest tail that is staged there
-        for (i64 p = p0; p < p0 + pc; ++p)
+        for (i64 p = p0; p < p0 + a.pc; ++p)
             if (teff[(size_t)p] <= kParetoLdsTail && teff[(size_t)p] > tmax) tmax = teff[(size_t)p];
         const size_t lds = sizeof(double) * (size_t)tmax;
         if (lds > 60 * 1024)
             HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pareto_fit),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        LAUNCH(ctx, K_PARETO_FIT, k_pareto_fit, dim3((unsigned)((pc + 7) / 8 * 8 * 2)), dim3(kParetoNT), lds,
-               (const double*)so.keys, M, pc, (const i64*)(d_tail + p0), so.keys_free, w.lg, gmax, a.d_res, kParField0);
-    }
-    double* h = ctx->pareto_host.as<double>();
-    HIP_TRY(ctx, hipMemcpyAsync(h, d_res, sizeof(double) * (size_t)kParFields * (size_t)P, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    prof_resolve(ctx);
-    double nbad = 0.0;
-    for (i64 p0 = 0; p0 < P; p0 += pcmax) {
-        const i64 pc = (P - p0 < pcmax) ? P - p0 : pcmax;
-        const double* r = h + (size_t)kParFields * (size_t)p0;
-        for (i64 p = 0; p < pc; ++p) {
-            nbad += r[(size_t)R_BAD * pc + p];
-            const double kl = r[(size_t)kParField0 * pc + p], kr = r[(size_t)(kParField0 + 1) * pc + p];
-            if (out->khat_left) out->khat_left[p0 + p] = kl;
-            if (out->khat_right) out->khat_right[p0 + p] = kr;
-            if (out->khat) out->khat[p0 + p] = (kr > kl) ? kr : kl;     // Python's max(left, right)
-            if (out->ndraws_tail) out->ndraws_tail[p0 + p] = teff[(size_t)(p0 + p)];
-        }
-    }
-    if (nbad > 0.0) return fail(ctx, MCR_ENONFINITE, "draws contain %.0f non-finite value(s)", nbad);
-    return MCR_OK;
+        LAUNCH(ctx, K_PARETO_FIT, k_pareto_fit, dim3((unsigned)((a.pc + 7) / 8 * 8 * 2)), dim3(kParetoNT), lds,
+               (const double*)so.keys, M, a.pc, (const i64*)(d_tail + p0), so.keys_free, lg, gmax, a.d_res, kParField0);
+        return MCR_OK;
+    });
+    if (rc) return rc;
+    return pooled_results(ctx, ctx->pareto_host, d_res, kParFields, P, pcmax, [&](const double* r, i64 pc, i64 p0, i64 p) {
+        const double kl = r[(size_t)kParField0 * pc + p], kr = r[(size_t)(kParField0 + 1) * pc + p];
+        if (out->khat_left) out->khat_left[p0 + p] = kl;
+        if (out->khat_right) out->khat_right[p0 + p] = kr;
+        if (out->khat) out->khat[p0 + p] = (kr > kl) ? kr : kl;     // Python's max(left, right)
+        if (out->ndraws_tail) out->ndraws_tail[p0 + p] = teff[(size_t)(p0 + p)];
+    });
 }
 
 static void pareto_fill_nan(const mcr_pareto* o, i64 P)
@@ -2273,22 +2346,12 @@ int mcr_pareto_khat(mcr_ctx* ctx, const void* draws, int dtype, int64_t C, int64
                     int64_t sp, const int64_t* ndraws_tail, mcr_pareto* out)
 {
     if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
-    {
-        std::vector<i64> teff;                 // (the device entry checks again: the errors come before the upload)
-        const int rc = pareto_check(ctx, draws, dtype, C, N, P, ndraws_tail, out, teff);
-        if (rc) return rc;
-    }
-    const i64 ext = tensor_extent(C, N, P, sc, sn, sp);
-    if (ext < 0) return fail(ctx, MCR_EINVAL, "negative strides are not supported");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    void* X = ctx->stage.p;
-    if (ext > 0) {
-        const size_t es = dtype == MCR_F64 ? 8 : 4;
-        const int rc = stage_buffers(ctx, {(size_t)ext * es}, &X);
-        if (rc) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(X, draws, (size_t)ext * es, hipMemcpyHostToDevice, ctx->stream));
-    }
-    return mcr_pareto_khat_dev(ctx, X ? X : draws, dtype, C, N, P, sc, sn, sp, ndraws_tail, out);
+    std::vector<i64> teff;                     // (the device entry checks again: the errors come before the upload)
+    int rc = pareto_check(ctx, draws, dtype, C, N, P, ndraws_tail, out, teff);
+    const void* X = nullptr;
+    if (!rc) rc = pooled_upload(ctx, draws, dtype, C, N, P, sc, sn, sp, &X);
+    if (rc) return rc;
+    return mcr_pareto_khat_dev(ctx, X, dtype, C, N, P, sc, sn, sp, ndraws_tail, out);
 }
 
 int64_t mcr_pareto_tail_length(int64_t M, double r_eff)
@@ -2314,6 +2377,144 @@ int mcr_pareto_fit_host(const double* sorted, int64_t M, int64_t ndraws_tail, do
     }
     if (khat_left) *khat_left = kl;
     if (khat_right) *khat_right = kr;
+    return MCR_OK;
+}
+
+// ---- Highest-density intervals (mcr_hdi.hpp) ----------------------------------------------------------------------------
+constexpr int kHdiField0 = kPoolField0;
+constexpr int hdi_fields(int nprob) { return kHdiField0 + 3 * nprob; }     // + lo, hi, index of every probability
+
+static_assert(kHdiSlice == MCR_HDI_SLICE && kHdiMaxProbs == MCR_HDI_MAX_PROBS, "mcmcref_hip.h states the slice and the cap");
+static_assert((kHdiSlice & (kHdiSlice - 1)) == 0, "a slice is a power of two");
+
+// Behind the pipeline's buffers: one candidate per (parameter, probability, slice), for the most slices a probability can
+// need (inc = 0: W = M) -- the plan knows the number of probabilities, not their values.
+static HdiCand* carve_hdi(Carve& cv, const PipeIn& a, int nprob)
+{
+    return cv.take<HdiCand>((size_t)a.pc * (size_t)nprob * (size_t)hdi_slices(a.M));
+}
+
+// Parameters per workspace chunk of an HDI call: what fits, and no more than k_hdi_window's one-dimensional grid holds.
+static int plan_hdi(mcr_ctx* ctx, i64 M, i64 P, int nprob, bool ingest, i64& pcmax)
+{
+    const i64 grid_hi = ((i64)0x7FFFFFFFll / ((i64)nprob * hdi_slices(M))) / 8 * 8;      // >= 4096: M < 2^31, nprob <= 16
+    return plan_pooled(ctx, M, P < grid_hi ? P : grid_hi, ingest, [&](Carve& cv, PipeIn& a) { carve_hdi(cv, a, nprob); }, pcmax);
+}
+
+// inc = floor(prob * M) of every probability: one rounded product.
+static int hdi_offsets(mcr_ctx* ctx, const double* probs, int nprob, i64 M, HdiArgs& h)
+{
+    if (nprob < 1 || nprob > kHdiMaxProbs) return fail(ctx, MCR_EINVAL, "nprob must be in [1, %d]; got %d", kHdiMaxProbs, nprob);
+    if (!probs) return fail(ctx, MCR_EINVAL, "probs is NULL");
+    h.nprob = nprob;
+    for (int j = 0; j < nprob; ++j) {
+        if (!(probs[j] > 0.0 && probs[j] < 1.0)) return fail(ctx, MCR_EINVAL, "probs[%d] = %g: a probability must lie in (0, 1)", j, probs[j]);
+        h.inc[j] = (i64)std::floor(probs[j] * (double)M);
+    }
+    return MCR_OK;
+}
+
+static int hdi_check(mcr_ctx* ctx, const void* draws, int dtype, i64 C, i64 N, i64 P, const double* probs, int nprob,
+                     const mcr_hdi_out* out, HdiArgs& h)
+{
+    const int rc = pooled_check(ctx, "mcr_hdi", draws, dtype, C, N, P, out);
+    return rc ? rc : hdi_offsets(ctx, probs, nprob, C * N, h);
+}
+
+static void hdi_store(const mcr_hdi_out* o, i64 at, double lo, double hi, i64 index)
+{
+    if (o->lo) o->lo[at] = lo;
+    if (o->hi) o->hi[at] = hi;
+    if (o->index) o->index[at] = index;
+}
+
+static int hdi_run(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i64 P, i64 sc, i64 sn, i64 sp,
+                   const HdiArgs& h, const mcr_hdi_out* out)
+{
+    const i64 M = C * N;
+    const int nprob = h.nprob, fields = hdi_fields(nprob), nsl = (int)hdi_slices(M);
+    const bool ingest = dtype == MCR_F32 || needs_ingest(C, N, P, sc, sn, sp);
+    i64 pcmax = 0;
+    int rc = plan_hdi(ctx, M, P, nprob, ingest, pcmax);
+    if (rc) return rc;
+    double* d_res = nullptr;
+    rc = carve(ctx, ctx->hdi_dev, [&](Carve& cv) { d_res = cv.take<double>((size_t)fields * (size_t)P); });
+    if (rc) return rc;
+    HdiCand* part = nullptr;
+    rc = pooled_chunks(ctx, draws_dev, dtype, C, N, P, sc, sn, sp, ingest, pcmax, fields, d_res,
+                       [&](Carve& cv, PipeIn& a) { part = carve_hdi(cv, a, nprob); },
+                       [&](const PipeIn& a, const Sorted& so, i64) -> int {
+        LAUNCH(ctx, K_HDI_WINDOW, k_hdi_window, dim3((unsigned)((a.pc + 7) / 8 * 8 * nprob * nsl)), dim3(kHdiNT), 0,
+               (const double*)so.keys, M, a.pc, h, nsl, part);
+        LAUNCH(ctx, K_HDI_PICK, k_hdi_pick, dim3((unsigned)((a.pc * nprob + 63) / 64)), dim3(64), 0,
+               (const double*)so.keys, M, a.pc, h, nsl, (const HdiCand*)part, a.d_res, kHdiField0);
+        return MCR_OK;
+    });
+    if (rc) return rc;
+    return pooled_results(ctx, ctx->hdi_host, d_res, fields, P, pcmax, [&](const double* r, i64 pc, i64 p0, i64 p) {
+        for (int j = 0; j < nprob; ++j) {
+            const double* f = r + (size_t)(kHdiField0 + 3 * j) * pc + p;
+            hdi_store(out, (p0 + p) * nprob + j, f[0], f[pc], (i64)f[2 * pc]);
+        }
+    });
+}
+
+int mcr_hdi_plan(mcr_ctx* ctx, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc, int64_t sn, int64_t sp, int nprob,
+                 int64_t* params_per_chunk)
+{
+    if (!ctx || !params_per_chunk) return fail(ctx, MCR_EINVAL, "mcr_hdi_plan: NULL argument");
+    if (nprob < 1 || nprob > kHdiMaxProbs) return fail(ctx, MCR_EINVAL, "nprob must be in [1, %d]; got %d", kHdiMaxProbs, nprob);
+    if (C < 1 || N < 1 || P < 1 || C > (i64)0x7FFFFFFFll / N || C * N >= (i64)0x7FFFFFFFll) { *params_per_chunk = 0; return MCR_OK; }
+    i64 pcmax = 0;
+    const int rc = plan_hdi(ctx, C * N, P, nprob, dtype == MCR_F32 || needs_ingest(C, N, P, sc, sn, sp), pcmax);
+    if (rc) return rc;
+    *params_per_chunk = pcmax;
+    return MCR_OK;
+}
+
+int mcr_hdi_dev(mcr_ctx* ctx, const void* draws_dev, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc, int64_t sn,
+                int64_t sp, const double* probs, int nprob, mcr_hdi_out* out)
+{
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    HdiArgs h{};
+    int rc = hdi_check(ctx, draws_dev, dtype, C, N, P, probs, nprob, out, h);
+    if (rc || P == 0) return rc;
+    if (C * N == 0) {
+        for (i64 at = 0; at < P * nprob; ++at) hdi_store(out, at, NAN, NAN, -1);
+        return MCR_OK;
+    }
+    if (tensor_extent(C, N, P, sc, sn, sp) < 0) return fail(ctx, MCR_EINVAL, "negative strides are not supported");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = hdi_run(ctx, draws_dev, dtype, C, N, P, sc, sn, sp, h, out);
+    return rc ? drain(ctx, rc, true) : rc;
+}
+
+int mcr_hdi(mcr_ctx* ctx, const void* draws, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc, int64_t sn, int64_t sp,
+            const double* probs, int nprob, mcr_hdi_out* out)
+{
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    HdiArgs h{};                               // (the device entry checks again: the errors come before the upload)
+    int rc = hdi_check(ctx, draws, dtype, C, N, P, probs, nprob, out, h);
+    const void* X = nullptr;
+    if (!rc) rc = pooled_upload(ctx, draws, dtype, C, N, P, sc, sn, sp, &X);
+    if (rc) return rc;
+    return mcr_hdi_dev(ctx, X, dtype, C, N, P, sc, sn, sp, probs, nprob, out);
+}
+
+int mcr_hdi_sorted_host(const double* sorted, int64_t M, const double* probs, int nprob, double* lo, double* hi, int64_t* index)
+{
+    if (M < 0 || (M > 0 && !sorted) || !probs || nprob < 1 || nprob > kHdiMaxProbs) return MCR_EINVAL;
+    for (int j = 0; j < nprob; ++j)
+        if (!(probs[j] > 0.0 && probs[j] < 1.0)) return MCR_EINVAL;
+    for (int j = 0; j < nprob; ++j) {
+        const i64 inc = (i64)std::floor(probs[j] * (double)M), W = M - inc;
+        HdiCand best = HdiCand::none();
+        for (i64 i = 0; i < W; ++i) hdi_take(best, sorted[i + inc] - sorted[i], i);
+        const bool ok = best.i >= 0 && best.i < W;
+        if (lo) lo[j] = ok ? sorted[best.i] : NAN;
+        if (hi) hi[j] = ok ? sorted[best.i + inc] : NAN;
+        if (index) index[j] = ok ? best.i : -1;
+    }
     return MCR_OK;
 }
 

@@ -72,6 +72,14 @@ class Pareto(C.Structure):
     _fields_ = [("khat", _dp), ("khat_left", _dp), ("khat_right", _dp), ("ndraws_tail", _ip)]
 
 
+MCR_HDI_MAX_PROBS = 16                                      # probabilities of a Context.hdi call
+MCR_HDI_SLICE = 16384                                       # windows k_hdi_window gives one workgroup
+
+
+class Hdi(C.Structure):
+    _fields_ = [("lo", _dp), ("hi", _dp), ("index", _ip)]
+
+
 class ModelDesc(C.Structure):
     _fields_ = [("draws_dev", C.c_void_p), ("dtype", C.c_int), ("min_chains", C.c_int),
                 ("C", C.c_int64), ("N", C.c_int64), ("P", C.c_int64),
@@ -163,6 +171,10 @@ SYMBOLS = {
     "mcr_pareto_plan": (C.c_int, [C.c_void_p, C.c_int] + [_I64] * 6 + [C.POINTER(C.c_int64)]),
     "mcr_pareto_tail_length": (C.c_int64, [_I64, C.c_double]),
     "mcr_pareto_fit_host": (C.c_int, [_dp, _I64, _I64, _dp, _dp, C.POINTER(C.c_int64)]),
+    "mcr_hdi": (C.c_int, [C.c_void_p] + _TENSOR + [_dp, C.c_int, C.POINTER(Hdi)]),
+    "mcr_hdi_dev": (C.c_int, [C.c_void_p] + _TENSOR + [_dp, C.c_int, C.POINTER(Hdi)]),
+    "mcr_hdi_plan": (C.c_int, [C.c_void_p, C.c_int] + [_I64] * 6 + [C.c_int, C.POINTER(C.c_int64)]),
+    "mcr_hdi_sorted_host": (C.c_int, [_dp, _I64, _dp, C.c_int, _dp, _dp, _ip]),
     "mcr_covariance": (C.c_int, [C.c_void_p, _dp, _I64, _I64, _dp]),
     "mcr_covariance_dev": (C.c_int, [C.c_void_p, C.c_void_p, _I64, _I64, C.c_void_p]),
     "mcr_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
@@ -397,6 +409,22 @@ def pareto_companions(khat: np.ndarray, M: int) -> tuple[np.ndarray, float]:
         min_ss = np.where(np.isnan(k), np.nan, min_ss)
         threshold = 1.0 - 1.0 / math.log10(M) if M > 1 else float("-inf") if M == 1 else float("nan")
     return min_ss, threshold
+
+
+def hdi_sorted_host(sorted_draws, prob=0.94):
+    """(lo, hi, index) of the highest-density interval(s) of an ASCENDING float64 array by the library's host routine
+    (mcr_hdi_sorted_host: the device's comparison; no device): floats and an int for a float `prob`, arrays of len(prob)
+    for a sequence.  ValueError for a probability outside (0, 1), none or more than MCR_HDI_MAX_PROBS of them."""
+    x = np.ascontiguousarray(sorted_draws, dtype=np.float64)
+    pr = np.ascontiguousarray(np.atleast_1d(prob), dtype=np.float64)
+    n = max(int(pr.size), 1)
+    lo, hi, idx = np.full(n, np.nan), np.full(n, np.nan), np.full(n, -1, dtype=np.int64)
+    rc = load_library().mcr_hdi_sorted_host(_as_dp(x), x.size, _as_dp(pr), int(pr.size), _as_dp(lo), _as_dp(hi), _as_ip(idx))
+    if rc != MCR_OK:
+        raise ValueError(f"mcr_hdi_sorted_host: bad argument (prob = {prob})")
+    if np.ndim(prob) == 0:
+        return float(lo[0]), float(hi[0]), int(idx[0])
+    return lo, hi, idx
 
 
 class PqImage:
@@ -1282,6 +1310,37 @@ class Context:
         """Parameters per workspace chunk of a pareto_khat call on this tensor (mcr_pareto_plan)."""
         v = C.c_int64(0)
         self._check(self.lib.mcr_pareto_plan(self.handle, *self._pareto_tensor(t, "pcn")[0], C.byref(v)))
+        return int(v.value)
+
+    def _hdi_tensor(self, draws, layout: str):
+        targs, ptr, fn = self._pareto_tensor(draws, layout)            # the same pooling of a ragged tensor
+        return targs, ptr, self.lib.mcr_hdi_dev if fn is self.lib.mcr_pareto_khat_dev else self.lib.mcr_hdi
+
+    def hdi(self, draws, layout: str = "pcn", prob=0.94) -> dict:
+        """Highest-density interval(s) of every parameter (mcr_hdi: ArviZ's unimodal hdi, the shortest interval holding
+        floor(prob * M) + 1 of the M pooled draws) of a host array or a DeviceTensor; the chains are pooled, so a ragged
+        tensor is accepted.  prob: a float, or a sequence of up to MCR_HDI_MAX_PROBS.  "lo", "hi" (float64) and "index"
+        (int64, the rank of lo in the ascending order; -1 with NaN endpoints when there is no window) are [P] arrays for
+        a float and [P][nprob] for a sequence; "prob" is what was asked for."""
+        targs, ptr, fn = self._hdi_tensor(draws, layout)
+        P = targs[3]
+        pr = np.ascontiguousarray(np.atleast_1d(prob), dtype=np.float64)
+        if pr.ndim != 1:
+            raise ValueError("prob must be a float or a flat sequence of floats")
+        n = int(pr.size)
+        lo, hi = np.full((max(P, 1), max(n, 1)), np.nan), np.full((max(P, 1), max(n, 1)), np.nan)
+        idx = np.full((max(P, 1), max(n, 1)), -1, dtype=np.int64)
+        out = Hdi(lo=_as_dp(lo), hi=_as_dp(hi), index=_as_ip(idx))
+        self._check(fn(self.handle, ptr, *targs, _as_dp(pr), n, C.byref(out)))
+        res = {"lo": lo[:P, :n], "hi": hi[:P, :n], "index": idx[:P, :n]}
+        if np.ndim(prob) == 0:
+            return {**{k: v[:, 0] for k, v in res.items()}, "prob": float(prob)}
+        return {**res, "prob": pr}
+
+    def hdi_params_per_chunk(self, t: "DeviceTensor", nprob: int = 1) -> int:
+        """Parameters per workspace chunk of an hdi call with nprob probabilities on this tensor (mcr_hdi_plan)."""
+        v = C.c_int64(0)
+        self._check(self.lib.mcr_hdi_plan(self.handle, *self._hdi_tensor(t, "pcn")[0], int(nprob), C.byref(v)))
         return int(v.value)
 
     def covariance(self, draws) -> np.ndarray:

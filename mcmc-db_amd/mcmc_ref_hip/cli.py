@@ -12,6 +12,7 @@ this package's own: the chain files of a CmdStan run, parsed on the GPU, printed
 parameter and, with `--sliced K`, along K random directions of the joint distribution; exits like `compare`).
 `nested-rhat FILE --superchains K` prints nested R-hat, the diagnostic for many short chains, of a draws table.
 `pareto-khat FILE` prints the Pareto k-hat of every parameter's tails: whether a mean and a std of the draws can be trusted.
+`hdi FILE` prints the highest-density interval(s) of every parameter: the shortest interval holding a share of the draws.
 """
 from __future__ import annotations
 
@@ -187,6 +188,21 @@ def pareto_khat_cmd(file: Path, params: str | None, tail_draws: int | None, form
     _echo_stats(stats, format_)
 
 
+@main.command("hdi")
+@click.argument("file", type=click.Path(path_type=Path, exists=True, dir_okay=False))
+@click.option("--params", default=None, help="Comma-separated parameter list")
+@click.option("--prob", "probs", multiple=True, type=float, help="Share of the draws inside the interval; may be repeated (default: 0.94)")
+@click.option("--format", "format_", type=click.Choice(["table", "json"], case_sensitive=False), default="table")
+def hdi_cmd(file: Path, params: str | None, probs: tuple[float, ...], format_: str) -> None:
+    """Highest-density intervals (ArviZ's unimodal hdi) of the pooled draws of a table (no counterpart in the reference):
+    per probability q the columns hdi_lo_q and hdi_hi_q."""
+    try:
+        stats = convert_mod.hdi_file(file, params=params.split(",") if params else None, prob=probs or (0.94,))
+    except (ValueError, KeyError, IndexError) as exc:
+        raise click.ClickException(str(exc)) from exc
+    _echo_stats(stats, format_)
+
+
 @main.command("diagnostics")
 @click.argument("model")
 @click.option("--format", "format_", type=click.Choice(["table", "csv", "json"], case_sensitive=False), default="table")
@@ -245,21 +261,27 @@ def compare_cmd(model: str, actual_path: Path, tolerance: float, format_: str) -
 @click.option("--sliced-ks-max", default=None, type=float, help="Fail when the largest sliced KS exceeds this")
 @click.option("--sliced-w1-max", default=None, type=float, help="Fail when the largest sliced W1 exceeds this")
 @click.option("--khat-max", default=None, type=float, help="Fail a parameter whose Pareto k-hat of the actual draws exceeds this")
+@click.option("--hdi-prob", default=None, type=float, help="Report the highest-density intervals of this share of both samples")
+@click.option("--hdi-tol", default=None, type=float,
+              help="Fail a parameter whose HDI endpoints differ by more than this share of the reference interval's width")
 @click.option("--format", "format_", type=click.Choice(["table", "json"], case_sensitive=False), default="table")
 def validate_cmd(model: str, actual_path: Path, tolerance: float, metrics: str, ks_max, w1_scaled_max, sliced: int, sliced_seed: int,
-                 sliced_ks_max, sliced_w1_max, khat_max, format_: str) -> None:
+                 sliced_ks_max, sliced_w1_max, khat_max, hdi_prob, hdi_tol, format_: str) -> None:
     """The reference's mean / std gate plus per-parameter KS / Wasserstein-1 and, with --sliced K, the same distances
     along K random directions of the joint distribution (validate.validate; no counterpart in the reference)."""
     from .validate import validate
     try:
         result = validate(model, _read_actual_csv(actual_path), tolerance=tolerance, metrics=tuple(metrics.split(",")),
                           ks_max=ks_max, w1_scaled_max=w1_scaled_max, sliced=sliced, sliced_seed=sliced_seed,
-                          sliced_ks_max=sliced_ks_max, sliced_w1_max=sliced_w1_max, khat_max=khat_max)
+                          sliced_ks_max=sliced_ks_max, sliced_w1_max=sliced_w1_max, khat_max=khat_max,
+                          hdi_prob=hdi_prob, hdi_tol=hdi_tol)
     except ValueError as exc:
         raise click.ClickException(str(exc)) from exc
+    with_hdi = hdi_prob is not None or hdi_tol is not None
     if format_ == "json":
         details = {p: {k: vars(v) for k, v in ms.items()} for p, ms in result.compare.details.items()}
-        click.echo(json.dumps({"passed": result.passed, "failures": result.failures,
+        hdi_keys = {"hdi_ref": result.hdi_ref, "hdi_actual": result.hdi_actual} if with_hdi else {}    # only when asked for
+        click.echo(json.dumps({**hdi_keys, "passed": result.passed, "failures": result.failures,
                                "compare": {"passed": result.compare.passed, "failures": result.compare.failures,
                                            "details": details},
                                "ks": result.ks, "wasserstein": result.wasserstein,
@@ -272,6 +294,10 @@ def validate_cmd(model: str, actual_path: Path, tolerance: float, metrics: str, 
             click.echo(f"- {failure}")
         if khat_max is not None:               # the two k-hat columns (the JSON form always has them)
             _print_table({p: {"khat_ref": result.khat_ref[p], "khat_actual": result.khat_actual[p]} for p in result.khat_actual})
+        if with_hdi:
+            _print_table({p: {"hdi_lo_ref": result.hdi_ref[p][0], "hdi_hi_ref": result.hdi_ref[p][1],
+                              "hdi_lo_actual": result.hdi_actual[p][0], "hdi_hi_actual": result.hdi_actual[p][1]}
+                          for p in result.hdi_actual})
     raise SystemExit(0 if result.passed else 2)
 
 

@@ -574,18 +574,24 @@ def _read_input(path: Path):
     raise ValueError(f"Unsupported input format: {path}")
 
 
-def nested_rhat_file(path: Path, superchains: int, params: Iterable[str] | None = None,
-                     context=None) -> dict[str, dict[str, float]]:
-    """Nested R-hat of every parameter of a draws table (a `.csv` or chain-list `.json.zip`, read on the host): any
-    number of equal-length chains, dealt to `superchains` superchains in blocks, in chain-id order.  Per parameter:
-    nrhat, nrhat_bulk, nrhat_tail, nrhat_raw (Context.nested_rhat)."""
-    table = _ensure_chain_draw(_read_input(Path(path)))
+def _table_and_names(table, params: Iterable[str] | None):
+    """The table with its bookkeeping columns, and the parameter columns asked for (all of them for None)."""
+    table = _ensure_chain_draw(table)
     names = [c for c in table.column_names if c not in ("chain", "draw")]
     if params is not None:
         missing = [p for p in params if p not in names]
         if missing:
             raise ValueError(f"Unknown parameter(s): {', '.join(missing)}")
         names = list(params)
+    return table, names
+
+
+def nested_rhat_file(path: Path, superchains: int, params: Iterable[str] | None = None,
+                     context=None) -> dict[str, dict[str, float]]:
+    """Nested R-hat of every parameter of a draws table (a `.csv` or chain-list `.json.zip`, read on the host): any
+    number of equal-length chains, dealt to `superchains` superchains in blocks, in chain-id order.  Per parameter:
+    nrhat, nrhat_bulk, nrhat_tail, nrhat_raw (Context.nested_rhat)."""
+    table, names = _table_and_names(_read_input(Path(path)), params)
     if not names:
         return {}
     x, counts = table_to_tensor(table, names)
@@ -604,13 +610,7 @@ def pareto_khat_file(path: Path, params: Iterable[str] | None = None, ndraws_tai
     """Pareto k-hat of every parameter of a draws table (a `.csv` or chain-list `.json.zip`, read on the host); the chains
     are pooled and may differ in length.  Per parameter: khat, khat_left, khat_right, ndraws_tail, min_ss
     (Context.pareto_khat); `ndraws_tail`: the tail length for every parameter instead of the default."""
-    table = _ensure_chain_draw(_read_input(Path(path)))
-    names = [c for c in table.column_names if c not in ("chain", "draw")]
-    if params is not None:
-        missing = [p for p in params if p not in names]
-        if missing:
-            raise ValueError(f"Unknown parameter(s): {', '.join(missing)}")
-        names = list(params)
+    table, names = _table_and_names(_read_input(Path(path)), params)
     if not names:
         return {}
     if ndraws_tail is not None and ndraws_tail < 1:
@@ -621,6 +621,31 @@ def pareto_khat_file(path: Path, params: Iterable[str] | None = None, ndraws_tai
         r = ctx.pareto_khat(x.reshape(len(names), 1, -1), "pcn", ndraws_tail=ndraws_tail)
     keys = ("khat", "khat_left", "khat_right", "ndraws_tail", "min_ss")
     return {n: {k: (int if k == "ndraws_tail" else float)(r[k][i]) for k in keys} for i, n in enumerate(names)}
+
+
+def hdi_file(path: Path, params: Iterable[str] | None = None, prob: Iterable[float] = (0.94,),
+             context=None) -> dict[str, dict[str, float]]:
+    """Highest-density intervals of every parameter of a draws table (a `.csv` or chain-list `.json.zip`, read on the
+    host); the chains are pooled and may differ in length.  Per parameter and probability q of `prob`: `hdi_lo_q` and
+    `hdi_hi_q`, q printed like `format(q, "g")` (Context.hdi).  A `.parquet` draws file of the store is read as well."""
+    path = Path(path)
+    if path.suffix == ".parquet":
+        import pyarrow.parquet as pq
+        table = pq.read_table(path)
+    else:
+        table = _read_input(path)
+    table, names = _table_and_names(table, params)
+    probs = [float(q) for q in prob]
+    if not probs or len(probs) > _ffi.MCR_HDI_MAX_PROBS or not all(0.0 < q < 1.0 for q in probs):
+        raise ValueError(f"prob: 1 to {_ffi.MCR_HDI_MAX_PROBS} probabilities inside (0, 1); got {probs}")
+    if not names:
+        return {}
+    x, _ = table_to_tensor(table, names)
+    ctx = context or _ffi.default_context()
+    with _ffi.value_errors():
+        r = ctx.hdi(x.reshape(len(names), 1, -1), "pcn", prob=probs)
+    return {n: {f"hdi_{k}_{q:g}": float(r[k][i, j]) for j, q in enumerate(probs) for k in ("lo", "hi")}
+            for i, n in enumerate(names)}
 
 
 def _ensure_chain_draw(table):

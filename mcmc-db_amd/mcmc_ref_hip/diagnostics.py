@@ -8,7 +8,8 @@ autocovariance sum) runs in libmcmcref_hip; chains may be ragged.
 `nested_rhat` is not the reference's: the diagnostic for many short chains (Margossian et al., "Nested R-hat: assessing
 the convergence of Markov chain Monte Carlo when running many short chains"; posterior::rhat_nested), for any number
 of equal-length chains.  `pareto_khat` is not the reference's either: the tail diagnostic for the draws behind a mean
-and a std (Vehtari et al., "Pareto smoothed importance sampling"; posterior::pareto_khat), on the pooled chains.
+and a std (Vehtari et al., "Pareto smoothed importance sampling"; posterior::pareto_khat), on the pooled chains.  Nor is
+`hdi`: the highest-density interval of the pooled chains (ArviZ's unimodal `hdi`).
 """
 from __future__ import annotations
 
@@ -117,3 +118,14 @@ def pareto_khat(chains: Sequence[Sequence[float]], *, r_eff=None, ndraws_tail=No
     limit theorem holds, from 0.5 the mean converges slowly and a std is not trustworthy, from 0.7 the estimates are
     unreliable, from 1 no mean exists.  NaN for fewer than 10 draws or constant tails."""
     return pareto_khat_detail(chains, r_eff=r_eff, ndraws_tail=ndraws_tail, context=context)["khat"]
+
+
+def hdi(chains: Sequence[Sequence[float]], prob: float = 0.94, *, context=None) -> tuple[float, float]:
+    """The highest-density interval of ONE parameter given as chains of any lengths (they are pooled): the shortest
+    interval that holds floor(prob * M) + 1 of the M draws, the first of several equally short ones (Context.hdi; ArviZ's
+    unimodal hdi).  (NaN, NaN) without draws."""
+    x = np.concatenate([np.asarray(c, dtype=np.float64).reshape(-1) for c in chains]) if len(chains) else np.zeros(0)
+    ctx = context or _ffi.default_context()
+    with _ffi.value_errors():
+        res = ctx.hdi(x.reshape(1, 1, -1), "pcn", prob=float(prob))
+    return float(res["lo"][0]), float(res["hi"][0])

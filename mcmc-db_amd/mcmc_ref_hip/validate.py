@@ -37,6 +37,8 @@ class ValidateResult:
     #                                              "worst_direction" {param: weight in standardised space}
     khat_ref: dict[str, float] = field(default_factory=dict)       # Pareto k-hat (the larger tail) of the reference draws
     khat_actual: dict[str, float] = field(default_factory=dict)    # ... and of `actual`
+    hdi_ref: dict[str, tuple[float, float]] = field(default_factory=dict)      # (lo, hi) of the reference draws' highest-density
+    hdi_actual: dict[str, tuple[float, float]] = field(default_factory=dict)   # interval and of `actual`'s: only with hdi_prob / hdi_tol
 
 
 def sliced_directions(k: int, std, seed: int = 4711) -> tuple[np.ndarray, np.ndarray]:
@@ -65,8 +67,11 @@ def validate(model: str, actual: Mapping[str, Sequence[float]], tolerance: float
              metrics: Sequence[str] = ("mean", "std"), ks_max: float | None = None,
              w1_scaled_max: float | None = None, store: DataStore | None = None, context=None, sliced: int = 0,
              sliced_seed: int = 4711, sliced_ks_max: float | None = None,
-             sliced_w1_max: float | None = None, khat_max: float | None = None) -> ValidateResult:
-    """khat_max: a parameter whose `khat_actual` (Context.pareto_khat, default tail length) exceeds it is a failure;
+             sliced_w1_max: float | None = None, khat_max: float | None = None, hdi_prob: float | None = None,
+             hdi_tol: float | None = None) -> ValidateResult:
+    """hdi_prob / hdi_tol: when either is given (hdi_prob is 0.94 then), `hdi_ref` / `hdi_actual` hold every parameter's
+    highest-density interval (Context.hdi) -- where the mass lies, which q5 / q50 / q95 alone do not say; with hdi_tol a
+    parameter fails when an endpoint is off by more than hdi_tol times the reference interval's own width.  khat_max: a parameter whose `khat_actual` (Context.pareto_khat, default tail length) exceeds it is a failure;
     without it the two k-hat columns are information only.  sliced=K > 0: K directions `sliced_directions(K, reference std, sliced_seed)` around the reference means, one
     `Context.sliced_two_sample` call; the result's `sliced_ks` / `sliced_w1` are the maxima over the directions and
     `sliced` holds the detail.  `sliced_ks_max` / `sliced_w1_max` turn them into failures; without them `passed` is what
@@ -105,9 +110,25 @@ def validate(model: str, actual: Mapping[str, Sequence[float]], tolerance: float
     else:
         for p in params:
             khat_act[p] = float(ctx.pareto_khat(np.asarray(actual[p], dtype=np.float64).reshape(1, 1, -1), "pcn")["khat"][0])
+    hdi_ref: dict[str, tuple[float, float]] = {}
+    hdi_act: dict[str, tuple[float, float]] = {}
+    if (hdi_prob is not None or hdi_tol is not None) and params:
+        prob = 0.94 if hdi_prob is None else float(hdi_prob)
+        with _ffi.value_errors():
+            groups = [(params, ref), (params, act)] if len(lens) == 1 else \
+                [(params, ref)] + [([p], np.asarray(actual[p], dtype=np.float64)[None, :]) for p in params]
+            for into, (names, x) in zip([hdi_ref] + [hdi_act] * len(groups), groups):
+                r = ctx.hdi(x.reshape(len(names), 1, -1), "pcn", prob=prob)
+                into.update({p: (float(r["lo"][i]), float(r["hi"][i])) for i, p in enumerate(names)})
     failures = list(cmp_res.failures)
     if khat_max is not None:
         failures += [f"{p}.khat_actual={khat_act[p]:.3g} > {khat_max}" for p in params if not khat_act[p] <= khat_max]
+    if hdi_tol is not None:
+        for p in params:
+            (lr, hr), (la, ha) = hdi_ref[p], hdi_act[p]
+            off = max(abs(la - lr), abs(ha - hr))
+            if not off <= hdi_tol * (hr - lr):
+                failures.append(f"{p}.hdi_offset={off:.3g} > {hdi_tol} * {hr - lr:.3g}")
     if ks_max is not None:
         failures += [f"{p}.ks={ks[p]:.3g} > {ks_max}" for p in params if not ks[p] <= ks_max]
     if w1_scaled_max is not None:
@@ -128,4 +149,4 @@ def validate(model: str, actual: Mapping[str, Sequence[float]], tolerance: float
             if sliced_w1_max is not None and not extra["sliced_w1"] <= sliced_w1_max:
                 failures.append(f"sliced.w1={extra['sliced_w1']:.3g} > {sliced_w1_max}")
     return ValidateResult(passed=not failures, compare=cmp_res, ks=ks, wasserstein=w1, wasserstein_scaled=scaled,
-                          failures=failures, khat_ref=khat_ref, khat_actual=khat_act, **extra)
+                          failures=failures, khat_ref=khat_ref, khat_actual=khat_act, hdi_ref=hdi_ref, hdi_actual=hdi_act, **extra)
