@@ -401,6 +401,74 @@ int mcr_hdi_sorted_host(const double* sorted, int64_t M, const double* probs, in
                         int64_t* index);
 #define MCR_HDI_MAX_PROBS 16          /* probabilities of a mcr_hdi call */
 #define MCR_HDI_SLICE 16384           /* windows k_hdi_window gives one workgroup */
+/* Autocorrelation functions and autocorrelation times: the autocorrelation of the RAW draws of every (parameter, chain)
+ * up to a maximum lag, the within-chain pooled autocorrelation per parameter, and the integrated autocorrelation time
+ * with Sokal's automatic window (posterior::autocorrelation, ArviZ's autocorr / plot_autocorr, emcee's integrated_time).
+ * ABSENT from the reference, whose only use of the time order is inside its ESS.  The ESS kernels here are not involved:
+ * they work on rank-normalised z, sum over chains, divide by n - lag and stop at the truncation lag.
+ * For one parameter and one chain x_0 ... x_{N-1}, maximum lag L, everything in IEEE double:
+ *     m     = (sum_i x_i) / N
+ *     d_i   = x_i - m
+ *     S_l   = sum_{i=0}^{N-l-1} d_i * d_{i+l}            l = 0 ... L
+ *     gamma_l = S_l / N                                  (flag MCR_ACF_UNBIASED: S_l / (N - l))
+ *     rho_l = gamma_l / gamma_0                          gamma_0 == 0 (a constant chain, or N == 1): every rho_l = NaN
+ * The biased form is the FFT-based arviz.autocorr / posterior::autocovariance, computed by direct sums; the unbiased one
+ * is the per-chain cov / (n - lag) of the reference's _autocorr (diagnostics.py:186-191).
+ * Integrated autocorrelation time, with the caller's window constant window_c (emcee's c; 5 is the usual value):
+ *     tau_W  = 2 (rho_0 + ... + rho_W) - 1               W = 0 ... L, a running sum left to right
+ *     window = the smallest W with W >= window_c * tau_W, or -1 when no W <= L satisfies it
+ *     tau    = tau_window, or tau_L when window == -1    (then a lower bound: the ACF has not decayed within L)
+ * NaN rho gives tau = NaN and window = -1.  This differs from emcee in one place: emcee returns the last index when no
+ * window is found; here that case is -1, so that it cannot be mistaken for a found window.
+ * Pooled over the C chains of a parameter (within-chain correlation: the chains are NOT concatenated):
+ *     gamma-bar_l = (sum_c gamma_{l,c}) / C in chain order c = 0 ... C-1,  rho-bar_l = gamma-bar_l / gamma-bar_0 (NaN
+ *     when that is 0); tau_pooled and window_pooled follow the same rule on rho-bar.
+ * One order of summation, a function of (N, l) and C alone:
+ *     m      lane j of 64 adds x_j, x_{j+64}, ... in index order; the 64 sums meet pairwise, v_j += v_{j+o} for j < o,
+ *            o = 32, 16, ... 1; m = v_0 / N.
+ *     S_l    the draws are cut into blocks of MCR_ACF_BLOCK consecutive i.  Block b: acc = +0, then
+ *            acc = fma(d_i, d_{i+l}, acc) for i = b B ... min(b B + B, N - l) - 1 ascending (an explicit fma on the device
+ *            and on the host).  S_l = ((0 + acc_0) + acc_1) + ... over all ceil(N / B) blocks in block order.
+ *     pooled, tau: left to right from +0, as written above.
+ * A (parameter, chain)'s outputs therefore have the same bits alone or at any place in a batch, under any workspace
+ * limit, in either layout, for aligned or misaligned rows, from the host or the device entry.  f32 draws are widened
+ * first by the ingest pass; the answer is that of the f64 call on the widened tensor.
+ * draws: host tensor addressed like mcr_summarize's.  out stays on the host; NULL members are skipped.  Synchronous.
+ * Limits: any C, C * N < 2^31 - 1, max_lag <= MCR_ACF_MAX_LAG: the products are direct, O(N * max_lag).  Larger lags, the
+ * full ACF by the FFT tier, and the ACF of the rank-normalised z codes are OUT OF SCOPE.
+ * MCR_EINVAL (message names the cause): a negative dimension, max_lag < 0, max_lag > N - 1 (when N >= 1), max_lag >
+ * MCR_ACF_MAX_LAG, unknown flag bits, window_c not finite or <= 0, negative strides, summaries in flight.
+ * MCR_ENONFINITE: NaN / Inf draws.  C * N == 0 fills NaN and -1, P == 0 writes nothing.  The context stays usable after
+ * every error.  The workspace is chunked over parameters (mcr_autocorr_plan reports the chunk).
+ * Kernels (mcr_acf.hpp): k_acf_mean, k_acf_products (the dense lag products, LDS-staged, 4 lags x 4 draws per thread and
+ * step), k_acf_finish (per chain), k_acf_pool (per parameter). */
+#define MCR_ACF_MAX_LAG   4096        /* the largest max_lag of a call */
+#define MCR_ACF_BLOCK     512         /* consecutive draws of one fma chain (part of the summation order) */
+#define MCR_ACF_UNBIASED  1           /* flags */
+typedef struct mcr_acf_out {          /* NULL members are skipped; L = max_lag */
+    double  *acf;                     /* [P][C][L+1] */
+    double  *var;                     /* [P][C]   gamma_0 */
+    double  *tau;                     /* [P][C] */
+    int64_t *window;                  /* [P][C] */
+    double  *acf_pooled;              /* [P][L+1] */
+    double  *tau_pooled;              /* [P] */
+    int64_t *window_pooled;           /* [P] */
+} mcr_acf_out;
+int mcr_autocorr(mcr_ctx* ctx, const void* draws, int dtype, int64_t C, int64_t N, int64_t P, int64_t stride_c,
+                 int64_t stride_n, int64_t stride_p, int64_t max_lag, int flags, double window_c, mcr_acf_out* out);
+/* The same on draws in this ctx's device memory; out stays on the host. */
+int mcr_autocorr_dev(mcr_ctx* ctx, const void* draws_dev, int dtype, int64_t C, int64_t N, int64_t P, int64_t stride_c,
+                     int64_t stride_n, int64_t stride_p, int64_t max_lag, int flags, double window_c, mcr_acf_out* out);
+/* Parameters per workspace chunk of such a call under the current workspace limit (0 for an empty shape).  MCR_ENOMEM
+ * when the limit does not fit one parameter; MCR_EINVAL for a max_lag the call would refuse. */
+int mcr_autocorr_plan(mcr_ctx* ctx, int dtype, int64_t C, int64_t N, int64_t P, int64_t stride_c, int64_t stride_n,
+                      int64_t stride_p, int64_t max_lag, int64_t* params_per_chunk);
+/* The same quantities of one parameter's chains in host memory, chains[C][N] row-major (host only, no ctx, no device);
+ * out as above with P = 1.  It runs the device's text in the device's summation order and uses only +, -, *, / and fma:
+ * its results equal the device's IN BITS (unlike mcr_pareto_fit_host, which goes through libm).  MCR_EINVAL as above
+ * (without a message), MCR_ENONFINITE for NaN / Inf draws. */
+int mcr_autocorr_host(const double* chains, int64_t C, int64_t N, int64_t max_lag, int flags, double window_c,
+                      mcr_acf_out* out);
 /* Population covariance matrix (ddof = 0, like compare.py:63) of P parameters over M pooled draws,
  * draws[P][M] host row-major -> cov[P][P].  The one dense contraction of the path: fp64 MFMA
  * (v_mfma_f64_16x16x4f64; LDS-staged 64 x 64 tiles, upper triangle, split over the draw axis).

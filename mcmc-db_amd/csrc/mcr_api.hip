@@ -31,6 +31,7 @@
 #include "mcr_fft.hpp"
 #include "mcr_ext.hpp"
 #include "mcr_nested.hpp"
+#include "mcr_acf.hpp"
 #include "mcr_pareto.hpp"
 #include "mcr_hdi.hpp"
 #include "mcr_parquet.hpp"
@@ -64,7 +65,8 @@ enum KernelId {
     K_JSON_INDEX, K_JSON_SCAN, K_JSON_PARSE,
     K_LAYOUT_SCAN, K_LAYOUT_KEYS, K_LAYOUT_HIST, K_LAYOUT_OFFSETS, K_LAYOUT_SCATTER, K_LAYOUT_BOUNDS,
     K_PQW_ENCODE, K_PQW_COMPACT, K_CSVW_FORMAT, K_CSVW_SCAN, K_CSVW_COMPACT, K_SELECT_ROWS, K_PROJECT,
-    K_CHAIN_MOMENTS, K_NESTED_COMBINE, K_PARETO_FIT, K_HDI_WINDOW, K_HDI_PICK, K_COUNT
+    K_CHAIN_MOMENTS, K_NESTED_COMBINE, K_PARETO_FIT, K_HDI_WINDOW, K_HDI_PICK,
+    K_ACF_MEAN, K_ACF_PRODUCTS, K_ACF_FINISH, K_ACF_POOL, K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {
     "k_ingest", "k_moments", "k_moments_final", "k_tile_sort", "k_merge", "k_order_stats", "k_rank_z",
@@ -75,7 +77,8 @@ const char* const kKernelNames[K_COUNT] = {
     "k_json_index", "k_json_scan", "k_json_parse",
     "k_layout_scan", "k_layout_keys", "k_layout_hist", "k_layout_offsets", "k_layout_scatter", "k_layout_bounds",
     "k_pqw_encode", "k_pqw_compact", "k_csvw_format", "k_csvw_scan", "k_csvw_compact", "k_select_rows", "k_project",
-    "k_chain_moments", "k_nested_combine", "k_pareto_fit", "k_hdi_window", "k_hdi_pick"};
+    "k_chain_moments", "k_nested_combine", "k_pareto_fit", "k_hdi_window", "k_hdi_pick",
+    "k_acf_mean", "k_acf_products", "k_acf_finish", "k_acf_pool"};
 
 struct EvPair { hipEvent_t a, b; int kid; };
 
@@ -195,6 +198,8 @@ struct mcr_ctx {
     PinBuf pareto_host{4};             // its results on the host
     DevBuf hdi_dev{4};                 // mcr_hdi: result table
     PinBuf hdi_host{4};                // its results on the host
+    DevBuf acf_dev{4};                 // mcr_autocorr: result arrays + the chains' non-finite counts
+    PinBuf acf_host{4};                // the counts on the host
     DevBuf guard_count;                // device counters (2 unsigned): band lags re-derived the reference's way (mcr_rho_guard_count),
                                        // tiles the tile sort sorted as pairs after all (mcr_tile_fallback_count)
 };
@@ -2516,6 +2521,216 @@ int mcr_hdi_sorted_host(const double* sorted, int64_t M, const double* probs, in
         if (index) index[j] = ok ? best.i : -1;
     }
     return MCR_OK;
+}
+
+// ---- Autocorrelation functions and times (mcr_acf.hpp) ---------------------------------------------------------------------
+static_assert(kAcfMaxLag == MCR_ACF_MAX_LAG && kAcfBlock == MCR_ACF_BLOCK, "mcmcref_hip.h states the lag limit and the block");
+
+struct AcfWs { double *X, *mean, *part, *gam; };
+
+// The workspace of a chunk of pc parameters: the ingest copy, the chains' means, the blocks' lag products, the chains' gamma.
+static void carve_acf(Carve& cv, AcfWs& w, i64 pc, i64 C, i64 N, const AcfGeom& g, bool ingest)
+{
+    const size_t chains = (size_t)pc * (size_t)C;
+    w.X = ingest ? cv.take<double>(chains * (size_t)N) : nullptr;
+    w.mean = cv.take<double>(chains);
+    w.part = cv.take<double>(chains * (size_t)g.nblk * (size_t)g.lp);
+    w.gam = cv.take<double>(chains * (size_t)g.lp);
+}
+
+// Parameters per workspace chunk of an autocorrelation call: what fits, and no more than k_acf_products' grid holds.
+static int plan_acf(mcr_ctx* ctx, i64 C, i64 N, i64 P, const AcfGeom& g, bool ingest, i64& pcmax)
+{
+    auto measure = [&](i64 pc) {
+        AcfWs w;
+        Carve m{nullptr};
+        carve_acf(m, w, pc, C, N, g, ingest);
+        return m.off;
+    };
+    const i64 grid_hi = ((i64)0x7FFFFFFFll / (g.nbg * g.nlb)) / 8 * 8;
+    pcmax = most_that_fit(P < grid_hi ? P : grid_hi, [&](i64 pc) { return measure(pc) <= ctx->ws_limit; });
+    if (!pcmax) return fail(ctx, MCR_ENOMEM, "one parameter needs %zu bytes of workspace; limit is %zu", measure(1), ctx->ws_limit);
+    return MCR_OK;
+}
+
+// The lag, flag and window arguments of a call on chains of N draws (`ctx` NULL: the host routine's, no message kept).
+static int acf_check_args(mcr_ctx* ctx, i64 N, i64 L, int flags, double wc)
+{
+    if (L < 0) return fail(ctx, MCR_EINVAL, "max_lag = %lld: a maximum lag must be >= 0", (long long)L);
+    if (L > kAcfMaxLag) return fail(ctx, MCR_EINVAL, "max_lag = %lld exceeds MCR_ACF_MAX_LAG = %lld", (long long)L, (long long)kAcfMaxLag);
+    if (N >= 1 && L > N - 1) return fail(ctx, MCR_EINVAL, "max_lag = %lld exceeds N - 1 = %lld", (long long)L, (long long)(N - 1));
+    if (flags & ~MCR_ACF_UNBIASED) return fail(ctx, MCR_EINVAL, "unknown flag bits 0x%x", (unsigned)(flags & ~MCR_ACF_UNBIASED));
+    if (!std::isfinite(wc) || !(wc > 0.0)) return fail(ctx, MCR_EINVAL, "window_c = %g: the window constant must be finite and > 0", wc);
+    return MCR_OK;
+}
+
+static int acf_check(mcr_ctx* ctx, const void* draws, int dtype, i64 C, i64 N, i64 P, i64 L, int flags, double wc, const mcr_acf_out* out)
+{
+    const int rc = pooled_check(ctx, "mcr_autocorr", draws, dtype, C, N, P, out);     // the tensor: as Pareto k-hat's and HDI's
+    return rc ? rc : acf_check_args(ctx, N, L, flags, wc);
+}
+
+// An empty chain (or none): NaN and -1 everywhere.
+static void acf_fill_nan(const mcr_acf_out* o, i64 C, i64 P, i64 L)
+{
+    const i64 pcn = P * C;
+    if (o->acf) for (i64 k = 0; k < pcn * (L + 1); ++k) o->acf[k] = NAN;
+    for (double* a : {o->var, o->tau})
+        if (a) for (i64 k = 0; k < pcn; ++k) a[k] = NAN;
+    if (o->window) for (i64 k = 0; k < pcn; ++k) o->window[k] = -1;
+    if (o->acf_pooled) for (i64 k = 0; k < P * (L + 1); ++k) o->acf_pooled[k] = NAN;
+    if (o->tau_pooled) for (i64 p = 0; p < P; ++p) o->tau_pooled[p] = NAN;
+    if (o->window_pooled) for (i64 p = 0; p < P; ++p) o->window_pooled[p] = -1;
+}
+
+static int acf_run(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i64 P, i64 sc, i64 sn, i64 sp, i64 L,
+                   int flags, double wc, const mcr_acf_out* out)
+{
+    const AcfGeom g = acf_geom(N, L);
+    const bool ingest = dtype == MCR_F32 || needs_ingest(C, N, P, sc, sn, sp);
+    i64 pcmax = 0;
+    int rc = plan_acf(ctx, C, N, P, g, ingest, pcmax);
+    if (rc) return rc;
+    const size_t pcn = (size_t)P * (size_t)C, nl = (size_t)(L + 1);
+    double *d_acf = nullptr, *d_var, *d_tau, *d_bad, *d_acfp, *d_taup;
+    i64 *d_win, *d_winp;
+    rc = carve(ctx, ctx->acf_dev, [&](Carve& cv) {
+        d_acf = out->acf ? cv.take<double>(pcn * nl) : nullptr;
+        d_var = cv.take<double>(pcn); d_tau = cv.take<double>(pcn); d_win = cv.take<i64>(pcn); d_bad = cv.take<double>(pcn);
+        d_acfp = cv.take<double>((size_t)P * nl); d_taup = cv.take<double>((size_t)P); d_winp = cv.take<i64>((size_t)P);
+    });
+    if (!rc) rc = ctx->acf_host.reserve(ctx, sizeof(double) * pcn);
+    if (rc) return rc;
+    // the chains of a launch lie along y and z (any C), four per workgroup in k_acf_mean
+    auto chain_grid = [](i64 n, unsigned gx) { const i64 gy = n < kMaxGridY ? n : kMaxGridY; return dim3(gx, (unsigned)gy, (unsigned)((n + gy - 1) / gy)); };
+    const size_t lds = sizeof(double) * acf_lds_doubles(g), lds_fin = sizeof(double) * nl;
+    for (i64 p0 = 0; p0 < P; p0 += pcmax) {
+        const i64 pc = (P - p0 < pcmax) ? P - p0 : pcmax;
+        AcfWs w;
+        rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) { carve_acf(cv, w, pc, C, N, g, ingest); });
+        if (rc) return rc;
+        const double* X = reinterpret_cast<const double*>(draws_dev) + p0 * C * N;
+        if (ingest) {
+            rc = launch_ingest(ctx, draws_dev, dtype, w.X, C, N, pc, sc, sn, sp, p0);
+            if (rc) return rc;
+            X = w.X;
+        }
+        const unsigned gx = (unsigned)((pc + 7) / 8 * 8);
+        const size_t at = (size_t)p0 * (size_t)C;
+        LAUNCH(ctx, K_ACF_MEAN, k_acf_mean, chain_grid((C + 3) / 4, gx), dim3(256), 0, X, C, N, pc, w.mean, d_bad + at);
+        LAUNCH(ctx, K_ACF_PRODUCTS, k_acf_products, chain_grid(C, (unsigned)(gx * g.nbg * g.nlb)), dim3((unsigned)acf_threads(g)), lds,
+               X, (const double*)w.mean, C, N, pc, g, w.part);
+        LAUNCH(ctx, K_ACF_FINISH, k_acf_finish, chain_grid(C, gx), dim3(kAcfFinNT), lds_fin, (const double*)w.part, C, N, pc, L, g,
+               flags & MCR_ACF_UNBIASED, wc, w.gam, d_acf ? d_acf + at * nl : nullptr, d_var + at, d_tau + at, d_win + at);
+        LAUNCH(ctx, K_ACF_POOL, k_acf_pool, dim3(gx), dim3(kAcfFinNT), lds_fin, (const double*)w.gam, C, pc, L, g.lp, wc,
+               d_acfp + (size_t)p0 * nl, d_taup + p0, d_winp + p0);
+    }
+    double* h_bad = ctx->acf_host.as<double>();
+    auto fetch = [&](void* dst, const void* src, size_t bytes) {
+        return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
+    };
+    HIP_TRY(ctx, fetch(h_bad, d_bad, sizeof(double) * pcn));
+    HIP_TRY(ctx, fetch(out->acf, d_acf, sizeof(double) * pcn * nl));
+    HIP_TRY(ctx, fetch(out->var, d_var, sizeof(double) * pcn));
+    HIP_TRY(ctx, fetch(out->tau, d_tau, sizeof(double) * pcn));
+    HIP_TRY(ctx, fetch(out->window, d_win, sizeof(i64) * pcn));
+    HIP_TRY(ctx, fetch(out->acf_pooled, d_acfp, sizeof(double) * (size_t)P * nl));
+    HIP_TRY(ctx, fetch(out->tau_pooled, d_taup, sizeof(double) * (size_t)P));
+    HIP_TRY(ctx, fetch(out->window_pooled, d_winp, sizeof(i64) * (size_t)P));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    prof_resolve(ctx);
+    double nbad = 0.0;
+    for (size_t k = 0; k < pcn; ++k) nbad += h_bad[k];
+    if (nbad > 0.0) return fail(ctx, MCR_ENONFINITE, "draws contain %.0f non-finite value(s)", nbad);
+    return MCR_OK;
+}
+
+int mcr_autocorr_plan(mcr_ctx* ctx, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc, int64_t sn, int64_t sp,
+                      int64_t max_lag, int64_t* params_per_chunk)
+{
+    if (!ctx || !params_per_chunk) return fail(ctx, MCR_EINVAL, "mcr_autocorr_plan: NULL argument");
+    if (C < 1 || N < 1 || P < 1 || C > (i64)0x7FFFFFFFll / N || C * N >= (i64)0x7FFFFFFFll) { *params_per_chunk = 0; return MCR_OK; }
+    const int rc0 = acf_check_args(ctx, N, max_lag, 0, 1.0);
+    if (rc0) return rc0;
+    i64 pcmax = 0;
+    const int rc = plan_acf(ctx, C, N, P, acf_geom(N, max_lag), dtype == MCR_F32 || needs_ingest(C, N, P, sc, sn, sp), pcmax);
+    if (rc) return rc;
+    *params_per_chunk = pcmax;
+    return MCR_OK;
+}
+
+int mcr_autocorr_dev(mcr_ctx* ctx, const void* draws_dev, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc, int64_t sn,
+                     int64_t sp, int64_t max_lag, int flags, double window_c, mcr_acf_out* out)
+{
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    int rc = acf_check(ctx, draws_dev, dtype, C, N, P, max_lag, flags, window_c, out);
+    if (rc || P == 0) return rc;
+    if (C * N == 0) { acf_fill_nan(out, C, P, max_lag); return MCR_OK; }
+    if (tensor_extent(C, N, P, sc, sn, sp) < 0) return fail(ctx, MCR_EINVAL, "negative strides are not supported");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = acf_run(ctx, draws_dev, dtype, C, N, P, sc, sn, sp, max_lag, flags, window_c, out);
+    return rc ? drain(ctx, rc, true) : rc;
+}
+
+int mcr_autocorr(mcr_ctx* ctx, const void* draws, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc, int64_t sn, int64_t sp,
+                 int64_t max_lag, int flags, double window_c, mcr_acf_out* out)
+{
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    int rc = acf_check(ctx, draws, dtype, C, N, P, max_lag, flags, window_c, out);   // (the device entry checks again: the errors come before the upload)
+    const void* X = nullptr;
+    if (!rc) rc = pooled_upload(ctx, draws, dtype, C, N, P, sc, sn, sp, &X);
+    if (rc) return rc;
+    return mcr_autocorr_dev(ctx, X, dtype, C, N, P, sc, sn, sp, max_lag, flags, window_c, out);
+}
+
+int mcr_autocorr_host(const double* chains, int64_t C, int64_t N, int64_t max_lag, int flags, double window_c, mcr_acf_out* out)
+{
+    if (!out || C < 0 || N < 0 || (N > 0 && (C > (i64)0x7FFFFFFFll / N || C * N >= (i64)0x7FFFFFFFll)) || (C * N > 0 && !chains)) return MCR_EINVAL;
+    const i64 L = max_lag;
+    const int rc = acf_check_args(nullptr, N, L, flags, window_c);
+    if (rc) return rc;
+    if (C * N == 0) { acf_fill_nan(out, C, 1, L); return MCR_OK; }
+    const bool unbiased = (flags & MCR_ACF_UNBIASED) != 0;
+    const i64 nblk = (N + kAcfBlock - 1) / kAcfBlock;
+    std::vector<double> d((size_t)N), gam((size_t)(L + 1)), rho((size_t)(L + 1)), pool((size_t)(L + 1), 0.0);
+    i64 nbad = 0;
+    for (i64 c = 0; c < C; ++c) {
+        const double* x = chains + c * N;
+        double v[kWave];
+        for (int j = 0; j < kWave; ++j) v[j] = acf_lane_sum(x, N, j, &nbad);
+        for (int o = kWave >> 1; o > 0; o >>= 1)                       // the xor tree, as lane 0 sees it
+            for (int j = 0; j < o; ++j) v[j] = v[j] + v[j + o];
+        const double m = v[0] / (double)N;
+        for (i64 i = 0; i < N; ++i) d[(size_t)i] = x[i] - m;
+        for (i64 l = 0; l <= L; ++l) {
+            double S = 0.0;
+            for (i64 b = 0; b < nblk; ++b) {
+                const i64 i0 = b * kAcfBlock, i1 = i0 + kAcfBlock < N - l ? i0 + kAcfBlock : N - l;
+                double acc = 0.0;
+                for (i64 i = i0; i < i1; ++i) acc = fma(d[(size_t)i], d[(size_t)(i + l)], acc);
+                S += acc;
+            }
+            gam[(size_t)l] = acf_gamma(S, N, l, unbiased);
+            pool[(size_t)l] += gam[(size_t)l];
+        }
+        for (i64 l = 0; l <= L; ++l) rho[(size_t)l] = acf_rho(gam[(size_t)l], gam[0]);
+        double t;
+        i64 w;
+        acf_tau_scan(rho.data(), L, window_c, t, w);
+        if (out->acf) memcpy(out->acf + c * (L + 1), rho.data(), sizeof(double) * (size_t)(L + 1));
+        if (out->var) out->var[c] = gam[0];
+        if (out->tau) out->tau[c] = t;
+        if (out->window) out->window[c] = w;
+    }
+    for (i64 l = 0; l <= L; ++l) pool[(size_t)l] = pool[(size_t)l] / (double)C;
+    for (i64 l = 0; l <= L; ++l) rho[(size_t)l] = acf_rho(pool[(size_t)l], pool[0]);
+    double t;
+    i64 w;
+    acf_tau_scan(rho.data(), L, window_c, t, w);
+    if (out->acf_pooled) memcpy(out->acf_pooled, rho.data(), sizeof(double) * (size_t)(L + 1));
+    if (out->tau_pooled) *out->tau_pooled = t;
+    if (out->window_pooled) *out->window_pooled = w;
+    return nbad > 0 ? MCR_ENONFINITE : MCR_OK;
 }
 
 // Device-resident form (draws_dev [P][M] f64, cov_dev [P][P] f64, both in this context's device memory): what

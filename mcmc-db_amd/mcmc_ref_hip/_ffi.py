@@ -80,6 +80,16 @@ class Hdi(C.Structure):
     _fields_ = [("lo", _dp), ("hi", _dp), ("index", _ip)]
 
 
+MCR_ACF_MAX_LAG = 4096                                      # the largest max_lag of a Context.autocorr call
+MCR_ACF_BLOCK = 512                                         # consecutive draws of one fma chain of k_acf_products
+MCR_ACF_UNBIASED = 1                                        # flag: gamma_l = S_l / (N - l)
+
+
+class Acf(C.Structure):
+    _fields_ = [("acf", _dp), ("var", _dp), ("tau", _dp), ("window", _ip), ("acf_pooled", _dp), ("tau_pooled", _dp),
+                ("window_pooled", _ip)]
+
+
 class ModelDesc(C.Structure):
     _fields_ = [("draws_dev", C.c_void_p), ("dtype", C.c_int), ("min_chains", C.c_int),
                 ("C", C.c_int64), ("N", C.c_int64), ("P", C.c_int64),
@@ -175,6 +185,10 @@ SYMBOLS = {
     "mcr_hdi_dev": (C.c_int, [C.c_void_p] + _TENSOR + [_dp, C.c_int, C.POINTER(Hdi)]),
     "mcr_hdi_plan": (C.c_int, [C.c_void_p, C.c_int] + [_I64] * 6 + [C.c_int, C.POINTER(C.c_int64)]),
     "mcr_hdi_sorted_host": (C.c_int, [_dp, _I64, _dp, C.c_int, _dp, _dp, _ip]),
+    "mcr_autocorr": (C.c_int, [C.c_void_p] + _TENSOR + [_I64, C.c_int, C.c_double, C.POINTER(Acf)]),
+    "mcr_autocorr_dev": (C.c_int, [C.c_void_p] + _TENSOR + [_I64, C.c_int, C.c_double, C.POINTER(Acf)]),
+    "mcr_autocorr_plan": (C.c_int, [C.c_void_p, C.c_int] + [_I64] * 7 + [C.POINTER(C.c_int64)]),
+    "mcr_autocorr_host": (C.c_int, [_dp, _I64, _I64, _I64, C.c_int, C.c_double, C.POINTER(Acf)]),
     "mcr_covariance": (C.c_int, [C.c_void_p, _dp, _I64, _I64, _dp]),
     "mcr_covariance_dev": (C.c_int, [C.c_void_p, C.c_void_p, _I64, _I64, C.c_void_p]),
     "mcr_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
@@ -425,6 +439,42 @@ def hdi_sorted_host(sorted_draws, prob=0.94):
     if np.ndim(prob) == 0:
         return float(lo[0]), float(hi[0]), int(idx[0])
     return lo, hi, idx
+
+
+def _acf_arrays(P: int, nc: int, L: int):
+    """The output arrays of an autocorrelation call (NaN / -1 until written) and the struct that points at them."""
+    p1, c1 = max(P, 1), max(nc, 1)
+    arrs = {"acf": np.full((p1, c1, L + 1), np.nan), "var": np.full((p1, c1), np.nan), "tau": np.full((p1, c1), np.nan),
+            "window": np.full((p1, c1), -1, dtype=np.int64), "acf_pooled": np.full((p1, L + 1), np.nan),
+            "tau_pooled": np.full(p1, np.nan), "window_pooled": np.full(p1, -1, dtype=np.int64)}
+    out = Acf(**{k: (_as_ip if a.dtype == np.int64 else _as_dp)(a) for k, a in arrs.items()})
+    return arrs, out
+
+
+def _acf_result(arrs: dict, P: int, nc: int, N: int, L: int) -> dict:
+    res = {k: a[:P, :nc] if k in ("acf", "var", "tau", "window") else a[:P] for k, a in arrs.items()}
+    with np.errstate(all="ignore"):
+        res["ess_chain"] = N / res["tau"]
+        res["ess_pooled"] = (nc * N) / res["tau_pooled"]
+    res["max_lag"] = L
+    return res
+
+
+def autocorr_host(chains, max_lag=None, unbiased: bool = False, window_c: float = 5.0) -> dict:
+    """Autocorrelation functions and times of ONE parameter's equal-length chains [C][N] by the library's host routine
+    (mcr_autocorr_host: the device's text in the device's summation order, equal to Context.autocorr in bits; no device).
+    The keys of Context.autocorr with P = 1.  ValueError for a bad max_lag or window_c, or non-finite draws."""
+    x = np.ascontiguousarray(chains, dtype=np.float64)
+    if x.ndim != 2:
+        raise ValueError("chains must be 2-D [C][N]")
+    nc, N = x.shape
+    L = min(100, max(N - 1, 0)) if max_lag is None else int(max_lag)
+    arrs, out = _acf_arrays(1, nc, L if 0 <= L <= MCR_ACF_MAX_LAG else 0)      # (a bad max_lag is refused before anything is written)
+    rc = load_library().mcr_autocorr_host(_as_dp(x), nc, N, L, MCR_ACF_UNBIASED if unbiased else 0, float(window_c), C.byref(out))
+    if rc != MCR_OK:
+        raise ValueError(f"mcr_autocorr_host: {'non-finite draws' if rc == MCR_ENONFINITE else 'bad argument'} "
+                         f"(max_lag = {L}, N = {N}, window_c = {window_c})")
+    return _acf_result(arrs, 1, nc, N, L)
 
 
 class PqImage:
@@ -1341,6 +1391,33 @@ class Context:
         """Parameters per workspace chunk of an hdi call with nprob probabilities on this tensor (mcr_hdi_plan)."""
         v = C.c_int64(0)
         self._check(self.lib.mcr_hdi_plan(self.handle, *self._hdi_tensor(t, "pcn")[0], int(nprob), C.byref(v)))
+        return int(v.value)
+
+    def _acf_tensor(self, draws, layout: str):
+        if isinstance(draws, DeviceTensor):
+            if draws.chain_off is not None:
+                raise ValueError("autocorrelation needs chains of equal length; a ragged tensor is not supported")
+            return draws.targs, draws.buf.ptr, self.lib.mcr_autocorr_dev
+        return tensor_args(draws, layout), draws.ctypes.data_as(C.c_void_p), self.lib.mcr_autocorr
+
+    def autocorr(self, draws, layout: str = "cnp", max_lag=None, unbiased: bool = False, window_c: float = 5.0) -> dict:
+        """Autocorrelation functions and integrated autocorrelation times of the raw draws (mcr_autocorr: ArviZ's autocorr,
+        emcee's integrated_time) of a host array (strided views included) or a DeviceTensor with equal-length chains.
+        max_lag: the default is min(100, N - 1); at most MCR_ACF_MAX_LAG.  unbiased: divide lag l by N - l instead of N.
+        Arrays: "acf" [P][C][L+1], "var" (gamma_0), "tau", "window" (int64, -1: the ACF has not decayed within max_lag and tau
+        is a lower bound) and "ess_chain" = N / tau, all [P][C]; the within-chain pooled "acf_pooled" [P][L+1],
+        "tau_pooled", "window_pooled", "ess_pooled" = C N / tau_pooled, all [P]; and the int "max_lag"."""
+        targs, ptr, fn = self._acf_tensor(draws, layout)
+        nc, N, P = targs[1], targs[2], targs[3]
+        L = min(100, max(N - 1, 0)) if max_lag is None else int(max_lag)
+        arrs, out = _acf_arrays(P, nc, L if 0 <= L <= MCR_ACF_MAX_LAG else 0)  # (a bad max_lag is refused before anything is written)
+        self._check(fn(self.handle, ptr, *targs, L, MCR_ACF_UNBIASED if unbiased else 0, float(window_c), C.byref(out)))
+        return _acf_result(arrs, P, nc, N, L)
+
+    def autocorr_params_per_chunk(self, t: "DeviceTensor", max_lag: int) -> int:
+        """Parameters per workspace chunk of an autocorr call with this max_lag on this tensor (mcr_autocorr_plan)."""
+        v = C.c_int64(0)
+        self._check(self.lib.mcr_autocorr_plan(self.handle, *self._acf_tensor(t, "pcn")[0], int(max_lag), C.byref(v)))
         return int(v.value)
 
     def covariance(self, draws) -> np.ndarray:

@@ -13,6 +13,8 @@ parameter and, with `--sliced K`, along K random directions of the joint distrib
 `nested-rhat FILE --superchains K` prints nested R-hat, the diagnostic for many short chains, of a draws table.
 `pareto-khat FILE` prints the Pareto k-hat of every parameter's tails: whether a mean and a std of the draws can be trusted.
 `hdi FILE` prints the highest-density interval(s) of every parameter: the shortest interval holding a share of the draws.
+`autocorr FILE` prints every parameter's integrated autocorrelation time (Sokal's window) and its stickiest and least
+sticky chain; as JSON, the autocorrelation function of every chain up to `--max-lag` as well.
 """
 from __future__ import annotations
 
@@ -201,6 +203,40 @@ def hdi_cmd(file: Path, params: str | None, probs: tuple[float, ...], format_: s
     except (ValueError, KeyError, IndexError) as exc:
         raise click.ClickException(str(exc)) from exc
     _echo_stats(stats, format_)
+
+
+@main.command("autocorr")
+@click.argument("file", type=click.Path(path_type=Path, exists=True, dir_okay=False))
+@click.option("--params", default=None, help="Comma-separated parameter list")
+@click.option("--max-lag", default=None, type=int, help="Largest lag (default: min(100, N - 1); at most 4096)")
+@click.option("--unbiased", is_flag=True, help="Divide lag l by N - l instead of N")
+@click.option("--window-c", default=5.0, type=float, help="Sokal's window constant: the first W >= c * tau_W (default: 5)")
+@click.option("--format", "format_", type=click.Choice(["table", "json"], case_sensitive=False), default="table")
+def autocorr_cmd(file: Path, params: str | None, max_lag: int | None, unbiased: bool, window_c: float, format_: str) -> None:
+    """Autocorrelation functions and integrated autocorrelation times (ArviZ's autocorr, emcee's integrated_time) of the
+    chains of a draws table (no counterpart in the reference).  The table prints the within-chain pooled tau, window (-1:
+    not decayed within --max-lag, tau is a lower bound) and ess_pooled, and the smallest and largest per-chain tau with
+    their chains; JSON carries the full arrays."""
+    try:
+        stats = convert_mod.autocorr_file(file, params=params.split(",") if params else None, max_lag=max_lag,
+                                          unbiased=unbiased, window_c=window_c)
+    except (ValueError, KeyError, IndexError) as exc:
+        raise click.ClickException(str(exc)) from exc
+    if format_ == "json":
+        click.echo(json.dumps(stats, indent=2, sort_keys=True))
+        return
+    rows = {}
+    for name, m in stats.items():
+        live = [(t, c) for c, t in enumerate(m["tau"]) if t == t]                 # (a constant chain has no tau)
+        lo, hi = (min(live), max(live)) if live else ((float("nan"), -1), (float("nan"), -1))
+        rows[name] = {"tau": m["tau_pooled"], "window": m["window_pooled"], "ess_pooled": m["ess_pooled"],
+                      "tau_min": lo[0], "chain_min": lo[1], "tau_max": hi[0], "chain_max": hi[1]}
+    headers = ["param", "tau", "window", "ess_pooled", "tau_min", "chain_min", "tau_max", "chain_max"]
+    widths = [max(len(h), 6) for h in headers]
+    click.echo(" ".join(h.ljust(w) for h, w in zip(headers, widths, strict=False)))
+    for name, m in rows.items():
+        row = [name] + [f"{m[h]:.6g}" for h in headers[1:]]
+        click.echo(" ".join(v.ljust(w) for v, w in zip(row, widths, strict=False)))
 
 
 @main.command("diagnostics")

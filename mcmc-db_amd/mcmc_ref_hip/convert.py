@@ -648,6 +648,35 @@ def hdi_file(path: Path, params: Iterable[str] | None = None, prob: Iterable[flo
             for i, n in enumerate(names)}
 
 
+def autocorr_file(path: Path, params: Iterable[str] | None = None, max_lag: int | None = None, unbiased: bool = False,
+                  window_c: float = 5.0, context=None) -> dict[str, dict]:
+    """Autocorrelation functions and times of every parameter of a draws table (a `.csv`, a chain-list `.json.zip` or a
+    `.parquet` draws file of the store, read on the host) with chains of equal length, in chain-id order.  Per parameter:
+    lists acf [C][L+1], tau, window, ess_chain [C], acf_pooled [L+1], and tau_pooled, window_pooled, ess_pooled, max_lag
+    (Context.autocorr).  ValueError for chains of unequal length."""
+    path = Path(path)
+    if path.suffix == ".parquet":
+        import pyarrow.parquet as pq
+        table = pq.read_table(path)
+    else:
+        table = _read_input(path)
+    table, names = _table_and_names(table, params)
+    if not names:
+        return {}
+    x, counts = table_to_tensor(table, names)
+    if len(counts) and not np.all(counts == counts[0]):
+        raise ValueError("autocorrelation requires chains of equal length")
+    C = len(counts)
+    ctx = context or _ffi.default_context()
+    with _ffi.value_errors():
+        r = ctx.autocorr(x.reshape(len(names), C, int(counts[0]) if C else 0), "pcn", max_lag=max_lag, unbiased=unbiased,
+                         window_c=window_c)
+    return {n: {"acf": r["acf"][i].tolist(), "tau": r["tau"][i].tolist(), "window": r["window"][i].tolist(),
+                "ess_chain": r["ess_chain"][i].tolist(), "acf_pooled": r["acf_pooled"][i].tolist(),
+                "tau_pooled": float(r["tau_pooled"][i]), "window_pooled": int(r["window_pooled"][i]),
+                "ess_pooled": float(r["ess_pooled"][i]), "max_lag": int(r["max_lag"])} for i, n in enumerate(names)}
+
+
 def _ensure_chain_draw(table):
     """Add the missing bookkeeping columns like the reference does (convert.py:105-120): a missing
     `draw` is the row number, a missing `chain` is chain 0 (int32, appended after the parameters)."""

@@ -9,7 +9,9 @@ autocovariance sum) runs in libmcmcref_hip; chains may be ragged.
 the convergence of Markov chain Monte Carlo when running many short chains"; posterior::rhat_nested), for any number
 of equal-length chains.  `pareto_khat` is not the reference's either: the tail diagnostic for the draws behind a mean
 and a std (Vehtari et al., "Pareto smoothed importance sampling"; posterior::pareto_khat), on the pooled chains.  Nor is
-`hdi`: the highest-density interval of the pooled chains (ArviZ's unimodal `hdi`).
+`hdi`: the highest-density interval of the pooled chains (ArviZ's unimodal `hdi`).  Nor `autocorr`: the autocorrelation
+function of every chain's raw draws and the integrated autocorrelation time with Sokal's window (ArviZ's `autocorr`,
+emcee's `integrated_time`) -- what one looks at when ESS is low.
 """
 from __future__ import annotations
 
@@ -129,3 +131,24 @@ def hdi(chains: Sequence[Sequence[float]], prob: float = 0.94, *, context=None) 
     with _ffi.value_errors():
         res = ctx.hdi(x.reshape(1, 1, -1), "pcn", prob=float(prob))
     return float(res["lo"][0]), float(res["hi"][0])
+
+
+def autocorr(chains: Sequence[Sequence[float]], max_lag: int | None = None, *, unbiased: bool = False, window_c: float = 5.0,
+             context=None) -> dict:
+    """Autocorrelation functions and times of ONE parameter given as equal-length chains (Context.autocorr): arrays "acf"
+    [C][L+1], "var", "tau", "window", "ess_chain" = N / tau per chain; the within-chain pooled "acf_pooled" [L+1] and the
+    scalars "tau_pooled", "window_pooled", "ess_pooled" = C N / tau_pooled, "max_lag" (default min(100, N - 1)).  A window
+    of -1 says the autocorrelation has not decayed within max_lag: tau is then a lower bound.  ValueError for chains of
+    unequal length, a bad max_lag or window_c, and non-finite draws."""
+    lengths = {len(c) for c in chains}
+    if len(lengths) > 1:
+        raise ValueError(f"autocorrelation requires chains of equal length; got lengths {sorted(lengths)}")
+    n = lengths.pop() if lengths else 0
+    x = np.ascontiguousarray(chains, dtype=np.float64).reshape(1, len(chains), n)
+    ctx = context or _ffi.default_context()
+    with _ffi.value_errors():
+        res = ctx.autocorr(x, "pcn", max_lag=max_lag, unbiased=unbiased, window_c=window_c)
+    out = {k: res[k][0] for k in ("acf", "var", "tau", "window", "ess_chain", "acf_pooled")}
+    out.update(tau_pooled=float(res["tau_pooled"][0]), window_pooled=int(res["window_pooled"][0]),
+               ess_pooled=float(res["ess_pooled"][0]), max_lag=res["max_lag"])
+    return out
