@@ -359,6 +359,79 @@ int64_t mcr_pareto_tail_length(int64_t M, double r_eff);                 /* host
 int mcr_pareto_fit_host(const double* sorted, int64_t M, int64_t ndraws_tail /* 0 = default */,
                         double* khat_left, double* khat_right, int64_t* t_eff);
 #define MCR_PARETO_LDS_TAIL 8192      /* the longest tail k_pareto_fit stages in LDS */
+/* Pareto-smoothed importance sampling (PSIS) and PSIS-LOO: the second half of the paper cited above (psislw / loo of
+ * ArviZ, psis / loo of the R package loo).  ABSENT from the reference.  The largest importance ratios of a column are
+ * replaced with the expected order statistics of the generalised Pareto distribution fitted to them and the weights are
+ * normalised; from a (chains x draws x observations) tensor of pointwise log-likelihoods this gives elpd_loo, p_loo and a
+ * k-hat per observation, the accepted way to compare two models fitted to the same data.
+ * For one column of M = C * N pooled values v, everything in IEEE double (f32 is widened first by the ingest pass; the
+ * answer is that of the f64 call on the widened tensor).  negate = 0: v are log importance ratios and x = v.  negate = 1
+ * (LOO): v are log-likelihoods and x = -v; the negation is exact.  Let x_(0) <= ... <= x_(M-1) be x in ascending order
+ * and y_(i) = x_(i) - x_(M-1).
+ *  1. Tail length.  A requested length t_req >= 1 from the caller (ndraws_tail), or the default
+ *         t_req = min((M + 4) / 5, T)        (integer division),  T the smallest t with t^2 * r_eff >= 9 M
+ *     T by mcr_pareto_tail_length's integer bisection; that is ceil(min(M / 5, 3 sqrt(M / r_eff))), loo's and ArviZ's rule
+ *     for EVERY M (not posterior's floor(M / 5) below 226 draws, which mcr_pareto_khat follows).  r_eff: per column, 1 when
+ *     none is given, finite and > 0; it plays no part where ndraws_tail is given.  mcr_psis_tail_length(M, r_eff) computes
+ *     the default on the host (0 for M < 1, MCR_EINVAL for a bad r_eff).  The effective length is t = min(t_req, M - 1).
+ *  2. Cutoff and tail.  cut = max(y_(M-t-1), log(DBL_MIN)), log(DBL_MIN) read as the double -708.3964185322641.  The tail
+ *     is the n values with y > cut, compared by value: with ties at the cutoff, or with the clamp active, n < t.  If
+ *     t == 0 or n <= 4: khat = +inf, nothing is smoothed, the weights are the normalised raw ratios.
+ *  3. Fit.  e_i = exp(y_(M-n+i)) - exp(cut), i = 0 ... n-1, ascending, fitted as mcr_pareto_khat fits a tail (rules 1-6
+ *     above: the same text, scaling and summation order): khat, the regularised (k n + 5) / (n + 10) -- NaN (a constant
+ *     tail) becoming +inf -- and sigma = -k / theta / 2^s from the UNregularised k of rule 5, theta of rule 4 and the scale
+ *     of rule 2 (loo::gpdfit and ArviZ's _gpdfit do the same).  Unless khat is finite and sigma > 0 nothing is smoothed.
+ *  4. Smoothing.  For tail index i let [s, e) be the maximal run of equal e_j that contains it, and p_i = (s + e) / (2 n):
+ *     (i + 0.5) / n, ArviZ's, for a value that is alone.  q_i = sigma * expm1(-khat * log1p(-p_i)) / khat, or
+ *     -sigma * log1p(-p_i) when |khat| < DBL_EPSILON.  The smoothed value is min(log(q_i + exp(cut)), 0).
+ *     The run rule is the one deliberate departure from ArviZ and loo: they give tied ratios different weights
+ *     according to argsort's order among them.  This library's sorts keep no order among equal keys, and a draw's weight
+ *     must be a function of its value alone.
+ *  5. Normalisation.  lw_(i) is the smoothed value of a tail index, else y_(i).  log_norm = m + log(sum_i exp(lw_(i) - m)),
+ *     m = max_i lw_(i) (every log-sum-exp here: the maximum first, then the sum).  The log weight of a draw is
+ *     lw - log_norm.
+ *  6. Outputs per column: khat; ndraws_tail, the n actually used, an int64; with negate = 1 also
+ *         lppd = logsumexp_i(-x_(i)) - log M,   elpd = logsumexp_i(lw_(i) - x_(i)) - log_norm,   p_loo = lppd - elpd
+ *     (NaN with negate = 0); and, where log_weights is given, the P x M log weights in TIME order: element
+ *     (p, c * N + n), contiguous in n.
+ *  7. Summation order.  Every sum and every maximum over the M sorted values is 256 partial results, partial s taking the
+ *     terms s, s + 256, ... in index order; each 64 consecutive partials are joined by the tree 32, 16, ... 1 and the four
+ *     results r_0 ... r_3 as (r_0 + r_2) + (r_1 + r_3).  The order is a function of M alone and runs over the sorted
+ *     values: it needs no positions and does not depend on the order among ties.  A column's outputs therefore have the
+ *     same bits alone or anywhere in a batch, on the host or the device entry, in either layout or a strided view, under
+ *     any workspace limit, for f32 against the widened f64, with or without log_weights, and for negate = 1 on v against
+ *     negate = 0 on -v.
+ * draws: host tensor addressed like mcr_summarize's.  r_eff, ndraws_tail: P entries each, or NULL.  out: P entries per
+ * array, NULL skipped; log_weights is a HOST pointer in mcr_psis and a pointer into THIS ctx's device memory in
+ * mcr_psis_dev (where every other array of out, r_eff and ndraws_tail stay on the host).
+ * Limits: any C, C * N < 2^31 - 1.  MCR_EINVAL (message names the cause): a negative dimension, negate other than 0 / 1,
+ * a ndraws_tail entry < 1, an r_eff entry that is not finite and > 0, summaries in flight, negative strides.
+ * MCR_ENONFINITE: NaN / Inf values -- a log ratio of -inf (a weight of exactly zero) is refused like any other.  M == 0
+ * gives NaN (ndraws_tail 0), P == 0 writes nothing.  The context stays usable after every error.  Synchronous.  ONE
+ * workgroup handles a column (a tail beyond MCR_PARETO_LDS_TAIL is fitted from global memory): beyond ~10^5 draws a
+ * column takes milliseconds.  k_psis_weights runs only where log_weights is given. */
+typedef struct mcr_psis_out {
+    double* khat; int64_t* ndraws_tail; double *lppd, *elpd, *p_loo;   /* P entries each, NULL skipped */
+    double* log_weights;                                               /* [P][M], time order; NULL: not computed */
+} mcr_psis_out;
+int mcr_psis(mcr_ctx* ctx, const void* draws, int dtype, int64_t C, int64_t N, int64_t P, int64_t stride_c, int64_t stride_n,
+             int64_t stride_p, int negate, const double* r_eff /* P entries or NULL */,
+             const int64_t* ndraws_tail /* P entries or NULL */, mcr_psis_out* out);
+/* The same on draws in this ctx's device memory; out->log_weights is a device pointer too. */
+int mcr_psis_dev(mcr_ctx* ctx, const void* draws_dev, int dtype, int64_t C, int64_t N, int64_t P, int64_t stride_c,
+                 int64_t stride_n, int64_t stride_p, int negate, const double* r_eff, const int64_t* ndraws_tail,
+                 mcr_psis_out* out);
+/* Columns per workspace chunk of such a call under the current workspace limit (0 for an empty shape); host_weights: the
+ * host entry with log_weights, whose chunk holds its weights too.  MCR_ENOMEM when the limit does not fit one column. */
+int mcr_psis_plan(mcr_ctx* ctx, int dtype, int64_t C, int64_t N, int64_t P, int64_t stride_c, int64_t stride_n,
+                  int64_t stride_p, int host_weights, int64_t* params_per_chunk);
+int64_t mcr_psis_tail_length(int64_t M, double r_eff);                   /* host only */
+/* One column on the host (host only, no ctx, no device): M values in ANY order (sorted here), ndraws_tail 0 = the
+ * default; NULL outputs are skipped; log_weights takes M entries in the order of `values`.  It runs the device's text in
+ * the device's summation order, but with the host's libm, so the results equal the device's to rounding, not in bits.
+ * MCR_EINVAL: M < 0 or >= 2^31 - 1, a NULL array, negate, ndraws_tail < 0, r_eff as above.  MCR_ENONFINITE: NaN / Inf. */
+int mcr_psis_host(const double* values, int64_t M, int negate, double r_eff, int64_t ndraws_tail /* 0 = default */,
+                  double* khat, int64_t* n_tail, double* lppd, double* elpd, double* p_loo, double* log_weights);
 /* Highest-density intervals (HDI): the shortest interval that holds a given share of a parameter's draws (ArviZ's
  * unimodal hdi, the hdi_3% / hdi_97% columns of its summary; hdi of bayestestR).  ABSENT from the reference.  For a skewed
  * or bounded parameter it differs from the equal-tailed interval of the same share by a large part of its width.

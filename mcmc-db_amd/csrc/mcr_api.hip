@@ -33,6 +33,7 @@
 #include "mcr_nested.hpp"
 #include "mcr_acf.hpp"
 #include "mcr_pareto.hpp"
+#include "mcr_psis.hpp"
 #include "mcr_hdi.hpp"
 #include "mcr_parquet.hpp"
 #include "mcr_pqwrite.hpp"
@@ -65,7 +66,7 @@ enum KernelId {
     K_JSON_INDEX, K_JSON_SCAN, K_JSON_PARSE,
     K_LAYOUT_SCAN, K_LAYOUT_KEYS, K_LAYOUT_HIST, K_LAYOUT_OFFSETS, K_LAYOUT_SCATTER, K_LAYOUT_BOUNDS,
     K_PQW_ENCODE, K_PQW_COMPACT, K_CSVW_FORMAT, K_CSVW_SCAN, K_CSVW_COMPACT, K_SELECT_ROWS, K_PROJECT,
-    K_CHAIN_MOMENTS, K_NESTED_COMBINE, K_PARETO_FIT, K_HDI_WINDOW, K_HDI_PICK,
+    K_CHAIN_MOMENTS, K_NESTED_COMBINE, K_PARETO_FIT, K_PSIS_COLUMN, K_PSIS_WEIGHTS, K_HDI_WINDOW, K_HDI_PICK,
     K_ACF_MEAN, K_ACF_PRODUCTS, K_ACF_FINISH, K_ACF_POOL, K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {
@@ -77,7 +78,7 @@ const char* const kKernelNames[K_COUNT] = {
     "k_json_index", "k_json_scan", "k_json_parse",
     "k_layout_scan", "k_layout_keys", "k_layout_hist", "k_layout_offsets", "k_layout_scatter", "k_layout_bounds",
     "k_pqw_encode", "k_pqw_compact", "k_csvw_format", "k_csvw_scan", "k_csvw_compact", "k_select_rows", "k_project",
-    "k_chain_moments", "k_nested_combine", "k_pareto_fit", "k_hdi_window", "k_hdi_pick",
+    "k_chain_moments", "k_nested_combine", "k_pareto_fit", "k_psis_column", "k_psis_weights", "k_hdi_window", "k_hdi_pick",
     "k_acf_mean", "k_acf_products", "k_acf_finish", "k_acf_pool"};
 
 struct EvPair { hipEvent_t a, b; int kid; };
@@ -196,6 +197,8 @@ struct mcr_ctx {
     PinBuf nest_host{4};               // its results on the host
     DevBuf pareto_dev{4};              // mcr_pareto_khat: tail lengths + result table
     PinBuf pareto_host{4};             // its results on the host
+    DevBuf psis_dev{4};                // mcr_psis: tail lengths + result table
+    PinBuf psis_host{4};               // its results on the host
     DevBuf hdi_dev{4};                 // mcr_hdi: result table
     PinBuf hdi_host{4};                // its results on the host
     DevBuf acf_dev{4};                 // mcr_autocorr: result arrays + the chains' non-finite counts
@@ -2243,10 +2246,10 @@ static int plan_pareto(mcr_ctx* ctx, i64 M, i64 P, bool ingest, i64& pcmax)
 
 // The default tail length: the smallest t with t^2 r_eff >= 9 M (that is ceil(3 sqrt(M / r_eff))) for M > 225, else
 // floor(M / 5).  A bisection over integers: t^2 is exact, its product with r_eff rounds once and is monotone in t, no
-// sqrt takes part.  Capped at 2^31, beyond the floor(M / 2) of any call.
-static i64 pareto_default_tail(i64 M, double r_eff)
+// sqrt takes part.  Capped at 2^31, beyond the floor(M / 2) of any call.  (pareto_tail_bisect: the bisection alone, for
+// every M -- mcr_psis takes its minimum with ceil(M / 5).)
+static i64 pareto_tail_bisect(i64 M, double r_eff)
 {
-    if (M <= 225) return M / 5;
     const double need = 9.0 * (double)M;
     i64 lo = 0, hi = (i64)1 << 31;                         // lo fails, hi holds (or is the cap)
     while (hi - lo > 1) {
@@ -2255,6 +2258,7 @@ static i64 pareto_default_tail(i64 M, double r_eff)
     }
     return hi;
 }
+static i64 pareto_default_tail(i64 M, double r_eff) { return M <= 225 ? M / 5 : pareto_tail_bisect(M, r_eff); }
 
 // Acceptance of a Pareto call, and the effective tail length of every parameter.
 static int pareto_check(mcr_ctx* ctx, const void* draws, int dtype, i64 C, i64 N, i64 P, const int64_t* ndraws_tail,
@@ -2382,6 +2386,212 @@ int mcr_pareto_fit_host(const double* sorted, int64_t M, int64_t ndraws_tail, do
     }
     if (khat_left) *khat_left = kl;
     if (khat_right) *khat_right = kr;
+    return MCR_OK;
+}
+
+// ---- Pareto-smoothed importance sampling and PSIS-LOO (mcr_psis.hpp) ------------------------------------------------------
+constexpr int kPsisField0 = kPoolField0;
+constexpr int kPsisFields = kPsisField0 + kPsisRows;       // + khat, ndraws_tail, lppd, elpd, p_loo
+
+struct PsisWs { double *lg, *cols, *w; };
+
+// The fit's grid values of a column: carve_pareto's scratch as it is, 2 pareto_grid(M / 2) >= pareto_grid(M - 1) doubles.
+static i64 psis_gmax(i64 M) { return 2 * (i64)pareto_grid(M / 2); }
+
+// Behind the pipeline's buffers: that scratch, the columns' scalars for k_psis_weights and, for the host entry's weights,
+// the chunk's [pc][M] log weights.
+static void carve_psis(Carve& cv, const PipeIn& a, bool host_weights, PsisWs& w)
+{
+    w.lg = carve_pareto(cv, a);
+    w.cols = cv.take<double>((size_t)a.pc * kPsisCols);
+    w.w = host_weights ? cv.take<double>((size_t)a.pc * (size_t)a.M) : nullptr;
+}
+
+// Columns per workspace chunk of a PSIS call: what fits, and no more than k_psis_weights' one-dimensional grid holds.
+static int plan_psis(mcr_ctx* ctx, i64 M, i64 P, bool ingest, bool host_weights, i64& pcmax)
+{
+    const i64 grid_hi = ((i64)0x7FFFFFFFll / ((M + kPsisBlock - 1) / kPsisBlock)) / 8 * 8;     // >= 1016: M < 2^31
+    return plan_pooled(ctx, M, P < grid_hi ? P : grid_hi, ingest,
+                       [&](Carve& cv, PipeIn& a) { PsisWs w; carve_psis(cv, a, host_weights, w); }, pcmax);
+}
+
+static bool psis_r_eff_ok(double r) { return r > 0.0 && !std::isinf(r); }
+
+// The default tail length of M >= 1 values: min(ceil(M / 5), the smallest t with t^2 r_eff >= 9 M).
+static i64 psis_default_tail(i64 M, double r_eff)
+{
+    const i64 fifth = (M + 4) / 5, root = pareto_tail_bisect(M, r_eff);
+    return fifth < root ? fifth : root;
+}
+
+// The effective tail length: min(t_req, M - 1), t_req the caller's (>= 1) or the default.
+static i64 psis_tail_eff(i64 M, i64 t_req, double r_eff)
+{
+    if (t_req < 1) t_req = psis_default_tail(M, r_eff);
+    return t_req < M - 1 ? t_req : M - 1;
+}
+
+// Acceptance of a PSIS call, and the effective tail length of every column.
+static int psis_check(mcr_ctx* ctx, const void* draws, int dtype, i64 C, i64 N, i64 P, int negate, const double* r_eff,
+                      const int64_t* ndraws_tail, const mcr_psis_out* out, std::vector<i64>& teff)
+{
+    const int rc = pooled_check(ctx, "mcr_psis", draws, dtype, C, N, P, out);
+    if (rc) return rc;
+    if (negate != 0 && negate != 1) return fail(ctx, MCR_EINVAL, "negate must be 0 or 1; got %d", negate);
+    const i64 M = C * N;
+    teff.resize((size_t)P);
+    for (i64 p = 0; p < P; ++p) {
+        if (ndraws_tail && ndraws_tail[p] < 1)
+            return fail(ctx, MCR_EINVAL, "ndraws_tail[%lld] = %lld: a tail length must be >= 1", (long long)p, (long long)ndraws_tail[p]);
+        if (r_eff && !psis_r_eff_ok(r_eff[p]))
+            return fail(ctx, MCR_EINVAL, "r_eff[%lld] = %g: a relative efficiency must be finite and > 0", (long long)p, r_eff[p]);
+        teff[(size_t)p] = M < 1 ? 0 : psis_tail_eff(M, ndraws_tail ? ndraws_tail[p] : 0, r_eff ? r_eff[p] : 1.0);
+    }
+    return MCR_OK;
+}
+
+static int psis_run(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i64 P, i64 sc, i64 sn, i64 sp, int negate,
+                    const std::vector<i64>& teff, const mcr_psis_out* out, bool host_weights)
+{
+    const i64 M = C * N;
+    const bool ingest = dtype == MCR_F32 || needs_ingest(C, N, P, sc, sn, sp);
+    const bool hw = host_weights && out->log_weights;
+    i64 pcmax = 0;
+    int rc = plan_psis(ctx, M, P, ingest, hw, pcmax);
+    if (rc) return rc;
+    i64* d_tail = nullptr;
+    double* d_res = nullptr;
+    rc = carve(ctx, ctx->psis_dev, [&](Carve& cv) {
+        d_tail = cv.take<i64>((size_t)P);
+        d_res = cv.take<double>((size_t)kPsisFields * (size_t)P);
+    });
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(d_tail, teff.data(), sizeof(i64) * (size_t)P, hipMemcpyHostToDevice, ctx->stream));
+    const i64 gmax = psis_gmax(M);
+    const unsigned nb = (unsigned)((M + kPsisBlock - 1) / kPsisBlock);
+    PsisWs w{};
+    rc = pooled_chunks(ctx, draws_dev, dtype, C, N, P, sc, sn, sp, ingest, pcmax, kPsisFields, d_res,
+                       [&](Carve& cv, PipeIn& a) { carve_psis(cv, a, hw, w); },
+                       [&](const PipeIn& a, const Sorted& so, i64 p0) -> int {
+        i64 tmax = 0;                          // the chunk's LDS: its longest tail that is staged there
+        for (i64 p = p0; p < p0 + a.pc; ++p)
+            if (teff[(size_t)p] <= kParetoLdsTail && teff[(size_t)p] > tmax) tmax = teff[(size_t)p];
+        const size_t lds = sizeof(double) * (size_t)(kPsisScratch + tmax);
+        if (lds > 60 * 1024)
+            HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_psis_column),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        const unsigned pgrp = (unsigned)((a.pc + 7) / 8 * 8);
+        LAUNCH(ctx, K_PSIS_COLUMN, k_psis_column, dim3(pgrp), dim3(kPsisNT), lds, (const double*)so.keys, M, a.pc, negate,
+               (const i64*)(d_tail + p0), so.keys_free, w.lg, gmax, a.d_res, kPsisField0, w.cols);
+        if (!out->log_weights) return MCR_OK;
+        double* dst = hw ? w.w : out->log_weights + p0 * M;
+        if (a.idx16)
+            LAUNCH(ctx, K_PSIS_WEIGHTS, k_psis_weights<unsigned short>, dim3(pgrp * nb), dim3(256), 0, (const double*)so.keys,
+                   (const unsigned short*)so.pos, M, a.pc, negate, (const double*)w.cols, dst);
+        else
+            LAUNCH(ctx, K_PSIS_WEIGHTS, k_psis_weights<u32>, dim3(pgrp * nb), dim3(256), 0, (const double*)so.keys,
+                   (const u32*)so.pos, M, a.pc, negate, (const double*)w.cols, dst);
+        if (hw)
+            HIP_TRY(ctx, hipMemcpyAsync(out->log_weights + p0 * M, w.w, sizeof(double) * (size_t)a.pc * (size_t)M,
+                                        hipMemcpyDeviceToHost, ctx->stream));
+        return MCR_OK;
+    });
+    if (rc) return rc;
+    return pooled_results(ctx, ctx->psis_host, d_res, kPsisFields, P, pcmax, [&](const double* r, i64 pc, i64 p0, i64 p) {
+        const double* f = r + (size_t)kPsisField0 * pc + p;
+        if (out->khat) out->khat[p0 + p] = f[PR_KHAT * pc];
+        if (out->ndraws_tail) out->ndraws_tail[p0 + p] = (i64)f[PR_NTAIL * pc];
+        if (out->lppd) out->lppd[p0 + p] = f[PR_LPPD * pc];
+        if (out->elpd) out->elpd[p0 + p] = f[PR_ELPD * pc];
+        if (out->p_loo) out->p_loo[p0 + p] = f[PR_PLOO * pc];
+    });
+}
+
+static void psis_fill_nan(const mcr_psis_out* o, i64 P)
+{
+    for (double* a : {o->khat, o->lppd, o->elpd, o->p_loo})
+        if (a) for (i64 p = 0; p < P; ++p) a[p] = NAN;
+    if (o->ndraws_tail) for (i64 p = 0; p < P; ++p) o->ndraws_tail[p] = 0;
+}
+
+static int psis_entry(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i64 P, i64 sc, i64 sn, i64 sp, int negate,
+                      const double* r_eff, const int64_t* ndraws_tail, mcr_psis_out* out, bool host_weights)
+{
+    std::vector<i64> teff;
+    int rc = psis_check(ctx, draws_dev, dtype, C, N, P, negate, r_eff, ndraws_tail, out, teff);
+    if (rc || P == 0) return rc;
+    if (C * N == 0) { psis_fill_nan(out, P); return MCR_OK; }
+    if (tensor_extent(C, N, P, sc, sn, sp) < 0) return fail(ctx, MCR_EINVAL, "negative strides are not supported");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = psis_run(ctx, draws_dev, dtype, C, N, P, sc, sn, sp, negate, teff, out, host_weights);
+    return rc ? drain(ctx, rc, true) : rc;
+}
+
+int mcr_psis_plan(mcr_ctx* ctx, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc, int64_t sn, int64_t sp,
+                  int host_weights, int64_t* params_per_chunk)
+{
+    if (!ctx || !params_per_chunk) return fail(ctx, MCR_EINVAL, "mcr_psis_plan: NULL argument");
+    if (C < 1 || N < 1 || P < 1 || C > (i64)0x7FFFFFFFll / N || C * N >= (i64)0x7FFFFFFFll) { *params_per_chunk = 0; return MCR_OK; }
+    i64 pcmax = 0;
+    const int rc = plan_psis(ctx, C * N, P, dtype == MCR_F32 || needs_ingest(C, N, P, sc, sn, sp), host_weights != 0, pcmax);
+    if (rc) return rc;
+    *params_per_chunk = pcmax;
+    return MCR_OK;
+}
+
+int mcr_psis_dev(mcr_ctx* ctx, const void* draws_dev, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc, int64_t sn,
+                 int64_t sp, int negate, const double* r_eff, const int64_t* ndraws_tail, mcr_psis_out* out)
+{
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    return psis_entry(ctx, draws_dev, dtype, C, N, P, sc, sn, sp, negate, r_eff, ndraws_tail, out, false);
+}
+
+int mcr_psis(mcr_ctx* ctx, const void* draws, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc, int64_t sn, int64_t sp,
+             int negate, const double* r_eff, const int64_t* ndraws_tail, mcr_psis_out* out)
+{
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    std::vector<i64> teff;                     // (the entry checks again: the errors come before the upload)
+    int rc = psis_check(ctx, draws, dtype, C, N, P, negate, r_eff, ndraws_tail, out, teff);
+    const void* X = nullptr;
+    if (!rc) rc = pooled_upload(ctx, draws, dtype, C, N, P, sc, sn, sp, &X);
+    if (rc) return rc;
+    return psis_entry(ctx, X, dtype, C, N, P, sc, sn, sp, negate, r_eff, ndraws_tail, out, true);
+}
+
+int64_t mcr_psis_tail_length(int64_t M, double r_eff)
+{
+    if (!psis_r_eff_ok(r_eff)) return MCR_EINVAL;
+    return M < 1 ? 0 : psis_default_tail(M, r_eff);
+}
+
+int mcr_psis_host(const double* values, int64_t M, int negate, double r_eff, int64_t ndraws_tail, double* khat,
+                  int64_t* n_tail, double* lppd, double* elpd, double* p_loo, double* log_weights)
+{
+    if (M < 0 || M >= (i64)0x7FFFFFFFll || (M > 0 && !values) || (negate != 0 && negate != 1) || ndraws_tail < 0 ||
+        !psis_r_eff_ok(r_eff))
+        return MCR_EINVAL;
+    PsisResult c{};
+    c.khat = c.lppd = c.elpd = c.ploo = NAN;
+    if (M > 0) {
+        for (i64 i = 0; i < M; ++i)
+            if (!std::isfinite(values[i])) return MCR_ENONFINITE;
+        std::vector<i64> at((size_t)M);
+        for (i64 i = 0; i < M; ++i) at[(size_t)i] = i;
+        std::sort(at.begin(), at.end(), [&](i64 a, i64 b) { return values[a] < values[b]; });
+        std::vector<double> keys((size_t)M);
+        for (i64 j = 0; j < M; ++j) keys[(size_t)j] = values[at[(size_t)j]];
+        const i64 t = psis_tail_eff(M, ndraws_tail, r_eff);
+        std::vector<double> e((size_t)(t > 0 ? t : 1)), lg((size_t)pareto_grid(t));
+        const PsisKeys s{keys.data(), M, negate};
+        c = psis_column(PsisHostGroup{}, s, t, e.data(), lg.data());
+        if (log_weights)
+            for (i64 j = 0; j < M; ++j) log_weights[at[(size_t)j]] = psis_log_weight(s, c, negate ? M - 1 - j : j);
+    }
+    if (khat) *khat = c.khat;
+    if (n_tail) *n_tail = c.n;
+    if (lppd) *lppd = c.lppd;
+    if (elpd) *elpd = c.elpd;
+    if (p_loo) *p_loo = c.ploo;
     return MCR_OK;
 }
 

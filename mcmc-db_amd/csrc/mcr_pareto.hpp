@@ -73,9 +73,10 @@ struct ParetoHostWave {
 
 // One tail of n >= 5 ascending exceedances e.  lg: G doubles of scratch for the profile values l_j, shared by the waves
 // of W.  Returns khat in every thread for which W::finisher() holds (and in every thread when it returns before the
-// grid: a constant tail, xstar == 0).
+// grid: a constant tail, xstar == 0).  raw (optional; mcr_psis.hpp): where the grid was run, the finisher's unregularised
+// k, theta and the power-of-two scale into raw[0 .. 2]; untouched by the early returns.
 template <class W>
-__host__ __device__ inline double pareto_fit(const W& w, const double* e, int n, double* lg)
+__host__ __device__ inline double pareto_fit(const W& w, const double* e, int n, double* lg, double* raw = nullptr)
 {
 #pragma clang fp contract(off)  // the host and the device round every product and sum alike
     if (e[n - 1] == e[0]) return NAN;                      // a constant tail
@@ -104,6 +105,7 @@ __host__ __device__ inline double pareto_fit(const W& w, const double* e, int n,
     const double L = m + log(se);
     const double th = w.sum([&](int l) { double s = 0.0; for (int j = l; j < G; j += kWave) s += theta_j(j + 1) * exp(lg[j] - L); return s; });
     const double k = profile(th);
+    if (raw) { raw[0] = k; raw[1] = th; raw[2] = sc; }
     const double khat = (k * dn + 5.0) / (dn + 10.0);      // the weakly informative prior: mean 0.5, weight 10
     return khat != khat ? INFINITY : khat;
 }

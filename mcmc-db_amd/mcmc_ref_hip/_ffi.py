@@ -72,6 +72,10 @@ class Pareto(C.Structure):
     _fields_ = [("khat", _dp), ("khat_left", _dp), ("khat_right", _dp), ("ndraws_tail", _ip)]
 
 
+class Psis(C.Structure):
+    _fields_ = [("khat", _dp), ("ndraws_tail", _ip), ("lppd", _dp), ("elpd", _dp), ("p_loo", _dp), ("log_weights", C.c_void_p)]
+
+
 MCR_HDI_MAX_PROBS = 16                                      # probabilities of a Context.hdi call
 MCR_HDI_SLICE = 16384                                       # windows k_hdi_window gives one workgroup
 
@@ -181,6 +185,11 @@ SYMBOLS = {
     "mcr_pareto_plan": (C.c_int, [C.c_void_p, C.c_int] + [_I64] * 6 + [C.POINTER(C.c_int64)]),
     "mcr_pareto_tail_length": (C.c_int64, [_I64, C.c_double]),
     "mcr_pareto_fit_host": (C.c_int, [_dp, _I64, _I64, _dp, _dp, C.POINTER(C.c_int64)]),
+    "mcr_psis": (C.c_int, [C.c_void_p] + _TENSOR + [C.c_int, _dp, _ip, C.POINTER(Psis)]),
+    "mcr_psis_dev": (C.c_int, [C.c_void_p] + _TENSOR + [C.c_int, _dp, _ip, C.POINTER(Psis)]),
+    "mcr_psis_plan": (C.c_int, [C.c_void_p, C.c_int] + [_I64] * 6 + [C.c_int, C.POINTER(C.c_int64)]),
+    "mcr_psis_tail_length": (C.c_int64, [_I64, C.c_double]),
+    "mcr_psis_host": (C.c_int, [_dp, _I64, C.c_int, C.c_double, _I64, _dp, _ip, _dp, _dp, _dp, _dp]),
     "mcr_hdi": (C.c_int, [C.c_void_p] + _TENSOR + [_dp, C.c_int, C.POINTER(Hdi)]),
     "mcr_hdi_dev": (C.c_int, [C.c_void_p] + _TENSOR + [_dp, C.c_int, C.POINTER(Hdi)]),
     "mcr_hdi_plan": (C.c_int, [C.c_void_p, C.c_int] + [_I64] * 6 + [C.c_int, C.POINTER(C.c_int64)]),
@@ -423,6 +432,51 @@ def pareto_companions(khat: np.ndarray, M: int) -> tuple[np.ndarray, float]:
         min_ss = np.where(np.isnan(k), np.nan, min_ss)
         threshold = 1.0 - 1.0 / math.log10(M) if M > 1 else float("-inf") if M == 1 else float("nan")
     return min_ss, threshold
+
+
+def psis_tail_length(M: int, r_eff: float = 1.0) -> int:
+    """The default tail length of PSIS for M values (mcr_psis_tail_length: ceil(min(M / 5, 3 sqrt(M / r_eff))), loo's and
+    ArviZ's rule for every M; no device).  ValueError unless r_eff is finite and > 0."""
+    t = int(load_library().mcr_psis_tail_length(int(M), float(r_eff)))
+    if t < 0:
+        raise ValueError(f"r_eff must be finite and > 0; got {r_eff}")
+    return t
+
+
+def psis_host(values, negate: bool = False, r_eff: float = 1.0, ndraws_tail: int = 0, weights: bool = True) -> dict:
+    """PSIS of ONE column of float64 values in any order by the library's host routine (mcr_psis_host: the device's text
+    and summation order with the host's libm; no device).  negate: the values are log-likelihoods (LOO).  ndraws_tail 0:
+    the default.  khat, ndraws_tail (the n used), lppd, elpd, p_loo (NaN without negate) and, with weights, log_weights in
+    the order of `values`.  ValueError for a bad argument or a non-finite value."""
+    x = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+    kh, lppd, elpd, ploo, n = C.c_double(), C.c_double(), C.c_double(), C.c_double(), C.c_int64()
+    lw = np.full(max(x.size, 1), np.nan) if weights else None
+    rc = load_library().mcr_psis_host(_as_dp(x), x.size, int(bool(negate)), float(r_eff), int(ndraws_tail), C.byref(kh),
+                                      C.byref(n), C.byref(lppd), C.byref(elpd), C.byref(ploo), _as_dp(lw))
+    if rc != MCR_OK:
+        raise ValueError(f"mcr_psis_host: {'non-finite value' if rc == MCR_ENONFINITE else 'bad argument'} "
+                         f"(r_eff = {r_eff}, ndraws_tail = {ndraws_tail})")
+    res = {"khat": kh.value, "ndraws_tail": int(n.value), "lppd": lppd.value, "elpd": elpd.value, "p_loo": ploo.value}
+    if weights:
+        res["log_weights"] = lw[:x.size]
+    return res
+
+
+LOO_KHAT_BINS = (0.5, 0.7, 1.0)                              # k-hat counted in (-inf, 0.5], (0.5, 0.7], (0.7, 1], (1, inf)
+
+
+def loo_totals(elpd_i, p_loo_i, lppd_i, khat) -> dict:
+    """The totals of pointwise PSIS-LOO results (ArviZ's loo): elpd_loo, p_loo and lppd as math.fsum of the columns, se =
+    sqrt(P var(elpd_i, ddof = 0)), and khat_counts, the k-hats in (-inf, 0.5], (0.5, 0.7], (0.7, 1] and (1, inf) (a NaN
+    in none)."""
+    e = np.asarray(elpd_i, dtype=np.float64)
+    k = np.asarray(khat, dtype=np.float64)
+    P = int(e.size)
+    lo = (-np.inf,) + LOO_KHAT_BINS
+    hi = LOO_KHAT_BINS + (np.inf,)
+    return {"elpd_loo": math.fsum(e), "se": math.sqrt(P * float(np.var(e))) if P else float("nan"),
+            "p_loo": math.fsum(np.asarray(p_loo_i, dtype=np.float64)), "lppd": math.fsum(np.asarray(lppd_i, dtype=np.float64)),
+            "khat_counts": [int(np.count_nonzero((k > a) & (k <= b))) for a, b in zip(lo, hi)], "n_obs": P}
 
 
 def hdi_sorted_host(sorted_draws, prob=0.94):
@@ -1360,6 +1414,71 @@ class Context:
         """Parameters per workspace chunk of a pareto_khat call on this tensor (mcr_pareto_plan)."""
         v = C.c_int64(0)
         self._check(self.lib.mcr_pareto_plan(self.handle, *self._pareto_tensor(t, "pcn")[0], C.byref(v)))
+        return int(v.value)
+
+    def _psis_call(self, draws, layout: str, negate: bool, r_eff, ndraws_tail, weights: bool) -> dict:
+        """Every output of mcr_psis (a host array) or mcr_psis_dev (a DeviceTensor: the weights are written to device
+        memory and fetched here); psis and loo each return their part."""
+        targs, ptr, fn = self._pareto_tensor(draws, layout)            # the same pooling of a ragged tensor
+        dev = fn is self.lib.mcr_pareto_khat_dev
+        M, P = targs[1] * targs[2], targs[3]
+        r = None if r_eff is None else np.ascontiguousarray(np.broadcast_to(np.asarray(r_eff, dtype=np.float64), (P,)))
+        tails = None if ndraws_tail is None else np.ascontiguousarray(np.broadcast_to(np.asarray(ndraws_tail), (P,)), dtype=np.int64)
+        arrs = {n: np.full(max(P, 1), np.nan) for n in ("khat", "lppd", "elpd", "p_loo")}
+        nt = np.zeros(max(P, 1), dtype=np.int64)
+        lw = buf = None
+        if weights and dev:
+            buf = DeviceBuffer(self, max(P * M * 8, 8))
+        elif weights:
+            lw = np.full(max(P * M, 1), np.nan)
+        wptr = buf.ptr if buf is not None else lw.ctypes.data_as(C.c_void_p) if lw is not None else None
+        out = Psis(ndraws_tail=_as_ip(nt), log_weights=wptr, **{n: _as_dp(a) for n, a in arrs.items()})
+        try:
+            self._check((self.lib.mcr_psis_dev if dev else self.lib.mcr_psis)(
+                self.handle, ptr, *targs, int(bool(negate)), _as_dp(r), _as_ip(tails), C.byref(out)))
+            if buf is not None:
+                lw = buf.download(np.float64, max(P * M, 1))
+        finally:
+            if buf is not None:
+                buf.free()
+        res = {n: a[:P] for n, a in arrs.items()}
+        res["ndraws_tail"] = nt[:P]
+        if weights:
+            res["log_weights"] = lw[:P * M].reshape(P, M)
+        res["min_ss"], res["khat_threshold"] = pareto_companions(res["khat"], M)
+        res["n_draws"] = int(M)
+        return res
+
+    def psis(self, log_ratios, layout: str = "pcn", r_eff=None, ndraws_tail=None, weights: bool = True) -> dict:
+        """Pareto-smoothed importance sampling of every column of log importance ratios (mcr_psis: ArviZ's psislw, loo::psis)
+        of a host array or a DeviceTensor; the chains are pooled, so a ragged tensor is accepted.  r_eff: a relative
+        efficiency or P of them (default 1); ndraws_tail: a tail length or P of them (>= 1) instead of the default.
+        "log_weights" [P][M] in time order (normalised: every row's exp sums to 1; left out with weights=False, when
+        k_psis_weights does not run), and per column "khat", "ndraws_tail" (the tail values actually smoothed over),
+        "min_ss"; the float "khat_threshold" (pareto_companions)."""
+        if r_eff is not None and ndraws_tail is not None:
+            raise ValueError("give r_eff or ndraws_tail, not both")
+        res = self._psis_call(log_ratios, layout, False, r_eff, ndraws_tail, weights)
+        return {k: v for k, v in res.items() if k not in ("lppd", "elpd", "p_loo", "n_draws")}
+
+    def loo(self, log_lik, layout: str = "pcn", r_eff=None, pointwise: bool = True) -> dict:
+        """PSIS-LOO of a (chains x draws x observations) tensor of pointwise log-likelihoods, the observations on the
+        parameter axis (mcr_psis with negate: ArviZ's loo, loo::loo).  r_eff: as in psis.  The floats "elpd_loo", "se",
+        "p_loo", "lppd", the ints "n_obs" and "n_draws", "khat_counts" (loo_totals), "khat_threshold"; with pointwise also
+        the arrays "elpd_i", "p_loo_i", "lppd_i", "khat" and "ndraws_tail" per observation."""
+        res = self._psis_call(log_lik, layout, True, r_eff, None, False)
+        out = loo_totals(res["elpd"], res["p_loo"], res["lppd"], res["khat"])
+        out["n_draws"], out["khat_threshold"] = res["n_draws"], res["khat_threshold"]
+        if pointwise:
+            out.update({"elpd_i": res["elpd"], "p_loo_i": res["p_loo"], "lppd_i": res["lppd"], "khat": res["khat"],
+                        "ndraws_tail": res["ndraws_tail"]})
+        return out
+
+    def psis_params_per_chunk(self, t: "DeviceTensor", host_weights: bool = False) -> int:
+        """Columns per workspace chunk of a psis / loo call on this tensor (mcr_psis_plan); host_weights: of the host
+        entry with weights, whose chunk holds them too."""
+        v = C.c_int64(0)
+        self._check(self.lib.mcr_psis_plan(self.handle, *self._pareto_tensor(t, "pcn")[0], int(host_weights), C.byref(v)))
         return int(v.value)
 
     def _hdi_tensor(self, draws, layout: str):

@@ -12,6 +12,7 @@ this package's own: the chain files of a CmdStan run, parsed on the GPU, printed
 parameter and, with `--sliced K`, along K random directions of the joint distribution; exits like `compare`).
 `nested-rhat FILE --superchains K` prints nested R-hat, the diagnostic for many short chains, of a draws table.
 `pareto-khat FILE` prints the Pareto k-hat of every parameter's tails: whether a mean and a std of the draws can be trusted.
+`loo FILE` prints PSIS-LOO of a table's pointwise log-likelihood columns: elpd_loo, p_loo and the observations' k-hats.
 `hdi FILE` prints the highest-density interval(s) of every parameter: the shortest interval holding a share of the draws.
 `autocorr FILE` prints every parameter's integrated autocorrelation time (Sokal's window) and its stickiest and least
 sticky chain; as JSON, the autocorrelation function of every chain up to `--max-lag` as well.
@@ -188,6 +189,54 @@ def pareto_khat_cmd(file: Path, params: str | None, tail_draws: int | None, form
     except (ValueError, KeyError, IndexError) as exc:
         raise click.ClickException(str(exc)) from exc
     _echo_stats(stats, format_)
+
+
+def _loo_summary(r: dict) -> dict:
+    return {k: r[k] for k in ("elpd_loo", "se", "p_loo", "lppd", "n_obs", "n_draws", "khat_counts", "khat_threshold")}
+
+
+@main.command("loo")
+@click.argument("file", type=click.Path(path_type=Path, exists=True, dir_okay=False))
+@click.option("--prefix", default="log_lik", help="The pointwise log-likelihood columns: names that start with this (default: log_lik)")
+@click.option("--params", default=None, help="Comma-separated column list to choose from")
+@click.option("--against", default=None, type=click.Path(path_type=Path, exists=True, dir_okay=False),
+              help="A second model fitted to the same data: print elpd_diff (FILE minus this) and se_diff as well")
+@click.option("--pointwise", is_flag=True, help="Print elpd, p_loo, lppd and k-hat of every observation")
+@click.option("--format", "format_", type=click.Choice(["table", "json"], case_sensitive=False), default="table")
+def loo_cmd(file: Path, prefix: str, params: str | None, against: Path | None, pointwise: bool, format_: str) -> None:
+    """PSIS-LOO (Vehtari et al.; ArviZ's loo) of the pointwise log-likelihood columns of a draws table (no counterpart in
+    the reference): elpd_loo with its standard error, p_loo, and the observations' Pareto k-hats counted in (-inf, 0.5],
+    (0.5, 0.7], (0.7, 1] and (1, inf) -- above 0.7 an observation's estimate is not reliable."""
+    plist = params.split(",") if params else None
+    try:
+        if against is not None:
+            cmp_ = convert_mod.loo_compare_files(file, against, params=plist, prefix=prefix)
+            r, other = cmp_["a"], cmp_["b"]
+        else:
+            cmp_, other, r = None, None, convert_mod.loo_file(file, params=plist, prefix=prefix)
+    except (ValueError, KeyError, IndexError) as exc:
+        raise click.ClickException(str(exc)) from exc
+    rows = {n: {"elpd": float(r["elpd_i"][i]), "p_loo": float(r["p_loo_i"][i]), "lppd": float(r["lppd_i"][i]),
+                "khat": float(r["khat"][i])} for i, n in enumerate(r["names"])} if pointwise else None
+    if format_ == "json":
+        out = _loo_summary(r)
+        if cmp_ is not None:
+            out.update(elpd_diff=cmp_["elpd_diff"], se_diff=cmp_["se_diff"], against=_loo_summary(other))
+        if rows is not None:
+            out["pointwise"] = rows
+        click.echo(json.dumps(out, indent=2, sort_keys=True))
+        return
+    for name, res in (("", r),) if other is None else ((str(file), r), (str(against), other)):
+        if name:
+            click.echo(f"# {name}")
+        click.echo(f"elpd_loo {res['elpd_loo']:.6g}  se {res['se']:.6g}  p_loo {res['p_loo']:.6g}  lppd {res['lppd']:.6g}")
+        click.echo(f"observations {res['n_obs']}  draws {res['n_draws']}")
+        c = res["khat_counts"]
+        click.echo(f"khat (-inf, 0.5] {c[0]}  (0.5, 0.7] {c[1]}  (0.7, 1] {c[2]}  (1, inf) {c[3]}")
+    if cmp_ is not None:
+        click.echo(f"elpd_diff {cmp_['elpd_diff']:.6g}  se_diff {cmp_['se_diff']:.6g}")
+    if rows is not None:
+        _print_table(rows)
 
 
 @main.command("hdi")

@@ -8,6 +8,7 @@ parameter), `_checks` (:164-172) and `_enforce_checks` (:175-178).
 from __future__ import annotations
 
 import json
+import math
 import time
 import zipfile
 from collections.abc import Iterable
@@ -621,6 +622,34 @@ def pareto_khat_file(path: Path, params: Iterable[str] | None = None, ndraws_tai
         r = ctx.pareto_khat(x.reshape(len(names), 1, -1), "pcn", ndraws_tail=ndraws_tail)
     keys = ("khat", "khat_left", "khat_right", "ndraws_tail", "min_ss")
     return {n: {k: (int if k == "ndraws_tail" else float)(r[k][i]) for k in keys} for i, n in enumerate(names)}
+
+
+def loo_file(path: Path, params: Iterable[str] | None = None, prefix: str = "log_lik", context=None) -> dict:
+    """PSIS-LOO of the pointwise log-likelihood columns of a draws table (a `.csv` or chain-list `.json.zip`, read on the
+    host): the columns whose name starts with `prefix` (of `params`, or of all), one observation each; the chains are
+    pooled and may differ in length.  Context.loo's result -- elpd_loo, se, p_loo, lppd, n_obs, n_draws, khat_counts,
+    khat_threshold, the pointwise arrays -- and "names", the observations' columns.  ValueError when no column matches."""
+    table, names = _table_and_names(_read_input(Path(path)), params)
+    names = [n for n in names if n.startswith(prefix)]
+    if not names:
+        raise ValueError(f"no column starts with {prefix!r}")
+    x, _ = table_to_tensor(table, names)
+    ctx = context or _ffi.default_context()
+    with _ffi.value_errors():
+        r = ctx.loo(x.reshape(len(names), 1, -1), "pcn")
+    r["names"] = names
+    return r
+
+
+def loo_compare_files(a: Path, b: Path, params: Iterable[str] | None = None, prefix: str = "log_lik", context=None) -> dict:
+    """Two models fitted to the same data, compared by PSIS-LOO (loo_file on each): elpd_diff = fsum(elpd_i^a - elpd_i^b)
+    (positive: `a` predicts better), se_diff = sqrt(P var(diff, ddof = 0)), and the two results under "a" and "b".
+    ValueError when the numbers of observations differ."""
+    ra, rb = loo_file(a, params, prefix, context), loo_file(b, params, prefix, context)
+    if ra["n_obs"] != rb["n_obs"]:
+        raise ValueError(f"the models have {ra['n_obs']} and {rb['n_obs']} observations: not fitted to the same data")
+    diff = ra["elpd_i"] - rb["elpd_i"]
+    return {"elpd_diff": math.fsum(diff), "se_diff": math.sqrt(diff.size * float(np.var(diff))), "a": ra, "b": rb}
 
 
 def hdi_file(path: Path, params: Iterable[str] | None = None, prob: Iterable[float] = (0.94,),

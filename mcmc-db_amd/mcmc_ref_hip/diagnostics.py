@@ -122,6 +122,21 @@ def pareto_khat(chains: Sequence[Sequence[float]], *, r_eff=None, ndraws_tail=No
     return pareto_khat_detail(chains, r_eff=r_eff, ndraws_tail=ndraws_tail, context=context)["khat"]
 
 
+def psis_log_weights(chains: Sequence[Sequence[float]], *, r_eff=None, ndraws_tail=None, context=None) -> dict:
+    """Pareto-smoothed importance sampling of ONE column of log importance ratios given as chains of any lengths (they
+    are pooled, chain after chain): "log_weights" (normalised, in the order of the pooled draws), "khat", "ndraws_tail"
+    (the tail values smoothed over), "min_ss" and "khat_threshold" (Context.psis).  The tail length comes from
+    `ndraws_tail`, or from the relative efficiency `r_eff`, or is the default of r_eff = 1."""
+    if r_eff is not None and ndraws_tail is not None:
+        raise ValueError("give r_eff or ndraws_tail, not both")
+    x = np.concatenate([np.asarray(c, dtype=np.float64).reshape(-1) for c in chains]) if len(chains) else np.zeros(0)
+    ctx = context or _ffi.default_context()
+    with _ffi.value_errors():
+        res = ctx.psis(x.reshape(1, 1, -1), "pcn", r_eff=r_eff, ndraws_tail=ndraws_tail)
+    return {"log_weights": res["log_weights"][0], "khat": float(res["khat"][0]), "ndraws_tail": int(res["ndraws_tail"][0]),
+            "min_ss": float(res["min_ss"][0]), "khat_threshold": res["khat_threshold"]}
+
+
 def hdi(chains: Sequence[Sequence[float]], prob: float = 0.94, *, context=None) -> tuple[float, float]:
     """The highest-density interval of ONE parameter given as chains of any lengths (they are pooled): the shortest
     interval that holds floor(prob * M) + 1 of the M draws, the first of several equally short ones (Context.hdi; ArviZ's
