@@ -262,6 +262,54 @@ int mcr_sliced_plan(mcr_ctx* ctx, int64_t Mr, int64_t Ma, int64_t P, int64_t K, 
 #define MCR_PROJ_TILE_M 512  /* draws per k_project workgroup (two per lane) */
 #define MCR_PROJ_TILE_K 8    /* directions per k_project workgroup (accumulators in registers) */
 #define MCR_PROJ_CHUNK_P 64  /* parameters whose weights and centers a k_project workgroup stages in LDS at a time */
+/* Energy distance (Szekely and Rizzo, "Energy statistics: a class of statistics based on distances"): the direction-free
+ * counterpart of the sliced check, a two-sample statistic of the JOINT distribution without a seed, a number of
+ * directions or any tuning parameter.  ABSENT from the reference.
+ *     E(X, Y) = 2 E|X - Y| - E|X - X'| - E|Y - Y'|
+ * As a V-statistic it is non-negative; in the population it is zero only when the two distributions are equal; it is
+ * rotation invariant.  ref[P][Mr], act[P][Ma]: f64, row-major, as for mcr_two_sample.  scale[P]: finite and >= 0, NULL
+ * means all ones.  For two draws x and y of either sample, everything in IEEE double:
+ *     1. the scaled value is u_p = x_p * scale_p, rounded once (scale == NULL: x_p itself);
+ *     2. acc starts at +0.0;
+ *     3. for p = 0 .. P-1 in order, t = u_p(x) - u_p(y), rounded once, and acc = fma(t, t, acc);
+ *     4. d(x, y) = sqrt(acc), correctly rounded.
+ * So d has the same bits wherever the pair sits in a tile, a launch or a chunk of parameters; d(x, y) = d(y, x) exactly;
+ * d(x, x) = +0.0 exactly; a parameter with scale 0 drops out.  The three pair sums
+ *     S_xy = sum_{i < Mr, j < Ma} d(ref_i, act_j)    S_xx = sum_{i, j < Mr} d(ref_i, ref_j)    S_yy = sum_{i, j < Ma} d(act_i, act_j)
+ * (S_xx and S_yy include their zero diagonals) are each taken in an order that depends on (Mr, Ma, P) only: a call gives
+ * the same bits on the host entry and on the device entry, on repeated calls, under any workspace limit, with or without
+ * profiling.  out[0..5], in this order:
+ *     A = S_xy / (double)(Mr Ma)     B = S_xx / (double)(Mr Mr)     C = S_yy / (double)(Ma Ma)      (one division each)
+ *     E = (A - B) + (A - C)          H = E / (2 A), or 0 when A == 0                                 (in [0, 1])
+ *     T = Mr Ma / (Mr + Ma) * E      (the test statistic of the energy two-sample test)
+ * B and C are the V-statistic means; M / (M - 1) times either is the U-statistic mean over the M (M - 1) pairs i != j.
+ * NO p-value is offered: a permutation test needs the pooled (Mr + Ma)^2 distance matrix, tens of gigabytes at these
+ * sizes, and assumes independent draws, which MCMC output is not.  E is a distance to be thresholded, like sliced_w1.
+ * Cost: O(M^2 P).  A call is refused when (Mr Ma + Mr (Mr + 1) / 2 + Ma (Ma + 1) / 2) P > MCR_ENERGY_MAX_WORK, and no
+ * single launch carries more than MCR_ENERGY_LAUNCH_WORK pair-parameters: with J = ceil(Mr / TI) ceil(Ma / TJ) +
+ * T(ceil(Mr / TI)) + T(ceil(Ma / TI)) tile jobs, T(n) = n (n + 1) / 2, a call is ceil(J / max(1, floor(MCR_ENERGY_LAUNCH_WORK
+ * / (TI TJ P)))) launches of k_energy_pairs (the jobs spread evenly over them) and one of k_energy_reduce.  The
+ * environment variable MCR_ENERGY_LAUNCH_WORK, read once at mcr_init, lowers the launch budget (tests; no bit changes).
+ * MCR_EINVAL (the message names the cause): a NULL pointer, Mr or Ma < 1, P < 1, a negative or non-finite scale,
+ * summaries in flight, work over the limit.  MCR_ENONFINITE: non-finite draws, or a squared distance that overflows.
+ * MCR_ENOMEM (naming the need): the workspace limit does not fit the partials.  The context stays usable after every
+ * error.  Synchronous.  Parity unpinned by the reference. */
+int mcr_energy_distance(mcr_ctx* ctx, const double* ref, int64_t Mr, const double* act, int64_t Ma, int64_t P,
+                        const double* scale, double* out6);
+/* The same with ref_dev / act_dev in this ctx's device memory (any 8-byte alignment); scale and out6 on the host. */
+int mcr_energy_distance_dev(mcr_ctx* ctx, const double* ref_dev, int64_t Mr, const double* act_dev, int64_t Ma, int64_t P,
+                            const double* scale, double* out6);
+/* The definition on the host, without a context: the same per-pair arithmetic bit for bit, the pair sums in long double
+ * (rounded to double before the one division).  The same argument errors and work limit (codes only, no message). */
+int mcr_energy_distance_host(const double* ref, int64_t Mr, const double* act, int64_t Ma, int64_t P, const double* scale,
+                             double* out6);
+/* Bytes of workspace such a call carves (one partial per tile job, the scales, the results). */
+int mcr_energy_workspace(mcr_ctx* ctx, int64_t Mr, int64_t Ma, int64_t P, size_t* bytes);
+#define MCR_ENERGY_TILE_I 128   /* draws x draws of a k_energy_pairs workgroup (TI, TJ) */
+#define MCR_ENERGY_TILE_J 128
+#define MCR_ENERGY_CHUNK_P 8    /* parameters a k_energy_pairs workgroup stages in LDS at a time */
+#define MCR_ENERGY_MAX_WORK 17592186044416ll   /* 2^44 pair-parameters of a call */
+#define MCR_ENERGY_LAUNCH_WORK 274877906944ll  /* 2^38 pair-parameters of a launch */
 /* Nested R-hat: the convergence diagnostic for MANY SHORT chains (Margossian, Hoffman, Sountsov, Riou-Durand, Vehtari,
  * Gelman, "Nested R-hat: assessing the convergence of Markov chain Monte Carlo when running many short chains";
  * rhat_nested of the R package posterior).  ABSENT from the reference: it replaces no reference line, and split R-hat /

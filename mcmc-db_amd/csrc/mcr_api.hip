@@ -30,6 +30,7 @@
 #include "mcr_diag.hpp"
 #include "mcr_fft.hpp"
 #include "mcr_ext.hpp"
+#include "mcr_energy.hpp"
 #include "mcr_nested.hpp"
 #include "mcr_acf.hpp"
 #include "mcr_pareto.hpp"
@@ -67,7 +68,7 @@ enum KernelId {
     K_LAYOUT_SCAN, K_LAYOUT_KEYS, K_LAYOUT_HIST, K_LAYOUT_OFFSETS, K_LAYOUT_SCATTER, K_LAYOUT_BOUNDS,
     K_PQW_ENCODE, K_PQW_COMPACT, K_CSVW_FORMAT, K_CSVW_SCAN, K_CSVW_COMPACT, K_SELECT_ROWS, K_PROJECT,
     K_CHAIN_MOMENTS, K_NESTED_COMBINE, K_PARETO_FIT, K_PSIS_COLUMN, K_PSIS_WEIGHTS, K_HDI_WINDOW, K_HDI_PICK,
-    K_ACF_MEAN, K_ACF_PRODUCTS, K_ACF_FINISH, K_ACF_POOL, K_COUNT
+    K_ACF_MEAN, K_ACF_PRODUCTS, K_ACF_FINISH, K_ACF_POOL, K_ENERGY_PAIRS, K_ENERGY_REDUCE, K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {
     "k_ingest", "k_moments", "k_moments_final", "k_tile_sort", "k_merge", "k_order_stats", "k_rank_z",
@@ -79,7 +80,7 @@ const char* const kKernelNames[K_COUNT] = {
     "k_layout_scan", "k_layout_keys", "k_layout_hist", "k_layout_offsets", "k_layout_scatter", "k_layout_bounds",
     "k_pqw_encode", "k_pqw_compact", "k_csvw_format", "k_csvw_scan", "k_csvw_compact", "k_select_rows", "k_project",
     "k_chain_moments", "k_nested_combine", "k_pareto_fit", "k_psis_column", "k_psis_weights", "k_hdi_window", "k_hdi_pick",
-    "k_acf_mean", "k_acf_products", "k_acf_finish", "k_acf_pool"};
+    "k_acf_mean", "k_acf_products", "k_acf_finish", "k_acf_pool", "k_energy_pairs", "k_energy_reduce"};
 
 struct EvPair { hipEvent_t a, b; int kid; };
 
@@ -203,6 +204,7 @@ struct mcr_ctx {
     PinBuf hdi_host{4};                // its results on the host
     DevBuf acf_dev{4};                 // mcr_autocorr: result arrays + the chains' non-finite counts
     PinBuf acf_host{4};                // the counts on the host
+    i64 energy_launch_work = kEnLaunchWork;   // MCR_ENERGY_LAUNCH_WORK: pair-parameters of one k_energy_pairs launch (tests lower it)
     DevBuf guard_count;                // device counters (2 unsigned): band lags re-derived the reference's way (mcr_rho_guard_count),
                                        // tiles the tile sort sorted as pairs after all (mcr_tile_fallback_count)
 };
@@ -1462,6 +1464,7 @@ int mcr_init(int device, mcr_ctx** out)
     if (const char* env = getenv("MCR_FFT")) ctx->fft_on = atoi(env) != 0;
     if (const char* env = getenv("MCR_SPLITTERS_PAIRWISE")) ctx->splitters_pairwise = atoi(env) != 0;
     if (const char* env = getenv("MCR_FORK")) ctx->fork_lone = atoi(env) != 0;
+    if (const char* env = getenv("MCR_ENERGY_LAUNCH_WORK")) { const long long v = atoll(env); if (v > 0 && v <= kEnLaunchWork) ctx->energy_launch_work = v; }
     if (const char* env = getenv("MCR_RHO_BAND")) { const double v = atof(env); if (v >= 0.0 && v < 1.0) ctx->rho_band = v; }
     if (ctx->guard_count.reserve(ctx, 2 * sizeof(unsigned)) != MCR_OK ||
         hipMemsetAsync(ctx->guard_count.p, 0, 2 * sizeof(unsigned), ctx->stream) != hipSuccess ||
@@ -2016,6 +2019,124 @@ int mcr_sliced_two_sample(mcr_ctx* ctx, const double* ref, int64_t Mr, const dou
     HIP_TRY(ctx, hipMemcpyAsync(Xr, ref, sizeof(double) * (size_t)P * Mr, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(Xa, act, sizeof(double) * (size_t)P * Ma, hipMemcpyHostToDevice, ctx->stream));
     return mcr_sliced_two_sample_dev(ctx, Xr, Mr, Xa, Ma, P, dirs, center, K, ks, w1, proj_ref, proj_act);
+}
+
+// ---- energy distance (mcr_energy.hpp) ---------------------------------------------------------------------------------
+static_assert(kEnTI == MCR_ENERGY_TILE_I && kEnTJ == MCR_ENERGY_TILE_J && kEnPC == MCR_ENERGY_CHUNK_P &&
+              kEnMaxWork == MCR_ENERGY_MAX_WORK && kEnLaunchWork == MCR_ENERGY_LAUNCH_WORK,
+              "mcmcref_hip.h states k_energy_pairs' geometry and the work limits");
+
+// The workspace of a call: one partial per tile job, the scales, the results (six outputs + the three sums).
+struct EnergyWs { double *part, *scale, *res; };
+
+static void carve_energy(Carve& cv, EnergyWs& w, const EnergyJobs& jb, i64 P)
+{
+    w.part = cv.take<double>((size_t)jb.total());
+    w.scale = cv.take<double>((size_t)P);
+    w.res = cv.take<double>(9);
+}
+
+// The shape of a call: MCR_EINVAL with the cause, else MCR_OK.
+static int energy_shape_check(mcr_ctx* ctx, i64 Mr, i64 Ma, i64 P)
+{
+    if (Mr < 1 || Ma < 1) return fail(ctx, MCR_EINVAL, "mcr_energy_distance: both samples need at least one draw (Mr = %lld, Ma = %lld)", Mr, Ma);
+    if (P < 1) return fail(ctx, MCR_EINVAL, "mcr_energy_distance: P = %lld, at least one parameter is needed", P);
+    if (!energy_work_ok(Mr, Ma, P))
+        return fail(ctx, MCR_EINVAL, "mcr_energy_distance: (Mr Ma + Mr (Mr + 1) / 2 + Ma (Ma + 1) / 2) P is over the work limit "
+                    "MCR_ENERGY_MAX_WORK = %lld pair-parameters (Mr = %lld, Ma = %lld, P = %lld): thin the samples", kEnMaxWork, Mr, Ma, P);
+    return MCR_OK;
+}
+
+static int energy_check(mcr_ctx* ctx, const void* ref, i64 Mr, const void* act, i64 Ma, i64 P, const double* scale, const double* out)
+{
+    if (!ref || !act || !out) return fail(ctx, MCR_EINVAL, "mcr_energy_distance: NULL argument (%s)", !ref ? "ref" : !act ? "act" : "out");
+    const int rc = energy_shape_check(ctx, Mr, Ma, P);
+    if (rc) return rc;
+    for (i64 p = 0; scale && p < P; ++p)
+        if (!(scale[p] >= 0.0) || std::isinf(scale[p]))
+            return fail(ctx, MCR_EINVAL, "mcr_energy_distance: scale[%lld] is negative or not finite", (long long)p);
+    if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "mcr_energy_distance with summaries in flight");
+    return MCR_OK;
+}
+
+int mcr_energy_workspace(mcr_ctx* ctx, int64_t Mr, int64_t Ma, int64_t P, size_t* bytes)
+{
+    if (!ctx || !bytes) return fail(ctx, MCR_EINVAL, "mcr_energy_workspace: NULL argument");
+    const int rc = energy_shape_check(ctx, Mr, Ma, P);
+    if (rc) return rc;
+    Carve m{nullptr};
+    EnergyWs w;
+    carve_energy(m, w, energy_jobs(Mr, Ma), P);
+    *bytes = m.off;
+    return MCR_OK;
+}
+
+int mcr_energy_distance_dev(mcr_ctx* ctx, const double* ref_dev, int64_t Mr, const double* act_dev, int64_t Ma, int64_t P,
+                            const double* scale, double* out)
+{
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    int rc = energy_check(ctx, ref_dev, Mr, act_dev, Ma, P, scale, out);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const EnergyJobs jb = energy_jobs(Mr, Ma);
+    EnergyWs w;
+    { Carve m{nullptr}; carve_energy(m, w, jb, P);
+      if (m.off > ctx->ws_limit)
+          return fail(ctx, MCR_ENOMEM, "workspace limit too small: the energy distance of this shape needs %zu bytes, the limit is %zu",
+                      m.off, ctx->ws_limit); }
+    rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) { carve_energy(cv, w, jb, P); });
+    if (rc) return rc;
+    const std::vector<double> ones(scale ? 0 : (size_t)P, 1.0);            // x * 1.0 is x: one kernel text for both
+    HIP_TRY(ctx, hipMemcpyAsync(w.scale, scale ? scale : ones.data(), sizeof(double) * (size_t)P, hipMemcpyHostToDevice, ctx->stream));
+    const bool aligned = ((Mr | Ma) & 1) == 0 &&
+                         ((reinterpret_cast<uintptr_t>(ref_dev) | reinterpret_cast<uintptr_t>(act_dev)) & 15) == 0;
+    i64 launches = 0, per = 0;
+    energy_launches(jb, P, ctx->energy_launch_work, launches, per);
+    for (i64 l = 0; l < launches; ++l) {                 // a partial per job: how the jobs are cut into launches changes no bit
+        const i64 job0 = l * per, n = jb.total() - job0 < per ? jb.total() - job0 : per;
+        const dim3 grid((unsigned)((n + 7) / 8 * 8));
+        if (aligned)
+            LAUNCH(ctx, K_ENERGY_PAIRS, (k_energy_pairs<true>), grid, dim3(kEnNT), 0, ref_dev, (i64)Mr, act_dev, (i64)Ma, (i64)P,
+                   (const double*)w.scale, job0, n, w.part);
+        else
+            LAUNCH(ctx, K_ENERGY_PAIRS, (k_energy_pairs<false>), grid, dim3(kEnNT), 0, ref_dev, (i64)Mr, act_dev, (i64)Ma, (i64)P,
+                   (const double*)w.scale, job0, n, w.part);
+    }
+    LAUNCH(ctx, K_ENERGY_REDUCE, k_energy_reduce, dim3(1), dim3(kEnNT), 0, (const double*)w.part, (i64)Mr, (i64)Ma, w.res);
+    double res[9];
+    HIP_TRY(ctx, hipMemcpyAsync(res, w.res, sizeof(res), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    prof_resolve(ctx);
+    if (!std::isfinite(res[6]) || !std::isfinite(res[7]) || !std::isfinite(res[8]))
+        return fail(ctx, MCR_ENONFINITE, "draws contain non-finite values, or a squared distance overflows");
+    memcpy(out, res, 6 * sizeof(double));
+    return MCR_OK;
+}
+
+int mcr_energy_distance(mcr_ctx* ctx, const double* ref, int64_t Mr, const double* act, int64_t Ma, int64_t P,
+                        const double* scale, double* out)
+{
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    int rc = energy_check(ctx, ref, Mr, act, Ma, P, scale, out);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    void* X[2];
+    rc = stage_buffers(ctx, {sizeof(double) * (size_t)P * Mr, sizeof(double) * (size_t)P * Ma}, X);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(X[0], ref, sizeof(double) * (size_t)P * Mr, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(X[1], act, sizeof(double) * (size_t)P * Ma, hipMemcpyHostToDevice, ctx->stream));
+    return mcr_energy_distance_dev(ctx, (const double*)X[0], Mr, (const double*)X[1], Ma, P, scale, out);
+}
+
+int mcr_energy_distance_host(const double* ref, int64_t Mr, const double* act, int64_t Ma, int64_t P, const double* scale,
+                             double* out)
+{
+    try {
+        const int rc = energy_host(ref, Mr, act, Ma, P, scale, out);
+        return rc == 0 ? MCR_OK : rc == 1 ? MCR_EINVAL : MCR_ENONFINITE;
+    } catch (const std::exception&) {
+        return MCR_ENOMEM;
+    }
 }
 
 // ---- nested R-hat (mcr_nested.hpp) ------------------------------------------------------------------------------------

@@ -110,6 +110,15 @@ MCR_PQW_F64, MCR_PQW_I64, MCR_PQW_SEQ = 0, 1, 2              # sources of a writ
 MCR_PQW_PAGE_ROWS, MCR_PQW_ROW_GROUP_ROWS = 8192, 1048576
 MCR_CSVW_TILE_FIELDS, MCR_CSVW_FIELD_MAX, MCR_SELECT_BLOCK_ROWS = 2048, 26, 256
 MCR_PROJ_TILE_M, MCR_PROJ_TILE_K, MCR_PROJ_CHUNK_P = 512, 8, 64     # k_project's geometry
+MCR_ENERGY_TILE_I, MCR_ENERGY_TILE_J, MCR_ENERGY_CHUNK_P = 128, 128, 8    # k_energy_pairs' geometry
+MCR_ENERGY_MAX_WORK, MCR_ENERGY_LAUNCH_WORK = 1 << 44, 1 << 38            # pair-parameters of a call, of one launch
+
+
+def energy_launches(Mr: int, Ma: int, P: int, launch_work: int = MCR_ENERGY_LAUNCH_WORK) -> int:
+    """k_energy_pairs launches of an energy_distance call of this shape (the rule stated in mcmcref_hip.h)."""
+    nr, na = -(-Mr // MCR_ENERGY_TILE_I), -(-Ma // MCR_ENERGY_TILE_J)
+    jobs = nr * na + nr * (nr + 1) // 2 + na * (na + 1) // 2
+    return -(-jobs // max(1, launch_work // (MCR_ENERGY_TILE_I * MCR_ENERGY_TILE_J * P)))
 CSV_HEADERS = {"quoted": 0, "plain": 1, "none": 2}           # MCR_CSVW_HEADER_*
 INT64_MAX = (1 << 63) - 1
 
@@ -177,6 +186,10 @@ SYMBOLS = {
     "mcr_sliced_two_sample_dev": (C.c_int, [C.c_void_p, C.c_void_p, _I64, C.c_void_p, _I64, _I64, _dp, _dp, _I64, _dp, _dp,
                                             _dp, _dp]),
     "mcr_sliced_plan": (C.c_int, [C.c_void_p, _I64, _I64, _I64, _I64, C.POINTER(C.c_int64)]),
+    "mcr_energy_distance": (C.c_int, [C.c_void_p, _dp, _I64, _dp, _I64, _I64, _dp, _dp]),
+    "mcr_energy_distance_dev": (C.c_int, [C.c_void_p, C.c_void_p, _I64, C.c_void_p, _I64, _I64, _dp, _dp]),
+    "mcr_energy_distance_host": (C.c_int, [_dp, _I64, _dp, _I64, _I64, _dp, _dp]),
+    "mcr_energy_workspace": (C.c_int, [C.c_void_p, _I64, _I64, _I64, C.POINTER(C.c_size_t)]),
     "mcr_nested_rhat": (C.c_int, [C.c_void_p] + _TENSOR + [C.POINTER(C.c_int32), C.POINTER(Nested)]),
     "mcr_nested_rhat_dev": (C.c_int, [C.c_void_p] + _TENSOR + [C.POINTER(C.c_int32), C.POINTER(Nested)]),
     "mcr_nested_plan": (C.c_int, [C.c_void_p, C.c_int] + [_I64] * 7 + [C.POINTER(C.c_int64)]),
@@ -281,6 +294,26 @@ SYMBOLS = {
                                   C.POINTER(C.c_uint8), _ip]),
     "mcr_parse_json_number": (C.c_int, [C.c_char_p, C.c_size_t, _dp, C.POINTER(C.c_int)]),
 }
+
+ENERGY_KEYS = ("a", "b", "c", "e", "h", "t")          # out6 of mcr_energy_distance, in order
+
+
+def energy_distance_host(ref, actual, scale=None) -> dict:
+    """mcr_energy_distance_host: the definition of Context.energy_distance on the host, without a GPU (the same per-pair
+    arithmetic bit for bit, the pair sums in long double)."""
+    r = np.ascontiguousarray(ref, dtype=np.float64)
+    a = np.ascontiguousarray(actual, dtype=np.float64)
+    if r.ndim != 2 or a.ndim != 2 or r.shape[0] != a.shape[0]:
+        raise ValueError("ref and actual must be 2-D with the same number of parameters")
+    s = None if scale is None else np.ascontiguousarray(scale, dtype=np.float64)
+    if s is not None and s.shape != (r.shape[0],):
+        raise ValueError("scale must have one entry per parameter")
+    out = np.full(6, np.nan)
+    rc = load_library().mcr_energy_distance_host(_as_dp(r), r.shape[1], _as_dp(a), a.shape[1], r.shape[0], _as_dp(s), _as_dp(out))
+    if rc != MCR_OK:
+        raise McrError(rc, "mcr_energy_distance_host")
+    return dict(zip(ENERGY_KEYS, (float(v) for v in out)))
+
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -1347,6 +1380,46 @@ class Context:
         """Directions per workspace chunk of a sliced_two_sample call of this shape (mcr_sliced_plan)."""
         v = C.c_int64(0)
         self._check(self.lib.mcr_sliced_plan(self.handle, Mr, Ma, P, K, C.byref(v)))
+        return int(v.value)
+
+    @staticmethod
+    def _energy_scale(scale, P: int):
+        s = None if scale is None else np.ascontiguousarray(scale, dtype=np.float64)
+        if s is not None and s.shape != (P,):
+            raise ValueError("scale must have one entry per parameter")
+        if s is not None and not (np.isfinite(s).all() and (s >= 0).all()):
+            raise ValueError("scale must be finite and >= 0")
+        return s
+
+    def energy_distance(self, ref, actual, scale=None) -> dict:
+        """Energy distance of Szekely and Rizzo between the joint draws ref [P][Mr] and actual [P][Ma] (2-D, finite), every
+        parameter multiplied by scale[p] first (None: ones) -- mcr_energy_distance.  Keys: a, b, c (the mean distances
+        between the samples, within ref, within actual), e = 2a - b - c, h = e / 2a in [0, 1], t = Mr Ma / (Mr + Ma) e."""
+        r = np.ascontiguousarray(ref, dtype=np.float64)
+        a = np.ascontiguousarray(actual, dtype=np.float64)
+        if r.ndim != 2 or a.ndim != 2 or r.shape[0] != a.shape[0]:
+            raise ValueError("ref and actual must be 2-D with the same number of parameters")
+        if not (np.isfinite(r).all() and np.isfinite(a).all()):
+            raise ValueError("draws contain non-finite values")
+        s = self._energy_scale(scale, r.shape[0])
+        return self._energy(self.lib.mcr_energy_distance, _as_dp(r), r.shape[1], _as_dp(a), a.shape[1], r.shape[0], s)
+
+    def energy_distance_dev(self, ref_ptr, Mr: int, act_ptr, Ma: int, P: int, scale=None) -> dict:
+        """energy_distance on draws already in this context's device memory: ref_ptr -> [P][Mr] f64, act_ptr -> [P][Ma]
+        f64 (device addresses or DeviceBuffer.ptr).  Non-finite draws raise McrError (MCR_ENONFINITE)."""
+        s = self._energy_scale(scale, int(P))
+        as_ptr = lambda v: v if isinstance(v, C.c_void_p) else C.c_void_p(int(v))
+        return self._energy(self.lib.mcr_energy_distance_dev, as_ptr(ref_ptr), int(Mr), as_ptr(act_ptr), int(Ma), int(P), s)
+
+    def _energy(self, entry, ref, Mr, act, Ma, P, s) -> dict:
+        out = np.full(6, np.nan)
+        self._check(entry(self.handle, ref, Mr, act, Ma, P, _as_dp(s), _as_dp(out)))
+        return dict(zip(ENERGY_KEYS, (float(v) for v in out)))
+
+    def energy_workspace(self, Mr: int, Ma: int, P: int) -> int:
+        """Bytes of workspace an energy_distance call of this shape carves (mcr_energy_workspace)."""
+        v = C.c_size_t(0)
+        self._check(self.lib.mcr_energy_workspace(self.handle, int(Mr), int(Ma), int(P), C.byref(v)))
         return int(v.value)
 
     def nested_rhat(self, draws, superchain_ids, layout: str = "pcn") -> dict:

@@ -349,17 +349,24 @@ def compare_cmd(model: str, actual_path: Path, tolerance: float, format_: str) -
 @click.option("--hdi-prob", default=None, type=float, help="Report the highest-density intervals of this share of both samples")
 @click.option("--hdi-tol", default=None, type=float,
               help="Fail a parameter whose HDI endpoints differ by more than this share of the reference interval's width")
+@click.option("--energy", is_flag=True, help="Energy distance of the standardised joint draws (direction-free joint check)")
+@click.option("--energy-max", default=None, type=float, help="Fail when the energy distance exceeds this (implies --energy)")
+@click.option("--energy-max-draws", default=None, type=click.IntRange(min=1),
+              help="Thin each sample by an even stride to at most this many draws first (the cost is quadratic)")
 @click.option("--format", "format_", type=click.Choice(["table", "json"], case_sensitive=False), default="table")
 def validate_cmd(model: str, actual_path: Path, tolerance: float, metrics: str, ks_max, w1_scaled_max, sliced: int, sliced_seed: int,
-                 sliced_ks_max, sliced_w1_max, khat_max, hdi_prob, hdi_tol, format_: str) -> None:
+                 sliced_ks_max, sliced_w1_max, khat_max, hdi_prob, hdi_tol, energy: bool, energy_max, energy_max_draws,
+                 format_: str) -> None:
     """The reference's mean / std gate plus per-parameter KS / Wasserstein-1 and, with --sliced K, the same distances
-    along K random directions of the joint distribution (validate.validate; no counterpart in the reference)."""
+    along K random directions of the joint distribution; with --energy the energy distance of the joint draws
+    (validate.validate; no counterpart in the reference)."""
     from .validate import validate
     try:
         result = validate(model, _read_actual_csv(actual_path), tolerance=tolerance, metrics=tuple(metrics.split(",")),
                           ks_max=ks_max, w1_scaled_max=w1_scaled_max, sliced=sliced, sliced_seed=sliced_seed,
                           sliced_ks_max=sliced_ks_max, sliced_w1_max=sliced_w1_max, khat_max=khat_max,
-                          hdi_prob=hdi_prob, hdi_tol=hdi_tol)
+                          hdi_prob=hdi_prob, hdi_tol=hdi_tol, energy=energy or energy_max is not None, energy_max=energy_max,
+                          energy_max_draws=energy_max_draws)
     except ValueError as exc:
         raise click.ClickException(str(exc)) from exc
     with_hdi = hdi_prob is not None or hdi_tol is not None
@@ -372,7 +379,8 @@ def validate_cmd(model: str, actual_path: Path, tolerance: float, metrics: str, 
                                "ks": result.ks, "wasserstein": result.wasserstein,
                                "wasserstein_scaled": result.wasserstein_scaled, "sliced_ks": result.sliced_ks,
                                "sliced_w1": result.sliced_w1, "sliced": result.sliced, "khat_ref": result.khat_ref,
-                               "khat_actual": result.khat_actual}, indent=2, sort_keys=True))
+                               "khat_actual": result.khat_actual, "energy": result.energy,
+                               "energy_detail": result.energy_detail}, indent=2, sort_keys=True))
     else:
         click.echo("passed" if result.passed else "failed")
         for failure in result.failures:

@@ -39,6 +39,17 @@ class ValidateResult:
     khat_actual: dict[str, float] = field(default_factory=dict)    # ... and of `actual`
     hdi_ref: dict[str, tuple[float, float]] = field(default_factory=dict)      # (lo, hi) of the reference draws' highest-density
     hdi_actual: dict[str, tuple[float, float]] = field(default_factory=dict)   # interval and of `actual`'s: only with hdi_prob / hdi_tol
+    energy: float | None = None                  # energy distance E of the standardised joint draws (energy=True)
+    energy_detail: dict | None = None            # "a", "b", "c", "e", "h", "t" of Context.energy_distance, "mr", "ma" (draws used)
+
+
+def energy_stride(m: int, max_draws: int | None) -> int:
+    """The even stride that thins m draws to at most max_draws: x[:, ::ceil(m / max_draws)] (1 without a limit)."""
+    if max_draws is None:
+        return 1
+    if max_draws < 1:
+        raise ValueError("energy_max_draws must be >= 1")
+    return max(1, -(-int(m) // int(max_draws)))
 
 
 def sliced_directions(k: int, std, seed: int = 4711) -> tuple[np.ndarray, np.ndarray]:
@@ -68,8 +79,15 @@ def validate(model: str, actual: Mapping[str, Sequence[float]], tolerance: float
              w1_scaled_max: float | None = None, store: DataStore | None = None, context=None, sliced: int = 0,
              sliced_seed: int = 4711, sliced_ks_max: float | None = None,
              sliced_w1_max: float | None = None, khat_max: float | None = None, hdi_prob: float | None = None,
-             hdi_tol: float | None = None) -> ValidateResult:
-    """hdi_prob / hdi_tol: when either is given (hdi_prob is 0.94 then), `hdi_ref` / `hdi_actual` hold every parameter's
+             hdi_tol: float | None = None, energy: bool = False, energy_max: float | None = None,
+             energy_max_draws: int | None = None) -> ValidateResult:
+    """energy=True: one `Context.energy_distance` call on the joint draws, every parameter scaled by 1 / reference std
+    (0 where that std is not finite and > 0: the `live` rule of `sliced_directions`): the direction-free counterpart of
+    `sliced`, without a seed.  `energy` is E, `energy_detail` the six numbers and the draws used.  `energy_max` adds the
+    failure `energy=E > energy_max`; without it `passed` is what it is without `energy`.  `energy_max_draws=n` thins each
+    sample first to at most n draws by an even stride (`energy_stride`): the cost is quadratic in the draws and
+    autocorrelated draws lose little.  Needs joint draws, like `sliced`; with no live parameter the fields stay None.
+    hdi_prob / hdi_tol: when either is given (hdi_prob is 0.94 then), `hdi_ref` / `hdi_actual` hold every parameter's
     highest-density interval (Context.hdi) -- where the mass lies, which q5 / q50 / q95 alone do not say; with hdi_tol a
     parameter fails when an endpoint is off by more than hdi_tol times the reference interval's own width.  khat_max: a parameter whose `khat_actual` (Context.pareto_khat, default tail length) exceeds it is a failure;
     without it the two k-hat columns are information only.  sliced=K > 0: K directions `sliced_directions(K, reference std, sliced_seed)` around the reference means, one
@@ -90,6 +108,10 @@ def validate(model: str, actual: Mapping[str, Sequence[float]], tolerance: float
         raise ValueError("sliced must be >= 0")
     if sliced > 0 and len(lens) > 1:
         raise ValueError("sliced needs joint draws: the parameters of `actual` differ in length")
+    if energy and len(lens) > 1:
+        raise ValueError("energy needs joint draws: the parameters of `actual` differ in length")
+    if energy:
+        energy_stride(1, energy_max_draws)          # a bad limit is refused before any work
     ks: dict[str, float] = {}
     w1: dict[str, float] = {}
     if len(lens) == 1 and params:
@@ -148,5 +170,19 @@ def validate(model: str, actual: Mapping[str, Sequence[float]], tolerance: float
                 failures.append(f"sliced.ks={extra['sliced_ks']:.3g} > {sliced_ks_max}")
             if sliced_w1_max is not None and not extra["sliced_w1"] <= sliced_w1_max:
                 failures.append(f"sliced.w1={extra['sliced_w1']:.3g} > {sliced_w1_max}")
+    if energy and params:
+        std = np.array([ref_stats[p]["std"] for p in params], dtype=np.float64)
+        live = np.isfinite(std) & (std > 0)
+        if live.any():
+            scale = np.zeros(std.size)
+            scale[live] = 1.0 / std[live]
+            er = ref[:, ::energy_stride(ref.shape[1], energy_max_draws)]
+            ea = act[:, ::energy_stride(act.shape[1], energy_max_draws)]
+            with _ffi.value_errors():
+                det = ctx.energy_distance(er, ea, scale)
+            det.update(mr=int(er.shape[1]), ma=int(ea.shape[1]))
+            extra.update(energy=det["e"], energy_detail=det)
+            if energy_max is not None and not det["e"] <= energy_max:
+                failures.append(f"energy={det['e']:.3g} > {energy_max}")
     return ValidateResult(passed=not failures, compare=cmp_res, ks=ks, wasserstein=w1, wasserstein_scaled=scaled,
                           failures=failures, khat_ref=khat_ref, khat_actual=khat_act, hdi_ref=hdi_ref, hdi_actual=hdi_act, **extra)
