@@ -194,16 +194,9 @@ struct mcr_ctx {
     bool f32_records = true; // MCR_F32_RECORDS=0: f32 tensors take the f64 kernels (widened by the tile sort) instead of mcr_sort32.hpp
     bool splitters_pairwise = false;   // MCR_SPLITTERS_PAIRWISE=1: rank the regular samples pair by pair whatever their number (A/B, parity tests)
     double rho_band = kRhoBand;   // MCR_RHO_BAND: half-width of the guard band of the tier-3 scan (0 = decide on the raw values)
-    DevBuf nest_dev{4};                // mcr_nested_rhat: chain permutation + result table
-    PinBuf nest_host{4};               // its results on the host
-    DevBuf pareto_dev{4};              // mcr_pareto_khat: tail lengths + result table
-    PinBuf pareto_host{4};             // its results on the host
-    DevBuf psis_dev{4};                // mcr_psis: tail lengths + result table
-    PinBuf psis_host{4};               // its results on the host
-    DevBuf hdi_dev{4};                 // mcr_hdi: result table
-    PinBuf hdi_host{4};                // its results on the host
-    DevBuf acf_dev{4};                 // mcr_autocorr: result arrays + the chains' non-finite counts
-    PinBuf acf_host{4};                // the counts on the host
+    DevBuf call_dev{4};                // the tensor calls (nested R-hat ... autocorrelation, one at a time): the call's result
+                                       // table behind its tail lengths or chain permutation
+    PinBuf call_host{4};               // its results (mcr_autocorr: the chains' non-finite counts) on the host
     i64 energy_launch_work = kEnLaunchWork;   // MCR_ENERGY_LAUNCH_WORK: pair-parameters of one k_energy_pairs launch (tests lower it)
     DevBuf guard_count;                // device counters (2 unsigned): band lags re-derived the reference's way (mcr_rho_guard_count),
                                        // tiles the tile sort sorted as pairs after all (mcr_tile_fallback_count)
@@ -1282,123 +1275,19 @@ int moments_impl(mcr_ctx* ctx, const T* src, i64 C, i64 N, i64 P, i64 sc, i64 sn
     return MCR_OK;
 }
 
-// ---- Calls on the pooled ascending order (Pareto k-hat, HDI) ---------------------------------------------------------------
-// Both run the summary pipeline without diagnostics and quantiles -- tile sort, merges / bucket partition, k_order_stats,
-// k_finalize for the non-finite count -- and then their own kernels on the keys the sort stage left.
-constexpr int kPoolField0 = R_Q0;                          // the pipeline runs without quantiles: its rows end here
-
-PipeIn stats_only_pipe(i64 M, i64 pc)
+// The host entries of the two-sample calls: ref [P][Mr] and act [P][Ma] uploaded side by side into ctx->stage.
+int stage_two_samples(mcr_ctx* ctx, const double* ref, i64 Mr, const double* act, i64 Ma, i64 P, const double** ref_dev,
+                      const double** act_dev)
 {
-    PipeIn a{};
-    a.M = M; a.pc = pc; a.C = 1; a.n = 1; a.nh = 0; a.nstage = 1; a.q.nq = 0; a.do_diag = false;
-    return a;
-}
-
-// The workspace of a stats-only chunk of a.pc parameters: the sort alone and the split points k_order_stats writes.
-// Returns the ingest copy.
-double* carve_stats_only(Carve& cv, PipeIn& a, bool ingest)
-{
-    double* X = carve_pipe(cv, a, false, FftPlan{}, ingest);
-    a.split = cv.take<i64>((size_t)a.pc);
-    return X;
-}
-
-// Parameters per workspace chunk, at most hi: extra(cv, a) carves what the caller needs behind the pipeline's buffers.
-template <class Extra>
-int plan_pooled(mcr_ctx* ctx, i64 M, i64 hi, bool ingest, Extra&& extra, i64& pcmax)
-{
-    auto measure = [&](i64 pc) {
-        PipeIn a = stats_only_pipe(M, pc);
-        Carve m{nullptr};
-        carve_stats_only(m, a, ingest);
-        extra(m, a);
-        return m.off;
-    };
-    pcmax = most_that_fit(hi < kMaxGridY / 2 ? hi : kMaxGridY / 2, [&](i64 pc) { return measure(pc) <= ctx->ws_limit; });
-    if (!pcmax) return fail(ctx, MCR_ENOMEM, "one parameter needs %zu bytes of workspace; limit is %zu", measure(1), ctx->ws_limit);
-    return MCR_OK;
-}
-
-// Acceptance of the tensor of such a call (`what` names the entry in the message).
-int pooled_check(mcr_ctx* ctx, const char* what, const void* draws, int dtype, i64 C, i64 N, i64 P, const void* out)
-{
-    if (!out) return fail(ctx, MCR_EINVAL, "out is NULL");
-    if (dtype != MCR_F64 && dtype != MCR_F32) return fail(ctx, MCR_EINVAL, "unsupported dtype %d", dtype);
-    if (C < 0 || N < 0 || P < 0) return fail(ctx, MCR_EINVAL, "negative dimension (C=%lld N=%lld P=%lld)", (long long)C, (long long)N, (long long)P);
-    if (N > 0 && (C > (i64)0x7FFFFFFFll / N || C * N >= (i64)0x7FFFFFFFll)) return fail(ctx, MCR_EINVAL, "C*N must be < 2^31 - 1");
-    if (!draws && C * N * P > 0) return fail(ctx, MCR_EINVAL, "draws is NULL");
-    if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "%s with summaries in flight", what);
-    return MCR_OK;
-}
-
-// The host entries' upload: the tensor's extent into ctx->stage.  *dev: the device copy (the host pointer for an empty one).
-int pooled_upload(mcr_ctx* ctx, const void* draws, int dtype, i64 C, i64 N, i64 P, i64 sc, i64 sn, i64 sp, const void** dev)
-{
-    const i64 ext = tensor_extent(C, N, P, sc, sn, sp);
-    if (ext < 0) return fail(ctx, MCR_EINVAL, "negative strides are not supported");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    void* X = ctx->stage.p;
-    if (ext > 0) {
-        const size_t es = dtype == MCR_F64 ? 8 : 4;
-        const int rc = stage_buffers(ctx, {(size_t)ext * es}, &X);
-        if (rc) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(X, draws, (size_t)ext * es, hipMemcpyHostToDevice, ctx->stream));
-    }
-    *dev = X ? X : draws;
-    return MCR_OK;
-}
-
-// The chunks of such a call: per chunk of at most pcmax parameters the ingest pass where the tensor needs one (f32 draws
-// are widened by it: the answer is the f64 call's on the widened tensor), the stats-only pipeline into the chunk's rows
-// d_res + fields * p0, then after(a, so, p0): the caller's kernels on the chunk's keys.  extra: as in plan_pooled.
-template <class Extra, class After>
-int pooled_chunks(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i64 P, i64 sc, i64 sn, i64 sp,
-                         bool ingest, i64 pcmax, int fields, double* d_res, Extra&& extra, After&& after)
-{
-    const i64 M = C * N;
-    for (i64 p0 = 0; p0 < P; p0 += pcmax) {
-        const i64 pc = (P - p0 < pcmax) ? P - p0 : pcmax;
-        PipeIn a = stats_only_pipe(M, pc);
-        double* X = nullptr;
-        int rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) { X = carve_stats_only(cv, a, ingest); extra(cv, a); });
-        if (rc) return rc;
-        if (ingest) {
-            rc = launch_ingest(ctx, draws_dev, dtype, X, C, N, pc, sc, sn, sp, p0);
-            if (rc) return rc;
-            a.X = X;
-        } else {
-            a.X = reinterpret_cast<const double*>(draws_dev) + p0 * M;
-        }
-        a.d_res = d_res + (size_t)fields * (size_t)p0;
-        Sorted so;
-        rc = run_pipeline(ctx, a, &so);        // sort, order statistics, finalize (the bad count)
-        if (!rc) rc = after(a, so, p0);
-        if (rc) return rc;
-    }
-    return MCR_OK;
-}
-
-// The one D2H of the result table at the end of such a call; each(r, pc, p0, p): the rows r of the chunk at p0, parameter
-// p of its pc.  MCR_ENONFINITE when the pipeline counted a NaN or Inf draw (the outputs are written all the same).
-template <class Each>
-int pooled_results(mcr_ctx* ctx, PinBuf& host, const double* d_res, int fields, i64 P, i64 pcmax, Each&& each)
-{
-    int rc = host.reserve(ctx, sizeof(double) * (size_t)fields * (size_t)P);
+    const size_t br = sizeof(double) * (size_t)P * Mr, ba = sizeof(double) * (size_t)P * Ma;
+    void* X[2];
+    const int rc = stage_buffers(ctx, {br, ba}, X);
     if (rc) return rc;
-    double* h = host.as<double>();
-    HIP_TRY(ctx, hipMemcpyAsync(h, d_res, sizeof(double) * (size_t)fields * (size_t)P, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    prof_resolve(ctx);
-    double nbad = 0.0;
-    for (i64 p0 = 0; p0 < P; p0 += pcmax) {
-        const i64 pc = (P - p0 < pcmax) ? P - p0 : pcmax;
-        const double* r = h + (size_t)fields * (size_t)p0;
-        for (i64 p = 0; p < pc; ++p) {
-            nbad += r[(size_t)R_BAD * pc + p];
-            each(r, pc, p0, p);
-        }
-    }
-    if (nbad > 0.0) return fail(ctx, MCR_ENONFINITE, "draws contain %.0f non-finite value(s)", nbad);
+    HIP_TRY(ctx, hipMemcpyAsync(X[0], ref, br, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(X[1], act, ba, hipMemcpyHostToDevice, ctx->stream));
+    *ref_dev = (const double*)X[0];
+    *act_dev = (const double*)X[1];
     return MCR_OK;
 }
 
@@ -2011,13 +1900,9 @@ int mcr_sliced_two_sample(mcr_ctx* ctx, const double* ref, int64_t Mr, const dou
     if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
     int rc = sliced_check(ctx, ref, Mr, act, Ma, P, dirs, center, K, ks, w1);
     if (rc || K == 0) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    void* X[2];
-    rc = stage_buffers(ctx, {sizeof(double) * (size_t)P * Mr, sizeof(double) * (size_t)P * Ma}, X);
+    const double *Xr, *Xa;
+    rc = stage_two_samples(ctx, ref, Mr, act, Ma, P, &Xr, &Xa);
     if (rc) return rc;
-    double *Xr = (double*)X[0], *Xa = (double*)X[1];
-    HIP_TRY(ctx, hipMemcpyAsync(Xr, ref, sizeof(double) * (size_t)P * Mr, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(Xa, act, sizeof(double) * (size_t)P * Ma, hipMemcpyHostToDevice, ctx->stream));
     return mcr_sliced_two_sample_dev(ctx, Xr, Mr, Xa, Ma, P, dirs, center, K, ks, w1, proj_ref, proj_act);
 }
 
@@ -2119,13 +2004,10 @@ int mcr_energy_distance(mcr_ctx* ctx, const double* ref, int64_t Mr, const doubl
     if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
     int rc = energy_check(ctx, ref, Mr, act, Ma, P, scale, out);
     if (rc) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    void* X[2];
-    rc = stage_buffers(ctx, {sizeof(double) * (size_t)P * Mr, sizeof(double) * (size_t)P * Ma}, X);
+    const double *Xr, *Xa;
+    rc = stage_two_samples(ctx, ref, Mr, act, Ma, P, &Xr, &Xa);
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(X[0], ref, sizeof(double) * (size_t)P * Mr, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(X[1], act, sizeof(double) * (size_t)P * Ma, hipMemcpyHostToDevice, ctx->stream));
-    return mcr_energy_distance_dev(ctx, (const double*)X[0], Mr, (const double*)X[1], Ma, P, scale, out);
+    return mcr_energy_distance_dev(ctx, Xr, Mr, Xa, Ma, P, scale, out);
 }
 
 int mcr_energy_distance_host(const double* ref, int64_t Mr, const double* act, int64_t Ma, int64_t P, const double* scale,
@@ -2139,65 +2021,257 @@ int mcr_energy_distance_host(const double* ref, int64_t Mr, const double* act, i
     }
 }
 
-// ---- nested R-hat (mcr_nested.hpp) ------------------------------------------------------------------------------------
-constexpr i64 kMaxNestedChains = (i64)1 << 20;
-constexpr int kNestKinds = 3;                              // raw, bulk, tail
-constexpr int kNestField0 = R_Q0;                          // the pipeline runs without quantiles: its rows end here
-constexpr int kNestFields = kNestField0 + 3 * kNestKinds;  // + (nrhat, B, W) per kind
+}  // extern "C"
 
-static_assert(kMaxNestedChains == MCR_NESTED_MAX_CHAINS && kNestBlock == MCR_NESTED_BLOCK, "mcmcref_hip.h states the nested limits");
+// ---- Calls on the pooled ascending order, and the other calls on one draw tensor ------------------------------------------
+// Nested R-hat, Pareto k-hat, PSIS, HDI and autocorrelation each take one (C, N, P) tensor, run synchronously and cut its
+// parameters into chunks under the workspace limit.  What that takes is here, once: the tensor and its acceptance
+// (Tensor, pooled_check), the entry and the plan entry (tensor_entry, plan_entry), the chunk size and the chunk loop
+// (plan_params, tensor_chunks) and the context's two call buffers (call_table, pooled_results).  Pareto k-hat, PSIS and HDI
+// run the summary pipeline without diagnostics and quantiles -- tile sort, merges / bucket partition, k_order_stats,
+// k_finalize for the non-finite count -- and then their own kernels on the keys the sort stage left (pooled_chunks); the
+// two with tails share tail_check and tail_lds.  A family below supplies its own arguments' check, its chunk's layout,
+// its launches and the scatter of its results, and nothing else.
+namespace {
 
-struct NestedWs { double *X, *mom, *sup; };
+struct Tensor {
+    const void* draws; int dtype; i64 C, N, P, sc, sn, sp;
+    i64 M() const { return C * N; }
+    i64 extent() const { return tensor_extent(C, N, P, sc, sn, sp); }
+    // f32 draws are widened by the ingest pass: the answer is the f64 call's on the widened tensor
+    bool ingest() const { return dtype == MCR_F32 || needs_ingest(C, N, P, sc, sn, sp); }
+};
 
-// The workspace of a chunk of a.pc parameters: the summary pipeline's layout for ONE chain of M draws (no buffer grows
-// with chains x segments), then the chain moments and the superchain records.
-static void carve_nested(Carve& cv, PipeIn& a, NestedWs& w, i64 C, i64 K, bool ingest)
+// Acceptance of the tensor of such a call (`what` names the entry in the message).
+int pooled_check(mcr_ctx* ctx, const char* what, const Tensor& t, const void* out)
 {
-    w.X = carve_pipe(cv, a, true, FftPlan{}, ingest);
-    w.mom = cv.take<double>((size_t)a.pc * kNestKinds * (size_t)C * 2);
-    w.sup = cv.take<double>((size_t)a.pc * kNestKinds * (size_t)(K > 0 ? K : 1) * 2);
+    if (!out) return fail(ctx, MCR_EINVAL, "out is NULL");
+    if (t.dtype != MCR_F64 && t.dtype != MCR_F32) return fail(ctx, MCR_EINVAL, "unsupported dtype %d", t.dtype);
+    if (t.C < 0 || t.N < 0 || t.P < 0) return fail(ctx, MCR_EINVAL, "negative dimension (C=%lld N=%lld P=%lld)", (long long)t.C, (long long)t.N, (long long)t.P);
+    if (t.N > 0 && (t.C > (i64)0x7FFFFFFFll / t.N || t.M() >= (i64)0x7FFFFFFFll)) return fail(ctx, MCR_EINVAL, "C*N must be < 2^31 - 1");
+    if (!t.draws && t.M() * t.P > 0) return fail(ctx, MCR_EINVAL, "draws is NULL");
+    if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "%s with summaries in flight", what);
+    return MCR_OK;
 }
 
-static PipeIn nested_pipe(i64 M, i64 pc)
+// A host entry's upload: the tensor's extent (> 0) into ctx->stage; t.draws becomes the device copy.
+int pooled_upload(mcr_ctx* ctx, Tensor& t)
 {
-    PipeIn a{};
-    a.M = M; a.pc = pc; a.C = 1; a.n = 1; a.nh = 0; a.nstage = 1; a.q.nq = 0; a.do_diag = true;
-    return a;
+    const size_t bytes = (size_t)t.extent() * (t.dtype == MCR_F64 ? 8 : 4);
+    void* X = nullptr;
+    const int rc = stage_buffers(ctx, {bytes}, &X);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(X, t.draws, bytes, hipMemcpyHostToDevice, ctx->stream));
+    t.draws = X;
+    return MCR_OK;
 }
 
-// Parameters per workspace chunk of a nested call (the most whose layout fits the limit and whose grids fit a launch).
-static int plan_nested(mcr_ctx* ctx, i64 C, i64 N, i64 P, i64 K, bool ingest, i64& pcmax)
+// An entry of such a call, the host's (the draws are uploaded) or the device's.  check(): the call's own arguments,
+// once, behind the tensor's acceptance: every refusal comes before anything is uploaded or written.  empty(): the
+// results of a tensor without draws (it has no extent: nothing is uploaded, and its strides are not looked at).
+// run(t): the call on the tensor in device memory.
+template <class Check, class Empty, class Run>
+int tensor_entry(mcr_ctx* ctx, const char* what, Tensor t, const void* out, bool host, Check&& check, Empty&& empty, Run&& run)
 {
-    const i64 M = C * N;
-    auto measure = [&](i64 pc) {
-        PipeIn a = nested_pipe(M, pc);
-        NestedWs w;
-        Carve m{nullptr};
-        carve_nested(m, a, w, C, K, ingest);
-        return m.off;
-    };
-    const i64 nb = (C + kNestChains - 1) / kNestChains;
-    const i64 grid_cap = ((i64)0x7FFFFFFF / nb) / 8 * 8;   // k_chain_moments: ceil(pc / 8) * 8 * nb workgroups
-    i64 hi = P < kMaxGridY / 2 ? P : kMaxGridY / 2;
-    if (hi > grid_cap) hi = grid_cap;
-    pcmax = most_that_fit(hi, [&](i64 pc) { return measure(pc) <= ctx->ws_limit; });
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    int rc = pooled_check(ctx, what, t, out);
+    if (!rc) rc = check();
+    if (rc || t.P == 0) return rc;
+    if (t.M() == 0) { empty(); return MCR_OK; }
+    if (t.extent() < 0) return fail(ctx, MCR_EINVAL, "negative strides are not supported");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (host && (rc = pooled_upload(ctx, t))) return rc;
+    rc = run(t);
+    return rc ? drain(ctx, rc, true) : rc;
+}
+
+// Parameters per workspace chunk: the most, up to P and to cap (what the launches' grids hold), whose layout fits the
+// workspace limit.  layout(cv, pc) carves a chunk of pc parameters.
+template <class Layout>
+int plan_params(mcr_ctx* ctx, i64 P, i64 cap, Layout&& layout, i64& pcmax)
+{
+    auto measure = [&](i64 pc) { Carve m{nullptr}; layout(m, pc); return m.off; };
+    pcmax = most_that_fit(P < cap ? P : cap, [&](i64 pc) { return measure(pc) <= ctx->ws_limit; });
     if (!pcmax) return fail(ctx, MCR_ENOMEM, "one parameter needs %zu bytes of workspace; limit is %zu", measure(1), ctx->ws_limit);
     return MCR_OK;
 }
 
-// Acceptance of a nested call, and the chains ordered by superchain (stable): K runs of L chains in perm.
-static int nested_check(mcr_ctx* ctx, const void* draws, int dtype, i64 C, i64 N, i64 P, const int32_t* superchain,
-                        const mcr_nested* out, std::vector<int32_t>& perm, i64& K, i64& L)
+// An mcr_*_plan entry: 0 for a shape no call runs on (empty, or one pooled_check refuses), else what plan(pcmax) --
+// the call's own argument check where it has one, then its plan_params -- answers (0 when it leaves pcmax alone).
+template <class Plan>
+int plan_entry(mcr_ctx* ctx, const char* what, const Tensor& t, int64_t* params_per_chunk, Plan&& plan)
 {
-    if (!out) return fail(ctx, MCR_EINVAL, "out is NULL");
-    if (dtype != MCR_F64 && dtype != MCR_F32) return fail(ctx, MCR_EINVAL, "unsupported dtype %d", dtype);
-    if (C < 0 || N < 0 || P < 0) return fail(ctx, MCR_EINVAL, "negative dimension (C=%lld N=%lld P=%lld)", (long long)C, (long long)N, (long long)P);
+    if (!ctx || !params_per_chunk) return fail(ctx, MCR_EINVAL, "%s: NULL argument", what);
+    i64 pcmax = 0;
+    if (t.C >= 1 && t.N >= 1 && t.P >= 1 && t.C <= (i64)0x7FFFFFFFll / t.N && t.M() < (i64)0x7FFFFFFFll) {
+        const int rc = plan(pcmax);
+        if (rc) return rc;
+    }
+    *params_per_chunk = pcmax;
+    return MCR_OK;
+}
+
+// The chunks of a call: per chunk of at most pcmax parameters its workspace -- layout(cv, pc), as in plan_params,
+// returns the chunk's ingest copy -- the ingest pass where the tensor needs one, then body(pc, p0, X): the call's launches
+// on the chunk's f64 draws X[pc][M], the copy or the user's tensor at parameter p0.
+template <class Layout, class Body>
+int tensor_chunks(mcr_ctx* ctx, const Tensor& t, i64 pcmax, Layout&& layout, Body&& body)
+{
+    const bool ingest = t.ingest();
+    for (i64 p0 = 0; p0 < t.P; p0 += pcmax) {
+        const i64 pc = (t.P - p0 < pcmax) ? t.P - p0 : pcmax;
+        double* copy = nullptr;
+        int rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) { copy = layout(cv, pc); });
+        if (!rc && ingest) rc = launch_ingest(ctx, t.draws, t.dtype, copy, t.C, t.N, pc, t.sc, t.sn, t.sp, p0);
+        if (!rc) rc = body(pc, p0, ingest ? copy : reinterpret_cast<const double*>(t.draws) + p0 * t.M());
+        if (rc) return rc;
+    }
+    return MCR_OK;
+}
+
+// The call-level device table (the context's, shared by these calls): `head` -- a call's tail lengths, its chain
+// permutation -- uploaded, and behind it the result rows.
+template <typename T>
+int call_table(mcr_ctx* ctx, const std::vector<T>& head, size_t res_doubles, T*& d_head, double*& d_res)
+{
+    const int rc = carve(ctx, ctx->call_dev, [&](Carve& cv) { d_head = cv.take<T>(head.size()); d_res = cv.take<double>(res_doubles); });
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(d_head, head.data(), sizeof(T) * head.size(), hipMemcpyHostToDevice, ctx->stream));
+    return MCR_OK;
+}
+
+// The one D2H of the result table at the end of a call whose chunks ran the pipeline; each(r, pc, p0, p): the rows r of
+// the chunk at p0, parameter p of its pc.  MCR_ENONFINITE when the pipeline counted a NaN or Inf draw (the outputs are
+// written all the same).
+template <class Each>
+int pooled_results(mcr_ctx* ctx, const double* d_res, int fields, i64 P, i64 pcmax, Each&& each)
+{
+    const size_t bytes = sizeof(double) * (size_t)fields * (size_t)P;
+    const int rc = ctx->call_host.reserve(ctx, bytes);
+    if (rc) return rc;
+    const double* h = ctx->call_host.as<double>();
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->call_host.p, d_res, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    prof_resolve(ctx);
+    double nbad = 0.0;
+    for (i64 at = 0; at < P; ++at) {
+        const i64 p = at % pcmax, p0 = at - p, pc = (P - p0 < pcmax) ? P - p0 : pcmax;
+        const double* r = h + (size_t)fields * (size_t)p0;
+        nbad += r[(size_t)R_BAD * pc + p];
+        each(r, pc, p0, p);
+    }
+    if (nbad > 0.0) return fail(ctx, MCR_ENONFINITE, "draws contain %.0f non-finite value(s)", nbad);
+    return MCR_OK;
+}
+
+constexpr int kPoolField0 = R_Q0;                          // the pipeline runs without quantiles: its rows end here
+
+// The pipeline on pc parameters of one chain of M pooled draws, without quantiles; do_diag: with the rank codes.
+PipeIn one_chain_pipe(i64 M, i64 pc, bool do_diag)
+{
+    PipeIn a{};
+    a.M = M; a.pc = pc; a.C = 1; a.n = 1; a.nh = 0; a.nstage = 1; a.q.nq = 0; a.do_diag = do_diag;
+    return a;
+}
+
+// The layout of a stats-only chunk, into a: the sort alone and the split points k_order_stats writes, then extra(cv, a):
+// what the caller needs behind the pipeline's buffers.
+template <class Extra>
+auto pooled_layout(const Tensor& t, PipeIn& a, Extra& extra)
+{
+    return [&](Carve& cv, i64 pc) {
+        a = one_chain_pipe(t.M(), pc, false);
+        double* X = carve_pipe(cv, a, false, FftPlan{}, t.ingest());
+        a.split = cv.take<i64>((size_t)pc);
+        extra(cv, a);
+        return X;
+    };
+}
+
+// Parameters per workspace chunk of a call on the pooled order; grid_hi: what its own kernels' grids hold.
+template <class Extra>
+int plan_pooled(mcr_ctx* ctx, const Tensor& t, Extra&& extra, i64& pcmax, i64 grid_hi = kMaxGridY / 2)
+{
+    PipeIn a{};
+    return plan_params(ctx, t.P, grid_hi < kMaxGridY / 2 ? grid_hi : kMaxGridY / 2, pooled_layout(t, a, extra), pcmax);
+}
+
+// The chunks of such a call: the stats-only pipeline into the chunk's rows d_res + fields * p0, then after(a, so, p0):
+// the caller's kernels on the chunk's keys.
+template <class Extra, class After>
+int pooled_chunks(mcr_ctx* ctx, const Tensor& t, i64 pcmax, int fields, double* d_res, Extra&& extra, After&& after)
+{
+    PipeIn a{};
+    return tensor_chunks(ctx, t, pcmax, pooled_layout(t, a, extra), [&](i64, i64 p0, const double* X) {
+        a.X = X;
+        a.d_res = d_res + (size_t)fields * (size_t)p0;
+        Sorted so;
+        const int rc = run_pipeline(ctx, a, &so);          // sort, order statistics, finalize (the bad count)
+        return rc ? rc : after(a, so, p0);
+    });
+}
+
+// A caller's tail length of parameter p, where it gives any.
+int tail_check(mcr_ctx* ctx, const int64_t* ndraws_tail, i64 p)
+{
+    if (ndraws_tail && ndraws_tail[p] < 1)
+        return fail(ctx, MCR_EINVAL, "ndraws_tail[%lld] = %lld: a tail length must be >= 1", (long long)p, (long long)ndraws_tail[p]);
+    return MCR_OK;
+}
+
+// The dynamic LDS of a tail kernel on the chunk [p0, p0 + pc): `base` doubles and the chunk's longest tail that is staged
+// there.  Above 60 KB the kernel is told.
+int tail_lds(mcr_ctx* ctx, const std::vector<i64>& teff, i64 p0, i64 pc, size_t base, const void* kernel, size_t& lds)
+{
+    i64 tmax = 0;
+    for (i64 p = p0; p < p0 + pc; ++p)
+        if (teff[(size_t)p] <= kParetoLdsTail && teff[(size_t)p] > tmax) tmax = teff[(size_t)p];
+    lds = sizeof(double) * (base + (size_t)tmax);
+    if (lds > 60 * 1024) HIP_TRY(ctx, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return MCR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- nested R-hat (mcr_nested.hpp) ------------------------------------------------------------------------------------
+constexpr i64 kMaxNestedChains = (i64)1 << 20;
+constexpr int kNestKinds = 3;                              // raw, bulk, tail
+constexpr int kNestField0 = kPoolField0;
+constexpr int kNestFields = kNestField0 + 3 * kNestKinds;  // + (nrhat, B, W) per kind
+
+static_assert(kMaxNestedChains == MCR_NESTED_MAX_CHAINS && kNestBlock == MCR_NESTED_BLOCK, "mcmcref_hip.h states the nested limits");
+
+// The workspace of a chunk of pc parameters: the summary pipeline's layout for ONE chain of M draws (no buffer grows
+// with chains x segments), then the chain moments and the superchain records.  Returns the ingest copy.
+struct NestedChunk {
+    const Tensor& t; i64 K;
+    PipeIn a{}; double *mom = nullptr, *sup = nullptr;
+    double* operator()(Carve& cv, i64 pc)
+    {
+        a = one_chain_pipe(t.M(), pc, true);
+        double* X = carve_pipe(cv, a, true, FftPlan{}, t.ingest());
+        mom = cv.take<double>((size_t)pc * kNestKinds * (size_t)t.C * 2);
+        sup = cv.take<double>((size_t)pc * kNestKinds * (size_t)(K > 0 ? K : 1) * 2);
+        return X;
+    }
+};
+
+// Parameters per workspace chunk of a nested call (the most whose layout fits the limit and whose grids fit a launch).
+static int plan_nested(mcr_ctx* ctx, NestedChunk& ch, i64& pcmax)
+{
+    const i64 nb = (ch.t.C + kNestChains - 1) / kNestChains;
+    const i64 grid_cap = ((i64)0x7FFFFFFF / nb) / 8 * 8;   // k_chain_moments: ceil(pc / 8) * 8 * nb workgroups
+    return plan_params(ctx, ch.t.P, grid_cap < kMaxGridY / 2 ? grid_cap : kMaxGridY / 2, ch, pcmax);
+}
+
+// What a nested call asks beyond pooled_check, and the chains ordered by superchain (stable): K runs of L chains in perm.
+static int nested_check(mcr_ctx* ctx, i64 C, const int32_t* superchain, std::vector<int32_t>& perm, i64& K, i64& L)
+{
     if (C > kMaxNestedChains)
         return fail(ctx, MCR_EINVAL, "nested R-hat supports at most %lld chains; got %lld", (long long)kMaxNestedChains, (long long)C);
-    if (C * N >= (i64)0x7FFFFFFFll) return fail(ctx, MCR_EINVAL, "C*N must be < 2^31");
-    if (!draws && C * N * P > 0) return fail(ctx, MCR_EINVAL, "draws is NULL");
     if (C > 0 && !superchain) return fail(ctx, MCR_EINVAL, "superchain is NULL");
-    if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "mcr_nested_rhat with summaries in flight");
     // superchains in the order of their first chain, chains in index order inside: the labels are names only
     std::unordered_map<int32_t, int32_t> dense;
     std::vector<int32_t> sid((size_t)C), count, first_label;
@@ -2219,74 +2293,45 @@ static int nested_check(mcr_ctx* ctx, const void* draws, int dtype, i64 C, i64 N
     return MCR_OK;
 }
 
-static int nested_run(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i64 P, i64 sc, i64 sn, i64 sp,
-                      const std::vector<int32_t>& perm, i64 K, i64 L, const mcr_nested* out)
+static int nested_run(mcr_ctx* ctx, const Tensor& t, const std::vector<int32_t>& perm, i64 K, i64 L, const mcr_nested* out)
 {
-    const i64 M = C * N;
-    // f32 draws are widened by the ingest pass: the raw kind reads f64 rows, and the answer is the f64 call's on the widened tensor
-    const bool ingest = dtype == MCR_F32 || needs_ingest(C, N, P, sc, sn, sp);
+    const i64 M = t.M(), C = t.C, N = t.N, P = t.P;        // (the raw kind reads f64 rows: those of the ingest copy for f32 draws)
+    NestedChunk ch{t, K};
     i64 pcmax = 0;
-    int rc = plan_nested(ctx, C, N, P, K, ingest, pcmax);
+    int rc = plan_nested(ctx, ch, pcmax);
     if (rc) return rc;
     int32_t* d_perm = nullptr;
-    double* d_res = nullptr;
-    rc = carve(ctx, ctx->nest_dev, [&](Carve& cv) {
-        d_perm = cv.take<int32_t>((size_t)C);
-        d_res = cv.take<double>((size_t)kNestFields * (size_t)P);
-    });
-    if (!rc) rc = ctx->nest_host.reserve(ctx, sizeof(double) * (size_t)kNestFields * (size_t)P);
-    if (rc) return rc;
-    double* ztab = nullptr;
+    double *d_res = nullptr, *ztab = nullptr;
     rc = get_ztab(ctx, M, &ztab);
+    if (!rc) rc = call_table(ctx, perm, (size_t)kNestFields * (size_t)P, d_perm, d_res);
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(d_perm, perm.data(), sizeof(int32_t) * (size_t)C, hipMemcpyHostToDevice, ctx->stream));
-    for (i64 p0 = 0; p0 < P; p0 += pcmax) {
-        const i64 pc = (P - p0 < pcmax) ? P - p0 : pcmax;
-        PipeIn a = nested_pipe(M, pc);
-        NestedWs w;
-        rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) { carve_nested(cv, a, w, C, K, ingest); });
-        if (rc) return rc;
+    rc = tensor_chunks(ctx, t, pcmax, ch, [&](i64 pc, i64 p0, const double* X) -> int {
+        PipeIn& a = ch.a;
         a.ztab = ztab;
-        if (ingest) {
-            rc = launch_ingest(ctx, draws_dev, dtype, w.X, C, N, pc, sc, sn, sp, p0);
-            if (rc) return rc;
-            a.X = w.X;
-        } else {
-            a.X = reinterpret_cast<const double*>(draws_dev) + p0 * M;
-        }
+        a.X = X;
         a.d_res = d_res + (size_t)kNestFields * (size_t)p0;
-        rc = run_pipeline(ctx, a);             // one chain: sort, order statistics, bulk codes, fold, finalize (the bad count)
+        const int rc = run_pipeline(ctx, a);   // one chain: sort, order statistics, bulk codes, fold, finalize (the bad count)
         if (rc) return rc;
         const i64 nb = (C + kNestChains - 1) / kNestChains;
         LAUNCH(ctx, K_CHAIN_MOMENTS, k_chain_moments, dim3((unsigned)((pc + 7) / 8 * 8 * nb)), dim3(kNestNT), 0,
-               (const double*)a.X, (const u32*)a.zb, (const u32*)a.zt, (const double*)ztab, M, C, N, pc, w.mom);
+               X, (const u32*)a.zb, (const u32*)a.zt, (const double*)ztab, M, C, N, pc, ch.mom);
         LAUNCH(ctx, K_NESTED_COMBINE, k_nested_combine, dim3((unsigned)pc, kNestKinds), dim3(kNestCombNT), 0,
-               (const double*)w.mom, (const int*)d_perm, C, K, L, N, w.sup, a.d_res, pc, kNestField0);
-    }
-    double* h = ctx->nest_host.as<double>();
-    HIP_TRY(ctx, hipMemcpyAsync(h, d_res, sizeof(double) * (size_t)kNestFields * (size_t)P, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    prof_resolve(ctx);
-    double nbad = 0.0;
+               (const double*)ch.mom, (const int*)d_perm, C, K, L, N, ch.sup, a.d_res, pc, kNestField0);
+        return MCR_OK;
+    });
+    if (rc) return rc;
     double* const dst[kNestKinds][3] = {{out->nrhat_raw, out->between_raw, out->within_raw},
                                         {out->nrhat_bulk, out->between_bulk, out->within_bulk},
                                         {out->nrhat_tail, out->between_tail, out->within_tail}};
-    for (i64 p0 = 0; p0 < P; p0 += pcmax) {
-        const i64 pc = (P - p0 < pcmax) ? P - p0 : pcmax;
-        const double* r = h + (size_t)kNestFields * (size_t)p0;
-        for (i64 p = 0; p < pc; ++p) {
-            nbad += r[(size_t)R_BAD * pc + p];
-            for (int k = 0; k < kNestKinds; ++k)
-                for (int f = 0; f < 3; ++f)
-                    if (dst[k][f]) dst[k][f][p0 + p] = r[(size_t)(kNestField0 + 3 * k + f) * pc + p];
-            if (out->nrhat) {                  // Python's max(bulk, tail)
-                const double rb = r[(size_t)(kNestField0 + 3) * pc + p], rt = r[(size_t)(kNestField0 + 6) * pc + p];
-                out->nrhat[p0 + p] = (rt > rb) ? rt : rb;
-            }
+    return pooled_results(ctx, d_res, kNestFields, P, pcmax, [&](const double* r, i64 pc, i64 p0, i64 p) {
+        for (int k = 0; k < kNestKinds; ++k)
+            for (int f = 0; f < 3; ++f)
+                if (dst[k][f]) dst[k][f][p0 + p] = r[(size_t)(kNestField0 + 3 * k + f) * pc + p];
+        if (out->nrhat) {                      // Python's max(bulk, tail)
+            const double rb = r[(size_t)(kNestField0 + 3) * pc + p], rt = r[(size_t)(kNestField0 + 6) * pc + p];
+            out->nrhat[p0 + p] = (rt > rb) ? rt : rb;
         }
-    }
-    if (nbad > 0.0) return fail(ctx, MCR_ENONFINITE, "draws contain %.0f non-finite value(s)", nbad);
-    return MCR_OK;
+    });
 }
 
 static void nested_fill_nan(const mcr_nested* o, i64 P)
@@ -2300,51 +2345,33 @@ static void nested_fill_nan(const mcr_nested* o, i64 P)
 int mcr_nested_plan(mcr_ctx* ctx, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc, int64_t sn, int64_t sp,
                     int64_t K, int64_t* params_per_chunk)
 {
-    if (!ctx || !params_per_chunk) return fail(ctx, MCR_EINVAL, "mcr_nested_plan: NULL argument");
-    if (C < 1 || N < 1 || P < 1 || K < 1 || C > kMaxNestedChains || C * N >= (i64)0x7FFFFFFFll) { *params_per_chunk = 0; return MCR_OK; }
-    i64 pcmax = 0;
-    const int rc = plan_nested(ctx, C, N, P, K, dtype == MCR_F32 || needs_ingest(C, N, P, sc, sn, sp), pcmax);
-    if (rc) return rc;
-    *params_per_chunk = pcmax;
-    return MCR_OK;
+    const Tensor t{nullptr, dtype, C, N, P, sc, sn, sp};
+    return plan_entry(ctx, "mcr_nested_plan", t, params_per_chunk, [&](i64& pcmax) -> int {
+        if (K < 1 || C > kMaxNestedChains) return MCR_OK;
+        NestedChunk ch{t, K};
+        return plan_nested(ctx, ch, pcmax);
+    });
+}
+
+static int nested_entry(mcr_ctx* ctx, const Tensor& t, const int32_t* superchain, mcr_nested* out, bool host)
+{
+    std::vector<int32_t> perm;
+    i64 K = 0, L = 0;
+    return tensor_entry(ctx, "mcr_nested_rhat", t, out, host, [&] { return nested_check(ctx, t.C, superchain, perm, K, L); },
+                        [&] { nested_fill_nan(out, t.P); },
+                        [&](const Tensor& dev) { return nested_run(ctx, dev, perm, K, L, out); });
 }
 
 int mcr_nested_rhat_dev(mcr_ctx* ctx, const void* draws_dev, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc,
                         int64_t sn, int64_t sp, const int32_t* superchain, mcr_nested* out)
 {
-    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
-    std::vector<int32_t> perm;
-    i64 K = 0, L = 0;
-    int rc = nested_check(ctx, draws_dev, dtype, C, N, P, superchain, out, perm, K, L);
-    if (rc || P == 0) return rc;
-    if (C * N == 0) { nested_fill_nan(out, P); return MCR_OK; }
-    if (tensor_extent(C, N, P, sc, sn, sp) < 0) return fail(ctx, MCR_EINVAL, "negative strides are not supported");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    rc = nested_run(ctx, draws_dev, dtype, C, N, P, sc, sn, sp, perm, K, L, out);
-    return rc ? drain(ctx, rc, true) : rc;
+    return nested_entry(ctx, {draws_dev, dtype, C, N, P, sc, sn, sp}, superchain, out, false);
 }
 
 int mcr_nested_rhat(mcr_ctx* ctx, const void* draws, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc, int64_t sn,
                     int64_t sp, const int32_t* superchain, mcr_nested* out)
 {
-    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
-    {
-        std::vector<int32_t> perm;             // (the device entry checks again: the errors come before the upload)
-        i64 K = 0, L = 0;
-        const int rc = nested_check(ctx, draws, dtype, C, N, P, superchain, out, perm, K, L);
-        if (rc) return rc;
-    }
-    const i64 ext = tensor_extent(C, N, P, sc, sn, sp);
-    if (ext < 0) return fail(ctx, MCR_EINVAL, "negative strides are not supported");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    void* X = ctx->stage.p;
-    if (ext > 0) {
-        const size_t es = dtype == MCR_F64 ? 8 : 4;
-        const int rc = stage_buffers(ctx, {(size_t)ext * es}, &X);
-        if (rc) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(X, draws, (size_t)ext * es, hipMemcpyHostToDevice, ctx->stream));
-    }
-    return mcr_nested_rhat_dev(ctx, X ? X : draws, dtype, C, N, P, sc, sn, sp, superchain, out);
+    return nested_entry(ctx, {draws, dtype, C, N, P, sc, sn, sp}, superchain, out, true);
 }
 
 // ---- Pareto k-hat (mcr_pareto.hpp) --------------------------------------------------------------------------------------
@@ -2360,9 +2387,9 @@ static double* carve_pareto(Carve& cv, const PipeIn& a)
 }
 
 // Parameters per workspace chunk of a Pareto call.
-static int plan_pareto(mcr_ctx* ctx, i64 M, i64 P, bool ingest, i64& pcmax)
+static int plan_pareto(mcr_ctx* ctx, const Tensor& t, i64& pcmax)
 {
-    return plan_pooled(ctx, M, P, ingest, [](Carve& cv, PipeIn& a) { carve_pareto(cv, a); }, pcmax);
+    return plan_pooled(ctx, t, [](Carve& cv, PipeIn& a) { carve_pareto(cv, a); }, pcmax);
 }
 
 // The default tail length: the smallest t with t^2 r_eff >= 9 M (that is ceil(3 sqrt(M / r_eff))) for M > 225, else
@@ -2381,56 +2408,40 @@ static i64 pareto_tail_bisect(i64 M, double r_eff)
 }
 static i64 pareto_default_tail(i64 M, double r_eff) { return M <= 225 ? M / 5 : pareto_tail_bisect(M, r_eff); }
 
-// Acceptance of a Pareto call, and the effective tail length of every parameter.
-static int pareto_check(mcr_ctx* ctx, const void* draws, int dtype, i64 C, i64 N, i64 P, const int64_t* ndraws_tail,
-                        const mcr_pareto* out, std::vector<i64>& teff)
+// The tail lengths a Pareto call is given, and the effective tail length of every parameter.
+static int pareto_check(mcr_ctx* ctx, i64 M, i64 P, const int64_t* ndraws_tail, std::vector<i64>& teff)
 {
-    const int rc = pooled_check(ctx, "mcr_pareto_khat", draws, dtype, C, N, P, out);
-    if (rc) return rc;
-    const i64 M = C * N;
     teff.resize((size_t)P);
     for (i64 p = 0; p < P; ++p) {
-        if (ndraws_tail && ndraws_tail[p] < 1)
-            return fail(ctx, MCR_EINVAL, "ndraws_tail[%lld] = %lld: a tail length must be >= 1", (long long)p, (long long)ndraws_tail[p]);
+        const int rc = tail_check(ctx, ndraws_tail, p);
+        if (rc) return rc;
         teff[(size_t)p] = pareto_tail_eff(M, ndraws_tail ? ndraws_tail[p] : pareto_default_tail(M, 1.0));
     }
     return MCR_OK;
 }
 
-static int pareto_run(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i64 P, i64 sc, i64 sn, i64 sp,
-                      const std::vector<i64>& teff, const mcr_pareto* out)
+static int pareto_run(mcr_ctx* ctx, const Tensor& t, const std::vector<i64>& teff, const mcr_pareto* out)
 {
-    const i64 M = C * N;
-    const bool ingest = dtype == MCR_F32 || needs_ingest(C, N, P, sc, sn, sp);
+    const i64 M = t.M(), P = t.P;
     i64 pcmax = 0;
-    int rc = plan_pareto(ctx, M, P, ingest, pcmax);
-    if (rc) return rc;
+    int rc = plan_pareto(ctx, t, pcmax);
     i64* d_tail = nullptr;
     double* d_res = nullptr;
-    rc = carve(ctx, ctx->pareto_dev, [&](Carve& cv) {
-        d_tail = cv.take<i64>((size_t)P);
-        d_res = cv.take<double>((size_t)kParFields * (size_t)P);
-    });
+    if (!rc) rc = call_table(ctx, teff, (size_t)kParFields * (size_t)P, d_tail, d_res);
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(d_tail, teff.data(), sizeof(i64) * (size_t)P, hipMemcpyHostToDevice, ctx->stream));
     const i64 gmax = pareto_grid(M / 2);
     double* lg = nullptr;
-    rc = pooled_chunks(ctx, draws_dev, dtype, C, N, P, sc, sn, sp, ingest, pcmax, kParFields, d_res,
-                       [&](Carve& cv, PipeIn& a) { lg = carve_pareto(cv, a); },
+    rc = pooled_chunks(ctx, t, pcmax, kParFields, d_res, [&](Carve& cv, PipeIn& a) { lg = carve_pareto(cv, a); },
                        [&](const PipeIn& a, const Sorted& so, i64 p0) -> int {
-        i64 tmax = 0;                          // the chunk's LDS: its longest tail that is staged there
-        for (i64 p = p0; p < p0 + a.pc; ++p)
-            if (teff[(size_t)p] <= kParetoLdsTail && teff[(size_t)p] > tmax) tmax = teff[(size_t)p];
-        const size_t lds = sizeof(double) * (size_t)tmax;
-        if (lds > 60 * 1024)
-            HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pareto_fit),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        size_t lds = 0;
+        const int rc = tail_lds(ctx, teff, p0, a.pc, 0, reinterpret_cast<const void*>(&k_pareto_fit), lds);
+        if (rc) return rc;
         LAUNCH(ctx, K_PARETO_FIT, k_pareto_fit, dim3((unsigned)((a.pc + 7) / 8 * 8 * 2)), dim3(kParetoNT), lds,
                (const double*)so.keys, M, a.pc, (const i64*)(d_tail + p0), so.keys_free, lg, gmax, a.d_res, kParField0);
         return MCR_OK;
     });
     if (rc) return rc;
-    return pooled_results(ctx, ctx->pareto_host, d_res, kParFields, P, pcmax, [&](const double* r, i64 pc, i64 p0, i64 p) {
+    return pooled_results(ctx, d_res, kParFields, P, pcmax, [&](const double* r, i64 pc, i64 p0, i64 p) {
         const double kl = r[(size_t)kParField0 * pc + p], kr = r[(size_t)(kParField0 + 1) * pc + p];
         if (out->khat_left) out->khat_left[p0 + p] = kl;
         if (out->khat_right) out->khat_right[p0 + p] = kr;
@@ -2449,39 +2460,27 @@ static void pareto_fill_nan(const mcr_pareto* o, i64 P)
 int mcr_pareto_plan(mcr_ctx* ctx, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc, int64_t sn, int64_t sp,
                     int64_t* params_per_chunk)
 {
-    if (!ctx || !params_per_chunk) return fail(ctx, MCR_EINVAL, "mcr_pareto_plan: NULL argument");
-    if (C < 1 || N < 1 || P < 1 || C > (i64)0x7FFFFFFFll / N || C * N >= (i64)0x7FFFFFFFll) { *params_per_chunk = 0; return MCR_OK; }
-    i64 pcmax = 0;
-    const int rc = plan_pareto(ctx, C * N, P, dtype == MCR_F32 || needs_ingest(C, N, P, sc, sn, sp), pcmax);
-    if (rc) return rc;
-    *params_per_chunk = pcmax;
-    return MCR_OK;
+    const Tensor t{nullptr, dtype, C, N, P, sc, sn, sp};
+    return plan_entry(ctx, "mcr_pareto_plan", t, params_per_chunk, [&](i64& pcmax) { return plan_pareto(ctx, t, pcmax); });
+}
+
+static int pareto_entry(mcr_ctx* ctx, const Tensor& t, const int64_t* ndraws_tail, mcr_pareto* out, bool host)
+{
+    std::vector<i64> teff;
+    return tensor_entry(ctx, "mcr_pareto_khat", t, out, host, [&] { return pareto_check(ctx, t.M(), t.P, ndraws_tail, teff); },
+                        [&] { pareto_fill_nan(out, t.P); }, [&](const Tensor& dev) { return pareto_run(ctx, dev, teff, out); });
 }
 
 int mcr_pareto_khat_dev(mcr_ctx* ctx, const void* draws_dev, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc,
                         int64_t sn, int64_t sp, const int64_t* ndraws_tail, mcr_pareto* out)
 {
-    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
-    std::vector<i64> teff;
-    int rc = pareto_check(ctx, draws_dev, dtype, C, N, P, ndraws_tail, out, teff);
-    if (rc || P == 0) return rc;
-    if (C * N == 0) { pareto_fill_nan(out, P); return MCR_OK; }
-    if (tensor_extent(C, N, P, sc, sn, sp) < 0) return fail(ctx, MCR_EINVAL, "negative strides are not supported");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    rc = pareto_run(ctx, draws_dev, dtype, C, N, P, sc, sn, sp, teff, out);
-    return rc ? drain(ctx, rc, true) : rc;
+    return pareto_entry(ctx, {draws_dev, dtype, C, N, P, sc, sn, sp}, ndraws_tail, out, false);
 }
 
 int mcr_pareto_khat(mcr_ctx* ctx, const void* draws, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc, int64_t sn,
                     int64_t sp, const int64_t* ndraws_tail, mcr_pareto* out)
 {
-    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
-    std::vector<i64> teff;                     // (the device entry checks again: the errors come before the upload)
-    int rc = pareto_check(ctx, draws, dtype, C, N, P, ndraws_tail, out, teff);
-    const void* X = nullptr;
-    if (!rc) rc = pooled_upload(ctx, draws, dtype, C, N, P, sc, sn, sp, &X);
-    if (rc) return rc;
-    return mcr_pareto_khat_dev(ctx, X, dtype, C, N, P, sc, sn, sp, ndraws_tail, out);
+    return pareto_entry(ctx, {draws, dtype, C, N, P, sc, sn, sp}, ndraws_tail, out, true);
 }
 
 int64_t mcr_pareto_tail_length(int64_t M, double r_eff)
@@ -2529,11 +2528,10 @@ static void carve_psis(Carve& cv, const PipeIn& a, bool host_weights, PsisWs& w)
 }
 
 // Columns per workspace chunk of a PSIS call: what fits, and no more than k_psis_weights' one-dimensional grid holds.
-static int plan_psis(mcr_ctx* ctx, i64 M, i64 P, bool ingest, bool host_weights, i64& pcmax)
+static int plan_psis(mcr_ctx* ctx, const Tensor& t, bool host_weights, i64& pcmax)
 {
-    const i64 grid_hi = ((i64)0x7FFFFFFFll / ((M + kPsisBlock - 1) / kPsisBlock)) / 8 * 8;     // >= 1016: M < 2^31
-    return plan_pooled(ctx, M, P < grid_hi ? P : grid_hi, ingest,
-                       [&](Carve& cv, PipeIn& a) { PsisWs w; carve_psis(cv, a, host_weights, w); }, pcmax);
+    const i64 grid_hi = ((i64)0x7FFFFFFFll / ((t.M() + kPsisBlock - 1) / kPsisBlock)) / 8 * 8;     // >= 1016: M < 2^31
+    return plan_pooled(ctx, t, [&](Carve& cv, PipeIn& a) { PsisWs w; carve_psis(cv, a, host_weights, w); }, pcmax, grid_hi);
 }
 
 static bool psis_r_eff_ok(double r) { return r > 0.0 && !std::isinf(r); }
@@ -2552,18 +2550,14 @@ static i64 psis_tail_eff(i64 M, i64 t_req, double r_eff)
     return t_req < M - 1 ? t_req : M - 1;
 }
 
-// Acceptance of a PSIS call, and the effective tail length of every column.
-static int psis_check(mcr_ctx* ctx, const void* draws, int dtype, i64 C, i64 N, i64 P, int negate, const double* r_eff,
-                      const int64_t* ndraws_tail, const mcr_psis_out* out, std::vector<i64>& teff)
+// The arguments of a PSIS call, and the effective tail length of every column.
+static int psis_check(mcr_ctx* ctx, i64 M, i64 P, int negate, const double* r_eff, const int64_t* ndraws_tail, std::vector<i64>& teff)
 {
-    const int rc = pooled_check(ctx, "mcr_psis", draws, dtype, C, N, P, out);
-    if (rc) return rc;
     if (negate != 0 && negate != 1) return fail(ctx, MCR_EINVAL, "negate must be 0 or 1; got %d", negate);
-    const i64 M = C * N;
     teff.resize((size_t)P);
     for (i64 p = 0; p < P; ++p) {
-        if (ndraws_tail && ndraws_tail[p] < 1)
-            return fail(ctx, MCR_EINVAL, "ndraws_tail[%lld] = %lld: a tail length must be >= 1", (long long)p, (long long)ndraws_tail[p]);
+        const int rc = tail_check(ctx, ndraws_tail, p);
+        if (rc) return rc;
         if (r_eff && !psis_r_eff_ok(r_eff[p]))
             return fail(ctx, MCR_EINVAL, "r_eff[%lld] = %g: a relative efficiency must be finite and > 0", (long long)p, r_eff[p]);
         teff[(size_t)p] = M < 1 ? 0 : psis_tail_eff(M, ndraws_tail ? ndraws_tail[p] : 0, r_eff ? r_eff[p] : 1.0);
@@ -2571,36 +2565,24 @@ static int psis_check(mcr_ctx* ctx, const void* draws, int dtype, i64 C, i64 N, 
     return MCR_OK;
 }
 
-static int psis_run(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i64 P, i64 sc, i64 sn, i64 sp, int negate,
-                    const std::vector<i64>& teff, const mcr_psis_out* out, bool host_weights)
+static int psis_run(mcr_ctx* ctx, const Tensor& t, int negate, const std::vector<i64>& teff, const mcr_psis_out* out, bool host_weights)
 {
-    const i64 M = C * N;
-    const bool ingest = dtype == MCR_F32 || needs_ingest(C, N, P, sc, sn, sp);
+    const i64 M = t.M(), P = t.P;
     const bool hw = host_weights && out->log_weights;
     i64 pcmax = 0;
-    int rc = plan_psis(ctx, M, P, ingest, hw, pcmax);
-    if (rc) return rc;
+    int rc = plan_psis(ctx, t, hw, pcmax);
     i64* d_tail = nullptr;
     double* d_res = nullptr;
-    rc = carve(ctx, ctx->psis_dev, [&](Carve& cv) {
-        d_tail = cv.take<i64>((size_t)P);
-        d_res = cv.take<double>((size_t)kPsisFields * (size_t)P);
-    });
+    if (!rc) rc = call_table(ctx, teff, (size_t)kPsisFields * (size_t)P, d_tail, d_res);
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(d_tail, teff.data(), sizeof(i64) * (size_t)P, hipMemcpyHostToDevice, ctx->stream));
     const i64 gmax = psis_gmax(M);
     const unsigned nb = (unsigned)((M + kPsisBlock - 1) / kPsisBlock);
     PsisWs w{};
-    rc = pooled_chunks(ctx, draws_dev, dtype, C, N, P, sc, sn, sp, ingest, pcmax, kPsisFields, d_res,
-                       [&](Carve& cv, PipeIn& a) { carve_psis(cv, a, hw, w); },
+    rc = pooled_chunks(ctx, t, pcmax, kPsisFields, d_res, [&](Carve& cv, PipeIn& a) { carve_psis(cv, a, hw, w); },
                        [&](const PipeIn& a, const Sorted& so, i64 p0) -> int {
-        i64 tmax = 0;                          // the chunk's LDS: its longest tail that is staged there
-        for (i64 p = p0; p < p0 + a.pc; ++p)
-            if (teff[(size_t)p] <= kParetoLdsTail && teff[(size_t)p] > tmax) tmax = teff[(size_t)p];
-        const size_t lds = sizeof(double) * (size_t)(kPsisScratch + tmax);
-        if (lds > 60 * 1024)
-            HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_psis_column),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        size_t lds = 0;
+        const int rc = tail_lds(ctx, teff, p0, a.pc, kPsisScratch, reinterpret_cast<const void*>(&k_psis_column), lds);
+        if (rc) return rc;
         const unsigned pgrp = (unsigned)((a.pc + 7) / 8 * 8);
         LAUNCH(ctx, K_PSIS_COLUMN, k_psis_column, dim3(pgrp), dim3(kPsisNT), lds, (const double*)so.keys, M, a.pc, negate,
                (const i64*)(d_tail + p0), so.keys_free, w.lg, gmax, a.d_res, kPsisField0, w.cols);
@@ -2618,7 +2600,7 @@ static int psis_run(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N
         return MCR_OK;
     });
     if (rc) return rc;
-    return pooled_results(ctx, ctx->psis_host, d_res, kPsisFields, P, pcmax, [&](const double* r, i64 pc, i64 p0, i64 p) {
+    return pooled_results(ctx, d_res, kPsisFields, P, pcmax, [&](const double* r, i64 pc, i64 p0, i64 p) {
         const double* f = r + (size_t)kPsisField0 * pc + p;
         if (out->khat) out->khat[p0 + p] = f[PR_KHAT * pc];
         if (out->ndraws_tail) out->ndraws_tail[p0 + p] = (i64)f[PR_NTAIL * pc];
@@ -2635,48 +2617,33 @@ static void psis_fill_nan(const mcr_psis_out* o, i64 P)
     if (o->ndraws_tail) for (i64 p = 0; p < P; ++p) o->ndraws_tail[p] = 0;
 }
 
-static int psis_entry(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i64 P, i64 sc, i64 sn, i64 sp, int negate,
-                      const double* r_eff, const int64_t* ndraws_tail, mcr_psis_out* out, bool host_weights)
+// host: the host entry, whose log weights (like its draws) are the caller's host memory.
+static int psis_entry(mcr_ctx* ctx, const Tensor& t, int negate, const double* r_eff, const int64_t* ndraws_tail, mcr_psis_out* out,
+                      bool host)
 {
     std::vector<i64> teff;
-    int rc = psis_check(ctx, draws_dev, dtype, C, N, P, negate, r_eff, ndraws_tail, out, teff);
-    if (rc || P == 0) return rc;
-    if (C * N == 0) { psis_fill_nan(out, P); return MCR_OK; }
-    if (tensor_extent(C, N, P, sc, sn, sp) < 0) return fail(ctx, MCR_EINVAL, "negative strides are not supported");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    rc = psis_run(ctx, draws_dev, dtype, C, N, P, sc, sn, sp, negate, teff, out, host_weights);
-    return rc ? drain(ctx, rc, true) : rc;
+    return tensor_entry(ctx, "mcr_psis", t, out, host, [&] { return psis_check(ctx, t.M(), t.P, negate, r_eff, ndraws_tail, teff); },
+                        [&] { psis_fill_nan(out, t.P); },
+                        [&](const Tensor& dev) { return psis_run(ctx, dev, negate, teff, out, host); });
 }
 
 int mcr_psis_plan(mcr_ctx* ctx, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc, int64_t sn, int64_t sp,
                   int host_weights, int64_t* params_per_chunk)
 {
-    if (!ctx || !params_per_chunk) return fail(ctx, MCR_EINVAL, "mcr_psis_plan: NULL argument");
-    if (C < 1 || N < 1 || P < 1 || C > (i64)0x7FFFFFFFll / N || C * N >= (i64)0x7FFFFFFFll) { *params_per_chunk = 0; return MCR_OK; }
-    i64 pcmax = 0;
-    const int rc = plan_psis(ctx, C * N, P, dtype == MCR_F32 || needs_ingest(C, N, P, sc, sn, sp), host_weights != 0, pcmax);
-    if (rc) return rc;
-    *params_per_chunk = pcmax;
-    return MCR_OK;
+    const Tensor t{nullptr, dtype, C, N, P, sc, sn, sp};
+    return plan_entry(ctx, "mcr_psis_plan", t, params_per_chunk, [&](i64& pcmax) { return plan_psis(ctx, t, host_weights != 0, pcmax); });
 }
 
 int mcr_psis_dev(mcr_ctx* ctx, const void* draws_dev, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc, int64_t sn,
                  int64_t sp, int negate, const double* r_eff, const int64_t* ndraws_tail, mcr_psis_out* out)
 {
-    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
-    return psis_entry(ctx, draws_dev, dtype, C, N, P, sc, sn, sp, negate, r_eff, ndraws_tail, out, false);
+    return psis_entry(ctx, {draws_dev, dtype, C, N, P, sc, sn, sp}, negate, r_eff, ndraws_tail, out, false);
 }
 
 int mcr_psis(mcr_ctx* ctx, const void* draws, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc, int64_t sn, int64_t sp,
              int negate, const double* r_eff, const int64_t* ndraws_tail, mcr_psis_out* out)
 {
-    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
-    std::vector<i64> teff;                     // (the entry checks again: the errors come before the upload)
-    int rc = psis_check(ctx, draws, dtype, C, N, P, negate, r_eff, ndraws_tail, out, teff);
-    const void* X = nullptr;
-    if (!rc) rc = pooled_upload(ctx, draws, dtype, C, N, P, sc, sn, sp, &X);
-    if (rc) return rc;
-    return psis_entry(ctx, X, dtype, C, N, P, sc, sn, sp, negate, r_eff, ndraws_tail, out, true);
+    return psis_entry(ctx, {draws, dtype, C, N, P, sc, sn, sp}, negate, r_eff, ndraws_tail, out, true);
 }
 
 int64_t mcr_psis_tail_length(int64_t M, double r_eff)
@@ -2731,14 +2698,14 @@ static HdiCand* carve_hdi(Carve& cv, const PipeIn& a, int nprob)
 }
 
 // Parameters per workspace chunk of an HDI call: what fits, and no more than k_hdi_window's one-dimensional grid holds.
-static int plan_hdi(mcr_ctx* ctx, i64 M, i64 P, int nprob, bool ingest, i64& pcmax)
+static int plan_hdi(mcr_ctx* ctx, const Tensor& t, int nprob, i64& pcmax)
 {
-    const i64 grid_hi = ((i64)0x7FFFFFFFll / ((i64)nprob * hdi_slices(M))) / 8 * 8;      // >= 4096: M < 2^31, nprob <= 16
-    return plan_pooled(ctx, M, P < grid_hi ? P : grid_hi, ingest, [&](Carve& cv, PipeIn& a) { carve_hdi(cv, a, nprob); }, pcmax);
+    const i64 grid_hi = ((i64)0x7FFFFFFFll / ((i64)nprob * hdi_slices(t.M()))) / 8 * 8;  // >= 4096: M < 2^31, nprob <= 16
+    return plan_pooled(ctx, t, [&](Carve& cv, PipeIn& a) { carve_hdi(cv, a, nprob); }, pcmax, grid_hi);
 }
 
-// inc = floor(prob * M) of every probability: one rounded product.
-static int hdi_offsets(mcr_ctx* ctx, const double* probs, int nprob, i64 M, HdiArgs& h)
+// The probabilities of a call, and inc = floor(prob * M) of every one: one rounded product.
+static int hdi_check(mcr_ctx* ctx, const double* probs, int nprob, i64 M, HdiArgs& h)
 {
     if (nprob < 1 || nprob > kHdiMaxProbs) return fail(ctx, MCR_EINVAL, "nprob must be in [1, %d]; got %d", kHdiMaxProbs, nprob);
     if (!probs) return fail(ctx, MCR_EINVAL, "probs is NULL");
@@ -2750,13 +2717,6 @@ static int hdi_offsets(mcr_ctx* ctx, const double* probs, int nprob, i64 M, HdiA
     return MCR_OK;
 }
 
-static int hdi_check(mcr_ctx* ctx, const void* draws, int dtype, i64 C, i64 N, i64 P, const double* probs, int nprob,
-                     const mcr_hdi_out* out, HdiArgs& h)
-{
-    const int rc = pooled_check(ctx, "mcr_hdi", draws, dtype, C, N, P, out);
-    return rc ? rc : hdi_offsets(ctx, probs, nprob, C * N, h);
-}
-
 static void hdi_store(const mcr_hdi_out* o, i64 at, double lo, double hi, i64 index)
 {
     if (o->lo) o->lo[at] = lo;
@@ -2764,21 +2724,17 @@ static void hdi_store(const mcr_hdi_out* o, i64 at, double lo, double hi, i64 in
     if (o->index) o->index[at] = index;
 }
 
-static int hdi_run(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i64 P, i64 sc, i64 sn, i64 sp,
-                   const HdiArgs& h, const mcr_hdi_out* out)
+static int hdi_run(mcr_ctx* ctx, const Tensor& t, const HdiArgs& h, const mcr_hdi_out* out)
 {
-    const i64 M = C * N;
+    const i64 M = t.M(), P = t.P;
     const int nprob = h.nprob, fields = hdi_fields(nprob), nsl = (int)hdi_slices(M);
-    const bool ingest = dtype == MCR_F32 || needs_ingest(C, N, P, sc, sn, sp);
     i64 pcmax = 0;
-    int rc = plan_hdi(ctx, M, P, nprob, ingest, pcmax);
-    if (rc) return rc;
+    int rc = plan_hdi(ctx, t, nprob, pcmax);
     double* d_res = nullptr;
-    rc = carve(ctx, ctx->hdi_dev, [&](Carve& cv) { d_res = cv.take<double>((size_t)fields * (size_t)P); });
+    if (!rc) rc = carve(ctx, ctx->call_dev, [&](Carve& cv) { d_res = cv.take<double>((size_t)fields * (size_t)P); });
     if (rc) return rc;
     HdiCand* part = nullptr;
-    rc = pooled_chunks(ctx, draws_dev, dtype, C, N, P, sc, sn, sp, ingest, pcmax, fields, d_res,
-                       [&](Carve& cv, PipeIn& a) { part = carve_hdi(cv, a, nprob); },
+    rc = pooled_chunks(ctx, t, pcmax, fields, d_res, [&](Carve& cv, PipeIn& a) { part = carve_hdi(cv, a, nprob); },
                        [&](const PipeIn& a, const Sorted& so, i64) -> int {
         LAUNCH(ctx, K_HDI_WINDOW, k_hdi_window, dim3((unsigned)((a.pc + 7) / 8 * 8 * nprob * nsl)), dim3(kHdiNT), 0,
                (const double*)so.keys, M, a.pc, h, nsl, part);
@@ -2787,7 +2743,7 @@ static int hdi_run(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N,
         return MCR_OK;
     });
     if (rc) return rc;
-    return pooled_results(ctx, ctx->hdi_host, d_res, fields, P, pcmax, [&](const double* r, i64 pc, i64 p0, i64 p) {
+    return pooled_results(ctx, d_res, fields, P, pcmax, [&](const double* r, i64 pc, i64 p0, i64 p) {
         for (int j = 0; j < nprob; ++j) {
             const double* f = r + (size_t)(kHdiField0 + 3 * j) * pc + p;
             hdi_store(out, (p0 + p) * nprob + j, f[0], f[pc], (i64)f[2 * pc]);
@@ -2798,43 +2754,31 @@ static int hdi_run(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N,
 int mcr_hdi_plan(mcr_ctx* ctx, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc, int64_t sn, int64_t sp, int nprob,
                  int64_t* params_per_chunk)
 {
-    if (!ctx || !params_per_chunk) return fail(ctx, MCR_EINVAL, "mcr_hdi_plan: NULL argument");
-    if (nprob < 1 || nprob > kHdiMaxProbs) return fail(ctx, MCR_EINVAL, "nprob must be in [1, %d]; got %d", kHdiMaxProbs, nprob);
-    if (C < 1 || N < 1 || P < 1 || C > (i64)0x7FFFFFFFll / N || C * N >= (i64)0x7FFFFFFFll) { *params_per_chunk = 0; return MCR_OK; }
-    i64 pcmax = 0;
-    const int rc = plan_hdi(ctx, C * N, P, nprob, dtype == MCR_F32 || needs_ingest(C, N, P, sc, sn, sp), pcmax);
-    if (rc) return rc;
-    *params_per_chunk = pcmax;
-    return MCR_OK;
+    const Tensor t{nullptr, dtype, C, N, P, sc, sn, sp};
+    return plan_entry(ctx, "mcr_hdi_plan", t, params_per_chunk, [&](i64& pcmax) {
+        if (nprob < 1 || nprob > kHdiMaxProbs) return fail(ctx, MCR_EINVAL, "nprob must be in [1, %d]; got %d", kHdiMaxProbs, nprob);
+        return plan_hdi(ctx, t, nprob, pcmax);
+    });
+}
+
+static int hdi_entry(mcr_ctx* ctx, const Tensor& t, const double* probs, int nprob, mcr_hdi_out* out, bool host)
+{
+    HdiArgs h{};
+    return tensor_entry(ctx, "mcr_hdi", t, out, host, [&] { return hdi_check(ctx, probs, nprob, t.M(), h); },
+                        [&] { for (i64 at = 0; at < t.P * nprob; ++at) hdi_store(out, at, NAN, NAN, -1); },
+                        [&](const Tensor& dev) { return hdi_run(ctx, dev, h, out); });
 }
 
 int mcr_hdi_dev(mcr_ctx* ctx, const void* draws_dev, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc, int64_t sn,
                 int64_t sp, const double* probs, int nprob, mcr_hdi_out* out)
 {
-    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
-    HdiArgs h{};
-    int rc = hdi_check(ctx, draws_dev, dtype, C, N, P, probs, nprob, out, h);
-    if (rc || P == 0) return rc;
-    if (C * N == 0) {
-        for (i64 at = 0; at < P * nprob; ++at) hdi_store(out, at, NAN, NAN, -1);
-        return MCR_OK;
-    }
-    if (tensor_extent(C, N, P, sc, sn, sp) < 0) return fail(ctx, MCR_EINVAL, "negative strides are not supported");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    rc = hdi_run(ctx, draws_dev, dtype, C, N, P, sc, sn, sp, h, out);
-    return rc ? drain(ctx, rc, true) : rc;
+    return hdi_entry(ctx, {draws_dev, dtype, C, N, P, sc, sn, sp}, probs, nprob, out, false);
 }
 
 int mcr_hdi(mcr_ctx* ctx, const void* draws, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc, int64_t sn, int64_t sp,
             const double* probs, int nprob, mcr_hdi_out* out)
 {
-    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
-    HdiArgs h{};                               // (the device entry checks again: the errors come before the upload)
-    int rc = hdi_check(ctx, draws, dtype, C, N, P, probs, nprob, out, h);
-    const void* X = nullptr;
-    if (!rc) rc = pooled_upload(ctx, draws, dtype, C, N, P, sc, sn, sp, &X);
-    if (rc) return rc;
-    return mcr_hdi_dev(ctx, X, dtype, C, N, P, sc, sn, sp, probs, nprob, out);
+    return hdi_entry(ctx, {draws, dtype, C, N, P, sc, sn, sp}, probs, nprob, out, true);
 }
 
 int mcr_hdi_sorted_host(const double* sorted, int64_t M, const double* probs, int nprob, double* lo, double* hi, int64_t* index)
@@ -2857,31 +2801,26 @@ int mcr_hdi_sorted_host(const double* sorted, int64_t M, const double* probs, in
 // ---- Autocorrelation functions and times (mcr_acf.hpp) ---------------------------------------------------------------------
 static_assert(kAcfMaxLag == MCR_ACF_MAX_LAG && kAcfBlock == MCR_ACF_BLOCK, "mcmcref_hip.h states the lag limit and the block");
 
-struct AcfWs { double *X, *mean, *part, *gam; };
-
-// The workspace of a chunk of pc parameters: the ingest copy, the chains' means, the blocks' lag products, the chains' gamma.
-static void carve_acf(Carve& cv, AcfWs& w, i64 pc, i64 C, i64 N, const AcfGeom& g, bool ingest)
-{
-    const size_t chains = (size_t)pc * (size_t)C;
-    w.X = ingest ? cv.take<double>(chains * (size_t)N) : nullptr;
-    w.mean = cv.take<double>(chains);
-    w.part = cv.take<double>(chains * (size_t)g.nblk * (size_t)g.lp);
-    w.gam = cv.take<double>(chains * (size_t)g.lp);
-}
+// The workspace of a chunk of pc parameters: the ingest copy (returned), the chains' means, the blocks' lag products, the
+// chains' gamma.
+struct AcfChunk {
+    const Tensor& t; AcfGeom g;
+    double *mean = nullptr, *part = nullptr, *gam = nullptr;
+    double* operator()(Carve& cv, i64 pc)
+    {
+        const size_t chains = (size_t)pc * (size_t)t.C;
+        double* X = t.ingest() ? cv.take<double>(chains * (size_t)t.N) : nullptr;
+        mean = cv.take<double>(chains);
+        part = cv.take<double>(chains * (size_t)g.nblk * (size_t)g.lp);
+        gam = cv.take<double>(chains * (size_t)g.lp);
+        return X;
+    }
+};
 
 // Parameters per workspace chunk of an autocorrelation call: what fits, and no more than k_acf_products' grid holds.
-static int plan_acf(mcr_ctx* ctx, i64 C, i64 N, i64 P, const AcfGeom& g, bool ingest, i64& pcmax)
+static int plan_acf(mcr_ctx* ctx, AcfChunk& ch, i64& pcmax)
 {
-    auto measure = [&](i64 pc) {
-        AcfWs w;
-        Carve m{nullptr};
-        carve_acf(m, w, pc, C, N, g, ingest);
-        return m.off;
-    };
-    const i64 grid_hi = ((i64)0x7FFFFFFFll / (g.nbg * g.nlb)) / 8 * 8;
-    pcmax = most_that_fit(P < grid_hi ? P : grid_hi, [&](i64 pc) { return measure(pc) <= ctx->ws_limit; });
-    if (!pcmax) return fail(ctx, MCR_ENOMEM, "one parameter needs %zu bytes of workspace; limit is %zu", measure(1), ctx->ws_limit);
-    return MCR_OK;
+    return plan_params(ctx, ch.t.P, ((i64)0x7FFFFFFFll / (ch.g.nbg * ch.g.nlb)) / 8 * 8, ch, pcmax);
 }
 
 // The lag, flag and window arguments of a call on chains of N draws (`ctx` NULL: the host routine's, no message kept).
@@ -2893,12 +2832,6 @@ static int acf_check_args(mcr_ctx* ctx, i64 N, i64 L, int flags, double wc)
     if (flags & ~MCR_ACF_UNBIASED) return fail(ctx, MCR_EINVAL, "unknown flag bits 0x%x", (unsigned)(flags & ~MCR_ACF_UNBIASED));
     if (!std::isfinite(wc) || !(wc > 0.0)) return fail(ctx, MCR_EINVAL, "window_c = %g: the window constant must be finite and > 0", wc);
     return MCR_OK;
-}
-
-static int acf_check(mcr_ctx* ctx, const void* draws, int dtype, i64 C, i64 N, i64 P, i64 L, int flags, double wc, const mcr_acf_out* out)
-{
-    const int rc = pooled_check(ctx, "mcr_autocorr", draws, dtype, C, N, P, out);     // the tensor: as Pareto k-hat's and HDI's
-    return rc ? rc : acf_check_args(ctx, N, L, flags, wc);
 }
 
 // An empty chain (or none): NaN and -1 everywhere.
@@ -2914,49 +2847,41 @@ static void acf_fill_nan(const mcr_acf_out* o, i64 C, i64 P, i64 L)
     if (o->window_pooled) for (i64 p = 0; p < P; ++p) o->window_pooled[p] = -1;
 }
 
-static int acf_run(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N, i64 P, i64 sc, i64 sn, i64 sp, i64 L,
-                   int flags, double wc, const mcr_acf_out* out)
+static int acf_run(mcr_ctx* ctx, const Tensor& t, i64 L, int flags, double wc, const mcr_acf_out* out)
 {
-    const AcfGeom g = acf_geom(N, L);
-    const bool ingest = dtype == MCR_F32 || needs_ingest(C, N, P, sc, sn, sp);
+    const i64 C = t.C, N = t.N, P = t.P;
+    AcfChunk ch{t, acf_geom(N, L)};
+    const AcfGeom& g = ch.g;
     i64 pcmax = 0;
-    int rc = plan_acf(ctx, C, N, P, g, ingest, pcmax);
+    int rc = plan_acf(ctx, ch, pcmax);
     if (rc) return rc;
     const size_t pcn = (size_t)P * (size_t)C, nl = (size_t)(L + 1);
     double *d_acf = nullptr, *d_var, *d_tau, *d_bad, *d_acfp, *d_taup;
     i64 *d_win, *d_winp;
-    rc = carve(ctx, ctx->acf_dev, [&](Carve& cv) {
+    rc = carve(ctx, ctx->call_dev, [&](Carve& cv) {
         d_acf = out->acf ? cv.take<double>(pcn * nl) : nullptr;
         d_var = cv.take<double>(pcn); d_tau = cv.take<double>(pcn); d_win = cv.take<i64>(pcn); d_bad = cv.take<double>(pcn);
         d_acfp = cv.take<double>((size_t)P * nl); d_taup = cv.take<double>((size_t)P); d_winp = cv.take<i64>((size_t)P);
     });
-    if (!rc) rc = ctx->acf_host.reserve(ctx, sizeof(double) * pcn);
+    if (!rc) rc = ctx->call_host.reserve(ctx, sizeof(double) * pcn);
     if (rc) return rc;
     // the chains of a launch lie along y and z (any C), four per workgroup in k_acf_mean
     auto chain_grid = [](i64 n, unsigned gx) { const i64 gy = n < kMaxGridY ? n : kMaxGridY; return dim3(gx, (unsigned)gy, (unsigned)((n + gy - 1) / gy)); };
     const size_t lds = sizeof(double) * acf_lds_doubles(g), lds_fin = sizeof(double) * nl;
-    for (i64 p0 = 0; p0 < P; p0 += pcmax) {
-        const i64 pc = (P - p0 < pcmax) ? P - p0 : pcmax;
-        AcfWs w;
-        rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) { carve_acf(cv, w, pc, C, N, g, ingest); });
-        if (rc) return rc;
-        const double* X = reinterpret_cast<const double*>(draws_dev) + p0 * C * N;
-        if (ingest) {
-            rc = launch_ingest(ctx, draws_dev, dtype, w.X, C, N, pc, sc, sn, sp, p0);
-            if (rc) return rc;
-            X = w.X;
-        }
+    rc = tensor_chunks(ctx, t, pcmax, ch, [&](i64 pc, i64 p0, const double* X) -> int {
         const unsigned gx = (unsigned)((pc + 7) / 8 * 8);
         const size_t at = (size_t)p0 * (size_t)C;
-        LAUNCH(ctx, K_ACF_MEAN, k_acf_mean, chain_grid((C + 3) / 4, gx), dim3(256), 0, X, C, N, pc, w.mean, d_bad + at);
+        LAUNCH(ctx, K_ACF_MEAN, k_acf_mean, chain_grid((C + 3) / 4, gx), dim3(256), 0, X, C, N, pc, ch.mean, d_bad + at);
         LAUNCH(ctx, K_ACF_PRODUCTS, k_acf_products, chain_grid(C, (unsigned)(gx * g.nbg * g.nlb)), dim3((unsigned)acf_threads(g)), lds,
-               X, (const double*)w.mean, C, N, pc, g, w.part);
-        LAUNCH(ctx, K_ACF_FINISH, k_acf_finish, chain_grid(C, gx), dim3(kAcfFinNT), lds_fin, (const double*)w.part, C, N, pc, L, g,
-               flags & MCR_ACF_UNBIASED, wc, w.gam, d_acf ? d_acf + at * nl : nullptr, d_var + at, d_tau + at, d_win + at);
-        LAUNCH(ctx, K_ACF_POOL, k_acf_pool, dim3(gx), dim3(kAcfFinNT), lds_fin, (const double*)w.gam, C, pc, L, g.lp, wc,
+               X, (const double*)ch.mean, C, N, pc, g, ch.part);
+        LAUNCH(ctx, K_ACF_FINISH, k_acf_finish, chain_grid(C, gx), dim3(kAcfFinNT), lds_fin, (const double*)ch.part, C, N, pc, L, g,
+               flags & MCR_ACF_UNBIASED, wc, ch.gam, d_acf ? d_acf + at * nl : nullptr, d_var + at, d_tau + at, d_win + at);
+        LAUNCH(ctx, K_ACF_POOL, k_acf_pool, dim3(gx), dim3(kAcfFinNT), lds_fin, (const double*)ch.gam, C, pc, L, g.lp, wc,
                d_acfp + (size_t)p0 * nl, d_taup + p0, d_winp + p0);
-    }
-    double* h_bad = ctx->acf_host.as<double>();
+        return MCR_OK;
+    });
+    if (rc) return rc;
+    double* h_bad = ctx->call_host.as<double>();
     auto fetch = [&](void* dst, const void* src, size_t bytes) {
         return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
     };
@@ -2979,39 +2904,31 @@ static int acf_run(mcr_ctx* ctx, const void* draws_dev, int dtype, i64 C, i64 N,
 int mcr_autocorr_plan(mcr_ctx* ctx, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc, int64_t sn, int64_t sp,
                       int64_t max_lag, int64_t* params_per_chunk)
 {
-    if (!ctx || !params_per_chunk) return fail(ctx, MCR_EINVAL, "mcr_autocorr_plan: NULL argument");
-    if (C < 1 || N < 1 || P < 1 || C > (i64)0x7FFFFFFFll / N || C * N >= (i64)0x7FFFFFFFll) { *params_per_chunk = 0; return MCR_OK; }
-    const int rc0 = acf_check_args(ctx, N, max_lag, 0, 1.0);
-    if (rc0) return rc0;
-    i64 pcmax = 0;
-    const int rc = plan_acf(ctx, C, N, P, acf_geom(N, max_lag), dtype == MCR_F32 || needs_ingest(C, N, P, sc, sn, sp), pcmax);
-    if (rc) return rc;
-    *params_per_chunk = pcmax;
-    return MCR_OK;
+    const Tensor t{nullptr, dtype, C, N, P, sc, sn, sp};
+    return plan_entry(ctx, "mcr_autocorr_plan", t, params_per_chunk, [&](i64& pcmax) {
+        const int rc = acf_check_args(ctx, N, max_lag, 0, 1.0);
+        if (rc) return rc;
+        AcfChunk ch{t, acf_geom(N, max_lag)};
+        return plan_acf(ctx, ch, pcmax);
+    });
+}
+
+static int acf_entry(mcr_ctx* ctx, const Tensor& t, i64 L, int flags, double wc, mcr_acf_out* out, bool host)
+{
+    return tensor_entry(ctx, "mcr_autocorr", t, out, host, [&] { return acf_check_args(ctx, t.N, L, flags, wc); },
+                        [&] { acf_fill_nan(out, t.C, t.P, L); }, [&](const Tensor& dev) { return acf_run(ctx, dev, L, flags, wc, out); });
 }
 
 int mcr_autocorr_dev(mcr_ctx* ctx, const void* draws_dev, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc, int64_t sn,
                      int64_t sp, int64_t max_lag, int flags, double window_c, mcr_acf_out* out)
 {
-    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
-    int rc = acf_check(ctx, draws_dev, dtype, C, N, P, max_lag, flags, window_c, out);
-    if (rc || P == 0) return rc;
-    if (C * N == 0) { acf_fill_nan(out, C, P, max_lag); return MCR_OK; }
-    if (tensor_extent(C, N, P, sc, sn, sp) < 0) return fail(ctx, MCR_EINVAL, "negative strides are not supported");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    rc = acf_run(ctx, draws_dev, dtype, C, N, P, sc, sn, sp, max_lag, flags, window_c, out);
-    return rc ? drain(ctx, rc, true) : rc;
+    return acf_entry(ctx, {draws_dev, dtype, C, N, P, sc, sn, sp}, max_lag, flags, window_c, out, false);
 }
 
 int mcr_autocorr(mcr_ctx* ctx, const void* draws, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc, int64_t sn, int64_t sp,
                  int64_t max_lag, int flags, double window_c, mcr_acf_out* out)
 {
-    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
-    int rc = acf_check(ctx, draws, dtype, C, N, P, max_lag, flags, window_c, out);   // (the device entry checks again: the errors come before the upload)
-    const void* X = nullptr;
-    if (!rc) rc = pooled_upload(ctx, draws, dtype, C, N, P, sc, sn, sp, &X);
-    if (rc) return rc;
-    return mcr_autocorr_dev(ctx, X, dtype, C, N, P, sc, sn, sp, max_lag, flags, window_c, out);
+    return acf_entry(ctx, {draws, dtype, C, N, P, sc, sn, sp}, max_lag, flags, window_c, out, true);
 }
 
 int mcr_autocorr_host(const double* chains, int64_t C, int64_t N, int64_t max_lag, int flags, double window_c, mcr_acf_out* out)

@@ -1428,13 +1428,7 @@ class Context:
         (any labels, every one equally often), or an int K for K contiguous blocks of C / K chains.  Arrays per
         parameter: nrhat = max(nrhat_bulk, nrhat_tail), nrhat_raw (the paper's, on the draws), between_* / within_* (B and
         W of each kind).  Chains are not split."""
-        if isinstance(draws, DeviceTensor):
-            if draws.chain_off is not None:
-                raise ValueError("nested R-hat needs chains of equal length; a ragged tensor is not supported")
-            targs, ptr, fn = draws.targs, draws.buf.ptr, self.lib.mcr_nested_rhat_dev
-        else:
-            targs, fn = tensor_args(draws, layout), self.lib.mcr_nested_rhat
-            ptr = draws.ctypes.data_as(C.c_void_p)
+        targs, ptr, fn, _ = self._tensor_call(draws, layout, "nested_rhat", False)
         ids = superchain_labels(superchain_ids, targs[1])
         P = targs[3]
         arrs = {n: np.full(max(P, 1), np.nan) for n in NESTED_FIELDS}
@@ -1444,19 +1438,28 @@ class Context:
 
     def nested_params_per_chunk(self, t: "DeviceTensor", K: int) -> int:
         """Parameters per workspace chunk of a nested_rhat call on this tensor with K superchains (mcr_nested_plan)."""
-        v = C.c_int64(0)
-        self._check(self.lib.mcr_nested_plan(self.handle, *t.targs, int(K), C.byref(v)))
-        return int(v.value)
+        return self._params_per_chunk("mcr_nested_plan", t.targs, int(K))
 
-    def _pareto_tensor(self, draws, layout: str):
-        """(targs, pointer, entry) of a pareto_khat call; a ragged tensor is one chain of its pooled draws."""
-        if isinstance(draws, DeviceTensor):
-            targs = draws.targs
-            if draws.chain_off is not None:
-                M = int(draws.chain_off[-1])
-                targs = (targs[0], 1, M, targs[3], M, 1, targs[6])
-            return targs, draws.buf.ptr, self.lib.mcr_pareto_khat_dev
-        return tensor_args(draws, layout), draws.ctypes.data_as(C.c_void_p), self.lib.mcr_pareto_khat
+    _EQUAL_CHAINS = {"nested_rhat": "nested R-hat", "autocorr": "autocorrelation"}
+
+    def _tensor_call(self, draws, layout: str, name: str, pooled: bool):
+        """(targs, pointer, entry, on_device) of a call mcr_<name> on a host array or, on_device, mcr_<name>_dev on a
+        DeviceTensor.  A ragged tensor is, pooled, one chain of its pooled draws; otherwise it is refused."""
+        if not isinstance(draws, DeviceTensor):
+            return tensor_args(draws, layout), draws.ctypes.data_as(C.c_void_p), getattr(self.lib, "mcr_" + name), False
+        targs = draws.targs
+        if draws.chain_off is not None:
+            if not pooled:
+                raise ValueError(f"{self._EQUAL_CHAINS[name]} needs chains of equal length; a ragged tensor is not supported")
+            M = int(draws.chain_off[-1])
+            targs = (targs[0], 1, M, targs[3], M, 1, targs[6])
+        return targs, draws.buf.ptr, getattr(self.lib, f"mcr_{name}_dev"), True
+
+    def _params_per_chunk(self, plan_symbol: str, targs, *extra) -> int:
+        """What an mcr_*_plan entry answers for a tensor and the call's own arguments."""
+        v = C.c_int64(0)
+        self._check(getattr(self.lib, plan_symbol)(self.handle, *targs, *extra, C.byref(v)))
+        return int(v.value)
 
     def pareto_khat(self, draws, layout: str = "pcn", r_eff=None, ndraws_tail=None) -> dict:
         """Pareto k-hat of every parameter's tails (mcr_pareto_khat: posterior::pareto_khat(tail = "both")) of a host
@@ -1466,7 +1469,7 @@ class Context:
         ndraws_tail (the effective length), min_ss; and the float khat_threshold (pareto_companions)."""
         if r_eff is not None and ndraws_tail is not None:
             raise ValueError("give r_eff or ndraws_tail, not both")
-        targs, ptr, fn = self._pareto_tensor(draws, layout)
+        targs, ptr, fn, _ = self._tensor_call(draws, layout, "pareto_khat", True)
         M, P = targs[1] * targs[2], targs[3]
         tails = None
         if r_eff is not None:
@@ -1485,15 +1488,12 @@ class Context:
 
     def pareto_params_per_chunk(self, t: "DeviceTensor") -> int:
         """Parameters per workspace chunk of a pareto_khat call on this tensor (mcr_pareto_plan)."""
-        v = C.c_int64(0)
-        self._check(self.lib.mcr_pareto_plan(self.handle, *self._pareto_tensor(t, "pcn")[0], C.byref(v)))
-        return int(v.value)
+        return self._params_per_chunk("mcr_pareto_plan", self._tensor_call(t, "pcn", "pareto_khat", True)[0])
 
     def _psis_call(self, draws, layout: str, negate: bool, r_eff, ndraws_tail, weights: bool) -> dict:
         """Every output of mcr_psis (a host array) or mcr_psis_dev (a DeviceTensor: the weights are written to device
         memory and fetched here); psis and loo each return their part."""
-        targs, ptr, fn = self._pareto_tensor(draws, layout)            # the same pooling of a ragged tensor
-        dev = fn is self.lib.mcr_pareto_khat_dev
+        targs, ptr, fn, dev = self._tensor_call(draws, layout, "psis", True)
         M, P = targs[1] * targs[2], targs[3]
         r = None if r_eff is None else np.ascontiguousarray(np.broadcast_to(np.asarray(r_eff, dtype=np.float64), (P,)))
         tails = None if ndraws_tail is None else np.ascontiguousarray(np.broadcast_to(np.asarray(ndraws_tail), (P,)), dtype=np.int64)
@@ -1507,8 +1507,7 @@ class Context:
         wptr = buf.ptr if buf is not None else lw.ctypes.data_as(C.c_void_p) if lw is not None else None
         out = Psis(ndraws_tail=_as_ip(nt), log_weights=wptr, **{n: _as_dp(a) for n, a in arrs.items()})
         try:
-            self._check((self.lib.mcr_psis_dev if dev else self.lib.mcr_psis)(
-                self.handle, ptr, *targs, int(bool(negate)), _as_dp(r), _as_ip(tails), C.byref(out)))
+            self._check(fn(self.handle, ptr, *targs, int(bool(negate)), _as_dp(r), _as_ip(tails), C.byref(out)))
             if buf is not None:
                 lw = buf.download(np.float64, max(P * M, 1))
         finally:
@@ -1550,13 +1549,7 @@ class Context:
     def psis_params_per_chunk(self, t: "DeviceTensor", host_weights: bool = False) -> int:
         """Columns per workspace chunk of a psis / loo call on this tensor (mcr_psis_plan); host_weights: of the host
         entry with weights, whose chunk holds them too."""
-        v = C.c_int64(0)
-        self._check(self.lib.mcr_psis_plan(self.handle, *self._pareto_tensor(t, "pcn")[0], int(host_weights), C.byref(v)))
-        return int(v.value)
-
-    def _hdi_tensor(self, draws, layout: str):
-        targs, ptr, fn = self._pareto_tensor(draws, layout)            # the same pooling of a ragged tensor
-        return targs, ptr, self.lib.mcr_hdi_dev if fn is self.lib.mcr_pareto_khat_dev else self.lib.mcr_hdi
+        return self._params_per_chunk("mcr_psis_plan", self._tensor_call(t, "pcn", "psis", True)[0], int(host_weights))
 
     def hdi(self, draws, layout: str = "pcn", prob=0.94) -> dict:
         """Highest-density interval(s) of every parameter (mcr_hdi: ArviZ's unimodal hdi, the shortest interval holding
@@ -1564,7 +1557,7 @@ class Context:
         tensor is accepted.  prob: a float, or a sequence of up to MCR_HDI_MAX_PROBS.  "lo", "hi" (float64) and "index"
         (int64, the rank of lo in the ascending order; -1 with NaN endpoints when there is no window) are [P] arrays for
         a float and [P][nprob] for a sequence; "prob" is what was asked for."""
-        targs, ptr, fn = self._hdi_tensor(draws, layout)
+        targs, ptr, fn, _ = self._tensor_call(draws, layout, "hdi", True)
         P = targs[3]
         pr = np.ascontiguousarray(np.atleast_1d(prob), dtype=np.float64)
         if pr.ndim != 1:
@@ -1581,16 +1574,7 @@ class Context:
 
     def hdi_params_per_chunk(self, t: "DeviceTensor", nprob: int = 1) -> int:
         """Parameters per workspace chunk of an hdi call with nprob probabilities on this tensor (mcr_hdi_plan)."""
-        v = C.c_int64(0)
-        self._check(self.lib.mcr_hdi_plan(self.handle, *self._hdi_tensor(t, "pcn")[0], int(nprob), C.byref(v)))
-        return int(v.value)
-
-    def _acf_tensor(self, draws, layout: str):
-        if isinstance(draws, DeviceTensor):
-            if draws.chain_off is not None:
-                raise ValueError("autocorrelation needs chains of equal length; a ragged tensor is not supported")
-            return draws.targs, draws.buf.ptr, self.lib.mcr_autocorr_dev
-        return tensor_args(draws, layout), draws.ctypes.data_as(C.c_void_p), self.lib.mcr_autocorr
+        return self._params_per_chunk("mcr_hdi_plan", self._tensor_call(t, "pcn", "hdi", True)[0], int(nprob))
 
     def autocorr(self, draws, layout: str = "cnp", max_lag=None, unbiased: bool = False, window_c: float = 5.0) -> dict:
         """Autocorrelation functions and integrated autocorrelation times of the raw draws (mcr_autocorr: ArviZ's autocorr,
@@ -1599,7 +1583,7 @@ class Context:
         Arrays: "acf" [P][C][L+1], "var" (gamma_0), "tau", "window" (int64, -1: the ACF has not decayed within max_lag and tau
         is a lower bound) and "ess_chain" = N / tau, all [P][C]; the within-chain pooled "acf_pooled" [P][L+1],
         "tau_pooled", "window_pooled", "ess_pooled" = C N / tau_pooled, all [P]; and the int "max_lag"."""
-        targs, ptr, fn = self._acf_tensor(draws, layout)
+        targs, ptr, fn, _ = self._tensor_call(draws, layout, "autocorr", False)
         nc, N, P = targs[1], targs[2], targs[3]
         L = min(100, max(N - 1, 0)) if max_lag is None else int(max_lag)
         arrs, out = _acf_arrays(P, nc, L if 0 <= L <= MCR_ACF_MAX_LAG else 0)  # (a bad max_lag is refused before anything is written)
@@ -1608,9 +1592,7 @@ class Context:
 
     def autocorr_params_per_chunk(self, t: "DeviceTensor", max_lag: int) -> int:
         """Parameters per workspace chunk of an autocorr call with this max_lag on this tensor (mcr_autocorr_plan)."""
-        v = C.c_int64(0)
-        self._check(self.lib.mcr_autocorr_plan(self.handle, *self._acf_tensor(t, "pcn")[0], int(max_lag), C.byref(v)))
-        return int(v.value)
+        return self._params_per_chunk("mcr_autocorr_plan", self._tensor_call(t, "pcn", "autocorr", False)[0], int(max_lag))
 
     def covariance(self, draws) -> np.ndarray:
         """Population covariance (ddof=0) of draws [P][M] -> [P][P] (fp64 MFMA)."""
