@@ -522,6 +522,80 @@ int mcr_hdi_sorted_host(const double* sorted, int64_t M, const double* probs, in
                         int64_t* index);
 #define MCR_HDI_MAX_PROBS 16          /* probabilities of a mcr_hdi call */
 #define MCR_HDI_SLICE 16384           /* windows k_hdi_window gives one workgroup */
+/* Importance-weighted summaries: the mean, sd, standard error of the mean and quantiles of every parameter under ONE
+ * weight per pooled draw, shared by all parameters (posterior::weight_draws + summarise_draws, loo::E_loo,
+ * numpy.quantile(weights=)).  ABSENT from the reference.  It is what the log weights of mcr_psis are for: draws from an
+ * approximation, reweighted towards the target.
+ * Weights.  v[m], m = c * N + n, M = C * N entries.  Without MCR_W_LOG: w_m = v_m, every v_m finite and >= 0.  With it:
+ * w_m = exp(v_m - max v), every v_m finite or -inf (-inf: the weight 0); NaN and +inf are refused.  A vector without a
+ * positive weight is refused, and so is one whose S1 or S2 overflows.
+ * Totals, once per call:   S1 = sum w     S2 = sum w^2     ess = S1^2 / S2   (Kish's effective sample size)
+ * Per parameter, over its draws x_m in TIME order, in two passes:
+ *     mean    = (sum w_m x_m) / S1
+ *     d_m     = x_m - mean,  a_m = w_m d_m
+ *     sd      = sqrt((sum a_m d_m) / S1)                 the population form, like mcr_summarize's std
+ *     mean_se = sqrt(sum a_m a_m) / S1                   the standard error of a self-normalised importance-sampling mean
+ * Per parameter and probability q, over the ascending order x_(0) <= ... <= x_(M-1) with u_j the weight of the draw
+ * that stands at j:
+ *     cum_j = the prefix sum of u up to and including j,    t = q * cum_(M-1)   (one rounded product)
+ *     j*    = the first j with cum_j >= t and cum_j > 0,    quantile = x_(j*)
+ * that is numpy.quantile(x, q, weights=w, method="inverted_cdf"), the only numpy method that takes weights; the clause
+ * cum_j > 0 makes q = 0 skip leading zero weights.  Among tied draws every index gives the same value, and the value is
+ * what is returned.  This is NOT the linear-interpolation quantile of mcr_summarize: with equal weights it is numpy's
+ * unweighted inverted_cdf and differs from q5 / q50 / q95 by at most one spacing of the order statistics.
+ * ONE association for every sum here -- S1, S2, the three moment sums, cum.  The indices are cut into blocks of
+ * MCR_WEIGHTED_BLOCK consecutive ones.  A block's terms (+0 past the end) are the leaves of the balanced binary tree over
+ * adjacent indices: node(0, i) = term i, node(L, i) = node(L-1, 2 i) + node(L-1, 2 i + 1); the block's sum is the root.
+ * The blocks are added in ascending order from +0.  The in-block prefix of c leaves is the root of the same tree with
+ * the leaves from c on replaced by +0 -- the tree's aligned nodes named by the binary digits of c, added from the
+ * smallest to the largest; the root itself for a whole block, so that a block's sum is its last in-block prefix -- and
+ * cum_j = (the sum of the blocks in front) + (the in-block prefix).  Every sum is monotone in its operands, so cum never
+ * falls and stays where the weights are zero: the first block whose running sum satisfies the two conditions, then the
+ * first j in that block, is the first j of all.  Every product is rounded before it is added.  A parameter's outputs therefore have the same bits alone
+ * or at any place in a batch, under any workspace limit, for either position width of the sort, from the host or the
+ * device entry, in either layout or a strided view, and for f32 draws against the widened f64 (the ingest pass widens
+ * first).  mcr_weighted_host reproduces them bit for bit for linear weights; log weights go through the device's exp,
+ * which need not be libm's, so out->weights returns the w_m the call formed, and a second call with those as linear
+ * weights gives the same bits.
+ * draws: host tensor addressed like mcr_summarize's.  weights: M entries, a HOST pointer in mcr_weighted_summary and a
+ * pointer into THIS ctx's device memory in mcr_weighted_summary_dev; out->weights likewise.  probs: nq probabilities in
+ * [0, 1], 0 <= nq <= MCR_WEIGHTED_MAX_Q; nq = 0 computes no quantile (the sort still runs: it counts the non-finite draws).
+ * Every other array of out stays on the host, NULL skipped.
+ * Limits: any C, C * N < 2^31 - 1.  MCR_EINVAL (message names the cause, the same on both entries): a negative dimension,
+ * unknown flag bits, nq out of range, a probability outside [0, 1] or NaN, a weight vector refused as above (checked on
+ * the device before any output is written: one small copy of the totals), summaries in flight, negative strides.
+ * MCR_ENONFINITE: NaN / Inf draws.  M == 0 gives NaN, ess included, without a launch; P == 0 writes nothing.  The context
+ * stays usable after every error.  Synchronous.
+ * Kernels (mcr_weighted.hpp): k_weight_prepare once per call, k_weighted_moments and k_weighted_combine twice per chunk,
+ * k_wq_blocks and k_wq_pick where nq > 0.  OUT OF SCOPE: weighted KS / W1 / HDI / k-hat, resampling, a weight vector
+ * per parameter, ragged mcr_summarize_chains input. */
+#define MCR_WEIGHTED_BLOCK 1024       /* consecutive indices of one summation tree (part of the summation order) */
+#define MCR_WEIGHTED_MAX_Q 16         /* probabilities of a call */
+#define MCR_W_LOG 1                   /* flags: the weight vector holds log weights */
+typedef struct mcr_weighted_out {
+    double *mean, *sd, *mean_se;      /* P entries each, NULL skipped */
+    double *quantiles;                /* [P][nq] */
+    double *ess, *weight_sum;         /* one entry each: S1^2 / S2 and S1 */
+    double *weights;                  /* [M], the w_m as formed; NULL: not returned */
+} mcr_weighted_out;
+int mcr_weighted_summary(mcr_ctx* ctx, const void* draws, int dtype, int64_t C, int64_t N, int64_t P, int64_t stride_c,
+                         int64_t stride_n, int64_t stride_p, const double* weights, int flags, const double* probs, int nq,
+                         mcr_weighted_out* out);
+/* The same on draws in this ctx's device memory; weights_dev and out->weights are device pointers too. */
+int mcr_weighted_summary_dev(mcr_ctx* ctx, const void* draws_dev, int dtype, int64_t C, int64_t N, int64_t P,
+                             int64_t stride_c, int64_t stride_n, int64_t stride_p, const double* weights_dev, int flags,
+                             const double* probs, int nq, mcr_weighted_out* out);
+/* Parameters per workspace chunk of such a call with nq probabilities under the current workspace limit (0 for an empty
+ * shape).  MCR_ENOMEM when the limit does not fit one parameter. */
+int mcr_weighted_plan(mcr_ctx* ctx, int dtype, int64_t C, int64_t N, int64_t P, int64_t stride_c, int64_t stride_n,
+                      int64_t stride_p, int nq, int64_t* params_per_chunk);
+/* One parameter on the host (host only, no ctx, no device): M draws x in time order and their M weights; std::sort on
+ * (value, position), then the association above.  quantiles takes nq entries, weights M; NULL outputs are skipped.
+ * MCR_EINVAL: M < 0 or >= 2^31 - 1, a NULL array, flags, nq or a probability as above, a refused weight vector.
+ * MCR_ENONFINITE: NaN / Inf draws.  M == 0 gives NaN. */
+int mcr_weighted_host(const double* x, const double* weights_in, int64_t M, int flags, const double* probs, int nq,
+                      double* mean, double* sd, double* mean_se, double* quantiles, double* ess, double* weight_sum,
+                      double* weights);
 /* Autocorrelation functions and autocorrelation times: the autocorrelation of the RAW draws of every (parameter, chain)
  * up to a maximum lag, the within-chain pooled autocorrelation per parameter, and the integrated autocorrelation time
  * with Sokal's automatic window (posterior::autocorrelation, ArviZ's autocorr / plot_autocorr, emcee's integrated_time).

@@ -36,6 +36,7 @@
 #include "mcr_pareto.hpp"
 #include "mcr_psis.hpp"
 #include "mcr_hdi.hpp"
+#include "mcr_weighted.hpp"
 #include "mcr_parquet.hpp"
 #include "mcr_pqwrite.hpp"
 #include "mcr_csvwrite.hpp"
@@ -68,6 +69,7 @@ enum KernelId {
     K_LAYOUT_SCAN, K_LAYOUT_KEYS, K_LAYOUT_HIST, K_LAYOUT_OFFSETS, K_LAYOUT_SCATTER, K_LAYOUT_BOUNDS,
     K_PQW_ENCODE, K_PQW_COMPACT, K_CSVW_FORMAT, K_CSVW_SCAN, K_CSVW_COMPACT, K_SELECT_ROWS, K_PROJECT,
     K_CHAIN_MOMENTS, K_NESTED_COMBINE, K_PARETO_FIT, K_PSIS_COLUMN, K_PSIS_WEIGHTS, K_HDI_WINDOW, K_HDI_PICK,
+    K_WEIGHT_PREPARE, K_WEIGHTED_MOMENTS, K_WEIGHTED_COMBINE, K_WQ_BLOCKS, K_WQ_PICK,
     K_ACF_MEAN, K_ACF_PRODUCTS, K_ACF_FINISH, K_ACF_POOL, K_ENERGY_PAIRS, K_ENERGY_REDUCE, K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {
@@ -80,6 +82,7 @@ const char* const kKernelNames[K_COUNT] = {
     "k_layout_scan", "k_layout_keys", "k_layout_hist", "k_layout_offsets", "k_layout_scatter", "k_layout_bounds",
     "k_pqw_encode", "k_pqw_compact", "k_csvw_format", "k_csvw_scan", "k_csvw_compact", "k_select_rows", "k_project",
     "k_chain_moments", "k_nested_combine", "k_pareto_fit", "k_psis_column", "k_psis_weights", "k_hdi_window", "k_hdi_pick",
+    "k_weight_prepare", "k_weighted_moments", "k_weighted_combine", "k_wq_blocks", "k_wq_pick",
     "k_acf_mean", "k_acf_products", "k_acf_finish", "k_acf_pool", "k_energy_pairs", "k_energy_reduce"};
 
 struct EvPair { hipEvent_t a, b; int kid; };
@@ -2795,6 +2798,225 @@ int mcr_hdi_sorted_host(const double* sorted, int64_t M, const double* probs, in
         if (hi) hi[j] = ok ? sorted[best.i + inc] : NAN;
         if (index) index[j] = ok ? best.i : -1;
     }
+    return MCR_OK;
+}
+
+// ---- Importance-weighted summaries (mcr_weighted.hpp) -------------------------------------------------------------------
+constexpr int kWgtField0 = kPoolField0;
+constexpr int wgt_fields(int nq) { return kWgtField0 + WR_Q0 + nq; }       // + mean, sd, mean_se and every quantile
+
+static_assert(kWgtBlock == MCR_WEIGHTED_BLOCK && kWgtMaxQ == MCR_WEIGHTED_MAX_Q, "mcmcref_hip.h states the block and the cap");
+
+struct WgtWs { double *part, *mean, *qb; };
+
+// Behind the pipeline's buffers: the moment passes' block sums (two per block in the second pass), the means between the
+// passes and, with quantiles, the sorted order's block sums.
+static void carve_weighted(Carve& cv, const PipeIn& a, int nq, WgtWs& w)
+{
+    const size_t nb = (size_t)wgt_blocks(a.M);
+    w.part = cv.take<double>((size_t)a.pc * nb * 2);
+    w.mean = cv.take<double>((size_t)a.pc);
+    w.qb = nq > 0 ? cv.take<double>((size_t)a.pc * nb) : nullptr;
+}
+
+// Parameters per workspace chunk of a weighted call: what fits, and no more than the one-dimensional grids hold.
+static int plan_weighted(mcr_ctx* ctx, const Tensor& t, int nq, i64& pcmax)
+{
+    const i64 grid_hi = ((i64)0x7FFFFFFFll / wgt_blocks(t.M())) / 8 * 8;          // >= 1016: M < 2^31
+    return plan_pooled(ctx, t, [&](Carve& cv, PipeIn& a) { WgtWs w; carve_weighted(cv, a, nq, w); }, pcmax, grid_hi);
+}
+
+// The call's own arguments: the flags, the weight vector's presence, the probabilities.
+static int weighted_check(mcr_ctx* ctx, const double* v, i64 M, int flags, const double* probs, int nq, WgtArgs& g)
+{
+    if (flags & ~MCR_W_LOG) return fail(ctx, MCR_EINVAL, "unknown flag bits 0x%x", flags & ~MCR_W_LOG);
+    if (nq < 0 || nq > kWgtMaxQ) return fail(ctx, MCR_EINVAL, "nq must be in [0, %d]; got %d", kWgtMaxQ, nq);
+    if (nq > 0 && !probs) return fail(ctx, MCR_EINVAL, "probs is NULL");
+    if (M > 0 && !v) return fail(ctx, MCR_EINVAL, "weights is NULL");
+    g.nq = nq;
+    for (int j = 0; j < nq; ++j) {
+        if (!(probs[j] >= 0.0 && probs[j] <= 1.0)) return fail(ctx, MCR_EINVAL, "probs[%d] = %g: a probability must lie in [0, 1]", j, probs[j]);
+        g.q[j] = probs[j];
+    }
+    return MCR_OK;
+}
+
+// What the prepared totals say about the weight vector, in one text for the device and the host routine.
+static const char* weighted_refusal(const double* tot, char* text, size_t len)
+{
+    if (tot[WT_BAD] > 0.0) snprintf(text, len, "weights: %.0f entries are not weights (linear: finite and >= 0; log: finite or -inf)", tot[WT_BAD]);
+    else if (!(tot[WT_S1] > 0.0)) snprintf(text, len, "weights: no entry is positive");
+    else if (std::isinf(tot[WT_S1]) || std::isinf(tot[WT_S2])) snprintf(text, len, "weights: their sum or sum of squares overflows");
+    else return nullptr;
+    return text;
+}
+
+static void weighted_fill_nan(const mcr_weighted_out* o, i64 P, int nq)
+{
+    for (double* a : {o->mean, o->sd, o->mean_se})
+        if (a) for (i64 p = 0; p < P; ++p) a[p] = NAN;
+    if (o->quantiles) for (i64 at = 0; at < P * nq; ++at) o->quantiles[at] = NAN;
+    if (o->ess) *o->ess = NAN;
+    if (o->weight_sum) *o->weight_sum = NAN;
+}
+
+// host: the host entry, whose weight vector and weights output (like its draws) are the caller's host memory.
+static int weighted_run(mcr_ctx* ctx, const Tensor& t, const double* v, int flags, const WgtArgs& g, const mcr_weighted_out* out, bool host)
+{
+    const i64 M = t.M(), P = t.P, nb = wgt_blocks(M);
+    const int nq = g.nq, fields = wgt_fields(nq), log = (flags & MCR_W_LOG) ? 1 : 0;
+    i64 pcmax = 0;
+    int rc = plan_weighted(ctx, t, nq, pcmax);
+    double *d_v = nullptr, *d_w = nullptr, *d_bs = nullptr, *d_tot = nullptr, *d_res = nullptr;
+    if (!rc) rc = carve(ctx, ctx->call_dev, [&](Carve& cv) {
+        d_v = host ? cv.take<double>((size_t)M) : nullptr;
+        d_w = cv.take<double>((size_t)M);
+        d_bs = cv.take<double>((size_t)nb * 2);
+        d_tot = cv.take<double>(kWgtTotals);
+        d_res = cv.take<double>((size_t)fields * (size_t)P);
+    });
+    if (rc) return rc;
+    if (host) HIP_TRY(ctx, hipMemcpyAsync(d_v, v, sizeof(double) * (size_t)M, hipMemcpyHostToDevice, ctx->stream));
+    LAUNCH(ctx, K_WEIGHT_PREPARE, k_weight_prepare, dim3(1), dim3(kWgtPrepNT), 0, host ? (const double*)d_v : v, M, log, d_w, d_bs, d_tot);
+    double tot[kWgtTotals];
+    HIP_TRY(ctx, hipMemcpyAsync(tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    char text[160];
+    if (weighted_refusal(tot, text, sizeof text)) return fail(ctx, MCR_EINVAL, "%s", text);
+    WgtWs w{};
+    const unsigned nsl = (unsigned)((nb + kWgtSlice - 1) / kWgtSlice);
+    rc = pooled_chunks(ctx, t, pcmax, fields, d_res, [&](Carve& cv, PipeIn& a) { carve_weighted(cv, a, nq, w); },
+                       [&](const PipeIn& a, const Sorted& so, i64) -> int {
+        const unsigned pgrp = (unsigned)((a.pc + 7) / 8 * 8);
+        LAUNCH(ctx, K_WEIGHTED_MOMENTS, k_weighted_moments<1>, dim3(pgrp * nsl), dim3(kWgtNT), 0, (const double*)a.X, (const double*)d_w, M, a.pc,
+               (const double*)w.mean, w.part);
+        LAUNCH(ctx, K_WEIGHTED_COMBINE, k_weighted_combine<1>, dim3((unsigned)a.pc), dim3(kWave), 0, (const double*)w.part, nb, a.pc,
+               (const double*)d_tot, w.mean, a.d_res, kWgtField0);
+        LAUNCH(ctx, K_WEIGHTED_MOMENTS, k_weighted_moments<2>, dim3(pgrp * nsl), dim3(kWgtNT), 0, (const double*)a.X, (const double*)d_w, M, a.pc,
+               (const double*)w.mean, w.part);
+        LAUNCH(ctx, K_WEIGHTED_COMBINE, k_weighted_combine<2>, dim3((unsigned)a.pc), dim3(kWave), 0, (const double*)w.part, nb, a.pc,
+               (const double*)d_tot, w.mean, a.d_res, kWgtField0);
+        if (!nq) return MCR_OK;
+        if (a.idx16) {
+            LAUNCH(ctx, K_WQ_BLOCKS, k_wq_blocks<unsigned short>, dim3(pgrp * (unsigned)nb), dim3(kWave), 0,
+                   (const unsigned short*)so.pos, (const double*)d_w, M, a.pc, w.qb);
+            LAUNCH(ctx, K_WQ_PICK, k_wq_pick<unsigned short>, dim3(pgrp), dim3(kWgtNT), 0, (const double*)so.keys,
+                   (const unsigned short*)so.pos, (const double*)d_w, M, a.pc, g, (const double*)w.qb, a.d_res, kWgtField0 + WR_Q0);
+        } else {
+            LAUNCH(ctx, K_WQ_BLOCKS, k_wq_blocks<u32>, dim3(pgrp * (unsigned)nb), dim3(kWave), 0, (const u32*)so.pos,
+                   (const double*)d_w, M, a.pc, w.qb);
+            LAUNCH(ctx, K_WQ_PICK, k_wq_pick<u32>, dim3(pgrp), dim3(kWgtNT), 0, (const double*)so.keys, (const u32*)so.pos,
+                   (const double*)d_w, M, a.pc, g, (const double*)w.qb, a.d_res, kWgtField0 + WR_Q0);
+        }
+        return MCR_OK;
+    });
+    if (rc) return rc;
+    if (out->weights)
+        HIP_TRY(ctx, hipMemcpyAsync(out->weights, d_w, sizeof(double) * (size_t)M, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
+                                    ctx->stream));
+    if (out->ess) *out->ess = wgt_sq(tot[WT_S1]) / tot[WT_S2];
+    if (out->weight_sum) *out->weight_sum = tot[WT_S1];
+    return pooled_results(ctx, d_res, fields, P, pcmax, [&](const double* r, i64 pc, i64 p0, i64 p) {
+        const double* f = r + (size_t)kWgtField0 * pc + p;
+        if (out->mean) out->mean[p0 + p] = f[WR_MEAN * pc];
+        if (out->sd) out->sd[p0 + p] = f[WR_SD * pc];
+        if (out->mean_se) out->mean_se[p0 + p] = f[WR_SE * pc];
+        if (out->quantiles) for (int j = 0; j < nq; ++j) out->quantiles[(p0 + p) * nq + j] = f[(WR_Q0 + j) * pc];
+    });
+}
+
+int mcr_weighted_plan(mcr_ctx* ctx, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc, int64_t sn, int64_t sp, int nq,
+                      int64_t* params_per_chunk)
+{
+    const Tensor t{nullptr, dtype, C, N, P, sc, sn, sp};
+    return plan_entry(ctx, "mcr_weighted_plan", t, params_per_chunk, [&](i64& pcmax) {
+        if (nq < 0 || nq > kWgtMaxQ) return fail(ctx, MCR_EINVAL, "nq must be in [0, %d]; got %d", kWgtMaxQ, nq);
+        return plan_weighted(ctx, t, nq, pcmax);
+    });
+}
+
+static int weighted_entry(mcr_ctx* ctx, const Tensor& t, const double* v, int flags, const double* probs, int nq,
+                          mcr_weighted_out* out, bool host)
+{
+    WgtArgs g{};
+    return tensor_entry(ctx, "mcr_weighted_summary", t, out, host, [&] { return weighted_check(ctx, v, t.M(), flags, probs, nq, g); },
+                        [&] { weighted_fill_nan(out, t.P, nq); },
+                        [&](const Tensor& dev) { return weighted_run(ctx, dev, v, flags, g, out, host); });
+}
+
+int mcr_weighted_summary_dev(mcr_ctx* ctx, const void* draws_dev, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc,
+                             int64_t sn, int64_t sp, const double* weights_dev, int flags, const double* probs, int nq,
+                             mcr_weighted_out* out)
+{
+    return weighted_entry(ctx, {draws_dev, dtype, C, N, P, sc, sn, sp}, weights_dev, flags, probs, nq, out, false);
+}
+
+int mcr_weighted_summary(mcr_ctx* ctx, const void* draws, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc, int64_t sn,
+                         int64_t sp, const double* weights, int flags, const double* probs, int nq, mcr_weighted_out* out)
+{
+    return weighted_entry(ctx, {draws, dtype, C, N, P, sc, sn, sp}, weights, flags, probs, nq, out, true);
+}
+
+int mcr_weighted_host(const double* x, const double* v, int64_t M, int flags, const double* probs, int nq, double* mean,
+                      double* sd, double* mean_se, double* quantiles, double* ess, double* weight_sum, double* weights)
+{
+    if (M < 0 || M >= (i64)0x7FFFFFFFll || (M > 0 && (!x || !v)) || (flags & ~MCR_W_LOG) || nq < 0 || nq > kWgtMaxQ || (nq > 0 && !probs))
+        return MCR_EINVAL;
+    for (int j = 0; j < nq; ++j)
+        if (!(probs[j] >= 0.0 && probs[j] <= 1.0)) return MCR_EINVAL;
+    double r_mean = NAN, r_sd = NAN, r_se = NAN, r_ess = NAN, r_s1 = NAN;
+    std::vector<double> q((size_t)nq, NAN);
+    if (M > 0) {
+        const int log = (flags & MCR_W_LOG) ? 1 : 0;
+        double tot[kWgtTotals] = {0.0, -INFINITY, 0.0, 0.0};
+        for (i64 m = 0; m < M; ++m) {
+            if (wgt_bad(v[m], log)) tot[WT_BAD] += 1.0;
+            else if (v[m] > tot[WT_MAX]) tot[WT_MAX] = v[m];
+        }
+        std::vector<double> w((size_t)M, 0.0);
+        WgtHostTree tr;
+        if (!(tot[WT_BAD] > 0.0) && !(log && !(tot[WT_MAX] > -INFINITY))) {
+            for (i64 m = 0; m < M; ++m) w[(size_t)m] = wgt_weight(v[m], log, tot[WT_MAX]);
+            tot[WT_S1] = wgt_host_sum(tr, M, [&](i64 m) { return w[(size_t)m]; });
+            tot[WT_S2] = wgt_host_sum(tr, M, [&](i64 m) { return wgt_sq(w[(size_t)m]); });
+        }
+        char text[160];
+        if (weighted_refusal(tot, text, sizeof text)) return MCR_EINVAL;
+        for (i64 m = 0; m < M; ++m)
+            if (!std::isfinite(x[m])) return MCR_ENONFINITE;
+        const double S1 = tot[WT_S1];
+        r_s1 = S1;
+        r_ess = wgt_sq(S1) / tot[WT_S2];
+        r_mean = wgt_host_sum(tr, M, [&](i64 m) { return wgt_wx(w[(size_t)m], x[m]); }) / S1;
+        double t1, t2;
+        const double q1 = wgt_host_sum(tr, M, [&](i64 m) { wgt_dev2(w[(size_t)m], x[m], r_mean, t1, t2); return t1; });
+        const double q2 = wgt_host_sum(tr, M, [&](i64 m) { wgt_dev2(w[(size_t)m], x[m], r_mean, t1, t2); return t2; });
+        r_sd = std::sqrt(q1 / S1);
+        r_se = std::sqrt(q2) / S1;
+        if (nq > 0) {
+            std::vector<i64> at((size_t)M);
+            for (i64 i = 0; i < M; ++i) at[(size_t)i] = i;
+            std::sort(at.begin(), at.end(), [&](i64 a, i64 b) { return x[a] < x[b] || (x[a] == x[b] && a < b); });
+            const auto u = [&](i64 j) { return w[(size_t)at[(size_t)j]]; };
+            std::vector<double> roots;
+            wgt_host_sum(tr, M, u, &roots);
+            for (int j = 0; j < nq; ++j) {
+                double t = 0.0, prev = 0.0;
+                const i64 b = wgt_find_block([&](i64 k) { return roots[(size_t)k]; }, (i64)roots.size(), probs[j], t, prev);
+                if (b < 0) continue;
+                tr.build([&](int i) { const i64 k = b * kWgtBlock + i; return k < M ? u(k) : 0.0; });
+                for (int i = 0; i < kWgtBlock && b * kWgtBlock + i < M; ++i)
+                    if (wgt_reached(wgt_add(prev, wgt_prefix(tr, i + 1)), t)) { q[(size_t)j] = x[at[(size_t)(b * kWgtBlock + i)]]; break; }
+            }
+        }
+        if (weights) for (i64 m = 0; m < M; ++m) weights[m] = w[(size_t)m];
+    }
+    if (mean) *mean = r_mean;
+    if (sd) *sd = r_sd;
+    if (mean_se) *mean_se = r_se;
+    if (ess) *ess = r_ess;
+    if (weight_sum) *weight_sum = r_s1;
+    if (quantiles) for (int j = 0; j < nq; ++j) quantiles[j] = q[(size_t)j];
     return MCR_OK;
 }
 

@@ -84,6 +84,16 @@ class Hdi(C.Structure):
     _fields_ = [("lo", _dp), ("hi", _dp), ("index", _ip)]
 
 
+MCR_WEIGHTED_BLOCK = 1024                                   # consecutive indices of one summation tree of a weighted call
+MCR_WEIGHTED_MAX_Q = 16                                     # probabilities of a Context.weighted_summary call
+MCR_W_LOG = 1                                               # flag: the weight vector holds log weights
+
+
+class Weighted(C.Structure):
+    _fields_ = [("mean", _dp), ("sd", _dp), ("mean_se", _dp), ("quantiles", _dp), ("ess", _dp), ("weight_sum", _dp),
+                ("weights", C.c_void_p)]
+
+
 MCR_ACF_MAX_LAG = 4096                                      # the largest max_lag of a Context.autocorr call
 MCR_ACF_BLOCK = 512                                         # consecutive draws of one fma chain of k_acf_products
 MCR_ACF_UNBIASED = 1                                        # flag: gamma_l = S_l / (N - l)
@@ -207,6 +217,10 @@ SYMBOLS = {
     "mcr_hdi_dev": (C.c_int, [C.c_void_p] + _TENSOR + [_dp, C.c_int, C.POINTER(Hdi)]),
     "mcr_hdi_plan": (C.c_int, [C.c_void_p, C.c_int] + [_I64] * 6 + [C.c_int, C.POINTER(C.c_int64)]),
     "mcr_hdi_sorted_host": (C.c_int, [_dp, _I64, _dp, C.c_int, _dp, _dp, _ip]),
+    "mcr_weighted_summary": (C.c_int, [C.c_void_p] + _TENSOR + [C.c_void_p, C.c_int, _dp, C.c_int, C.POINTER(Weighted)]),
+    "mcr_weighted_summary_dev": (C.c_int, [C.c_void_p] + _TENSOR + [C.c_void_p, C.c_int, _dp, C.c_int, C.POINTER(Weighted)]),
+    "mcr_weighted_plan": (C.c_int, [C.c_void_p, C.c_int] + [_I64] * 6 + [C.c_int, C.POINTER(C.c_int64)]),
+    "mcr_weighted_host": (C.c_int, [_dp, _dp, _I64, C.c_int, _dp, C.c_int] + [_dp] * 7),
     "mcr_autocorr": (C.c_int, [C.c_void_p] + _TENSOR + [_I64, C.c_int, C.c_double, C.POINTER(Acf)]),
     "mcr_autocorr_dev": (C.c_int, [C.c_void_p] + _TENSOR + [_I64, C.c_int, C.c_double, C.POINTER(Acf)]),
     "mcr_autocorr_plan": (C.c_int, [C.c_void_p, C.c_int] + [_I64] * 7 + [C.POINTER(C.c_int64)]),
@@ -526,6 +540,44 @@ def hdi_sorted_host(sorted_draws, prob=0.94):
     if np.ndim(prob) == 0:
         return float(lo[0]), float(hi[0]), int(idx[0])
     return lo, hi, idx
+
+
+def weight_arguments(M: int, log_weights, weights, quantiles) -> tuple[np.ndarray, int, np.ndarray]:
+    """(the weight vector, the flags, the probabilities) of a weighted call on M pooled draws.  ValueError unless exactly
+    one of log_weights and weights is given and holds M entries, and the probabilities are at most MCR_WEIGHTED_MAX_Q
+    values in [0, 1]."""
+    if (log_weights is None) == (weights is None):
+        raise ValueError("give exactly one of log_weights and weights")
+    v = np.ascontiguousarray(weights if log_weights is None else log_weights, dtype=np.float64).reshape(-1)
+    if v.size != M:
+        raise ValueError(f"the weight vector has {v.size} entries for {M} pooled draws")
+    q = np.ascontiguousarray(np.atleast_1d(quantiles), dtype=np.float64).reshape(-1)
+    if q.size > MCR_WEIGHTED_MAX_Q:
+        raise ValueError(f"at most {MCR_WEIGHTED_MAX_Q} quantiles; got {q.size}")
+    if not np.all((q >= 0.0) & (q <= 1.0)):
+        raise ValueError(f"quantiles must lie in [0, 1]; got {quantiles}")
+    return v, 0 if log_weights is None else MCR_W_LOG, q
+
+
+def weighted_host(x, *, log_weights=None, weights=None, quantiles=(0.05, 0.5, 0.95), return_weights: bool = False) -> dict:
+    """The weighted summary of ONE parameter's draws in time order by the library's host routine (mcr_weighted_host: the
+    device's association, std::sort; no device): the floats mean, sd, mean_se, ess, weight_sum and the array quantiles;
+    with return_weights the weights as formed.  Linear weights give the device's bits; log weights go through libm's exp.
+    ValueError for a bad argument, a refused weight vector or a non-finite draw."""
+    d = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+    v, flags, q = weight_arguments(d.size, log_weights, weights, quantiles)
+    f = [C.c_double(np.nan) for _ in range(5)]
+    qs = np.full(max(q.size, 1), np.nan)
+    w = np.full(max(d.size, 1), np.nan) if return_weights else None
+    rc = load_library().mcr_weighted_host(_as_dp(d), _as_dp(v), d.size, flags, _as_dp(q), int(q.size), C.byref(f[0]),
+                                          C.byref(f[1]), C.byref(f[2]), _as_dp(qs), C.byref(f[3]), C.byref(f[4]), _as_dp(w))
+    if rc != MCR_OK:
+        raise ValueError(f"mcr_weighted_host: {'non-finite draw' if rc == MCR_ENONFINITE else 'bad argument or weight vector'}")
+    res = dict(zip(("mean", "sd", "mean_se", "ess", "weight_sum"), (c.value for c in f)))
+    res["quantiles"] = qs[:q.size]
+    if return_weights:
+        res["weights"] = w[:d.size]
+    return res
 
 
 def _acf_arrays(P: int, nc: int, L: int):
@@ -1575,6 +1627,50 @@ class Context:
     def hdi_params_per_chunk(self, t: "DeviceTensor", nprob: int = 1) -> int:
         """Parameters per workspace chunk of an hdi call with nprob probabilities on this tensor (mcr_hdi_plan)."""
         return self._params_per_chunk("mcr_hdi_plan", self._tensor_call(t, "pcn", "hdi", True)[0], int(nprob))
+
+    def weighted_summary(self, draws, layout: str = "pcn", *, log_weights=None, weights=None, quantiles=(0.05, 0.5, 0.95),
+                         return_weights: bool = False) -> dict:
+        """Importance-weighted mean, sd, standard error of the mean and quantiles of every parameter (mcr_weighted_summary:
+        posterior's weight_draws + summarise_draws, numpy.quantile(weights=, method="inverted_cdf")) of a host array or a
+        DeviceTensor under ONE weight per pooled draw, m = c * N + n; the chains are pooled, so a ragged tensor is
+        accepted.  Exactly one of log_weights (finite or -inf; Context.psis's rows are such) and weights (finite, >= 0).
+        "mean", "sd", "mean_se" [P], "quantiles" [P][nq] (inverted CDF: draws, never interpolated), the floats "ess"
+        (Kish's) and "weight_sum", "n_draws"; with return_weights "weights" [M], the linear weights the call formed."""
+        targs, ptr, fn, dev = self._tensor_call(draws, layout, "weighted_summary", True)
+        M, P = targs[1] * targs[2], targs[3]
+        v, flags, q = weight_arguments(M, log_weights, weights, quantiles)
+        nq = int(q.size)
+        arrs = {n: np.full(max(P, 1), np.nan) for n in ("mean", "sd", "mean_se")}
+        qs = np.full((max(P, 1), max(nq, 1)), np.nan)
+        ess, s1 = C.c_double(np.nan), C.c_double(np.nan)
+        w = np.full(max(M, 1), np.nan) if return_weights else None
+        vbuf = wbuf = None
+        try:
+            if dev:
+                vbuf = DeviceBuffer(self, max(M * 8, 8))
+                if M:
+                    vbuf.upload(v)
+                wbuf = DeviceBuffer(self, max(M * 8, 8)) if return_weights else None
+            vptr = vbuf.ptr if dev else v.ctypes.data_as(C.c_void_p)
+            wptr = None if w is None else wbuf.ptr if dev else w.ctypes.data_as(C.c_void_p)
+            out = Weighted(quantiles=_as_dp(qs), ess=C.pointer(ess), weight_sum=C.pointer(s1), weights=wptr,
+                           **{n: _as_dp(a) for n, a in arrs.items()})
+            self._check(fn(self.handle, ptr, *targs, vptr, flags, _as_dp(q), nq, C.byref(out)))
+            if wbuf is not None:
+                w = wbuf.download(np.float64, max(M, 1))
+        finally:
+            for b in (vbuf, wbuf):
+                if b is not None:
+                    b.free()
+        res = {n: a[:P] for n, a in arrs.items()}
+        res.update({"quantiles": qs[:P, :nq], "ess": ess.value, "weight_sum": s1.value, "n_draws": int(M)})
+        if return_weights:
+            res["weights"] = w[:M]
+        return res
+
+    def weighted_params_per_chunk(self, t: "DeviceTensor", nq: int = 3) -> int:
+        """Parameters per workspace chunk of a weighted_summary call with nq quantiles on this tensor (mcr_weighted_plan)."""
+        return self._params_per_chunk("mcr_weighted_plan", self._tensor_call(t, "pcn", "weighted_summary", True)[0], int(nq))
 
     def autocorr(self, draws, layout: str = "cnp", max_lag=None, unbiased: bool = False, window_c: float = 5.0) -> dict:
         """Autocorrelation functions and integrated autocorrelation times of the raw draws (mcr_autocorr: ArviZ's autocorr,

@@ -13,6 +13,7 @@ parameter and, with `--sliced K`, along K random directions of the joint distrib
 `nested-rhat FILE --superchains K` prints nested R-hat, the diagnostic for many short chains, of a draws table.
 `pareto-khat FILE` prints the Pareto k-hat of every parameter's tails: whether a mean and a std of the draws can be trusted.
 `loo FILE` prints PSIS-LOO of a table's pointwise log-likelihood columns: elpd_loo, p_loo and the observations' k-hats.
+`weighted-summary FILE` prints every parameter's mean, sd, standard error and quantiles under a column of importance weights.
 `hdi FILE` prints the highest-density interval(s) of every parameter: the shortest interval holding a share of the draws.
 `autocorr FILE` prints every parameter's integrated autocorrelation time (Sokal's window) and its stickiest and least
 sticky chain; as JSON, the autocorrelation function of every chain up to `--max-lag` as well.
@@ -252,6 +253,34 @@ def hdi_cmd(file: Path, params: str | None, probs: tuple[float, ...], format_: s
     except (ValueError, KeyError, IndexError) as exc:
         raise click.ClickException(str(exc)) from exc
     _echo_stats(stats, format_)
+
+
+@main.command("weighted-summary")
+@click.argument("file", type=click.Path(path_type=Path, exists=True, dir_okay=False))
+@click.option("--log-weights", default=None, help="The column of log importance ratios (or log weights)")
+@click.option("--weights", default=None, help="The column of linear weights (>= 0)")
+@click.option("--params", default=None, help="Comma-separated parameter list")
+@click.option("--quantile", "quantiles", multiple=True, type=float, help="A probability in [0, 1]; may be repeated (default: 0.05 0.5 0.95)")
+@click.option("--no-psis", is_flag=True, help="Use the log weights as they are, without Pareto smoothing")
+@click.option("--format", "format_", type=click.Choice(["table", "json"], case_sensitive=False), default="table")
+def weighted_summary_cmd(file: Path, log_weights: str | None, weights: str | None, params: str | None,
+                         quantiles: tuple[float, ...], no_psis: bool, format_: str) -> None:
+    """Importance-weighted mean, sd, standard error and inverted-CDF quantiles of every parameter of a draws table under
+    one weight column (no counterpart in the reference).  Log weights are Pareto-smoothed first (PSIS) unless --no-psis:
+    a k-hat above 0.7 says the weighted estimates are not reliable."""
+    try:
+        res = convert_mod.weighted_summary_file(file, log_weights=log_weights, weights=weights,
+                                                params=params.split(",") if params else None,
+                                                quantiles=quantiles or (0.05, 0.5, 0.95),
+                                                psis=not no_psis and weights is None)
+    except (ValueError, KeyError, IndexError) as exc:
+        raise click.ClickException(str(exc)) from exc
+    if format_ == "json":
+        click.echo(json.dumps(res, indent=2, sort_keys=True))
+        return
+    click.echo(f"draws {res['n_draws']}  ess {res['ess']:.6g}" +
+               (f"  khat {res['khat']:.3g} (threshold {res['khat_threshold']:.3g})" if "khat" in res else ""))
+    _print_table(res["params"])
 
 
 @main.command("autocorr")

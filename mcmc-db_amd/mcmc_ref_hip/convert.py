@@ -677,6 +677,51 @@ def hdi_file(path: Path, params: Iterable[str] | None = None, prob: Iterable[flo
             for i, n in enumerate(names)}
 
 
+def weighted_summary_file(path: Path, log_weights: str | None = None, weights: str | None = None,
+                          params: Iterable[str] | None = None, quantiles: Iterable[float] = (0.05, 0.5, 0.95),
+                          psis: bool = True, context=None) -> dict:
+    """Importance-weighted summaries of every parameter of a draws table (a `.csv`, a chain-list `.json.zip` or a
+    `.parquet` draws file of the store, read on the host); the chains are pooled and may differ in length.  The column
+    named by `log_weights` (log importance ratios or log weights) or by `weights` (linear, >= 0) is the weight of every
+    row and is left out of the parameters.  psis=True (log_weights only): the column first goes through Context.psis with
+    r_eff = 1 and its smoothed log weights are used; the result then carries "khat" and "khat_threshold".  "params":
+    per parameter mean, sd, mean_se and `q<100 q>` for every q of `quantiles` -- inverted-CDF quantiles
+    (Context.weighted_summary); at top level also "ess" (Kish's) and "n_draws"."""
+    if (log_weights is None) == (weights is None):
+        raise ValueError("give exactly one of log_weights and weights")
+    if psis and weights is not None:
+        raise ValueError("psis=True smooths log weights: give log_weights, or psis=False with weights")
+    wname = weights if log_weights is None else log_weights
+    qs = [float(q) for q in quantiles]
+    _ffi.weight_arguments(0, None, [], qs)                    # the quantiles are refused before anything is read
+    path = Path(path)
+    if path.suffix == ".parquet":
+        import pyarrow.parquet as pq
+        table = pq.read_table(path)
+    else:
+        table = _read_input(path)
+    table, names = _table_and_names(table, None if params is None else [p for p in params if p != wname] + [wname])
+    if wname not in names:
+        raise ValueError(f"Unknown weight column: {wname}")
+    names = [n for n in names if n != wname]
+    x, _ = table_to_tensor(table, names + [wname])
+    v, x = x[-1], x[:-1]
+    ctx = context or _ffi.default_context()
+    out: dict = {}
+    with _ffi.value_errors():
+        if psis:
+            sm = ctx.psis(v.reshape(1, 1, -1), "pcn")
+            v = sm["log_weights"][0]
+            out.update(khat=float(sm["khat"][0]), khat_threshold=sm["khat_threshold"])
+        r = ctx.weighted_summary(x.reshape(len(names), 1, -1), "pcn", quantiles=qs,
+                                 **({"weights": v} if log_weights is None else {"log_weights": v}))
+    out.update(ess=r["ess"], n_draws=r["n_draws"])
+    out["params"] = {n: {"mean": float(r["mean"][i]), "sd": float(r["sd"][i]), "mean_se": float(r["mean_se"][i]),
+                         **{f"q{100 * q:g}": float(r["quantiles"][i, j]) for j, q in enumerate(qs)}}
+                     for i, n in enumerate(names)}
+    return out
+
+
 def autocorr_file(path: Path, params: Iterable[str] | None = None, max_lag: int | None = None, unbiased: bool = False,
                   window_c: float = 5.0, context=None) -> dict[str, dict]:
     """Autocorrelation functions and times of every parameter of a draws table (a `.csv`, a chain-list `.json.zip` or a

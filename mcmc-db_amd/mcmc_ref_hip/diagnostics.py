@@ -148,6 +148,21 @@ def hdi(chains: Sequence[Sequence[float]], prob: float = 0.94, *, context=None) 
     return float(res["lo"][0]), float(res["hi"][0])
 
 
+def weighted_summary(chains: Sequence[Sequence[float]], *, log_weights=None, weights=None, quantiles=(0.05, 0.5, 0.95),
+                     context=None) -> dict:
+    """The importance-weighted summary of ONE parameter given as chains of any lengths (they are pooled, chain after
+    chain; the weight vector follows the pooled order): the floats "mean", "sd", "mean_se", "ess" (Kish's), "weight_sum",
+    the int "n_draws" and the array "quantiles" -- inverted-CDF quantiles, numpy.quantile(weights=, method="inverted_cdf")
+    (Context.weighted_summary).  Exactly one of log_weights and weights."""
+    x = np.concatenate([np.asarray(c, dtype=np.float64).reshape(-1) for c in chains]) if len(chains) else np.zeros(0)
+    ctx = context or _ffi.default_context()
+    with _ffi.value_errors():
+        res = ctx.weighted_summary(x.reshape(1, 1, -1), "pcn", log_weights=log_weights, weights=weights, quantiles=quantiles)
+    out = {k: float(res[k][0]) for k in ("mean", "sd", "mean_se")}
+    out.update(ess=res["ess"], weight_sum=res["weight_sum"], n_draws=res["n_draws"], quantiles=res["quantiles"][0])
+    return out
+
+
 def autocorr(chains: Sequence[Sequence[float]], max_lag: int | None = None, *, unbiased: bool = False, window_c: float = 5.0,
              context=None) -> dict:
     """Autocorrelation functions and times of ONE parameter given as equal-length chains (Context.autocorr): arrays "acf"

@@ -186,3 +186,57 @@ def validate(model: str, actual: Mapping[str, Sequence[float]], tolerance: float
                 failures.append(f"energy={det['e']:.3g} > {energy_max}")
     return ValidateResult(passed=not failures, compare=cmp_res, ks=ks, wasserstein=w1, wasserstein_scaled=scaled,
                           failures=failures, khat_ref=khat_ref, khat_actual=khat_act, hdi_ref=hdi_ref, hdi_actual=hdi_act, **extra)
+
+
+@dataclass(frozen=True)
+class WeightedValidateResult:
+    passed: bool
+    compare: CompareResult                       # the reference's gate on the weighted stats of `actual`
+    stats: dict[str, dict[str, float]]           # per parameter: mean, std, mean_se, q5, q50, q95 under the weights
+    ess: float                                   # Kish's effective sample size of the weights
+    khat: float | None                           # Pareto k-hat of the log weights (psis=True), else None
+    failures: list[str] = field(default_factory=list)
+
+
+def validate_weighted(model: str, actual: Mapping[str, Sequence[float]], log_weights: Sequence[float],
+                      tolerance: float = 0.15, metrics: Sequence[str] = ("mean", "std"), psis: bool = True,
+                      khat_max: float | None = None, ess_min: float | None = None, store: DataStore | None = None,
+                      context=None) -> WeightedValidateResult:
+    """The reference's gate (`compare_stats`) on draws from an approximation, reweighted towards the target: `actual`
+    holds joint draws (every parameter the same length) and `log_weights` one log importance ratio per draw.  psis=True
+    smooths them first (Context.psis, r_eff = 1) and reports the k-hat.  `stats` holds the weighted mean, std (the
+    population form) and mean_se of every parameter (Context.weighted_summary), and under q5 / q50 / q95 the weighted
+    inverted-CDF quantiles: draws, not the reference's linear interpolation -- with equal weights they differ from it by at
+    most one spacing of the order statistics.  khat_max / ess_min add the failures `khat=... > khat_max` and
+    `ess=... < ess_min`; without them the two numbers are information only."""
+    store = store or DataStore()
+    ctx = context or _ffi.default_context()
+    params = list(actual.keys())
+    lens = {len(actual[p]) for p in params}
+    if len(lens) > 1:
+        raise ValueError("weighted validation needs joint draws: the parameters of `actual` differ in length")
+    lw = np.ascontiguousarray(log_weights, dtype=np.float64).reshape(-1)
+    table = store.open_draws(model, params=params).read_all()
+    from .backends import HipBackend
+    ref_stats = HipBackend(ctx).stats(table, params)
+    khat = None
+    stats: dict[str, dict[str, float]] = {}
+    ess = float("nan")
+    with _ffi.value_errors():
+        if psis:
+            sm = ctx.psis(lw.reshape(1, 1, -1), "pcn")
+            lw, khat = sm["log_weights"][0], float(sm["khat"][0])
+        if params:
+            act = np.stack([np.asarray(actual[p], dtype=np.float64) for p in params])
+            r = ctx.weighted_summary(act.reshape(len(params), 1, -1), "pcn", log_weights=lw, quantiles=(0.05, 0.5, 0.95))
+            ess = r["ess"]
+            stats = {p: {"mean": float(r["mean"][i]), "std": float(r["sd"][i]), "mean_se": float(r["mean_se"][i]),
+                         "q5": float(r["quantiles"][i, 0]), "q50": float(r["quantiles"][i, 1]),
+                         "q95": float(r["quantiles"][i, 2])} for i, p in enumerate(params)}
+    cmp_res = compare_stats(ref_stats, stats, tolerance=tolerance, metrics=metrics, context=ctx)
+    failures = list(cmp_res.failures)
+    if khat_max is not None and khat is not None and not khat <= khat_max:
+        failures.append(f"khat={khat:.3g} > {khat_max}")
+    if ess_min is not None and not ess >= ess_min:
+        failures.append(f"ess={ess:.6g} < {ess_min}")
+    return WeightedValidateResult(passed=not failures, compare=cmp_res, stats=stats, ess=ess, khat=khat, failures=failures)
