@@ -596,6 +596,73 @@ int mcr_weighted_plan(mcr_ctx* ctx, int dtype, int64_t C, int64_t N, int64_t P, 
 int mcr_weighted_host(const double* x, const double* weights_in, int64_t M, int flags, const double* probs, int nq,
                       double* mean, double* sd, double* mean_se, double* quantiles, double* ess, double* weight_sum,
                       double* weights);
+/* Simulation-based calibration (SBC; Talts et al. 2018, Schad et al. 2021, the SBC R package): where the true value of
+ * a parameter stands among the posterior draws of a fit to data simulated from it, for S simulations at once.  ABSENT
+ * from the reference.  It checks a sampler when no reference posterior exists: over many simulations the rank is uniform
+ * exactly when the sampler is right.
+ * Input: S simulations, each a (C, N, P) draw tensor addressed like mcr_summarize's, simulation s starting stride_s
+ * elements behind simulation s - 1; f64 or f32 (f32 draws are widened first by the ingest pass: the answer is that of the
+ * f64 call on the widened tensor).  truth[S][P]: the values the data were simulated from, HOST doubles in both entries.
+ * Thinning is no argument: a thinned tensor is the same tensor with a larger stride_n and a smaller N.
+ * For every (s, p), with x_0 ... x_{L-1} the L = C * N draws of that simulation and parameter, chain after chain, and
+ * t = truth[s][p], everything in IEEE double:
+ *     n_less  = #{i : x_i < t}        n_equal = #{i : x_i == t}        (-0.0 == +0.0; a NaN draw is in neither)
+ *     mean    = (sum x_i) / L
+ *     sd      = sqrt((sum (x_i - mean)^2) / L)      the population form, like mcr_summarize's std, in two passes; the
+ *                                                   difference and its square are rounded one after the other
+ * The rank of t is n_less plus, by the method's convention, a uniform draw from 0 .. n_equal (the caller's: see
+ * mcmc_ref_hip.sbc).  ONE association for both sums, that of the weighted summaries above: the indices i are cut into
+ * blocks of MCR_WEIGHTED_BLOCK consecutive ones; a block's terms (+0 past the end) are the leaves of the balanced binary
+ * tree over adjacent indices, node(0, i) = term i, node(k, i) = node(k-1, 2 i) + node(k-1, 2 i + 1), the block's sum is the
+ * root; the blocks are added in ascending order from +0.  It is defined on the indices of the row, not on addresses, so
+ * an (s, p)'s outputs have the same bits alone or at any place in a batch, under any workspace limit, for aligned or
+ * misaligned rows, in any layout or strided view, from the host or the device entry, and mcr_sbc_ranks_host reproduces
+ * them bit for bit.
+ * out: HOST arrays of [S][P] entries each, NULL skipped.
+ * Limits: S * P < 2^31, C * N < 2^31 - 1.  MCR_EINVAL (message names the cause; nothing has been uploaded or written): a
+ * negative dimension, S * P >= 2^31, C * N >= 2^31 - 1, a NULL or non-finite entry of truth, negative strides, summaries in
+ * flight.  MCR_ENONFINITE: NaN / Inf draws, with their number in the message; the outputs are written all the same.
+ * L == 0 gives the counts 0 and NaN mean and sd without a launch; S == 0 or P == 0 writes nothing.  The context stays usable
+ * after every error.  Synchronous; the result table comes back in one copy.
+ * Kernels (mcr_sbc.hpp): k_sbc_ranks, a wave per (s, p).  When the draws are f64 and every simulation is [P][C][N]
+ * contiguous with stride_s = P * C * N, it reads the caller's memory: one launch, no copy.  Otherwise the simulations are
+ * cut into workspace chunks (mcr_sbc_plan), one k_ingest (its grid's z runs over the chunk's simulations) and one k_sbc_ranks
+ * per chunk, all on the stream without a host synchronisation in between. */
+typedef struct mcr_sbc_out {
+    int64_t *n_less, *n_equal;        /* [S][P] each, NULL skipped */
+    double  *mean, *sd;
+} mcr_sbc_out;
+int mcr_sbc_ranks(mcr_ctx* ctx, const void* draws, int dtype, int64_t S, int64_t C, int64_t N, int64_t P, int64_t stride_s,
+                  int64_t stride_c, int64_t stride_n, int64_t stride_p, const double* truth, mcr_sbc_out* out);
+/* The same on draws in this ctx's device memory; truth and out stay on the host. */
+int mcr_sbc_ranks_dev(mcr_ctx* ctx, const void* draws_dev, int dtype, int64_t S, int64_t C, int64_t N, int64_t P,
+                      int64_t stride_s, int64_t stride_c, int64_t stride_n, int64_t stride_p, const double* truth,
+                      mcr_sbc_out* out);
+/* Simulations per workspace chunk of such a call under the current workspace limit: S when the call reads the caller's
+ * memory, 0 for an empty shape.  MCR_ENOMEM when the limit does not fit one simulation's ingest copy; MCR_EINVAL for a
+ * shape the call would refuse (S < 0, S * P >= 2^31). */
+int mcr_sbc_plan(mcr_ctx* ctx, int dtype, int64_t S, int64_t C, int64_t N, int64_t P, int64_t stride_s, int64_t stride_c,
+                 int64_t stride_n, int64_t stride_p, int64_t* sims_per_chunk);
+/* The definition on the host (host only, no ctx, no device): x is [S][P][L] contiguous doubles.  MCR_EINVAL: a NULL array,
+ * a negative size, S * P >= 2^31, L >= 2^31 - 1, a non-finite entry of truth (nothing is written).  MCR_ENONFINITE: NaN / Inf
+ * draws (the outputs are written).  L == 0 gives 0 and NaN. */
+int mcr_sbc_ranks_host(const double* x, int64_t S, int64_t P, int64_t L, const double* truth, mcr_sbc_out* out);
+/* The uniformity of the ranks (host only, no ctx).  ranks[S][P], each in 0 .. L; B bins, 2 <= B <= L + 1; S >= 1.
+ *     bin(r)      = floor(r * B / (L + 1))
+ *     expected[b] = S * #{r in 0 .. L : bin(r) == b} / (L + 1)      exact also when B does not divide L + 1
+ *     counts[p][b] = #{s : bin(ranks[s][p]) == b}
+ *     chi2[p]     = sum_b (counts[p][b] - expected[b])^2 / expected[b]   in bin order, B - 1 degrees of freedom
+ *     pvalue[p]   = mcr_chi2_sf(chi2[p], B - 1)
+ *     ecdf_dev[p] = max over r in 0 .. L of |#{s : ranks[s][p] <= r} / S - (r + 1) / (L + 1)|, formed as the integer maximum of
+ *                   |#{...} (L + 1) - (r + 1) S| and divided once by S (L + 1), as the two-sample KS is
+ * Outputs: counts [P][B], expected [B], chi2, pvalue, ecdf_dev [P]; NULL skipped.  MCR_EINVAL: a NULL ranks, S < 1, P < 0,
+ * L < 0, B outside 2 .. L + 1, a rank outside 0 .. L (outputs of earlier parameters have been written). */
+int mcr_sbc_uniformity(const int64_t* ranks, int64_t S, int64_t P, int64_t L, int64_t B, int64_t* counts, double* expected,
+                       double* chi2, double* pvalue, double* ecdf_dev);
+/* The survival function of the chi-square distribution with dof > 0 degrees of freedom at x >= 0: the regularised upper
+ * incomplete gamma function Q(dof / 2, x / 2), by the series of P below x / 2 < dof / 2 + 1 and by the continued fraction
+ * of Q above.  NaN for dof <= 0, x < 0 or NaN. */
+double mcr_chi2_sf(double x, double dof);
 /* Autocorrelation functions and autocorrelation times: the autocorrelation of the RAW draws of every (parameter, chain)
  * up to a maximum lag, the within-chain pooled autocorrelation per parameter, and the integrated autocorrelation time
  * with Sokal's automatic window (posterior::autocorrelation, ArviZ's autocorr / plot_autocorr, emcee's integrated_time).

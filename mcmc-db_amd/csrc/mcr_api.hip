@@ -37,6 +37,7 @@
 #include "mcr_psis.hpp"
 #include "mcr_hdi.hpp"
 #include "mcr_weighted.hpp"
+#include "mcr_sbc.hpp"
 #include "mcr_parquet.hpp"
 #include "mcr_pqwrite.hpp"
 #include "mcr_csvwrite.hpp"
@@ -69,7 +70,7 @@ enum KernelId {
     K_LAYOUT_SCAN, K_LAYOUT_KEYS, K_LAYOUT_HIST, K_LAYOUT_OFFSETS, K_LAYOUT_SCATTER, K_LAYOUT_BOUNDS,
     K_PQW_ENCODE, K_PQW_COMPACT, K_CSVW_FORMAT, K_CSVW_SCAN, K_CSVW_COMPACT, K_SELECT_ROWS, K_PROJECT,
     K_CHAIN_MOMENTS, K_NESTED_COMBINE, K_PARETO_FIT, K_PSIS_COLUMN, K_PSIS_WEIGHTS, K_HDI_WINDOW, K_HDI_PICK,
-    K_WEIGHT_PREPARE, K_WEIGHTED_MOMENTS, K_WEIGHTED_COMBINE, K_WQ_BLOCKS, K_WQ_PICK,
+    K_WEIGHT_PREPARE, K_WEIGHTED_MOMENTS, K_WEIGHTED_COMBINE, K_WQ_BLOCKS, K_WQ_PICK, K_SBC_RANKS,
     K_ACF_MEAN, K_ACF_PRODUCTS, K_ACF_FINISH, K_ACF_POOL, K_ENERGY_PAIRS, K_ENERGY_REDUCE, K_COUNT
 };
 const char* const kKernelNames[K_COUNT] = {
@@ -82,7 +83,7 @@ const char* const kKernelNames[K_COUNT] = {
     "k_layout_scan", "k_layout_keys", "k_layout_hist", "k_layout_offsets", "k_layout_scatter", "k_layout_bounds",
     "k_pqw_encode", "k_pqw_compact", "k_csvw_format", "k_csvw_scan", "k_csvw_compact", "k_select_rows", "k_project",
     "k_chain_moments", "k_nested_combine", "k_pareto_fit", "k_psis_column", "k_psis_weights", "k_hdi_window", "k_hdi_pick",
-    "k_weight_prepare", "k_weighted_moments", "k_weighted_combine", "k_wq_blocks", "k_wq_pick",
+    "k_weight_prepare", "k_weighted_moments", "k_weighted_combine", "k_wq_blocks", "k_wq_pick", "k_sbc_ranks",
     "k_acf_mean", "k_acf_products", "k_acf_finish", "k_acf_pool", "k_energy_pairs", "k_energy_reduce"};
 
 struct EvPair { hipEvent_t a, b; int kid; };
@@ -880,24 +881,28 @@ int prep_quantiles(mcr_ctx* ctx, const double* qs, int nq, i64 M, QArgs& q, i64*
 
 constexpr int res_fields(int nq) { return R_Q0 + nq; }
 
+// nt tensors in one launch (along z, at most kMaxGridY): tensor z starts z * ss elements into src, its copy z * xs into X.
+// The summary and the tensor calls ingest ONE tensor per chunk (nt = 1, ss = xs = 0: the launch they always made); only
+// mcr_sbc_ranks passes a batch, its chunk's simulations.
 template <typename T>
-int launch_ingest_as(mcr_ctx* ctx, const void* src, double* X, i64 C, i64 N, i64 pc, i64 sc, i64 sn, i64 sp, i64 p0)
+int launch_ingest_as(mcr_ctx* ctx, const void* src, double* X, i64 C, i64 N, i64 pc, i64 sc, i64 sn, i64 sp, i64 p0, i64 nt, i64 ss, i64 xs)
 {
     if (sp == 1 && sn != 1 && pc > 1) {
         const i64 nb = (N + 63) / 64;
-        LAUNCH(ctx, K_INGEST, (k_ingest_transpose<T>), dim3((unsigned)(nb * C), (unsigned)((pc + 63) / 64)),
-               dim3(256), 0, (const T*)src, X, C, N, pc, sc, sn, sp, p0);
+        LAUNCH(ctx, K_INGEST, (k_ingest_transpose<T>), dim3((unsigned)(nb * C), (unsigned)((pc + 63) / 64), (unsigned)nt),
+               dim3(256), 0, (const T*)src, X, C, N, pc, sc, sn, sp, p0, ss, xs);
     } else {
         const i64 nb = (N + 255) / 256;
-        LAUNCH(ctx, K_INGEST, (k_ingest_rows<T>), dim3((unsigned)(nb * C), (unsigned)pc), dim3(256), 0,
-               (const T*)src, X, C, N, sc, sn, sp, p0);
+        LAUNCH(ctx, K_INGEST, (k_ingest_rows<T>), dim3((unsigned)(nb * C), (unsigned)pc, (unsigned)nt), dim3(256), 0,
+               (const T*)src, X, C, N, sc, sn, sp, p0, ss, xs);
     }
     return MCR_OK;
 }
-int launch_ingest(mcr_ctx* ctx, const void* src, int dtype, double* X, i64 C, i64 N, i64 pc, i64 sc, i64 sn, i64 sp, i64 p0)
+int launch_ingest(mcr_ctx* ctx, const void* src, int dtype, double* X, i64 C, i64 N, i64 pc, i64 sc, i64 sn, i64 sp, i64 p0, i64 nt = 1,
+                  i64 ss = 0, i64 xs = 0)
 {
-    return dtype == MCR_F64 ? launch_ingest_as<double>(ctx, src, X, C, N, pc, sc, sn, sp, p0)
-                            : launch_ingest_as<float>(ctx, src, X, C, N, pc, sc, sn, sp, p0);
+    return dtype == MCR_F64 ? launch_ingest_as<double>(ctx, src, X, C, N, pc, sc, sn, sp, p0, nt, ss, xs)
+                            : launch_ingest_as<float>(ctx, src, X, C, N, pc, sc, sn, sp, p0, nt, ss, xs);
 }
 
 void fill_nan(const mcr_summary& o, i64 P, int nq)
@@ -1145,7 +1150,7 @@ int run_summary(mcr_ctx* ctx, const SummaryCall& c)
                                                // three more launches and two event waits (measured: C1 4 M param-draws 306 -> 288 us,
                                                // 10 x 1000 x 45 149 -> 166, 4 x 1000 x 10 124 -> 133), short enough not to fill the chip
             if (cp.ingest) {
-                rc = launch_ingest(ctx, c.draws_dev, c.dtype, X, iC, iN, pc, isc, isn, c.sp, p0);
+                rc = launch_ingest(ctx, c.draws_dev, c.dtype, X, iC, iN, pc, isc, isn, c.sp, p0);      // (one tensor: z = 1)
                 if (rc) return rc;
                 a.X = X;
             } else {
@@ -2034,15 +2039,22 @@ int mcr_energy_distance_host(const double* ref, int64_t Mr, const double* act, i
 // run the summary pipeline without diagnostics and quantiles -- tile sort, merges / bucket partition, k_order_stats,
 // k_finalize for the non-finite count -- and then their own kernels on the keys the sort stage left (pooled_chunks); the
 // two with tails share tail_check and tail_lds.  A family below supplies its own arguments' check, its chunk's layout,
-// its launches and the scatter of its results, and nothing else.
+// its launches and the scatter of its results, and nothing else.  Simulation-based calibration takes S such tensors (the
+// Tensor's fourth axis) through the same entry and cuts its SIMULATIONS into chunks, where it needs the ingest copy at all.
 namespace {
 
 struct Tensor {
     const void* draws; int dtype; i64 C, N, P, sc, sn, sp;
+    i64 S = 1, ss = 0;   // the fourth axis (mcr_sbc_ranks): S such tensors, each ss elements behind the one before
     i64 M() const { return C * N; }
-    i64 extent() const { return tensor_extent(C, N, P, sc, sn, sp); }
+    i64 extent() const
+    {
+        const i64 e = tensor_extent(C, N, P, sc, sn, sp);
+        if (S < 1 || e <= 0) return S < 1 ? 0 : e;
+        return ss < 0 ? -1 : (S - 1) * ss + e;
+    }
     // f32 draws are widened by the ingest pass: the answer is the f64 call's on the widened tensor
-    bool ingest() const { return dtype == MCR_F32 || needs_ingest(C, N, P, sc, sn, sp); }
+    bool ingest() const { return dtype == MCR_F32 || needs_ingest(C, N, P, sc, sn, sp) || (S > 1 && ss != P * M()); }
 };
 
 // Acceptance of the tensor of such a call (`what` names the entry in the message).
@@ -2052,7 +2064,7 @@ int pooled_check(mcr_ctx* ctx, const char* what, const Tensor& t, const void* ou
     if (t.dtype != MCR_F64 && t.dtype != MCR_F32) return fail(ctx, MCR_EINVAL, "unsupported dtype %d", t.dtype);
     if (t.C < 0 || t.N < 0 || t.P < 0) return fail(ctx, MCR_EINVAL, "negative dimension (C=%lld N=%lld P=%lld)", (long long)t.C, (long long)t.N, (long long)t.P);
     if (t.N > 0 && (t.C > (i64)0x7FFFFFFFll / t.N || t.M() >= (i64)0x7FFFFFFFll)) return fail(ctx, MCR_EINVAL, "C*N must be < 2^31 - 1");
-    if (!t.draws && t.M() * t.P > 0) return fail(ctx, MCR_EINVAL, "draws is NULL");
+    if (!t.draws && t.S != 0 && t.M() * t.P > 0) return fail(ctx, MCR_EINVAL, "draws is NULL");   // (S == 0: nothing to read)
     if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "%s with summaries in flight", what);
     return MCR_OK;
 }
@@ -2079,7 +2091,7 @@ int tensor_entry(mcr_ctx* ctx, const char* what, Tensor t, const void* out, bool
     if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
     int rc = pooled_check(ctx, what, t, out);
     if (!rc) rc = check();
-    if (rc || t.P == 0) return rc;
+    if (rc || t.P == 0 || t.S == 0) return rc;
     if (t.M() == 0) { empty(); return MCR_OK; }
     if (t.extent() < 0) return fail(ctx, MCR_EINVAL, "negative strides are not supported");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -2125,7 +2137,7 @@ int tensor_chunks(mcr_ctx* ctx, const Tensor& t, i64 pcmax, Layout&& layout, Bod
         const i64 pc = (t.P - p0 < pcmax) ? t.P - p0 : pcmax;
         double* copy = nullptr;
         int rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) { copy = layout(cv, pc); });
-        if (!rc && ingest) rc = launch_ingest(ctx, t.draws, t.dtype, copy, t.C, t.N, pc, t.sc, t.sn, t.sp, p0);
+        if (!rc && ingest) rc = launch_ingest(ctx, t.draws, t.dtype, copy, t.C, t.N, pc, t.sc, t.sn, t.sp, p0);   // (one tensor: z = 1)
         if (!rc) rc = body(pc, p0, ingest ? copy : reinterpret_cast<const double*>(t.draws) + p0 * t.M());
         if (rc) return rc;
     }
@@ -3017,6 +3029,200 @@ int mcr_weighted_host(const double* x, const double* v, int64_t M, int flags, co
     if (ess) *ess = r_ess;
     if (weight_sum) *weight_sum = r_s1;
     if (quantiles) for (int j = 0; j < nq; ++j) quantiles[j] = q[(size_t)j];
+    return MCR_OK;
+}
+
+// ---- Simulation-based calibration (mcr_sbc.hpp) ------------------------------------------------------------------------------
+// The tensor's fourth axis: the call is cut into chunks of SIMULATIONS, not of parameters, and only where it needs the
+// ingest copy; the result table [kSbcFields][S P] lies behind the uploaded truth in the call's device table.
+
+// What a call asks of its shape beyond pooled_check (`ctx` NULL: the host routine's, no message kept): the plan entry's too.
+static int sbc_shape_check(mcr_ctx* ctx, i64 S, i64 P)
+{
+    if (S < 0) return fail(ctx, MCR_EINVAL, "negative dimension (S=%lld)", (long long)S);
+    if (P > 0 && S > (i64)0x7FFFFFFFll / P) return fail(ctx, MCR_EINVAL, "S*P must be < 2^31");
+    return MCR_OK;
+}
+
+// ... and of its true values.
+static int sbc_check(mcr_ctx* ctx, i64 S, i64 P, const double* truth)
+{
+    const int rc = sbc_shape_check(ctx, S, P);
+    if (rc) return rc;
+    if (!truth && S * P > 0) return fail(ctx, MCR_EINVAL, "truth is NULL");
+    for (i64 k = 0; k < S * P; ++k)
+        if (!std::isfinite(truth[k]))
+            return fail(ctx, MCR_EINVAL, "truth[%lld][%lld] = %g: the true values must be finite", (long long)(k / P), (long long)(k % P), truth[k]);
+    return MCR_OK;
+}
+
+// Simulations without draws: the counts 0, NaN mean and sd.
+static void sbc_fill_empty(const mcr_sbc_out* o, i64 rows)
+{
+    for (int64_t* a : {o->n_less, o->n_equal})
+        if (a) for (i64 k = 0; k < rows; ++k) a[k] = 0;
+    for (double* a : {o->mean, o->sd})
+        if (a) for (i64 k = 0; k < rows; ++k) a[k] = NAN;
+}
+
+// Simulations per workspace chunk: all of them where the kernel reads the caller's rows, else as many ingest copies as fit.
+static int plan_sbc(mcr_ctx* ctx, const Tensor& t, i64& scmax)
+{
+    scmax = t.S;
+    if (!t.ingest()) return MCR_OK;
+    // k P < 2^31 rows (sbc_shape_check) of M < 2^31 - 1 draws: the count of doubles stays below 2^62; its bytes may not fit
+    auto measure = [&](i64 k) {
+        const size_t n = (size_t)k * (size_t)t.P * (size_t)t.M();
+        if (n > SIZE_MAX / (2 * sizeof(double))) return (size_t)SIZE_MAX;
+        Carve m{nullptr};
+        m.take<double>(n);
+        return m.off;
+    };
+    scmax = most_that_fit(t.S, [&](i64 k) { return measure(k) <= ctx->ws_limit; });
+    if (!scmax) return fail(ctx, MCR_ENOMEM, "one simulation needs %zu bytes of workspace; limit is %zu", measure(1), ctx->ws_limit);
+    return MCR_OK;
+}
+
+// Rows of up to kSbcRegBlocks blocks stay in registers between the passes; one block needs a quarter of them.
+static int launch_sbc(mcr_ctx* ctx, const double* X, i64 L, i64 rows, const double* d_truth, double* d_res, i64 stride)
+{
+    const dim3 grid((unsigned)((rows + kSbcRows - 1) / kSbcRows));
+    if (L > kWgtBlock && L <= (i64)kSbcRegBlocks * kWgtBlock)
+        LAUNCH(ctx, K_SBC_RANKS, (k_sbc_ranks<kSbcRegBlocks>), grid, dim3(kSbcNT), 0, X, L, rows, d_truth, d_res, stride);
+    else
+        LAUNCH(ctx, K_SBC_RANKS, (k_sbc_ranks<1>), grid, dim3(kSbcNT), 0, X, L, rows, d_truth, d_res, stride);
+    return MCR_OK;
+}
+
+static int sbc_run(mcr_ctx* ctx, const Tensor& t, const double* truth, const mcr_sbc_out* out)
+{
+    const i64 L = t.M(), P = t.P, rows = t.S * P;
+    i64 scmax = 0;
+    int rc = plan_sbc(ctx, t, scmax);
+    if (rc) return rc;
+    const std::vector<double> head(truth, truth + rows);
+    double *d_truth = nullptr, *d_res = nullptr;
+    rc = call_table(ctx, head, (size_t)kSbcFields * (size_t)rows, d_truth, d_res);
+    if (!rc) rc = ctx->call_host.reserve(ctx, sizeof(double) * (size_t)kSbcFields * (size_t)rows);
+    if (rc) return rc;
+    const bool ingest = t.ingest();
+    const size_t es = t.dtype == MCR_F64 ? 8 : 4;
+    for (i64 s0 = 0; s0 < t.S; s0 += scmax) {
+        const i64 sc = t.S - s0 < scmax ? t.S - s0 : scmax, r0 = s0 * P;
+        const double* X = reinterpret_cast<const double*>(t.draws) + r0 * L;
+        if (ingest) {
+            double* copy = nullptr;
+            rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) { copy = cv.take<double>((size_t)sc * (size_t)P * (size_t)L); });
+            for (i64 s = 0; s < sc && !rc; s += kMaxGridY)                         // (k_ingest's simulations lie along z,
+                for (i64 p0 = 0; p0 < P && !rc; p0 += kMaxGridY / 2) {             //  its parameters along y)
+                    const i64 ns = sc - s < kMaxGridY ? sc - s : kMaxGridY, pc = P - p0 < kMaxGridY / 2 ? P - p0 : kMaxGridY / 2;
+                    rc = launch_ingest(ctx, static_cast<const char*>(t.draws) + (size_t)(s0 + s) * (size_t)t.ss * es, t.dtype,
+                                       copy + (s * P + p0) * L, t.C, t.N, pc, t.sc, t.sn, t.sp, p0, ns, t.ss, P * L);
+                }
+            if (rc) return rc;
+            X = copy;
+        }
+        rc = launch_sbc(ctx, X, L, sc * P, d_truth + r0, d_res + r0, rows);
+        if (rc) return rc;
+    }
+    const double* h = ctx->call_host.as<double>();
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->call_host.p, d_res, sizeof(double) * (size_t)kSbcFields * (size_t)rows, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    prof_resolve(ctx);
+    double nbad = 0.0;
+    for (i64 k = 0; k < rows; ++k) {
+        if (out->n_less) out->n_less[k] = (int64_t)h[(size_t)SB_LESS * (size_t)rows + (size_t)k];
+        if (out->n_equal) out->n_equal[k] = (int64_t)h[(size_t)SB_EQUAL * (size_t)rows + (size_t)k];
+        nbad += h[(size_t)SB_BAD * (size_t)rows + (size_t)k];
+    }
+    if (out->mean) memcpy(out->mean, h + (size_t)SB_MEAN * (size_t)rows, sizeof(double) * (size_t)rows);
+    if (out->sd) memcpy(out->sd, h + (size_t)SB_SD * (size_t)rows, sizeof(double) * (size_t)rows);
+    if (nbad > 0.0) return fail(ctx, MCR_ENONFINITE, "draws contain %.0f non-finite value(s)", nbad);
+    return MCR_OK;
+}
+
+static Tensor sbc_tensor(const void* draws, int dtype, i64 S, i64 C, i64 N, i64 P, i64 ss, i64 sc, i64 sn, i64 sp)
+{
+    Tensor t{draws, dtype, C, N, P, sc, sn, sp};
+    t.S = S; t.ss = ss;
+    return t;
+}
+
+static int sbc_entry(mcr_ctx* ctx, const Tensor& t, const double* truth, mcr_sbc_out* out, bool host)
+{
+    return tensor_entry(ctx, "mcr_sbc_ranks", t, out, host, [&] { return sbc_check(ctx, t.S, t.P, truth); },
+                        [&] { sbc_fill_empty(out, t.S * t.P); }, [&](const Tensor& dev) { return sbc_run(ctx, dev, truth, out); });
+}
+
+int mcr_sbc_ranks_dev(mcr_ctx* ctx, const void* draws_dev, int dtype, int64_t S, int64_t C, int64_t N, int64_t P, int64_t ss,
+                      int64_t sc, int64_t sn, int64_t sp, const double* truth, mcr_sbc_out* out)
+{
+    return sbc_entry(ctx, sbc_tensor(draws_dev, dtype, S, C, N, P, ss, sc, sn, sp), truth, out, false);
+}
+
+int mcr_sbc_ranks(mcr_ctx* ctx, const void* draws, int dtype, int64_t S, int64_t C, int64_t N, int64_t P, int64_t ss, int64_t sc,
+                  int64_t sn, int64_t sp, const double* truth, mcr_sbc_out* out)
+{
+    return sbc_entry(ctx, sbc_tensor(draws, dtype, S, C, N, P, ss, sc, sn, sp), truth, out, true);
+}
+
+int mcr_sbc_plan(mcr_ctx* ctx, int dtype, int64_t S, int64_t C, int64_t N, int64_t P, int64_t ss, int64_t sc, int64_t sn,
+                 int64_t sp, int64_t* sims_per_chunk)
+{
+    const Tensor t = sbc_tensor(nullptr, dtype, S, C, N, P, ss, sc, sn, sp);
+    return plan_entry(ctx, "mcr_sbc_plan", t, sims_per_chunk, [&](i64& scmax) {
+        const int rc = sbc_shape_check(ctx, S, P);                         // (what the call would refuse, the plan refuses)
+        return rc || S < 1 ? rc : plan_sbc(ctx, t, scmax);
+    });
+}
+
+int mcr_sbc_ranks_host(const double* x, int64_t S, int64_t P, int64_t L, const double* truth, mcr_sbc_out* out)
+{
+    if (!out || P < 0 || L < 0 || L >= (i64)0x7FFFFFFFll) return MCR_EINVAL;
+    const int rc = sbc_check(nullptr, S, P, truth);
+    if (rc) return rc;
+    const i64 rows = S * P;
+    if (rows == 0) return MCR_OK;
+    if (L == 0) { sbc_fill_empty(out, rows); return MCR_OK; }
+    if (!x) return MCR_EINVAL;
+    WgtHostTree tr;
+    i64 nbad = 0;
+    for (i64 k = 0; k < rows; ++k) {
+        i64 less, equal, bad;
+        double mean, sd;
+        sbc_row_host(tr, x + k * L, L, truth[k], less, equal, bad, mean, sd);
+        if (out->n_less) out->n_less[k] = less;
+        if (out->n_equal) out->n_equal[k] = equal;
+        if (out->mean) out->mean[k] = mean;
+        if (out->sd) out->sd[k] = sd;
+        nbad += bad;
+    }
+    return nbad > 0 ? MCR_ENONFINITE : MCR_OK;
+}
+
+double mcr_chi2_sf(double x, double dof)
+{
+    if (!(dof > 0.0) || !(x >= 0.0)) return NAN;
+    return sbc_gamma_q(0.5 * dof, 0.5 * x);
+}
+
+int mcr_sbc_uniformity(const int64_t* ranks, int64_t S, int64_t P, int64_t L, int64_t B, int64_t* counts, double* expected,
+                       double* chi2, double* pvalue, double* ecdf_dev)
+{
+    if (!ranks || S < 1 || P < 0 || L < 0 || L >= (i64)0x7FFFFFFFll || B < 2 || B > L + 1) return MCR_EINVAL;
+    std::vector<double> ex((size_t)B);
+    for (i64 b = 0; b < B; ++b)
+        ex[(size_t)b] = (double)S * (double)(sbc_bin_start(b + 1, B, L) - sbc_bin_start(b, B, L)) / (double)(L + 1);
+    if (expected) memcpy(expected, ex.data(), sizeof(double) * (size_t)B);
+    std::vector<i64> sorted((size_t)S);
+    for (i64 p = 0; p < P; ++p) {
+        double c2, ec;
+        if (!sbc_uniform_column(reinterpret_cast<const i64*>(ranks) + p, S, P, L, B, ex.data(), sorted, counts ? reinterpret_cast<i64*>(counts) + p * B : nullptr, c2, ec))
+            return MCR_EINVAL;
+        if (chi2) chi2[p] = c2;
+        if (pvalue) pvalue[p] = mcr_chi2_sf(c2, (double)(B - 1));
+        if (ecdf_dev) ecdf_dev[p] = ec;
+    }
     return MCR_OK;
 }
 

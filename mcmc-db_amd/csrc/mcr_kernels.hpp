@@ -95,13 +95,16 @@ __global__ __launch_bounds__(256) void k_decode_codes(const u32* __restrict__ co
 }
 
 // ------------------------------------------------------------------------------------------------
-// Ingest: arbitrary element strides / f32 -> X[p][c*N + t] f64.
+// Ingest: arbitrary element strides / f32 -> X[p][c*N + t] f64.  Along z the tensors of a batch (mcr_sbc_ranks' simulations):
+// tensor z starts z * ss elements into src and z * xs doubles into X; one tensor: gridDim.z = 1.
 // rows variant: lanes run along t (coalesced when stride_n == 1).
 // ------------------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void k_ingest_rows(const T* __restrict__ src, double* __restrict__ X,
-                                                     i64 C, i64 N, i64 sc, i64 sn, i64 sp, i64 p0)
+                                                     i64 C, i64 N, i64 sc, i64 sn, i64 sp, i64 p0, i64 ss, i64 xs)
 {
+    src += (i64)blockIdx.z * ss;
+    X += (i64)blockIdx.z * xs;
     const i64 nb = (N + 255) / 256;
     const i64 c = blockIdx.x / nb, t = (blockIdx.x % nb) * 256 + threadIdx.x;
     const i64 p = blockIdx.y;
@@ -113,9 +116,11 @@ __global__ __launch_bounds__(256) void k_ingest_rows(const T* __restrict__ src, 
 template <typename T>
 __global__ __launch_bounds__(256) void k_ingest_transpose(const T* __restrict__ src,
                                                           double* __restrict__ X, i64 C, i64 N, i64 P,
-                                                          i64 sc, i64 sn, i64 sp, i64 p0)
+                                                          i64 sc, i64 sn, i64 sp, i64 p0, i64 ss, i64 xs)
 {
     __shared__ double tile[64][65];
+    src += (i64)blockIdx.z * ss;
+    X += (i64)blockIdx.z * xs;
     const i64 nb = (N + 63) / 64;
     const i64 c = blockIdx.x / nb, t0 = (blockIdx.x % nb) * 64;
     const i64 pl0 = (i64)blockIdx.y * 64;

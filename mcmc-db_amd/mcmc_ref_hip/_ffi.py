@@ -94,6 +94,10 @@ class Weighted(C.Structure):
                 ("weights", C.c_void_p)]
 
 
+class Sbc(C.Structure):
+    _fields_ = [("n_less", _ip), ("n_equal", _ip), ("mean", _dp), ("sd", _dp)]
+
+
 MCR_ACF_MAX_LAG = 4096                                      # the largest max_lag of a Context.autocorr call
 MCR_ACF_BLOCK = 512                                         # consecutive draws of one fma chain of k_acf_products
 MCR_ACF_UNBIASED = 1                                        # flag: gamma_l = S_l / (N - l)
@@ -160,6 +164,7 @@ class KernelTime(C.Structure):
 # every symbol include/mcmcref_hip.h declares: (restype, argtypes)
 _I64 = C.c_int64
 _TENSOR = [C.c_void_p, C.c_int, _I64, _I64, _I64, _I64, _I64, _I64]
+_TENSOR4 = [C.c_void_p, C.c_int] + [_I64] * 8               # S simulations of such a tensor: S, C, N, P and their strides
 SYMBOLS = {
     "mcr_version": (C.c_int, []),
     "mcr_device_count": (C.c_int, []),
@@ -221,6 +226,12 @@ SYMBOLS = {
     "mcr_weighted_summary_dev": (C.c_int, [C.c_void_p] + _TENSOR + [C.c_void_p, C.c_int, _dp, C.c_int, C.POINTER(Weighted)]),
     "mcr_weighted_plan": (C.c_int, [C.c_void_p, C.c_int] + [_I64] * 6 + [C.c_int, C.POINTER(C.c_int64)]),
     "mcr_weighted_host": (C.c_int, [_dp, _dp, _I64, C.c_int, _dp, C.c_int] + [_dp] * 7),
+    "mcr_sbc_ranks": (C.c_int, [C.c_void_p] + _TENSOR4 + [_dp, C.POINTER(Sbc)]),
+    "mcr_sbc_ranks_dev": (C.c_int, [C.c_void_p] + _TENSOR4 + [_dp, C.POINTER(Sbc)]),
+    "mcr_sbc_plan": (C.c_int, [C.c_void_p, C.c_int] + [_I64] * 8 + [C.POINTER(C.c_int64)]),
+    "mcr_sbc_ranks_host": (C.c_int, [_dp, _I64, _I64, _I64, _dp, C.POINTER(Sbc)]),
+    "mcr_sbc_uniformity": (C.c_int, [_ip, _I64, _I64, _I64, _I64, _ip, _dp, _dp, _dp, _dp]),
+    "mcr_chi2_sf": (C.c_double, [C.c_double, C.c_double]),
     "mcr_autocorr": (C.c_int, [C.c_void_p] + _TENSOR + [_I64, C.c_int, C.c_double, C.POINTER(Acf)]),
     "mcr_autocorr_dev": (C.c_int, [C.c_void_p] + _TENSOR + [_I64, C.c_int, C.c_double, C.POINTER(Acf)]),
     "mcr_autocorr_plan": (C.c_int, [C.c_void_p, C.c_int] + [_I64] * 7 + [C.POINTER(C.c_int64)]),
@@ -411,16 +422,19 @@ class SummaryBuffers:
         return out
 
 
+def _dtype_code(dtype) -> int:
+    if dtype == np.float64:
+        return MCR_F64
+    if dtype == np.float32:
+        return MCR_F32
+    raise TypeError(f"unsupported dtype {dtype}; use float64 or float32")
+
+
 def tensor_args(draws: np.ndarray, layout: str):
     """(dtype code, C, N, P, stride_c, stride_n, stride_p) for a 3-D array whose axes are `layout`."""
     if draws.ndim != 3 or sorted(layout) != ["c", "n", "p"]:
         raise ValueError("draws must be 3-D and layout a permutation of 'cnp'")
-    if draws.dtype == np.float64:
-        code = MCR_F64
-    elif draws.dtype == np.float32:
-        code = MCR_F32
-    else:
-        raise TypeError(f"unsupported dtype {draws.dtype}; use float64 or float32")
+    code = _dtype_code(draws.dtype)
     ax = {a: i for i, a in enumerate(layout)}
     dims = [draws.shape[ax[a]] for a in "cnp"]
     strides = [draws.strides[ax[a]] // draws.itemsize for a in "cnp"]
@@ -578,6 +592,84 @@ def weighted_host(x, *, log_weights=None, weights=None, quantiles=(0.05, 0.5, 0.
     if return_weights:
         res["weights"] = w[:d.size]
     return res
+
+
+def tensor4_args(draws: np.ndarray, layout: str):
+    """(dtype code, S, C, N, P, stride_s, stride_c, stride_n, stride_p) for a 4-D array whose axes are `layout`, a
+    permutation of "scnp": simulations, chains, draws, parameters."""
+    if draws.ndim != 4 or sorted(layout) != ["c", "n", "p", "s"]:
+        raise ValueError("draws must be 4-D and layout a permutation of 'scnp'")
+    ax = {a: i for i, a in enumerate(layout)}
+    dims = [draws.shape[ax[a]] for a in "scnp"]
+    strides = [draws.strides[ax[a]] // draws.itemsize for a in "scnp"]
+    if any(s < 0 for s in strides):
+        raise ValueError("negative strides are not supported")
+    return (_dtype_code(draws.dtype), *dims, *strides)
+
+
+def thin_args(targs4, thin: int):
+    """The arguments of the same tensor with the draws n = 0, thin, 2 thin, ... of every chain: a larger stride_n."""
+    if int(thin) != thin or thin < 1:
+        raise ValueError("thin must be an integer >= 1")
+    code, S, C_, N, P, ss, sc, sn, sp = targs4
+    return (code, S, C_, -(-N // int(thin)), P, ss, sc, sn * int(thin), sp)
+
+
+def _sbc_arrays(S: int, P: int):
+    """The output arrays of a rank call (-1 / NaN until written) and the struct that points at them."""
+    shape = (max(S, 1), max(P, 1))
+    arrs = {"n_less": np.full(shape, -1, dtype=np.int64), "n_equal": np.full(shape, -1, dtype=np.int64),
+            "mean": np.full(shape, np.nan), "sd": np.full(shape, np.nan)}
+    out = Sbc(n_less=_as_ip(arrs["n_less"]), n_equal=_as_ip(arrs["n_equal"]), mean=_as_dp(arrs["mean"]), sd=_as_dp(arrs["sd"]))
+    return arrs, out
+
+
+def _truth_array(truth, S: int, P: int) -> np.ndarray:
+    t = np.ascontiguousarray(truth, dtype=np.float64)
+    if t.shape != (S, P):
+        raise ValueError(f"truth must be [S][P] = {(S, P)}; got {t.shape}")
+    return t
+
+
+def sbc_ranks_host(draws, truth) -> dict:
+    """mcr_sbc_ranks_host: the definition of Context.sbc_ranks on the host, without a GPU (the device's summation order:
+    the same bits).  draws [S][P][L], truth [S][P].  "n_less", "n_equal" (int64), "mean", "sd" [S][P] and the int
+    "n_draws" = L.  ValueError for a bad argument or a non-finite truth, McrError(MCR_ENONFINITE) for a non-finite draw."""
+    x = np.ascontiguousarray(draws, dtype=np.float64)
+    if x.ndim != 3:
+        raise ValueError("draws must be 3-D [S][P][L]")
+    S, P, L = x.shape
+    t = _truth_array(truth, S, P)
+    arrs, out = _sbc_arrays(S, P)
+    rc = load_library().mcr_sbc_ranks_host(_as_dp(x), S, P, L, _as_dp(t), C.byref(out))
+    if rc == MCR_ENONFINITE:
+        raise McrError(rc, "draws contain non-finite value(s)")
+    if rc != MCR_OK:
+        raise ValueError("mcr_sbc_ranks_host: bad argument or non-finite truth")
+    return {**{k: a[:S, :P] for k, a in arrs.items()}, "n_draws": int(L)}
+
+
+def chi2_sf(x: float, dof: float) -> float:
+    """mcr_chi2_sf: the upper tail probability of the chi-square distribution with dof degrees of freedom at x."""
+    return float(load_library().mcr_chi2_sf(float(x), float(dof)))
+
+
+def sbc_uniformity(ranks, n_draws: int, bins: int) -> dict:
+    """mcr_sbc_uniformity: ranks [S][P] in 0 .. n_draws -> "counts" [P][bins] (int64), "expected" [bins], "chi2", "pvalue"
+    (bins - 1 degrees of freedom) and "ecdf_dev" [P].  ValueError for a bad argument or a rank out of range."""
+    r = np.ascontiguousarray(ranks, dtype=np.int64)
+    if r.ndim != 2:
+        raise ValueError("ranks must be 2-D [S][P]")
+    S, P = r.shape
+    B = int(bins)
+    counts = np.zeros((max(P, 1), max(B, 1)), dtype=np.int64)
+    expected = np.full(max(B, 1), np.nan)
+    per = {k: np.full(max(P, 1), np.nan) for k in ("chi2", "pvalue", "ecdf_dev")}
+    rc = load_library().mcr_sbc_uniformity(_as_ip(r), S, P, int(n_draws), B, _as_ip(counts), _as_dp(expected),
+                                           *(_as_dp(per[k]) for k in ("chi2", "pvalue", "ecdf_dev")))
+    if rc != MCR_OK:
+        raise ValueError("mcr_sbc_uniformity: needs S >= 1, 2 <= bins <= n_draws + 1 and every rank in 0 .. n_draws")
+    return {"counts": counts[:P, :B], "expected": expected[:B], **{k: a[:P] for k, a in per.items()}}
 
 
 def _acf_arrays(P: int, nc: int, L: int):
@@ -824,6 +916,24 @@ class DeviceTensor:
     @property
     def shape_cnp(self):
         return self.targs[1:4]
+
+    def free(self):
+        self.buf.free()
+
+
+class DeviceSims:
+    """The draw tensors of S simulations resident in HBM (Context.upload_sims): device buffer + tensor4_args' nine entries
+    (dtype, S, C, N, P and their strides).  Only Context.sbc_ranks takes it; it is NOT a DeviceTensor, so that no call on
+    one (C, N, P) tensor can read the nine entries as seven."""
+
+    def __init__(self, ctx: "Context", buf, targs):
+        if len(targs) != 9:
+            raise ValueError("DeviceSims needs (dtype, S, C, N, P, stride_s, stride_c, stride_n, stride_p)")
+        self.ctx, self.buf, self.targs = ctx, buf, tuple(targs)
+
+    @property
+    def shape_scnp(self):
+        return self.targs[1:5]
 
     def free(self):
         self.buf.free()
@@ -1497,6 +1607,8 @@ class Context:
     def _tensor_call(self, draws, layout: str, name: str, pooled: bool):
         """(targs, pointer, entry, on_device) of a call mcr_<name> on a host array or, on_device, mcr_<name>_dev on a
         DeviceTensor.  A ragged tensor is, pooled, one chain of its pooled draws; otherwise it is refused."""
+        if isinstance(draws, DeviceSims):
+            raise ValueError(f"{name} takes one (C, N, P) tensor; a DeviceSims holds S of them (Context.sbc_ranks)")
         if not isinstance(draws, DeviceTensor):
             return tensor_args(draws, layout), draws.ctypes.data_as(C.c_void_p), getattr(self.lib, "mcr_" + name), False
         targs = draws.targs
@@ -1671,6 +1783,46 @@ class Context:
     def weighted_params_per_chunk(self, t: "DeviceTensor", nq: int = 3) -> int:
         """Parameters per workspace chunk of a weighted_summary call with nq quantiles on this tensor (mcr_weighted_plan)."""
         return self._params_per_chunk("mcr_weighted_plan", self._tensor_call(t, "pcn", "weighted_summary", True)[0], int(nq))
+
+    def upload_sims(self, draws: np.ndarray, layout: str = "spcn") -> DeviceSims:
+        """The draws of S simulations in HBM, for sbc_ranks: a 4-D C-contiguous array whose axes are `layout`."""
+        targs = tensor4_args(draws, layout)
+        if not draws.flags.c_contiguous:
+            raise ValueError("upload_sims() needs a C-contiguous array (permute the layout string instead)")
+        return DeviceSims(self, DeviceBuffer(self, max(draws.nbytes, 8)).upload(draws), targs)
+
+    def _sbc_call(self, draws, layout: str, thin: int):
+        """(thinned targs, pointer, entry) of a rank call on a 4-D host array or on the DeviceSims of S simulations."""
+        if isinstance(draws, DeviceTensor):
+            raise ValueError("sbc_ranks needs the DeviceSims of S simulations (Context.upload_sims), not one DeviceTensor")
+        if isinstance(draws, DeviceSims):
+            return thin_args(draws.targs, thin), draws.buf.ptr, self.lib.mcr_sbc_ranks_dev
+        return thin_args(tensor4_args(draws, layout), thin), draws.ctypes.data_as(C.c_void_p), self.lib.mcr_sbc_ranks
+
+    def sbc_ranks_rc(self, draws, truth, layout: str = "spcn", thin: int = 1) -> tuple[int, dict]:
+        """sbc_ranks with the library's return code beside the result instead of an exception: MCR_ENONFINITE leaves the
+        outputs written, a refusal leaves them as they were filled (-1 and NaN)."""
+        targs, ptr, fn = self._sbc_call(draws, layout, thin)
+        S, P = targs[1], targs[4]
+        t = _truth_array(truth, S, P)
+        arrs, out = _sbc_arrays(S, P)
+        rc = fn(self.handle, ptr, *targs, _as_dp(t), C.byref(out))
+        return rc, {**{k: a[:S, :P] for k, a in arrs.items()}, "n_draws": int(targs[2] * targs[3])}
+
+    def sbc_ranks(self, draws, truth, layout: str = "spcn", thin: int = 1) -> dict:
+        """Where every true value stands among its posterior draws, for S simulations at once (mcr_sbc_ranks: simulation-based
+        calibration).  draws: a 4-D host array whose axes are `layout`, a permutation of "scnp" (strided views included), or a
+        DeviceSims from upload_sims; truth [S][P].  thin = k takes the draws n = 0, k, 2k, ... of every chain.  [S][P]
+        arrays: "n_less" and "n_equal" (int64: the draws below the truth, and equal to it), "mean", "sd" (population) of the
+        L = C * ceil(N / k) pooled draws; and the int "n_draws" = L."""
+        rc, res = self.sbc_ranks_rc(draws, truth, layout, thin)
+        self._check(rc)
+        return res
+
+    def sbc_sims_per_chunk(self, draws, layout: str = "spcn", thin: int = 1) -> int:
+        """Simulations per workspace chunk of an sbc_ranks call on these draws (mcr_sbc_plan); all S where the call reads
+        the tensor in place."""
+        return self._params_per_chunk("mcr_sbc_plan", self._sbc_call(draws, layout, thin)[0])
 
     def autocorr(self, draws, layout: str = "cnp", max_lag=None, unbiased: bool = False, window_c: float = 5.0) -> dict:
         """Autocorrelation functions and integrated autocorrelation times of the raw draws (mcr_autocorr: ArviZ's autocorr,

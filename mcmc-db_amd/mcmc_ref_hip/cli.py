@@ -17,6 +17,8 @@ parameter and, with `--sliced K`, along K random directions of the joint distrib
 `hdi FILE` prints the highest-density interval(s) of every parameter: the shortest interval holding a share of the draws.
 `autocorr FILE` prints every parameter's integrated autocorrelation time (Sokal's window) and its stickiest and least
 sticky chain; as JSON, the autocorrelation function of every chain up to `--max-lag` as well.
+`sbc --truth TABLE FILE...` is simulation-based calibration: one draws file per simulated data set, the rank of each true
+value among its draws, and per parameter the uniformity of those ranks; exits 1 when `--p-min` is given and missed.
 """
 from __future__ import annotations
 
@@ -281,6 +283,38 @@ def weighted_summary_cmd(file: Path, log_weights: str | None, weights: str | Non
     click.echo(f"draws {res['n_draws']}  ess {res['ess']:.6g}" +
                (f"  khat {res['khat']:.3g} (threshold {res['khat_threshold']:.3g})" if "khat" in res else ""))
     _print_table(res["params"])
+
+
+@main.command("sbc")
+@click.argument("files", nargs=-1, required=True, type=click.Path(path_type=Path, exists=True, dir_okay=False))
+@click.option("--truth", "truth", required=True, type=click.Path(path_type=Path, exists=True, dir_okay=False),
+              help="CSV or Parquet table of the true values: one row per simulation, one column per parameter")
+@click.option("--thin", default=1, type=int, help="Keep every K-th draw of a simulation (default: 1)")
+@click.option("--bins", default=None, type=int, help="Bins of the rank histogram (default: a divisor of draws + 1, at most 20)")
+@click.option("--p-min", default=None, type=float, help="Fail (exit 1) when a parameter's chi-square p-value is below this")
+@click.option("--params", default=None, help="Comma-separated parameter list")
+@click.option("--format", "format_", type=click.Choice(["table", "json"], case_sensitive=False), default="table")
+def sbc_cmd(files: tuple[Path, ...], truth: Path, thin: int, bins: int | None, p_min: float | None, params: str | None,
+            format_: str) -> None:
+    """Simulation-based calibration (no counterpart in the reference): FILES are the draws of one fit each, in the order of
+    the rows of --truth.  Per parameter: the chi-square statistic of the rank histogram with its degrees of freedom and
+    p-value, the largest ECDF deviation, the mean |z| and the mean posterior contraction."""
+    from . import sbc as sbc_mod
+
+    try:
+        res = sbc_mod.sbc_files(files, truth, params=params.split(",") if params else None, thin=thin, bins=bins, p_min=p_min)
+    except (ValueError, KeyError, IndexError) as exc:
+        raise click.ClickException(str(exc)) from exc
+    if format_ == "json":
+        click.echo(json.dumps({"simulations": int(res.ranks.shape[0]), "draws": res.n_draws, "bins": res.bins, "ties": res.n_tied,
+                               "params": res.table(), "failures": list(res.failures)}, indent=2, sort_keys=True))
+    else:
+        click.echo(f"simulations {res.ranks.shape[0]}  draws {res.n_draws}  bins {res.bins}  ties {res.n_tied}")
+        _print_table(res.table())
+        for line in res.failures:
+            click.echo(f"- {line}")
+    if not res.passed:
+        raise SystemExit(1)
 
 
 @main.command("autocorr")
