@@ -16,8 +16,28 @@ def ctx():
     return _ffi.default_context()
 
 
-def test_two_sample_matches_scipy(ctx):
+def assert_two_sample_matches_scipy(ks, w1, ref, act, what=()):
+    """(ks, w1) of ref [P][Mr], act [P][Ma] against scipy, parameter by parameter (tests/call_families.py shares this gate)."""
     from scipy.stats import ks_2samp, wasserstein_distance
+    P, Mr, Ma = ref.shape[0], ref.shape[1], act.shape[1]
+    for p in range(P):
+        exact = ks_2samp(ref[p], act[p], method="exact" if max(Mr, Ma) <= 10000 else "asymp").statistic
+        if max(Mr, Ma) <= 10000:
+            assert ks[p] == exact, (*what, P, Mr, Ma, p)      # scipy's exact mode returns the same rational
+        else:
+            assert ks[p] == pytest.approx(exact, rel=1e-13)   # asymp mode: float CDF differences
+        assert w1[p] == pytest.approx(wasserstein_distance(ref[p], act[p]), rel=1e-12, abs=1e-15)
+
+
+def assert_covariance_matches_numpy(cov, x, what=()):
+    """cov [P][P] of x [P][M] against np.cov (tests/call_families.py shares this gate)."""
+    P = x.shape[0]
+    exp = np.cov(x, ddof=0).reshape(P, P)
+    assert np.allclose(cov, exp, rtol=1e-10, atol=1e-12 * np.abs(exp).max()), (*what, P, x.shape[1])
+    assert np.allclose(cov, cov.T, rtol=1e-12, atol=0)
+
+
+def test_two_sample_matches_scipy(ctx):
     rng = np.random.default_rng(4)
     from mcmc_ref_hip import _ffi
     cases = [(3, 10000, 4000), (2, 5000, 5000), (4, 37, 41), (1, 1, 1), (2, 70000, 9000), (1, 4096, 8192),
@@ -32,13 +52,7 @@ def test_two_sample_matches_scipy(ctx):
                 ks, w1 = fresh.two_sample(ref, act)
         else:
             ks, w1 = ctx.two_sample(ref, act)
-        for p in range(P):
-            exact = ks_2samp(ref[p], act[p], method="exact" if max(Mr, Ma) <= 10000 else "asymp").statistic
-            if max(Mr, Ma) <= 10000:
-                assert ks[p] == exact, (P, Mr, Ma, p)            # scipy's exact mode returns the same rational
-            else:
-                assert ks[p] == pytest.approx(exact, rel=1e-13)   # asymp mode: float CDF differences
-            assert w1[p] == pytest.approx(wasserstein_distance(ref[p], act[p]), rel=1e-12, abs=1e-15)
+        assert_two_sample_matches_scipy(ks, w1, ref, act)
     same = rng.normal(size=(2, 1000))
     ks, w1 = ctx.two_sample(same, same)
     assert np.all(ks == 0.0) and np.all(w1 == 0.0)
@@ -61,10 +75,7 @@ def test_covariance_mfma_matches_numpy(ctx):
     for P, M in [(1, 10), (5, 1000), (16, 4096), (33, 10001), (65, 77), (130, 3001), (100, 40000)]:
         L = rng.normal(size=(P, P))
         x = (L @ rng.normal(size=(P, M))) * 1e-2 + rng.normal(size=(P, 1)) * 50.0   # correlated, offset means
-        cov = ctx.covariance(x)
-        exp = np.cov(x, ddof=0).reshape(P, P)
-        assert np.allclose(cov, exp, rtol=1e-10, atol=1e-12 * np.abs(exp).max()), (P, M)
-        assert np.allclose(cov, cov.T, rtol=1e-12, atol=0)
+        assert_covariance_matches_numpy(ctx.covariance(x), x)
     draws, params, rec = load_model("eight_schools-eight_schools_noncentered")
     x = draws.reshape(len(params), -1)
     cov = ctx.covariance(x)

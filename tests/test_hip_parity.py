@@ -218,19 +218,28 @@ def test_constant_halves_of_a_chain_that_is_not_constant(ctx, oracle):
     assert np.isinf(oracle.summarize(x, "pcn", min_chains=2)["rhat"][0])
 
 
+def check_basic_stats(out, exp):
+    """A basic_stats result against the recorded or the oracle's one (tests/call_families.py shares this gate)."""
+    assert close(out["mean"], exp["mean"], 1e-12, scale=1e-12 * (exp["std"] if exp["std"] == exp["std"] else 0))
+    assert close(out["std"], exp["std"], 1e-12)
+
+
+def check_compare(rel, ok, exp_rel, exp_ok):
+    """A compare result against the recorded or the oracle's one: the relative errors exactly, the verdicts equal."""
+    assert len(rel) == len(ok) == len(exp_rel) == len(exp_ok)
+    for j in range(len(exp_rel)):
+        assert close(rel[j], exp_rel[j], 0.0) and bool(ok[j]) == bool(exp_ok[j]), (j, rel[j], exp_rel[j], ok[j], exp_ok[j])
+
+
 def test_basic_stats_and_compare(ctx, oracle):
     g = load_json("compare_cases.json")
     for rec in g["basic"]:
-        out = ctx.basic_stats(rec["values"])
-        exp = rec["out"]
-        assert close(out["mean"], exp["mean"], 1e-12, scale=1e-12 * (exp["std"] if exp["std"] == exp["std"] else 0))
-        assert close(out["std"], exp["std"], 1e-12)
+        check_basic_stats(ctx.basic_stats(rec["values"]), rec["out"])
     for rec in g["compare"]:
         for p, ms in rec["details"].items():
             names = list(ms)
             rel, ok = ctx.compare([ms[m]["ref"] for m in names], [ms[m]["actual"] for m in names], rec["tolerance"])
-            for j, m in enumerate(names):
-                assert close(rel[j], ms[m]["rel_error"], 0.0) and bool(ok[j]) == ms[m]["passed"]
+            check_compare(rel, ok, [ms[m]["rel_error"] for m in names], [ms[m]["passed"] for m in names])
     v = np.random.default_rng(3).normal(100.0, 1e-3, size=1_000_003)
     out, exp = ctx.basic_stats(v), oracle.basic_stats(v)
     assert close(out["mean"], exp["mean"], 1e-12) and close(out["std"], exp["std"], 1e-9)

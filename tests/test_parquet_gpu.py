@@ -37,8 +37,12 @@ def bits(a):
 
 def check_roundtrip(ctx, img: bytes, columns=None):
     from mcmc_ref_hip.parquet import read_columns
+    return assert_equals_pyarrow(read_columns(ctx, img, columns), img, columns)
+
+
+def assert_equals_pyarrow(got: dict, img: bytes, columns=None):
+    """What read_columns gave for the image against pyarrow's reading of it, in bits (tests/call_families.py shares this gate)."""
     t = pq.read_table(io.BytesIO(img))
-    got = read_columns(ctx, img, columns)
     names = columns if columns is not None else [f.name for f in t.schema if pa.types.is_integer(f.type) or
                                                  pa.types.is_floating(f.type)]
     assert list(got) == list(names)

@@ -113,8 +113,14 @@ def test_ranks_and_z_of_every_draw(ctx, oracle, M, kind):
     ms = (time.perf_counter() - t0) * 1e3
     print(f"\n{what}: {ms:.1f} ms; median {got['median']!r} rhat {got['rhat']!r} ess {got['ess_bulk']!r} / {got['ess_tail']!r} "
           f"lags {got['lag_bulk']} / {got['lag_tail']}")
+    check_diagnosis(got, x, chains, oracle, what)
+
+
+def check_diagnosis(got, x, chains, oracle, what):
+    """A diagnose_chains(debug=True) result of the pooled draws x in `chains`: the per-draw gate, the statistics against the
+    oracle up to ORACLE_MAX_M pooled draws, and last the median in bits (tests/call_families.py shares this gate)."""
     med = check_ranks_and_z(got, x, what)
-    if M <= ORACLE_MAX_M:
+    if len(x) <= ORACLE_MAX_M:
         exp = oracle.diag(chains, 2)
         print(f"{what}: oracle rhat {exp['rhat']!r} ess {exp['ess_bulk']!r} / {exp['ess_tail']!r} lags {exp['lag_bulk']} / "
               f"{exp['lag_tail']}")

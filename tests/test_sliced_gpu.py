@@ -75,15 +75,19 @@ def check_projection(ctx, P, Mr, Ma, K, seed):
     ref, act, W, center = offset_case(P, Mr, Ma, K, seed)
     ks, w1, zr, za = ctx.sliced_two_sample(ref, act, W, center, projections=True)
     assert zr.shape == (K, Mr) and za.shape == (K, Ma) and ks.shape == w1.shape == (K,)
+    return max(projection_error(X, W, center, z, (P, Mr, Ma, K)) for X, z in ((ref, zr), (act, za)))
+
+
+def projection_error(X, W, center, z, what=()) -> float:
+    """The projected rows z [K][M] of X [P][M] inside the derived bound of the 80-bit reference; the worst |err| / bound
+    (tests/call_families.py shares this gate)."""
+    P = X.shape[0]
     gamma = (P + 2) * EPS / (1 - (P + 2) * EPS)
-    worst = 0.0
-    for X, z in ((ref, zr), (act, za)):
-        want, mag = longdouble_projection(X, W, center)
-        err, bound = np.abs(z.astype(np.longdouble) - want), gamma * mag
-        bad = np.argwhere(~(err <= bound))
-        assert len(bad) == 0, (P, Mr, Ma, K, "first (k, m):", bad[:5])
-        worst = max(worst, float((err[bound > 0] / bound[bound > 0]).max()) if (bound > 0).any() else 0.0)
-    return worst
+    want, mag = longdouble_projection(X, W, center)
+    err, bound = np.abs(z.astype(np.longdouble) - want), gamma * mag
+    bad = np.argwhere(~(err <= bound))
+    assert len(bad) == 0, (*what, "first (k, m):", bad[:5])
+    return float((err[bound > 0] / bound[bound > 0]).max()) if (bound > 0).any() else 0.0
 
 
 # ---- the projection against an 80-bit reference ------------------------------------------------------------------------
