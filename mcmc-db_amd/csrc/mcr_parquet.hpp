@@ -14,6 +14,8 @@
 // Supported (everything the packaged corpus and pyarrow's default writer produce for flat numeric tables):
 // flat schemas, REQUIRED / OPTIONAL columns without nulls, DOUBLE / FLOAT / INT32 / INT64, UNCOMPRESSED / SNAPPY,
 // data pages v1 and v2, dictionary fallback to PLAIN inside a column chunk, any number of row groups and pages.
+// Definition levels are read in the RLE / bit-packed hybrid only: a v1 page of an OPTIONAL column that declares the
+// deprecated BIT_PACKED level encoding is refused in open().
 // Everything else fails the call with a message naming the feature -- never a partial answer.
 #pragma once
 #include "mcr_device.hpp"
@@ -99,6 +101,7 @@ struct Page {              // host view of a page
     u64 payload_off;       // file offset of the bytes after the page header
     u32 comp_size, uncomp_size, num_values;
     u32 rep_bytes = 0, def_bytes = 0; bool v2_compressed = true;
+    int def_encoding = ENC_RLE;   // v1 data pages: DataPageHeader.definition_level_encoding
     u64 row_off = 0;       // data pages: first row of the page within the column
     int dict = -1;         // data pages: index (into `pages`) of the chunk's dictionary page
     u32 dict_count = 0;
@@ -183,6 +186,7 @@ inline bool parse_page_header(File& f, u64 off, Page& pg)
                 if (id == 5 || id == 7) {                 // DataPageHeader / DictionaryPageHeader
                     if (sid == 1 && st == 5) pg.num_values = (u32)t.zigzag();
                     else if (sid == 2 && st == 5) pg.encoding = (int)t.zigzag();
+                    else if (id == 5 && sid == 3 && st == 5) pg.def_encoding = (int)t.zigzag();
                     else t.skip(st);
                 } else {                                  // DataPageHeaderV2
                     if (sid == 1 && st == 5) pg.num_values = (u32)t.zigzag();
@@ -276,6 +280,13 @@ inline bool open(File& f, const void* bytes, size_t len)
                 else if (pg.kind == PAGE_DATA || pg.kind == PAGE_DATA_V2) {
                     pg.row_off = rows_done[c] + (u64)seen; pg.dict = dict; pg.dict_count = dict_count;
                     seen += pg.num_values;
+                    // v1 levels are decoded as a 4-byte length + RLE / bit-packed hybrid; the deprecated BIT_PACKED
+                    // encoding has no length prefix and would be misread (a REQUIRED column carries no levels at all)
+                    if (pg.kind == PAGE_DATA && f.cols[c].max_def > 0 && pg.def_encoding != ENC_RLE)
+                        return fail(f, "column '" + f.cols[c].name + "' has definition levels in " +
+                                       (pg.def_encoding == ENC_BIT_PACKED ? std::string("the deprecated BIT_PACKED encoding")
+                                                                          : "encoding " + std::to_string(pg.def_encoding)) +
+                                       "; only RLE levels are decoded");
                     if (pg.kind == PAGE_DATA_V2 && (u64)pg.rep_bytes + pg.def_bytes > pg.comp_size) return fail(f, "v2 level bytes exceed the page");
                 } else return fail(f, "unknown page type " + std::to_string(pg.kind));
                 f.pages.push_back(pg); ++ch.n_pages;

@@ -82,6 +82,7 @@ def mixed_table(n=6000, seed=3):
     dict(data_page_size=2048, write_batch_size=64),
     dict(data_page_size=1500, write_batch_size=32, row_group_size=1700, data_page_version="2.0"),
     dict(use_dictionary=["ties", "runs"], compression={"x": "none", "ties": "snappy"}),
+    dict(version="1.0"),                                         # PLAIN_DICTIONARY (encoding 2) on dictionary and data pages
 ])
 def test_roundtrip_writer_options(ctx, kw):
     check_roundtrip(ctx, image(mixed_table(), **kw))
