@@ -19,6 +19,7 @@ import math
 import os
 import threading
 import time
+import typing
 from pathlib import Path
 
 import numpy as np
@@ -708,14 +709,14 @@ def autocorr_host(chains, max_lag=None, unbiased: bool = False, window_c: float 
     return _acf_result(arrs, 1, nc, N, L)
 
 
-class PqImage:
-    """A Parquet file image the library owns (mcr_pq_image): `view` is its bytes without a copy, valid until close()."""
+class Image:
+    """Bytes the library owns (an mcr_pq_image or an mcr_text_image): `view` is its bytes without a copy, valid until
+    close().  `data`, `size` and `free` are the three library functions of its kind."""
 
-    def __init__(self, lib, handle):
-        self.lib, self.handle = lib, handle
-        self.size = int(lib.mcr_pq_image_size(handle))
-        self.pages = int(lib.mcr_pq_image_pages(handle))
-        self.view = memoryview((C.c_ubyte * self.size).from_address(lib.mcr_pq_image_data(handle))).cast("B")
+    def __init__(self, handle, data, size, free):
+        self.handle, self._free = handle, free
+        self.size = int(size(handle))
+        self.view = memoryview((C.c_ubyte * self.size).from_address(data(handle))).cast("B") if self.size else memoryview(b"")
 
     def tobytes(self) -> bytes:
         return self.view.tobytes()
@@ -727,7 +728,7 @@ class PqImage:
         if self.handle:
             self.view.release()
             self.view = None
-            self.lib.mcr_pq_image_free(self.handle)
+            self._free(self.handle)
             self.handle = None
 
     def __enter__(self):
@@ -743,39 +744,16 @@ class PqImage:
             pass
 
 
-class TextImage:
-    """A text image the library owns (mcr_text_image): `view` is its bytes without a copy, valid until close()."""
+def PqImage(lib, handle) -> Image:
+    """A Parquet file image the library owns (mcr_pq_image); `pages` counts its pages."""
+    image = Image(handle, lib.mcr_pq_image_data, lib.mcr_pq_image_size, lib.mcr_pq_image_free)
+    image.pages = int(lib.mcr_pq_image_pages(handle))
+    return image
 
-    def __init__(self, lib, handle):
-        self.lib, self.handle = lib, handle
-        self.size = int(lib.mcr_text_image_size(handle))
-        data = lib.mcr_text_image_data(handle)
-        self.view = memoryview((C.c_ubyte * self.size).from_address(data)).cast("B") if self.size else memoryview(b"")
 
-    def tobytes(self) -> bytes:
-        return self.view.tobytes()
-
-    def __len__(self):
-        return self.size
-
-    def close(self):
-        if self.handle:
-            self.view.release()
-            self.view = None
-            self.lib.mcr_text_image_free(self.handle)
-            self.handle = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):  # pragma: no cover - best effort
-        try:
-            self.close()
-        except Exception:
-            pass
+def TextImage(lib, handle) -> Image:
+    """A text image the library owns (mcr_text_image)."""
+    return Image(handle, lib.mcr_text_image_data, lib.mcr_text_image_size, lib.mcr_text_image_free)
 
 
 def _pq_columns(columns, host: bool):
@@ -837,7 +815,18 @@ def format_double(v: float) -> str:
     return buf.raw[:n.value].decode()
 
 
-class DeviceBuffer:
+class _Owner:
+    """An owner of device memory is a context manager: leaving the `with` calls free(), and free() may be called again.
+    A function that hands its allocation on enters it into a contextlib.ExitStack and ends with pop_all()."""
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+
+class DeviceBuffer(_Owner):
     def __init__(self, ctx: "Context", nbytes: int):
         self.ctx, self.nbytes = ctx, nbytes
         self.ptr = C.c_void_p()
@@ -862,13 +851,14 @@ class DeviceBuffer:
             self.ptr = C.c_void_p()
 
 
-class DeviceArena:
+class DeviceArena(_Owner):
     """One device allocation shared by the models of a batch (hipMalloc / hipFree cost ~0.1 ms each, which
-    would dominate a 57-file corpus pass); freed when the last view is."""
+    would dominate a 57-file corpus pass).  Its maker holds it until free() -- the end of the maker's `with` -- and every
+    view holds it too: the buffer is freed with the last of them, at once when no view is left."""
 
     def __init__(self, ctx, nbytes: int):
         self.buf = DeviceBuffer(ctx, max(nbytes, 8))
-        self.refs = 0
+        self.refs, self.held = 1, True
 
     def view(self, offset: int, nbytes: int) -> "DeviceView":
         self.refs += 1
@@ -879,8 +869,13 @@ class DeviceArena:
         if self.refs <= 0:
             self.buf.free()
 
+    def free(self):
+        if self.held:
+            self.held = False
+            self.release()
 
-class DeviceView:
+
+class DeviceView(_Owner):
     """Slice of an arena with DeviceBuffer's interface (ptr / download / free)."""
 
     def __init__(self, arena: DeviceArena, offset: int, nbytes: int):
@@ -904,7 +899,7 @@ class DeviceView:
             self.ptr = C.c_void_p()
 
 
-class DeviceTensor:
+class DeviceTensor(_Owner):
     """A draw tensor resident in HBM: device buffer + the (dtype, dims, strides) it was uploaded with.
 
     chain_off (int64, C + 1 offsets) marks f64 draws [P][M] whose chains differ in length (Context.ragged_tensor): the
@@ -921,7 +916,7 @@ class DeviceTensor:
         self.buf.free()
 
 
-class DeviceSims:
+class DeviceSims(_Owner):
     """The draw tensors of S simulations resident in HBM (Context.upload_sims): device buffer + tensor4_args' nine entries
     (dtype, S, C, N, P and their strides).  Only Context.sbc_ranks takes it; it is NOT a DeviceTensor, so that no call on
     one (C, N, P) tensor can read the nine entries as seven."""
@@ -937,6 +932,21 @@ class DeviceSims:
 
     def free(self):
         self.buf.free()
+
+
+class CsvTable(typing.NamedTuple):
+    """One file of Context.csv_table_decode.  close() frees the slices."""
+    names: list            # parameter names in file order, without `chain` / `draw`
+    values: DeviceView     # [P][M] f64 in file row order
+    all_int: np.ndarray    # [P] bool: every literal of the column is an integer
+    ids: tuple             # (chain, draw) as int64 DeviceViews of M entries, None for an absent column
+    hard: int              # fields finished on the host
+    header: list           # every column name of the file
+
+    def close(self):
+        for b in (self.values, *self.ids):
+            if b is not None:
+                b.free()
 
 
 class Context:
@@ -984,7 +994,9 @@ class Context:
         targs = tensor_args(draws, layout)
         if not draws.flags.c_contiguous:
             raise ValueError("upload() needs a C-contiguous array (permute the layout string instead)")
-        buf = DeviceBuffer(self, max(draws.nbytes, 8)).upload(draws)
+        with contextlib.ExitStack() as stack:
+            buf = stack.enter_context(DeviceBuffer(self, max(draws.nbytes, 8))).upload(draws)
+            stack.pop_all()
         return DeviceTensor(self, buf, targs)
 
     def alloc_tensor(self, C_: int, N: int, P: int, dtype=np.float64) -> DeviceTensor:
@@ -1071,27 +1083,23 @@ class Context:
         call) or a DeviceTensor of ragged_tensor (then `counts` is not needed).  The result is shaped like
         summarize()'s: pooled mean / std / q / median, and the diagnostics of diagnostics.py for ragged chains."""
         qs = self._quantiles(quantiles)
-        owned = None
-        if isinstance(draws, DeviceTensor):
-            t = draws if draws.chain_off is not None else self.ragged_tensor(draws.buf, counts, draws.targs[3])
-        else:
-            x = np.ascontiguousarray(draws, dtype=np.float64)
-            if x.ndim != 2:
-                raise ValueError("draws must be 2-D [P][M]")
-            if int(np.sum(counts)) != x.shape[1]:
-                raise ValueError("counts must add up to the number of draws per parameter")
-            owned = DeviceBuffer(self, max(x.nbytes, 8))
-            if x.nbytes:
-                owned.upload(x)
-            t = self.ragged_tensor(owned, counts, x.shape[0])
-        try:
+        with contextlib.ExitStack() as stack:
+            if isinstance(draws, DeviceTensor):
+                t = draws if draws.chain_off is not None else self.ragged_tensor(draws.buf, counts, draws.targs[3])
+            else:
+                x = np.ascontiguousarray(draws, dtype=np.float64)
+                if x.ndim != 2:
+                    raise ValueError("draws must be 2-D [P][M]")
+                if int(np.sum(counts)) != x.shape[1]:
+                    raise ValueError("counts must add up to the number of draws per parameter")
+                owned = stack.enter_context(DeviceBuffer(self, max(x.nbytes, 8)))
+                if x.nbytes:
+                    owned.upload(x)
+                t = self.ragged_tensor(owned, counts, x.shape[0])
             bufs = SummaryBuffers(t.targs[3], qs.size, diagnostics)
             self._check(self.lib.mcr_summarize_chains_dev(self.handle, t.buf.ptr, t.targs[6], _as_ip(t.chain_off),
                                                           t.targs[1], t.targs[3], int(min_chains), _as_dp(qs), qs.size,
                                                           C.byref(bufs.struct)))
-        finally:
-            if owned is not None:
-                owned.free()
         return bufs.result()
 
     def chain_layout(self, chain_ptr, draw_ptr, M: int, cap: int = 256, order: "DeviceBuffer | None" = None):
@@ -1099,21 +1107,19 @@ class Context:
         DeviceBuffer of M int64 row numbers in np.lexsort((draw, chain)) order -- the caller's `order` buffer (at least
         8 M bytes) or, without one, a new buffer the caller frees -- or None when the rows are in that order already.
         None when the library declines (MCR_EFALLBACK: no 64-bit row key) -- sort on the host then."""
-        mine = order is None
-        if mine:
-            order = DeviceBuffer(self, max(int(M) * 8, 8))
-        ids, counts = np.zeros(max(cap, 1), dtype=np.int64), np.zeros(max(cap, 1), dtype=np.int64)
-        n, in_order = C.c_int(0), C.c_int(0)
-        rc = self.lib.mcr_chain_layout_dev(self.handle, chain_ptr, draw_ptr, int(M), order.ptr, _as_ip(ids), _as_ip(counts),
-                                           int(cap), C.byref(n), C.byref(in_order))
-        if rc != MCR_OK or in_order.value:
-            if mine:
-                order.free()
-            order = None
-        if rc == MCR_EFALLBACK:
-            return None
-        self._check(rc)
-        return ids[:n.value].copy(), order, counts[:n.value].copy()
+        with contextlib.ExitStack() as stack:                # a buffer made here is handed on only with a row order in it
+            if order is None:
+                order = stack.enter_context(DeviceBuffer(self, max(int(M) * 8, 8)))
+            ids, counts = np.zeros(max(cap, 1), dtype=np.int64), np.zeros(max(cap, 1), dtype=np.int64)
+            n, in_order = C.c_int(0), C.c_int(0)
+            rc = self.lib.mcr_chain_layout_dev(self.handle, chain_ptr, draw_ptr, int(M), order.ptr, _as_ip(ids), _as_ip(counts),
+                                               int(cap), C.byref(n), C.byref(in_order))
+            if rc == MCR_EFALLBACK:
+                return None
+            self._check(rc)
+            if not in_order.value:
+                stack.pop_all()
+            return ids[:n.value].copy(), None if in_order.value else order, counts[:n.value].copy()
 
     def chain_layout_many(self, tables, cap: int = 256) -> list:
         """The in-order test of many tables in one round trip (mcr_chain_layout_many_dev): tables = [(chain pointer,
@@ -1143,35 +1149,29 @@ class Context:
         (device pointer or buffer, count) -- what select_rows returns -- or int64 values in host memory, uploaded
         here.  header: "quoted" (pyarrow's default), "plain" or "none".  Close the image to free its pinned memory."""
         arr, _keep = _pq_columns(columns, host=False)
-        own, ptr, n = None, None, 0
-        if row_index is not None and isinstance(row_index, tuple):
-            ptr, n = row_index
-            ptr = getattr(ptr, "ptr", ptr)
-        elif row_index is not None:
-            idx = np.ascontiguousarray(row_index, dtype=np.int64)
-            own = DeviceBuffer(self, max(idx.nbytes, 8)).upload(idx)
-            ptr, n = own.ptr, idx.size
-        h = C.c_void_p()
-        try:
+        ptr, n = None, 0
+        with contextlib.ExitStack() as stack:
+            if row_index is not None and isinstance(row_index, tuple):
+                ptr, n = row_index
+                ptr = getattr(ptr, "ptr", ptr)
+            elif row_index is not None:
+                idx = np.ascontiguousarray(row_index, dtype=np.int64)
+                ptr, n = stack.enter_context(DeviceBuffer(self, max(idx.nbytes, 8))).upload(idx).ptr, idx.size
+            h = C.c_void_p()
             self._check(self.lib.mcr_csv_write_dev(self.handle, arr, len(columns), int(rows), ptr, int(n), CSV_HEADERS[header],
                                                    C.byref(h)))
-        finally:
-            if own is not None:
-                own.free()
         return TextImage(self.lib, h)
 
     def select_rows(self, chain_ptr, M: int, chains) -> tuple:
         """mcr_select_rows_dev: (device buffer of int64 row indices, count) of the rows of the device int64 column
         `chain_ptr[0 .. M)` whose value is in `chains`, in order: the row_index of write_csv.  Free the buffer."""
         want = np.ascontiguousarray(list(chains), dtype=np.int64)
-        out = DeviceBuffer(self, max(int(M) * 8, 8))
         n = C.c_int64()
-        try:
+        with contextlib.ExitStack() as stack:
+            out = stack.enter_context(DeviceBuffer(self, max(int(M) * 8, 8)))
             self._check(self.lib.mcr_select_rows_dev(self.handle, getattr(chain_ptr, "ptr", chain_ptr), int(M), _as_ip(want), want.size,
                                                      out.ptr, C.byref(n)))
-        except BaseException:
-            out.free()
-            raise
+            stack.pop_all()
         return out, int(n.value)
 
     def gather_rows_order(self, src_ptr, P: int, M: int, order_ptr, dst_ptr):
@@ -1266,31 +1266,29 @@ class Context:
             self._check(L.mcr_csv_stage(self.handle, hs, n, _as_ip(rows)))
             t2 = time.perf_counter()
             N, P = int(rows.min()), len(names)
-            t = self.alloc_tensor(n, N, P)
             hard = C.c_int64(0)
-            try:
+            with contextlib.ExitStack() as stack:
+                t = stack.enter_context(self.alloc_tensor(n, N, P))
                 self._check(L.mcr_csv_decode(self.handle, cols.ctypes.data_as(C.POINTER(C.c_int)), P, N, t.buf.ptr,
                                              N, 1, n * N, C.byref(hard)))
-            except Exception:
-                t.free()
-                raise
-            if phases is not None:
-                t3 = time.perf_counter()
-                phases.update(read_upload_ms=(t1 - t0) * 1e3, index_ms=(t2 - t1) * 1e3, parse_finish_ms=(t3 - t2) * 1e3,
-                              text_bytes=sum(os.path.getsize(p) for p in paths), hard=int(hard.value))
-            return names, t, int(hard.value)
+                if phases is not None:
+                    t3 = time.perf_counter()
+                    phases.update(read_upload_ms=(t1 - t0) * 1e3, index_ms=(t2 - t1) * 1e3, parse_finish_ms=(t3 - t2) * 1e3,
+                                  text_bytes=sum(os.path.getsize(p) for p in paths), hard=int(hard.value))
+                stack.pop_all()
+                return names, t, int(hard.value)
         finally:
             for h in hs[:n]:
                 if h:
                     L.mcr_csv_close(h)
 
     def csv_table_decode(self, paths, phases: dict | None = None):
-        """Table CSVs -> per file (parameter names in file order without `chain` / `draw`, [P][M] f64 DeviceView in file
+        """Table CSVs -> per file a CsvTable (parameter names in file order without `chain` / `draw`, [P][M] f64 DeviceView in file
         row order, all_int flags [P], (chain ids, draw ids) as int64 DeviceViews of M entries or None for an absent
         column, fields finished on the host, header names): ONE read (mcr_csv_open_table_paths), one line index
         (mcr_csv_stage) and one parse (mcr_csv_decode_table) for all files.  None when the host reader must decide for
         one of them: the library answers MCR_EFALLBACK or a header is not UTF-8 (`phases["fallback"]` says why).
-        `phases` receives the host clock of the three calls (ms).  Free every slice."""
+        `phases` receives the host clock of the three calls (ms).  Close every entry."""
         L, n = self.lib, len(paths)
         note = phases if phases is not None else {}
         arr = (C.c_char_p * max(n, 1))(*[os.fsencode(p) for p in paths])
@@ -1326,36 +1324,27 @@ class Context:
                 ids[f] = [h.index("chain") if "chain" in h else -1, h.index("draw") if "draw" in h else -1]
             all_int = np.zeros((max(n, 1), max(Pmax, 1)), dtype=np.uint8)
             sizes = [len(params[f]) * int(rows[f]) * 8 for f in range(n)]
-            out = DeviceArena(self, sum(sizes))
-            idb = DeviceArena(self, 2 * int(rows[:n].sum()) * 8)
             hard = C.c_int64(0)
-            try:
-                fell = declined(L.mcr_csv_decode_table(self.handle, cols.ctypes.data_as(C.POINTER(C.c_int)), cols.shape[1],
-                                                       ids.ctypes.data_as(C.POINTER(C.c_int)), int(rows.max()), out.buf.ptr, 0, 1, 0,
-                                                       idb.buf.ptr, all_int.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(hard)))
-            except BaseException:
-                out.buf.free()
-                idb.buf.free()
-                raise
-            if fell or n == 0:
-                out.buf.free()
-                idb.buf.free()
-                return None if fell else []
-            got, off, ioff = [], 0, 0
-            for f in range(n):
-                M, P = int(rows[f]), len(params[f])
-                pair = [idb.view((ioff + w * M) * 8, M * 8) if ids[f, w] >= 0 else None for w in range(2)]
-                got.append(([heads[f][c] for c in params[f]], out.view(off, sizes[f]),
-                            all_int[f, :P].astype(bool), tuple(pair), int(hard.value), heads[f]))
-                off += sizes[f]
-                ioff += 2 * M
-            if idb.refs == 0:
-                idb.buf.free()
-            if phases is not None:
-                t3 = time.perf_counter()
-                phases.update(read_upload_ms=(t1 - t0) * 1e3, index_ms=(t2 - t1) * 1e3, parse_finish_ms=(t3 - t2) * 1e3,
-                              text_bytes=sum(os.path.getsize(p) for p in paths), hard=int(hard.value))
-            return got
+            with contextlib.ExitStack() as stack, DeviceArena(self, sum(sizes)) as out, \
+                    DeviceArena(self, 2 * int(rows[:n].sum()) * 8) as idb:
+                if declined(L.mcr_csv_decode_table(self.handle, cols.ctypes.data_as(C.POINTER(C.c_int)), cols.shape[1],
+                                                   ids.ctypes.data_as(C.POINTER(C.c_int)), int(rows.max()), out.buf.ptr, 0, 1, 0,
+                                                   idb.buf.ptr, all_int.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(hard))):
+                    return None
+                got, off, ioff = [], 0, 0
+                for f in range(n):                           # the slices are the caller's; the arenas live as long as they do
+                    M, P = int(rows[f]), len(params[f])
+                    pair = [stack.enter_context(idb.view((ioff + w * M) * 8, M * 8)) if ids[f, w] >= 0 else None for w in range(2)]
+                    got.append(CsvTable([heads[f][c] for c in params[f]], stack.enter_context(out.view(off, sizes[f])),
+                                        all_int[f, :P].astype(bool), tuple(pair), int(hard.value), heads[f]))
+                    off += sizes[f]
+                    ioff += 2 * M
+                if phases is not None and n:
+                    t3 = time.perf_counter()
+                    phases.update(read_upload_ms=(t1 - t0) * 1e3, index_ms=(t2 - t1) * 1e3, parse_finish_ms=(t3 - t2) * 1e3,
+                                  text_bytes=sum(os.path.getsize(p) for p in paths), hard=int(hard.value))
+                stack.pop_all()
+                return got
         finally:
             for h in hs[:n]:
                 if h:
@@ -1392,22 +1381,22 @@ class Context:
             P = len(names)
             arrays = np.ascontiguousarray(arrays, dtype=np.intc).reshape(n, P)
             t1 = time.perf_counter()
-            t = self.alloc_tensor(n, N, P)
             hard = C.c_int64(0)
             all_int = np.zeros((n, max(P, 1)), dtype=np.uint8)
-            rc = L.mcr_json_decode(self.handle, h, arrays.ctypes.data_as(C.POINTER(C.c_int)), P, N, t.buf.ptr, N, 1, n * N,
-                                   all_int.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(hard))
-            if rc != MCR_OK:
-                t.free()
+            with contextlib.ExitStack() as stack:
+                t = stack.enter_context(self.alloc_tensor(n, N, P))
+                rc = L.mcr_json_decode(self.handle, h, arrays.ctypes.data_as(C.POINTER(C.c_int)), P, N, t.buf.ptr, N, 1, n * N,
+                                       all_int.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(hard))
                 if rc == MCR_EFALLBACK:
                     note["fallback"] = (L.mcr_last_error(self.handle) or b"").decode(errors="replace")
                     return None
                 self._check(rc)
-            if phases is not None:
-                t2 = time.perf_counter()
-                phases.update(upload_index_walk_ms=(t1 - t0) * 1e3, parse_finish_ms=(t2 - t1) * 1e3, text_bytes=len(text),
-                              hard=int(hard.value))
-            return list(names), t, all_int[:, :P].astype(bool), int(hard.value)
+                if phases is not None:
+                    t2 = time.perf_counter()
+                    phases.update(upload_index_walk_ms=(t1 - t0) * 1e3, parse_finish_ms=(t2 - t1) * 1e3, text_bytes=len(text),
+                                  hard=int(hard.value))
+                stack.pop_all()
+                return list(names), t, all_int[:, :P].astype(bool), int(hard.value)
         finally:
             L.mcr_json_close(h)
 
@@ -1663,20 +1652,14 @@ class Context:
         tails = None if ndraws_tail is None else np.ascontiguousarray(np.broadcast_to(np.asarray(ndraws_tail), (P,)), dtype=np.int64)
         arrs = {n: np.full(max(P, 1), np.nan) for n in ("khat", "lppd", "elpd", "p_loo")}
         nt = np.zeros(max(P, 1), dtype=np.int64)
-        lw = buf = None
-        if weights and dev:
-            buf = DeviceBuffer(self, max(P * M * 8, 8))
-        elif weights:
-            lw = np.full(max(P * M, 1), np.nan)
-        wptr = buf.ptr if buf is not None else lw.ctypes.data_as(C.c_void_p) if lw is not None else None
-        out = Psis(ndraws_tail=_as_ip(nt), log_weights=wptr, **{n: _as_dp(a) for n, a in arrs.items()})
-        try:
+        lw = np.full(max(P * M, 1), np.nan) if weights and not dev else None
+        with contextlib.ExitStack() as stack:
+            buf = stack.enter_context(DeviceBuffer(self, max(P * M * 8, 8))) if weights and dev else None
+            wptr = buf.ptr if buf is not None else lw.ctypes.data_as(C.c_void_p) if lw is not None else None
+            out = Psis(ndraws_tail=_as_ip(nt), log_weights=wptr, **{n: _as_dp(a) for n, a in arrs.items()})
             self._check(fn(self.handle, ptr, *targs, int(bool(negate)), _as_dp(r), _as_ip(tails), C.byref(out)))
             if buf is not None:
                 lw = buf.download(np.float64, max(P * M, 1))
-        finally:
-            if buf is not None:
-                buf.free()
         res = {n: a[:P] for n, a in arrs.items()}
         res["ndraws_tail"] = nt[:P]
         if weights:
@@ -1757,12 +1740,12 @@ class Context:
         ess, s1 = C.c_double(np.nan), C.c_double(np.nan)
         w = np.full(max(M, 1), np.nan) if return_weights else None
         vbuf = wbuf = None
-        try:
+        with contextlib.ExitStack() as stack:
             if dev:
-                vbuf = DeviceBuffer(self, max(M * 8, 8))
+                vbuf = stack.enter_context(DeviceBuffer(self, max(M * 8, 8)))
                 if M:
                     vbuf.upload(v)
-                wbuf = DeviceBuffer(self, max(M * 8, 8)) if return_weights else None
+                wbuf = stack.enter_context(DeviceBuffer(self, max(M * 8, 8))) if return_weights else None
             vptr = vbuf.ptr if dev else v.ctypes.data_as(C.c_void_p)
             wptr = None if w is None else wbuf.ptr if dev else w.ctypes.data_as(C.c_void_p)
             out = Weighted(quantiles=_as_dp(qs), ess=C.pointer(ess), weight_sum=C.pointer(s1), weights=wptr,
@@ -1770,10 +1753,6 @@ class Context:
             self._check(fn(self.handle, ptr, *targs, vptr, flags, _as_dp(q), nq, C.byref(out)))
             if wbuf is not None:
                 w = wbuf.download(np.float64, max(M, 1))
-        finally:
-            for b in (vbuf, wbuf):
-                if b is not None:
-                    b.free()
         res = {n: a[:P] for n, a in arrs.items()}
         res.update({"quantiles": qs[:P, :nq], "ess": ess.value, "weight_sum": s1.value, "n_draws": int(M)})
         if return_weights:
@@ -1789,7 +1768,10 @@ class Context:
         targs = tensor4_args(draws, layout)
         if not draws.flags.c_contiguous:
             raise ValueError("upload_sims() needs a C-contiguous array (permute the layout string instead)")
-        return DeviceSims(self, DeviceBuffer(self, max(draws.nbytes, 8)).upload(draws), targs)
+        with contextlib.ExitStack() as stack:
+            buf = stack.enter_context(DeviceBuffer(self, max(draws.nbytes, 8))).upload(draws)
+            stack.pop_all()
+        return DeviceSims(self, buf, targs)
 
     def _sbc_call(self, draws, layout: str, thin: int):
         """(thinned targs, pointer, entry) of a rank call on a 4-D host array or on the DeviceSims of S simulations."""

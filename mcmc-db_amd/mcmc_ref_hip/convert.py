@@ -7,16 +7,16 @@ parameter), `_checks` (:164-172) and `_enforce_checks` (:175-178).
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import math
 import time
 import zipfile
 from collections.abc import Iterable
-from contextlib import closing
 from dataclasses import dataclass
 from datetime import date
 from pathlib import Path
-from typing import Any
+from typing import Any, NamedTuple
 
 import numpy as np
 
@@ -243,10 +243,43 @@ def _json_image(ctx, params: list[str], t, int_columns: list[bool]):
         return ctx.write_parquet(cols, n_chains * n_draws)
 
 
+def _upload_draws(ctx, x: np.ndarray, counts, P: int):
+    """The DeviceTensor of host draws x [P][M] in (chain, draw) order whose chains are `counts` draws long: [P][C][N]
+    where they are equally long, else the ragged tensor of Context.ragged_tensor.  Free it."""
+    if np.all(counts == counts[0]):
+        return ctx.upload(x.reshape(P, len(counts), int(counts[0])), "pcn")
+    xc = np.ascontiguousarray(x, dtype=np.float64)
+    with contextlib.ExitStack() as stack:
+        buf = stack.enter_context(_ffi.DeviceBuffer(ctx, max(xc.nbytes, 8))).upload(xc)
+        stack.pop_all()
+    return ctx.ragged_tensor(buf, counts, P)
+
+
+@dataclass
+class _Prepared:
+    """One job of convert_files, read and laid out.  What is written: the Arrow `table`, or the `image` of the draws
+    file encoded on the device.  What the diagnostics read: the host matrix `x` [P][M], or the resident `tensor`
+    (convert_files puts the upload of `x` there too).  close() frees the image and the tensor."""
+    params: list
+    n_chains: int
+    n_draws: int
+    counts: np.ndarray
+    table: Any = None
+    image: Any = None
+    x: Any = None
+    tensor: Any = None
+
+    def close(self):
+        if self.image is not None:
+            self.image.close()
+        if self.tensor is not None:
+            self.tensor.free()
+
+
 def _read_json_zip_prepared(path: Path, min_chains: int, context, writer: str = "host"):
-    """A `.json.zip` input of convert_files through the device reader: the `prepared` entry with the draws resident
-    (a DeviceTensor in place of the host matrix), or None for the host route.  writer="auto": the entry holds the
-    encoded draws file (a PqImage) in place of the table, and nothing is downloaded."""
+    """A `.json.zip` input of convert_files through the device reader: the `_Prepared` entry with the draws resident, or
+    None for the host route.  writer="auto": the entry holds the encoded draws file in place of the table, and nothing
+    is downloaded."""
     try:
         ctx = context or _ffi.default_context()
     except _ffi.HipUnavailableError:
@@ -255,21 +288,19 @@ def _read_json_zip_prepared(path: Path, min_chains: int, context, writer: str = 
     if got is None:
         return None
     params, t, int_columns = got
-    try:
+    with contextlib.ExitStack() as stack:
+        stack.enter_context(t)
         _, n_chains, n_draws, P = t.targs[:4]
         if n_draws == 0:                                   # nothing to parse: the host reader's empty table
-            t.free()
             return None
         if n_chains < min_chains:
             raise ValueError(f"R-hat diagnostics require at least {min_chains} chains; got {n_chains} chain(s)")
-        table = _json_image(ctx, params, t, int_columns) if writer == "auto" else None
-        if table is None:
+        table, image = None, _json_image(ctx, params, t, int_columns) if writer == "auto" else None
+        if image is None:
             flat = t.buf.download(np.float64, P * n_chains * n_draws).reshape(P, n_chains * n_draws)
             table = _json_table(params, flat, n_chains, n_draws, int_columns)
-    except BaseException:
-        t.free()
-        raise
-    return table, params, n_chains, n_draws, t, np.full(n_chains, n_draws)
+        stack.pop_all()
+        return _Prepared(params, n_chains, n_draws, np.full(n_chains, n_draws), table=table, image=image, tensor=t)
 
 
 def summarize_json_zip(path: Path, min_chains: int = 4, quantiles=(0.05, 0.5, 0.95), diagnostics: bool = True,
@@ -286,82 +317,57 @@ def summarize_json_zip(path: Path, min_chains: int = 4, quantiles=(0.05, 0.5, 0.
         if not params or len(counts) == 0:
             return {}
         with _ffi.value_errors():
-            t = ctx.upload(x.reshape(len(params), len(counts), int(counts[0])), "pcn")
+            t = _upload_draws(ctx, x, counts, len(params))
     else:
         params, t, _ints = got
-    try:
-        with _ffi.value_errors():
-            r = ctx.summarize(t, min_chains=min_chains, quantiles=quantiles, diagnostics=diagnostics)
-    finally:
-        t.free()
+    with t, _ffi.value_errors():
+        r = ctx.summarize(t, min_chains=min_chains, quantiles=quantiles, diagnostics=diagnostics)
     return dict(zip(params, _ffi.entries(r, list(quantiles), diagnostics)))
 
 
-def _csv_draws(ctx, got, note: dict):
-    """One file of Context.csv_table_decode -> (parquet.DeviceDraws, file-order buffer, int flags, header, ids) with the
-    rows put in (chain, draw) order by the device layout code (`parquet._device_layout`, the host's lexsort where that
-    declines, as parquet.read_draws_many does).  A missing `chain` is chain 0 and a missing `draw` the row number
-    (`_ensure_chain_draw`); without both the rows are in order as they stand.  ids: the downloaded (chain, draw) columns or None.  Takes over `got`'s
-    buffers: they are freed here if anything fails."""
-    import ctypes as C
+class CsvDraws(NamedTuple):
+    """One file of read_csv_many_dev.  close() frees the draws and the file-order buffer (they may share memory)."""
+    draws: Any             # parquet.DeviceDraws: [P][M] in (chain, draw) order, chain ids, counts
+    file_order: Any        # the [P][M] f64 values in FILE row order
+    int_columns: list      # per parameter: every literal of the column is an integer
+    header: list           # every column name of the file
+    ids: tuple             # the downloaded (chain, draw) columns, None for an absent one
 
+    def close(self):
+        self.draws.free()
+        self.file_order.free()
+
+
+def _csv_draws(ctx, got: "_ffi.CsvTable", note: dict) -> CsvDraws:
+    """One file of Context.csv_table_decode with its rows put in (chain, draw) order (parquet.draws_in_order).  A missing
+    `chain` is chain 0 and a missing `draw` the row number (`_ensure_chain_draw`); without both the rows are in order as
+    they stand.  Takes over `got`: it is closed here, and what is returned holds views of its own."""
     from . import parquet
     names, buf, ints, (chain, draw), _hard, header = got
-    P, M = len(names), buf.nbytes // 8 // max(len(names), 1)
-    made, dbuf = [], None
-    try:
-        if not names:
-            M = (chain or draw).nbytes // 8
+    M = buf.nbytes // 8 // len(names) if names else (chain or draw).nbytes // 8
+    with contextlib.ExitStack() as stack, contextlib.ExitStack() as handed:
+        stack.callback(got.close)                         # the draws and the file-order buffer hold views of their own
+        known, order, ptrs = None, None, [None if b is None else b.ptr for b in (chain, draw)]
         if chain is None and draw is None:
-            chain_ids, order, counts = np.zeros(1, dtype=np.int64), None, np.full(1, M, dtype=np.int64)
-        else:
-            cptr, dptr = (b.ptr if b is not None else None for b in (chain, draw))
-            if cptr is None:                                   # one chain
-                made.append(_ffi.DeviceBuffer(ctx, M * 8).upload(np.zeros(M, dtype=np.int64)))
-                cptr = made[-1].ptr
-            if dptr is None:                                   # file order within each chain: draw = row number
-                made.append(_ffi.DeviceBuffer(ctx, M * 8).upload(np.arange(M, dtype=np.int64)))
-                dptr = made[-1].ptr
-            made.append(_ffi.DeviceBuffer(ctx, M * 8))         # the row order, if the rows need one
-            lay = parquet._device_layout(ctx, cptr, dptr, M, made[-1])
-            if lay is None:                                    # no 64-bit row key, or very many chains
-                note["layout"] = "host"
-                hc = chain.download(np.int64, M) if chain is not None else np.zeros(M, dtype=np.int64)
-                hd = draw.download(np.int64, M) if draw is not None else np.arange(M, dtype=np.int64)
-                chain_ids, order, counts = parquet._layout(hc, hd)
-                if order is not None and P:
-                    order = np.ascontiguousarray(order, dtype=np.int64)
-                    dbuf = _ffi.DeviceBuffer(ctx, P * M * 8)
-                    ctx._check(ctx.lib.mcr_gather_rows_dev(ctx.handle, buf.ptr, P, M, order.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                           dbuf.ptr))
-            else:
-                chain_ids, order, counts = lay
-                if order is not None and P:
-                    dbuf = _ffi.DeviceBuffer(ctx, P * M * 8)
-                    ctx.gather_rows_order(buf.ptr, P, M, order.ptr, dbuf.ptr)
+            known = np.zeros(1, dtype=np.int64), np.full(1, M, dtype=np.int64)
+        else:                                             # a missing chain: one chain; a missing draw: the row number
+            for w, fill in enumerate((np.zeros, np.arange)):
+                if ptrs[w] is None:
+                    ptrs[w] = stack.enter_context(_ffi.DeviceBuffer(ctx, M * 8)).upload(fill(M, dtype=np.int64)).ptr
+            order = stack.enter_context(_ffi.DeviceBuffer(ctx, M * 8))         # the row order, if the rows need one
+        d = handed.enter_context(parquet.draws_in_order(ctx, buf, names, M, ptrs[0], ptrs[1], order, known, note))
+        if not names:                                     # id columns alone: a layout, and no tensor
+            d.tensor = None
         ids = tuple(None if b is None else b.download(np.int64, M) for b in (chain, draw))
-        if dbuf is None:
-            dbuf = buf.share()
-        tensor = None
-        if P and len(counts) and np.all(counts == counts[0]):
-            Cn, N = len(counts), int(counts[0])
-            tensor = _ffi.DeviceTensor(ctx, dbuf, (_ffi.MCR_F64, Cn, N, P, N, 1, Cn * N))
-        return parquet.DeviceDraws(tensor, dbuf, names, chain_ids, np.asarray(counts, dtype=np.int64)), buf, [bool(v) for v in ints], header, ids
-    except BaseException:
-        buf.free()
-        if dbuf is not None:
-            dbuf.free()
-        raise
-    finally:
-        for b in made + [chain, draw]:
-            if b is not None:
-                b.free()
+        fbuf = handed.enter_context(buf.share())
+        handed.pop_all()
+        return CsvDraws(d, fbuf, [bool(v) for v in ints], header, ids)
 
 
 def read_csv_many_dev(paths, context=None, phases: dict | None = None):
     """`read_csv_dev` for several files with one read, one line index and one parse (Context.csv_table_decode): a list
-    of (DeviceDraws, file-order buffer, int flags, header names, (chain, draw) id columns or None each), or None when
-    the host reader must decide for one of them (`phases["fallback"]` says why and for which)."""
+    of CsvDraws (DeviceDraws, file-order buffer, int flags, header names, (chain, draw) id columns or None each), or None
+    when the host reader must decide for one of them (`phases["fallback"]` says why and for which).  Close every entry."""
     import os
     note = phases if phases is not None else {}
     paths = [Path(p) for p in paths]
@@ -374,19 +380,13 @@ def read_csv_many_dev(paths, context=None, phases: dict | None = None):
         got = ctx.csv_table_decode([str(p) for p in paths], note)
     if got is None:
         return None
-    out = []
-    try:
+    with contextlib.ExitStack() as stack:
+        stack.callback(lambda: [g.close() for g in got])       # the files that no _csv_draws has taken over
+        out = []
         while got:
             out.append(_csv_draws(ctx, got.pop(0), note))
-    except BaseException:
-        for g in got:
-            for b in (g[1], *g[3]):
-                if b is not None:
-                    b.free()
-        for d, fb, *_ in out:
-            d.free()
-            fb.free()
-        raise
+            stack.callback(out[-1].close)
+        stack.pop_all()
     return out
 
 
@@ -422,12 +422,13 @@ def _csv_image(ctx, fbuf, M: int, int_columns, header, ids):
     file-order [P][M] values (Context.write_parquet): the file's columns in its order, int64 where every literal is an
     integer, the id columns from the file (16 bytes per row go back up: the layout step downloaded and freed them), and
     the bookkeeping columns `_ensure_chain_draw` appends as generated int32 columns, in its positions."""
-    cols, made, k = [], [], 0
-    try:
+    cols, k = [], 0
+    with contextlib.ExitStack() as stack:
         for name in header:
             if name in ("chain", "draw"):
-                made.append(_ffi.DeviceBuffer(ctx, max(M * 8, 8)).upload(np.ascontiguousarray(ids[name == "draw"], dtype=np.int64)))
-                cols.append(_ffi.pq_column(name, _ffi.MCR_PQ_INT64, made[-1], 1, _ffi.MCR_PQW_I64))
+                col = stack.enter_context(_ffi.DeviceBuffer(ctx, max(M * 8, 8)))
+                col.upload(np.ascontiguousarray(ids[name == "draw"], dtype=np.int64))
+                cols.append(_ffi.pq_column(name, _ffi.MCR_PQ_INT64, col, 1, _ffi.MCR_PQW_I64))
             else:
                 cols.append(_ffi.pq_column(name, _ffi.MCR_PQ_INT64 if int_columns[k] else _ffi.MCR_PQ_DOUBLE,
                                            fbuf.ptr.value + 8 * k * M, 1, _ffi.MCR_PQW_F64))
@@ -438,36 +439,27 @@ def _csv_image(ctx, fbuf, M: int, int_columns, header, ids):
             cols.append(_ffi.pq_sequence("draw", _ffi.MCR_PQ_INT32))
         with _ffi.value_errors():
             return ctx.write_parquet(cols, M)
-    finally:
-        for b in made:
-            b.free()
 
 
-def _csv_prepared(ctx, got, min_chains: int, writer: str = "host"):
-    """The `prepared` entry of convert_files for one file of read_csv_many_dev (the draws resident).  writer="auto": the
-    entry holds the encoded draws file (a PqImage) in place of the table, and the matrix is not downloaded."""
+def _csv_prepared(ctx, got: CsvDraws, min_chains: int, writer: str = "host") -> _Prepared:
+    """The `_Prepared` entry of convert_files for one file of read_csv_many_dev (the draws resident).  writer="auto": the
+    entry holds the encoded draws file in place of the table, and the matrix is not downloaded.  Takes over `got`."""
     d, fbuf, int_columns, header, ids = got
-    table = None
-    try:
+    with contextlib.ExitStack() as stack:
+        stack.enter_context(d)
         P, M = len(d.params), int(d.counts.sum())
-        if writer == "auto":
-            table = _csv_image(ctx, fbuf, M, int_columns, header, ids)
-        else:
-            flat = fbuf.download(np.float64, P * M).reshape(P, M)
-            table = _ensure_chain_draw(_csv_table(d, flat, int_columns, header, ids))
-        fbuf.free()
-        fbuf = None
+        table = image = None
+        with fbuf:
+            if writer == "auto":
+                image = stack.enter_context(_csv_image(ctx, fbuf, M, int_columns, header, ids))
+            else:
+                flat = fbuf.download(np.float64, P * M).reshape(P, M)
+                table = _ensure_chain_draw(_csv_table(d, flat, int_columns, header, ids))
         if d.params and len(d.counts) < min_chains:
             raise ValueError(f"R-hat diagnostics require at least {min_chains} chains; got {len(d.counts)} chain(s)")
         t = d.tensor if d.rectangular else ctx.ragged_tensor(d.buf, d.counts, P)
-        return table, d.params, int(len(d.counts)), int(d.counts.min()), t, d.counts
-    except BaseException:
-        if isinstance(table, _ffi.PqImage):
-            table.close()
-        d.free()
-        if fbuf is not None:
-            fbuf.free()
-        raise
+        stack.pop_all()
+        return _Prepared(d.params, int(len(d.counts)), int(d.counts.min()), d.counts, table=table, image=image, tensor=t)
 
 
 _CSV_BATCH_BYTES = 3 << 30     # text of the .csv jobs read by one library call (its limit is 4 GiB less 1 MiB, padding included)
@@ -502,31 +494,35 @@ def _read_csv_prepared_many(paths, min_chains: int, context, writer: str = "host
         groups[-1].append(i)
         size += n
     got: list = [None] * len(paths)
-    for group in groups:
-        while group:
-            res, note = read(group)
-            if res is not None:
-                for i, g in zip(group, res):
-                    got[i] = g
-                break
-            named = [i for i in group if note.get("fallback", "").startswith(f"csv table: {paths[i]}: ")]
-            if len(named) != 1:                                # not a fallback of one file: each on its own
-                for i in group if len(group) > 1 else []:
-                    got[i] = (read([i])[0] or [None])[0]
-                break
-            group = [i for i in group if i != named[0]]
     done: dict = {}
-    for i, g in enumerate(got):
-        if g is None:
-            continue
-        if not g[0].params:                                    # only bookkeeping columns: the host route's empty model
-            g[0].free()
-            g[1].free()
-            continue
-        try:
-            done[i] = _csv_prepared(ctx, g, min_chains, writer)
-        except Exception as exc:  # noqa: BLE001 - reported per job
-            done[i] = exc
+    with contextlib.ExitStack() as stack:
+        stack.callback(lambda: [g.close() for g in got if g is not None])      # the files read and not yet taken over
+        for group in groups:
+            while group:
+                res, note = read(group)
+                if res is not None:
+                    for i, g in zip(group, res):
+                        got[i] = g
+                    break
+                named = [i for i in group if note.get("fallback", "").startswith(f"csv table: {paths[i]}: ")]
+                if len(named) != 1:                            # not a fallback of one file: each on its own
+                    for i in group if len(group) > 1 else []:
+                        got[i] = (read([i])[0] or [None])[0]
+                    break
+                group = [i for i in group if i != named[0]]
+        for i, g in enumerate(got):
+            if g is None:
+                continue
+            got[i] = None
+            if not g.draws.params:                             # only bookkeeping columns: the host route's empty model
+                g.close()
+                continue
+            try:
+                done[i] = _csv_prepared(ctx, g, min_chains, writer)
+                stack.callback(done[i].close)
+            except Exception as exc:  # noqa: BLE001 - reported per job
+                done[i] = exc
+        stack.pop_all()
     return done
 
 
@@ -538,31 +534,23 @@ def summarize_csv(path: Path, min_chains: int = 4, quantiles=(0.05, 0.5, 0.95), 
     import pyarrow.csv as pacsv
     ctx = context if context is not None else _ffi.default_context()
     got = read_csv_dev(Path(path), context=ctx)
-    if got is None:
-        table = _ensure_chain_draw(pacsv.read_csv(Path(path)))
-        params = [c for c in table.column_names if c not in {"chain", "draw"}]
-        x, counts = table_to_tensor(table, params)
-        if not params or len(counts) == 0:
-            return {}
-        with _ffi.value_errors():
-            if np.all(counts == counts[0]):
-                t = ctx.upload(x.reshape(len(params), len(counts), int(counts[0])), "pcn")
-            else:
-                xc = np.ascontiguousarray(x, dtype=np.float64)
-                t = ctx.ragged_tensor(_ffi.DeviceBuffer(ctx, max(xc.nbytes, 8)).upload(xc), counts, len(params))
-    else:
-        d, fbuf, _ints = got
-        fbuf.free()
-        params = d.params
-        if not params:
-            d.free()
-            return {}
-        t = d.tensor if d.rectangular else ctx.ragged_tensor(d.buf, d.counts, len(params))
-    try:
-        with _ffi.value_errors():
-            r = ctx.summarize(t, min_chains=min_chains, quantiles=quantiles, diagnostics=diagnostics)
-    finally:
-        t.free()
+    with contextlib.ExitStack() as stack, _ffi.value_errors():
+        if got is None:
+            table = _ensure_chain_draw(pacsv.read_csv(Path(path)))
+            params = [c for c in table.column_names if c not in {"chain", "draw"}]
+            x, counts = table_to_tensor(table, params)
+            if not params or len(counts) == 0:
+                return {}
+            t = stack.enter_context(_upload_draws(ctx, x, counts, len(params)))
+        else:
+            d, fbuf, _ints = got
+            stack.enter_context(d)
+            fbuf.free()
+            params = d.params
+            if not params:
+                return {}
+            t = d.tensor if d.rectangular else ctx.ragged_tensor(d.buf, d.counts, len(params))
+        r = ctx.summarize(t, min_chains=min_chains, quantiles=quantiles, diagnostics=diagnostics)
     return dict(zip(params, _ffi.entries(r, list(quantiles), diagnostics)))
 
 
@@ -573,6 +561,23 @@ def _read_input(path: Path):
     if _is_json_zip(path):
         return _read_json_zip(path)
     raise ValueError(f"Unsupported input format: {path}")
+
+
+def _read_table(path, parquet: bool):
+    """The host's table of a `.csv` or chain-list `.json.zip`; with `parquet` of a `.parquet` draws file of the store too."""
+    path = Path(path)
+    if parquet and path.suffix == ".parquet":
+        import pyarrow.parquet as pq
+        return pq.read_table(path)
+    return _read_input(path)
+
+
+def _equal_chains(table, names: list[str], what: str) -> np.ndarray:
+    """The draws [P][C][N] of a table whose chains are equally long; ValueError (`what` requires it) where they are not."""
+    x, counts = table_to_tensor(table, names)
+    if len(counts) and not np.all(counts == counts[0]):
+        raise ValueError(f"{what} requires chains of equal length")
+    return x.reshape(len(names), len(counts), int(counts[0]) if len(counts) else 0)
 
 
 def _table_and_names(table, params: Iterable[str] | None):
@@ -592,16 +597,13 @@ def nested_rhat_file(path: Path, superchains: int, params: Iterable[str] | None 
     """Nested R-hat of every parameter of a draws table (a `.csv` or chain-list `.json.zip`, read on the host): any
     number of equal-length chains, dealt to `superchains` superchains in blocks, in chain-id order.  Per parameter:
     nrhat, nrhat_bulk, nrhat_tail, nrhat_raw (Context.nested_rhat)."""
-    table, names = _table_and_names(_read_input(Path(path)), params)
+    table, names = _table_and_names(_read_table(path, parquet=False), params)
     if not names:
         return {}
-    x, counts = table_to_tensor(table, names)
-    if len(counts) and not np.all(counts == counts[0]):
-        raise ValueError("nested R-hat requires chains of equal length")
-    C = len(counts)
+    x = _equal_chains(table, names, "nested R-hat")
     ctx = context or _ffi.default_context()
     with _ffi.value_errors():
-        r = ctx.nested_rhat(x.reshape(len(names), C, int(counts[0]) if C else 0), int(superchains), "pcn")
+        r = ctx.nested_rhat(x, int(superchains), "pcn")
     keys = ("nrhat", "nrhat_bulk", "nrhat_tail", "nrhat_raw")
     return {n: {k: float(r[k][i]) for k in keys} for i, n in enumerate(names)}
 
@@ -611,7 +613,7 @@ def pareto_khat_file(path: Path, params: Iterable[str] | None = None, ndraws_tai
     """Pareto k-hat of every parameter of a draws table (a `.csv` or chain-list `.json.zip`, read on the host); the chains
     are pooled and may differ in length.  Per parameter: khat, khat_left, khat_right, ndraws_tail, min_ss
     (Context.pareto_khat); `ndraws_tail`: the tail length for every parameter instead of the default."""
-    table, names = _table_and_names(_read_input(Path(path)), params)
+    table, names = _table_and_names(_read_table(path, parquet=False), params)
     if not names:
         return {}
     if ndraws_tail is not None and ndraws_tail < 1:
@@ -629,7 +631,7 @@ def loo_file(path: Path, params: Iterable[str] | None = None, prefix: str = "log
     host): the columns whose name starts with `prefix` (of `params`, or of all), one observation each; the chains are
     pooled and may differ in length.  Context.loo's result -- elpd_loo, se, p_loo, lppd, n_obs, n_draws, khat_counts,
     khat_threshold, the pointwise arrays -- and "names", the observations' columns.  ValueError when no column matches."""
-    table, names = _table_and_names(_read_input(Path(path)), params)
+    table, names = _table_and_names(_read_table(path, parquet=False), params)
     names = [n for n in names if n.startswith(prefix)]
     if not names:
         raise ValueError(f"no column starts with {prefix!r}")
@@ -657,13 +659,7 @@ def hdi_file(path: Path, params: Iterable[str] | None = None, prob: Iterable[flo
     """Highest-density intervals of every parameter of a draws table (a `.csv` or chain-list `.json.zip`, read on the
     host); the chains are pooled and may differ in length.  Per parameter and probability q of `prob`: `hdi_lo_q` and
     `hdi_hi_q`, q printed like `format(q, "g")` (Context.hdi).  A `.parquet` draws file of the store is read as well."""
-    path = Path(path)
-    if path.suffix == ".parquet":
-        import pyarrow.parquet as pq
-        table = pq.read_table(path)
-    else:
-        table = _read_input(path)
-    table, names = _table_and_names(table, params)
+    table, names = _table_and_names(_read_table(path, parquet=True), params)
     probs = [float(q) for q in prob]
     if not probs or len(probs) > _ffi.MCR_HDI_MAX_PROBS or not all(0.0 < q < 1.0 for q in probs):
         raise ValueError(f"prob: 1 to {_ffi.MCR_HDI_MAX_PROBS} probabilities inside (0, 1); got {probs}")
@@ -694,13 +690,8 @@ def weighted_summary_file(path: Path, log_weights: str | None = None, weights: s
     wname = weights if log_weights is None else log_weights
     qs = [float(q) for q in quantiles]
     _ffi.weight_arguments(0, None, [], qs)                    # the quantiles are refused before anything is read
-    path = Path(path)
-    if path.suffix == ".parquet":
-        import pyarrow.parquet as pq
-        table = pq.read_table(path)
-    else:
-        table = _read_input(path)
-    table, names = _table_and_names(table, None if params is None else [p for p in params if p != wname] + [wname])
+    table, names = _table_and_names(_read_table(path, parquet=True),
+                                    None if params is None else [p for p in params if p != wname] + [wname])
     if wname not in names:
         raise ValueError(f"Unknown weight column: {wname}")
     names = [n for n in names if n != wname]
@@ -728,23 +719,13 @@ def autocorr_file(path: Path, params: Iterable[str] | None = None, max_lag: int 
     `.parquet` draws file of the store, read on the host) with chains of equal length, in chain-id order.  Per parameter:
     lists acf [C][L+1], tau, window, ess_chain [C], acf_pooled [L+1], and tau_pooled, window_pooled, ess_pooled, max_lag
     (Context.autocorr).  ValueError for chains of unequal length."""
-    path = Path(path)
-    if path.suffix == ".parquet":
-        import pyarrow.parquet as pq
-        table = pq.read_table(path)
-    else:
-        table = _read_input(path)
-    table, names = _table_and_names(table, params)
+    table, names = _table_and_names(_read_table(path, parquet=True), params)
     if not names:
         return {}
-    x, counts = table_to_tensor(table, names)
-    if len(counts) and not np.all(counts == counts[0]):
-        raise ValueError("autocorrelation requires chains of equal length")
-    C = len(counts)
+    x = _equal_chains(table, names, "autocorrelation")
     ctx = context or _ffi.default_context()
     with _ffi.value_errors():
-        r = ctx.autocorr(x.reshape(len(names), C, int(counts[0]) if C else 0), "pcn", max_lag=max_lag, unbiased=unbiased,
-                         window_c=window_c)
+        r = ctx.autocorr(x, "pcn", max_lag=max_lag, unbiased=unbiased, window_c=window_c)
     return {n: {"acf": r["acf"][i].tolist(), "tau": r["tau"][i].tolist(), "window": r["window"][i].tolist(),
                 "ess_chain": r["ess_chain"][i].tolist(), "acf_pooled": r["acf_pooled"][i].tolist(),
                 "tau_pooled": float(r["tau_pooled"][i]), "window_pooled": int(r["window_pooled"][i]),
@@ -796,101 +777,87 @@ def convert_files(jobs, out_draws_dir: Path, out_meta_dir: Path, force: bool = F
     min_chains = 1 if force else 4
     n = len(jobs)
     results: list = [None] * n
-    prepared: dict[int, tuple] = {}
-    csv_jobs = [i for i, (p, _name) in enumerate(jobs) if reader == "auto" and Path(p).suffix == ".csv"]
-    csv_done = _read_csv_prepared_many([Path(jobs[i][0]) for i in csv_jobs], min_chains, context, writer) if csv_jobs else {}
-    for k, got in csv_done.items():
-        if isinstance(got, Exception):
-            results[csv_jobs[k]] = got
-        else:
-            prepared[csv_jobs[k]] = got
-    for i, (input_path, _name) in enumerate(jobs):
-        if i in prepared or results[i] is not None:
-            continue
-        try:
-            if reader == "auto" and _is_json_zip(Path(input_path)):
-                got = _read_json_zip_prepared(Path(input_path), min_chains, context, writer)
-                if got is not None:
-                    prepared[i] = got
-                    continue
-            table = _ensure_chain_draw(_read_input(Path(input_path)))
-            params = [c for c in table.column_names if c not in {"chain", "draw"}]
-            n_chains, n_draws = _count_chains_draws(table)
-            x, counts = table_to_tensor(table, params)
-            if params and len(counts) < min_chains:
-                raise ValueError(f"R-hat diagnostics require at least {min_chains} chains; got {len(counts)} chain(s)")
-            prepared[i] = (table, params, n_chains, n_draws, x, counts)
-        except Exception as exc:  # noqa: BLE001 - reported per job
-            results[i] = exc
-    prepared = dict(sorted(prepared.items()))               # job order, whichever reader prepared a job
-    diags: dict[int, dict] = {}
-    todo = []                                         # models with parameters, rectangular and ragged, in job order
-    for i, (_table, params, _nc, _nd, _x, _counts) in prepared.items():
-        if not params:
-            diags[i] = {}
-        else:
-            todo.append(i)
-    ctx = (context or _ffi.default_context()) if todo else None
-
-    def calls():
-        for i in todo:
-            _table, params, _nc, _nd, x, counts = prepared[i]
-            if isinstance(x, _ffi.DeviceTensor):            # read on the device: already resident
-                resident.discard(i)
-                yield i, x, {"min_chains": min_chains, "quantiles": ()}
+    prepared: dict[int, _Prepared] = {}
+    with contextlib.ExitStack() as stack:                   # every prepared job is closed, however this ends
+        csv_jobs = [i for i, (p, _name) in enumerate(jobs) if reader == "auto" and Path(p).suffix == ".csv"]
+        csv_done = _read_csv_prepared_many([Path(jobs[i][0]) for i in csv_jobs], min_chains, context, writer) if csv_jobs else {}
+        for k, got in csv_done.items():
+            if isinstance(got, Exception):
+                results[csv_jobs[k]] = got
+            else:
+                prepared[csv_jobs[k]] = got
+                stack.callback(got.close)
+        for i, (input_path, _name) in enumerate(jobs):
+            if i in prepared or results[i] is not None:
                 continue
             try:
-                if np.all(counts == counts[0]):
-                    t = ctx.upload(x.reshape(len(params), len(counts), int(counts[0])), "pcn")
-                else:                                       # chains of unequal length: a ragged call in the same window
-                    xc = np.ascontiguousarray(x, dtype=np.float64)
-                    t = ctx.ragged_tensor(_ffi.DeviceBuffer(ctx, max(xc.nbytes, 8)).upload(xc), counts, len(params))
-            except _ffi.McrError as exc:
-                results[i] = ValueError(exc.message)
-                continue
-            yield i, t, {"min_chains": min_chains, "quantiles": ()}
+                if reader == "auto" and _is_json_zip(Path(input_path)):
+                    got = _read_json_zip_prepared(Path(input_path), min_chains, context, writer)
+                    if got is not None:
+                        prepared[i] = got
+                        stack.callback(got.close)
+                        continue
+                table = _ensure_chain_draw(_read_input(Path(input_path)))
+                params = [c for c in table.column_names if c not in {"chain", "draw"}]
+                n_chains, n_draws = _count_chains_draws(table)
+                x, counts = table_to_tensor(table, params)
+                if params and len(counts) < min_chains:
+                    raise ValueError(f"R-hat diagnostics require at least {min_chains} chains; got {len(counts)} chain(s)")
+                prepared[i] = _Prepared(params, n_chains, n_draws, counts, table=table, x=x)
+                stack.callback(prepared[i].close)
+            except Exception as exc:  # noqa: BLE001 - reported per job
+                results[i] = exc
+        prepared = dict(sorted(prepared.items()))           # job order, whichever reader prepared a job
+        diags: dict[int, dict] = {}
+        todo = []                                     # models with parameters, rectangular and ragged, in job order
+        for i, e in prepared.items():
+            if not e.params:
+                diags[i] = {}
+            else:
+                todo.append(i)
+        ctx = (context or _ffi.default_context()) if todo else None
 
-    # anything but a kernel-side failure of one model (an McrError of its own, kept as its result) ends the batch, and
-    # the window then leaves nothing in flight and no device tensor allocated behind the exception
-    resident = {i for i in todo if isinstance(prepared[i][4], _ffi.DeviceTensor)}   # not yet handed to the window
-    try:
+        def calls():
+            for i in todo:
+                e = prepared[i]
+                if e.tensor is None:                        # read on the host: uploaded as its turn comes
+                    try:
+                        e.tensor = _upload_draws(ctx, e.x, e.counts, len(e.params))
+                    except _ffi.McrError as exc:
+                        results[i] = ValueError(exc.message)
+                        continue
+                yield i, e.tensor, {"min_chains": min_chains, "quantiles": ()}
+
+        # anything but a kernel-side failure of one model (an McrError of its own, kept as its result) ends the batch, and
+        # the window then leaves nothing in flight; it frees each tensor as its call retires, the entries free the rest
         if todo:
-            with closing(_ffi.pipeline(ctx, calls(), owns=True)) as done:
+            with contextlib.closing(_ffi.pipeline(ctx, calls(), owns=True)) as done:
                 for i, r in done:
                     if isinstance(r, _ffi.McrError):
                         results[i] = ValueError(r.message)
                     else:
-                        diags[i] = dict(zip(prepared[i][1], _ffi.entries(r)))
-    finally:
-        for i in resident:
-            prepared[i][4].free()
-    for i, (table, params, n_chains, n_draws, _x, _counts) in prepared.items():
-        image = table if isinstance(table, _ffi.PqImage) else None        # encoded on the device: host bytes by now
-        if results[i] is not None:
-            if image is not None:
-                image.close()
-            continue
-        name = jobs[i][1]
-        try:
-            checks = _checks(n_chains, n_draws, diags[i])
-            if not force:
-                _enforce_checks(checks)
-            meta = {"model": name, "parameters": params, "n_chains": n_chains, "n_draws_per_chain": n_draws,
-                    "diagnostics": diags[i], "generated_date": date.today().isoformat(), "checks": checks,
-                    "source": source}
-            draws_path = out_draws_dir / f"{name}.draws.parquet"
-            meta_path = out_meta_dir / f"{name}.meta.json"
-            if image is not None:
-                draws_path.write_bytes(image.view)
-            else:
-                pq.write_table(table, draws_path)
-            meta_path.write_text(json.dumps(meta, indent=2, sort_keys=True))
-            results[i] = ConvertResult(draws_path=draws_path, meta_path=meta_path, meta=meta)
-        except Exception as exc:  # noqa: BLE001
-            results[i] = exc
-        finally:
-            if image is not None:
-                image.close()
+                        diags[i] = dict(zip(prepared[i].params, _ffi.entries(r)))
+        for i, e in prepared.items():
+            if results[i] is not None:
+                continue
+            name = jobs[i][1]
+            try:
+                checks = _checks(e.n_chains, e.n_draws, diags[i])
+                if not force:
+                    _enforce_checks(checks)
+                meta = {"model": name, "parameters": e.params, "n_chains": e.n_chains, "n_draws_per_chain": e.n_draws,
+                        "diagnostics": diags[i], "generated_date": date.today().isoformat(), "checks": checks,
+                        "source": source}
+                draws_path = out_draws_dir / f"{name}.draws.parquet"
+                meta_path = out_meta_dir / f"{name}.meta.json"
+                if e.image is not None:                     # encoded on the device: host bytes by now
+                    draws_path.write_bytes(e.image.view)
+                else:
+                    pq.write_table(e.table, draws_path)
+                meta_path.write_text(json.dumps(meta, indent=2, sort_keys=True))
+                results[i] = ConvertResult(draws_path=draws_path, meta_path=meta_path, meta=meta)
+            except Exception as exc:  # noqa: BLE001
+                results[i] = exc
     return results
 
 

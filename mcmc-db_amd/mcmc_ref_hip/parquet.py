@@ -8,10 +8,10 @@ decoded by HIP kernels straight into HBM; the statistics then run on that tensor
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import mmap
 import os
-from contextlib import closing
 from pathlib import Path
 from typing import Iterable, Sequence
 
@@ -147,7 +147,7 @@ def _download(ctx: "_ffi.Context", ptr, dtype, count: int) -> np.ndarray:
 _Arena, _View = _ffi.DeviceArena, _ffi.DeviceView      # one allocation shared by the models of a batch, and its slices
 
 
-class DeviceDraws:
+class DeviceDraws(_ffi._Owner):
     """Draws of one model in HBM: `tensor` is [P][M] f64 in (chain, draw) order; counts = draws per chain."""
 
     def __init__(self, tensor: DeviceTensor | None, buf, params: list[str], chain_ids: np.ndarray,
@@ -166,13 +166,51 @@ class DeviceDraws:
         self.buf.free()
 
 
+def draws_in_order(ctx: "_ffi.Context", values: _View, params: list[str], M: int, chain_ptr, draw_ptr, order: DeviceBuffer,
+                   known=None, note: dict | None = None) -> DeviceDraws:
+    """The row-order step of every reader: the DeviceDraws of `values`, [P][M] f64 in file row order, with the rows in
+    (chain, draw) order -- the integer bookkeeping of `_chains_from_table`.  chain_ptr / draw_ptr: the id columns in
+    device memory (M int64 each); `order`: scratch of 8 M bytes for a row order.  known: (chain ids, counts) where the
+    rows are known to be in order (Context.chain_layout_many said so, or there are no id columns); else the device
+    layout decides, and where it declines the host's lexsort of the downloaded ids (`note["layout"] = "host"`).  Rows out
+    of order are gathered into a new buffer; otherwise the draws hold another view of `values`.  `values` stays the
+    caller's either way."""
+    P = len(params)
+    rows = None                                       # the row order: `order` on the device, an int64 array from the host
+    if known is not None:
+        chain_ids, counts = known
+    else:
+        lay = _device_layout(ctx, chain_ptr, draw_ptr, M, order)
+        if lay is None:                               # no 64-bit row key, or very many chains: the host's lexsort
+            if note is not None:
+                note["layout"] = "host"
+            lay = _layout(_download(ctx, chain_ptr, np.int64, M), _download(ctx, draw_ptr, np.int64, M))
+        chain_ids, rows, counts = lay
+    with contextlib.ExitStack() as stack:
+        if rows is None or not (P and M):
+            buf = stack.enter_context(values.share())
+        else:
+            buf = stack.enter_context(DeviceBuffer(ctx, P * M * 8))
+            if isinstance(rows, np.ndarray):
+                rows = np.ascontiguousarray(rows, dtype=np.int64)
+                ctx._check(ctx.lib.mcr_gather_rows_dev(ctx.handle, values.ptr, P, M, rows.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                       buf.ptr))
+            else:
+                ctx.gather_rows_order(values.ptr, P, M, rows.ptr, buf.ptr)
+        tensor = None
+        if len(counts) and np.all(counts == counts[0]):
+            Cn, N = len(counts), int(counts[0])
+            tensor = DeviceTensor(ctx, buf, (MCR_F64, Cn, N, P, N, 1, Cn * N))
+        stack.pop_all()
+        return DeviceDraws(tensor, buf, params, chain_ids, np.asarray(counts, dtype=np.int64))
+
+
 def read_draws_many(ctx: "_ffi.Context", sources: Sequence, params: Sequence[Iterable[str] | None] | None = None
                     ) -> list[DeviceDraws]:
     """Decodes many draws files with one batched decode call (all pages of all files in one grid)."""
-    files = [s if isinstance(s, ParquetFile) else ParquetFile(s, ctx) for s in sources]
-    owned = [not isinstance(s, ParquetFile) for s in sources]
-    try:
-        reqs, plan, bufs = [], [], []
+    with contextlib.ExitStack() as stack, contextlib.ExitStack() as handed:
+        files = [s if isinstance(s, ParquetFile) else stack.enter_context(ParquetFile(s, ctx)) for s in sources]
+        reqs, plan = [], []
         wants, sizes, colidx, ididx = [], [], [], []
         for k, f in enumerate(files):
             want = list(params[k]) if params is not None and params[k] is not None else \
@@ -181,75 +219,30 @@ def read_draws_many(ctx: "_ffi.Context", sources: Sequence, params: Sequence[Ite
             colidx.append([f.index(n) for n in want])      # KeyError for an unknown name BEFORE any device allocation
             ididx.append((f.index("chain"), f.index("draw")))
             sizes.append(len(want) * f.num_rows * 8)       # packed: same-shape neighbours form ONE [P][C][N] tensor
-        arena = _Arena(ctx, sum(sizes))
+        arena = stack.enter_context(_Arena(ctx, sum(sizes)))
         id_rows = sum(f.num_rows for f in files)
-        ids_all = DeviceBuffer(ctx, max(2 * id_rows * 8, 8))
-        order_buf = DeviceBuffer(ctx, max(max((f.num_rows for f in files), default=0) * 8, 8))    # one file's row order at a time
+        ids_all = stack.enter_context(DeviceBuffer(ctx, max(2 * id_rows * 8, 8)))
+        # one file's row order at a time
+        order_buf = stack.enter_context(DeviceBuffer(ctx, max(max((f.num_rows for f in files), default=0) * 8, 8)))
         off = ioff = 0
         for f, want, size, cols, (i_chain, i_draw) in zip(files, wants, sizes, colidx, ididx):
             M = f.num_rows
-            buf = arena.view(off, len(cols) * M * 8)
+            buf = stack.enter_context(arena.view(off, len(cols) * M * 8))      # file row order; the draws take a view of their own
             base, ibase = buf.ptr.value, ids_all.ptr.value + ioff * 8
             for j, c in enumerate(cols):
                 reqs.append((f, c, MCR_PQ_F64, base + j * M * 8))
             reqs.append((f, i_chain, MCR_PQ_I64, ibase))
             reqs.append((f, i_draw, MCR_PQ_I64, ibase + M * 8))
-            plan.append((want, M, buf, ioff))
-            bufs.append(buf)
+            plan.append((want, M, buf, C.c_void_p(ibase), C.c_void_p(ibase + M * 8)))
             off += size
             ioff += 2 * M
-        out = []
-        try:
-            decode(ctx, reqs)
-            # nearly every file is in (chain, draw) order: one round trip says so for all of them, and gives their chains
-            ordered = ctx.chain_layout_many([(ids_all.ptr.value + ioff * 8, ids_all.ptr.value + (ioff + M) * 8, M)
-                                             for _want, M, _buf, ioff in plan], cap=_LAYOUT_CAP)
-            for k, (want, M, buf, ioff) in enumerate(plan):
-                chain_ptr = C.c_void_p(ids_all.ptr.value + ioff * 8)
-                draw_ptr = C.c_void_p(ids_all.ptr.value + (ioff + M) * 8)
-                lay = (ordered[k][0], None, ordered[k][1]) if ordered[k] is not None else \
-                    _device_layout(ctx, chain_ptr, draw_ptr, M, order_buf)
-                if lay is None:                              # no 64-bit row key, or very many chains: the host's lexsort
-                    cd = _download(ctx, chain_ptr, np.int64, 2 * M)
-                    chain_ids, order, counts = _layout(cd[:M], cd[M:])
-                    if order is not None and want and M:
-                        dst = DeviceBuffer(ctx, len(want) * M * 8)
-                        bufs[k] = None
-                        order = np.ascontiguousarray(order, dtype=np.int64)
-                        try:
-                            ctx._check(ctx.lib.mcr_gather_rows_dev(ctx.handle, buf.ptr, len(want), M,
-                                                                   order.ctypes.data_as(C.POINTER(C.c_int64)), dst.ptr))
-                        finally:
-                            buf.free()
-                            buf = bufs[k] = dst
-                else:
-                    chain_ids, order, counts = lay           # order: order_buf, or None for rows in order
-                    if order is not None and want and M:
-                        dst = DeviceBuffer(ctx, len(want) * M * 8)
-                        bufs[k] = None
-                        try:
-                            ctx.gather_rows_order(buf.ptr, len(want), M, order.ptr, dst.ptr)
-                        finally:
-                            buf.free()
-                            buf = bufs[k] = dst
-                tensor = None
-                if len(counts) and np.all(counts == counts[0]):
-                    Cn, N = len(counts), int(counts[0])
-                    tensor = DeviceTensor(ctx, buf, (MCR_F64, Cn, N, len(want), N, 1, Cn * N))
-                out.append(DeviceDraws(tensor, buf, want, chain_ids, counts))
-        except BaseException:
-            for b in bufs:
-                if b is not None:
-                    b.free()
-            raise
-        finally:
-            ids_all.free()
-            order_buf.free()
+        decode(ctx, reqs)
+        # nearly every file is in (chain, draw) order: one round trip says so for all of them, and gives their chains
+        ordered = ctx.chain_layout_many([(cp, dp, M) for _want, M, _buf, cp, dp in plan], cap=_LAYOUT_CAP)
+        out = [handed.enter_context(draws_in_order(ctx, buf, want, M, cp, dp, order_buf, known))
+               for (want, M, buf, cp, dp), known in zip(plan, ordered)]
+        handed.pop_all()
         return out
-    finally:
-        for f, o in zip(files, owned):
-            if o:
-                f.close()
 
 
 def read_draws(ctx: "_ffi.Context", source, params: Iterable[str] | None = None) -> DeviceDraws:
@@ -262,31 +255,24 @@ def decode_columns(ctx: "_ffi.Context", f: ParquetFile, names: Sequence[str]):
     M = f.num_rows
     cols = [f.index(n) for n in names]               # KeyError for an unknown name before any device allocation
     kinds = [MCR_PQ_I64 if f.column_types[c] in (1, 2) else MCR_PQ_F64 for c in cols]
-    buf = DeviceBuffer(ctx, max(len(names) * M * 8, 8))
-    try:
+    with contextlib.ExitStack() as stack:
+        buf = stack.enter_context(DeviceBuffer(ctx, max(len(names) * M * 8, 8)))
         decode(ctx, [(f, c, k, buf.ptr.value + j * M * 8) for j, (c, k) in enumerate(zip(cols, kinds))])
-    except BaseException:
-        buf.free()
-        raise
+        stack.pop_all()
     return buf, kinds
 
 
 def read_columns(ctx: "_ffi.Context", source, columns: Iterable[str] | None = None) -> dict[str, np.ndarray]:
     """Host arrays of numeric columns decoded on the device (ints as int64, floats as float64)."""
-    f = source if isinstance(source, ParquetFile) else ParquetFile(source, ctx)
-    try:
+    with contextlib.ExitStack() as stack:
+        f = source if isinstance(source, ParquetFile) else stack.enter_context(ParquetFile(source, ctx))
         names = list(columns) if columns is not None else [n for n, t in zip(f.column_names, f.column_types) if t in NUMERIC]
         M = f.num_rows
         buf, kinds = decode_columns(ctx, f, names)
-        try:
+        with buf:
             raw = buf.download(np.int64, len(names) * M).reshape(len(names), M)
-        finally:
-            buf.free()
         return {n: (raw[j].copy() if k == MCR_PQ_I64 else raw[j].view(np.float64).copy())
                 for j, (n, k) in enumerate(zip(names, kinds))}
-    finally:
-        if not isinstance(source, ParquetFile):
-            f.close()
 
 
 def write_draws_dev(ctx: "_ffi.Context", path, columns, rows: int, row_group_rows: int = 0) -> int:
@@ -353,8 +339,8 @@ def summarize_files(ctx: "_ffi.Context", sources: Sequence, params: Sequence[Ite
         fast = _summarize_paths(ctx, [os.fspath(s_) for s_ in sources], min_chains, qs, diagnostics)
         if fast is not None:
             return fast
-    models = read_draws_many(ctx, sources, params)
-    try:
+    with contextlib.ExitStack() as stack:
+        models = [stack.enter_context(d) for d in read_draws_many(ctx, sources, params)]
         # Jobs: maximal runs of neighbouring models that sit back to back in the arena and share (C, N) are ONE
         # tensor with their parameters concatenated -- one kernel pipeline instead of one per model.
         jobs = []                                    # (first model, n models, tensor args, min_chains, diagnostics)
@@ -391,7 +377,7 @@ def summarize_files(ctx: "_ffi.Context", sources: Sequence, params: Sequence[Ite
                 yield j, t, {"min_chains": min_chains if diagnostics else 1, "quantiles": qs, "diagnostics": diagnostics}
 
         results = [None] * len(models)
-        with _ffi.value_errors(), closing(_ffi.pipeline(ctx, calls())) as done:
+        with _ffi.value_errors(), contextlib.closing(_ffi.pipeline(ctx, calls())) as done:
             for j, r in done:
                 if isinstance(r, McrError):
                     raise r
@@ -399,6 +385,3 @@ def summarize_files(ctx: "_ffi.Context", sources: Sequence, params: Sequence[Ite
                 results[k0:k1] = _ffi.split_result(r, [len(d.params) for d in models[k0:k1]])
         return [{} if r is None else dict(zip(d.params, _ffi.entries(r, qs, diagnostics)))
                 for d, r in zip(models, results)]
-    finally:
-        for d in models:
-            d.free()

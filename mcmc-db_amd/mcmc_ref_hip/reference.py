@@ -145,8 +145,7 @@ def export_draws(model: str, dest, params: Sequence[str] | None = None, chains: 
             if exc.code != _ffi.MCR_EINVAL:
                 raise
             return _export_arrow(model, dest, params, chains, format_, store)
-    sel = None
-    try:
+    with buf:
         cols = [_ffi.pq_column(n, t, buf.ptr.value + j * M * 8, 1, _ffi.MCR_PQW_I64 if k == _ffi.MCR_PQ_I64 else _ffi.MCR_PQW_F64)
                 for j, (n, t, k) in enumerate(zip(names, types, kinds))]
         if format_ == "parquet":
@@ -154,14 +153,12 @@ def export_draws(model: str, dest, params: Sequence[str] | None = None, chains: 
                 return _export_arrow(model, dest, params, chains, format_, store)
             with ctx.write_parquet(cols, M) as image:
                 parquet._write_view(dest, image.view)
-            return None
-        if chains is not None:
-            sel = ctx.select_rows(buf.ptr.value, M, [int(c) for c in chains])
-        parquet.write_csv_dev(ctx, dest, cols, M, row_index=sel)
-    finally:
-        if sel is not None:
-            sel[0].free()
-        buf.free()
+        elif chains is None:
+            parquet.write_csv_dev(ctx, dest, cols, M)
+        else:
+            rows, n = ctx.select_rows(buf.ptr.value, M, [int(c) for c in chains])
+            with rows:
+                parquet.write_csv_dev(ctx, dest, cols, M, row_index=(rows, n))
     return None
 
 
