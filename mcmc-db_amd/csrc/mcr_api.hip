@@ -26,7 +26,6 @@
 #include <vector>
 
 #include "mcr_kernels.hpp"
-#include "mcr_sort32.hpp"
 #include "mcr_diag.hpp"
 #include "mcr_fft.hpp"
 #include "mcr_ext.hpp"
@@ -195,7 +194,7 @@ struct mcr_ctx {
     int64_t k_launches[K_COUNT] = {0};
     double k_ms[K_COUNT] = {0};
     bool fft_on = true;      // MCR_FFT=0: long chains take the direct tier-3 rounds only (A/B measurements, parity tests)
-    bool f32_records = true; // MCR_F32_RECORDS=0: f32 tensors take the f64 kernels (widened by the tile sort) instead of mcr_sort32.hpp
+    bool f32_records = true; // MCR_F32_RECORDS=0: f32 tensors take the f64 kernels (widened by the tile sort) instead of the packed records (k_tile_sort32, RecSlots)
     bool splitters_pairwise = false;   // MCR_SPLITTERS_PAIRWISE=1: rank the regular samples pair by pair whatever their number (A/B, parity tests)
     double rho_band = kRhoBand;   // MCR_RHO_BAND: half-width of the guard band of the tier-3 scan (0 = decide on the raw values)
     DevBuf call_dev{4};                // the tensor calls (nested R-hat ... autocorrelation, one at a time): the call's result
@@ -439,7 +438,7 @@ WsPlan plan_ws(i64 M)
 struct PipeIn {
     const void* X;       // [pc][M] contiguous: f64 (user tensor or ingest buffer) or, x_f32, the user's f32 tensor itself
     bool x_f32 = false;
-    // f32 tensors take the packed records of mcr_sort32.hpp whenever the bucket partition applies (pooled arrays up to
+    // f32 tensors take the packed records (k_tile_sort32, RecSlots<u64>) whenever the bucket partition applies (pooled arrays up to
     // 512 K draws) and MCR_F32_RECORDS is not 0; otherwise the tile sort widens the f32 draws and the f64 kernels run
     bool records = false;
     bool idx16 = false;  // M <= kIdx16Max: 16-bit positions through the sort (else 32-bit)
@@ -681,98 +680,96 @@ int launch_splitters(mcr_ctx* ctx, const PipeIn& a, const KT* keys)
 
 // What the sort stage leaves: the ascending (key, position) order of every parameter in one of the two ping-pong buffer
 // pairs, the other pair free, and whether the bulk rank codes z_bulk are written already (bucket path with do_diag).
-// On the f32 records path the keys are packed (key, position) records and the positions are unused.
+// On the f32 records path the keys are packed (key, position) records and the positions are unused: pos / pos_free are then
+// the two position buffers in no particular order (which is which depends on the number of merge passes), nothing may read them.
 struct Sorted {
     double* keys; void* pos;
     double* keys_free; void* pos_free;
     bool ranked;
 };
 
-// Tile sort + (bucket partition | merge passes).
-template <typename IdxT>
-int sort_stage_t(mcr_ctx* ctx, PipeIn& a, Sorted& out)
+// The tile sort of the stage: k_tile_sort for pairs (f64 draws, or f32 widened on load), k_tile_sort32 for f32 records.
+template <class Slots>
+int launch_tile_sort(mcr_ctx* ctx, const PipeIn& a, typename Slots::KeyT* keys, typename Slots::PosT* pos, double* samp)
 {
-    const i64 M = a.M, pc = a.pc;
-    const unsigned py = (unsigned)pc;
-    constexpr size_t lds_tile = sort_lds_bytes<IdxT>(kTile);
-    // (the z lookup table of this M comes from the context's cache: get_ztab)
-    // 1. tile sort (+ moment partials, + regular samples when a tile is already a run)
-    const bool bucket = a.bk_B > 0;
-    double* const samp1 = (bucket && a.bk_R == kTile) ? a.samp : (double*)nullptr;
-    if (a.x_f32) {
-        LAUNCH(ctx, K_TILE_SORT, (k_tile_sort<kTileNT, kTileVT, IdxT, float>), dim3((unsigned)a.ntiles, py), dim3(kTileNT),
-               lds_tile, (const float*)a.X, M, a.kA, (IdxT*)a.iA, a.part, (int)a.ntiles, samp1,
+    const dim3 grid((unsigned)a.ntiles, (unsigned)a.pc);
+    if constexpr (std::is_same<Slots, RecSlots<u64>>::value) {
+        LAUNCH(ctx, K_TILE_SORT, (k_tile_sort32<kTileNT, kTileVT>), grid, dim3(kTileNT), (size_t)kTile * 8,
+               (const float*)a.X, a.M, keys, a.part, (int)a.ntiles, samp);
+    } else if (a.x_f32) {
+        LAUNCH(ctx, K_TILE_SORT, (k_tile_sort<kTileNT, kTileVT, typename Slots::PosT, float>), grid, dim3(kTileNT),
+               Slots::lds_bytes(kTile), (const float*)a.X, a.M, keys, pos, a.part, (int)a.ntiles, samp,
                ctx->guard_count.as<unsigned>() + 1);
     } else {
-        LAUNCH(ctx, K_TILE_SORT, (k_tile_sort<kTileNT, kTileVT, IdxT, double>), dim3((unsigned)a.ntiles, py), dim3(kTileNT),
-               lds_tile, (const double*)a.X, M, a.kA, (IdxT*)a.iA, a.part, (int)a.ntiles, samp1,
+        LAUNCH(ctx, K_TILE_SORT, (k_tile_sort<kTileNT, kTileVT, typename Slots::PosT, double>), grid, dim3(kTileNT),
+               Slots::lds_bytes(kTile), (const double*)a.X, a.M, keys, pos, a.part, (int)a.ntiles, samp,
                ctx->guard_count.as<unsigned>() + 1);
     }
-    double *kin = a.kA, *kout = a.kB;
-    IdxT *iin = (IdxT*)a.iA, *iout = (IdxT*)a.iB;
+    return MCR_OK;
+}
+
+// Tile sort + (bucket partition | merge passes), on (f64 key, position) pairs in the key and position buffers, or -- f32
+// tensors in the Arrow layout on the bucket path -- on packed records: those live in the f64 key buffers kA / kB (8 bytes
+// per draw), and the position buffers travel along unused.
+template <class Slots>
+int sort_stage_t(mcr_ctx* ctx, PipeIn& a, Sorted& out)
+{
+    using KeyT = typename Slots::KeyT;
+    using PosT = typename Slots::PosT;
+    const i64 M = a.M, pc = a.pc;
+    const unsigned py = (unsigned)pc;
+    constexpr bool kRec = Slots::kTail > 0;
+    constexpr size_t lds = Slots::lds_bytes(kTile);
+    // (the z lookup table of this M comes from the context's cache: get_ztab)
+    KeyT *kin = reinterpret_cast<KeyT*>(a.kA), *kout = reinterpret_cast<KeyT*>(a.kB);
+    PosT *iin = (PosT*)a.iA, *iout = (PosT*)a.iB;
+    // 1. tile sort (+ moment partials, + regular samples when a tile is already a run)
+    const bool bucket = a.bk_B > 0;
+    {
+        const int rc = launch_tile_sort<Slots>(ctx, a, kin, iin, (bucket && a.bk_R == kTile) ? a.samp : (double*)nullptr);
+        if (rc) return rc;
+    }
     const unsigned nblk = (unsigned)((M + kTile - 1) / kTile);
     // 2. pairwise merge-path passes: up to the run length of the bucket partition, or all the way
+    //    (two split points per workgroup: behind the pairs' slots, in static LDS next to the records')
     const i64 Rstop = bucket ? a.bk_R : M;
     for (i64 R = kTile; R < Rstop; R *= 2) {
-        LAUNCH(ctx, K_MERGE, (k_merge<kMergeNT, kMergeVT, false, IdxT>), dim3(nblk, py), dim3(kMergeNT), lds_tile + 256,
-               (const double*)kin, (const IdxT*)iin, kout, iout, M, R, (double*)nullptr, pc,
-               QArgs{}, (u32*)nullptr, (const i64*)nullptr);
+        LAUNCH(ctx, K_MERGE, (k_merge<kMergeNT, kMergeVT, Slots>), dim3(nblk, py), dim3(kMergeNT), lds + (kRec ? 0 : 256),
+               (const KeyT*)kin, (const PosT*)iin, kout, iout, M, R);
         std::swap(kin, kout);
         std::swap(iin, iout);
     }
     if (bucket) {
         // 3. exact k-way partition + in-LDS bucket merge, fused with ranks -> z
         if (a.bk_R != kTile)
-            LAUNCH(ctx, K_SPLITTERS, k_sample_runs<double>, dim3((unsigned)a.bk_k, py), dim3(256), 0, (const double*)kin, M,
+            LAUNCH(ctx, K_SPLITTERS, k_sample_runs<KeyT>, dim3((unsigned)a.bk_k, py), dim3(256), 0, (const KeyT*)kin, M,
                    a.bk_R, a.samp);
         {
-            const int rc = launch_splitters<double>(ctx, a, (const double*)kin);
+            const int rc = launch_splitters<KeyT>(ctx, a, (const KeyT*)kin);
             if (rc) return rc;
         }
         const unsigned pgrp = (unsigned)((pc + 7) / 8 * 8);   // XCD-aware 1-D grid (xcd_map)
-        LAUNCH(ctx, K_BUCKET_MERGE, (k_bucket_merge<kMergeNT, kMergeVT, IdxT>), dim3(pgrp * (unsigned)a.bk_B), dim3(kMergeNT),
-               lds_tile, (const double*)kin, (const IdxT*)iin, kout, iout, M, a.bk_k, a.bk_B, (const u32*)a.cut,
-               (const u32*)a.boff, a.do_diag ? a.zb : (u32*)nullptr, pc, a.bk_R);
+        // (two kernels, see k_bucket_merge; the scratch: in the pairs' top 64 key slots, 512 bytes behind the records)
+        u32* const zb = a.do_diag ? a.zb : (u32*)nullptr;
+        if constexpr (kRec) {
+            LAUNCH(ctx, K_BUCKET_MERGE, (k_bucket_merge32<kMergeNT, kMergeVT>), dim3(pgrp * (unsigned)a.bk_B), dim3(kMergeNT),
+                   lds + 512, (const u64*)kin, kout, M, a.bk_k, a.bk_B, (const u32*)a.cut, (const u32*)a.boff, zb, pc, a.bk_R);
+        } else {
+            LAUNCH(ctx, K_BUCKET_MERGE, (k_bucket_merge<kMergeNT, kMergeVT, PosT>), dim3(pgrp * (unsigned)a.bk_B), dim3(kMergeNT),
+                   lds, (const double*)kin, (const PosT*)iin, kout, iout, M, a.bk_k, a.bk_B, (const u32*)a.cut,
+                   (const u32*)a.boff, zb, pc, a.bk_R);
+        }
         std::swap(kin, kout);
         std::swap(iin, iout);
     }
-    out = Sorted{kin, iin, kout, iout, bucket};
-    return MCR_OK;
-}
-
-// f32 tensors (Arrow layout, bucket path): the same stage on packed (key, position) records (mcr_sort32.hpp).  The
-// record arrays live in the f64 key buffers kA / kB (8 bytes per draw); the position buffers stay unused.
-int sort_stage_rec(mcr_ctx* ctx, PipeIn& a, Sorted& out)
-{
-    const i64 M = a.M, pc = a.pc;
-    const unsigned py = (unsigned)pc;
-    u64 *rin = reinterpret_cast<u64*>(a.kA), *rout = reinterpret_cast<u64*>(a.kB);
-    LAUNCH(ctx, K_TILE_SORT, (k_tile_sort32<kTileNT, kTileVT>), dim3((unsigned)a.ntiles, py), dim3(kTileNT), (size_t)kTile * 8,
-           (const float*)a.X, M, rin, a.part, (int)a.ntiles, (a.bk_R == kTile) ? a.samp : (double*)nullptr);
-    const unsigned nblk = (unsigned)((M + kTile - 1) / kTile);
-    for (i64 R = kTile; R < a.bk_R; R *= 2) {
-        LAUNCH(ctx, K_MERGE, (k_merge32<kMergeNT, kMergeVT>), dim3(nblk, py), dim3(kMergeNT), rec_lds_bytes(kTile),
-               (const u64*)rin, rout, M, R);
-        std::swap(rin, rout);
-    }
-    if (a.bk_R != kTile)
-        LAUNCH(ctx, K_SPLITTERS, k_sample_runs<u64>, dim3((unsigned)a.bk_k, py), dim3(256), 0, (const u64*)rin, M, a.bk_R, a.samp);
-    {
-        const int rc = launch_splitters<u64>(ctx, a, (const u64*)rin);
-        if (rc) return rc;
-    }
-    const unsigned pgrp = (unsigned)((pc + 7) / 8 * 8);
-    LAUNCH(ctx, K_BUCKET_MERGE, (k_bucket_merge32<kMergeNT, kMergeVT>), dim3(pgrp * (unsigned)a.bk_B), dim3(kMergeNT),
-           rec_lds_bytes(kTile) + 512, (const u64*)rin, rout, M, a.bk_k, a.bk_B, (const u32*)a.cut, (const u32*)a.boff,
-           a.do_diag ? a.zb : (u32*)nullptr, pc, a.bk_R);
-    out = Sorted{reinterpret_cast<double*>(rout), a.iA, reinterpret_cast<double*>(rin), a.iB, true};
+    out = Sorted{reinterpret_cast<double*>(kin), iin, reinterpret_cast<double*>(kout), iout, bucket};
     return MCR_OK;
 }
 
 int sort_stage(mcr_ctx* ctx, PipeIn& a, Sorted& out)
 {
-    if (a.records) return sort_stage_rec(ctx, a, out);
-    return a.idx16 ? sort_stage_t<unsigned short>(ctx, a, out) : sort_stage_t<u32>(ctx, a, out);
+    if (a.records) return sort_stage_t<RecSlots<u64>>(ctx, a, out);
+    return a.idx16 ? sort_stage_t<PairSlots<unsigned short>>(ctx, a, out) : sort_stage_t<PairSlots<u32>>(ctx, a, out);
 }
 
 // Order statistics by the fold kernel's own workgroups (a launch less) while a parameter has few of them; a pooled
@@ -787,12 +784,12 @@ int launch_fold(mcr_ctx* ctx, const PipeIn& a, const Sorted& s)
     const unsigned fgrid = (unsigned)((a.pc + 7) / 8 * 8) * (unsigned)((a.M + (kTile - 64) - 1) / (kTile - 64));   // 4032 outputs per fold workgroup
     const i64* split = order_stats_in_fold(a) ? (const i64*)nullptr : (const i64*)a.split;
     if (a.records) {
-        LAUNCH(ctx, K_FOLD_MERGE, (k_merge<kMergeNT, kMergeVT, true, IdxT, u64>), dim3(fgrid), dim3(kMergeNT),
-               sort_lds_bytes<IdxT>(kTile), (const u64*)s.keys, (const IdxT*)nullptr, (double*)nullptr, (IdxT*)nullptr, a.M,
+        LAUNCH(ctx, K_FOLD_MERGE, (k_fold_merge<kMergeNT, kMergeVT, IdxT, u64>), dim3(fgrid), dim3(kMergeNT),
+               PairSlots<IdxT>::lds_bytes(kTile), (const u64*)s.keys, (const IdxT*)s.pos, (double*)nullptr, (IdxT*)nullptr, a.M,      // (positions unused: not null, the kernel offsets the pointer)
                (i64)0, a.d_res, a.pc, a.q, a.zt, split);
     } else {
-        LAUNCH(ctx, K_FOLD_MERGE, (k_merge<kMergeNT, kMergeVT, true, IdxT>), dim3(fgrid), dim3(kMergeNT),
-               sort_lds_bytes<IdxT>(kTile), (const double*)s.keys, (const IdxT*)s.pos, s.keys_free, (IdxT*)s.pos_free, a.M,
+        LAUNCH(ctx, K_FOLD_MERGE, (k_fold_merge<kMergeNT, kMergeVT, IdxT>), dim3(fgrid), dim3(kMergeNT),
+               PairSlots<IdxT>::lds_bytes(kTile), (const double*)s.keys, (const IdxT*)s.pos, s.keys_free, (IdxT*)s.pos_free, a.M,
                (i64)0, a.d_res, a.pc, a.q, a.zt, split);
     }
     return MCR_OK;

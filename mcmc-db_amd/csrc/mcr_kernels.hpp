@@ -6,15 +6,15 @@
 //   k_tile_sort     X (f64, or f32 widened on load) -> sorted 4096-draw tiles of (key f64, pooled position u16 | u32),
 //                   sorted as 64-bit records (upper 52 bits + tile slot), checked, as (key, position) pairs if that fails
 //                   + the tile's (count, mean, M2) + every 64th order statistic of each tile
-//                   (f32 tensors: the packed-record kernels of mcr_sort32.hpp take the first four places of this list)
-//   k_merge<false>  only for M > 64K: pairwise merge-path passes until at most 16 sorted runs remain
+//                   (f32 tensors: k_tile_sort32 and the RecSlots<u64> instances take the first four places of this list)
+//   k_merge         only for M > 64K: pairwise merge-path passes until at most 16 sorted runs remain
 //                   (k_sample_runs then takes the regular samples of those runs)
 //   k_splitters     exact k-way partition by regular sampling: deterministic bucket bound
 //   k_bucket_merge  per bucket: gather <= 16 sorted pieces, merge in LDS, write the pooled ascending
 //                   order, and (fused) tie-averaged ranks -> rank code -> time order                 (a7)
 //   (order statistics: quantiles, median, fold split point -- by the first wave of every fold workgroup;
 //    a k_order_stats launch of their own for Backend.stats calls and for pooled arrays beyond 64K)      (a2/a3/a8)
-//   k_merge<true>   |x - med| order by ONE merge of the two monotone halves (no second sort), fused
+//   k_fold_merge    |x - med| order by ONE merge of the two monotone halves (no second sort), fused
 //                   with the rank codes of the folded values, their scatter write-combined in LDS   (a8, a7)
 //   k_acov_seg / k_diag_combine(2) / k_tier3 (or k_long_list + k_dev_fill + FFT | k_acov_long + k_diag_long_scan)
 //                   (mcr_diag.hpp, mcr_fft.hpp) split R-hat + ESS for bulk and folded z, lags in three tiers;
@@ -35,11 +35,6 @@ enum ResField {
     R_MEAN = 0, R_STD, R_MEDIAN, R_RHAT, R_RHAT_BULK, R_RHAT_TAIL, R_ESS_BULK, R_ESS_TAIL,
     R_LAG_BULK, R_LAG_TAIL, R_BAD, R_Q0  // R_Q0 .. R_Q0 + nq - 1
 };
-
-#ifndef MCR_WCOMB
-#define MCR_WCOMB 1          // 0: the fold kernel scatters its codes as they come (A/B builds)
-#endif
-constexpr bool kWriteCombine = MCR_WCOMB != 0;
 
 struct QArgs {
     int nq;
@@ -297,28 +292,6 @@ __global__ void k_moments_final(const double* __restrict__ part, int S, i64 P, d
 // Also emits the moments (count, mean, M2) of its tile (so the draws are read from HBM once).
 // Partial tiles are padded with +inf (draws are finite or the call fails with MCR_ENONFINITE).
 // ------------------------------------------------------------------------------------------------
-// 16 registers per lane, fully static 60-comparator network (mcr_sortnet.h): every index is a
-// compile-time constant, so the keys stay in VGPRs (a loop-carried index here makes hipcc emulate
-// dynamic register indexing with 16-way select chains: 10x the instructions).
-template <int VT>
-__device__ __forceinline__ void thread_sort(double (&k)[VT], u32 (&ix)[VT])
-{
-    static_assert(VT == 16 || VT == 8, "sorting networks exist for 16 and 8 items per lane");
-#define MCR_CE(a, b)                                                        \
-    {                                                                       \
-        const bool sw = k[b] < k[a];                                        \
-        const double lo = sw ? k[b] : k[a], hi = sw ? k[a] : k[b];          \
-        const u32 ilo = sw ? ix[b] : ix[a], ihi = sw ? ix[a] : ix[b];       \
-        k[a] = lo; k[b] = hi; ix[a] = ilo; ix[b] = ihi;                     \
-    }
-    if constexpr (VT == 16) { MCR_NET16(MCR_CE) } else { MCR_NET8(MCR_CE) }
-#undef MCR_CE
-}
-
-#ifndef MCR_TILE_DPP_LEVELS
-#define MCR_TILE_DPP_LEVELS 3      // 0: every merge level in LDS; 2 / 3: the first two / three in registers (below); 2 only with MCR_TILE_REC=0
-#endif
-
 // The first two merge levels of the tile sort (16 -> 32 -> 64 sorted draws) without the LDS: bitonic merges across 2 and 4
 // lanes.  Lane L of a group holds the sorted draws 16 L .. 16 L + 15 of the group's run in its registers.  To merge the
 // ascending runs A and B of a group, draw e of A meets draw n-1-e of B (the partner lane is the mirror lane of the
@@ -331,6 +304,9 @@ __device__ __forceinline__ void thread_sort(double (&k)[VT], u32 (&ix)[VT])
 // the merge-path route.  A third level (8 lanes: row_half_mirror, then distances 32 and 16) costs the VALU of its LDS
 // form and still wins for the LDS instructions and the barrier pair it saves; a fourth (16 lanes: lane ^ 4 takes two
 // DPP movs per word) measured slower than its LDS form (tile sort 396 -> 408 us on 1000 parameters).  Ties keep their own side (stability is irrelevant: equal draws share one average rank).
+// (The helpers themselves -- lane_pair_stage_rec, lane_bitonic_merge16_rec, lane_merge_levels_rec -- are below, once for
+// every kind of register item.)
+//
 // b where the lane's bit of m is set, else a: one v_cndmask on a mask built on the scalar unit (the compiler's own lowering
 // of a per-lane choice between two compare results goes through 0 / 1 in VGPRs: six more VALU per exchange).
 __device__ __forceinline__ u32 select_by_mask(u32 a, u32 b, unsigned long long m)
@@ -343,63 +319,6 @@ __device__ __forceinline__ double select_by_mask(double a, double b, unsigned lo
 {
     return __hiloint2double((int)select_by_mask((u32)__double2hiint(a), (u32)__double2hiint(b), m),
                             (int)select_by_mask((u32)__double2loint(a), (u32)__double2loint(b), m));
-}
-
-// MIN_LANES: the lanes that keep the minimum of an exchange (the others keep the maximum)
-template <int CTRL, bool MIRROR, unsigned long long MIN_LANES>
-__device__ __forceinline__ void lane_pair_stage(double (&k)[16], u32 (&ix)[16])
-{
-    auto exchange = [](double& own, u32& own_i, double o, u32 oi) {
-        const unsigned long long lt = __builtin_amdgcn_ballot_w64(o < own), gt = __builtin_amdgcn_ballot_w64(own < o);
-        const unsigned long long take = (lt & MIN_LANES) | (gt & ~MIN_LANES);
-        own = select_by_mask(own, o, take);
-        own_i = select_by_mask(own_i, oi, take);
-    };
-#pragma unroll
-    for (int r = 0; r < (MIRROR ? 8 : 16); ++r) {
-        const int s = MIRROR ? 15 - r : r;                  // my register r meets the partner's register s
-        const double o_r = dpp_f64<CTRL>(k[s]);
-        const u32 oi_r = dpp_u32<CTRL>(ix[s]);
-        if (MIRROR) {
-            const double o_s = dpp_f64<CTRL>(k[r]);         // ... and my register s the partner's register r
-            const u32 oi_s = dpp_u32<CTRL>(ix[r]);
-            exchange(k[s], ix[s], o_s, oi_s);
-        }
-        exchange(k[r], ix[r], o_r, oi_r);
-    }
-}
-
-__device__ __forceinline__ void lane_bitonic_merge16(double (&k)[16], u32 (&ix)[16])
-{
-#define MCR_CE(a, b)                                                        \
-    {                                                                       \
-        const bool sw = k[b] < k[a];                                        \
-        const double lo = sw ? k[b] : k[a], hi = sw ? k[a] : k[b];          \
-        const u32 ilo = sw ? ix[b] : ix[a], ihi = sw ? ix[a] : ix[b];       \
-        k[a] = lo; k[b] = hi; ix[a] = ilo; ix[b] = ihi;                     \
-    }
-    // half-cleaners at distance 8, 4, 2, 1 (mcr_sortnet.h); every index a literal (a loop-carried index would make hipcc
-    // emulate dynamic register indexing with 16-way select chains)
-    MCR_BITONIC16(MCR_CE)
-#undef MCR_CE
-}
-
-// registers sorted per lane -> runs of 64 draws sorted across every aligned group of 4 lanes
-__device__ __forceinline__ void lane_merge_levels_16_to_64(double (&k)[16], u32 (&ix)[16])
-{
-    constexpr unsigned long long kEvenLanes = 0x5555555555555555ull, kLowPairs = 0x3333333333333333ull;
-    lane_pair_stage<0xB1, true, kEvenLanes>(k, ix);       // quad_perm [1,0,3,2]: 2 x 16 -> 32
-    lane_bitonic_merge16(k, ix);
-    lane_pair_stage<0x1B, true, kLowPairs>(k, ix);        // quad_perm [3,2,1,0]: 2 x 32 -> 64, mirror lane of the quad
-    lane_pair_stage<0xB1, false, kEvenLanes>(k, ix);      // half-cleaner at distance 16
-    lane_bitonic_merge16(k, ix);
-#if MCR_TILE_DPP_LEVELS >= 3
-    constexpr unsigned long long kLowQuads = 0x0F0F0F0F0F0F0F0Full;
-    lane_pair_stage<0x141, true, kLowQuads>(k, ix);       // row_half_mirror: 2 x 64 -> 128, mirror lane of the group of 8
-    lane_pair_stage<0x4E, false, kLowPairs>(k, ix);       // quad_perm [2,3,0,1]: half-cleaner at distance 32
-    lane_pair_stage<0xB1, false, kEvenLanes>(k, ix);      // half-cleaner at distance 16
-    lane_bitonic_merge16(k, ix);
-#endif
 }
 
 // Serial merge of up to VT outputs from LDS runs A = skey[pos16(a0 + .)] (na items) and
@@ -433,147 +352,24 @@ __device__ __forceinline__ void serial_merge(const double* skey, int a0, int na,
     }
 }
 
-#ifndef MCR_TILE_REC
-#define MCR_TILE_REC 1      // 1: f64 tiles are sorted as records, with the pair sort as the fallback (k_tile_sort below)
-#endif
-// The pair sort is a function of its own under the record sort: inlined, the two sorts' registers exceed the 128 that four
-// waves per SIMD allow, or spill on the record path.  As a call the record path has no spill; the callee's frame (104
-// bytes per lane, its callee-saved registers) is touched by falling tiles only.
-#if MCR_TILE_REC == 0
-#define MCR_TILE_PAIRS_INLINE __forceinline__
-#else
-#define MCR_TILE_PAIRS_INLINE __noinline__
-#endif
-
-// IdxT = the pooled-position payload: u16 when M < 65536 (C1 and every packaged model: 10 bytes per LDS slot, so FOUR
-// 4096-draw tiles are resident per CU instead of three, and 10 instead of 12 bytes per draw go to HBM and back),
-// u32 otherwise.  LDS: skey[T] then sidx[T], nothing else -- the single read "one slot past the last run" of
-// serial_merge lands on sidx[0] (in bounds, value never selected); the reduction scratch reuses skey at the end.
-template <typename IdxT> constexpr size_t sort_lds_bytes(int T) { return (size_t)T * (8 + sizeof(IdxT)); }
-
-// The tile sort on (f64 key, position) PAIRS: the whole kernel up to round 7, and since then what a workgroup falls back to
-// when its tile cannot be sorted as records (below); inlined as the kernel itself with -DMCR_TILE_REC=0.
-template <int NT, int VT, typename IdxT, typename XT>
-__device__ MCR_TILE_PAIRS_INLINE void tile_sort_pairs(const XT* __restrict__ X, i64 M,
-                                                      double* __restrict__ keys, IdxT* __restrict__ idx,
-                                                      double* __restrict__ part, int ntiles,
-                                                      double* __restrict__ samp)
-{
-    constexpr int T = NT * VT;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    double* skey = reinterpret_cast<double*>(smem);
-    IdxT* sidx = reinterpret_cast<IdxT*>(skey + T);
-    double* red = skey;      // only after the sorted tile has left LDS (barrier below)
-
-    const int tid = threadIdx.x, tile = blockIdx.x;
-    const i64 p = blockIdx.y;
-    const i64 base = (i64)tile * T;
-    const int count = (int)((M - base < (i64)T) ? M - base : (i64)T);
-    const XT* src = X + p * M + base;    // XT = float: f32 tensors in the Arrow layout are widened here, not by an ingest pass
-
-    // Lane tid takes draws i * NT + tid straight into its sort registers (coalesced loads, no staging pass through the LDS):
-    // the network and the merge levels sort whatever 16 draws a lane starts with.  Which of a tile's equal draws comes first
-    // therefore differs from a blocked hand-out; nothing downstream sees it (equal draws share one average rank).
-    // count == T is workgroup-uniform: a full tile (nine of C1's ten per parameter) takes the paths without a per-draw
-    // `e < count` test, chosen by a scalar branch around each of the three places that have one.
-    const bool full = count == T;
-    double k[VT];
-    u32 ix[VT];
-    double bad = 0.0;
-    auto load = [&](auto full_c) {
-        constexpr bool FULL = decltype(full_c)::value;
-#pragma unroll
-        for (int i = 0; i < VT; ++i) {
-            const int e = i * NT + tid;
-            const bool live = FULL || e < count;
-            // a pad slot re-reads the tile's last draw instead of skipping the load: a load under a per-lane test waits for
-            // its value inside the test, and the lane's 16 loads go out one round trip after the other
-            const double v = (double)src[FULL ? e : min(e, count - 1)];
-            k[i] = live ? v : INFINITY;
-            ix[i] = live ? (u32)(base + e) : 0xFFFFFFFFu;
-            bad += (live && !isfinite(v)) ? 1.0 : 0.0;
-        }
-    };
-    if (full) load(std::true_type{}); else load(std::false_type{});
-    thread_sort<VT>(k, ix);
-    constexpr bool kLaneLevels = MCR_TILE_DPP_LEVELS >= 2 && VT == 16;
-    if constexpr (kLaneLevels) lane_merge_levels_16_to_64(k, ix);
-    // (no barrier: this is the workgroup's first access to the LDS)
-#pragma unroll
-    for (int i = 0; i < VT; ++i) {
-        const int e = tid * VT + i;
-        skey[pos16(e)] = k[i];
-        sidx[posi(e)] = (IdxT)ix[i];
-    }
-    __syncthreads();
-
-    for (int coop = kLaneLevels ? (MCR_TILE_DPP_LEVELS >= 3 ? 16 : 8) : 2; coop <= NT; coop <<= 1) {
-        const int first = tid & ~(coop - 1);
-        const int run = VT * (coop >> 1);
-        const int a0 = first * VT, b0 = a0 + run;
-        const int diag = VT * (tid - first);
-        auto A = [&](int i) { return skey[pos16(a0 + i)]; };
-        auto B = [&](int j) { return skey[pos16(b0 + j)]; };
-        const int ai = merge_path32(A, run, B, run, diag);
-        int srcs[VT];
-        serial_merge<VT>(skey, a0, run, b0, run, ai, diag - ai, VT, k, srcs);
-#pragma unroll
-        for (int i = 0; i < VT; ++i) ix[i] = sidx[posi(srcs[i])];
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < VT; ++i) {
-            const int e = tid * VT + i;
-            skey[pos16(e)] = k[i];
-            sidx[posi(e)] = (IdxT)ix[i];
-        }
-        __syncthreads();
-    }
-
-    auto write_out = [&](auto full_c) {
-        constexpr bool FULL = decltype(full_c)::value;
-#pragma nounroll
-        for (int e = tid; e < (FULL ? T : count); e += NT) {
-            keys[p * M + base + e] = skey[pos16(e)];
-            idx[p * M + base + e] = sidx[posi(e)];
-        }
-    };
-    if (full) write_out(std::true_type{}); else write_out(std::false_type{});
-    // regular samples (every 64th order statistic of the tile) for the exact bucket partition
-    if (samp != nullptr && tid < T / 64) {
-        const int e = 64 * tid + 63;
-        samp[(p * ntiles + tile) * (T / 64) + tid] = (e < count) ? skey[pos16(e)] : INFINITY;
-    }
-    __syncthreads();                 // `red` aliases skey from here on
-    // Moments of the tile, two-pass like the reference (mean first, then squared deviations; compare.py:62-63), from the
-    // lane's VT sorted draws still in registers (the draws are read from HBM exactly once): k_finalize merges the
-    // tiles with Chan's update.  Slots at or beyond `count` hold the +inf pads.
-    double s1 = 0.0, s2 = 0.0, e1 = 0.0, mt = 0.0;
-    auto moments = [&](auto full_c) {
-        constexpr bool FULL = decltype(full_c)::value;
-        const int nlive = count - tid * VT;         // the lane's sorted slots [0, nlive) hold draws, the others pads
-#pragma unroll
-        for (int i = 0; i < VT; ++i) s1 += (FULL || i < nlive) ? k[i] : 0.0;
-        s1 = block_sum<NT>(s1, red);
-        mt = s1 / (double)count;
-        // second pass about mt; e1 = sum (x - mt) is what rounding left of the mean
-#pragma unroll
-        for (int i = 0; i < VT; ++i) { const double d = (FULL || i < nlive) ? k[i] - mt : 0.0; s2 = fma(d, d, s2); e1 += d; }
-    };
-    if (full) moments(std::true_type{}); else moments(std::false_type{});
-    block_sum3<NT>(s2, e1, bad, red);
-    if (tid == 0) store_slice_moments(part + (p * ntiles + tile) * kMomRec, mt, e1, s2, bad, (double)count);
-}
-
 // ------------------------------------------------------------------------------------------------
 // Sorting RECORDS: one 64-bit word per draw that orders by itself and carries its payload, so a compare-exchange is one
 // compare + four selects (or one minimum + one maximum) instead of one compare + six selects, a lane-pair exchange moves
 // two words instead of three, and nothing is gathered after a merge level.  R = u64 (f32 draws: key image << 32 |
-// position, mcr_sort32.hpp) or double (f64 draws: the draw with its low 12 mantissa bits replaced by its tile slot,
+// position, k_tile_sort32) or double (f64 draws: the draw with its low 12 mantissa bits replaced by its tile slot,
 // k_tile_sort below).
+// The register helpers of this section are written once, for any item R that has rec_ce, dpp_rec, select_by_mask and
+// `<`: the two records, and KeyPos -- the (f64 key, position) PAIR of the pair sort, three words that order by the key.
 // ------------------------------------------------------------------------------------------------
-#ifndef MCR_TILE_REC_MINMAX
-#define MCR_TILE_REC_MINMAX 1      // 0: double records are exchanged by compare + selects like the integer ones (A/B builds)
-#endif
+struct KeyPos { double k; u32 ix; };
+__device__ __forceinline__ bool operator<(const KeyPos& a, const KeyPos& b) { return a.k < b.k; }
+
+__device__ __forceinline__ u32 rec_key(u64 r) { return (u32)(r >> 32); }
+__device__ __forceinline__ u32 rec_pos(u64 r) { return (u32)r; }
+// the f64 value the statistics use
+__device__ __forceinline__ double key_f64(double k) { return k; }
+__device__ __forceinline__ double key_f64(u64 r) { return key_value(rec_key(r)); }
+
 template <typename R> __device__ __forceinline__ R rec_pad();
 template <> __device__ __forceinline__ u64 rec_pad<u64>() { return kRecPad; }
 template <> __device__ __forceinline__ double rec_pad<double>() { return INFINITY; }
@@ -590,19 +386,22 @@ __device__ __forceinline__ void rec_ce(u64& a, u64& b)
 // compiler cannot prove quiet -- one more instruction for every register that comes out of a DPP move.
 __device__ __forceinline__ void rec_ce(double& a, double& b)
 {
-#if MCR_TILE_REC_MINMAX
     double lo, hi;
     asm("v_min_f64 %0, %1, %2" : "=v"(lo) : "v"(a), "v"(b));
     asm("v_max_f64 %0, %1, %2" : "=v"(hi) : "v"(a), "v"(b));
     a = lo; b = hi;
-#else
-    const bool sw = b < a;
-    const double lo = sw ? b : a, hi = sw ? a : b;
-    a = lo; b = hi;
-#endif
+}
+__device__ __forceinline__ void rec_ce(KeyPos& a, KeyPos& b)
+{
+    const bool sw = b.k < a.k;
+    const double lo = sw ? b.k : a.k, hi = sw ? a.k : b.k;
+    const u32 ilo = sw ? b.ix : a.ix, ihi = sw ? a.ix : b.ix;
+    a.k = lo; b.k = hi; a.ix = ilo; b.ix = ihi;
 }
 
-// Register sort of VT records per lane (the networks of mcr_sortnet.h).
+// Register sort of VT items per lane: fully static networks (60 comparators for 16 registers, mcr_sortnet.h).  Every
+// index is a compile-time constant, so the items stay in VGPRs (a loop-carried index here makes hipcc emulate dynamic
+// register indexing with 16-way select chains: 10x the instructions).
 template <int VT, typename R>
 __device__ __forceinline__ void thread_sort_rec(R (&r)[VT])
 {
@@ -612,8 +411,8 @@ __device__ __forceinline__ void thread_sort_rec(R (&r)[VT])
 #undef MCR_CE
 }
 
-// lane_merge_levels_16_to_64 (+ the third level) on records: the first three merge levels of the tile sort (16 -> 128
-// records) as bitonic merges across 2, 4 and 8 lanes over DPP; records are distinct, so an exchange is one compare per side.
+// The first three merge levels of the tile sort (16 -> 128 items) as bitonic merges across 2, 4 and 8 lanes over DPP
+// (above); an exchange is one compare per side.
 template <int CTRL>
 __device__ __forceinline__ u64 dpp_rec(u64 v)
 {
@@ -624,6 +423,12 @@ __device__ __forceinline__ double dpp_rec(double v) { return dpp_f64<CTRL>(v); }
 __device__ __forceinline__ u64 select_by_mask(u64 a, u64 b, unsigned long long m)
 {
     return ((u64)select_by_mask((u32)(a >> 32), (u32)(b >> 32), m) << 32) | (u64)select_by_mask((u32)a, (u32)b, m);
+}
+template <int CTRL>
+__device__ __forceinline__ KeyPos dpp_rec(const KeyPos& v) { return KeyPos{dpp_f64<CTRL>(v.k), dpp_u32<CTRL>(v.ix)}; }
+__device__ __forceinline__ KeyPos select_by_mask(const KeyPos& a, const KeyPos& b, unsigned long long m)
+{
+    return KeyPos{select_by_mask(a.k, b.k, m), select_by_mask(a.ix, b.ix, m)};
 }
 
 template <int CTRL, bool MIRROR, unsigned long long MIN_LANES, typename R>
@@ -698,6 +503,207 @@ __device__ __forceinline__ void serial_merge_rec(const R* srec, int a0, int na, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// What a slot of the sort stage's LDS holds.  The tile sorts' shared parts and the merge pass are written once over
+// one of two layouts of a workgroup's T slots:
+//   PairSlots<IdxT>  an f64 key in skey[T], then its pooled position in sidx[T].  IdxT = u16 when M < 65536 (C1 and every
+//                    packaged model: 10 bytes per slot, so FOUR 4096-slot workgroups are resident per CU instead of three,
+//                    and 10 instead of 12 bytes per draw go to HBM and back), u32 otherwise.  Nothing else: the single read
+//                    "one slot past the last run" of serial_merge lands on sidx[0] (in bounds, never selected), and the
+//                    64 key slots at the top are free for scratch in every kernel that needs some (their runs are
+//                    bounded by T - 64).
+//   RecSlots<R>      one record in srec[T] that orders by itself and carries its position (R = u64: f32 draws; R = double:
+//                    the f64 tile sort, which only stores, reads and merges them).  Two more slots than records, so that the
+//                    read one past the last run stays in bounds (the tile sorts give exactly T and clamp instead: LIM).
+// KeyT / PosT are the element types of the arrays in memory (a record stage has no position arrays: its position pointers are never used).
+// An Item is a slot's content in registers.
+// ------------------------------------------------------------------------------------------------
+template <typename IdxT>
+struct PairSlots {
+    using KeyT = double;
+    using PosT = IdxT;
+    using Item = KeyPos;
+    static constexpr int kTail = 0;     // slots behind the T of the workgroup
+    static constexpr size_t lds_bytes(int T) { return (size_t)T * (8 + sizeof(IdxT)); }
+    double* skey;
+    IdxT* sidx;
+    __device__ __forceinline__ PairSlots(char* smem, int T)
+        : skey(reinterpret_cast<double*>(smem)), sidx(reinterpret_cast<IdxT*>(skey + T)) {}
+    static __device__ __forceinline__ Item load(const double* k, const IdxT* ix, i64 g) { return Item{k[g], (u32)ix[g]}; }
+    __device__ __forceinline__ void put(int e, const Item& v) const { skey[pos16(e)] = v.k; sidx[posi(e)] = (IdxT)v.ix; }
+    __device__ __forceinline__ double get(int e) const { return skey[pos16(e)]; }        // what the merges order by
+    // serial merge of `nout` <= VT outputs (serial_merge); the positions are gathered from the slots the keys came from
+    template <int VT, int LIM = 0>
+    __device__ __forceinline__ void merge(int a0, int na, int b0, int nb, int ai, int bi, int nout, Item (&out)[VT]) const
+    {
+        double k[VT];
+        int src[VT];
+        serial_merge<VT>(skey, a0, na, b0, nb, ai, bi, nout, k, src);
+#pragma unroll
+        for (int i = 0; i < VT; ++i) out[i] = Item{k[i], (u32)sidx[posi(src[i])]};
+    }
+    __device__ __forceinline__ void write(double* k, IdxT* ix, i64 g, int e) const { k[g] = skey[pos16(e)]; ix[g] = sidx[posi(e)]; }   // slot e -> element g
+};
+
+template <typename R>
+struct RecSlots {
+    using KeyT = R;
+    using PosT = u32;
+    using Item = R;
+    static constexpr int kTail = 2;
+    static constexpr size_t lds_bytes(int T) { return (size_t)(T + kTail) * 8; }
+    R* srec;
+    __device__ __forceinline__ RecSlots(char* smem, int) : srec(reinterpret_cast<R*>(smem)) {}
+    static __device__ __forceinline__ R load(const R* r, const u32*, i64 g) { return r[g]; }
+    __device__ __forceinline__ void put(int e, R v) const { srec[pos16(e)] = v; }
+    __device__ __forceinline__ R get(int e) const { return srec[pos16(e)]; }
+    // LIM > 0: see serial_merge_rec
+    template <int VT, int LIM = 0>
+    __device__ __forceinline__ void merge(int a0, int na, int b0, int nb, int ai, int bi, int nout, R (&out)[VT]) const
+    {
+        serial_merge_rec<VT, LIM>(srec, a0, na, b0, nb, ai, bi, nout, out);
+    }
+    __device__ __forceinline__ void write(R* r, const void*, i64 g, int e) const { r[g] = srec[pos16(e)]; }    // (no position array: a pointer nothing can be read or written through)
+};
+
+// ---- what the three tile sorts share: everything behind the lane's VT items sorted in registers ------------------
+// The merge levels in the LDS behind the three register levels: the lane's items go to its slots, then every level merges
+// pairs of runs by merge path and hands the lane its VT outputs in r[].  !STORE_LAST: the outputs of the last level stay in
+// registers only.  LIM: see serial_merge_rec.
+template <int NT, int VT, int LIM, bool STORE_LAST, class Slots>
+__device__ __forceinline__ void tile_merge_levels(const Slots& s, typename Slots::Item (&r)[VT])
+{
+    const int tid = threadIdx.x;
+    // (no barrier: this is the workgroup's first access to the LDS)
+#pragma unroll
+    for (int i = 0; i < VT; ++i) s.put(tid * VT + i, r[i]);
+    __syncthreads();
+    for (int coop = (VT == 16) ? 16 : 2; coop <= NT; coop <<= 1) {     // (16 registers per lane: lane_merge_levels_rec came first)
+        const int first = tid & ~(coop - 1);
+        const int run = VT * (coop >> 1);
+        const int a0 = first * VT, b0 = a0 + run;
+        const int diag = VT * (tid - first);
+        auto A = [&](int i) { return s.get(a0 + i); };
+        auto B = [&](int j) { return s.get(b0 + j); };
+        const int ai = merge_path32(A, run, B, run, diag);
+        s.template merge<VT, LIM>(a0, run, b0, run, ai, diag - ai, VT, r);
+        __syncthreads();
+        if (STORE_LAST || coop < NT) {
+#pragma unroll
+            for (int i = 0; i < VT; ++i) s.put(tid * VT + i, r[i]);
+            __syncthreads();
+        }
+    }
+}
+
+// The sorted tile from the LDS to out[g0 + e], coalesced.  count == T is workgroup-uniform: a full tile (nine of C1's ten
+// per parameter) takes the loop without a per-draw `e < count` test, chosen by a scalar branch -- here, in the kernels'
+// loads and in tile_moments.
+template <int NT, int VT, class Slots>
+__device__ __forceinline__ void tile_write_out(const Slots& s, typename Slots::KeyT* __restrict__ keys,
+                                               typename Slots::PosT* __restrict__ idx, i64 g0, int count)
+{
+    constexpr int T = NT * VT;
+    const int tid = threadIdx.x;
+    auto write_out = [&](auto full_c) {
+        constexpr bool FULL = decltype(full_c)::value;
+#pragma nounroll
+        for (int e = tid; e < (FULL ? T : count); e += NT) s.write(keys + g0, idx + g0, e, e);
+    };
+    if (count == T) write_out(std::true_type{}); else write_out(std::false_type{});
+}
+
+// The tile sorts run on a grid (ntiles, P): this workgroup's row in the per-tile tables
+__device__ __forceinline__ i64 tile_row(int ntiles) { return (i64)blockIdx.y * ntiles + (int)blockIdx.x; }
+
+// regular samples (every 64th order statistic of the tile) for the exact bucket partition, into samp (may be null)
+template <int NT, int VT, class Slots>
+__device__ __forceinline__ void tile_store_samples(const Slots& s, double* __restrict__ samp, int ntiles, int count)
+{
+    constexpr int T = NT * VT;
+    const int tid = threadIdx.x;
+    if (samp != nullptr && tid < T / 64) {
+        const int e = 64 * tid + 63;
+        samp[tile_row(ntiles) * (T / 64) + tid] = (e < count) ? key_f64(s.get(e)) : INFINITY;
+    }
+}
+
+// Moments of the tile, two-pass like the reference (mean first, then squared deviations; compare.py:62-63), from the
+// lane's VT sorted draws still in registers (the draws are read from HBM exactly once): val(i) = the draw in the lane's
+// sorted slot i as f64, slots at or beyond `count` hold pads.  The same values in the same slots, added in the same order,
+// whichever sort put them there.  `red`: the reduction scratch, the head of the LDS once the sorted tile has left it
+// (barrier before the call).  k_finalize merges the tiles' records in `part` with Chan's update.
+template <int NT, int VT, class VF>
+__device__ __forceinline__ void tile_moments(VF val, int count, double bad, double* red, double* __restrict__ part, int ntiles)
+{
+    const int tid = threadIdx.x;
+    double s1 = 0.0, s2 = 0.0, e1 = 0.0, mt = 0.0;
+    auto moments = [&](auto full_c) {
+        constexpr bool FULL = decltype(full_c)::value;
+        const int nlive = count - tid * VT;         // the lane's sorted slots [0, nlive) hold draws, the others pads
+#pragma unroll
+        for (int i = 0; i < VT; ++i) s1 += (FULL || i < nlive) ? val(i) : 0.0;
+        s1 = block_sum<NT>(s1, red);
+        mt = s1 / (double)count;
+        // second pass about mt; e1 = sum (x - mt) is what rounding left of the mean
+#pragma unroll
+        for (int i = 0; i < VT; ++i) { const double d = (FULL || i < nlive) ? val(i) - mt : 0.0; s2 = fma(d, d, s2); e1 += d; }
+    };
+    if (count == NT * VT) moments(std::true_type{}); else moments(std::false_type{});
+    block_sum3<NT>(s2, e1, bad, red);
+    if (tid == 0) store_slice_moments(part + tile_row(ntiles) * kMomRec, mt, e1, s2, bad, (double)count);
+}
+
+// The tile sort on (f64 key, position) PAIRS: the whole kernel up to round 7, and since then what a workgroup falls back to
+// when its tile cannot be sorted as records (below).
+// A function of its own under the record sort: inlined, the two sorts' registers exceed the 128 that four waves per SIMD
+// allow, or spill on the record path.  As a call the record path has no spill; the callee's frame (104 bytes per lane, its
+// callee-saved registers) is touched by falling tiles only.
+template <int NT, int VT, typename IdxT, typename XT>
+__device__ __noinline__ void tile_sort_pairs(const XT* __restrict__ X, i64 M,
+                                             double* __restrict__ keys, IdxT* __restrict__ idx,
+                                             double* __restrict__ part, int ntiles,
+                                             double* __restrict__ samp)
+{
+    constexpr int T = NT * VT;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const PairSlots<IdxT> s(smem, T);
+
+    const int tid = threadIdx.x, tile = blockIdx.x;
+    const i64 p = blockIdx.y;
+    const i64 base = (i64)tile * T;
+    const int count = (int)((M - base < (i64)T) ? M - base : (i64)T);
+    const XT* src = X + p * M + base;    // XT = float: f32 tensors in the Arrow layout are widened here, not by an ingest pass
+
+    // Lane tid takes draws i * NT + tid straight into its sort registers (coalesced loads, no staging pass through the LDS):
+    // the network and the merge levels sort whatever 16 draws a lane starts with.  Which of a tile's equal draws comes first
+    // therefore differs from a blocked hand-out; nothing downstream sees it (equal draws share one average rank).
+    KeyPos r[VT];
+    double bad = 0.0;
+    auto load = [&](auto full_c) {
+        constexpr bool FULL = decltype(full_c)::value;
+#pragma unroll
+        for (int i = 0; i < VT; ++i) {
+            const int e = i * NT + tid;
+            const bool live = FULL || e < count;
+            // a pad slot re-reads the tile's last draw instead of skipping the load: a load under a per-lane test waits for
+            // its value inside the test, and the lane's 16 loads go out one round trip after the other
+            const double v = (double)src[FULL ? e : min(e, count - 1)];
+            r[i].k = live ? v : INFINITY;
+            r[i].ix = live ? (u32)(base + e) : 0xFFFFFFFFu;
+            bad += (live && !isfinite(v)) ? 1.0 : 0.0;
+        }
+    };
+    if (count == T) load(std::true_type{}); else load(std::false_type{});
+    thread_sort_rec<VT>(r);
+    if constexpr (VT == 16) lane_merge_levels_rec(r);
+    tile_merge_levels<NT, VT, 0, true>(s, r);
+    tile_write_out<NT, VT>(s, keys, idx, p * M + base, count);
+    tile_store_samples<NT, VT>(s, samp, ntiles, count);
+    __syncthreads();                 // the reduction scratch takes the place of the keys from here on
+    tile_moments<NT, VT>([&](int i) { return r[i].k; }, count, bad, s.skey, part, ntiles);
+}
+
+// ------------------------------------------------------------------------------------------------
 // The tile sort proper: f64 draws as 64-bit records, with the pair sort above as the exact fallback.
 // An f64 key and a 12-bit tile slot do not fit 64 bits, but they almost do: two draws of one tile that agree in their upper
 // 52 bits and differ below lie within 2^-40 of each other, relatively -- rounded, tied or ordinary draws never do.  So
@@ -715,7 +721,6 @@ __device__ __forceinline__ void serial_merge_rec(const R* srec, int a0, int na, 
 // check.  Equal keys come out by slot instead of by hand-out; nothing downstream sees it.  Non-finite draws are counted and
 // sorted as a tiny finite stand-in (the call fails with MCR_ENONFINITE anyway), pads are +inf.  f32 draws widen to
 // doubles whose low 29 bits are zero: they never fall back.
-// -DMCR_TILE_REC=0: the pair sort alone; 2: every tile falls back after its record sort (tests, and the price of one).
 // `fallbacks` (may be null) counts the tiles that fell back (mcr_tile_fallback_count).
 // amdgpu_waves_per_eu(4): 40 KB of LDS put four workgroups = four waves per SIMD on a CU; told so, the compiler keeps kernel
 // and callee within 128 registers (two waves per SIMD otherwise).
@@ -726,17 +731,14 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void k_
                                                   double* __restrict__ part, int ntiles,
                                                   double* __restrict__ samp, unsigned* __restrict__ fallbacks)
 {
-#if MCR_TILE_REC == 0
-    tile_sort_pairs<NT, VT, IdxT, XT>(X, M, keys, idx, part, ntiles, samp);
-#else
     constexpr int T = NT * VT;
     constexpr u32 kSlotMask = 0xFFFu;
     static_assert(T <= 4096, "a record has 12 bits for the tile slot");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    double* srec = reinterpret_cast<double*>(smem);                          // records, then the rebuilt keys
-    unsigned short* slow = reinterpret_cast<unsigned short*>(srec + T);      // the draws' low 12 bits by slot ...
-    IdxT* sidx = reinterpret_cast<IdxT*>(srec + T);                          // ... and, once they are back in the keys, the positions
-    double* red = srec;      // only after the sorted tile has left LDS
+    const RecSlots<double> recs(smem, T);                                    // the records ...
+    const PairSlots<IdxT> s(smem, T);                                        // ... then the rebuilt keys and their positions
+    double* srec = recs.srec;
+    unsigned short* slow = reinterpret_cast<unsigned short*>(srec + T);      // the draws' low 12 bits by slot, where the positions will be
 
     const int tid = threadIdx.x, tile = blockIdx.x;
     const i64 p = blockIdx.y;
@@ -771,30 +773,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void k_
     };
     if (full) load(std::true_type{}); else load(std::false_type{});
     thread_sort_rec<VT>(r);
-    static_assert(MCR_TILE_DPP_LEVELS == 0 || MCR_TILE_DPP_LEVELS >= 3,
-                  "the record sort has all three register levels or none: build MCR_TILE_DPP_LEVELS=2 with MCR_TILE_REC=0");
-    constexpr bool kLaneLevels = MCR_TILE_DPP_LEVELS >= 3 && VT == 16;
-    if constexpr (kLaneLevels) lane_merge_levels_rec(r);
-#pragma unroll
-    for (int i = 0; i < VT; ++i) srec[pos16(tid * VT + i)] = r[i];
-    __syncthreads();
-    // (the read "one slot past the last run" of serial_merge_rec lands on slow[0..3]: in bounds, never selected)
-    for (int coop = kLaneLevels ? 16 : 2; coop <= NT; coop <<= 1) {
-        const int first = tid & ~(coop - 1);
-        const int run = VT * (coop >> 1);
-        const int a0 = first * VT, b0 = a0 + run;
-        const int diag = VT * (tid - first);
-        auto A = [&](int i) { return srec[pos16(a0 + i)]; };
-        auto B = [&](int j) { return srec[pos16(b0 + j)]; };
-        const int ai = merge_path32(A, run, B, run, diag);
-        serial_merge_rec<VT>(srec, a0, run, b0, run, ai, diag - ai, VT, r);
-        __syncthreads();
-        if (coop < NT) {                 // the last level's records stay in registers
-#pragma unroll
-            for (int i = 0; i < VT; ++i) srec[pos16(tid * VT + i)] = r[i];
-            __syncthreads();
-        }
-    }
+    if constexpr (VT == 16) lane_merge_levels_rec(r);
+    // (the read "one slot past the last run" of serial_merge_rec lands on slow[0..3]: in bounds, never selected; the last
+    //  level's records stay in registers)
+    tile_merge_levels<NT, VT, 0, false>(recs, r);
 
     // rebuild keys and positions of the lane's 16 consecutive sorted draws; check; stage them for the coalesced write-out
     double k[VT];
@@ -826,7 +808,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void k_
     if (lane == 0) { srec[wave] = k[0]; wflag[wave] = wave_viol ? 1 : 0; }
     if (lane == kWave - 1) srec[NW + wave] = k[VT - 1];
     __syncthreads();
-    bool fall = MCR_TILE_REC == 2;
+    bool fall = false;
 #pragma unroll
     for (int w = 0; w < NW; ++w) {
         fall |= wflag[w] != 0;
@@ -841,42 +823,69 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void k_
     // (every lane read its low bits before the first of the two barriers: the positions may take their place)
 #pragma unroll
     for (int i = 0; i < VT; ++i) {
-        srec[pos16(tid * VT + i)] = k[i];
-        sidx[posi(tid * VT + i)] = (IdxT)((u32)base + slot[i]);
+        // (spelt out: through s.put the compiler issues the sixteen key stores in one burst behind the position stores,
+        //  1.5 % of the kernel on 400 000-draw arrays)
+        s.skey[pos16(tid * VT + i)] = k[i];
+        s.sidx[posi(tid * VT + i)] = (IdxT)((u32)base + slot[i]);
     }
     __syncthreads();
+    tile_write_out<NT, VT>(s, keys, idx, p * M + base, count);
+    tile_store_samples<NT, VT>(s, samp, ntiles, count);
+    __syncthreads();                 // the reduction scratch takes the place of the keys from here on
+    tile_moments<NT, VT>([&](int i) { return k[i]; }, count, bad, srec, part, ntiles);
+}
 
-    auto write_out = [&](auto full_c) {
+// ------------------------------------------------------------------------------------------------
+// The tile sort of f32 draw tensors (BASELINE config 4: 4 x 100000 x 10000 f32): 4096 pooled f32 draws of one parameter
+// -> sorted records, the tile's moments (two-pass on the widened values, as k_tile_sort) and every 64th order statistic.
+//     record = order-preserving image of the f32 bits (f32_key) << 32 | pooled position
+// instead of an f64 key plus a separate position: 8 bytes per LDS slot and per HBM element instead of 12, one integer
+// compare per merge step that orders (value, position) at once, no payload gather after a merge level, and no widening
+// ingest pass over the tensor (it is read from HBM exactly once, as f32).  The stages behind it (k_merge, k_bucket_merge,
+// the fold) run on these records through RecSlots<u64>.  Same results as the f64 kernels bit for bit: widening f32 -> f64
+// preserves order and equality, so ranks, order statistics and the widened values the moments / fold step see are
+// identical.  +inf pads are kRecPad.  Reference spec of the whole stage: the `sorted(flat, key=...)` and average ranks of
+// src/mcmc_ref/diagnostics.py:101-122.
+// LDS: exactly T records, so that five tiles fit a CU; the merges clamp their reads to the last slot (LIM).
+// ------------------------------------------------------------------------------------------------
+template <int NT, int VT>
+__global__ __launch_bounds__(NT) void k_tile_sort32(const float* __restrict__ X, i64 M, u64* __restrict__ recs,
+                                                    double* __restrict__ part, int ntiles, double* __restrict__ samp)
+{
+    constexpr int T = NT * VT;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const RecSlots<u64> s(smem, T);
+
+    const int tid = threadIdx.x, tile = blockIdx.x;
+    const i64 p = blockIdx.y;
+    const i64 base = (i64)tile * T;
+    const int count = (int)((M - base < (i64)T) ? M - base : (i64)T);
+    const float* src = X + p * M + base;
+
+    // As tile_sort_pairs: lane tid takes draws i * NT + tid straight into its sort registers (no staging pass through the
+    // LDS).  Records are distinct (the position is the low word), so the sorted tile does not depend on which draws a lane
+    // starts with.
+    u64 r[VT];
+    double bad = 0.0;
+    auto load = [&](auto full_c) {
         constexpr bool FULL = decltype(full_c)::value;
-#pragma nounroll
-        for (int e = tid; e < (FULL ? T : count); e += NT) {
-            keys[p * M + base + e] = srec[pos16(e)];
-            idx[p * M + base + e] = sidx[posi(e)];
+#pragma unroll
+        for (int i = 0; i < VT; ++i) {
+            const int e = i * NT + tid;
+            const bool live = FULL || e < count;
+            const float v = src[FULL ? e : min(e, count - 1)];      // every load unconditional and in flight, as in k_tile_sort
+            bad += (live && !isfinite(v)) ? 1.0 : 0.0;
+            r[i] = live ? (((u64)f32_key(v) << 32) | (u64)(u32)(base + e)) : kRecPad;
         }
     };
-    if (full) write_out(std::true_type{}); else write_out(std::false_type{});
-    // regular samples (every 64th order statistic of the tile) for the exact bucket partition
-    if (samp != nullptr && tid < T / 64) {
-        const int e = 64 * tid + 63;
-        samp[(p * ntiles + tile) * (T / 64) + tid] = (e < count) ? srec[pos16(e)] : INFINITY;
-    }
-    __syncthreads();                 // `red` aliases srec from here on
-    // the tile's moments from the lane's sorted draws in registers: the same values in the same slots as in the pair sort,
-    // added in the same order
-    double s1 = 0.0, s2 = 0.0, e1 = 0.0, mt = 0.0;
-    auto moments = [&](auto full_c) {
-        constexpr bool FULL = decltype(full_c)::value;
-#pragma unroll
-        for (int i = 0; i < VT; ++i) s1 += (FULL || i < nlive) ? k[i] : 0.0;
-        s1 = block_sum<NT>(s1, red);
-        mt = s1 / (double)count;
-#pragma unroll
-        for (int i = 0; i < VT; ++i) { const double d = (FULL || i < nlive) ? k[i] - mt : 0.0; s2 = fma(d, d, s2); e1 += d; }
-    };
-    if (full) moments(std::true_type{}); else moments(std::false_type{});
-    block_sum3<NT>(s2, e1, bad, red);
-    if (tid == 0) store_slice_moments(part + (p * ntiles + tile) * kMomRec, mt, e1, s2, bad, (double)count);
-#endif
+    if (count == T) load(std::true_type{}); else load(std::false_type{});
+    thread_sort_rec<VT>(r);
+    if constexpr (VT == 16) lane_merge_levels_rec(r);
+    tile_merge_levels<NT, VT, T - 1, true>(s, r);
+    tile_write_out<NT, VT>(s, recs, reinterpret_cast<u32*>(recs), p * M + base, count);     // (records have no position array: the second pointer is never used)
+    tile_store_samples<NT, VT>(s, samp, ntiles, count);
+    __syncthreads();                 // the reduction scratch takes the place of the records from here on
+    tile_moments<NT, VT>([&](int i) { return key_f64(r[i]); }, count, bad, reinterpret_cast<double*>(smem), part, ntiles);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1083,40 +1092,118 @@ __device__ __forceinline__ i64 wave_order_stats(const KT* __restrict__ k, i64 M,
 }
 
 // ------------------------------------------------------------------------------------------------
-// Merge pass.  FOLD == false: merges pairs of sorted runs of length R (merge sort pass).
-// FOLD == true : produces the ascending order of |x - med| from the ascending order of x with a
-// single merge: the values below the median, walked downwards (med - x, non-decreasing because
-// rounding is monotone), against the values at or above it (x - med).  This replaces the second
-// full sort of src/mcmc_ref/diagnostics.py:93-98 + :110.  Each workgroup owns OB = NT*VT outputs.
-// FOLD, fused ranks: whether the block's first / last tie run goes on outside it is decided from the element just
+// Merge pass: merges pairs of sorted runs of length R (one pass of a merge sort).  Each workgroup owns OB = NT*VT
+// outputs: two waves find its two split points by merge path, all threads gather its stretch of the two runs into the LDS,
+// merge it there and write it out.
+// Slots: what the LDS holds and the pass writes -- PairSlots<IdxT> (sorted keys in `kin`, positions in `iin`) or
+// RecSlots<u64> (sorted f32 records in `kin`; `iin` / `iout` unused).
+// ------------------------------------------------------------------------------------------------
+template <int NT, int VT, class Slots>
+__global__ __launch_bounds__(NT) void k_merge(const typename Slots::KeyT* __restrict__ kin,
+                                              const typename Slots::PosT* __restrict__ iin,
+                                              typename Slots::KeyT* __restrict__ kout,
+                                              typename Slots::PosT* __restrict__ iout, i64 M, i64 R)
+{
+    using Item = typename Slots::Item;
+    constexpr int OB = NT * VT;                             // LDS slots = outputs per workgroup
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const Slots s(smem, OB);
+    // the two split points: behind the slots (pairs: the launch adds 256 bytes) or, where the dynamic LDS ends with the
+    // slots (records), in 16 static bytes
+    i64* sh;
+    if constexpr (Slots::kTail > 0) { __shared__ i64 sh_rec[2]; sh = sh_rec; }
+    else sh = reinterpret_cast<i64*>(smem + Slots::lds_bytes(OB));
+
+    const int tid = threadIdx.x;
+    const i64 p = blockIdx.y;
+    const i64 o0 = (i64)blockIdx.x * OB;
+    if (o0 >= M) return;
+    const typename Slots::KeyT* kp = kin + p * M;
+    const typename Slots::PosT* ip = iin + p * M;
+
+    const i64 pb = (o0 / (2 * R)) * (2 * R);
+    const i64 abase = pb, na = (M - pb < R) ? M - pb : R;
+    const i64 bbase = pb + na, nb = (M - bbase < R) ? M - bbase : R;
+    const i64 d0 = o0 - pb, tot = na + nb;
+    const i64 d1 = (d0 + OB < tot) ? d0 + OB : tot;
+
+    // (the pass orders by the stored element itself: the key, or the whole record)
+    auto GA = [&](i64 i) { return kp[abase + i]; };
+    auto GB = [&](i64 j) { return kp[bbase + j]; };
+    if (tid < 64) { const i64 r0 = merge_path_wave(GA, na, GB, nb, d0); if (tid == 0) sh[0] = r0; }
+    else if (tid < 128) { const i64 r1 = merge_path_wave(GA, na, GB, nb, d1); if (tid == 64) sh[1] = r1; }
+    __syncthreads();
+    const i64 ai0 = sh[0], ai1 = sh[1];
+    const i64 bi0 = d0 - ai0;
+    const int ca = (int)(ai1 - ai0), cb = (int)((d1 - ai1) - bi0);
+    const int total = ca + cb;
+    {   // gather the two runs: slot e = j * NT + tid; all VT loads of a lane are issued before the first LDS store waits for
+        // one (slots at or beyond `total` read element 0 and are not stored)
+        Item gv[VT];
+#pragma unroll
+        for (int j = 0; j < VT; ++j) {
+            const int e = j * NT + tid;
+            i64 g = (e < ca) ? abase + ai0 + e : bbase + bi0 + (e - ca);
+            g = (e < total) ? g : 0;
+            gv[j] = Slots::load(kp, ip, g);
+        }
+#pragma unroll
+        for (int j = 0; j < VT; ++j) {
+            const int e = j * NT + tid;
+            if (e < total) s.put(e, gv[j]);
+        }
+    }
+    __syncthreads();
+
+    const int diag = (tid * VT < total) ? tid * VT : total;
+    const int nout = (total - diag < VT) ? total - diag : VT;
+    auto A = [&](int i) { return s.get(i); };
+    auto B = [&](int j) { return s.get(ca + j); };
+    const int ai = merge_path32(A, ca, B, cb, diag);
+    Item out[VT];
+    s.template merge<VT>(0, ca, ca, cb, ai, diag - ai, nout, out);
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < VT; ++i)
+        if (i < nout) s.put(diag + i, out[i]);
+    __syncthreads();
+    for (int e = tid; e < total; e += NT) s.write(kout, iout, p * M + o0 + e, e);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Fold: produces the ascending order of |x - med| from the ascending order of x with a single merge: the values below the
+// median, walked downwards (med - x, non-decreasing because rounding is monotone), against the values at or above it
+// (x - med).  This replaces the second full sort of src/mcmc_ref/diagnostics.py:93-98 + :110.  The skeleton is k_merge's
+// (split points, gather, merge in the LDS), on (f64 key, position) pairs whatever the input: the folded keys are f64.
+// Fused ranks: whether the block's first / last tie run goes on outside it is decided from the element just
 // before and just behind the block in each run.  Those four neighbours are loaded WITH the gather, in four of its dead
 // slots (clamped index, no test in front of the load) and parked in the scratch; after the merge every thread compares
 // them with the block's edge keys in the LDS.  (They were four scalar loads behind the merge, each inside its own test
 // and waited for alone by one thread, between two barriers that are gone with them.)
+// KT = double: sorted keys in `kin`, positions in `iin`.  KT = u64: sorted f32 records in `kin`, `iin` unused -- the
+// keys are widened on the fly.  `R` is unused (the launch passes 0).
+// LDS: skey[OBS] then sidx[OBS] as in PairSlots<IdxT>, spelt out: through the slot type the kernel computes the same but
+// is scheduled differently (0.9 % slower on f32 records).
 // ------------------------------------------------------------------------------------------------
-// KT = double: sorted keys in `kin`, positions in `iin`.  KT = u64 (FOLD only): sorted f32 records in `kin`
-// (mcr_sort32.hpp), `iin` unused -- the fold step widens the keys on the fly, its own keys |x - med| are f64.
-template <int NT, int VT, bool FOLD, typename IdxT, typename KT = double>
-__global__ __launch_bounds__(NT) void k_merge(const KT* __restrict__ kin, const IdxT* __restrict__ iin,
-                                              double* __restrict__ kout, IdxT* __restrict__ iout, i64 M,
-                                              i64 R, double* __restrict__ res, i64 P,
-                                              QArgs q, u32* __restrict__ z, const i64* __restrict__ split_in)
+template <int NT, int VT, typename IdxT, typename KT = double>
+__global__ __launch_bounds__(NT) void k_fold_merge(const KT* __restrict__ kin, const IdxT* __restrict__ iin,
+                                                   double* __restrict__ kout, IdxT* __restrict__ iout, i64 M,
+                                                   i64 R, double* __restrict__ res, i64 P,
+                                                   QArgs q, u32* __restrict__ z, const i64* __restrict__ split_in)
 {
     constexpr int OBS = NT * VT;                            // LDS slots
-    // The fold kernel owns 64 outputs fewer than it has slots and keeps its scratch in the 64 key slots that frees:
+    // The kernel owns 64 outputs fewer than it has slots and keeps its scratch in the 64 key slots that frees:
     // its LDS is then exactly 4096 * (8 + sizeof(IdxT)) bytes, i.e. FOUR workgroups per CU with 16-bit positions.
-    constexpr int OB = FOLD ? OBS - 64 : OBS;               // outputs per workgroup
+    constexpr int OB = OBS - 64;                            // outputs per workgroup
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double* skey = reinterpret_cast<double*>(smem);
     IdxT* sidx = reinterpret_cast<IdxT*>(skey + OBS);
-    i64* sh = FOLD ? reinterpret_cast<i64*>(skey + OB) : reinterpret_cast<i64*>(sidx + OBS);
+    i64* sh = reinterpret_cast<i64*>(skey + OB);
 
     const int tid = threadIdx.x;
-    i64 p = blockIdx.y;
-    int blk = blockIdx.x;
-    if (FOLD) {   // 1-D XCD-aware grid (the fused z scatter of one parameter stays in one L2)
-        if (!xcd_map(P, (int)((M + OB - 1) / OB), p, blk)) return;
-    }
+    i64 p;
+    int blk;
+    if (!xcd_map(P, (int)((M + OB - 1) / OB), p, blk)) return;      // 1-D XCD-aware grid (the fused z scatter of one parameter stays in one L2)
     const i64 o0 = (i64)blk * OB;
     if (o0 >= M) return;
     const KT* kp = kin + p * M;
@@ -1126,42 +1213,28 @@ __global__ __launch_bounds__(NT) void k_merge(const KT* __restrict__ kin, const 
         if constexpr (sizeof(KT) == 8 && !__is_same(KT, double)) return (u32)kp[g]; else return (u32)ip[g];
     };
 
-    i64 abase, na, bbase, nb, d0;
-    double med = 0.0;
-    if (!FOLD) {
-        const i64 pb = (o0 / (2 * R)) * (2 * R);
-        abase = pb;
-        na = (M - pb < R) ? M - pb : R;
-        bbase = pb + na;
-        nb = (M - bbase < R) ? M - bbase : R;
-        d0 = o0 - pb;
-    } else {
-        // The order statistics of the parameter, by the first wave of EVERY fold workgroup (a launch of their own in round
-        // 2): the median and the split point are three to five dependent loads, the parameter's first workgroup also
-        // writes the quantiles and the median.
-        // (long arrays -- a hundred fold workgroups per parameter -- get them from a k_order_stats launch instead: split_in)
-        if (split_in != nullptr) {
-            if (tid == 0) { sh[0] = split_in[p]; reinterpret_cast<double*>(sh)[1] = res[R_MEDIAN * P + p]; }
-        } else if (tid < 64) {
-            double m_;
-            const i64 s_ = wave_order_stats(kp, M, q, blk == 0, res, P, p, m_);
-            if (tid == 0) { sh[0] = s_; reinterpret_cast<double*>(sh)[1] = m_; }
-        }
-        __syncthreads();
-        const i64 s = sh[0];
-        med = reinterpret_cast<double*>(sh)[1];
-        __syncthreads();
-        abase = s - 1;  // walked downwards
-        na = s;
-        bbase = s;
-        nb = M - s;
-        d0 = o0;
+    // The order statistics of the parameter, by the first wave of EVERY fold workgroup (a launch of their own in round
+    // 2): the median and the split point are three to five dependent loads, the parameter's first workgroup also
+    // writes the quantiles and the median.
+    // (long arrays -- a hundred fold workgroups per parameter -- get them from a k_order_stats launch instead: split_in)
+    if (split_in != nullptr) {
+        if (tid == 0) { sh[0] = split_in[p]; reinterpret_cast<double*>(sh)[1] = res[R_MEDIAN * P + p]; }
+    } else if (tid < 64) {
+        double m_;
+        const i64 s_ = wave_order_stats(kp, M, q, blk == 0, res, P, p, m_);
+        if (tid == 0) { sh[0] = s_; reinterpret_cast<double*>(sh)[1] = m_; }
     }
+    __syncthreads();
+    const i64 split = sh[0];
+    const double med = reinterpret_cast<double*>(sh)[1];
+    __syncthreads();
+    const i64 abase = split - 1;  // walked downwards
+    const i64 na = split, bbase = split, nb = M - split, d0 = o0;
     const i64 tot = na + nb;
     const i64 d1 = (d0 + OB < tot) ? d0 + OB : tot;
 
-    auto GA = [&](i64 i) -> double { return FOLD ? med - KEY(abase - i) : KEY(abase + i); };
-    auto GB = [&](i64 j) -> double { return FOLD ? KEY(bbase + j) - med : KEY(bbase + j); };
+    auto GA = [&](i64 i) -> double { return med - KEY(abase - i); };
+    auto GB = [&](i64 j) -> double { return KEY(bbase + j) - med; };
     if (tid < 64) { const i64 r0 = merge_path_wave(GA, na, GB, nb, d0); if (tid == 0) sh[0] = r0; }
     else if (tid < 128) { const i64 r1 = merge_path_wave(GA, na, GB, nb, d1); if (tid == 64) sh[1] = r1; }
     __syncthreads();
@@ -1170,10 +1243,10 @@ __global__ __launch_bounds__(NT) void k_merge(const KT* __restrict__ kin, const 
     const int ca = (int)(ai1 - ai0), cb = (int)((d1 - ai1) - bi0);
     const int total = ca + cb;
 
-    // The fold's edge neighbours: the element just before and just behind the block in each run, which decide after the
-    // merge whether the first / last tie run goes on outside the block.  Their places follow from s and the two split
-    // points, so they ride with the gather: the slots OB .. OB + 3 are dead in every workgroup (total <= OB), and the
-    // four lanes that own them load a neighbour there instead of element 0 -- index clamped into [0, M), no test in
+    // The edge neighbours: the element just before and just behind the block in each run, which decide after the
+    // merge whether the first / last tie run goes on outside the block.  Their places follow from the split point and the
+    // two diagonals' split points, so they ride with the gather: the slots OB .. OB + 3 are dead in every workgroup
+    // (total <= OB), and the four lanes that own them load a neighbour there instead of element 0 -- index clamped into [0, M), no test in
     // front of the load -- and park it, folded like GA / GB fold it, in sh[kEdge ..].  A neighbour that does not exist
     // (the block starts or ends a run) is parked as NaN, which equals no key.
     // sh: [0, 2) split point and median, then the two diagonals' split points; [2, 10) the edge bounds; [12, 20) the
@@ -1183,15 +1256,15 @@ __global__ __launch_bounds__(NT) void k_merge(const KT* __restrict__ kin, const 
         // LDS store waits for one (slots at or beyond `total` read element 0 and are not stored)
         double gv[VT]; u32 gi[VT];
         const int edge = tid - (OB - (VT - 1) * NT);                  // 0 .. 3 in the lanes of the slots OB .. OB + 3
-        const bool is_edge = FOLD && edge >= 0 && edge < 4;
+        const bool is_edge = edge >= 0 && edge < 4;
         bool edge_there = false;
 #pragma unroll
         for (int j = 0; j < VT; ++j) {
             const int e = j * NT + tid;
             bool inA = e < ca;
-            i64 g = inA ? (FOLD ? abase - (ai0 + e) : abase + ai0 + e) : bbase + bi0 + (e - ca);
+            i64 g = inA ? abase - (ai0 + e) : bbase + bi0 + (e - ca);
             g = (e < total) ? g : 0;
-            if (FOLD && j == VT - 1) {
+            if (j == VT - 1) {
                 // A before: GA(ai0 - 1), A behind: GA(ai1), B before: GB(bi0 - 1), B behind: GB(bi1)
                 const i64 bi1 = d1 - ai1;
                 const bool behind = (edge & 1) != 0, inB = (edge & 2) != 0;
@@ -1203,7 +1276,7 @@ __global__ __launch_bounds__(NT) void k_merge(const KT* __restrict__ kin, const 
                 inA = is_edge ? !inB : inA;
             }
             const double x = KEY(g);
-            gv[j] = FOLD ? (inA ? med - x : x - med) : x;
+            gv[j] = inA ? med - x : x - med;
             gi[j] = POS(g);
         }
 #pragma unroll
@@ -1235,7 +1308,7 @@ __global__ __launch_bounds__(NT) void k_merge(const KT* __restrict__ kin, const 
         }
     }
     __syncthreads();
-    if (!FOLD || z == nullptr) {
+    if (z == nullptr) {     // the folded order itself, for a caller without rank codes
         for (int e = tid; e < total; e += NT) {
             kout[p * M + o0 + e] = skey[pos16(e)];
             iout[p * M + o0 + e] = sidx[posi(e)];
@@ -1269,7 +1342,7 @@ __global__ __launch_bounds__(NT) void k_merge(const KT* __restrict__ kin, const 
     const i64 glast = sh[2 + 5] + sh[2 + 7];    // upper bounds (both runs) of the last value
     int rs[VT], re[VT];
     block_tie_runs<NT, VT>([&](int g) { return skey[pos16(g)]; }, total, reinterpret_cast<int*>(sh + 12), rs, re);
-    const bool by_line = kWriteCombine && M <= 65535;        // (workgroup-uniform)
+    const bool by_line = M <= 65535;        // (workgroup-uniform)
     u32 hcode[VT], hpos[VT];
 #pragma unroll
     for (int i = 0; i < VT; ++i) {
@@ -1323,7 +1396,7 @@ __host__ __device__ inline size_t splitters_lds_bytes(int S, int B, int k, int m
 //          rank in the strict order (value, run, position), since the merges are stable and the runs enter in order.
 //          ~190 LDS round trips per thread on the stress shape instead of 6.5 samples x 12 runs x 9 probes = 700
 //          (k_splitters was 12.4 ms of its 216 ms step, and the first kernel of the long-chain profile: VERDICT r3 item 8).
-template <typename KT, int MVT>      // KT = double (sorted keys) or u64 (sorted f32 records, mcr_sort32.hpp)
+template <typename KT, int MVT>      // KT = double (sorted keys) or u64 (sorted f32 records)
 __global__ __launch_bounds__(1024) void k_splitters(const KT* __restrict__ keys,
                                                     const double* __restrict__ samp, i64 M, int k, int B,
                                                     int D, i64 R, u32* __restrict__ cut, u32* __restrict__ boff)
@@ -1529,6 +1602,10 @@ __device__ __forceinline__ i64 bucket_neighbour(int lane, int k, i64 R, i64 M, c
 // neighbours that tell whether an edge tie run goes on in the next bucket are loaded with the gather, in its dead
 // last slots, and parked in the scratch until the rounds are done (they were two guarded loads per lane behind them).
 // Replaces log2(k) global merge passes + k_rank_z of the first version.
+// Written out once for pairs (here) and once for f32 records (k_bucket_merge32 below), unlike the merge pass and the tile
+// sorts: one text over PairSlots / RecSlots computes the same, but the compiler allocates it differently (pairs with 16-bit
+// positions 55 -> 60 VGPRs, records 48 -> 50), and these two kernels are kept at the registers they were tuned at.  A change
+// to one of them belongs in the other as well.
 // ------------------------------------------------------------------------------------------------
 template <int NT, int VT, typename IdxT>
 __global__ __launch_bounds__(NT) void k_bucket_merge(const double* __restrict__ kin, const IdxT* __restrict__ iin,
@@ -1700,6 +1777,160 @@ __global__ __launch_bounds__(NT) void k_bucket_merge(const double* __restrict__ 
             // (scattered as it is: with four merge rounds to overlap them, this kernel's stores are hidden already --
             //  scatter_codes_by_line here measured 382 -> 382 us per 1000 parameters)
             z[p * M + min((u32)sidx[posi(e)], (u32)(M - 1))] = (u32)(gs + ge);   // code of the tie run: rank = (code + 1) / 2
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Bucket merge on f32 records (k_bucket_merge above, line for line): gather <= k sorted pieces, merge in LDS, write the
+// pooled ascending records and -- fused -- the rank code of every draw to time order.
+// ------------------------------------------------------------------------------------------------
+template <int NT, int VT>
+__global__ __launch_bounds__(NT) void k_bucket_merge32(const u64* __restrict__ rin, u64* __restrict__ rout, i64 M,
+                                                       int k, int B, const u32* __restrict__ cut,
+                                                       const u32* __restrict__ boff, u32* __restrict__ z, i64 P, i64 R)
+{
+    constexpr int T = NT * VT;
+    static_assert(T == 4096, "the partition bound of k_splitters assumes 4096-slot buckets");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    u64* srec = reinterpret_cast<u64*>(smem);
+    int* sst = reinterpret_cast<int*>(srec + T + 2);   // padded piece starts [k+1]; the scratch is laid out as in k_bucket_merge
+    int* spl = sst + kBkLen;                            // piece lengths [k]
+    int* sps = sst + kBkSrc;                            // piece source offsets in tile [k]
+    int* sext = sst + kBkExt;                           // [2] does the first / last tie run go on outside the bucket?
+    i64* sedge = reinterpret_cast<i64*>(sst + kBkEdge); // [4] global run bounds of the edge values
+    u64* sne = reinterpret_cast<u64*>(sst + kBkNext);   // [2k] the runs' keys just before / behind their pieces
+    static_assert(2 * (NT / kWave) <= 4 * kMaxBucketTiles, "the tie-run scratch takes the neighbours' place");
+
+    const int tid = threadIdx.x;
+    i64 p;
+    int b;
+    if (!xcd_map(P, B, p, b)) return;
+    const u64* rp = rin + p * M;
+    const u32* c0 = cut + (p * (B + 1) + b) * k;
+    const u32* c1 = c0 + k;
+    if (k < 1 || k > kMaxBucketTiles) return;       // (the scratch holds sixteen pieces)
+    if (tid < kWave) bucket_piece_table(c0, c1, k, sst, spl, sps);
+    __syncthreads();
+    const int padded = sst[k];
+    const int total = (int)(boff[p * (B + 1) + b + 1] - boff[p * (B + 1) + b]);
+    const i64 obase = boff[p * (B + 1) + b];
+    if (padded > T - 64 || total < 0 || total > padded || obase + total > M) return;   // never with a valid partition
+    // the runs' records just before / behind this bucket's pieces ride in the gather's dead last slots (see
+    // k_bucket_merge); a neighbour that does not exist is parked as a value no 32-bit key equals
+    const int ne_lane = tid - (T - 64 - (VT - 1) * NT);
+    bool ne_there = false;
+    i64 ne_g = 0;
+    if (ne_lane >= 0) ne_g = bucket_neighbour(ne_lane, k, R, M, spl, sps, ne_there);
+    const bool is_ne = ne_lane >= 0 && ne_lane < 2 * k;
+    u64 ne = 0;
+    {   // gather: one piece search per 16-slot chunk, all VT loads in flight together (see k_bucket_merge)
+        const int lane = tid & 63, wv = tid >> 6;
+        u32 my_g = 0; int my_n = 0;
+        if ((lane & 15) < VT) {
+            const int e0 = (lane & 15) * NT + 64 * wv + 16 * (lane >> 4);
+            if (e0 < padded) {
+                int t = 0;
+#pragma unroll
+                for (int step = 8; step > 0; step >>= 1)
+                    if (t + step < k && e0 >= sst[t + step]) t += step;
+                const int o = e0 - sst[t];
+                my_n = spl[t] - o;
+                my_g = (u32)((i64)t * R) + (u32)sps[t] + (u32)o;
+            }
+        }
+        u64 gr[VT];
+#pragma unroll
+        for (int j = 0; j < VT; ++j) {
+            const int within = lane & 15;
+            const u32 g0 = (u32)row_lane((int)my_g, j);      // lane j of my row of 16 looked the chunk up
+            const int n = row_lane(my_n, j);
+            const bool live = within < n;
+            i64 g = live ? (i64)(g0 + (u32)within) : 0;
+            if (j == VT - 1) g = is_ne ? ne_g : g;
+            const u64 r = rp[g];
+            gr[j] = live ? r : kRecPad;
+            if (j == VT - 1) ne = r;
+        }
+#pragma unroll
+        for (int j = 0; j < VT; ++j) {
+            const int e = j * NT + tid;
+            if (e < padded) srec[pos16(e)] = gr[j];
+        }
+    }
+    if (is_ne) sne[ne_lane] = ne_there ? (u64)rec_key(ne) : ~0ull;
+    wait_loads();
+    __syncthreads();
+    const int chunk0 = tid * VT;
+    int mypiece = 0;      // the piece that holds slot chunk0 (pieces are padded to 16 >= VT slots)
+#pragma unroll
+    for (int step = 8; step > 0; step >>= 1)
+        if (mypiece + step < k && chunk0 >= sst[mypiece + step]) mypiece += step;
+    for (int w = 1; w < k; w <<= 1) {
+        u64 r[VT];
+        bool moved = false;
+        if (chunk0 < padded) {
+            const int ra = mypiece & ~(2 * w - 1);
+            const int a0 = sst[ra];
+            const int a1 = sst[(ra + w < k) ? ra + w : k];
+            const int b1 = sst[(ra + 2 * w < k) ? ra + 2 * w : k];
+            const int na = a1 - a0, nb = b1 - a1, diag = chunk0 - a0;
+            moved = nb > 0;
+            if (moved) {
+                auto A = [&](int i) { return srec[pos16(a0 + i)]; };
+                auto Bf = [&](int j) { return srec[pos16(a1 + j)]; };
+                const int ai = merge_path32(A, na, Bf, nb, diag);
+                serial_merge_rec<VT>(srec, a0, na, a1, nb, ai, diag - ai, VT, r);
+            }
+        }
+        __syncthreads();
+        if (moved) {
+#pragma unroll
+            for (int i = 0; i < VT; ++i) srec[pos16(chunk0 + i)] = r[i];
+        }
+        __syncthreads();
+    }
+    for (int e = tid; e < total; e += NT) rout[p * M + obase + e] = srec[pos16(e)];
+    if (z == nullptr || total == 0) return;
+    // tie runs that continue in a neighbouring bucket: look at the record just before / after this bucket's piece in
+    // every run; only then pay for the bound searches
+    if (tid < 4) sedge[tid] = 0;
+    const u32 kfirst = rec_key(srec[pos16(0)]), klast = rec_key(srec[pos16(total - 1)]);
+    if (tid < kWave) {
+        const int t = (tid < k) ? tid : k - 1;
+        const bool e0 = tid < k && sne[t] == (u64)kfirst;
+        const bool e1 = tid < k && sne[k + t] == (u64)klast;
+        const bool a0 = __ballot(e0) != 0, a1 = __ballot(e1) != 0;
+        if (tid == 0) { sext[0] = a0; sext[1] = a1; }
+    }
+    __syncthreads();
+    const bool ext0 = sext[0] != 0, ext1 = sext[1] != 0;
+    if ((ext0 || ext1) && tid < 2 * k) {
+        const int t = tid % k, which = tid / k;           // 0: first value, 1: last value
+        const u32 v = which ? klast : kfirst;
+        const i64 tbase = (i64)t * R;
+        const int cnt = (int)((M - tbase < R) ? M - tbase : R);
+        const u64* a = rp + tbase;
+        int lo = 0, hi = cnt;
+        while (lo < hi) { const int m = (lo + hi) >> 1; if (rec_key(a[m]) < v) lo = m + 1; else hi = m; }
+        const int lb = lo;
+        hi = cnt;
+        while (lo < hi) { const int m = (lo + hi) >> 1; if (!(v < rec_key(a[m]))) lo = m + 1; else hi = m; }
+        atomicAdd(reinterpret_cast<unsigned long long*>(&sedge[2 * which]), (unsigned long long)lb);
+        atomicAdd(reinterpret_cast<unsigned long long*>(&sedge[2 * which + 1]), (unsigned long long)lo);
+    }
+    __syncthreads();
+    int rs[VT], re[VT];
+    block_tie_runs<NT, VT>([&](int g) { return rec_key(srec[pos16(g)]); }, total, sst + kBkNext, rs, re);
+#pragma unroll
+    for (int i = 0; i < VT; ++i) {
+        const int e = tid * VT + i;
+        if (e < total) {
+            const u64 r = srec[pos16(e)];
+            i64 gs = obase + rs[i], ge = obase + re[i];
+            if (ext0 && rec_key(r) == kfirst) gs = sedge[0];
+            if (ext1 && rec_key(r) == klast) ge = sedge[3];
+            z[p * M + min(rec_pos(r), (u32)(M - 1))] = (u32)(gs + ge);   // code of the tie run: rank = (code + 1) / 2
         }
     }
 }

@@ -519,7 +519,7 @@ def test_moments_with_an_outlying_first_draw(ctx, oracle):
 
 
 def test_f32_records_equal_the_widened_path(ctx, oracle, monkeypatch):
-    """f32 tensors in the Arrow layout are sorted as packed (key, position) records (mcr_sort32.hpp, VERDICT r1 item
+    """f32 tensors in the Arrow layout are sorted as packed (key, position) records (k_tile_sort32 and RecSlots in mcr_kernels.hpp, VERDICT r1 item
     4).  Widening f32 -> f64 keeps order and equality, so EVERY output must be bit-identical to the f64 kernels run on
     the same draws (MCR_F32_RECORDS=0), and equal to the oracle: one tile, many tiles, the pre-merged long path
     (N = 100000 geometry), heavy ties, +-0, denormals, huge magnitudes."""

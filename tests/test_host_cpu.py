@@ -265,7 +265,7 @@ int main(void) {
 
 
 def test_register_merge_levels_merge_every_pair_of_sorted_01_runs(tmp_path):
-    """The tile sort's merge levels in registers (csrc/mcr_kernels.hpp lane_merge_levels_16_to_64 and its third level):
+    """The tile sort's merge levels in registers (csrc/mcr_kernels.hpp lane_merge_levels_rec):
     a group of 2 / 4 / 8 lanes with 16 registers each holds two sorted runs; the mirror exchange with the partner lane
     (lane ^ 1, mirror lane of the quad, mirror lane of the group of 8; mirror register), the half-cleaners across lanes
     (lane ^ 2, lane ^ 1; same register) and the 16-input bitonic merge of mcr_sortnet.h inside each lane must leave the

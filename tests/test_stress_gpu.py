@@ -1,6 +1,6 @@
 """BASELINE config 4 at FULL size in the `-m gpu` suite: 4 x 100000 x 10000 f32 =
 16 GB of draws generated on the device, ALL 10 000 parameters through the full pipeline (chunked through the
-workspace; f32 tensors are sorted as packed records, csrc/mcr_sort32.hpp), checked by
+workspace; f32 tensors are sorted as packed records, k_tile_sort32 and RecSlots in csrc/mcr_kernels.hpp), checked by
 
   * size-independent properties over every parameter (the generator's location / scale, ordered quantiles, median ==
     q50, 0 < ESS <= M, rhat = max(bulk, tail) < 1.01 for iid draws, non-negative integer lags), and
