@@ -29,6 +29,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#pragma GCC visibility push(default)
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -1172,4 +1173,5 @@ int mcr_parse_json_number(const char* text, size_t len, double* value, int* is_i
 #ifdef __cplusplus
 }
 #endif
+#pragma GCC visibility pop
 #endif /* MCMCREF_HIP_H */

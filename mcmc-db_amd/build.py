@@ -1,17 +1,24 @@
 #!/usr/bin/env python3
-"""Builds mcmc-db_amd/lib/libmcmcref_hip.so for gfx950 with hipcc (cross-compiles without a GPU)."""
+"""Builds mcmc-db_amd/lib/libmcmcref_hip.so for gfx950 with hipcc (cross-compiles without a GPU).
+
+One object per translation unit of csrc/ (lib/obj/), each with the dependency file the compiler writes for it; stale
+units compile concurrently and the objects are linked into the library.  No kernel is called across units, so the link
+needs no relocatable device code."""
 from __future__ import annotations
 
 import os
 import shutil
 import subprocess
 import sys
+from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
 HERE = Path(__file__).resolve().parent
-SRC = HERE / "csrc" / "mcr_api.hip"
-DEPS = sorted((HERE / "csrc").glob("*.h*")) + [SRC, HERE.parent / "include" / "mcmcref_hip.h"]
+UNITS = ("mcr_api", "mcr_files", "mcr_comm")
+OBJ = HERE / "lib" / "obj"
 OUT = HERE / "lib" / "libmcmcref_hip.so"
+FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fvisibility=hidden",
+         "-Wall", "-Wno-unused-value", "-Wno-pass-failed"]
 
 
 def hipcc() -> str:
@@ -21,16 +28,40 @@ def hipcc() -> str:
     raise RuntimeError("hipcc not found (set HIPCC or add /opt/rocm/bin to PATH)")
 
 
-def build(force: bool = False, verbose: bool = False) -> Path:
-    OUT.parent.mkdir(exist_ok=True)
-    if not force and OUT.exists() and all(OUT.stat().st_mtime >= d.stat().st_mtime for d in DEPS):
-        return OUT
-    cmd = [hipcc(), "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-shared",
-           "-Wall", "-Wno-unused-value", "-Wno-pass-failed", "-o", str(OUT), str(SRC)]
+def dep_files(dep: Path) -> list[str]:
+    """The prerequisites a make-style dependency file names ("target: file file \\<newline> file ...")."""
+    words = dep.read_text().replace("\\\n", " ").split(":", 1)[1].split()
+    return [w.replace("\\ ", " ") for w in words]
+
+
+def stale(unit: str) -> bool:
+    """The object is missing, or older than a file its dependency file names (or that file cannot be read)."""
+    obj, dep = OBJ / f"{unit}.o", OBJ / f"{unit}.d"
+    try:
+        return any(os.stat(f).st_mtime > obj.stat().st_mtime for f in dep_files(dep))
+    except (OSError, IndexError, UnicodeError):
+        return True
+
+
+def run(cmd: list[str], verbose: bool) -> None:
     if verbose:
-        cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")
         print(" ".join(cmd), flush=True)
     subprocess.run(cmd, check=True)
+
+
+def build(force: bool = False, verbose: bool = False) -> Path:
+    OBJ.mkdir(parents=True, exist_ok=True)
+    cc = [hipcc()] + (["-Rpass-analysis=kernel-resource-usage"] if verbose else [])
+    todo = [u for u in UNITS if force or stale(u)]
+    if todo:
+        jobs = min(len(todo), int(os.environ.get("MAX_JOBS", "4")))
+        with ThreadPoolExecutor(max_workers=max(jobs, 1)) as pool:
+            list(pool.map(lambda u: run(cc + FLAGS + ["-c", "-MD", "-MF", str(OBJ / f"{u}.d"), "-o", str(OBJ / f"{u}.o"),
+                                                      str(HERE / "csrc" / f"{u}.hip")], verbose), todo))
+    objs = [OBJ / f"{u}.o" for u in UNITS]
+    if todo or not OUT.exists() or any(o.stat().st_mtime > OUT.stat().st_mtime for o in objs):
+        run([hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared", f"-Wl,--version-script={HERE / 'csrc' / 'mcr_exports.map'}",
+             "-o", str(OUT)] + [str(o) for o in objs], verbose)
     return OUT
 
 

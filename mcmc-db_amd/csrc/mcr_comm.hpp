@@ -31,7 +31,7 @@ struct Api {
     decltype(&ncclAllGather) AllGather = nullptr;
     decltype(&ncclAllReduce) AllReduce = nullptr;
     decltype(&ncclGetErrorString) GetErrorString = nullptr;
-    decltype(&ncclCommGetAsyncError) CommGetAsyncError = nullptr;   // the deadlines (mcr_api.hip, comm_wait) poll and abort
+    decltype(&ncclCommGetAsyncError) CommGetAsyncError = nullptr;   // the deadlines (mcr_comm.hip, comm_wait) poll and abort
     decltype(&ncclCommAbort) CommAbort = nullptr;
 };
 

@@ -7,6 +7,8 @@ import ctypes
 import json
 import os
 import re
+import shutil
+import subprocess
 import sys
 from pathlib import Path
 
@@ -37,6 +39,14 @@ def test_abi_exports_every_declared_symbol(built_lib):
     assert set(_ffi.SYMBOLS) == declared
     lib = _ffi.load_library()
     assert lib.mcr_version() == 100
+    # the ABI is the header: the library's dynamic symbols hold its C entries and nothing of its C++ namespace
+    nm = shutil.which("nm")
+    if nm is None:
+        pytest.skip("nm is not on the path")
+    out = subprocess.run([nm, "-D", "--defined-only", str(built_lib)], check=True, capture_output=True, text=True).stdout
+    defined = [line.split()[-1] for line in out.splitlines() if line.split()]
+    assert {s for s in defined if s.startswith("mcr_")} == declared
+    assert not [s for s in defined if "_ZN3mcr" in s]
 
 
 def test_no_gpu_fails_loudly(built_lib):

@@ -12,7 +12,6 @@ import build as B  # noqa: E402
 name, flags = sys.argv[1], sys.argv[2:]
 out = B.OUT.parent / "variants" / f"libmcmcref_hip_{name}.so"
 out.parent.mkdir(parents=True, exist_ok=True)
-cmd = [B.hipcc(), "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-shared", "-Wall", "-Wno-unused-value",
-       "-Wno-pass-failed", *flags, "-o", str(out), str(B.SRC)]
+cmd = [B.hipcc(), *B.FLAGS, "-shared", *flags, "-o", str(out), *(str(B.HERE / "csrc" / f"{u}.hip") for u in B.UNITS)]
 subprocess.run(cmd, check=True)
 print(out)
