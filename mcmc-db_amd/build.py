@@ -14,7 +14,7 @@ from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
 HERE = Path(__file__).resolve().parent
-UNITS = ("mcr_api", "mcr_files", "mcr_comm")
+UNITS = ("mcr_api", "mcr_stats", "mcr_files", "mcr_comm")
 OBJ = HERE / "lib" / "obj"
 OUT = HERE / "lib" / "libmcmcref_hip.so"
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fvisibility=hidden",

@@ -21,7 +21,7 @@
 // block loop above and uses only +, -, x, / and fma: it equals the device in bits.
 #pragma once
 #include <cmath>
-#include "mcr_nested.hpp"   // xor_tree_sum; mcr_kernels.hpp: xcd_map
+#include "mcr_device.hpp"
 
 namespace mcr {
 

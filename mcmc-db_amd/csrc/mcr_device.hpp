@@ -124,6 +124,13 @@ __device__ __forceinline__ int wave_suffix_min(int v, int& excl)
     return v;
 }
 
+// The xor tree over the first `width` lanes of a wave (32, 16, .. 1 for 64): every lane gets the same bits.
+__device__ __forceinline__ double xor_tree_sum(double v, int width = kWave)
+{
+    for (int o = width >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
+    return v;
+}
+
 // Deterministic block sum (fixed association order): wave shuffle tree, then waves in index order.
 // `red` is LDS scratch of NT/64 doubles.  Every thread gets the result.
 template <int NT>
@@ -203,6 +210,29 @@ __device__ __noinline__ double inv_cdf(double p)
     }
     x = num / den;
     return (q < 0.0) ? -x : x;
+}
+
+// ---- the z table and the one-dimensional grids ---------------------------------------------------
+// Rank code -> z.  The clamp only matters for tensors the call is about to reject (NaN draws break
+// the sort's ordering, so some codes may be stale workspace bytes): it keeps the read inside the table.
+__device__ __forceinline__ double zdec(const double* __restrict__ ztab, u32 code, i64 M)
+{
+    const u32 cmax = (u32)(2 * M - 1);
+    return ztab[code < cmax ? code : cmax];
+}
+
+// XCD-aware block -> (parameter, block-within-parameter) map for kernels that scatter into one
+// parameter's z array.  Workgroups are dealt round-robin over the 8 XCDs (blocks L and L+8 share
+// an XCD, each XCD has its own L2), so parameter p runs all its nb blocks on XCD p % 8, back to
+// back: its 8-byte scattered z stores then merge into whole lines in ONE L2 instead of leaving
+// partial sectors in eight.  Launch with a 1-D grid of ceil(P/8)*8*nb blocks.  Speed only.
+__device__ __forceinline__ bool xcd_map(i64 P, int nb, i64& p, int& blk)
+{
+    const i64 L = blockIdx.x;
+    const i64 xcd = L & 7, j = L >> 3;
+    p = (j / nb) * 8 + xcd;
+    blk = (int)(j % nb);
+    return p < P;
 }
 
 // ---- merge path --------------------------------------------------------------------------------

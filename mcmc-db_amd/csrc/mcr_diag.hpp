@@ -52,14 +52,6 @@ enum SegField { SG_S = kLag1, SG_S0, SG_Q0, SG_S1, SG_Q1, SG_MIN, SG_MAX, SG_MIN
 
 __device__ __forceinline__ i64 pos8(i64 j) { return j + ((j >> 3) << 1); }
 
-// Rank code -> z.  The clamp only matters for tensors the call is about to reject (NaN draws break
-// the sort's ordering, so some codes may be stale workspace bytes): it keeps the read inside the table.
-__device__ __forceinline__ double zdec(const double* __restrict__ ztab, u32 code, i64 M)
-{
-    const u32 cmax = (u32)(2 * M - 1);
-    return ztab[code < cmax ? code : cmax];
-}
-
 // One block of LPL * LG lags of raw products for a staged segment, accumulated into the lane's LPL registers.
 // A: swizzled segment (>= seglen rounded up to 8 * 64 / LG draws), B: swizzled window that starts `lag base`
 // draws later (LPL * LG + 16 draws longer); both zero padded.  Lane (g, ph) = (lane % LG, lane / LG) owns lags

@@ -4,7 +4,7 @@
 // scipy.stats.wasserstein_distance / numpy.cov, whose published definitions are restated here.  Also the projection of
 // the draws onto directions (k_project), which turns the two-sample pass into a check of the joint distribution.
 #pragma once
-#include "mcr_device.hpp"
+#include "mcr_pipe.hpp"        // kMomRec: the sort stage's moment records
 
 namespace mcr {
 

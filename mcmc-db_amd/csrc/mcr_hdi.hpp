@@ -11,7 +11,7 @@
 // order of evaluation: a parameter's bits do not depend on its place in a batch, the chunking, the slice length or the
 // loads' width.  ONE text compares two candidates on the device and on the host (hdi_before).
 #pragma once
-#include "mcr_kernels.hpp"   // xcd_map
+#include "mcr_device.hpp"
 
 namespace mcr {
 

@@ -1,7 +1,8 @@
 // mcr_host.hpp -- what the translation units of libmcmcref_hip.so share: the context, its buffers and the tools of a call
-// (fail, HIP_TRY, LAUNCH, the profiling events, the workspace carving).  This is the complete list of what mcr_api.hip
-// (context, pipeline, statistics), mcr_files.hip (file and text ingest, writers) and mcr_comm.hip (RCCL) may use of each
-// other; everything else lives in its unit's anonymous namespace.  Internal: not installed, and it includes no kernel header.
+// (fail, HIP_TRY, LAUNCH, the profiling events, the workspace carving).  With mcr_pipe.hpp -- how mcr_stats.hip runs the
+// pipeline of mcr_api.hip -- this is the complete list of what mcr_api.hip (context, summary pipeline), mcr_stats.hip (the
+// other statistics), mcr_files.hip (file and text ingest, writers) and mcr_comm.hip (RCCL) may use of each other; everything
+// else lives in its unit's anonymous namespace.  Internal: not installed, and it includes no kernel header.
 #pragma once
 #include "../../include/mcmcref_hip.h"
 
@@ -210,7 +211,7 @@ struct mcr_ctx {
     DevBuf call_dev{4};                // the tensor calls (nested R-hat ... autocorrelation, one at a time): the call's result
                                        // table behind its tail lengths or chain permutation
     PinBuf call_host{4};               // its results (mcr_autocorr: the chains' non-finite counts) on the host
-    i64 energy_launch_work = 0;   // MCR_ENERGY_LAUNCH_WORK (mcr_init: kEnLaunchWork): pair-parameters of one k_energy_pairs launch (tests lower it)
+    i64 energy_launch_work = 0;   // MCR_ENERGY_LAUNCH_WORK (mcr_init): pair-parameters of one k_energy_pairs launch (tests lower it)
     DevBuf guard_count;                // device counters (2 unsigned): band lags re-derived the reference's way (mcr_rho_guard_count),
                                        // tiles the tile sort sorted as pairs after all (mcr_tile_fallback_count)
 };
@@ -331,7 +332,7 @@ template <class Layout> int carve(mcr_ctx* ctx, DevBuf& buf, Layout&& layout)
 
 // ---- the summary path, as far as mcr_summarize_files enqueues on it (defined in mcr_api.hip, with the comments) ----
 
-struct PipeIn;      // a pipeline's arguments and carved buffers: mcr_api.hip alone looks inside
+struct PipeIn;      // a pipeline's arguments and carved buffers (mcr_pipe.hpp): mcr_api.hip and mcr_stats.hip look inside
 
 // One summary call.  !ragged: a rectangular tensor (C, N, strides), chain c at c * N -- the offset table stays resident
 // in the slot between calls of one shape.  ragged: f64 draws with the chains back to back as chain_off says (host, C + 1

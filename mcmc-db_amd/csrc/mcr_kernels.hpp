@@ -25,39 +25,10 @@
 // (aN) = row of SURVEY.md section 8(a); reference file:line citations are next to each kernel.
 #pragma once
 #include <type_traits>
-#include "mcr_device.hpp"
+#include "mcr_pipe.hpp"      // ResField, QArgs, kMomRec
 #include "mcr_sortnet.h"
 
 namespace mcr {
-
-// result table: SoA, res[field * P + p]
-enum ResField {
-    R_MEAN = 0, R_STD, R_MEDIAN, R_RHAT, R_RHAT_BULK, R_RHAT_TAIL, R_ESS_BULK, R_ESS_TAIL,
-    R_LAG_BULK, R_LAG_TAIL, R_BAD, R_Q0  // R_Q0 .. R_Q0 + nq - 1
-};
-
-struct QArgs {
-    int nq;
-    i64 lo[32];
-    double g[32];
-    // the draws in time order, [pc][M] (f64, or f32 with xf32): only a median of exactly zero looks at them (wave_order_stats)
-    const void* xt = nullptr;
-    int xf32 = 0;
-};
-
-// XCD-aware block -> (parameter, block-within-parameter) map for kernels that scatter into one
-// parameter's z array.  Workgroups are dealt round-robin over the 8 XCDs (blocks L and L+8 share
-// an XCD, each XCD has its own L2), so parameter p runs all its nb blocks on XCD p % 8, back to
-// back: its 8-byte scattered z stores then merge into whole lines in ONE L2 instead of leaving
-// partial sectors in eight.  Launch with a 1-D grid of ceil(P/8)*8*nb blocks.  Speed only.
-__device__ __forceinline__ bool xcd_map(i64 P, int nb, i64& p, int& blk)
-{
-    const i64 L = blockIdx.x;
-    const i64 xcd = L & 7, j = L >> 3;
-    p = (j / nb) * 8 + xcd;
-    blk = (int)(j % nb);
-    return p < P;
-}
 
 // ------------------------------------------------------------------------------------------------
 // z lookup table.  A draw's z depends only on its tie run [s, e) and M:
@@ -145,8 +116,6 @@ __global__ __launch_bounds__(256) void k_ingest_transpose(const T* __restrict__ 
 // sqrt(slice) in the variance, 1e-12 for draws of spread 1e-6 around 3.
 // rows variant: grid (S, P); the block streams a contiguous slice of X[p][.] with 16-byte loads.
 // ------------------------------------------------------------------------------------------------
-constexpr int kMomRec = 5;
-
 __device__ __forceinline__ void store_slice_moments(double* o, double K, double s1, double s2, double bad, double n)
 {
     const double dm = (n > 0.0) ? s1 / n : 0.0;         // s1 = sum (x - K), s2 = sum (x - K)^2

@@ -14,7 +14,7 @@
 // shape (C, N, K) alone: a parameter's results do not depend on its place in the batch, on the workspace chunking or on
 // the alignment of its rows.
 #pragma once
-#include "mcr_diag.hpp"
+#include "mcr_device.hpp"
 
 namespace mcr {
 
@@ -35,12 +35,6 @@ constexpr int kNestNT = 256, kNestChains = kNestNT / kWave;
 constexpr int kNestPairs = 4;                              // pairs of draws per lane and block
 constexpr int kNestElems = 2 * kNestPairs;
 constexpr int kNestBlock = kWave * kNestElems;             // 512 draws: the longest chain the second pass takes from registers
-
-__device__ __forceinline__ double xor_tree_sum(double v, int width = kWave)
-{
-    for (int o = width >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-    return v;
-}
 
 // The block of a chain that starts at draw `base`: v[kind][e], e = 2 j + h <-> draw base + 128 j + 2 lane + h; 0.0 past N.
 template <bool VEC>

@@ -17,7 +17,7 @@
 // is a function of n alone, so a parameter's bits do not depend on its place in a batch, the chunking or the entry.
 // Host and device differ only in their libm (log1p, log, exp).
 #pragma once
-#include "mcr_nested.hpp"   // xor_tree_sum
+#include "mcr_device.hpp"
 
 namespace mcr {
 

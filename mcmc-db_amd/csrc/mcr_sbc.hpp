@@ -6,14 +6,14 @@
 // A row is one (simulation, parameter): L consecutive fp64 draws, row = s * P + p.  Rows are short (L is 100 .. 4000) and
 // there are many (S P is 1e4 .. 1e6), so a WAVE owns a row and a workgroup of four waves four consecutive rows: no LDS, no
 // barrier, no atomics.  The two sums of a row -- sum x, then sum (x - mean)^2 -- use the one association of
-// mcr_weighted.hpp: the balanced tree over the 1024 adjacent indices of a block (+0 past the end), blocks added in
+// mcr_tree.hpp: the balanced tree over the 1024 adjacent indices of a block (+0 past the end), blocks added in
 // ascending order from +0.  It is defined on the indices of the row, so a row's bits depend neither on where the row
 // lies (16-byte loads when its first draw is 16-byte aligned, 8-byte loads otherwise: wgt_load2) nor on the rows around it.
 #pragma once
 #include <algorithm>
 #include <cmath>
 #include <vector>
-#include "mcr_weighted.hpp"   // wgt_add, wgt_load2, wgt_blocks, WgtHostTree, wgt_host_sum
+#include "mcr_tree.hpp"
 
 namespace mcr {
 
@@ -50,28 +50,6 @@ __device__ __forceinline__ void sbc_count(const double (&xa)[kWgtRows], const do
         if (i < L) { less += xa[r] < t; equal += xa[r] == t; bad += sbc_nonfinite(xa[r]); }
         if (i + 1 < L) { less += xb[r] < t; equal += xb[r] == t; bad += sbc_nonfinite(xb[r]); }
     }
-}
-
-// wgt_wave_root's sums -- the same operands at every node, so the same bits -- with 10 cross-lane exchanges of a double
-// instead of 48.  The eight rows each need the xor tree over the 64 lanes; at the steps 1, 2 and 4 a lane keeps the half of
-// its values its lane bit names and sends the other half to the partner, who keeps those: both add own + partner's, which
-// is what v + shfl_xor(v) adds (an IEEE sum does not depend on the order of its operands).  From step 8 on one value is
-// left per lane, row 4 b0 + 2 b1 + b2 of the lane's low bits b0 b1 b2; the rows' totals are then read from the lanes
-// 0, 4, 2, 6, 1, 5, 3, 7 and joined as levels 8 .. 10.  Every lane returns the root.
-__device__ __forceinline__ double sbc_wave_root(const double (&v)[kWgtRows], int lane)
-{
-#pragma clang fp contract(off)
-    const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4;
-    double a[4], c[2];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) a[j] = (b0 ? v[j + 4] : v[j]) + __shfl_xor(b0 ? v[j] : v[j + 4], 1, kWave);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) c[j] = (b1 ? a[j + 2] : a[j]) + __shfl_xor(b1 ? a[j] : a[j + 2], 2, kWave);
-    double d = (b2 ? c[1] : c[0]) + __shfl_xor(b2 ? c[0] : c[1], 4, kWave);
-    for (int o = 8; o < kWave; o <<= 1) d = d + __shfl_xor(d, o, kWave);
-    const double t0 = __shfl(d, 0, kWave), t1 = __shfl(d, 4, kWave), t2 = __shfl(d, 2, kWave), t3 = __shfl(d, 6, kWave);
-    const double t4 = __shfl(d, 1, kWave), t5 = __shfl(d, 5, kWave), t6 = __shfl(d, 3, kWave), t7 = __shfl(d, 7, kWave);
-    return ((t0 + t1) + (t2 + t3)) + ((t4 + t5) + (t6 + t7));
 }
 
 // The block's tree of x (the +0 past the end is what was loaded) ...

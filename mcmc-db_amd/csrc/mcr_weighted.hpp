@@ -5,30 +5,18 @@
 // as they are (streaming, coalesced), and only the cumulative-weight search runs in the sorted order, through the gather
 // w[pos[j]] of the sort stage's positions.
 //
-// ONE association for every sum.  The indices of a sum are cut into blocks of kWgtBlock = 1024 consecutive ones; a
-// block's terms are the leaves of the balanced binary tree over adjacent indices (leaf i of the block is index
-// 1024 b + i, +0 past the end):
-//     node(0, i) = leaf i          node(L, i) = node(L-1, 2 i) + node(L-1, 2 i + 1)          block sum = node(10, 0)
-// and the blocks are added in ascending order from +0.  The in-block prefix of c = j + 1 leaves is the root of the SAME
-// tree with the leaves from c on replaced by +0 (wgt_prefix): for c = 1024 it is the root, so a block's sum IS its last
-// in-block prefix; it never falls as c grows, and zero weights leave it where it is, so that "the first j whose
-// cumulative weight reaches t" is one index whichever way it is searched.  Products are rounded before they are added
-// (fp contract off).
+// Every sum has the ONE association of mcr_tree.hpp: balanced trees over blocks of kWgtBlock = 1024 consecutive indices,
+// the blocks added in ascending order from +0.
 #pragma once
-#include <vector>
-#include "mcr_nested.hpp"   // mcr_kernels.hpp: xcd_map
+#include "mcr_tree.hpp"
 
 namespace mcr {
 
-constexpr int kWgtBlock = 1024;               // MCR_WEIGHTED_BLOCK: consecutive indices of one tree
-constexpr int kWgtLevels = 10;                // log2(kWgtBlock)
 constexpr int kWgtMaxQ = 16;                  // MCR_WEIGHTED_MAX_Q: probabilities of a call
-constexpr int kWgtRows = kWgtBlock / (2 * kWave);   // a wave's 16-byte loads per lane and block
 constexpr int kWgtNT = 256;                   // threads of k_weighted_moments and k_wq_pick
 constexpr int kWgtSlice = 16;                 // blocks of a k_weighted_moments workgroup (four per wave)
 constexpr int kWgtPrepNT = 1024;              // threads of the one k_weight_prepare workgroup
 constexpr int kWgtTree = kWgtBlock / 4 * 2;   // doubles of k_wq_pick's tree in LDS: the nodes of levels 2 .. 10 (511)
-static_assert(kWgtRows == 8 && (1 << kWgtLevels) == kWgtBlock, "the wave's join of its rows is written for eight");
 
 // The call's totals, prepared once (k_weight_prepare)
 enum WgtTotal { WT_BAD = 0, WT_MAX, WT_S1, WT_S2, kWgtTotals };
@@ -40,8 +28,6 @@ struct WgtArgs {
     int nq;
     double q[kWgtMaxQ];
 };
-
-__host__ __device__ inline i64 wgt_blocks(i64 M) { return (M + kWgtBlock - 1) / kWgtBlock; }
 
 // Whether v cannot be a weight: linear weights are finite and >= 0, log weights are finite or -inf.
 __host__ __device__ inline bool wgt_bad(double v, int log)
@@ -70,30 +56,6 @@ __host__ __device__ inline void wgt_dev2(double w, double x, double mean, double
     t1 = a * d;
     t2 = a * a;
 }
-__host__ __device__ inline double wgt_add(double a, double b)
-{
-#pragma clang fp contract(off)
-    return a + b;
-}
-
-// The in-block prefix of the first c leaves, c in [1, kWgtBlock]: the root of the tree whose leaves from c on are +0.
-// A sum with +0 is its other operand, so what is left are the aligned nodes named by the binary digits of c, added from
-// the smallest to the largest.  node(L, i) is the tree's node i of level L.  Every sum is monotone in its operands: the
-// prefix never falls from c to c + 1, and it stays where the weights are zero.
-template <class Node>
-__host__ __device__ inline double wgt_prefix(const Node& node, int c)
-{
-    double acc = 0.0;
-    bool any = false;
-    for (int L = 0; L <= kWgtLevels; ++L)
-        if (c & (1 << L)) {
-            const double n = node(L, (c >> L) - 1);
-            acc = any ? wgt_add(n, acc) : n;
-            any = true;
-        }
-    return acc;
-}
-
 // Whether a cumulative weight answers the threshold t = q * total: numpy's inverted_cdf, which never stops on a leading
 // run of zero weights.
 __host__ __device__ inline bool wgt_reached(double cum, double t) { return cum >= t && cum > 0.0; }
@@ -122,57 +84,6 @@ __host__ __device__ inline i64 wgt_find_block(const Sum& sum, i64 nb, double q, 
     }
     prev = acc;
     return -1;
-}
-
-// The root of a block's tree from one wave: v[r] = leaf(128 r + 2 lane) + leaf(128 r + 2 lane + 1), level 1.  The xor
-// steps 1 .. 32 are the levels 2 .. 7 (an IEEE sum does not depend on the order of its two operands), the join of the eight
-// rows the levels 8 .. 10.  Every lane returns the root.
-__device__ __forceinline__ double wgt_wave_root(double (&v)[kWgtRows])
-{
-#pragma clang fp contract(off)
-    for (int o = 1; o < kWave; o <<= 1) {
-#pragma unroll
-        for (int r = 0; r < kWgtRows; ++r) v[r] = v[r] + __shfl_xor(v[r], o, kWave);
-    }
-    return ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-}
-
-// sums[0] + sums[1] + ... + sums[n - 1] in ascending order from +0 by one wave: 64 consecutive sums per coalesced load,
-// then the additions one after the other on every lane (a broadcast per term, no dependent load in the chain).  Every
-// lane returns the sum.  hit(b, acc, next) sees every step: the prefix in front of b and the one that includes it.
-template <class Hit>
-__device__ __forceinline__ double wgt_wave_serial(const double* sums, i64 n, int lane, Hit&& hit)
-{
-    double acc = 0.0;
-    for (i64 b0 = 0; b0 < n; b0 += kWave) {
-        const double v = b0 + lane < n ? sums[b0 + lane] : 0.0;
-        const int m = n - b0 < kWave ? (int)(n - b0) : kWave;
-#pragma unroll
-        for (int l = 0; l < kWave; ++l) {                    // (unrolled: the lane is a constant, the broadcasts run ahead)
-            if (l < m) {
-                const double nxt = wgt_add(acc, __shfl(v, l, kWave));
-                hit(b0 + l, acc, nxt);
-                acc = nxt;
-            }
-        }
-    }
-    return acc;
-}
-__device__ __forceinline__ double wgt_wave_serial(const double* sums, i64 n, int lane)
-{
-    return wgt_wave_serial(sums, n, lane, [](i64, double, double) {});
-}
-
-// Elements i and i + 1 of a[0 .. M), +0 past the end.  wide: a + i is 16-byte aligned (i is even: the alignment of a).
-__device__ __forceinline__ void wgt_load2(const double* __restrict__ a, i64 i, i64 M, bool wide, double& lo, double& hi)
-{
-    if (wide && i + 1 < M) {
-        const double2 t = *reinterpret_cast<const double2*>(a + i);
-        lo = t.x; hi = t.y;
-    } else {
-        lo = i < M ? a[i] : 0.0;
-        hi = i + 1 < M ? a[i + 1] : 0.0;
-    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -449,30 +360,4 @@ __global__ __launch_bounds__(kWgtNT) void k_wq_pick(const double* __restrict__ k
     }
 }
 
-// The host routine's tree of one block: every level, level L at lev[L].
-struct WgtHostTree {
-    std::vector<double> lev[kWgtLevels + 1];
-    WgtHostTree() { for (int L = 0; L <= kWgtLevels; ++L) lev[L].resize((size_t)(kWgtBlock >> L)); }
-    // leaf(i): term i of the block, +0 past the end of the sum
-    template <class Leaf> double build(Leaf&& leaf)
-    {
-        for (int i = 0; i < kWgtBlock; ++i) lev[0][(size_t)i] = leaf(i);
-        for (int L = 1; L <= kWgtLevels; ++L)
-            for (int i = 0; i < (kWgtBlock >> L); ++i) lev[L][(size_t)i] = wgt_add(lev[L - 1][(size_t)(2 * i)], lev[L - 1][(size_t)(2 * i + 1)]);
-        return lev[kWgtLevels][0];
-    }
-    double operator()(int L, int i) const { return lev[L][(size_t)i]; }
-};
-
-// A sum of M terms in the one association: the blocks' roots, added in ascending order from +0.  roots: kept where given.
-template <class Term> inline double wgt_host_sum(WgtHostTree& tr, i64 M, Term&& term, std::vector<double>* roots = nullptr)
-{
-    double acc = 0.0;
-    for (i64 b = 0; b < wgt_blocks(M); ++b) {
-        const double r = tr.build([&](int i) { const i64 m = b * kWgtBlock + i; return m < M ? term(m) : 0.0; });
-        if (roots) roots->push_back(r);
-        acc = wgt_add(acc, r);
-    }
-    return acc;
-}
 }  // namespace mcr

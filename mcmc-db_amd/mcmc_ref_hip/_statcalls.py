@@ -22,7 +22,7 @@ def _void_p(v) -> C.c_void_p:
 
 
 class _StatCalls:
-    """The statistics entries: what the statistics part of mcr_api.hip implements."""
+    """The statistics entries: what mcr_api.hip and mcr_stats.hip implement."""
 
     def compare(self, ref, actual, tol: float):
         r = np.ascontiguousarray(ref, dtype=np.float64)

@@ -2,7 +2,7 @@
 the CPU so that a wrong reference cannot pass for a right kernel.  tests/test_ext_edges_gpu.py imports from here.
 
 * `cov_plan`, `two_sample_blocks` restate the launch arithmetic of `mcr_covariance_dev` / `mcr_two_sample`
-  (mcr_api.hip): the GPU tests assert through them that a shape still reaches the edge it was chosen for.
+  (mcr_stats.hip): the GPU tests assert through them that a shape still reaches the edge it was chosen for.
 * `exact_cov_inputs`: integer-valued draws whose population covariance is exact in f64 in ANY summation order.
 * `longdouble_cov`, `cov_tolerance`: a two-pass extended-precision covariance for real-valued draws and the per-entry
   bound the kernel is held to (no max-norm term: every entry is judged on the scale of its own two parameters).
@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 
 EPS = 2.0 ** -52
-COV_TILE, COV_STEP, MERGE_TILE = 128, 16, 4096     # kCovBM, kCovBK (mcr_ext.hpp); kTile (mcr_api.hip)
+COV_TILE, COV_STEP, MERGE_TILE = 128, 16, 4096     # kCovBM, kCovBK (mcr_ext.hpp); kTile (mcr_pipe.hpp)
 COV_MAX_P = 8192
 
 

@@ -1,10 +1,12 @@
 // sbc_host_check.cpp -- the host routines of simulation-based calibration (mcr_sbc_ranks_host, mcr_sbc_uniformity,
-// mcr_chi2_sf) as a stand-alone program, for sanitizer runs.  They live in mcr_api.hip, whose headers hold kernels, so the
-// program is built with hipcc and the sanitizers are given to the host side alone; no device is opened:
+// mcr_chi2_sf) as a stand-alone program, for sanitizer runs.  They live in mcr_stats.hip, whose headers hold kernels and
+// which runs the pipeline of mcr_api.hip, so the program is built from both units with hipcc and the sanitizers are given
+// to the host side alone; no device is opened:
 //
 //     hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined \
 //         -Xarch_host -fno-sanitize-recover=undefined -Iinclude -Wno-unused-value -Wno-pass-failed \
-//         -x hip mcmc-db_amd/csrc/mcr_api.hip tools/sbc_host_check.cpp -o sbc_host_check && ./sbc_host_check
+//         -x hip mcmc-db_amd/csrc/mcr_api.hip mcmc-db_amd/csrc/mcr_stats.hip tools/sbc_host_check.cpp \
+//         -o sbc_host_check && ./sbc_host_check
 //
 // It walks the routines through their edges -- no draws, one draw, row lengths around the summation block of 1024, bins 2,
 // 20 and L + 1, every refusal, non-finite draws -- and checks what is exact: the counts against a plain loop, uniform
