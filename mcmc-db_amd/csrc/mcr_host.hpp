@@ -90,7 +90,16 @@ constexpr int kMaxGridY = 65535;
     X(K_ACF_FINISH, "k_acf_finish")                      \
     X(K_ACF_POOL, "k_acf_pool")                          \
     X(K_ENERGY_PAIRS, "k_energy_pairs")                  \
-    X(K_ENERGY_REDUCE, "k_energy_reduce")
+    X(K_ENERGY_REDUCE, "k_energy_reduce")                \
+    X(K_CHOL_PANEL, "k_chol_panel")                      \
+    X(K_CHOL_BELOW, "k_chol_below")                      \
+    X(K_CHOL_UPDATE, "k_chol_update")                    \
+    X(K_CHOL_FINISH, "k_chol_finish")                    \
+    X(K_SOLVE_LOWER, "k_solve_lower")                    \
+    X(K_SYM_SCALE, "k_sym_scale")                        \
+    X(K_ROW_SUMSQ, "k_row_sumsq")                        \
+    X(K_GAUSS_SUMS, "k_gauss_sums")                      \
+    X(K_ROW_MEAN, "k_row_mean")
 #define MCR_KERNEL_ID(id, name) id,
 #define MCR_KERNEL_NAME(id, name) name,
 enum KernelId { MCR_KERNELS(MCR_KERNEL_ID) K_COUNT };       // K_INGEST = 0

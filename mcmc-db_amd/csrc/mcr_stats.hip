@@ -1,7 +1,7 @@
 // mcr_stats.hip -- the statistics unit of libmcmcref_hip.so's C ABI (see include/mcmcref_hip.h) beside the summary:
 // two-sample and sliced KS / W1, the energy distance, and the calls on one draw tensor -- nested R-hat, Pareto k-hat, PSIS,
 // HDI, weighted summaries, SBC, autocorrelation -- and covariance, each with its plan, device, host-upload and *_host
-// entries.  What they use of the summary pipeline of mcr_api.hip is mcr_pipe.hpp; no kernel of that unit is launched here.
+// entries; and the extension entries of include/mcmcref_hip_ext.h (mcrx_*: Cholesky, lower solve, Gaussian check).  What they use of the summary pipeline of mcr_api.hip is mcr_pipe.hpp; no kernel of that unit is launched here.
 #include "mcr_pipe.hpp"
 
 #include <cmath>
@@ -18,6 +18,8 @@
 #include "mcr_hdi.hpp"
 #include "mcr_weighted.hpp"
 #include "mcr_sbc.hpp"
+#include "mcr_gauss.hpp"
+#include "../../include/mcmcref_hip_ext.h"
 
 using namespace mcr;
 using namespace mcr::host;
@@ -1721,6 +1723,64 @@ int mcr_autocorr_host(const double* chains, int64_t C, int64_t N, int64_t max_la
     return nbad > 0 ? MCR_ENONFINITE : MCR_OK;
 }
 
+// The covariance of one sample as a plan, a layout and its launches, so that mcr_covariance_dev and the Gaussian check
+// (which carves once for everything it does) run the same kernels on the same geometry.
+struct CovPlan { int nb, ksplit; i64 P64, tiles, kchunk; };
+struct CovWs { double *partial, *mpart, *mean, *std; };
+constexpr int kCovMomS = 8;
+
+static CovPlan cov_plan(i64 M, i64 P)
+{
+    CovPlan c;
+    c.nb = (int)((P + kCovBM - 1) / kCovBM);
+    c.P64 = (i64)c.nb * kCovBM;
+    c.tiles = (i64)c.nb * (c.nb + 1) / 2;                            // workgroups per draw slice (none below the diagonal)
+    int ksplit = (int)((512 + c.tiles - 1) / c.tiles);               // >= ~512 workgroups: two per CU
+    const i64 maxsplit = (M + 16 * kCovBK - 1) / (16 * kCovBK);      // a slice is at least 16 panels long
+    if (ksplit > maxsplit) ksplit = (int)maxsplit;
+    {   // the slices' partial tiles are summed by k_cov_final: at most 128 MB of them
+        const i64 cap = ((i64)128 << 20) / (c.P64 * c.P64 * 8);
+        if (ksplit > cap) ksplit = (int)(cap < 1 ? 1 : cap);
+    }
+    if (ksplit < 1) ksplit = 1;
+    i64 kchunk = (M + ksplit - 1) / ksplit;
+    c.kchunk = (kchunk + kCovBK - 1) / kCovBK * kCovBK;
+    c.ksplit = (int)((M + c.kchunk - 1) / c.kchunk);
+    return c;
+}
+
+static void carve_cov(Carve& cv, CovWs& w, const CovPlan& c, i64 P)
+{
+    w.partial = cv.take<double>((size_t)c.ksplit * c.P64 * c.P64);
+    w.mpart = cv.take<double>((size_t)P * kCovMomS * kMomRec);
+    w.mean = cv.take<double>((size_t)P);
+    w.std = cv.take<double>((size_t)P);
+}
+
+// k_cov_mfma and k_cov_final around the given means on the current stream; no synchronisation.  partial may be larger than
+// the plan needs.
+static int cov_tiles_launch(mcr_ctx* ctx, const double* draws_dev, i64 M, i64 P, const CovPlan& c, const double* mean,
+                            double* partial, double* cov_dev)
+{
+    if ((M & 1) == 0 && (reinterpret_cast<uintptr_t>(draws_dev) & 15) == 0) {
+        LAUNCH(ctx, K_COV, (k_cov_mfma<true>), dim3((unsigned)c.tiles, (unsigned)c.ksplit), dim3(256), 0, draws_dev,
+               mean, (i64)M, (i64)P, c.nb, c.kchunk, partial);
+    } else {
+        LAUNCH(ctx, K_COV, (k_cov_mfma<false>), dim3((unsigned)c.tiles, (unsigned)c.ksplit), dim3(256), 0, draws_dev,
+               mean, (i64)M, (i64)P, c.nb, c.kchunk, partial);
+    }
+    LAUNCH(ctx, K_COV_FINAL, k_cov_final, dim3((unsigned)((P * P + 255) / 256)), dim3(256), 0, (const double*)partial,
+           c.ksplit, c.nb, (i64)M, (i64)P, cov_dev);
+    return MCR_OK;
+}
+
+// The streaming moments, then the tiles around their means: mcr_covariance.
+static int cov_launch(mcr_ctx* ctx, const double* draws_dev, i64 M, i64 P, const CovPlan& c, const CovWs& w, double* cov_dev)
+{
+    const int rc = moments_rows(ctx, draws_dev, M, P, w.mean, w.std, w.mpart, (M >= 8 * 2048) ? kCovMomS : 1);
+    return rc ? rc : cov_tiles_launch(ctx, draws_dev, M, P, c, w.mean, w.partial, cov_dev);
+}
+
 // Device-resident form (draws_dev [P][M] f64, cov_dev [P][P] f64, both in this context's device memory): what
 // tools/cov_bench.py times.  Synchronous.
 int mcr_covariance_dev(mcr_ctx* ctx, const double* draws_dev, int64_t M, int64_t P, double* cov_dev)
@@ -1731,40 +1791,12 @@ int mcr_covariance_dev(mcr_ctx* ctx, const double* draws_dev, int64_t M, int64_t
     if (P > 8192) return fail(ctx, MCR_EINVAL, "P > 8192 not supported by mcr_covariance");
     if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "mcr_covariance with summaries in flight");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int nb = (int)((P + kCovBM - 1) / kCovBM);
-    const i64 P64 = (i64)nb * kCovBM;
-    const i64 tiles = (i64)nb * (nb + 1) / 2;                        // workgroups per draw slice (none below the diagonal)
-    int ksplit = (int)((512 + tiles - 1) / tiles);                   // >= ~512 workgroups: two per CU
-    const i64 maxsplit = (M + 16 * kCovBK - 1) / (16 * kCovBK);      // a slice is at least 16 panels long
-    if (ksplit > maxsplit) ksplit = (int)maxsplit;
-    {   // the slices' partial tiles are summed by k_cov_final: at most 128 MB of them
-        const i64 cap = ((i64)128 << 20) / (P64 * P64 * 8);
-        if (ksplit > cap) ksplit = (int)(cap < 1 ? 1 : cap);
-    }
-    if (ksplit < 1) ksplit = 1;
-    i64 kchunk = (M + ksplit - 1) / ksplit;
-    kchunk = (kchunk + kCovBK - 1) / kCovBK * kCovBK;
-    ksplit = (int)((M + kchunk - 1) / kchunk);
-    const int S = 8;
-    double *partial, *mpart, *d_mean, *d_std;
-    int rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) {
-        partial = cv.take<double>((size_t)ksplit * P64 * P64);
-        mpart = cv.take<double>((size_t)P * S * kMomRec);
-        d_mean = cv.take<double>((size_t)P);
-        d_std = cv.take<double>((size_t)P);
-    });
+    const CovPlan c = cov_plan(M, P);
+    CovWs w;
+    int rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) { carve_cov(cv, w, c, P); });
     if (rc) return rc;
-    rc = moments_rows(ctx, draws_dev, M, P, d_mean, d_std, mpart, (M >= 8 * 2048) ? S : 1);
+    rc = cov_launch(ctx, draws_dev, M, P, c, w, cov_dev);
     if (rc) return rc;
-    if ((M & 1) == 0 && (reinterpret_cast<uintptr_t>(draws_dev) & 15) == 0) {
-        LAUNCH(ctx, K_COV, (k_cov_mfma<true>), dim3((unsigned)tiles, (unsigned)ksplit), dim3(256), 0, draws_dev,
-               (const double*)d_mean, (i64)M, (i64)P, nb, kchunk, partial);
-    } else {
-        LAUNCH(ctx, K_COV, (k_cov_mfma<false>), dim3((unsigned)tiles, (unsigned)ksplit), dim3(256), 0, draws_dev,
-               (const double*)d_mean, (i64)M, (i64)P, nb, kchunk, partial);
-    }
-    LAUNCH(ctx, K_COV_FINAL, k_cov_final, dim3((unsigned)((P * P + 255) / 256)), dim3(256), 0, (const double*)partial,
-           ksplit, nb, (i64)M, (i64)P, cov_dev);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     prof_resolve(ctx);
     return MCR_OK;
@@ -1787,6 +1819,318 @@ int mcr_covariance(mcr_ctx* ctx, const double* draws, int64_t M, int64_t P, doub
     HIP_TRY(ctx, hipMemcpyAsync(cov, d_cov, sizeof(double) * (size_t)P * P, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return MCR_OK;
+}
+
+// ---- the extension entries (include/mcmcref_hip_ext.h, mcr_gauss.hpp): Cholesky, lower solve, Gaussian check ----------
+static_assert(kCholNB == MCRX_CHOL_NB && kLinalgMaxP == MCRX_LINALG_MAX_P && kGaussOut == MCRX_G_OUT,
+              "mcmcref_hip_ext.h states the block size, the order limit and the number of outputs");
+
+// The order and a row stride of a matrix argument: MCR_EINVAL with the cause, else MCR_OK.
+static int linalg_check(mcr_ctx* ctx, const char* who, i64 P, const char* ld_name, i64 ld, i64 ld_min)
+{
+    if (P < 0) return fail(ctx, MCR_EINVAL, "%s: P = %lld is negative", who, P);
+    if (P > kLinalgMaxP) return fail(ctx, MCR_EINVAL, "%s: P = %lld is over MCRX_LINALG_MAX_P = %lld", who, P, kLinalgMaxP);
+    if (ld < ld_min) return fail(ctx, MCR_EINVAL, "%s: %s = %lld is smaller than the row length %lld", who, ld_name, ld, ld_min);
+    if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "%s with summaries in flight", who);
+    return MCR_OK;
+}
+
+// The factorisation's launches on the current stream, in place on A: 3 ceil(P / NB) - 1 of them, no synchronisation.
+// *info_dev is 0 on entry (a set word makes every kernel but the finisher return at once).
+static int chol_launch(mcr_ctx* ctx, double* A, i64 P, i64 lda, i64* info_dev, double* logdet_dev)
+{
+    const i64 nblk = (P + kCholNB - 1) / kCholNB;
+    for (i64 b = 0; b < nblk; ++b) {
+        const i64 k0 = b * kCholNB, m = nblk - b - 1;             // m block rows under the diagonal block
+        LAUNCH(ctx, K_CHOL_PANEL, k_chol_panel, dim3(1), dim3(kCholNB), 0, A, P, lda, k0, info_dev);
+        if (m == 0) break;
+        LAUNCH(ctx, K_CHOL_BELOW, k_chol_below, dim3((unsigned)m), dim3(kCholNB), 0, A, P, lda, k0, (const i64*)info_dev);
+        LAUNCH(ctx, K_CHOL_UPDATE, k_chol_update, dim3((unsigned)(m * (m + 1) / 2)), dim3(256), 0, A, P, lda, k0, (const i64*)info_dev);
+    }
+    LAUNCH(ctx, K_CHOL_FINISH, k_chol_finish, dim3((unsigned)((P * P + 255) / 256)), dim3(256), 0, A, P, lda,
+           (const i64*)info_dev, logdet_dev);
+    return MCR_OK;
+}
+
+static int solve_launch(mcr_ctx* ctx, const double* L, i64 P, i64 ldl, double* B, i64 K, i64 ldb, const i64* info0, const i64* info1)
+{
+    LAUNCH(ctx, K_SOLVE_LOWER, k_solve_lower, dim3((unsigned)((K + kCholNB - 1) / kCholNB)), dim3(256), 0, L, P, ldl, B, K, ldb,
+           info0, info1);
+    return MCR_OK;
+}
+
+// mcrx_cholesky_dev behind its argument check, P > 0: the status words from the lane's workspace, the launches, the results.
+static int chol_run(mcr_ctx* ctx, double* a_dev, i64 P, i64 lda, int64_t* info, double* logdet)
+{
+    i64* d_info; double* d_logdet;
+    int rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) { d_info = cv.take<i64>(1); d_logdet = cv.take<double>(1); });
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(d_info, 0, sizeof(i64), ctx->stream));
+    rc = chol_launch(ctx, a_dev, P, lda, d_info, d_logdet);
+    if (rc) return rc;
+    i64 h_info = 0; double h_logdet = 0.0;
+    HIP_TRY(ctx, hipMemcpyAsync(&h_info, d_info, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&h_logdet, d_logdet, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    prof_resolve(ctx);
+    if (info) *info = h_info;
+    if (logdet) *logdet = h_logdet;
+    return MCR_OK;
+}
+
+int mcrx_cholesky_dev(mcr_ctx* ctx, double* a_dev, int64_t P, int64_t lda, int64_t* info, double* logdet)
+{
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    const int rc = linalg_check(ctx, "mcrx_cholesky", P, "lda", lda, P);
+    if (rc) return rc;
+    if (P == 0) { if (info) *info = 0; if (logdet) *logdet = 0.0; return MCR_OK; }
+    if (!a_dev) return fail(ctx, MCR_EINVAL, "mcrx_cholesky: NULL argument (a)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return chol_run(ctx, a_dev, P, lda, info, logdet);
+}
+
+int mcrx_cholesky(mcr_ctx* ctx, const double* a, int64_t P, int64_t lda, double* l, int64_t* info, double* logdet)
+{
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    int rc = linalg_check(ctx, "mcrx_cholesky", P, "lda", lda, P);
+    if (rc) return rc;
+    if (P == 0) { if (info) *info = 0; if (logdet) *logdet = 0.0; return MCR_OK; }
+    if (!a || !l) return fail(ctx, MCR_EINVAL, "mcrx_cholesky: NULL argument (%s)", !a ? "a" : "l");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    void* buf[1];
+    rc = stage_buffers(ctx, {sizeof(double) * (size_t)P * P}, buf);
+    if (rc) return rc;
+    double* A = (double*)buf[0];
+    const size_t row = sizeof(double) * (size_t)P;
+    HIP_TRY(ctx, hipMemcpy2DAsync(A, row, a, sizeof(double) * (size_t)lda, row, (size_t)P, hipMemcpyHostToDevice, ctx->stream));
+    rc = chol_run(ctx, A, P, P, info, logdet);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(l, A, row * (size_t)P, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return MCR_OK;
+}
+
+int mcrx_cholesky_host(const double* a, int64_t P, int64_t lda, double* l, int64_t* info, double* logdet)
+{
+    i64 bad = 0;
+    if (chol_host(a, P, lda, l, &bad, logdet)) return MCR_EINVAL;
+    if (info) *info = bad;
+    return MCR_OK;
+}
+
+static int solve_check(mcr_ctx* ctx, i64 P, i64 ldl, i64 K, i64 ldb)
+{
+    if (K < 0) return fail(ctx, MCR_EINVAL, "mcrx_solve_lower: K = %lld is negative", K);
+    if (P >= 0 && ldb < K) return fail(ctx, MCR_EINVAL, "mcrx_solve_lower: ldb = %lld is smaller than the row length %lld", ldb, K);
+    return linalg_check(ctx, "mcrx_solve_lower", P, "ldl", ldl, P);
+}
+
+int mcrx_solve_lower_dev(mcr_ctx* ctx, const double* l_dev, int64_t P, int64_t ldl, double* b_dev, int64_t K, int64_t ldb)
+{
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    int rc = solve_check(ctx, P, ldl, K, ldb);
+    if (rc) return rc;
+    if (P == 0 || K == 0) return MCR_OK;
+    if (!l_dev || !b_dev) return fail(ctx, MCR_EINVAL, "mcrx_solve_lower: NULL argument (%s)", !l_dev ? "l" : "b");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = solve_launch(ctx, l_dev, P, ldl, b_dev, K, ldb, nullptr, nullptr);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    prof_resolve(ctx);
+    return MCR_OK;
+}
+
+int mcrx_solve_lower(mcr_ctx* ctx, const double* l, int64_t P, int64_t ldl, const double* b, int64_t K, int64_t ldb, double* x)
+{
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    int rc = solve_check(ctx, P, ldl, K, ldb);
+    if (rc) return rc;
+    if (P == 0 || K == 0) return MCR_OK;
+    if (!l || !b || !x) return fail(ctx, MCR_EINVAL, "mcrx_solve_lower: NULL argument (%s)", !l ? "l" : !b ? "b" : "x");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    void* buf[2];
+    rc = stage_buffers(ctx, {sizeof(double) * (size_t)P * P, sizeof(double) * (size_t)P * K}, buf);
+    if (rc) return rc;
+    double *L = (double*)buf[0], *B = (double*)buf[1];
+    const size_t lrow = sizeof(double) * (size_t)P, brow = sizeof(double) * (size_t)K;
+    HIP_TRY(ctx, hipMemcpy2DAsync(L, lrow, l, sizeof(double) * (size_t)ldl, lrow, (size_t)P, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpy2DAsync(B, brow, b, sizeof(double) * (size_t)ldb, brow, (size_t)P, hipMemcpyHostToDevice, ctx->stream));
+    rc = solve_launch(ctx, L, P, P, B, K, K, nullptr, nullptr);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(x, B, brow * (size_t)P, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    prof_resolve(ctx);
+    return MCR_OK;
+}
+
+int mcrx_solve_lower_host(const double* l, int64_t P, int64_t ldl, const double* b, int64_t K, int64_t ldb, double* x)
+{
+    return solve_lower_host(l, P, ldl, b, K, ldb, x) ? MCR_EINVAL : MCR_OK;
+}
+
+// The workspace of a Gaussian check, carved once: the covariance's partials (the larger of the two samples' plans), both
+// samples' means, both matrices (factored in place), W -- each
+// covariance before its scaled gather, then each solve result --, the right-hand sides, the rows' sums, the live
+// parameters' scales and indices, the six sums and the two status words.
+struct GaussWs {
+    double *partial, *mean_ref, *mean_act, *Cr, *Ca, *W, *yr, *ya, *rows_r, *rows_a, *s, *res; int* idx; i64* info;
+};
+
+static void carve_gauss(Carve& cv, GaussWs& w, const CovPlan& cr, const CovPlan& ca, i64 P)
+{
+    w.partial = cv.take<double>((size_t)(cr.ksplit >= ca.ksplit ? cr.ksplit : ca.ksplit) * cr.P64 * cr.P64);      // (P64 is the same)
+    w.mean_ref = cv.take<double>((size_t)P);
+    w.mean_act = cv.take<double>((size_t)P);
+    w.Cr = cv.take<double>((size_t)P * P);
+    w.Ca = cv.take<double>((size_t)P * P);
+    w.W = cv.take<double>((size_t)P * P);
+    w.yr = cv.take<double>((size_t)P);
+    w.ya = cv.take<double>((size_t)P);
+    w.rows_r = cv.take<double>((size_t)P);
+    w.rows_a = cv.take<double>((size_t)P);
+    w.s = cv.take<double>((size_t)P);
+    w.idx = cv.take<int>((size_t)P);
+    w.res = cv.take<double>(6);
+    w.info = cv.take<i64>(2);
+}
+
+static int gauss_shape_check(mcr_ctx* ctx, i64 Mr, i64 Ma, i64 P)
+{
+    if (P < 0) return fail(ctx, MCR_EINVAL, "mcrx_gaussian_check: P = %lld is negative", P);
+    if (P > kLinalgMaxP) return fail(ctx, MCR_EINVAL, "mcrx_gaussian_check: P = %lld is over MCRX_LINALG_MAX_P = %lld", P, kLinalgMaxP);
+    if (Mr < 1 || Ma < 1) return fail(ctx, MCR_EINVAL, "mcrx_gaussian_check: both samples need at least one draw (Mr = %lld, Ma = %lld)", Mr, Ma);
+    return MCR_OK;
+}
+
+// Everything but the shape, for P > 0.
+static int gauss_check(mcr_ctx* ctx, const void* ref, const void* act, i64 P, const double* scale, double jitter,
+                       const double* out, const int64_t* info3)
+{
+    if (!ref || !act || !out || !info3)
+        return fail(ctx, MCR_EINVAL, "mcrx_gaussian_check: NULL argument (%s)", !ref ? "ref" : !act ? "act" : !out ? "out8" : "info3");
+    if (!(jitter >= 0.0) || std::isinf(jitter)) return fail(ctx, MCR_EINVAL, "mcrx_gaussian_check: jitter is negative or not finite");
+    for (i64 p = 0; scale && p < P; ++p)
+        if (!(scale[p] >= 0.0) || std::isinf(scale[p]))
+            return fail(ctx, MCR_EINVAL, "mcrx_gaussian_check: scale[%lld] is negative or not finite", (long long)p);
+    if (!ctx->order.empty()) return fail(ctx, MCR_EINVAL, "mcrx_gaussian_check with summaries in flight");
+    return MCR_OK;
+}
+
+int mcrx_gaussian_workspace(mcr_ctx* ctx, int64_t Mr, int64_t Ma, int64_t P, size_t* bytes)
+{
+    if (!ctx || !bytes) return fail(ctx, MCR_EINVAL, "mcrx_gaussian_workspace: NULL argument");
+    const int rc = gauss_shape_check(ctx, Mr, Ma, P);
+    if (rc) return rc;
+    *bytes = 0;
+    if (P == 0) return MCR_OK;
+    Carve m{nullptr};
+    GaussWs w;
+    carve_gauss(m, w, cov_plan(Mr, P), cov_plan(Ma, P), P);
+    *bytes = m.off;
+    return MCR_OK;
+}
+
+int mcrx_gaussian_check_dev(mcr_ctx* ctx, const double* ref_dev, int64_t Mr, const double* act_dev, int64_t Ma, int64_t P,
+                            const double* scale, double jitter, double* out8, int64_t* info3, double* shift)
+{
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    int rc = gauss_shape_check(ctx, Mr, Ma, P);
+    if (rc) return rc;
+    if (P == 0) return MCR_OK;
+    rc = gauss_check(ctx, ref_dev, act_dev, P, scale, jitter, out8, info3);
+    if (rc) return rc;
+    std::vector<int> idx;
+    std::vector<double> s;
+    gauss_live(scale, P, idx, s);
+    const i64 PL = (i64)idx.size();
+    info3[MCRX_G_P_LIVE] = PL; info3[MCRX_G_INFO_REF] = info3[MCRX_G_INFO_ACT] = 0;
+    if (PL == 0) { gauss_outputs(out8, 0, 0, 0); return MCR_OK; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const CovPlan cr = cov_plan(Mr, P), ca = cov_plan(Ma, P);
+    GaussWs w;
+    { Carve m{nullptr}; carve_gauss(m, w, cr, ca, P);
+      if (m.off > ctx->ws_limit)
+          return fail(ctx, MCR_ENOMEM, "workspace limit too small: the Gaussian check of this shape needs %zu bytes, the limit is %zu",
+                      m.off, ctx->ws_limit); }
+    rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) { carve_gauss(cv, w, cr, ca, P); });
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(w.s, s.data(), sizeof(double) * (size_t)PL, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(w.idx, idx.data(), sizeof(int) * (size_t)PL, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(w.info, 0, 2 * sizeof(i64), ctx->stream));
+    const i64 *info_r = w.info, *info_a = w.info + 1;
+    const dim3 gather((unsigned)((PL * PL + 255) / 256));
+    const double* none = nullptr;
+    // both covariances through W into their scaled, gathered matrices; the second gather also makes the mean shift.  The
+    // means are k_row_mean's, not the streaming moments' (whose summation order follows the rows' alignment).
+    LAUNCH(ctx, K_ROW_MEAN, k_row_mean, dim3((unsigned)P), dim3(256), 0, ref_dev, (i64)Mr, w.mean_ref);
+    rc = cov_tiles_launch(ctx, ref_dev, Mr, P, cr, w.mean_ref, w.partial, w.W);
+    if (rc) return rc;
+    LAUNCH(ctx, K_SYM_SCALE, k_sym_scale, gather, dim3(256), 0, (const double*)w.W, (i64)P, (const double*)w.s, (const int*)w.idx, PL,
+           jitter, w.Cr, none, none, (double*)nullptr, (double*)nullptr);
+    LAUNCH(ctx, K_ROW_MEAN, k_row_mean, dim3((unsigned)P), dim3(256), 0, act_dev, (i64)Ma, w.mean_act);
+    rc = cov_tiles_launch(ctx, act_dev, Ma, P, ca, w.mean_act, w.partial, w.W);
+    if (rc) return rc;
+    LAUNCH(ctx, K_SYM_SCALE, k_sym_scale, gather, dim3(256), 0, (const double*)w.W, (i64)P, (const double*)w.s, (const int*)w.idx, PL,
+           jitter, w.Ca, (const double*)w.mean_ref, (const double*)w.mean_act, w.yr, w.ya);
+    // the factors (their log-determinants land in res[4], res[5]) and the whitened mean shifts
+    rc = chol_launch(ctx, w.Cr, PL, PL, w.info, w.res + 4);
+    if (!rc) rc = chol_launch(ctx, w.Ca, PL, PL, w.info + 1, w.res + 5);
+    if (!rc) rc = solve_launch(ctx, w.Cr, PL, PL, w.yr, 1, 1, info_r, nullptr);
+    if (!rc) rc = solve_launch(ctx, w.Ca, PL, PL, w.ya, 1, 1, info_a, nullptr);
+    if (rc) return rc;
+    // |L_r^-1 L_a|_F^2 and |L_a^-1 L_r|_F^2: a copy of the other factor is the right-hand side
+    const size_t mat = sizeof(double) * (size_t)PL * PL;
+    HIP_TRY(ctx, hipMemcpyAsync(w.W, w.Ca, mat, hipMemcpyDeviceToDevice, ctx->stream));
+    rc = solve_launch(ctx, w.Cr, PL, PL, w.W, PL, PL, info_r, info_a);
+    if (rc) return rc;
+    LAUNCH(ctx, K_ROW_SUMSQ, k_row_sumsq, dim3((unsigned)PL), dim3(256), 0, (const double*)w.W, PL, PL, w.rows_r, info_r, info_a);
+    HIP_TRY(ctx, hipMemcpyAsync(w.W, w.Cr, mat, hipMemcpyDeviceToDevice, ctx->stream));
+    rc = solve_launch(ctx, w.Ca, PL, PL, w.W, PL, PL, info_r, info_a);
+    if (rc) return rc;
+    LAUNCH(ctx, K_ROW_SUMSQ, k_row_sumsq, dim3((unsigned)PL), dim3(256), 0, (const double*)w.W, PL, PL, w.rows_a, info_r, info_a);
+    LAUNCH(ctx, K_GAUSS_SUMS, k_gauss_sums, dim3(1), dim3(256), 0, (const double*)w.yr, (const double*)w.ya, (const double*)w.rows_r,
+           (const double*)w.rows_a, PL, w.res);
+    double res[6];
+    i64 info[2];
+    HIP_TRY(ctx, hipMemcpyAsync(res, w.res, sizeof(res), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(info, w.info, sizeof(info), hipMemcpyDeviceToHost, ctx->stream));
+    if (shift) HIP_TRY(ctx, hipMemcpyAsync(shift, w.yr, sizeof(double) * (size_t)PL, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    prof_resolve(ctx);
+    memcpy(out8, res, sizeof(res));
+    gauss_outputs(out8, PL, info[0], info[1]);
+    info3[MCRX_G_INFO_REF] = info[0];
+    info3[MCRX_G_INFO_ACT] = info[1];
+    if (shift && info[0]) for (i64 i = 0; i < PL; ++i) shift[i] = std::numeric_limits<double>::quiet_NaN();
+    return MCR_OK;
+}
+
+int mcrx_gaussian_check(mcr_ctx* ctx, const double* ref, int64_t Mr, const double* act, int64_t Ma, int64_t P,
+                        const double* scale, double jitter, double* out8, int64_t* info3, double* shift)
+{
+    if (!ctx) return fail(nullptr, MCR_EINVAL, "ctx is NULL");
+    int rc = gauss_shape_check(ctx, Mr, Ma, P);
+    if (rc) return rc;
+    if (P == 0) return MCR_OK;
+    rc = gauss_check(ctx, ref, act, P, scale, jitter, out8, info3);
+    if (rc) return rc;
+    const double *Xr, *Xa;
+    rc = stage_two_samples(ctx, ref, Mr, act, Ma, P, &Xr, &Xa);
+    if (rc) return rc;
+    return mcrx_gaussian_check_dev(ctx, Xr, Mr, Xa, Ma, P, scale, jitter, out8, info3, shift);
+}
+
+int mcrx_gaussian_check_host(const double* ref, int64_t Mr, const double* act, int64_t Ma, int64_t P, const double* scale,
+                             double jitter, double* out8, int64_t* info3, double* shift)
+{
+    try {
+        i64 info[3] = {0, 0, 0};
+        if (gauss_host(ref, Mr, act, Ma, P, scale, jitter, out8, info3 ? info : nullptr, shift)) return MCR_EINVAL;
+        if (info3 && P > 0) for (int k = 0; k < 3; ++k) info3[k] = info[k];
+        return MCR_OK;
+    } catch (const std::exception&) {
+        return MCR_ENOMEM;
+    }
 }
 
 }  // extern "C"

@@ -416,26 +416,36 @@ def compare_cmd(model: str, actual_path: Path, tolerance: float, format_: str) -
 @click.option("--energy-max", default=None, type=float, help="Fail when the energy distance exceeds this (implies --energy)")
 @click.option("--energy-max-draws", default=None, type=click.IntRange(min=1),
               help="Thin each sample by an even stride to at most this many draws first (the cost is quadratic)")
+@click.option("--gaussian", is_flag=True, help="Joint Gaussian check: Mahalanobis distance of the mean shift, KL of the two Gaussian fits")
+@click.option("--gaussian-jitter", default=0.0, type=float, help="Added to the diagonal of both standardised covariance matrices")
+@click.option("--gaussian-shift-max", default=None, type=float, help="Fail when the Mahalanobis distance exceeds this (implies --gaussian)")
+@click.option("--gaussian-kl-max", default=None, type=float, help="Fail when the symmetrised KL exceeds this (implies --gaussian)")
 @click.option("--format", "format_", type=click.Choice(["table", "json"], case_sensitive=False), default="table")
 def validate_cmd(model: str, actual_path: Path, tolerance: float, metrics: str, ks_max, w1_scaled_max, sliced: int, sliced_seed: int,
                  sliced_ks_max, sliced_w1_max, khat_max, hdi_prob, hdi_tol, energy: bool, energy_max, energy_max_draws,
-                 format_: str) -> None:
+                 gaussian: bool, gaussian_jitter: float, gaussian_shift_max, gaussian_kl_max, format_: str) -> None:
     """The reference's mean / std gate plus per-parameter KS / Wasserstein-1 and, with --sliced K, the same distances
-    along K random directions of the joint distribution; with --energy the energy distance of the joint draws
+    along K random directions of the joint distribution; with --energy the energy distance of the joint draws;
+    with --gaussian the Mahalanobis distance of the mean shift and the KL divergences of the two Gaussian fits
     (validate.validate; no counterpart in the reference)."""
     from .validate import validate
+    with_gaussian = gaussian or gaussian_shift_max is not None or gaussian_kl_max is not None
     try:
         result = validate(model, _read_actual_csv(actual_path), tolerance=tolerance, metrics=tuple(metrics.split(",")),
                           ks_max=ks_max, w1_scaled_max=w1_scaled_max, sliced=sliced, sliced_seed=sliced_seed,
                           sliced_ks_max=sliced_ks_max, sliced_w1_max=sliced_w1_max, khat_max=khat_max,
                           hdi_prob=hdi_prob, hdi_tol=hdi_tol, energy=energy or energy_max is not None, energy_max=energy_max,
-                          energy_max_draws=energy_max_draws)
+                          energy_max_draws=energy_max_draws,
+                          **({"gaussian": True, "gaussian_jitter": gaussian_jitter, "gaussian_shift_max": gaussian_shift_max,
+                              "gaussian_kl_max": gaussian_kl_max} if with_gaussian else {}))
     except ValueError as exc:
         raise click.ClickException(str(exc)) from exc
     with_hdi = hdi_prob is not None or hdi_tol is not None
     if format_ == "json":
         details = {p: {k: vars(v) for k, v in ms.items()} for p, ms in result.compare.details.items()}
         hdi_keys = {"hdi_ref": result.hdi_ref, "hdi_actual": result.hdi_actual} if with_hdi else {}    # only when asked for
+        if with_gaussian:
+            hdi_keys.update(gaussian=result.gaussian, gaussian_shift=result.gaussian_shift)
         click.echo(json.dumps({**hdi_keys, "passed": result.passed, "failures": result.failures,
                                "compare": {"passed": result.compare.passed, "failures": result.compare.failures,
                                            "details": details},
@@ -454,7 +464,38 @@ def validate_cmd(model: str, actual_path: Path, tolerance: float, metrics: str, 
             _print_table({p: {"hdi_lo_ref": result.hdi_ref[p][0], "hdi_hi_ref": result.hdi_ref[p][1],
                               "hdi_lo_actual": result.hdi_actual[p][0], "hdi_hi_actual": result.hdi_actual[p][1]}
                           for p in result.hdi_actual})
+        if with_gaussian and result.gaussian is not None:
+            _print_gaussian(result.gaussian)
     raise SystemExit(0 if result.passed else 2)
+
+
+def _print_gaussian(g: dict) -> None:
+    click.echo(f"gaussian shift {g['mahalanobis']:.6g}  kl_act_ref {g['kl_act_ref']:.6g}  kl_ref_act {g['kl_ref_act']:.6g}  "
+               f"kl_sym {g['kl_sym']:.6g}  params {g['p_live']}")
+    for key in ("singular_ref", "singular_actual"):
+        if g.get(key) is not None:
+            click.echo(f"{key} {g[key]}")
+    _print_table({p: {"shift": v} for p, v in g["shift"].items()})
+
+
+@main.command("gaussian-check")
+@click.argument("ref_file", type=click.Path(path_type=Path, exists=True, dir_okay=False))
+@click.argument("act_file", type=click.Path(path_type=Path, exists=True, dir_okay=False))
+@click.option("--params", default=None, help="Comma-separated parameter list (default: the reference file's)")
+@click.option("--jitter", default=0.0, type=float, help="Added to the diagonal of both standardised covariance matrices")
+@click.option("--format", "format_", type=click.Choice(["table", "json"], case_sensitive=False), default="table")
+def gaussian_check_cmd(ref_file: Path, act_file: Path, params: str | None, jitter: float, format_: str) -> None:
+    """Joint Gaussian check of the draws in ACT_FILE against those in REF_FILE (no counterpart in the reference): the
+    Mahalanobis distance of the mean shift in the reference's metric, the KL divergences of the two Gaussian fits, and
+    every parameter's shift given the ones before it, in conditional standard deviations."""
+    try:
+        r = convert_mod.gaussian_check_files(ref_file, act_file, params=params.split(",") if params else None, jitter=jitter)
+    except (ValueError, KeyError, IndexError) as exc:
+        raise click.ClickException(str(exc)) from exc
+    if format_ == "json":
+        click.echo(json.dumps(r, indent=2, sort_keys=True))
+    else:
+        _print_gaussian(r)
 
 
 @main.command("convert")

@@ -673,6 +673,36 @@ def hdi_file(path: Path, params: Iterable[str] | None = None, prob: Iterable[flo
             for i, n in enumerate(names)}
 
 
+def gaussian_check_files(ref_path: Path, act_path: Path, params: Iterable[str] | None = None, jitter: float = 0.0,
+                         context=None) -> dict:
+    """The joint Gaussian check (gaussian.gaussian_check) of the draws table `act_path` against the draws table
+    `ref_path` (each a `.csv`, a chain-list `.json.zip` or a `.parquet` draws file of the store, read on the host; the
+    chains are pooled).  The parameters are `params`, or those of the reference table; the other table must have them
+    too.  Every parameter is scaled by 1 / its reference std (0, so left out, where that is not finite and > 0) and
+    `jitter` is added to the diagonal of both scaled covariance matrices.  The call's dict, with `params` (the live
+    parameters, in order), `shift` keyed by them, and `singular_ref` / `singular_actual` (a parameter's name or None)."""
+    from .gaussian import gaussian_check
+    rt, names = _table_and_names(_read_table(ref_path, parquet=True), params)
+    at, _ = _table_and_names(_read_table(act_path, parquet=True), names)
+    if not names:
+        raise ValueError("no parameter to compare")
+    ref, _ = table_to_tensor(rt, names)
+    act, _ = table_to_tensor(at, names)
+    ref, act = ref.reshape(len(names), -1), act.reshape(len(names), -1)
+    std = ref.std(axis=1)
+    live = np.isfinite(std) & (std > 0)
+    scale = np.zeros(len(names))
+    scale[live] = 1.0 / std[live]
+    with _ffi.value_errors():
+        r = gaussian_check(ref, act, scale=scale, jitter=jitter, shift=True, context=context)
+    kept = [n for i, n in enumerate(names) if live[i]]
+    r["params"] = kept
+    r["shift"] = {n: float(v) for n, v in zip(kept, r["shift"])}
+    r["singular_ref"] = kept[r["info_ref"] - 1] if r["info_ref"] else None
+    r["singular_actual"] = kept[r["info_act"] - 1] if r["info_act"] else None
+    return r
+
+
 def weighted_summary_file(path: Path, log_weights: str | None = None, weights: str | None = None,
                           params: Iterable[str] | None = None, quantiles: Iterable[float] = (0.05, 0.5, 0.95),
                           psis: bool = True, context=None) -> dict:

@@ -41,6 +41,18 @@ class ValidateResult:
     hdi_actual: dict[str, tuple[float, float]] = field(default_factory=dict)   # interval and of `actual`'s: only with hdi_prob / hdi_tol
     energy: float | None = None                  # energy distance E of the standardised joint draws (energy=True)
     energy_detail: dict | None = None            # "a", "b", "c", "e", "h", "t" of Context.energy_distance, "mr", "ma" (draws used)
+    # Not fields -- the field list of this class is closed --: what a result without the Gaussian check answers where a
+    # GaussianValidateResult has its two fields.
+    gaussian = None
+    gaussian_shift = None
+
+
+@dataclass(frozen=True)
+class GaussianValidateResult(ValidateResult):
+    """What validate(gaussian=True) returns when it made the check: a ValidateResult with two more fields."""
+    gaussian: dict | None = None                 # gaussian.gaussian_check of the standardised joint draws, "shift" as
+    #                                              {param: conditional shift}, "singular_ref" / "singular_actual" (a name or None)
+    gaussian_shift: float | None = None          # its Mahalanobis distance: the mean shift in joint reference standard deviations
 
 
 def energy_stride(m: int, max_draws: int | None) -> int:
@@ -80,8 +92,19 @@ def validate(model: str, actual: Mapping[str, Sequence[float]], tolerance: float
              sliced_seed: int = 4711, sliced_ks_max: float | None = None,
              sliced_w1_max: float | None = None, khat_max: float | None = None, hdi_prob: float | None = None,
              hdi_tol: float | None = None, energy: bool = False, energy_max: float | None = None,
-             energy_max_draws: int | None = None) -> ValidateResult:
-    """energy=True: one `Context.energy_distance` call on the joint draws, every parameter scaled by 1 / reference std
+             energy_max_draws: int | None = None, gaussian: bool = False, gaussian_jitter: float = 0.0,
+             gaussian_shift_max: float | None = None, gaussian_kl_max: float | None = None) -> ValidateResult:
+    """gaussian=True: the result is a `GaussianValidateResult` (a plain `ValidateResult` answers None for its two extra
+    fields); one `gaussian.gaussian_check` call on the joint draws, every parameter scaled by 1 / reference std (0
+    where that std is not finite and > 0, as for `energy`), `gaussian_jitter` added to the diagonal of both scaled covariance
+    matrices: do the first two moments of the joint distributions agree?  `gaussian_shift` is the Mahalanobis distance of
+    the mean shift in the reference's metric, `gaussian` the call's dict with `shift` keyed by parameter (each live
+    parameter's shift given the ones before it, in conditional standard deviations).  A singular covariance is reported by
+    the NAME of the first parameter that is constant or exactly dependent on the ones before it, in
+    `gaussian["singular_ref"]` / `["singular_actual"]` (else None); what needs that factor is NaN.  `gaussian_shift_max`
+    and `gaussian_kl_max` (on `kl_sym`) add the failures `gaussian.shift=... > max` and `gaussian.kl=... > max` -- a NaN
+    fails them --; without them `passed` is what it is without `gaussian`.  Needs joint draws.
+    energy=True: one `Context.energy_distance` call on the joint draws, every parameter scaled by 1 / reference std
     (0 where that std is not finite and > 0: the `live` rule of `sliced_directions`): the direction-free counterpart of
     `sliced`, without a seed.  `energy` is E, `energy_detail` the six numbers and the draws used.  `energy_max` adds the
     failure `energy=E > energy_max`; without it `passed` is what it is without `energy`.  `energy_max_draws=n` thins each
@@ -112,6 +135,8 @@ def validate(model: str, actual: Mapping[str, Sequence[float]], tolerance: float
         raise ValueError("energy needs joint draws: the parameters of `actual` differ in length")
     if energy:
         energy_stride(1, energy_max_draws)          # a bad limit is refused before any work
+    if gaussian and len(lens) > 1:
+        raise ValueError("gaussian needs joint draws: the parameters of `actual` differ in length")
     ks: dict[str, float] = {}
     w1: dict[str, float] = {}
     if len(lens) == 1 and params:
@@ -184,8 +209,27 @@ def validate(model: str, actual: Mapping[str, Sequence[float]], tolerance: float
             extra.update(energy=det["e"], energy_detail=det)
             if energy_max is not None and not det["e"] <= energy_max:
                 failures.append(f"energy={det['e']:.3g} > {energy_max}")
-    return ValidateResult(passed=not failures, compare=cmp_res, ks=ks, wasserstein=w1, wasserstein_scaled=scaled,
-                          failures=failures, khat_ref=khat_ref, khat_actual=khat_act, hdi_ref=hdi_ref, hdi_actual=hdi_act, **extra)
+    if gaussian and params:
+        from .gaussian import gaussian_check
+        std = np.array([ref_stats[p]["std"] for p in params], dtype=np.float64)
+        live = np.isfinite(std) & (std > 0)
+        if live.any():
+            scale = np.zeros(std.size)
+            scale[live] = 1.0 / std[live]
+            with _ffi.value_errors():
+                det = gaussian_check(ref, act, scale=scale, jitter=gaussian_jitter, shift=True, context=ctx)
+            names = [p for i, p in enumerate(params) if live[i]]
+            det["shift"] = {p: float(v) for p, v in zip(names, det["shift"])}
+            det["singular_ref"] = names[det["info_ref"] - 1] if det["info_ref"] else None
+            det["singular_actual"] = names[det["info_act"] - 1] if det["info_act"] else None
+            extra.update(gaussian=det, gaussian_shift=det["mahalanobis"])
+            if gaussian_shift_max is not None and not det["mahalanobis"] <= gaussian_shift_max:
+                failures.append(f"gaussian.shift={det['mahalanobis']:.3g} > {gaussian_shift_max}")
+            if gaussian_kl_max is not None and not det["kl_sym"] <= gaussian_kl_max:
+                failures.append(f"gaussian.kl={det['kl_sym']:.3g} > {gaussian_kl_max}")
+    result = GaussianValidateResult if "gaussian" in extra else ValidateResult
+    return result(passed=not failures, compare=cmp_res, ks=ks, wasserstein=w1, wasserstein_scaled=scaled,
+                  failures=failures, khat_ref=khat_ref, khat_actual=khat_act, hdi_ref=hdi_ref, hdi_actual=hdi_act, **extra)
 
 
 @dataclass(frozen=True)
