@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Builds mcmc-db_amd/lib/libmcmcref_hip.so for gfx950 with hipcc (cross-compiles without a GPU).
+"""Builds mcmc-db_amd/lib/libmcmcref_hip.so and its companion libmcmcref_iess.so (include/mcmcref_iess.h: its own units,
+its own version script, no link against the first) for gfx950 with hipcc (cross-compiles without a GPU).
 
 One object per translation unit of csrc/ (lib/obj/), each with the dependency file the compiler writes for it; stale
 units compile concurrently and the objects are linked into the library.  No kernel is called across units, so the link
@@ -15,10 +16,13 @@ from pathlib import Path
 
 HERE = Path(__file__).resolve().parent
 UNITS = ("mcr_api", "mcr_stats", "mcr_files", "mcr_comm")
+IESS_UNITS = ("mci_api",)
 OBJ = HERE / "lib" / "obj"
 OUT = HERE / "lib" / "libmcmcref_hip.so"
+IESS_OUT = HERE / "lib" / "libmcmcref_iess.so"
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fvisibility=hidden",
          "-Wall", "-Wno-unused-value", "-Wno-pass-failed"]
+IESS_FLAGS = FLAGS + ["-ffp-contract=off", f"-I{HERE.parent / 'include'}"]    # host and device must round alike
 
 
 def hipcc() -> str:
@@ -49,19 +53,26 @@ def run(cmd: list[str], verbose: bool) -> None:
     subprocess.run(cmd, check=True)
 
 
+def link(out: Path, units: tuple, version_script: str, relinked: bool, verbose: bool) -> None:
+    objs = [OBJ / f"{u}.o" for u in units]
+    if relinked or not out.exists() or any(o.stat().st_mtime > out.stat().st_mtime for o in objs):
+        run([hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared", f"-Wl,--version-script={HERE / 'csrc' / version_script}",
+             "-o", str(out)] + [str(o) for o in objs], verbose)
+
+
 def build(force: bool = False, verbose: bool = False) -> Path:
+    """Both libraries; returns the path of libmcmcref_hip.so."""
     OBJ.mkdir(parents=True, exist_ok=True)
     cc = [hipcc()] + (["-Rpass-analysis=kernel-resource-usage"] if verbose else [])
-    todo = [u for u in UNITS if force or stale(u)]
+    flags = {**{u: FLAGS for u in UNITS}, **{u: IESS_FLAGS for u in IESS_UNITS}}
+    todo = [u for u in flags if force or stale(u)]
     if todo:
         jobs = min(len(todo), int(os.environ.get("MAX_JOBS", "4")))
         with ThreadPoolExecutor(max_workers=max(jobs, 1)) as pool:
-            list(pool.map(lambda u: run(cc + FLAGS + ["-c", "-MD", "-MF", str(OBJ / f"{u}.d"), "-o", str(OBJ / f"{u}.o"),
-                                                      str(HERE / "csrc" / f"{u}.hip")], verbose), todo))
-    objs = [OBJ / f"{u}.o" for u in UNITS]
-    if todo or not OUT.exists() or any(o.stat().st_mtime > OUT.stat().st_mtime for o in objs):
-        run([hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared", f"-Wl,--version-script={HERE / 'csrc' / 'mcr_exports.map'}",
-             "-o", str(OUT)] + [str(o) for o in objs], verbose)
+            list(pool.map(lambda u: run(cc + flags[u] + ["-c", "-MD", "-MF", str(OBJ / f"{u}.d"), "-o", str(OBJ / f"{u}.o"),
+                                                         str(HERE / "csrc" / f"{u}.hip")], verbose), todo))
+    link(OUT, UNITS, "mcr_exports.map", any(u in UNITS for u in todo), verbose)
+    link(IESS_OUT, IESS_UNITS, "mci_exports.map", any(u in IESS_UNITS for u in todo), verbose)
     return OUT
 
 

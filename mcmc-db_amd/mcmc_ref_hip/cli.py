@@ -14,6 +14,7 @@ parameter and, with `--sliced K`, along K random directions of the joint distrib
 `pareto-khat FILE` prints the Pareto k-hat of every parameter's tails: whether a mean and a std of the draws can be trusted.
 `loo FILE` prints PSIS-LOO of a table's pointwise log-likelihood columns: elpd_loo, p_loo and the observations' k-hats.
 `weighted-summary FILE` prints every parameter's mean, sd, standard error and quantiles under a column of importance weights.
+`ess-quantile FILE` prints the effective draws behind every parameter's quantile estimates (and its local efficiency).
 `hdi FILE` prints the highest-density interval(s) of every parameter: the shortest interval holding a share of the draws.
 `autocorr FILE` prints every parameter's integrated autocorrelation time (Sokal's window) and its stickiest and least
 sticky chain; as JSON, the autocorrelation function of every chain up to `--max-lag` as well.
@@ -252,6 +253,24 @@ def hdi_cmd(file: Path, params: str | None, probs: tuple[float, ...], format_: s
     per probability q the columns hdi_lo_q and hdi_hi_q."""
     try:
         stats = convert_mod.hdi_file(file, params=params.split(",") if params else None, prob=probs or (0.94,))
+    except (ValueError, KeyError, IndexError) as exc:
+        raise click.ClickException(str(exc)) from exc
+    _echo_stats(stats, format_)
+
+
+@main.command("ess-quantile")
+@click.argument("file", type=click.Path(path_type=Path, exists=True, dir_okay=False))
+@click.option("--params", default=None, help="Comma-separated parameter list")
+@click.option("--probs", "probs", multiple=True, type=float, help="A probability inside (0, 1); may be repeated (default: 0.05 0.5 0.95)")
+@click.option("--local", "local", default=None, type=int, help="Also the local efficiency in this many quantile bins (at most 32)")
+@click.option("--format", "format_", type=click.Choice(["table", "json"], case_sensitive=False), default="table")
+def ess_quantile_cmd(file: Path, params: str | None, probs: tuple[float, ...], local: int | None, format_: str) -> None:
+    """Effective draws behind the quantile estimates of a table (no counterpart in the reference): per probability q the
+    quantile q_q and ess_q_q, the ESS of the indicator x <= quantile under the library's ESS rule (unsplit chains, first
+    negative autocorrelation; not Geyer's rule), and ess_tail_min, the smaller of the two outermost."""
+    try:
+        stats = convert_mod.ess_quantile_file(file, params=params.split(",") if params else None,
+                                              probs=probs or (0.05, 0.5, 0.95), local=local)
     except (ValueError, KeyError, IndexError) as exc:
         raise click.ClickException(str(exc)) from exc
     _echo_stats(stats, format_)

@@ -673,6 +673,39 @@ def hdi_file(path: Path, params: Iterable[str] | None = None, prob: Iterable[flo
             for i, n in enumerate(names)}
 
 
+def ess_quantile_file(path: Path, params: Iterable[str] | None = None, probs: Iterable[float] = (0.05, 0.5, 0.95),
+                      local: int | None = None, context=None) -> dict[str, dict[str, float]]:
+    """The effective draws behind the quantile estimates of every parameter of a draws table (a `.csv`, a chain-list
+    `.json.zip` or a `.parquet` draws file of the store, read on the host; chains of equal length).  Per parameter and
+    probability q of `probs`: `q_q` (the quantile) and `ess_q_q` (the ESS of the indicator x <= quantile), q printed like
+    `format(q, "g")`, and `ess_tail_min`, the smaller of the ESS at the smallest and the largest probability
+    (indicator.ess_quantile).  With `local` = a number of bins, `eff_local_j` as well: ESS / draws of the j-th bin between
+    consecutive quantiles (indicator.ess_local)."""
+    from .indicator import ess_local, ess_quantile
+    table, names = _table_and_names(_read_table(path, parquet=True), params)
+    probs = [float(q) for q in probs]
+    if not probs or len(probs) > 32 or not all(0.0 < q < 1.0 for q in probs):
+        raise ValueError(f"probs: 1 to 32 probabilities inside (0, 1); got {probs}")
+    if local is not None and not 1 <= local <= 32:
+        raise ValueError(f"local: 1 to 32 bins; got {local}")
+    if not names:
+        return {}
+    x = _equal_chains(table, names, "the ESS of a quantile")
+    ctx = context or _ffi.default_context()
+    with _ffi.value_errors():
+        r = ess_quantile(x, probs, "pcn", ctx)
+        loc = ess_local(x, local, "pcn", ctx) if local is not None else None
+    out = {}
+    for i, n in enumerate(names):
+        row = {f"q_{q:g}": float(r["thresholds"][i, j]) for j, q in enumerate(probs)}
+        row.update({f"ess_q_{q:g}": float(r["ess"][i, j]) for j, q in enumerate(probs)})
+        row["ess_tail_min"] = float(r["tail_min"][i])
+        if loc is not None:
+            row.update({f"eff_local_{j}": float(v) for j, v in enumerate(loc["efficiency"][i])})
+        out[n] = row
+    return out
+
+
 def gaussian_check_files(ref_path: Path, act_path: Path, params: Iterable[str] | None = None, jitter: float = 0.0,
                          context=None) -> dict:
     """The joint Gaussian check (gaussian.gaussian_check) of the draws table `act_path` against the draws table
