@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Builds mcmc-db_amd/lib/libmcmcref_hip.so and its companion libmcmcref_iess.so (include/mcmcref_iess.h: its own units,
-its own version script, no link against the first) for gfx950 with hipcc (cross-compiles without a GPU).
+"""Builds mcmc-db_amd/lib/libmcmcref_hip.so and its companions libmcmcref_iess.so (include/mcmcref_iess.h) and
+libmcmcref_bm.so (include/mcmcref_bm.h) -- each with its own units and its own version script, none linked against
+another -- for gfx950 with hipcc (cross-compiles without a GPU).
 
 One object per translation unit of csrc/ (lib/obj/), each with the dependency file the compiler writes for it; stale
 units compile concurrently and the objects are linked into the library.  No kernel is called across units, so the link
@@ -17,9 +18,11 @@ from pathlib import Path
 HERE = Path(__file__).resolve().parent
 UNITS = ("mcr_api", "mcr_stats", "mcr_files", "mcr_comm")
 IESS_UNITS = ("mci_api",)
+BM_UNITS = ("mcb_api",)
 OBJ = HERE / "lib" / "obj"
 OUT = HERE / "lib" / "libmcmcref_hip.so"
 IESS_OUT = HERE / "lib" / "libmcmcref_iess.so"
+BM_OUT = HERE / "lib" / "libmcmcref_bm.so"
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fvisibility=hidden",
          "-Wall", "-Wno-unused-value", "-Wno-pass-failed"]
 IESS_FLAGS = FLAGS + ["-ffp-contract=off", f"-I{HERE.parent / 'include'}"]    # host and device must round alike
@@ -61,10 +64,10 @@ def link(out: Path, units: tuple, version_script: str, relinked: bool, verbose: 
 
 
 def build(force: bool = False, verbose: bool = False) -> Path:
-    """Both libraries; returns the path of libmcmcref_hip.so."""
+    """All three libraries; returns the path of libmcmcref_hip.so."""
     OBJ.mkdir(parents=True, exist_ok=True)
     cc = [hipcc()] + (["-Rpass-analysis=kernel-resource-usage"] if verbose else [])
-    flags = {**{u: FLAGS for u in UNITS}, **{u: IESS_FLAGS for u in IESS_UNITS}}
+    flags = {**{u: FLAGS for u in UNITS}, **{u: IESS_FLAGS for u in IESS_UNITS + BM_UNITS}}
     todo = [u for u in flags if force or stale(u)]
     if todo:
         jobs = min(len(todo), int(os.environ.get("MAX_JOBS", "4")))
@@ -73,6 +76,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
                                                          str(HERE / "csrc" / f"{u}.hip")], verbose), todo))
     link(OUT, UNITS, "mcr_exports.map", any(u in UNITS for u in todo), verbose)
     link(IESS_OUT, IESS_UNITS, "mci_exports.map", any(u in IESS_UNITS for u in todo), verbose)
+    link(BM_OUT, BM_UNITS, "mcb_exports.map", any(u in BM_UNITS for u in todo), verbose)
     return OUT
 
 

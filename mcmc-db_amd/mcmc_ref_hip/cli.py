@@ -15,6 +15,8 @@ parameter and, with `--sliced K`, along K random directions of the joint distrib
 `loo FILE` prints PSIS-LOO of a table's pointwise log-likelihood columns: elpd_loo, p_loo and the observations' k-hats.
 `weighted-summary FILE` prints every parameter's mean, sd, standard error and quantiles under a column of importance weights.
 `ess-quantile FILE` prints the effective draws behind every parameter's quantile estimates (and its local efficiency).
+`multi-ess FILE` prints the multivariate effective sample size of a table from its batch-means long-run covariance, and
+`mean-test REF_FILE ACT_FILE` the calibrated joint test of equal means of two tables; exits 1 when `--p-min` is missed.
 `hdi FILE` prints the highest-density interval(s) of every parameter: the shortest interval holding a share of the draws.
 `autocorr FILE` prints every parameter's integrated autocorrelation time (Sokal's window) and its stickiest and least
 sticky chain; as JSON, the autocorrelation function of every chain up to `--max-lag` as well.
@@ -274,6 +276,46 @@ def ess_quantile_cmd(file: Path, params: str | None, probs: tuple[float, ...], l
     except (ValueError, KeyError, IndexError) as exc:
         raise click.ClickException(str(exc)) from exc
     _echo_stats(stats, format_)
+
+
+@main.command("multi-ess")
+@click.argument("file", type=click.Path(path_type=Path, exists=True, dir_okay=False))
+@click.option("--params", default=None, help="Comma-separated parameter list")
+@click.option("--batch", default=None, type=int, help="Batch size (default: about sqrt(draws per chain))")
+@click.option("--r", "r", type=click.Choice(["1", "3"]), default="3", help="3: lugsail batch means (default); 1: plain")
+@click.option("--format", "format_", type=click.Choice(["table", "json"], case_sensitive=False), default="table")
+def multi_ess_cmd(file: Path, params: str | None, batch: int | None, r: str, format_: str) -> None:
+    """The multivariate effective sample size of a table (no counterpart in the reference): mESS of Vats, Flegal and Jones
+    from the batch-means long-run covariance, and per parameter the Monte Carlo standard error of the mean and ess_bm."""
+    try:
+        stats = convert_mod.multi_ess_file(file, params=params.split(",") if params else None, batch=batch, r=int(r))
+    except (ValueError, KeyError, IndexError) as exc:
+        raise click.ClickException(str(exc)) from exc
+    _echo_stats(stats, format_)
+
+
+@main.command("mean-test")
+@click.argument("ref_file", type=click.Path(path_type=Path, exists=True, dir_okay=False))
+@click.argument("act_file", type=click.Path(path_type=Path, exists=True, dir_okay=False))
+@click.option("--params", default=None, help="Comma-separated parameter list")
+@click.option("--jitter", default=0.0, type=float, help="Added to the diagonal of the pooled covariance (correlation scale)")
+@click.option("--p-min", default=None, type=float, help="Fail (exit 1) when the p-value is below this")
+@click.option("--format", "format_", type=click.Choice(["table", "json"], case_sensitive=False), default="table")
+def mean_test_cmd(ref_file: Path, act_file: Path, params: str | None, jitter: float, p_min: float | None, format_: str) -> None:
+    """Have the means moved?  The joint test of equal means of two tables on the lugsail batch-means long-run covariance:
+    T, its asymptotic chi-square p-value, and every parameter's shift in Monte Carlo standard errors."""
+    try:
+        res = convert_mod.mean_test_files(ref_file, act_file, params=params.split(",") if params else None, jitter=jitter)
+    except (ValueError, KeyError, IndexError) as exc:
+        raise click.ClickException(str(exc)) from exc
+    if format_ == "json":
+        click.echo(json.dumps(res, indent=2, sort_keys=True))
+    else:
+        click.echo(f"T={res['T']:.6g} dof={res['dof']} p_value={res['p_value']:.6g} mess_ref={res['mess_ref']:.6g} "
+                   f"mess_act={res['mess_act']:.6g}" + (f" singular={res['singular']}" if res["singular"] else ""))
+        _print_table({n: {"z": z, "shift": res["shift"][n]} for n, z in res["z"].items()})
+    if p_min is not None and not res["p_value"] >= p_min:
+        raise SystemExit(1)
 
 
 @main.command("weighted-summary")

@@ -933,3 +933,58 @@ def convert_file(input_path: Path, name: str, out_draws_dir: Path, out_meta_dir:
     if isinstance(res, Exception):
         raise res
     return res
+
+
+def multi_ess_file(path: Path, params: Iterable[str] | None = None, batch: int | None = None, r: int = 3,
+                   context=None) -> dict[str, dict[str, float]]:
+    """The multivariate effective sample size of a draws table (a `.csv`, a chain-list `.json.zip` or a `.parquet` draws
+    file of the store, read on the host; chains of equal length), from the lugsail (r = 3) or plain (r = 1) batch-means
+    long-run covariance at batch size `batch` (None: batchmeans.batch_size).  Per parameter `mean`, `mcse_mean` and
+    `ess_bm`; the row `(joint)` holds `mess`, `p_live`, `batch`, `batches_per_chain` and `info_sigma` (non-zero: the
+    long-run covariance is singular or indefinite and `mess` NaN).  Every parameter is scaled by 1 / its std (a constant
+    one is dropped)."""
+    from .batchmeans import multi_ess
+    table, names = _table_and_names(_read_table(path, parquet=True), params)
+    if not names:
+        return {}
+    x = _equal_chains(table, names, "the multivariate ESS")
+    std = x.reshape(len(names), -1).std(axis=1)
+    live = np.isfinite(std) & (std > 0)
+    scale = np.zeros(std.size)
+    scale[live] = 1.0 / std[live]
+    ctx = context or _ffi.default_context()
+    with _ffi.value_errors():
+        m = multi_ess(x, batch=batch, r=r, scale=scale, context=ctx)
+    out = {n: {"mean": float(m["mu"][i]), "mcse_mean": float(m["mcse_mean"][i]), "ess_bm": float(m["ess_bm"][i])}
+           for i, n in enumerate(names)}
+    out["(joint)"] = {"mess": float(m["mess"]), "p_live": float(m["p_live"]), "batch": float(m["b"]),
+                      "batches_per_chain": float(m["a"]), "info_sigma": float(m["info_sigma"])}
+    return out
+
+
+def mean_test_files(ref_path: Path, act_path: Path, params: Iterable[str] | None = None, jitter: float = 0.0, r: int = 3,
+                    context=None) -> dict:
+    """The joint test of equal means of two draws tables (formats as `multi_ess_file`; chains of equal length within a
+    file): batchmeans.mean_shift_test with every parameter scaled by 1 / the reference file's std.  Returns "T", "dof",
+    "p_value", "info", "singular" (a parameter name or None), "mess_ref", "mess_act", the batch geometry, and "z" /
+    "shift" keyed by live parameter."""
+    from .batchmeans import mean_shift_test
+    rt, names = _table_and_names(_read_table(ref_path, parquet=True), params)
+    at, _ = _table_and_names(_read_table(act_path, parquet=True), names)
+    if not names:
+        raise ValueError("no parameter to test")
+    ref = _equal_chains(rt, names, "the mean test")
+    act = _equal_chains(at, names, "the mean test")
+    std = ref.reshape(len(names), -1).std(axis=1)
+    live = np.isfinite(std) & (std > 0)
+    scale = np.zeros(std.size)
+    scale[live] = 1.0 / std[live]
+    with _ffi.value_errors():
+        det = mean_shift_test(ref, act, scale=scale, jitter=jitter, r=r, context=context or _ffi.default_context())
+    kept = [n for i, n in enumerate(names) if live[i]]
+    out = {k: (int(det[k]) if k in ("dof", "info", "b_ref", "a_ref", "b_act", "a_act") else float(det[k]))
+           for k in ("T", "dof", "p_value", "info", "mess_ref", "mess_act", "b_ref", "a_ref", "b_act", "a_act")}
+    out["singular"] = kept[det["info"] - 1] if det["info"] else None
+    out["z"] = {n: float(v) for n, v in zip(kept, det["z"])}
+    out["shift"] = {n: float(v) for n, v in zip(kept, det["shift"])}
+    return out

@@ -284,3 +284,54 @@ def validate_weighted(model: str, actual: Mapping[str, Sequence[float]], log_wei
     if ess_min is not None and not ess >= ess_min:
         failures.append(f"ess={ess:.6g} < {ess_min}")
     return WeightedValidateResult(passed=not failures, compare=cmp_res, stats=stats, ess=ess, khat=khat, failures=failures)
+
+
+@dataclass(frozen=True)
+class MeanShiftValidateResult:
+    passed: bool
+    test: dict                                   # batchmeans.mean_shift_test, "z" and "shift" keyed by (live) parameter
+    p_value: float                               # its asymptotic chi-square p-value (NaN when V is singular)
+    failures: list[str] = field(default_factory=list)
+
+
+def validate_mean_shift(model: str, actual: Mapping[str, Sequence[float]], chains: int, p_min: float | None = None,
+                        jitter: float = 0.0, r: int = 3, store: DataStore | None = None, context=None) -> MeanShiftValidateResult:
+    """A calibrated joint test of the means of `actual` against a model's reference draws: `batchmeans.mean_shift_test`
+    with every parameter scaled by 1 / reference std (0 where that std is not finite and > 0).  `validate` takes pooled
+    draws and knows no chains, and the long-run covariance needs them: `actual[p]` holds the pooled draws of `chains`
+    equally long chains, chain after chain; the reference's chains come from its table.  `test["z"]` is every live
+    parameter's shift in Monte Carlo standard errors, `test["singular"]` the name of the parameter at which the pooled
+    covariance is singular (else None: then T and p_value are NaN).  `p_min` adds the failure `mean_shift.p=... < p_min`
+    -- a NaN fails it --; without it `passed` is True.  The chi-square is asymptotic: it wants batches longer than the
+    autocorrelation time and many more batches than parameters."""
+    from .batchmeans import mean_shift_test
+    from .convert import table_to_tensor
+    store = store or DataStore()
+    ctx = context or _ffi.default_context()
+    params = list(actual.keys())
+    chains = int(chains)
+    lens = {len(actual[p]) for p in params}
+    if not params or len(lens) != 1:
+        raise ValueError("mean_shift needs joint draws: at least one parameter, all of the same length")
+    m = lens.pop()
+    if chains < 1 or m == 0 or m % chains:
+        raise ValueError(f"{m} draws per parameter are not {chains} chains of equal length")
+    x, counts = table_to_tensor(store.open_draws(model, params=params).read_all(), params)
+    if len(counts) == 0 or not np.all(counts == counts[0]):
+        raise ValueError("mean_shift requires reference chains of equal length")
+    ref = x.reshape(len(params), len(counts), int(counts[0]))
+    act = np.stack([np.asarray(actual[p], dtype=np.float64) for p in params]).reshape(len(params), chains, m // chains)
+    std = ref.reshape(len(params), -1).std(axis=1)
+    live = np.isfinite(std) & (std > 0)
+    scale = np.zeros(std.size)
+    scale[live] = 1.0 / std[live]
+    with _ffi.value_errors():
+        det = mean_shift_test(ref, act, scale=scale, jitter=jitter, r=r, context=ctx)
+    names = [p for i, p in enumerate(params) if live[i]]
+    det["z"] = {p: float(v) for p, v in zip(names, det["z"])}
+    det["shift"] = {p: float(v) for p, v in zip(names, det["shift"])}
+    det["singular"] = names[det["info"] - 1] if det["info"] else None
+    failures = []
+    if p_min is not None and not det["p_value"] >= p_min:
+        failures.append(f"mean_shift.p={det['p_value']:.3g} < {p_min}")
+    return MeanShiftValidateResult(passed=not failures, test=det, p_value=det["p_value"], failures=failures)
