@@ -18,7 +18,13 @@ the families that sort, 4 x 16 385 = 65 540 pooled draws (32-bit positions, seve
 the others the second size their own edge tests use.  Large draws are offset by 1000 * (index + 1) where the statistic
 allows, so that a word a large call left behind is never a plausible value of the small call that follows.
 
-REFUSED: calls that end in a documented error, most of them after device work has run.
+The entries of the four ABI tables are placed here: `_abi.SYMBOLS` (mcr_*), `_xabi.XSYMBOLS` (mcrx_*: they carve the main
+context's lane workspace), `_iabi.ISYMBOLS` (mci_*) and `_babi.BSYMBOLS` (mcb_*), the last two in companion libraries whose
+handles -- one per Context, each with buffers of its own that only grow -- the families reach through
+`indicator._handle(ctx)` and `batchmeans._handle(ctx)`.
+
+REFUSED: calls that end in a documented error, most of them after device work has run, and one that stops part-way with
+MCR_OK and says so in its result.
 """
 from __future__ import annotations
 
@@ -684,10 +690,201 @@ class ChainLayout(Family):
         assert np.array_equal(r["order"], order) and np.array_equal(r["ids"], ids) and np.array_equal(r["counts"], counts)
 
 
+# ---- the extension entries and the two companion libraries ---------------------------------------------------------------
+# mcrx_* carve the main context's lane workspace; mci_* and mcb_* each have a handle of their own per Context (a stream, a
+# workspace and an upload buffer that only grow), and mean_shift_test crosses all three in one call.  Each of these
+# families also has `host(inputs)`: the same fields from the definitions on the host, which the CPU test feeds to `check`.
+
+def _scalars(r: dict) -> dict:
+    """unpack()'s 0-d arrays as Python numbers, as the public calls return them."""
+    return {k: (v.item() if isinstance(v, np.ndarray) and v.ndim == 0 else v) for k, v in r.items()}
+
+
+class Linalg(Family):
+    """mcrx_cholesky of an SPD matrix, then mcrx_solve_lower of the factor it returned against K right-hand sides."""
+    name, symbols = "linalg", ("mcrx_cholesky", "mcrx_solve_lower")
+    SHAPES = {"small": (17, 1), "large": (3 * 64 + 1, 65)}                  # (P, K): 3 NB + 1, test_gaussian_gpu's largest
+
+    def build(self, size):
+        from test_gaussian_refs_cpu import spd
+        P, K = self.SHAPES[size]
+        return dict(A=spd(P, 1e3, self.seed(size)), B=np.random.default_rng(self.seed(size)).standard_normal((P, K)))
+
+    @staticmethod
+    def _both(inputs, cholesky, solve_lower):
+        L, info, logdet = cholesky(inputs["A"])
+        return pack(dict(L=L, info=info, logdet=logdet, X=solve_lower(L, inputs["B"])))
+
+    def run(self, ctx, inputs):
+        from mcmc_ref_hip import gaussian
+        return self._both(inputs, lambda a: gaussian.cholesky(a, context=ctx), lambda l, b: gaussian.solve_lower(l, b, context=ctx))
+
+    def host(self, inputs):
+        from mcmc_ref_hip import gaussian
+        return self._both(inputs, gaussian.cholesky_host, gaussian.solve_lower_host)
+
+    def check(self, inputs, got, ctx=None):
+        from test_gaussian_refs_cpu import check_factor, solve_residual_ratio
+        r = _scalars(unpack(got))
+        check_factor(inputs["A"], r["L"], r["info"], r["logdet"], self.name)
+        ratio = solve_residual_ratio(r["L"], r["X"], inputs["B"])
+        assert r["X"].shape == inputs["B"].shape and ratio <= 1.0, (self.name, ratio)
+
+
+class GaussianCheck(Family):
+    """scale = 1 / the reference's std with the middle parameter dropped by a zero: P_live < P, so Cr, Ca and W are
+    written PL x PL inside their P x P carve."""
+    name, symbols = "gaussian_check", ("mcrx_gaussian_check",)
+    SHAPES = {"small": (3, 131, 77), "large": (2 * 64 + 1, 2049, 1025)}      # (P, Mr, Ma): 2 NB + 1
+
+    def __init__(self, index):
+        super().__init__(index)
+        self._want: dict = {}
+
+    def build(self, size):
+        from test_gaussian_refs_cpu import pair
+        P, Mr, Ma = self.SHAPES[size]
+        ref, act = pair(P, Mr, Ma, seed=self.seed(size))
+        scale = 1.0 / ref.std(axis=1)
+        scale[P // 2] = 0.0
+        return dict(ref=ref, act=act, scale=scale)
+
+    def reference(self, inputs) -> dict:
+        """gaussian_reference of the inputs (long double), once per size."""
+        from test_gaussian_refs_cpu import gaussian_reference
+        key = id(inputs)
+        if key not in self._want:
+            self._want[key] = gaussian_reference(inputs["ref"], inputs["act"], inputs["scale"])
+        return self._want[key]
+
+    def run(self, ctx, inputs):
+        from mcmc_ref_hip import gaussian
+        return pack(gaussian.gaussian_check(inputs["ref"], inputs["act"], inputs["scale"], shift=True, context=ctx))
+
+    def host(self, inputs):
+        from mcmc_ref_hip import gaussian
+        return pack(gaussian.gaussian_check_host(inputs["ref"], inputs["act"], inputs["scale"], shift=True))
+
+    def check(self, inputs, got, ctx=None):
+        from test_gaussian_refs_cpu import check_statistics
+        r, want = _scalars(unpack(got)), self.reference(inputs)
+        assert want["p_live"] == inputs["ref"].shape[0] - 1
+        check_statistics(r, want, self.name)
+        assert np.abs(r["shift"] - want["shift"]).max() <= 1e-9 * max(1.0, np.abs(want["shift"]).max()), self.name
+
+
+class IndicatorEss(Family):
+    """x <= the pooled quantiles at PROBS; parameter 0 is rounded to halves (ties, and draws equal to a threshold).  small:
+    the ballot pack and the lag kernel on LDS; large: the smallest N whose C (ceil(N / 64) + 1) words exceed MCI_LDS_WORDS,
+    parameters innermost: the tile pack and the lag kernel on global words with its prefix counts."""
+    name, symbols = "indicator_ess", ("mci_indicator_ess",)
+    PROBS = (0.05, 0.5, 0.95)
+    LDS_WORDS = 8192                                          # MCI_LDS_WORDS (the CPU test holds it to the mirror)
+
+    def shape(self, size):
+        """(C, N, P, layout)"""
+        if size == "small":
+            return 2, 129, 3, "pcn"
+        C_ = 3
+        return C_, 64 * (self.LDS_WORDS // C_ - 1) + 1, 2, "cnp"
+
+    def build(self, size):
+        from test_indicator_gpu import draws, quantile_requests
+        C_, N, P, layout = self.shape(size)
+        if size == "small":
+            x = draws(self.seed(size), P, C_, N)
+        else:                                                 # iid: the walk ends in the first lag block
+            x = np.random.default_rng(self.seed(size)).normal(size=(P, C_, N))
+            x[0] = np.round(x[0] * 2) / 2
+        upper = quantile_requests(x, self.PROBS)[1]
+        return dict(x=np.ascontiguousarray(np.transpose(x, ["pcn".index(a) for a in layout])), layout=layout, upper=upper)
+
+    def run(self, ctx, inputs):
+        from mcmc_ref_hip import indicator
+        return pack(indicator.indicator_ess(inputs["x"], -np.inf, inputs["upper"], inputs["layout"], ctx))
+
+    def host(self, inputs):
+        from mcmc_ref_hip import indicator
+        return pack(indicator.indicator_ess_host(inputs["x"], -np.inf, inputs["upper"], inputs["layout"]))
+
+    def check(self, inputs, got, ctx=None):
+        from test_indicator_gpu import same
+        from test_indicator_refs_cpu import close, restate
+        r = unpack(got)
+        assert same(r, unpack(self.host(inputs))), self.name
+        x = np.transpose(inputs["x"], [inputs["layout"].index(a) for a in "pcn"])
+        p, k = x.shape[0] - 1, 1                              # the last parameter's median, by the definition in integers
+        exp = restate((x[p] <= inputs["upper"][p, k]).astype(np.int64))
+        assert (int(r["trunc"][p, k]), int(r["ones"][p, k])) == exp[1:] and close(float(r["ess"][p, k]), exp[0]), (self.name, exp)
+
+
+class BatchMeans(Family):
+    """small: stride_n == 1, the time route with one register row of batches; large: parameters innermost, the tile
+    route, a batch of more than one block of 1024 leaves, P off the 64-parameter tile.  (b is a multiple of 3: r = 3.)"""
+    name, symbols = "batch_means", ("mcb_batch_means",)
+    SHAPES = {"small": (2, 131, 3, 9, "pcn"), "large": (3, 3 * 1101 + 7, 130, 1101, "cnp")}      # (C, N, P, b, layout)
+
+    def build(self, size):
+        from test_batchmeans_gpu import draws
+        C_, N, P, b, layout = self.SHAPES[size]
+        x = draws(self.seed(size), P, C_, N) + self.offset(size)
+        return dict(x=np.ascontiguousarray(np.transpose(x, ["pcn".index(a) for a in layout])), layout=layout, b=b)
+
+    def run(self, ctx, inputs):
+        from mcmc_ref_hip import batchmeans
+        return pack(batchmeans.batch_means(inputs["x"], inputs["layout"], batch=inputs["b"], r=3, context=ctx))
+
+    def host(self, inputs):
+        from mcmc_ref_hip import batchmeans
+        return pack(batchmeans.batch_means_host(inputs["x"], inputs["layout"], batch=inputs["b"], r=3))
+
+    def check(self, inputs, got, ctx=None):
+        from test_batchmeans_gpu import same
+        from test_batchmeans_refs_cpu import bits, restate_batch_means
+        r = _scalars(unpack(got))
+        assert same(r, _scalars(unpack(self.host(inputs)))), self.name
+        bm, mu = restate_batch_means(inputs["x"], inputs["layout"], inputs["b"])
+        assert bits(r["bm"]) == bits(bm) and bits(r["mu"]) == bits(mu), self.name
+
+
+class MeanShiftTest(Family):
+    """One call, three handles: mcb_batch_means_dev -> mcb_pooled_dev -> mcr_covariance_dev -> mcb_lrv_finish_dev /
+    mcb_pool_dev -> mcrx_cholesky_dev -> mcrx_solve_lower_dev.  The cases are test_batchmeans_refs_cpu.e2e_case's at the
+    smallest and the largest P_live (cached there per P, with the long double answer)."""
+    name = "mean_shift_test"
+    symbols = ("mcb_batch_means_dev", "mcb_pooled_dev", "mcr_covariance_dev", "mcb_lrv_finish_dev", "mcb_pool_dev", "mcrx_cholesky_dev",
+               "mcrx_solve_lower_dev")
+
+    @staticmethod
+    def p_live(size) -> int:
+        from test_batchmeans_refs_cpu import E2E_P
+        return min(E2E_P) if size == "small" else max(E2E_P)
+
+    def build(self, size):
+        from test_batchmeans_refs_cpu import e2e_case
+        ref, act, scale, b_ref, b_act, _ = e2e_case(self.p_live(size))
+        return dict(ref=ref, act=act, scale=scale, b_ref=b_ref, b_act=b_act, size=size)
+
+    def run(self, ctx, inputs):
+        from mcmc_ref_hip import batchmeans
+        return pack(batchmeans.mean_shift_test(inputs["ref"], inputs["act"], scale=inputs["scale"], r=3, context=ctx,
+                                               batch_ref=inputs["b_ref"], batch_act=inputs["b_act"]))
+
+    def host(self, inputs):
+        from mcmc_ref_hip import batchmeans
+        return pack(batchmeans.mean_shift_test_host(inputs["ref"], inputs["act"], scale=inputs["scale"], r=3,
+                                                    batch_ref=inputs["b_ref"], batch_act=inputs["b_act"]))
+
+    def check(self, inputs, got, ctx=None):
+        from test_batchmeans_refs_cpu import check_mean_test, e2e_case
+        check_mean_test(_scalars(unpack(got)), e2e_case(self.p_live(inputs["size"]))[5], self.name)
+
+
 FAMILIES = [cls(i) for i, cls in enumerate((
     Summarize, Enqueue, DiagnoseChains, Moments, Compare, TwoSample, SlicedTwoSample, EnergyDistance, Covariance, NestedRhat,
     ParetoKhat, Psis, Hdi, Autocorr, WeightedSummary, SbcRanks, ReadColumns, SummarizeFiles, CsvDecode, JsonDecode,
-    CsvTableDecode, WriteParquet, WriteCsv, ChainLayout))]
+    CsvTableDecode, WriteParquet, WriteCsv, ChainLayout, Linalg, GaussianCheck, IndicatorEss, BatchMeans, MeanShiftTest))]
+NEW_FAMILIES = FAMILIES[24:]                                  # the ones with `host`
 BY_NAME = {f.name: f for f in FAMILIES}
 NAMES = [f.name for f in FAMILIES]
 
@@ -695,11 +892,13 @@ NAMES = [f.name for f in FAMILIES]
 # ---- refused calls ---------------------------------------------------------------------------------------------------
 
 class Refusal:
-    """A call that returns a documented error: call(ctx) makes it and asserts the code and the message."""
+    """A call that returns a documented error: call(ctx) makes it and asserts the code and the message.  With `outcome`
+    (a predicate on what the call returned) the call is one that stops part-way and says so in its result, not in a code:
+    then the code is MCR_OK, no message is asked for, and call(ctx) asserts the predicate."""
 
-    def __init__(self, name: str, family: str, defect: str, code_name: str, fragment: str, build, call):
+    def __init__(self, name: str, family: str, defect: str, code_name: str, fragment: str, build, call, outcome=None):
         self.name, self.family, self.defect, self.code_name, self.fragment = name, family, defect, code_name, fragment
-        self._build, self._call, self._inputs = build, call, None
+        self._build, self._call, self._inputs, self.outcome = build, call, None, outcome
 
     def inputs(self):
         if self._inputs is None:
@@ -712,6 +911,10 @@ class Refusal:
 
     def call(self, ctx):
         from mcmc_ref_hip import _ffi
+        if self.outcome is not None:
+            result = self._call(ctx, self.inputs())
+            assert self.code() == _ffi.MCR_OK and self.outcome(result), (self.name, result)
+            return
         try:
             rc = self._call(ctx, self.inputs())
             message = (ctx.lib.mcr_last_error(ctx.handle) or b"").decode()
@@ -796,6 +999,66 @@ def _under_the_limit(ctx, i):
     return 0
 
 
+COMPANION_LIMIT = 1 << 30                                     # the default limit of an mci or mcb handle, which the tests restore
+TINY_LIMIT = 64                                               # below the 256 bytes any one parameter's workspace is rounded up to
+
+
+def _batchmeans():
+    from mcmc_ref_hip import batchmeans
+    return batchmeans
+
+
+def _stopped_inputs():
+    from test_gaussian_refs_cpu import NB, defect_matrix
+    A, info = defect_matrix(2 * NB + 5, "neg", NB + 1)
+    return dict(A=A, info=info)
+
+
+def _cholesky_raw(ctx, i):
+    """(info, logdet, the info the definition gives)"""
+    from mcmc_ref_hip import gaussian
+    _, info, logdet = gaussian.cholesky(i["A"], context=ctx)
+    return info, logdet, i["info"]
+
+
+def _gaussian_limit_inputs():
+    from test_gaussian_refs_cpu import gauss_case
+    ref, act, scale, _ = gauss_case(129, 2000, 1500)           # test_gaussian_gpu.test_workspace_limit's shape
+    return dict(ref=ref, act=act, scale=scale)
+
+
+def _gaussian_under_the_limit(ctx, i):
+    from mcmc_ref_hip import gaussian
+    P, Mr = i["ref"].shape
+    assert gaussian.gaussian_workspace(Mr, i["act"].shape[1], P, context=ctx) > LOW_LIMIT
+    ctx._check(ctx.lib.mcr_set_workspace_limit(ctx.handle, LOW_LIMIT))
+    try:
+        gaussian.gaussian_check(i["ref"], i["act"], i["scale"], context=ctx)
+    finally:
+        ctx._check(ctx.lib.mcr_set_workspace_limit(ctx.handle, BIG_LIMIT))
+    return 0
+
+
+def _indicator_under_the_limit(ctx, i):
+    from mcmc_ref_hip import indicator
+    indicator.set_workspace_limit(TINY_LIMIT, ctx)
+    try:
+        indicator.indicator_ess(i["x"], -np.inf, 0.0, "pcn", ctx)
+    finally:
+        indicator.set_workspace_limit(COMPANION_LIMIT, ctx)
+    return 0
+
+
+def _batch_means_under_the_limit(ctx, i):
+    bm = _batchmeans()
+    bm.set_workspace_limit(TINY_LIMIT, context=ctx)
+    try:
+        bm.batch_means(i["x"], batch=i["batch"], r=3, context=ctx)
+    finally:
+        bm.set_workspace_limit(COMPANION_LIMIT, context=ctx)
+    return 0
+
+
 REFUSED = [
     # one NaN in the last of the two sort tiles of a parameter (4 x 1100 pooled draws)
     Refusal("summarize_nan_in_last_tile", "summarize", "one_nan", "MCR_ENONFINITE", "non-finite",
@@ -823,6 +1086,20 @@ REFUSED = [
     # a parameter's 160 000 keys alone are larger than the limit
     Refusal("summarize_under_the_limit", "summarize", "limit", "MCR_ENOMEM", "one parameter needs",
             lambda: dict(x=_tensor(9008, (2, 4, 40000))), _under_the_limit),
+    # the pivot of column NB + 1 is -1: the second diagonal block stops at its second column, the panels after it skip on
+    # the info word, and the factor area is left half-done.  MCR_OK: the finding is in (info, logdet).
+    Refusal("cholesky_stopped_mid_block", "linalg", "negative_pivot", "MCR_OK", "", _stopped_inputs, _cholesky_raw,
+            outcome=lambda r: r[0] == r[2] and r[1] != r[1]),
+    # after both samples were staged
+    Refusal("gaussian_check_under_the_limit", "gaussian_check", "gaussian_limit", "MCR_ENOMEM", "workspace limit too small",
+            _gaussian_limit_inputs, _gaussian_under_the_limit),
+    Refusal("indicator_under_the_limit", "indicator_ess", "companion_limit", "MCR_ENOMEM", "one parameter needs",
+            lambda: dict(x=_tensor(9009, (2, 2, 100)), batch=None), _indicator_under_the_limit),
+    Refusal("batch_means_under_the_limit", "batch_means", "companion_limit", "MCR_ENOMEM", "limit",
+            lambda: dict(x=_tensor(9010, (2, 3, 3 * 99 + 5)), batch=99), _batch_means_under_the_limit),
+    Refusal("batch_means_batch_over_n", "batch_means", "batch_over_n", "MCR_EINVAL", "outside [1, N",
+            lambda: dict(x=_tensor(9011, (2, 3, 3 * 99 + 5)), batch=3 * 99 + 6),
+            lambda ctx, i: _batchmeans().batch_means(i["x"], batch=i["batch"], r=1, context=ctx) and 0),
 ]
 
 
@@ -831,17 +1108,23 @@ REFUSED = [
 NOT_IN_THE_MATRIX = {
     "no context, or no device work": (
         "mcr_version", "mcr_device_count", "mcr_init", "mcr_free", "mcr_last_error", "mcr_pareto_tail_length", "mcr_psis_tail_length",
-        "mcr_sbc_uniformity", "mcr_chi2_sf", "mcr_format_double", "mcr_parse_double", "mcr_parse_csv_number", "mcr_parse_json_number"),
+        "mcr_sbc_uniformity", "mcr_chi2_sf", "mcr_format_double", "mcr_parse_double", "mcr_parse_csv_number", "mcr_parse_json_number",
+        "mci_version", "mci_init", "mci_free", "mci_last_error", "mcb_version", "mcb_init", "mcb_free", "mcb_last_error"),
     "a query of the planner: host arithmetic on the limit": (
         "mcr_plan_chunks", "mcr_plan_chunks_chains", "mcr_sliced_plan", "mcr_energy_workspace", "mcr_nested_plan", "mcr_pareto_plan",
-        "mcr_psis_plan", "mcr_hdi_plan", "mcr_weighted_plan", "mcr_sbc_plan", "mcr_autocorr_plan"),
-    "the profiler": ("mcr_profile_enable", "mcr_profile_reset", "mcr_profile_get"),
+        "mcr_psis_plan", "mcr_hdi_plan", "mcr_weighted_plan", "mcr_sbc_plan", "mcr_autocorr_plan", "mcrx_gaussian_workspace",
+        "mci_indicator_plan", "mcb_batch_size"),
+    "the profiler": ("mcr_profile_enable", "mcr_profile_reset", "mcr_profile_get", "mci_profile_enable", "mci_kernel_ms",
+                     "mcb_profile_enable", "mcb_kernel_ms"),
     "the caller's own memory, and waiting": ("mcr_dev_alloc", "mcr_dev_free", "mcr_memcpy_h2d", "mcr_memcpy_d2h", "mcr_sync"),
-    "a setting (REFUSED's last entry sets and restores it)": ("mcr_set_workspace_limit",),
+    "a setting (REFUSED's *_under_the_limit entries set and restore it)": (
+        "mcr_set_workspace_limit", "mci_set_workspace_limit", "mcb_set_workspace_limit"),
     "a counter": ("mcr_rho_guard_count", "mcr_tile_fallback_count"),
     "measurement and synthetic data: they write the caller's tensor only": ("mcr_hbm_probe", "mcr_fill_synthetic", "mcr_fill_synthetic_at"),
     "a host routine": ("mcr_energy_distance_host", "mcr_pareto_fit_host", "mcr_psis_host", "mcr_hdi_sorted_host", "mcr_weighted_host",
-                       "mcr_sbc_ranks_host", "mcr_autocorr_host", "mcr_parquet_write_host", "mcr_csv_write_host"),
+                       "mcr_sbc_ranks_host", "mcr_autocorr_host", "mcr_parquet_write_host", "mcr_csv_write_host",
+                       "mcrx_cholesky_host", "mcrx_solve_lower_host", "mcrx_gaussian_check_host", "mci_indicator_ess_host",
+                       "mcb_batch_means_host", "mcb_lrv_finish_host", "mcb_pool_host", "mcb_tree_sum_host"),
     "the communicator": ("mcr_comm_unique_id", "mcr_comm_init", "mcr_comm_free", "mcr_comm_world", "mcr_comm_rank", "mcr_comm_has_deadline",
                          "mcr_comm_all_gather", "mcr_comm_all_reduce", "mcr_comm_barrier"),
     "an accessor of a handle": (
@@ -851,12 +1134,15 @@ NOT_IN_THE_MATRIX = {
     "test_call_order_gpu.test_default_lanes calls it between the families": ("mcr_summarize_wait",),
     # Not among the reasons the matrix was planned with: the twin of an entry that IS in the matrix.  It carves the same
     # layout in the same buffers behind the caller's upload (or, for the images, behind another way to hand the bytes
-    # over), and its own family's route tests hold it to the matrix entry's bits.
+    # over), and its own family's route tests hold it to the matrix entry's bits: mcrx_gaussian_check_dev in
+    # test_gaussian_gpu.test_gaussian_check_against_long_double, mci_indicator_ess_dev in
+    # test_indicator_gpu.test_routes_entries_and_dtypes_agree.  (mcr_covariance_dev, mcrx_cholesky_dev, mcrx_solve_lower_dev
+    # and mcb_batch_means_dev are reached by the mean_shift_test family.)
     "the device-resident (or caller-image) twin of an entry in the matrix": (
         "mcr_summarize_dev", "mcr_summarize_models", "mcr_summarize_chains_enqueue", "mcr_summarize_chains_dev",
         "mcr_sliced_two_sample_dev", "mcr_energy_distance_dev", "mcr_nested_rhat_dev", "mcr_pareto_khat_dev", "mcr_psis_dev",
-        "mcr_hdi_dev", "mcr_weighted_summary_dev", "mcr_sbc_ranks_dev", "mcr_autocorr_dev", "mcr_covariance_dev", "mcr_csv_open",
-        "mcr_csv_open_table", "mcr_chain_layout_many_dev"),
+        "mcr_hdi_dev", "mcr_weighted_summary_dev", "mcr_sbc_ranks_dev", "mcr_autocorr_dev", "mcr_csv_open",
+        "mcr_csv_open_table", "mcr_chain_layout_many_dev", "mcrx_gaussian_check_dev", "mci_indicator_ess_dev"),
     # Also outside the planned reasons: three small row utilities of the exporters, each one kernel on the caller's
     # buffers plus a counter word; test_csv_write_gpu and test_chain_layout_gpu run them behind summaries.
     "a row utility on the caller's buffers": ("mcr_select_rows_dev", "mcr_gather_rows_dev", "mcr_gather_rows_order_dev"),
