@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Builds mcmc-db_amd/lib/libmcmcref_hip.so and its companions libmcmcref_iess.so (include/mcmcref_iess.h) and
-libmcmcref_bm.so (include/mcmcref_bm.h) -- each with its own units and its own version script, none linked against
-another -- for gfx950 with hipcc (cross-compiles without a GPU).
+"""Builds mcmc-db_amd/lib/libmcmcref_hip.so and its companions libmcmcref_iess.so (include/mcmcref_iess.h),
+libmcmcref_bm.so (include/mcmcref_bm.h) and libmcmcref_std.so (include/mcmcref_std.h) -- each with its own units and its
+own version script, none linked against another -- for gfx950 with hipcc (cross-compiles without a GPU).
+libmcmcref_std.so reuses the sort stage and the summary pipeline as code: the objects of the main units are linked into
+it beside its own unit, and its version script keeps every name but mcs_* local.
 
 One object per translation unit of csrc/ (lib/obj/), each with the dependency file the compiler writes for it; stale
 units compile concurrently and the objects are linked into the library.  No kernel is called across units, so the link
@@ -19,10 +21,12 @@ HERE = Path(__file__).resolve().parent
 UNITS = ("mcr_api", "mcr_stats", "mcr_files", "mcr_comm")
 IESS_UNITS = ("mci_api",)
 BM_UNITS = ("mcb_api",)
+STD_UNITS = ("mcs_api",)
 OBJ = HERE / "lib" / "obj"
 OUT = HERE / "lib" / "libmcmcref_hip.so"
 IESS_OUT = HERE / "lib" / "libmcmcref_iess.so"
 BM_OUT = HERE / "lib" / "libmcmcref_bm.so"
+STD_OUT = HERE / "lib" / "libmcmcref_std.so"
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fvisibility=hidden",
          "-Wall", "-Wno-unused-value", "-Wno-pass-failed"]
 IESS_FLAGS = FLAGS + ["-ffp-contract=off", f"-I{HERE.parent / 'include'}"]    # host and device must round alike
@@ -64,10 +68,10 @@ def link(out: Path, units: tuple, version_script: str, relinked: bool, verbose: 
 
 
 def build(force: bool = False, verbose: bool = False) -> Path:
-    """All three libraries; returns the path of libmcmcref_hip.so."""
+    """All four libraries; returns the path of libmcmcref_hip.so."""
     OBJ.mkdir(parents=True, exist_ok=True)
     cc = [hipcc()] + (["-Rpass-analysis=kernel-resource-usage"] if verbose else [])
-    flags = {**{u: FLAGS for u in UNITS}, **{u: IESS_FLAGS for u in IESS_UNITS + BM_UNITS}}
+    flags = {**{u: FLAGS for u in UNITS}, **{u: IESS_FLAGS for u in IESS_UNITS + BM_UNITS + STD_UNITS}}
     todo = [u for u in flags if force or stale(u)]
     if todo:
         jobs = min(len(todo), int(os.environ.get("MAX_JOBS", "4")))
@@ -77,6 +81,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     link(OUT, UNITS, "mcr_exports.map", any(u in UNITS for u in todo), verbose)
     link(IESS_OUT, IESS_UNITS, "mci_exports.map", any(u in IESS_UNITS for u in todo), verbose)
     link(BM_OUT, BM_UNITS, "mcb_exports.map", any(u in BM_UNITS for u in todo), verbose)
+    link(STD_OUT, UNITS + STD_UNITS, "mcs_exports.map", any(u in UNITS + STD_UNITS for u in todo), verbose)
     return OUT
 
 

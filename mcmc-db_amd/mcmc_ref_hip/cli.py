@@ -15,6 +15,8 @@ parameter and, with `--sliced K`, along K random directions of the joint distrib
 `loo FILE` prints PSIS-LOO of a table's pointwise log-likelihood columns: elpd_loo, p_loo and the observations' k-hats.
 `weighted-summary FILE` prints every parameter's mean, sd, standard error and quantiles under a column of importance weights.
 `ess-quantile FILE` prints the effective draws behind every parameter's quantile estimates (and its local efficiency).
+`std-diagnostics FILE` prints R-hat and ESS in the Stan convention (split chains, Blom scores, Geyer's rule): the numbers
+of stansummary, posterior and ArviZ, where `diagnostics` and `cmdstan-summary` print the reference's.
 `multi-ess FILE` prints the multivariate effective sample size of a table from its batch-means long-run covariance, and
 `mean-test REF_FILE ACT_FILE` the calibrated joint test of equal means of two tables; exits 1 when `--p-min` is missed.
 `hdi FILE` prints the highest-density interval(s) of every parameter: the shortest interval holding a share of the draws.
@@ -276,6 +278,24 @@ def ess_quantile_cmd(file: Path, params: str | None, probs: tuple[float, ...], l
     except (ValueError, KeyError, IndexError) as exc:
         raise click.ClickException(str(exc)) from exc
     _echo_stats(stats, format_)
+
+
+@main.command("std-diagnostics")
+@click.argument("file", type=click.Path(path_type=Path, exists=True, dir_okay=False))
+@click.option("--params", default=None, help="Comma-separated parameter list")
+@click.option("--basic", is_flag=True, help="Also rhat_basic, ess_mean and mcse_mean of the draws themselves")
+@click.option("--json", "as_json", is_flag=True, help="Print JSON instead of a table")
+def std_diagnostics_cmd(file: Path, params: str | None, basic: bool, as_json: bool) -> None:
+    """R-hat and ESS of a table in the Stan convention (no counterpart in the reference): split chains, rank
+    normalisation with Blom scores, folding, Geyer's initial sequences -- rhat, ess_bulk and ess_tail as stansummary,
+    posterior and ArviZ define them, with the walks' lags.  Chains of equal length; for an odd length the middle draw of
+    each chain is dropped."""
+    from . import standard
+    try:
+        stats = standard.diagnostics_file(file, params=params.split(",") if params else None, basic=basic)
+    except (ValueError, KeyError, IndexError) as exc:
+        raise click.ClickException(str(exc)) from exc
+    _echo_stats(stats, "json" if as_json else "table")
 
 
 @main.command("multi-ess")
