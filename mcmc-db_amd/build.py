@@ -60,6 +60,12 @@ def run(cmd: list[str], verbose: bool) -> None:
     subprocess.run(cmd, check=True)
 
 
+# (output, units, version script): libmcmcref_std.so links the main units' objects beside its own
+LIBRARIES = ((OUT, UNITS, "mcr_exports.map"), (IESS_OUT, IESS_UNITS, "mci_exports.map"), (BM_OUT, BM_UNITS, "mcb_exports.map"),
+             (STD_OUT, UNITS + STD_UNITS, "mcs_exports.map"))
+UNIT_FLAGS = {**{u: FLAGS for u in UNITS}, **{u: IESS_FLAGS for u in IESS_UNITS + BM_UNITS + STD_UNITS}}
+
+
 def link(out: Path, units: tuple, version_script: str, relinked: bool, verbose: bool) -> None:
     objs = [OBJ / f"{u}.o" for u in units]
     if relinked or not out.exists() or any(o.stat().st_mtime > out.stat().st_mtime for o in objs):
@@ -71,17 +77,14 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     """All four libraries; returns the path of libmcmcref_hip.so."""
     OBJ.mkdir(parents=True, exist_ok=True)
     cc = [hipcc()] + (["-Rpass-analysis=kernel-resource-usage"] if verbose else [])
-    flags = {**{u: FLAGS for u in UNITS}, **{u: IESS_FLAGS for u in IESS_UNITS + BM_UNITS + STD_UNITS}}
-    todo = [u for u in flags if force or stale(u)]
+    todo = [u for u in UNIT_FLAGS if force or stale(u)]
     if todo:
         jobs = min(len(todo), int(os.environ.get("MAX_JOBS", "4")))
         with ThreadPoolExecutor(max_workers=max(jobs, 1)) as pool:
-            list(pool.map(lambda u: run(cc + flags[u] + ["-c", "-MD", "-MF", str(OBJ / f"{u}.d"), "-o", str(OBJ / f"{u}.o"),
+            list(pool.map(lambda u: run(cc + UNIT_FLAGS[u] + ["-c", "-MD", "-MF", str(OBJ / f"{u}.d"), "-o", str(OBJ / f"{u}.o"),
                                                          str(HERE / "csrc" / f"{u}.hip")], verbose), todo))
-    link(OUT, UNITS, "mcr_exports.map", any(u in UNITS for u in todo), verbose)
-    link(IESS_OUT, IESS_UNITS, "mci_exports.map", any(u in IESS_UNITS for u in todo), verbose)
-    link(BM_OUT, BM_UNITS, "mcb_exports.map", any(u in BM_UNITS for u in todo), verbose)
-    link(STD_OUT, UNITS + STD_UNITS, "mcs_exports.map", any(u in UNITS + STD_UNITS for u in todo), verbose)
+    for out, units, version_script in LIBRARIES:
+        link(out, units, version_script, any(u in units for u in todo), verbose)
     return OUT
 
 

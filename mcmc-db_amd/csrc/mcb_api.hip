@@ -1,50 +1,22 @@
-// mcb_api.hip -- the entries of include/mcmcref_bm.h: the handle (a stream, two cached device allocations that only
-// grow), the chunked batch-means call, the element-wise steps and the definitions on the host.  The library stands alone:
-// nothing of libmcmcref_hip.so's or libmcmcref_iess.so's.
+// mcb_api.hip -- the entries of include/mcmcref_bm.h: the handle (that of mcc_handle.hpp: a stream, two cached device
+// allocations that only grow), the chunked batch-means call, the element-wise steps and the definitions on the host.  The
+// library stands alone: nothing of libmcmcref_hip.so's or libmcmcref_iess.so's.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <vector>
 
 #include "mcb_kernels.hpp"
+#include "mcc_handle.hpp"
 
 namespace mcb {
 
-struct Handle {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    void* ws = nullptr;                 // one chunk's batch sums; the pool's live indices and scales
-    size_t ws_bytes = 0;
-    void* up = nullptr;                 // the host entry's copy of the tensor, and its outputs
-    size_t up_bytes = 0;
-    size_t limit = (size_t)1 << 30;
-    bool profile = false;
-    double ms[MCB_KERNELS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    char err[256] = "";
-};
-
-static thread_local char g_err[256] = "";
-
-static int fail(char* err, int code, const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(err, 256, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define MCB_HIP(h, call)                                                                                       \
-    do {                                                                                                       \
-        const hipError_t e_ = (call);                                                                          \
-        if (e_ != hipSuccess) return fail((h)->err, MCR_EHIP, "%s: %s", #call, hipGetErrorString(e_));         \
-    } while (0)
-
-static size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
+using Handle = mcc::Handle<MCB_KERNELS>;     // ws: one chunk's batch sums; the pool's live indices and scales.  up: the
+                                             // host entry's copy of the tensor, and its outputs
+using mcc::align_up;
+using mcc::fail;
+using mcc::g_err;
 
 // What every entry that takes a tensor refuses, in one place; `err` receives the cause.
 static int check_tensor(char* err, const void* draws, int dtype, int64_t C, int64_t N, int64_t P, int64_t sc, int64_t sn, int64_t sp)
@@ -123,46 +95,12 @@ static int make_plan(Handle* h, int64_t C, int64_t N, int64_t P, int64_t sn, int
     }
     pl->segs = (pl->a + pl->G - 1) / pl->G;
     const size_t per = sums ? (size_t)pl->A * 8 : 0;
-    if (align_up(per) > h->limit)
-        return fail(h->err, MCR_ENOMEM, "one parameter needs %zu bytes of workspace, the limit is %zu", align_up(per), h->limit);
-    int64_t lo = 1, hi = P;                                   // the most parameters under the limit
-    while (lo < hi) {
-        const int64_t mid = lo + (hi - lo + 1) / 2;
-        if (align_up((size_t)mid * per) <= h->limit) lo = mid;
-        else hi = mid - 1;
-    }
+    const int64_t lo = mcc::most_that_fit(P, [&](int64_t pc) { return align_up((size_t)pc * per, 256) <= h->limit; });
+    if (!lo) return fail(h->err, MCR_ENOMEM, "one parameter needs %zu bytes of workspace, the limit is %zu", align_up(per, 256), h->limit);
     const int64_t waves = C * pl->segs;                        // per parameter: no grid of a chunk reaches 2^31
     const int64_t grid_cap = ((int64_t)INT32_MAX - kTile) / waves;
     if (grid_cap < 1) return fail(h->err, MCR_EINVAL, "%lld batches are too many for one launch", (long long)pl->A);
     pl->chunk = lo < grid_cap ? lo : grid_cap;
-    return MCR_OK;
-}
-
-static int ensure(Handle* h, void** ptr, size_t* have, size_t need, const char* what)
-{
-    if (need <= *have) return MCR_OK;
-    if (*ptr) MCB_HIP(h, hipFree(*ptr));
-    *ptr = nullptr;
-    *have = 0;
-    if (hipMalloc(ptr, need) != hipSuccess) {
-        *ptr = nullptr;
-        (void)hipGetLastError();
-        return fail(h->err, MCR_ENOMEM, "cannot allocate %zu bytes for %s", need, what);
-    }
-    *have = need;
-    return MCR_OK;
-}
-
-static void clear_ms(Handle* h)
-{
-    for (double& v : h->ms) v = 0.0;
-}
-
-static int add_ms(Handle* h, int kernel, hipEvent_t from, hipEvent_t to)
-{
-    float t = 0.f;
-    MCB_HIP(h, hipEventElapsedTime(&t, from, to));
-    h->ms[kernel] += t;
     return MCR_OK;
 }
 
@@ -194,10 +132,10 @@ static int run_means(Handle* h, const void* x_dev, int dtype, int64_t C, int64_t
 {
     Plan pl;
     if (const int rc = make_plan(h, C, N, P, sn, b, mu_dev != nullptr, &pl)) return rc;
-    MCB_HIP(h, hipSetDevice(h->device));
+    MCC_HIP(h, hipSetDevice(h->device));
     if (mu_dev)
-        if (const int rc = ensure(h, &h->ws, &h->ws_bytes, align_up((size_t)pl.chunk * (size_t)pl.A * 8), "the batch sums")) return rc;
-    clear_ms(h);
+        if (const int rc = mcc::ensure(h, &h->ws, &h->ws_bytes, align_up((size_t)pl.chunk * (size_t)pl.A * 8, 256), "for the batch sums")) return rc;
+    h->timer.clear();
     const size_t es = dtype == MCR_F64 ? 8 : 4;
     const int route = pl.time ? MCB_KERNEL_TIME : MCB_KERNEL_TILE;
     for (int64_t p0 = 0; p0 < P; p0 += pl.chunk) {
@@ -205,23 +143,19 @@ static int run_means(Handle* h, const void* x_dev, int dtype, int64_t C, int64_t
         const char* x = (const char*)x_dev + (size_t)p0 * (size_t)sp * es;
         double* sums = mu_dev ? (double*)h->ws : nullptr;
         double* bm = bm_dev ? bm_dev + p0 * ld : nullptr;
-        if (h->profile) MCB_HIP(h, hipEventRecord(h->ev[0], h->stream));
+        MCC_HIP(h, h->timer.begin(h->stream));
         if (dtype == MCR_F64) launch_route(h, pl, (const double*)x, C, N, Pc, sc, sn, sp, b, sums, bm, ld);
         else launch_route(h, pl, (const float*)x, C, N, Pc, sc, sn, sp, b, sums, bm, ld);
-        MCB_HIP(h, hipGetLastError());
-        if (h->profile) MCB_HIP(h, hipEventRecord(h->ev[1], h->stream));
+        MCC_HIP(h, hipGetLastError());
+        MCC_HIP(h, h->timer.mark(h->stream, route));
         if (mu_dev) {
             if (dtype == MCR_F64) launch_mean(h, pl, (const double*)x, N, Pc, sn, sp, b, sums, mu_dev + p0);
             else launch_mean(h, pl, (const float*)x, N, Pc, sn, sp, b, sums, mu_dev + p0);
-            MCB_HIP(h, hipGetLastError());
+            MCC_HIP(h, hipGetLastError());
+            MCC_HIP(h, h->timer.mark(h->stream, MCB_KERNEL_MEAN));
         }
-        if (h->profile) MCB_HIP(h, hipEventRecord(h->ev[2], h->stream));
-        MCB_HIP(h, hipStreamSynchronize(h->stream));             // the next chunk writes the same workspace
-        if (h->profile) {
-            if (const int rc = add_ms(h, route, h->ev[0], h->ev[1])) return rc;
-            if (mu_dev)
-                if (const int rc = add_ms(h, MCB_KERNEL_MEAN, h->ev[1], h->ev[2])) return rc;
-        }
+        MCC_HIP(h, hipStreamSynchronize(h->stream));             // the next chunk writes the same workspace
+        MCC_HIP(h, h->timer.collect());
     }
     return MCR_OK;
 }
@@ -230,13 +164,13 @@ static int run_means(Handle* h, const void* x_dev, int dtype, int64_t C, int64_t
 template <class Launch>
 static int run_one(Handle* h, int kernel, Launch&& launch)
 {
-    clear_ms(h);
-    if (h->profile) MCB_HIP(h, hipEventRecord(h->ev[0], h->stream));
+    h->timer.clear();
+    MCC_HIP(h, h->timer.begin(h->stream));
     launch();
-    MCB_HIP(h, hipGetLastError());
-    if (h->profile) MCB_HIP(h, hipEventRecord(h->ev[1], h->stream));
-    MCB_HIP(h, hipStreamSynchronize(h->stream));
-    if (h->profile) return add_ms(h, kernel, h->ev[0], h->ev[1]);
+    MCC_HIP(h, hipGetLastError());
+    MCC_HIP(h, h->timer.mark(h->stream, kernel));
+    MCC_HIP(h, hipStreamSynchronize(h->stream));
+    MCC_HIP(h, h->timer.collect());
     return MCR_OK;
 }
 
@@ -275,52 +209,14 @@ int mcb_version(void) { return MCB_VERSION; }
 
 int mcb_init(int device, void** handle)
 {
-    if (!handle) return fail(g_err, MCR_EINVAL, "mcb_init: NULL handle pointer");
-    *handle = nullptr;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
-        (void)hipGetLastError();
-        return fail(g_err, MCR_ENODEVICE, "no HIP device is usable");
-    }
-    if (device < 0 || device >= count) return fail(g_err, MCR_ENODEVICE, "device %d: %d device(s) are visible", device, count);
-    Handle* h = new Handle;
-    h->device = device;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipEventCreate(&h->ev[i]);
-    if (e != hipSuccess) {
-        fail(g_err, MCR_EHIP, "mcb_init: %s", hipGetErrorString(e));
-        mcb_free(h);
-        return MCR_EHIP;
-    }
-    *handle = h;
-    return MCR_OK;
+    return mcc::open<Handle>(device, handle, "mcb_init", [] { return hipSuccess; });
 }
 
-void mcb_free(void* handle)
-{
-    Handle* h = (Handle*)handle;
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->ws) (void)hipFree(h->ws);
-    if (h->up) (void)hipFree(h->up);
-    for (hipEvent_t e : h->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
+void mcb_free(void* handle) { mcc::close((Handle*)handle); }
 
-const char* mcb_last_error(void* handle) { return handle ? ((Handle*)handle)->err : g_err; }
+const char* mcb_last_error(void* handle) { return mcc::last_error((Handle*)handle); }
 
-int mcb_set_workspace_limit(void* handle, size_t bytes)
-{
-    Handle* h = (Handle*)handle;
-    if (!h) return MCR_EINVAL;
-    if (bytes == 0) return fail(h->err, MCR_EINVAL, "a workspace limit of 0 bytes");
-    h->limit = bytes;
-    return MCR_OK;
-}
+int mcb_set_workspace_limit(void* handle, size_t bytes) { return mcc::set_workspace_limit((Handle*)handle, bytes); }
 
 int mcb_batch_size(int64_t N, int r, int64_t* b, int64_t* a)
 {
@@ -351,19 +247,16 @@ int mcb_batch_means(void* handle, const void* draws, int dtype, int64_t C, int64
     Handle* h = (Handle*)handle;
     if (!h) return MCR_EINVAL;
     if (const int rc = check_means(h->err, draws, dtype, C, N, P, stride_c, stride_n, stride_p, b, bm, ld, mu)) return rc;
-    const size_t es = dtype == MCR_F64 ? 8 : 4;
-    const size_t span = ((size_t)(C - 1) * (size_t)stride_c + (size_t)(N - 1) * (size_t)stride_n + (size_t)(P - 1) * (size_t)stride_p + 1) * es;
     const size_t bm_bytes = bm ? (size_t)P * (size_t)ld * 8 : 0, mu_bytes = mu ? (size_t)P * 8 : 0;
-    MCB_HIP(h, hipSetDevice(h->device));
-    if (const int rc = ensure(h, &h->up, &h->up_bytes, align_up(span) + align_up(bm_bytes) + align_up(mu_bytes), "the tensor")) return rc;
-    char* at = (char*)h->up;
-    double* d_bm = bm ? (double*)(at + align_up(span)) : nullptr;
-    double* d_mu = mu ? (double*)(at + align_up(span) + align_up(bm_bytes)) : nullptr;
-    MCB_HIP(h, hipMemcpy(h->up, draws, span, hipMemcpyHostToDevice));      // (complete on return: the kernels may start)
-    if (bm && ld > C * (N / b)) MCB_HIP(h, hipMemcpy(d_bm, bm, bm_bytes, hipMemcpyHostToDevice));   // the padding comes back as it was
+    char* at = nullptr;                                                     // the outputs, behind the tensor
+    if (const int rc = mcc::upload_span(h, draws, dtype, C, N, P, stride_c, stride_n, stride_p, align_up(bm_bytes, 256) + mu_bytes, &at))
+        return rc;
+    double* d_bm = bm ? (double*)at : nullptr;
+    double* d_mu = mu ? (double*)(at + align_up(bm_bytes, 256)) : nullptr;
+    if (bm && ld > C * (N / b)) MCC_HIP(h, hipMemcpy(d_bm, bm, bm_bytes, hipMemcpyHostToDevice));   // the padding comes back as it was
     if (const int rc = run_means(h, h->up, dtype, C, N, P, stride_c, stride_n, stride_p, b, d_bm, ld, d_mu)) return rc;
-    if (bm) MCB_HIP(h, hipMemcpy(bm, d_bm, bm_bytes, hipMemcpyDeviceToHost));
-    if (mu) MCB_HIP(h, hipMemcpy(mu, d_mu, mu_bytes, hipMemcpyDeviceToHost));
+    if (bm) MCC_HIP(h, hipMemcpy(bm, d_bm, bm_bytes, hipMemcpyDeviceToHost));
+    if (mu) MCC_HIP(h, hipMemcpy(mu, d_mu, mu_bytes, hipMemcpyDeviceToHost));
     return MCR_OK;
 }
 
@@ -384,7 +277,7 @@ int mcb_pooled_dev(void* handle, const void* draws_dev, int dtype, int64_t C, in
     if (const int rc = check_tensor(h->err, draws_dev, dtype, C, N, P, stride_c, stride_n, stride_p)) return rc;
     if (!pooled_dev) return fail(h->err, MCR_EINVAL, "a NULL output pointer");
     if (ld < C * N) return fail(h->err, MCR_EINVAL, "ld = %lld is smaller than C * N = %lld draws", (long long)ld, (long long)(C * N));
-    MCB_HIP(h, hipSetDevice(h->device));
+    MCC_HIP(h, hipSetDevice(h->device));
     return run_one(h, MCB_KERNEL_POOLED, [&] {
         if (dtype == MCR_F64)
             hipLaunchKernelGGL(k_bm_pooled<double>, dim3(flat_grid(C * N * P)), dim3(kThreads), 0, h->stream, (const double*)draws_dev, C,
@@ -402,7 +295,7 @@ int mcb_lrv_finish_dev(void* handle, const double* cb_dev, const double* cb3_dev
     if (!h) return MCR_EINVAL;
     if (const int rc = check_finish(h->err, cb_dev, cb3_dev, P, b, A, A3, r, sigma_dev)) return rc;
     const double f = lrv_factor(b, A), f3 = r == 3 ? lrv_factor(b / 3, A3) : 0.0;
-    MCB_HIP(h, hipSetDevice(h->device));
+    MCC_HIP(h, hipSetDevice(h->device));
     return run_one(h, MCB_KERNEL_FINISH, [&] {
         hipLaunchKernelGGL(k_bm_finish, dim3(flat_grid(P * P)), dim3(kThreads), 0, h->stream, cb_dev, cb3_dev, P * P, f, f3, r, A,
                            sigma_dev);
@@ -430,15 +323,15 @@ int mcb_pool_dev(void* handle, const double* sig_ref_dev, const double* mu_ref_d
         return rc;
     const int64_t PL = (int64_t)idx.size();
     *p_live = PL;
-    clear_ms(h);
+    h->timer.clear();
     if (PL == 0) return MCR_OK;
-    MCB_HIP(h, hipSetDevice(h->device));
-    const size_t half = align_up((size_t)PL * 8);
-    if (const int rc = ensure(h, &h->ws, &h->ws_bytes, 2 * half, "the live parameters")) return rc;
+    MCC_HIP(h, hipSetDevice(h->device));
+    const size_t half = align_up((size_t)PL * 8, 256);
+    if (const int rc = mcc::ensure(h, &h->ws, &h->ws_bytes, 2 * half, "for the live parameters")) return rc;
     int64_t* d_idx = (int64_t*)h->ws;
     double* d_s = (double*)((char*)h->ws + half);
-    MCB_HIP(h, hipMemcpyAsync(d_idx, idx.data(), (size_t)PL * 8, hipMemcpyHostToDevice, h->stream));
-    MCB_HIP(h, hipMemcpyAsync(d_s, s.data(), (size_t)PL * 8, hipMemcpyHostToDevice, h->stream));
+    MCC_HIP(h, hipMemcpyAsync(d_idx, idx.data(), (size_t)PL * 8, hipMemcpyHostToDevice, h->stream));
+    MCC_HIP(h, hipMemcpyAsync(d_s, s.data(), (size_t)PL * 8, hipMemcpyHostToDevice, h->stream));
     return run_one(h, MCB_KERNEL_POOL, [&] {
         hipLaunchKernelGGL(k_bm_pool, dim3(flat_grid(PL * PL)), dim3(kThreads), 0, h->stream, sig_ref_dev, mu_ref_dev, (double)M_ref,
                            sig_act_dev, mu_act_dev, (double)M_act, P, PL, d_idx, d_s, jitter, v_dev, d_dev, z_dev);
@@ -480,22 +373,8 @@ int mcb_tree_sum_host(const double* y, int64_t n, int squares, double* sum)
     return MCR_OK;
 }
 
-int mcb_profile_enable(void* handle, int on)
-{
-    Handle* h = (Handle*)handle;
-    if (!h) return MCR_EINVAL;
-    h->profile = on != 0;
-    clear_ms(h);
-    return MCR_OK;
-}
+int mcb_profile_enable(void* handle, int on) { return mcc::profile_enable((Handle*)handle, on); }
 
-int mcb_kernel_ms(void* handle, double* ms, int cap)
-{
-    Handle* h = (Handle*)handle;
-    if (!h) return MCR_EINVAL;
-    if (!ms || cap < MCB_KERNELS) return fail(h->err, MCR_EINVAL, "mcb_kernel_ms needs room for MCB_KERNELS = %d times", MCB_KERNELS);
-    for (int i = 0; i < MCB_KERNELS; ++i) ms[i] = h->ms[i];
-    return MCR_OK;
-}
+int mcb_kernel_ms(void* handle, double* ms, int cap) { return mcc::kernel_ms((Handle*)handle, "mcb", "MCB", ms, cap); }
 
 }  // extern "C"

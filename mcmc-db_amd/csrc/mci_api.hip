@@ -1,49 +1,21 @@
-// mci_api.hip -- the entries of include/mcmcref_iess.h: the handle (a stream, two cached device allocations that only
-// grow), the chunked call, and the definition on the host.  The library stands alone: nothing of libmcmcref_hip.so's.
+// mci_api.hip -- the entries of include/mcmcref_iess.h: the handle (that of mcc_handle.hpp: a stream, two cached device
+// allocations that only grow), the chunked call, and the definition on the host.  The library stands alone: nothing of
+// libmcmcref_hip.so's.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <vector>
 
+#include "mcc_handle.hpp"
 #include "mci_kernels.hpp"
 
 namespace mci {
 
-struct Handle {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    void* ws = nullptr;                 // one chunk's thresholds, outputs, words and popcounts
-    size_t ws_bytes = 0;
-    void* up = nullptr;                 // the host entry's copy of the tensor
-    size_t up_bytes = 0;
-    size_t limit = (size_t)1 << 30;
-    bool profile = false;
-    double ms[MCI_KERNELS] = {0.0, 0.0};
-    char err[256] = "";
-};
-
-static thread_local char g_init_err[256] = "";
-
-static int fail(char* err, int code, const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(err, 256, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define MCI_HIP(h, call)                                                                                       \
-    do {                                                                                                       \
-        const hipError_t e_ = (call);                                                                          \
-        if (e_ != hipSuccess) return fail((h)->err, MCR_EHIP, "%s: %s", #call, hipGetErrorString(e_));         \
-    } while (0)
-
-static size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
+using Handle = mcc::Handle<MCI_KERNELS>;     // ws: one chunk's thresholds, outputs, words and popcounts
+using mcc::Carve;
+using mcc::fail;
+using mcc::g_err;
 
 // What every entry refuses, in one place; `err` receives the cause.
 static int check_dims(char* err, int dtype, int64_t C, int64_t N, int64_t P, int K)
@@ -74,11 +46,27 @@ struct Plan {
     int64_t chunk = 0;
 };
 
+// The buffers of a chunk of Pc parameters, as they lie in the workspace.
+struct Chunk {
+    double *lo, *hi, *ess; int64_t *trunc, *ones; uint64_t* bits; uint32_t* pre;
+    Chunk(Carve& cv, const Plan& pl, int64_t Pc, int K)
+    {
+        const size_t pk = (size_t)Pc * (size_t)K;
+        lo = cv.take<double>(pk);
+        hi = cv.take<double>(pk);
+        ess = cv.take<double>(pk);
+        trunc = cv.take<int64_t>(pk);
+        ones = cv.take<int64_t>(pk);
+        bits = cv.take<uint64_t>(pk * (size_t)pl.words);
+        pre = pl.lds ? nullptr : cv.take<uint32_t>(pk * (size_t)pl.words);
+    }
+};
+
 static size_t chunk_bytes(const Plan& pl, int64_t Pc, int K)
 {
-    const size_t pk = (size_t)Pc * (size_t)K;
-    return 2 * align_up(pk * 8) + 3 * align_up(pk * 8) + align_up(pk * (size_t)pl.words * 8) +
-           (pl.lds ? 0 : align_up(pk * (size_t)pl.words * 4));
+    Carve m{nullptr};
+    Chunk(m, pl, Pc, K);
+    return mcc::align_up(m.off, 256);                         // what the limit is held against: the last buffer rounded too
 }
 
 static int make_plan(Handle* h, int64_t C, int64_t N, int64_t P, int K, Plan* pl)
@@ -86,14 +74,8 @@ static int make_plan(Handle* h, int64_t C, int64_t N, int64_t P, int K, Plan* pl
     pl->Wp = (N + 63) / 64 + 1;
     pl->words = C * pl->Wp;
     pl->lds = pl->words <= MCI_LDS_WORDS;
-    if (chunk_bytes(*pl, 1, K) > h->limit)
-        return fail(h->err, MCR_ENOMEM, "one parameter needs %zu bytes of workspace, the limit is %zu", chunk_bytes(*pl, 1, K), h->limit);
-    int64_t lo = 1, hi = P;                                   // the most parameters under the limit
-    while (lo < hi) {
-        const int64_t mid = lo + (hi - lo + 1) / 2;
-        if (chunk_bytes(*pl, mid, K) <= h->limit) lo = mid;
-        else hi = mid - 1;
-    }
+    const int64_t lo = mcc::most_that_fit(P, [&](int64_t pc) { return chunk_bytes(*pl, pc, K) <= h->limit; });
+    if (!lo) return fail(h->err, MCR_ENOMEM, "one parameter needs %zu bytes of workspace, the limit is %zu", chunk_bytes(*pl, 1, K), h->limit);
     // no grid of a chunk reaches 2^31: k_pack_* launch at most `words` workgroups per parameter, k_lag K
     const int64_t grid_cap = ((int64_t)INT32_MAX - 1) / (pl->words > K ? pl->words : K);
     if (grid_cap < 1) return fail(h->err, MCR_EINVAL, "%lld chains are too many for one launch", (long long)C);
@@ -121,55 +103,32 @@ static int run_dev(Handle* h, const void* draws_dev, int dtype, int64_t C, int64
 {
     Plan pl;
     if (const int rc = make_plan(h, C, N, P, K, &pl)) return rc;
-    MCI_HIP(h, hipSetDevice(h->device));
-    const size_t need = chunk_bytes(pl, pl.chunk, K);
-    if (need > h->ws_bytes) {
-        if (h->ws) MCI_HIP(h, hipFree(h->ws));
-        h->ws = nullptr;
-        h->ws_bytes = 0;
-        if (hipMalloc(&h->ws, need) != hipSuccess) {
-            h->ws = nullptr;
-            (void)hipGetLastError();
-            return fail(h->err, MCR_ENOMEM, "cannot allocate %zu bytes of device workspace", need);
-        }
-        h->ws_bytes = need;
-    }
-    h->ms[0] = h->ms[1] = 0.0;
+    MCC_HIP(h, hipSetDevice(h->device));
+    if (const int rc = mcc::ensure(h, &h->ws, &h->ws_bytes, chunk_bytes(pl, pl.chunk, K), "of device workspace")) return rc;
+    h->timer.clear();
     const size_t es = dtype == MCR_F64 ? 8 : 4;
     for (int64_t p0 = 0; p0 < P; p0 += pl.chunk) {
         const int64_t Pc = P - p0 < pl.chunk ? P - p0 : pl.chunk;
         const size_t pk = (size_t)Pc * (size_t)K;
-        char* at = (char*)h->ws;
-        double* d_lo = (double*)at;       at += align_up(pk * 8);
-        double* d_hi = (double*)at;       at += align_up(pk * 8);
-        double* d_ess = (double*)at;      at += align_up(pk * 8);
-        int64_t* d_trunc = (int64_t*)at;  at += align_up(pk * 8);
-        int64_t* d_ones = (int64_t*)at;   at += align_up(pk * 8);
-        uint64_t* d_bits = (uint64_t*)at; at += align_up(pk * (size_t)pl.words * 8);
-        uint32_t* d_pre = pl.lds ? nullptr : (uint32_t*)at;
-        MCI_HIP(h, hipMemcpyAsync(d_lo, lower + p0 * K, pk * 8, hipMemcpyHostToDevice, h->stream));
-        MCI_HIP(h, hipMemcpyAsync(d_hi, upper + p0 * K, pk * 8, hipMemcpyHostToDevice, h->stream));
+        Carve cv{(char*)h->ws, h->ws_bytes};
+        const Chunk d(cv, pl, Pc, K);
+        MCC_HIP(h, hipMemcpyAsync(d.lo, lower + p0 * K, pk * 8, hipMemcpyHostToDevice, h->stream));
+        MCC_HIP(h, hipMemcpyAsync(d.hi, upper + p0 * K, pk * 8, hipMemcpyHostToDevice, h->stream));
         const char* x = (const char*)draws_dev + (size_t)p0 * (size_t)sp * es;
-        if (h->profile) MCI_HIP(h, hipEventRecord(h->ev[0], h->stream));
-        if (dtype == MCR_F64) launch_pack(h, pl, (const double*)x, C, N, Pc, sc, sn, sp, d_lo, d_hi, K, d_bits);
-        else launch_pack(h, pl, (const float*)x, C, N, Pc, sc, sn, sp, d_lo, d_hi, K, d_bits);
-        MCI_HIP(h, hipGetLastError());
-        if (h->profile) MCI_HIP(h, hipEventRecord(h->ev[1], h->stream));
-        if (pl.lds) hipLaunchKernelGGL(k_lag<true>, dim3((unsigned)pk), dim3(kThreads), lds_bytes(pl.words), h->stream, d_bits, d_pre, C, N, pl.Wp, d_ess, d_trunc, d_ones);
-        else hipLaunchKernelGGL(k_lag<false>, dim3((unsigned)pk), dim3(kThreads), 0, h->stream, d_bits, d_pre, C, N, pl.Wp, d_ess, d_trunc, d_ones);
-        MCI_HIP(h, hipGetLastError());
-        if (h->profile) MCI_HIP(h, hipEventRecord(h->ev[2], h->stream));
-        if (ess) MCI_HIP(h, hipMemcpyAsync(ess + p0 * K, d_ess, pk * 8, hipMemcpyDeviceToHost, h->stream));
-        if (trunc) MCI_HIP(h, hipMemcpyAsync(trunc + p0 * K, d_trunc, pk * 8, hipMemcpyDeviceToHost, h->stream));
-        if (ones) MCI_HIP(h, hipMemcpyAsync(ones + p0 * K, d_ones, pk * 8, hipMemcpyDeviceToHost, h->stream));
-        MCI_HIP(h, hipStreamSynchronize(h->stream));
-        if (h->profile) {
-            float a = 0.f, b = 0.f;
-            MCI_HIP(h, hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
-            MCI_HIP(h, hipEventElapsedTime(&b, h->ev[1], h->ev[2]));
-            h->ms[MCI_KERNEL_PACK] += a;
-            h->ms[MCI_KERNEL_LAG] += b;
-        }
+        MCC_HIP(h, h->timer.begin(h->stream));
+        if (dtype == MCR_F64) launch_pack(h, pl, (const double*)x, C, N, Pc, sc, sn, sp, d.lo, d.hi, K, d.bits);
+        else launch_pack(h, pl, (const float*)x, C, N, Pc, sc, sn, sp, d.lo, d.hi, K, d.bits);
+        MCC_HIP(h, hipGetLastError());
+        MCC_HIP(h, h->timer.mark(h->stream, MCI_KERNEL_PACK));
+        if (pl.lds) hipLaunchKernelGGL(k_lag<true>, dim3((unsigned)pk), dim3(kThreads), lds_bytes(pl.words), h->stream, d.bits, d.pre, C, N, pl.Wp, d.ess, d.trunc, d.ones);
+        else hipLaunchKernelGGL(k_lag<false>, dim3((unsigned)pk), dim3(kThreads), 0, h->stream, d.bits, d.pre, C, N, pl.Wp, d.ess, d.trunc, d.ones);
+        MCC_HIP(h, hipGetLastError());
+        MCC_HIP(h, h->timer.mark(h->stream, MCI_KERNEL_LAG));
+        if (ess) MCC_HIP(h, hipMemcpyAsync(ess + p0 * K, d.ess, pk * 8, hipMemcpyDeviceToHost, h->stream));
+        if (trunc) MCC_HIP(h, hipMemcpyAsync(trunc + p0 * K, d.trunc, pk * 8, hipMemcpyDeviceToHost, h->stream));
+        if (ones) MCC_HIP(h, hipMemcpyAsync(ones + p0 * K, d.ones, pk * 8, hipMemcpyDeviceToHost, h->stream));
+        MCC_HIP(h, hipStreamSynchronize(h->stream));
+        MCC_HIP(h, h->timer.collect());
     }
     return MCR_OK;
 }
@@ -245,54 +204,16 @@ int mci_version(void) { return MCI_VERSION; }
 
 int mci_init(int device, void** handle)
 {
-    if (!handle) return fail(g_init_err, MCR_EINVAL, "mci_init: NULL handle pointer");
-    *handle = nullptr;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
-        (void)hipGetLastError();
-        return fail(g_init_err, MCR_ENODEVICE, "no HIP device is usable");
-    }
-    if (device < 0 || device >= count) return fail(g_init_err, MCR_ENODEVICE, "device %d: %d device(s) are visible", device, count);
-    Handle* h = new Handle;
-    h->device = device;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipEventCreate(&h->ev[i]);
-    if (e == hipSuccess)                                        // beyond the 64 KiB a launch may ask for by default
-        e = hipFuncSetAttribute((const void*)k_lag<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(MCI_LDS_WORDS));
-    if (e != hipSuccess) {
-        fail(g_init_err, MCR_EHIP, "mci_init: %s", hipGetErrorString(e));
-        mci_free(h);
-        return MCR_EHIP;
-    }
-    *handle = h;
-    return MCR_OK;
+    return mcc::open<Handle>(device, handle, "mci_init", [] {      // beyond the 64 KiB a launch may ask for by default
+        return hipFuncSetAttribute((const void*)k_lag<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(MCI_LDS_WORDS));
+    });
 }
 
-void mci_free(void* handle)
-{
-    Handle* h = (Handle*)handle;
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->ws) (void)hipFree(h->ws);
-    if (h->up) (void)hipFree(h->up);
-    for (hipEvent_t e : h->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
+void mci_free(void* handle) { mcc::close((Handle*)handle); }
 
-const char* mci_last_error(void* handle) { return handle ? ((Handle*)handle)->err : g_init_err; }
+const char* mci_last_error(void* handle) { return mcc::last_error((Handle*)handle); }
 
-int mci_set_workspace_limit(void* handle, size_t bytes)
-{
-    Handle* h = (Handle*)handle;
-    if (!h) return MCR_EINVAL;
-    if (bytes == 0) return fail(h->err, MCR_EINVAL, "a workspace limit of 0 bytes");
-    h->limit = bytes;
-    return MCR_OK;
-}
+int mci_set_workspace_limit(void* handle, size_t bytes) { return mcc::set_workspace_limit((Handle*)handle, bytes); }
 
 int mci_indicator_plan(void* handle, int dtype, int64_t C, int64_t N, int64_t P, int K, int64_t* params_per_chunk)
 {
@@ -323,28 +244,14 @@ int mci_indicator_ess(void* handle, const void* draws, int dtype, int64_t C, int
     Handle* h = (Handle*)handle;
     if (!h) return MCR_EINVAL;
     if (const int rc = check_call(h->err, draws, dtype, C, N, P, stride_c, stride_n, stride_p, lower, upper, K)) return rc;
-    const size_t es = dtype == MCR_F64 ? 8 : 4;
-    const size_t span = ((size_t)(C - 1) * (size_t)stride_c + (size_t)(N - 1) * (size_t)stride_n + (size_t)(P - 1) * (size_t)stride_p + 1) * es;
-    MCI_HIP(h, hipSetDevice(h->device));
-    if (span > h->up_bytes) {
-        if (h->up) MCI_HIP(h, hipFree(h->up));
-        h->up = nullptr;
-        h->up_bytes = 0;
-        if (hipMalloc(&h->up, span) != hipSuccess) {
-            h->up = nullptr;
-            (void)hipGetLastError();
-            return fail(h->err, MCR_ENOMEM, "cannot allocate %zu bytes for the tensor", span);
-        }
-        h->up_bytes = span;
-    }
-    MCI_HIP(h, hipMemcpy(h->up, draws, span, hipMemcpyHostToDevice));      // (complete on return: the kernels may start)
+    if (const int rc = mcc::upload_span(h, draws, dtype, C, N, P, stride_c, stride_n, stride_p)) return rc;
     return run_dev(h, h->up, dtype, C, N, P, stride_c, stride_n, stride_p, lower, upper, K, ess, trunc, ones);
 }
 
 int mci_indicator_ess_host(const double* chains, int64_t C, int64_t N, const double* lower, const double* upper, int K,
                            double* ess, int64_t* trunc, int64_t* ones)
 {
-    if (const int rc = check_call(g_init_err, chains, MCR_F64, C, N, 1, N, 1, 0, lower, upper, K)) return rc;
+    if (const int rc = check_call(g_err, chains, MCR_F64, C, N, 1, N, 1, 0, lower, upper, K)) return rc;
     const int64_t Wp = (N + 63) / 64 + 1;
     std::vector<uint64_t> B((size_t)(C * Wp));
     for (int k = 0; k < K; ++k) {
@@ -359,22 +266,8 @@ int mci_indicator_ess_host(const double* chains, int64_t C, int64_t N, const dou
     return MCR_OK;
 }
 
-int mci_profile_enable(void* handle, int on)
-{
-    Handle* h = (Handle*)handle;
-    if (!h) return MCR_EINVAL;
-    h->profile = on != 0;
-    h->ms[0] = h->ms[1] = 0.0;
-    return MCR_OK;
-}
+int mci_profile_enable(void* handle, int on) { return mcc::profile_enable((Handle*)handle, on); }
 
-int mci_kernel_ms(void* handle, double* ms, int cap)
-{
-    Handle* h = (Handle*)handle;
-    if (!h) return MCR_EINVAL;
-    if (!ms || cap < MCI_KERNELS) return fail(h->err, MCR_EINVAL, "mci_kernel_ms needs room for MCI_KERNELS = %d times", MCI_KERNELS);
-    for (int i = 0; i < MCI_KERNELS; ++i) ms[i] = h->ms[i];
-    return MCR_OK;
-}
+int mci_kernel_ms(void* handle, double* ms, int cap) { return mcc::kernel_ms((Handle*)handle, "mci", "MCI", ms, cap); }
 
 }  // extern "C"

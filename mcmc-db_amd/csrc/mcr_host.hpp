@@ -1,5 +1,5 @@
 // mcr_host.hpp -- what the translation units of libmcmcref_hip.so share: the context, its buffers and the tools of a call
-// (fail, HIP_TRY, LAUNCH, the profiling events, the workspace carving).  With mcr_pipe.hpp -- how mcr_stats.hip runs the
+// (fail, HIP_TRY, LAUNCH, the profiling events, the workspace carving: Carve, align_up and most_that_fit of mcr_carve.hpp).  With mcr_pipe.hpp -- how mcr_stats.hip runs the
 // pipeline of mcr_api.hip -- this is the complete list of what mcr_api.hip (context, summary pipeline), mcr_stats.hip (the
 // other statistics), mcr_files.hip (file and text ingest, writers) and mcr_comm.hip (RCCL) may use of each other; everything
 // else lives in its unit's anonymous namespace.  Internal: not installed, and it includes no kernel header.
@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "mcr_carve.hpp"
 #include "mcr_device.hpp"
 
 namespace mcr {
@@ -295,35 +296,6 @@ template <bool kPinned> int Buf<kPinned>::reserve(mcr_ctx* ctx, size_t bytes)
     }
     cap = want;
     return MCR_OK;
-}
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-// Cuts a workspace into 256-byte aligned buffers.  A Carve with a null base only measures: off ends as the byte count.
-// Over a real workspace of `end` bytes a take past the end hands out nullptr, and the caller fails on over().
-struct Carve {
-    char* base; size_t end = SIZE_MAX; size_t off = 0;
-    template <typename T> T* take(size_t n)
-    {
-        off = align_up(off, 256);
-        T* p = base && off + n * sizeof(T) <= end ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += n * sizeof(T);
-        return p;
-    }
-    bool over() const { return off > end; }
-};
-
-// The chunk size of a call under the workspace limit: the largest k in [1, hi] that fits, 0 when not even 1 does.  fits
-// is monotone (k fits: so does every smaller count) and is asked about hi first -- a call that fits whole costs one
-// measurement.
-template <class Fits> i64 most_that_fit(i64 hi, Fits&& fits)
-{
-    if (hi < 1) return 0;
-    if (fits(hi)) return hi;
-    if (!fits(1)) return 0;
-    i64 lo = 1;                                              // lo fits, hi does not
-    while (hi - lo > 1) { const i64 mid = lo + (hi - lo) / 2; if (fits(mid)) lo = mid; else hi = mid; }
-    return lo;
 }
 
 // Measures a layout (a callable on a Carve&), makes the buffer that large, then carves it.

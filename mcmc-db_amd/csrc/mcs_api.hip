@@ -4,12 +4,12 @@
 // time order -- through mcr_pipe.hpp, as mcr_stats.hip does, then the kernels of mcs_kernels.hpp.
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <numeric>
 #include <vector>
 
+#include "mcc_handle.hpp"
 #include "mcs_kernels.hpp"
 
 using namespace mcr;
@@ -17,27 +17,15 @@ using namespace mcr::host;
 
 namespace mcs {
 
-struct Handle {
+// limit (the context's default at first), the phase timer and the error text are the companions' common part; mcc::fail
+// writes that text (a bare fail is the context's here).
+struct Handle : mcc::Common<MCS_KERNELS> {
     mcr_ctx* ctx = nullptr;
     mcr::host::DevBuf blom;             // the Blom table of blom_S kept draws
     i64 blom_S = -1;
-    size_t limit = 0;                   // workspace of one chunk (mcs_set_workspace_limit); the context's default at first
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    bool profile = false;
-    double ms[MCS_KERNELS] = {0.0, 0.0, 0.0};
-    char err[512] = "";
 };
 
-static thread_local char g_err[512] = "";
-
-static int refuse(char* err, int code, const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(err, 512, fmt, ap);
-    va_end(ap);
-    return code;
-}
+using mcc::g_err;
 
 // A failure of the context's: its message becomes the handle's.
 static int from_ctx(Handle* h, int rc)
@@ -82,13 +70,13 @@ static void scatter(const Outs& o, i64 p, const double* r, int nser)
 // What every entry refuses, in one place; `err` receives the cause.
 static int check_call(char* err, const void* draws, int dtype, i64 C, i64 N, i64 P, i64 sc, i64 sn, i64 sp, int flags)
 {
-    if (!draws) return refuse(err, MCR_EINVAL, "a NULL tensor pointer");
-    if (dtype != MCR_F64 && dtype != MCR_F32) return refuse(err, MCR_EINVAL, "dtype %d is neither MCR_F64 nor MCR_F32", dtype);
-    if (C < 1 || P < 1 || N < 2) return refuse(err, MCR_EINVAL, "C and P must be >= 1 and N >= 2 (a split chain has N / 2 draws)");
-    if (N > MCS_MAX_DRAWS) return refuse(err, MCR_EINVAL, "N = %lld exceeds MCS_MAX_DRAWS = %d draws per chain", (long long)N, MCS_MAX_DRAWS);
-    if (C >= INT32_MAX || C * N >= (i64)INT32_MAX) return refuse(err, MCR_EINVAL, "C * N must be below 2^31 - 1");
-    if (sc < 0 || sn < 0 || sp < 0) return refuse(err, MCR_EINVAL, "negative strides are not supported");
-    if (flags & ~MCS_WANT_BASIC) return refuse(err, MCR_EINVAL, "flags = %d: only MCS_WANT_BASIC is defined", flags);
+    if (!draws) return mcc::fail(err, MCR_EINVAL, "a NULL tensor pointer");
+    if (dtype != MCR_F64 && dtype != MCR_F32) return mcc::fail(err, MCR_EINVAL, "dtype %d is neither MCR_F64 nor MCR_F32", dtype);
+    if (C < 1 || P < 1 || N < 2) return mcc::fail(err, MCR_EINVAL, "C and P must be >= 1 and N >= 2 (a split chain has N / 2 draws)");
+    if (N > MCS_MAX_DRAWS) return mcc::fail(err, MCR_EINVAL, "N = %lld exceeds MCS_MAX_DRAWS = %d draws per chain", (long long)N, MCS_MAX_DRAWS);
+    if (C >= INT32_MAX || C * N >= (i64)INT32_MAX) return mcc::fail(err, MCR_EINVAL, "C * N must be below 2^31 - 1");
+    if (sc < 0 || sn < 0 || sp < 0) return mcc::fail(err, MCR_EINVAL, "negative strides are not supported");
+    if (flags & ~MCS_WANT_BASIC) return mcc::fail(err, MCR_EINVAL, "flags = %d: only MCS_WANT_BASIC is defined", flags);
     return MCR_OK;
 }
 
@@ -135,7 +123,7 @@ static int plan(Handle* h, Chunk& ch, i64& pcmax)
     const i64 cap = std::min<i64>(grid_cap, kMaxGridY / 2);
     auto measure = [&](i64 pc) { Carve mcv{nullptr}; ch(mcv, pc); return mcv.off; };
     pcmax = most_that_fit(std::min(ch.c.P, cap), [&](i64 pc) { return measure(pc) <= h->limit; });
-    if (!pcmax) return refuse(h->err, MCR_ENOMEM, "one parameter needs %zu bytes of workspace; the limit is %zu", measure(1), h->limit);
+    if (!pcmax) return mcc::fail(h->err, MCR_ENOMEM, "one parameter needs %zu bytes of workspace; the limit is %zu", measure(1), h->limit);
     return MCR_OK;
 }
 
@@ -179,7 +167,7 @@ static int run_ctx(Handle* h, const Call& c, const Outs& o)
         double* copy = nullptr;
         rc = carve(ctx, lane_ws(ctx), [&](Carve& cv) { copy = ch(cv, pc); });
         if (rc) return rc;
-        if (h->profile) HIP_TRY(ctx, hipEventRecord(h->ev[0], ctx->stream));
+        HIP_TRY(ctx, h->timer.begin(ctx->stream));
         const double* X = copy;
         if (c.in_place()) X = reinterpret_cast<const double*>(c.draws) + p0 * S;
         else if ((c.N & 1) == 0) rc = launch_ingest(ctx, c.draws, c.dtype, copy, c.C, c.N, pc, c.sc, c.sn, c.sp, p0);
@@ -199,24 +187,20 @@ static int run_ctx(Handle* h, const Call& c, const Outs& o)
         a.d_res = d_res + (size_t)kPipeFields * (size_t)p0;
         rc = run_pipeline(ctx, a);                          // one chain: sort, quantiles, bulk codes, fold, finalize (the bad count)
         if (rc) return rc;
-        if (h->profile) HIP_TRY(ctx, hipEventRecord(h->ev[1], ctx->stream));
+        HIP_TRY(ctx, h->timer.mark(ctx->stream, MCS_KERNEL_PIPE));
         const SeriesIn si{X, a.zb, a.zt, blom, a.d_res, m, n, pc, c.nser};
         hipLaunchKernelGGL(k_mcs_series, dim3((unsigned)((pc * m + kWaves - 1) / kWaves)), dim3(kThreads), 0, ctx->stream, si, ch.D, ch.mom);
         MCS_LAUNCHED(ctx, "k_mcs_series");
-        if (h->profile) HIP_TRY(ctx, hipEventRecord(h->ev[2], ctx->stream));
+        HIP_TRY(ctx, h->timer.mark(ctx->stream, MCS_KERNEL_SERIES));
         double* out_at = d_out + (size_t)p0 * c.nser * kOutRec;
         const dim3 wgrid((unsigned)pc, (unsigned)c.nser);
         if (lds) hipLaunchKernelGGL(k_mcs_walk<true>, wgrid, dim3(kThreads), (size_t)n * 8, ctx->stream, (const double*)ch.D, (const double*)ch.mom, m, n, c.nser, out_at);
         else hipLaunchKernelGGL(k_mcs_walk<false>, wgrid, dim3(kThreads), 0, ctx->stream, (const double*)ch.D, (const double*)ch.mom, m, n, c.nser, out_at);
         MCS_LAUNCHED(ctx, "k_mcs_walk");
-        if (h->profile) {
-            HIP_TRY(ctx, hipEventRecord(h->ev[3], ctx->stream));
+        HIP_TRY(ctx, h->timer.mark(ctx->stream, MCS_KERNEL_WALK));
+        if (h->timer.on) {
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            for (int k = 0; k < MCS_KERNELS; ++k) {
-                float t = 0.f;
-                HIP_TRY(ctx, hipEventElapsedTime(&t, h->ev[k], h->ev[k + 1]));
-                h->ms[k] += t;
-            }
+            HIP_TRY(ctx, h->timer.collect());
         }
     }
     const size_t bytes = sizeof(double) * (res_n + out_n);
@@ -241,8 +225,8 @@ static int run_ctx(Handle* h, const Call& c, const Outs& o)
 static int run_dev(Handle* h, Call c, const Outs& o, bool host)
 {
     mcr_ctx* ctx = h->ctx;
-    for (double& v : h->ms) v = 0.0;
-    if (hipSetDevice(ctx->device) != hipSuccess) return refuse(h->err, MCR_EHIP, "hipSetDevice(%d) failed", ctx->device);
+    h->timer.clear();
+    if (hipSetDevice(ctx->device) != hipSuccess) return mcc::fail(h->err, MCR_EHIP, "hipSetDevice(%d) failed", ctx->device);
     int rc = MCR_OK;
     if (host) {                                             // the span the strides reach, into the context's staging buffer
         const size_t bytes = (size_t)tensor_extent(c.C, c.N, c.P, c.sc, c.sn, c.sp) * (c.dtype == MCR_F64 ? 8 : 4);
@@ -363,7 +347,7 @@ static int host_param(const double* chains, i64 C, i64 N, int flags, const Outs&
     for (i64 k = 0; k < m; ++k)
         for (i64 i = 0; i < n; ++i) x[(size_t)(k * n + i)] = chains[(k >> 1) * N + (k & 1) * (N - n) + i];
     for (double v : x)
-        if (!std::isfinite(v)) return refuse(g_err, MCR_ENONFINITE, "draws contain non-finite value(s)");
+        if (!std::isfinite(v)) return mcc::fail(g_err, MCR_ENONFINITE, "draws contain non-finite value(s)");
     std::vector<double> sorted, series((size_t)S), unused, fold((size_t)S);
     std::vector<double> out((size_t)(nser * kOutRec));
     host_scores(x, sorted, series);
@@ -411,15 +395,14 @@ MCS_EXPORT void mcs_free(void* handle)
         (void)sync_all(h->ctx);
     }
     h->blom.release();
-    for (hipEvent_t e : h->ev)
-        if (e) (void)hipEventDestroy(e);
+    h->timer.destroy();
     if (h->ctx) mcr_free(h->ctx);
     delete h;
 }
 
 MCS_EXPORT int mcs_init(int device, void** handle)
 {
-    if (!handle) return refuse(g_err, MCR_EINVAL, "mcs_init: NULL handle pointer");
+    if (!handle) return mcc::fail(g_err, MCR_EINVAL, "mcs_init: NULL handle pointer");
     *handle = nullptr;
     Handle* h = new Handle;
     const int rc = mcr_init(device, &h->ctx);
@@ -429,10 +412,9 @@ MCS_EXPORT int mcs_init(int device, void** handle)
         delete h;
         return rc;
     }
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipEventCreate(&h->ev[i]);
+    const hipError_t e = h->timer.create();
     if (e != hipSuccess) {
-        refuse(g_err, MCR_EHIP, "mcs_init: %s", hipGetErrorString(e));
+        mcc::fail(g_err, MCR_EHIP, "mcs_init: %s", hipGetErrorString(e));
         mcs_free(h);
         return MCR_EHIP;
     }
@@ -441,23 +423,16 @@ MCS_EXPORT int mcs_init(int device, void** handle)
     return MCR_OK;
 }
 
-MCS_EXPORT const char* mcs_last_error(void* handle) { return handle ? ((Handle*)handle)->err : g_err; }
+MCS_EXPORT const char* mcs_last_error(void* handle) { return mcc::last_error((Handle*)handle); }
 
-MCS_EXPORT int mcs_set_workspace_limit(void* handle, size_t bytes)
-{
-    Handle* h = (Handle*)handle;
-    if (!h) return MCR_EINVAL;
-    if (bytes == 0) return refuse(h->err, MCR_EINVAL, "a workspace limit of 0 bytes");
-    h->limit = bytes;
-    return MCR_OK;
-}
+MCS_EXPORT int mcs_set_workspace_limit(void* handle, size_t bytes) { return mcc::set_workspace_limit((Handle*)handle, bytes); }
 
 MCS_EXPORT int mcs_plan(void* handle, int dtype, int64_t C, int64_t N, int64_t P, int64_t stride_c, int64_t stride_n,
                         int64_t stride_p, int flags, int64_t* params_per_chunk)
 {
     Handle* h = (Handle*)handle;
     if (!h) return MCR_EINVAL;
-    if (!params_per_chunk) return refuse(h->err, MCR_EINVAL, "a NULL result pointer");
+    if (!params_per_chunk) return mcc::fail(h->err, MCR_EINVAL, "a NULL result pointer");
     if (const int rc = check_call(h->err, h, dtype, C, N, P, stride_c, stride_n, stride_p, flags)) return rc;
     const Call c{nullptr, dtype, C, N, P, stride_c, stride_n, stride_p, (flags & MCS_WANT_BASIC) ? kSeries : kSeries - 1};
     Chunk ch{c};
@@ -493,22 +468,8 @@ MCS_EXPORT int mcs_diagnostics_host(const double* chains, int64_t C, int64_t N, 
     return host_param(chains, C, N, flags, MCS_OUTS);
 }
 
-MCS_EXPORT int mcs_profile_enable(void* handle, int on)
-{
-    Handle* h = (Handle*)handle;
-    if (!h) return MCR_EINVAL;
-    h->profile = on != 0;
-    for (double& v : h->ms) v = 0.0;
-    return MCR_OK;
-}
+MCS_EXPORT int mcs_profile_enable(void* handle, int on) { return mcc::profile_enable((Handle*)handle, on); }
 
-MCS_EXPORT int mcs_kernel_ms(void* handle, double* ms, int cap)
-{
-    Handle* h = (Handle*)handle;
-    if (!h) return MCR_EINVAL;
-    if (!ms || cap < MCS_KERNELS) return refuse(h->err, MCR_EINVAL, "mcs_kernel_ms needs room for MCS_KERNELS = %d times", MCS_KERNELS);
-    for (int i = 0; i < MCS_KERNELS; ++i) ms[i] = h->ms[i];
-    return MCR_OK;
-}
+MCS_EXPORT int mcs_kernel_ms(void* handle, double* ms, int cap) { return mcc::kernel_ms((Handle*)handle, "mcs", "MCS", ms, cap); }
 
 }  // extern "C"

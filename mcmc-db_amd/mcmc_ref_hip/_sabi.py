@@ -1,16 +1,15 @@
 """The Python mirror of include/mcmcref_std.h, the ABI of the companion library libmcmcref_std.so (`mcs_*` entries,
 `MCS_*` constants): R-hat and ESS in the Stan convention -- split chains, Blom scores, Geyer's initial sequences.  The
 library is a further shared object next to libmcmcref_hip.so -- it carries its own copy of the main library's sort stage
-and summary pipeline -- and is loaded lazily, by the first call that needs it, after the main one.  Imports `_abi` only
-(return codes, the error types, pointer helpers); `_ffi` imports neither this module nor `standard`.
+and summary pipeline -- and is loaded lazily, by the first call that needs it, after the main one (`_companion`: the loader
+and the handle).  Imports `_abi` and `_companion` only; `_ffi` imports neither this module nor `standard`.
 """
 from __future__ import annotations
 
 import ctypes as C
-import os
-import threading
 
-from ._abi import DEFAULT_LIB, MCR_ENODEVICE, MCR_OK, HipUnavailableError, McrError, _I64, _dp, _ip, load_library
+from ._abi import _I64, _dp, _ip
+from ._companion import Companion
 
 MCS_VERSION = 100
 MCS_MAX_DRAWS = 1048576
@@ -42,65 +41,8 @@ SSYMBOLS = {
     "mcs_kernel_ms": (C.c_int, [_vp, _dp, C.c_int]),
 }
 
-DEFAULT_STD_LIB = DEFAULT_LIB.with_name("libmcmcref_std.so")
-
-_lib = None
-_lib_lock = threading.Lock()
-
-
-def load_std_library():
-    """dlopen libmcmcref_std.so, after the main library, and bind every entry its header declares (works without a GPU)."""
-    global _lib
-    with _lib_lock:
-        if _lib is None:
-            load_library()
-            path = type(DEFAULT_STD_LIB)(os.environ.get("MCMC_REF_HIP_STD_LIB", str(DEFAULT_STD_LIB)))
-            if not path.exists():
-                raise HipUnavailableError(f"{path} not found: build it with `python mcmc-db_amd/build.py` "
-                                          "(there is no CPU fallback)")
-            try:
-                L = C.CDLL(str(path))
-            except OSError as exc:
-                raise HipUnavailableError(f"cannot load {path}: {exc}") from exc
-            for name, (res, args) in SSYMBOLS.items():
-                fn = getattr(L, name)
-                fn.restype = res
-                fn.argtypes = args
-            _lib = L
-    return _lib
-
-
-class StdHandle:
-    """An mcs handle on one device: the owner of the companion library's context there."""
-
-    def __init__(self, device: int = 0):
-        self.lib = load_std_library()
-        h = _vp()
-        rc = self.lib.mcs_init(int(device), C.byref(h))
-        if rc != MCR_OK:
-            msg = (self.lib.mcs_last_error(None) or b"").decode()
-            if rc == MCR_ENODEVICE:
-                raise HipUnavailableError(msg)
-            raise McrError(rc, msg)
-        self.handle, self.device = h, int(device)
-
-    def check(self, rc: int):
-        if rc != MCR_OK:
-            raise McrError(rc, (self.lib.mcs_last_error(self.handle) or b"").decode())
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.mcs_free(self.handle)
-            self.handle = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):  # pragma: no cover - best effort
-        try:
-            self.close()
-        except Exception:
-            pass
+STD = Companion("mcs_", "libmcmcref_std.so", "MCMC_REF_HIP_STD_LIB", SSYMBOLS, "StdHandle",
+                "An mcs handle on one device: the owner of the companion library's context there.", main_first=True)
+DEFAULT_STD_LIB = STD.default_path
+load_std_library = STD.load
+StdHandle = STD.Handle

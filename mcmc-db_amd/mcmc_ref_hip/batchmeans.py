@@ -21,29 +21,17 @@ import contextlib
 import ctypes as C
 import math
 import time
-import weakref
 
 import numpy as np
 
 from . import _ffi
 from ._abi import _as_dp, tensor_args
-from ._babi import KERNEL_NAMES, MCB_KERNELS, BmHandle, host_check, load_bm_library
+from ._babi import BM, KERNEL_NAMES, host_check, load_bm_library
+from ._companion import device_tensor
 from ._device import DeviceBuffer, DeviceTensor
 from ._hostdefs import chi2_sf
 
-_handles: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()      # Context -> BmHandle
-
-
-def _ctx(context):
-    return context or _ffi.default_context()
-
-
-def _handle(ctx) -> BmHandle:
-    h = _handles.get(ctx)
-    if h is None or h.handle is None:
-        h = _handles[ctx] = BmHandle(ctx.device)
-        weakref.finalize(ctx, h.close)
-    return h
+_handle = BM.handle                     # Context -> its BmHandle
 
 
 def batch_size(N: int, r: int = 3) -> tuple[int, int]:
@@ -149,10 +137,9 @@ class _Dev:
         return self.stack.enter_context(DeviceBuffer(self.ctx, max(8 * int(count), 8)))
 
     def tensor(self, draws, layout):
-        if isinstance(draws, DeviceTensor):
-            if draws.chain_off is not None:
-                raise ValueError("chains of different lengths are not supported")
-            return draws, draws.targs
+        t = device_tensor(draws)
+        if t is not None:
+            return t, t.targs
         t = self.stack.enter_context(self.ctx.upload(np.ascontiguousarray(draws), layout))
         return t, t.targs
 
@@ -338,7 +325,7 @@ def batch_means(draws, layout: str = "pcn", batch=None, r: int = 3, context=None
     context): bm [P][A] (A = C a batch means, chain by chain), mu [P] (the mean of the draws the batches cover), b and a.
     `batch` is the batch size (None: `batch_size(N, r)`); the batches cover the last a b draws of each chain.  One
     streaming pass -- mcb_batch_means(_dev).  Calls `context.sync()` first.  The same bits in any layout and chunking."""
-    ctx = _ctx(context)
+    ctx = context or _ffi.default_context()
     h = _handle(ctx)
     ctx.sync()
     if isinstance(draws, DeviceTensor):
@@ -363,7 +350,7 @@ def long_run_covariance(draws, layout: str = "pcn", batch=None, r: int = 3, cont
     lugsail for r = 3), mu [P], mcse_mean [P] = sqrt(sigma_pp / (A b)), ess_bm [P] = C N lambda_pp / sigma_pp, lambda
     [P][P] (the sample covariance of the pooled draws), b, a and info (0, or 1 + the first parameter at which sigma is not
     positive definite; with fewer than two batches sigma is NaN)."""
-    ctx = _ctx(context)
+    ctx = context or _ffi.default_context()
     ctx.sync()
     with contextlib.ExitStack() as stack:
         return _long_run_covariance(_Dev(ctx, stack), draws, layout, batch, r)
@@ -373,7 +360,7 @@ def multi_ess(draws, layout: str = "pcn", batch=None, r: int = 3, scale=None, co
     """The multivariate effective sample size mESS = C N exp((logdet Lambda - logdet Sigma) / P_live) of the live parameters
     (scale [P] > 0; None: all), with p_live, info_sigma / info_lambda (a singular or, after lugsail, indefinite matrix
     gives mess = NaN), the two logdets, and per parameter mu, ess_bm and mcse_mean."""
-    ctx = _ctx(context)
+    ctx = context or _ffi.default_context()
     ctx.sync()
     with contextlib.ExitStack() as stack:
         return _multi_ess(_Dev(ctx, stack), draws, layout, batch, r, scale)
@@ -388,7 +375,7 @@ def mean_shift_test(ref, act, scale=None, jitter: float = 0.0, r: int = 3, conte
     (= L^-1 d: entry i is parameter i's shift given the ones before it), info (0, or 1 + the live index at which V is
     singular or indefinite: then T, p_value and shift are NaN), mess_ref / mess_act (`multi_ess` of each; NaN with
     mess=False) and the batch geometry b_ref, a_ref, b_act, a_act.  `stages` (a dict) receives the wall time of each step."""
-    ctx = _ctx(context)
+    ctx = context or _ffi.default_context()
     ctx.sync()
     with contextlib.ExitStack() as stack:
         return _mean_shift_test(_Dev(ctx, stack, stages), ref, act, layout, scale, jitter, r, batch_ref, batch_act, mess)
@@ -396,19 +383,14 @@ def mean_shift_test(ref, act, scale=None, jitter: float = 0.0, r: int = 3, conte
 
 def set_workspace_limit(nbytes: int, context=None) -> None:
     """The most device workspace one chunk of parameters of a batch-means call may take (mcb_set_workspace_limit)."""
-    h = _handle(_ctx(context))
-    h.check(h.lib.mcb_set_workspace_limit(h.handle, int(nbytes)))
+    BM.set_workspace_limit(context or _ffi.default_context(), nbytes)
 
 
 def profile(on: bool, context=None) -> None:
     """Time the kernels of every later mcb call with HIP events (mcb_profile_enable)."""
-    h = _handle(_ctx(context))
-    h.check(h.lib.mcb_profile_enable(h.handle, int(bool(on))))
+    BM.profile(context or _ffi.default_context(), on)
 
 
 def kernel_ms(context=None) -> dict:
     """The last mcb call's kernel times in milliseconds by kernel name (mcb_kernel_ms); 0 for a kernel that did not run."""
-    h = _handle(_ctx(context))
-    ms = np.zeros(MCB_KERNELS)
-    h.check(h.lib.mcb_kernel_ms(h.handle, _as_dp(ms), MCB_KERNELS))
-    return dict(zip(KERNEL_NAMES, (float(v) for v in ms)))
+    return BM.kernel_ms(context or _ffi.default_context(), KERNEL_NAMES)

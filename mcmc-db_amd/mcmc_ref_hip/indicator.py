@@ -15,29 +15,15 @@ definition on the host and need neither.
 """
 from __future__ import annotations
 
-import ctypes as C
-import weakref
-
 import numpy as np
 
 from . import _ffi
-from ._abi import MCR_OK, McrError, _as_dp, _as_ip, _dtype_code, tensor_args
+from ._abi import _as_dp, _as_ip, _dtype_code, tensor_args
+from ._companion import tensor_entry
 from ._device import DeviceTensor
-from ._iabi import KERNEL_NAMES, MCI_KERNELS, MCI_MAX_REQUESTS, IessHandle, load_iess_library
+from ._iabi import IESS, KERNEL_NAMES, MCI_MAX_REQUESTS
 
-_handles: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()      # Context -> IessHandle
-
-
-def _ctx(context):
-    return context or _ffi.default_context()
-
-
-def _handle(ctx) -> IessHandle:
-    h = _handles.get(ctx)
-    if h is None or h.handle is None:
-        h = _handles[ctx] = IessHandle(ctx.device)
-        weakref.finalize(ctx, h.close)
-    return h
+_handle = IESS.handle                   # Context -> its IessHandle
 
 
 def _requests(lower, upper, P: int) -> tuple[np.ndarray, np.ndarray, int]:
@@ -57,16 +43,6 @@ def _outputs(P: int, K: int):
     return np.full((P, K), np.nan), np.zeros((P, K), dtype=np.int64), np.zeros((P, K), dtype=np.int64)
 
 
-def _tensor(draws, layout: str):
-    """(the entry's name, pointer, tensor arguments) of a numpy array or a DeviceTensor."""
-    if isinstance(draws, DeviceTensor):
-        if draws.chain_off is not None:
-            raise ValueError("chains of different lengths are not supported")
-        return "mci_indicator_ess_dev", draws.buf.ptr, draws.targs
-    draws = np.asarray(draws)
-    return "mci_indicator_ess", draws.ctypes.data_as(C.c_void_p), tensor_args(draws, layout)
-
-
 def indicator_ess(draws, lower, upper, layout: str = "pcn", context=None) -> dict:
     """ESS of the indicator lower < x <= upper for every parameter of `draws` (a 3-D numpy array whose axes are `layout`, or
     a DeviceTensor of the context) and every request: `lower` / `upper` are scalars, [K] or [P][K], K <= 32; -inf / +inf
@@ -74,8 +50,8 @@ def indicator_ess(draws, lower, upper, layout: str = "pcn", context=None) -> dic
     fewer than 2 draws; C N for a constant indicator), trunc [P][K] (the first lag with a negative autocovariance, N when
     there is none, 0 for a constant indicator, -1 for N < 2) and ones [P][K] (the pooled count) -- mci_indicator_ess(_dev).
     Calls `context.sync()` first.  A parameter's numbers have the same bits alone, in any batch, layout and chunking."""
-    ctx = _ctx(context)
-    entry, ptr, targs = _tensor(draws, layout)
+    ctx = context or _ffi.default_context()
+    entry, ptr, targs = tensor_entry(draws, layout, "mci_indicator_ess")
     lo, hi, K = _requests(lower, upper, targs[3])
     ess, trunc, ones = _outputs(targs[3], K)
     ctx.sync()
@@ -87,7 +63,7 @@ def indicator_ess(draws, lower, upper, layout: str = "pcn", context=None) -> dic
 def indicator_ess_host(draws, lower, upper, layout: str = "pcn") -> dict:
     """mci_indicator_ess_host: the definition of `indicator_ess` on the host, parameter by parameter, without a GPU.  The
     same bits as the device."""
-    lib = load_iess_library()
+    lib = IESS.load()
     draws = np.asarray(draws)
     tensor_args(draws, layout)
     x = np.ascontiguousarray(np.transpose(draws, [layout.index(a) for a in "pcn"]), dtype=np.float64)
@@ -95,10 +71,8 @@ def indicator_ess_host(draws, lower, upper, layout: str = "pcn") -> dict:
     lo, hi, K = _requests(lower, upper, P)
     ess, trunc, ones = _outputs(P, K)
     for p in range(P):
-        rc = lib.mci_indicator_ess_host(_as_dp(x[p]), x.shape[1], x.shape[2], _as_dp(lo[p]), _as_dp(hi[p]), K, _as_dp(ess[p]),
-                                        _as_ip(trunc[p]), _as_ip(ones[p]))
-        if rc != MCR_OK:
-            raise McrError(rc, (lib.mci_last_error(None) or b"").decode())
+        IESS.host_check(lib.mci_indicator_ess_host(_as_dp(x[p]), x.shape[1], x.shape[2], _as_dp(lo[p]), _as_dp(hi[p]), K,
+                                                   _as_dp(ess[p]), _as_ip(trunc[p]), _as_ip(ones[p])))
     return {"ess": ess, "trunc": trunc, "ones": ones}
 
 
@@ -112,7 +86,7 @@ def ess_quantile(draws, probs=(0.05, 0.5, 0.95), layout: str = "pcn", context=No
     context's summarize reports (numpy's linear interpolation).  Returns thresholds [P][len(probs)], ess, trunc (as
     `indicator_ess`) and tail_min [P] = min(ess at the smallest prob, ess at the largest) -- with the default probs the
     smaller of the 5 % and 95 % indicator ESS, what Stan calls ess_tail, under this library's truncation rule."""
-    ctx = _ctx(context)
+    ctx = context or _ffi.default_context()
     probs = [float(q) for q in probs]
     if not probs or not all(0.0 <= q <= 1.0 for q in probs):
         raise ValueError(f"probs: probabilities inside [0, 1]; got {probs}")
@@ -127,7 +101,7 @@ def ess_local(draws, bins: int = 20, layout: str = "pcn", context=None) -> dict:
     """Local efficiency: the ESS of q_{j/bins} < x <= q_{(j+1)/bins} for j = 0 .. bins - 1 (bins <= 32), the first lower
     edge -inf and the last upper edge +inf.  Returns edges [P][bins - 1] (the inner quantiles), ess and trunc [P][bins]
     and efficiency = ess / (C N): the data of the local-efficiency plot."""
-    ctx = _ctx(context)
+    ctx = context or _ffi.default_context()
     bins = int(bins)
     if not 1 <= bins <= MCI_MAX_REQUESTS:
         raise ValueError(f"bins: 1 to {MCI_MAX_REQUESTS}; got {bins}")
@@ -142,27 +116,19 @@ def ess_local(draws, bins: int = 20, layout: str = "pcn", context=None) -> dict:
 
 def set_workspace_limit(nbytes: int, context=None) -> None:
     """The most device workspace one chunk of parameters of an indicator call may take (mci_set_workspace_limit)."""
-    h = _handle(_ctx(context))
-    h.check(h.lib.mci_set_workspace_limit(h.handle, int(nbytes)))
+    IESS.set_workspace_limit(context or _ffi.default_context(), nbytes)
 
 
 def params_per_chunk(C_: int, N: int, P: int, K: int, dtype=np.float64, context=None) -> int:
     """Parameters per chunk of an indicator call of this shape under the workspace limit (mci_indicator_plan)."""
-    h = _handle(_ctx(context))
-    v = C.c_int64(0)
-    h.check(h.lib.mci_indicator_plan(h.handle, _dtype_code(np.dtype(dtype)), int(C_), int(N), int(P), int(K), C.byref(v)))
-    return int(v.value)
+    return IESS.plan(context or _ffi.default_context(), "mci_indicator_plan", _dtype_code(np.dtype(dtype)), int(C_), int(N), int(P), int(K))
 
 
 def profile(on: bool, context=None) -> None:
     """Time the kernels of every later indicator call with HIP events (mci_profile_enable)."""
-    h = _handle(_ctx(context))
-    h.check(h.lib.mci_profile_enable(h.handle, int(bool(on))))
+    IESS.profile(context or _ffi.default_context(), on)
 
 
 def kernel_ms(context=None) -> dict:
     """The last indicator call's kernel times in milliseconds, {"pack": ..., "lag": ...} (mci_kernel_ms)."""
-    h = _handle(_ctx(context))
-    ms = np.zeros(MCI_KERNELS)
-    h.check(h.lib.mci_kernel_ms(h.handle, _as_dp(ms), MCI_KERNELS))
-    return dict(zip(KERNEL_NAMES, (float(v) for v in ms)))
+    return IESS.kernel_ms(context or _ffi.default_context(), KERNEL_NAMES)

@@ -17,32 +17,18 @@ with the context.  `diagnostics_host` is the definition on the host and needs ne
 """
 from __future__ import annotations
 
-import ctypes as C
-import weakref
 from pathlib import Path
 from typing import Iterable
 
 import numpy as np
 
 from . import _ffi
-from ._abi import MCR_OK, McrError, _as_dp, _as_ip, _dtype_code, tensor_args
-from ._device import DeviceTensor
-from ._sabi import DOUBLE_OUTPUTS, INT_OUTPUTS, KERNEL_NAMES, MCS_KERNELS, MCS_WANT_BASIC, StdHandle, load_std_library
+from ._abi import _as_dp, _as_ip, _dtype_code
+from ._companion import tensor_entry
+from ._sabi import DOUBLE_OUTPUTS, INT_OUTPUTS, KERNEL_NAMES, MCS_WANT_BASIC, STD
 
-_handles: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()      # Context -> StdHandle
+_handle = STD.handle                    # Context -> its StdHandle
 BASIC_OUTPUTS = ("rhat_basic", "ess_mean", "mcse_mean", "lag_mean")
-
-
-def _ctx(context):
-    return context or _ffi.default_context()
-
-
-def _handle(ctx) -> StdHandle:
-    h = _handles.get(ctx)
-    if h is None or h.handle is None:
-        h = _handles[ctx] = StdHandle(ctx.device)
-        weakref.finalize(ctx, h.close)
-    return h
 
 
 def _outputs(P: int) -> dict:
@@ -67,14 +53,8 @@ def diagnostics(draws, layout: str = "pcn", basic: bool = False, context=None) -
     fewer than 8 draws have no ESS (NaN); a constant parameter has NaN everywhere.  Non-finite draws raise.  Calls
     `context.sync()` first.  A parameter's numbers have the same bits alone, in any batch, layout, dtype route and chunking.
     The cost grows with the walk: a chain that has not converged takes O(N^2) products (mcs_diagnostics(_dev))."""
-    ctx = _ctx(context)
-    if isinstance(draws, DeviceTensor):
-        if draws.chain_off is not None:
-            raise ValueError("chains of different lengths are not supported")
-        entry, ptr, targs = "mcs_diagnostics_dev", draws.buf.ptr, draws.targs
-    else:
-        draws = np.asarray(draws)
-        entry, ptr, targs = "mcs_diagnostics", draws.ctypes.data_as(C.c_void_p), tensor_args(draws, layout)
+    ctx = context or _ffi.default_context()
+    entry, ptr, targs = tensor_entry(draws, layout, "mcs_diagnostics")
     out = _outputs(targs[3])
     ctx.sync()
     h = _handle(ctx)
@@ -85,7 +65,7 @@ def diagnostics(draws, layout: str = "pcn", basic: bool = False, context=None) -
 def diagnostics_host(chains, basic: bool = False) -> dict:
     """mcs_diagnostics_host: the definition on the host, without a GPU, for `chains` [C][N] of one parameter (a dict of
     scalars) or [P][C][N] (a dict of [P] arrays).  Agrees with `diagnostics` to 1e-9 relative, the lags exactly."""
-    lib = load_std_library()
+    lib = STD.load()
     x = np.ascontiguousarray(chains, dtype=np.float64)
     if x.ndim not in (2, 3):
         raise ValueError("chains must be [C][N] or [P][C][N]")
@@ -94,9 +74,7 @@ def diagnostics_host(chains, basic: bool = False) -> dict:
     out = _outputs(x.shape[0])
     for p in range(x.shape[0]):
         one = {k: v[p:p + 1] for k, v in out.items()}
-        rc = lib.mcs_diagnostics_host(_as_dp(x[p]), x.shape[1], x.shape[2], MCS_WANT_BASIC if basic else 0, *_pointers(one))
-        if rc != MCR_OK:
-            raise McrError(rc, (lib.mcs_last_error(None) or b"").decode())
+        STD.host_check(lib.mcs_diagnostics_host(_as_dp(x[p]), x.shape[1], x.shape[2], MCS_WANT_BASIC if basic else 0, *_pointers(one)))
     out = _result(out, basic)
     return {k: v[0].item() for k, v in out.items()} if single else out
 
@@ -117,30 +95,22 @@ def diagnostics_file(path: Path, params: Iterable[str] | None = None, basic: boo
 
 def set_workspace_limit(nbytes: int, context=None) -> None:
     """The most device workspace one chunk of parameters of a diagnostics call may take (mcs_set_workspace_limit)."""
-    h = _handle(_ctx(context))
-    h.check(h.lib.mcs_set_workspace_limit(h.handle, int(nbytes)))
+    STD.set_workspace_limit(context or _ffi.default_context(), nbytes)
 
 
 def params_per_chunk(C_: int, N: int, P: int, dtype=np.float64, basic: bool = False, strides=None, context=None) -> int:
     """Parameters per chunk of a diagnostics call of this shape under the workspace limit (mcs_plan); `strides` =
     (stride_c, stride_n, stride_p) in elements, default contiguous [P][C][N]."""
-    h = _handle(_ctx(context))
     sc, sn, sp = strides or (N, 1, C_ * N)
-    v = C.c_int64(0)
-    h.check(h.lib.mcs_plan(h.handle, _dtype_code(np.dtype(dtype)), int(C_), int(N), int(P), int(sc), int(sn), int(sp),
-                           MCS_WANT_BASIC if basic else 0, C.byref(v)))
-    return int(v.value)
+    return STD.plan(context or _ffi.default_context(), "mcs_plan", _dtype_code(np.dtype(dtype)), int(C_), int(N), int(P), int(sc), int(sn),
+                    int(sp), MCS_WANT_BASIC if basic else 0)
 
 
 def profile(on: bool, context=None) -> None:
     """Time the phases of every later diagnostics call with HIP events (mcs_profile_enable)."""
-    h = _handle(_ctx(context))
-    h.check(h.lib.mcs_profile_enable(h.handle, int(bool(on))))
+    STD.profile(context or _ffi.default_context(), on)
 
 
 def kernel_ms(context=None) -> dict:
     """The last diagnostics call's times in milliseconds, {"pipe": ..., "series": ..., "walk": ...} (mcs_kernel_ms)."""
-    h = _handle(_ctx(context))
-    ms = np.zeros(MCS_KERNELS)
-    h.check(h.lib.mcs_kernel_ms(h.handle, _as_dp(ms), MCS_KERNELS))
-    return dict(zip(KERNEL_NAMES, (float(v) for v in ms)))
+    return STD.kernel_ms(context or _ffi.default_context(), KERNEL_NAMES)
