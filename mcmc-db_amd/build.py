@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Builds mcmc-db_amd/lib/libmcmcref_hip.so and its companions libmcmcref_iess.so (include/mcmcref_iess.h),
-libmcmcref_bm.so (include/mcmcref_bm.h) and libmcmcref_std.so (include/mcmcref_std.h) -- each with its own units and its
-own version script, none linked against another -- for gfx950 with hipcc (cross-compiles without a GPU).
-libmcmcref_std.so reuses the sort stage and the summary pipeline as code: the objects of the main units are linked into
-it beside its own unit, and its version script keeps every name but mcs_* local.
+libmcmcref_bm.so (include/mcmcref_bm.h), libmcmcref_std.so (include/mcmcref_std.h) and libmcmcref_recdf.so
+(include/mcmcref_recdf.h) -- each with its own units and its own version script, none linked against another -- for
+gfx950 with hipcc (cross-compiles without a GPU).  libmcmcref_std.so and libmcmcref_recdf.so reuse the sort stage and the
+summary pipeline as code: the objects of the main units are linked into each beside its own unit, and its version
+script keeps every name but mcs_* (mce_*) local.
 
 One object per translation unit of csrc/ (lib/obj/), each with the dependency file the compiler writes for it; stale
 units compile concurrently and the objects are linked into the library.  No kernel is called across units, so the link
@@ -22,11 +23,13 @@ UNITS = ("mcr_api", "mcr_stats", "mcr_files", "mcr_comm")
 IESS_UNITS = ("mci_api",)
 BM_UNITS = ("mcb_api",)
 STD_UNITS = ("mcs_api",)
+RECDF_UNITS = ("mce_api",)
 OBJ = HERE / "lib" / "obj"
 OUT = HERE / "lib" / "libmcmcref_hip.so"
 IESS_OUT = HERE / "lib" / "libmcmcref_iess.so"
 BM_OUT = HERE / "lib" / "libmcmcref_bm.so"
 STD_OUT = HERE / "lib" / "libmcmcref_std.so"
+RECDF_OUT = HERE / "lib" / "libmcmcref_recdf.so"
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fvisibility=hidden",
          "-Wall", "-Wno-unused-value", "-Wno-pass-failed"]
 IESS_FLAGS = FLAGS + ["-ffp-contract=off", f"-I{HERE.parent / 'include'}"]    # host and device must round alike
@@ -60,10 +63,10 @@ def run(cmd: list[str], verbose: bool) -> None:
     subprocess.run(cmd, check=True)
 
 
-# (output, units, version script): libmcmcref_std.so links the main units' objects beside its own
+# (output, units, version script): libmcmcref_std.so and libmcmcref_recdf.so link the main units' objects beside their own
 LIBRARIES = ((OUT, UNITS, "mcr_exports.map"), (IESS_OUT, IESS_UNITS, "mci_exports.map"), (BM_OUT, BM_UNITS, "mcb_exports.map"),
-             (STD_OUT, UNITS + STD_UNITS, "mcs_exports.map"))
-UNIT_FLAGS = {**{u: FLAGS for u in UNITS}, **{u: IESS_FLAGS for u in IESS_UNITS + BM_UNITS + STD_UNITS}}
+             (STD_OUT, UNITS + STD_UNITS, "mcs_exports.map"), (RECDF_OUT, UNITS + RECDF_UNITS, "mce_exports.map"))
+UNIT_FLAGS = {**{u: FLAGS for u in UNITS}, **{u: IESS_FLAGS for u in IESS_UNITS + BM_UNITS + STD_UNITS + RECDF_UNITS}}
 
 
 def link(out: Path, units: tuple, version_script: str, relinked: bool, verbose: bool) -> None:
@@ -74,7 +77,7 @@ def link(out: Path, units: tuple, version_script: str, relinked: bool, verbose: 
 
 
 def build(force: bool = False, verbose: bool = False) -> Path:
-    """All four libraries; returns the path of libmcmcref_hip.so."""
+    """All five libraries; returns the path of libmcmcref_hip.so."""
     OBJ.mkdir(parents=True, exist_ok=True)
     cc = [hipcc()] + (["-Rpass-analysis=kernel-resource-usage"] if verbose else [])
     todo = [u for u in UNIT_FLAGS if force or stale(u)]

@@ -1,4 +1,4 @@
-// mcc_handle.hpp -- what the companion libraries (libmcmcref_iess.so, libmcmcref_bm.so, libmcmcref_std.so) share around
+// mcc_handle.hpp -- what the companion libraries (libmcmcref_iess.so, libmcmcref_bm.so, libmcmcref_std.so, libmcmcref_recdf.so) share around
 // their kernels: the error text, the HIP-call macro, the kernel timer, the limit / profile / kernel_ms entries, and for the
 // libraries that stand alone (mci_api.hip, mcb_api.hip) the handle with its stream and two grow-only device allocations.
 // Header-only, and nothing of libmcmcref_hip.so's but the return codes and the context-free mcr_carve.hpp.
@@ -38,7 +38,7 @@ inline int fail(char* err, int code, const char* fmt, ...)
 // The kernels of one call between events on its stream: begin, a mark behind each kernel (or phase), and after the
 // stream was synchronised collect adds every interval to its kernel's time.  Off (the default): nothing is recorded.
 template <int kKernels> struct Timer {
-    static constexpr int kMarks = 3;
+    static constexpr int kMarks = kKernels > 3 ? kKernels : 3;
     bool on = false;
     hipEvent_t ev[kMarks + 1] = {};
     int kernel[kMarks] = {}, n = 0;

@@ -17,6 +17,8 @@ parameter and, with `--sliced K`, along K random directions of the joint distrib
 `ess-quantile FILE` prints the effective draws behind every parameter's quantile estimates (and its local efficiency).
 `std-diagnostics FILE` prints R-hat and ESS in the Stan convention (split chains, Blom scores, Geyer's rule): the numbers
 of stansummary, posterior and ArviZ, where `diagnostics` and `cmdstan-summary` print the reference's.
+`rank-ecdf FILE` prints the per-chain rank-ECDF uniformity test with simultaneous bands: which chain disagrees with the
+pooled draws, at which quantile, and whether by more than chance.
 `multi-ess FILE` prints the multivariate effective sample size of a table from its batch-means long-run covariance, and
 `mean-test REF_FILE ACT_FILE` the calibrated joint test of equal means of two tables; exits 1 when `--p-min` is missed.
 `hdi FILE` prints the highest-density interval(s) of every parameter: the shortest interval holding a share of the draws.
@@ -293,6 +295,44 @@ def std_diagnostics_cmd(file: Path, params: str | None, basic: bool, as_json: bo
     from . import standard
     try:
         stats = standard.diagnostics_file(file, params=params.split(",") if params else None, basic=basic)
+    except (ValueError, KeyError, IndexError) as exc:
+        raise click.ClickException(str(exc)) from exc
+    _echo_stats(stats, "json" if as_json else "table")
+
+
+def _thin_option(_ctx, _param, value: str):
+    if value == "ess":
+        return value
+    try:
+        thin = int(value)
+    except ValueError:
+        thin = 0
+    if thin < 1:
+        raise click.BadParameter("an integer >= 1 or \"ess\"")
+    return thin
+
+
+@main.command("rank-ecdf")
+@click.argument("file", type=click.Path(path_type=Path, exists=True, dir_okay=False))
+@click.option("--params", default=None, help="Comma-separated parameter list")
+@click.option("--points", default=None, type=click.IntRange(2, 1024), help="Evaluation points K (default: min(n, 100))")
+@click.option("--thin", default="1", callback=_thin_option, help="Keep every T-th draw, or \"ess\": a stride from the bulk ESS")
+@click.option("--sims", default=4000, type=click.IntRange(1), help="Simulated samples behind the simultaneous level")
+@click.option("--seed", default=0, type=int, help="Seed of the simulated samples")
+@click.option("--alpha", default=0.05, type=click.FloatRange(0.0, 1.0), help="Level of the test")
+@click.option("--host", is_flag=True, help="By the definition on the host, without a GPU")
+@click.option("--json", "as_json", is_flag=True, help="Print JSON instead of a table")
+def rank_ecdf_cmd(file: Path, params: str | None, points: int | None, thin, sims: int, seed: int, alpha: float, host: bool,
+                  as_json: bool) -> None:
+    """Which chain disagrees, and where (no counterpart in the reference): the per-chain rank-ECDF uniformity test with
+    simultaneous bands of Saeilynoja, Buerkner and Vehtari.  One row per parameter: the p-value, reject (1 when p <=
+    alpha), the offending chain, the point as a pooled quantile and the largest difference between that chain's ECDF and
+    the pooled one.  The draws must be exchangeable: thin autocorrelated chains.  Chains of equal length.  Exits
+    non-zero only on errors."""
+    from . import rankecdf
+    try:
+        stats = rankecdf.rank_ecdf_file(file, params=params.split(",") if params else None, points=points, thin=thin, sims=sims,
+                                        seed=seed, alpha=alpha, host=host)
     except (ValueError, KeyError, IndexError) as exc:
         raise click.ClickException(str(exc)) from exc
     _echo_stats(stats, "json" if as_json else "table")
